@@ -2,6 +2,14 @@
 """bench.py -- ICP iterations/s of the MI355X-native registration path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c3|c5] [--nn auto|grid|brute]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps), times the K steps once and prints the line: `value`, `ms_per_step` and the
+contract's keys.  `--full` adds everything else described below -- the HIP-event kernel timing and `roofline`, the
+CPU baseline, the extra workloads, precisions and sizes -- and times the K-step block `--blocks` times (default 7,
+`value` = the median).  `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy
+(float64; c4: the transformation, fitness, inlier_rmse, num_correspondences and the correspondence of every source
+point; c3 / c5: the same fields per problem / per work item); the inputs are seeded, so two builds can be compared.
 
 `--gpus N` with N > 1 starts its own ranks (re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`);
@@ -17,7 +25,7 @@ Workloads (BASELINE.json configs):
       N > 1: the SOURCE is sharded (each rank holds the full target), every rank reduces its shard
       and ONE all-reduce of the 38 f64 accumulators per iteration sums them; total work is fixed:
       "scaling": "strong".  A weak-scaling line (source N x 262,144 -> the same 4,194,304-point target) is
-      measured after the timed region and reported under "weak_scaling".
+      measured after the timed region (--full) and reported under "weak_scaling".
   c3: all objects of one scene in flight on ONE GPU: 12 objects x 24 yaw starts = 288 small ICPs
       (source 4k..40k points, target half of it, r = 0.02, 30 iterations).  One STEP = one
       visma_icp_run_batch over the set.  N > 1: problems dealt round-robin by size, no collective.
@@ -28,13 +36,13 @@ Workloads (BASELINE.json configs):
 NN search: `auto` (default) = the radius-cell grid, exact mode (fp32 ranking of the candidates,
 the ones inside the rounding band re-ranked in f64: the reference's correspondences);
 `brute` = the LDS-tiled brute-force kernel north_star names (fp32-VALU-bound).  A few brute-force
-steps are always run after the timed region and reported under `brute_force`.
+steps are run after the timed region (--full) and reported under `brute_force`.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with the extra objects
+Prints ONE JSON line on rank 0, with (--full) the extra objects
 `roofline` (dominant kernel = NN correspondence) and `cpu_baseline` (the reference itself,
 oracle/_ref, timed on this host).  c4: `value` = K iterations of a FRESH registration from T = I (the
 reference's loop, Registration.cpp:167-185: first pass cold, the rest warm-started while the pose moves), timed
-`--blocks` times (default 7), each between a barrier + synchronize pair, winners forgotten before each: the MEDIAN,
+`--blocks` times (7 with --full, else 1), each between a barrier + synchronize pair, winners forgotten before each: the MEDIAN,
 min / max in `blocks`; `value_converged` / `converged` = the registration carried on past its convergence (what
 rounds 1-4 reported as `value`: no caller gets there); `end_to_end` (host arrays in ->
 transformation out: upload, grid build, 31 passes; the PCIe-inclusive rate -- never `value`),
@@ -94,13 +102,47 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=20)
     ap.add_argument("--cpu-repeats", type=int, default=3)
-    ap.add_argument("--blocks", type=int, default=7, help="how many times the K-step block is timed (value = median)")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="how many times the K-step block is timed (value = median); default 1, 7 with --full")
     ap.add_argument("--extras-file", default=os.path.join(ROOT, "bench_extras.json"),
                     help="side file for the full result: every extra workload and note (the line on stdout carries the "
                          "contract's keys only and names this file)")
     ap.add_argument("--no-extras", action="store_true",
                     help="c4: skip from_initial_pose / end_to_end / roofline_saturated / scaling_workloads")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the kernel timing and roofline, the CPU baseline, the extra "
+                         "workloads, precisions and sizes (the --no-* options above switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float64)")
+    args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 7 if args.full else 1
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps once, print the line -- nothing else
+        args.no_extras = args.no_cpu_baseline = args.no_weak = True
+        args.brute_steps = args.f32_steps = 0
+    return args
+
+
+DUMP_POINTS = 1 << 20           # --dump-outputs: per-source-point arrays of at most this many points (8 MB each)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one float64 .npy per output of the timed path's last step (rank 0 only)."""
+    if not directory:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def result_arrays(results):
+    """The RegistrationResult fields of a list of results, one array per field."""
+    return {"transformation": np.stack([r.transformation_ for r in results]),
+            "fitness": [r.fitness_ for r in results],
+            "inlier_rmse": [r.inlier_rmse_ for r in results],
+            "num_correspondences": [r.num_correspondences for r in results],
+            "iterations": [r.iterations for r in results]}
 
 
 # ------------------------------------------------------------------------------------------
@@ -582,17 +624,24 @@ def timed_block(R, ctx, T, radius, steps):
     return T, last, R.reduce_max(time.perf_counter() - t0)
 
 
-def timed_registrations(R, ctx, radius, warmup, steps, nn_mode, prof_every, blocks=5):
+def timed_registrations(R, ctx, radius, warmup, steps, nn_mode, prof_every, blocks=5, kernel_timing=True, prime=False):
     """SURVEY 8d's registration, `blocks` times: W untimed iterations (grid build, buffers, code objects), then every
     block a FRESH registration -- nothing remembered from earlier passes -- of K timed iterations from T = I: the first
     pass cold, the rest warm-started while the pose moves (Registration.cpp:167-185 under criteria (0, 0, K)).  Each
-    block between two barrier + synchronize pairs.  Returns the final transform of the last block and every elapsed time."""
+    block between two barrier + synchronize pairs.  Returns the final transform of the last block and every elapsed time.
+    kernel_timing=False: no extra passes afterwards when the timed ones carried no HIP-event timing.
+    prime=True (a plain run): one short untimed fresh registration after the warm-up, so that the timed block does not
+    pay what only the first registration of a context pays (the persistent launch's first start); --full's median of
+    seven blocks leaves that block out instead."""
     from visma_amd import _lib
     ctx.set_nn_mode({"auto": _lib.NN_AUTO, "grid": _lib.NN_GRID, "brute": _lib.NN_BRUTE}[nn_mode])
     ctx.set_profiling(prof_every)
     ctx.get_timing(reset=True)
     if warmup > 0:
         ctx.iterate(np.eye(4), radius, warmup)      # also builds the grid (one-off)
+    if prime:
+        ctx.forget_winners()
+        ctx.iterate(np.eye(4), radius, min(steps, 4))
     setup = ctx.get_timing(reset=True)
     elapsed, last, T = [], None, np.eye(4)
     for _ in range(max(blocks, 1)):
@@ -601,7 +650,7 @@ def timed_registrations(R, ctx, radius, warmup, steps, nn_mode, prof_every, bloc
         T, last, el = timed_block(R, ctx, np.eye(4), radius, steps)
         elapsed.append(el)
     tm = ctx.get_timing(reset=True)
-    if tm["nn_launches"] == 0:
+    if tm["nn_launches"] == 0 and kernel_timing:
         ctx.set_profiling(1)
         ctx.forget_winners()
         ctx.iterate(np.eye(4), radius, 3)
@@ -829,12 +878,32 @@ def run_c4(R, args):
     # the grid (two event records cost ~7 us of a ~50 us iteration)
     # (with fewer than 8 steps nothing is timed inside the timed region: timed_iterations measures the
     #  kernel on three extra passes afterwards)
-    prof_every = 1 if args.nn == "brute" else (4 if args.steps >= 8 else 0)
+    # (a plain run times no kernel: only --full reports the roofline)
+    prof_every = 0 if not args.full else 1 if args.nn == "brute" else (4 if args.steps >= 8 else 0)
     blocks = 1 if args.nn == "brute" else max(args.blocks, 1)
     # `value` (since round 5): SURVEY 8d's registration as the reference runs it -- K iterations from T = I, the cold
     # first pass included (Registration.cpp:167-185) --, the median of `blocks` fresh registrations
-    T, last, elapsed_all, tm, setup = timed_registrations(R, ctx, radius, args.warmup, args.steps, args.nn, prof_every, blocks)
+    T, last, elapsed_all, tm, setup = timed_registrations(R, ctx, radius, args.warmup, args.steps, args.nn, prof_every, blocks,
+                                                          kernel_timing=args.full, prime=not args.full)
     elapsed = float(np.median(elapsed_all))
+    # (the launch counters of `tm` are filled by the HIP-event timing only)
+    persistent = tm.get("persist_passes", 0) > 0 or (not args.full and ctx.persistent_info()["last_loop_persistent"] > 0)
+    if R.rank == 0 and args.dump_outputs:
+        # what ctx.iterate returned in the last timed step, and the correspondences of that pass per source point
+        # (one rank: every source point; with several, rank 0's slice)
+        si, ti, d2 = ctx.get_correspondences()
+        idx = np.full(ns_local, -1.0)
+        idx[si] = ti
+        dist2 = np.full(ns_local, -1.0)
+        dist2[si] = d2
+        arrays = {"transformation": T, "fitness": [last.fitness_], "inlier_rmse": [last.inlier_rmse_],
+                  "num_correspondences": [last.num_correspondences]}
+        if ns_local > DUMP_POINTS:
+            # (a fixed, seeded sample of the source points keeps the dump under 64 MB)
+            pick = np.sort(np.random.default_rng(0).choice(ns_local, DUMP_POINTS, replace=False))
+            idx, dist2, arrays["correspondence_sample"] = idx[pick], dist2[pick], pick
+        arrays.update(correspondence_index=idx, correspondence_distance2=dist2)
+        dump_outputs(args.dump_outputs, arrays)
     mode = "grid" if ctx.nn_mode_used() == _lib.NN_GRID else "brute"
     search = ctx.search_mode_used()
     kernel_kind = ctx.search_kernel_used()
@@ -847,7 +916,7 @@ def run_c4(R, args):
         R.dist.all_reduce(lo, op=R.dist.ReduceOp.MIN)
         ranks_agree = bool(R.torch.equal(hi, lo))
     nl = max(tm["nn_launches"], 1)
-    nn_ms = R.reduce_max(tm["nn_ms"] / nl)
+    nn_ms = R.reduce_max(tm["nn_ms"] / nl) if args.full else 0.0
     cand = tm["grid_candidates"] / nl
 
     # the regime rounds 1-4 reported as `value`: the registration carried on past its convergence (2K more iterations
@@ -943,7 +1012,7 @@ def run_c4(R, args):
     c5 = None
     if not args.no_extras and args.nn != "brute":
         sub = argparse.Namespace(**vars(args))
-        sub.steps, sub.warmup, sub.no_cpu_baseline = 2, 1, True
+        sub.steps, sub.warmup, sub.no_cpu_baseline, sub.dump_outputs = 2, 1, True, None
         c5r = run_c5(R, sub, tag="sw")
         if c5r is not None:
             c5 = {"icp_iterations_per_sec": c5r["value"], "registrations_per_sec": c5r["registrations_per_sec"],
@@ -953,7 +1022,8 @@ def run_c4(R, args):
     if R.rank == 0:
         tile = _lib.tile_config()
         exact = search != "f32"
-        if mode == "grid":
+        roofline = None
+        if args.full and mode == "grid":
             # (traffic: PMC passes of tools/run_c4_iterations.py in ITS regime -- fresh registrations from the identity;
             #  the converged regime's counters belong to `converged.roofline`)
             roofline = grid_roofline(ns_local, nt_local, nn_ms, cand, tm["grid_candidates_27cell"] / nl,
@@ -961,18 +1031,18 @@ def run_c4(R, args):
                                      exact, kernel_kind if kernel_kind in ("warm", "serial") else "serial",
                                      tm["grid_certified"] / nl)
             roofline = persistent_launches(roofline, tm, ns_local, nt_local, "grid_persist_initial")
-        else:
+        elif args.full:
             roofline = brute_roofline(ns_local, nt_local, nn_ms, tile, load_traffic("brute", ns_local, nt_local))
-        roofline["launches_timed"] = tm["nn_launches"] if "launch" not in roofline else roofline["launch"]["launches_timed"]
-        roofline["timed_every_nth_pass"] = prof_every if "launch" not in roofline else 1
-        roofline["separate_fold_launch_avg_ms"] = tm["reduce_ms"] / max(tm["reduce_launches"], 1)
-        roofline["regime"] = "the timed region: %d fresh registrations of %d iterations from T = I (cold pass + warm passes)" % (
-            len(elapsed_all), args.steps)
+        if roofline is not None:
+            roofline["launches_timed"] = tm["nn_launches"] if "launch" not in roofline else roofline["launch"]["launches_timed"]
+            roofline["timed_every_nth_pass"] = prof_every if "launch" not in roofline else 1
+            roofline["separate_fold_launch_avg_ms"] = tm["reduce_ms"] / max(tm["reduce_launches"], 1)
+            roofline["regime"] = "the timed region: %d fresh registrations of %d iterations from T = I (cold pass + warm passes)" % (
+                len(elapsed_all), args.steps)
         par = ("source-sharded x%d, 1 all-reduce(38 f64)/iter via %s" % (R.world, comm_kind)
                if args.shard == "source" else
                "target-sharded x%d, ncclAllReduce(min, %d u64) + ncclAllReduce(38 f64)/iter via %s" % (R.world, ns, comm_kind))
-        launch_mode = ("ONE persistent launch per host loop (passes inside it)" if tm.get("persist_passes", 0) > 0
-                       else "one launch per pass")
+        launch_mode = ("ONE persistent launch per host loop (passes inside it)" if persistent else "one launch per pass")
         if R.dist is not None:
             par += "; launch mode: %s%s; ranks meet over torch.distributed/%s" % (
                 launch_mode, " (VISMA_ICP_PERSIST_RANKS=1)" if os.environ.get("VISMA_ICP_PERSIST_RANKS") == "1" else
@@ -997,14 +1067,17 @@ def run_c4(R, args):
                                    "Registration.cpp:167-185), winners forgotten before each",
                        "iterations_per_sec": [args.steps / e for e in elapsed_all],
                        "min": args.steps / max(elapsed_all), "max": args.steps / min(elapsed_all)},
-            "candidates_evaluated_per_sec": cand * R.world * args.steps / elapsed if mode == "grid" else float(ns) * nt * args.steps / elapsed,
             "equivalent_bruteforce_mpairs_per_sec": float(ns) * nt * args.steps / elapsed / 1e6,
             "matched_corr_per_sec": last.num_correspondences * args.steps / elapsed,
             "fitness": last.fitness_, "inlier_rmse": last.inlier_rmse_, "ranks_hold_identical_transforms": ranks_agree,
             "err_vs_T_gt": synth.rel_frobenius(T, T_gt),
-            "setup_ms": {"grid_build_kernels": setup["aux_ms"]},
-            "roofline": roofline,
         }
+        if args.full:
+            # (from the HIP-event timing and the kernel's candidate counters: only --full switches them on)
+            out["candidates_evaluated_per_sec"] = (cand * R.world * args.steps / elapsed if mode == "grid" else
+                                                   float(ns) * nt * args.steps / elapsed)
+            out["setup_ms"] = {"grid_build_kernels": setup["aux_ms"]}
+            out["roofline"] = roofline
         # one phrase per key for the line on stdout (the long forms above stay in the side file)
         out["config_short"] = {
             "workload": "C4 S-surf %d->%d, %d ICP iterations of a fresh registration from T=I (cold pass + warm passes), "
@@ -1201,27 +1274,31 @@ def run_c3(R, args):
         its += sum(r.iterations for r in res)
     R.barrier_sync()
     elapsed = R.reduce_max(time.perf_counter() - t0)
-    # the search launches of the WHOLE batch on one context, alone on the GPU, timed by HIP events (after the timed
-    # region)
-    ctx.set_profiling(1)
-    ctx.get_timing(reset=True)
-    ctx.run_batch(batch, max_iter=iters)
-    tm = ctx.get_timing(reset=True)
-    ctx.set_profiling(0)
-    my_queries = sum(len(p[0]) for p in my)
+    if R.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays(res))          # the last step: this rank's problems, in order
     total_its = R.reduce_sum(float(its))
-    nl = max(tm["nn_launches"], 1)
-    nn_ms = R.reduce_max(tm["nn_ms"] / nl)
+    roofline = None
+    if args.full:
+        # the search launches of the WHOLE batch on one context, alone on the GPU, timed by HIP events (after the timed
+        # region)
+        ctx.set_profiling(1)
+        ctx.get_timing(reset=True)
+        ctx.run_batch(batch, max_iter=iters)
+        tm = ctx.get_timing(reset=True)
+        ctx.set_profiling(0)
+        nl = max(tm["nn_launches"], 1)
+        nn_ms = R.reduce_max(tm["nn_ms"] / nl)
+        if R.rank == 0:
+            queries = sum(len(p[0]) for p in my)
+            nt_total = sum(len(objs[i][1]) for i in mine)
+            roofline = grid_roofline(queries, nt_total, nn_ms, tm["grid_candidates"] / nl, tm["grid_candidates_27cell"] / nl,
+                                     batch_traffic("c3:wave") if R.world == 1 else None, True,
+                                     "wave" if ctx.search_kernel_used() == "warm" else "serial", 0.0)   # (batches: grid_wave.hip)
+            roofline["traffic_source"] = "profiles/traffic.json c3:wave (PMC passes of `bench.py --workload c3` with one worker " \
+                                         "context, all problems per launch; not this run)"
+            roofline["launches_timed"] = tm["nn_launches"]
     out = None
     if R.rank == 0:
-        queries = my_queries
-        nt_total = sum(len(objs[i][1]) for i in mine)
-        roofline = grid_roofline(queries, nt_total, nn_ms, tm["grid_candidates"] / nl, tm["grid_candidates_27cell"] / nl,
-                                 batch_traffic("c3:wave") if R.world == 1 else None, True,
-                                 "wave" if ctx.search_kernel_used() == "warm" else "serial", 0.0)   # (batches: grid_wave.hip)
-        roofline["traffic_source"] = "profiles/traffic.json c3:wave (PMC passes of `bench.py --workload c3` with one worker context, all " \
-                                     "problems per launch; not this run)"
-        roofline["launches_timed"] = tm["nn_launches"]
         out = {
             "metric": "icp_iterations_per_sec", "value": total_its / elapsed, "unit": "ICP iterations/s",
             "n_gpus": R.world, "steps": args.steps, "warmup": args.warmup,
@@ -1235,8 +1312,9 @@ def run_c3(R, args):
                                       "per GPU (visma_icp_run_batch_multi: each its own stream and host thread, shares side by side), no collective" % (R.world, W)},
             "config_short": {"parallelism": "replicas only: %d rank(s) x %d worker context(s) per GPU, no collective" % (R.world, W)},
             "problems_per_sec": len(probs) * args.steps / elapsed,
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if R.world == 1 and not args.no_cpu_baseline:
             kind, threads, run = cpu_registration()
             t0 = time.perf_counter()
@@ -1346,9 +1424,12 @@ def run_c5(R, args, tag=""):
                 pass
         base = ctypes.addressof(ctypes.c_char.from_buffer(shm.buf))
 
+    last = []
+
     def one_pass(slot):
         res = corpus.run(ctxs, (base + 8 * slot) if shm is not None else None)
         mine = [r for r in res if r[2] >= 0]
+        last[:] = res
         return sum(r[3] for r in mine), len(mine)
 
     for w in range(nwarm):
@@ -1362,6 +1443,14 @@ def run_c5(R, args, tag=""):
         done += b
     R.barrier_sync()
     elapsed = R.reduce_max(time.perf_counter() - t0)
+    if R.rank == 0 and args.dump_outputs:
+        # the last pass, every item (with several ranks: the items this rank did, zeros elsewhere)
+        mine = [r[2] >= 0 for r in last]
+        arrays = result_arrays([r[0] for r in last])
+        arrays["best_level"] = [r[1] for r in last]
+        arrays["iterations_all_starts"] = [r[3] for r in last]
+        arrays["done_here"] = mine
+        dump_outputs(args.dump_outputs, arrays)
     total_its = R.reduce_sum(float(its))
     per_rank_items = done
     total_items = int(round(R.reduce_sum(float(done))))
@@ -1373,7 +1462,7 @@ def run_c5(R, args, tag=""):
             shm.unlink()
     # roofline of the batch kernel: one profiled pass over the first chunks (after the timed region)
     roofline = None
-    if R.rank == 0:
+    if R.rank == 0 and args.full:
         ctx.set_profiling(1)
         b_alg = b_comp = ms = 0.0
         launches = 0
@@ -1421,8 +1510,9 @@ def run_c5(R, args, tag=""):
                                           R.world, C5_CHUNK, " in shared memory" if R.world > 1 else "", nctx)},
             "registrations_per_sec": len(items) * args.steps / elapsed,
             "items_done_by_rank0": per_rank_items, "items_done_by_all_ranks": total_items,
-            "roofline": roofline,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if R.world == 1 and not args.no_cpu_baseline:
             kind, threads, run = cpu_registration()
             from visma_amd import synth

@@ -338,6 +338,62 @@ def gen_pcd(ref):
     print("pcd fixture:", {k: (v.tolist(), out.get(k[:-3] + "_xyz", np.zeros((0, 3))).shape) for k, v in out.items() if k.endswith("_ok")})
 
 
+PCD_DATA_HEAD = 8192          # points of fragment.pcd kept in its fixture (the whole file is 3.6 MB)
+
+
+def gen_pcd_data(ref):
+    """The reference's own real-scan PCD files as fixtures (pcd_data/: the two Feature clouds whole, the first
+    PCD_DATA_HEAD points of fragment.pcd with its header's counts changed to match) and what the compiled reference's
+    reader returns for each (pcd_data.npz)."""
+    d = os.path.join(HERE, "pcd_data")
+    os.makedirs(d, exist_ok=True)
+    for name in ("cloud_bin_0.pcd", "cloud_bin_1.pcd"):
+        open(os.path.join(d, name), "wb").write(open(O3D_DATA + "/Feature/" + name, "rb").read())
+    raw = open(O3D_DATA + "/fragment.pcd", "rb").read()
+    end = raw.index(b"DATA binary\n") + len(b"DATA binary\n")
+    head = raw[:end].decode()
+    n = int(head.split("POINTS ")[1].split()[0])
+    stride = (len(raw) - end) // n
+    head = head.replace("WIDTH %d\n" % n, "WIDTH %d\n" % PCD_DATA_HEAD).replace("POINTS %d\n" % n, "POINTS %d\n" % PCD_DATA_HEAD)
+    open(os.path.join(d, "fragment_head.pcd"), "wb").write(head.encode() + raw[end:end + PCD_DATA_HEAD * stride])
+    out = {}
+    for name in sorted(os.listdir(d)):
+        c = ref.read_pcd_cloud(os.path.join(d, name))
+        assert c is not None, name
+        for k in ("xyz", "normals", "colors"):
+            out[name.replace(".", "_") + "_" + k] = c[k]
+    np.savez_compressed(os.path.join(HERE, "pcd_data.npz"), **out)
+
+
+def gen_live_checks(ref):
+    """What the compiled reference returns for the seeded inputs of the two tests that used to call it directly
+    (live_checks.npz): VoxelDownSample of an anisotropic cloud with NaN normals at three voxel sizes (in the reference's
+    own output order), Eigen's 3 x 3 JacobiSVD of 400 matrices and FindPlaneNormal of a flat cloud."""
+    out = {}
+    rng = np.random.default_rng(4)                       # (tests/test_voxel.py: test_oracle_matches_live_reference)
+    pts = rng.standard_normal((5000, 3)) * np.array([3.0, 0.5, 1.0])
+    nrm = rng.standard_normal((5000, 3))
+    nrm[::97] = np.nan
+    out["voxel_xyz"], out["voxel_normals"] = pts, nrm
+    for i, v in enumerate((0.07, 0.5, 4.0)):
+        p, n = ref.voxel_down_sample(pts, v, nrm, None)[:2]
+        out["voxel_size_%d" % i], out["voxel_p_%d" % i], out["voxel_n_%d" % i] = np.array([v]), p, n
+    rng = np.random.default_rng(5)                       # (tests/test_annotation.py: test_against_the_library_itself_...)
+    A_all, parts = [], []
+    for k in range(400):
+        A = rng.standard_normal((3, 3)) * 10 ** rng.uniform(-8, 8)
+        if k % 2:
+            A = A @ A.T
+        A_all.append(A)
+        parts.append(ref.jacobi_svd3(A))
+    out["svd_A"] = np.array(A_all)
+    for j in range(len(parts[0])):
+        out["svd_%d" % j] = np.array([x[j] for x in parts])
+    P = rng.standard_normal((5000, 3)) * [2.0, 0.01, 1.0] + [3, -2, 9]
+    out["plane_P"], out["plane_n"] = P, ref.find_plane_normal(P)
+    np.savez_compressed(os.path.join(HERE, "live_checks.npz"), **out)
+
+
 def gen_normals(ref):
     """open3d::EstimateNormals (O3D/Core/Geometry/EstimateNormals.cpp:114-153): outputs of the compiled
     reference for the three searches, on chair CAD samples and on a real scan fragment, with and
@@ -381,6 +437,10 @@ def main():
         return gen_io(ref)
     if len(sys.argv) > 1 and sys.argv[1] == "pcd":
         return gen_pcd(ref)
+    if len(sys.argv) > 1 and sys.argv[1] == "pcd_data":
+        return gen_pcd_data(ref)
+    if len(sys.argv) > 1 and sys.argv[1] == "live_checks":
+        return gen_live_checks(ref)
     if len(sys.argv) > 1 and sys.argv[1] == "normals":
         return gen_normals(ref)
     V, F = load_obj(REF + "/misc/hermanmiller_aeron.obj")
@@ -581,6 +641,8 @@ def main():
     gen_mesh(ref)
     gen_io(ref)
     gen_pcd(ref)
+    gen_pcd_data(ref)
+    gen_live_checks(ref)
     gen_normals(ref)
     print("golden fixtures written to", HERE)
 

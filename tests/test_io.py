@@ -144,21 +144,21 @@ def test_pcd_failures_are_reported(io, name):
         io.read_pcd(os.path.join(D, name))
 
 
-REF_PCDS = ["/root/reference/thirdparty/Open3D/examples/TestData/fragment.pcd",
-            "/root/reference/thirdparty/Open3D/examples/TestData/Feature/cloud_bin_0.pcd",
-            "/root/reference/thirdparty/Open3D/examples/TestData/Feature/cloud_bin_1.pcd"]
+PCD_DATA = ["fragment_head.pcd", "cloud_bin_0.pcd", "cloud_bin_1.pcd"]
 
 
-@pytest.mark.parametrize("path", REF_PCDS)
-def test_pcd_reference_data_files(io, path):
-    """The reference's own real-scan fixtures, where the reference tree is present (this container)."""
-    from oracle.oracle import Ref
-    if not (os.path.exists(path) and Ref.available()):
-        pytest.skip("reference tree / oracle/_ref not present")
-    want = Ref().read_pcd_cloud(path)
-    got = io.read_pcd(path)
+@pytest.mark.parametrize("name", PCD_DATA)
+def test_pcd_reference_data_files(io, name):
+    """The reference's own real-scan data files (golden/pcd_data/: the two Feature clouds, the first 8,192 points of
+    fragment.pcd) against what the compiled reference's reader returned for them (golden/pcd_data.npz, written by
+    gen_golden.py pcd_data)."""
+    gold = np.load(os.path.join(HERE, "golden", "pcd_data.npz"))
+    key = name.replace(".", "_")
+    got = io.read_pcd(os.path.join(HERE, "golden", "pcd_data", name))
     for k in ("xyz", "normals", "colors"):
-        assert np.array_equal(got[k], want[k], equal_nan=True), k
+        want = gold[key + "_" + k]
+        assert len(want) > 0 and got[k].shape == want.shape, (k, got[k].shape, want.shape)
+        assert np.array_equal(got[k], want, equal_nan=True), k
 
 
 # ---------------------------------------------------------------- pose files

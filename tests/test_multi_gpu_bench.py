@@ -29,8 +29,9 @@ def _bench(extra, env_extra, gpus):
     # the full result (every extra workload, the long phrases) goes to the side file the line names; the line on stdout
     # is the contract's summary: one line, under 4 KB
     side = os.path.join(tempfile.mkdtemp(prefix="visma_bench_"), "extras.json")
+    # (--full: the roofline, the weak-scaling line, scaling_workloads and the seven timed blocks these tests read)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "6", "--warmup", "2",
-           "--ns", "65536", "--nt", "262144", "--no-cpu-baseline", "--brute-steps", "0", "--f32-steps", "0",
+           "--ns", "65536", "--nt", "262144", "--full", "--no-cpu-baseline", "--brute-steps", "0", "--f32-steps", "0",
            "--extras-file", side] + extra
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -9,7 +9,7 @@ for what in "$@"; do
         for lib in base product; do
           if [ $lib = base ]; then export VISMA_ICP_LIB=/root/repo/_ab_old/libvisma_icp_base.so; else unset VISMA_ICP_LIB; fi
           steps=5; [ $what = c5 ] && steps=2
-          timeout 600 python bench.py --workload $what --steps $steps --warmup 1 --no-cpu-baseline --extras-file /tmp/x.json 2>> $out/err.log | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$what $lib', d['value'], d.get('registrations_per_sec'), d['roofline']['avg_launch_ms'], d['roofline'].get('certified_fraction'))" | tee -a $out/ab.txt
+          timeout 600 python bench.py --workload $what --steps $steps --warmup 1 --full --no-cpu-baseline --extras-file $out/extras.json 2>> $out/err.log | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$what $lib', d['value'], d.get('registrations_per_sec'), d['roofline']['avg_launch_ms'], d['roofline'].get('certified_fraction'))" | tee -a $out/ab.txt
         done; done ;;
     c4) for i in 1 2 3; do
         VISMA_ICP_LIB=/root/repo/_ab_old/libvisma_icp_base.so timeout 300 python tools/ab_probe.py 4194304 262144 >> $out/ab_c4.jsonl 2>&1
