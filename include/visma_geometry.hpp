@@ -279,11 +279,13 @@ struct AnnotationPose {
 // 2 x |scan| points (:126) and centred (T2); all (model, scan) pairs are then registered TOGETHER by the native work
 // queue (RegisterModelsToScenes: rotation_level yaw starts per pair in flight), and Ttot = (T1 T0)^-1 T3 T2 comes back
 // per object.  `alignment_json` (optional): written as the tool writes it (:156, 170-186).
+// upright = true: the registrations rotate about +Y only -- the frame T0 has turned the floor normal onto.
 inline std::vector<AnnotationPose> AnnotateObjects(const std::vector<AnnotationObject> &objects, const Eigen::Matrix4d &T0,
                                                    double voxel_size, int rotation_level, double distance_threshold,
                                                    const std::string &alignment_json = std::string(),
                                                    SamplingMode mode = SamplingMode::Surface, uint64_t seed = 0,
-                                                   const std::vector<int> &devices = std::vector<int>())
+                                                   const std::vector<int> &devices = std::vector<int>(),
+                                                   bool upright = false)
 {
     const size_t n = objects.size();
     std::vector<AnnotationPose> out(n);
@@ -315,7 +317,8 @@ inline std::vector<AnnotationPose> AnnotateObjects(const std::vector<AnnotationO
         out[k].n_model = (int)model->points_.size();
         pairs[k] = std::make_pair(model, scan);
     }
-    const std::vector<Eigen::Matrix4d> T3 = open3d::cicp::RegisterModelsToScenes(pairs, rotation_level, distance_threshold, devices);
+    const std::vector<Eigen::Matrix4d> T3 = open3d::cicp::RegisterModelsToScenes(pairs, rotation_level, distance_threshold, devices,
+                                                                                 nullptr, upright);
     std::vector<visma_io_pose> poses(n);
     for (size_t k = 0; k < n; k++) {
         out[k].T3 = T3[k];

@@ -234,6 +234,42 @@ VISMA_ICP_API int visma_icp_solve_from_stats(const double stats[VISMA_ICP_NSTATS
                                              int solver, int with_scaling,
                                              double T_update[16]);
 
+/* The two updates constrained to a rotation about the axis `axis` (target
+ * frame; normalised here, a zero, near-zero or non-finite axis returns
+ * VISMA_ICP_ERR_INVALID) plus a 3-D translation.  plane = 0: the exact
+ * least-squares closed form for the fixed correspondences (angle from the
+ * cross-covariance projected on the plane normal to the axis; identity when
+ * K = 0).  plane = 1: one Gauss-Newton step on (angle, translation) -- the
+ * 6-DoF point-to-plane system restricted to 4 unknowns, the same |det| < 1e-6
+ * guard (identity when it rejects), the exact rotation about the axis.  What a
+ * context with visma_icp_set_rotation_axis solves. */
+VISMA_ICP_API int visma_icp_solve_from_stats_axis(const double stats[VISMA_ICP_NSTATS],
+                                                  int plane, const double axis[3],
+                                                  double T_update[16]);
+
+/* ---- rotation constrained to one axis (orientation constrained ICP) ----- */
+
+/* visma_icp_set_rotation_axis(ctx, axis): from now on every solve of this
+ * context rotates about `axis` only (in the target frame -- +Y for a scan whose
+ * floor normal has been turned onto +Y) plus a free 3-D translation, through
+ * every entry point: run, iterate, run_point_to_plane, both yaw sweeps, both
+ * batches, run_batch_multi and run_corpus (whose contexts must all have the
+ * same setting).  NULL clears it (the default: the unconstrained solves).  The
+ * library normalises the axis; a zero, near-zero or non-finite one returns
+ * VISMA_ICP_ERR_INVALID.  While it is set, solver GN_EULER / GN_EXPMAP and
+ * with_scaling = 1 return VISMA_ICP_ERR_INVALID.
+ * Invariant: R_result^T a = R_init^T a -- the tilt of `init` relative to the
+ * axis is kept (start from a pose whose rotation fixes a, and every result
+ * fixes it).
+ * Sharded ranks do NOT take an axis: set_rotation_axis on a context that is
+ * target-sharded or one of several ranks (comm_init, comm_ipc_init,
+ * set_allreduce with nranks > 1), and those calls on a context with an axis
+ * set, return VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_set_rotation_axis(visma_icp_ctx *ctx, const double axis[3]);
+/* The unit axis in use (zeros when none) and *enabled = 0 / 1. */
+VISMA_ICP_API int visma_icp_get_rotation_axis(const visma_icp_ctx *ctx, double axis_out[3],
+                                              int *enabled);
+
 /* ---- the full loop ------------------------------------------------------ */
 
 /* open3d::RegistrationICP (O3D/Core/Registration/Registration.h:102-107,

@@ -59,6 +59,42 @@ public:
     bool with_scaling_ = false;
 };
 
+// Orientation constrained ICP (the VISMA paper's estimator): the rotation turns about `up_` only (+Y: the frame of a
+// scan whose floor normal has been turned onto +Y), the translation is free.  cicp::RegistrationICP runs both fully on
+// the GPU (the thread context's visma_icp_set_rotation_axis, for that call only); ComputeTransformation solves the same
+// 4-DoF update on the host (visma_icp_solve_from_stats_axis), so the generic plugin loop gets it too.
+class TransformationEstimationPointToPointYaw : public TransformationEstimation {
+public:
+    TransformationEstimationPointToPointYaw(const Eigen::Vector3d &up = Eigen::Vector3d::UnitY()) : up_(up) {}
+    ~TransformationEstimationPointToPointYaw() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPoint;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    Eigen::Vector3d up_;
+};
+
+class TransformationEstimationPointToPlaneYaw : public TransformationEstimation {
+public:
+    TransformationEstimationPointToPlaneYaw(const Eigen::Vector3d &up = Eigen::Vector3d::UnitY()) : up_(up) {}
+    ~TransformationEstimationPointToPlaneYaw() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPlane;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    Eigen::Vector3d up_;
+};
+
 namespace detail {
 
 inline void to_rowmajor(const Eigen::Matrix4d &M, double T[16])
@@ -198,6 +234,49 @@ inline Eigen::Matrix4d host_update(const Cloud &s, const Cloud &t, const Corr &c
     return from_rowmajor(T);
 }
 
+// the 4-DoF update (rotation about `up` + translation) of explicit correspondences
+template <typename Cloud, typename Corr>
+inline Eigen::Matrix4d host_update_axis(const Cloud &s, const Cloud &t, const Corr &corres, bool plane,
+                                        const Eigen::Vector3d &up)
+{
+    if (corres.empty() || (plane && !t.HasNormals())) return Eigen::Matrix4d::Identity();
+    double st[VISMA_ICP_NSTATS], T[16];
+    const double a[3] = {up[0], up[1], up[2]};
+    host_stats(s, t, corres, plane, st);
+    if (visma_icp_solve_from_stats_axis(st, plane ? 1 : 0, a, T) != VISMA_ICP_OK)
+        throw std::invalid_argument("rotation axis is zero, near zero or not finite");
+    return from_rowmajor(T);
+}
+
+// the stock point-to-plane ComputeRMSE (TransformationEstimation.cpp:64-75, with its `err = r * r`)
+template <typename Cloud, typename Corr>
+inline double host_rmse_point_to_plane(const Cloud &s, const Cloud &t, const Corr &c)
+{
+    if (c.empty() || !t.HasNormals()) return 0.0;
+    const auto &l = c.back();
+    const double r = (s.points_[l[0]] - t.points_[l[1]]).dot(t.normals_[l[1]]);
+    return std::sqrt(r * r / (double)c.size());
+}
+
+// The thread context's rotation axis for the duration of one call: set on entry (axis != NULL), cleared on every exit
+// (exceptions included) -- the next call on this thread solves unconstrained again.
+class AxisScope {
+public:
+    AxisScope(visma_icp_ctx *ctx, const Eigen::Vector3d *axis) : ctx_(nullptr)
+    {
+        if (!axis) return;
+        const double a[3] = {(*axis)[0], (*axis)[1], (*axis)[2]};
+        check(ctx, visma_icp_set_rotation_axis(ctx, a), "visma_icp_set_rotation_axis");
+        ctx_ = ctx;
+    }
+    ~AxisScope() { if (ctx_) (void)visma_icp_set_rotation_axis(ctx_, nullptr); }
+    AxisScope(const AxisScope &) = delete;
+    AxisScope &operator=(const AxisScope &) = delete;
+
+private:
+    visma_icp_ctx *ctx_;
+};
+
 template <typename Cloud, typename Corr>
 inline double host_rmse_point_to_point(const Cloud &s, const Cloud &t, const Corr &corres)
 {
@@ -269,6 +348,25 @@ inline RegistrationResult RegistrationICP(
                           ? static_cast<const TransformationEstimationPointToPoint *>(&estimation) : nullptr;
     const auto *p2l = dyn == typeid(TransformationEstimationPointToPlane)
                           ? static_cast<const TransformationEstimationPointToPlane *>(&estimation) : nullptr;
+    const auto *yaw_p2p = dyn == typeid(TransformationEstimationPointToPointYaw)
+                              ? static_cast<const TransformationEstimationPointToPointYaw *>(&estimation) : nullptr;
+    const auto *yaw_p2l = dyn == typeid(TransformationEstimationPointToPlaneYaw)
+                              ? static_cast<const TransformationEstimationPointToPlaneYaw *>(&estimation) : nullptr;
+    if (yaw_p2p || yaw_p2l) {
+        detail::AxisScope axis(ctx, yaw_p2p ? &yaw_p2p->up_ : &yaw_p2l->up_);
+        if (yaw_p2p)
+            detail::check(ctx, visma_icp_run(ctx, T, max_correspondence_distance, criteria.max_iteration_,
+                                             criteria.relative_fitness_, criteria.relative_rmse_,
+                                             VISMA_ICP_SOLVER_KABSCH, 0, &r),
+                          "visma_icp_run");
+        else
+            detail::check(ctx, visma_icp_run_point_to_plane(ctx, T, max_correspondence_distance,
+                                                            criteria.max_iteration_, criteria.relative_fitness_,
+                                                            criteria.relative_rmse_, &r),
+                          "visma_icp_run_point_to_plane");
+        detail::fill_result(ctx, r, source.points_.size(), result);
+        return result;
+    }
     if (four || p2p) {
         const bool scaling = four ? four->with_scaling_ : p2p->with_scaling_;
         detail::check(ctx, visma_icp_run(ctx, T, max_correspondence_distance, criteria.max_iteration_,
@@ -317,16 +415,21 @@ inline RegistrationResult RegistrationICP(
 // feh::RegisterModelToScene (src/annotation.cpp:29-64) with its JSON options
 // as plain arguments: rotation_level yaw initialisations about +Y, a full ICP
 // from each, the first result with strictly the most correspondences wins.
+// upright = true: every ICP rotates about +Y only (the orientation constrained
+// ICP of the paper; the yaw starts are upright, so is every result).
 inline Eigen::Matrix4d RegisterModelToScene(const PointCloud &model, const PointCloud &scene,
                                             int rotation_level, double distance_threshold,
                                             bool point_to_plane = false,
-                                            RegistrationResult *best_out = nullptr)
+                                            RegistrationResult *best_out = nullptr,
+                                            bool upright = false)
 {
     RegistrationResult best;
+    const Eigen::Vector3d up = Eigen::Vector3d::UnitY();
     const bool plane_ready = point_to_plane && model.HasNormals() && scene.HasNormals();
     if ((!point_to_plane || plane_ready) && rotation_level > 0 && distance_threshold > 0.0) {
         // all levels in one library call (the sweep is advanced on the GPU), either estimator
         visma_icp_ctx *ctx = detail::upload(model, scene, point_to_plane, distance_threshold);
+        detail::AxisScope axis(ctx, upright ? &up : nullptr);
         visma_icp_result b;
         int level = -1;
         const ICPConvergenceCriteria c;
@@ -358,7 +461,13 @@ inline Eigen::Matrix4d RegisterModelToScene(const PointCloud &model, const Point
         Eigen::Matrix4d init = Eigen::Matrix4d::Identity();
         init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
         RegistrationResult r;
-        if (point_to_plane)
+        if (upright && point_to_plane)
+            r = cicp::RegistrationICP(model, scene, distance_threshold, init,
+                                      TransformationEstimationPointToPlaneYaw(up), ICPConvergenceCriteria());
+        else if (upright)
+            r = cicp::RegistrationICP(model, scene, distance_threshold, init,
+                                      TransformationEstimationPointToPointYaw(up), ICPConvergenceCriteria());
+        else if (point_to_plane)
             r = cicp::RegistrationICP(model, scene, distance_threshold, init,
                                 TransformationEstimationPointToPlane(), ICPConvergenceCriteria());
         else
@@ -377,10 +486,11 @@ inline Eigen::Matrix4d RegisterModelToScene(const PointCloud &model, const Point
 // `devices`: one queue worker (context, own stream) per entry -- the SAME GPU may be listed several times, and should:
 // while one worker packs and uploads its next chunk, the others' searches have the device (three on one GPU: ~1.5x one).
 // Empty = three workers on device 0.  Point-to-point estimator (ICP.point_to_plane = false).
+// upright = true: every ICP rotates about +Y only (as RegisterModelToScene's).
 inline std::vector<Eigen::Matrix4d> RegisterModelsToScenes(
     const std::vector<std::pair<std::shared_ptr<PointCloud>, std::shared_ptr<PointCloud>>> &model_scan_pairs,
     int rotation_level, double distance_threshold, const std::vector<int> &devices = std::vector<int>(),
-    std::vector<RegistrationResult> *best_out = nullptr)
+    std::vector<RegistrationResult> *best_out = nullptr, bool upright = false)
 {
     const size_t n = model_scan_pairs.size();
     std::vector<Eigen::Matrix4d> T(n, Eigen::Matrix4d::Identity());
@@ -402,6 +512,11 @@ inline std::vector<Eigen::Matrix4d> RegisterModelsToScenes(
         visma_icp_ctx *c = nullptr;
         if (visma_icp_create(&c, d) != VISMA_ICP_OK) { destroy_all(); throw std::runtime_error("visma_icp_create failed (no gfx950 GPU?)"); }
         ctxs.push_back(c);
+        const double up[3] = {0.0, 1.0, 0.0};
+        if (upright && visma_icp_set_rotation_axis(c, up) != VISMA_ICP_OK) {
+            destroy_all();
+            throw std::runtime_error("visma_icp_set_rotation_axis failed");
+        }
     }
     const ICPConvergenceCriteria crit;
     visma_icp_corpus_params p;
@@ -616,6 +731,31 @@ inline Eigen::Matrix4d TransformationEstimationPointToPoint4DoF::ComputeTransfor
     const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
 {
     return detail::host_update(source, target, corres, false, with_scaling_);
+}
+
+// ---- the estimators constrained to a rotation about up_ ----------------------
+inline double TransformationEstimationPointToPointYaw::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_rmse_point_to_point(source, target, corres);
+}
+
+inline Eigen::Matrix4d TransformationEstimationPointToPointYaw::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_update_axis(source, target, corres, false, up_);
+}
+
+inline double TransformationEstimationPointToPlaneYaw::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_rmse_point_to_plane(source, target, corres);
+}
+
+inline Eigen::Matrix4d TransformationEstimationPointToPlaneYaw::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_update_axis(source, target, corres, true, up_);
 }
 
 }  // namespace cicp

@@ -195,6 +195,10 @@ def _bind(L):
     if hasattr(L, "visma_icp_set_ring_search"):          # (A/B runs load older builds through VISMA_ICP_LIB)
         L.visma_icp_set_ring_search.argtypes = [C.c_void_p, C.c_int]
         L.visma_icp_get_ring_search.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    if hasattr(L, "visma_icp_set_rotation_axis"):        # (A/B runs load older builds through VISMA_ICP_LIB)
+        L.visma_icp_set_rotation_axis.argtypes = [C.c_void_p, _dp]
+        L.visma_icp_get_rotation_axis.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
+        L.visma_icp_solve_from_stats_axis.argtypes = [_dp, C.c_int, _dp, _dp]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -590,6 +594,22 @@ class Context:
         self._chk(self.L.visma_icp_get_ring_search(self._h, C.byref(r), C.byref(c), C.byref(o)))
         return {"rings": r.value, "cell": c.value, "occupancy": o.value}
 
+    def set_rotation_axis(self, axis=None):
+        """every solve of this context rotates about `axis` only (target frame, e.g. (0, 1, 0) for a gravity-aligned scan)
+        plus a free translation; None clears it (the default: the unconstrained solves).  visma_icp_set_rotation_axis"""
+        if axis is None:
+            self._chk(self.L.visma_icp_set_rotation_axis(self._h, None))
+        else:
+            a = _f64(axis, (3,))
+            self._chk(self.L.visma_icp_set_rotation_axis(self._h, _p(a, _dp)))
+
+    def rotation_axis(self):
+        """the unit axis in use, or None"""
+        a = np.zeros(3)
+        e = C.c_int(0)
+        self._chk(self.L.visma_icp_get_rotation_axis(self._h, _p(a, _dp), C.byref(e)))
+        return a if e.value else None
+
     def test_stall_command(self, nth, ms):
         self._chk(self.L.visma_icp_test_stall_command(self._h, int(nth), float(ms)))
 
@@ -894,4 +914,15 @@ def solve_from_stats(stats, solver=SOLVER_KABSCH, with_scaling=False):
     rc = L.visma_icp_solve_from_stats(_p(st, _dp), int(solver), int(bool(with_scaling)), _p(T, _dp))
     if rc != OK:
         raise IcpError(rc, "solve_from_stats")
+    return T.reshape(4, 4)
+
+
+def solve_from_stats_axis(stats, axis, plane=False):
+    """the update constrained to a rotation about `axis` plus a translation (visma_icp_solve_from_stats_axis): the closed
+    form (plane=False) or one 4-unknown Gauss-Newton point-to-plane step (plane=True)"""
+    L = load()
+    st = _f64(stats, (NSTATS,)); a = _f64(axis, (3,)); T = np.empty(16)
+    rc = L.visma_icp_solve_from_stats_axis(_p(st, _dp), int(bool(plane)), _p(a, _dp), _p(T, _dp))
+    if rc != OK:
+        raise IcpError(rc, "solve_from_stats_axis")
     return T.reshape(4, 4)

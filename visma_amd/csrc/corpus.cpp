@@ -91,6 +91,19 @@ void worker(Shared &s, int w)
     }
 }
 
+// every context must solve the same way: the same rotation axis (visma_icp_set_rotation_axis) or none
+bool same_axis(visma_icp_ctx *const *ctxs, int n_ctx)
+{
+    double a0[3], a[3];
+    int e0 = 0, e = 0;
+    if (visma_icp_get_rotation_axis(ctxs[0], a0, &e0) != VISMA_ICP_OK) return false;
+    for (int w = 1; w < n_ctx; w++) {
+        if (visma_icp_get_rotation_axis(ctxs[w], a, &e) != VISMA_ICP_OK) return false;
+        if (e != e0 || (e && (a[0] != a0[0] || a[1] != a0[1] || a[2] != a0[2]))) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" int visma_icp_run_corpus(visma_icp_ctx *const *ctxs, int n_ctx, const visma_icp_corpus_item *items,
@@ -106,6 +119,7 @@ extern "C" int visma_icp_run_corpus(visma_icp_ctx *const *ctxs, int n_ctx, const
     if (params->level < 1 || params->level > 4096 || params->max_iter < 0 || !(params->max_dist > 0.0)) return bad("bad corpus parameters");
     for (int w = 0; w < n_ctx; w++)
         if (!ctxs[w]) return bad("NULL context");
+    if (!same_axis(ctxs, n_ctx)) return bad("the contexts differ in their rotation axis (visma_icp_set_rotation_axis)");
     for (int64_t i = 0; i < n_items; i++) {
         const visma_icp_corpus_item &it = items[i];
         if (it.n_model < 0 || it.n_scene < 0 || (it.n_model > 0 && !it.model_xyz) || (it.n_scene > 0 && !it.scene_xyz))
@@ -145,6 +159,7 @@ extern "C" int visma_icp_run_batch_multi(visma_icp_ctx *const *ctxs, int n_ctx, 
     if (!ctxs || n_ctx < 1 || n < 0 || (n > 0 && (!probs || !out))) return bad("bad batch arguments");
     for (int w = 0; w < n_ctx; w++)
         if (!ctxs[w]) return bad("NULL context");
+    if (!same_axis(ctxs, n_ctx)) return bad("the contexts differ in their rotation axis (visma_icp_set_rotation_axis)");
     if (n == 0) return VISMA_ICP_OK;
     // groups of problems over the same target
     struct Group { const double *tgt; int64_t nt; double work; std::vector<int> members; };

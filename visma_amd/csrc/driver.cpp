@@ -599,6 +599,42 @@ int visma_icp_solve_from_stats(const double stats[VISMA_ICP_NSTATS], int solver,
     return VISMA_ICP_OK;
 }
 
+int visma_icp_solve_from_stats_axis(const double stats[VISMA_ICP_NSTATS], int plane, const double axis[3],
+                                    double T_update[16])
+{
+    double a[3];
+    if (!stats || !axis || !T_update || !normalise_axis(axis, a)) return VISMA_ICP_ERR_INVALID;
+    bool ok = true;
+    const Mat4 T = plane ? gn_axis_from_stats(stats, a, &ok) : kabsch_axis_from_stats(stats, a);
+    std::memcpy(T_update, T.m, sizeof(T.m));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_set_rotation_axis(visma_icp_ctx *ctx, const double axis[3])
+{
+    CTX_CHECK();
+    if (!axis) {
+        ctx->use_axis = false;
+        ctx->axis[0] = ctx->axis[1] = ctx->axis[2] = 0.0;
+        return VISMA_ICP_OK;
+    }
+    double a[3];
+    if (!normalise_axis(axis, a)) return ctx->fail(VISMA_ICP_ERR_INVALID, "rotation axis is zero, near zero or not finite");
+    if (ctx->sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "sharded ranks take no rotation axis");
+    ctx->use_axis = true;
+    std::memcpy(ctx->axis, a, sizeof(a));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_get_rotation_axis(const visma_icp_ctx *ctx, double axis_out[3], int *enabled)
+{
+    if (!ctx) { g_create_error = "ctx is NULL"; return VISMA_ICP_ERR_INVALID; }
+    if (!axis_out && !enabled) return VISMA_ICP_ERR_INVALID;
+    if (axis_out) std::memcpy(axis_out, ctx->axis, sizeof(ctx->axis));
+    if (enabled) *enabled = ctx->use_axis ? 1 : 0;
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_run(visma_icp_ctx *ctx, const double init[16], double max_dist, int max_iter,
                   double rel_fitness, double rel_rmse, int solver, int with_scaling,
                   visma_icp_result *out)
@@ -606,6 +642,7 @@ int visma_icp_run(visma_icp_ctx *ctx, const double init[16], double max_dist, in
     CTX_CHECK();
     if (!init || !out || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad run arguments");
     if (solver < 0 || solver > VISMA_ICP_SOLVER_GN_EXPMAP) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown solver");
+    if (int rc = ctx->check_axis_solver(solver, with_scaling != 0)) return rc;
     return ctx->run(init, max_dist, max_iter, rel_fitness, rel_rmse, solver, with_scaling != 0, false, out);
 }
 
@@ -615,6 +652,7 @@ int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, i
     CTX_CHECK();
     if (!T_inout || steps < 0 || !(max_dist > 0.0)) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad iterate arguments");
     if (solver < 0 || solver > VISMA_ICP_SOLVER_GN_EXPMAP) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown solver");
+    if (int rc = ctx->check_axis_solver(solver, with_scaling != 0)) return rc;
     if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
     Mat4 Tc = to_centred(Mat4::from(T_inout), ctx->centre);
     double stats[VISMA_ICP_NSTATS], fit = 0, rmse = 0;
@@ -628,6 +666,7 @@ int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, i
         lp.max_iter = steps; lp.solver = solver; lp.passes = steps;
         lp.scaling = with_scaling != 0; lp.plane = false; lp.world = world; lp.check_stop = false;
         lp.ns_total = ctx->ns_total > 0 ? ctx->ns_total : ctx->eng->ns();
+        ctx->fill_axis(lp);
         Engine::LoopResult r;
         int rc = ctx->eng->run_loop(lp, nullptr, 1, &r);
         if (rc) return ctx->eng_fail(rc);
@@ -686,6 +725,7 @@ int visma_icp_run_yaw_sweep(visma_icp_ctx *ctx, int level, double max_dist, int 
 {
     CTX_CHECK();
     if (solver < 0 || solver > VISMA_ICP_SOLVER_GN_EXPMAP) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown solver");
+    if (int rc = ctx->check_axis_solver(solver, false)) return rc;
     return yaw_sweep(ctx, level, max_dist, max_iter, rel_fitness, rel_rmse, solver, false, best, best_level, per_level);
 }
 
@@ -741,6 +781,7 @@ static int yaw_sweep(visma_icp_ctx *ctx, int level, double max_dist, int max_ite
         lp.world = visma_icp_ctx::wants_world_frame(solver, plane);
         lp.check_stop = true;
         lp.ns_total = ctx->ns_total > 0 ? ctx->ns_total : ctx->eng->ns();
+        ctx->fill_axis(lp);
         std::vector<Engine::LoopResult> rs((size_t)level);
         int rc = ctx->eng->run_loop(lp, Tc0.data(), level, rs.data());
         if (rc == VISMA_ICP_OK) {
@@ -918,6 +959,7 @@ static int run_batch_impl(visma_icp_ctx *ctx, const visma_icp_problem *probs, co
             lp.scaling = false; lp.plane = plane;
             lp.world = visma_icp_ctx::wants_world_frame(solver, plane);
             lp.check_stop = true; lp.ns_total = 0;
+            ctx->fill_axis(lp);
             std::vector<Engine::LoopResult> rs((size_t)n);
             int rc = ctx->eng->run_loop_batch(lp, pb, rs.data());
             tr.mark("engine batch loop");
@@ -954,6 +996,7 @@ int visma_icp_run_batch(visma_icp_ctx *ctx, const visma_icp_problem *probs, int 
     CTX_CHECK();
     if (n < 0 || (n > 0 && (!probs || !out)) || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad batch arguments");
     if (solver < 0 || solver > VISMA_ICP_SOLVER_GN_EXPMAP) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown solver");
+    if (int rc = ctx->check_axis_solver(solver, false)) return rc;
     return run_batch_impl(ctx, probs, nullptr, n, max_iter, rel_fitness, rel_rmse, solver, out);
 }
 
@@ -1145,6 +1188,7 @@ int visma_icp_comm_init(visma_icp_ctx *ctx, int rank, int nranks, const void *un
 {
     CTX_CHECK();
     if (!unique_id || nranks < 1 || rank < 0 || rank >= nranks) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad comm arguments");
+    if (ctx->use_axis && nranks > 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "sharded ranks take no rotation axis");
     int rc = ctx->eng->comm_init(rank, nranks, unique_id);
     if (rc) return ctx->eng_fail(rc);
     ctx->rank = rank;
@@ -1165,6 +1209,7 @@ int visma_icp_comm_ipc_init(visma_icp_ctx *ctx, int rank, int nranks, const void
 {
     CTX_CHECK();
     if (!handles || nranks < 1 || rank < 0 || rank >= nranks) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad comm arguments");
+    if (ctx->use_axis && nranks > 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "sharded ranks take no rotation axis");
     int rc = ctx->eng->ipc_init(rank, nranks, handles);
     if (rc) return ctx->eng_fail(rc);
     ctx->rank = rank;
@@ -1176,6 +1221,7 @@ int visma_icp_set_allreduce(visma_icp_ctx *ctx, visma_icp_allreduce_fn fn, void 
 {
     CTX_CHECK();
     if (nranks < 1 || rank < 0 || rank >= nranks) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad rank arguments");
+    if (ctx->use_axis && nranks > 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "sharded ranks take no rotation axis");
     ctx->host_allreduce = fn;
     ctx->host_allreduce_user = user;
     ctx->rank = rank;
@@ -1205,6 +1251,7 @@ int visma_icp_get_search_precision_used(visma_icp_ctx *ctx, int *is_f64)
 int visma_icp_set_target_shard(visma_icp_ctx *ctx, int64_t global_offset, int64_t global_nt, const double centre[3])
 {
     CTX_CHECK();
+    if (ctx->use_axis && global_nt > 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "sharded ranks take no rotation axis");
     int rc = ctx->eng->set_target_shard(global_offset, global_nt);
     if (rc) return ctx->eng_fail(rc);
     ctx->target_sharded = global_nt > 0;

@@ -38,6 +38,22 @@ struct visma_icp_ctx {
     double last_aux_kernel_ms = 0.0;  // kernel time of the last mesh-distance call
     double last_aux_build_ms = 0.0;   // ... and of building its search structure
     int mesh_method = 0;              // 0 choose, 1 brute force, 2 BVH
+    // visma_icp_set_rotation_axis: every solve of this context rotates about `axis` (unit, target frame) only
+    bool use_axis = false;
+    double axis[3] = {0, 0, 0};
+    bool sharded() const { return target_sharded || nranks > 1; }
+    // (an axis admits the closed form and point-to-plane: a Gauss-Newton point-to-point solver or scaling is refused)
+    int check_axis_solver(int solver, bool scaling)
+    {
+        if (use_axis && (solver != VISMA_ICP_SOLVER_KABSCH || scaling))
+            return fail(VISMA_ICP_ERR_INVALID, "a rotation axis is set: only the closed-form solver without scaling applies");
+        return VISMA_ICP_OK;
+    }
+    void fill_axis(Engine::LoopParams &lp) const
+    {
+        lp.use_axis = use_axis;
+        for (int a = 0; a < 3; a++) lp.axis[a] = axis[a];
+    }
 
     int fail(int code, const std::string &msg) { err = msg; return code; }
     int eng_fail(int code) { err = eng->error(); return code; }
@@ -101,6 +117,7 @@ struct visma_icp_ctx {
     Mat4 solve(const double *stats, int solver, bool scaling, bool plane) const
     {
         bool ok;
+        if (use_axis) return plane ? gn_axis_from_stats(stats, axis, &ok) : kabsch_axis_from_stats(stats, axis);
         if (plane) return gn_from_stats(stats, false, &ok);  // TransformationEstimation.cpp:94-102
         switch (solver) {
         case VISMA_ICP_SOLVER_GN_EULER: return gn_from_stats(stats, false, &ok);
@@ -128,6 +145,7 @@ struct visma_icp_ctx {
             lp.max_iter = max_iter; lp.solver = solver; lp.passes = max_iter + 1;
             lp.scaling = scaling; lp.plane = plane; lp.world = world; lp.check_stop = true;
             lp.ns_total = ns_total > 0 ? ns_total : eng->ns();
+            fill_axis(lp);
             Engine::LoopResult r;
             int rc = eng->run_loop(lp, nullptr, 1, &r);
             if (rc) return eng_fail(rc);

@@ -306,6 +306,8 @@ public:
         int max_iter, solver, passes;   // passes = NN passes to enqueue at most
         bool scaling, plane, world, check_stop;
         int64_t ns_total;
+        bool use_axis = false;          // visma_icp_set_rotation_axis: every update rotates about `axis` (unit) only
+        double axis[3] = {0, 0, 0};
     };
     struct LoopResult {
         Mat4 Tc;

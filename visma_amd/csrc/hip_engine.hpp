@@ -742,6 +742,7 @@ private:
     // the closed-form update on one GPU; Gauss-Newton / point-to-plane loops and ranks keep solve_state_kernel
     int solve_in_fold_ = 0;          // VISMA_ICP_SOLVE_IN_FOLD=1: see DESIGN.md 4.4 -- measured SLOWER than the launch of its own (A/B knob)
     // (`lanes`: the launch's lanes code -- the certificate kernels of grid_coop.hip do not carry the epilogue)
+    // (a rotation axis stays on this path: advance_state<true> has the axis closed form too)
     bool solve_in_fold(const LoopParams &lp, int lanes = 0, int nprob = 2) const
     {
         static const bool forced = std::getenv("VISMA_ICP_COOP_KERNEL") != nullptr;

@@ -644,6 +644,8 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
         h.plane = lp.plane ? 1 : 0; h.world_frame = lp.world ? 1 : 0;
         h.check_stop = lp.check_stop ? 1 : 0;
         h.r2f = r2f_;
+        h.use_axis = lp.use_axis ? 1 : 0;
+        for (int a = 0; a < 3; a++) h.axis[a] = lp.axis[a];
     }
     HIP_TRY(hipMemcpyAsync(d_state_, h_state_, sizeof(DevIcpState) * nprob, hipMemcpyHostToDevice, stream_));
     DevIcpState *st = (DevIcpState *)d_state_;
@@ -655,6 +657,7 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
     int done = 0;
     bool sweep_tried = false;
     // (a loop the persistent sweep launch may take over runs its first pass alone: the launch starts behind it)
+    // (a rotation axis keeps the loop a candidate: the launch's closed-form update, advance_state<true>, honours it)
     const bool sweep_candidate = sweep_persist_ && use_grid_ && fused_fold_ && !tshard_ && !comm_ && ipc_n_ <= 1 && !lp.plane &&
                                  lp.solver == VISMA_ICP_SOLVER_KABSCH && lp.passes >= 3;
     while (done < lp.passes) {
@@ -1062,6 +1065,8 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
         h.max_iter = lp.max_iter; h.solver = lp.solver; h.scaling = lp.scaling ? 1 : 0;
         h.plane = lp.plane ? 1 : 0; h.world_frame = lp.world ? 1 : 0; h.check_stop = lp.check_stop ? 1 : 0;
         h.r2f = (float)(pb[b].max_dist * pb[b].max_dist);
+        h.use_axis = lp.use_axis ? 1 : 0;
+        for (int a = 0; a < 3; a++) h.axis[a] = lp.axis[a];
     }
     HIP_TRY(hipMemcpyAsync(d_state_, h_state_, sizeof(DevIcpState) * B, hipMemcpyHostToDevice, stream_));
     // the staging memory of the caller must stay valid until the copies are done

@@ -406,4 +406,139 @@ VISMA_HD Mat4 gn_from_stats(const double *st, bool expmap, bool *ok)
     return T;
 }
 
+// ---- 4 degrees of freedom: rotation about a fixed unit axis `a` (target frame) + a 3-D translation ----------------------
+// (the orientation constrained ICP of the VISMA paper: gravity-aligned scans, yaw only).  DESIGN.md 4.5b.
+
+// R = c I + s [a]x + (1 - c) a a^T: the rotation by the angle with cosine c and sine s about the unit axis a
+VISMA_HD void axis_rotation3(const double a[3], double c, double s, double R[9])
+{
+    const double v = 1.0 - c;
+    R[0] = c + v * a[0] * a[0];        R[1] = v * a[0] * a[1] - s * a[2]; R[2] = v * a[0] * a[2] + s * a[1];
+    R[3] = v * a[1] * a[0] + s * a[2]; R[4] = c + v * a[1] * a[1];        R[5] = v * a[1] * a[2] - s * a[0];
+    R[6] = v * a[2] * a[0] - s * a[1]; R[7] = v * a[2] * a[1] + s * a[0]; R[8] = c + v * a[2] * a[2];
+}
+
+// Point-to-point, closed form: the exact least-squares minimiser over rotations about `a` plus a translation for the
+// fixed correspondence set (the constrained analogue of Umeyama).  With sigma = sum q p^T / K - qm pm^T (as
+// kabsch_from_stats forms it), sum |R p + t - q|^2 is smallest where tr(R^T sigma) = cos A + sin B + a^T sigma a is
+// largest: A = tr sigma - a^T sigma a, B = a . vee(sigma - sigma^T), so (cos, sin) = (A, B) / hypot(A, B).  No atan2 /
+// sin / cos -- only +, -, x, /, sqrt in a fixed order: host and device agree bit for bit (the build has
+// -ffp-contract=off).  A (near-)zero or non-finite hypot (every pair on a line parallel to `a`, K = 0): no rotation.
+VISMA_HD Mat4 kabsch_axis_from_stats(const double *st, const double a[3])
+{
+    const NormalEq e = unpack_stats(st);
+    if (!(e.K > 0.0)) return Mat4::identity();
+    const double P[3] = {e.JTJ[2 * 6 + 4], e.JTJ[0 * 6 + 5], e.JTJ[1 * 6 + 3]};
+    const double Q[3] = {P[0] - e.JTr[3], P[1] - e.JTr[4], P[2] - e.JTr[5]};
+    const double inv = 1.0 / e.K;
+    double pm[3], qm[3], sigma[9];
+    for (int i = 0; i < 3; i++) { pm[i] = P[i] * inv; qm[i] = Q[i] * inv; }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) sigma[i * 3 + j] = e.M[i * 3 + j] * inv - qm[i] * pm[j];
+    double asa = 0.0, m2 = 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) {
+            asa += a[i] * sigma[i * 3 + j] * a[j];
+            const double mk = e.M[i * 3 + j] * inv;
+            m2 += mk * mk;
+        }
+    const double A = (sigma[0] + sigma[4] + sigma[8]) - asa;
+    const double B = a[0] * (sigma[7] - sigma[5]) + a[1] * (sigma[2] - sigma[6]) + a[2] * (sigma[3] - sigma[1]);
+    const double h2 = A * A + B * B;
+    double c = 1.0, s = 0.0;
+    // (h below 1e-12 of the moments sigma is formed from -- the level of their summation's rounding: the data do not
+    //  determine the angle, e.g. every pair on a line parallel to a)
+    if (h2 > 1e-24 * m2 && h2 > 0.0 && h2 < 1e300) {
+        const double h = sqrt(h2);
+        c = A / h;
+        s = B / h;
+    }
+    double R[9];
+    axis_rotation3(a, c, s, R);
+    Mat4 T = Mat4::identity();
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) T(i, j) = R[i * 3 + j];
+        T(i, 3) = qm[i] - (R[i * 3] * pm[0] + R[i * 3 + 1] * pm[1] + R[i * 3 + 2] * pm[2]);
+    }
+    return T;
+}
+
+// Solve A x = b (4x4, partial pivoting, the steps of solve6); returns det(A).
+VISMA_HD double solve4(const double A[16], const double b[4], double x[4])
+{
+    double M[4][5];
+    for (int i = 0; i < 4; i++) {
+        for (int j = 0; j < 4; j++) M[i][j] = A[i * 4 + j];
+        M[i][4] = b[i];
+    }
+    double det = 1.0;
+    for (int c = 0; c < 4; c++) {
+        int piv = c;
+        for (int r = c + 1; r < 4; r++)
+            if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
+        if (M[piv][c] == 0.0) {
+            for (int i = 0; i < 4; i++) x[i] = 0.0;
+            return 0.0;
+        }
+        if (piv != c) {
+            for (int j = 0; j < 5; j++) { const double t = M[c][j]; M[c][j] = M[piv][j]; M[piv][j] = t; }
+            det = -det;
+        }
+        det *= M[c][c];
+        for (int r = c + 1; r < 4; r++) {
+            const double f = M[r][c] / M[c][c];
+            for (int j = c; j < 5; j++) M[r][j] -= f * M[c][j];
+        }
+    }
+    for (int r = 3; r >= 0; r--) {
+        double s = M[r][4];
+        for (int j = r + 1; j < 4; j++) s -= M[r][j] * x[j];
+        x[r] = s / M[r][r];
+    }
+    return det;
+}
+
+// Point-to-plane: one Gauss-Newton step on (angle about a, translation).  The 6-DoF Jacobian row [p x n, n] restricted
+// by P = [[a, 0], [0, I3]] (6x4): H = P^T (J^T J) P, g = P^T (J^T r), H y = -g; the |det| < 1e-6 guard of gn_from_stats
+// (Eigen.cpp:35-56) on the 4x4 system.  The update is the exact rotation by y0 about a (the Euler map of y0 a is a
+// rotation about a only for a coordinate axis) and the translation y1..3.
+VISMA_HD Mat4 gn_axis_from_stats(const double *st, const double a[3], bool *ok)
+{
+    const NormalEq e = unpack_stats(st);
+    *ok = false;
+    if (!(e.K > 0.0)) return Mat4::identity();
+    double H[16], g[4], y[4];
+    double Ja[6];                                       // (J^T J) column block times a: rows 0..5
+    for (int i = 0; i < 6; i++) Ja[i] = e.JTJ[i * 6] * a[0] + e.JTJ[i * 6 + 1] * a[1] + e.JTJ[i * 6 + 2] * a[2];
+    H[0] = a[0] * Ja[0] + a[1] * Ja[1] + a[2] * Ja[2];
+    for (int j = 0; j < 3; j++) {
+        H[1 + j] = Ja[3 + j];
+        H[(1 + j) * 4] = Ja[3 + j];
+        for (int k = 0; k < 3; k++) H[(1 + j) * 4 + 1 + k] = e.JTJ[(3 + j) * 6 + 3 + k];
+    }
+    g[0] = -(a[0] * e.JTr[0] + a[1] * e.JTr[1] + a[2] * e.JTr[2]);
+    for (int j = 0; j < 3; j++) g[1 + j] = -e.JTr[3 + j];
+    const double det = solve4(H, g, y);
+    if (fabs(det) < 1e-6 || isnan(det) || isinf(det)) return Mat4::identity();
+    *ok = true;
+    double R[9];
+    axis_rotation3(a, cos(y[0]), sin(y[0]), R);
+    Mat4 T = Mat4::identity();
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) T(i, j) = R[i * 3 + j];
+        T(i, 3) = y[1 + i];
+    }
+    return T;
+}
+
+// The unit axis of a caller's vector: false for a zero, near-zero or non-finite one
+inline bool normalise_axis(const double in[3], double out[3])
+{
+    const double n2 = in[0] * in[0] + in[1] * in[1] + in[2] * in[2];
+    if (!(n2 > 1e-24) || !(n2 < 1e300)) return false;
+    const double n = sqrt(n2);
+    for (int i = 0; i < 3; i++) out[i] = in[i] / n;
+    return true;
+}
+
 }  // namespace visma

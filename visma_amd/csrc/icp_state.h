@@ -12,7 +12,9 @@
 namespace visma {
 
 // KABSCH_ONLY: the closed-form update alone (the caller has checked !plane && solver == 0): without the 6 x 6
-// Gauss-Newton paths the step needs ~60 registers instead of > 128 (inside a search kernel held to 128 it must not spill)
+// Gauss-Newton paths the step needs ~60 registers instead of > 128 (inside a search kernel held to 128 it must not spill).
+// Both versions honour st->use_axis (rotation about st->axis only): the closed form of a point-to-point loop, the 4 x 4
+// Gauss-Newton step of a point-to-plane one.
 template <bool KABSCH_ONLY = false>
 __device__ __forceinline__ void advance_state(DevIcpState *st)
 {
@@ -41,9 +43,19 @@ __device__ __forceinline__ void advance_state(DevIcpState *st)
     Mat4 upd;
     bool ok = true;
     if constexpr (KABSCH_ONLY) {
-        upd = kabsch_from_stats(stats, st->scaling != 0);
+        // (the rotation-about-an-axis closed form is the cheaper of the two: no polar iteration, no SVD)
+        if (st->use_axis)
+            upd = kabsch_axis_from_stats(stats, st->axis);
+        else
+            upd = kabsch_from_stats(stats, st->scaling != 0);
     } else {
-        if (st->plane || st->solver == 1)
+        if (st->use_axis) {
+            // (the host refuses a Gauss-Newton point-to-point solver and scaling with an axis)
+            if (st->plane)
+                upd = gn_axis_from_stats(stats, st->axis, &ok);
+            else
+                upd = kabsch_axis_from_stats(stats, st->axis);
+        } else if (st->plane || st->solver == 1)
             upd = gn_from_stats(stats, false, &ok);
         else if (st->solver == 2)
             upd = gn_from_stats(stats, true, &ok);

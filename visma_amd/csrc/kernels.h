@@ -43,6 +43,9 @@ struct DevIcpState {
     float r2f;
     int have_prev;       // Tc_prev holds the transform of the previous NN pass (the certificate of grid_coop.hip)
     double Tc_prev[12];
+    double axis[3];      // use_axis: every update rotates about this unit axis only (host_math.hpp: *_axis_from_stats)
+    int use_axis;
+    int pad_axis;        // (the state is copied as 8-byte words)
 };
 
 // The fold of the partial rows inside the search launch (device_common.h: fused_fold).
