@@ -62,5 +62,9 @@ inline bool OrientNormalsToAlignWithDirection(PointCloud &cloud,
                                               const Eigen::Vector3d &orientation_reference = Eigen::Vector3d(0.0, 0.0, 1.0));
 inline bool OrientNormalsTowardsCameraLocation(PointCloud &cloud,
                                                const Eigen::Vector3d &camera_location = Eigen::Vector3d::Zero());
+/// Distance of every source point to the nearest target point, and of every point to the nearest other point of its
+/// cloud (shapes of O3D/Core/Geometry/PointCloud.h:161-167 and :180-183); on the GPU, in visma_icp_open3d.hpp.
+inline std::vector<double> ComputePointCloudToPointCloudDistance(const PointCloud &source, const PointCloud &target);
+inline std::vector<double> ComputePointCloudNearestNeighborDistance(const PointCloud &input);
 
 }  // namespace open3d

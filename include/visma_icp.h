@@ -605,6 +605,21 @@ VISMA_ICP_API int visma_icp_point_mesh_distance(visma_icp_ctx *ctx, const double
                                                 const double *V, int64_t nv, const int32_t *F,
                                                 int64_t nf, double *d2, int32_t *face,
                                                 double *closest);
+/* open3d::ComputePointCloudToPointCloudDistance (O3D/Core/Geometry/PointCloud.cpp:122-142; PointCloud.h:161-167)
+ * on the GPU: dist_out[i] = sqrt(min_j d2(src_i, tgt_j)), with no radius, for the ns source points (n x 3 f64,
+ * caller's order).  d2 is flann's L2<double>, ((dx*dx) + dy*dy) + dz*dz in f64, and the result equals the
+ * reference's bit for bit.  An empty target gives 0.0 for every query (the reference's SearchKNN fails on an
+ * empty tree and its preset dists[0] = 0 comes back, KDTreeFlann.cpp:124-127); a row with a NaN coordinate leaves
+ * the other rows unaffected, its own value unspecified.  Up to 2^31 - 1 points per cloud.  The context's clouds
+ * and search state are not touched. */
+VISMA_ICP_API int visma_icp_point_cloud_distance(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns,
+                                                 const double *tgt_xyz, int64_t nt, double *dist_out);
+/* open3d::ComputePointCloudNearestNeighborDistance (PointCloud.cpp:200-219; PointCloud.h:180-183) on the GPU:
+ * dist_out[i] = sqrt(min_{j != i} d2(xyz_i, xyz_j)) -- the reference's SearchKNN(p, 2) -> dists[1], so a duplicate
+ * point gives 0 and a one-point cloud gives 0.0 (its `<= 1` branch).  Same arithmetic, limits and guarantees as
+ * visma_icp_point_cloud_distance. */
+VISMA_ICP_API int visma_icp_nearest_neighbor_distance(visma_icp_ctx *ctx, const double *xyz, int64_t n,
+                                                      double *dist_out);
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

@@ -14,6 +14,8 @@
 //                                      (include/tool.h:40-42, src/annotation.cpp:29-64)
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
+//   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
+//                                      (O3D/Core/Geometry/PointCloud.h:161-183)
 //
 // No Eigen type crosses a binary boundary: the C ABI takes raw row-major
 // doubles, so a translation unit built with -DEIGEN_DEFAULT_TO_ROW_MAJOR (as
@@ -601,6 +603,36 @@ inline bool EstimateNormals(PointCloud &cloud, const KDTreeSearchParam &search_p
     return true;
 }
 
+// open3d::ComputePointCloudToPointCloudDistance (O3D/Core/Geometry/PointCloud.cpp:122-142) on the GPU: for every
+// source point the distance to the nearest target point, no radius, bit for bit the reference's (0 for every
+// point when the target is empty).
+inline std::vector<double> ComputePointCloudToPointCloudDistance(const PointCloud &source, const PointCloud &target)
+{
+    std::vector<double> distances(source.points_.size());
+    if (!distances.empty()) {
+        visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+        detail::check(ctx, visma_icp_point_cloud_distance(ctx, detail::xyz(source.points_),
+                                                          (int64_t)source.points_.size(), detail::xyz(target.points_),
+                                                          (int64_t)target.points_.size(), distances.data()),
+                      "visma_icp_point_cloud_distance");
+    }
+    return distances;
+}
+
+// open3d::ComputePointCloudNearestNeighborDistance (PointCloud.cpp:200-219) on the GPU: for every point the
+// distance to the nearest other point of the cloud (0 for a duplicate point and for a one-point cloud).
+inline std::vector<double> ComputePointCloudNearestNeighborDistance(const PointCloud &input)
+{
+    std::vector<double> nn_dis(input.points_.size());
+    if (!nn_dis.empty()) {
+        visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+        detail::check(ctx, visma_icp_nearest_neighbor_distance(ctx, detail::xyz(input.points_),
+                                                               (int64_t)input.points_.size(), nn_dis.data()),
+                      "visma_icp_nearest_neighbor_distance");
+    }
+    return nn_dis;
+}
+
 // O3D/Core/Geometry/EstimateNormals.cpp:155-174
 inline bool OrientNormalsToAlignWithDirection(PointCloud &cloud,
                                               const Eigen::Vector3d &orientation_reference = Eigen::Vector3d(0.0, 0.0, 1.0))
@@ -810,6 +842,14 @@ inline bool ReadPointCloudFromPCD(const std::string &filename, PointCloud &point
 inline bool EstimateNormals(PointCloud &cloud, const KDTreeSearchParam &search_param)
 {
     return cicp::EstimateNormals(cloud, search_param);
+}
+inline std::vector<double> ComputePointCloudToPointCloudDistance(const PointCloud &source, const PointCloud &target)
+{
+    return cicp::ComputePointCloudToPointCloudDistance(source, target);
+}
+inline std::vector<double> ComputePointCloudNearestNeighborDistance(const PointCloud &input)
+{
+    return cicp::ComputePointCloudNearestNeighborDistance(input);
 }
 inline bool OrientNormalsToAlignWithDirection(PointCloud &cloud, const Eigen::Vector3d &orientation_reference)
 {

@@ -199,6 +199,9 @@ def _bind(L):
         L.visma_icp_set_rotation_axis.argtypes = [C.c_void_p, _dp]
         L.visma_icp_get_rotation_axis.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
         L.visma_icp_solve_from_stats_axis.argtypes = [_dp, C.c_int, _dp, _dp]
+    if hasattr(L, "visma_icp_point_cloud_distance"):     # (A/B runs load older builds through VISMA_ICP_LIB)
+        L.visma_icp_point_cloud_distance.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _dp]
+        L.visma_icp_nearest_neighbor_distance.argtypes = [C.c_void_p, _dp, C.c_int64, _dp]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -512,6 +515,23 @@ class Context:
         self._chk(self.L.visma_icp_point_mesh_distance(self._h, _p(P, _dp), len(P), _p(V, _dp), len(V),
                                                        _p(F, _ip), len(F), _p(d2, _dp), _p(face, _ip), _p(cl, _dp)))
         return d2[:len(P)], face[:len(P)], cl[:len(P)]
+
+    def point_cloud_distance(self, src, tgt):
+        """open3d::ComputePointCloudToPointCloudDistance on the GPU: the distance of every source point to the nearest
+        target point (no radius; 0 for an empty target)."""
+        src = _f64(src, (-1, 3)); tgt = _f64(tgt, (-1, 3))
+        d = np.empty(max(len(src), 1))
+        self._chk(self.L.visma_icp_point_cloud_distance(self._h, _p(src, _dp), len(src), _p(tgt, _dp), len(tgt),
+                                                        _p(d, _dp)))
+        return d[:len(src)]
+
+    def nearest_neighbor_distance(self, xyz):
+        """open3d::ComputePointCloudNearestNeighborDistance on the GPU: the distance of every point to the nearest
+        other point of the cloud (0 for a duplicate, [0.0] for one point)."""
+        p = _f64(xyz, (-1, 3))
+        d = np.empty(max(len(p), 1))
+        self._chk(self.L.visma_icp_nearest_neighbor_distance(self._h, _p(p, _dp), len(p), _p(d, _dp)))
+        return d[:len(p)]
 
     def last_mesh_kernel_ms(self):
         """-> (query kernel ms, search-structure build ms) of the last mesh-distance call."""

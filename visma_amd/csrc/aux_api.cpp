@@ -1,5 +1,6 @@
 // aux_api.cpp -- C ABI of the steps either side of the ICP loop: VoxelDownSample, EstimateNormals, mesh sampling
-// and point-to-mesh distance, the error metric, and the SO(3) / SE(3) functions (host + device self-tests).
+// and point-to-mesh distance, cloud-to-cloud and nearest-neighbour distances, the error metric, and the SO(3) /
+// SE(3) functions (host + device self-tests).
 #include "driver_ctx.hpp"
 #include "plane_math.hpp"
 
@@ -56,6 +57,37 @@ int visma_icp_point_mesh_distance(visma_icp_ctx *ctx, const double *P, int64_t n
                                           std::string("point_mesh_distance: ") + hipGetErrorString(e));
     ctx->last_aux_kernel_ms = ms;
     ctx->last_aux_build_ms = bms;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_point_cloud_distance(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *tgt_xyz,
+                                   int64_t nt, double *dist_out)
+{
+    CTX_CHECK();
+    if (ns < 0 || nt < 0 || (ns > 0 && (!src_xyz || !dist_out)) || (nt > 0 && !tgt_xyz))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad point_cloud_distance arguments");
+    if (ns > 0x7fffffff || nt > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    if (ns == 0) return VISMA_ICP_OK;
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    hipError_t e = point_cloud_distance_device(src_xyz, ns, tgt_xyz, nt, dist_out, ctx->eng->aux_stream());
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("point_cloud_distance: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_nearest_neighbor_distance(visma_icp_ctx *ctx, const double *xyz, int64_t n, double *dist_out)
+{
+    CTX_CHECK();
+    if (n < 0 || (n > 0 && (!xyz || !dist_out)))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad nearest_neighbor_distance arguments");
+    if (n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    if (n == 0) return VISMA_ICP_OK;
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    hipError_t e = nearest_neighbor_distance_device(xyz, n, dist_out, ctx->eng->aux_stream());
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("nearest_neighbor_distance: ") + hipGetErrorString(e));
     return VISMA_ICP_OK;
 }
 

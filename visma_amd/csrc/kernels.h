@@ -368,6 +368,13 @@ hipError_t surface_distances_device(const double *h_Vs, int64_t nvs, const int32
                                     int quirks, unsigned long long seed, int method, double *h_dist,
                                     int64_t *n_out, float *kernel_ms, float *build_ms, hipStream_t stream);
 
+// ---- cloud-to-cloud distances (cloud_distance.hip): host arrays in, host arrays out ----
+// exact unbounded nearest-neighbour distance of every source point to the target (0 for an empty target), and of
+// every point to the nearest other point of its own cloud (0 for a one-point cloud); own buffers, the given stream
+hipError_t point_cloud_distance_device(const double *h_src, int64_t ns, const double *h_tgt, int64_t nt,
+                                       double *h_dist, hipStream_t stream);
+hipError_t nearest_neighbor_distance_device(const double *h_xyz, int64_t n, double *h_dist, hipStream_t stream);
+
 // ---- normal estimation (normals.hip): host arrays in, host arrays out ----------
 // open3d::EstimateNormals; search_type 0 KNN(knn) | 1 Radius(radius) | 2 Hybrid(radius, max_nn = knn)
 constexpr int kNormalsMaxList = 170;     // longer result lists live in global memory (a heap per point) instead of LDS

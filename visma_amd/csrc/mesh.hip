@@ -11,9 +11,7 @@
 //
 // Everything is f64: these steps run once per evaluation, their results are
 // compared value for value with the reference.
-#include "device_common.h"
-
-#include <hipcub/hipcub.hpp>
+#include "bvh_common.h"
 
 #include <math.h>
 #include <vector>
@@ -138,36 +136,18 @@ __global__ __launch_bounds__(kMeshBlock) void point_mesh_kernel(
 constexpr int kLeaf = 4;
 constexpr int kBvhBlock = 64;
 
-struct MortonParams {
-    double lo[3], inv[3];            // code = min(1023, (c - lo) * inv)
-};
-
-__device__ __forceinline__ unsigned spread10(unsigned v)
-{
-    v = (v | (v << 16)) & 0x030000FFu;
-    v = (v | (v << 8)) & 0x0300F00Fu;
-    v = (v | (v << 4)) & 0x030C30C3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
 __global__ __launch_bounds__(256) void tri_code_kernel(const double *__restrict__ V, const int *__restrict__ F,
                                                        long long nf, MortonParams mp,
                                                        unsigned *__restrict__ key, unsigned *__restrict__ val)
 {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= nf) return;
-    unsigned code = 0;
+    double c[3];
 #pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double c = (V[3 * (long long)F[3 * f] + a] + V[3 * (long long)F[3 * f + 1] + a] +
-                          V[3 * (long long)F[3 * f + 2] + a]) * (1.0 / 3.0);
-        double q = (c - mp.lo[a]) * mp.inv[a];
-        q = q >= 0.0 ? q : 0.0;                       // also catches NaN
-        const unsigned qi = q < 1023.0 ? (unsigned)q : 1023u;
-        code |= spread10(qi) << (2 - a);
-    }
-    key[f] = code;
+    for (int a = 0; a < 3; a++)
+        c[a] = (V[3 * (long long)F[3 * f] + a] + V[3 * (long long)F[3 * f + 1] + a] +
+                V[3 * (long long)F[3 * f + 2] + a]) * (1.0 / 3.0);
+    key[f] = morton_code(c, mp);
     val[f] = (unsigned)f;
 }
 
@@ -204,39 +184,6 @@ __global__ __launch_bounds__(256) void bvh_leaf_kernel(const double *__restrict_
     double *n = nodes + 6 * (P + g);
 #pragma unroll
     for (int a = 0; a < 3; a++) { n[a] = lo[a] - inflate; n[3 + a] = hi[a] + inflate; }
-}
-
-__global__ __launch_bounds__(256) void bvh_level_kernel(long long first, long long count, double *__restrict__ nodes)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= count) return;
-    const long long n = first + i;
-    const double *l = nodes + 6 * (2 * n), *r = l + 6;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        nodes[6 * n + a] = fmin(l[a], r[a]);
-        nodes[6 * n + 3 + a] = fmax(l[3 + a], r[3 + a]);
-    }
-}
-
-__device__ __forceinline__ double box_lower_bound(const double *__restrict__ n, const double p[3])
-{
-    double s = 0.0;
-    double t[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        const double below = n[a] - p[a], above = p[a] - n[3 + a];
-        t[a] = fmax(0.0, fmax(below, above));        // +inf for an empty (inverted) box
-    }
-    s = t[0] * t[0] + t[1] * t[1] + t[2] * t[2];
-    return s;
-}
-
-__device__ __forceinline__ float round_down_f32(double x)
-{
-    float f = (float)x;
-    if ((double)f > x) f = nextafterf(f, -INFINITY);
-    return f;
 }
 
 // Dynamic LDS: `depth` stack levels of (node u32, lower bound f32 rounded DOWN) per thread.
@@ -293,29 +240,6 @@ __global__ __launch_bounds__(kBvhBlock) void point_mesh_bvh_kernel(
     d2_out[i] = best;
     if (face_out) face_out[i] = bf;
     if (closest_out) { closest_out[3 * i] = bq[0]; closest_out[3 * i + 1] = bq[1]; closest_out[3 * i + 2] = bq[2]; }
-}
-
-__global__ __launch_bounds__(256) void point_code_kernel(const double *__restrict__ Pq, long long np, MortonParams mp,
-                                                         unsigned *__restrict__ key, unsigned *__restrict__ val)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= np) return;
-    unsigned code = 0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-        double q = (Pq[3 * i + a] - mp.lo[a]) * mp.inv[a];
-        q = q >= 0.0 ? q : 0.0;
-        const unsigned qi = q < 1023.0 ? (unsigned)q : 1023u;
-        code |= spread10(qi) << (2 - a);
-    }
-    key[i] = code;
-    val[i] = (unsigned)i;
-}
-
-__global__ __launch_bounds__(256) void sqrt_kernel(double *__restrict__ d, long long n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) d[i] = sqrt(d[i]);                     // correctly rounded, as std::sqrt / Eigen cwiseSqrt
 }
 
 // ---------------------------------------------------------------------------
@@ -403,13 +327,6 @@ hipError_t launch_exclusive_scan_u32(const unsigned *in, long long n, unsigned *
 // ---------------------------------------------------------------------------
 namespace {
 
-struct DBuf {                                       // device allocation, freed on scope exit
-    void *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
 #define MESH_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
 
 struct DevMesh {
@@ -459,27 +376,19 @@ hipError_t build_search(const DevMesh &m, int method, DevBvh &b, hipStream_t str
         return hipGetLastError();
     }
     if (nf >= ((int64_t)1 << 25)) return hipErrorInvalidValue;
-    MortonParams &mp = b.mp;
+    b.mp = morton_params(m.lo, m.hi);
+    const MortonParams &mp = b.mp;
     double ext = 0.0;
-    for (int a = 0; a < 3; a++) {
-        const double e = m.hi[a] - m.lo[a];
-        mp.lo[a] = m.lo[a];
-        mp.inv[a] = e > 0.0 ? 1024.0 / e : 0.0;
-        ext = fmax(ext, fmax(fabs(m.lo[a]), fabs(m.hi[a])));
-    }
+    for (int a = 0; a < 3; a++) ext = fmax(ext, fmax(fabs(m.lo[a]), fabs(m.hi[a])));
     DBuf key, key2, val, tmp;
-    size_t tmp_bytes = 0;
     MESH_TRY(key.alloc(sizeof(unsigned) * nf));
     MESH_TRY(key2.alloc(sizeof(unsigned) * nf));
     MESH_TRY(val.alloc(sizeof(unsigned) * nf));
     MESH_TRY(b.faceid.alloc(sizeof(unsigned) * nf));
     hipLaunchKernelGGL(tri_code_kernel, dim3(fb), dim3(256), 0, stream, m.V.as<double>(), m.F.as<int>(), (long long)nf,
                        mp, key.as<unsigned>(), val.as<unsigned>());
-    MESH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key.as<unsigned>(), key2.as<unsigned>(),
-                                                val.as<unsigned>(), b.faceid.as<unsigned>(), (int)nf, 0, 30, stream));
-    MESH_TRY(tmp.alloc(tmp_bytes));
-    MESH_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, key.as<unsigned>(), key2.as<unsigned>(),
-                                                val.as<unsigned>(), b.faceid.as<unsigned>(), (int)nf, 0, 30, stream));
+    MESH_TRY(morton_sort(key.as<unsigned>(), key2.as<unsigned>(), val.as<unsigned>(), b.faceid.as<unsigned>(), nf, tmp,
+                         stream));
     hipLaunchKernelGGL(tri_gather_kernel, dim3(fb), dim3(256), 0, stream, m.V.as<double>(), m.F.as<int>(),
                        b.faceid.as<unsigned>(), (long long)nf, b.tri.as<double>());
     const int64_t nleaf = (nf + kLeaf - 1) / kLeaf;
@@ -489,10 +398,7 @@ hipError_t build_search(const DevMesh &m, int method, DevBvh &b, hipStream_t str
     MESH_TRY(b.nodes.alloc(sizeof(double) * 6 * 2 * P));
     hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, b.tri.as<double>(),
                        (long long)nf, (long long)P, ldexp(ext, -40), b.nodes.as<double>());
-    for (int64_t first = P >> 1; first >= 1; first >>= 1)
-        hipLaunchKernelGGL(bvh_level_kernel, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, stream,
-                           (long long)first, (long long)first, b.nodes.as<double>());
-    MESH_TRY(hipGetLastError());
+    MESH_TRY(build_bvh_levels(b.nodes.as<double>(), P, stream));
     // the temporaries above are freed when this function returns: wait for the kernels using them
     return hipStreamSynchronize(stream);
 }
@@ -509,18 +415,14 @@ hipError_t launch_query(const DevBvh &b, const double *d_P, int64_t np, double *
     DBuf key, key2, val, order, tmp;
     const bool sorted = np >= 4096 && np < ((int64_t)1 << 31);
     if (sorted) {
-        size_t tmp_bytes = 0;
         MESH_TRY(key.alloc(sizeof(unsigned) * np));
         MESH_TRY(key2.alloc(sizeof(unsigned) * np));
         MESH_TRY(val.alloc(sizeof(unsigned) * np));
         MESH_TRY(order.alloc(sizeof(unsigned) * np));
         hipLaunchKernelGGL(point_code_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, d_P,
                            (long long)np, b.mp, key.as<unsigned>(), val.as<unsigned>());
-        MESH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key.as<unsigned>(), key2.as<unsigned>(),
-                                                    val.as<unsigned>(), order.as<unsigned>(), (int)np, 0, 30, stream));
-        MESH_TRY(tmp.alloc(tmp_bytes));
-        MESH_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, key.as<unsigned>(), key2.as<unsigned>(),
-                                                    val.as<unsigned>(), order.as<unsigned>(), (int)np, 0, 30, stream));
+        MESH_TRY(morton_sort(key.as<unsigned>(), key2.as<unsigned>(), val.as<unsigned>(), order.as<unsigned>(), np,
+                             tmp, stream));
     }
     int depth = 2;                                   // levels below the root + slack
     for (int64_t q = b.P; q > 1; q >>= 1) depth++;
