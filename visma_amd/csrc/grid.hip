@@ -994,185 +994,73 @@ __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
     if (fold.tickets) fused_fold<PLANE, kBlock, false, kSolveInFold>(fold, partials, row0, lb, bpp, prob);
 }
 
+// the lane-serial kernel of one (G, U) pair: shared clouds and batches (a.descs), fp32 / all-f64 / exact search
 template <bool PLANE, int G, int U>
-static void launch_grid_t(int nblocks, hipStream_t stream, const float4 *src, int ns,
-                          const float4 *sorted, const unsigned *start, const GridParams &g,
-                          const float4 *nrm, const Xform32 &T32, const Xform64 &T64,
-                          const Offset64 &off, float r2f, int *idx_out, float *d2_out,
-                          double *partials, unsigned long long *cand, const DevIcpState *st,
-                          int nprob, long long out_stride, const Pt64 *src64, const Pt64 *sorted64, double r2d,
-                          const Pt64 *nrm64, int exact, const FoldArgs &fold, double *d64_out, Pt64 *prevq_out)
+static void launch_grid_t(const SearchArgs &a, const SearchGeom &geo, hipStream_t stream)
 {
-    // one query per lane? (see ONE above)
-    const long long total_groups = (long long)nblocks * (kBlock / G);
-    const bool one = ((long long)ns + total_groups - 1) / total_groups <= G;
-#define VISMA_GRID_LAUNCH(ONE_, F64_, HYB_)                                                                     \
-    hipLaunchKernelGGL((nn_grid_reduce_kernel<PLANE, G, U, ONE_, F64_, HYB_>), dim3(nblocks * nprob),             \
-                       dim3(kBlock), 0, stream, src, ns, sorted, start, g, nrm, T32, T64, off, r2f, idx_out,      \
-                       d2_out, partials, cand, st, nblocks, out_stride, (const ProbDesc *)nullptr, nprob, src64,  \
-                       sorted64, r2d, nrm64, fold, d64_out, prevq_out)
-    if (src64 && exact) {
-        if (one) VISMA_GRID_LAUNCH(true, false, true); else VISMA_GRID_LAUNCH(false, false, true);
-    } else if (src64) {
-        if (one) VISMA_GRID_LAUNCH(true, true, false); else VISMA_GRID_LAUNCH(false, true, false);
+    // (the kernel takes the packed copy through the same parameter: P12 triples behind a float4 pointer)
+    const float4 *cand = a.packed() ? reinterpret_cast<const float4 *>(a.sorted12) : a.sorted;
+#define VISMA_GRID_LAUNCH(ONE_, F64_, HYB_)                                                                         \
+    hipLaunchKernelGGL((nn_grid_reduce_kernel<PLANE, G, U, ONE_, F64_, HYB_>), dim3(geo.total_blocks), dim3(kBlock), \
+                       0, stream, a.src, (int)a.ns, cand, a.start, a.g, a.nrm, a.T32, a.T64, a.off, a.r2f,          \
+                       a.idx_out, a.d2_out, a.partials, a.cand_count, a.st, geo.bpp, (long long)a.out_stride,       \
+                       a.descs, a.nprob, a.src64, a.sorted64, a.r2d, a.nrm64, a.fold, a.d64_out, a.wst_io)
+    if (a.packed()) {
+        if (geo.one) VISMA_GRID_LAUNCH(true, false, true); else VISMA_GRID_LAUNCH(false, false, true);
+    } else if (a.src64) {
+        if (geo.one) VISMA_GRID_LAUNCH(true, true, false); else VISMA_GRID_LAUNCH(false, true, false);
     } else {
-        if (one) VISMA_GRID_LAUNCH(true, false, false); else VISMA_GRID_LAUNCH(false, false, false);
+        if (geo.one) VISMA_GRID_LAUNCH(true, false, false); else VISMA_GRID_LAUNCH(false, false, false);
     }
 #undef VISMA_GRID_LAUNCH
 }
 
-hipError_t launch_nn_grid_reduce(const float4 *src, int64_t ns, const float4 *sorted,
-                                 const unsigned *start, const GridParams &g,
-                                 const float4 *tgt_normals, const Xform32 &T32, const Xform64 &T64,
-                                 const double frame_offset[3], float r2f, int point_to_plane,
-                                 int32_t *idx_out, float *d2_out, double *partials,
-                                 int max_partial_blocks, int *nblocks_out, int lanes_per_query,
-                                 unsigned long long *cand_count, const DevIcpState *st,
-                                 int nprob, int64_t out_stride, hipStream_t stream, const Pt64 *src64,
-                                 const Pt64 *sorted64, double r2d, const Pt64 *nrm64, int exact,
-                                 const FoldArgs *fold, double *d64_out, Pt64 *prevq_io, int warm, const Xform64 *Tprev,
-                                 const PersistArgs *persist, Pt64 *ru_io, const RingTable *ring)
+hipError_t launch_nn_grid_reduce(const SearchArgs &a, hipStream_t stream)
 {
-    if ((src64 == nullptr) != (sorted64 == nullptr)) return hipErrorInvalidValue;
+    const bool batch = a.descs != nullptr;
+    if ((a.src64 == nullptr) != (a.sorted64 == nullptr) || (a.packed() && !a.sorted12)) return hipErrorInvalidValue;
+    // (point-to-plane batches: exact or fp32 search)
+    if (batch && (!a.st || (a.point_to_plane && a.src64 && !a.exact))) return hipErrorInvalidValue;
+    // the flattened exact search applies (batches never use half-pitch rows: grid_plan(..., max_sub = 1))
+    const bool coop = a.lanes == kCoopLanes && a.packed() && a.wst_io && (batch || a.g.sub == 1);
     // (the persistent launch exists for the certificate kernel only)
-    if (persist && !(lanes_per_query == kCoopLanes && src64 && exact && g.sub == 1 && prevq_io)) return hipErrorInvalidValue;
-    Offset64 off;
-    for (int a = 0; a < 3; a++) off.v[a] = frame_offset ? frame_offset[a] : 0.0;
-    const FoldArgs fa = fold ? *fold : FoldArgs{};
-    const int G = lanes_per_query % 100;
-    int U = lanes_per_query / 100;
-    if (U == 0) U = (G >= 8) ? 2 : 4;
-    int64_t want = (ns * G + kBlock - 1) / kBlock;
-    int nblocks = (int)(want > max_partial_blocks ? max_partial_blocks : want);
-    if (nblocks < 1) nblocks = 1;
-    if (g.ring > 0) {
+    if (a.persist && !coop) return hipErrorInvalidValue;
+    const int G = a.lanes % 100;
+    int U = a.lanes / 100;
+    if (U == 0 && !batch) U = (G >= 8) ? 2 : 4;
+    const int nblocks = batch ? 1 : search_blocks(a.ns, a.lanes, a.max_blocks);
+    SearchGeom geo{batch ? a.total_blocks : nblocks * a.nprob, nblocks, a.one_per_lane};
+    if (a.g.ring > 0) {
         // cells smaller than the radius: the ring search (grid_ring.hip), G lanes per query
-        if (!src64 || persist || !ring) return hipErrorInvalidValue;
-        // (`sorted` is the packed 12-byte copy when the search is the exact one: HipEngine::search_sorted)
-        hipError_t e = launch_nn_ring(G, nblocks, nprob, (int)ns, src64, sorted64, exact ? (const float *)sorted : nullptr, start, g,
-                                      *ring, tgt_normals, nrm64, T64, off, r2f,
-                                      point_to_plane, idx_out, d2_out, d64_out, prevq_io, warm & 1, partials, cand_count, st,
-                                      (long long)out_stride, fa, stream);
-        if (nblocks_out) *nblocks_out = nblocks;
-        return e;
+        if (!a.src64 || a.persist || !a.ring.rows) return hipErrorInvalidValue;
+        return launch_nn_ring(a, nblocks, stream);
     }
-    if (lanes_per_query == kCoopLanes) {
-        if (src64 && exact && g.sub == 1 && prevq_io) {
-            // the flattened exact search (grid_coop.hip): `sorted` is the packed 12-byte copy
-            const bool one = (ns + (int64_t)nblocks * kBlock - 1) / ((int64_t)nblocks * kBlock) <= 1;
-            hipError_t e = launch_nn_coop(nblocks * nprob, nblocks, nprob, nullptr, (int)ns, (const float *)sorted, start, g,
-                                          tgt_normals, nrm64, T64, off, r2f, point_to_plane, one ? 1 : 0, idx_out, d2_out,
-                                          partials, cand_count, st, (long long)out_stride, src64, sorted64, fa, d64_out,
-                                          prevq_io, warm, stream, Tprev, persist, ru_io);
-            if (nblocks_out) *nblocks_out = nblocks;
-            return e;
+    if (a.lanes == kCoopLanes) {
+        if (coop) {
+            if (!batch) geo.one = (a.ns + (int64_t)nblocks * kBlock - 1) / ((int64_t)nblocks * kBlock) <= 1;
+            return launch_nn_coop(a, geo, stream);
         }
         U = 8;                                             // not the exact search: the lane-serial kernel
     }
+    if (!batch) {
+        // one query per lane? (see ONE above)
+        const long long total_groups = (long long)nblocks * (kBlock / (G > 0 ? G : 1));
+        geo.one = (a.ns + total_groups - 1) / total_groups <= G;
+    }
+    // the (G, U) pairs the driver's policies use (HipEngine::grid_lanes: 801, 1201, 402, 802, 804, 408) and no others
+    // since round 4 -- every pair is 12 kernel instantiations: PLANE x ONE x {fp32, f64, exact}.  Batches: the policy of
+    // HipEngine::run_loop_batch (801, 804, 402) -- the other pairs went in round 4
+    if (batch && !((G == 4 && U == 8) || (G == 1 && U == 8) || (G == 2 && U == 4))) return hipErrorInvalidValue;
 #define VISMA_GRID_CASE(GG, UU)                                                                    \
     if (G == GG && U == UU) {                                                                      \
-        if (point_to_plane)                                                                        \
-            launch_grid_t<true, GG, UU>(nblocks, stream, src, (int)ns, sorted, start, g,           \
-                                        tgt_normals, T32, T64, off, r2f, idx_out, d2_out,          \
-                                        partials, cand_count, st, nprob, (long long)out_stride, src64, sorted64, r2d, nrm64, exact, fa, d64_out, prevq_io);   \
-        else                                                                                       \
-            launch_grid_t<false, GG, UU>(nblocks, stream, src, (int)ns, sorted, start, g,          \
-                                         tgt_normals, T32, T64, off, r2f, idx_out, d2_out,         \
-                                         partials, cand_count, st, nprob, (long long)out_stride, src64, sorted64, r2d, nrm64, exact, fa, d64_out, prevq_io);  \
-        launched = true;                                                                           \
+        if (a.point_to_plane) launch_grid_t<true, GG, UU>(a, geo, stream);                         \
+        else launch_grid_t<false, GG, UU>(a, geo, stream);                                         \
+        return hipGetLastError();                                                                  \
     }
-    bool launched = false;
-    // the (G, U) pairs the driver's policies use (HipEngine::grid_lanes: 801, 1201, 402, 802, 804, 408) and no others
-    // since round 4 -- every pair is 12 kernel instantiations: PLANE x ONE x {fp32, f64, exact}
     VISMA_GRID_CASE(1, 8) VISMA_GRID_CASE(1, 12) VISMA_GRID_CASE(2, 4) VISMA_GRID_CASE(2, 8)
     VISMA_GRID_CASE(4, 8) VISMA_GRID_CASE(8, 4)
-    if (!launched) return hipErrorInvalidValue;
 #undef VISMA_GRID_CASE
-    if (nblocks_out) *nblocks_out = nblocks;
-    return hipGetLastError();
-}
-
-template <int G, int U, bool ONE, bool F64, bool HYB, bool PLANE = false>
-static void launch_grid_batch_t(int total_blocks, hipStream_t stream, const float4 *src,
-                                const float4 *sorted, const unsigned *start, const ProbDesc *descs,
-                                int nprob, int *idx_out, float *d2_out, double *partials,
-                                const DevIcpState *st, const Pt64 *src64, const Pt64 *sorted64, const FoldArgs &fold,
-                                unsigned long long *cand, const float4 *nrm = nullptr, const Pt64 *nrm64 = nullptr,
-                                Pt64 *prevq_out = nullptr)
-{
-    const Xform32 T32{};
-    const Xform64 T64{};
-    const Offset64 off{};
-    const GridParams g{};
-    hipLaunchKernelGGL((nn_grid_reduce_kernel<PLANE, G, U, ONE, F64, HYB>), dim3(total_blocks), dim3(kBlock), 0, stream,
-                       src, 0, sorted, start, g, nrm, T32, T64, off, 0.f, idx_out,
-                       d2_out, partials, cand, st, 1, 0ll, descs, nprob, src64, sorted64, 0.0,
-                       nrm64, fold, (double *)nullptr, prevq_out);
-}
-
-// lanes_per_query = G + 100 * U; one_per_lane: every problem has at most G queries per lane group;
-// src64 / sorted64 (both or neither): the f64 search (exact = 0) or the exact fp32+f64 search (exact = 1),
-// arrays concatenated like src / sorted
-hipError_t launch_nn_grid_reduce_batch(const float4 *src, const float4 *sorted, const unsigned *start,
-                                       const ProbDesc *descs, int nprob, int total_blocks,
-                                       int32_t *idx_out, float *d2_out, double *partials,
-                                       int lanes_per_query, int one_per_lane, const DevIcpState *st,
-                                       hipStream_t stream, const Pt64 *src64, const Pt64 *sorted64, int exact,
-                                       const FoldArgs *fold, unsigned long long *cand_count,
-                                       const float4 *nrm, const Pt64 *nrm64, Pt64 *prevq_io, int warm)
-{
-    if (!st || !descs || (src64 == nullptr) != (sorted64 == nullptr)) return hipErrorInvalidValue;
-    const bool plane = nrm != nullptr || nrm64 != nullptr;
-    if (plane && src64 && !exact) return hipErrorInvalidValue;      // point-to-plane batches: exact or fp32 search
-    const FoldArgs fa = fold ? *fold : FoldArgs{};
-    const int G = lanes_per_query % 100;
-    int U = lanes_per_query / 100;
-    if (lanes_per_query == kCoopLanes) {
-        if (src64 && exact && prevq_io) {
-            // (batches never use half-pitch rows: grid_plan(..., max_sub = 1))
-            const Xform64 T64{};
-            const Offset64 off{};
-            const GridParams g{};
-            return launch_nn_coop(total_blocks, 1, nprob, descs, 0, (const float *)sorted, start, g, nrm, nrm64, T64, off,
-                                  0.f, plane ? 1 : 0, one_per_lane, idx_out, d2_out, partials, cand_count, st, 0ll, src64,
-                                  sorted64, fa, nullptr, prevq_io, warm, stream);
-        }
-        U = 8;
-    }
-    bool launched = false;
-#define VISMA_BATCH_ARGS total_blocks, stream, src, sorted, start, descs, nprob, idx_out, d2_out, partials, st
-#define VISMA_BATCH_CASE(GG, UU)                                                                              \
-    if (G == GG && U == UU && plane) {                                                                        \
-        if (src64 && one_per_lane)                                                                            \
-            launch_grid_batch_t<GG, UU, true, false, true, true>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nrm, nrm64, prevq_io);   \
-        else if (src64)                                                                                       \
-            launch_grid_batch_t<GG, UU, false, false, true, true>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nrm, nrm64, prevq_io);  \
-        else if (one_per_lane)                                                                                \
-            launch_grid_batch_t<GG, UU, true, false, false, true>(VISMA_BATCH_ARGS, nullptr, nullptr, fa, cand_count, nrm, nrm64, prevq_io); \
-        else                                                                                                  \
-            launch_grid_batch_t<GG, UU, false, false, false, true>(VISMA_BATCH_ARGS, nullptr, nullptr, fa, cand_count, nrm, nrm64, prevq_io); \
-        launched = true;                                                                                      \
-    } else if (G == GG && U == UU) {                                                                          \
-        if (src64 && exact && one_per_lane)                                                                   \
-            launch_grid_batch_t<GG, UU, true, false, true>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nullptr, nullptr, prevq_io);            \
-        else if (src64 && exact)                                                                              \
-            launch_grid_batch_t<GG, UU, false, false, true>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nullptr, nullptr, prevq_io);           \
-        else if (src64 && one_per_lane)                                                                       \
-            launch_grid_batch_t<GG, UU, true, true, false>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nullptr, nullptr, prevq_io);            \
-        else if (src64)                                                                                       \
-            launch_grid_batch_t<GG, UU, false, true, false>(VISMA_BATCH_ARGS, src64, sorted64, fa, cand_count, nullptr, nullptr, prevq_io);           \
-        else if (one_per_lane)                                                                                \
-            launch_grid_batch_t<GG, UU, true, false, false>(VISMA_BATCH_ARGS, nullptr, nullptr, fa, cand_count, nullptr, nullptr, prevq_io);          \
-        else                                                                                                  \
-            launch_grid_batch_t<GG, UU, false, false, false>(VISMA_BATCH_ARGS, nullptr, nullptr, fa, cand_count, nullptr, nullptr, prevq_io);         \
-        launched = true;                                                                                      \
-    }
-    // (the batch policy of HipEngine::run_batch: 801, 804, 402 -- the other pairs went in round 4)
-    VISMA_BATCH_CASE(4, 8) VISMA_BATCH_CASE(1, 8) VISMA_BATCH_CASE(2, 4)
-#undef VISMA_BATCH_CASE
-#undef VISMA_BATCH_ARGS
-    if (!launched) return hipErrorInvalidValue;
-    return hipGetLastError();
+    return hipErrorInvalidValue;
 }
 
 }  // namespace visma

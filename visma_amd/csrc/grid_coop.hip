@@ -191,7 +191,7 @@ __device__ __forceinline__ bool coop_body(
     long long row0;
     if (descs) {
         // batch of problems with their own clouds (largest p with first_block <= blockIdx.x; wave-uniform)
-        if (warm & 2) {
+        if (warm & kWarmMap) {
             // (the launcher put a workgroup -> problem map behind the descriptors)
             prob = reinterpret_cast<const int *>(descs + nprob)[blockIdx.x];
         } else {
@@ -232,14 +232,14 @@ __device__ __forceinline__ bool coop_body(
         if (!load_loop_state(st, T32_unused, T64, off, r2f)) return false;
         if (st) {
             // device-resident loop: the transform of the previous pass travels with the state (advance_state)
-            warm &= ~4;
-            if (st->have_prev && !(warm & 8)) {              // (warm & 8: certificates switched off, A/B timing)
-                warm |= 4;
+            warm &= ~kWarmTprev;
+            if (st->have_prev && !(warm & kWarmNoCert)) {    // (certificates switched off: A/B timing)
+                warm |= kWarmTprev;
 #pragma unroll
                 for (int k = 0; k < 12; k++) Tprev.m[k] = st->Tc_prev[k];
             }
         }
-        if (!(warm & 1)) warm &= ~4;
+        if (!(warm & kWarmRead)) warm &= ~kWarmTprev;
     }
     const double r2d = (double)r2f;                         // (double)(float)(r*r): KDTreeFlann.cpp:184-185
     COOP_PROBE_BEGIN();
@@ -460,7 +460,7 @@ __device__ __forceinline__ bool coop_body(
     //  body -- youngest slot highest --, 2 = reversed in every other phase)
     auto set_phase_prio = [&](const int phase) {
         if constexpr (PERSIST) {
-            const int mode = (warm >> 5) & 3;
+            const int mode = (warm >> kWarmPrioShift) & kWarmPrioMask;
             if (mode != 0) {
                 const int slot = (int)((blockIdx.x * 4u) / gridDim.x);
                 const int p = mode == 1 ? slot : ((phase & 1) ? slot : 3 - slot);
@@ -491,14 +491,14 @@ __device__ __forceinline__ bool coop_body(
             }
             if constexpr (PERSIST) {
                 if (res.first) {
-                    if (warm & 1) w8 = wst_io[i];
+                    if (warm & kWarmRead) w8 = wst_io[i];
                 } else {
                     // the state the pass before left in this lane's slots
                     w8.x = s_q64[tid][0]; w8.y = s_q64[tid][1]; w8.z = s_q64[tid][2];
                     w8.w = (unsigned long long)__float_as_uint(s_dprev[tid]) | ((unsigned long long)__float_as_uint(res.lb[tid]) << 32);
                 }
             } else {
-                if (warm & 1) w8 = wst_io[i];
+                if (warm & kWarmRead) w8 = wst_io[i];
             }
         }
         // (se3_act: the restatement of SE3Type's action on a point, core/se3.h:103-106 -- same products, same order)
@@ -513,13 +513,13 @@ __device__ __forceinline__ bool coop_body(
         u8.x = u8.y = u8.z = __longlong_as_double(-1ll);
         u8.w = ~0ull;
         if constexpr (kCoopRu) {
-            if (ru_io && active && (warm & 4)) u8 = ru_io[i];
+            if (ru_io && active && (warm & kWarmTprev)) u8 = ru_io[i];
         }
         // ---- the certificate: has the query moved by less than the room its previous result left?
         unsigned widx = (unsigned)w8.w;
         bool has_w = w8.x == w8.x;                           // (NaN: no previous winner)
         bool cert = false;
-        if (warm & 4) {
+        if (warm & kWarmTprev) {
             const float hx = (float)hp[0], hy = (float)hp[1], hz = (float)hp[2];
             const float rup = sqrtf(r2f) * (1.0f + 2.4e-7f);
             const float E = 2.4e-7f * (fabsf(hx) + fabsf(hy) + fabsf(hz) + rup) + 4.8e-7f * rup;
@@ -1317,7 +1317,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
         }
         // (after the first pass: the state the pass before left is there, and so is its transform)
         int w = VISMA_KARG(warm);
-        if (pass > 1) { w |= 1; if (!(w & 8)) w |= 4; }
+        if (pass > 1) { w |= kWarmRead; if (!(w & kWarmNoCert)) w |= kWarmTprev; }
         FoldArgs f{};
         f.tickets = VISMA_KARG(fold.tickets); f.partials2 = VISMA_KARG(fold.partials2);
         f.ticket_stride = VISMA_KARG(fold.ticket_stride); f.stats_out = VISMA_KARG(fold.stats_out);
@@ -1420,46 +1420,38 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) 
 #undef VISMA_COOP_PARAMS
 #undef VISMA_COOP_ARGS
 
-#define VISMA_COOP_LAUNCH(KERNEL_)                                                                               \
-    hipLaunchKernelGGL(KERNEL_, dim3(total_blocks), dim3(kBlock), 0, stream, ns, s12, start, g, nrm, T64, off,   \
-                       r2f, idx_out, d2_out, partials, cand_count, st, bpp, out_stride, descs, nprob, src64,     \
-                       sorted64, nrm64, fold, d64_out, wst_io, warm, Tp, ru_io)
+#define VISMA_COOP_LAUNCH(KERNEL_)                                                                                  \
+    hipLaunchKernelGGL(KERNEL_, dim3(geo.total_blocks), dim3(kBlock), 0, stream, (int)a.ns, a.sorted12, a.start, a.g, \
+                       a.nrm, a.T64, a.off, a.r2f, a.idx_out, a.d2_out, a.partials, a.cand_count, a.st, geo.bpp,     \
+                       (long long)a.out_stride, a.descs, a.nprob, a.src64, a.sorted64, a.nrm64, a.fold, a.d64_out,   \
+                       a.wst_io, warm, Tp, a.ru_io)
 
-// The warm-started, flattened exact search.  Shared clouds: `nprob` problems of `bpp` workgroups each
-// (descs == NULL); own clouds: descs[nprob], total_blocks workgroups.  `one`: at most one query per lane.
-// warm & 2: a workgroup -> problem map (int per workgroup) follows descs[nprob].
-// wst_io (one Pt64 per query, laid out like idx_out): read when `warm & 1` (the winners of the previous pass
-// over the SAME source order and target: f64 point, original index | LB << 32; NaN coordinates = none, all bits
-// set = nothing known), always written.  warm & 4: Tprev is the transform of the pass that left the state
-// (device loops take it from their DevIcpState instead) -- queries whose winner provably cannot have changed skip
-// the search (the certificate above).
-hipError_t launch_nn_coop(int total_blocks, int bpp, int nprob, const ProbDesc *descs, int ns, const float *s12,
-                          const unsigned *start, const GridParams &g, const float4 *nrm, const Pt64 *nrm64,
-                          const Xform64 &T64, const Offset64 &off, float r2f, int point_to_plane, int one,
-                          int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                          const DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                          const FoldArgs &fold, double *d64_out, Pt64 *wst_io, int warm, hipStream_t stream,
-                          const Xform64 *Tprev, const PersistArgs *persist, Pt64 *ru_io)
+// The warm-started, flattened exact search.  Shared clouds: a.nprob problems of geo.bpp workgroups each
+// (a.descs == NULL); own clouds: descs[nprob], geo.total_blocks workgroups.  With a.Tprev (device loops: from their
+// DevIcpState instead) queries whose winner provably cannot have changed skip the search (the certificate above).
+hipError_t launch_nn_coop(const SearchArgs &a, const SearchGeom &geo, hipStream_t stream)
 {
-    if (!src64 || !sorted64 || !s12 || !wst_io) return hipErrorInvalidValue;
-    if (persist) {
+    if (!a.src64 || !a.sorted64 || !a.sorted12 || !a.wst_io) return hipErrorInvalidValue;
+    const FoldArgs &fold = a.fold;
+    const int warm = a.Tprev ? (a.warm | kWarmTprev) : (a.warm & ~kWarmTprev);
+    if (const PersistArgs *persist = a.persist) {
         // (the certificate kernels carry no solve epilogue: a fold that asks for one would leave the state where it is,
         //  silently -- refuse it here rather than trust the caller's predicate)
         if (fold.solve) return hipErrorInvalidValue;
         // one registration, one query per lane, the fold and its publication inside the launch, everybody resident
-        if (descs || nprob != 1 || !one || st || !fold.rows_tagged || !fold.rows2_tagged || !fold.dead_flag || !fold.host_out ||
-            (fold.ipc_n > 1 && !fold.peer_table) || d64_out ||
+        if (a.descs || a.nprob != 1 || !geo.one || a.st || !fold.rows_tagged || !fold.rows2_tagged || !fold.dead_flag || !fold.host_out ||
+            (fold.ipc_n > 1 && !fold.peer_table) || a.d64_out ||
             persist->max_passes < 1 || !persist->host_cmd || !persist->relay || !persist->host_flag ||
-            total_blocks > coop_persist_capacity(point_to_plane))
+            geo.total_blocks > coop_persist_capacity(a.point_to_plane))
             return hipErrorInvalidValue;
         CoopPersistParams P{};
-        P.ns = ns; P.s12f = s12; P.start = start; P.g = g; P.nrm = nrm; P.T64 = T64; P.off = off; P.r2f = r2f;
-        P.idx_out = idx_out; P.d2_out = d2_out; P.partials = partials; P.cand_count = cand_count; P.bpp = bpp;
-        P.src64 = src64; P.sorted64 = sorted64; P.nrm64 = nrm64; P.fold = fold; P.wst_io = wst_io;
-        if (Tprev) { P.Tprev = *Tprev; warm |= 4; } else warm &= ~4;
-        P.warm = warm; P.pa = *persist; P.ru_io = ru_io;
-        if (point_to_plane) hipLaunchKernelGGL(nn_coop_kernel_persist<true>, dim3(total_blocks), dim3(kBlock), 0, stream, P);
-        else hipLaunchKernelGGL(nn_coop_kernel_persist<false>, dim3(total_blocks), dim3(kBlock), 0, stream, P);
+        P.ns = (int)a.ns; P.s12f = a.sorted12; P.start = a.start; P.g = a.g; P.nrm = a.nrm; P.T64 = a.T64; P.off = a.off; P.r2f = a.r2f;
+        P.idx_out = a.idx_out; P.d2_out = a.d2_out; P.partials = a.partials; P.cand_count = a.cand_count; P.bpp = geo.bpp;
+        P.src64 = a.src64; P.sorted64 = a.sorted64; P.nrm64 = a.nrm64; P.fold = fold; P.wst_io = a.wst_io;
+        if (a.Tprev) P.Tprev = *a.Tprev;
+        P.warm = warm; P.pa = *persist; P.ru_io = a.ru_io;
+        if (a.point_to_plane) hipLaunchKernelGGL(nn_coop_kernel_persist<true>, dim3(geo.total_blocks), dim3(kBlock), 0, stream, P);
+        else hipLaunchKernelGGL(nn_coop_kernel_persist<false>, dim3(geo.total_blocks), dim3(kBlock), 0, stream, P);
         return hipGetLastError();
     }
     // batches (problems with their own clouds) and sweeps over shared clouds: round 3's wave-synchronous kernel
@@ -1468,17 +1460,14 @@ hipError_t launch_nn_coop(int total_blocks, int bpp, int nprob, const ProbDesc *
         const char *e = std::getenv("VISMA_ICP_COOP_KERNEL");
         return !e ? 0 : (e[0] == 'c' ? 1 : (e[0] == 'w' ? 2 : 0));
     }();
-    if (forced == 2 || (forced == 0 && (descs || nprob > 1)))
-        return launch_nn_wave(total_blocks, bpp, nprob, descs, ns, s12, start, g, nrm, nrm64, T64, off, r2f, point_to_plane, one,
-                              idx_out, d2_out, partials, cand_count, st, out_stride, src64, sorted64, fold, d64_out, wst_io,
-                              warm & (3 | 8), stream);       // (8: certificates off -- the wave kernel's no-partner one too)
+    if (forced == 2 || (forced == 0 && (a.descs || a.nprob > 1))) return launch_nn_wave(a, geo, stream);
     if (fold.solve) return hipErrorInvalidValue;            // (as above: only launch_nn_wave's kernels honour it)
     Xform64 Tp{};
-    if (Tprev) { Tp = *Tprev; warm |= 4; } else warm &= ~4;
-    if (point_to_plane) {
-        if (one) VISMA_COOP_LAUNCH(nn_coop_kernel_one<true>); else VISMA_COOP_LAUNCH(nn_coop_kernel_many<true>);
+    if (a.Tprev) Tp = *a.Tprev;
+    if (a.point_to_plane) {
+        if (geo.one) VISMA_COOP_LAUNCH(nn_coop_kernel_one<true>); else VISMA_COOP_LAUNCH(nn_coop_kernel_many<true>);
     } else {
-        if (one) VISMA_COOP_LAUNCH(nn_coop_kernel_one<false>); else VISMA_COOP_LAUNCH(nn_coop_kernel_many<false>);
+        if (geo.one) VISMA_COOP_LAUNCH(nn_coop_kernel_one<false>); else VISMA_COOP_LAUNCH(nn_coop_kernel_many<false>);
     }
     return hipGetLastError();
 }

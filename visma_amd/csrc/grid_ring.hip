@@ -475,28 +475,28 @@ __global__ __launch_bounds__(256) void count_occupied_kernel(const unsigned *__r
 
 }  // namespace
 
-// `lanes` (1, 2, 4, 8) lanes per query, `nblocks` workgroups per problem, `nprob` problems over shared clouds (st: their loop
-// states or NULL); g.ring > 0.
-// state_io: per query the winner's f64 point and original index (all bits set = none), laid out like idx_out: read when
-// `warm` (every entry must be none or a point of THIS target), always written.
-hipError_t launch_nn_ring(int lanes, int nblocks, int nprob, int ns, const Pt64 *src64, const Pt64 *sorted64, const float *s12, const unsigned *start,
-                          const GridParams &g, const RingTable &tab, const float4 *nrm, const Pt64 *nrm64, const Xform64 &T64,
-                          const Offset64 &off, float r2f, int point_to_plane, int32_t *idx_out, float *d2_out, double *d64_out,
-                          Pt64 *state_io, int warm, double *partials, unsigned long long *cand_count, const DevIcpState *st,
-                          long long out_stride, const FoldArgs &fold, hipStream_t stream)
+// a.lanes % 100 = 1, 2, 4 or 8 lanes per query, `nblocks` workgroups per problem, a.nprob problems over shared clouds (a.st:
+// their loop states or NULL); g.ring > 0.
+// wst_io: per query the winner's f64 point and original index (all bits set = none), laid out like idx_out: read when
+// a.warm & kWarmRead (every entry must be none or a point of THIS target), always written.
+hipError_t launch_nn_ring(const SearchArgs &a, int nblocks, hipStream_t stream)
 {
-    if (!src64 || !sorted64 || !start || g.ring < 1 || g.sub != 1 || !tab.rows || tab.nrows != (2 * g.ring + 1) * (2 * g.ring + 1) || nblocks < 1 || nprob < 1 ||
-        (lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8))
+    const int lanes = a.lanes % 100;
+    const GridParams &g = a.g;
+    if (!a.src64 || !a.sorted64 || !a.start || g.ring < 1 || g.sub != 1 || !a.ring.rows || a.ring.nrows != (2 * g.ring + 1) * (2 * g.ring + 1) ||
+        nblocks < 1 || a.nprob < 1 || (lanes != 1 && lanes != 2 && lanes != 4 && lanes != 8))
         return hipErrorInvalidValue;
-    if (point_to_plane && !nrm && !nrm64) return hipErrorInvalidValue;
-    const bool one = (long long)nblocks * (kBlock / lanes) >= (long long)ns;       // at most one query per lane group
+    if (a.point_to_plane && !a.nrm && !a.nrm64) return hipErrorInvalidValue;
+    const bool one = (long long)nblocks * (kBlock / lanes) >= (long long)a.ns;       // at most one query per lane group
+    const P12 *s12 = a.packed() ? reinterpret_cast<const P12 *>(a.sorted12) : nullptr;
 #define VISMA_RING_LAUNCH(PLANE_, ONE_, G_, R_)                                                                                  \
-    hipLaunchKernelGGL((nn_ring_kernel<PLANE_, ONE_, G_, R_>), dim3(nblocks * nprob), dim3(kBlock), 0, stream, ns, src64,        \
-                       sorted64, reinterpret_cast<const P12 *>(s12), start, g, tab.rows, tab.nrows, nrm, nrm64, T64, off, r2f, idx_out, d2_out,       \
-                       d64_out, state_io, warm, partials, cand_count, st, nblocks, out_stride, fold)
+    hipLaunchKernelGGL((nn_ring_kernel<PLANE_, ONE_, G_, R_>), dim3(nblocks * a.nprob), dim3(kBlock), 0, stream, (int)a.ns,      \
+                       a.src64, a.sorted64, s12, a.start, g, a.ring.rows, a.ring.nrows, a.nrm, a.nrm64, a.T64, a.off, a.r2f,     \
+                       a.idx_out, a.d2_out, a.d64_out, a.wst_io, a.warm & kWarmRead, a.partials, a.cand_count, a.st, nblocks,    \
+                       (long long)a.out_stride, a.fold)
 #define VISMA_RING_CASE(G_, R_)                                                                                                  \
     if (lanes == G_) {                                                                                                           \
-        if (point_to_plane) { if (one) VISMA_RING_LAUNCH(true, true, G_, R_); else VISMA_RING_LAUNCH(true, false, G_, R_); }     \
+        if (a.point_to_plane) { if (one) VISMA_RING_LAUNCH(true, true, G_, R_); else VISMA_RING_LAUNCH(true, false, G_, R_); }     \
         else { if (one) VISMA_RING_LAUNCH(false, true, G_, R_); else VISMA_RING_LAUNCH(false, false, G_, R_); }                  \
     }
 #ifndef VISMA_RING_R8

@@ -132,7 +132,7 @@ __device__ __forceinline__ bool wave_body(
     long long row0;
     if (descs) {
         // batch of problems with their own clouds (largest p with first_block <= blockIdx.x; wave-uniform)
-        if (warm & 2) {
+        if (warm & kWarmMap) {
             // (the launcher put a workgroup -> problem map behind the descriptors)
             prob = reinterpret_cast<const int *>(descs + nprob)[blockIdx.x];
         } else {
@@ -205,7 +205,7 @@ __device__ __forceinline__ bool wave_body(
         float4 qprev = make_float4(NAN, NAN, NAN, 0.f);     // the previous pass's winner (fp32 view), NaN = none
         if (active) {
             s8 = src64[i];
-            if (warm & 1) {
+            if (warm & kWarmRead) {
                 // (the state of grid_coop.hip: the previous winner's f64 point; all bits set = NaN = none)
                 const Pt64 w8 = prevq_io[i];
                 qprev = make_float4((float)w8.x, (float)w8.y, (float)w8.z, 0.f);
@@ -747,44 +747,36 @@ int nn_wave_sweep_capacity()
     return cap[dev];
 }
 
-hipError_t launch_nn_wave_sweep(int bpp, int nprob, int ns, const float *s12, const unsigned *start, const GridParams &g,
-                                float r2f, int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                                DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                                const FoldArgs &fold, Pt64 *prevq_io, const SweepArgs &sa, hipStream_t stream)
+hipError_t launch_nn_wave_sweep(const SearchArgs &a, const SweepArgs &sa, hipStream_t stream)
 {
-    if (!src64 || !sorted64 || !s12 || !prevq_io || !st || !fold.tickets || !sa.relay || !sa.dead || sa.max_passes < 1 ||
-        bpp < 1 || nprob < 1 || (long long)bpp * kBlock < ns || bpp * nprob > nn_wave_sweep_capacity())
+    const int bpp = search_blocks(a.ns, kCoopLanes, a.max_blocks);
+    if (!a.src64 || !a.sorted64 || !a.sorted12 || !a.wst_io || !a.st || !a.fold.tickets || !sa.relay || !sa.dead || sa.max_passes < 1 ||
+        a.nprob < 1 || (long long)bpp * kBlock < a.ns || bpp * a.nprob > nn_wave_sweep_capacity())
         return hipErrorInvalidValue;
     SweepParams P{};
-    P.ns = ns; P.s12f = s12; P.start = start; P.g = g; P.r2f = r2f; P.idx_out = idx_out; P.d2_out = d2_out; P.partials = partials;
-    P.cand_count = cand_count; P.st = st; P.bpp = bpp; P.out_stride = out_stride; P.nprob = nprob; P.src64 = src64;
-    P.sorted64 = sorted64; P.fold = fold; P.prevq_io = prevq_io; P.sa = sa;
-    hipLaunchKernelGGL(nn_wave_kernel_sweep<false>, dim3(bpp * nprob), dim3(kBlock), 0, stream, P);
+    P.ns = (int)a.ns; P.s12f = a.sorted12; P.start = a.start; P.g = a.g; P.r2f = a.r2f; P.idx_out = a.idx_out; P.d2_out = a.d2_out;
+    P.partials = a.partials; P.cand_count = a.cand_count; P.st = a.st; P.bpp = bpp; P.out_stride = (long long)a.out_stride;
+    P.nprob = a.nprob; P.src64 = a.src64; P.sorted64 = a.sorted64; P.fold = a.fold; P.prevq_io = a.wst_io; P.sa = sa;
+    hipLaunchKernelGGL(nn_wave_kernel_sweep<false>, dim3(bpp * a.nprob), dim3(kBlock), 0, stream, P);
     return hipGetLastError();
 }
 
-#define VISMA_WAVE_LAUNCH(KERNEL_)                                                                               \
-    hipLaunchKernelGGL(KERNEL_, dim3(total_blocks), dim3(kBlock), 0, stream, ns, s12, start, g, nrm, T64, off,   \
-                       r2f, idx_out, d2_out, partials, cand_count, st, bpp, out_stride, descs, nprob, src64,     \
-                       sorted64, nrm64, fold, d64_out, prevq_io, warm)
+#define VISMA_WAVE_LAUNCH(KERNEL_)                                                                                  \
+    hipLaunchKernelGGL(KERNEL_, dim3(geo.total_blocks), dim3(kBlock), 0, stream, (int)a.ns, a.sorted12, a.start, a.g, \
+                       a.nrm, a.T64, a.off, a.r2f, a.idx_out, a.d2_out, a.partials, a.cand_count, a.st, geo.bpp,     \
+                       (long long)a.out_stride, a.descs, a.nprob, a.src64, a.sorted64, a.nrm64, a.fold, a.d64_out,   \
+                       a.wst_io, warm)
 
-// The warm-started, flattened exact search.  Shared clouds: `nprob` problems of `bpp` workgroups each
-// (descs == NULL); own clouds: descs[nprob], total_blocks workgroups.  `one`: at most one query per lane.
-// warm & 2: a workgroup -> problem map (int per workgroup) follows descs[nprob].
-// prevq_io (one float4 per query, laid out like idx_out): read when `warm & 1` (the winners of the previous pass
-// over the SAME source order and target, as fp32 points of the candidate array; NaN = none), always written.
-hipError_t launch_nn_wave(int total_blocks, int bpp, int nprob, const ProbDesc *descs, int ns, const float *s12,
-                          const unsigned *start, const GridParams &g, const float4 *nrm, const Pt64 *nrm64,
-                          const Xform64 &T64, const Offset64 &off, float r2f, int point_to_plane, int one,
-                          int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                          const DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                          const FoldArgs &fold, double *d64_out, Pt64 *prevq_io, int warm, hipStream_t stream)
+// The warm-started, flattened exact search of round 3 (what launch_nn_coop hands batches and sweeps): same arguments,
+// no Tprev and no runner-up state; wst_io holds the winners as points of the candidate array.
+hipError_t launch_nn_wave(const SearchArgs &a, const SearchGeom &geo, hipStream_t stream)
 {
-    if (!src64 || !sorted64 || !s12 || !prevq_io) return hipErrorInvalidValue;
-    if (point_to_plane) {
-        if (one) VISMA_WAVE_LAUNCH(nn_wave_kernel_one<true>); else VISMA_WAVE_LAUNCH(nn_wave_kernel_many<true>);
+    if (!a.src64 || !a.sorted64 || !a.sorted12 || !a.wst_io) return hipErrorInvalidValue;
+    const int warm = a.warm & (kWarmRead | kWarmMap | kWarmNoCert);
+    if (a.point_to_plane) {
+        if (geo.one) VISMA_WAVE_LAUNCH(nn_wave_kernel_one<true>); else VISMA_WAVE_LAUNCH(nn_wave_kernel_many<true>);
     } else {
-        if (one) VISMA_WAVE_LAUNCH(nn_wave_kernel_one<false>); else VISMA_WAVE_LAUNCH(nn_wave_kernel_many<false>);
+        if (geo.one) VISMA_WAVE_LAUNCH(nn_wave_kernel_one<false>); else VISMA_WAVE_LAUNCH(nn_wave_kernel_many<false>);
     }
     return hipGetLastError();
 }

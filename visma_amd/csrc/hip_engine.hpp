@@ -114,11 +114,6 @@ public:
     void *d_raw_ = nullptr;
     size_t raw_bytes_ = 0;
     void *d_sorted12_ = nullptr;                           // packed (x,y,z) copy of d_sorted_ for the exact search
-    const float4 *search_sorted() const                    // what launch_nn_grid_reduce gets as `sorted`
-    {
-        if (exact_ && d_src64_ && d_sorted64_ && d_sorted12_) return (const float4 *)d_sorted12_;
-        return (const float4 *)d_sorted_;
-    }
     int set_clouds64(const Pt64 *src, const Pt64 *tgt) override
     {
         HIP_TRY(hipSetDevice(device_));
@@ -502,8 +497,38 @@ private:
     int64_t view_offset_ = 0, loop_out_stride_ = 0;
     static constexpr int kGridMaxBlocks = 32768;   // (8 M queries at one per lane: the warm kernel keeps 4 waves per SIMD only there)
     double r2d_ = 0.0;
-    const Pt64 *f64_src() const { return d_sorted64_ ? (const Pt64 *)d_src64_ : nullptr; }
-    const Pt64 *f64_sorted() const { return d_src64_ ? (const Pt64 *)d_sorted64_ : nullptr; }
+    bool f64_views() const { return d_src64_ && d_sorted64_; }   // the grid search has source and target in f64
+    // What every search launch over the resident clouds shares: clouds, grid, ring table, normals, radii, the outputs and
+    // the per-query state.  The caller adds the pass: lanes, max_blocks, T64, off, point_to_plane, the problems
+    // (st, nprob, out_stride), fold, Tprev, persist, and changes what differs (warm, cand_count, d64_out, ru_io).
+    SearchArgs search_args() const
+    {
+        SearchArgs a;
+        a.ns = ns_;
+        a.src = (const float4 *)d_src_;
+        a.sorted = (const float4 *)d_sorted_;
+        if (f64_views()) {
+            a.src64 = (const Pt64 *)d_src64_;
+            a.sorted64 = (const Pt64 *)d_sorted64_;
+            a.sorted12 = (const float *)d_sorted12_;
+        }
+        a.start = (const unsigned *)d_start_;
+        a.g = grid_;
+        a.ring = ring_tab_;
+        a.nrm = (const float4 *)d_nrm_;
+        a.nrm64 = (const Pt64 *)d_nrm64_;
+        a.T32 = T32_;
+        a.r2f = r2f_;
+        a.r2d = r2d_;
+        a.exact = exact_ ? 1 : 0;
+        a.idx_out = (int32_t *)d_idx_;
+        a.d2_out = (float *)d_d2_;
+        a.partials = (double *)d_partials_;
+        a.wst_io = (Pt64 *)d_pos_;
+        a.ru_io = runner_up_ ? (Pt64 *)d_ru_ : nullptr;
+        a.warm = kWarmRead;
+        return a;
+    }
     int grid_sub_ = 1;         // row refinement the planner may use (VISMA_ICP_GRID_SUB=2: 25 half-pitch rows --
                                // 42 % fewer candidates at C4 but slower, 59 vs 51 us: more rows, 4x the table)
     int grid_blocks_env_ = 0;  // VISMA_ICP_GRID_BLOCKS override of the workgroup cap below
@@ -534,7 +559,6 @@ private:
     // VISMA_ICP_RUNNER_UP=1 (read when the context is created) with such a build
     void *d_ru_ = nullptr;
     int runner_up_ = 0;
-    Pt64 *ru_state() const { return runner_up_ ? (Pt64 *)d_ru_ : nullptr; }
     // the certificate of grid_coop.hip: the transform of the pass that left the state (host-driven passes over ONE
     // problem; device loops carry it in their DevIcpState and leave prev_T_valid_ false behind them)
     Xform64 prev_T_{};
@@ -627,9 +651,8 @@ private:
     }
     void *d_occ_ = nullptr, *d_ring_tab_ = nullptr;
     int ring_tab_rings_ = 0;
-    RingTable ring_tab_{nullptr, 0};         // what a ring pass gets beside grid_ (launch_nn_grid_reduce: `ring`)
+    RingTable ring_tab_{nullptr, 0};         // what a ring pass gets beside grid_ (SearchArgs::ring)
     static int nrows_of_rings(int rings) { return (2 * rings + 1) * (2 * rings + 1); }
-    const RingTable *ring_table() const { return grid_.ring > 0 ? &ring_tab_ : nullptr; }
     double grid_occupancy_ = 0.0;            // points per occupied cell of the radius-sized table (0 = not measured)
     int grid_lanes(int nprob = 1) const
     {
@@ -638,13 +661,13 @@ private:
         const int64_t q = ns_ * (int64_t)nprob;                  // queries of one launch
         // measured on MI355X: small clouds need the extra parallelism, large ones the locality
         // (lanes per query, loads in flight per lane), encoded G + 100*U
-        if (f64_src() && exact_)   // exact search (re-measured with the branch-free insertion: tools/lanes_probe.py,
+        if (f64_views() && exact_)   // exact search (re-measured with the branch-free insertion: tools/lanes_probe.py,
                                    // bench.py --workload c5: sweeps of ~200 k queries 801 309 k it/s, 402 295 k, 802 274 k)
             // single problems (also the source shards of 2 / 4 / 8 ranks against a 4 M-point target, tools/lanes_probe.py
             // 32768 / 65536 / 131072 x 4194304: 804 31.6 us vs 408 34.0; 802 34.0; 1201 41.5 vs 801 43.0, 802 47.6)
             return nprob > 1 ? (q <= 32768 ? 408 : (q <= 98304 ? 402 : 801))
                              : (q <= 32768 ? 804 : (q <= 98304 ? 802 : (q <= 196608 ? 1201 : 801)));
-        if (f64_src())   // 32-byte candidates: fewer in flight per lane (measured 5k: 408 15.8 us vs 804 18.1)
+        if (f64_views())   // 32-byte candidates: fewer in flight per lane (measured 5k: 408 15.8 us vs 804 18.1)
             return q <= 32768 ? 408 : (nprob > 1 ? 402 : (q <= 131072 ? 802 : 801));
         if (nprob > 1) return q <= 32768 ? 804 : 402;          // sweeps: many queries per launch
         return ns_ <= 32768 ? 804 : (ns_ <= 98304 ? 802 : 1201);
@@ -717,14 +740,6 @@ private:
         return a;
     }
 #endif
-    // workgroups per problem of launch_nn_grid_reduce (same arithmetic as the launcher)
-    static int grid_launch_blocks(int64_t ns, int lanes, int max_blocks)
-    {
-        const int G = lanes % 100;
-        int64_t want = (ns * G + kBlock - 1) / kBlock;
-        int nb = (int)(want > max_blocks ? max_blocks : want);
-        return nb < 1 ? 1 : nb;
-    }
     // fold arguments for `nprob` problems of `bpp` workgroups each (buffers grown as needed)
     void add_ipc(FoldArgs *fa)
     {

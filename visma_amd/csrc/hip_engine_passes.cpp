@@ -155,7 +155,7 @@ int HipEngine::reduce(const Mat4 &Tc, bool plane, const double offset[3], double
             }
         }
         if (!in_session) {
-            const int nb = grid_launch_blocks(ns_, lanes, grid_blocks());
+            const int nb = search_blocks(ns_, lanes, grid_blocks());
             PersistArgs pa{};
             const PersistArgs *pp = nullptr;
             if (loop_scope_ && loop_budget_ >= 2 && persist_possible(lanes, nb, fused, plane)) {
@@ -195,7 +195,7 @@ int HipEngine::reduce(const Mat4 &Tc, bool plane, const double offset[3], double
                 // passes after it run the certificate kernel -- queue their launch now, behind the cold pass, and let it wait
                 // for its first transform like for every later one.  (pass_lanes() speaks about the NEXT pass now: the cold
                 // launch left the per-query state behind.)
-                const int nb2 = grid_launch_blocks(ns_, kCoopLanes, grid_blocks());
+                const int nb2 = search_blocks(ns_, kCoopLanes, grid_blocks());
                 if (persist_possible(kCoopLanes, nb2, fused, plane)) {
                     const int budget = loop_budget_;
                     loop_budget_ = budget - 1;                       // (what the launch may run: the passes after this one)
@@ -336,12 +336,15 @@ int HipEngine::launch_grid_pass(const Xform64 &T64, bool plane, const double off
     // the fold of the partial rows runs inside the search launch (no second kernel)
     const bool fused = fused_fold_ && !tshard_;
     const int lanes = pass_lanes();
-    int nblocks = 1, e0 = -1;
-    FoldArgs fa{};
+    int e0 = -1;
+    SearchArgs a = search_args();
+    a.lanes = lanes;
+    a.max_blocks = grid_blocks();
+    const int nblocks = search_blocks(ns_, lanes, a.max_blocks);
+    FoldArgs &fa = a.fold;
     if (fused) {
         // (peer-to-peer mailboxes: the folding workgroup exchanges with the peers and publishes itself)
-        int rc = make_fold(grid_launch_blocks(ns_, lanes, grid_blocks()), 1, (double *)d_stats_, 0,
-                           ipc ? h_stats_dev_ : pub, seq, &fa);
+        int rc = make_fold(nblocks, 1, (double *)d_stats_, 0, ipc ? h_stats_dev_ : pub, seq, &fa);
         if (rc) return rc;
         if (ipc) { add_ipc(&fa); *ipc_done = true; }
         if (persist) {
@@ -352,7 +355,7 @@ int HipEngine::launch_grid_pass(const Xform64 &T64, bool plane, const double off
                 HIP_TRY(hipMalloc(&d_fold_tag_, (kRows + kGroups) * kRowBytes));
                 HIP_TRY(hipMemsetAsync(d_fold_tag_, 0, (kRows + kGroups) * kRowBytes, stream_));
             }
-            if ((size_t)grid_launch_blocks(ns_, lanes, grid_blocks()) > kRows) { err_ = "persistent launch larger than its fold rows"; return VISMA_ICP_ERR_STATE; }
+            if ((size_t)nblocks > kRows) { err_ = "persistent launch larger than its fold rows"; return VISMA_ICP_ERR_STATE; }
             // (the rows validate themselves with fold_row_tag(sequence number): when a session's numbers run through the
             //  tag's wrap, the buffer is cleared first -- a row of 2^32 - 1 passes ago must not validate)
             if (seq % kFoldTagPeriod + (unsigned long long)persist->max_passes >= kFoldTagPeriod)
@@ -364,15 +367,15 @@ int HipEngine::launch_grid_pass(const Xform64 &T64, bool plane, const double off
         }
     }
     if (prof) { e0 = next_event_pair(); HIP_TRY(hipEventRecord(ev_[e0], stream_)); }
-    HIP_TRY(launch_nn_grid_reduce((const float4 *)d_src_, ns_, search_sorted(),
-                                  (const unsigned *)d_start_, grid_, (const float4 *)d_nrm_,
-                                  T32_, T64, offset, r2f_, plane ? 1 : 0, (int32_t *)d_idx_,
-                                  (float *)d_d2_, (double *)d_partials_, grid_blocks(),
-                                  &nblocks, lanes,
-                                  prof ? (unsigned long long *)d_cand_ : nullptr, nullptr,
-                                  1, 0, stream_, f64_src(), f64_sorted(), r2d_, (const Pt64 *)d_nrm64_,
-                                  exact_ ? 1 : 0, fused ? &fa : nullptr, shard_d64(), (Pt64 *)d_pos_, 1 | (persist ? persist_prio_ << 5 : 0), cert_prev(), persist, ru_state(),
-                                  ring_table()));
+    a.T64 = T64;
+    for (int k = 0; k < 3; k++) a.off.v[k] = offset ? offset[k] : 0.0;
+    a.point_to_plane = plane ? 1 : 0;
+    a.cand_count = prof ? (unsigned long long *)d_cand_ : nullptr;
+    a.d64_out = shard_d64();
+    if (persist) a.warm |= persist_prio_ << kWarmPrioShift;
+    a.Tprev = cert_prev();
+    a.persist = persist;
+    HIP_TRY(launch_nn_grid_reduce(a, stream_));
     if (!early) {
         // (an early persistent launch has run nothing yet: what its first pass leaves is noted when that pass has been seen)
         last_kernel_ = pass_kernel(lanes);
@@ -541,14 +544,13 @@ int HipEngine::get_correspondences(int32_t *idx, float *d2)
     if (use_grid_ && grid_pending_) {
         // nn_pass without a reduction: run the fused kernel for its index output
         const Xform64 T64 = T64_last_;
-        int nblocks = 1;
-        HIP_TRY(launch_nn_grid_reduce((const float4 *)d_src_, ns_, search_sorted(),
-                                      (const unsigned *)d_start_, grid_, (const float4 *)d_nrm_,
-                                      T32_, T64, nullptr, r2f_, 0, (int32_t *)d_idx_,
-                                      (float *)d_d2_, (double *)d_partials_, reduce_max_blocks(),
-                                      &nblocks, (last_kernel_ = pass_kernel(pass_lanes()), pass_lanes()), nullptr, nullptr, 1, 0, stream_,
-                                      f64_src(), f64_sorted(), r2d_, (const Pt64 *)d_nrm64_, exact_ ? 1 : 0,
-                                      nullptr, nullptr, (Pt64 *)d_pos_, 1, cert_prev(), nullptr, ru_state(), ring_table()));
+        SearchArgs a = search_args();
+        a.lanes = pass_lanes();
+        a.max_blocks = reduce_max_blocks();
+        a.T64 = T64;
+        a.Tprev = cert_prev();
+        last_kernel_ = pass_kernel(a.lanes);
+        HIP_TRY(launch_nn_grid_reduce(a, stream_));
         pos_fresh_ = d_pos_ != nullptr;
         note_state_pass(T64);
         grid_pending_ = false;
@@ -669,7 +671,7 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
         if (done >= 1 && !sweep_tried && sweep_candidate && pass_lanes(nprob) == kCoopLanes && coop_ok() && device_ >= 0 && device_ < 64 &&
             !std::getenv("VISMA_ICP_COOP_KERNEL")) {
             sweep_tried = true;
-            const int nb = grid_launch_blocks(ns_, kCoopLanes, reduce_max_blocks());
+            const int nb = search_blocks(ns_, kCoopLanes, reduce_max_blocks());
             const int cap = nn_wave_sweep_capacity();
             int expect = 0;
             if ((int64_t)nb * kBlock >= ns_ && (int64_t)nb * nprob <= (int64_t)((double)cap * persist_cu_share()) &&
@@ -690,8 +692,13 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
                 }
                 unsigned long long *dead = (unsigned long long *)d_sweep_relay_ + 32 * (size_t)sweep_relay_cap_;
                 HIP_TRY(hipMemsetAsync(dead, 0, sizeof(unsigned long long), stream_));
-                FoldArgs fa{};
-                rc = make_fold(nb, nprob, st->stats, (long long)(sizeof(DevIcpState) / sizeof(double)), nullptr, 0, &fa);
+                SearchArgs a = search_args();
+                a.max_blocks = reduce_max_blocks();            // (nb workgroups per problem)
+                a.st = st;
+                a.nprob = nprob;
+                a.out_stride = loop_out_stride_;
+                a.cand_count = profiling_ ? (unsigned long long *)d_cand_ : nullptr;
+                rc = make_fold(nb, nprob, st->stats, (long long)(sizeof(DevIcpState) / sizeof(double)), nullptr, 0, &a.fold);
                 if (rc) return rc;
                 SweepArgs sa{};
                 sa.relay = (unsigned long long *)d_sweep_relay_;
@@ -703,10 +710,7 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
                 sweep_tag_ += (unsigned)rem + 1u;
                 int e0 = -1;
                 if (profiling_) { e0 = next_event_pair(); HIP_TRY(hipEventRecord(ev_[e0], stream_)); }
-                HIP_TRY(launch_nn_wave_sweep(nb, nprob, (int)ns_, (const float *)d_sorted12_, (const unsigned *)d_start_, grid_, r2f_,
-                                             (int32_t *)d_idx_, (float *)d_d2_, (double *)d_partials_,
-                                             profiling_ ? (unsigned long long *)d_cand_ : nullptr, st, loop_out_stride_,
-                                             (const Pt64 *)d_src64_, (const Pt64 *)d_sorted64_, fa, (Pt64 *)d_pos_, sa, stream_));
+                HIP_TRY(launch_nn_wave_sweep(a, sa, stream_));
                 if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 0}); }
                 last_kernel_ = 2;
                 pos_fresh_ = d_pos_ != nullptr;
@@ -736,12 +740,15 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
             bool fused = false, solved_in_fold = false;
             if (use_grid_) {
                 // fold inside the search launch: the statistics land in the problems' device state
-                FoldArgs fa{};
+                SearchArgs a = search_args();
+                FoldArgs &fa = a.fold;
                 fused = fused_fold_ != 0 && !tshard_;       // (target shards fold after their exchange)
                 const int lanes = pass_lanes(nprob);
+                a.lanes = lanes;
+                a.max_blocks = reduce_max_blocks();
+                nblocks = search_blocks(ns_, lanes, a.max_blocks);
                 if (fused) {
-                    rc = make_fold(grid_launch_blocks(ns_, lanes, reduce_max_blocks()), nprob,
-                                   st->stats, (long long)(sizeof(DevIcpState) / sizeof(double)), nullptr, 0, &fa);
+                    rc = make_fold(nblocks, nprob, st->stats, (long long)(sizeof(DevIcpState) / sizeof(double)), nullptr, 0, &fa);
                     if (rc) return rc;
                     if (ipc_n_ > 1) add_ipc(&fa);      // (one problem per rank: ipc needs nprob == 1)
                     // closed-form update on one GPU: the workgroup that completes a problem's fold advances its state
@@ -749,16 +756,16 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
                     if (solve_in_fold(lp, lanes, nprob)) fa.solve = st;
                 }
                 solved_in_fold = fused && fa.solve != nullptr;
-                HIP_TRY(launch_nn_grid_reduce((const float4 *)d_src_, ns_, search_sorted(),
-                                              (const unsigned *)d_start_, grid_, (const float4 *)d_nrm_,
-                                              T32_, T64, nullptr, r2f_, plane, (int32_t *)d_idx_,
-                                              (float *)d_d2_, (double *)d_partials_,
-                                              reduce_max_blocks(), &nblocks, lanes,
-                                              profiling_ ? (unsigned long long *)d_cand_ : nullptr, st,
-                                              nprob, loop_out_stride_, stream_, f64_src(), f64_sorted(), r2d_, (const Pt64 *)d_nrm64_,
-                                              exact_ ? 1 : 0, fused ? &fa : nullptr, tshard_ ? shard_d64() : nullptr,
-                                              (Pt64 *)d_pos_, cert_enabled_ ? 1 : (1 | 8), nullptr, nullptr, nprob == 1 ? ru_state() : nullptr,
-                                              ring_table()));
+                a.T64 = T64;                             // (ignored: the kernels read the transform from the state)
+                a.point_to_plane = plane;
+                a.cand_count = profiling_ ? (unsigned long long *)d_cand_ : nullptr;
+                a.st = st;
+                a.nprob = nprob;
+                a.out_stride = loop_out_stride_;
+                a.d64_out = tshard_ ? shard_d64() : nullptr;
+                if (!cert_enabled_) a.warm |= kWarmNoCert;
+                if (nprob != 1) a.ru_io = nullptr;
+                HIP_TRY(launch_nn_grid_reduce(a, stream_));
                 last_kernel_ = pass_kernel(lanes);
                 pos_fresh_ = d_pos_ != nullptr;
                 prev_T_valid_ = false;                   // (the state's pose now lives in the device loop's state)
@@ -1076,7 +1083,8 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
     if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 2}); }
     // ---- the loop: one NN launch (search + fold) + one solve launch per pass for ALL problems
     DevIcpState *st = (DevIcpState *)d_state_;
-    FoldArgs bfa{};
+    SearchArgs ba;
+    FoldArgs &bfa = ba.fold;
     if (fused_fold_) {
         int max_nb = 1;
         for (int b = 0; b < B; b++) max_nb = std::max(max_nb, descs[b].nblocks);
@@ -1096,21 +1104,32 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
     const bool coop = coop_enabled_ && packed && std::getenv("VISMA_ICP_BATCH_LANES") == nullptr &&
                       (tgt_tot + kSortedSlack) * 12 < (1ll << 32);
     bool fresh = false;
+    // (its own buffers: the problems' clouds concatenated; grids, radii and transforms live in the descriptors and states)
+    ba.src = (const float4 *)bt_src_;
+    ba.sorted = (const float4 *)bt_sorted_;
+    ba.sorted12 = packed ? (const float *)bt_sorted12_ : nullptr;
+    if (f64) { ba.src64 = (const Pt64 *)bt_src64_; ba.sorted64 = (const Pt64 *)bt_sorted64_; }
+    ba.start = (const unsigned *)bt_start_;
+    if (lp.plane && f64) ba.nrm64 = (const Pt64 *)bt_nrm64_; else if (lp.plane) ba.nrm = (const float4 *)bt_nrm_;
+    ba.descs = (const ProbDesc *)bt_descs_;
+    ba.nprob = B;
+    ba.total_blocks = total_blocks;
+    ba.one_per_lane = one_per_lane ? 1 : 0;
+    ba.point_to_plane = (ba.nrm || ba.nrm64) ? 1 : 0;
+    ba.exact = exact_ ? 1 : 0;
+    ba.st = st;
+    ba.idx_out = (int32_t *)bt_idx_;
+    ba.d2_out = (float *)bt_d2_;
+    ba.partials = (double *)d_partials_;
+    ba.cand_count = profiling_ ? (unsigned long long *)d_cand_ : nullptr;
+    ba.wst_io = (Pt64 *)bt_pos_;
+    ba.warm = kWarmRead | kWarmMap | (cert_enabled_ ? 0 : kWarmNoCert);   // (the workgroup map follows the descriptors)
     while (done < lp.passes) {
         const int n = std::min(chunk, lp.passes - done);
         for (int j = 0; j < n; j++) {
             if (profiling_) { e0 = next_event_pair(); HIP_TRY(hipEventRecord(ev_[e0], stream_)); }
-            HIP_TRY(launch_nn_grid_reduce_batch((const float4 *)bt_src_, packed ? (const float4 *)bt_sorted12_ : (const float4 *)bt_sorted_,
-                                                (const unsigned *)bt_start_, (const ProbDesc *)bt_descs_, B,
-                                                total_blocks, (int32_t *)bt_idx_, (float *)bt_d2_,
-                                                (double *)d_partials_, (coop && fresh) ? kCoopLanes : lanes, one_per_lane ? 1 : 0, st, stream_,
-                                                f64 ? (const Pt64 *)bt_src64_ : nullptr,
-                                                f64 ? (const Pt64 *)bt_sorted64_ : nullptr, exact_ ? 1 : 0,
-                                                fused_fold_ ? &bfa : nullptr,
-                                                profiling_ ? (unsigned long long *)d_cand_ : nullptr,
-                                                (lp.plane && !f64) ? (const float4 *)bt_nrm_ : nullptr,
-                                                (lp.plane && f64) ? (const Pt64 *)bt_nrm64_ : nullptr,
-                                                (Pt64 *)bt_pos_, cert_enabled_ ? (1 | 2) : (1 | 2 | 8)));   // warm | workgroup map behind the descriptors
+            ba.lanes = (coop && fresh) ? kCoopLanes : lanes;
+            HIP_TRY(launch_nn_grid_reduce(ba, stream_));
             last_kernel_ = (coop && fresh) ? 2 : 1;
             fresh = true;
             if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 0}); }

@@ -402,40 +402,22 @@ hipError_t launch_grid_build(const float4 *tgt, int64_t nt, const GridParams &g,
                              unsigned *cell_of, unsigned *count, unsigned *bsum,
                              unsigned *start, float4 *sorted, hipStream_t stream,
                              const Pt64 *tgt64 = nullptr, Pt64 *sorted64 = nullptr);
-// fused transform + grid NN + Jacobian/residual + reduction to partial rows
-// (launch_finalize folds them); also writes idx_out / d2_out.
-hipError_t launch_nn_grid_reduce(const float4 *src, int64_t ns, const float4 *sorted,
-                                 const unsigned *start, const GridParams &g,
-                                 const float4 *tgt_normals, const Xform32 &T32, const Xform64 &T64,
-                                 const double frame_offset[3], float r2f, int point_to_plane,
-                                 int32_t *idx_out, float *d2_out, double *partials,
-                                 int max_partial_blocks, int *nblocks_out, int lanes_per_query,
-                                 unsigned long long *cand_count, const DevIcpState *st,
-                                 int nprob, int64_t out_stride, hipStream_t stream,
-                                 const Pt64 *src64 = nullptr, const Pt64 *sorted64 = nullptr,
-                                 double r2d = 0.0, const Pt64 *nrm64 = nullptr, int exact = 0,
-                                 const FoldArgs *fold = nullptr, double *d64_out = nullptr,
-                                 Pt64 *wst_io = nullptr, int warm = 0, const Xform64 *Tprev = nullptr,
-                                 const PersistArgs *persist = nullptr, Pt64 *ru_io = nullptr,
-                                 const RingTable *ring = nullptr);
-// ring: the visiting order of a grid with g.ring > 0 (grid_ring.hip).
-// persist: run the launch as the persistent certificate kernel (one problem, one query per lane, fused fold with
-// host publication; hipErrorInvalidValue where that does not apply -- ask coop_persist_capacity first).
-// wst_io (one Pt64 per query, laid out like idx_out): the exact searches leave their winners there (f64 point,
-// original index | LB << 32 -- see grid_coop.hip; NaN coordinates = none, all bits set = nothing known); the
-// warm-started search (kCoopLanes) reads them when `warm & 1`, and with Tprev (the transform of the pass that left
-// them; device loops: from their DevIcpState) skips the search of queries whose winner provably cannot have changed.
-// The exact search with the candidates of a wave flattened over its lanes (grid_coop.hip); selected by
-// lanes_per_query = kCoopLanes (G = 1, U = 99) in the two launchers around it, which fall back to the
-// lane-serial kernel where it does not apply (fp32-only / all-f64 search, half-pitch rows).
+// ---- the grid searches (grid.hip, grid_coop.hip, grid_wave.hip, grid_ring.hip) -----------------------------------
+// fused transform + grid NN + Jacobian/residual + reduction to partial rows (launch_finalize folds them, or the
+// launch itself: SearchArgs::fold); also writes idx_out / d2_out.
+// The exact search with the candidates of a wave flattened over its lanes (grid_coop.hip; grid_wave.hip: round 3's
+// kernel behind the same code, for batches and sweeps): the lanes code G = 1, U = 99.  launch_nn_grid_reduce falls back
+// to the lane-serial kernel (1, 8) where it does not apply (fp32-only / all-f64 search, half-pitch rows, no wst_io).
 constexpr int kCoopLanes = 9901;
-// (grid_wave.hip: round 3's kernel behind the same lanes code -- launch_nn_coop hands batches and sweeps to it)
-hipError_t launch_nn_wave(int total_blocks, int bpp, int nprob, const ProbDesc *descs, int ns, const float *s12,
-                          const unsigned *start, const GridParams &g, const float4 *nrm, const Pt64 *nrm64,
-                          const Xform64 &T64, const Offset64 &off, float r2f, int point_to_plane, int one,
-                          int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                          const DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                          const FoldArgs &fold, double *d64_out, Pt64 *prevq_io, int warm, hipStream_t stream);
+// The bits of SearchArgs::warm -- a kernel argument of the flattened searches: the values are fixed.
+enum : int {
+    kWarmRead = 1,       // wst_io holds the winners of the previous pass over the SAME source order and target: start from them
+    kWarmMap = 2,        // batches: a workgroup -> problem map (one int per workgroup) follows descs[nprob]
+    kWarmTprev = 4,      // Tprev is valid (launch_nn_coop sets / clears it from SearchArgs::Tprev, device loops from
+                         // DevIcpState::have_prev): queries whose winner provably cannot have changed skip the search
+    kWarmNoCert = 8,     // certificates switched off (VISMA_ICP_CERT=0, A/B timing) -- the wave kernel's no-partner one too
+    kWarmPrioShift = 5, kWarmPrioMask = 3   // bits 5-6: VISMA_ICP_PERSIST_PRIO 1 / 2 of a persistent launch (experiment)
+};
 // The persistent form of the batch / sweep search over SHARED clouds (grid_wave.hip, round 6): ONE launch runs up to
 // max_passes warm passes of nprob problems of bpp workgroups each -- search, fold, closed-form update, compose and stop
 // test inside the launch (fused_fold<..., LOOPED, SOLVE>), the next transform handed to the problem's workgroups through
@@ -450,15 +432,85 @@ struct SweepArgs {
     int passes0;               // DevIcpState::passes of every problem when the launch begins (its first pass makes it passes0 + 1)
     long long wait_ticks;      // how long a workgroup waits for its problem's next transform (100 MHz ticks)
 };
-// ---- the ring search over cells smaller than the radius (grid_ring.hip; g.ring > 0): `nblocks` workgroups per problem,
-// eight lanes per query; s12 (the packed fp32 copy of sorted64, 12 bytes per point) or NULL: candidates ranked in fp32 with
-// the f64 re-rank of the rounding band, or in f64 throughout -- same results.  state_io: per query the winner's f64 point and original index (all bits
-// set = none), read when `warm`, always written.
-hipError_t launch_nn_ring(int lanes, int nblocks, int nprob, int ns, const Pt64 *src64, const Pt64 *sorted64, const float *s12, const unsigned *start,
-                          const GridParams &g, const RingTable &tab, const float4 *nrm, const Pt64 *nrm64, const Xform64 &T64, const Offset64 &off,
-                          float r2f, int point_to_plane, int32_t *idx_out, float *d2_out, double *d64_out, Pt64 *state_io,
-                          int warm, double *partials, unsigned long long *cand_count, const DevIcpState *st,
-                          long long out_stride, const FoldArgs &fold, hipStream_t stream);
+
+// What a search launch is given (host side only: the launchers spread it over the kernels' own argument lists).
+// Shared clouds (descs == NULL): nprob problems search the same source against the same target.  Batches (descs):
+// every problem has its own clouds at offsets into concatenated arrays, its grid in descs[] and its transform, frame
+// offset and radius in st[] -- ns, g, ring, T32, T64, off, r2f, r2d, max_blocks, out_stride, d64_out stay as they are here.
+struct SearchArgs {
+    // ---- source
+    int64_t ns = 0;
+    const float4 *src = nullptr;
+    const Pt64 *src64 = nullptr;           // f64 views of source and target: both or neither (fp32-only search)
+    // ---- target
+    const float4 *sorted = nullptr;        // cell-sorted, w = original index: the fp32-only and the all-f64 search
+    const float *sorted12 = nullptr;       // ... its packed copy, 12 bytes per point: what the exact search ranks on
+    const Pt64 *sorted64 = nullptr;
+    const unsigned *start = nullptr;       // cell table
+    GridParams g{};
+    RingTable ring{nullptr, 0};            // the visiting order of a grid with g.ring > 0 (grid_ring.hip)
+    const float4 *nrm = nullptr;           // target normals by ORIGINAL index (batches: concatenated like the unsorted
+    const Pt64 *nrm64 = nullptr;           // targets) -> the point-to-plane estimator
+    // ---- problems
+    const ProbDesc *descs = nullptr;       // device: every problem's offsets / grid / workgroup range
+    int nprob = 1;
+    int max_blocks = 1;                    // shared clouds: cap of the workgroups per problem (search_blocks)
+    int total_blocks = 0;                  // batches: sum of descs[].nblocks
+    int one_per_lane = 0;                  // batches: no problem has more than G queries per lane group
+    int64_t out_stride = 0;                // shared clouds: problem b writes idx_out / d2_out / wst_io at b * out_stride
+    // ---- the pass
+    Xform32 T32{};
+    Xform64 T64{};
+    Offset64 off{};
+    float r2f = 0.f;
+    double r2d = 0.0;
+    int point_to_plane = 0;
+    int exact = 0;                         // with the f64 views: fp32 ranking + f64 re-rank (1) or f64 throughout (0)
+    int lanes = 0;                         // lanes code G + 100 U (lanes per query, loads in flight per lane), or kCoopLanes
+    DevIcpState *st = nullptr;             // device loops: the problems' states (transform, radius, frame offset from there)
+    int warm = 0;                          // kWarm* bits
+    const Xform64 *Tprev = nullptr;        // the transform of the pass that left wst_io (host-driven passes; see kWarmTprev)
+    FoldArgs fold{};                       // fold.tickets == NULL: the partial rows are folded by a separate launch
+    const PersistArgs *persist = nullptr;  // run the launch as the persistent certificate kernel: one problem, one query
+                                           // per lane, fused fold with host publication; hipErrorInvalidValue where that
+                                           // does not apply -- ask coop_persist_capacity first
+    // ---- outputs and per-query state
+    int32_t *idx_out = nullptr;
+    float *d2_out = nullptr;
+    double *d64_out = nullptr;             // f64 squared distances (target-sharded ranks compare shards in f64), or NULL
+    double *partials = nullptr;            // one row of kReduceAcc per workgroup
+    unsigned long long *cand_count = nullptr;   // profiling counters, or NULL
+    Pt64 *wst_io = nullptr;                // one per query, laid out like idx_out: the exact searches leave their winners
+                                           // there (f64 point, original index | LB << 32 -- grid_coop.hip; NaN coordinates =
+                                           // none, all bits set = nothing known); read when warm & kWarmRead
+    Pt64 *ru_io = nullptr;                 // the runner-up half of that state (-DVISMA_COOP_RU=1 builds), or NULL
+
+    // which candidate array the kernels read: sorted12 (true) or sorted
+    bool packed() const { return src64 != nullptr && exact != 0; }
+};
+// workgroups per problem of a pass over shared clouds: one lane group of G = lanes % 100 per query up to the cap
+inline int search_blocks(int64_t ns, int lanes, int max_blocks)
+{
+    const int64_t want = (ns * (lanes % 100) + kBlock - 1) / kBlock;
+    const int nb = (int)(want > max_blocks ? max_blocks : want);
+    return nb < 1 ? 1 : nb;
+}
+// the geometry launch_nn_grid_reduce hands to the launchers behind it
+struct SearchGeom {
+    int total_blocks, bpp;                 // workgroups of the launch / per problem (batches: 1)
+    int one;                               // at most one query per lane
+};
+// Every kind of pass: the ring search (g.ring > 0), the flattened exact search (lanes == kCoopLanes) or the lane-serial
+// kernel of the (G, U) pairs the policies use; shared clouds run nprob * search_blocks(ns, lanes, max_blocks) workgroups.
+hipError_t launch_nn_grid_reduce(const SearchArgs &a, hipStream_t stream);
+hipError_t launch_nn_coop(const SearchArgs &a, const SearchGeom &geo, hipStream_t stream);
+hipError_t launch_nn_wave(const SearchArgs &a, const SearchGeom &geo, hipStream_t stream);
+// the ring search over cells smaller than the radius: a.lanes % 100 = 1, 2, 4, 8 lanes per query, `nblocks` workgroups
+// per problem; candidates ranked in fp32 on sorted12 with the f64 re-rank of the rounding band (a.packed()), or in f64
+// throughout -- same results.  wst_io is always written.
+hipError_t launch_nn_ring(const SearchArgs &a, int nblocks, hipStream_t stream);
+// the persistent sweep: nprob problems of search_blocks(ns, kCoopLanes, max_blocks) workgroups, one query per lane
+hipError_t launch_nn_wave_sweep(const SearchArgs &a, const SweepArgs &sa, hipStream_t stream);
 // the visiting order of a grid with g.ring = rings (a new device buffer the caller owns: hipFree); *nrows = (2 rings + 1)^2
 hipError_t build_ring_table(int rings, void **d_tab, int *nrows);
 // ... the same order on the host (empty for rings outside 1 .. kRingMaxRings)
@@ -466,32 +518,8 @@ std::vector<RingRow> ring_visiting_order(int rings);
 // *out (device, zeroed by the caller) += the number of non-zero entries of count[0 .. n)
 hipError_t launch_count_occupied(const unsigned *count, int64_t n, unsigned long long *out, hipStream_t stream);
 int nn_wave_sweep_capacity();
-hipError_t launch_nn_wave_sweep(int bpp, int nprob, int ns, const float *s12, const unsigned *start, const GridParams &g,
-                                float r2f, int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                                DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                                const FoldArgs &fold, Pt64 *prevq_io, const SweepArgs &sa, hipStream_t stream);
-
-hipError_t launch_nn_coop(int total_blocks, int bpp, int nprob, const ProbDesc *descs, int ns, const float *s12,
-                          const unsigned *start, const GridParams &g, const float4 *nrm, const Pt64 *nrm64,
-                          const Xform64 &T64, const Offset64 &off, float r2f, int point_to_plane, int one,
-                          int32_t *idx_out, float *d2_out, double *partials, unsigned long long *cand_count,
-                          const DevIcpState *st, long long out_stride, const Pt64 *src64, const Pt64 *sorted64,
-                          const FoldArgs &fold, double *d64_out, Pt64 *wst_io, int warm, hipStream_t stream,
-                          const Xform64 *Tprev = nullptr, const PersistArgs *persist = nullptr, Pt64 *ru_io = nullptr);
 // workgroups of the persistent kernel the current device holds at once (0: none -- do not launch it)
 int coop_persist_capacity(int point_to_plane);
-// Batch of problems with different clouds: `descs` (device) gives every problem's
-// offsets / grid / workgroup range; total_blocks = sum of descs[].nblocks.
-hipError_t launch_nn_grid_reduce_batch(const float4 *src, const float4 *sorted, const unsigned *start,
-                                       const ProbDesc *descs, int nprob, int total_blocks,
-                                       int32_t *idx_out, float *d2_out, double *partials,
-                                       int lanes_per_query, int one_per_lane, const DevIcpState *st,
-                                       hipStream_t stream, const Pt64 *src64 = nullptr,
-                                       const Pt64 *sorted64 = nullptr, int exact = 0,
-                                       const FoldArgs *fold = nullptr, unsigned long long *cand_count = nullptr,
-                                       const float4 *nrm = nullptr, const Pt64 *nrm64 = nullptr,
-                                       Pt64 *wst_io = nullptr, int warm = 0);
-// (nrm / nrm64: target normals concatenated like the UNSORTED targets -> the point-to-plane estimator)
 hipError_t launch_finalize_solve_batch(const double *partials, const ProbDesc *descs, DevIcpState *st,
                                        int nprob, hipStream_t stream, int plane = 0);
 
