@@ -309,6 +309,57 @@ VISMA_ICP_API int visma_icp_run_yaw_sweep(visma_icp_ctx *ctx, int level, double 
                                           visma_icp_result *best, int *best_level,
                                           visma_icp_result *per_level);
 
+/* ---- trimmed ICP (Chetverikov, Svirko, Stepanov, Krsek: "The Trimmed Iterative Closest Point Algorithm",
+ * ICPR 2002): of the K pairs a pass finds inside the radius only the m with the smallest distance enter the solve.
+ * For a model registered against a PARTIAL scan: model points whose surface the scan never saw still find
+ * partners inside the radius (the rim of the scanned part, the floor); those are the longest pairs of the pass.
+ *
+ *   keep in (0, 1]: the share of the SOURCE cloud expected to have a true partner (the paper's overlap).
+ *   m = min(K, floor(keep * NS)), NS the number of source points; below 3, m = min(K, 3).  keep = 1: m = K.
+ *   Kept are the m pairs with the smallest key (d2, source index): d2 the fp32 squared distance that
+ *   visma_icp_get_correspondences reports for the pair -- in every search precision --, the caller's source
+ *   index breaking exact ties.  The kept set is unique and does not depend on the order of execution.
+ *
+ * A keep BELOW the true overlap stalls the registration (the shortest pairs are the ones that are aligned
+ * already): on a full-overlap pair keep = 0.5 ends at 5.9e-2 relative error after 60 iterations where the
+ * plain run reaches 8e-4.  With keep at the overlap a radius several times the default becomes usable.
+ *
+ * The estimator is point-to-point: SOLVER_KABSCH with or without scaling, or, on a context with
+ * visma_icp_set_rotation_axis, the axis-constrained closed form.  The Gauss-Newton point-to-point solvers and
+ * point-to-plane are not offered trimmed (VISMA_ICP_ERR_INVALID).  Sharded contexts (comm_init, comm_ipc_init,
+ * set_allreduce with more than one rank, set_target_shard): VISMA_ICP_ERR_INVALID -- an order statistic across
+ * ranks does not exist yet. */
+typedef struct {
+    int64_t kept;          /* m */
+    double trimmed_rmse;   /* sqrt(sum of |p - q|^2 over the kept pairs / m); 0 when m = 0 */
+    double d2_cut;         /* the largest kept fp32 squared distance; 0 when m = 0 */
+} visma_icp_trim_info;
+
+/* The statistics of the last visma_icp_nn_pass over the kept pairs only (same layout and centred frame as
+ * visma_icp_reduce: out_stats[0] = m, out_stats[1] = the sum of |p - q|^2 over them, ...). */
+VISMA_ICP_API int visma_icp_reduce_trimmed(visma_icp_ctx *ctx, double keep, double out_stats[VISMA_ICP_NSTATS],
+                                           visma_icp_trim_info *info);
+/* RegistrationICP's loop (Registration.cpp:167-185) with the trimmed pass in place of the plain one.  Its stop
+ * test compares fitness and TRIMMED rmse (the objective this loop minimises) of consecutive passes.
+ * out->num_correspondences = K, out->fitness = K / NS and out->inlier_rmse (over all K) are the untrimmed values
+ * of the last pass (callers pick yaw winners by them); what the trimming did is in *info (may be NULL).
+ * One launch sequence per pass (search, select, masked reduction); never the persistent launch.  keep = 1 is
+ * visma_icp_run, bit for bit. */
+VISMA_ICP_API int visma_icp_run_trimmed(visma_icp_ctx *ctx, const double init[16], double max_dist, double keep,
+                                        int max_iter, double rel_fitness, double rel_rmse, int solver,
+                                        int with_scaling, visma_icp_result *out, visma_icp_trim_info *info);
+/* visma_icp_run_yaw_sweep with every start a trimmed run (one after the other); the winner is the first start
+ * with strictly the most correspondences K.  per_level / per_level_info / best_info may be NULL.  Afterwards the
+ * context holds the last pass of the LAST start (get_correspondences, get_kept_mask). */
+VISMA_ICP_API int visma_icp_run_yaw_sweep_trimmed(visma_icp_ctx *ctx, int level, double max_dist, double keep,
+                                                  int max_iter, double rel_fitness, double rel_rmse, int solver,
+                                                  visma_icp_result *best, int *best_level,
+                                                  visma_icp_result *per_level, visma_icp_trim_info *best_info,
+                                                  visma_icp_trim_info *per_level_info);
+/* kept_per_src[i] = 1 iff source point i (caller's order, NS entries) was kept by the last trimmed pass.
+ * visma_icp_get_correspondences keeps returning all K pairs. */
+VISMA_ICP_API int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src);
+
 /* ---- batched small problems (AnnotationTool loop, src/annotation.cpp:103-168) */
 
 typedef struct {

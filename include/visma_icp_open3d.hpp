@@ -12,6 +12,10 @@
 //   open3d::cicp::EvaluateRegistration (Registration.h:96-99)
 //   open3d::cicp::RegisterModelToScene feh::RegisterModelToScene
 //                                      (include/tool.h:40-42, src/annotation.cpp:29-64)
+//                                      (keep < 1: trimmed ICP from every start)
+//   open3d::cicp::TransformationEstimationPointToPointTrimmed(keep)
+//                                      trimmed ICP through RegistrationICP: only the keep * |source| closest pairs
+//                                      of every iteration enter the solve (a model against a partial scan)
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -95,6 +99,30 @@ public:
                                                  const PointCloud &target,
                                                  const CorrespondenceSet &corres) const override;
     Eigen::Vector3d up_;
+};
+
+// Trimmed ICP (Chetverikov et al., ICPR 2002): per iteration only the floor(keep * |source|) pairs with the smallest
+// distance enter the closed-form solve (visma_icp_run_trimmed; visma_icp.h states the rule).  keep = the share of the
+// SOURCE the target can see; with it a radius several times the usual one becomes usable on a partial scan; a keep
+// below the true overlap stalls.  What cicp::RegistrationICP returns for it:
+//   correspondence_set_  the KEPT pairs of the last pass, sorted by source index (what a later solve should get)
+//   fitness_             K / |source| over ALL pairs inside the radius (callers pick yaw winners by it)
+//   inlier_rmse_         the TRIMMED rmse: over the kept pairs (the objective the loop minimises)
+// ComputeTransformation(source, target, corres) solves over the corres it is given, like the other estimators.
+class TransformationEstimationPointToPointTrimmed : public TransformationEstimation {
+public:
+    explicit TransformationEstimationPointToPointTrimmed(double keep = 1.0) : keep_(keep) {}
+    ~TransformationEstimationPointToPointTrimmed() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPoint;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    double keep_ = 1.0;
 };
 
 namespace detail {
@@ -185,6 +213,27 @@ inline void fill_result(visma_icp_ctx *ctx, const visma_icp_result &r, size_t ns
           "visma_icp_get_correspondences");
     out.correspondence_set_.resize((size_t)k);
     for (int64_t i = 0; i < k; i++) out.correspondence_set_[i] = Eigen::Vector2i(si[i], ti[i]);
+}
+
+// ... of a trimmed run: the KEPT pairs (sorted by source index), fitness over all K, the trimmed rmse
+template <typename Result>
+inline void fill_result_trimmed(visma_icp_ctx *ctx, const visma_icp_result &r, const visma_icp_trim_info &info, size_t ns,
+                                Result &out)
+{
+    out.transformation_ = from_rowmajor(r.transformation);
+    out.fitness_ = r.fitness;
+    out.inlier_rmse_ = info.trimmed_rmse;
+    out.correspondence_set_.clear();
+    if (r.num_correspondences <= 0) return;
+    std::vector<int32_t> si(ns ? ns : 1), ti(ns ? ns : 1);
+    std::vector<uint8_t> kept(ns ? ns : 1);
+    int64_t k = 0;
+    check(ctx, visma_icp_get_correspondences(ctx, si.data(), ti.data(), nullptr, &k),
+          "visma_icp_get_correspondences");
+    check(ctx, visma_icp_get_kept_mask(ctx, kept.data()), "visma_icp_get_kept_mask");
+    out.correspondence_set_.reserve((size_t)info.kept);
+    for (int64_t i = 0; i < k; i++)
+        if (kept[(size_t)si[i]]) out.correspondence_set_.push_back(Eigen::Vector2i(si[i], ti[i]));
 }
 
 // 38 statistics of explicit correspondences, accumulated on the host in f64
@@ -369,6 +418,20 @@ inline RegistrationResult RegistrationICP(
         detail::fill_result(ctx, r, source.points_.size(), result);
         return result;
     }
+    if (dyn == typeid(TransformationEstimationPointToPointTrimmed)) {
+        const auto *trim = static_cast<const TransformationEstimationPointToPointTrimmed *>(&estimation);
+        if (!(trim->keep_ > 0.0 && trim->keep_ <= 1.0)) {
+            std::fprintf(stderr, "Error: TransformationEstimationPointToPointTrimmed requires keep in (0, 1].\n");
+            return RegistrationResult(init);
+        }
+        visma_icp_trim_info info;
+        detail::check(ctx, visma_icp_run_trimmed(ctx, T, max_correspondence_distance, trim->keep_, criteria.max_iteration_,
+                                                 criteria.relative_fitness_, criteria.relative_rmse_,
+                                                 VISMA_ICP_SOLVER_KABSCH, 0, &r, &info),
+                      "visma_icp_run_trimmed");
+        detail::fill_result_trimmed(ctx, r, info, source.points_.size(), result);
+        return result;
+    }
     if (four || p2p) {
         const bool scaling = four ? four->with_scaling_ : p2p->with_scaling_;
         detail::check(ctx, visma_icp_run(ctx, T, max_correspondence_distance, criteria.max_iteration_,
@@ -423,10 +486,42 @@ inline Eigen::Matrix4d RegisterModelToScene(const PointCloud &model, const Point
                                             int rotation_level, double distance_threshold,
                                             bool point_to_plane = false,
                                             RegistrationResult *best_out = nullptr,
-                                            bool upright = false)
+                                            bool upright = false, double keep = 1.0)
 {
     RegistrationResult best;
     const Eigen::Vector3d up = Eigen::Vector3d::UnitY();
+    if (keep != 1.0 && !(keep > 0.0 && keep < 1.0)) {
+        std::fprintf(stderr, "Error: RegisterModelToScene requires keep in (0, 1].\n");
+        return best.transformation_;
+    }
+    if (keep != 1.0 && point_to_plane) std::fprintf(stderr, "Warning: keep applies to the point-to-point estimator only; ignored.\n");
+    if (keep != 1.0 && !point_to_plane && rotation_level > 0 && distance_threshold > 0.0) {
+        // trimmed ICP from every start (keep: the share of the model the scan can see), the winner by K as always;
+        // *best_out: TransformationEstimationPointToPointTrimmed's result of the winning start
+        visma_icp_ctx *ctx = detail::upload(model, scene, false, distance_threshold);
+        detail::AxisScope axis(ctx, upright ? &up : nullptr);
+        const ICPConvergenceCriteria c;
+        visma_icp_result b;
+        visma_icp_trim_info bi;
+        int level = -1;
+        detail::check(ctx, visma_icp_run_yaw_sweep_trimmed(ctx, rotation_level, distance_threshold, keep, c.max_iteration_,
+                                                           c.relative_fitness_, c.relative_rmse_, VISMA_ICP_SOLVER_KABSCH,
+                                                           &b, &level, nullptr, &bi, nullptr),
+                      "visma_icp_run_yaw_sweep_trimmed");
+        best.transformation_ = detail::from_rowmajor(b.transformation);
+        if (best_out) {
+            *best_out = best;
+            if (level >= 0) {
+                // one trimmed pass at the winning transform materialises its kept pairs
+                visma_icp_result r;
+                visma_icp_trim_info ri;
+                detail::check(ctx, visma_icp_run_trimmed(ctx, b.transformation, distance_threshold, keep, 0, 0.0, 0.0,
+                                                         VISMA_ICP_SOLVER_KABSCH, 0, &r, &ri), "visma_icp_run_trimmed");
+                detail::fill_result_trimmed(ctx, r, ri, model.points_.size(), *best_out);
+            }
+        }
+        return best.transformation_;
+    }
     const bool plane_ready = point_to_plane && model.HasNormals() && scene.HasNormals();
     if ((!point_to_plane || plane_ready) && rotation_level > 0 && distance_threshold > 0.0) {
         // all levels in one library call (the sweep is advanced on the GPU), either estimator
@@ -763,6 +858,18 @@ inline Eigen::Matrix4d TransformationEstimationPointToPoint4DoF::ComputeTransfor
     const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
 {
     return detail::host_update(source, target, corres, false, with_scaling_);
+}
+
+inline double TransformationEstimationPointToPointTrimmed::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_rmse_point_to_point(source, target, corres);
+}
+
+inline Eigen::Matrix4d TransformationEstimationPointToPointTrimmed::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_update(source, target, corres, false, false);
 }
 
 // ---- the estimators constrained to a rotation about up_ ----------------------

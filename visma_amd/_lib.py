@@ -202,6 +202,15 @@ def _bind(L):
     if hasattr(L, "visma_icp_point_cloud_distance"):     # (A/B runs load older builds through VISMA_ICP_LIB)
         L.visma_icp_point_cloud_distance.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _dp]
         L.visma_icp_nearest_neighbor_distance.argtypes = [C.c_void_p, _dp, C.c_int64, _dp]
+    if hasattr(L, "visma_icp_run_trimmed"):              # (A/B runs load older builds through VISMA_ICP_LIB)
+        _tp = C.POINTER(CTrimInfo)
+        L.visma_icp_reduce_trimmed.argtypes = [C.c_void_p, C.c_double, _dp, _tp]
+        L.visma_icp_run_trimmed.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                            C.c_int, C.c_int, C.POINTER(CResult), _tp]
+        L.visma_icp_run_yaw_sweep_trimmed.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                      C.c_double, C.c_int, C.POINTER(CResult), C.POINTER(C.c_int),
+                                                      C.POINTER(CResult), _tp, _tp]
+        L.visma_icp_get_kept_mask.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -232,6 +241,23 @@ def _f64(a, shape=None):
 
 def _p(a, t):
     return a.ctypes.data_as(t)
+
+
+class CTrimInfo(C.Structure):
+    """visma_icp_trim_info"""
+    _fields_ = [("kept", C.c_int64), ("trimmed_rmse", C.c_double), ("d2_cut", C.c_double)]
+
+
+class TrimInfo:
+    """What a trimmed pass kept: m pairs, their rmse, the largest kept fp32 squared distance."""
+
+    def __init__(self, c):
+        self.kept = int(c.kept)
+        self.trimmed_rmse = float(c.trimmed_rmse)
+        self.d2_cut = float(c.d2_cut)
+
+    def __repr__(self):
+        return "TrimInfo(kept=%d, trimmed_rmse=%.6g, d2_cut=%.6g)" % (self.kept, self.trimmed_rmse, self.d2_cut)
 
 
 class Result:
@@ -373,6 +399,19 @@ class Context:
         self._chk(self.L.visma_icp_reduce(self._h, _p(st, _dp)))
         return st
 
+    def reduce_trimmed(self, keep):
+        """The statistics of the last nn_pass over the floor(keep * ns) pairs with the smallest (d2, source index)
+        -> (stats, TrimInfo)."""
+        st = np.empty(NSTATS); info = CTrimInfo()
+        self._chk(self.L.visma_icp_reduce_trimmed(self._h, float(keep), _p(st, _dp), C.byref(info)))
+        return st, TrimInfo(info)
+
+    def kept_mask(self):
+        """bool per source point (caller's order): kept by the last trimmed pass."""
+        m = np.zeros(max(self.ns, 1), np.uint8)
+        self._chk(self.L.visma_icp_get_kept_mask(self._h, _p(m, C.POINTER(C.c_uint8))))
+        return m[:self.ns].astype(bool)
+
     def get_correspondences(self):
         si = np.empty(max(self.ns, 1), np.int32); ti = np.empty(max(self.ns, 1), np.int32)
         d2 = np.empty(max(self.ns, 1), np.float32); k = C.c_int64(0)
@@ -397,6 +436,32 @@ class Context:
                                        float(rel_fitness), float(rel_rmse), int(solver),
                                        int(bool(with_scaling)), C.byref(out)))
         return Result(out)
+
+    def run_trimmed(self, init=None, max_dist=0.05, keep=1.0, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                    solver=SOLVER_KABSCH, with_scaling=False):
+        """Trimmed ICP: per pass only the floor(keep * ns) closest pairs enter the solve.  keep = the share of the
+        source the target can see; a keep below the true overlap stalls.  -> Result with .trim (TrimInfo)."""
+        init = _f64(np.eye(4) if init is None else init, (16,))
+        out = CResult(); info = CTrimInfo()
+        self._chk(self.L.visma_icp_run_trimmed(self._h, _p(init, _dp), float(max_dist), float(keep), int(max_iter),
+                                               float(rel_fitness), float(rel_rmse), int(solver),
+                                               int(bool(with_scaling)), C.byref(out), C.byref(info)))
+        r = Result(out)
+        r.trim = TrimInfo(info)
+        return r
+
+    def run_yaw_sweep_trimmed(self, level, max_dist, keep, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6,
+                              solver=SOLVER_KABSCH):
+        best = CResult(); bl = C.c_int(-1); per = (CResult * level)()
+        bi = CTrimInfo(); pi = (CTrimInfo * level)()
+        self._chk(self.L.visma_icp_run_yaw_sweep_trimmed(self._h, int(level), float(max_dist), float(keep), int(max_iter),
+                                                         float(rel_fitness), float(rel_rmse), int(solver), C.byref(best),
+                                                         C.byref(bl), per, C.byref(bi), pi))
+        rb = Result(best); rb.trim = TrimInfo(bi)
+        rs = []
+        for p, i in zip(per, pi):
+            r = Result(p); r.trim = TrimInfo(i); rs.append(r)
+        return rb, bl.value, rs
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""

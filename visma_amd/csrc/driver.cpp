@@ -377,6 +377,7 @@ static int set_clouds_f64_impl(visma_icp_ctx *ctx, const double *src, int64_t ns
         if (!raw_target) return ctx->fail(VISMA_ICP_ERR_STATE, "a mesh-sampled source needs the HIP engine");
         rc = ctx->eng->set_source_meshes_f64(ms->meshes, ms->n, ms->quirks, ms->seed, c, want64 && ctx->eng->supports_device_loop(),
                                              ctx->src_order, ms->ns_out);
+        ctx->src_order_gen++;
         if (rc == VISMA_ICP_ERR_STATE) return ctx->fail(VISMA_ICP_ERR_STATE, "a mesh-sampled source needs the HIP engine");
         if (rc) return ctx->eng_fail(rc);
         raw_source = true;
@@ -394,6 +395,7 @@ static int set_clouds_f64_impl(visma_icp_ctx *ctx, const double *src, int64_t ns
             if (rc) return ctx->eng_fail(rc);
         }
         rc = ctx->eng->set_source_f64(src, ns, sstride, c, want64 && ctx->eng->supports_device_loop(), ctx->src_order);
+        ctx->src_order_gen++;
         raw_source = rc == VISMA_ICP_OK;
         if (!raw_source && rc != VISMA_ICP_ERR_STATE) return ctx->eng_fail(rc);
     }
@@ -403,7 +405,7 @@ static int set_clouds_f64_impl(visma_icp_ctx *ctx, const double *src, int64_t ns
         pack_f64_to(src, ns, sstride, c, sb, true);
     }
     tm[ti++] = t_now();   // source pack
-    if (!raw_source) morton_order_ptr(sb, ns, ctx->src_order, true);
+    if (!raw_source) { morton_order_ptr(sb, ns, ctx->src_order, true); ctx->src_order_gen++; }
     tm[ti++] = t_now();   // morton
     if (!raw_source) {
         rc = ctx->eng->set_source(sb, ns);
@@ -472,6 +474,7 @@ int visma_icp_set_source(visma_icp_ctx *ctx, const float *xyz, int64_t ns, int s
     float *buf = ctx->eng->staging(1, (size_t)std::max<int64_t>(ns, 1) * 4);
     pack_f32_to(xyz, ns, stride, buf);
     morton_order_ptr(buf, ns, ctx->src_order, true);
+    ctx->src_order_gen++;
     int rc = ctx->eng->set_source(buf, ns);
     if (rc) return ctx->eng_fail(rc);
     ctx->enter_uncentred_frame(true);
@@ -499,6 +502,7 @@ int visma_icp_set_source_device(visma_icp_ctx *ctx, const void *d, int64_t ns)
     int rc = ctx->eng->set_source_device(d, ns);
     if (rc) return ctx->eng_fail(rc);
     ctx->src_order.clear();   // device-resident source is used in the caller's order
+    ctx->src_order_gen++;
     ctx->enter_uncentred_frame(true);
     ctx->have_src = true;
     return VISMA_ICP_OK;
@@ -644,6 +648,124 @@ int visma_icp_run(visma_icp_ctx *ctx, const double init[16], double max_dist, in
     if (solver < 0 || solver > VISMA_ICP_SOLVER_GN_EXPMAP) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown solver");
     if (int rc = ctx->check_axis_solver(solver, with_scaling != 0)) return rc;
     return ctx->run(init, max_dist, max_iter, rel_fitness, rel_rmse, solver, with_scaling != 0, false, out);
+}
+
+// ---- trimmed ICP ----------------------------------------------------------------------------------------------------
+static int check_trimmed(visma_icp_ctx *ctx, double keep)
+{
+    if (!(keep > 0.0) || !(keep <= 1.0) || !std::isfinite(keep)) return ctx->fail(VISMA_ICP_ERR_INVALID, "keep must lie in (0, 1]");
+    if (ctx->sharded() || ctx->eng->is_sharded())
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "trimmed ICP runs on one rank: an order statistic across ranks is not available");
+    if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_reduce_trimmed(visma_icp_ctx *ctx, double keep, double out_stats[VISMA_ICP_NSTATS], visma_icp_trim_info *info)
+{
+    CTX_CHECK();
+    if (!out_stats || !info) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (int rc = check_trimmed(ctx, keep)) return rc;
+    Engine::TrimPass tr;
+    int rc = ctx->eng->reduce_trimmed(ctx->last_Tc, nullptr, keep, ctx->order_ptr(), ctx->src_order_gen, out_stats, &tr);
+    if (rc) return ctx->eng_fail(rc);
+    ctx->trim_state = 1;
+    info->kept = tr.kept;
+    info->trimmed_rmse = visma_icp_ctx::trimmed_rmse(out_stats);
+    info->d2_cut = tr.d2_cut;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_run_trimmed(visma_icp_ctx *ctx, const double init[16], double max_dist, double keep, int max_iter,
+                          double rel_fitness, double rel_rmse, int solver, int with_scaling, visma_icp_result *out,
+                          visma_icp_trim_info *info)
+{
+    CTX_CHECK();
+    if (!init || !out || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad run arguments");
+    if (solver != VISMA_ICP_SOLVER_KABSCH) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimmed ICP: the closed-form solver only");
+    if (int rc = ctx->check_axis_solver(solver, with_scaling != 0)) return rc;
+    if (int rc = check_trimmed(ctx, keep)) return rc;
+    if (keep == 1.0) {
+        // every pair is kept: the plain run, bit for bit
+        int rc = ctx->run(init, max_dist, max_iter, rel_fitness, rel_rmse, solver, with_scaling != 0, false, out);
+        if (rc) return rc;
+        ctx->trim_state = max_dist > 0.0 ? 2 : 0;
+        if (info) {
+            std::memset(info, 0, sizeof(*info));
+            info->kept = out->num_correspondences;
+            info->trimmed_rmse = out->inlier_rmse;
+            if (max_dist > 0.0 && out->num_correspondences > 0) {
+                const int64_t ns = ctx->eng->ns();
+                std::vector<int32_t> idx((size_t)std::max<int64_t>(ns, 1));
+                std::vector<float> dd((size_t)std::max<int64_t>(ns, 1));
+                rc = ctx->eng->get_correspondences(idx.data(), dd.data());
+                if (rc) return ctx->eng_fail(rc);
+                float mx = 0.f;
+                for (int64_t i = 0; i < ns; i++)
+                    if (idx[(size_t)i] >= 0) mx = std::max(mx, dd[(size_t)i]);
+                info->d2_cut = (double)mx;
+            }
+        }
+        return VISMA_ICP_OK;
+    }
+    return ctx->run_trimmed(init, max_dist, keep, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, info);
+}
+
+int visma_icp_run_yaw_sweep_trimmed(visma_icp_ctx *ctx, int level, double max_dist, double keep, int max_iter,
+                                    double rel_fitness, double rel_rmse, int solver, visma_icp_result *best, int *best_level,
+                                    visma_icp_result *per_level, visma_icp_trim_info *best_info,
+                                    visma_icp_trim_info *per_level_info)
+{
+    CTX_CHECK();
+    if (level <= 0 || !best || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad sweep arguments");
+    if (solver != VISMA_ICP_SOLVER_KABSCH) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimmed ICP: the closed-form solver only");
+    if (int rc = ctx->check_axis_solver(solver, false)) return rc;
+    if (int rc = check_trimmed(ctx, keep)) return rc;
+    // src/annotation.cpp:35-61, one start after the other
+    const double interval = 2.0 * M_PI / (double)level;
+    visma_icp_result b;
+    visma_icp_trim_info bi;
+    std::memset(&b, 0, sizeof(b));
+    std::memset(&bi, 0, sizeof(bi));
+    const Mat4 I = Mat4::identity();
+    std::memcpy(b.transformation, I.m, sizeof(I.m));
+    int bl = -1;
+    for (int i = 0; i < level; i++) {
+        const double a = interval * i, c = std::cos(a), s = std::sin(a);
+        Mat4 init = Mat4::identity();
+        init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
+        visma_icp_result r;
+        visma_icp_trim_info ri;
+        int rc = visma_icp_run_trimmed(ctx, init.m, max_dist, keep, max_iter, rel_fitness, rel_rmse, solver, 0, &r, &ri);
+        if (rc) return rc;
+        if (per_level) per_level[i] = r;
+        if (per_level_info) per_level_info[i] = ri;
+        if (r.num_correspondences > b.num_correspondences) { b = r; bi = ri; bl = i; }   // strict >
+    }
+    *best = b;
+    if (best_info) *best_info = bi;
+    if (best_level) *best_level = bl;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src)
+{
+    CTX_CHECK();
+    if (!kept_per_src) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output buffer");
+    if (ctx->trim_state == 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no trimmed pass yet");
+    const int64_t ns = ctx->eng->ns();
+    std::vector<uint8_t> mask((size_t)std::max<int64_t>(ns, 1));
+    if (ctx->trim_state == 2) {
+        std::vector<int32_t> idx((size_t)std::max<int64_t>(ns, 1));
+        int rc = ctx->eng->get_correspondences(idx.data(), nullptr);
+        if (rc) return ctx->eng_fail(rc);
+        for (int64_t i = 0; i < ns; i++) mask[(size_t)i] = idx[(size_t)i] >= 0 ? 1 : 0;
+    } else {
+        int rc = ctx->eng->get_kept_mask(mask.data());
+        if (rc) return ctx->eng_fail(rc);
+    }
+    const int32_t *order = ctx->order_ptr();
+    for (int64_t pos = 0; pos < ns; pos++) kept_per_src[order ? order[pos] : pos] = mask[(size_t)pos];
+    return VISMA_ICP_OK;
 }
 
 int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, int steps, int solver,

@@ -35,6 +35,8 @@ struct visma_icp_ctx {
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)
+    unsigned long long src_order_gen = 0;   // advanced with every change of src_order (the engine keeps a device copy)
+    int trim_state = 0;               // the last trimmed pass: 0 none, 1 on the engine, 2 plain pass with every pair kept
     double last_aux_kernel_ms = 0.0;  // kernel time of the last mesh-distance call
     double last_aux_build_ms = 0.0;   // ... and of building its search structure
     int mesh_method = 0;              // 0 choose, 1 brute force, 2 BVH
@@ -124,6 +126,68 @@ struct visma_icp_ctx {
         case VISMA_ICP_SOLVER_GN_EXPMAP: return gn_from_stats(stats, true, &ok);
         default: return kabsch_from_stats(stats, scaling);
         }
+    }
+
+    const int32_t *order_ptr() const { return (int64_t)src_order.size() == eng->ns() && eng->ns() > 0 ? src_order.data() : nullptr; }
+
+    // one NN pass + trimmed reduction: stats over the kept pairs; fitness and rmse over all K; *tr what was kept
+    int pass_trimmed(const Mat4 &Tc, double max_dist, double keep, double *stats, double *fit, double *rmse,
+                     Engine::TrimPass *tr)
+    {
+        int rc = eng->nn_pass(Tc, max_dist);
+        if (rc) return eng_fail(rc);
+        last_Tc = Tc;
+        last_plane = false;
+        rc = eng->reduce_trimmed(Tc, nullptr, keep, order_ptr(), src_order_gen, stats, tr);
+        if (rc) return eng_fail(rc);
+        trim_state = 1;
+        const int64_t denom = ns_total > 0 ? ns_total : eng->ns();
+        if (tr->found > 0) {
+            *fit = (double)tr->found / (double)denom;
+            *rmse = std::sqrt(tr->sum_all / (double)tr->found);
+        } else {
+            *fit = 0.0;
+            *rmse = 0.0;
+        }
+        return VISMA_ICP_OK;
+    }
+    static double trimmed_rmse(const double *stats) { return stats[0] > 0.0 ? std::sqrt(stats[1] / stats[0]) : 0.0; }
+
+    // RegistrationICP's loop with the trimmed pass; the stop test looks at fitness and the TRIMMED rmse
+    int run_trimmed(const double *init, double max_dist, double keep, int max_iter, double rel_fit, double rel_rmse,
+                    bool scaling, visma_icp_result *out, visma_icp_trim_info *info)
+    {
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out->transformation, init, sizeof(double) * 16);
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (!(max_dist > 0.0)) return VISMA_ICP_OK;                 // Registration.cpp:148-151
+        last_radius = max_dist;
+        Mat4 Tc = to_centred(Mat4::from(init), centre);
+        double stats[VISMA_ICP_NSTATS], fit, rmse;
+        Engine::TrimPass tr;
+        int rc = pass_trimmed(Tc, max_dist, keep, stats, &fit, &rmse, &tr);
+        if (rc) return rc;
+        double trmse = trimmed_rmse(stats);
+        int it = 0;
+        for (int i = 0; i < max_iter; i++) {
+            const Mat4 upd = solve(stats, VISMA_ICP_SOLVER_KABSCH, scaling, false);
+            Tc = apply_update(upd, Tc, false);
+            const double bfit = fit, brmse = trmse;
+            rc = pass_trimmed(Tc, max_dist, keep, stats, &fit, &rmse, &tr);
+            if (rc) return rc;
+            trmse = trimmed_rmse(stats);
+            it = i + 1;
+            if (std::fabs(bfit - fit) < rel_fit && std::fabs(brmse - trmse) < rel_rmse) break;
+        }
+        const Mat4 T = from_centred(Tc, centre);
+        std::memcpy(out->transformation, T.m, sizeof(T.m));
+        out->fitness = fit;
+        out->inlier_rmse = rmse;
+        out->num_correspondences = tr.found;
+        out->iterations = it;
+        out->nn_passes = it + 1;
+        if (info) { info->kept = tr.kept; info->trimmed_rmse = trmse; info->d2_cut = tr.d2_cut; }
+        return VISMA_ICP_OK;
     }
 
     int run(const double *init, double max_dist, int max_iter, double rel_fit, double rel_rmse,

@@ -273,6 +273,29 @@ public:
     // q+offset): zero = centred frame, the cloud centre = the caller's frame.
     virtual int reduce(const Mat4 &Tc, bool plane, const double offset[3], double *stats) = 0;
     virtual int get_correspondences(int32_t *idx, float *d2) = 0;
+    // Trimmed ICP: the pending pass's search, then the statistics over the m pairs with the smallest key
+    // (fp32 d2, caller's source index) only -- m = trim_count(K, ns, keep).  `order` (NULL: identity) maps a source
+    // position of the engine to the caller's index and is re-read only when `order_gen` changes.
+    struct TrimPass {
+        int64_t found = 0, kept = 0;    // K, m
+        double sum_all = 0.0;           // sum of |p - q|^2 over all K pairs (inlier_rmse)
+        double d2_cut = 0.0;            // the largest kept fp32 squared distance (0 when m = 0)
+    };
+    static int64_t trim_count(int64_t K, int64_t ns, double keep)
+    {
+        int64_t m = std::min(K, (int64_t)std::floor(keep * (double)ns));
+        if (m < 3) m = std::min<int64_t>(K, 3);
+        return m;
+    }
+    virtual int reduce_trimmed(const Mat4 &, const double * /* offset[3] */, double /* keep */, const int32_t * /* order */,
+                               unsigned long long /* order_gen */, double * /* stats */, TrimPass *)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // 1 per kept source POSITION of the last trimmed pass
+    virtual int get_kept_mask(uint8_t *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual bool is_sharded() const { return false; }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

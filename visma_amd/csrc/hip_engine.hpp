@@ -46,6 +46,8 @@ public:
         if (h_flag_) (void)hipHostFree(h_flag_);
         free_dev(d_relay_); free_dev(d_timeline_); free_dev(d_peer_table_); free_dev(d_fold_tag_);
         if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
+        free_dev(d_trim_work_); free_dev(d_trim_partials_); free_dev(d_trim_mask_); free_dev(d_trim_order_);
+        if (h_trim_) (void)hipHostFree(h_trim_);
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -299,6 +301,18 @@ public:
     void select_problem(int b) override { view_offset_ = (int64_t)b * loop_out_stride_; }
 
     int run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out) override;
+
+    // trimmed ICP (trim.hip): the plain pass, then select + masked reduction over its d_idx_ / d_d2_
+    int reduce_trimmed(const Mat4 &Tc, const double *offset, double keep, const int32_t *order, unsigned long long order_gen,
+                       double *stats, TrimPass *out) override;
+    int get_kept_mask(uint8_t *mask) override;
+    bool is_sharded() const override { return comm_ != nullptr || ipc_n_ > 1 || tshard_ || minreduce_ != nullptr; }
+    void *d_trim_work_ = nullptr, *d_trim_partials_ = nullptr, *d_trim_mask_ = nullptr, *d_trim_order_ = nullptr;
+    double *h_trim_ = nullptr, *h_trim_dev_ = nullptr;     // mapped: kTrimPublished granules {value, sequence number}
+    int64_t trim_mask_cap_ = 0, trim_order_cap_ = 0, trim_mask_ns_ = -1;
+    unsigned long long trim_order_gen_ = ~0ull, trim_seq_ = 0;
+    const int32_t *trim_order_src_ = nullptr;
+    bool trim_dirty_ = false;                              // a pass did not run to its end: the work words are cleared
 
     int run_loop_batch(const LoopParams &lp, const std::vector<BatchProblem> &pb, LoopResult *out) override;
 

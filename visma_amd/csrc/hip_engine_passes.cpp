@@ -573,6 +573,117 @@ int HipEngine::get_correspondences(int32_t *idx, float *d2)
     return VISMA_ICP_OK;
 }
 
+// One trimmed pass: the plain pass as reduce() runs it (its statistics over all K pairs are what fitness and inlier_rmse
+// need, and K decides m), then three select launches and the masked reduction over d_idx_ / d_d2_, all on the stream;
+// the host waits for the tagged granules of the masked reduction like reduce() waits for its own.
+int HipEngine::reduce_trimmed(const Mat4 &Tc, const double *offset, double keep, const int32_t *order,
+                              unsigned long long order_gen, double *stats, TrimPass *out)
+{
+    if (is_sharded()) { err_ = "trimmed ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    if (!have_pass_) { err_ = "reduce before nn_pass"; return VISMA_ICP_ERR_STATE; }
+    if (view_offset_ != 0) { err_ = "trimmed reduction needs an nn_pass of its own"; return VISMA_ICP_ERR_STATE; }
+    const double zero[3] = {0, 0, 0};
+    if (!offset) offset = zero;
+    double all[kNStats];
+    int rc = reduce(Tc, false, offset, all);
+    if (rc) return rc;
+    if (sess_live_) { rc = end_session(); if (rc) return rc; }   // (never behind a launch that waits for this thread)
+    HIP_TRY(hipSetDevice(device_));
+    const int64_t K = (int64_t)std::llround(all[0]);
+    const int64_t m = trim_count(K, ns_, keep);
+    out->found = K;
+    out->kept = m;
+    out->sum_all = all[1];
+    out->d2_cut = 0.0;
+    if (!d_trim_work_) {
+        HIP_TRY(hipMalloc(&d_trim_work_, sizeof(unsigned) * kTrimWorkWords));
+        HIP_TRY(hipMalloc(&d_trim_partials_, sizeof(double) * kReduceAcc * 1024));
+        HIP_TRY(hipHostMalloc((void **)&h_trim_, sizeof(double) * 2 * kTrimPublished, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(h_trim_, 0, sizeof(double) * 2 * kTrimPublished);
+        HIP_TRY(hipHostGetDevicePointer((void **)&h_trim_dev_, h_trim_, 0));
+        trim_dirty_ = true;
+    }
+    if (ns_ > trim_mask_cap_) {
+        free_dev(d_trim_mask_);
+        HIP_TRY(hipMalloc(&d_trim_mask_, (size_t)std::max<int64_t>(ns_, 1)));
+        trim_mask_cap_ = ns_;
+    }
+    trim_mask_ns_ = ns_;
+    if (m <= 0) {
+        for (int i = 0; i < kNStats; i++) stats[i] = 0.0;
+        if (ns_ > 0) HIP_TRY(hipMemsetAsync(d_trim_mask_, 0, (size_t)ns_, stream_));
+        return VISMA_ICP_OK;
+    }
+    if (order && (order_gen != trim_order_gen_ || order != trim_order_src_ || ns_ > trim_order_cap_)) {
+        if (ns_ > trim_order_cap_) {
+            free_dev(d_trim_order_);
+            HIP_TRY(hipMalloc(&d_trim_order_, sizeof(int32_t) * (size_t)ns_));
+            trim_order_cap_ = ns_;
+        }
+        HIP_TRY(hipMemcpyAsync(d_trim_order_, order, sizeof(int32_t) * (size_t)ns_, hipMemcpyHostToDevice, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));                 // (the caller's vector may change after this call)
+        trim_order_gen_ = order_gen;
+        trim_order_src_ = order;
+    }
+    if (trim_dirty_) HIP_TRY(hipMemsetAsync(d_trim_work_, 0, sizeof(unsigned) * kTrimWorkWords, stream_));
+    trim_dirty_ = true;
+    const int32_t *d_order = order ? (const int32_t *)d_trim_order_ : nullptr;
+    HIP_TRY(launch_trim_select((const float *)d_d2_, (const int32_t *)d_idx_, d_order, ns_, (unsigned)m, (unsigned *)d_trim_work_, stream_));
+    TrimReduceArgs a;
+    // the coordinates the plain pass summed from: the f64 copies where the search ran on them
+    const bool s64 = use_grid_ ? f64_views() : brute_exact();
+    if (s64) { a.src64 = (const Pt64 *)d_src64_; a.tgt64 = (const Pt64 *)d_tgt64_; }
+    if (s64 && !a.tgt64) { err_ = "trimmed reduction: no f64 target"; return VISMA_ICP_ERR_STATE; }
+    a.src = (const float4 *)d_src_; a.tgt = (const float4 *)d_tgt_;
+    a.idx = (const int32_t *)d_idx_; a.d2 = (const float *)d_d2_;
+    a.order = d_order;
+    a.ns = ns_;
+    for (int i = 0; i < 12; i++) a.T64.m[i] = Tc.m[i];
+    for (int k = 0; k < 3; k++) a.off.v[k] = offset[k];
+    a.work = (unsigned *)d_trim_work_;
+    a.mask = (unsigned char *)d_trim_mask_;
+    a.partials = (double *)d_trim_partials_;
+    a.host_out = h_trim_dev_;
+    const unsigned long long seq = ++trim_seq_;
+    a.seq = seq;
+    HIP_TRY(launch_trim_reduce(a, stream_));
+    volatile unsigned long long *g = reinterpret_cast<volatile unsigned long long *>(h_trim_);
+    auto all_tagged = [&]() {
+        for (int i = kTrimPublished - 1; i >= 0; --i)
+            if (g[2 * i + 1] != seq) return false;
+        return true;
+    };
+    bool seen = false;
+    for (long long spin = 0; spin < 400000000ll && !seen; ++spin) {
+        seen = all_tagged();
+        if (!seen && (spin & 0xFFFFFll) == 0xFFFFFll && hipStreamQuery(stream_) != hipErrorNotReady) { seen = all_tagged(); break; }
+    }
+    if (!seen) {
+        HIP_TRY(hipStreamSynchronize(stream_));   // surfaces a kernel fault, if any
+        if (!all_tagged()) { err_ = "trimmed statistics were not published"; return VISMA_ICP_ERR_HIP; }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    double pub[kTrimPublished];
+    for (int i = 0; i < kTrimPublished; i++) {
+        const unsigned long long v = g[2 * i];
+        std::memcpy(&pub[i], &v, sizeof(double));
+    }
+    trim_dirty_ = false;
+    for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
+    out->d2_cut = pub[kNStats];
+    if ((int64_t)std::llround(pub[kNStats + 1]) != m) { err_ = "trimmed reduction kept another number of pairs than the select cut"; return VISMA_ICP_ERR_HIP; }
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::get_kept_mask(uint8_t *mask)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (trim_mask_ns_ != ns_ || !d_trim_mask_) { err_ = "no trimmed pass yet"; return VISMA_ICP_ERR_STATE; }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (ns_ > 0) HIP_TRY(hipMemcpy(mask, d_trim_mask_, (size_t)ns_, hipMemcpyDeviceToHost));
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

@@ -523,6 +523,32 @@ int coop_persist_capacity(int point_to_plane);
 hipError_t launch_finalize_solve_batch(const double *partials, const ProbDesc *descs, DevIcpState *st,
                                        int nprob, hipStream_t stream, int plane = 0);
 
+// ---- trimmed ICP (trim.hip): the m pairs with the smallest key (d2, source index) of the last pass ----
+constexpr int kTrimHistWords = 3 * 2048;               // the select's histograms: three rounds of up to 2048 bins
+constexpr int kTrimWorkWords = kTrimHistWords + 8;     // ... + 4 tickets + the state {cut d2 bits, need, ties, cut index}
+constexpr int kTrimPublished = kNStats + 2;            // granules to the host: 38 statistics, cut d2, kept pairs
+struct TrimReduceArgs {
+    const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
+    const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
+    const int32_t *idx = nullptr;                      // the pass's winners per source position (< 0: no pair)
+    const float *d2 = nullptr;                         // ... and their fp32 squared distances: the ranking value
+    const int32_t *order = nullptr;                    // source position -> caller's source index (NULL: identity)
+    int64_t ns = 0;
+    Xform64 T64{};
+    Offset64 off{};
+    unsigned *work = nullptr;                          // kTrimWorkWords words, zero before the first pass (self re-arming)
+    unsigned char *mask = nullptr;                     // out: 1 per kept source position
+    double *partials = nullptr;                        // trim_reduce_blocks(ns) rows of kReduceAcc
+    double *host_out = nullptr;                        // mapped host memory: kTrimPublished granules {value, seq}
+    unsigned long long seq = 0;
+};
+int trim_select_blocks(int64_t ns);
+int trim_reduce_blocks(int64_t ns);
+// the three rounds of the select; m in [1, K]: the rank of the cut among the pairs
+hipError_t launch_trim_select(const float *d2, const int32_t *idx, const int32_t *order, int64_t ns, unsigned m, unsigned *work,
+                              hipStream_t stream);
+hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream);
+
 // fill n float4 with +inf (target padding)
 hipError_t launch_fill_inf(float4 *dst, int64_t n, hipStream_t stream);
 // AoS stride-s floats -> float4 (w = 0)
