@@ -820,7 +820,8 @@ double vo_point_triangle_sqdist(const double p[3], const double a[3], const doub
         const double d3 = dot3(ab, bp), d4 = dot3(ac, bp);
         if (d3 >= 0.0 && d4 <= d3) { memcpy(q, b, sizeof(q)); goto done; }       /* vertex b */
         const double vc = d1 * d4 - d3 * d2;
-        if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                               /* edge ab */
+        /* igl::point_simplex_squared_distance guards this region with a != b (0 / 0 otherwise) */
+        if ((a[0] != b[0] || a[1] != b[1] || a[2] != b[2]) && vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {   /* edge ab */
             const double v = d1 / (d1 - d3);
             for (int i = 0; i < 3; i++) q[i] = a[i] + v * ab[i];
             goto done;

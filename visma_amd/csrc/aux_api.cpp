@@ -16,12 +16,10 @@ int visma_icp_voxel_down_sample(visma_icp_ctx *ctx, const double *xyz, int64_t n
     if (n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
     if (!ctx->eng->supports_device_loop())   // only the HIP engine owns a GPU
         return ctx->fail(VISMA_ICP_ERR_STATE, "voxel_down_sample needs the HIP engine");
-    int too_fine = 0;
     if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
     hipError_t e = voxel_down_sample_device(xyz, normals, colors, n, voxel_size, out_xyz, out_normals,
-                                            out_colors, n_out, &too_fine, ctx->eng->aux_stream());
+                                            out_colors, n_out, ctx->eng->aux_stream());
     if (e != hipSuccess) return ctx->fail(VISMA_ICP_ERR_HIP, std::string("voxel_down_sample: ") + hipGetErrorString(e));
-    if (too_fine) return ctx->fail(VISMA_ICP_ERR_INVALID, "voxel grid too fine to key in 62 bits");
     return VISMA_ICP_OK;
 }
 

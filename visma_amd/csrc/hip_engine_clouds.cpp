@@ -284,12 +284,10 @@ int HipEngine::set_target_voxel_f64(const double *xyz, int64_t n, int stride, do
     }
     double *d_o = nullptr;
     int64_t nvox = 0;
-    int too_fine = 0;
     hipError_t e = voxel_down_sample_core((const double *)d_in, nullptr, nullptr, n, voxel, &d_o, nullptr, nullptr, &nvox,
-                                          &too_fine, stream_);
+                                          stream_);
     free_dev(d_in);
     if (e != hipSuccess) { err_ = std::string("voxel_down_sample: ") + hipGetErrorString(e); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
-    if (too_fine) { (void)hipFree(d_o); err_ = "voxel grid too fine to key in 62 bits"; return VISMA_ICP_ERR_INVALID; }
     if (d_vox_out_) (void)hipFree(d_vox_out_);
     d_vox_out_ = d_o;
     vox_out_n_ = nvox;

@@ -48,7 +48,9 @@ __device__ __forceinline__ double point_triangle(const double p[3], const double
         if (d3 >= 0.0 && d4 <= d3) { q[0] = b[0]; q[1] = b[1]; q[2] = b[2]; done = true; }      // vertex b
         if (!done) {
             const double vc = d1 * d4 - d3 * d2;
-            if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                                           // edge ab
+            // (a != b as in igl::point_simplex_squared_distance: with a == b, d1 / (d1 - d3) is 0 / 0 and the face
+            // would drop out of the minimum; it falls through to c and the edges ac, bc like the reference's)
+            if ((a[0] != b[0] || a[1] != b[1] || a[2] != b[2]) && vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {   // edge ab
                 const double v = d1 / (d1 - d3);
 #pragma unroll
                 for (int i = 0; i < 3; i++) q[i] = a[i] + v * ab[i];

@@ -12,6 +12,12 @@
 // taken in exactly the reference's order, so every output value is bit-identical
 // to the reference's; only the ORDER of the output voxels differs (ascending key
 // here, hash-map iteration order there).
+//
+// A grid of 4e18 cells or more does not fit that key (the reference's own limit is
+// only voxel * INT_MAX >= extent, i.e. up to 2^31 cells per axis).  Such a cloud is
+// ordered by (ix, iy, iz) with three stable 32-bit sorts instead -- iz, then iy,
+// then ix -- and run heads compare the three indices: the same ascending
+// (ix, iy, iz) output order, the same input-order sums.
 #include "device_common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -86,6 +92,42 @@ __global__ __launch_bounds__(256) void vox_key_kernel(const double *__restrict__
     val[i] = (unsigned)i;
 }
 
+// ---- the grid that does not fit one 64-bit key: the three indices kept apart ----
+__global__ __launch_bounds__(256) void vox_index_kernel(const double *__restrict__ xyz, long long n, VoxParams vp,
+                                                        unsigned *__restrict__ vi, unsigned *__restrict__ key,
+                                                        unsigned *__restrict__ val)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int a = 0; a < 3; a++)      // DownSample.cpp:201-204, same f64 expression (0 <= index <= INT_MAX)
+        vi[3 * i + a] = (unsigned)(int)floor((xyz[3 * i + a] - vp.vmin[a]) / vp.voxel);
+    key[i] = vi[3 * i + 2];
+    val[i] = (unsigned)i;
+}
+
+__global__ __launch_bounds__(256) void vox_axis_key_kernel(const unsigned *__restrict__ vi,
+                                                           const unsigned *__restrict__ perm, long long n, int axis,
+                                                           unsigned *__restrict__ key)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    key[j] = vi[3 * (long long)perm[j] + axis];
+}
+
+__global__ __launch_bounds__(256) void vox_head3_kernel(const unsigned *__restrict__ vi,
+                                                        const unsigned *__restrict__ perm, long long n,
+                                                        unsigned *__restrict__ head)
+{
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    unsigned h = 1u;
+    if (j > 0) {
+        const unsigned *a = vi + 3 * (long long)perm[j], *b = vi + 3 * (long long)perm[j - 1];
+        h = (a[0] != b[0] || a[1] != b[1] || a[2] != b[2]) ? 1u : 0u;
+    }
+    head[j] = h;
+}
+
 __global__ __launch_bounds__(256) void vox_head_kernel(const unsigned long long *__restrict__ key,
                                                        long long n, unsigned *__restrict__ head)
 {
@@ -151,10 +193,9 @@ hipError_t launch_exclusive_scan_u32(const unsigned *in, long long n, unsigned *
 // here with *n_out voxels (NULL / 0 when the reference would return an empty cloud); the caller frees them.
 hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, const double *d_col, int64_t n, double voxel,
                                   double **d_oxyz_out, double **d_onrm_out, double **d_ocol_out, int64_t *n_out,
-                                  int *too_fine, hipStream_t stream)
+                                  hipStream_t stream)
 {
     *n_out = 0;
-    *too_fine = 0;
     *d_oxyz_out = nullptr;
     if (d_onrm_out) *d_onrm_out = nullptr;
     if (d_ocol_out) *d_ocol_out = nullptr;
@@ -162,6 +203,7 @@ hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, cons
     hipError_t rc = hipSuccess;
     double *d_oxyz = nullptr, *d_onrm = nullptr, *d_ocol = nullptr;
     unsigned long long *d_box = nullptr, *d_key = nullptr, *d_key2 = nullptr;
+    unsigned *d_vi = nullptr, *d_k32 = nullptr, *d_k32b = nullptr;
     unsigned *d_val = nullptr, *d_val2 = nullptr, *d_head = nullptr, *d_vid = nullptr, *d_bsum = nullptr, *d_vstart = nullptr;
     void *d_tmp = nullptr;
     size_t tmp_bytes = 0;
@@ -172,7 +214,7 @@ hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, cons
     unsigned last_vid = 0, last_head = 0;
     int64_t nvox = 0;
     int end_bit = 64;
-    bool keep = false;
+    bool keep = false, wide = false;
 
     VOX_TRY(hipMalloc(&d_box, sizeof(unsigned long long) * 8));
     hipLaunchKernelGGL(vox_bbox_init_kernel, dim3(1), dim3(64), 0, stream, d_box);
@@ -190,25 +232,41 @@ hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, cons
         dims[a] = floor(((mx[a] - vp.vmin[a]) / voxel)) + 2.0;
         cells *= dims[a];
     }
-    if (!(cells < 4.0e18)) { *too_fine = 1; goto done; }
+    wide = !(cells < 4.0e18);                                  // the grid does not fit one 64-bit key
     vp.voxel = voxel;
     vp.ny = (long long)dims[1];
     vp.nz = (long long)dims[2];
-    end_bit = 1;
-    while (end_bit < 64 && ldexp(1.0, end_bit) < cells) end_bit++;
-
-    VOX_TRY(hipMalloc(&d_key, sizeof(unsigned long long) * n));
-    VOX_TRY(hipMalloc(&d_key2, sizeof(unsigned long long) * n));
     VOX_TRY(hipMalloc(&d_val, sizeof(unsigned) * n));
     VOX_TRY(hipMalloc(&d_val2, sizeof(unsigned) * n));
-    hipLaunchKernelGGL(vox_key_kernel, dim3(pb), dim3(256), 0, stream, d_xyz, (long long)n, vp, d_key, d_val);
-    VOX_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
-    VOX_TRY(hipMalloc(&d_tmp, tmp_bytes > 0 ? tmp_bytes : 16));
-    VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
     VOX_TRY(hipMalloc(&d_head, sizeof(unsigned) * (n + 1)));
     VOX_TRY(hipMalloc(&d_vid, sizeof(unsigned) * (n + 1)));
     VOX_TRY(hipMalloc(&d_bsum, sizeof(unsigned) * (n / 2048 + 2)));
-    hipLaunchKernelGGL(vox_head_kernel, dim3(pb), dim3(256), 0, stream, d_key2, (long long)n, d_head);
+    if (!wide) {
+        end_bit = 1;
+        while (end_bit < 64 && ldexp(1.0, end_bit) < cells) end_bit++;
+        VOX_TRY(hipMalloc(&d_key, sizeof(unsigned long long) * n));
+        VOX_TRY(hipMalloc(&d_key2, sizeof(unsigned long long) * n));
+        hipLaunchKernelGGL(vox_key_kernel, dim3(pb), dim3(256), 0, stream, d_xyz, (long long)n, vp, d_key, d_val);
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
+        VOX_TRY(hipMalloc(&d_tmp, tmp_bytes > 0 ? tmp_bytes : 16));
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
+        hipLaunchKernelGGL(vox_head_kernel, dim3(pb), dim3(256), 0, stream, d_key2, (long long)n, d_head);
+    } else {
+        // least significant index first; every pass is stable, so after the third the points stand in
+        // ascending (ix, iy, iz) and, within a voxel, in ascending point index.  The order ends in d_val2.
+        VOX_TRY(hipMalloc(&d_vi, sizeof(unsigned) * 3 * n));
+        VOX_TRY(hipMalloc(&d_k32, sizeof(unsigned) * n));
+        VOX_TRY(hipMalloc(&d_k32b, sizeof(unsigned) * n));
+        hipLaunchKernelGGL(vox_index_kernel, dim3(pb), dim3(256), 0, stream, d_xyz, (long long)n, vp, d_vi, d_k32, d_val);
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
+        VOX_TRY(hipMalloc(&d_tmp, tmp_bytes > 0 ? tmp_bytes : 16));
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
+        hipLaunchKernelGGL(vox_axis_key_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val2, (long long)n, 1, d_k32);
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val2, d_val, (int)n, 0, 32, stream));
+        hipLaunchKernelGGL(vox_axis_key_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val, (long long)n, 0, d_k32);
+        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
+        hipLaunchKernelGGL(vox_head3_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val2, (long long)n, d_head);
+    }
     VOX_TRY(launch_exclusive_scan_u32(d_head, (long long)n, d_bsum, d_vid, stream));
     VOX_TRY(hipMemcpyAsync(&last_vid, d_vid + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
     VOX_TRY(hipMemcpyAsync(&last_head, d_head + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
@@ -233,19 +291,17 @@ done:
     if (!keep) { (void)hipFree(d_oxyz); (void)hipFree(d_onrm); (void)hipFree(d_ocol); }
     (void)hipFree(d_box); (void)hipFree(d_key); (void)hipFree(d_key2); (void)hipFree(d_val);
     (void)hipFree(d_val2); (void)hipFree(d_head); (void)hipFree(d_vid); (void)hipFree(d_bsum); (void)hipFree(d_vstart);
-    (void)hipFree(d_tmp);
+    (void)hipFree(d_tmp); (void)hipFree(d_vi); (void)hipFree(d_k32); (void)hipFree(d_k32b);
     return rc;
 }
 
 // Host arrays in, host arrays out.  Returns hipSuccess and *n_out (0 when the reference would return an empty
-// cloud); *too_fine is set when the voxel grid cannot be keyed in 62 bits.
+// cloud).
 hipError_t voxel_down_sample_device(const double *h_xyz, const double *h_nrm, const double *h_col,
                                     int64_t n, double voxel, double *h_out_xyz, double *h_out_nrm,
-                                    double *h_out_col, int64_t *n_out, int *too_fine,
-                                    hipStream_t stream)
+                                    double *h_out_col, int64_t *n_out, hipStream_t stream)
 {
     *n_out = 0;
-    *too_fine = 0;
     if (!(voxel > 0.0) || n <= 0) return hipSuccess;       // DownSample.cpp:183-186
     hipError_t rc = hipSuccess;
     double *d_xyz = nullptr, *d_nrm = nullptr, *d_col = nullptr, *d_oxyz = nullptr, *d_onrm = nullptr, *d_ocol = nullptr;
@@ -254,7 +310,7 @@ hipError_t voxel_down_sample_device(const double *h_xyz, const double *h_nrm, co
     VOX_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
     if (h_nrm) { VOX_TRY(hipMalloc(&d_nrm, sizeof(double) * 3 * n)); VOX_TRY(hipMemcpyAsync(d_nrm, h_nrm, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream)); }
     if (h_col) { VOX_TRY(hipMalloc(&d_col, sizeof(double) * 3 * n)); VOX_TRY(hipMemcpyAsync(d_col, h_col, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream)); }
-    VOX_TRY(voxel_down_sample_core(d_xyz, d_nrm, d_col, n, voxel, &d_oxyz, &d_onrm, &d_ocol, &nvox, too_fine, stream));
+    VOX_TRY(voxel_down_sample_core(d_xyz, d_nrm, d_col, n, voxel, &d_oxyz, &d_onrm, &d_ocol, &nvox, stream));
     if (nvox > 0) {
         VOX_TRY(hipMemcpyAsync(h_out_xyz, d_oxyz, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
         if (h_nrm && h_out_nrm) VOX_TRY(hipMemcpyAsync(h_out_nrm, d_onrm, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
