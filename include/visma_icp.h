@@ -360,6 +360,88 @@ VISMA_ICP_API int visma_icp_run_yaw_sweep_trimmed(visma_icp_ctx *ctx, int level,
  * visma_icp_get_correspondences keeps returning all K pairs. */
 VISMA_ICP_API int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src);
 
+/* ---- robust ICP: M-estimators by iteratively re-weighted least squares (Huber 1964; Beaton & Tukey 1974; the
+ * Cauchy / Lorentzian kernel as in Fitzgibbon 2003; tuning constants of Holland & Welsch 1977).  Every pair a pass
+ * finds inside the radius enters the solve with a weight w(r) of its own residual r; the scale c of the weight
+ * function is the caller's or comes from the median residual of the pass.  Unlike trimmed ICP it takes no overlap
+ * share: prefer it where the overlap is not known per object.
+ *
+ *   Pairs: those of the last visma_icp_nn_pass (all K pairs inside the radius).
+ *   Residual r_i >= 0: point-to-point |p_i - q_i|; point-to-plane |(p_i - q_i) . n_i|, n_i the target normal; in
+ *   f64 from the coordinates the plain reduction sums from (the f64 copies where the search ran on them).
+ *   Weights, for a scale c:
+ *     HUBER   w = 1 if r <= c, else c / r
+ *     TUKEY   w = (1 - (r/c)^2)^2 if r < c, else 0
+ *     CAUCHY  w = 1 / (1 + (r/c)^2)
+ *     c == 0: every family gives w = 1 if r == 0, else 0 (no NaN is produced)
+ *     L2      w = 1: the plain run, bit for bit (as keep = 1 is for trimmed ICP)
+ *   Scale:
+ *     scale > 0   c = scale, in the caller's units, fixed for the whole run
+ *     scale == 0  per pass c = max(tune * 1.4826 * med, min_scale); med the LOWER median of the residuals: the m-th
+ *                 smallest with m = (K + 1) / 2, med = sqrt((double)v) with v
+ *                   point-to-point: the m-th smallest fp32 squared distance among the pairs, as
+ *                                   visma_icp_get_correspondences reports them (the scale is a function of the
+ *                                   pass's public output alone);
+ *                   point-to-plane: the m-th smallest of (float)(r_i^2).
+ *                 K == 0: c = min_scale.
+ *     tune == 0   the family's 95 %-efficiency constant: Huber 1.345, Tukey 4.685, Cauchy 2.385
+ *   A non-finite or negative scale, tune or min_scale, or an unknown kernel: VISMA_ICP_ERR_INVALID before any pass.
+ *
+ * The weighted statistics have the layout of visma_icp_reduce with every pair's contribution times w_i:
+ * out_stats[0] = sum w, out_stats[1] = sum w |p - q|^2, ...  The solves take them as they are: sum w == 0 gives the
+ * identity update (the rule for K == 0); the Gauss-Newton solve keeps the reference's |det| < 1e-6 guard as it is --
+ * weights SHRINK J^T J, so a pass whose weights are small overall meets that guard sooner than the plain pass.
+ *
+ * Estimators: point-to-point with SOLVER_KABSCH, with or without scaling; point-to-plane (plane != 0; it needs
+ * visma_icp_set_target_normals_f64 -- without normals the run returns init, Registration.cpp:152-157); both with or
+ * without visma_icp_set_rotation_axis.  The point-to-plane statistics are in the caller's (world) frame.
+ * NOT offered (VISMA_ICP_ERR_INVALID): sharded contexts (comm_init, comm_ipc_init, set_allreduce with more than one
+ * rank, set_target_shard), batches and the corpus, the Gauss-Newton point-to-point solvers, and robust weights
+ * together with keep < 1. */
+enum {
+    VISMA_ICP_ROBUST_L2 = 0,
+    VISMA_ICP_ROBUST_HUBER = 1,
+    VISMA_ICP_ROBUST_TUKEY = 2,
+    VISMA_ICP_ROBUST_CAUCHY = 3
+};
+typedef struct {
+    int kernel;            /* VISMA_ICP_ROBUST_* */
+    double scale;          /* > 0: fixed c; 0: automatic, per pass */
+    double tune;           /* automatic scale: c = tune * 1.4826 * median; 0: the family's constant */
+    double min_scale;      /* automatic scale: lower bound of c */
+} visma_icp_robust;
+typedef struct {
+    double scale;              /* c of the last pass */
+    double median_residual;    /* automatic scale: med of the last pass; 0 with a fixed scale or K = 0 */
+    double weight_sum;         /* sum w (= the statistics' [0]) */
+    int64_t zero_weight;       /* pairs with w == 0 */
+    double robust_rmse;        /* sqrt(sum w |p - q|^2 / sum w); 0 when sum w is not positive */
+} visma_icp_robust_info;
+
+/* The weighted statistics of the last visma_icp_nn_pass (plane == 0: centred frame as visma_icp_reduce; plane != 0:
+ * point-to-plane rows in the world frame). */
+VISMA_ICP_API int visma_icp_reduce_robust(visma_icp_ctx *ctx, const visma_icp_robust *cfg, int plane,
+                                          double out_stats[VISMA_ICP_NSTATS], visma_icp_robust_info *info);
+/* RegistrationICP's loop (Registration.cpp:167-185) with the weighted pass.  Its stop test compares fitness (K / NS,
+ * unweighted) and the ROBUST rmse of consecutive passes.  out->num_correspondences = K, out->fitness and
+ * out->inlier_rmse are the unweighted values of the last pass; *info (may be NULL) is what the weights did there.
+ * One launch sequence per pass; never the persistent launch.  kernel = L2 is visma_icp_run, bit for bit. */
+VISMA_ICP_API int visma_icp_run_robust(visma_icp_ctx *ctx, const double init[16], double max_dist,
+                                       const visma_icp_robust *cfg, int plane, int max_iter, double rel_fitness,
+                                       double rel_rmse, int with_scaling, visma_icp_result *out,
+                                       visma_icp_robust_info *info);
+/* visma_icp_run_yaw_sweep with every start a robust run (one after the other); the winner is the first start with
+ * strictly the most correspondences K.  per_level / per_level_info / best_info may be NULL.  Afterwards the context
+ * holds the last pass of the LAST start. */
+VISMA_ICP_API int visma_icp_run_yaw_sweep_robust(visma_icp_ctx *ctx, int level, double max_dist,
+                                                 const visma_icp_robust *cfg, int plane, int max_iter,
+                                                 double rel_fitness, double rel_rmse, visma_icp_result *best,
+                                                 int *best_level, visma_icp_result *per_level,
+                                                 visma_icp_robust_info *best_info, visma_icp_robust_info *per_level_info);
+/* w_per_src[i] = the weight of source point i (caller's order, NS entries) in the last robust pass, 0 where the
+ * point has no pair.  VISMA_ICP_ERR_STATE before a robust pass.  (After an L2 run: 1 for every pair.) */
+VISMA_ICP_API int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src);
+
 /* ---- batched small problems (AnnotationTool loop, src/annotation.cpp:103-168) */
 
 typedef struct {

@@ -16,6 +16,10 @@
 //   open3d::cicp::TransformationEstimationPointToPointTrimmed(keep)
 //                                      trimmed ICP through RegistrationICP: only the keep * |source| closest pairs
 //                                      of every iteration enter the solve (a model against a partial scan)
+//   open3d::cicp::TransformationEstimationPointToPointRobust(kernel) / ...PointToPlaneRobust(kernel)
+//                                      robust ICP through RegistrationICP: every pair weighted by a function of its
+//                                      own residual (cicp::RobustKernel: Huber, Tukey, Cauchy; the scale from the
+//                                      median residual unless given) -- no overlap share needed
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -123,6 +127,63 @@ public:
                                                  const PointCloud &target,
                                                  const CorrespondenceSet &corres) const override;
     double keep_ = 1.0;
+};
+
+// Robust ICP (visma_icp_run_robust; visma_icp.h states weights and scale): an M-estimator in place of the least-squares
+// objective -- every pair of an iteration is weighted by a function of its own residual.  What later Open3D versions
+// call RobustKernel.  scale = 0: the scale comes from the median residual of every pass (tune = 0: the family's
+// 95 %-efficiency constant), so nothing about the overlap has to be known.
+struct RobustKernel {
+    enum Type { L2 = VISMA_ICP_ROBUST_L2, Huber = VISMA_ICP_ROBUST_HUBER, Tukey = VISMA_ICP_ROBUST_TUKEY, Cauchy = VISMA_ICP_ROBUST_CAUCHY };
+    RobustKernel(Type type_ = Tukey, double scale_ = 0.0, double tune_ = 0.0, double min_scale_ = 0.0)
+        : type(type_), scale(scale_), tune(tune_), min_scale(min_scale_) {}
+    Type type;
+    double scale = 0, tune = 0, min_scale = 0;
+    visma_icp_robust c_config() const
+    {
+        visma_icp_robust c;
+        c.kernel = (int)type; c.scale = scale; c.tune = tune; c.min_scale = min_scale;
+        return c;
+    }
+};
+
+// What cicp::RegistrationICP returns for the two robust estimators:
+//   correspondence_set_  all K pairs of the last pass (their weights: visma_icp_get_pair_weights on the thread context)
+//   fitness_             K / |source|, unweighted
+//   inlier_rmse_         the ROBUST rmse sqrt(sum w |p - q|^2 / sum w) (what the loop's stop test looks at)
+// ComputeTransformation(source, target, corres) solves unweighted over the corres it is given, like the other estimators.
+class TransformationEstimationPointToPointRobust : public TransformationEstimation {
+public:
+    explicit TransformationEstimationPointToPointRobust(const RobustKernel &kernel = RobustKernel(), bool with_scaling = false)
+        : kernel_(kernel), with_scaling_(with_scaling) {}
+    ~TransformationEstimationPointToPointRobust() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPoint;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    RobustKernel kernel_;
+    bool with_scaling_ = false;
+};
+
+class TransformationEstimationPointToPlaneRobust : public TransformationEstimation {
+public:
+    explicit TransformationEstimationPointToPlaneRobust(const RobustKernel &kernel = RobustKernel()) : kernel_(kernel) {}
+    ~TransformationEstimationPointToPlaneRobust() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPlane;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    RobustKernel kernel_;
 };
 
 namespace detail {
@@ -432,6 +493,19 @@ inline RegistrationResult RegistrationICP(
         detail::fill_result_trimmed(ctx, r, info, source.points_.size(), result);
         return result;
     }
+    if (dyn == typeid(TransformationEstimationPointToPointRobust) || dyn == typeid(TransformationEstimationPointToPlaneRobust)) {
+        const auto *rp = plane ? nullptr : static_cast<const TransformationEstimationPointToPointRobust *>(&estimation);
+        const visma_icp_robust cfg = plane ? static_cast<const TransformationEstimationPointToPlaneRobust *>(&estimation)->kernel_.c_config()
+                                           : rp->kernel_.c_config();
+        visma_icp_robust_info info;
+        detail::check(ctx, visma_icp_run_robust(ctx, T, max_correspondence_distance, &cfg, plane ? 1 : 0, criteria.max_iteration_,
+                                                criteria.relative_fitness_, criteria.relative_rmse_,
+                                                rp && rp->with_scaling_ ? 1 : 0, &r, &info),
+                      "visma_icp_run_robust");
+        detail::fill_result(ctx, r, source.points_.size(), result);
+        result.inlier_rmse_ = info.robust_rmse;
+        return result;
+    }
     if (four || p2p) {
         const bool scaling = four ? four->with_scaling_ : p2p->with_scaling_;
         detail::check(ctx, visma_icp_run(ctx, T, max_correspondence_distance, criteria.max_iteration_,
@@ -486,10 +560,49 @@ inline Eigen::Matrix4d RegisterModelToScene(const PointCloud &model, const Point
                                             int rotation_level, double distance_threshold,
                                             bool point_to_plane = false,
                                             RegistrationResult *best_out = nullptr,
-                                            bool upright = false, double keep = 1.0)
+                                            bool upright = false, double keep = 1.0,
+                                            const cicp::RobustKernel *robust = nullptr)
 {
     RegistrationResult best;
     const Eigen::Vector3d up = Eigen::Vector3d::UnitY();
+    if (robust && keep != 1.0) {
+        std::fprintf(stderr, "Error: RegisterModelToScene takes robust weights or keep < 1, not both.\n");
+        return best.transformation_;
+    }
+    if (robust && rotation_level > 0 && distance_threshold > 0.0 && (!point_to_plane || (model.HasNormals() && scene.HasNormals()))) {
+        // a robust ICP from every start, the winner by K as always; *best_out: the robust estimator's result of the winning start
+        visma_icp_ctx *ctx = detail::upload(model, scene, point_to_plane, distance_threshold);
+        detail::AxisScope axis(ctx, upright ? &up : nullptr);
+        const ICPConvergenceCriteria c;
+        const visma_icp_robust cfg = robust->c_config();
+        visma_icp_result b;
+        visma_icp_robust_info bi;
+        int level = -1;
+        detail::check(ctx, visma_icp_run_yaw_sweep_robust(ctx, rotation_level, distance_threshold, &cfg, point_to_plane ? 1 : 0,
+                                                          c.max_iteration_, c.relative_fitness_, c.relative_rmse_, &b, &level,
+                                                          nullptr, &bi, nullptr),
+                      "visma_icp_run_yaw_sweep_robust");
+        best.transformation_ = detail::from_rowmajor(b.transformation);
+        best.fitness_ = b.fitness;
+        best.inlier_rmse_ = bi.robust_rmse;
+        if (best_out) {
+            *best_out = best;
+            if (level >= 0) {
+                // one robust pass at the winning transform materialises its pairs (and their weights on the context)
+                visma_icp_result r;
+                visma_icp_robust_info ri;
+                detail::check(ctx, visma_icp_run_robust(ctx, b.transformation, distance_threshold, &cfg, point_to_plane ? 1 : 0, 0,
+                                                        0.0, 0.0, 0, &r, &ri), "visma_icp_run_robust");
+                detail::fill_result(ctx, r, model.points_.size(), *best_out);
+                best_out->inlier_rmse_ = ri.robust_rmse;
+            }
+        }
+        return best.transformation_;
+    }
+    if (robust && point_to_plane) {
+        std::fprintf(stderr, "Error: TransformationEstimationPointToPlane requires pre-computed normal vectors.\n");
+        return best.transformation_;
+    }
     if (keep != 1.0 && !(keep > 0.0 && keep < 1.0)) {
         std::fprintf(stderr, "Error: RegisterModelToScene requires keep in (0, 1].\n");
         return best.transformation_;
@@ -870,6 +983,31 @@ inline Eigen::Matrix4d TransformationEstimationPointToPointTrimmed::ComputeTrans
     const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
 {
     return detail::host_update(source, target, corres, false, false);
+}
+
+inline double TransformationEstimationPointToPointRobust::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_rmse_point_to_point(source, target, corres);
+}
+
+inline Eigen::Matrix4d TransformationEstimationPointToPointRobust::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_update(source, target, corres, false, with_scaling_);
+}
+
+inline double TransformationEstimationPointToPlaneRobust::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    return detail::host_rmse_point_to_plane(source, target, corres);
+}
+
+inline Eigen::Matrix4d TransformationEstimationPointToPlaneRobust::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    if (!target.HasNormals()) return Eigen::Matrix4d::Identity();
+    return detail::host_update(source, target, corres, true, false);
 }
 
 // ---- the estimators constrained to a rotation about up_ ----------------------

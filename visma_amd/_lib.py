@@ -211,6 +211,15 @@ def _bind(L):
                                                       C.c_double, C.c_int, C.POINTER(CResult), C.POINTER(C.c_int),
                                                       C.POINTER(CResult), _tp, _tp]
         L.visma_icp_get_kept_mask.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
+    if hasattr(L, "visma_icp_run_robust"):               # (A/B runs load older builds through VISMA_ICP_LIB)
+        _rc, _ri = C.POINTER(CRobust), C.POINTER(CRobustInfo)
+        L.visma_icp_reduce_robust.argtypes = [C.c_void_p, _rc, C.c_int, _dp, _ri]
+        L.visma_icp_run_robust.argtypes = [C.c_void_p, _dp, C.c_double, _rc, C.c_int, C.c_int, C.c_double, C.c_double,
+                                           C.c_int, C.POINTER(CResult), _ri]
+        L.visma_icp_run_yaw_sweep_robust.argtypes = [C.c_void_p, C.c_int, C.c_double, _rc, C.c_int, C.c_int, C.c_double,
+                                                     C.c_double, C.POINTER(CResult), C.POINTER(C.c_int),
+                                                     C.POINTER(CResult), _ri, _ri]
+        L.visma_icp_get_pair_weights.argtypes = [C.c_void_p, _dp]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -258,6 +267,43 @@ class TrimInfo:
 
     def __repr__(self):
         return "TrimInfo(kept=%d, trimmed_rmse=%.6g, d2_cut=%.6g)" % (self.kept, self.trimmed_rmse, self.d2_cut)
+
+
+ROBUST_L2, ROBUST_HUBER, ROBUST_TUKEY, ROBUST_CAUCHY = 0, 1, 2, 3
+_ROBUST_NAMES = {"l2": ROBUST_L2, "huber": ROBUST_HUBER, "tukey": ROBUST_TUKEY, "cauchy": ROBUST_CAUCHY}
+
+
+class CRobust(C.Structure):
+    """visma_icp_robust"""
+    _fields_ = [("kernel", C.c_int), ("scale", C.c_double), ("tune", C.c_double), ("min_scale", C.c_double)]
+
+
+class CRobustInfo(C.Structure):
+    """visma_icp_robust_info"""
+    _fields_ = [("scale", C.c_double), ("median_residual", C.c_double), ("weight_sum", C.c_double),
+                ("zero_weight", C.c_int64), ("robust_rmse", C.c_double)]
+
+
+def _robust(kernel, scale, tune, min_scale):
+    if isinstance(kernel, str):
+        kernel = _ROBUST_NAMES[kernel.lower()]
+    return CRobust(int(kernel), float(scale), float(tune), float(min_scale))
+
+
+class RobustInfo:
+    """What the weights of a robust pass did: the scale c, the median residual it came from (automatic scale), the sum
+    of the weights, the pairs with weight 0 and the weighted rmse."""
+
+    def __init__(self, c):
+        self.scale = float(c.scale)
+        self.median_residual = float(c.median_residual)
+        self.weight_sum = float(c.weight_sum)
+        self.zero_weight = int(c.zero_weight)
+        self.robust_rmse = float(c.robust_rmse)
+
+    def __repr__(self):
+        return "RobustInfo(scale=%.6g, median_residual=%.6g, weight_sum=%.6g, zero_weight=%d, robust_rmse=%.6g)" % (
+            self.scale, self.median_residual, self.weight_sum, self.zero_weight, self.robust_rmse)
 
 
 class Result:
@@ -461,6 +507,45 @@ class Context:
         rs = []
         for p, i in zip(per, pi):
             r = Result(p); r.trim = TrimInfo(i); rs.append(r)
+        return rb, bl.value, rs
+
+    def reduce_robust(self, kernel, scale=0.0, tune=0.0, min_scale=0.0, plane=False):
+        """The statistics of the last nn_pass with every pair weighted by its residual (kernel: ROBUST_* or "huber",
+        "tukey", "cauchy", "l2"; scale 0: from the median residual) -> (stats, RobustInfo)."""
+        st = np.empty(NSTATS); info = CRobustInfo(); cfg = _robust(kernel, scale, tune, min_scale)
+        self._chk(self.L.visma_icp_reduce_robust(self._h, C.byref(cfg), int(bool(plane)), _p(st, _dp), C.byref(info)))
+        return st, RobustInfo(info)
+
+    def pair_weights(self):
+        """float64 per source point (caller's order): its weight in the last robust pass, 0 without a pair."""
+        w = np.zeros(max(self.ns, 1))
+        self._chk(self.L.visma_icp_get_pair_weights(self._h, _p(w, _dp)))
+        return w[:self.ns]
+
+    def run_robust(self, init=None, max_dist=0.05, kernel=ROBUST_TUKEY, scale=0.0, tune=0.0, min_scale=0.0, plane=False,
+                   max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6, with_scaling=False):
+        """Robust ICP: every pair weighted by a function of its own residual; no overlap share is needed.
+        -> Result with .robust (RobustInfo)."""
+        init = _f64(np.eye(4) if init is None else init, (16,))
+        out = CResult(); info = CRobustInfo(); cfg = _robust(kernel, scale, tune, min_scale)
+        self._chk(self.L.visma_icp_run_robust(self._h, _p(init, _dp), float(max_dist), C.byref(cfg), int(bool(plane)),
+                                              int(max_iter), float(rel_fitness), float(rel_rmse), int(bool(with_scaling)),
+                                              C.byref(out), C.byref(info)))
+        r = Result(out)
+        r.robust = RobustInfo(info)
+        return r
+
+    def run_yaw_sweep_robust(self, level, max_dist, kernel=ROBUST_TUKEY, scale=0.0, tune=0.0, min_scale=0.0, plane=False,
+                             max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+        best = CResult(); bl = C.c_int(-1); per = (CResult * level)()
+        bi = CRobustInfo(); pi = (CRobustInfo * level)(); cfg = _robust(kernel, scale, tune, min_scale)
+        self._chk(self.L.visma_icp_run_yaw_sweep_robust(self._h, int(level), float(max_dist), C.byref(cfg), int(bool(plane)),
+                                                        int(max_iter), float(rel_fitness), float(rel_rmse), C.byref(best),
+                                                        C.byref(bl), per, C.byref(bi), pi))
+        rb = Result(best); rb.robust = RobustInfo(bi)
+        rs = []
+        for p, i in zip(per, pi):
+            r = Result(p); r.robust = RobustInfo(i); rs.append(r)
         return rb, bl.value, rs
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):

@@ -768,6 +768,140 @@ int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src)
     return VISMA_ICP_OK;
 }
 
+// ---- robust ICP -----------------------------------------------------------------------------------------------------
+// the configuration as the engine takes it (tune resolved); everything that is wrong with it before any pass
+static int check_robust(visma_icp_ctx *ctx, const visma_icp_robust *cfg, Engine::RobustConfig *rc_out)
+{
+    if (!cfg) return ctx->fail(VISMA_ICP_ERR_INVALID, "robust configuration is NULL");
+    if (cfg->kernel < VISMA_ICP_ROBUST_L2 || cfg->kernel > VISMA_ICP_ROBUST_CAUCHY)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown robust kernel");
+    if (!std::isfinite(cfg->scale) || cfg->scale < 0.0) return ctx->fail(VISMA_ICP_ERR_INVALID, "robust scale must be finite and >= 0");
+    if (!std::isfinite(cfg->tune) || cfg->tune < 0.0) return ctx->fail(VISMA_ICP_ERR_INVALID, "robust tune must be finite and >= 0");
+    if (!std::isfinite(cfg->min_scale) || cfg->min_scale < 0.0)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "robust min_scale must be finite and >= 0");
+    if (ctx->sharded() || ctx->eng->is_sharded())
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "robust ICP runs on one rank: a median across ranks is not available");
+    if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
+    rc_out->kernel = cfg->kernel;
+    rc_out->scale = cfg->scale;
+    rc_out->min_scale = cfg->min_scale;
+    rc_out->tune = cfg->tune;
+    if (cfg->tune == 0.0)   // the 95 %-efficiency constants (Holland & Welsch 1977)
+        rc_out->tune = cfg->kernel == VISMA_ICP_ROBUST_HUBER ? 1.345 : cfg->kernel == VISMA_ICP_ROBUST_TUKEY ? 4.685 : 2.385;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_reduce_robust(visma_icp_ctx *ctx, const visma_icp_robust *cfg, int plane, double out_stats[VISMA_ICP_NSTATS],
+                            visma_icp_robust_info *info)
+{
+    CTX_CHECK();
+    if (!out_stats || !info) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    Engine::RobustConfig rc_cfg;
+    if (int rc = check_robust(ctx, cfg, &rc_cfg)) return rc;
+    if (plane && !ctx->eng->has_normals()) return ctx->fail(VISMA_ICP_ERR_STATE, "point-to-plane needs target normals");
+    if (rc_cfg.kernel == VISMA_ICP_ROBUST_L2) {
+        // every weight is 1: the plain statistics
+        const double zero[3] = {0, 0, 0};
+        int rc = ctx->eng->reduce(ctx->last_Tc, plane != 0, plane ? ctx->centre : zero, out_stats);
+        if (rc) return ctx->eng_fail(rc);
+        ctx->robust_state = 2;
+        std::memset(info, 0, sizeof(*info));
+        info->weight_sum = out_stats[0];
+        info->robust_rmse = visma_icp_ctx::trimmed_rmse(out_stats);
+        return VISMA_ICP_OK;
+    }
+    Engine::RobustPass rp;
+    int rc = ctx->eng->reduce_robust(ctx->last_Tc, plane ? ctx->centre : nullptr, plane != 0, rc_cfg, out_stats, &rp);
+    if (rc) return ctx->eng_fail(rc);
+    ctx->robust_state = 1;
+    ctx->last_plane = plane != 0;
+    visma_icp_ctx::fill_robust_info(info, out_stats, rp);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_run_robust(visma_icp_ctx *ctx, const double init[16], double max_dist, const visma_icp_robust *cfg, int plane,
+                         int max_iter, double rel_fitness, double rel_rmse, int with_scaling, visma_icp_result *out,
+                         visma_icp_robust_info *info)
+{
+    CTX_CHECK();
+    if (!init || !out || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad run arguments");
+    Engine::RobustConfig rc_cfg;
+    if (int rc = check_robust(ctx, cfg, &rc_cfg)) return rc;
+    if (!plane) { if (int rc = ctx->check_axis_solver(VISMA_ICP_SOLVER_KABSCH, with_scaling != 0)) return rc; }
+    if (rc_cfg.kernel == VISMA_ICP_ROBUST_L2) {
+        // every weight is 1: the plain run, bit for bit
+        int rc = plane ? ctx->run(init, max_dist, max_iter, rel_fitness, rel_rmse, VISMA_ICP_SOLVER_GN_EULER, false, true, out)
+                       : ctx->run(init, max_dist, max_iter, rel_fitness, rel_rmse, VISMA_ICP_SOLVER_KABSCH, with_scaling != 0, false, out);
+        if (rc) return rc;
+        const bool ran = max_dist > 0.0 && !(plane && !ctx->eng->has_normals());
+        ctx->robust_state = ran ? 2 : 0;
+        if (info) {
+            std::memset(info, 0, sizeof(*info));
+            info->weight_sum = (double)out->num_correspondences;
+            info->robust_rmse = out->inlier_rmse;
+        }
+        return VISMA_ICP_OK;
+    }
+    return ctx->run_robust(init, max_dist, rc_cfg, plane != 0, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, info);
+}
+
+int visma_icp_run_yaw_sweep_robust(visma_icp_ctx *ctx, int level, double max_dist, const visma_icp_robust *cfg, int plane,
+                                   int max_iter, double rel_fitness, double rel_rmse, visma_icp_result *best, int *best_level,
+                                   visma_icp_result *per_level, visma_icp_robust_info *best_info,
+                                   visma_icp_robust_info *per_level_info)
+{
+    CTX_CHECK();
+    if (level <= 0 || !best || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad sweep arguments");
+    Engine::RobustConfig rc_cfg;
+    if (int rc = check_robust(ctx, cfg, &rc_cfg)) return rc;
+    // src/annotation.cpp:35-61, one start after the other
+    const double interval = 2.0 * M_PI / (double)level;
+    visma_icp_result b;
+    visma_icp_robust_info bi;
+    std::memset(&b, 0, sizeof(b));
+    std::memset(&bi, 0, sizeof(bi));
+    const Mat4 I = Mat4::identity();
+    std::memcpy(b.transformation, I.m, sizeof(I.m));
+    int bl = -1;
+    for (int i = 0; i < level; i++) {
+        const double a = interval * i, c = std::cos(a), s = std::sin(a);
+        Mat4 init = Mat4::identity();
+        init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
+        visma_icp_result r;
+        visma_icp_robust_info ri;
+        int rc = visma_icp_run_robust(ctx, init.m, max_dist, cfg, plane, max_iter, rel_fitness, rel_rmse, 0, &r, &ri);
+        if (rc) return rc;
+        if (per_level) per_level[i] = r;
+        if (per_level_info) per_level_info[i] = ri;
+        if (r.num_correspondences > b.num_correspondences) { b = r; bi = ri; bl = i; }   // strict >
+    }
+    *best = b;
+    if (best_info) *best_info = bi;
+    if (best_level) *best_level = bl;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src)
+{
+    CTX_CHECK();
+    if (!w_per_src) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output buffer");
+    if (ctx->robust_state == 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no robust pass yet");
+    const int64_t ns = ctx->eng->ns();
+    std::vector<double> w((size_t)std::max<int64_t>(ns, 1));
+    if (ctx->robust_state == 2) {
+        std::vector<int32_t> idx((size_t)std::max<int64_t>(ns, 1));
+        int rc = ctx->eng->get_correspondences(idx.data(), nullptr);
+        if (rc) return ctx->eng_fail(rc);
+        for (int64_t i = 0; i < ns; i++) w[(size_t)i] = idx[(size_t)i] >= 0 ? 1.0 : 0.0;
+    } else {
+        int rc = ctx->eng->get_pair_weights(w.data());
+        if (rc) return ctx->eng_fail(rc);
+    }
+    const int32_t *order = ctx->order_ptr();
+    for (int64_t pos = 0; pos < ns; pos++) w_per_src[order ? order[pos] : pos] = w[(size_t)pos];
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, int steps, int solver,
                       int with_scaling, visma_icp_result *out)
 {

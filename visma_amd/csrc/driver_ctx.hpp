@@ -37,6 +37,7 @@ struct visma_icp_ctx {
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)
     unsigned long long src_order_gen = 0;   // advanced with every change of src_order (the engine keeps a device copy)
     int trim_state = 0;               // the last trimmed pass: 0 none, 1 on the engine, 2 plain pass with every pair kept
+    int robust_state = 0;             // the last robust pass: 0 none, 1 on the engine, 2 plain pass (L2: every weight 1)
     double last_aux_kernel_ms = 0.0;  // kernel time of the last mesh-distance call
     double last_aux_build_ms = 0.0;   // ... and of building its search structure
     int mesh_method = 0;              // 0 choose, 1 brute force, 2 BVH
@@ -187,6 +188,74 @@ struct visma_icp_ctx {
         out->iterations = it;
         out->nn_passes = it + 1;
         if (info) { info->kept = tr.kept; info->trimmed_rmse = trmse; info->d2_cut = tr.d2_cut; }
+        return VISMA_ICP_OK;
+    }
+
+    // one NN pass + weighted reduction: the weighted stats; fitness and rmse over all K, unweighted; *rp what the weights did
+    int pass_robust(const Mat4 &Tc, double max_dist, const Engine::RobustConfig &cfg, bool plane, double *stats, double *fit,
+                    double *rmse, Engine::RobustPass *rp)
+    {
+        int rc = eng->nn_pass(Tc, max_dist);
+        if (rc) return eng_fail(rc);
+        last_Tc = Tc;
+        last_plane = plane;
+        rc = eng->reduce_robust(Tc, plane ? centre : nullptr, plane, cfg, stats, rp);   // (point-to-plane: world frame, as pass())
+        if (rc) return eng_fail(rc);
+        robust_state = 1;
+        const int64_t denom = ns_total > 0 ? ns_total : eng->ns();
+        if (rp->found > 0) {
+            *fit = (double)rp->found / (double)denom;
+            *rmse = std::sqrt(rp->sum_all / (double)rp->found);
+        } else {
+            *fit = 0.0;
+            *rmse = 0.0;
+        }
+        return VISMA_ICP_OK;
+    }
+    static void fill_robust_info(visma_icp_robust_info *info, const double *stats, const Engine::RobustPass &rp)
+    {
+        info->scale = rp.scale;
+        info->median_residual = std::sqrt(rp.v);
+        info->weight_sum = stats[0];
+        info->zero_weight = rp.zero_weight;
+        info->robust_rmse = trimmed_rmse(stats);
+    }
+
+    // RegistrationICP's loop with the weighted pass; the stop test looks at fitness and the ROBUST rmse
+    int run_robust(const double *init, double max_dist, const Engine::RobustConfig &cfg, bool plane, int max_iter,
+                   double rel_fit, double rel_rmse, bool scaling, visma_icp_result *out, visma_icp_robust_info *info)
+    {
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out->transformation, init, sizeof(double) * 16);
+        if (info) std::memset(info, 0, sizeof(*info));
+        if (!(max_dist > 0.0)) return VISMA_ICP_OK;                 // Registration.cpp:148-151
+        last_radius = max_dist;
+        if (plane && !eng->has_normals()) return VISMA_ICP_OK;      // Registration.cpp:152-157
+        Mat4 Tc = to_centred(Mat4::from(init), centre);
+        double stats[VISMA_ICP_NSTATS], fit, rmse;
+        Engine::RobustPass rp;
+        int rc = pass_robust(Tc, max_dist, cfg, plane, stats, &fit, &rmse, &rp);
+        if (rc) return rc;
+        double wrmse = trimmed_rmse(stats);
+        int it = 0;
+        for (int i = 0; i < max_iter; i++) {
+            const Mat4 upd = solve(stats, VISMA_ICP_SOLVER_KABSCH, scaling, plane);
+            Tc = apply_update(upd, Tc, plane);
+            const double bfit = fit, brmse = wrmse;
+            rc = pass_robust(Tc, max_dist, cfg, plane, stats, &fit, &rmse, &rp);
+            if (rc) return rc;
+            wrmse = trimmed_rmse(stats);
+            it = i + 1;
+            if (std::fabs(bfit - fit) < rel_fit && std::fabs(brmse - wrmse) < rel_rmse) break;
+        }
+        const Mat4 T = from_centred(Tc, centre);
+        std::memcpy(out->transformation, T.m, sizeof(T.m));
+        out->fitness = fit;
+        out->inlier_rmse = rmse;
+        out->num_correspondences = rp.found;
+        out->iterations = it;
+        out->nn_passes = it + 1;
+        if (info) fill_robust_info(info, stats, rp);
         return VISMA_ICP_OK;
     }
 

@@ -296,6 +296,30 @@ public:
     // 1 per kept source POSITION of the last trimmed pass
     virtual int get_kept_mask(uint8_t *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     virtual bool is_sharded() const { return false; }
+    // Robust ICP (robust.hip): the pending pass's search, then the statistics with every pair weighted by a function of
+    // its own residual (|p - q|, or |(p - q) . n| with `plane`).  cfg as the driver checked it, tune resolved (> 0 or
+    // unused); scale == 0: c = max(tune * 1.4826 * median residual, min_scale), per pass.
+    struct RobustConfig {
+        int kernel = 0;                 // VISMA_ICP_ROBUST_HUBER / TUKEY / CAUCHY
+        double scale = 0.0, tune = 0.0, min_scale = 0.0;
+    };
+    struct RobustPass {
+        int64_t found = 0;              // K
+        double sum_all = 0.0;           // sum of |p - q|^2 over all K pairs (inlier_rmse)
+        double scale = 0.0;             // c of this pass
+        double v = 0.0;                 // automatic scale: the squared median residual as ranked (fp32 value); else 0
+        int64_t zero_weight = 0;        // pairs with w == 0
+        double weight_sum = 0.0;        // = stats[0]
+        double sum_wr2 = 0.0;           // sum of w r^2
+    };
+    virtual int reduce_robust(const Mat4 &, const double * /* offset[3] */, bool /* plane */, const RobustConfig &,
+                              double * /* stats */, RobustPass *)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // the weight per source POSITION of the last robust pass (0 where a position has no pair)
+    virtual int get_pair_weights(double *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

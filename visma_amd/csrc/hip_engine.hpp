@@ -48,6 +48,8 @@ public:
         if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
         free_dev(d_trim_work_); free_dev(d_trim_partials_); free_dev(d_trim_mask_); free_dev(d_trim_order_);
         if (h_trim_) (void)hipHostFree(h_trim_);
+        free_dev(d_rob_work_); free_dev(d_rob_partials_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
+        if (h_rob_) (void)hipHostFree(h_rob_);
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -313,6 +315,16 @@ public:
     unsigned long long trim_order_gen_ = ~0ull, trim_seq_ = 0;
     const int32_t *trim_order_src_ = nullptr;
     bool trim_dirty_ = false;                              // a pass did not run to its end: the work words are cleared
+
+    // robust ICP (robust.hip): the plain pass, then (automatic scale) the median select and the weighted reduction
+    int reduce_robust(const Mat4 &Tc, const double *offset, bool plane, const RobustConfig &cfg, double *stats,
+                      RobustPass *out) override;
+    int get_pair_weights(double *w) override;
+    void *d_rob_work_ = nullptr, *d_rob_partials_ = nullptr, *d_rob_w_ = nullptr, *d_rob_r2_ = nullptr;
+    double *h_rob_ = nullptr, *h_rob_dev_ = nullptr;       // mapped: kRobustPublished granules {value, sequence number}
+    int64_t rob_w_cap_ = 0, rob_r2_cap_ = 0, rob_w_ns_ = -1;
+    unsigned long long rob_seq_ = 0;
+    bool rob_dirty_ = false;                               // a pass did not run to its end: the work words are cleared
 
     int run_loop_batch(const LoopParams &lp, const std::vector<BatchProblem> &pb, LoopResult *out) override;
 

@@ -684,6 +684,126 @@ int HipEngine::get_kept_mask(uint8_t *mask)
     return VISMA_ICP_OK;
 }
 
+// One robust pass: the plain pass as reduce() runs it (K, the sum of d^2 over all K pairs, the warm-start state), then
+// -- automatic scale -- the three select launches for the median (point-to-plane: over the residuals a small kernel
+// writes first, point-to-point: over the pass's own d2) and the weighted reduction, all on the stream; the host waits
+// for the tagged granules of the weighted reduction like reduce() waits for its own.
+int HipEngine::reduce_robust(const Mat4 &Tc, const double *offset, bool plane, const RobustConfig &cfg, double *stats,
+                             RobustPass *out)
+{
+    if (is_sharded()) { err_ = "robust ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    if (!have_pass_) { err_ = "reduce before nn_pass"; return VISMA_ICP_ERR_STATE; }
+    if (view_offset_ != 0) { err_ = "robust reduction needs an nn_pass of its own"; return VISMA_ICP_ERR_STATE; }
+    if (plane && !d_nrm_) { err_ = "point-to-plane needs target normals"; return VISMA_ICP_ERR_STATE; }
+    const double zero[3] = {0, 0, 0};
+    if (!offset) offset = zero;
+    double all[kNStats];
+    int rc = reduce(Tc, false, offset, all);
+    if (rc) return rc;
+    if (sess_live_) { rc = end_session(); if (rc) return rc; }   // (never behind a launch that waits for this thread)
+    HIP_TRY(hipSetDevice(device_));
+    const int64_t K = (int64_t)std::llround(all[0]);
+    *out = RobustPass();
+    out->found = K;
+    out->sum_all = all[1];
+    if (!d_rob_work_) {
+        HIP_TRY(hipMalloc(&d_rob_work_, sizeof(unsigned) * kTrimWorkWords));
+        HIP_TRY(hipMalloc(&d_rob_partials_, sizeof(double) * kRobustRow * 1024));
+        HIP_TRY(hipHostMalloc((void **)&h_rob_, sizeof(double) * 2 * kRobustPublished, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(h_rob_, 0, sizeof(double) * 2 * kRobustPublished);
+        HIP_TRY(hipHostGetDevicePointer((void **)&h_rob_dev_, h_rob_, 0));
+        rob_dirty_ = true;
+    }
+    if (ns_ > rob_w_cap_) {
+        free_dev(d_rob_w_);
+        HIP_TRY(hipMalloc(&d_rob_w_, sizeof(double) * (size_t)std::max<int64_t>(ns_, 1)));
+        rob_w_cap_ = ns_;
+    }
+    rob_w_ns_ = -1;                                          // (until this pass has written every weight)
+    const bool automatic = cfg.scale == 0.0 && K > 0;        // (K == 0: c = min_scale, nothing to rank)
+    if (automatic && plane && ns_ > rob_r2_cap_) {
+        free_dev(d_rob_r2_);
+        HIP_TRY(hipMalloc(&d_rob_r2_, sizeof(float) * (size_t)std::max<int64_t>(ns_, 1)));
+        rob_r2_cap_ = ns_;
+    }
+    if (rob_dirty_) HIP_TRY(hipMemsetAsync(d_rob_work_, 0, sizeof(unsigned) * kTrimWorkWords, stream_));
+    rob_dirty_ = true;
+    RobustArgs a;
+    // the coordinates the plain pass summed from: the f64 copies where the search ran on them
+    const bool s64 = use_grid_ ? f64_views() : brute_exact();
+    if (s64) { a.src64 = (const Pt64 *)d_src64_; a.tgt64 = (const Pt64 *)d_tgt64_; a.nrm64 = (const Pt64 *)d_nrm64_; }
+    if (s64 && !a.tgt64) { err_ = "robust reduction: no f64 target"; return VISMA_ICP_ERR_STATE; }
+    a.src = (const float4 *)d_src_; a.tgt = (const float4 *)d_tgt_;
+    a.nrm = (const float4 *)d_nrm_;
+    a.idx = (const int32_t *)d_idx_;
+    a.ns = ns_;
+    for (int i = 0; i < 12; i++) a.T64.m[i] = Tc.m[i];
+    for (int k = 0; k < 3; k++) a.off.v[k] = offset[k];
+    a.kernel = cfg.kernel;
+    a.auto_scale = automatic ? 1 : 0;
+    a.scale = cfg.scale == 0.0 ? cfg.min_scale : cfg.scale;  // (read only without the select)
+    a.tune_k = cfg.tune * 1.4826;
+    a.min_scale = cfg.min_scale;
+    a.select_work = (const unsigned *)d_rob_work_;
+    a.ticket = (unsigned *)d_rob_work_ + kTrimHistWords + 3; // (the select's rounds take tickets 0 .. 2)
+    a.r2_out = (float *)d_rob_r2_;
+    a.w_out = (double *)d_rob_w_;
+    a.partials = (double *)d_rob_partials_;
+    a.host_out = h_rob_dev_;
+    if (automatic) {
+        // the lower median: the m-th smallest ranking value, m = (K + 1) / 2; only its value is used, never the tie order
+        const unsigned m = (unsigned)((K + 1) / 2);
+        const float *rank = (const float *)d_d2_;
+        if (plane) {
+            HIP_TRY(launch_robust_residual(a, stream_));
+            rank = (const float *)d_rob_r2_;
+        }
+        HIP_TRY(launch_trim_select(rank, (const int32_t *)d_idx_, nullptr, ns_, m, (unsigned *)d_rob_work_, stream_));
+    }
+    const unsigned long long seq = ++rob_seq_;
+    a.seq = seq;
+    HIP_TRY(launch_robust_reduce(a, plane ? 1 : 0, stream_));
+    volatile unsigned long long *g = reinterpret_cast<volatile unsigned long long *>(h_rob_);
+    auto all_tagged = [&]() {
+        for (int i = kRobustPublished - 1; i >= 0; --i)
+            if (g[2 * i + 1] != seq) return false;
+        return true;
+    };
+    bool seen = false;
+    for (long long spin = 0; spin < 400000000ll && !seen; ++spin) {
+        seen = all_tagged();
+        if (!seen && (spin & 0xFFFFFll) == 0xFFFFFll && hipStreamQuery(stream_) != hipErrorNotReady) { seen = all_tagged(); break; }
+    }
+    if (!seen) {
+        HIP_TRY(hipStreamSynchronize(stream_));   // surfaces a kernel fault, if any
+        if (!all_tagged()) { err_ = "robust statistics were not published"; return VISMA_ICP_ERR_HIP; }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    double pub[kRobustPublished];
+    for (int i = 0; i < kRobustPublished; i++) {
+        const unsigned long long v = g[2 * i];
+        std::memcpy(&pub[i], &v, sizeof(double));
+    }
+    rob_dirty_ = false;
+    rob_w_ns_ = ns_;
+    for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
+    out->scale = pub[kNStats];
+    out->v = pub[kNStats + 1];
+    out->zero_weight = (int64_t)std::llround(pub[kNStats + 2]);
+    out->weight_sum = pub[0];
+    out->sum_wr2 = pub[kNStats + 3];
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::get_pair_weights(double *w)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (rob_w_ns_ != ns_ || !d_rob_w_) { err_ = "no robust pass yet"; return VISMA_ICP_ERR_STATE; }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (ns_ > 0) HIP_TRY(hipMemcpy(w, d_rob_w_, sizeof(double) * (size_t)ns_, hipMemcpyDeviceToHost));
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

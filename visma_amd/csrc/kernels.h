@@ -548,6 +548,34 @@ hipError_t launch_trim_select(const float *d2, const int32_t *idx, const int32_t
                               hipStream_t stream);
 hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream);
 
+// ---- robust ICP (robust.hip): every pair of the last pass weighted by a function of its own residual ----
+constexpr int kRobustL2 = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3;   // = VISMA_ICP_ROBUST_*
+constexpr int kRobustRow = 32;                         // doubles per partial row: Acc<PLANE>::N + pairs with w == 0 + sum w r^2
+constexpr int kRobustPublished = kNStats + 4;          // granules to the host: 38 statistics, c, v, pairs with w == 0, sum w r^2
+struct RobustArgs {
+    const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
+    const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
+    const float4 *nrm = nullptr;                       // target normals by original index (point-to-plane), and ...
+    const Pt64 *nrm64 = nullptr;                       // ... in f64 where the f64 passes read them
+    const int32_t *idx = nullptr;                      // the pass's winners per source position (< 0: no pair)
+    int64_t ns = 0;
+    Xform64 T64{};
+    Offset64 off{};
+    int kernel = kRobustHuber;                         // kRobustHuber / Tukey / Cauchy
+    int auto_scale = 0;                                // 0: c = scale; 1: c = max(tune_k * sqrt(v), min_scale), v from the select
+    double scale = 0.0, tune_k = 0.0, min_scale = 0.0; // tune_k = tune * 1.4826
+    const unsigned *select_work = nullptr;             // the select's work words (kTrimWorkWords): its state holds v's bits
+    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
+    float *r2_out = nullptr;                           // residual kernel: (float)(r^2) per source position
+    double *w_out = nullptr;                           // out: the weight per source position (0: no pair)
+    double *partials = nullptr;                        // robust_reduce_blocks(ns) rows of kRobustRow
+    double *host_out = nullptr;                        // mapped host memory: kRobustPublished granules {value, seq}
+    unsigned long long seq = 0;
+};
+int robust_reduce_blocks(int64_t ns);
+hipError_t launch_robust_residual(const RobustArgs &a, hipStream_t stream);
+hipError_t launch_robust_reduce(const RobustArgs &a, int plane, hipStream_t stream);
+
 // fill n float4 with +inf (target padding)
 hipError_t launch_fill_inf(float4 *dst, int64_t n, hipStream_t stream);
 // AoS stride-s floats -> float4 (w = 0)
