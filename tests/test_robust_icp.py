@@ -709,6 +709,72 @@ def test_two_robust_runs_are_bit_identical(lib, plane):
     assert _same(a, b) and np.array_equal(wa, wb) and _same_info(a.robust, b.robust)
 
 
+def _pair_pass_outputs(c, T, radius, step):
+    """one nn_pass + one trimmed or robust reduction -> every value it returns, as bit patterns"""
+    kind, kw = step
+    c.nn_pass(T, radius)
+    if kind == "trimmed":
+        st, info = c.reduce_trimmed(kw["keep"])
+        fields = [float(info.kept), info.trimmed_rmse, info.d2_cut]
+        per_src = c.kept_mask().astype(np.uint8)
+    else:
+        st, info = c.reduce_robust(kw["kernel"], scale=kw.get("scale", 0.0), plane=kw.get("plane", False))
+        fields = [info.scale, info.median_residual, info.weight_sum, float(info.zero_weight), info.robust_rmse]
+        per_src = c.pair_weights().view(np.uint64)
+    return st.view(np.uint64).copy(), np.array(fields, np.float64).view(np.uint64), per_src.copy(), info
+
+
+@pytest.mark.gpu
+def test_trimmed_and_robust_passes_share_one_context(lib):
+    """The trimmed and the robust pass work in ONE set of work words, partial rows and host granules per context.
+    Passes of both kinds in turn on one context -- the early return that launches nothing and the reduction without a
+    select among them -- must each return what the same call returns on a fresh context, bit for bit: statistics,
+    info, kept mask, weights.  16,500 sources give 65 partial rows, the smallest count at which a thread of the fold
+    takes a second trip.  (No keep alone makes m = 0 -- below 3 pairs m is min(K, 3) --, so the early return is
+    reached with a radius that finds no pair; the smallest keep at the working radius, m = 3, runs as well.)"""
+    rng = np.random.default_rng(165)
+    src, tgt = _clouds(rng, 16500, 4096)
+    nrm = _unit_normals(rng, len(tgt))
+    T = _rand_T(rng, 0.1, 0.05)
+    r, r_none = 0.15, 1e-6
+    steps = [
+        (("trimmed", dict(keep=0.5)), r),
+        (("robust", dict(kernel=TUKEY, plane=True)), r),                    # automatic scale, point-to-plane
+        (("trimmed", dict(keep=1e-6)), r),                                  # floor(keep * ns) = 0: m = 3
+        (("trimmed", dict(keep=1e-6)), r_none),                             # K = 0, m = 0: nothing is launched
+        (("robust", dict(kernel=HUBER, scale=r / 3.0)), r),                 # fixed scale, point-to-point
+        (("robust", dict(kernel=TUKEY)), r_none),                           # K = 0: the reduction without the select
+        (("trimmed", dict(keep=0.9)), r),
+    ]
+
+    def context():
+        c = lib.Context(0)
+        c.set_target(tgt)
+        c.set_source(src)
+        c.set_target_normals_f64(nrm)
+        return c
+
+    shared = context()
+    for step, radius in steps:
+        got = _pair_pass_outputs(shared, T, radius, step)
+        fresh = context()
+        want = _pair_pass_outputs(fresh, T, radius, step)
+        fresh.close()
+        for g, w in zip(got[:3], want[:3]):
+            assert np.array_equal(g, w), (step, radius)
+        info = got[3]
+        if step[0] == "trimmed":                       # (the cases are what they claim to be)
+            if radius == r_none:
+                assert info.kept == 0
+            elif step[1]["keep"] == 1e-6:
+                assert info.kept == 3
+            else:
+                assert info.kept > 3
+        else:
+            assert (info.weight_sum > 0.0) == (radius == r)
+    shared.close()
+
+
 @pytest.mark.gpu
 def test_sweep_equals_single_runs(lib):
     src, tgt, _, _ = synth.make_pair(5000, 20000)

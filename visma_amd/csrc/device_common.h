@@ -97,6 +97,14 @@ __device__ __forceinline__ double load_agent_f64(const double *p)
                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return __longlong_as_double((long long)v);
 }
+__device__ __forceinline__ unsigned ld_agent_u32(const unsigned *p)
+{
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_agent_u32(unsigned *p, unsigned v)
+{
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -227,7 +235,7 @@ __device__ __forceinline__ double wave_sum_multi(double *v)
 }
 
 // wavefront shuffle reduction -> LDS across the 4 waves -> one partial row
-// (row = nullptr: partials + blockIdx.x * kReduceAcc; agent: write-through stores for the fused fold)
+// (row = nullptr: partials + blockIdx.x * STRIDE; agent: write-through stores for the fused fold)
 // the thread's number in its workgroup; OPAQUE: as a value the compiler cannot see through (inside the loop of the
 // persistent kernel everything derived from threadIdx.x alone was hoisted out of the loop and spilled)
 template <bool OPAQUE, int NTH = kBlock>
@@ -251,7 +259,7 @@ __device__ __forceinline__ void store_granule_agent(u4_t *dst, double v, unsigne
     asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(dst), "v"(g) : "memory");
 }
 
-template <int NACC, int NWAVES = kBlock / 64, bool OPAQUE_TID = false>
+template <int NACC, int NWAVES = kBlock / 64, bool OPAQUE_TID = false, int STRIDE = kReduceAcc>
 __device__ __forceinline__ void block_reduce_store(double *acc, double *partials, bool agent = false, void *tagged_row = nullptr,
                                                    unsigned tag = 0u)
 {
@@ -271,7 +279,7 @@ __device__ __forceinline__ void block_reduce_store(double *acc, double *partials
             //  an acknowledgement, the group's reducer polls for the tag)
             store_granule_agent(reinterpret_cast<u4_t *>(tagged_row) + (long long)blockIdx.x * 32 + tidx, v, tag);
         } else {
-            double *dst = partials + (long long)blockIdx.x * kReduceAcc + tidx;
+            double *dst = partials + (long long)blockIdx.x * STRIDE + tidx;
             if (agent) store_agent_f64(dst, v);
             else *dst = v;
         }
@@ -356,18 +364,73 @@ __device__ __forceinline__ void fold_partials(const double *__restrict__ partial
 // global_store_dwordx4, so the host can accept a value as soon as its tag shows
 // the expected sequence number -- no system-scope fence (whose L2 write-back of
 // the launch's ~2 MB of dirty index output cost ~10 us per iteration).
+// N: the values published (the pair passes append a few of their own to the statistics)
+template <int N = kNStats>
 __device__ __forceinline__ void publish_tagged_stats(const double *stats, double *host_out,
                                                      unsigned long long seq)
 {
     typedef unsigned int u4 __attribute__((ext_vector_type(4)));
     __syncthreads();                                   // stats[] was written by thread 0
-    if (threadIdx.x < kNStats) {
+    if (threadIdx.x < N) {
         const unsigned long long v = (unsigned long long)__double_as_longlong(stats[threadIdx.x]);
         u4 g;
         g.x = (unsigned)v; g.y = (unsigned)(v >> 32);
         g.z = (unsigned)seq; g.w = (unsigned)(seq >> 32);
         __builtin_nontemporal_store(g, reinterpret_cast<u4 *>(host_out) + threadIdx.x);
     }
+}
+
+// The tail of a pass over the pairs of the last nn_pass (trim.hip, robust.hip; 256 threads).  Every workgroup has stored
+// its partial row (STRIDE doubles, NCOL <= 32 of them used, agent-scope stores) at partials[blockIdx.x * STRIDE].  The
+// hand-off of the agent-scope recipe: every storing wave drains, one relaxed agent atomic as the ticket, the last
+// workgroup to arrive acquires and re-arms the ticket for the next pass.  That workgroup alone returns true, with the
+// column totals in tot[0 .. 32) (LDS): thread (sg, sa) sums rows sg, sg + 8, ... of column sa, eight independent loads
+// at a time, then the eight sums are added in order.  The order of the additions is fixed and is part of the result:
+// a run is bit-identical to itself (and NOT to fused_fold, whose two levels group the rows differently).
+template <int NCOL, int STRIDE>
+__device__ __forceinline__ bool pair_pass_fold(const double *partials, unsigned *ticket, double *tot)
+{
+    constexpr int NG = 256 / 32;
+    __shared__ double f_part[NG][33];
+    __shared__ int last;
+    const int tid = threadIdx.x;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave drains
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = t == gridDim.x - 1u ? 1 : 0;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            st_agent_u32(ticket, 0u);                        // re-armed for the next pass
+        }
+    }
+    __syncthreads();
+    if (!last) return false;
+    const int sa = tid & 31, sg = tid >> 5;
+    {
+        double v = 0.0;
+        if (sa < NCOL)
+            for (int r0 = sg; r0 < (int)gridDim.x; r0 += 8 * NG) {
+                double w[8];
+#pragma unroll
+                for (int u = 0; u < 8; u++) {
+                    const int r = r0 + u * NG;
+                    w[u] = r < (int)gridDim.x ? load_agent_f64(partials + (long long)r * STRIDE + sa) : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < 8; u++) v += w[u];
+            }
+        f_part[sg][sa] = v;
+    }
+    __syncthreads();
+    if (tid < 32) {
+        double t = 0.0;
+#pragma unroll
+        for (int gg = 0; gg < NG; gg++) t += f_part[gg][tid];
+        tot[tid] = t;
+    }
+    __syncthreads();
+    return true;
 }
 
 // One rank's part of the one-shot all-reduce over xGMI (see ipc_allreduce_kernel in kernels.hip): lane a

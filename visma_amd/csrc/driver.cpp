@@ -194,6 +194,55 @@ void morton_order(std::vector<float> &pts, int64_t n, std::vector<int32_t> &orde
 
 }  // namespace
 
+// ---- what the yaw sweeps and the per-source outputs share ------------------------------------------------------------
+// start i of `level` yaw starts (src/annotation.cpp:35-39): the rotation by i * 2 pi / level about the y axis
+static Mat4 yaw_start(int i, int level)
+{
+    const double interval = 2.0 * M_PI / (double)level;
+    const double a = interval * i, c = std::cos(a), s = std::sin(a);
+    Mat4 init = Mat4::identity();
+    init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
+    return init;
+}
+
+struct NoInfo {};
+// src/annotation.cpp:35-61, one start after the other: run_one(init, &result, &info) per start, the start with the most
+// correspondences wins (strict >: the first of equals)
+template <class Info, class RunOne>
+static int sweep_sequential(int level, RunOne run_one, visma_icp_result *best, int *best_level, visma_icp_result *per_level,
+                            Info *best_info = nullptr, Info *per_level_info = nullptr)
+{
+    visma_icp_result b;
+    Info bi;
+    std::memset(&b, 0, sizeof(b));
+    std::memset(&bi, 0, sizeof(bi));
+    const Mat4 I = Mat4::identity();
+    std::memcpy(b.transformation, I.m, sizeof(I.m));
+    int bl = -1;
+    for (int i = 0; i < level; i++) {
+        visma_icp_result r;
+        Info ri;
+        int rc = run_one(yaw_start(i, level), &r, &ri);
+        if (rc) return rc;
+        if (per_level) per_level[i] = r;
+        if (per_level_info) per_level_info[i] = ri;
+        if (r.num_correspondences > b.num_correspondences) { b = r; bi = ri; bl = i; }   // strict >
+    }
+    *best = b;
+    if (best_info) *best_info = bi;
+    if (best_level) *best_level = bl;
+    return VISMA_ICP_OK;
+}
+
+// a value per engine position -> per caller's source index
+template <class T>
+static void scatter_by_order(const visma_icp_ctx *ctx, const std::vector<T> &by_pos, T *per_src)
+{
+    const int32_t *order = ctx->order_ptr();
+    const int64_t ns = ctx->eng->ns();
+    for (int64_t pos = 0; pos < ns; pos++) per_src[order ? order[pos] : pos] = by_pos[(size_t)pos];
+}
+
 extern "C" {
 
 const char *visma_icp_version(void) { return "visma-icp-mi355x 0.1 (gfx950)"; }
@@ -669,9 +718,7 @@ int visma_icp_reduce_trimmed(visma_icp_ctx *ctx, double keep, double out_stats[V
     int rc = ctx->eng->reduce_trimmed(ctx->last_Tc, nullptr, keep, ctx->order_ptr(), ctx->src_order_gen, out_stats, &tr);
     if (rc) return ctx->eng_fail(rc);
     ctx->trim_state = 1;
-    info->kept = tr.kept;
-    info->trimmed_rmse = visma_icp_ctx::trimmed_rmse(out_stats);
-    info->d2_cut = tr.d2_cut;
+    visma_icp_ctx::fill_trim_info(info, out_stats, tr);
     return VISMA_ICP_OK;
 }
 
@@ -707,7 +754,12 @@ int visma_icp_run_trimmed(visma_icp_ctx *ctx, const double init[16], double max_
         }
         return VISMA_ICP_OK;
     }
-    return ctx->run_trimmed(init, max_dist, keep, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, info);
+    if (info) std::memset(info, 0, sizeof(*info));
+    Engine::TrimPass tr;
+    return ctx->run_pair_passes(
+        init, max_dist, false, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, &ctx->trim_state, tr,
+        [&](const Mat4 &Tc, double *stats) { return ctx->eng->reduce_trimmed(Tc, nullptr, keep, ctx->order_ptr(), ctx->src_order_gen, stats, &tr); },
+        [&](const double *stats) { if (info) visma_icp_ctx::fill_trim_info(info, stats, tr); });
 }
 
 int visma_icp_run_yaw_sweep_trimmed(visma_icp_ctx *ctx, int level, double max_dist, double keep, int max_iter,
@@ -720,31 +772,9 @@ int visma_icp_run_yaw_sweep_trimmed(visma_icp_ctx *ctx, int level, double max_di
     if (solver != VISMA_ICP_SOLVER_KABSCH) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimmed ICP: the closed-form solver only");
     if (int rc = ctx->check_axis_solver(solver, false)) return rc;
     if (int rc = check_trimmed(ctx, keep)) return rc;
-    // src/annotation.cpp:35-61, one start after the other
-    const double interval = 2.0 * M_PI / (double)level;
-    visma_icp_result b;
-    visma_icp_trim_info bi;
-    std::memset(&b, 0, sizeof(b));
-    std::memset(&bi, 0, sizeof(bi));
-    const Mat4 I = Mat4::identity();
-    std::memcpy(b.transformation, I.m, sizeof(I.m));
-    int bl = -1;
-    for (int i = 0; i < level; i++) {
-        const double a = interval * i, c = std::cos(a), s = std::sin(a);
-        Mat4 init = Mat4::identity();
-        init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
-        visma_icp_result r;
-        visma_icp_trim_info ri;
-        int rc = visma_icp_run_trimmed(ctx, init.m, max_dist, keep, max_iter, rel_fitness, rel_rmse, solver, 0, &r, &ri);
-        if (rc) return rc;
-        if (per_level) per_level[i] = r;
-        if (per_level_info) per_level_info[i] = ri;
-        if (r.num_correspondences > b.num_correspondences) { b = r; bi = ri; bl = i; }   // strict >
-    }
-    *best = b;
-    if (best_info) *best_info = bi;
-    if (best_level) *best_level = bl;
-    return VISMA_ICP_OK;
+    return sweep_sequential(level, [&](const Mat4 &init, visma_icp_result *r, visma_icp_trim_info *ri) {
+        return visma_icp_run_trimmed(ctx, init.m, max_dist, keep, max_iter, rel_fitness, rel_rmse, solver, 0, r, ri);
+    }, best, best_level, per_level, best_info, per_level_info);
 }
 
 int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src)
@@ -763,8 +793,7 @@ int visma_icp_get_kept_mask(visma_icp_ctx *ctx, uint8_t *kept_per_src)
         int rc = ctx->eng->get_kept_mask(mask.data());
         if (rc) return ctx->eng_fail(rc);
     }
-    const int32_t *order = ctx->order_ptr();
-    for (int64_t pos = 0; pos < ns; pos++) kept_per_src[order ? order[pos] : pos] = mask[(size_t)pos];
+    scatter_by_order(ctx, mask, kept_per_src);
     return VISMA_ICP_OK;
 }
 
@@ -842,7 +871,12 @@ int visma_icp_run_robust(visma_icp_ctx *ctx, const double init[16], double max_d
         }
         return VISMA_ICP_OK;
     }
-    return ctx->run_robust(init, max_dist, rc_cfg, plane != 0, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, info);
+    if (info) std::memset(info, 0, sizeof(*info));
+    Engine::RobustPass rp;
+    return ctx->run_pair_passes(
+        init, max_dist, plane != 0, max_iter, rel_fitness, rel_rmse, with_scaling != 0, out, &ctx->robust_state, rp,
+        [&](const Mat4 &Tc, double *stats) { return ctx->eng->reduce_robust(Tc, plane ? ctx->centre : nullptr, plane != 0, rc_cfg, stats, &rp); },
+        [&](const double *stats) { if (info) visma_icp_ctx::fill_robust_info(info, stats, rp); });
 }
 
 int visma_icp_run_yaw_sweep_robust(visma_icp_ctx *ctx, int level, double max_dist, const visma_icp_robust *cfg, int plane,
@@ -854,31 +888,9 @@ int visma_icp_run_yaw_sweep_robust(visma_icp_ctx *ctx, int level, double max_dis
     if (level <= 0 || !best || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad sweep arguments");
     Engine::RobustConfig rc_cfg;
     if (int rc = check_robust(ctx, cfg, &rc_cfg)) return rc;
-    // src/annotation.cpp:35-61, one start after the other
-    const double interval = 2.0 * M_PI / (double)level;
-    visma_icp_result b;
-    visma_icp_robust_info bi;
-    std::memset(&b, 0, sizeof(b));
-    std::memset(&bi, 0, sizeof(bi));
-    const Mat4 I = Mat4::identity();
-    std::memcpy(b.transformation, I.m, sizeof(I.m));
-    int bl = -1;
-    for (int i = 0; i < level; i++) {
-        const double a = interval * i, c = std::cos(a), s = std::sin(a);
-        Mat4 init = Mat4::identity();
-        init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
-        visma_icp_result r;
-        visma_icp_robust_info ri;
-        int rc = visma_icp_run_robust(ctx, init.m, max_dist, cfg, plane, max_iter, rel_fitness, rel_rmse, 0, &r, &ri);
-        if (rc) return rc;
-        if (per_level) per_level[i] = r;
-        if (per_level_info) per_level_info[i] = ri;
-        if (r.num_correspondences > b.num_correspondences) { b = r; bi = ri; bl = i; }   // strict >
-    }
-    *best = b;
-    if (best_info) *best_info = bi;
-    if (best_level) *best_level = bl;
-    return VISMA_ICP_OK;
+    return sweep_sequential(level, [&](const Mat4 &init, visma_icp_result *r, visma_icp_robust_info *ri) {
+        return visma_icp_run_robust(ctx, init.m, max_dist, cfg, plane, max_iter, rel_fitness, rel_rmse, 0, r, ri);
+    }, best, best_level, per_level, best_info, per_level_info);
 }
 
 int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src)
@@ -897,8 +909,7 @@ int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src)
         int rc = ctx->eng->get_pair_weights(w.data());
         if (rc) return ctx->eng_fail(rc);
     }
-    const int32_t *order = ctx->order_ptr();
-    for (int64_t pos = 0; pos < ns; pos++) w_per_src[order ? order[pos] : pos] = w[(size_t)pos];
+    scatter_by_order(ctx, w, w_per_src);
     return VISMA_ICP_OK;
 }
 
@@ -1001,33 +1012,23 @@ static int yaw_sweep(visma_icp_ctx *ctx, int level, double max_dist, int max_ite
     if (level <= 0 || !best || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad sweep arguments");
     if (plane && ctx->have_tgt && !ctx->eng->has_normals() && max_dist > 0.0) {
         // Registration.cpp:152-157: every start returns RegistrationResult(init); none has correspondences
-        const double interval0 = 2.0 * M_PI / (double)level;
         std::memset(best, 0, sizeof(*best));
         const Mat4 I = Mat4::identity();
         std::memcpy(best->transformation, I.m, sizeof(I.m));
         if (best_level) *best_level = -1;
         for (int i = 0; per_level && i < level; i++) {
-            const double a = interval0 * i, c = std::cos(a), s = std::sin(a);
-            Mat4 init = Mat4::identity();
-            init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
+            const Mat4 init = yaw_start(i, level);
             std::memset(&per_level[i], 0, sizeof(per_level[i]));
             std::memcpy(per_level[i].transformation, init.m, sizeof(init.m));
         }
         return VISMA_ICP_OK;
     }
     // src/annotation.cpp:35-61
-    const double interval = 2.0 * M_PI / (double)level;
     if (ctx->use_device_loop_batched() && max_dist > 0.0 && ctx->have_src && ctx->have_tgt) {
         // all `level` ICPs in flight together: one launch per iteration covers every
         // (yaw, source point) pair over the shared grid, `level` solves run in parallel
-        std::vector<Mat4> inits((size_t)level), Tc0((size_t)level);
-        for (int i = 0; i < level; i++) {
-            const double a = interval * i, c = std::cos(a), s = std::sin(a);
-            Mat4 init = Mat4::identity();
-            init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
-            inits[i] = init;
-            Tc0[i] = to_centred(init, ctx->centre);
-        }
+        std::vector<Mat4> Tc0((size_t)level);
+        for (int i = 0; i < level; i++) Tc0[i] = to_centred(yaw_start(i, level), ctx->centre);
         Engine::LoopParams lp;
         lp.Tc0 = Tc0[0];
         std::memcpy(lp.centre, ctx->centre, sizeof(ctx->centre));
@@ -1066,24 +1067,9 @@ static int yaw_sweep(visma_icp_ctx *ctx, int level, double max_dist, int max_ite
         if (rc != VISMA_ICP_ERR_STATE) return ctx->eng_fail(rc);
         // (brute-force search selected, or RCCL attached): fall through to the sequential sweep
     }
-    visma_icp_result b;
-    std::memset(&b, 0, sizeof(b));
-    const Mat4 I = Mat4::identity();
-    std::memcpy(b.transformation, I.m, sizeof(I.m));
-    int bl = -1;
-    for (int i = 0; i < level; i++) {
-        const double a = interval * i, c = std::cos(a), s = std::sin(a);
-        Mat4 init = Mat4::identity();
-        init(0, 0) = c; init(0, 2) = s; init(2, 0) = -s; init(2, 2) = c;
-        visma_icp_result r;
-        int rc = ctx->run(init.m, max_dist, max_iter, rel_fitness, rel_rmse, solver, false, plane, &r);
-        if (rc) return rc;
-        if (per_level) per_level[i] = r;
-        if (r.num_correspondences > b.num_correspondences) { b = r; bl = i; }
-    }
-    *best = b;
-    if (best_level) *best_level = bl;
-    return VISMA_ICP_OK;
+    return sweep_sequential<NoInfo>(level, [&](const Mat4 &init, visma_icp_result *r, NoInfo *) {
+        return ctx->run(init.m, max_dist, max_iter, rel_fitness, rel_rmse, solver, false, plane, r);
+    }, best, best_level, per_level);
 }
 
 // normals == NULL: the point-to-point estimator with `solver`; otherwise normals[i] are the target

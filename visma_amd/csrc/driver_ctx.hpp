@@ -79,16 +79,8 @@ struct visma_icp_ctx {
             if (host_allreduce(host_allreduce_user, stats, VISMA_ICP_NSTATS) != 0)
                 return fail(VISMA_ICP_ERR_ENGINE, "host all-reduce callback failed");
         }
-        const double K = stats[0];
-        const int64_t denom = ns_total > 0 ? ns_total : eng->ns();
-        *k = (int64_t)std::llround(K);
-        if (K > 0.0) {  // Registration.cpp:87-94
-            *fit = K / (double)denom;
-            *rmse = std::sqrt(stats[1] / K);
-        } else {
-            *fit = 0.0;
-            *rmse = 0.0;
-        }
+        *k = (int64_t)std::llround(stats[0]);
+        fit_rmse(stats[0], stats[1], fit, rmse);
         return VISMA_ICP_OK;
     }
 
@@ -131,86 +123,20 @@ struct visma_icp_ctx {
 
     const int32_t *order_ptr() const { return (int64_t)src_order.size() == eng->ns() && eng->ns() > 0 ? src_order.data() : nullptr; }
 
-    // one NN pass + trimmed reduction: stats over the kept pairs; fitness and rmse over all K; *tr what was kept
-    int pass_trimmed(const Mat4 &Tc, double max_dist, double keep, double *stats, double *fit, double *rmse,
-                     Engine::TrimPass *tr)
+    // fitness and inlier_rmse over all K pairs of a pass (Registration.cpp:87-94)
+    void fit_rmse(double K, double sum_d2, double *fit, double *rmse) const
     {
-        int rc = eng->nn_pass(Tc, max_dist);
-        if (rc) return eng_fail(rc);
-        last_Tc = Tc;
-        last_plane = false;
-        rc = eng->reduce_trimmed(Tc, nullptr, keep, order_ptr(), src_order_gen, stats, tr);
-        if (rc) return eng_fail(rc);
-        trim_state = 1;
         const int64_t denom = ns_total > 0 ? ns_total : eng->ns();
-        if (tr->found > 0) {
-            *fit = (double)tr->found / (double)denom;
-            *rmse = std::sqrt(tr->sum_all / (double)tr->found);
-        } else {
-            *fit = 0.0;
-            *rmse = 0.0;
-        }
-        return VISMA_ICP_OK;
+        *fit = K > 0.0 ? K / (double)denom : 0.0;
+        *rmse = K > 0.0 ? std::sqrt(sum_d2 / K) : 0.0;
     }
+    // the rmse of a trimmed or weighted pass's own statistics
     static double trimmed_rmse(const double *stats) { return stats[0] > 0.0 ? std::sqrt(stats[1] / stats[0]) : 0.0; }
-
-    // RegistrationICP's loop with the trimmed pass; the stop test looks at fitness and the TRIMMED rmse
-    int run_trimmed(const double *init, double max_dist, double keep, int max_iter, double rel_fit, double rel_rmse,
-                    bool scaling, visma_icp_result *out, visma_icp_trim_info *info)
+    static void fill_trim_info(visma_icp_trim_info *info, const double *stats, const Engine::TrimPass &tr)
     {
-        std::memset(out, 0, sizeof(*out));
-        std::memcpy(out->transformation, init, sizeof(double) * 16);
-        if (info) std::memset(info, 0, sizeof(*info));
-        if (!(max_dist > 0.0)) return VISMA_ICP_OK;                 // Registration.cpp:148-151
-        last_radius = max_dist;
-        Mat4 Tc = to_centred(Mat4::from(init), centre);
-        double stats[VISMA_ICP_NSTATS], fit, rmse;
-        Engine::TrimPass tr;
-        int rc = pass_trimmed(Tc, max_dist, keep, stats, &fit, &rmse, &tr);
-        if (rc) return rc;
-        double trmse = trimmed_rmse(stats);
-        int it = 0;
-        for (int i = 0; i < max_iter; i++) {
-            const Mat4 upd = solve(stats, VISMA_ICP_SOLVER_KABSCH, scaling, false);
-            Tc = apply_update(upd, Tc, false);
-            const double bfit = fit, brmse = trmse;
-            rc = pass_trimmed(Tc, max_dist, keep, stats, &fit, &rmse, &tr);
-            if (rc) return rc;
-            trmse = trimmed_rmse(stats);
-            it = i + 1;
-            if (std::fabs(bfit - fit) < rel_fit && std::fabs(brmse - trmse) < rel_rmse) break;
-        }
-        const Mat4 T = from_centred(Tc, centre);
-        std::memcpy(out->transformation, T.m, sizeof(T.m));
-        out->fitness = fit;
-        out->inlier_rmse = rmse;
-        out->num_correspondences = tr.found;
-        out->iterations = it;
-        out->nn_passes = it + 1;
-        if (info) { info->kept = tr.kept; info->trimmed_rmse = trmse; info->d2_cut = tr.d2_cut; }
-        return VISMA_ICP_OK;
-    }
-
-    // one NN pass + weighted reduction: the weighted stats; fitness and rmse over all K, unweighted; *rp what the weights did
-    int pass_robust(const Mat4 &Tc, double max_dist, const Engine::RobustConfig &cfg, bool plane, double *stats, double *fit,
-                    double *rmse, Engine::RobustPass *rp)
-    {
-        int rc = eng->nn_pass(Tc, max_dist);
-        if (rc) return eng_fail(rc);
-        last_Tc = Tc;
-        last_plane = plane;
-        rc = eng->reduce_robust(Tc, plane ? centre : nullptr, plane, cfg, stats, rp);   // (point-to-plane: world frame, as pass())
-        if (rc) return eng_fail(rc);
-        robust_state = 1;
-        const int64_t denom = ns_total > 0 ? ns_total : eng->ns();
-        if (rp->found > 0) {
-            *fit = (double)rp->found / (double)denom;
-            *rmse = std::sqrt(rp->sum_all / (double)rp->found);
-        } else {
-            *fit = 0.0;
-            *rmse = 0.0;
-        }
-        return VISMA_ICP_OK;
+        info->kept = tr.kept;
+        info->trimmed_rmse = trimmed_rmse(stats);
+        info->d2_cut = tr.d2_cut;
     }
     static void fill_robust_info(visma_icp_robust_info *info, const double *stats, const Engine::RobustPass &rp)
     {
@@ -221,41 +147,54 @@ struct visma_icp_ctx {
         info->robust_rmse = trimmed_rmse(stats);
     }
 
-    // RegistrationICP's loop with the weighted pass; the stop test looks at fitness and the ROBUST rmse
-    int run_robust(const double *init, double max_dist, const Engine::RobustConfig &cfg, bool plane, int max_iter,
-                   double rel_fit, double rel_rmse, bool scaling, visma_icp_result *out, visma_icp_robust_info *info)
+    // RegistrationICP's loop around a pass over the pairs (trimmed, robust).  reduce(Tc, stats) is the engine's reduction
+    // behind each NN pass: its statistics feed the solve, `pp` (filled by it) has K and the sum over all K pairs for
+    // fitness and inlier_rmse.  The stop test looks at fitness and the rmse of the pass's OWN statistics.  *state: 1 once
+    // a pass ran on the engine.  fill_info(stats) runs behind the last pass.
+    template <class Reduce, class FillInfo>
+    int run_pair_passes(const double *init, double max_dist, bool plane, int max_iter, double rel_fit, double rel_rmse,
+                        bool scaling, visma_icp_result *out, int *state, const Engine::PairPass &pp, Reduce reduce,
+                        FillInfo fill_info)
     {
         std::memset(out, 0, sizeof(*out));
         std::memcpy(out->transformation, init, sizeof(double) * 16);
-        if (info) std::memset(info, 0, sizeof(*info));
         if (!(max_dist > 0.0)) return VISMA_ICP_OK;                 // Registration.cpp:148-151
         last_radius = max_dist;
         if (plane && !eng->has_normals()) return VISMA_ICP_OK;      // Registration.cpp:152-157
         Mat4 Tc = to_centred(Mat4::from(init), centre);
-        double stats[VISMA_ICP_NSTATS], fit, rmse;
-        Engine::RobustPass rp;
-        int rc = pass_robust(Tc, max_dist, cfg, plane, stats, &fit, &rmse, &rp);
+        double stats[VISMA_ICP_NSTATS], fit = 0.0, rmse = 0.0, own = 0.0;
+        auto pass = [&]() -> int {
+            int rc = eng->nn_pass(Tc, max_dist);
+            if (rc) return eng_fail(rc);
+            last_Tc = Tc;
+            last_plane = plane;
+            rc = reduce(Tc, stats);
+            if (rc) return eng_fail(rc);
+            *state = 1;
+            fit_rmse((double)pp.found, pp.sum_all, &fit, &rmse);
+            own = trimmed_rmse(stats);
+            return VISMA_ICP_OK;
+        };
+        int rc = pass();
         if (rc) return rc;
-        double wrmse = trimmed_rmse(stats);
         int it = 0;
         for (int i = 0; i < max_iter; i++) {
             const Mat4 upd = solve(stats, VISMA_ICP_SOLVER_KABSCH, scaling, plane);
-            Tc = apply_update(upd, Tc, plane);
-            const double bfit = fit, brmse = wrmse;
-            rc = pass_robust(Tc, max_dist, cfg, plane, stats, &fit, &rmse, &rp);
+            Tc = apply_update(upd, Tc, plane);                      // (point-to-plane: world frame, as run())
+            const double bfit = fit, bown = own;
+            rc = pass();
             if (rc) return rc;
-            wrmse = trimmed_rmse(stats);
             it = i + 1;
-            if (std::fabs(bfit - fit) < rel_fit && std::fabs(brmse - wrmse) < rel_rmse) break;
+            if (std::fabs(bfit - fit) < rel_fit && std::fabs(bown - own) < rel_rmse) break;
         }
         const Mat4 T = from_centred(Tc, centre);
         std::memcpy(out->transformation, T.m, sizeof(T.m));
         out->fitness = fit;
         out->inlier_rmse = rmse;
-        out->num_correspondences = rp.found;
+        out->num_correspondences = pp.found;
         out->iterations = it;
         out->nn_passes = it + 1;
-        if (info) fill_robust_info(info, stats, rp);
+        fill_info(stats);
         return VISMA_ICP_OK;
     }
 

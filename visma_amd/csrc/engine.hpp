@@ -276,9 +276,12 @@ public:
     // Trimmed ICP: the pending pass's search, then the statistics over the m pairs with the smallest key
     // (fp32 d2, caller's source index) only -- m = trim_count(K, ns, keep).  `order` (NULL: identity) maps a source
     // position of the engine to the caller's index and is re-read only when `order_gen` changes.
-    struct TrimPass {
-        int64_t found = 0, kept = 0;    // K, m
+    struct PairPass {                   // what the plain pass under a trimmed or robust one found
+        int64_t found = 0;              // K
         double sum_all = 0.0;           // sum of |p - q|^2 over all K pairs (inlier_rmse)
+    };
+    struct TrimPass : PairPass {
+        int64_t kept = 0;               // m
         double d2_cut = 0.0;            // the largest kept fp32 squared distance (0 when m = 0)
     };
     static int64_t trim_count(int64_t K, int64_t ns, double keep)
@@ -303,9 +306,7 @@ public:
         int kernel = 0;                 // VISMA_ICP_ROBUST_HUBER / TUKEY / CAUCHY
         double scale = 0.0, tune = 0.0, min_scale = 0.0;
     };
-    struct RobustPass {
-        int64_t found = 0;              // K
-        double sum_all = 0.0;           // sum of |p - q|^2 over all K pairs (inlier_rmse)
+    struct RobustPass : PairPass {
         double scale = 0.0;             // c of this pass
         double v = 0.0;                 // automatic scale: the squared median residual as ranked (fp32 value); else 0
         int64_t zero_weight = 0;        // pairs with w == 0

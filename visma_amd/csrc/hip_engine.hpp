@@ -46,10 +46,8 @@ public:
         if (h_flag_) (void)hipHostFree(h_flag_);
         free_dev(d_relay_); free_dev(d_timeline_); free_dev(d_peer_table_); free_dev(d_fold_tag_);
         if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
-        free_dev(d_trim_work_); free_dev(d_trim_partials_); free_dev(d_trim_mask_); free_dev(d_trim_order_);
-        if (h_trim_) (void)hipHostFree(h_trim_);
-        free_dev(d_rob_work_); free_dev(d_rob_partials_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
-        if (h_rob_) (void)hipHostFree(h_rob_);
+        free_dev(d_trim_mask_); free_dev(d_trim_order_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
+        pair_.release();
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -309,22 +307,37 @@ public:
                        double *stats, TrimPass *out) override;
     int get_kept_mask(uint8_t *mask) override;
     bool is_sharded() const override { return comm_ != nullptr || ipc_n_ > 1 || tshard_ || minreduce_ != nullptr; }
-    void *d_trim_work_ = nullptr, *d_trim_partials_ = nullptr, *d_trim_mask_ = nullptr, *d_trim_order_ = nullptr;
-    double *h_trim_ = nullptr, *h_trim_dev_ = nullptr;     // mapped: kTrimPublished granules {value, sequence number}
+    void *d_trim_mask_ = nullptr, *d_trim_order_ = nullptr;
     int64_t trim_mask_cap_ = 0, trim_order_cap_ = 0, trim_mask_ns_ = -1;
-    unsigned long long trim_order_gen_ = ~0ull, trim_seq_ = 0;
+    unsigned long long trim_order_gen_ = ~0ull;
     const int32_t *trim_order_src_ = nullptr;
-    bool trim_dirty_ = false;                              // a pass did not run to its end: the work words are cleared
 
     // robust ICP (robust.hip): the plain pass, then (automatic scale) the median select and the weighted reduction
     int reduce_robust(const Mat4 &Tc, const double *offset, bool plane, const RobustConfig &cfg, double *stats,
                       RobustPass *out) override;
     int get_pair_weights(double *w) override;
-    void *d_rob_work_ = nullptr, *d_rob_partials_ = nullptr, *d_rob_w_ = nullptr, *d_rob_r2_ = nullptr;
-    double *h_rob_ = nullptr, *h_rob_dev_ = nullptr;       // mapped: kRobustPublished granules {value, sequence number}
+    void *d_rob_w_ = nullptr, *d_rob_r2_ = nullptr;
     int64_t rob_w_cap_ = 0, rob_r2_cap_ = 0, rob_w_ns_ = -1;
-    unsigned long long rob_seq_ = 0;
-    bool rob_dirty_ = false;                               // a pass did not run to its end: the work words are cleared
+
+    // What a pass over the pairs of the last nn_pass works in.  The trimmed and the robust pass share the one instance:
+    // they never overlap on the stream, and each pass re-arms the words it used.  Sized for the larger user.
+    struct PairScratch {
+        unsigned *work = nullptr;                          // kTrimWorkWords: the select's histograms, 4 tickets, its state
+        double *partials = nullptr;                        // 1024 rows of kRobustRow doubles
+        double *host = nullptr, *host_dev = nullptr;       // mapped: kRobustPublished granules {value, sequence number}
+        unsigned long long seq = 0;
+        bool dirty = false;                                // a pass did not run to its end: the work words are cleared
+        hipError_t ensure();
+        hipError_t arm(hipStream_t stream);                // clear if dirty, mark dirty: call before a pass's first launch
+        void disarm() { dirty = false; }                   // ... and this when its granules have arrived
+        void release();
+    } pair_;
+    // the checks and the plain pass under both: K and the sum of d^2 over all pairs in *out (`what`: "trimmed" / "robust")
+    int pair_pass_begin(const char *what, const Mat4 &Tc, const double *offset, bool plane, PairPass *out);
+    // the arguments both reductions share, the scratch included (a new sequence number)
+    int pair_pass_args(const char *what, const Mat4 &Tc, const double *offset, PairPassArgs *a);
+    // spins until the n granules at `host` carry `seq`; their values to out[0 .. n)
+    int wait_granules(const double *host, int n, unsigned long long seq, const char *what, double *out);
 
     int run_loop_batch(const LoopParams &lp, const std::vector<BatchProblem> &pb, LoopResult *out) override;
 

@@ -573,36 +573,111 @@ int HipEngine::get_correspondences(int32_t *idx, float *d2)
     return VISMA_ICP_OK;
 }
 
+// ---- what the trimmed and the robust pass share ----
+hipError_t HipEngine::PairScratch::ensure()
+{
+    if (host_dev) return hipSuccess;
+    hipError_t e = hipMalloc((void **)&work, sizeof(unsigned) * kTrimWorkWords);
+    if (e == hipSuccess) e = hipMalloc((void **)&partials, sizeof(double) * kRobustRow * 1024);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&host, sizeof(double) * 2 * kRobustPublished, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) {
+        std::memset(host, 0, sizeof(double) * 2 * kRobustPublished);
+        e = hipHostGetDevicePointer((void **)&host_dev, host, 0);
+    }
+    if (e != hipSuccess) release();                          // (all or nothing: the next call starts over)
+    dirty = true;
+    return e;
+}
+
+hipError_t HipEngine::PairScratch::arm(hipStream_t stream)
+{
+    const hipError_t e = dirty ? hipMemsetAsync(work, 0, sizeof(unsigned) * kTrimWorkWords, stream) : hipSuccess;
+    dirty = true;
+    return e;
+}
+
+void HipEngine::PairScratch::release()
+{
+    if (work) (void)hipFree(work);
+    if (partials) (void)hipFree(partials);
+    if (host) (void)hipHostFree(host);
+    *this = PairScratch();
+}
+
+static const double kNoOffset[3] = {0, 0, 0};
+
+int HipEngine::pair_pass_begin(const char *what, const Mat4 &Tc, const double *offset, bool plane, PairPass *out)
+{
+    if (is_sharded()) { err_ = std::string(what) + " ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    if (!have_pass_) { err_ = "reduce before nn_pass"; return VISMA_ICP_ERR_STATE; }
+    if (view_offset_ != 0) { err_ = std::string(what) + " reduction needs an nn_pass of its own"; return VISMA_ICP_ERR_STATE; }
+    if (plane && !d_nrm_) { err_ = "point-to-plane needs target normals"; return VISMA_ICP_ERR_STATE; }
+    double all[kNStats];
+    int rc = reduce(Tc, false, offset ? offset : kNoOffset, all);
+    if (rc) return rc;
+    if (sess_live_) { rc = end_session(); if (rc) return rc; }   // (never behind a launch that waits for this thread)
+    HIP_TRY(hipSetDevice(device_));
+    out->found = (int64_t)std::llround(all[0]);
+    out->sum_all = all[1];
+    HIP_TRY(pair_.ensure());
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::pair_pass_args(const char *what, const Mat4 &Tc, const double *offset, PairPassArgs *a)
+{
+    // the coordinates the plain pass summed from: the f64 copies where the search ran on them
+    const bool s64 = use_grid_ ? f64_views() : brute_exact();
+    if (s64) { a->src64 = (const Pt64 *)d_src64_; a->tgt64 = (const Pt64 *)d_tgt64_; }
+    if (s64 && !a->tgt64) { err_ = std::string(what) + " reduction: no f64 target"; return VISMA_ICP_ERR_STATE; }
+    a->src = (const float4 *)d_src_; a->tgt = (const float4 *)d_tgt_;
+    a->idx = (const int32_t *)d_idx_;
+    a->ns = ns_;
+    if (!offset) offset = kNoOffset;
+    for (int i = 0; i < 12; i++) a->T64.m[i] = Tc.m[i];
+    for (int k = 0; k < 3; k++) a->off.v[k] = offset[k];
+    a->partials = pair_.partials;
+    a->host_out = pair_.host_dev;
+    a->seq = ++pair_.seq;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::wait_granules(const double *host, int n, unsigned long long seq, const char *what, double *out)
+{
+    // every granule carries the sequence number it was written for
+    volatile const unsigned long long *g = reinterpret_cast<volatile const unsigned long long *>(host);
+    auto all_tagged = [&]() {
+        for (int i = n - 1; i >= 0; --i)
+            if (g[2 * i + 1] != seq) return false;
+        return true;
+    };
+    bool seen = false;
+    for (long long spin = 0; spin < 400000000ll && !seen; ++spin) {
+        seen = all_tagged();
+        if (!seen && (spin & 0xFFFFFll) == 0xFFFFFll && hipStreamQuery(stream_) != hipErrorNotReady) { seen = all_tagged(); break; }
+    }
+    if (!seen) {
+        HIP_TRY(hipStreamSynchronize(stream_));   // surfaces a kernel fault, if any
+        if (!all_tagged()) { err_ = std::string(what) + " statistics were not published"; return VISMA_ICP_ERR_HIP; }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    for (int i = 0; i < n; i++) {
+        const unsigned long long v = g[2 * i];
+        std::memcpy(&out[i], &v, sizeof(double));
+    }
+    return VISMA_ICP_OK;
+}
+
 // One trimmed pass: the plain pass as reduce() runs it (its statistics over all K pairs are what fitness and inlier_rmse
 // need, and K decides m), then three select launches and the masked reduction over d_idx_ / d_d2_, all on the stream;
 // the host waits for the tagged granules of the masked reduction like reduce() waits for its own.
 int HipEngine::reduce_trimmed(const Mat4 &Tc, const double *offset, double keep, const int32_t *order,
                               unsigned long long order_gen, double *stats, TrimPass *out)
 {
-    if (is_sharded()) { err_ = "trimmed ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
-    if (!have_pass_) { err_ = "reduce before nn_pass"; return VISMA_ICP_ERR_STATE; }
-    if (view_offset_ != 0) { err_ = "trimmed reduction needs an nn_pass of its own"; return VISMA_ICP_ERR_STATE; }
-    const double zero[3] = {0, 0, 0};
-    if (!offset) offset = zero;
-    double all[kNStats];
-    int rc = reduce(Tc, false, offset, all);
+    int rc = pair_pass_begin("trimmed", Tc, offset, false, out);
     if (rc) return rc;
-    if (sess_live_) { rc = end_session(); if (rc) return rc; }   // (never behind a launch that waits for this thread)
-    HIP_TRY(hipSetDevice(device_));
-    const int64_t K = (int64_t)std::llround(all[0]);
-    const int64_t m = trim_count(K, ns_, keep);
-    out->found = K;
+    const int64_t m = trim_count(out->found, ns_, keep);
     out->kept = m;
-    out->sum_all = all[1];
     out->d2_cut = 0.0;
-    if (!d_trim_work_) {
-        HIP_TRY(hipMalloc(&d_trim_work_, sizeof(unsigned) * kTrimWorkWords));
-        HIP_TRY(hipMalloc(&d_trim_partials_, sizeof(double) * kReduceAcc * 1024));
-        HIP_TRY(hipHostMalloc((void **)&h_trim_, sizeof(double) * 2 * kTrimPublished, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(h_trim_, 0, sizeof(double) * 2 * kTrimPublished);
-        HIP_TRY(hipHostGetDevicePointer((void **)&h_trim_dev_, h_trim_, 0));
-        trim_dirty_ = true;
-    }
     if (ns_ > trim_mask_cap_) {
         free_dev(d_trim_mask_);
         HIP_TRY(hipMalloc(&d_trim_mask_, (size_t)std::max<int64_t>(ns_, 1)));
@@ -625,50 +700,20 @@ int HipEngine::reduce_trimmed(const Mat4 &Tc, const double *offset, double keep,
         trim_order_gen_ = order_gen;
         trim_order_src_ = order;
     }
-    if (trim_dirty_) HIP_TRY(hipMemsetAsync(d_trim_work_, 0, sizeof(unsigned) * kTrimWorkWords, stream_));
-    trim_dirty_ = true;
-    const int32_t *d_order = order ? (const int32_t *)d_trim_order_ : nullptr;
-    HIP_TRY(launch_trim_select((const float *)d_d2_, (const int32_t *)d_idx_, d_order, ns_, (unsigned)m, (unsigned *)d_trim_work_, stream_));
     TrimReduceArgs a;
-    // the coordinates the plain pass summed from: the f64 copies where the search ran on them
-    const bool s64 = use_grid_ ? f64_views() : brute_exact();
-    if (s64) { a.src64 = (const Pt64 *)d_src64_; a.tgt64 = (const Pt64 *)d_tgt64_; }
-    if (s64 && !a.tgt64) { err_ = "trimmed reduction: no f64 target"; return VISMA_ICP_ERR_STATE; }
-    a.src = (const float4 *)d_src_; a.tgt = (const float4 *)d_tgt_;
-    a.idx = (const int32_t *)d_idx_; a.d2 = (const float *)d_d2_;
-    a.order = d_order;
-    a.ns = ns_;
-    for (int i = 0; i < 12; i++) a.T64.m[i] = Tc.m[i];
-    for (int k = 0; k < 3; k++) a.off.v[k] = offset[k];
-    a.work = (unsigned *)d_trim_work_;
+    rc = pair_pass_args("trimmed", Tc, offset, &a);
+    if (rc) return rc;
+    a.d2 = (const float *)d_d2_;
+    a.order = order ? (const int32_t *)d_trim_order_ : nullptr;
+    a.work = pair_.work;
     a.mask = (unsigned char *)d_trim_mask_;
-    a.partials = (double *)d_trim_partials_;
-    a.host_out = h_trim_dev_;
-    const unsigned long long seq = ++trim_seq_;
-    a.seq = seq;
+    HIP_TRY(pair_.arm(stream_));
+    HIP_TRY(launch_trim_select(a.d2, a.idx, a.order, ns_, (unsigned)m, a.work, stream_));
     HIP_TRY(launch_trim_reduce(a, stream_));
-    volatile unsigned long long *g = reinterpret_cast<volatile unsigned long long *>(h_trim_);
-    auto all_tagged = [&]() {
-        for (int i = kTrimPublished - 1; i >= 0; --i)
-            if (g[2 * i + 1] != seq) return false;
-        return true;
-    };
-    bool seen = false;
-    for (long long spin = 0; spin < 400000000ll && !seen; ++spin) {
-        seen = all_tagged();
-        if (!seen && (spin & 0xFFFFFll) == 0xFFFFFll && hipStreamQuery(stream_) != hipErrorNotReady) { seen = all_tagged(); break; }
-    }
-    if (!seen) {
-        HIP_TRY(hipStreamSynchronize(stream_));   // surfaces a kernel fault, if any
-        if (!all_tagged()) { err_ = "trimmed statistics were not published"; return VISMA_ICP_ERR_HIP; }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
     double pub[kTrimPublished];
-    for (int i = 0; i < kTrimPublished; i++) {
-        const unsigned long long v = g[2 * i];
-        std::memcpy(&pub[i], &v, sizeof(double));
-    }
-    trim_dirty_ = false;
+    rc = wait_granules(pair_.host, kTrimPublished, a.seq, "trimmed", pub);
+    if (rc) return rc;
+    pair_.disarm();
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->d2_cut = pub[kNStats];
     if ((int64_t)std::llround(pub[kNStats + 1]) != m) { err_ = "trimmed reduction kept another number of pairs than the select cut"; return VISMA_ICP_ERR_HIP; }
@@ -691,29 +736,11 @@ int HipEngine::get_kept_mask(uint8_t *mask)
 int HipEngine::reduce_robust(const Mat4 &Tc, const double *offset, bool plane, const RobustConfig &cfg, double *stats,
                              RobustPass *out)
 {
-    if (is_sharded()) { err_ = "robust ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
-    if (!have_pass_) { err_ = "reduce before nn_pass"; return VISMA_ICP_ERR_STATE; }
-    if (view_offset_ != 0) { err_ = "robust reduction needs an nn_pass of its own"; return VISMA_ICP_ERR_STATE; }
-    if (plane && !d_nrm_) { err_ = "point-to-plane needs target normals"; return VISMA_ICP_ERR_STATE; }
-    const double zero[3] = {0, 0, 0};
-    if (!offset) offset = zero;
-    double all[kNStats];
-    int rc = reduce(Tc, false, offset, all);
+    RobustPass found;
+    int rc = pair_pass_begin("robust", Tc, offset, plane, &found);
     if (rc) return rc;
-    if (sess_live_) { rc = end_session(); if (rc) return rc; }   // (never behind a launch that waits for this thread)
-    HIP_TRY(hipSetDevice(device_));
-    const int64_t K = (int64_t)std::llround(all[0]);
-    *out = RobustPass();
-    out->found = K;
-    out->sum_all = all[1];
-    if (!d_rob_work_) {
-        HIP_TRY(hipMalloc(&d_rob_work_, sizeof(unsigned) * kTrimWorkWords));
-        HIP_TRY(hipMalloc(&d_rob_partials_, sizeof(double) * kRobustRow * 1024));
-        HIP_TRY(hipHostMalloc((void **)&h_rob_, sizeof(double) * 2 * kRobustPublished, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(h_rob_, 0, sizeof(double) * 2 * kRobustPublished);
-        HIP_TRY(hipHostGetDevicePointer((void **)&h_rob_dev_, h_rob_, 0));
-        rob_dirty_ = true;
-    }
+    *out = found;
+    const int64_t K = out->found;
     if (ns_ > rob_w_cap_) {
         free_dev(d_rob_w_);
         HIP_TRY(hipMalloc(&d_rob_w_, sizeof(double) * (size_t)std::max<int64_t>(ns_, 1)));
@@ -726,65 +753,36 @@ int HipEngine::reduce_robust(const Mat4 &Tc, const double *offset, bool plane, c
         HIP_TRY(hipMalloc(&d_rob_r2_, sizeof(float) * (size_t)std::max<int64_t>(ns_, 1)));
         rob_r2_cap_ = ns_;
     }
-    if (rob_dirty_) HIP_TRY(hipMemsetAsync(d_rob_work_, 0, sizeof(unsigned) * kTrimWorkWords, stream_));
-    rob_dirty_ = true;
     RobustArgs a;
-    // the coordinates the plain pass summed from: the f64 copies where the search ran on them
-    const bool s64 = use_grid_ ? f64_views() : brute_exact();
-    if (s64) { a.src64 = (const Pt64 *)d_src64_; a.tgt64 = (const Pt64 *)d_tgt64_; a.nrm64 = (const Pt64 *)d_nrm64_; }
-    if (s64 && !a.tgt64) { err_ = "robust reduction: no f64 target"; return VISMA_ICP_ERR_STATE; }
-    a.src = (const float4 *)d_src_; a.tgt = (const float4 *)d_tgt_;
+    rc = pair_pass_args("robust", Tc, offset, &a);
+    if (rc) return rc;
+    if (a.src64) a.nrm64 = (const Pt64 *)d_nrm64_;
     a.nrm = (const float4 *)d_nrm_;
-    a.idx = (const int32_t *)d_idx_;
-    a.ns = ns_;
-    for (int i = 0; i < 12; i++) a.T64.m[i] = Tc.m[i];
-    for (int k = 0; k < 3; k++) a.off.v[k] = offset[k];
     a.kernel = cfg.kernel;
     a.auto_scale = automatic ? 1 : 0;
     a.scale = cfg.scale == 0.0 ? cfg.min_scale : cfg.scale;  // (read only without the select)
     a.tune_k = cfg.tune * 1.4826;
     a.min_scale = cfg.min_scale;
-    a.select_work = (const unsigned *)d_rob_work_;
-    a.ticket = (unsigned *)d_rob_work_ + kTrimHistWords + 3; // (the select's rounds take tickets 0 .. 2)
+    a.select_work = pair_.work;
+    a.ticket = pair_.work + kTrimHistWords + 3;              // (the select's rounds take tickets 0 .. 2)
     a.r2_out = (float *)d_rob_r2_;
     a.w_out = (double *)d_rob_w_;
-    a.partials = (double *)d_rob_partials_;
-    a.host_out = h_rob_dev_;
+    HIP_TRY(pair_.arm(stream_));
     if (automatic) {
         // the lower median: the m-th smallest ranking value, m = (K + 1) / 2; only its value is used, never the tie order
         const unsigned m = (unsigned)((K + 1) / 2);
         const float *rank = (const float *)d_d2_;
         if (plane) {
             HIP_TRY(launch_robust_residual(a, stream_));
-            rank = (const float *)d_rob_r2_;
+            rank = a.r2_out;
         }
-        HIP_TRY(launch_trim_select(rank, (const int32_t *)d_idx_, nullptr, ns_, m, (unsigned *)d_rob_work_, stream_));
+        HIP_TRY(launch_trim_select(rank, a.idx, nullptr, ns_, m, pair_.work, stream_));
     }
-    const unsigned long long seq = ++rob_seq_;
-    a.seq = seq;
     HIP_TRY(launch_robust_reduce(a, plane ? 1 : 0, stream_));
-    volatile unsigned long long *g = reinterpret_cast<volatile unsigned long long *>(h_rob_);
-    auto all_tagged = [&]() {
-        for (int i = kRobustPublished - 1; i >= 0; --i)
-            if (g[2 * i + 1] != seq) return false;
-        return true;
-    };
-    bool seen = false;
-    for (long long spin = 0; spin < 400000000ll && !seen; ++spin) {
-        seen = all_tagged();
-        if (!seen && (spin & 0xFFFFFll) == 0xFFFFFll && hipStreamQuery(stream_) != hipErrorNotReady) { seen = all_tagged(); break; }
-    }
-    if (!seen) {
-        HIP_TRY(hipStreamSynchronize(stream_));   // surfaces a kernel fault, if any
-        if (!all_tagged()) { err_ = "robust statistics were not published"; return VISMA_ICP_ERR_HIP; }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
     double pub[kRobustPublished];
-    for (int i = 0; i < kRobustPublished; i++) {
-        const unsigned long long v = g[2 * i];
-        std::memcpy(&pub[i], &v, sizeof(double));
-    }
-    rob_dirty_ = false;
+    rc = wait_granules(pair_.host, kRobustPublished, a.seq, "robust", pub);
+    if (rc) return rc;
+    pair_.disarm();
     rob_w_ns_ = ns_;
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->scale = pub[kNStats];

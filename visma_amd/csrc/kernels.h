@@ -522,24 +522,28 @@ int coop_persist_capacity(int point_to_plane);
 hipError_t launch_finalize_solve_batch(const double *partials, const ProbDesc *descs, DevIcpState *st,
                                        int nprob, hipStream_t stream, int plane = 0);
 
+// ---- passes over the pairs of the last nn_pass (trim.hip, robust.hip): what every such reduction is given ----
+struct PairPassArgs {
+    const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
+    const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
+    const int32_t *idx = nullptr;                      // the pass's winners per source position (< 0: no pair)
+    int64_t ns = 0;
+    Xform64 T64{};
+    Offset64 off{};
+    double *partials = nullptr;                        // one row per workgroup (trimmed: kReduceAcc doubles, robust: kRobustRow)
+    double *host_out = nullptr;                        // mapped host memory: granules {value, seq}
+    unsigned long long seq = 0;
+};
+
 // ---- trimmed ICP (trim.hip): the m pairs with the smallest key (d2, source index) of the last pass ----
 constexpr int kTrimHistWords = 3 * 2048;               // the select's histograms: three rounds of up to 2048 bins
 constexpr int kTrimWorkWords = kTrimHistWords + 8;     // ... + 4 tickets + the state {cut d2 bits, need, ties, cut index}
 constexpr int kTrimPublished = kNStats + 2;            // granules to the host: 38 statistics, cut d2, kept pairs
-struct TrimReduceArgs {
-    const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
-    const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
-    const int32_t *idx = nullptr;                      // the pass's winners per source position (< 0: no pair)
-    const float *d2 = nullptr;                         // ... and their fp32 squared distances: the ranking value
+struct TrimReduceArgs : PairPassArgs {
+    const float *d2 = nullptr;                         // the winners' fp32 squared distances: the ranking value
     const int32_t *order = nullptr;                    // source position -> caller's source index (NULL: identity)
-    int64_t ns = 0;
-    Xform64 T64{};
-    Offset64 off{};
     unsigned *work = nullptr;                          // kTrimWorkWords words, zero before the first pass (self re-arming)
     unsigned char *mask = nullptr;                     // out: 1 per kept source position
-    double *partials = nullptr;                        // trim_reduce_blocks(ns) rows of kReduceAcc
-    double *host_out = nullptr;                        // mapped host memory: kTrimPublished granules {value, seq}
-    unsigned long long seq = 0;
 };
 int trim_select_blocks(int64_t ns);
 int trim_reduce_blocks(int64_t ns);
@@ -552,15 +556,9 @@ hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream);
 constexpr int kRobustL2 = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3;   // = VISMA_ICP_ROBUST_*
 constexpr int kRobustRow = 32;                         // doubles per partial row: Acc<PLANE>::N + pairs with w == 0 + sum w r^2
 constexpr int kRobustPublished = kNStats + 4;          // granules to the host: 38 statistics, c, v, pairs with w == 0, sum w r^2
-struct RobustArgs {
-    const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
-    const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
+struct RobustArgs : PairPassArgs {
     const float4 *nrm = nullptr;                       // target normals by original index (point-to-plane), and ...
     const Pt64 *nrm64 = nullptr;                       // ... in f64 where the f64 passes read them
-    const int32_t *idx = nullptr;                      // the pass's winners per source position (< 0: no pair)
-    int64_t ns = 0;
-    Xform64 T64{};
-    Offset64 off{};
     int kernel = kRobustHuber;                         // kRobustHuber / Tukey / Cauchy
     int auto_scale = 0;                                // 0: c = scale; 1: c = max(tune_k * sqrt(v), min_scale), v from the select
     double scale = 0.0, tune_k = 0.0, min_scale = 0.0; // tune_k = tune * 1.4826
@@ -568,9 +566,6 @@ struct RobustArgs {
     unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
     float *r2_out = nullptr;                           // residual kernel: (float)(r^2) per source position
     double *w_out = nullptr;                           // out: the weight per source position (0: no pair)
-    double *partials = nullptr;                        // robust_reduce_blocks(ns) rows of kRobustRow
-    double *host_out = nullptr;                        // mapped host memory: kRobustPublished granules {value, seq}
-    unsigned long long seq = 0;
 };
 int robust_reduce_blocks(int64_t ns);
 hipError_t launch_robust_residual(const RobustArgs &a, hipStream_t stream);

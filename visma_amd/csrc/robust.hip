@@ -9,10 +9,10 @@
 //                                  and w times the pair's contribution to every accumulator of Acc<PLANE>; w per source
 //                                  position goes to memory.  Automatic scale: the median's bit pattern is read from the
 //                                  select's state word and c is formed here in f64 -- no host round trip between select
-//                                  and reduction.  Then the recipe of trim_reduce_kernel: one partial row per workgroup
-//                                  (agent-scope stores), every storing wave drains, one relaxed agent-scope ticket, the
-//                                  last workgroup acquires, folds the rows in row order, expands the moments and
-//                                  publishes 38 statistics, c, v, the pairs with w == 0 and sum w r^2 as tagged granules.
+//                                  and reduction.  Then the pair-pass tail trim_reduce_kernel ends in (device_common.h:
+//                                  block_reduce_store, pair_pass_fold, publish_tagged_stats) with rows of kRobustRow
+//                                  doubles: the last workgroup has the column totals, expands the moments and
+//                                  publishes 38 statistics, c, v, the pairs with w == 0 and sum w r^2.
 // No floating-point atomics: a run is bit-identical to itself.  (Reasoning and numbers: DESIGN.md 4.4c4.)
 #include "device_common.h"
 
@@ -23,15 +23,6 @@ namespace {
 constexpr int kRobustThreads = 256;
 constexpr int kRobustExtra = 2;                        // behind the accumulators of Acc<PLANE>: pairs with w == 0, sum w r^2
 static_assert(Acc<true>::N + kRobustExtra <= kRobustRow && kRobustRow <= 32, "a partial row holds every accumulator; the fold has 32 columns");
-
-__device__ __forceinline__ unsigned ld_agent_u32(const unsigned *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent_u32(unsigned *p, unsigned v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // the weight of a residual r >= 0 at scale c (visma_icp.h); c == 0 (or not positive): 1 for r == 0, else 0 -- never NaN
 __device__ __forceinline__ double robust_weight(int kernel, double r, double c)
@@ -99,12 +90,8 @@ __global__ __launch_bounds__(kRobustThreads) void robust_reduce_kernel(RobustArg
 {
     constexpr int NACC = Acc<PLANE>::N;
     constexpr int NROW = NACC + kRobustExtra;
-    constexpr int NWAVES = kRobustThreads / 64;
-    __shared__ double wsum[NWAVES][NROW];
-    __shared__ double f_part[kRobustThreads / 32][33];
     __shared__ double f_tot[32];
     __shared__ double f_stats[kRobustPublished];
-    __shared__ int last;
     const int tid = threadIdx.x;
     // the scale: the caller's, or from the median the select left in its state word
     double c = a.scale, v = 0.0;
@@ -136,58 +123,8 @@ __global__ __launch_bounds__(kRobustThreads) void robust_reduce_kernel(RobustArg
         }
         a.w_out[i] = w;
     }
-    // block_reduce_store's recipe with a row of kRobustRow doubles (its rows have kReduceAcc)
-    {
-        const int lane = tid & 63, wave = tid >> 6;
-        const double tot = wave_sum_multi<NROW>(acc);
-        const int slot = multi_index<NROW>(lane);
-        if (slot >= 0) wsum[wave][slot] = tot;
-        __syncthreads();
-        if (tid < NROW) {
-            double s = wsum[0][tid];
-#pragma unroll
-            for (int w = 1; w < NWAVES; w++) s += wsum[w][tid];
-            store_agent_f64(a.partials + (long long)blockIdx.x * kRobustRow + tid, s);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave drains
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = t == gridDim.x - 1u ? 1 : 0;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            st_agent_u32(a.ticket, 0u);                      // re-armed for the next pass
-        }
-    }
-    __syncthreads();
-    if (!last) return;
-    // the rows in row order: thread (sg, sa) sums rows sg, sg + 8, ... of column sa, then the eight sums in order
-    constexpr int NG = kRobustThreads / 32;
-    const int sa = tid & 31, sg = tid >> 5;
-    {
-        double s = 0.0;
-        if (sa < NROW)
-            for (int r0 = sg; r0 < (int)gridDim.x; r0 += 8 * NG) {
-                double w[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int r = r0 + u * NG;
-                    w[u] = r < (int)gridDim.x ? load_agent_f64(a.partials + (long long)r * kRobustRow + sa) : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++) s += w[u];
-            }
-        f_part[sg][sa] = s;
-    }
-    __syncthreads();
-    if (tid < 32) {
-        double t = 0.0;
-#pragma unroll
-        for (int gg = 0; gg < NG; gg++) t += f_part[gg][tid];
-        f_tot[tid] = t;
-    }
-    __syncthreads();
+    block_reduce_store<NROW, kRobustThreads / 64, false, kRobustRow>(acc, a.partials, true);
+    if (!pair_pass_fold<NROW, kRobustRow>(a.partials, a.ticket, f_tot)) return;
     if (tid == 0) {
         expand_moments<PLANE>(f_tot, f_stats);
         f_stats[kNStats] = c;
@@ -195,15 +132,7 @@ __global__ __launch_bounds__(kRobustThreads) void robust_reduce_kernel(RobustArg
         f_stats[kNStats + 2] = f_tot[NACC];                  // pairs with w == 0
         f_stats[kNStats + 3] = f_tot[NACC + 1];              // sum w r^2
     }
-    __syncthreads();
-    if (tid < kRobustPublished) {
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        const unsigned long long b = (unsigned long long)__double_as_longlong(f_stats[tid]);
-        u4 g;
-        g.x = (unsigned)b; g.y = (unsigned)(b >> 32);
-        g.z = (unsigned)a.seq; g.w = (unsigned)(a.seq >> 32);
-        __builtin_nontemporal_store(g, reinterpret_cast<u4 *>(a.host_out) + tid);
-    }
+    publish_tagged_stats<kRobustPublished>(f_stats, a.host_out, a.seq);
 }
 
 int robust_reduce_blocks(int64_t ns) { return trim_reduce_blocks(ns); }

@@ -12,10 +12,10 @@
 //                             caller's source index: the same select over the 32 index bits of the tied pairs, run by
 //                             that last workgroup alone (rare; the price is three scans of the queries by 256 threads).
 //  trim_reduce_kernel<S64>    the reduction's arithmetic (accumulate_pair / accumulate_pair_d, device_common.h) over
-//                             the pairs with key (d2 bits << 32 | source index) <= cut key, the kept mask, one partial
-//                             row per workgroup; the last workgroup folds the rows in row order (fused fold recipe of
-//                             device_common.h), expands the moments and publishes statistics, cut distance and kept
-//                             count as tagged granules to mapped host memory.  No floating-point atomics: a run is
+//                             the pairs with key (d2 bits << 32 | source index) <= cut key, the kept mask, then the
+//                             pair-pass tail (device_common.h: block_reduce_store, pair_pass_fold,
+//                             publish_tagged_stats): the last workgroup has the column totals, expands the moments and
+//                             publishes statistics, cut distance and kept count.  No floating-point atomics: a run is
 //                             bit-identical to itself.
 // No sort, no copy of the distances to the host.  Four launches per pass (reasoning and numbers: DESIGN.md).
 #include "device_common.h"
@@ -25,15 +25,6 @@ namespace visma {
 namespace {
 
 constexpr int kTrimThreads = 256;
-
-__device__ __forceinline__ unsigned ld_agent_u32(const unsigned *p)
-{
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent_u32(unsigned *p, unsigned v)
-{
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // All 256 threads: the bin of h[0 .. NB) that holds rank `need` (1-based, need <= sum of h) and the count of the bins
 // before it.  Results in res[0] (bin), res[1] (before); h is left as it was.
@@ -166,10 +157,8 @@ template <bool S64>
 __global__ __launch_bounds__(kTrimThreads) void trim_reduce_kernel(TrimReduceArgs a)
 {
     constexpr int NACC = Acc<false>::N;
-    __shared__ double f_part[kTrimThreads / 32][33];
     __shared__ double f_tot[32];
     __shared__ double f_stats[kTrimPublished];
-    __shared__ int last;
     const int tid = threadIdx.x;
     unsigned *tickets = a.work + kTrimHistWords;
     const unsigned *state = tickets + 4;
@@ -194,58 +183,13 @@ __global__ __launch_bounds__(kTrimThreads) void trim_reduce_kernel(TrimReduceArg
         }
     }
     block_reduce_store<NACC>(acc, a.partials, true);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // every storing wave drains
-    __syncthreads();
-    if (tid == 0) {
-        const unsigned t = __hip_atomic_fetch_add(tickets + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = t == gridDim.x - 1u ? 1 : 0;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            st_agent_u32(tickets + 3, 0u);
-        }
-    }
-    __syncthreads();
-    if (!last) return;
-    // the rows in row order: thread (sg, sa) sums rows sg, sg + 8, ... of statistic sa, then the eight sums in order
-    constexpr int NG = kTrimThreads / 32;
-    const int sa = tid & 31, sg = tid >> 5;
-    {
-        double v = 0.0;
-        if (sa < NACC)
-            for (int r0 = sg; r0 < (int)gridDim.x; r0 += 8 * NG) {
-                double w[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int r = r0 + u * NG;
-                    w[u] = r < (int)gridDim.x ? load_agent_f64(a.partials + (long long)r * kReduceAcc + sa) : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++) v += w[u];
-            }
-        f_part[sg][sa] = v;
-    }
-    __syncthreads();
-    if (tid < 32) {
-        double t = 0.0;
-#pragma unroll
-        for (int gg = 0; gg < NG; gg++) t += f_part[gg][tid];
-        f_tot[tid] = t;
-    }
-    __syncthreads();
+    if (!pair_pass_fold<NACC, kReduceAcc>(a.partials, tickets + 3, f_tot)) return;
     if (tid == 0) {
         expand_moments<false>(f_tot, f_stats);
         f_stats[kNStats] = (double)__uint_as_float(vbits);    // the cut: the largest kept d2
         f_stats[kNStats + 1] = f_tot[0];                       // kept pairs (= stats[0])
     }
-    __syncthreads();
-    if (tid < kTrimPublished) {
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        const unsigned long long v = (unsigned long long)__double_as_longlong(f_stats[tid]);
-        u4 g;
-        g.x = (unsigned)v; g.y = (unsigned)(v >> 32);
-        g.z = (unsigned)a.seq; g.w = (unsigned)(a.seq >> 32);
-        __builtin_nontemporal_store(g, reinterpret_cast<u4 *>(a.host_out) + tid);
-    }
+    publish_tagged_stats<kTrimPublished>(f_stats, a.host_out, a.seq);
 }
 
 int trim_select_blocks(int64_t ns)
