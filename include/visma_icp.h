@@ -442,6 +442,68 @@ VISMA_ICP_API int visma_icp_run_yaw_sweep_robust(visma_icp_ctx *ctx, int level, 
  * point has no pair.  VISMA_ICP_ERR_STATE before a robust pass.  (After an L2 run: 1 for every pair.) */
 VISMA_ICP_API int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src);
 
+/* ---- generalized ICP (plane-to-plane; Segal, Haehnel, Thrun: "Generalized-ICP", RSS 2009).  Every pair's residual is
+ * weighted by the inverse of the sum of both points' local surface covariances, so a source point may slide along
+ * either surface at no cost.  The covariance of a surface element is a function of its normal alone,
+ * C = I - (1 - epsilon) n n^T (a neighbourhood covariance with its eigenvalues replaced by (1, 1, epsilon)): the method
+ * takes source normals, target normals and epsilon, no covariance arrays.  Prefer it where the source is a sampled
+ * CAD model whose normals are exact.
+ *
+ *   Pairs: those of the last visma_icp_nn_pass (all K pairs inside the radius), (i, j) = (source, target).  In f64:
+ *     p = T s_i as the robust pass forms it, q = t_j, d = p - q
+ *     m = R n^s_i (the source normal turned by the rotation of T), n = n^t_j
+ *     C = 2 I - (1 - epsilon)(n n^T + m m^T)
+ *     M = C^-1 by the closed-form adjugate / determinant of a symmetric 3 x 3
+ *     J = [ -[p]x | I ] (3 x 6); the unknowns x = [alpha beta gamma tx ty tz] as in the 6 x 6 point-to-plane path
+ *   Frame and offset as visma_icp_reduce_robust with plane != 0: rows in the caller's (world) frame.
+ *   Normals are used AS GIVEN: unit length is the caller's business (a longer normal makes C indefinite beyond
+ *   |n|^2 = 2 / (1 - epsilon)).  A zero normal leaves its point isotropic (its share of C is I).  A non-finite normal
+ *   reaches the sums only, never an index or an address.
+ *   epsilon = 1 is point-to-point (M = I / 2); epsilon -> 0 with the source isotropic is point-to-plane.
+ *
+ * Statistics in the layout of visma_icp_reduce (the host solves take them unchanged):
+ *   [0] = K   [1] = sum |d|^2 (unweighted: inlier_rmse is the plain one)
+ *   [2:23] = upper triangle of sum J^T M J   [23:29] = sum J^T M d   [29:38] = 0
+ * and in visma_icp_gicp_info: cost = sum d^T M d, mahalanobis_rmse = sqrt(cost / K), 0 when K = 0.
+ * No floating-point atomics: a run is bit-identical to itself.
+ *
+ * The update solves A x = -b as visma_icp_solve_from_stats(VISMA_ICP_SOLVER_GN_EULER) does -- the reference's
+ * |det A| < 1e-6 guard and its Rz Ry Rx map --, on a context with a rotation axis as
+ * visma_icp_solve_from_stats_axis(plane = 1).  The eigenvalues of M lie in [1/2, 1/(2 epsilon)] for unit normals, so
+ * det A >= det(J^T J of the point-to-point Gauss-Newton step) / 64: the guard rejects a pass no sooner than at 64 x
+ * the determinant at which it rejects the point-to-point Gauss-Newton step over the same pairs.
+ *
+ * epsilon outside (0, 1] or not finite: VISMA_ICP_ERR_INVALID before any pass.  NOT offered (VISMA_ICP_ERR_INVALID):
+ * sharded contexts (comm_init, comm_ipc_init, set_allreduce with more than one rank, set_target_shard).  Not
+ * combined with robust weights or trimming; no batches, no corpus. */
+typedef struct {
+    double cost;               /* sum d^T M d of the last pass */
+    double mahalanobis_rmse;   /* sqrt(cost / K); 0 when K = 0 */
+} visma_icp_gicp_info;
+
+/* Normals of the source, one per point in the caller's order (nxyz[i * stride + 0..2]), after the source is set; ns
+ * must be the source's count (VISMA_ICP_ERR_INVALID).  A new source drops them, as a new target drops its normals. */
+VISMA_ICP_API int visma_icp_set_source_normals_f64(visma_icp_ctx *ctx, const double *nxyz, int64_t ns, int stride);
+/* The generalized statistics of the last visma_icp_nn_pass.  Without both sets of normals, or before a pass:
+ * VISMA_ICP_ERR_STATE. */
+VISMA_ICP_API int visma_icp_reduce_gicp(visma_icp_ctx *ctx, double epsilon, double out_stats[VISMA_ICP_NSTATS],
+                                        visma_icp_gicp_info *info);
+/* RegistrationICP's loop (Registration.cpp:167-185) with the generalized pass.  Its stop test compares fitness
+ * (K / NS) and mahalanobis_rmse of consecutive passes.  out->num_correspondences = K, out->fitness and
+ * out->inlier_rmse are the unweighted values of the last pass; *info (may be NULL) belongs to that pass.  Without both
+ * sets of normals the run returns init (Registration.cpp:152-157, as point-to-plane does).  One launch sequence per
+ * pass; never the persistent launch. */
+VISMA_ICP_API int visma_icp_run_gicp(visma_icp_ctx *ctx, const double init[16], double max_dist, double epsilon,
+                                     int max_iter, double rel_fitness, double rel_rmse, visma_icp_result *out,
+                                     visma_icp_gicp_info *info);
+/* visma_icp_run_yaw_sweep with every start a generalized run (one after the other); the winner is the first start
+ * with strictly the most correspondences K.  per_level / per_level_info / best_info may be NULL.  Afterwards the
+ * context holds the last pass of the LAST start. */
+VISMA_ICP_API int visma_icp_run_yaw_sweep_gicp(visma_icp_ctx *ctx, int level, double max_dist, double epsilon,
+                                               int max_iter, double rel_fitness, double rel_rmse,
+                                               visma_icp_result *best, int *best_level, visma_icp_result *per_level,
+                                               visma_icp_gicp_info *best_info, visma_icp_gicp_info *per_level_info);
+
 /* ---- batched small problems (AnnotationTool loop, src/annotation.cpp:103-168) */
 
 typedef struct {

@@ -20,6 +20,10 @@
 //                                      robust ICP through RegistrationICP: every pair weighted by a function of its
 //                                      own residual (cicp::RobustKernel: Huber, Tukey, Cauchy; the scale from the
 //                                      median residual unless given) -- no overlap share needed
+//   open3d::cicp::TransformationEstimationGeneralized(epsilon)
+//                                      generalized ICP (plane-to-plane) through RegistrationICP: every pair weighted
+//                                      by the inverse of the sum of both points' surface covariances; needs the
+//                                      normals of BOTH clouds (a sampled CAD model has exact ones)
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -184,6 +188,32 @@ public:
                                                  const PointCloud &target,
                                                  const CorrespondenceSet &corres) const override;
     RobustKernel kernel_;
+};
+
+// Generalized ICP (Segal, Haehnel, Thrun, RSS 2009; visma_icp_run_gicp -- visma_icp.h states the step): the covariance of
+// a point is that of a surface element with its normal, C = I - (1 - epsilon) n n^T, and every pair is weighted by
+// (C_target + R C_source R^T)^-1.  What later Open3D versions call TransformationEstimationForGeneralizedICP, without
+// covariance arrays.  Normals are used as given: unit length is the caller's business.  What cicp::RegistrationICP
+// returns for it:
+//   correspondence_set_  all K pairs of the last pass
+//   fitness_, inlier_rmse_  K / |source| and the plain rmse over the K pairs (the loop's stop test looks at the
+//                        Mahalanobis rmse sqrt(sum d^T M d / K): visma_icp_gicp_info)
+// ComputeRMSE(source, target, corres) is that Mahalanobis rmse and ComputeTransformation the generalized step over the
+// corres they are given, restated on the host; source.normals_ are taken as lying in the frame of source.points_.
+class TransformationEstimationGeneralized : public TransformationEstimation {
+public:
+    explicit TransformationEstimationGeneralized(double epsilon = 1e-3) : epsilon_(epsilon) {}
+    ~TransformationEstimationGeneralized() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::PointToPlane;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    double epsilon_ = 1e-3;
 };
 
 namespace detail {
@@ -360,6 +390,51 @@ inline Eigen::Matrix4d host_update_axis(const Cloud &s, const Cloud &t, const Co
     return from_rowmajor(T);
 }
 
+// The generalized statistics of explicit correspondences (visma_icp.h: generalized ICP) on the host; source normals as
+// they are (already in the frame of the source points).  Returns sum d^T M d.
+template <typename Cloud, typename Corr>
+inline double host_stats_gicp(const Cloud &source, const Cloud &target, const Corr &corres, double epsilon,
+                              double st[VISMA_ICP_NSTATS])
+{
+    double A[6][6] = {{0}}, b[6] = {0}, r2 = 0.0, cost = 0.0;
+    const double k1 = 1.0 - epsilon;
+    for (const auto &c : corres) {
+        const Eigen::Vector3d &p = source.points_[c[0]], &q = target.points_[c[1]];
+        const Eigen::Vector3d &m = source.normals_[c[0]], &n = target.normals_[c[1]];
+        const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+        double C[3][3], M[3][3];
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) C[i][j] = (i == j ? 2.0 : 0.0) - k1 * (n[i] * n[j] + m[i] * m[j]);
+        const double a00 = C[1][1] * C[2][2] - C[1][2] * C[1][2], a01 = C[0][2] * C[1][2] - C[0][1] * C[2][2];
+        const double a02 = C[0][1] * C[1][2] - C[0][2] * C[1][1], a11 = C[0][0] * C[2][2] - C[0][2] * C[0][2];
+        const double a12 = C[0][1] * C[0][2] - C[0][0] * C[1][2], a22 = C[0][0] * C[1][1] - C[0][1] * C[0][1];
+        const double det = C[0][0] * a00 + C[0][1] * a01 + C[0][2] * a02;
+        M[0][0] = a00 / det; M[0][1] = M[1][0] = a01 / det; M[0][2] = M[2][0] = a02 / det;
+        M[1][1] = a11 / det; M[1][2] = M[2][1] = a12 / det; M[2][2] = a22 / det;
+        // J = [-hat(p) | I]
+        const double J[3][6] = {{0.0, p[2], -p[1], 1.0, 0.0, 0.0}, {-p[2], 0.0, p[0], 0.0, 1.0, 0.0}, {p[1], -p[0], 0.0, 0.0, 0.0, 1.0}};
+        double MJ[3][6], e[3];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 6; j++) MJ[i][j] = M[i][0] * J[0][j] + M[i][1] * J[1][j] + M[i][2] * J[2][j];
+            e[i] = M[i][0] * d[0] + M[i][1] * d[1] + M[i][2] * d[2];
+        }
+        for (int i = 0; i < 6; i++) {
+            for (int j = i; j < 6; j++) A[i][j] += J[0][i] * MJ[0][j] + J[1][i] * MJ[1][j] + J[2][i] * MJ[2][j];
+            b[i] += J[0][i] * e[0] + J[1][i] * e[1] + J[2][i] * e[2];
+        }
+        r2 += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        cost += d[0] * e[0] + d[1] * e[1] + d[2] * e[2];
+    }
+    int o = 0;
+    st[o++] = (double)corres.size();
+    st[o++] = r2;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++) st[o++] = A[i][j];
+    for (int i = 0; i < 6; i++) st[o++] = b[i];
+    while (o < VISMA_ICP_NSTATS) st[o++] = 0.0;
+    return cost;
+}
+
 // the stock point-to-plane ComputeRMSE (TransformationEstimation.cpp:64-75, with its `err = r * r`)
 template <typename Cloud, typename Corr>
 inline double host_rmse_point_to_plane(const Cloud &s, const Cloud &t, const Corr &c)
@@ -504,6 +579,21 @@ inline RegistrationResult RegistrationICP(
                       "visma_icp_run_robust");
         detail::fill_result(ctx, r, source.points_.size(), result);
         result.inlier_rmse_ = info.robust_rmse;
+        return result;
+    }
+    if (dyn == typeid(TransformationEstimationGeneralized)) {
+        const auto *g = static_cast<const TransformationEstimationGeneralized *>(&estimation);
+        if (!(g->epsilon_ > 0.0 && g->epsilon_ <= 1.0)) {
+            std::fprintf(stderr, "Error: TransformationEstimationGeneralized requires epsilon in (0, 1].\n");
+            return RegistrationResult(init);
+        }
+        detail::check(ctx, visma_icp_set_source_normals_f64(ctx, detail::xyz(source.normals_), (int64_t)source.normals_.size(), 3),
+                      "visma_icp_set_source_normals_f64");
+        visma_icp_gicp_info info;
+        detail::check(ctx, visma_icp_run_gicp(ctx, T, max_correspondence_distance, g->epsilon_, criteria.max_iteration_,
+                                              criteria.relative_fitness_, criteria.relative_rmse_, &r, &info),
+                      "visma_icp_run_gicp");
+        detail::fill_result(ctx, r, source.points_.size(), result);
         return result;
     }
     if (four || p2p) {
@@ -1008,6 +1098,24 @@ inline Eigen::Matrix4d TransformationEstimationPointToPlaneRobust::ComputeTransf
 {
     if (!target.HasNormals()) return Eigen::Matrix4d::Identity();
     return detail::host_update(source, target, corres, true, false);
+}
+
+inline double TransformationEstimationGeneralized::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    if (corres.empty() || !source.HasNormals() || !target.HasNormals()) return 0.0;
+    double st[VISMA_ICP_NSTATS];
+    return std::sqrt(detail::host_stats_gicp(source, target, corres, epsilon_, st) / (double)corres.size());
+}
+
+inline Eigen::Matrix4d TransformationEstimationGeneralized::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    if (corres.empty() || !source.HasNormals() || !target.HasNormals()) return Eigen::Matrix4d::Identity();
+    double st[VISMA_ICP_NSTATS], T[16];
+    (void)detail::host_stats_gicp(source, target, corres, epsilon_, st);
+    visma_icp_solve_from_stats(st, VISMA_ICP_SOLVER_GN_EULER, 0, T);
+    return detail::from_rowmajor(T);
 }
 
 // ---- the estimators constrained to a rotation about up_ ----------------------

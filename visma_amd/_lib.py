@@ -220,6 +220,15 @@ def _bind(L):
                                                      C.c_double, C.POINTER(CResult), C.POINTER(C.c_int),
                                                      C.POINTER(CResult), _ri, _ri]
         L.visma_icp_get_pair_weights.argtypes = [C.c_void_p, _dp]
+    if hasattr(L, "visma_icp_run_gicp"):                 # (A/B runs load older builds through VISMA_ICP_LIB)
+        _gi = C.POINTER(CGicpInfo)
+        L.visma_icp_set_source_normals_f64.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_int]
+        L.visma_icp_reduce_gicp.argtypes = [C.c_void_p, C.c_double, _dp, _gi]
+        L.visma_icp_run_gicp.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                         C.POINTER(CResult), _gi]
+        L.visma_icp_run_yaw_sweep_gicp.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                   C.c_double, C.POINTER(CResult), C.POINTER(C.c_int), C.POINTER(CResult),
+                                                   _gi, _gi]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -304,6 +313,22 @@ class RobustInfo:
     def __repr__(self):
         return "RobustInfo(scale=%.6g, median_residual=%.6g, weight_sum=%.6g, zero_weight=%d, robust_rmse=%.6g)" % (
             self.scale, self.median_residual, self.weight_sum, self.zero_weight, self.robust_rmse)
+
+
+class CGicpInfo(C.Structure):
+    """visma_icp_gicp_info"""
+    _fields_ = [("cost", C.c_double), ("mahalanobis_rmse", C.c_double)]
+
+
+class GicpInfo:
+    """A generalized pass: cost = sum d^T M d over its pairs and mahalanobis_rmse = sqrt(cost / K)."""
+
+    def __init__(self, c):
+        self.cost = float(c.cost)
+        self.mahalanobis_rmse = float(c.mahalanobis_rmse)
+
+    def __repr__(self):
+        return "GicpInfo(cost=%.6g, mahalanobis_rmse=%.6g)" % (self.cost, self.mahalanobis_rmse)
 
 
 class Result:
@@ -546,6 +571,41 @@ class Context:
         rs = []
         for p, i in zip(per, pi):
             r = Result(p); r.robust = RobustInfo(i); rs.append(r)
+        return rb, bl.value, rs
+
+    def set_source_normals_f64(self, n):
+        """Normals of the source (caller's order, after the source is set; used as given): what generalized ICP needs
+        next to the target's."""
+        n = _f64(n, (-1, 3))
+        self._chk(self.L.visma_icp_set_source_normals_f64(self._h, _p(n, _dp), len(n), 3))
+
+    def reduce_gicp(self, epsilon=1e-3):
+        """The generalized (plane-to-plane) statistics of the last nn_pass -> (stats, GicpInfo)."""
+        st = np.empty(NSTATS); info = CGicpInfo()
+        self._chk(self.L.visma_icp_reduce_gicp(self._h, float(epsilon), _p(st, _dp), C.byref(info)))
+        return st, GicpInfo(info)
+
+    def run_gicp(self, init=None, max_dist=0.05, epsilon=1e-3, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+        """Generalized ICP: every pair weighted by the inverse of the sum of both points' surface covariances
+        C = I - (1 - epsilon) n n^T; needs source and target normals.  -> Result with .gicp (GicpInfo)."""
+        init = _f64(np.eye(4) if init is None else init, (16,))
+        out = CResult(); info = CGicpInfo()
+        self._chk(self.L.visma_icp_run_gicp(self._h, _p(init, _dp), float(max_dist), float(epsilon), int(max_iter),
+                                            float(rel_fitness), float(rel_rmse), C.byref(out), C.byref(info)))
+        r = Result(out)
+        r.gicp = GicpInfo(info)
+        return r
+
+    def run_yaw_sweep_gicp(self, level, max_dist, epsilon=1e-3, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+        best = CResult(); bl = C.c_int(-1); per = (CResult * level)()
+        bi = CGicpInfo(); pi = (CGicpInfo * level)()
+        self._chk(self.L.visma_icp_run_yaw_sweep_gicp(self._h, int(level), float(max_dist), float(epsilon), int(max_iter),
+                                                      float(rel_fitness), float(rel_rmse), C.byref(best), C.byref(bl), per,
+                                                      C.byref(bi), pi))
+        rb = Result(best); rb.gicp = GicpInfo(bi)
+        rs = []
+        for p, i in zip(per, pi):
+            r = Result(p); r.gicp = GicpInfo(i); rs.append(r)
         return rb, bl.value, rs
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):

@@ -12,7 +12,7 @@ namespace {
 class HookEngine : public Engine {
 public:
     HookEngine(const visma_icp_engine &vt, void *user) : vt_(vt), user_(user) {}
-    int set_source(const float *p, int64_t n) override { ns_ = n; return wrap(vt_.set_source(user_, p, n)); }
+    int set_source(const float *p, int64_t n) override { ns_ = n; has_source_normals_ = false; return wrap(vt_.set_source(user_, p, n)); }
     int set_target(const float *p, int64_t n) override { nt_ = n; has_normals_ = false; return wrap(vt_.set_target(user_, p, n)); }
     int set_target_normals(const float *p, int64_t n) override
     {
@@ -911,6 +911,87 @@ int visma_icp_get_pair_weights(visma_icp_ctx *ctx, double *w_per_src)
     }
     scatter_by_order(ctx, w, w_per_src);
     return VISMA_ICP_OK;
+}
+
+// ---- generalized ICP --------------------------------------------------------------------------------------------------
+// everything that is wrong with a call before any pass
+static int check_gicp(visma_icp_ctx *ctx, double epsilon)
+{
+    if (!std::isfinite(epsilon) || !(epsilon > 0.0) || epsilon > 1.0)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "generalized ICP: epsilon must lie in (0, 1]");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "generalized ICP runs on one rank");
+    if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_set_source_normals_f64(visma_icp_ctx *ctx, const double *n, int64_t ns, int stride)
+{
+    CTX_CHECK();
+    if (!ctx->have_src) return ctx->fail(VISMA_ICP_ERR_STATE, "set the source first");
+    if (ns != ctx->eng->ns() || stride < 3 || (ns > 0 && !n)) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad normals arguments");
+    // by source POSITION: the engine holds the source in Morton order
+    const int32_t *order = ctx->order_ptr();
+    std::vector<float> n4((size_t)std::max<int64_t>(ns, 1) * 4);
+    std::vector<Pt64> n8;
+    if (ctx->eng->supports_device_loop()) n8.resize((size_t)std::max<int64_t>(ns, 1));
+    for (int64_t pos = 0; pos < ns; pos++) {
+        const double *q = n + (size_t)(order ? order[pos] : pos) * stride;
+        float *f = &n4[(size_t)pos * 4];
+        f[0] = (float)q[0]; f[1] = (float)q[1]; f[2] = (float)q[2]; f[3] = 0.f;
+        if (!n8.empty()) n8[(size_t)pos] = Pt64{q[0], q[1], q[2], 0ull};
+    }
+    int rc = ctx->eng->set_source_normals(n4.data(), n8.empty() ? nullptr : n8.data(), ns);
+    if (rc) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_reduce_gicp(visma_icp_ctx *ctx, double epsilon, double out_stats[VISMA_ICP_NSTATS], visma_icp_gicp_info *info)
+{
+    CTX_CHECK();
+    if (!out_stats || !info) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (int rc = check_gicp(ctx, epsilon)) return rc;
+    if (!ctx->eng->has_normals() || !ctx->eng->has_source_normals())
+        return ctx->fail(VISMA_ICP_ERR_STATE, "generalized ICP needs source and target normals");
+    Engine::GicpPass gp;
+    int rc = ctx->eng->reduce_gicp(ctx->last_Tc, ctx->centre, epsilon, out_stats, &gp);
+    if (rc) return ctx->eng_fail(rc);
+    ctx->last_plane = true;
+    visma_icp_ctx::fill_gicp_info(info, gp);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_run_gicp(visma_icp_ctx *ctx, const double init[16], double max_dist, double epsilon, int max_iter,
+                       double rel_fitness, double rel_rmse, visma_icp_result *out, visma_icp_gicp_info *info)
+{
+    CTX_CHECK();
+    if (!init || !out || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad run arguments");
+    if (int rc = check_gicp(ctx, epsilon)) return rc;
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!ctx->eng->has_source_normals()) {                       // Registration.cpp:152-157, as without target normals
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out->transformation, init, sizeof(double) * 16);
+        if (max_dist > 0.0) ctx->last_radius = max_dist;
+        return VISMA_ICP_OK;
+    }
+    Engine::GicpPass gp;
+    return ctx->run_pair_passes(
+        init, max_dist, true, max_iter, rel_fitness, rel_rmse, false, out, nullptr, gp,
+        [&](const Mat4 &Tc, double *stats) { return ctx->eng->reduce_gicp(Tc, ctx->centre, epsilon, stats, &gp); },
+        [&](const double *) { if (info) visma_icp_ctx::fill_gicp_info(info, gp); },
+        [&](const double *) { return gp.found > 0 ? std::sqrt(gp.cost / (double)gp.found) : 0.0; });
+}
+
+int visma_icp_run_yaw_sweep_gicp(visma_icp_ctx *ctx, int level, double max_dist, double epsilon, int max_iter,
+                                 double rel_fitness, double rel_rmse, visma_icp_result *best, int *best_level,
+                                 visma_icp_result *per_level, visma_icp_gicp_info *best_info,
+                                 visma_icp_gicp_info *per_level_info)
+{
+    CTX_CHECK();
+    if (level <= 0 || !best || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad sweep arguments");
+    if (int rc = check_gicp(ctx, epsilon)) return rc;
+    return sweep_sequential(level, [&](const Mat4 &init, visma_icp_result *r, visma_icp_gicp_info *ri) {
+        return visma_icp_run_gicp(ctx, init.m, max_dist, epsilon, max_iter, rel_fitness, rel_rmse, r, ri);
+    }, best, best_level, per_level, best_info, per_level_info);
 }
 
 int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, int steps, int solver,

@@ -147,14 +147,30 @@ struct visma_icp_ctx {
         info->robust_rmse = trimmed_rmse(stats);
     }
 
-    // RegistrationICP's loop around a pass over the pairs (trimmed, robust).  reduce(Tc, stats) is the engine's reduction
+    static void fill_gicp_info(visma_icp_gicp_info *info, const Engine::GicpPass &gp)
+    {
+        info->cost = gp.cost;
+        info->mahalanobis_rmse = gp.found > 0 ? std::sqrt(gp.cost / (double)gp.found) : 0.0;
+    }
+
+    // RegistrationICP's loop around a pass over the pairs (trimmed, robust, generalized).  reduce(Tc, stats) is the engine's reduction
     // behind each NN pass: its statistics feed the solve, `pp` (filled by it) has K and the sum over all K pairs for
-    // fitness and inlier_rmse.  The stop test looks at fitness and the rmse of the pass's OWN statistics.  *state: 1 once
+    // fitness and inlier_rmse.  The stop test looks at fitness and the rmse of the pass's OWN statistics.  *state (may be NULL): 1 once
     // a pass ran on the engine.  fill_info(stats) runs behind the last pass.
     template <class Reduce, class FillInfo>
     int run_pair_passes(const double *init, double max_dist, bool plane, int max_iter, double rel_fit, double rel_rmse,
                         bool scaling, visma_icp_result *out, int *state, const Engine::PairPass &pp, Reduce reduce,
                         FillInfo fill_info)
+    {
+        return run_pair_passes(init, max_dist, plane, max_iter, rel_fit, rel_rmse, scaling, out, state, pp, reduce, fill_info,
+                               [](const double *stats) { return trimmed_rmse(stats); });
+    }
+    // ... own_rmse(stats): the rmse the stop test compares, where it is not that of the statistics' [1] / [0] (generalized
+    // ICP: the Mahalanobis rmse of the pass, which `reduce` left with the caller)
+    template <class Reduce, class FillInfo, class OwnRmse>
+    int run_pair_passes(const double *init, double max_dist, bool plane, int max_iter, double rel_fit, double rel_rmse,
+                        bool scaling, visma_icp_result *out, int *state, const Engine::PairPass &pp, Reduce reduce,
+                        FillInfo fill_info, OwnRmse own_rmse)
     {
         std::memset(out, 0, sizeof(*out));
         std::memcpy(out->transformation, init, sizeof(double) * 16);
@@ -170,9 +186,9 @@ struct visma_icp_ctx {
             last_plane = plane;
             rc = reduce(Tc, stats);
             if (rc) return eng_fail(rc);
-            *state = 1;
+            if (state) *state = 1;
             fit_rmse((double)pp.found, pp.sum_all, &fit, &rmse);
-            own = trimmed_rmse(stats);
+            own = own_rmse(stats);
             return VISMA_ICP_OK;
         };
         int rc = pass();

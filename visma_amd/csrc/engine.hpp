@@ -321,6 +321,25 @@ public:
     }
     // the weight per source POSITION of the last robust pass (0 where a position has no pair)
     virtual int get_pair_weights(double *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // Generalized ICP (gicp.hip): source normals by source POSITION (the order of set_source), fp32 and -- NULL: none --
+    // f64; a count other than the source's is refused, a new source drops them (as the target does with its normals).
+    // An engine without the pass keeps only the fact that they were given.
+    virtual int set_source_normals(const float * /* nxyzw */, const Pt64 * /* n64 */, int64_t ns)
+    {
+        if (ns != ns_) { err_ = "normals count != source count"; return VISMA_ICP_ERR_INVALID; }
+        has_source_normals_ = true;
+        return VISMA_ICP_OK;
+    }
+    // ... the pending pass's search, then the statistics with every pair weighted by M = (C_t + R C_s R^T)^-1,
+    // C = I - (1 - epsilon) n n^T (visma_icp.h); rows in the frame of `offset`
+    struct GicpPass : PairPass {
+        double cost = 0.0;              // sum of d^T M d
+    };
+    virtual int reduce_gicp(const Mat4 &, const double * /* offset[3] */, double /* epsilon */, double * /* stats */, GicpPass *)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.
@@ -454,11 +473,12 @@ public:
     int64_t ns() const { return ns_; }
     int64_t nt() const { return nt_; }
     bool has_normals() const { return has_normals_; }
+    bool has_source_normals() const { return has_source_normals_; }
 
 protected:
     std::string err_;
     int64_t ns_ = 0, nt_ = 0;
-    bool has_normals_ = false;
+    bool has_normals_ = false, has_source_normals_ = false;
 };
 
 

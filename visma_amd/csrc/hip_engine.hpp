@@ -29,6 +29,7 @@ public:
         free_dev(d_src_); free_dev(d_tgt_); free_dev(d_nrm_); free_dev(d_keys_); free_dev(d_gkeys_);
         free_dev(d_claim_); free_dev(d_d64_);
         free_dev(d_src64_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
+        free_dev(d_snrm_); free_dev(d_snrm64_);
         for (int i = 0; i < 4; i++) if (pin_[i]) (void)hipHostFree(pin_[i]);
         free_dev(d_idx_); free_dev(d_d2_); free_dev(d_pos_); free_dev(d_ru_); free_dev(d_partials_); free_dev(d_stats_);
         if (d_vox_out_) (void)hipFree(d_vox_out_);
@@ -319,6 +320,11 @@ public:
     void *d_rob_w_ = nullptr, *d_rob_r2_ = nullptr;
     int64_t rob_w_cap_ = 0, rob_r2_cap_ = 0, rob_w_ns_ = -1;
 
+    // generalized ICP (gicp.hip): the plain pass, then the reduction weighted by both points' surface covariances
+    int set_source_normals(const float *nxyzw, const Pt64 *n64, int64_t ns) override;
+    int reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon, double *stats, GicpPass *out) override;
+    void *d_snrm_ = nullptr, *d_snrm64_ = nullptr;          // source normals by source position: fp32, and f64 next to d_src64_
+
     // What a pass over the pairs of the last nn_pass works in.  The trimmed and the robust pass share the one instance:
     // they never overlap on the stream, and each pass re-arms the words it used.  Sized for the larger user.
     struct PairScratch {
@@ -420,6 +426,8 @@ private:
         ns_ = ns;
         have_pass_ = false;
         free_dev(d_src64_);                                      // belongs to the previous source
+        free_dev(d_snrm_); free_dev(d_snrm64_);                  // ... and so do its normals
+        has_source_normals_ = false;
         return invalidate_pos();
     }
     int ensure_target(int64_t nt);

@@ -802,6 +802,51 @@ int HipEngine::get_pair_weights(double *w)
     return VISMA_ICP_OK;
 }
 
+int HipEngine::set_source_normals(const float *nxyzw, const Pt64 *n64, int64_t ns)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (ns != ns_) { err_ = "normals count != source count"; return VISMA_ICP_ERR_INVALID; }
+    free_dev(d_snrm_); free_dev(d_snrm64_);
+    has_source_normals_ = false;
+    HIP_TRY(hipMalloc(&d_snrm_, sizeof(float4) * (size_t)std::max<int64_t>(ns, 1)));
+    if (ns > 0) HIP_TRY(hipMemcpy(d_snrm_, nxyzw, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice));
+    if (n64 && d_src64_) {                                   // (read where the pass sums from the f64 clouds)
+        HIP_TRY(hipMalloc(&d_snrm64_, sizeof(Pt64) * (size_t)std::max<int64_t>(ns, 1)));
+        if (ns > 0) HIP_TRY(hipMemcpy(d_snrm64_, n64, sizeof(Pt64) * (size_t)ns, hipMemcpyHostToDevice));
+    }
+    has_source_normals_ = true;
+    return VISMA_ICP_OK;
+}
+
+// One generalized pass: the plain pass as reduce() runs it (K, the sum of d^2 over all K pairs, the warm-start state), then
+// the reduction weighted by the inverse of the sum of both points' surface covariances on the stream; the host waits
+// for its tagged granules like reduce() waits for its own.
+int HipEngine::reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon, double *stats, GicpPass *out)
+{
+    if (!d_snrm_) { err_ = "generalized ICP needs source normals"; return VISMA_ICP_ERR_STATE; }
+    GicpPass found;
+    int rc = pair_pass_begin("generalized", Tc, offset, true, &found);
+    if (rc) return rc;
+    *out = found;
+    GicpArgs a;
+    rc = pair_pass_args("generalized", Tc, offset, &a);
+    if (rc) return rc;
+    if (a.src64) { a.nrm64 = (const Pt64 *)d_nrm64_; a.snrm64 = (const Pt64 *)d_snrm64_; }
+    a.nrm = (const float4 *)d_nrm_;
+    a.snrm = (const float4 *)d_snrm_;
+    a.epsilon = epsilon;
+    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
+    HIP_TRY(pair_.arm(stream_));
+    HIP_TRY(launch_gicp_reduce(a, stream_));
+    double pub[kGicpPublished];
+    rc = wait_granules(pair_.host, kGicpPublished, a.seq, "generalized", pub);
+    if (rc) return rc;
+    pair_.disarm();
+    for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
+    out->cost = pub[kNStats];
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

@@ -571,6 +571,17 @@ int robust_reduce_blocks(int64_t ns);
 hipError_t launch_robust_residual(const RobustArgs &a, hipStream_t stream);
 hipError_t launch_robust_reduce(const RobustArgs &a, int plane, hipStream_t stream);
 
+// ---- generalized ICP (gicp.hip): every pair of the last pass weighted by the inverse of the sum of both points' surface covariances ----
+constexpr int kGicpRow = 32;                           // doubles per partial row: 30 accumulators (K, sum |d|^2, 21 + 6, the cost)
+constexpr int kGicpPublished = kNStats + 1;            // granules to the host: 38 statistics, sum d^T M d
+struct GicpArgs : PairPassArgs {
+    const float4 *nrm = nullptr, *snrm = nullptr;      // target normals by original index, source normals by source position, and ...
+    const Pt64 *nrm64 = nullptr, *snrm64 = nullptr;    // ... in f64 where the f64 passes read them (each on its own: NULL = the fp32 copy)
+    double epsilon = 1.0;                              // the covariance along the normal, in (0, 1]
+    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
+};
+hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream);
+
 // fill n float4 with +inf (target padding)
 hipError_t launch_fill_inf(float4 *dst, int64_t n, hipStream_t stream);
 // AoS stride-s floats -> float4 (w = 0)
