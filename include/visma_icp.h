@@ -504,6 +504,75 @@ VISMA_ICP_API int visma_icp_run_yaw_sweep_gicp(visma_icp_ctx *ctx, int level, do
                                                visma_icp_result *best, int *best_level, visma_icp_result *per_level,
                                                visma_icp_gicp_info *best_info, visma_icp_gicp_info *per_level_info);
 
+/* ---- colored ICP (Park, Zhou, Koltun: "Colored Point Cloud Registration Revisited", ICCV 2017; the reference's
+ * O3D/Core/Registration/ColoredICP.cpp).  Every pair enters the normal equations with two rows: the point-to-plane row and
+ * a photometric row that compares the source point's intensity with the target's, carried along the target's colour
+ * gradient to the source point's projection into the target's tangent plane.  A flat or smooth surface leaves the motion
+ * inside the surface free for every geometric estimator (on a plane the point-to-plane 6 x 6 is singular and the
+ * |det| < 1e-6 guard returns the identity); a texture pins it.  Prefer it for textured surfaces whose geometry leaves a
+ * motion free.
+ *
+ *   Of a colour only the intensity I = (r + g + b) / 3.0 is kept (ColoredICP.cpp:94-95: f64, in that order), one f64 per
+ *   point; there is no fp32 copy (k / 255 is not an fp32 number, and the photometric residual is a difference of nearby
+ *   values).
+ *
+ *   The colour gradient g of target point k (ColoredICP.cpp:74-137), normal n, intensity I_k: neighbours by the Hybrid
+ *   search (radius, max_nn) in the order of visma_icp_estimate_normals(search_type = 2); fewer than 3 list entries: g = 0.
+ *   Else entry 0 is skipped whatever index it holds (the reference takes it for the point itself); every other entry a
+ *   gives the row a' - p, a' = a - ((a - p).n) n, with the right side I_a - I_k; one more row (nn - 1) n, nn the list
+ *   length, with the right side 0.  A^T A and A^T b are summed in f64 in list order; |det(A^T A)| < 1e-6 or a determinant
+ *   that is not finite: g = 0 (Eigen.cpp:41-43); else the symmetric 3 x 3 is solved in closed form (the reference: LDLT --
+ *   agreement to rounding, not to the bit).  max_nn outside [3, 170]: VISMA_ICP_ERR_INVALID (the lists live in LDS).
+ *
+ *   Pairs: those of the last visma_icp_nn_pass, (i, j) = (source, target).  In f64, lambda = lambda_geometric:
+ *     p = T s_i as the generalized pass forms it, q = t_j, n = n_j, g = g_j
+ *     r_g = sqrt(lambda) (p - q).n                      J_g = sqrt(lambda) [p x n | n]
+ *     p' = p - ((p - q).n) n
+ *     r_c = sqrt(1 - lambda) (I_s - (g.(p' - q) + I_t))  h = -(I - n n^T) g    J_c = sqrt(1 - lambda) [p x h | h]
+ *   Frame and offset as visma_icp_reduce_gicp: rows in the caller's (world) frame.  Normals, colours and gradients are
+ *   used AS GIVEN; a non-finite one reaches the sums only, never an index or an address.
+ *
+ * Statistics in the layout of visma_icp_reduce (the host solves take them unchanged: VISMA_ICP_SOLVER_GN_EULER, on a
+ * context with a rotation axis visma_icp_solve_from_stats_axis(plane = 1)):
+ *   [0] = K   [1] = sum |p - q|^2   [2:23] = upper triangle of sum (J_g^T J_g + J_c^T J_c)
+ *   [23:29] = sum (J_g^T r_g + J_c^T r_c)   [29:38] = 0
+ * and in visma_icp_colored_info the cost sum (r_g^2 + r_c^2) -- what the reference's ComputeRMSE returns
+ * (ColoredICP.cpp:203-232) -- and its two parts.  No floating-point atomics: a run is bit-identical to itself.
+ *
+ * lambda_geometric outside [0, 1] or not finite becomes 0.968, as ColoredICP.cpp:54-55 does: NOT an error.
+ * NOT offered: sharded contexts (VISMA_ICP_ERR_INVALID, as the generalized pass); a yaw sweep, batches or a corpus
+ * (sampled CAD models carry no colour); a combination with trimming, robust weights or the generalized weights. */
+typedef struct {
+    double cost;               /* sum r_g^2 + r_c^2 of the last pass */
+    double geometric_cost;     /* sum r_g^2 */
+    double photometric_cost;   /* sum r_c^2 */
+} visma_icp_colored_info;
+
+/* Colours of the source / the target, one per point in the caller's order (rgb[i * stride + 0..2]), after the cloud is
+ * set; the count must be the cloud's (VISMA_ICP_ERR_INVALID).  A new source or target drops its colours, as it drops
+ * its normals. */
+VISMA_ICP_API int visma_icp_set_source_colors_f64(visma_icp_ctx *ctx, const double *rgb, int64_t ns, int stride);
+VISMA_ICP_API int visma_icp_set_target_colors_f64(visma_icp_ctx *ctx, const double *rgb, int64_t nt, int stride);
+/* Computes the colour gradient of the context's target and keeps it on the device.  Without target normals and target
+ * colours: VISMA_ICP_ERR_STATE.  A new target, new target normals or new target colours drop it.  The points and
+ * normals are the copies the passes read: f64 where the context holds them, else fp32. */
+VISMA_ICP_API int visma_icp_prepare_colored(visma_icp_ctx *ctx, double radius, int max_nn);
+/* ... nt x 3 doubles in the caller's order; VISMA_ICP_ERR_STATE without a gradient. */
+VISMA_ICP_API int visma_icp_get_color_gradient(visma_icp_ctx *ctx, double *out, int64_t nt);
+/* The colored statistics of the last visma_icp_nn_pass.  Before a pass, or without target normals, target colours, source
+ * colours or the gradient: VISMA_ICP_ERR_STATE. */
+VISMA_ICP_API int visma_icp_reduce_colored(visma_icp_ctx *ctx, double lambda_geometric, double out_stats[VISMA_ICP_NSTATS],
+                                           visma_icp_colored_info *info);
+/* RegistrationColoredICP (ColoredICP.cpp:236-246): the gradient by visma_icp_prepare_colored(2 * max_dist, 30) unless one
+ * for exactly these two values is held, then RegistrationICP's loop (Registration.cpp:159-185) with the colored pass.
+ * Its stop test compares the plain fitness (K / NS) and the plain inlier_rmse of consecutive passes, as the reference's
+ * loop does for every estimator -- not the colored cost.  *info (may be NULL) belongs to the last pass.  Without target
+ * normals, target colours or source colours the run returns init (as visma_icp_run_gicp without normals).  One launch
+ * sequence per pass; never the persistent launch. */
+VISMA_ICP_API int visma_icp_run_colored(visma_icp_ctx *ctx, const double init[16], double max_dist, double lambda_geometric,
+                                        int max_iter, double rel_fitness, double rel_rmse, visma_icp_result *out,
+                                        visma_icp_colored_info *info);
+
 /* ---- batched small problems (AnnotationTool loop, src/annotation.cpp:103-168) */
 
 typedef struct {
@@ -791,6 +860,11 @@ VISMA_ICP_API int visma_icp_sample_mesh(visma_icp_ctx *ctx, const double *V, int
 VISMA_ICP_API int visma_icp_estimate_normals(visma_icp_ctx *ctx, const double *xyz, int64_t n,
                                              const double *normals_in, int search_type, int knn,
                                              double radius, double *normals_out);
+
+/* The colour gradient per point of colored ICP (the block above visma_icp_colored_info states it) for any cloud:
+ * xyz, normals, colors n x 3 f64 in, out_grad n x 3 f64.  max_nn outside [3, 170]: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_color_gradient(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals,
+                                           const double *colors, double radius, int max_nn, double *out_grad);
 
 /* Point -> triangle-mesh squared distance, face and closest point for np query
  * points: what igl::AABB::squared_distance returns inside feh::MeasureSurfaceError

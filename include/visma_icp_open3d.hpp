@@ -24,6 +24,10 @@
 //                                      generalized ICP (plane-to-plane) through RegistrationICP: every pair weighted
 //                                      by the inverse of the sum of both points' surface covariances; needs the
 //                                      normals of BOTH clouds (a sampled CAD model has exact ones)
+//   open3d::cicp::TransformationEstimationForColoredICP(lambda_geometric) / cicp::RegistrationColoredICP
+//                                      colored ICP (O3D/Core/Registration/ColoredICP.h): a photometric row next to
+//                                      the point-to-plane row of every pair; needs the target's normals and the
+//                                      colours of BOTH clouds -- for textured surfaces whose geometry leaves a motion free
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -214,6 +218,34 @@ public:
                                                  const PointCloud &target,
                                                  const CorrespondenceSet &corres) const override;
     double epsilon_ = 1e-3;
+};
+
+// Colored ICP (Park, Zhou, Koltun, ICCV 2017; O3D/Core/Registration/ColoredICP.cpp; visma_icp.h states the step).
+// lambda_geometric outside [0, 1] becomes 0.968, as the reference's constructor does.  What cicp::RegistrationICP returns
+// for it: all K pairs of the last pass, K / |source| and the plain rmse over them (what the loop's stop test compares).
+// The library computes the target's colour gradient itself (Hybrid search: 2 x the correspondence distance, 30).
+// ComputeRMSE(source, target, corres) is the reference's value -- the SUM r_g^2 + r_c^2, no root, no mean
+// (ColoredICP.cpp:203-232) -- and ComputeTransformation the colored step over the corres they are given, restated on the
+// host.  Both need the target's gradient in color_gradient_ (one per target point: cicp::ComputeColorGradient); without
+// one of that size they return 0 and the identity.
+class TransformationEstimationForColoredICP : public TransformationEstimation {
+public:
+    explicit TransformationEstimationForColoredICP(double lambda_geometric = 0.968) : lambda_geometric_(lambda_geometric)
+    {
+        if (!(lambda_geometric_ >= 0.0 && lambda_geometric_ <= 1.0)) lambda_geometric_ = 0.968;
+    }
+    ~TransformationEstimationForColoredICP() override {}
+    TransformationEstimationType GetTransformationEstimationType() const override
+    {
+        return TransformationEstimationType::ColoredICP;
+    }
+    inline double ComputeRMSE(const PointCloud &source, const PointCloud &target,
+                              const CorrespondenceSet &corres) const override;
+    inline Eigen::Matrix4d ComputeTransformation(const PointCloud &source,
+                                                 const PointCloud &target,
+                                                 const CorrespondenceSet &corres) const override;
+    double lambda_geometric_ = 0.968;
+    std::vector<Eigen::Vector3d> color_gradient_;      // of the target, for the host restatements only
 };
 
 namespace detail {
@@ -435,6 +467,49 @@ inline double host_stats_gicp(const Cloud &source, const Cloud &target, const Co
     return cost;
 }
 
+// The colored statistics of explicit correspondences (visma_icp.h: colored ICP) on the host; grad: the target's colour
+// gradient, one per target point.  Returns sum r_g^2 + r_c^2.
+template <typename Cloud, typename Corr>
+inline double host_stats_colored(const Cloud &source, const Cloud &target, const Corr &corres, const std::vector<Eigen::Vector3d> &grad,
+                                 double lambda, double st[VISMA_ICP_NSTATS])
+{
+    double A[6][6] = {{0}}, b[6] = {0}, r2 = 0.0, cost = 0.0;
+    const double sg = std::sqrt(lambda), sc = std::sqrt(1.0 - lambda);
+    auto add_row = [&](const Eigen::Vector3d &p, const double v[3], double s, double r) {
+        const double J[6] = {s * (p[1] * v[2] - p[2] * v[1]), s * (p[2] * v[0] - p[0] * v[2]), s * (p[0] * v[1] - p[1] * v[0]),
+                             s * v[0], s * v[1], s * v[2]};
+        for (int i = 0; i < 6; i++) {
+            for (int j = i; j < 6; j++) A[i][j] += J[i] * J[j];
+            b[i] += J[i] * r;
+        }
+    };
+    for (const auto &c : corres) {
+        const Eigen::Vector3d &p = source.points_[c[0]], &q = target.points_[c[1]];
+        const Eigen::Vector3d &n = target.normals_[c[1]], &g = grad[c[1]];
+        const Eigen::Vector3d &cs = source.colors_[c[0]], &ct = target.colors_[c[1]];
+        const double is = (cs[0] + cs[1] + cs[2]) / 3.0, it = (ct[0] + ct[1] + ct[2]) / 3.0;
+        const double d[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
+        const double dn = d[0] * n[0] + d[1] * n[1] + d[2] * n[2];
+        const double e[3] = {(p[0] - dn * n[0]) - q[0], (p[1] - dn * n[1]) - q[1], (p[2] - dn * n[2]) - q[2]};
+        const double rg = sg * dn, rc = sc * (is - ((g[0] * e[0] + g[1] * e[1] + g[2] * e[2]) + it));
+        const double gn = g[0] * n[0] + g[1] * n[1] + g[2] * n[2];
+        const double h[3] = {-(g[0] - gn * n[0]), -(g[1] - gn * n[1]), -(g[2] - gn * n[2])};   // -(I - n n^T) g
+        const double nn[3] = {n[0], n[1], n[2]};
+        add_row(p, nn, sg, rg);
+        add_row(p, h, sc, rc);
+        r2 += d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        cost += rg * rg + rc * rc;
+    }
+    int o = 0;
+    st[o++] = (double)corres.size();
+    st[o++] = r2;
+    for (int i = 0; i < 6; i++)
+        for (int j = i; j < 6; j++) st[o++] = A[i][j];
+    for (int i = 0; i < 6; i++) st[o++] = b[i];
+    while (o < VISMA_ICP_NSTATS) st[o++] = 0.0;
+    return cost;
+}
+
 // the stock point-to-plane ComputeRMSE (TransformationEstimation.cpp:64-75, with its `err = r * r`)
 template <typename Cloud, typename Corr>
 inline double host_rmse_point_to_plane(const Cloud &s, const Cloud &t, const Corr &c)
@@ -596,6 +671,25 @@ inline RegistrationResult RegistrationICP(
         detail::fill_result(ctx, r, source.points_.size(), result);
         return result;
     }
+    if (dyn == typeid(TransformationEstimationForColoredICP)) {
+        const auto *c = static_cast<const TransformationEstimationForColoredICP *>(&estimation);
+        if (!target.HasNormals() || !target.HasColors() || !source.HasColors()) {
+            std::fprintf(stderr, "Error: TransformationEstimationForColoredICP requires target normals and the colours of both clouds.\n");
+            return RegistrationResult(init);
+        }
+        detail::check(ctx, visma_icp_set_target_normals_f64(ctx, detail::xyz(target.normals_), (int64_t)target.normals_.size(), 3),
+                      "visma_icp_set_target_normals_f64");
+        detail::check(ctx, visma_icp_set_target_colors_f64(ctx, detail::xyz(target.colors_), (int64_t)target.colors_.size(), 3),
+                      "visma_icp_set_target_colors_f64");
+        detail::check(ctx, visma_icp_set_source_colors_f64(ctx, detail::xyz(source.colors_), (int64_t)source.colors_.size(), 3),
+                      "visma_icp_set_source_colors_f64");
+        visma_icp_colored_info info;
+        detail::check(ctx, visma_icp_run_colored(ctx, T, max_correspondence_distance, c->lambda_geometric_, criteria.max_iteration_,
+                                                 criteria.relative_fitness_, criteria.relative_rmse_, &r, &info),
+                      "visma_icp_run_colored");
+        detail::fill_result(ctx, r, source.points_.size(), result);
+        return result;
+    }
     if (four || p2p) {
         const bool scaling = four ? four->with_scaling_ : p2p->with_scaling_;
         detail::check(ctx, visma_icp_run(ctx, T, max_correspondence_distance, criteria.max_iteration_,
@@ -639,6 +733,29 @@ inline RegistrationResult RegistrationICP(
             break;
     }
     return result;
+}
+
+// open3d::RegistrationColoredICP (O3D/Core/Registration/ColoredICP.h): the colour gradient of the target by the Hybrid
+// search (2 x max_distance, 30), then RegistrationICP with the colored estimator.
+inline RegistrationResult RegistrationColoredICP(const PointCloud &source, const PointCloud &target, double max_distance,
+                                                 const Eigen::Matrix4d &init = Eigen::Matrix4d::Identity(),
+                                                 const ICPConvergenceCriteria &criteria = ICPConvergenceCriteria(),
+                                                 double lambda_geometric = 0.968)
+{
+    return cicp::RegistrationICP(source, target, max_distance, init, TransformationEstimationForColoredICP(lambda_geometric), criteria);
+}
+
+// The colour gradient per point of a cloud with normals and colours, as the library computes it for colored ICP
+// (visma_icp_color_gradient): what TransformationEstimationForColoredICP::color_gradient_ takes.
+inline std::vector<Eigen::Vector3d> ComputeColorGradient(const PointCloud &cloud, double radius, int max_nn = 30)
+{
+    std::vector<Eigen::Vector3d> g(cloud.points_.size(), Eigen::Vector3d::Zero());
+    if (g.empty() || !cloud.HasNormals() || !cloud.HasColors()) return g;
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    detail::check(ctx, visma_icp_color_gradient(ctx, detail::xyz(cloud.points_), (int64_t)g.size(), detail::xyz(cloud.normals_),
+                                                detail::xyz(cloud.colors_), radius, max_nn, g[0].data()),
+                  "visma_icp_color_gradient");
+    return g;
 }
 
 // feh::RegisterModelToScene (src/annotation.cpp:29-64) with its JSON options
@@ -1118,6 +1235,28 @@ inline Eigen::Matrix4d TransformationEstimationGeneralized::ComputeTransformatio
     return detail::from_rowmajor(T);
 }
 
+inline double TransformationEstimationForColoredICP::ComputeRMSE(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    if (corres.empty() || !target.HasNormals() || !target.HasColors() || !source.HasColors() ||
+        color_gradient_.size() != target.points_.size())
+        return 0.0;
+    double st[VISMA_ICP_NSTATS];
+    return detail::host_stats_colored(source, target, corres, color_gradient_, lambda_geometric_, st);
+}
+
+inline Eigen::Matrix4d TransformationEstimationForColoredICP::ComputeTransformation(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
+{
+    if (corres.empty() || !target.HasNormals() || !target.HasColors() || !source.HasColors() ||
+        color_gradient_.size() != target.points_.size())
+        return Eigen::Matrix4d::Identity();
+    double st[VISMA_ICP_NSTATS], T[16];
+    (void)detail::host_stats_colored(source, target, corres, color_gradient_, lambda_geometric_, st);
+    visma_icp_solve_from_stats(st, VISMA_ICP_SOLVER_GN_EULER, 0, T);
+    return detail::from_rowmajor(T);
+}
+
 // ---- the estimators constrained to a rotation about up_ ----------------------
 inline double TransformationEstimationPointToPointYaw::ComputeRMSE(
     const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres) const
@@ -1183,6 +1322,13 @@ inline RegistrationResult EvaluateRegistration(const PointCloud &source, const P
                                                const Eigen::Matrix4d &transformation)
 {
     return cicp::EvaluateRegistration(source, target, max_correspondence_distance, transformation);
+}
+inline RegistrationResult RegistrationColoredICP(const PointCloud &source, const PointCloud &target, double max_distance,
+                                                 const Eigen::Matrix4d &init = Eigen::Matrix4d::Identity(),
+                                                 const ICPConvergenceCriteria &criteria = ICPConvergenceCriteria(),
+                                                 double lambda_geometric = 0.968)
+{
+    return cicp::RegistrationColoredICP(source, target, max_distance, init, criteria, lambda_geometric);
 }
 inline bool ReadPointCloudFromPLY(const std::string &filename, PointCloud &pointcloud)
 {

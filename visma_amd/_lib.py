@@ -229,6 +229,16 @@ def _bind(L):
         L.visma_icp_run_yaw_sweep_gicp.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
                                                    C.c_double, C.POINTER(CResult), C.POINTER(C.c_int), C.POINTER(CResult),
                                                    _gi, _gi]
+    if hasattr(L, "visma_icp_run_colored"):              # (A/B runs load older builds through VISMA_ICP_LIB)
+        _ci = C.POINTER(CColoredInfo)
+        L.visma_icp_set_source_colors_f64.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_int]
+        L.visma_icp_set_target_colors_f64.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_int]
+        L.visma_icp_prepare_colored.argtypes = [C.c_void_p, C.c_double, C.c_int]
+        L.visma_icp_get_color_gradient.argtypes = [C.c_void_p, _dp, C.c_int64]
+        L.visma_icp_reduce_colored.argtypes = [C.c_void_p, C.c_double, _dp, _ci]
+        L.visma_icp_run_colored.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                            C.POINTER(CResult), _ci]
+        L.visma_icp_color_gradient.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_double, C.c_int, _dp]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -329,6 +339,24 @@ class GicpInfo:
 
     def __repr__(self):
         return "GicpInfo(cost=%.6g, mahalanobis_rmse=%.6g)" % (self.cost, self.mahalanobis_rmse)
+
+
+class CColoredInfo(C.Structure):
+    """visma_icp_colored_info"""
+    _fields_ = [("cost", C.c_double), ("geometric_cost", C.c_double), ("photometric_cost", C.c_double)]
+
+
+class ColoredInfo:
+    """A colored pass: cost = sum r_g^2 + r_c^2 over its pairs (the reference's ComputeRMSE) and its two parts."""
+
+    def __init__(self, c):
+        self.cost = float(c.cost)
+        self.geometric_cost = float(c.geometric_cost)
+        self.photometric_cost = float(c.photometric_cost)
+
+    def __repr__(self):
+        return "ColoredInfo(cost=%.6g, geometric_cost=%.6g, photometric_cost=%.6g)" % (
+            self.cost, self.geometric_cost, self.photometric_cost)
 
 
 class Result:
@@ -608,6 +636,44 @@ class Context:
             r = Result(p); r.gicp = GicpInfo(i); rs.append(r)
         return rb, bl.value, rs
 
+    def set_source_colors_f64(self, rgb):
+        """Colours of the source (caller's order, after the source is set): colored ICP keeps I = (r + g + b) / 3."""
+        c = _f64(rgb, (-1, 3))
+        self._chk(self.L.visma_icp_set_source_colors_f64(self._h, _p(c, _dp), len(c), 3))
+
+    def set_target_colors_f64(self, rgb):
+        c = _f64(rgb, (-1, 3))
+        self._chk(self.L.visma_icp_set_target_colors_f64(self._h, _p(c, _dp), len(c), 3))
+
+    def prepare_colored(self, radius, max_nn=30):
+        """The colour gradient of the target (Hybrid search: radius, max_nn), kept on the device; needs target normals
+        and target colours."""
+        self._chk(self.L.visma_icp_prepare_colored(self._h, float(radius), int(max_nn)))
+
+    def color_gradient_of_target(self):
+        """The kept gradient, (nt, 3) in the caller's order."""
+        nt = int(getattr(self, "nt", 0))
+        out = np.empty((max(nt, 1), 3))
+        self._chk(self.L.visma_icp_get_color_gradient(self._h, _p(out, _dp), nt))
+        return out[:nt].copy()
+
+    def reduce_colored(self, lambda_geometric=0.968):
+        """The colored statistics of the last nn_pass -> (stats, ColoredInfo)."""
+        st = np.empty(NSTATS); info = CColoredInfo()
+        self._chk(self.L.visma_icp_reduce_colored(self._h, float(lambda_geometric), _p(st, _dp), C.byref(info)))
+        return st, ColoredInfo(info)
+
+    def run_colored(self, init=None, max_dist=0.05, lambda_geometric=0.968, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+        """Colored ICP: a photometric row next to the point-to-plane row of every pair; needs target normals and both
+        clouds' colours.  -> Result with .colored (ColoredInfo)."""
+        init = _f64(np.eye(4) if init is None else init, (16,))
+        out = CResult(); info = CColoredInfo()
+        self._chk(self.L.visma_icp_run_colored(self._h, _p(init, _dp), float(max_dist), float(lambda_geometric), int(max_iter),
+                                               float(rel_fitness), float(rel_rmse), C.byref(out), C.byref(info)))
+        r = Result(out)
+        r.colored = ColoredInfo(info)
+        return r
+
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""
         T = _f64(np.eye(4) if T is None else T, (16,)).copy()
@@ -691,6 +757,17 @@ class Context:
         out = np.empty((max(n, 1), 3))
         self._chk(self.L.visma_icp_estimate_normals(self._h, _p(p, _dp), n, None if nin is None else _p(nin, _dp),
                                                     kind, int(knn or 0), float(radius or 0.0), _p(out, _dp)))
+        return out[:n].copy()
+
+    def color_gradient(self, xyz, normals, colors, radius, max_nn=30):
+        """The colour gradient per point of colored ICP (ColoredICP.cpp:74-137) for any cloud -> (n, 3)."""
+        p = _f64(xyz, (-1, 3)); n = len(p)
+        nn = _f64(normals, (-1, 3)); cc = _f64(colors, (-1, 3))
+        if len(nn) != n or len(cc) != n:
+            raise ValueError("color_gradient: one normal and one colour per point")
+        out = np.empty((max(n, 1), 3))
+        self._chk(self.L.visma_icp_color_gradient(self._h, _p(p, _dp), n, _p(nn, _dp), _p(cc, _dp), float(radius), int(max_nn),
+                                                  _p(out, _dp)))
         return out[:n].copy()
 
     def voxel_down_sample(self, xyz, voxel_size, normals=None, colors=None):

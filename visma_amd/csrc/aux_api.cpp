@@ -39,6 +39,22 @@ int visma_icp_estimate_normals(visma_icp_ctx *ctx, const double *xyz, int64_t n,
     return VISMA_ICP_OK;
 }
 
+int visma_icp_color_gradient(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, const double *colors,
+                             double radius, int max_nn, double *out_grad)
+{
+    CTX_CHECK();
+    if (n < 0 || (n > 0 && (!xyz || !normals || !colors || !out_grad)) || std::isnan(radius))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad color_gradient arguments");
+    if (max_nn < 3 || max_nn > kNormalsMaxList) return ctx->fail(VISMA_ICP_ERR_INVALID, "color_gradient: max_nn must lie in [3, 170]");
+    if (n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "color_gradient needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    hipError_t e = color_gradient_device(xyz, n, normals, colors, radius, max_nn, out_grad, ctx->eng->aux_stream());
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("color_gradient: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_point_mesh_distance(visma_icp_ctx *ctx, const double *P, int64_t np, const double *V,
                                   int64_t nv, const int32_t *F, int64_t nf, double *d2, int32_t *face,
                                   double *closest)

@@ -12,12 +12,13 @@ namespace {
 class HookEngine : public Engine {
 public:
     HookEngine(const visma_icp_engine &vt, void *user) : vt_(vt), user_(user) {}
-    int set_source(const float *p, int64_t n) override { ns_ = n; has_source_normals_ = false; return wrap(vt_.set_source(user_, p, n)); }
-    int set_target(const float *p, int64_t n) override { nt_ = n; has_normals_ = false; return wrap(vt_.set_target(user_, p, n)); }
+    int set_source(const float *p, int64_t n) override { ns_ = n; has_source_normals_ = has_source_colors_ = false; return wrap(vt_.set_source(user_, p, n)); }
+    int set_target(const float *p, int64_t n) override { nt_ = n; has_normals_ = has_target_colors_ = false; drop_color_gradient(); return wrap(vt_.set_target(user_, p, n)); }
     int set_target_normals(const float *p, int64_t n) override
     {
         if (!vt_.set_target_normals) { err_ = "engine has no normals support"; return VISMA_ICP_ERR_ENGINE; }
         has_normals_ = true;
+        drop_color_gradient();
         return wrap(vt_.set_target_normals(user_, p, n));
     }
     int nn_pass(const Mat4 &Tc, double r) override { return wrap(vt_.nn_pass(user_, Tc.m, r)); }
@@ -992,6 +993,109 @@ int visma_icp_run_yaw_sweep_gicp(visma_icp_ctx *ctx, int level, double max_dist,
     return sweep_sequential(level, [&](const Mat4 &init, visma_icp_result *r, visma_icp_gicp_info *ri) {
         return visma_icp_run_gicp(ctx, init.m, max_dist, epsilon, max_iter, rel_fitness, rel_rmse, r, ri);
     }, best, best_level, per_level, best_info, per_level_info);
+}
+
+// ---- colored ICP ------------------------------------------------------------------------------------------------------
+// ColoredICP.cpp:54-55: a lambda_geometric outside [0, 1] (or not finite) is replaced, not refused
+static double colored_lambda(double lambda) { return (std::isfinite(lambda) && lambda >= 0.0 && lambda <= 1.0) ? lambda : 0.968; }
+
+// everything that is wrong with a call before any pass
+static int check_colored(visma_icp_ctx *ctx)
+{
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "colored ICP runs on one rank");
+    if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_set_source_colors_f64(visma_icp_ctx *ctx, const double *rgb, int64_t ns, int stride)
+{
+    CTX_CHECK();
+    if (!ctx->have_src) return ctx->fail(VISMA_ICP_ERR_STATE, "set the source first");
+    if (ns != ctx->eng->ns() || stride < 3 || (ns > 0 && !rgb)) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad colours arguments");
+    // by source POSITION: the engine holds the source in Morton order
+    std::vector<double> inten((size_t)std::max<int64_t>(ns, 1));
+    color_intensities(rgb, ns, stride, ctx->order_ptr(), inten.data());
+    int rc = ctx->eng->set_source_intensity(inten.data(), ns);
+    if (rc) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_set_target_colors_f64(visma_icp_ctx *ctx, const double *rgb, int64_t nt, int stride)
+{
+    CTX_CHECK();
+    if (!ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "set the target first");
+    if (nt != ctx->eng->nt() || stride < 3 || (nt > 0 && !rgb)) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad colours arguments");
+    std::vector<double> inten((size_t)std::max<int64_t>(nt, 1));
+    color_intensities(rgb, nt, stride, nullptr, inten.data());
+    int rc = ctx->eng->set_target_intensity(inten.data(), nt);
+    if (rc) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_prepare_colored(visma_icp_ctx *ctx, double radius, int max_nn)
+{
+    CTX_CHECK();
+    if (max_nn < 3 || max_nn > kNormalsMaxList) return ctx->fail(VISMA_ICP_ERR_INVALID, "prepare_colored: max_nn must lie in [3, 170]");
+    if (std::isnan(radius)) return ctx->fail(VISMA_ICP_ERR_INVALID, "prepare_colored: radius is not a number");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "colored ICP runs on one rank");
+    if (!ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "target not set");       // (the source is not looked at)
+    if (!ctx->eng->has_normals() || !ctx->eng->has_target_colors())
+        return ctx->fail(VISMA_ICP_ERR_STATE, "colored ICP needs target normals and target colours");
+    int rc = ctx->eng->prepare_colored(radius, max_nn);
+    if (rc) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_get_color_gradient(visma_icp_ctx *ctx, double *out, int64_t nt)
+{
+    CTX_CHECK();
+    if (nt != ctx->eng->nt() || (nt > 0 && !out)) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad get_color_gradient arguments");
+    if (!ctx->eng->has_color_gradient()) return ctx->fail(VISMA_ICP_ERR_STATE, "no colour gradient: prepare_colored first");
+    int rc = ctx->eng->get_color_gradient(out);
+    if (rc) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_reduce_colored(visma_icp_ctx *ctx, double lambda_geometric, double out_stats[VISMA_ICP_NSTATS],
+                             visma_icp_colored_info *info)
+{
+    CTX_CHECK();
+    if (!out_stats || !info) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (int rc = check_colored(ctx)) return rc;
+    if (!ctx->eng->has_normals() || !ctx->eng->has_target_colors() || !ctx->eng->has_source_colors() || !ctx->eng->has_color_gradient())
+        return ctx->fail(VISMA_ICP_ERR_STATE, "colored ICP needs target normals, both clouds' colours and the colour gradient");
+    Engine::ColoredPass cp;
+    int rc = ctx->eng->reduce_colored(ctx->last_Tc, ctx->centre, colored_lambda(lambda_geometric), out_stats, &cp);
+    if (rc) return ctx->eng_fail(rc);
+    ctx->last_plane = true;
+    visma_icp_ctx::fill_colored_info(info, cp);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_run_colored(visma_icp_ctx *ctx, const double init[16], double max_dist, double lambda_geometric, int max_iter,
+                          double rel_fitness, double rel_rmse, visma_icp_result *out, visma_icp_colored_info *info)
+{
+    CTX_CHECK();
+    if (!init || !out || max_iter < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad run arguments");
+    if (int rc = check_colored(ctx)) return rc;
+    if (info) std::memset(info, 0, sizeof(*info));
+    const double lambda = colored_lambda(lambda_geometric);
+    // Registration.cpp:148-157 and ColoredICP.cpp:144-146: no radius, no normals or no colours return init
+    if (!(max_dist > 0.0) || !ctx->eng->has_normals() || !ctx->eng->has_target_colors() || !ctx->eng->has_source_colors()) {
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out->transformation, init, sizeof(double) * 16);
+        if (max_dist > 0.0) ctx->last_radius = max_dist;
+        return VISMA_ICP_OK;
+    }
+    if (!ctx->eng->has_color_gradient(2.0 * max_dist, 30)) {     // ColoredICP.cpp:242-243
+        int rc = ctx->eng->prepare_colored(2.0 * max_dist, 30);
+        if (rc) return ctx->eng_fail(rc);
+    }
+    Engine::ColoredPass cp;
+    return ctx->run_pair_passes(
+        init, max_dist, true, max_iter, rel_fitness, rel_rmse, false, out, nullptr, cp,
+        [&](const Mat4 &Tc, double *stats) { return ctx->eng->reduce_colored(Tc, ctx->centre, lambda, stats, &cp); },
+        [&](const double *) { if (info) visma_icp_ctx::fill_colored_info(info, cp); });
 }
 
 int visma_icp_iterate(visma_icp_ctx *ctx, double T_inout[16], double max_dist, int steps, int solver,

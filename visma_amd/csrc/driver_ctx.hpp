@@ -153,7 +153,14 @@ struct visma_icp_ctx {
         info->mahalanobis_rmse = gp.found > 0 ? std::sqrt(gp.cost / (double)gp.found) : 0.0;
     }
 
-    // RegistrationICP's loop around a pass over the pairs (trimmed, robust, generalized).  reduce(Tc, stats) is the engine's reduction
+    static void fill_colored_info(visma_icp_colored_info *info, const Engine::ColoredPass &cp)
+    {
+        info->cost = cp.geometric_cost + cp.photometric_cost;
+        info->geometric_cost = cp.geometric_cost;
+        info->photometric_cost = cp.photometric_cost;
+    }
+
+    // RegistrationICP's loop around a pass over the pairs (trimmed, robust, generalized, colored).  reduce(Tc, stats) is the engine's reduction
     // behind each NN pass: its statistics feed the solve, `pp` (filled by it) has K and the sum over all K pairs for
     // fitness and inlier_rmse.  The stop test looks at fitness and the rmse of the pass's OWN statistics.  *state (may be NULL): 1 once
     // a pass ran on the engine.  fill_info(stats) runs behind the last pass.

@@ -340,6 +340,35 @@ public:
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;
     }
+    // Colored ICP (color_gradient.hip, colored.hip): one f64 intensity per point -- the source's by source POSITION, the
+    // target's by original index --; a count other than the cloud's is refused, a new cloud drops its own (as it drops
+    // its normals).  An engine without the pass keeps only the fact that they were given.
+    virtual int set_source_intensity(const double *, int64_t ns)
+    {
+        if (ns != ns_) { err_ = "colours count != source count"; return VISMA_ICP_ERR_INVALID; }
+        has_source_colors_ = true;
+        return VISMA_ICP_OK;
+    }
+    virtual int set_target_intensity(const double *, int64_t nt)
+    {
+        if (nt != nt_) { err_ = "colours count != target count"; return VISMA_ICP_ERR_INVALID; }
+        has_target_colors_ = true;
+        drop_color_gradient();
+        return VISMA_ICP_OK;
+    }
+    // ... the colour gradient of the target by the Hybrid search (radius, max_nn), kept on the device; a new target, new
+    // target normals or new target colours drop it
+    virtual int prepare_colored(double /* radius */, int /* max_nn */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int get_color_gradient(double * /* nt x 3, original order */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // ... the pending pass's search, then the statistics of the two rows per pair (visma_icp.h); rows in the frame of `offset`
+    struct ColoredPass : PairPass {
+        double geometric_cost = 0.0, photometric_cost = 0.0;   // sum r_g^2, sum r_c^2
+    };
+    virtual int reduce_colored(const Mat4 &, const double * /* offset[3] */, double /* lambda */, double * /* stats */, ColoredPass *)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.
@@ -474,11 +503,19 @@ public:
     int64_t nt() const { return nt_; }
     bool has_normals() const { return has_normals_; }
     bool has_source_normals() const { return has_source_normals_; }
+    bool has_source_colors() const { return has_source_colors_; }
+    bool has_target_colors() const { return has_target_colors_; }
+    bool has_color_gradient() const { return has_color_gradient_; }
+    bool has_color_gradient(double radius, int max_nn) const { return has_color_gradient_ && grad_radius_ == radius && grad_max_nn_ == max_nn; }
 
 protected:
     std::string err_;
     int64_t ns_ = 0, nt_ = 0;
     bool has_normals_ = false, has_source_normals_ = false;
+    bool has_source_colors_ = false, has_target_colors_ = false, has_color_gradient_ = false;
+    double grad_radius_ = 0.0;                   // the search the kept gradient was computed with
+    int grad_max_nn_ = 0;
+    virtual void drop_color_gradient() { has_color_gradient_ = false; }
 };
 
 

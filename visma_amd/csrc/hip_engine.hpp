@@ -30,6 +30,7 @@ public:
         free_dev(d_claim_); free_dev(d_d64_);
         free_dev(d_src64_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
         free_dev(d_snrm_); free_dev(d_snrm64_);
+        free_dev(d_sint_); free_dev(d_tint_); free_dev(d_grad_);
         for (int i = 0; i < 4; i++) if (pin_[i]) (void)hipHostFree(pin_[i]);
         free_dev(d_idx_); free_dev(d_d2_); free_dev(d_pos_); free_dev(d_ru_); free_dev(d_partials_); free_dev(d_stats_);
         if (d_vox_out_) (void)hipFree(d_vox_out_);
@@ -231,6 +232,7 @@ public:
         HIP_TRY(hipMalloc(&d_nrm_, sizeof(float4) * (nt > 0 ? nt : 1)));
         if (nt > 0) HIP_TRY(hipMemcpy(d_nrm_, nxyzw, sizeof(float4) * nt, hipMemcpyHostToDevice));
         has_normals_ = true;
+        drop_color_gradient();                                   // (it was computed with the previous normals)
         return VISMA_ICP_OK;
     }
 
@@ -324,6 +326,17 @@ public:
     int set_source_normals(const float *nxyzw, const Pt64 *n64, int64_t ns) override;
     int reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon, double *stats, GicpPass *out) override;
     void *d_snrm_ = nullptr, *d_snrm64_ = nullptr;          // source normals by source position: fp32, and f64 next to d_src64_
+
+    // colored ICP (color_gradient.hip, colored.hip): f64 intensities of both clouds, the target's colour gradient, then the
+    // plain pass and the reduction over the two rows per pair
+    int set_source_intensity(const double *by_position, int64_t ns) override;
+    int set_target_intensity(const double *by_index, int64_t nt) override;
+    int prepare_colored(double radius, int max_nn) override;
+    int get_color_gradient(double *out) override;
+    int reduce_colored(const Mat4 &Tc, const double *offset, double lambda, double *stats, ColoredPass *out) override;
+    void drop_color_gradient() override { free_dev(d_grad_); has_color_gradient_ = false; }
+    void *d_sint_ = nullptr, *d_tint_ = nullptr;            // one double per point: by source position, by original target index
+    void *d_grad_ = nullptr;                                // 3 doubles per target point, original order
 
     // What a pass over the pairs of the last nn_pass works in.  The trimmed and the robust pass share the one instance:
     // they never overlap on the stream, and each pass re-arms the words it used.  Sized for the larger user.
@@ -428,6 +441,8 @@ private:
         free_dev(d_src64_);                                      // belongs to the previous source
         free_dev(d_snrm_); free_dev(d_snrm64_);                  // ... and so do its normals
         has_source_normals_ = false;
+        free_dev(d_sint_);                                       // ... and its colours
+        has_source_colors_ = false;
         return invalidate_pos();
     }
     int ensure_target(int64_t nt);

@@ -561,6 +561,9 @@ int HipEngine::ensure_target(int64_t nt)
     if (nt > 0x7fffffff - 4096) { err_ = "target too large for 32-bit indices"; return VISMA_ICP_ERR_INVALID; }
     free_dev(d_tgt_); free_dev(d_nrm_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
     has_normals_ = false;
+    free_dev(d_tint_);                                       // the previous target's colours and their gradient
+    has_target_colors_ = false;
+    drop_color_gradient();
     host_box_valid_ = false;
     // pad to a whole number of LDS chunks with +inf points (never accepted)
     nt_pad_ = ((nt + kTChunk - 1) / kTChunk) * kTChunk;

@@ -847,6 +847,101 @@ int HipEngine::reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon,
     return VISMA_ICP_OK;
 }
 
+int HipEngine::set_source_intensity(const double *by_position, int64_t ns)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (ns != ns_) { err_ = "colours count != source count"; return VISMA_ICP_ERR_INVALID; }
+    free_dev(d_sint_);
+    has_source_colors_ = false;
+    HIP_TRY(hipMalloc(&d_sint_, sizeof(double) * (size_t)std::max<int64_t>(ns, 1)));
+    if (ns > 0) HIP_TRY(hipMemcpy(d_sint_, by_position, sizeof(double) * (size_t)ns, hipMemcpyHostToDevice));
+    has_source_colors_ = true;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::set_target_intensity(const double *by_index, int64_t nt)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (nt != nt_) { err_ = "colours count != target count"; return VISMA_ICP_ERR_INVALID; }
+    free_dev(d_tint_);
+    has_target_colors_ = false;
+    drop_color_gradient();
+    HIP_TRY(hipMalloc(&d_tint_, sizeof(double) * (size_t)std::max<int64_t>(nt, 1)));
+    if (nt > 0) HIP_TRY(hipMemcpy(d_tint_, by_index, sizeof(double) * (size_t)nt, hipMemcpyHostToDevice));
+    has_target_colors_ = true;
+    return VISMA_ICP_OK;
+}
+
+// The colour gradient of the target from what the context holds of it: the f64 points and normals where the f64 search
+// keeps them, else the fp32 copies (then exactly the values every pass reads).  The gradient does not depend on the
+// frame, so the centred coordinates serve as they are.
+int HipEngine::prepare_colored(double radius, int max_nn)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (is_sharded()) { err_ = "colored ICP runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    if (!d_nrm_ || !d_tint_ || !d_tgt_) { err_ = "colored ICP needs target normals and target colours"; return VISMA_ICP_ERR_STATE; }
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    drop_color_gradient();
+    HIP_TRY(hipMalloc(&d_grad_, sizeof(double) * 3 * (size_t)std::max<int64_t>(nt_, 1)));
+    ColorGradientInput in;
+    if (d_tgt64_) in.xyz64 = (const Pt64 *)d_tgt64_; else in.xyz32 = (const float4 *)d_tgt_;
+    if (d_tgt64_ && d_nrm64_) in.nrm64 = (const Pt64 *)d_nrm64_; else in.nrm32 = (const float4 *)d_nrm_;
+    in.intensity = (const double *)d_tint_;
+    in.n = nt_;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    hipError_t e = color_gradient_on_device(in, radius, max_nn, (double *)d_grad_, stream_);
+    if (e != hipSuccess) {
+        free_dev(d_grad_);
+        err_ = std::string("color gradient: ") + hipGetErrorString(e);
+        return e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP;
+    }
+    has_color_gradient_ = true;
+    grad_radius_ = radius;
+    grad_max_nn_ = max_nn;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::get_color_gradient(double *out)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!has_color_gradient_ || !d_grad_) { err_ = "no colour gradient: prepare_colored first"; return VISMA_ICP_ERR_STATE; }
+    if (nt_ > 0) HIP_TRY(hipMemcpy(out, d_grad_, sizeof(double) * 3 * (size_t)nt_, hipMemcpyDeviceToHost));
+    return VISMA_ICP_OK;
+}
+
+// One colored pass: the plain pass as reduce() runs it (K, the sum of d^2 over all K pairs, the warm-start state), then
+// the reduction over the point-to-plane and the photometric row of every pair on the stream; the host waits for its
+// tagged granules like reduce() waits for its own.
+int HipEngine::reduce_colored(const Mat4 &Tc, const double *offset, double lambda, double *stats, ColoredPass *out)
+{
+    if (!d_sint_ || !d_tint_ || !d_grad_ || !has_color_gradient_) { err_ = "colored ICP needs both clouds' colours and the colour gradient"; return VISMA_ICP_ERR_STATE; }
+    ColoredPass found;
+    int rc = pair_pass_begin("colored", Tc, offset, true, &found);
+    if (rc) return rc;
+    *out = found;
+    ColoredArgs a;
+    rc = pair_pass_args("colored", Tc, offset, &a);
+    if (rc) return rc;
+    if (a.src64) a.nrm64 = (const Pt64 *)d_nrm64_;
+    a.nrm = (const float4 *)d_nrm_;
+    a.grad = (const double *)d_grad_;
+    a.src_int = (const double *)d_sint_;
+    a.tgt_int = (const double *)d_tint_;
+    a.sqrt_lambda = std::sqrt(lambda);
+    a.sqrt_one_minus_lambda = std::sqrt(1.0 - lambda);
+    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
+    HIP_TRY(pair_.arm(stream_));
+    HIP_TRY(launch_colored_reduce(a, stream_));
+    double pub[kColoredPublished];
+    rc = wait_granules(pair_.host, kColoredPublished, a.seq, "colored", pub);
+    if (rc) return rc;
+    pair_.disarm();
+    for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
+    out->geometric_cost = pub[kNStats];
+    out->photometric_cost = pub[kNStats + 1];
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

@@ -582,6 +582,37 @@ struct GicpArgs : PairPassArgs {
 };
 hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream);
 
+// ---- colored ICP (color_gradient.hip, colored.hip): a photometric row next to the point-to-plane row of every pair ----
+// I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
+inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }
+void color_intensities(const double *rgb, int64_t n, int stride, const int32_t *order, double *out);
+// What the gradient kernel is given, all on the device: points and normals in exactly one of three forms each (n x 3
+// doubles, Pt64, float4), one intensity per point.  origin: the point the fp32 binning copy is taken relative to.
+struct ColorGradientInput {
+    const double *xyz = nullptr; const Pt64 *xyz64 = nullptr; const float4 *xyz32 = nullptr;
+    const double *nrm = nullptr; const Pt64 *nrm64 = nullptr; const float4 *nrm32 = nullptr;
+    const double *intensity = nullptr;
+    int64_t n = 0;
+    double origin[3] = {0.0, 0.0, 0.0};
+};
+// the gradient per point (n x 3 doubles on the device, the points' order) by the Hybrid search (radius, max_nn);
+// max_nn outside [3, kNormalsMaxList]: hipErrorInvalidValue.  Returns with the stream idle.
+hipError_t color_gradient_on_device(const ColorGradientInput &in, double radius, int max_nn, double *d_grad, hipStream_t stream);
+// ... host arrays in and out; h_rgb: n x 3 colours
+hipError_t color_gradient_device(const double *h_xyz, int64_t n, const double *h_nrm, const double *h_rgb, double radius,
+                                 int max_nn, double *h_out, hipStream_t stream);
+constexpr int kColoredRow = 32;                        // doubles per partial row: 31 accumulators (K, sum |d|^2, 21 + 6, the two costs)
+constexpr int kColoredPublished = kNStats + 2;         // granules to the host: 38 statistics, sum r_g^2, sum r_c^2
+struct ColoredArgs : PairPassArgs {
+    const float4 *nrm = nullptr;                       // target normals by original index, and ...
+    const Pt64 *nrm64 = nullptr;                       // ... in f64 where the f64 passes read them
+    const double *grad = nullptr;                      // the target's colour gradient, 3 doubles per point by original index
+    const double *src_int = nullptr, *tgt_int = nullptr;   // intensities: by source position, by original target index
+    double sqrt_lambda = 1.0, sqrt_one_minus_lambda = 0.0;
+    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
+};
+hipError_t launch_colored_reduce(const ColoredArgs &a, hipStream_t stream);
+
 // fill n float4 with +inf (target padding)
 hipError_t launch_fill_inf(float4 *dst, int64_t n, hipStream_t stream);
 // AoS stride-s floats -> float4 (w = 0)

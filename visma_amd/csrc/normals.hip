@@ -21,7 +21,8 @@
 // heap-sorted at the end: any knn / max_nn.  Radius searches (no bound on the list) first COUNT every point's
 // neighbours, then run as a Hybrid search whose max_nn is the largest count: the moments are summed in list order
 // like the reference's (round 2 summed them in scan order: 3e-7 off where two eigenvalues nearly coincide).
-#include "device_common.h"
+// The LDS-resident list, its order and the walk over the cells are nn_list.h's (shared with color_gradient.hip).
+#include "nn_list.h"
 
 #include <math.h>
 
@@ -135,7 +136,9 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
         atomicAdd(a.n27 + 1, 1ull);
         return;
     }
-    int cnt = 0;
+    NnList L;                                                     // (SPILL: the same fields address the heap)
+    L.d2 = ld2; L.id = lid; L.stride = lstride; L.cap = a.cap;
+    int &cnt = L.cnt;
     double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto moments = [&](const double x, const double y, const double z) {
         // EstimateNormals.cpp:95-105
@@ -143,10 +146,7 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
         c[3] += x * x; c[4] += x * y; c[5] += x * z;
         c[6] += y * y; c[7] += y * z; c[8] += z * z;
     };
-    auto less = [&](double d, int id, int j) {
-        const double dj = ld2[(size_t)j * lstride];
-        return d < dj || (d == dj && id < lid[(size_t)j * lstride]);
-    };
+    auto less = [&](double d, int id, int j) { return nn_list_less(L, d, id, j); };
     // (SPILL) max-heap on (d2, index): the root is the entry a nearer candidate replaces
     auto sift_down = [&](int pos, int len, double d, int id) {
         for (;;) {
@@ -162,11 +162,7 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
         lid[(size_t)pos * lstride] = id;
     };
     auto consider = [&](const Pt64 &p) {
-        // flann L2 (dist.h:159-176): result += diff * diff over x, y, z
-        const double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-        double d = dx * dx;
-        d += dy * dy;
-        d += dz * dz;
+        const double d = nn_dist2(q, p);
         if (TYPE != 0 && !(d < a.r2d)) return;
         if (COUNT) { cnt++; return; }
         const int id = (int)p.w;
@@ -190,34 +186,11 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
             }
             return;
         }
-        int pos;
-        if (cnt < a.cap) pos = cnt++;
-        else if (less(d, id, a.cap - 1)) pos = a.cap - 1;
-        else return;
-        while (pos > 0 && less(d, id, pos - 1)) {
-            ld2[(size_t)pos * lstride] = ld2[(size_t)(pos - 1) * lstride];
-            lid[(size_t)pos * lstride] = lid[(size_t)(pos - 1) * lstride];
-            pos--;
-        }
-        ld2[(size_t)pos * lstride] = d;
-        lid[(size_t)pos * lstride] = id;
-    };
-    auto scan_cells = [&](int z, int y, int xa, int xb) {              // cells xa..xb of row (y, z), clipped
-        if (z < 0 || z >= g.dim[2] || y < 0 || y >= g.dim[1]) return;
-        xa = max(xa, 0); xb = min(xb, g.dim[0] - 1);
-        if (xa > xb) return;
-        const long long row = ((long long)z * g.dim[1] + y) * g.dim[0];
-        const unsigned b = a.start[row + xa], e = a.start[row + xb + 1];
-        for (unsigned j = b; j < e; j++) consider(a.sorted64[j]);
+        nn_list_insert(L, d, id);
     };
     const int rmax = TYPE == 0 ? max(max(g.dim[0], g.dim[1]), g.dim[2]) : 1;
     for (int R = 0; R <= rmax; R++) {
-        // the shell of cells at Chebyshev distance R: full x-runs on its y/z faces, two cells elsewhere
-        for (int dz = -R; dz <= R; dz++)
-            for (int dy = -R; dy <= R; dy++) {
-                if (max(abs(dy), abs(dz)) == R) scan_cells(cz + dz, cy + dy, cx - R, cx + R);
-                else { scan_cells(cz + dz, cy + dy, cx - R, cx - R); scan_cells(cz + dz, cy + dy, cx + R, cx + R); }
-            }
+        nn_scan_shell(g, a.start, a.sorted64, cx, cy, cz, R, consider);
         if (TYPE != 0) continue;
         // every point nearer than R cell edges has been seen (0.1 % slack for the fp32 binning)
         if (cnt == a.cap && R >= 1) {
@@ -303,11 +276,10 @@ struct DevBufs {
 template <int TYPE, int MODE, bool SPILL>
 hipError_t launch_normals(const NormalArgs &a, hipStream_t stream)
 {
-    // list bytes per thread: cap * 12 (LDS lists only); keep a workgroup's list within 128 KiB of LDS
-    const size_t per_thread = (MODE != 0 || SPILL) ? 0 : (size_t)a.cap * 12;
-    int nth = 256;
-    while (nth > 64 && per_thread * nth > 60 * 1024) nth >>= 1;      // (64 threads: up to 128 KiB of the 160)
-    const size_t lds = per_thread * nth + 64;
+    // LDS lists only: the workgroup size and the bytes its lists take (nn_list.h)
+    const int lds_cap = (MODE != 0 || SPILL) ? 0 : a.cap;
+    const int nth = nn_list_threads(lds_cap);
+    const size_t lds = nn_list_lds_bytes(lds_cap, nth);
     const unsigned blocks = (unsigned)((a.q_count + nth - 1) / nth);
     if (a.q_count <= 0) return hipSuccess;
 #define VISMA_NRM_LAUNCH(NTH_)                                                                                  \
