@@ -12,3 +12,5 @@
 #include "Geometry/PointCloud.h"
 #include "Registration/TransformationEstimation.h"
 #include "Registration/Registration.h"
+#include "Registration/Feature.h"
+#include "Registration/FastGlobalRegistration.h"

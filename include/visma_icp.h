@@ -866,6 +866,85 @@ VISMA_ICP_API int visma_icp_estimate_normals(visma_icp_ctx *ctx, const double *x
 VISMA_ICP_API int visma_icp_color_gradient(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals,
                                            const double *colors, double radius, int max_nn, double *out_grad);
 
+/* ---- registration without an initial pose: FPFH features, their matching, fast global registration -----------------
+ * Every other registration of this header starts from a pose the caller supplies.  Where there is none: the FPFH of
+ * both clouds, visma_icp_fast_global_registration on them, then any ICP of this header from the pose it returns
+ * (INTEGRATION.md).
+ *
+ * open3d::ComputeFPFHFeature (O3D/Core/Registration/Feature.cpp:38-157) on the GPU: out[i * 33 + j] is the reference's
+ * feature->data_(j, i).  xyz and normals n x 3 f64.  The neighbour lists are those of visma_icp_estimate_normals for
+ *   search_type 0  KDTreeSearchParamKNN(knn)            (a neighbour at a NaN distance is never listed)
+ *               2  KDTreeSearchParamHybrid(radius, knn)  (a radius that is not finite or <= 0: all zeros)
+ * in flann's order, ascending (d2, index); search_type 1, and a list length knn (the point itself counted) outside
+ * [2, 170] -- the lists live in LDS --: VISMA_ICP_ERR_INVALID.  f64 statement by statement: the SPFH pass skips entry 0
+ * of the list whatever index it holds and bins every other pair's three angles with the weight 100 / (len - 1) -- the
+ * zero 4-vector ComputePairFeatures returns for a zero distance or a zero cross product is binned too (bins 5, 16, 27);
+ * a bin argument that is not finite goes to bin 0 --; the FPFH pass runs over the same list, skips entry 0 and entries
+ * at distance 0, sums SPFH / d2 in list order, rescales each histogram to 100 where its sum is not 0 and adds the point's
+ * own SPFH.  A list of length <= 1 leaves the column zero.  A non-finite normal or coordinate reaches sums only. */
+#define VISMA_FPFH_DIM 33
+VISMA_ICP_API int visma_icp_compute_fpfh(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals,
+                                         int search_type, int knn, double radius, double *out /* n x 33, point-major */);
+/* For every row of fb (nb x dim, row-major) the row of fa (na x dim) at the smallest squared distance: nn_of_b[k] in
+ * [0, na), d2_of_b[k] (may be NULL) the distance.  d2 is flann's L2<double> to the bit (flann/algorithms/dist.h:150-177):
+ * f64, plain differences, ascending j, whole groups of four added as result += ((s0 + s1) + s2) + s3, the last dim % 4
+ * one by one.  Exact ties go to the lowest index.  A distance that is NaN or +inf never wins: a row of fb holding a NaN,
+ * or na == 0, gets -1 and +inf, and a NaN row of fa is nobody's answer.  dim outside [1, 64]: VISMA_ICP_ERR_INVALID.  Up
+ * to 2^31 - 1 rows each.  Brute force on the GPU (feature_match.hip). */
+VISMA_ICP_API int visma_icp_match_features(visma_icp_ctx *ctx, const double *fa, int64_t na, const double *fb, int64_t nb,
+                                           int dim, int32_t *nn_of_b /* nb */, double *d2_of_b /* nb, may be NULL */);
+
+/* open3d::FastGlobalRegistration (Zhou, Park, Koltun: "Fast Global Registration", ECCV 2016;
+ * O3D/Core/Registration/FastGlobalRegistration.cpp:42-375).  Clouds ns x 3 / nt x 3 f64, features n x 33 as
+ * visma_icp_compute_fpfh writes them.  In the reference's order:
+ *   normalize   both clouds minus their means, then divided by the larger max norm unless use_absolute_scale (:189-240)
+ *   swap        so that i is the larger cloud (:47-58)
+ *   match       visma_icp_match_features in both directions (:60-83)
+ *   cross check (i, j) with nn(j) == i and nn(i) == j, ascending i (:98-123); n_mutual of them
+ *   tuple test  100 * n_mutual trials at most (:126-174): a trial draws three indices into the cross-checked list, is
+ *               accepted when all three edge ratios lie strictly inside (tuple_scale, 1 / tuple_scale), and pushes its
+ *               three pairs; the loop ends once maximum_tuple_count trials have been accepted.  The reference seeds
+ *               rand() from the clock, so only its mapping can be matched: trial t takes triples[3 t .. 3 t + 2] modulo
+ *               n_mutual when `triples` is given (n_triples trials at most), else words 0..2 of the Philox4x32-10 of
+ *               visma_icp_sample_mesh at counter (t, 0) keyed by `seed`, modulo n_mutual.
+ *   un-swap     pairs are (source index, target index) again
+ *   optimize    OptimizePairwiseRegistration (:242-325): s = (par / (|p - q|^2 + par))^2 per pair, three rows per pair,
+ *               SolveLinearSystem(-JTJ, JTr) with its |det| < 1e-6 guard (zeros), TransformVector6dToMatrix4d,
+ *               trans = delta * trans, par /= division_factor where itr % 4 == 0 && par > max_corr_dist (decrease_mu);
+ *               par starts at scale_global, as the reference passes it.  Fewer than 10 pairs: the identity.
+ *   map back    GetTransformationOriginalScale, then the inverse (:329-342, :373-374)
+ * out_T is source-to-target, row-major, as RegistrationResult holds it.  A context with a rotation axis is not treated
+ * specially: this is the 6-DoF method, there is no 4-DoF variant.  An empty cloud: VISMA_ICP_ERR_INVALID. */
+typedef struct {
+    double division_factor, max_corr_dist, tuple_scale;
+    int use_absolute_scale, decrease_mu, iteration_number, maximum_tuple_count;
+} visma_icp_fgr_option;   /* NULL where one is taken: 1.4, 0.025, 0.95, 0, 1, 64, 1000 (FastGlobalRegistration.h:44-50) */
+typedef struct {
+    int64_t n_mutual;         /* pairs that passed the cross check */
+    int64_t n_tuple_corres;   /* pairs the tuple test pushed (3 per accepted trial): what the optimisation runs on */
+    int64_t n_trials;         /* trials drawn */
+} visma_icp_fgr_info;
+/* Normalize, swap, match, cross check, tuple test, un-swap: the pairs into src_idx / tgt_idx (`capacity` entries each;
+ * 3 * max(1, min(maximum_tuple_count, 100 * min(ns, nt))) always suffice, fewer: VISMA_ICP_ERR_INVALID when they do not),
+ * *n_out of them.  info may be NULL. */
+VISMA_ICP_API int visma_icp_fgr_correspondences(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *src_fpfh,
+                                                const double *tgt_xyz, int64_t nt, const double *tgt_fpfh,
+                                                const visma_icp_fgr_option *opt, uint64_t seed, const int32_t *triples,
+                                                int64_t n_triples, int32_t *src_idx, int32_t *tgt_idx, int64_t capacity,
+                                                int64_t *n_out, visma_icp_fgr_info *info);
+/* Normalize, optimize over the k given pairs, map back (host only, no context): out_T source-to-target; out_T_opt (may be
+ * NULL) what OptimizePairwiseRegistration itself returned, in the normalized frame (it moves the target onto the source).
+ * An index outside its cloud: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_fgr_optimize(const double *src_xyz, int64_t ns, const double *tgt_xyz, int64_t nt,
+                                         const int32_t *src_idx, const int32_t *tgt_idx, int64_t k,
+                                         const visma_icp_fgr_option *opt, double out_T[16], double out_T_opt[16]);
+/* The whole of it: visma_icp_fgr_correspondences, then visma_icp_fgr_optimize on its pairs. */
+VISMA_ICP_API int visma_icp_fast_global_registration(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns,
+                                                     const double *src_fpfh, const double *tgt_xyz, int64_t nt,
+                                                     const double *tgt_fpfh, const visma_icp_fgr_option *opt, uint64_t seed,
+                                                     const int32_t *triples, int64_t n_triples, double out_T[16],
+                                                     visma_icp_fgr_info *info);
+
 /* Point -> triangle-mesh squared distance, face and closest point for np query
  * points: what igl::AABB::squared_distance returns inside feh::MeasureSurfaceError
  * (include/geometry.h:123-136).  face / closest may be NULL; exact ties go to the

@@ -28,6 +28,10 @@
 //                                      colored ICP (O3D/Core/Registration/ColoredICP.h): a photometric row next to
 //                                      the point-to-plane row of every pair; needs the target's normals and the
 //                                      colours of BOTH clouds -- for textured surfaces whose geometry leaves a motion free
+//   open3d::cicp::ComputeFPFHFeature / cicp::FastGlobalRegistration
+//                                      registration WITHOUT an initial pose (O3D/Core/Registration/Feature.h,
+//                                      FastGlobalRegistration.h): FPFH of both clouds, matched, tuple-tested and
+//                                      optimised; its result is the `init` of any RegistrationICP above
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -49,6 +53,9 @@
 #include <string>
 #include <typeinfo>
 #include <vector>
+
+#include <Core/Registration/Feature.h>
+#include <Core/Registration/FastGlobalRegistration.h>
 
 #include "visma_icp.h"
 #include "visma_io.h"
@@ -1018,6 +1025,113 @@ inline bool EstimateNormals(PointCloud &cloud, const KDTreeSearchParam &search_p
     return true;
 }
 
+// open3d::ComputeFPFHFeature (O3D/Core/Registration/Feature.cpp:112-157) on the GPU: column i of data_ is the FPFH of
+// point i.  KNN and Hybrid searches with a list length in [2, 170]; a cloud without normals gives zeros, as the
+// reference does.
+inline std::shared_ptr<Feature> ComputeFPFHFeature(const PointCloud &input, const KDTreeSearchParam &search_param = KDTreeSearchParamKNN())
+{
+    auto feature = std::make_shared<Feature>();
+    const int64_t n = (int64_t)input.points_.size();
+    feature->Resize(VISMA_FPFH_DIM, (int)n);
+    if (n == 0 || !input.HasNormals()) return feature;
+    int type = 0, knn = 0;
+    double radius = 0.0;
+    switch (search_param.GetSearchType()) {
+    case KDTreeSearchParam::SearchType::Knn:
+        knn = static_cast<const KDTreeSearchParamKNN &>(search_param).knn_;
+        break;
+    case KDTreeSearchParam::SearchType::Radius:
+        type = 1;
+        break;
+    case KDTreeSearchParam::SearchType::Hybrid:
+        type = 2;
+        radius = static_cast<const KDTreeSearchParamHybrid &>(search_param).radius_;
+        knn = static_cast<const KDTreeSearchParamHybrid &>(search_param).max_nn_;
+        break;
+    }
+    std::vector<double> rows((size_t)n * VISMA_FPFH_DIM);
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    detail::check(ctx, visma_icp_compute_fpfh(ctx, detail::xyz(input.points_), n, detail::xyz(input.normals_), type, knn, radius,
+                                              rows.data()),
+                  "visma_icp_compute_fpfh");
+    for (int64_t i = 0; i < n; i++)
+        for (int j = 0; j < VISMA_FPFH_DIM; j++) feature->data_(j, i) = rows[(size_t)i * VISMA_FPFH_DIM + j];
+    return feature;
+}
+
+using FastGlobalRegistrationOption = open3d::FastGlobalRegistrationOption;
+
+namespace detail {
+
+inline visma_icp_fgr_option fgr_option(const FastGlobalRegistrationOption &o)
+{
+    visma_icp_fgr_option c;
+    c.division_factor = o.division_factor_; c.max_corr_dist = o.maximum_correspondence_distance_; c.tuple_scale = o.tuple_scale_;
+    c.use_absolute_scale = o.use_absolute_scale_ ? 1 : 0; c.decrease_mu = o.decrease_mu_ ? 1 : 0;
+    c.iteration_number = o.iteration_number_; c.maximum_tuple_count = o.maximum_tuple_count_;
+    return c;
+}
+
+// point-major rows of a Feature (its columns), whatever the storage order of data_
+inline std::vector<double> feature_rows(const Feature &f)
+{
+    const int64_t dim = (int64_t)f.data_.rows(), n = (int64_t)f.data_.cols();
+    std::vector<double> rows((size_t)(dim * n));
+    for (int64_t i = 0; i < n; i++)
+        for (int64_t j = 0; j < dim; j++) rows[(size_t)(i * dim + j)] = f.data_(j, i);
+    return rows;
+}
+
+// fast global registration's optimisation over given pairs (source index, target index), host only
+// (visma_icp_fgr_optimize): the transform source-to-target; opt_out (may be NULL) what OptimizePairwiseRegistration returned
+inline Eigen::Matrix4d fgr_optimize(const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres,
+                                    const FastGlobalRegistrationOption &option, Eigen::Matrix4d *opt_out = nullptr)
+{
+    std::vector<int32_t> si(corres.size()), ti(corres.size());
+    for (size_t c = 0; c < corres.size(); c++) { si[c] = corres[c][0]; ti[c] = corres[c][1]; }
+    const visma_icp_fgr_option o = fgr_option(option);
+    double T[16], Topt[16];
+    if (visma_icp_fgr_optimize(xyz(source.points_), (int64_t)source.points_.size(), xyz(target.points_),
+                               (int64_t)target.points_.size(), si.data(), ti.data(), (int64_t)si.size(), &o, T, Topt) != VISMA_ICP_OK)
+        throw std::runtime_error("visma_icp_fgr_optimize: bad arguments");
+    if (opt_out) *opt_out = from_rowmajor(Topt);
+    return from_rowmajor(T);
+}
+
+}  // namespace detail
+
+// open3d::FastGlobalRegistration (O3D/Core/Registration/FastGlobalRegistration.cpp:347-375): matching on the GPU, the rest
+// on the host.  The reference seeds rand() from the clock; here the tuple test draws from a Philox stream keyed by `seed`
+// (visma_icp.h), 0 for the overload without one: a registration is reproducible.  The result holds the transformation
+// only, as the reference's does.  Features of another dimension than 33, or not one per point: the identity, with a message.
+inline RegistrationResult FastGlobalRegistration(const PointCloud &source, const PointCloud &target, const Feature &source_feature,
+                                                 const Feature &target_feature, const FastGlobalRegistrationOption &option,
+                                                 uint64_t seed)
+{
+    if (source_feature.Dimension() != VISMA_FPFH_DIM || target_feature.Dimension() != VISMA_FPFH_DIM ||
+        source_feature.Num() != source.points_.size() || target_feature.Num() != target.points_.size() ||
+        source.points_.empty() || target.points_.empty()) {
+        std::fprintf(stderr, "Error: FastGlobalRegistration requires one 33-dimensional feature per point of two non-empty clouds.\n");
+        return RegistrationResult(Eigen::Matrix4d::Identity());
+    }
+    const std::vector<double> fs = detail::feature_rows(source_feature), ft = detail::feature_rows(target_feature);
+    const visma_icp_fgr_option o = detail::fgr_option(option);
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    double T[16];
+    detail::check(ctx, visma_icp_fast_global_registration(ctx, detail::xyz(source.points_), (int64_t)source.points_.size(), fs.data(),
+                                                          detail::xyz(target.points_), (int64_t)target.points_.size(), ft.data(), &o,
+                                                          seed, nullptr, 0, T, nullptr),
+                  "visma_icp_fast_global_registration");
+    return RegistrationResult(detail::from_rowmajor(T));
+}
+
+inline RegistrationResult FastGlobalRegistration(const PointCloud &source, const PointCloud &target, const Feature &source_feature,
+                                                 const Feature &target_feature,
+                                                 const FastGlobalRegistrationOption &option = FastGlobalRegistrationOption())
+{
+    return cicp::FastGlobalRegistration(source, target, source_feature, target_feature, option, 0);
+}
+
 // open3d::ComputePointCloudToPointCloudDistance (O3D/Core/Geometry/PointCloud.cpp:122-142) on the GPU: for every
 // source point the distance to the nearest target point, no radius, bit for bit the reference's (0 for every
 // point when the target is empty).
@@ -1329,6 +1443,15 @@ inline RegistrationResult RegistrationColoredICP(const PointCloud &source, const
                                                  double lambda_geometric = 0.968)
 {
     return cicp::RegistrationColoredICP(source, target, max_distance, init, criteria, lambda_geometric);
+}
+inline std::shared_ptr<Feature> ComputeFPFHFeature(const PointCloud &input, const KDTreeSearchParam &search_param)
+{
+    return cicp::ComputeFPFHFeature(input, search_param);
+}
+inline RegistrationResult FastGlobalRegistration(const PointCloud &source, const PointCloud &target, const Feature &source_feature,
+                                                 const Feature &target_feature, const FastGlobalRegistrationOption &option)
+{
+    return cicp::FastGlobalRegistration(source, target, source_feature, target_feature, option);
 }
 inline bool ReadPointCloudFromPLY(const std::string &filename, PointCloud &pointcloud)
 {

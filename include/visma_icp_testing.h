@@ -91,6 +91,16 @@ VISMA_ICP_API int visma_icp_last_mesh_kernel_ms(visma_icp_ctx *ctx, double *quer
  * 2 = BVH.  Both give the same minimum, face and closest point, bit for bit. */
 VISMA_ICP_API int visma_icp_set_mesh_search(visma_icp_ctx *ctx, int method);
 
+/* (measurement) visma_icp_compute_fpfh with the design of its second pass chosen -- second_pass 0: as the product
+ * decides (the first pass's lists kept in global memory where they fit), 1: kept, 2: rebuilt by the second pass; same
+ * values, bit for bit -- and ms[3] = device time of the grid build, the SPFH pass and the FPFH pass; and
+ * visma_icp_match_features with the device time of its kernel.  ms / kernel_ms may be NULL. */
+VISMA_ICP_API int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals,
+                                               int search_type, int knn, double radius, double *out, int second_pass,
+                                               double ms[3]);
+VISMA_ICP_API int visma_icp_match_features_probe(visma_icp_ctx *ctx, const double *fa, int64_t na, const double *fb,
+                                                 int64_t nb, int dim, int32_t *nn_of_b, double *d2_of_b, double *kernel_ms);
+
 /* Device self-test of the SO(3) math the kernels are built on (restatement of
  * core/rodrigues.h:143-226 in visma_amd/csrc/so3.h): for n axis-angle vectors
  * w (3n doubles) computes, ON THE GPU, R = rodrigues(w) (9n) and

@@ -239,6 +239,17 @@ def _bind(L):
         L.visma_icp_run_colored.argtypes = [C.c_void_p, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
                                             C.POINTER(CResult), _ci]
         L.visma_icp_color_gradient.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_double, C.c_int, _dp]
+    if hasattr(L, "visma_icp_fast_global_registration"):  # (A/B runs load older builds through VISMA_ICP_LIB)
+        _fo, _fi = C.POINTER(CFgrOption), C.POINTER(CFgrInfo)
+        L.visma_icp_compute_fpfh.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int, C.c_int, C.c_double, _dp]
+        L.visma_icp_compute_fpfh_probe.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int, C.c_int, C.c_double, _dp, C.c_int, _dp]
+        L.visma_icp_match_features.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _ip, _dp]
+        L.visma_icp_match_features_probe.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _ip, _dp, _dp]
+        L.visma_icp_fgr_correspondences.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _fo, C.c_uint64, _ip,
+                                                    C.c_int64, _ip, _ip, C.c_int64, C.POINTER(C.c_int64), _fi]
+        L.visma_icp_fgr_optimize.argtypes = [_dp, C.c_int64, _dp, C.c_int64, _ip, _ip, C.c_int64, _fo, _dp, _dp]
+        L.visma_icp_fast_global_registration.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _fo, C.c_uint64,
+                                                         _ip, C.c_int64, _dp, _fi]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -357,6 +368,62 @@ class ColoredInfo:
     def __repr__(self):
         return "ColoredInfo(cost=%.6g, geometric_cost=%.6g, photometric_cost=%.6g)" % (
             self.cost, self.geometric_cost, self.photometric_cost)
+
+
+class CFgrOption(C.Structure):
+    """visma_icp_fgr_option (defaults: FastGlobalRegistration.h:44-50)"""
+    _fields_ = [("division_factor", C.c_double), ("max_corr_dist", C.c_double), ("tuple_scale", C.c_double),
+                ("use_absolute_scale", C.c_int), ("decrease_mu", C.c_int), ("iteration_number", C.c_int),
+                ("maximum_tuple_count", C.c_int)]
+
+
+class CFgrInfo(C.Structure):
+    """visma_icp_fgr_info"""
+    _fields_ = [("n_mutual", C.c_int64), ("n_tuple_corres", C.c_int64), ("n_trials", C.c_int64)]
+
+
+FPFH_DIM = 33
+
+
+def fgr_option(division_factor=1.4, max_corr_dist=0.025, tuple_scale=0.95, use_absolute_scale=False, decrease_mu=True,
+               iteration_number=64, maximum_tuple_count=1000):
+    return CFgrOption(float(division_factor), float(max_corr_dist), float(tuple_scale), int(bool(use_absolute_scale)),
+                      int(bool(decrease_mu)), int(iteration_number), int(maximum_tuple_count))
+
+
+class FgrInfo:
+    """What fast global registration's matching did: pairs after the cross check, pairs the tuple test pushed, trials drawn."""
+
+    def __init__(self, c):
+        self.n_mutual = int(c.n_mutual)
+        self.n_tuple_corres = int(c.n_tuple_corres)
+        self.n_trials = int(c.n_trials)
+
+    def __repr__(self):
+        return "FgrInfo(n_mutual=%d, n_tuple_corres=%d, n_trials=%d)" % (self.n_mutual, self.n_tuple_corres, self.n_trials)
+
+
+def _fgr_triples(triples):
+    if triples is None:
+        return None, 0, None
+    t = np.ascontiguousarray(triples, np.int32).reshape(-1, 3)
+    return t, len(t), _p(t, _ip)
+
+
+def fgr_optimize(src, tgt, src_idx, tgt_idx, option=None):
+    """Fast global registration's optimisation over given pairs (host only) -> (T source-to-target, the normalized-frame
+    result of OptimizePairwiseRegistration)."""
+    s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+    si = np.ascontiguousarray(src_idx, np.int32).ravel(); ti = np.ascontiguousarray(tgt_idx, np.int32).ravel()
+    if len(si) != len(ti):
+        raise ValueError("fgr_optimize: one target index per source index")
+    T = np.empty(16); Topt = np.empty(16)
+    o = option if option is not None else fgr_option()
+    rc = load().visma_icp_fgr_optimize(_p(s, _dp), len(s), _p(t, _dp), len(t), _p(si, _ip), _p(ti, _ip), len(si), C.byref(o),
+                                       _p(T, _dp), _p(Topt, _dp))
+    if rc != OK:
+        raise IcpError(rc, "fgr_optimize: bad arguments")
+    return T.reshape(4, 4), Topt.reshape(4, 4)
 
 
 class Result:
@@ -769,6 +836,76 @@ class Context:
         self._chk(self.L.visma_icp_color_gradient(self._h, _p(p, _dp), n, _p(nn, _dp), _p(cc, _dp), float(radius), int(max_nn),
                                                   _p(out, _dp)))
         return out[:n].copy()
+
+    def compute_fpfh(self, xyz, normals, knn=100, radius=None, second_pass=None, timing=None):
+        """open3d::ComputeFPFHFeature on the GPU -> (n, 33), row i the reference's column i.  radius None: KNN(knn); else
+        Hybrid(radius, knn).  second_pass (measurement): 1 keeps the lists of the first pass, 2 rebuilds them; timing: a
+        list that receives [grid ms, SPFH ms, FPFH ms]."""
+        p = _f64(xyz, (-1, 3)); n = len(p)
+        nn = _f64(normals, (-1, 3))
+        if len(nn) != n:
+            raise ValueError("compute_fpfh: one normal per point")
+        out = np.empty((max(n, 1), FPFH_DIM))
+        kind, r = (0, 0.0) if radius is None else (2, float(radius))
+        if second_pass is None and timing is None:
+            self._chk(self.L.visma_icp_compute_fpfh(self._h, _p(p, _dp), n, _p(nn, _dp), kind, int(knn), r, _p(out, _dp)))
+        else:
+            ms = np.zeros(3)
+            self._chk(self.L.visma_icp_compute_fpfh_probe(self._h, _p(p, _dp), n, _p(nn, _dp), kind, int(knn), r, _p(out, _dp),
+                                                          int(second_pass or 0), _p(ms, _dp)))
+            if timing is not None:
+                timing[:] = list(ms)
+        return out[:n].copy()
+
+    def match_features(self, fa, fb, timing=None):
+        """For every row of fb the row of fa at the smallest squared distance (flann's L2, lowest index on ties)
+        -> (indices (nb,) int32, -1 where none; d2 (nb,))."""
+        b = _f64(fb); b = b.reshape(len(b), -1) if b.ndim != 2 else b
+        a = _f64(fa); a = a.reshape(len(a), -1) if a.ndim != 2 else a
+        dim = b.shape[1] if len(b) else a.shape[1]
+        if len(a) and len(b) and a.shape[1] != b.shape[1]:
+            raise ValueError("match_features: both sets need the same dimension")
+        nn = np.empty(max(len(b), 1), np.int32); d2 = np.empty(max(len(b), 1))
+        ms = C.c_double(0.0)
+        self._chk(self.L.visma_icp_match_features_probe(self._h, _p(a, _dp), len(a), _p(b, _dp), len(b), int(dim), _p(nn, _ip),
+                                                        _p(d2, _dp), C.byref(ms)))
+        if timing is not None:
+            timing[:] = [ms.value]
+        return nn[:len(b)].copy(), d2[:len(b)].copy()
+
+    def fgr_correspondences(self, src, src_fpfh, tgt, tgt_fpfh, option=None, seed=0, triples=None):
+        """Fast global registration up to its tuple test -> ((k, 2) int32 pairs (source, target), FgrInfo)."""
+        s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+        fs = _f64(src_fpfh, (-1, FPFH_DIM)); ft = _f64(tgt_fpfh, (-1, FPFH_DIM))
+        if len(fs) != len(s) or len(ft) != len(t):
+            raise ValueError("fgr_correspondences: one feature row per point")
+        o = option if option is not None else fgr_option()
+        tr, ntr, trp = _fgr_triples(triples)
+        cap = 3 * max(1, min(int(o.maximum_tuple_count), 100 * min(len(s), len(t))))
+        si = np.empty(cap, np.int32); ti = np.empty(cap, np.int32)
+        k = C.c_int64(0); info = CFgrInfo()
+        self._chk(self.L.visma_icp_fgr_correspondences(self._h, _p(s, _dp), len(s), _p(fs, _dp), _p(t, _dp), len(t), _p(ft, _dp),
+                                                       C.byref(o), int(seed), trp, ntr, _p(si, _ip), _p(ti, _ip), cap,
+                                                       C.byref(k), C.byref(info)))
+        return np.stack([si[:k.value], ti[:k.value]], 1), FgrInfo(info)
+
+    def fgr_optimize(self, src, tgt, src_idx, tgt_idx, option=None):
+        """The module's fgr_optimize (host only; here for symmetry with the C++ names)."""
+        return fgr_optimize(src, tgt, src_idx, tgt_idx, option)
+
+    def fast_global_registration(self, src, src_fpfh, tgt, tgt_fpfh, option=None, seed=0, triples=None):
+        """open3d::FastGlobalRegistration -> (T source-to-target (4, 4), FgrInfo)."""
+        s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+        fs = _f64(src_fpfh, (-1, FPFH_DIM)); ft = _f64(tgt_fpfh, (-1, FPFH_DIM))
+        if len(fs) != len(s) or len(ft) != len(t):
+            raise ValueError("fast_global_registration: one feature row per point")
+        o = option if option is not None else fgr_option()
+        tr, ntr, trp = _fgr_triples(triples)
+        T = np.empty(16); info = CFgrInfo()
+        self._chk(self.L.visma_icp_fast_global_registration(self._h, _p(s, _dp), len(s), _p(fs, _dp), _p(t, _dp), len(t),
+                                                            _p(ft, _dp), C.byref(o), int(seed), trp, ntr, _p(T, _dp),
+                                                            C.byref(info)))
+        return T.reshape(4, 4), FgrInfo(info)
 
     def voxel_down_sample(self, xyz, voxel_size, normals=None, colors=None):
         """open3d::VoxelDownSample on the GPU -> (points, normals, colors), voxels in ascending index order."""

@@ -55,6 +55,152 @@ int visma_icp_color_gradient(visma_icp_ctx *ctx, const double *xyz, int64_t n, c
     return VISMA_ICP_OK;
 }
 
+// ---- FPFH, feature matching, fast global registration ----
+
+int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type,
+                                 int knn, double radius, double *out, int second_pass, double ms[3])
+{
+    CTX_CHECK();
+    if (n < 0 || (n > 0 && (!xyz || !normals || !out)) || second_pass < 0 || second_pass > 2)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad compute_fpfh arguments");
+    if (search_type != 0 && search_type != 2)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "compute_fpfh: search_type must be 0 (KNN) or 2 (Hybrid)");
+    if (knn < 2 || knn > kNormalsMaxList) return ctx->fail(VISMA_ICP_ERR_INVALID, "compute_fpfh: knn must lie in [2, 170]");
+    if (n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "compute_fpfh needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    hipError_t e = compute_fpfh_device(xyz, n, normals, search_type, knn, radius, out, second_pass, ms, ctx->eng->aux_stream());
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("compute_fpfh: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_compute_fpfh(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type, int knn,
+                           double radius, double *out)
+{
+    return visma_icp_compute_fpfh_probe(ctx, xyz, n, normals, search_type, knn, radius, out, 0, nullptr);
+}
+
+int visma_icp_match_features_probe(visma_icp_ctx *ctx, const double *fa, int64_t na, const double *fb, int64_t nb, int dim,
+                                   int32_t *nn_of_b, double *d2_of_b, double *kernel_ms)
+{
+    CTX_CHECK();
+    if (dim < 1 || dim > 64) return ctx->fail(VISMA_ICP_ERR_INVALID, "match_features: dim must lie in [1, 64]");
+    if (na < 0 || nb < 0 || (na > 0 && !fa) || (nb > 0 && (!fb || !nn_of_b)))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad match_features arguments");
+    if (na > 0x7fffffff || nb > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many rows for 32-bit indices");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (nb == 0) return VISMA_ICP_OK;
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "match_features needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    hipError_t e = match_features_device(fa, na, fb, nb, dim, nn_of_b, d2_of_b, kernel_ms, ctx->eng->aux_stream());
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("match_features: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_match_features(visma_icp_ctx *ctx, const double *fa, int64_t na, const double *fb, int64_t nb, int dim,
+                             int32_t *nn_of_b, double *d2_of_b)
+{
+    return visma_icp_match_features_probe(ctx, fa, na, fb, nb, dim, nn_of_b, d2_of_b, nullptr);
+}
+
+static FgrOption fgr_option_of(const visma_icp_fgr_option *opt)
+{
+    FgrOption o;
+    if (opt) {
+        o.division_factor = opt->division_factor; o.max_corr_dist = opt->max_corr_dist; o.tuple_scale = opt->tuple_scale;
+        o.use_absolute_scale = opt->use_absolute_scale; o.decrease_mu = opt->decrease_mu;
+        o.iteration_number = opt->iteration_number; o.maximum_tuple_count = opt->maximum_tuple_count;
+    }
+    return o;
+}
+
+// steps 0-3 of AdvancedMatching on the normalized clouds; pairs (source index, target index)
+static int fgr_correspondences_impl(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *src_fpfh,
+                                    const double *tgt_xyz, int64_t nt, const double *tgt_fpfh, const FgrOption &o, uint64_t seed,
+                                    const int32_t *triples, int64_t n_triples, std::vector<int32_t> &oi, std::vector<int32_t> &oj,
+                                    visma_icp_fgr_info *info)
+{
+    const FgrNormalized N = fgr_normalize(src_xyz, ns, tgt_xyz, nt, o.use_absolute_scale != 0);
+    const bool swapped = nt > ns;                                 // i is the larger cloud (:51-58)
+    const int fi = swapped ? 1 : 0, fj = swapped ? 0 : 1;
+    const double *feat[2] = {src_fpfh, tgt_fpfh};
+    const int64_t cnt[2] = {ns, nt};
+    std::vector<int32_t> nn_i_of_j((size_t)cnt[fj]), nn_j_of_i((size_t)cnt[fi]);
+    if (int rc = visma_icp_match_features(ctx, feat[fi], cnt[fi], feat[fj], cnt[fj], VISMA_FPFH_DIM, nn_i_of_j.data(), nullptr)) return rc;
+    if (int rc = visma_icp_match_features(ctx, feat[fj], cnt[fj], feat[fi], cnt[fi], VISMA_FPFH_DIM, nn_j_of_i.data(), nullptr)) return rc;
+    std::vector<int32_t> ci, cj, ti, tj;
+    fgr_cross_check(nn_i_of_j.data(), cnt[fj], nn_j_of_i.data(), cnt[fi], ci, cj);
+    const int64_t trials = fgr_tuple_test(N.xyz[fi].data(), N.xyz[fj].data(), ci, cj, o.tuple_scale, o.maximum_tuple_count, seed,
+                                          triples, n_triples, ti, tj);
+    if (swapped) ti.swap(tj);
+    oi.swap(ti); oj.swap(tj);
+    if (info) {
+        info->n_mutual = (int64_t)ci.size();
+        info->n_tuple_corres = (int64_t)oi.size();
+        info->n_trials = trials;
+    }
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_fgr_correspondences(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *src_fpfh,
+                                  const double *tgt_xyz, int64_t nt, const double *tgt_fpfh, const visma_icp_fgr_option *opt,
+                                  uint64_t seed, const int32_t *triples, int64_t n_triples, int32_t *src_idx, int32_t *tgt_idx,
+                                  int64_t capacity, int64_t *n_out, visma_icp_fgr_info *info)
+{
+    CTX_CHECK();
+    if (ns <= 0 || nt <= 0 || !src_xyz || !tgt_xyz || !src_fpfh || !tgt_fpfh || !n_out || capacity < 0 ||
+        (capacity > 0 && (!src_idx || !tgt_idx)) || n_triples < 0 || (n_triples > 0 && !triples))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad fgr_correspondences arguments");
+    if (ns > 0x7fffffff || nt > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    std::vector<int32_t> oi, oj;
+    if (int rc = fgr_correspondences_impl(ctx, src_xyz, ns, src_fpfh, tgt_xyz, nt, tgt_fpfh, fgr_option_of(opt), seed,
+                                          n_triples > 0 ? triples : nullptr, n_triples, oi, oj, info))
+        return rc;
+    if ((int64_t)oi.size() > capacity) return ctx->fail(VISMA_ICP_ERR_INVALID, "fgr_correspondences: the index buffers are too small");
+    std::copy(oi.begin(), oi.end(), src_idx);
+    std::copy(oj.begin(), oj.end(), tgt_idx);
+    *n_out = (int64_t)oi.size();
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_fgr_optimize(const double *src_xyz, int64_t ns, const double *tgt_xyz, int64_t nt, const int32_t *src_idx,
+                           const int32_t *tgt_idx, int64_t k, const visma_icp_fgr_option *opt, double out_T[16],
+                           double out_T_opt[16])
+{
+    if (ns <= 0 || nt <= 0 || !src_xyz || !tgt_xyz || k < 0 || (k > 0 && (!src_idx || !tgt_idx)) || !out_T)
+        return VISMA_ICP_ERR_INVALID;
+    for (int64_t c = 0; c < k; c++)
+        if (src_idx[c] < 0 || src_idx[c] >= ns || tgt_idx[c] < 0 || tgt_idx[c] >= nt) return VISMA_ICP_ERR_INVALID;
+    const FgrOption o = fgr_option_of(opt);
+    const FgrNormalized N = fgr_normalize(src_xyz, ns, tgt_xyz, nt, o.use_absolute_scale != 0);
+    const Mat4 t = fgr_optimize(N.xyz[0].data(), N.xyz[1].data(), src_idx, tgt_idx, k, o, N.scale_global);
+    const Mat4 T = fgr_map_back(t, N);
+    memcpy(out_T, T.m, sizeof(T.m));
+    if (out_T_opt) memcpy(out_T_opt, t.m, sizeof(t.m));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_fast_global_registration(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *src_fpfh,
+                                       const double *tgt_xyz, int64_t nt, const double *tgt_fpfh, const visma_icp_fgr_option *opt,
+                                       uint64_t seed, const int32_t *triples, int64_t n_triples, double out_T[16],
+                                       visma_icp_fgr_info *info)
+{
+    CTX_CHECK();
+    if (ns <= 0 || nt <= 0 || !src_xyz || !tgt_xyz || !src_fpfh || !tgt_fpfh || !out_T || n_triples < 0 ||
+        (n_triples > 0 && !triples))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "bad fast_global_registration arguments");
+    if (ns > 0x7fffffff || nt > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    std::vector<int32_t> oi, oj;
+    if (int rc = fgr_correspondences_impl(ctx, src_xyz, ns, src_fpfh, tgt_xyz, nt, tgt_fpfh, fgr_option_of(opt), seed,
+                                          n_triples > 0 ? triples : nullptr, n_triples, oi, oj, info))
+        return rc;
+    if (visma_icp_fgr_optimize(src_xyz, ns, tgt_xyz, nt, oi.data(), oj.data(), (int64_t)oi.size(), opt, out_T, nullptr))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "fast_global_registration: optimize rejected its pairs");
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_point_mesh_distance(visma_icp_ctx *ctx, const double *P, int64_t np, const double *V,
                                   int64_t nv, const int32_t *F, int64_t nf, double *d2, int32_t *face,
                                   double *closest)

@@ -14,7 +14,10 @@
 #pragma once
 
 #include <math.h>
+#include <stdint.h>
 #include <string.h>
+
+#include <vector>
 
 #include "so3.h"
 
@@ -539,6 +542,189 @@ inline bool normalise_axis(const double in[3], double out[3])
     const double n = sqrt(n2);
     for (int i = 0; i < 3; i++) out[i] = in[i] / n;
     return true;
+}
+
+// ---- fast global registration (Zhou, Park, Koltun, ECCV 2016; O3D/Core/Registration/FastGlobalRegistration.cpp) -----------
+// Host only: everything after the feature matching works on a few thousand correspondences.  DESIGN.md 4.4c7.
+
+struct FgrOption {                                     // FastGlobalRegistration.h:44-50
+    double division_factor = 1.4, max_corr_dist = 0.025, tuple_scale = 0.95;
+    int use_absolute_scale = 0, decrease_mu = 1, iteration_number = 64, maximum_tuple_count = 1000;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11), the generator of mesh.hip's sampling kernel, on the host
+inline void philox4x32_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
+{
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+inline double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
+
+// NormalizePointCloud (:189-240) on copies: cloud k minus its mean, both divided by scale_global
+struct FgrNormalized {
+    std::vector<double> xyz[2];
+    double mean[2][3];
+    double scale_global, scale_start;
+};
+
+inline FgrNormalized fgr_normalize(const double *c0, int64_t n0, const double *c1, int64_t n1, bool use_absolute_scale)
+{
+    FgrNormalized N;
+    const double *in[2] = {c0, c1};
+    const int64_t cnt[2] = {n0, n1};
+    double scale = 0.0;
+    for (int k = 0; k < 2; k++) {
+        double m[3] = {0.0, 0.0, 0.0}, max_scale = 0.0;
+        for (int64_t i = 0; i < cnt[k]; i++)
+            for (int a = 0; a < 3; a++) m[a] = m[a] + in[k][3 * i + a];
+        for (int a = 0; a < 3; a++) N.mean[k][a] = m[a] = m[a] / (double)(int)cnt[k];
+        N.xyz[k].resize((size_t)(3 * cnt[k]));
+        for (int64_t i = 0; i < cnt[k]; i++) {
+            double *p = &N.xyz[k][(size_t)(3 * i)];
+            for (int a = 0; a < 3; a++) p[a] = in[k][3 * i + a] - m[a];
+            const double len = norm3(p[0], p[1], p[2]);
+            if (len > max_scale) max_scale = len;
+        }
+        if (max_scale > scale) scale = max_scale;
+    }
+    N.scale_global = use_absolute_scale ? 1.0 : scale;
+    N.scale_start = use_absolute_scale ? scale : 1.0;
+    for (int k = 0; k < 2; k++)
+        for (double &v : N.xyz[k]) v /= N.scale_global;
+    return N;
+}
+
+// STEP 2 of AdvancedMatching (:98-123) from both full nearest-neighbour maps: (i, j) with nn_i_of_j[j] == i and
+// nn_j_of_i[i] == j, ascending i.  (The reference asks for nn_j_of_i only where some j hits i; a kept pair's i is hit by its
+// own j, so the full map gives the same list.)
+inline void fgr_cross_check(const int32_t *nn_i_of_j, int64_t nj, const int32_t *nn_j_of_i, int64_t ni, std::vector<int32_t> &ci,
+                            std::vector<int32_t> &cj)
+{
+    ci.clear(); cj.clear();
+    for (int64_t i = 0; i < ni; i++) {
+        const int32_t j = nn_j_of_i[i];
+        if (j < 0 || j >= nj || nn_i_of_j[j] != (int32_t)i) continue;
+        ci.push_back((int32_t)i);
+        cj.push_back(j);
+    }
+}
+
+// STEP 3 (:126-174): trial t draws three indices into the cross-checked list -- from `triples` (3 per trial, taken modulo
+// ncorr) or words 0..2 of Philox4x32-10 at counter (t, 0), key `seed`, modulo ncorr --; all three edge ratios strictly
+// inside (scale, 1 / scale) pushes the three pairs.  Returns the trials drawn.
+inline int64_t fgr_tuple_test(const double *pi, const double *pj, const std::vector<int32_t> &ci, const std::vector<int32_t> &cj,
+                              double scale, int maximum_tuple_count, uint64_t seed, const int32_t *triples, int64_t n_triples,
+                              std::vector<int32_t> &oi, std::vector<int32_t> &oj)
+{
+    oi.clear(); oj.clear();
+    const int64_t ncorr = (int64_t)ci.size();
+    int64_t trials = ncorr * 100;
+    if (triples) trials = n_triples < trials ? n_triples : trials;
+    int64_t cnt = 0, t = 0;
+    for (; t < trials; t++) {
+        int64_t r[3];
+        if (triples) {
+            for (int k = 0; k < 3; k++) r[k] = (((int64_t)triples[3 * t + k] % ncorr) + ncorr) % ncorr;
+        } else {
+            uint32_t w[4];
+            philox4x32_host((uint32_t)t, (uint32_t)((uint64_t)t >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+            for (int k = 0; k < 3; k++) r[k] = (int64_t)(w[k] % (uint64_t)ncorr);
+        }
+        double li[3], lj[3];
+        for (int k = 0; k < 3; k++) {
+            const double *a = pi + 3 * (int64_t)ci[(size_t)r[k]], *b = pi + 3 * (int64_t)ci[(size_t)r[(k + 1) % 3]];
+            li[k] = norm3(a[0] - b[0], a[1] - b[1], a[2] - b[2]);
+            const double *c = pj + 3 * (int64_t)cj[(size_t)r[k]], *d = pj + 3 * (int64_t)cj[(size_t)r[(k + 1) % 3]];
+            lj[k] = norm3(c[0] - d[0], c[1] - d[1], c[2] - d[2]);
+        }
+        if ((li[0] * scale < lj[0]) && (lj[0] < li[0] / scale) && (li[1] * scale < lj[1]) && (lj[1] < li[1] / scale) &&
+            (li[2] * scale < lj[2]) && (lj[2] < li[2] / scale)) {
+            for (int k = 0; k < 3; k++) { oi.push_back(ci[(size_t)r[k]]); oj.push_back(cj[(size_t)r[k]]); }
+            cnt++;
+        }
+        if (cnt >= maximum_tuple_count) { t++; break; }
+    }
+    return t;
+}
+
+// OptimizePairwiseRegistration (:242-325): the graduated Geman-McClure Gauss-Newton loop over pairs (i0[c], i1[c]) of the
+// clouds p0, p1; returns trans with trans * p1 ~ p0.  Fewer than 10 pairs: the identity.
+inline Mat4 fgr_optimize(const double *p0, const double *p1, const int32_t *i0, const int32_t *i1, int64_t K, const FgrOption &o,
+                         double par)
+{
+    Mat4 trans = Mat4::identity();
+    if (K < 10) return trans;
+    std::vector<double> q((size_t)(3 * K));                   // the moved copies of p1's points, per pair
+    for (int64_t c = 0; c < K; c++)
+        for (int a = 0; a < 3; a++) q[(size_t)(3 * c + a)] = p1[3 * (int64_t)i1[c] + a];
+    for (int itr = 0; itr < o.iteration_number; itr++) {
+        double JTJ[36], JTr[6];
+        for (double &v : JTJ) v = 0.0;
+        for (double &v : JTr) v = 0.0;
+        for (int64_t c = 0; c < K; c++) {
+            const double *p = p0 + 3 * (int64_t)i0[c], *qq = &q[(size_t)(3 * c)];
+            const double rpq[3] = {p[0] - qq[0], p[1] - qq[1], p[2] - qq[2]};
+            const double temp = par / ((rpq[0] * rpq[0] + rpq[1] * rpq[1] + rpq[2] * rpq[2]) + par);
+            const double s = temp * temp;
+            // the three rows (:282-307): J and its three non-zero entries
+            const int idx[3][3] = {{1, 2, 3}, {2, 0, 4}, {0, 1, 5}};
+            const double val[3][3] = {{-qq[2], qq[1], -1.0}, {-qq[0], qq[2], -1.0}, {-qq[1], qq[0], -1.0}};
+            for (int row = 0; row < 3; row++) {
+                const double r = rpq[row];
+                for (int a = 0; a < 3; a++) {
+                    for (int b = 0; b < 3; b++) JTJ[idx[row][a] * 6 + idx[row][b]] += val[row][a] * val[row][b] * s;
+                    JTr[idx[row][a]] += val[row][a] * r * s;
+                }
+            }
+        }
+        // SolveLinearSystem(-JTJ, JTr) (Eigen.cpp:35-56): zeros where the determinant guard rejects
+        double A[36], x[6];
+        for (int k = 0; k < 36; k++) A[k] = -JTJ[k];
+        const double det = solve6(A, JTr, x);
+        if (fabs(det) < 1e-6 || isnan(det) || isinf(det))
+            for (double &v : x) v = 0.0;
+        const Mat4 delta = euler_zyx_to_mat4(x);
+        trans = delta * trans;
+        for (int64_t c = 0; c < K; c++) {                      // PointCloud::Transform(delta)
+            double *qq = &q[(size_t)(3 * c)];
+            double n[3];
+            for (int a = 0; a < 3; a++) n[a] = delta(a, 0) * qq[0] + delta(a, 1) * qq[1] + delta(a, 2) * qq[2] + delta(a, 3) * 1.0;
+            qq[0] = n[0]; qq[1] = n[1]; qq[2] = n[2];
+        }
+        if (o.decrease_mu && itr % 4 == 0 && par > o.max_corr_dist) par /= o.division_factor;
+    }
+    return trans;
+}
+
+// GetTransformationOriginalScale(...).inverse() (:329-342, :373-374): source to target in the callers' frame
+inline Mat4 fgr_map_back(const Mat4 &t, const FgrNormalized &N)
+{
+    double R[9], tt[3];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) R[i * 3 + j] = t(i, j);
+        tt[i] = (-t(i, 0) * N.mean[1][0] + -t(i, 1) * N.mean[1][1] + -t(i, 2) * N.mean[1][2]) + t(i, 3) * N.scale_global + N.mean[0][i];
+    }
+    // the inverse of [R tt; 0 1] for a general R: adjugate over determinant
+    const double det = det3(R);
+    double Ri[9];
+    Ri[0] = (R[4] * R[8] - R[5] * R[7]) / det; Ri[1] = (R[2] * R[7] - R[1] * R[8]) / det; Ri[2] = (R[1] * R[5] - R[2] * R[4]) / det;
+    Ri[3] = (R[5] * R[6] - R[3] * R[8]) / det; Ri[4] = (R[0] * R[8] - R[2] * R[6]) / det; Ri[5] = (R[2] * R[3] - R[0] * R[5]) / det;
+    Ri[6] = (R[3] * R[7] - R[4] * R[6]) / det; Ri[7] = (R[1] * R[6] - R[0] * R[7]) / det; Ri[8] = (R[0] * R[4] - R[1] * R[3]) / det;
+    Mat4 out = Mat4::identity();
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) out(i, j) = Ri[i * 3 + j];
+        out(i, 3) = -(Ri[i * 3] * tt[0] + Ri[i * 3 + 1] * tt[1] + Ri[i * 3 + 2] * tt[2]);
+    }
+    return out;
 }
 
 }  // namespace visma

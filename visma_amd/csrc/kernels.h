@@ -601,7 +601,17 @@ hipError_t color_gradient_on_device(const ColorGradientInput &in, double radius,
 // ... host arrays in and out; h_rgb: n x 3 colours
 hipError_t color_gradient_device(const double *h_xyz, int64_t n, const double *h_nrm, const double *h_rgb, double radius,
                                  int max_nn, double *h_out, hipStream_t stream);
-constexpr int kColoredRow = 32;                        // doubles per partial row: 31 accumulators (K, sum |d|^2, 21 + 6, the two costs)
+// ---- FPFH features and their matching (fpfh.hip, feature_match.hip): host arrays in, host arrays out ----
+// open3d::ComputeFPFHFeature: n x 33 doubles, point-major; search_type 0 KNN(knn) | 2 Hybrid(radius, max_nn = knn), knn in
+// [2, kNormalsMaxList], else hipErrorInvalidValue.  second_pass 0: the first pass's lists kept in global memory where they
+// fit, 1: kept, 2: rebuilt by the second pass.  ms (may be NULL): device time of the grid build and of the two passes.
+hipError_t compute_fpfh_device(const double *h_xyz, int64_t n, const double *h_nrm, int search_type, int knn, double radius,
+                               double *h_out, int second_pass, double ms[3], hipStream_t stream);
+// for every row of fb (nb x dim) the row of fa (na x dim) at the smallest flann-L2 distance, lowest index on ties, -1 and
+// +inf where no distance is finite; dim in [1, 64].  h_d2 and kernel_ms may be NULL.
+hipError_t match_features_device(const double *h_fa, int64_t na, const double *h_fb, int64_t nb, int dim, int32_t *h_nn,
+                                 double *h_d2, double *kernel_ms, hipStream_t stream);
+constexpr int kColoredRow = 32;                       // doubles per partial row: 31 accumulators (K, sum |d|^2, 21 + 6, the two costs)
 constexpr int kColoredPublished = kNStats + 2;         // granules to the host: 38 statistics, sum r_g^2, sum r_c^2
 struct ColoredArgs : PairPassArgs {
     const float4 *nrm = nullptr;                       // target normals by original index, and ...
