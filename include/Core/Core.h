@@ -14,3 +14,4 @@
 #include "Registration/Registration.h"
 #include "Registration/Feature.h"
 #include "Registration/FastGlobalRegistration.h"
+#include "Registration/CorrespondenceChecker.h"

@@ -1,10 +1,12 @@
 // Core/Registration/Registration.h -- criteria / result types and the
-// RegistrationICP entry point of the path (shape of
-// O3D/Core/Registration/Registration.h:46-107).  In this stand-alone header set
+// RegistrationICP / RegistrationRANSAC... entry points of the path (shape of
+// O3D/Core/Registration/Registration.h:46-129).  In this stand-alone header set
 // open3d::RegistrationICP forwards to the MI355X driver
 // open3d::cicp::RegistrationICP (visma_icp_open3d.hpp).
 #pragma once
 #include <Eigen/Core>
+#include <functional>
+#include <vector>
 
 #include "TransformationEstimation.h"
 
@@ -20,6 +22,18 @@ public:
     double relative_rmse_;
     int max_iteration_;
 };
+
+// RANSAC stops after max_iteration_ trials or once max_validation_ of them have been validated (Registration.h:61-78)
+class RANSACConvergenceCriteria {
+public:
+    RANSACConvergenceCriteria(int max_iteration = 1000, int max_validation = 1000)
+        : max_iteration_(max_iteration), max_validation_(max_validation) {}
+    int max_iteration_;
+    int max_validation_;
+};
+
+class CorrespondenceChecker;
+class Feature;
 
 class RegistrationResult {
 public:
@@ -40,5 +54,16 @@ inline RegistrationResult RegistrationICP(
     const Eigen::Matrix4d &init = Eigen::Matrix4d::Identity(),
     const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false),
     const ICPConvergenceCriteria &criteria = ICPConvergenceCriteria());
+
+inline RegistrationResult RegistrationRANSACBasedOnCorrespondence(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres, double max_correspondence_distance,
+    const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false), int ransac_n = 6,
+    const RANSACConvergenceCriteria &criteria = RANSACConvergenceCriteria());
+
+inline RegistrationResult RegistrationRANSACBasedOnFeatureMatching(
+    const PointCloud &source, const PointCloud &target, const Feature &source_feature, const Feature &target_feature,
+    double max_correspondence_distance, const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false),
+    int ransac_n = 4, const std::vector<std::reference_wrapper<const CorrespondenceChecker>> &checkers = {},
+    const RANSACConvergenceCriteria &criteria = RANSACConvergenceCriteria());
 
 }  // namespace open3d

@@ -945,6 +945,98 @@ VISMA_ICP_API int visma_icp_fast_global_registration(visma_icp_ctx *ctx, const d
                                                      const int32_t *triples, int64_t n_triples, double out_T[16],
                                                      visma_icp_fgr_info *info);
 
+/* ---- RANSAC global registration: the second method without an initial pose -----------------------------------------
+ * open3d::RegistrationRANSACBasedOnFeatureMatching and ...BasedOnCorrespondence (O3D/Core/Registration/Registration.h:61-78,
+ * 109-129; Registration.cpp:98-123, 188-353) with the three CorrespondenceCheckers (CorrespondenceChecker.cpp:35-89) and
+ * RANSACConvergenceCriteria.  The trial loop runs on the GPU, one lane per trial (ransac.hip); the validation of the
+ * trials that pass is EvaluateRegistration at many poses: visma_icp_run_batch with zero iterations.  The reference seeds
+ * rand() from the clock and lets OpenMP threads race for total_validation; here the result is a function of the inputs and
+ * `seed` (or `draws`).  Feature matching, as a serial loop:
+ *   pair table  nn[i] = the target feature nearest to source feature i: ONE visma_icp_match_features(tgt_feat, src_feat)
+ *               (num_similar_features == 1, :244): exact, ties to the lowest index, -1 for a NaN row
+ *   trials      t = 0, 1, ... in order.  Trial t takes the ransac_n source indices draws[t * ransac_n + j] mod ns when
+ *               `draws` is given (n_draw_trials trials at most), else word j mod 4 of the Philox4x32-10 of
+ *               visma_icp_sample_mesh at counter (t, j / 4) keyed by `seed`, modulo ns (:273-293).  Duplicates are allowed,
+ *               as in the reference.  ransac_n lies in [3, 8]: outside, VISMA_ICP_ERR_INVALID (:237 returns for < 3).
+ *   no partner  a trial that draws a row with nn == -1 is rejected before alignment
+ *   edge        (before alignment, every i < j, :35-53)  rejected when dis_source < dis_target * s || dis_target <
+ *               dis_source * s, both plain norms
+ *   solve       TransformationEstimationPointToPoint(false): Eigen::umeyama without scaling on the ransac_n pairs
+ *   distance    (:55-68)  rejected when |target - T source| > distance_threshold for a pair
+ *   normal      (:70-89)  rejected when target normal . (R source normal) < cos(normal_angle) for a pair; skipped when
+ *               either cloud has no normals.  Every comparison is the reference's: one with a NaN is false and rejects
+ *               nothing.  A trial that draws a point that is not finite solves R = I, t = NaN, as Eigen::umeyama does.
+ *   validate    every trial that passes: EvaluateRegistration(source, target, max_dist, T) (:127-139)
+ *   stop        after max_iteration trials, or once max_validation trials have been validated: the validated trials are the
+ *               FIRST max_validation passing trials in trial order, whatever the launch geometry (max_validation <= 0:
+ *               none -- the reference's racing counter would still validate one)
+ *   best        strictly greater fitness, or equal fitness and strictly smaller rmse (:321-325); a full tie stays with the
+ *               lowest trial.  No validated trial, or none with a correspondence: the reference's empty result (identity,
+ *               fitness 0, rmse 0).
+ * Then the context holds the pair (as after visma_icp_set_clouds_f64) and one ordinary pass at the best T: fitness, rmse and
+ * count are those of visma_icp_run(init = T, max_iter = 0), and visma_icp_get_correspondences serves correspondence_set_.
+ * A source point that is not finite takes part in the trials as it is and is never anybody's correspondence; a passing
+ * trial whose T is not finite is validated to zero correspondences without a search.
+ * Correspondences (:188-224): min(max_iteration, max_validation) trials (n_draw_trials at most); trial t draws ransac_n
+ * entries of the K given pairs (same two draw sources, modulo K), solves, and scores the WHOLE list (:98-123): dis2 <
+ * max_dist^2 strictly, fitness = good / K, rmse = sqrt(error2 / good); best as above; no checkers.  The result carries those
+ * numbers (num_correspondences = good); the context's clouds are not touched.
+ * Only the point-to-point estimator without scaling.  A context's rotation axis is not honoured: 6 degrees of freedom, as
+ * visma_icp_fast_global_registration. */
+typedef struct {
+    int ransac_n;                    /* pairs per trial, [3, 8] */
+    int max_iteration;               /* RANSACConvergenceCriteria::max_iteration_ */
+    int max_validation;              /* ...::max_validation_ */
+    double edge_length_similarity;   /* CorrespondenceCheckerBasedOnEdgeLength; <= 0 (or NaN): checker off */
+    double distance_threshold;       /* CorrespondenceCheckerBasedOnDistance; <= 0: off */
+    double normal_angle;             /* CorrespondenceCheckerBasedOnNormal, radians; <= 0: off */
+    int chunk_trials;                /* trials per launch; 0: the library's choice.  Never changes a result. */
+} visma_icp_ransac_option;           /* NULL where one is taken: 4, 1000, 1000, checkers off, 0 (Registration.h:61-78) */
+typedef struct {
+    int64_t n_trials;                /* trials consumed */
+    int64_t n_rejected_before;       /* ... rejected before alignment (no partner, edge lengths) */
+    int64_t n_rejected_after;        /* ... rejected after alignment (distance, normals) */
+    int64_t n_validated;             /* ... validated */
+    int64_t best_trial;              /* -1: none */
+    double hypothesis_ms;            /* device time of the trial kernels and their compaction */
+    double validation_ms;            /* host time of the validation (feature matching) or the scoring (correspondences) */
+} visma_icp_ransac_info;
+#define VISMA_RANSAC_PASS 0            /* verdicts of visma_icp_ransac_hypotheses: solved, every checker passed */
+#define VISMA_RANSAC_REJECTED_BEFORE 1 /* rejected before alignment; its T is all zeros */
+#define VISMA_RANSAC_REJECTED_AFTER 2  /* solved, rejected by the distance or the normal checker */
+/* The hypothesis stage alone, trials [first_trial, first_trial + n_trials): verdict_out[n_trials], T_out[n_trials x 16]
+ * row-major.  Pair k is (pair_src[k], pair_tgt[k]), or (k, pair_tgt[k]) where pair_src is NULL (a feature pair table:
+ * n_pairs == ns); pair_tgt may hold -1.  Normals both or NULL.  `draws` (or NULL) holds ransac_n entries for every trial
+ * from 0: (first_trial + n_trials) * ransac_n of them.  opt's max_iteration / max_validation play no part. */
+VISMA_ICP_API int visma_icp_ransac_hypotheses(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *tgt_xyz,
+                                              int64_t nt, const double *src_normals, const double *tgt_normals,
+                                              const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                              const visma_icp_ransac_option *opt, uint64_t seed, const int32_t *draws,
+                                              int64_t first_trial, int64_t n_trials, int8_t *verdict_out, double *T_out);
+/* The same on the host, no context: the very functions the kernels run (visma_amd/csrc/ransac.hpp). */
+VISMA_ICP_API int visma_icp_ransac_hypotheses_host(const double *src_xyz, int64_t ns, const double *tgt_xyz, int64_t nt,
+                                                   const double *src_normals, const double *tgt_normals,
+                                                   const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                                   const visma_icp_ransac_option *opt, uint64_t seed, const int32_t *draws,
+                                                   int64_t first_trial, int64_t n_trials, int8_t *verdict_out, double *T_out);
+/* Features ns x dim / nt x dim, row-major, dim in [1, 64]; normals both or NULL; info may be NULL.  An empty cloud,
+ * max_dist <= 0 (the reference's early return), ransac_n or dim out of range: VISMA_ICP_ERR_INVALID, before anything
+ * reaches a device. */
+VISMA_ICP_API int visma_icp_registration_ransac_feature_matching(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns,
+                                                                 const double *src_feat, const double *tgt_xyz, int64_t nt,
+                                                                 const double *tgt_feat, int dim, const double *src_normals,
+                                                                 const double *tgt_normals, double max_dist,
+                                                                 const visma_icp_ransac_option *opt, uint64_t seed,
+                                                                 const int32_t *draws, int64_t n_draw_trials,
+                                                                 visma_icp_result *result, visma_icp_ransac_info *info);
+/* K pairs (src_idx[c], tgt_idx[c]); an index outside its cloud, K < ransac_n: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_registration_ransac_correspondence(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns,
+                                                               const double *tgt_xyz, int64_t nt, const int32_t *src_idx,
+                                                               const int32_t *tgt_idx, int64_t K, double max_dist, int ransac_n,
+                                                               int max_iteration, int max_validation, uint64_t seed,
+                                                               const int32_t *draws, int64_t n_draw_trials,
+                                                               visma_icp_result *result, visma_icp_ransac_info *info);
+
 /* Point -> triangle-mesh squared distance, face and closest point for np query
  * points: what igl::AABB::squared_distance returns inside feh::MeasureSurfaceError
  * (include/geometry.h:123-136).  face / closest may be NULL; exact ties go to the

@@ -56,6 +56,7 @@
 
 #include <Core/Registration/Feature.h>
 #include <Core/Registration/FastGlobalRegistration.h>
+#include <Core/Registration/CorrespondenceChecker.h>
 
 #include "visma_icp.h"
 #include "visma_io.h"
@@ -1132,6 +1133,135 @@ inline RegistrationResult FastGlobalRegistration(const PointCloud &source, const
     return cicp::FastGlobalRegistration(source, target, source_feature, target_feature, option, 0);
 }
 
+namespace detail {
+
+// RANSAC runs TransformationEstimationPointToPoint(false) only (the stock class or the 4DoF one, which is the same
+// arithmetic without an axis); anything else is reported and the caller gets the reference's empty result
+inline bool ransac_estimation_supported(const TransformationEstimation &estimation, const char *who)
+{
+    const std::type_info &dyn = typeid(estimation);
+    const auto *p2p = dyn == typeid(TransformationEstimationPointToPoint) ? static_cast<const TransformationEstimationPointToPoint *>(&estimation) : nullptr;
+    const auto *four = dyn == typeid(TransformationEstimationPointToPoint4DoF) ? static_cast<const TransformationEstimationPointToPoint4DoF *>(&estimation) : nullptr;
+    if ((p2p && !p2p->with_scaling_) || (four && !four->with_scaling_)) return true;
+    std::fprintf(stderr, "Error: %s: unsupported estimation (only TransformationEstimationPointToPoint(false) runs on the GPU).\n", who);
+    return false;
+}
+
+}  // namespace detail
+
+// open3d::RegistrationRANSACBasedOnFeatureMatching (O3D/Core/Registration/Registration.cpp:226-353) on the GPU
+// (visma_icp.h, "RANSAC global registration").  The reference seeds rand() from the clock and races its threads for the
+// validation count; here trial t draws from a Philox stream keyed by `seed` (0 for the overload without one) and the
+// validated trials are the first max_validation_ that pass, in trial order: a registration is reproducible.  The checkers
+// must be the three built-in classes, one of each at most, with a positive distance and a non-zero angle (the GPU cannot
+// call a user's virtual Check); ransac_n lies in [3, 8].  Outside
+// that, an estimation other than point-to-point without scaling, features that are not one per point, or the reference's
+// own early returns: RegistrationResult(), with a message where the reference has none.
+inline RegistrationResult RegistrationRANSACBasedOnFeatureMatching(
+    const PointCloud &source, const PointCloud &target, const Feature &source_feature, const Feature &target_feature,
+    double max_correspondence_distance, const TransformationEstimation &estimation, int ransac_n,
+    const std::vector<std::reference_wrapper<const CorrespondenceChecker>> &checkers, const RANSACConvergenceCriteria &criteria,
+    uint64_t seed)
+{
+    if (ransac_n < 3 || max_correspondence_distance <= 0.0) return RegistrationResult();
+    if (!detail::ransac_estimation_supported(estimation, "RegistrationRANSACBasedOnFeatureMatching")) return RegistrationResult();
+    visma_icp_ransac_option o = {ransac_n, criteria.max_iteration_, criteria.max_validation_, 0.0, 0.0, 0.0, 0};
+    bool has_edge = false, has_distance = false, has_normal = false;
+    for (const auto &c : checkers) {
+        const std::type_info &dyn = typeid(c.get());
+        if (dyn == typeid(CorrespondenceCheckerBasedOnEdgeLength) && !has_edge) {
+            // (a similarity <= 0 rejects nothing in the reference either: the option's "off" is the same checker)
+            has_edge = true;
+            o.edge_length_similarity = static_cast<const CorrespondenceCheckerBasedOnEdgeLength &>(c.get()).similarity_threshold_;
+        } else if (dyn == typeid(CorrespondenceCheckerBasedOnDistance) && !has_distance) {
+            has_distance = true;
+            o.distance_threshold = static_cast<const CorrespondenceCheckerBasedOnDistance &>(c.get()).distance_threshold_;
+        } else if (dyn == typeid(CorrespondenceCheckerBasedOnNormal) && !has_normal) {
+            has_normal = true;                                   // (cos is even: a negative angle is the same checker)
+            o.normal_angle = std::fabs(static_cast<const CorrespondenceCheckerBasedOnNormal &>(c.get()).normal_angle_threshold_);
+        }
+        else {
+            std::fprintf(stderr, "Error: RegistrationRANSACBasedOnFeatureMatching: unsupported checker (one each of the three "
+                                 "built-in CorrespondenceChecker classes runs on the GPU).\n");
+            return RegistrationResult();
+        }
+    }
+    // in visma_icp_ransac_option a threshold <= 0 means "no checker"; the reference's distance checker at <= 0 rejects every
+    // trial and its normal checker at 0 asks for a dot product >= 1: neither can be said there, so they are reported
+    if ((has_distance && !(o.distance_threshold > 0.0)) || (has_normal && !(o.normal_angle > 0.0))) {
+        std::fprintf(stderr, "Error: RegistrationRANSACBasedOnFeatureMatching: unsupported checker threshold (a distance and an angle "
+                             "must be positive).\n");
+        return RegistrationResult();
+    }
+    if (ransac_n > 8 || source.points_.empty() || target.points_.empty() || source_feature.Dimension() != target_feature.Dimension() ||
+        source_feature.Dimension() < 1 || source_feature.Dimension() > 64 || source_feature.Num() != source.points_.size() ||
+        target_feature.Num() != target.points_.size()) {
+        std::fprintf(stderr, "Error: RegistrationRANSACBasedOnFeatureMatching: unsupported arguments (ransac_n in [3, 8], one feature "
+                             "of 1 to 64 dimensions per point of two non-empty clouds).\n");
+        return RegistrationResult();
+    }
+    const std::vector<double> fs = detail::feature_rows(source_feature), ft = detail::feature_rows(target_feature);
+    const bool normals = source.HasNormals() && target.HasNormals();
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    visma_icp_result r;
+    detail::check(ctx, visma_icp_registration_ransac_feature_matching(
+                           ctx, detail::xyz(source.points_), (int64_t)source.points_.size(), fs.data(), detail::xyz(target.points_),
+                           (int64_t)target.points_.size(), ft.data(), (int)source_feature.Dimension(),
+                           normals ? detail::xyz(source.normals_) : nullptr, normals ? detail::xyz(target.normals_) : nullptr,
+                           max_correspondence_distance, &o, seed, nullptr, 0, &r, nullptr),
+                  "visma_icp_registration_ransac_feature_matching");
+    RegistrationResult result;
+    if (r.num_correspondences > 0) detail::fill_result(ctx, r, source.points_.size(), result);
+    return result;
+}
+
+inline RegistrationResult RegistrationRANSACBasedOnFeatureMatching(
+    const PointCloud &source, const PointCloud &target, const Feature &source_feature, const Feature &target_feature,
+    double max_correspondence_distance, const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false),
+    int ransac_n = 4, const std::vector<std::reference_wrapper<const CorrespondenceChecker>> &checkers = {},
+    const RANSACConvergenceCriteria &criteria = RANSACConvergenceCriteria())
+{
+    return cicp::RegistrationRANSACBasedOnFeatureMatching(source, target, source_feature, target_feature, max_correspondence_distance,
+                                                          estimation, ransac_n, checkers, criteria, 0);
+}
+
+// open3d::RegistrationRANSACBasedOnCorrespondence (Registration.cpp:188-224): fitness and rmse over the pair list, no
+// correspondence set, as the reference returns it
+inline RegistrationResult RegistrationRANSACBasedOnCorrespondence(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres, double max_correspondence_distance,
+    const TransformationEstimation &estimation, int ransac_n, const RANSACConvergenceCriteria &criteria, uint64_t seed)
+{
+    if (ransac_n < 3 || (int)corres.size() < ransac_n || max_correspondence_distance <= 0.0) return RegistrationResult();
+    if (!detail::ransac_estimation_supported(estimation, "RegistrationRANSACBasedOnCorrespondence")) return RegistrationResult();
+    if (ransac_n > 8 || source.points_.empty() || target.points_.empty()) {
+        std::fprintf(stderr, "Error: RegistrationRANSACBasedOnCorrespondence: unsupported arguments (ransac_n in [3, 8], two "
+                             "non-empty clouds).\n");
+        return RegistrationResult();
+    }
+    std::vector<int32_t> si(corres.size()), ti(corres.size());
+    for (size_t c = 0; c < corres.size(); c++) { si[c] = corres[c][0]; ti[c] = corres[c][1]; }
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    visma_icp_result r;
+    detail::check(ctx, visma_icp_registration_ransac_correspondence(
+                           ctx, detail::xyz(source.points_), (int64_t)source.points_.size(), detail::xyz(target.points_),
+                           (int64_t)target.points_.size(), si.data(), ti.data(), (int64_t)si.size(), max_correspondence_distance,
+                           ransac_n, criteria.max_iteration_, criteria.max_validation_, seed, nullptr, 0, &r, nullptr),
+                  "visma_icp_registration_ransac_correspondence");
+    RegistrationResult result(detail::from_rowmajor(r.transformation));
+    result.fitness_ = r.fitness;
+    result.inlier_rmse_ = r.inlier_rmse;
+    return result;
+}
+
+inline RegistrationResult RegistrationRANSACBasedOnCorrespondence(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres, double max_correspondence_distance,
+    const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false), int ransac_n = 6,
+    const RANSACConvergenceCriteria &criteria = RANSACConvergenceCriteria())
+{
+    return cicp::RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_correspondence_distance, estimation, ransac_n,
+                                                         criteria, 0);
+}
+
 // open3d::ComputePointCloudToPointCloudDistance (O3D/Core/Geometry/PointCloud.cpp:122-142) on the GPU: for every
 // source point the distance to the nearest target point, no radius, bit for bit the reference's (0 for every
 // point when the target is empty).
@@ -1452,6 +1582,21 @@ inline RegistrationResult FastGlobalRegistration(const PointCloud &source, const
                                                  const Feature &target_feature, const FastGlobalRegistrationOption &option)
 {
     return cicp::FastGlobalRegistration(source, target, source_feature, target_feature, option);
+}
+inline RegistrationResult RegistrationRANSACBasedOnCorrespondence(
+    const PointCloud &source, const PointCloud &target, const CorrespondenceSet &corres, double max_correspondence_distance,
+    const TransformationEstimation &estimation, int ransac_n, const RANSACConvergenceCriteria &criteria)
+{
+    return cicp::RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_correspondence_distance, estimation, ransac_n,
+                                                         criteria);
+}
+inline RegistrationResult RegistrationRANSACBasedOnFeatureMatching(
+    const PointCloud &source, const PointCloud &target, const Feature &source_feature, const Feature &target_feature,
+    double max_correspondence_distance, const TransformationEstimation &estimation, int ransac_n,
+    const std::vector<std::reference_wrapper<const CorrespondenceChecker>> &checkers, const RANSACConvergenceCriteria &criteria)
+{
+    return cicp::RegistrationRANSACBasedOnFeatureMatching(source, target, source_feature, target_feature, max_correspondence_distance,
+                                                          estimation, ransac_n, checkers, criteria);
 }
 inline bool ReadPointCloudFromPLY(const std::string &filename, PointCloud &pointcloud)
 {

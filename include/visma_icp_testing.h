@@ -101,6 +101,15 @@ VISMA_ICP_API int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double 
 VISMA_ICP_API int visma_icp_match_features_probe(visma_icp_ctx *ctx, const double *fa, int64_t na, const double *fb,
                                                  int64_t nb, int dim, int32_t *nn_of_b, double *d2_of_b, double *kernel_ms);
 
+/* Measurement (tools/ransac_probe.py): the hypothesis stage of visma_icp_ransac_hypotheses over trials [0, n_trials) without
+ * its rows -- counts[3] = trials per verdict (pass, rejected before, rejected after alignment), *ms = device time of the
+ * trial kernels and their compaction, chunk by chunk as the registration runs them. */
+VISMA_ICP_API int visma_icp_ransac_hypotheses_probe(visma_icp_ctx *ctx, const double *src_xyz, int64_t ns, const double *tgt_xyz,
+                                                    int64_t nt, const double *src_normals, const double *tgt_normals,
+                                                    const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                                    const visma_icp_ransac_option *opt, uint64_t seed, int64_t n_trials,
+                                                    int64_t counts[3], double *ms);
+
 /* Device self-test of the SO(3) math the kernels are built on (restatement of
  * core/rodrigues.h:143-226 in visma_amd/csrc/so3.h): for n axis-angle vectors
  * w (3n doubles) computes, ON THE GPU, R = rodrigues(w) (9n) and

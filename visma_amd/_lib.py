@@ -250,6 +250,18 @@ def _bind(L):
         L.visma_icp_fgr_optimize.argtypes = [_dp, C.c_int64, _dp, C.c_int64, _ip, _ip, C.c_int64, _fo, _dp, _dp]
         L.visma_icp_fast_global_registration.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, _fo, C.c_uint64,
                                                          _ip, C.c_int64, _dp, _fi]
+    if hasattr(L, "visma_icp_registration_ransac_feature_matching"):
+        _ro, _ri, _bp = C.POINTER(CRansacOption), C.POINTER(CRansacInfo), C.POINTER(C.c_int8)
+        hyp = [_dp, C.c_int64, _dp, C.c_int64, _dp, _dp, _ip, _ip, C.c_int64, _ro, C.c_uint64, _ip, C.c_int64, C.c_int64, _bp, _dp]
+        L.visma_icp_ransac_hypotheses.argtypes = [C.c_void_p] + hyp
+        L.visma_icp_ransac_hypotheses_host.argtypes = hyp
+        L.visma_icp_ransac_hypotheses_probe.argtypes = [C.c_void_p] + hyp[:11] + [C.c_int64, C.POINTER(C.c_int64), _dp]
+        L.visma_icp_registration_ransac_feature_matching.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, _dp, C.c_int64, _dp, C.c_int, _dp,
+                                                                     _dp, C.c_double, _ro, C.c_uint64, _ip, C.c_int64,
+                                                                     C.POINTER(CResult), _ri]
+        L.visma_icp_registration_ransac_correspondence.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _ip, _ip, C.c_int64,
+                                                                   C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, _ip, C.c_int64,
+                                                                   C.POINTER(CResult), _ri]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -424,6 +436,85 @@ def fgr_optimize(src, tgt, src_idx, tgt_idx, option=None):
     if rc != OK:
         raise IcpError(rc, "fgr_optimize: bad arguments")
     return T.reshape(4, 4), Topt.reshape(4, 4)
+
+
+class CRansacOption(C.Structure):
+    """visma_icp_ransac_option (defaults: Registration.h:61-78, every checker off)"""
+    _fields_ = [("ransac_n", C.c_int), ("max_iteration", C.c_int), ("max_validation", C.c_int),
+                ("edge_length_similarity", C.c_double), ("distance_threshold", C.c_double), ("normal_angle", C.c_double),
+                ("chunk_trials", C.c_int)]
+
+
+class CRansacInfo(C.Structure):
+    """visma_icp_ransac_info"""
+    _fields_ = [("n_trials", C.c_int64), ("n_rejected_before", C.c_int64), ("n_rejected_after", C.c_int64),
+                ("n_validated", C.c_int64), ("best_trial", C.c_int64), ("hypothesis_ms", C.c_double), ("validation_ms", C.c_double)]
+
+
+RANSAC_PASS, RANSAC_REJECTED_BEFORE, RANSAC_REJECTED_AFTER = 0, 1, 2
+
+
+def ransac_option(ransac_n=4, max_iteration=1000, max_validation=1000, edge_length_similarity=0.0, distance_threshold=0.0,
+                  normal_angle=0.0, chunk_trials=0):
+    """A checker threshold <= 0 turns that checker off; chunk_trials 0: the library's choice."""
+    return CRansacOption(int(ransac_n), int(max_iteration), int(max_validation), float(edge_length_similarity),
+                         float(distance_threshold), float(normal_angle), int(chunk_trials))
+
+
+class RansacInfo:
+    """What the RANSAC loop did: trials consumed, rejected before / after alignment, validated, the best trial (-1: none)."""
+
+    def __init__(self, c):
+        self.n_trials = int(c.n_trials)
+        self.n_rejected_before = int(c.n_rejected_before)
+        self.n_rejected_after = int(c.n_rejected_after)
+        self.n_validated = int(c.n_validated)
+        self.best_trial = int(c.best_trial)
+        self.hypothesis_ms = float(c.hypothesis_ms)
+        self.validation_ms = float(c.validation_ms)
+
+    def __repr__(self):
+        return ("RansacInfo(n_trials=%d, n_rejected_before=%d, n_rejected_after=%d, n_validated=%d, best_trial=%d)"
+                % (self.n_trials, self.n_rejected_before, self.n_rejected_after, self.n_validated, self.best_trial))
+
+
+def _ransac_draws(draws, ransac_n):
+    if draws is None:
+        return None, 0, None
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1, max(int(ransac_n), 1))
+    return d, len(d), _p(d, _ip)
+
+
+def _ransac_hyp_args(src, tgt, src_normals, tgt_normals, pair_src, pair_tgt, option, draws, first_trial, n_trials):
+    s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+    sn = None if src_normals is None else _f64(src_normals, (-1, 3))
+    tn = None if tgt_normals is None else _f64(tgt_normals, (-1, 3))
+    ps = None if pair_src is None else np.ascontiguousarray(pair_src, np.int32).ravel()
+    pt = np.ascontiguousarray(pair_tgt, np.int32).ravel()
+    if (sn is not None and len(sn) != len(s)) or (tn is not None and len(tn) != len(t)) or (ps is not None and len(ps) != len(pt)):
+        raise ValueError("ransac_hypotheses: one normal per point, one target index per source index")
+    o = option if option is not None else ransac_option()
+    d, nd, dp_ = _ransac_draws(draws, o.ransac_n)
+    if d is not None and nd < int(first_trial) + int(n_trials):
+        raise ValueError("ransac_hypotheses: draws for every trial from 0")
+    verdict = np.zeros(max(int(n_trials), 1), np.int8); T = np.zeros((max(int(n_trials), 1), 16))
+    keep = (s, t, sn, tn, ps, pt, d)
+    return keep, o, verdict, T, [_p(s, _dp), len(s), _p(t, _dp), len(t), None if sn is None else _p(sn, _dp),
+                                 None if tn is None else _p(tn, _dp), None if ps is None else _p(ps, _ip), _p(pt, _ip), len(pt),
+                                 C.byref(o)]
+
+
+def ransac_hypotheses_host(src, tgt, pair_tgt, option=None, seed=0, draws=None, first_trial=0, n_trials=0, src_normals=None,
+                           tgt_normals=None, pair_src=None):
+    """The hypothesis stage of RANSAC on the host (no context): the functions the kernels run
+    -> (verdict (n,) int8, T (n, 4, 4))."""
+    keep, o, verdict, T, args = _ransac_hyp_args(src, tgt, src_normals, tgt_normals, pair_src, pair_tgt, option, draws, first_trial,
+                                                 n_trials)
+    rc = load().visma_icp_ransac_hypotheses_host(*args, int(seed), None if keep[6] is None else _p(keep[6], _ip), int(first_trial),
+                                                 int(n_trials), _p(verdict, C.POINTER(C.c_int8)), _p(T, _dp))
+    if rc != OK:
+        raise IcpError(rc, "ransac_hypotheses_host: bad arguments")
+    return verdict[:int(n_trials)].copy(), T[:int(n_trials)].reshape(-1, 4, 4).copy()
 
 
 class Result:
@@ -906,6 +997,65 @@ class Context:
                                                             _p(ft, _dp), C.byref(o), int(seed), trp, ntr, _p(T, _dp),
                                                             C.byref(info)))
         return T.reshape(4, 4), FgrInfo(info)
+
+    def ransac_hypotheses(self, src, tgt, pair_tgt, option=None, seed=0, draws=None, first_trial=0, n_trials=0, src_normals=None,
+                          tgt_normals=None, pair_src=None):
+        """The hypothesis stage of RANSAC on the GPU, trials [first_trial, first_trial + n_trials): pair k is
+        (pair_src[k], pair_tgt[k]) or, without pair_src, (k, pair_tgt[k]) -> (verdict (n,) int8, T (n, 4, 4))."""
+        keep, o, verdict, T, args = _ransac_hyp_args(src, tgt, src_normals, tgt_normals, pair_src, pair_tgt, option, draws,
+                                                     first_trial, n_trials)
+        self._chk(self.L.visma_icp_ransac_hypotheses(self._h, *args, int(seed), None if keep[6] is None else _p(keep[6], _ip),
+                                                     int(first_trial), int(n_trials), _p(verdict, C.POINTER(C.c_int8)), _p(T, _dp)))
+        return verdict[:int(n_trials)].copy(), T[:int(n_trials)].reshape(-1, 4, 4).copy()
+
+    def ransac_hypotheses_probe(self, src, tgt, pair_tgt, option=None, seed=0, n_trials=0, src_normals=None, tgt_normals=None,
+                                pair_src=None):
+        """Measurement: the hypothesis stage over trials [0, n_trials) without its rows
+        -> ([passed, rejected before, rejected after], device ms)."""
+        keep, o, _, _, args = _ransac_hyp_args(src, tgt, src_normals, tgt_normals, pair_src, pair_tgt, option, None, 0, 0)
+        counts = np.zeros(3, np.int64); ms = C.c_double(0.0)
+        self._chk(self.L.visma_icp_ransac_hypotheses_probe(self._h, *args, int(seed), int(n_trials),
+                                                           _p(counts, C.POINTER(C.c_int64)), C.byref(ms)))
+        return [int(c) for c in counts], ms.value
+
+    def registration_ransac_feature_matching(self, src, src_feat, tgt, tgt_feat, max_dist, option=None, seed=0, draws=None,
+                                             src_normals=None, tgt_normals=None):
+        """open3d::RegistrationRANSACBasedOnFeatureMatching (point-to-point, the three built-in checkers through `option`)
+        -> Result with .ransac (RansacInfo).  The context then holds the pair and the pass at the returned pose."""
+        s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+        fs = _f64(src_feat); ft = _f64(tgt_feat)
+        fs = fs.reshape(len(s), -1) if len(s) else fs; ft = ft.reshape(len(t), -1) if len(t) else ft
+        if fs.ndim != 2 or ft.ndim != 2 or fs.shape[1] != ft.shape[1]:
+            raise ValueError("registration_ransac_feature_matching: one feature row per point, one dimension")
+        sn = None if src_normals is None else _f64(src_normals, (-1, 3))
+        tn = None if tgt_normals is None else _f64(tgt_normals, (-1, 3))
+        o = option if option is not None else ransac_option()
+        d, nd, dp_ = _ransac_draws(draws, o.ransac_n)
+        out = CResult(); info = CRansacInfo()
+        self._chk(self.L.visma_icp_registration_ransac_feature_matching(
+            self._h, _p(s, _dp), len(s), _p(fs, _dp), _p(t, _dp), len(t), _p(ft, _dp), int(fs.shape[1]),
+            None if sn is None else _p(sn, _dp), None if tn is None else _p(tn, _dp), float(max_dist), C.byref(o), int(seed), dp_, nd,
+            C.byref(out), C.byref(info)))
+        self.ns, self.nt = len(s), len(t)
+        r = Result(out)
+        r.ransac = RansacInfo(info)
+        return r
+
+    def registration_ransac_correspondence(self, src, tgt, pairs, max_dist, ransac_n=6, max_iteration=1000, max_validation=1000,
+                                           seed=0, draws=None):
+        """open3d::RegistrationRANSACBasedOnCorrespondence over pairs (K, 2) (source index, target index) -> Result with
+        .ransac; fitness and rmse are those of the pair list."""
+        s = _f64(src, (-1, 3)); t = _f64(tgt, (-1, 3))
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        si = np.ascontiguousarray(pr[:, 0]); ti = np.ascontiguousarray(pr[:, 1])
+        d, nd, dp_ = _ransac_draws(draws, ransac_n)
+        out = CResult(); info = CRansacInfo()
+        self._chk(self.L.visma_icp_registration_ransac_correspondence(
+            self._h, _p(s, _dp), len(s), _p(t, _dp), len(t), _p(si, _ip), _p(ti, _ip), len(si), float(max_dist), int(ransac_n),
+            int(max_iteration), int(max_validation), int(seed), dp_, nd, C.byref(out), C.byref(info)))
+        r = Result(out)
+        r.ransac = RansacInfo(info)
+        return r
 
     def voxel_down_sample(self, xyz, voxel_size, normals=None, colors=None):
         """open3d::VoxelDownSample on the GPU -> (points, normals, colors), voxels in ascending index order."""

@@ -1,8 +1,9 @@
 // aux_api.cpp -- C ABI of the steps either side of the ICP loop: VoxelDownSample, EstimateNormals, mesh sampling
-// and point-to-mesh distance, cloud-to-cloud and nearest-neighbour distances, the error metric, and the SO(3) /
-// SE(3) functions (host + device self-tests).
+// and point-to-mesh distance, cloud-to-cloud and nearest-neighbour distances, FPFH / fast global registration / RANSAC global
+// registration (no initial pose), the error metric, and the SO(3) / SE(3) functions (host + device self-tests).
 #include "driver_ctx.hpp"
 #include "plane_math.hpp"
+#include "ransac.hpp"
 
 extern "C" {
 
@@ -198,6 +199,388 @@ int visma_icp_fast_global_registration(visma_icp_ctx *ctx, const double *src_xyz
         return rc;
     if (visma_icp_fgr_optimize(src_xyz, ns, tgt_xyz, nt, oi.data(), oj.data(), (int64_t)oi.size(), opt, out_T, nullptr))
         return ctx->fail(VISMA_ICP_ERR_INVALID, "fast_global_registration: optimize rejected its pairs");
+    return VISMA_ICP_OK;
+}
+
+// ---- RANSAC global registration (include/visma_icp.h; trial arithmetic: ransac.hpp; kernels: ransac.hip) ----
+
+static const visma_icp_ransac_option kRansacDefaults = {4, 1000, 1000, 0.0, 0.0, 0.0, 0};
+constexpr int64_t kRansacChunk = 1 << 19;             // trials per launch: 48 MB of T slots
+
+// the arguments every entry point shares; NULL: fine, else the message
+static const char *ransac_check(const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn, const double *tn,
+                                const visma_icp_ransac_option &o, const int32_t *draws, int64_t n_draw_trials)
+{
+    if (ns <= 0 || nt <= 0 || !src || !tgt) return "ransac: an empty cloud";
+    if (ns > 0x7fffffff || nt > 0x7fffffff) return "too many points for 32-bit indices";
+    if ((sn == nullptr) != (tn == nullptr)) return "ransac: normals for both clouds or for none";
+    if (o.ransac_n < kRansacMinN || o.ransac_n > kRansacMaxN) return "ransac: ransac_n must lie in [3, 8]";
+    if (o.chunk_trials < 0 || o.chunk_trials > (1 << 22)) return "ransac: chunk_trials must lie in [0, 4194304]";
+    if (n_draw_trials < 0 || (n_draw_trials > 0 && !draws)) return "ransac: bad draws";
+    return nullptr;
+}
+
+static RansacProblem ransac_problem(const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn, const double *tn,
+                                    const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                    const visma_icp_ransac_option &o, uint64_t seed, const int32_t *draws, int64_t n_draw_trials)
+{
+    RansacProblem p;
+    p.src = src; p.ns = ns; p.tgt = tgt; p.nt = nt; p.src_n = sn; p.tgt_n = tn;
+    p.pair_src = pair_src; p.pair_tgt = pair_tgt; p.n_pairs = n_pairs;
+    p.draws = draws; p.n_draw_trials = draws ? n_draw_trials : 0;
+    p.seed = seed; p.ransac_n = o.ransac_n;
+    p.use_edge = o.edge_length_similarity > 0.0; p.edge = o.edge_length_similarity;
+    p.use_dist = o.distance_threshold > 0.0; p.dist = o.distance_threshold;
+    p.use_normal = o.normal_angle > 0.0; p.cos_normal = std::cos(o.normal_angle);
+    return p;
+}
+
+static RansacView ransac_host_view(const RansacProblem &p)
+{
+    RansacView v;
+    v.src = p.src; v.tgt = p.tgt; v.src_n = p.src_n; v.tgt_n = p.tgt_n;
+    v.pair_src = p.pair_src; v.pair_tgt = p.pair_tgt; v.n_pairs = p.n_pairs;
+    v.draws = p.draws; v.seed = p.seed;
+    v.edge = p.edge; v.dist = p.dist; v.cos_normal = p.cos_normal;
+    v.use_edge = p.use_edge; v.use_dist = p.use_dist; v.use_normal = p.use_normal;
+    return v;
+}
+
+static int ransac_trial_host(const RansacView &v, int n, long long t, double T[12])
+{
+    switch (n) {
+    case 3: return ransac_trial<3>(v, t, T);
+    case 4: return ransac_trial<4>(v, t, T);
+    case 5: return ransac_trial<5>(v, t, T);
+    case 6: return ransac_trial<6>(v, t, T);
+    case 7: return ransac_trial<7>(v, t, T);
+    default: return ransac_trial<8>(v, t, T);
+    }
+}
+
+static const char *ransac_check_hypotheses(const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn,
+                                           const double *tn, const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                           const visma_icp_ransac_option &o, const int32_t *draws, int64_t first_trial,
+                                           int64_t n_trials, const int8_t *verdict_out, const double *T_out)
+{
+    if (const char *m = ransac_check(src, ns, tgt, nt, sn, tn, o, draws, 0)) return m;
+    if (!pair_tgt || n_pairs <= 0 || n_pairs > 0x7fffffff || (!pair_src && n_pairs != ns)) return "ransac_hypotheses: bad pair table";
+    if (first_trial < 0 || n_trials < 0 || (n_trials > 0 && (!verdict_out || !T_out))) return "bad ransac_hypotheses arguments";
+    for (int64_t k = 0; k < n_pairs; k++)
+        if (pair_tgt[k] < -1 || pair_tgt[k] >= nt || (pair_src && (pair_src[k] < 0 || pair_src[k] >= ns)))
+            return "ransac_hypotheses: a pair outside its cloud";
+    return nullptr;
+}
+
+int visma_icp_ransac_hypotheses_host(const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn, const double *tn,
+                                     const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                     const visma_icp_ransac_option *opt, uint64_t seed, const int32_t *draws, int64_t first_trial,
+                                     int64_t n_trials, int8_t *verdict_out, double *T_out)
+{
+    const visma_icp_ransac_option o = opt ? *opt : kRansacDefaults;
+    if (ransac_check_hypotheses(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, draws, first_trial, n_trials, verdict_out, T_out))
+        return VISMA_ICP_ERR_INVALID;
+    const RansacView v = ransac_host_view(ransac_problem(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, seed, draws,
+                                                         first_trial + n_trials));
+    parallel_for(n_trials, 256, [&](int64_t i) {
+        double T[12];
+        const int r = ransac_trial_host(v, o.ransac_n, first_trial + i, T);
+        verdict_out[i] = (int8_t)r;
+        double *out = T_out + 16 * i;
+        for (int c = 0; c < 12; c++) out[c] = T[c];
+        out[12] = out[13] = out[14] = 0.0;
+        out[15] = r == kRansacBefore ? 0.0 : 1.0;
+    });
+    return VISMA_ICP_OK;
+}
+
+struct RansacDeviceHolder {
+    RansacDevice *d = nullptr;
+    ~RansacDeviceHolder() { ransac_device_destroy(d); }
+};
+
+int visma_icp_ransac_hypotheses(visma_icp_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn,
+                                const double *tn, const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                const visma_icp_ransac_option *opt, uint64_t seed, const int32_t *draws, int64_t first_trial,
+                                int64_t n_trials, int8_t *verdict_out, double *T_out)
+{
+    CTX_CHECK();
+    const visma_icp_ransac_option o = opt ? *opt : kRansacDefaults;
+    if (const char *m = ransac_check_hypotheses(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, draws, first_trial, n_trials,
+                                                verdict_out, T_out))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, m);
+    if (n_trials == 0) return VISMA_ICP_OK;
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "ransac_hypotheses needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    const int64_t chunk = std::min<int64_t>(o.chunk_trials > 0 ? o.chunk_trials : kRansacChunk, n_trials);
+    RansacDeviceHolder H;
+    hipError_t e = ransac_device_create(ransac_problem(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, seed, draws,
+                                                       first_trial + n_trials), chunk, ctx->eng->aux_stream(), &H.d);
+    for (int64_t t = 0; e == hipSuccess && t < n_trials; t += chunk)
+        e = ransac_device_chunk(H.d, first_trial + t, std::min(chunk, n_trials - t),
+                                verdict_out + t, T_out + 16 * t, nullptr, nullptr, nullptr);
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("ransac_hypotheses: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_ransac_hypotheses_probe(visma_icp_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt, const double *sn,
+                                      const double *tn, const int32_t *pair_src, const int32_t *pair_tgt, int64_t n_pairs,
+                                      const visma_icp_ransac_option *opt, uint64_t seed, int64_t n_trials, int64_t counts[3], double *ms)
+{
+    CTX_CHECK();
+    const visma_icp_ransac_option o = opt ? *opt : kRansacDefaults;
+    int8_t none = 0;
+    double noT = 0.0;
+    if (const char *m = ransac_check_hypotheses(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, nullptr, 0, n_trials, &none, &noT))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, m);
+    if (!counts || !ms || n_trials <= 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad ransac_hypotheses_probe arguments");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "ransac_hypotheses_probe needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    const int64_t chunk = std::min<int64_t>(o.chunk_trials > 0 ? o.chunk_trials : kRansacChunk, n_trials);
+    RansacDeviceHolder H;
+    hipError_t e = ransac_device_create(ransac_problem(src, ns, tgt, nt, sn, tn, pair_src, pair_tgt, n_pairs, o, seed, nullptr, 0), chunk,
+                                        ctx->eng->aux_stream(), &H.d);
+    std::vector<int8_t> verdict((size_t)chunk);
+    counts[0] = counts[1] = counts[2] = 0;
+    *ms = 0.0;
+    for (int64_t t = 0; e == hipSuccess && t < n_trials; t += chunk) {
+        const int64_t m = std::min(chunk, n_trials - t);
+        e = ransac_device_chunk(H.d, t, m, verdict.data(), nullptr, nullptr, nullptr, ms);
+        for (int64_t i = 0; e == hipSuccess && i < m; i++) {
+            const int8_t r = verdict[(size_t)i];
+            if (r < 0 || r > kRansacAfter) { e = hipErrorUnknown; break; }           // (no trial leaves another verdict)
+            counts[r]++;
+        }
+    }
+    if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                          std::string("ransac_hypotheses_probe: ") + hipGetErrorString(e));
+    return VISMA_ICP_OK;
+}
+
+static void ransac_empty_result(visma_icp_result *r)
+{
+    std::memset(r, 0, sizeof(*r));
+    const Mat4 I = Mat4::identity();
+    std::memcpy(r->transformation, I.m, sizeof(I.m));
+}
+
+static double ransac_now_ms()
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// The source as the searches see it: a point that is not finite (the trials read it as it is) is moved where no transform
+// of this call can bring it within max_dist of the target.  Every T solved here maps the mean of its source sample onto
+// the mean of its target sample and is rigid, so |T far - (a target point)| >= |far - (a source point)| - (target extent).
+static const double *ransac_search_source(const double *src, int64_t ns, const double *tgt, int64_t nt, double max_dist,
+                                          std::vector<double> &copy)
+{
+    bool clean = true;
+    for (int64_t i = 0; clean && i < 3 * ns; i++) clean = std::isfinite(src[i]);
+    if (clean) return src;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, ext = 0.0;
+    bool first = true;
+    auto grow = [&](const double *p) {
+        if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) return;
+        for (int a = 0; a < 3; a++) {
+            if (first || p[a] < lo[a]) lo[a] = p[a];
+            if (first || p[a] > hi[a]) hi[a] = p[a];
+        }
+        first = false;
+    };
+    for (int64_t i = 0; i < ns; i++) grow(src + 3 * i);
+    for (int64_t i = 0; i < nt; i++) grow(tgt + 3 * i);
+    for (int a = 0; a < 3; a++) ext += hi[a] - lo[a];
+    const double far = 1000.0 * (ext + max_dist);
+    copy.assign(src, src + 3 * ns);
+    for (int64_t i = 0; i < ns; i++) {
+        double *p = &copy[(size_t)(3 * i)];
+        if (std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2])) continue;
+        for (int a = 0; a < 3; a++) p[a] = hi[a] + far;
+    }
+    return copy.data();
+}
+
+// EvaluateRegistration at every T (16 doubles each) through the batch path: one upload and one grid of the pair per
+// sub-batch, the poses as its initial transforms, zero iterations.  A T that is not finite: zero correspondences.
+static int ransac_validate(visma_icp_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt, double max_dist,
+                           const std::vector<double> &Ts, std::vector<visma_icp_result> &out)
+{
+    const int64_t n = (int64_t)(Ts.size() / 16);
+    out.assign((size_t)n, visma_icp_result());
+    std::vector<int64_t> finite;
+    for (int64_t i = 0; i < n; i++) {
+        bool ok = true;
+        for (int c = 0; c < 16; c++) ok = ok && std::isfinite(Ts[(size_t)(16 * i + c)]);
+        std::memset(&out[(size_t)i], 0, sizeof(visma_icp_result));
+        std::memcpy(out[(size_t)i].transformation, &Ts[(size_t)(16 * i)], 16 * sizeof(double));
+        if (ok) finite.push_back(i);
+    }
+    // (the split never changes a result: every problem of a batch is searched and reduced on its own)
+    const int64_t per = std::max<int64_t>(1, std::min<int64_t>(64, (int64_t)(8 << 20) / std::max<int64_t>(ns, 1)));
+    std::vector<visma_icp_problem> pb;
+    std::vector<visma_icp_result> rs;
+    for (size_t b = 0; b < finite.size(); b += (size_t)per) {
+        const size_t m = std::min(finite.size() - b, (size_t)per);
+        pb.assign(m, visma_icp_problem());
+        rs.assign(m, visma_icp_result());
+        for (size_t k = 0; k < m; k++) {
+            pb[k].src_xyz = src; pb[k].ns = ns; pb[k].tgt_xyz = tgt; pb[k].nt = nt; pb[k].max_dist = max_dist;
+            std::memcpy(pb[k].init, &Ts[(size_t)(16 * finite[b + k])], 16 * sizeof(double));
+        }
+        if (int rc = visma_icp_run_batch(ctx, pb.data(), (int)m, 0, 0.0, 0.0, VISMA_ICP_SOLVER_KABSCH, rs.data())) return rc;
+        for (size_t k = 0; k < m; k++) out[(size_t)finite[b + k]] = rs[k];
+    }
+    return VISMA_ICP_OK;
+}
+
+// Registration.cpp:215-219 / :321-325 over the trials in order; -1: nobody beat the empty result
+static int64_t ransac_best(const std::vector<double> &fitness, const std::vector<double> &rmse)
+{
+    int64_t best = -1;
+    double bf = 0.0, br = 0.0;
+    for (size_t i = 0; i < fitness.size(); i++)
+        if (fitness[i] > bf || (fitness[i] == bf && rmse[i] < br)) { best = (int64_t)i; bf = fitness[i]; br = rmse[i]; }
+    return best;
+}
+
+int visma_icp_registration_ransac_feature_matching(visma_icp_ctx *ctx, const double *src, int64_t ns, const double *src_feat,
+                                                   const double *tgt, int64_t nt, const double *tgt_feat, int dim, const double *sn,
+                                                   const double *tn, double max_dist, const visma_icp_ransac_option *opt,
+                                                   uint64_t seed, const int32_t *draws, int64_t n_draw_trials,
+                                                   visma_icp_result *result, visma_icp_ransac_info *info)
+{
+    CTX_CHECK();
+    const visma_icp_ransac_option o = opt ? *opt : kRansacDefaults;
+    if (const char *m = ransac_check(src, ns, tgt, nt, sn, tn, o, draws, n_draw_trials)) return ctx->fail(VISMA_ICP_ERR_INVALID, m);
+    if (!src_feat || !tgt_feat || !result) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad registration_ransac_feature_matching arguments");
+    if (dim < 1 || dim > 64) return ctx->fail(VISMA_ICP_ERR_INVALID, "registration_ransac_feature_matching: dim must lie in [1, 64]");
+    if (!(max_dist > 0.0)) return ctx->fail(VISMA_ICP_ERR_INVALID, "registration_ransac_feature_matching: max_dist must be positive");
+    if (!ctx->eng->supports_device_loop())
+        return ctx->fail(VISMA_ICP_ERR_STATE, "registration_ransac_feature_matching needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    ransac_empty_result(result);
+    visma_icp_ransac_info I = {0, 0, 0, 0, -1, 0.0, 0.0};
+    int64_t trials = std::max(o.max_iteration, 0);
+    if (draws) trials = std::min(trials, n_draw_trials);
+    const int64_t want = std::max(o.max_validation, 0);
+    if (want == 0) trials = 0;
+    std::vector<int64_t> pass_trial;
+    std::vector<double> pass_T;
+    if (trials > 0) {
+        std::vector<int32_t> nn((size_t)ns);
+        if (int rc = visma_icp_match_features(ctx, tgt_feat, nt, src_feat, ns, dim, nn.data(), nullptr)) return rc;
+        const int64_t chunk = std::min<int64_t>(o.chunk_trials > 0 ? o.chunk_trials : kRansacChunk, trials);
+        RansacDeviceHolder H;
+        hipError_t e = ransac_device_create(ransac_problem(src, ns, tgt, nt, sn, tn, nullptr, nn.data(), ns, o, seed, draws, trials),
+                                            chunk, ctx->eng->aux_stream(), &H.d);
+        std::vector<int8_t> verdict((size_t)chunk);
+        int64_t done = 0;
+        while (e == hipSuccess && done < trials && (int64_t)pass_trial.size() < want) {
+            const int64_t m = std::min(chunk, trials - done);
+            e = ransac_device_chunk(H.d, done, m, verdict.data(), nullptr, &pass_trial, &pass_T, &I.hypothesis_ms);
+            if (e != hipSuccess) break;
+            // the serial loop stops with the trial that was validated last: count the chunk up to there
+            int64_t upto = m;
+            if ((int64_t)pass_trial.size() >= want) {
+                pass_trial.resize((size_t)want);
+                pass_T.resize((size_t)(16 * want));
+                upto = pass_trial.back() + 1 - done;
+            }
+            for (int64_t i = 0; i < upto; i++) {
+                I.n_rejected_before += verdict[(size_t)i] == kRansacBefore;
+                I.n_rejected_after += verdict[(size_t)i] == kRansacAfter;
+            }
+            done += upto;
+        }
+        if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                              std::string("registration_ransac_feature_matching: ") + hipGetErrorString(e));
+        I.n_trials = done;
+        I.n_validated = (int64_t)pass_trial.size();
+    }
+    if (!pass_trial.empty()) {
+        const double t0 = ransac_now_ms();
+        std::vector<double> copy;
+        const double *ssrc = ransac_search_source(src, ns, tgt, nt, max_dist, copy);
+        std::vector<visma_icp_result> rs;
+        if (int rc = ransac_validate(ctx, ssrc, ns, tgt, nt, max_dist, pass_T, rs)) return rc;
+        std::vector<double> fit(rs.size()), rmse(rs.size());
+        for (size_t i = 0; i < rs.size(); i++) { fit[i] = rs[i].fitness; rmse[i] = rs[i].inlier_rmse; }
+        const int64_t b = ransac_best(fit, rmse);
+        I.validation_ms = ransac_now_ms() - t0;
+        if (b >= 0) {
+            I.best_trial = pass_trial[(size_t)b];
+            if (int rc = visma_icp_set_clouds_f64(ctx, ssrc, ns, 3, tgt, nt, 3)) return rc;
+            // twice: the first pass after an upload searches cold, every later one starts from the previous pass's winners and
+            // folds its sums in another order (rmse may differ in the last bit).  The numbers returned are those of the state
+            // the context is left in: the ones visma_icp_run(init = T, max_iter = 0) repeats.
+            for (int pass = 0; pass < 2; pass++)
+                if (int rc = visma_icp_run(ctx, &pass_T[(size_t)(16 * b)], max_dist, 0, 0.0, 0.0, VISMA_ICP_SOLVER_KABSCH, 0, result)) return rc;
+        }
+    }
+    if (info) *info = I;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_registration_ransac_correspondence(visma_icp_ctx *ctx, const double *src, int64_t ns, const double *tgt, int64_t nt,
+                                                 const int32_t *src_idx, const int32_t *tgt_idx, int64_t K, double max_dist,
+                                                 int ransac_n, int max_iteration, int max_validation, uint64_t seed,
+                                                 const int32_t *draws, int64_t n_draw_trials, visma_icp_result *result,
+                                                 visma_icp_ransac_info *info)
+{
+    CTX_CHECK();
+    visma_icp_ransac_option o = kRansacDefaults;
+    o.ransac_n = ransac_n; o.max_iteration = max_iteration; o.max_validation = max_validation;
+    if (const char *m = ransac_check(src, ns, tgt, nt, nullptr, nullptr, o, draws, n_draw_trials)) return ctx->fail(VISMA_ICP_ERR_INVALID, m);
+    if (!src_idx || !tgt_idx || !result || K > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad registration_ransac_correspondence arguments");
+    if (K < ransac_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "registration_ransac_correspondence: fewer pairs than ransac_n");
+    if (!(max_dist > 0.0)) return ctx->fail(VISMA_ICP_ERR_INVALID, "registration_ransac_correspondence: max_dist must be positive");
+    for (int64_t c = 0; c < K; c++)
+        if (src_idx[c] < 0 || src_idx[c] >= ns || tgt_idx[c] < 0 || tgt_idx[c] >= nt)
+            return ctx->fail(VISMA_ICP_ERR_INVALID, "registration_ransac_correspondence: a pair outside its cloud");
+    if (!ctx->eng->supports_device_loop())
+        return ctx->fail(VISMA_ICP_ERR_STATE, "registration_ransac_correspondence needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    ransac_empty_result(result);
+    visma_icp_ransac_info I = {0, 0, 0, 0, -1, 0.0, 0.0};
+    int64_t trials = std::max(std::min(max_iteration, max_validation), 0);
+    if (draws) trials = std::min(trials, n_draw_trials);
+    if (trials > 0) {
+        const int64_t chunk = std::min<int64_t>(kRansacChunk, trials);
+        RansacDeviceHolder H;
+        hipError_t e = ransac_device_create(ransac_problem(src, ns, tgt, nt, nullptr, nullptr, src_idx, tgt_idx, K, o, seed, draws, trials),
+                                            chunk, ctx->eng->aux_stream(), &H.d);
+        std::vector<int8_t> verdict((size_t)chunk);
+        std::vector<int64_t> pass_trial;
+        std::vector<double> pass_T;
+        for (int64_t t = 0; e == hipSuccess && t < trials; t += chunk)
+            e = ransac_device_chunk(H.d, t, std::min(chunk, trials - t), verdict.data(), nullptr, &pass_trial,
+                                    &pass_T, &I.hypothesis_ms);
+        const double t0 = ransac_now_ms();
+        std::vector<int64_t> good(pass_trial.size());
+        std::vector<double> err2(pass_trial.size());
+        if (e == hipSuccess) e = ransac_score_device(H.d, pass_T.data(), (int64_t)pass_trial.size(), max_dist, good.data(), err2.data());
+        if (e != hipSuccess) return ctx->fail(e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP,
+                                              std::string("registration_ransac_correspondence: ") + hipGetErrorString(e));
+        std::vector<double> fit(good.size()), rmse(good.size());
+        for (size_t i = 0; i < good.size(); i++) {
+            fit[i] = good[i] == 0 ? 0.0 : (double)good[i] / (double)K;
+            rmse[i] = good[i] == 0 ? 0.0 : std::sqrt(err2[i] / (double)good[i]);
+        }
+        const int64_t b = ransac_best(fit, rmse);
+        I.validation_ms = ransac_now_ms() - t0;
+        I.n_trials = trials;
+        I.n_validated = (int64_t)pass_trial.size();
+        if (b >= 0) {
+            I.best_trial = pass_trial[(size_t)b];
+            std::memcpy(result->transformation, &pass_T[(size_t)(16 * b)], 16 * sizeof(double));
+            result->fitness = fit[(size_t)b];
+            result->inlier_rmse = rmse[(size_t)b];
+            result->num_correspondences = good[(size_t)b];
+        }
+    }
+    if (info) *info = I;
     return VISMA_ICP_OK;
 }
 

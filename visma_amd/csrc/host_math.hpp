@@ -292,6 +292,28 @@ VISMA_HD NormalEq unpack_stats(const double *st)
     return e;
 }
 
+// R = U S V^T of Umeyama (Umeyama.h:139-152) for the cross-covariance sigma, and sum_i s_i S_i (:155-158), returned:
+// through the polar factor when det sigma > 0 and sigma is well conditioned (every registration of a real surface), else
+// through the SVD
+VISMA_HD double umeyama_rotation(const double sigma[9], double R[9])
+{
+    double strace;
+    if (polar_rotation3(sigma, R)) {
+        strace = 0.0;                                        // tr(R^T sigma) = s1 + s2 + s3
+        for (int i = 0; i < 9; i++) strace += R[i] * sigma[i];
+    } else {
+        const Svd3 d = svd3(sigma);
+        double S[3] = {1.0, 1.0, 1.0};
+        if (det3(d.U) * det3(d.V) < 0.0) S[2] = -1.0;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                R[i * 3 + j] = d.U[i * 3] * S[0] * d.V[j * 3] + d.U[i * 3 + 1] * S[1] * d.V[j * 3 + 1] +
+                               d.U[i * 3 + 2] * S[2] * d.V[j * 3 + 2];
+        strace = d.s[0] * S[0] + d.s[1] * S[1] + d.s[2] * S[2];
+    }
+    return strace;
+}
+
 // Closed-form least-squares rigid (optionally similarity) update for the
 // fixed correspondence set, from the moments.
 VISMA_HD Mat4 kabsch_from_stats(const double *st, bool with_scaling)
@@ -306,22 +328,8 @@ VISMA_HD Mat4 kabsch_from_stats(const double *st, bool with_scaling)
     for (int a = 0; a < 3; a++) { pm[a] = P[a] * inv; qm[a] = Q[a] * inv; }
     for (int a = 0; a < 3; a++)
         for (int b = 0; b < 3; b++) sigma[a * 3 + b] = e.M[a * 3 + b] * inv - qm[a] * pm[b];
-    // R = U S V^T (Umeyama.h:139-152) and sum_i s_i S_i (:155-158): through the polar factor when det sigma > 0 and
-    // sigma is well conditioned (every registration of a real surface), else through the SVD
-    double R[9], strace;
-    if (polar_rotation3(sigma, R)) {
-        strace = 0.0;                                        // tr(R^T sigma) = s1 + s2 + s3
-        for (int i = 0; i < 9; i++) strace += R[i] * sigma[i];
-    } else {
-        const Svd3 d = svd3(sigma);
-        double S[3] = {1.0, 1.0, 1.0};
-        if (det3(d.U) * det3(d.V) < 0.0) S[2] = -1.0;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++)
-                R[i * 3 + j] = d.U[i * 3] * S[0] * d.V[j * 3] + d.U[i * 3 + 1] * S[1] * d.V[j * 3 + 1] +
-                               d.U[i * 3 + 2] * S[2] * d.V[j * 3 + 2];
-        strace = d.s[0] * S[0] + d.s[1] * S[1] + d.s[2] * S[2];
-    }
+    double R[9];
+    const double strace = umeyama_rotation(sigma, R);
     double c = 1.0;
     if (with_scaling) {
         // tr(sum(|p|^2 I - p p^T)) = 2 sum |p|^2
@@ -552,8 +560,8 @@ struct FgrOption {                                     // FastGlobalRegistration
     int use_absolute_scale = 0, decrease_mu = 1, iteration_number = 64, maximum_tuple_count = 1000;
 };
 
-// Philox4x32-10 (Salmon et al., SC'11), the generator of mesh.hip's sampling kernel, on the host
-inline void philox4x32_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
+// Philox4x32-10 (Salmon et al., SC'11), the generator of mesh.hip's sampling kernel, on the host (and in ransac.hip)
+VISMA_HD void philox4x32_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
 {
     for (int r = 0; r < 10; r++) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
@@ -567,7 +575,7 @@ inline void philox4x32_host(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, 
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-inline double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
+VISMA_HD double norm3(double x, double y, double z) { return sqrt(x * x + y * y + z * z); }
 
 // NormalizePointCloud (:189-240) on copies: cloud k minus its mean, both divided by scale_global
 struct FgrNormalized {

@@ -611,6 +611,30 @@ hipError_t compute_fpfh_device(const double *h_xyz, int64_t n, const double *h_n
 // +inf where no distance is finite; dim in [1, 64].  h_d2 and kernel_ms may be NULL.
 hipError_t match_features_device(const double *h_fa, int64_t na, const double *h_fb, int64_t nb, int dim, int32_t *h_nn,
                                  double *h_d2, double *kernel_ms, hipStream_t stream);
+// ---- RANSAC global registration (ransac.hip; the arithmetic of one trial: ransac.hpp) ----
+struct RansacProblem {                                 // host arrays
+    const double *src = nullptr; int64_t ns = 0;       // ns x 3
+    const double *tgt = nullptr; int64_t nt = 0;
+    const double *src_n = nullptr, *tgt_n = nullptr;   // normals (both or none are used)
+    const int32_t *pair_src = nullptr;                 // pair k = (pair_src[k], pair_tgt[k]); NULL: (k, pair_tgt[k])
+    const int32_t *pair_tgt = nullptr;                 // in [-1, nt): -1 = no partner
+    int64_t n_pairs = 0;
+    const int32_t *draws = nullptr; int64_t n_draw_trials = 0;   // ransac_n draws per trial, or NULL: seeded
+    uint64_t seed = 0;
+    int ransac_n = 4;
+    double edge = 0.0, dist = 0.0, cos_normal = 0.0;
+    int use_edge = 0, use_dist = 0, use_normal = 0;
+};
+struct RansacDevice;                                   // the problem resident on the device + the buffers of one chunk
+hipError_t ransac_device_create(const RansacProblem &p, int64_t chunk_cap, hipStream_t stream, RansacDevice **out);
+void ransac_device_destroy(RansacDevice *D);
+// trials [t0, t0 + n), n <= chunk_cap: h_verdict[n]
+// (kRansacPass / Before / After), h_T_all (may be NULL) n x 16 with zeros where nothing was solved; the trials that passed
+// are appended in trial order to pass_trial / pass_T (16 doubles each; both may be NULL); *ms (may be NULL) += device time
+hipError_t ransac_device_chunk(RansacDevice *D, int64_t t0, int64_t n, int8_t *h_verdict, double *h_T_all,
+                               std::vector<int64_t> *pass_trial, std::vector<double> *pass_T, double *ms);
+// the whole pair list scored under n transforms (h_T: n x 16): pairs with dis2 < max_dist^2 and the sum of their dis2
+hipError_t ransac_score_device(RansacDevice *D, const double *h_T, int64_t n, double max_dist, int64_t *h_good, double *h_err2);
 constexpr int kColoredRow = 32;                       // doubles per partial row: 31 accumulators (K, sum |d|^2, 21 + 6, the two costs)
 constexpr int kColoredPublished = kNStats + 2;         // granules to the host: 38 statistics, sum r_g^2, sum r_c^2
 struct ColoredArgs : PairPassArgs {
