@@ -15,3 +15,5 @@
 #include "Registration/Feature.h"
 #include "Registration/FastGlobalRegistration.h"
 #include "Registration/CorrespondenceChecker.h"
+#include "Registration/PoseGraph.h"
+#include "Registration/GlobalOptimization.h"

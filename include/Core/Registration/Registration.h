@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "TransformationEstimation.h"
+#include "../Utility/Eigen.h"
 
 namespace open3d {
 
@@ -65,5 +66,11 @@ inline RegistrationResult RegistrationRANSACBasedOnFeatureMatching(
     double max_correspondence_distance, const TransformationEstimation &estimation = TransformationEstimationPointToPoint(false),
     int ransac_n = 4, const std::vector<std::reference_wrapper<const CorrespondenceChecker>> &checkers = {},
     const RANSACConvergenceCriteria &criteria = RANSACConvergenceCriteria());
+
+// The information matrix of a pose-graph edge (Registration.h:132-135): sum G^T G over the pairs of a pass at
+// `transformation` -- without the identity terms the reference adds (visma_icp.h states the deviation)
+inline Eigen::Matrix6d GetInformationMatrixFromPointClouds(const PointCloud &source, const PointCloud &target,
+                                                           double max_correspondence_distance,
+                                                           const Eigen::Matrix4d &transformation);
 
 }  // namespace open3d

@@ -1037,6 +1037,114 @@ VISMA_ICP_API int visma_icp_registration_ransac_correspondence(visma_icp_ctx *ct
                                                                const int32_t *draws, int64_t n_draw_trials,
                                                                visma_icp_result *result, visma_icp_ransac_info *info);
 
+/* ---- multiway registration: the information matrix of an edge, pose-graph optimisation ------------------------------
+ * (Choi, Zhou, Koltun: "Robust Reconstruction of Indoor Scenes", CVPR 2015; Kuemmerle et al.: "g2o", ICRA 2011; the
+ * reference's GetInformationMatrixFromPointClouds, Registration.cpp:352-413, and GlobalOptimization.cpp.)
+ *
+ * N fragments are registered pairwise (odometry edges from ICP, loop closures from FGR or RANSAC); every edge is
+ * weighted by its information matrix; the line-process optimisation drops the false loop closures and settles all
+ * poses at once.
+ *
+ * The information matrix of an edge with transformation T: over the K pairs (i, j) of a nearest-neighbour pass at T
+ * inside max_dist, with q = t_j the TARGET point in the caller's frame,
+ *     G = [ 0  z -y 1 0 0 ;  -z 0 x 0 1 0 ;  y -x 0 0 0 1 ]       out = sum G^T G   (6 x 6, row-major)
+ * i.e. [[sum hat(q)^T hat(q), sum hat(q)^T], [sum hat(q), K I]].  The kernel (information.hip) forms ten f64 sums
+ * K, sum x y z, sum xx yy zz xy xz yz from q = (stored point) + (the context's centre) and the host lays them out.
+ *
+ * DEVIATION from the reference, on purpose: the reference starts GTG at the identity AND starts every OpenMP thread's
+ * private copy at the identity, so it returns sum G^T G + (1 + P) I with P its number of threads (502 with one thread,
+ * 504 with three, for K = 500).  This library returns the pure sum: out[35] == K exactly, which is what the
+ * line-process weight of visma_icp_global_optimization reads it as, and the result does not depend on a thread count.
+ *
+ * No floating-point atomics: a run is bit-identical to itself, and an edge's matrix does not depend on what else a call
+ * computed.  K = 0: the zero matrix, VISMA_ICP_OK.  A non-finite entry of T: the zero matrix and *k = 0 without a search
+ * (as the RANSAC validation treats such a pose).  Non-finite points are what the search makes of them, no error: a
+ * non-finite SOURCE point has no pair (the matrix is that of the other pairs); a non-finite TARGET coordinate makes the
+ * centroid visma_icp_set_clouds_f64 centres both clouds on non-finite, so nothing has a pair: K = 0, the zero matrix.
+ * Clouds not set: VISMA_ICP_ERR_STATE.
+ * Sharded contexts: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_information_matrix(visma_icp_ctx *ctx, const double T[16], double max_dist, double out[36],
+                                               int64_t *k);
+/* The same over the pairs of the last visma_icp_nn_pass (as visma_icp_reduce_gicp reduces them).  Before a pass:
+ * VISMA_ICP_ERR_STATE. */
+VISMA_ICP_API int visma_icp_reduce_information(visma_icp_ctx *ctx, double out[36]);
+/* Every edge of a pose graph in one call: probs[i].src_xyz / tgt_xyz are the edge's clouds, probs[i].init its
+ * transformation, probs[i].max_dist its radius; out is n x 36, k (may be NULL) n counts.  A host loop over the edges
+ * (upload, search, reduce; one reduction launch per edge): edges that pass the same target (pointer and count) are
+ * handled one after the other and the target is uploaded once for them.  ONLY the upload is shared: a new source
+ * invalidates the target's search grid on the engine, so every edge builds its own.  Every out[i] is bit-equal to what
+ * visma_icp_set_clouds_f64 + visma_icp_information_matrix return for that edge, in whatever order the edges come.
+ * Afterwards the context holds the clouds of the last edge handled (visma_icp_get_cloud_sizes: which sizes). */
+VISMA_ICP_API int visma_icp_information_matrices(visma_icp_ctx *ctx, const visma_icp_problem *probs, int n, double *out,
+                                                 int64_t *k);
+/* The number of points of the source and of the target the context holds (0 for a cloud that is not set). */
+VISMA_ICP_API int visma_icp_get_cloud_sizes(visma_icp_ctx *ctx, int64_t *ns, int64_t *nt);
+
+/* The pose graph on plain arrays (pure functions; no ctx, no GPU).  Node i has a 4 x 4 pose (row-major, node to world);
+ * an edge says: transformation maps the SOURCE node's cloud onto the TARGET node's (PoseGraph.h:52-86).  Odometry edges
+ * are certain (uncertain = 0), loop closures uncertain; confidence is the line-process value in [0, 1]. */
+typedef struct {
+    int32_t source, target;
+    double transformation[16];
+    double information[36];
+    int32_t uncertain;
+    double confidence;
+} visma_icp_pose_graph_edge;
+typedef struct {                       /* GlobalOptimizationOption; NULL where one is taken: 0.075, 0.25, 1.0, -1 */
+    double max_correspondence_distance;    /* < 0: 0.075 */
+    double edge_prune_threshold;           /* outside [0, 1]: 0.25 */
+    double preference_loop_closure;        /* < 0: 1.0 */
+    int32_t reference_node;                /* the node whose pose is the same after the optimisation; outside the graph: none */
+} visma_icp_global_optimization_option;
+typedef struct {                       /* GlobalOptimizationConvergenceCriteria; NULL: 100, 1e-6 x 4, 20, 2/3, 1/3 */
+    int32_t max_iteration;
+    double min_relative_increment;
+    double min_relative_residual_increment;
+    double min_right_term;
+    double min_residual;
+    int32_t max_iteration_lm;
+    double upper_scale_factor;             /* outside [0, 1]: 2/3 */
+    double lower_scale_factor;             /* outside [0, 1]: 1/3 */
+} visma_icp_global_optimization_criteria;
+#define VISMA_ICP_GLOBAL_GAUSS_NEWTON 0
+#define VISMA_ICP_GLOBAL_LEVENBERG_MARQUARDT 1
+/* The clamping of the reference's constructors, in place. */
+VISMA_ICP_API int visma_icp_global_optimization_option_clamp(visma_icp_global_optimization_option *opt);
+VISMA_ICP_API int visma_icp_global_optimization_criteria_clamp(visma_icp_global_optimization_criteria *crit);
+/* 1: every consecutive node pair (i, i + 1) has an edge and every edge names nodes of the graph; 0 otherwise
+ * (ValidatePoseGraph); -VISMA_ICP_ERR_INVALID for NULL or negative arguments. */
+VISMA_ICP_API int visma_icp_pose_graph_validate(int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges);
+/* zeta (6 per edge): the linearised misalignment X^-1 Tt^-1 Ts of every edge (ComputeZeta).  An edge naming a node
+ * outside the graph: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_pose_graph_zeta(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges,
+                                            int n_edges, double *zeta_out);
+/* H (6n x 6n, row-major) and b (6n) of the Gauss-Newton step at the given poses with the edges' confidences
+ * (ComputeLinearSystem). */
+VISMA_ICP_API int visma_icp_pose_graph_linear_system(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges,
+                                                     int n_edges, double *H_out, double *b_out);
+/* ONE optimisation (GlobalOptimizationMethod::OptimizePoseGraph): no validation, no pruning, no compensation; poses and
+ * the edges' confidences are updated.  An edge naming a node outside the graph: VISMA_ICP_ERR_INVALID.
+ * Gauss-Newton solves the SINGULAR system of a graph without a fixed node, as the reference does: the rigid motion common
+ * to all poses it returns is rounding noise there and here (0.13 between two builds on a 6-node graph); the poses
+ * relative to one another are not.  Levenberg-Marquardt's damping fixes the common motion. */
+VISMA_ICP_API int visma_icp_pose_graph_optimize(double *poses, int n_nodes, visma_icp_pose_graph_edge *edges, int n_edges,
+                                                int method, const visma_icp_global_optimization_criteria *criteria,
+                                                const visma_icp_global_optimization_option *option);
+/* The whole of GlobalOptimization(): validation (an invalid graph comes back untouched, with VISMA_ICP_OK as the reference
+ * returns nothing: ask visma_icp_pose_graph_validate),
+ * the first optimisation, pruning (an uncertain edge with confidence <= edge_prune_threshold is dropped; the edges that
+ * stay are moved to the front of `edges` in their order and *n_edges is their number), the second optimisation, the
+ * compensation of reference_node.  Both methods restate the reference's stopping tests in the reference's order: the
+ * right-hand side's largest coefficient (not its absolute value) below min_right_term, the relative increment, the
+ * relative residual increment, the residual, the iteration limits; Levenberg-Marquardt with tau = 1e-5, rho with its
+ * + 1e-3 and the scale factor clamped to [lower, upper].  Linear solves: a dense L D L^T with diagonal pivoting
+ * throughout (the reference's sparse Cholesky inside Levenberg-Marquardt is an implementation detail).  information[35]
+ * is read as the edge's number of correspondences (see the deviation above).  criteria / option may be NULL and are
+ * clamped as the reference's constructors clamp.  poses: n_nodes x 16, in and out. */
+VISMA_ICP_API int visma_icp_global_optimization(double *poses, int n_nodes, visma_icp_pose_graph_edge *edges, int *n_edges,
+                                                int method, const visma_icp_global_optimization_criteria *criteria,
+                                                const visma_icp_global_optimization_option *option);
+
 /* Point -> triangle-mesh squared distance, face and closest point for np query
  * points: what igl::AABB::squared_distance returns inside feh::MeasureSurfaceError
  * (include/geometry.h:123-136).  face / closest may be NULL; exact ties go to the

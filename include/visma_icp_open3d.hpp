@@ -32,6 +32,11 @@
 //                                      registration WITHOUT an initial pose (O3D/Core/Registration/Feature.h,
 //                                      FastGlobalRegistration.h): FPFH of both clouds, matched, tuple-tested and
 //                                      optimised; its result is the `init` of any RegistrationICP above
+//   open3d::cicp::GetInformationMatrixFromPointClouds / cicp::GlobalOptimization
+//                                      multiway registration (O3D/Core/Registration/Registration.h:132-135,
+//                                      GlobalOptimization.h): the information matrix of an edge on the GPU -- one call
+//                                      for every edge of a PoseGraph --, then the line-process pose-graph optimisation
+//                                      on the host.  WITHOUT the identity terms Open3D 0.3.0 adds to the matrix
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -57,6 +62,9 @@
 #include <Core/Registration/Feature.h>
 #include <Core/Registration/FastGlobalRegistration.h>
 #include <Core/Registration/CorrespondenceChecker.h>
+#include <Core/Registration/PoseGraph.h>
+#include <Core/Registration/GlobalOptimizationConvergenceCriteria.h>
+#include <Core/Registration/GlobalOptimizationMethod.h>
 
 #include "visma_icp.h"
 #include "visma_io.h"
@@ -1262,6 +1270,123 @@ inline RegistrationResult RegistrationRANSACBasedOnCorrespondence(
                                                          criteria, 0);
 }
 
+// open3d::GetInformationMatrixFromPointClouds (Registration.cpp:355-413) on the GPU: sum G^T G over the pairs of a pass at
+// `transformation`, G = [-hat(q) | I] with q the target point.  NOT the reference's value: it adds (1 + P) I, P its number
+// of OpenMP threads; this is the pure sum, (5, 5) the number of pairs (visma_icp.h).
+inline Eigen::Matrix6d GetInformationMatrixFromPointClouds(const PointCloud &source, const PointCloud &target,
+                                                           double max_correspondence_distance,
+                                                           const Eigen::Matrix4d &transformation)
+{
+    Eigen::Matrix6d G = Eigen::Matrix6d::Zero();
+    if (source.points_.empty() || target.points_.empty() || !(max_correspondence_distance > 0.0)) return G;
+    visma_icp_ctx *ctx = detail::upload(source, target, false, max_correspondence_distance);
+    double T[16], out[36];
+    detail::to_rowmajor(transformation, T);
+    detail::check(ctx, visma_icp_information_matrix(ctx, T, max_correspondence_distance, out, nullptr), "visma_icp_information_matrix");
+    for (int i = 0; i < 6; i++)
+        for (int j = 0; j < 6; j++) G(i, j) = out[i * 6 + j];
+    return G;
+}
+
+// ... for every edge of a pose graph in one call: clouds[i] is the cloud of node i; edge e gets
+// information_ = GetInformationMatrixFromPointClouds(clouds[source], clouds[target], max_distance, e.transformation_).
+// Edges with the same target node share its upload.  An edge naming no cloud, or an empty cloud, keeps its matrix.
+inline void GetInformationMatrixFromPointClouds(PoseGraph &pose_graph, const std::vector<const PointCloud *> &clouds,
+                                                double max_correspondence_distance)
+{
+    std::vector<visma_icp_problem> probs;
+    std::vector<size_t> which;
+    for (size_t e = 0; e < pose_graph.edges_.size(); e++) {
+        const PoseGraphEdge &t = pose_graph.edges_[e];
+        if (t.source_node_id_ < 0 || t.target_node_id_ < 0 || (size_t)t.source_node_id_ >= clouds.size() ||
+            (size_t)t.target_node_id_ >= clouds.size() || !clouds[t.source_node_id_] || !clouds[t.target_node_id_]) continue;
+        const PointCloud &s = *clouds[t.source_node_id_], &q = *clouds[t.target_node_id_];
+        if (s.points_.empty() || q.points_.empty()) continue;
+        visma_icp_problem p;
+        p.src_xyz = detail::xyz(s.points_); p.ns = (int64_t)s.points_.size();
+        p.tgt_xyz = detail::xyz(q.points_); p.nt = (int64_t)q.points_.size();
+        detail::to_rowmajor(t.transformation_, p.init);
+        p.max_dist = max_correspondence_distance;
+        probs.push_back(p);
+        which.push_back(e);
+    }
+    if (probs.empty() || !(max_correspondence_distance > 0.0)) return;
+    std::vector<double> out(probs.size() * 36);
+    visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
+    detail::check(ctx, visma_icp_information_matrices(ctx, probs.data(), (int)probs.size(), out.data(), nullptr),
+                  "visma_icp_information_matrices");
+    for (size_t k = 0; k < which.size(); k++)
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) pose_graph.edges_[which[k]].information_(i, j) = out[k * 36 + i * 6 + j];
+}
+
+namespace detail {
+
+// a PoseGraph through visma_icp_global_optimization (whole) or visma_icp_pose_graph_optimize (one optimisation)
+inline void run_pose_graph(PoseGraph &g, bool whole, int method, const GlobalOptimizationConvergenceCriteria &c,
+                           const GlobalOptimizationOption &o)
+{
+    std::vector<double> poses(g.nodes_.size() * 16);
+    for (size_t i = 0; i < g.nodes_.size(); i++) to_rowmajor(g.nodes_[i].pose_, &poses[i * 16]);
+    std::vector<visma_icp_pose_graph_edge> edges(g.edges_.size());
+    for (size_t e = 0; e < g.edges_.size(); e++) {
+        const PoseGraphEdge &t = g.edges_[e];
+        edges[e].source = t.source_node_id_; edges[e].target = t.target_node_id_;
+        to_rowmajor(t.transformation_, edges[e].transformation);
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) edges[e].information[i * 6 + j] = t.information_(i, j);
+        edges[e].uncertain = t.uncertain_ ? 1 : 0;
+        edges[e].confidence = t.confidence_;
+    }
+    const visma_icp_global_optimization_criteria cc = {c.max_iteration_, c.min_relative_increment_, c.min_relative_residual_increment_,
+                                                       c.min_right_term_, c.min_residual_, c.max_iteration_lm_,
+                                                       c.upper_scale_factor_, c.lower_scale_factor_};
+    const visma_icp_global_optimization_option oo = {o.max_correspondence_distance_, o.edge_prune_threshold_,
+                                                     o.preference_loop_closure_, o.reference_node_};
+    int ne = (int)edges.size();
+    const int rc = whole ? visma_icp_global_optimization(poses.data(), (int)g.nodes_.size(), edges.data(), &ne, method, &cc, &oo)
+                         : visma_icp_pose_graph_optimize(poses.data(), (int)g.nodes_.size(), edges.data(), ne, method, &cc, &oo);
+    if (rc != VISMA_ICP_OK) {
+        std::fprintf(stderr, "Error: pose-graph optimisation: an edge names a node outside the graph.\n");
+        return;
+    }
+    for (size_t i = 0; i < g.nodes_.size(); i++) g.nodes_[i].pose_ = from_rowmajor(&poses[i * 16]);
+    std::vector<PoseGraphEdge> kept;                         // the surviving edges as the library returns them, member by member
+    for (int k = 0; k < ne; k++) {
+        Eigen::Matrix6d info;
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) info(i, j) = edges[k].information[i * 6 + j];
+        kept.push_back(PoseGraphEdge(edges[k].source, edges[k].target, from_rowmajor(edges[k].transformation), info,
+                                     edges[k].uncertain != 0, edges[k].confidence));
+    }
+    g.edges_.swap(kept);
+}
+
+inline int pose_graph_method(const GlobalOptimizationMethod &method)
+{
+    return dynamic_cast<const GlobalOptimizationGaussNewton *>(&method) ? VISMA_ICP_GLOBAL_GAUSS_NEWTON
+                                                                        : VISMA_ICP_GLOBAL_LEVENBERG_MARQUARDT;
+}
+
+}  // namespace detail
+
+// open3d::GlobalOptimization (GlobalOptimization.cpp:641-662) on the host: both methods restated test by test
+// (visma_icp.h).  `method`: a GlobalOptimizationGaussNewton selects Gauss-Newton, any other Levenberg-Marquardt.
+inline void GlobalOptimization(PoseGraph &pose_graph, const GlobalOptimizationMethod &method,
+                               const GlobalOptimizationConvergenceCriteria &criteria = GlobalOptimizationConvergenceCriteria(),
+                               const GlobalOptimizationOption &option = GlobalOptimizationOption())
+{
+    detail::run_pose_graph(pose_graph, true, detail::pose_graph_method(method), criteria, option);
+}
+
+// ... with the reference's default method.  (No default argument above: the real Open3D headers declare the method
+// classes without bodies a header-only adapter could construct.)
+inline void GlobalOptimization(PoseGraph &pose_graph)
+{
+    detail::run_pose_graph(pose_graph, true, VISMA_ICP_GLOBAL_LEVENBERG_MARQUARDT, GlobalOptimizationConvergenceCriteria(),
+                           GlobalOptimizationOption());
+}
+
 // open3d::ComputePointCloudToPointCloudDistance (O3D/Core/Geometry/PointCloud.cpp:122-142) on the GPU: for every
 // source point the distance to the nearest target point, no radius, bit for bit the reference's (0 for every
 // point when the target is empty).
@@ -1560,6 +1685,38 @@ inline Eigen::Matrix4d TransformationEstimationPointToPlane::ComputeTransformati
 inline std::shared_ptr<PointCloud> VoxelDownSample(const PointCloud &input, double voxel_size)
 {
     return cicp::VoxelDownSample(input, voxel_size);
+}
+inline Eigen::Matrix6d GetInformationMatrixFromPointClouds(const PointCloud &source, const PointCloud &target,
+                                                           double max_correspondence_distance,
+                                                           const Eigen::Matrix4d &transformation)
+{
+    return cicp::GetInformationMatrixFromPointClouds(source, target, max_correspondence_distance, transformation);
+}
+inline void GlobalOptimizationGaussNewton::OptimizePoseGraph(PoseGraph &pose_graph,
+                                                             const GlobalOptimizationConvergenceCriteria &criteria,
+                                                             const GlobalOptimizationOption &option) const
+{
+    cicp::detail::run_pose_graph(pose_graph, false, VISMA_ICP_GLOBAL_GAUSS_NEWTON, criteria, option);
+}
+inline void GlobalOptimizationLevenbergMarquardt::OptimizePoseGraph(PoseGraph &pose_graph,
+                                                                    const GlobalOptimizationConvergenceCriteria &criteria,
+                                                                    const GlobalOptimizationOption &option) const
+{
+    cicp::detail::run_pose_graph(pose_graph, false, VISMA_ICP_GLOBAL_LEVENBERG_MARQUARDT, criteria, option);
+}
+inline void GlobalOptimization(PoseGraph &pose_graph, const GlobalOptimizationMethod &method,
+                               const GlobalOptimizationConvergenceCriteria &criteria, const GlobalOptimizationOption &option)
+{
+    cicp::GlobalOptimization(pose_graph, method, criteria, option);
+}
+inline std::shared_ptr<PoseGraph> CreatePoseGraphWithoutInvalidEdges(const PoseGraph &pose_graph,
+                                                                     const GlobalOptimizationOption &option)
+{
+    std::shared_ptr<PoseGraph> pruned = std::make_shared<PoseGraph>();
+    pruned->nodes_ = pose_graph.nodes_;
+    for (const PoseGraphEdge &t : pose_graph.edges_)
+        if (!t.uncertain_ || t.confidence_ > option.edge_prune_threshold_) pruned->edges_.push_back(t);
+    return pruned;
 }
 inline RegistrationResult EvaluateRegistration(const PointCloud &source, const PointCloud &target,
                                                double max_correspondence_distance,

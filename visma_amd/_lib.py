@@ -61,6 +61,25 @@ class CProblem(C.Structure):
                 ("init", C.c_double * 16), ("max_dist", C.c_double)]
 
 
+class CPoseGraphEdge(C.Structure):
+    """visma_icp_pose_graph_edge"""
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("transformation", C.c_double * 16),
+                ("information", C.c_double * 36), ("uncertain", C.c_int32), ("confidence", C.c_double)]
+
+
+class CGlobalOptimizationOption(C.Structure):
+    """visma_icp_global_optimization_option"""
+    _fields_ = [("max_correspondence_distance", C.c_double), ("edge_prune_threshold", C.c_double),
+                ("preference_loop_closure", C.c_double), ("reference_node", C.c_int32)]
+
+
+class CGlobalOptimizationCriteria(C.Structure):
+    """visma_icp_global_optimization_criteria"""
+    _fields_ = [("max_iteration", C.c_int32), ("min_relative_increment", C.c_double),
+                ("min_relative_residual_increment", C.c_double), ("min_right_term", C.c_double), ("min_residual", C.c_double),
+                ("max_iteration_lm", C.c_int32), ("upper_scale_factor", C.c_double), ("lower_scale_factor", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _dp, C.c_int)
 MINREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_int64)
 ENG_SET = C.CFUNCTYPE(C.c_int, C.c_void_p, _fp, C.c_int64)
@@ -262,6 +281,21 @@ def _bind(L):
         L.visma_icp_registration_ransac_correspondence.argtypes = [C.c_void_p, _dp, C.c_int64, _dp, C.c_int64, _ip, _ip, C.c_int64,
                                                                    C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, _ip, C.c_int64,
                                                                    C.POINTER(CResult), _ri]
+    if hasattr(L, "visma_icp_information_matrix"):       # (A/B runs load older builds through VISMA_ICP_LIB)
+        _ep = C.POINTER(CPoseGraphEdge)
+        L.visma_icp_information_matrix.argtypes = [C.c_void_p, _dp, C.c_double, _dp, C.POINTER(C.c_int64)]
+        L.visma_icp_reduce_information.argtypes = [C.c_void_p, _dp]
+        L.visma_icp_information_matrices.argtypes = [C.c_void_p, C.POINTER(CProblem), C.c_int, _dp, C.POINTER(C.c_int64)]
+        L.visma_icp_global_optimization_option_clamp.argtypes = [C.POINTER(CGlobalOptimizationOption)]
+        L.visma_icp_global_optimization_criteria_clamp.argtypes = [C.POINTER(CGlobalOptimizationCriteria)]
+        L.visma_icp_pose_graph_validate.argtypes = [C.c_int, _ep, C.c_int]
+        L.visma_icp_pose_graph_zeta.argtypes = [_dp, C.c_int, _ep, C.c_int, _dp]
+        L.visma_icp_pose_graph_linear_system.argtypes = [_dp, C.c_int, _ep, C.c_int, _dp, _dp]
+        L.visma_icp_global_optimization.argtypes = [_dp, C.c_int, _ep, C.POINTER(C.c_int), C.c_int,
+                                                    C.POINTER(CGlobalOptimizationCriteria), C.POINTER(CGlobalOptimizationOption)]
+        L.visma_icp_pose_graph_optimize.argtypes = [_dp, C.c_int, _ep, C.c_int, C.c_int,
+                                                    C.POINTER(CGlobalOptimizationCriteria), C.POINTER(CGlobalOptimizationOption)]
+        L.visma_icp_get_cloud_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -515,6 +549,122 @@ def ransac_hypotheses_host(src, tgt, pair_tgt, option=None, seed=0, draws=None, 
     if rc != OK:
         raise IcpError(rc, "ransac_hypotheses_host: bad arguments")
     return verdict[:int(n_trials)].copy(), T[:int(n_trials)].reshape(-1, 4, 4).copy()
+
+
+class PoseGraphEdge:
+    """An edge of a pose graph (Open3D's PoseGraphEdge): `transformation` maps the source node's cloud onto the target
+    node's; loop closures are `uncertain`; `confidence` is the line-process value."""
+
+    def __init__(self, source, target, transformation=None, information=None, uncertain=False, confidence=1.0):
+        self.source = int(source); self.target = int(target)
+        self.transformation = _f64(np.eye(4) if transformation is None else transformation, (4, 4)).copy()
+        self.information = _f64(np.eye(6) if information is None else information, (6, 6)).copy()
+        self.uncertain = bool(uncertain)
+        self.confidence = float(confidence)
+
+    def __repr__(self):
+        return "PoseGraphEdge(%d -> %d, uncertain=%s, confidence=%.6g)" % (self.source, self.target, self.uncertain, self.confidence)
+
+
+def global_optimization_option(max_correspondence_distance=0.075, edge_prune_threshold=0.25, preference_loop_closure=1.0,
+                               reference_node=-1):
+    """GlobalOptimizationOption, clamped as the reference's constructor clamps."""
+    o = CGlobalOptimizationOption(float(max_correspondence_distance), float(edge_prune_threshold), float(preference_loop_closure),
+                                  int(reference_node))
+    load().visma_icp_global_optimization_option_clamp(C.byref(o))
+    return o
+
+
+def global_optimization_criteria(max_iteration=100, min_relative_increment=1e-6, min_relative_residual_increment=1e-6,
+                                 min_right_term=1e-6, min_residual=1e-6, max_iteration_lm=20, upper_scale_factor=2. / 3.,
+                                 lower_scale_factor=1. / 3.):
+    """GlobalOptimizationConvergenceCriteria, clamped as the reference's constructor clamps."""
+    c = CGlobalOptimizationCriteria(int(max_iteration), float(min_relative_increment), float(min_relative_residual_increment),
+                                    float(min_right_term), float(min_residual), int(max_iteration_lm), float(upper_scale_factor),
+                                    float(lower_scale_factor))
+    load().visma_icp_global_optimization_criteria_clamp(C.byref(c))
+    return c
+
+
+def _pose_graph_args(poses, edges):
+    P = _f64(poses, (-1, 16)).copy()
+    arr = (CPoseGraphEdge * max(len(edges), 1))()
+    for i, e in enumerate(edges):
+        arr[i].source = e.source; arr[i].target = e.target
+        arr[i].transformation = (C.c_double * 16)(*_f64(e.transformation, (16,)))
+        arr[i].information = (C.c_double * 36)(*_f64(e.information, (36,)))
+        arr[i].uncertain = 1 if e.uncertain else 0
+        arr[i].confidence = float(e.confidence)
+    return P, arr
+
+
+def pose_graph_validate(n_nodes, edges):
+    """ValidatePoseGraph: every consecutive node pair has an edge and every edge names nodes of the graph."""
+    _, arr = _pose_graph_args(np.zeros((0, 16)), edges)
+    rc = load().visma_icp_pose_graph_validate(int(n_nodes), arr, len(edges))
+    if rc < 0 or rc > 1:
+        raise IcpError(rc, "pose_graph_validate: bad arguments")
+    return bool(rc)
+
+
+def pose_graph_zeta(poses, edges):
+    """The linearised misalignment of every edge at the given poses (n x 4 x 4) -> n_edges x 6 (host only)."""
+    P, arr = _pose_graph_args(poses, edges)
+    z = np.zeros((max(len(edges), 1), 6))
+    rc = load().visma_icp_pose_graph_zeta(_p(P, _dp), len(P), arr, len(edges), _p(z, _dp))
+    if rc != OK:
+        raise IcpError(rc, "pose_graph_zeta: bad arguments")
+    return z[:len(edges)]
+
+
+def pose_graph_linear_system(poses, edges):
+    """H (6n x 6n) and b (6n) of the Gauss-Newton step at the given poses with the edges' confidences (host only)."""
+    P, arr = _pose_graph_args(poses, edges)
+    n = 6 * len(P)
+    H = np.zeros((max(n, 1), max(n, 1))); b = np.zeros(max(n, 1))
+    rc = load().visma_icp_pose_graph_linear_system(_p(P, _dp), len(P), arr, len(edges), _p(H, _dp), _p(b, _dp))
+    if rc != OK:
+        raise IcpError(rc, "pose_graph_linear_system: bad arguments")
+    return (H[:n, :n], b[:n]) if n else (np.zeros((0, 0)), np.zeros(0))
+
+
+_GLOBAL_METHODS = {"gn": 0, "gauss_newton": 0, "gauss-newton": 0, "lm": 1, "levenberg_marquardt": 1, "levenberg-marquardt": 1}
+
+
+def pose_graph_optimize(poses, edges, method="lm", criteria=None, option=None):
+    """ONE optimisation of a pose graph (GlobalOptimizationMethod::OptimizePoseGraph; host only): no validation, no pruning,
+    no compensation of the reference node -> (poses, the edges with their new confidences)."""
+    m = _GLOBAL_METHODS.get(method.lower()) if isinstance(method, str) else int(method)
+    if m not in (0, 1):
+        raise ValueError("pose_graph_optimize: method is 'gn' or 'lm'")
+    P, arr = _pose_graph_args(poses, edges)
+    rc = load().visma_icp_pose_graph_optimize(_p(P, _dp), len(P), arr, len(edges), m,
+                                              C.byref(criteria) if criteria is not None else None,
+                                              C.byref(option) if option is not None else None)
+    if rc != OK:
+        raise IcpError(rc, "pose_graph_optimize: bad arguments")
+    out = [PoseGraphEdge(arr[i].source, arr[i].target, np.array(arr[i].transformation[:]), np.array(arr[i].information[:]),
+                         arr[i].uncertain != 0, arr[i].confidence) for i in range(len(edges))]
+    return P.reshape(-1, 4, 4), out
+
+
+def global_optimization(poses, edges, method="lm", criteria=None, option=None):
+    """Open3D's GlobalOptimization on a pose graph (host only): poses n x 4 x 4, edges PoseGraphEdge objects ->
+    (poses, the edges that survive the pruning with their confidences).  An invalid graph (pose_graph_validate) comes
+    back unchanged."""
+    m = _GLOBAL_METHODS.get(method.lower()) if isinstance(method, str) else int(method)
+    if m not in (0, 1):
+        raise ValueError("global_optimization: method is 'gn' or 'lm'")
+    P, arr = _pose_graph_args(poses, edges)
+    ne = C.c_int(len(edges))
+    rc = load().visma_icp_global_optimization(_p(P, _dp), len(P), arr, C.byref(ne), m,
+                                              C.byref(criteria) if criteria is not None else None,
+                                              C.byref(option) if option is not None else None)
+    if rc != OK:
+        raise IcpError(rc, "global_optimization: bad arguments")
+    out = [PoseGraphEdge(arr[i].source, arr[i].target, np.array(arr[i].transformation[:]), np.array(arr[i].information[:]),
+                         arr[i].uncertain != 0, arr[i].confidence) for i in range(ne.value)]
+    return P.reshape(-1, 4, 4), out
 
 
 class Result:
@@ -831,6 +981,45 @@ class Context:
         r = Result(out)
         r.colored = ColoredInfo(info)
         return r
+
+    def information_matrix(self, T=None, max_dist=0.05):
+        """The information matrix of the edge T between the context's clouds (Choi et al. 2015): sum G^T G over the pairs
+        of a pass at T inside max_dist, G = [-hat(q) | I], q the target point -> (6 x 6, K).  Without the identity
+        terms of Open3D 0.3.0: [5, 5] == K."""
+        T = _f64(np.eye(4) if T is None else T, (16,))
+        out = np.empty(36); k = C.c_int64(0)
+        self._chk(self.L.visma_icp_information_matrix(self._h, _p(T, _dp), float(max_dist), _p(out, _dp), C.byref(k)))
+        return out.reshape(6, 6), k.value
+
+    def reduce_information(self):
+        """The information matrix over the pairs of the last nn_pass -> 6 x 6."""
+        out = np.empty(36)
+        self._chk(self.L.visma_icp_reduce_information(self._h, _p(out, _dp)))
+        return out.reshape(6, 6)
+
+    def information_matrices(self, problems):
+        """Every edge of a pose graph in one call.  problems: (src, tgt, T, radius) tuples; tuples that pass the same
+        target array share its upload -> (n x 6 x 6, K per edge).  Each matrix is bit-equal to set_clouds_f64 +
+        information_matrix for that edge."""
+        n = len(problems)
+        arr = (CProblem * max(n, 1))(); keep = {}
+
+        def once(a):                                     # one C array per Python array: the library groups by pointer
+            if id(a) not in keep:
+                keep[id(a)] = (a, _f64(a, (-1, 3)))
+            return keep[id(a)][1]
+        for i, (src, tgt, init, r) in enumerate(problems):
+            s = once(src); t = once(tgt)
+            arr[i].src_xyz = _p(s, _dp); arr[i].ns = len(s)
+            arr[i].tgt_xyz = _p(t, _dp); arr[i].nt = len(t)
+            arr[i].init = (C.c_double * 16)(*_f64(np.eye(4) if init is None else init, (16,)))
+            arr[i].max_dist = float(r)
+        out = np.zeros((max(n, 1), 36)); k = np.zeros(max(n, 1), np.int64)
+        self._chk(self.L.visma_icp_information_matrices(self._h, arr, n, _p(out, _dp), _p(k, C.POINTER(C.c_int64))))
+        cs, ct = C.c_int64(0), C.c_int64(0)              # the clouds of the last edge the library handled
+        self._chk(self.L.visma_icp_get_cloud_sizes(self._h, C.byref(cs), C.byref(ct)))
+        self.ns, self.nt = int(cs.value), int(ct.value)
+        return out[:n].reshape(n, 6, 6), k[:n]
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""

@@ -584,6 +584,144 @@ int visma_icp_registration_ransac_correspondence(visma_icp_ctx *ctx, const doubl
     return VISMA_ICP_OK;
 }
 
+// ---- the pose graph (host_math.hpp; pure functions) ---------------------------------------------------------------------
+int visma_icp_global_optimization_option_clamp(visma_icp_global_optimization_option *o)
+{
+    if (!o) return VISMA_ICP_ERR_INVALID;
+    // (the reference's comparisons, so a NaN stays what the caller gave)
+    if (o->max_correspondence_distance < 0.0) o->max_correspondence_distance = 0.075;
+    if (o->edge_prune_threshold < 0.0 || o->edge_prune_threshold > 1.0) o->edge_prune_threshold = 0.25;
+    if (o->preference_loop_closure < 0.0) o->preference_loop_closure = 1.0;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_global_optimization_criteria_clamp(visma_icp_global_optimization_criteria *c)
+{
+    if (!c) return VISMA_ICP_ERR_INVALID;
+    if (c->upper_scale_factor < 0.0 || c->upper_scale_factor > 1.0) c->upper_scale_factor = 2. / 3.;
+    if (c->lower_scale_factor < 0.0 || c->lower_scale_factor > 1.0) c->lower_scale_factor = 1. / 3.;
+    return VISMA_ICP_OK;
+}
+
+static bool pose_graph_args_ok(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges)
+{
+    return n_nodes >= 0 && n_edges >= 0 && (n_nodes == 0 || poses) && (n_edges == 0 || edges);
+}
+
+static PoseGraphData pose_graph_of(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges)
+{
+    PoseGraphData g;
+    g.nodes.resize((size_t)n_nodes);
+    for (int i = 0; i < n_nodes; i++) g.nodes[(size_t)i] = Mat4::from(poses + (size_t)i * 16);
+    g.edges.resize((size_t)n_edges);
+    for (int e = 0; e < n_edges; e++) {
+        PgEdge &t = g.edges[(size_t)e];
+        t.source = edges[e].source; t.target = edges[e].target;
+        t.X = Mat4::from(edges[e].transformation);
+        std::memcpy(t.info, edges[e].information, sizeof(t.info));
+        t.uncertain = edges[e].uncertain != 0;
+        t.confidence = edges[e].confidence;
+    }
+    return g;
+}
+
+static bool pose_graph_ids_ok(const PoseGraphData &g)
+{
+    const int n = (int)g.nodes.size();
+    for (const PgEdge &t : g.edges)
+        if (t.source < 0 || t.source >= n || t.target < 0 || t.target >= n) return false;
+    return true;
+}
+
+int visma_icp_pose_graph_validate(int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges)
+{
+    if (n_nodes < 0 || n_edges < 0 || (n_edges > 0 && !edges)) return -VISMA_ICP_ERR_INVALID;
+    PoseGraphData g;
+    g.nodes.resize((size_t)n_nodes);
+    g.edges.resize((size_t)n_edges);
+    for (int e = 0; e < n_edges; e++) { g.edges[(size_t)e].source = edges[e].source; g.edges[(size_t)e].target = edges[e].target; }
+    return pg_validate(g) ? 1 : 0;
+}
+
+int visma_icp_pose_graph_zeta(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges, double *zeta_out)
+{
+    if (!pose_graph_args_ok(poses, n_nodes, edges, n_edges) || (n_edges > 0 && !zeta_out)) return VISMA_ICP_ERR_INVALID;
+    const PoseGraphData g = pose_graph_of(poses, n_nodes, edges, n_edges);
+    if (!pose_graph_ids_ok(g)) return VISMA_ICP_ERR_INVALID;
+    std::vector<double> zeta;
+    pg_zeta(g, zeta);
+    if (!zeta.empty()) std::memcpy(zeta_out, zeta.data(), sizeof(double) * zeta.size());
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_pose_graph_linear_system(const double *poses, int n_nodes, const visma_icp_pose_graph_edge *edges, int n_edges,
+                                       double *H_out, double *b_out)
+{
+    if (!pose_graph_args_ok(poses, n_nodes, edges, n_edges) || (n_nodes > 0 && (!H_out || !b_out))) return VISMA_ICP_ERR_INVALID;
+    const PoseGraphData g = pose_graph_of(poses, n_nodes, edges, n_edges);
+    if (!pose_graph_ids_ok(g)) return VISMA_ICP_ERR_INVALID;
+    std::vector<double> zeta, H, b;
+    pg_zeta(g, zeta);
+    pg_linear_system(g, zeta, H, b);
+    if (!H.empty()) std::memcpy(H_out, H.data(), sizeof(double) * H.size());
+    if (!b.empty()) std::memcpy(b_out, b.data(), sizeof(double) * b.size());
+    return VISMA_ICP_OK;
+}
+
+static int pose_graph_run(bool whole, double *poses, int n_nodes, visma_icp_pose_graph_edge *edges, int *n_edges, int method,
+                          const visma_icp_global_optimization_criteria *criteria, const visma_icp_global_optimization_option *option)
+{
+    if (!n_edges || !pose_graph_args_ok(poses, n_nodes, edges, *n_edges)) return VISMA_ICP_ERR_INVALID;
+    if (method != VISMA_ICP_GLOBAL_GAUSS_NEWTON && method != VISMA_ICP_GLOBAL_LEVENBERG_MARQUARDT) return VISMA_ICP_ERR_INVALID;
+    visma_icp_global_optimization_option o = {0.075, 0.25, 1.0, -1};
+    visma_icp_global_optimization_criteria c = {100, 1e-6, 1e-6, 1e-6, 1e-6, 20, 2. / 3., 1. / 3.};
+    if (option) o = *option;
+    if (criteria) c = *criteria;
+    visma_icp_global_optimization_option_clamp(&o);
+    visma_icp_global_optimization_criteria_clamp(&c);
+    PgOption po;
+    po.max_corr_dist = o.max_correspondence_distance; po.edge_prune_threshold = o.edge_prune_threshold;
+    po.preference_loop_closure = o.preference_loop_closure; po.reference_node = o.reference_node;
+    PgCriteria pc;
+    pc.max_iteration = c.max_iteration; pc.min_relative_increment = c.min_relative_increment;
+    pc.min_relative_residual_increment = c.min_relative_residual_increment; pc.min_right_term = c.min_right_term;
+    pc.min_residual = c.min_residual; pc.max_iteration_lm = c.max_iteration_lm;
+    pc.upper_scale_factor = c.upper_scale_factor; pc.lower_scale_factor = c.lower_scale_factor;
+    PoseGraphData g = pose_graph_of(poses, n_nodes, edges, *n_edges);
+    if (whole) {
+        if (!pg_global_optimization(g, method, pc, po)) return VISMA_ICP_OK;     // an invalid graph: untouched
+    } else {
+        if (!pose_graph_ids_ok(g)) return VISMA_ICP_ERR_INVALID;
+        pg_optimize(g, method, pc, po);
+    }
+    for (int i = 0; i < n_nodes; i++) std::memcpy(poses + (size_t)i * 16, g.nodes[(size_t)i].m, sizeof(double) * 16);
+    for (size_t e = 0; e < g.edges.size(); e++) {
+        const PgEdge &t = g.edges[e];
+        visma_icp_pose_graph_edge &d = edges[e];
+        d.source = t.source; d.target = t.target;
+        std::memcpy(d.transformation, t.X.m, sizeof(d.transformation));
+        std::memcpy(d.information, t.info, sizeof(d.information));
+        d.uncertain = t.uncertain;
+        d.confidence = t.confidence;
+    }
+    *n_edges = (int)g.edges.size();
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_global_optimization(double *poses, int n_nodes, visma_icp_pose_graph_edge *edges, int *n_edges, int method,
+                                  const visma_icp_global_optimization_criteria *criteria,
+                                  const visma_icp_global_optimization_option *option)
+{
+    return pose_graph_run(true, poses, n_nodes, edges, n_edges, method, criteria, option);
+}
+
+int visma_icp_pose_graph_optimize(double *poses, int n_nodes, visma_icp_pose_graph_edge *edges, int n_edges, int method,
+                                  const visma_icp_global_optimization_criteria *criteria,
+                                  const visma_icp_global_optimization_option *option)
+{
+    return pose_graph_run(false, poses, n_nodes, edges, &n_edges, method, criteria, option);
+}
+
 int visma_icp_point_mesh_distance(visma_icp_ctx *ctx, const double *P, int64_t np, const double *V,
                                   int64_t nv, const int32_t *F, int64_t nf, double *d2, int32_t *face,
                                   double *closest)

@@ -1439,6 +1439,118 @@ int visma_icp_run_batch_point_to_plane(visma_icp_ctx *ctx, const visma_icp_probl
                           VISMA_ICP_SOLVER_GN_EULER, out);
 }
 
+// ---- the information matrix of an edge (information.hip) ---------------------------------------------------------------
+static int check_information(visma_icp_ctx *ctx)
+{
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "the information matrix runs on one rank");
+    if (!ctx->have_src || !ctx->have_tgt) return ctx->fail(VISMA_ICP_ERR_STATE, "clouds not set");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_reduce_information(visma_icp_ctx *ctx, double out[36])
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (int rc = check_information(ctx)) return rc;
+    double sums[kInfoAcc];
+    Engine::PairPass pp;
+    int rc = ctx->eng->reduce_information(ctx->last_Tc, ctx->centre, sums, &pp);
+    if (rc) return ctx->eng_fail(rc);
+    information_from_sums(sums, out);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_information_matrix(visma_icp_ctx *ctx, const double T[16], double max_dist, double out[36], int64_t *k)
+{
+    CTX_CHECK();
+    if (!T || !out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (!(max_dist > 0.0)) return ctx->fail(VISMA_ICP_ERR_INVALID, "max_dist must be > 0");
+    if (int rc = check_information(ctx)) return rc;
+    for (int i = 0; i < 36; i++) out[i] = 0.0;
+    if (k) *k = 0;
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(T[i])) return VISMA_ICP_OK;           // (a pose that is no pose has no pairs)
+    int rc = visma_icp_nn_pass(ctx, T, max_dist);
+    if (rc) return rc;
+    rc = visma_icp_reduce_information(ctx, out);
+    if (rc) return rc;
+    if (k) *k = (int64_t)std::llround(out[35]);
+    return VISMA_ICP_OK;
+}
+
+// A new source next to the target of the last visma_icp_set_clouds_f64, centred where that call centred: the source half
+// of that call on the engine's raw path.  VISMA_ICP_ERR_STATE: not on this engine (the caller uploads both clouds).
+static int set_source_beside_target_f64(visma_icp_ctx *ctx, const double *src, int64_t ns)
+{
+    if (!ctx->centred_upload || !ctx->have_tgt || ctx->fixed_centre || std::getenv("VISMA_ICP_RAW_UPLOAD_MIN")) return VISMA_ICP_ERR_STATE;
+    const bool want64 = ctx->search_precision != 0 && ctx->eng->supports_device_loop();
+    int rc = ctx->eng->set_source_f64(src, ns, 3, ctx->centre, want64, ctx->src_order);
+    ctx->src_order_gen++;
+    if (rc) { ctx->have_src = false; return rc; }
+    ctx->eng->set_exact(ctx->search_precision == 1);
+    if (!want64) {
+        rc = ctx->eng->set_clouds64(nullptr, nullptr);
+        if (rc) { ctx->have_src = false; return rc; }
+    }
+    ctx->have_src = true;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_get_cloud_sizes(visma_icp_ctx *ctx, int64_t *ns, int64_t *nt)
+{
+    CTX_CHECK();
+    if (!ns || !nt) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *ns = ctx->have_src ? ctx->eng->ns() : 0;
+    *nt = ctx->have_tgt ? ctx->eng->nt() : 0;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_information_matrices(visma_icp_ctx *ctx, const visma_icp_problem *probs, int n, double *out, int64_t *k)
+{
+    CTX_CHECK();
+    if (n < 0 || (n > 0 && (!probs || !out))) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad batch arguments");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "the information matrix runs on one rank");
+    for (int i = 0; i < n; i++) {
+        const visma_icp_problem &q = probs[i];
+        if (q.ns < 0 || q.nt < 0 || (q.ns > 0 && !q.src_xyz) || (q.nt > 0 && !q.tgt_xyz) || !(q.max_dist > 0.0))
+            return ctx->fail(VISMA_ICP_ERR_INVALID, "bad batch problem");
+    }
+    // edges in groups of one target (first occurrences in the caller's order): the target is uploaded once per group.
+    // (Its search grid is NOT kept: a new source invalidates it on the engine, so every edge builds its own.)
+    std::vector<int> order;
+    std::vector<char> taken((size_t)n, 0);
+    for (int i = 0; i < n; i++) {
+        if (taken[(size_t)i]) continue;
+        std::vector<int> group;
+        for (int j = i; j < n; j++)
+            if (!taken[(size_t)j] && probs[j].tgt_xyz == probs[i].tgt_xyz && probs[j].nt == probs[i].nt) { group.push_back(j); taken[(size_t)j] = 1; }
+        order.insert(order.end(), group.begin(), group.end());
+    }
+    int prev = -1;
+    for (int e : order) {
+        const visma_icp_problem &q = probs[e];
+        double *o = out + (size_t)e * 36;
+        for (int i = 0; i < 36; i++) o[i] = 0.0;
+        if (k) k[e] = 0;
+        bool finite = true;
+        for (int i = 0; i < 16; i++) finite = finite && std::isfinite(q.init[i]);
+        if (!finite) continue;
+        int rc = VISMA_ICP_ERR_STATE;
+        if (prev >= 0 && probs[prev].tgt_xyz == q.tgt_xyz && probs[prev].nt == q.nt) {
+            rc = set_source_beside_target_f64(ctx, q.src_xyz, q.ns);
+            if (rc && rc != VISMA_ICP_ERR_STATE) return ctx->eng_fail(rc);
+        }
+        if (rc) {
+            rc = visma_icp_set_clouds_f64(ctx, q.src_xyz, q.ns, 3, q.tgt_xyz, q.nt, 3);
+            if (rc) return rc;
+        }
+        prev = e;
+        rc = visma_icp_information_matrix(ctx, q.init, q.max_dist, o, k ? &k[e] : nullptr);
+        if (rc) return rc;
+    }
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_set_nn_mode(visma_icp_ctx *ctx, int nn_mode)
 {
     CTX_CHECK();

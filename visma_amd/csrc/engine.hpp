@@ -369,6 +369,13 @@ public:
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;
     }
+    // Information matrix (information.hip): the pending pass's search, then the ten sums K, sum x y z, sum xx yy zz xy xz yz
+    // over the TARGET points of its pairs, in the frame of `offset` (information_from_sums lays them out as the 6 x 6)
+    virtual int reduce_information(const Mat4 &, const double * /* offset[3] */, double * /* sums[10] */, PairPass *)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

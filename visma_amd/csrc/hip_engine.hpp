@@ -327,6 +327,9 @@ public:
     int reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon, double *stats, GicpPass *out) override;
     void *d_snrm_ = nullptr, *d_snrm64_ = nullptr;          // source normals by source position: fp32, and f64 next to d_src64_
 
+    // information matrix (information.hip): the plain pass, then the ten sums over the target points of its pairs
+    int reduce_information(const Mat4 &Tc, const double *offset, double *sums, PairPass *out) override;
+
     // colored ICP (color_gradient.hip, colored.hip): f64 intensities of both clouds, the target's colour gradient, then the
     // plain pass and the reduction over the two rows per pair
     int set_source_intensity(const double *by_position, int64_t ns) override;

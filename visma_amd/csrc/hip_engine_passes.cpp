@@ -942,6 +942,25 @@ int HipEngine::reduce_colored(const Mat4 &Tc, const double *offset, double lambd
     return VISMA_ICP_OK;
 }
 
+// The information matrix of the last pass's pairs: the plain pass as reduce() runs it (K, the warm-start state), then the
+// ten sums over the pairs' target points on the stream; the host waits for the tagged granules like reduce() waits for
+// its own.
+int HipEngine::reduce_information(const Mat4 &Tc, const double *offset, double *sums, PairPass *out)
+{
+    int rc = pair_pass_begin("information", Tc, offset, false, out);
+    if (rc) return rc;
+    InformationArgs a;
+    rc = pair_pass_args("information", Tc, offset, &a);
+    if (rc) return rc;
+    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
+    HIP_TRY(pair_.arm(stream_));
+    HIP_TRY(launch_information_reduce(a, stream_));
+    rc = wait_granules(pair_.host, kInfoAcc, a.seq, "information", sums);
+    if (rc) return rc;
+    pair_.disarm();
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

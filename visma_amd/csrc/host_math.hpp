@@ -735,4 +735,405 @@ inline Mat4 fgr_map_back(const Mat4 &t, const FgrNormalized &N)
     return out;
 }
 
+// ---- multiway registration (Choi, Zhou, Koltun, CVPR 2015; O3D/Core/Registration/GlobalOptimization.cpp) ------------------
+// Host only: 6 unknowns per node, tens or hundreds of nodes.  DESIGN.md 4.4c9.
+
+// The information matrix sum G^T G, G = [-hat(q) | I], from the ten sums of information.hip
+// s = {K, sum x, y, z, sum xx, yy, zz, xy, xz, yz}; row-major 6 x 6.  (No identity terms: visma_icp.h.)
+inline void information_from_sums(const double s[10], double out[36])
+{
+    for (int i = 0; i < 36; i++) out[i] = 0.0;
+    const double K = s[0], X = s[1], Y = s[2], Z = s[3], xx = s[4], yy = s[5], zz = s[6], xy = s[7], xz = s[8], yz = s[9];
+    out[0] = yy + zz; out[1] = -xy;     out[2] = -xz;
+    out[6] = -xy;     out[7] = xx + zz; out[8] = -yz;
+    out[12] = -xz;    out[13] = -yz;    out[14] = xx + yy;
+    // the upper right block is sum hat(q)^T = -hat(sum q), the lower left its transpose
+    out[4] = -Z; out[5] = Y; out[9] = Z; out[11] = -X; out[15] = -Y; out[16] = X;
+    out[24] = -Z; out[30] = Y; out[19] = Z; out[31] = -X; out[20] = -Y; out[26] = X;
+    out[21] = out[28] = out[35] = K;
+}
+
+// the inverse of a general 4 x 4 by cofactors (what Eigen's fixed-size inverse() evaluates)
+inline Mat4 inverse4(const Mat4 &A)
+{
+    const double *m = A.m;
+    double inv[16];
+    inv[0] = m[5] * m[10] * m[15] - m[5] * m[11] * m[14] - m[9] * m[6] * m[15] + m[9] * m[7] * m[14] + m[13] * m[6] * m[11] - m[13] * m[7] * m[10];
+    inv[4] = -m[4] * m[10] * m[15] + m[4] * m[11] * m[14] + m[8] * m[6] * m[15] - m[8] * m[7] * m[14] - m[12] * m[6] * m[11] + m[12] * m[7] * m[10];
+    inv[8] = m[4] * m[9] * m[15] - m[4] * m[11] * m[13] - m[8] * m[5] * m[15] + m[8] * m[7] * m[13] + m[12] * m[5] * m[11] - m[12] * m[7] * m[9];
+    inv[12] = -m[4] * m[9] * m[14] + m[4] * m[10] * m[13] + m[8] * m[5] * m[14] - m[8] * m[6] * m[13] - m[12] * m[5] * m[10] + m[12] * m[6] * m[9];
+    inv[1] = -m[1] * m[10] * m[15] + m[1] * m[11] * m[14] + m[9] * m[2] * m[15] - m[9] * m[3] * m[14] - m[13] * m[2] * m[11] + m[13] * m[3] * m[10];
+    inv[5] = m[0] * m[10] * m[15] - m[0] * m[11] * m[14] - m[8] * m[2] * m[15] + m[8] * m[3] * m[14] + m[12] * m[2] * m[11] - m[12] * m[3] * m[10];
+    inv[9] = -m[0] * m[9] * m[15] + m[0] * m[11] * m[13] + m[8] * m[1] * m[15] - m[8] * m[3] * m[13] - m[12] * m[1] * m[11] + m[12] * m[3] * m[9];
+    inv[13] = m[0] * m[9] * m[14] - m[0] * m[10] * m[13] - m[8] * m[1] * m[14] + m[8] * m[2] * m[13] + m[12] * m[1] * m[10] - m[12] * m[2] * m[9];
+    inv[2] = m[1] * m[6] * m[15] - m[1] * m[7] * m[14] - m[5] * m[2] * m[15] + m[5] * m[3] * m[14] + m[13] * m[2] * m[7] - m[13] * m[3] * m[6];
+    inv[6] = -m[0] * m[6] * m[15] + m[0] * m[7] * m[14] + m[4] * m[2] * m[15] - m[4] * m[3] * m[14] - m[12] * m[2] * m[7] + m[12] * m[3] * m[6];
+    inv[10] = m[0] * m[5] * m[15] - m[0] * m[7] * m[13] - m[4] * m[1] * m[15] + m[4] * m[3] * m[13] + m[12] * m[1] * m[7] - m[12] * m[3] * m[5];
+    inv[14] = -m[0] * m[5] * m[14] + m[0] * m[6] * m[13] + m[4] * m[1] * m[14] - m[4] * m[2] * m[13] - m[12] * m[1] * m[6] + m[12] * m[2] * m[5];
+    inv[3] = -m[1] * m[6] * m[11] + m[1] * m[7] * m[10] + m[5] * m[2] * m[11] - m[5] * m[3] * m[10] - m[9] * m[2] * m[7] + m[9] * m[3] * m[6];
+    inv[7] = m[0] * m[6] * m[11] - m[0] * m[7] * m[10] - m[4] * m[2] * m[11] + m[4] * m[3] * m[10] + m[8] * m[2] * m[7] - m[8] * m[3] * m[6];
+    inv[11] = -m[0] * m[5] * m[11] + m[0] * m[7] * m[9] + m[4] * m[1] * m[11] - m[4] * m[3] * m[9] - m[8] * m[1] * m[7] + m[8] * m[3] * m[5];
+    inv[15] = m[0] * m[5] * m[10] - m[0] * m[6] * m[9] - m[4] * m[1] * m[10] + m[4] * m[2] * m[9] + m[8] * m[1] * m[6] - m[8] * m[2] * m[5];
+    const double det = m[0] * inv[0] + m[1] * inv[4] + m[2] * inv[8] + m[3] * inv[12];
+    Mat4 r;
+    for (int i = 0; i < 16; i++) r.m[i] = inv[i] / det;
+    return r;
+}
+
+// TransformMatrix4dToVector6d (Eigen.cpp:70-86)
+inline void mat4_to_vec6(const Mat4 &T, double out[6])
+{
+    const double sy = sqrt(T(0, 0) * T(0, 0) + T(1, 0) * T(1, 0));
+    if (!(sy < 1e-6)) {
+        out[0] = atan2(T(2, 1), T(2, 2));
+        out[1] = atan2(-T(2, 0), sy);
+        out[2] = atan2(T(1, 0), T(0, 0));
+    } else {
+        out[0] = atan2(-T(1, 2), T(1, 1));
+        out[1] = atan2(-T(2, 0), sy);
+        out[2] = 0.0;
+    }
+    out[3] = T(0, 3); out[4] = T(1, 3); out[5] = T(2, 3);
+}
+
+struct PgEdge {                                        // PoseGraphEdge (PoseGraph.h:52-86)
+    int source = -1, target = -1;
+    Mat4 X = Mat4::identity();
+    double info[36];
+    int uncertain = 0;
+    double confidence = 1.0;
+};
+struct PgOption {                                      // GlobalOptimizationOption, clamped as its constructor clamps
+    double max_corr_dist = 0.075, edge_prune_threshold = 0.25, preference_loop_closure = 1.0;
+    int reference_node = -1;
+};
+struct PgCriteria {                                    // GlobalOptimizationConvergenceCriteria, likewise
+    int max_iteration = 100;
+    double min_relative_increment = 1e-6, min_relative_residual_increment = 1e-6, min_right_term = 1e-6, min_residual = 1e-6;
+    int max_iteration_lm = 20;
+    double upper_scale_factor = 2.0 / 3.0, lower_scale_factor = 1.0 / 3.0;
+};
+struct PoseGraphData {
+    std::vector<Mat4> nodes;
+    std::vector<PgEdge> edges;
+};
+
+// GetLinearized6DVector (:71-79)
+inline void pg_linearized6(const Mat4 &M, double o[6])
+{
+    o[0] = (-M(1, 2) + M(2, 1)) / 2.0;
+    o[1] = (-M(2, 0) + M(0, 2)) / 2.0;
+    o[2] = (-M(0, 1) + M(1, 0)) / 2.0;
+    o[3] = M(0, 3); o[4] = M(1, 3); o[5] = M(2, 3);
+}
+
+// ValidatePoseGraph (:372-402)
+inline bool pg_validate(const PoseGraphData &g)
+{
+    const int n_nodes = (int)g.nodes.size();
+    for (int i = 0; i < n_nodes - 1; i++) {
+        bool valid = false;
+        for (const PgEdge &t : g.edges)
+            if (t.source == i && t.target - t.source == 1) valid = true;
+        if (!valid) return false;
+    }
+    for (const PgEdge &t : g.edges)
+        if (!(t.source >= 0 && t.source < n_nodes && t.target >= 0 && t.target < n_nodes)) return false;
+    return true;
+}
+
+// ComputeZeta (:161-172): 6 per edge, the linearised X^-1 Tt^-1 Ts
+inline void pg_zeta(const PoseGraphData &g, std::vector<double> &zeta)
+{
+    zeta.assign(g.edges.size() * 6, 0.0);
+    for (size_t e = 0; e < g.edges.size(); e++) {
+        const PgEdge &t = g.edges[e];
+        const Mat4 A = inverse4(t.X) * inverse4(g.nodes[(size_t)t.target]);
+        pg_linearized6(A * g.nodes[(size_t)t.source], &zeta[e * 6]);
+    }
+}
+
+// ComputeLinearSystem (:187-229): H (6n x 6n, row-major) and b (6n)
+inline void pg_linear_system(const PoseGraphData &g, const std::vector<double> &zeta, std::vector<double> &H, std::vector<double> &b)
+{
+    const int n = (int)g.nodes.size() * 6;
+    H.assign((size_t)n * n, 0.0);
+    b.assign((size_t)n, 0.0);
+    for (size_t ei = 0; ei < g.edges.size(); ei++) {
+        const PgEdge &t = g.edges[ei];
+        const double *e = &zeta[ei * 6];
+        const Mat4 A = inverse4(t.X) * inverse4(g.nodes[(size_t)t.target]);
+        const Mat4 &Ts = g.nodes[(size_t)t.source];
+        // GetJacobian (:101-118): column i of Js is the linearised A Op_i Ts; Jt's the same with -Op_i, its exact negative
+        double Js[36], Jt[36];
+        static const int op_at[6][2] = {{6, 9}, {2, 8}, {1, 4}, {3, 3}, {7, 7}, {11, 11}};     // the entries -1 / +1 (or the 1)
+        for (int i = 0; i < 6; i++) {
+            Mat4 Op;
+            for (double &v : Op.m) v = 0.0;
+            if (i < 3) { Op.m[op_at[i][0]] = i == 1 ? 1.0 : -1.0; Op.m[op_at[i][1]] = i == 1 ? -1.0 : 1.0; }
+            else Op.m[op_at[i][0]] = 1.0;
+            double col[6];
+            pg_linearized6((A * Op) * Ts, col);
+            for (int r = 0; r < 6; r++) { Js[r * 6 + i] = col[r]; Jt[r * 6 + i] = -col[r]; }
+        }
+        double JsTI[36], JtTI[36], eTI[6];
+        for (int r = 0; r < 6; r++) {
+            for (int c = 0; c < 6; c++) {
+                double s1 = 0.0, s2 = 0.0;
+                for (int k = 0; k < 6; k++) { s1 += Js[k * 6 + r] * t.info[k * 6 + c]; s2 += Jt[k * 6 + r] * t.info[k * 6 + c]; }
+                JsTI[r * 6 + c] = s1; JtTI[r * 6 + c] = s2;
+            }
+            double s = 0.0;
+            for (int k = 0; k < 6; k++) s += e[k] * t.info[k * 6 + r];
+            eTI[r] = s;
+        }
+        const double l = t.confidence;
+        const int ii = t.source * 6, jj = t.target * 6;
+        for (int r = 0; r < 6; r++) {
+            for (int c = 0; c < 6; c++) {
+                double ss = 0.0, st = 0.0, ts = 0.0, tt = 0.0;
+                for (int k = 0; k < 6; k++) {
+                    ss += l * JsTI[r * 6 + k] * Js[k * 6 + c]; st += l * JsTI[r * 6 + k] * Jt[k * 6 + c];
+                    ts += l * JtTI[r * 6 + k] * Js[k * 6 + c]; tt += l * JtTI[r * 6 + k] * Jt[k * 6 + c];
+                }
+                H[(size_t)(ii + r) * n + ii + c] += ss; H[(size_t)(ii + r) * n + jj + c] += st;
+                H[(size_t)(jj + r) * n + ii + c] += ts; H[(size_t)(jj + r) * n + jj + c] += tt;
+            }
+            double bs = 0.0, bt = 0.0;
+            for (int k = 0; k < 6; k++) { bs += l * eTI[k] * Js[k * 6 + r]; bt += l * eTI[k] * Jt[k * 6 + r]; }
+            b[(size_t)(ii + r)] -= bs; b[(size_t)(jj + r)] -= bt;
+        }
+    }
+}
+
+// A x = b by the dense L D L^T with diagonal pivoting that Eigen's LDLT<MatrixXd, Lower> runs (LDLT.h:291-400, :558-600): the
+// largest remaining diagonal entry first, no cut-off on a pivot other than exactly zero (whose row of the solve gives 0).
+// Gauss-Newton hands it the singular H of a graph without a fixed node, as the reference does.
+inline void ldlt_solve(std::vector<double> A, int n, const double *b, double *x)
+{
+    std::vector<int> tr((size_t)n);
+    std::vector<double> temp((size_t)n);
+    auto a = [&](int i, int j) -> double & { return A[(size_t)i * n + j]; };
+    for (int k = 0; k < n; k++) {
+        int p = k;
+        for (int i = k + 1; i < n; i++)
+            if (fabs(a(i, i)) > fabs(a(p, p))) p = i;
+        tr[(size_t)k] = p;
+        if (p != k) {                                        // the transposition on the lower triangle
+            for (int j = 0; j < k; j++) { const double v = a(k, j); a(k, j) = a(p, j); a(p, j) = v; }
+            for (int i = p + 1; i < n; i++) { const double v = a(i, k); a(i, k) = a(i, p); a(i, p) = v; }
+            { const double v = a(k, k); a(k, k) = a(p, p); a(p, p) = v; }
+            for (int i = k + 1; i < p; i++) { const double v = a(i, k); a(i, k) = a(p, i); a(p, i) = v; }
+        }
+        if (k > 0) {
+            for (int j = 0; j < k; j++) temp[(size_t)j] = a(j, j) * a(k, j);
+            double s = 0.0;
+            for (int j = 0; j < k; j++) s += a(k, j) * temp[(size_t)j];
+            a(k, k) -= s;
+            for (int i = k + 1; i < n; i++) {
+                double u = 0.0;
+                for (int j = 0; j < k; j++) u += a(i, j) * temp[(size_t)j];
+                a(i, k) -= u;
+            }
+        }
+        const double akk = a(k, k);
+        const bool valid = fabs(akk) > 0.0;
+        if (k == 0 && !valid) {                              // the whole diagonal is zero
+            for (int j = 0; j < n; j++) tr[(size_t)j] = j;
+            break;
+        }
+        if (valid)
+            for (int i = k + 1; i < n; i++) a(i, k) /= akk;
+    }
+    for (int i = 0; i < n; i++) x[i] = b[i];
+    for (int k = 0; k < n; k++) { const double v = x[k]; x[k] = x[tr[(size_t)k]]; x[tr[(size_t)k]] = v; }
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < i; j++) x[i] -= a(i, j) * x[j];
+    const double tol = 1.0 / 1.7976931348623157e308;
+    for (int i = 0; i < n; i++) x[i] = fabs(a(i, i)) > tol ? x[i] / a(i, i) : 0.0;
+    for (int i = n - 1; i >= 0; i--)
+        for (int j = i + 1; j < n; j++) x[i] -= a(j, i) * x[j];
+    for (int k = n - 1; k >= 0; k--) { const double v = x[k]; x[k] = x[tr[(size_t)k]]; x[tr[(size_t)k]] = v; }
+}
+
+// ComputeLineProcessWeight (:329-350): information(5, 5) read as the number of correspondences
+inline double pg_line_process_weight(const PoseGraphData &g, const PgOption &o)
+{
+    if (g.edges.empty()) return 0.0;
+    double avg = 0.0;
+    for (const PgEdge &t : g.edges) avg += t.info[35];
+    avg /= (double)(int)g.edges.size();
+    return o.preference_loop_closure * pow(o.max_corr_dist, 2) * avg;
+}
+
+inline double pg_quadratic(const double *e, const double *info)
+{
+    double r = 0.0;
+    for (int a = 0; a < 6; a++) {
+        double s = 0.0;
+        for (int c = 0; c < 6; c++) s += info[a * 6 + c] * e[c];
+        r += e[a] * s;
+    }
+    return r;
+}
+
+// UpdateConfidence (:122-141)
+inline int pg_update_confidence(PoseGraphData &g, const std::vector<double> &zeta, double w, const PgOption &o)
+{
+    int valid = 0;
+    for (size_t e = 0; e < g.edges.size(); e++) {
+        const double temp = w / (w + pg_quadratic(&zeta[e * 6], g.edges[e].info));
+        g.edges[e].confidence = temp * temp;
+        if (temp * temp > o.edge_prune_threshold) valid++;
+    }
+    return valid;
+}
+
+// ComputeResidual (:144-158)
+inline double pg_residual(const PoseGraphData &g, const std::vector<double> &zeta, double w)
+{
+    double residual = 0.0;
+    for (size_t e = 0; e < g.edges.size(); e++) {
+        const double l = g.edges[e].confidence;
+        residual += l * pg_quadratic(&zeta[e * 6], g.edges[e].info) + w * pow(sqrt(l) - 1, 2.0);
+    }
+    return residual;
+}
+
+inline void pg_pose_vector(const PoseGraphData &g, std::vector<double> &x)
+{
+    x.resize(g.nodes.size() * 6);
+    for (size_t i = 0; i < g.nodes.size(); i++) mat4_to_vec6(g.nodes[i], &x[i * 6]);
+}
+
+inline PoseGraphData pg_updated(const PoseGraphData &g, const std::vector<double> &delta)
+{
+    PoseGraphData r = g;
+    for (size_t i = 0; i < r.nodes.size(); i++) r.nodes[i] = euler_zyx_to_mat4(&delta[i * 6]) * r.nodes[i];
+    return r;
+}
+
+inline double pg_norm(const std::vector<double> &v)
+{
+    double s = 0.0;
+    for (double e : v) s += e * e;
+    return sqrt(s);
+}
+inline double pg_max_coeff(const std::vector<double> &v)
+{
+    double m = v[0];
+    for (double e : v) m = e > m ? e : m;
+    return m;
+}
+inline bool pg_check_increment(const std::vector<double> &delta, const std::vector<double> &x, const PgCriteria &c)
+{
+    return pg_norm(delta) < c.min_relative_increment * (pg_norm(x) + c.min_relative_increment);
+}
+
+// GlobalOptimizationGaussNewton::OptimizePoseGraph (:432-514) and GlobalOptimizationLevenbergMarquardt's (:516-639): the
+// reference's tests in the reference's order
+inline void pg_optimize(PoseGraphData &g, int method, const PgCriteria &c, const PgOption &o)
+{
+    const int n = (int)g.nodes.size() * 6;
+    if (n == 0) return;
+    const double w = pg_line_process_weight(g, o);
+    std::vector<double> zeta, zeta_new, H, b, x, delta((size_t)n), HL;
+    pg_zeta(g, zeta);
+    double current_residual = pg_residual(g, zeta, w), new_residual;
+    pg_update_confidence(g, zeta, w, o);
+    pg_pose_vector(g, x);
+    pg_linear_system(g, zeta, H, b);
+    auto right_term = [&]() { return pg_max_coeff(b) < c.min_right_term; };                   // maxCoeff, not its absolute value
+    auto residual_increment = [&]() { return current_residual - new_residual < c.min_relative_residual_increment * current_residual; };
+    auto accept = [&](PoseGraphData &next) {
+        current_residual = new_residual;
+        zeta = zeta_new;
+        g = next;
+        pg_pose_vector(g, x);
+        pg_update_confidence(g, zeta, w, o);
+        pg_linear_system(g, zeta, H, b);
+    };
+    bool stop = false;
+    if (method == 0) {
+        if (right_term()) return;
+        for (int iter = 0; !stop; iter++) {
+            ldlt_solve(H, n, b.data(), delta.data());
+            stop = stop || pg_check_increment(delta, x, c);
+            if (stop) break;
+            PoseGraphData next = pg_updated(g, delta);
+            pg_zeta(next, zeta_new);
+            new_residual = pg_residual(g, zeta_new, w);
+            stop = stop || residual_increment();
+            if (stop) break;
+            accept(next);
+            stop = stop || right_term();
+            if (stop) break;
+            stop = stop || current_residual < c.min_residual || iter >= c.max_iteration;
+        }
+        return;
+    }
+    double hmax = H[0];
+    for (int i = 1; i < n; i++) hmax = H[(size_t)i * n + i] > hmax ? H[(size_t)i * n + i] : hmax;
+    const double tau = 1e-5;
+    double current_lambda = tau * hmax, ni = 2.0, rho = 0.0;
+    stop = stop || right_term();
+    if (stop) return;
+    for (int iter = 0; !stop; iter++) {
+        int lm_count = 0;
+        do {
+            HL = H;
+            for (int i = 0; i < n; i++) HL[(size_t)i * n + i] += current_lambda * 1.0;
+            ldlt_solve(HL, n, b.data(), delta.data());           // (dense throughout: the reference's sparse Cholesky is an implementation detail)
+            stop = stop || pg_check_increment(delta, x, c);
+            if (!stop) {
+                PoseGraphData next = pg_updated(g, delta);
+                pg_zeta(next, zeta_new);
+                new_residual = pg_residual(g, zeta_new, w);
+                double dot = 0.0;
+                for (int i = 0; i < n; i++) dot += delta[(size_t)i] * (current_lambda * delta[(size_t)i] + b[(size_t)i]);
+                rho = (current_residual - new_residual) / (dot + 1e-3);
+                if (rho > 0) {
+                    stop = stop || residual_increment();
+                    if (stop) break;
+                    double alpha = 1. - pow((2 * rho - 1), 3);
+                    alpha = alpha < c.upper_scale_factor ? alpha : c.upper_scale_factor;
+                    const double scale = c.lower_scale_factor > alpha ? c.lower_scale_factor : alpha;
+                    current_lambda *= scale;
+                    ni = 2;
+                    accept(next);
+                    stop = stop || right_term();
+                    if (stop) break;
+                } else {
+                    current_lambda *= ni;
+                    ni *= 2;
+                }
+            }
+            lm_count++;
+            stop = stop || lm_count >= c.max_iteration_lm;
+        } while (!((rho > 0) || stop));
+        stop = stop || current_residual < c.min_residual || iter >= c.max_iteration;
+    }
+}
+
+// GlobalOptimization (:641-662): validation, the first optimisation, CreatePoseGraphWithoutInvalidEdges (:406-430), the
+// second optimisation, CompensateReferencePoseGraphNode (:352-370).  false: an invalid graph, returned untouched.
+inline bool pg_global_optimization(PoseGraphData &g, int method, const PgCriteria &c, const PgOption &o)
+{
+    if (!pg_validate(g)) return false;
+    PoseGraphData pre = g;
+    pg_optimize(pre, method, c, o);
+    PoseGraphData pruned;
+    pruned.nodes = pre.nodes;
+    for (const PgEdge &t : pre.edges)
+        if (!t.uncertain || t.confidence > o.edge_prune_threshold) pruned.edges.push_back(t);
+    pg_optimize(pruned, method, c, o);
+    const int n_nodes = (int)pruned.nodes.size();
+    if (o.reference_node >= 0 && o.reference_node < n_nodes) {
+        const Mat4 comp = g.nodes[(size_t)o.reference_node] * inverse4(pruned.nodes[(size_t)o.reference_node]);
+        for (Mat4 &p : pruned.nodes) p = comp * p;
+    }
+    g = pruned;
+    return true;
+}
+
 }  // namespace visma

@@ -582,6 +582,14 @@ struct GicpArgs : PairPassArgs {
 };
 hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream);
 
+// ---- information matrix (information.hip): the ten sums over the target points of the last pass's pairs ----
+constexpr int kInfoAcc = 10;                           // K, sum x, y, z, sum xx, yy, zz, xy, xz, yz: what is published, too
+constexpr int kInfoRow = 16;                           // doubles per partial row
+struct InformationArgs : PairPassArgs {
+    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
+};
+hipError_t launch_information_reduce(const InformationArgs &a, hipStream_t stream);
+
 // ---- colored ICP (color_gradient.hip, colored.hip): a photometric row next to the point-to-plane row of every pair ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
 inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }
