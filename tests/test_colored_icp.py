@@ -616,7 +616,8 @@ def _surface(rng, n, spread=1.0):
 
 _stat_cache = {}
 STAT_SIZES = [(300, 2000, 1e-6), (1, 500, 0.05), (255, 2000, 0.05), (256, 2000, 0.05), (257, 2000, 0.05), (3000, 6000, 0.05),
-              (20000, 20000, 0.03)]
+              (20000, 20000, 0.03),
+              (262145, 2000, 0.05)]   # one source position past 1,024 x 256: the grid-stride loop runs twice
 
 
 def stat_case(ns, nt, radius):

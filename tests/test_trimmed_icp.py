@@ -268,6 +268,7 @@ SHAPES = [
     (70000, 3000, 0.1),     # large-source path (8 points per thread)
     (1, 1, 10.0),
     (3, 100000, 0.05),
+    (300000, 3000, 0.1),    # more than 1,024 x 256 source positions: the grid-stride loop runs twice
 ]
 _spec_cache = {}
 

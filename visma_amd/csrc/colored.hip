@@ -4,36 +4,20 @@
 // intensity carried along the target's colour gradient g (color_gradient.hip) to the source point's projection into
 // the target's tangent plane (visma_icp.h states the step).
 //
-//  colored_reduce_kernel<S64>   per pair: p, q as the plain reduction forms them, the two rows J_g = sg [p x n | n],
-//                               r_g = sg (p - q).n and J_c = sc [p x h | h], h = -(I - n n^T) g,
-//                               r_c = sc (I_s - (g.(p' - q) + I_t)), sg = sqrt(lambda), sc = sqrt(1 - lambda); both rows
-//                               have the shape [p x v | v], so one helper adds the 21 upper entries of J^T J and the 6
-//                               of J^T r for each.  With K, |p - q|^2, r_g^2 and r_c^2: 31 accumulators.  Then the
-//                               pair-pass tail the trimmed, the robust and the generalized reduction end in
-//                               (device_common.h: block_reduce_store, pair_pass_fold, publish_tagged_stats) with rows
-//                               of kColoredRow doubles: the last workgroup has the column totals and publishes 38
-//                               statistics and the two costs.
+//  ColoredReduce   per pair: p, q as the plain reduction forms them, the two rows J_g = sg [p x n | n], r_g = sg (p - q).n
+//                  and J_c = sc [p x h | h], h = -(I - n n^T) g, r_c = sc (I_s - (g.(p' - q) + I_t)), sg = sqrt(lambda),
+//                  sc = sqrt(1 - lambda); both rows have the shape [p x v | v], so one helper adds the 21 upper entries of
+//                  J^T J and the 6 of J^T r for each.  With K, |p - q|^2, r_g^2 and r_c^2: 31 accumulators.  In the frame
+//                  of pair_pass.h; the last workgroup publishes 38 statistics and the two costs.
 // Intensities and gradients exist in f64 only (k / 255 is not an fp32 number, and the photometric residual is a difference
 // of nearby values); points and normals are the copies the search ran on.  A colour, a gradient or a normal is never an
 // index or an address: a non-finite one reaches the sums only.  No floating-point atomics: a run is bit-identical to
 // itself.  (Reasoning and numbers: DESIGN.md 4.4c6.)
-#include "device_common.h"
+#include "pair_pass.h"
 
 namespace visma {
 
 namespace {
-
-constexpr int kColoredThreads = 256;
-constexpr int kColoredAcc = 31;                          // K, sum |d|^2, 21 of J^T J, 6 of J^T r, sum r_g^2, sum r_c^2
-static_assert(kColoredAcc <= kColoredRow && kColoredRow <= 32, "a partial row holds every accumulator; the fold has 32 columns");
-static_assert(kColoredRow <= kRobustRow && kColoredPublished <= kRobustPublished, "the pair passes share one scratch, sized for the robust pass");
-
-template <bool S64>
-__device__ __forceinline__ void load3(const float4 *a32, const Pt64 *a64, long long i, double v[3])
-{
-    if (S64 && a64) { const Pt64 t = a64[i]; v[0] = t.x; v[1] = t.y; v[2] = t.z; }
-    else { const float4 t = a32[i]; v[0] = (double)t.x; v[1] = (double)t.y; v[2] = (double)t.z; }
-}
 
 // the row J = s [p x v | v] with residual r: acc[2 .. 23) += upper triangle of J^T J (row by row), acc[23 .. 29) += J^T r
 __device__ __forceinline__ void add_row(double *acc, const double p[3], const double v[3], double s, double r)
@@ -54,31 +38,30 @@ __device__ __forceinline__ void add_row(double *acc, const double p[3], const do
 
 }  // namespace
 
-template <bool S64>
-__global__ __launch_bounds__(kColoredThreads) void colored_reduce_kernel(ColoredArgs a)
-{
-    __shared__ double f_tot[32];
-    __shared__ double f_stats[kColoredPublished];
-    const int tid = threadIdx.x;
-    const double *T = a.T64.m;
-    const double sg = a.sqrt_lambda, sc = a.sqrt_one_minus_lambda;
-    double acc[kColoredAcc];
-#pragma unroll
-    for (int k = 0; k < kColoredAcc; k++) acc[k] = 0.0;
-    for (long long i = (long long)blockIdx.x * kColoredThreads + tid; i < a.ns; i += (long long)gridDim.x * kColoredThreads) {
-        const int j = a.idx[i];
-        if (j < 0) continue;
+struct ColoredReduce {
+    using Args = ColoredArgs;
+    static constexpr int kAcc = 31;                      // K, sum |d|^2, 21 of J^T J, 6 of J^T r, sum r_g^2, sum r_c^2
+    static constexpr int kPublished = kColoredPublished;
+    static constexpr bool kPublishTotals = false;
+
+    __device__ explicit ColoredReduce(const Args &) {}
+    template <bool S64>
+    __device__ __forceinline__ void visit(const Args &a, long long i, int j, double *acc)
+    {
+        if (j < 0) return;
+        const double sg = a.sqrt_lambda, sc = a.sqrt_one_minus_lambda;
         double s[3], q[3], n[3];
-        load3<S64>(a.src, a.src64, i, s);
-        load3<S64>(a.tgt, a.tgt64, j, q);
-        load3<S64>(a.nrm, a.nrm64, j, n);
+        pair_load3<S64>(a.src, a.src64, i, s);
+        pair_load3<S64>(a.tgt, a.tgt64, j, q);
+        pair_load3<S64>(a.nrm, a.nrm64, j, n);
         const double g[3] = {a.grad[3ll * j], a.grad[3ll * j + 1], a.grad[3ll * j + 2]};
         const double is = a.src_int[i], it = a.tgt_int[j];
-        // p = T64 * s: the expression of accumulate_pair_d, then both points into the frame of `off`
+        // p = T64 * s, then both points into the frame of `off`
         double p[3], d[3];
+        pair_transform(a.T64, s, p);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            p[k] = (T[4 * k] * s[0] + T[4 * k + 1] * s[1] + T[4 * k + 2] * s[2] + T[4 * k + 3]) + a.off.v[k];
+            p[k] += a.off.v[k];
             q[k] += a.off.v[k];
             d[k] = p[k] - q[k];
         }
@@ -99,24 +82,15 @@ __global__ __launch_bounds__(kColoredThreads) void colored_reduce_kernel(Colored
         acc[29] += rg * rg;
         acc[30] += rc * rc;
     }
-    block_reduce_store<kColoredAcc, kColoredThreads / 64, false, kColoredRow>(acc, a.partials, true);
-    if (!pair_pass_fold<kColoredAcc, kColoredRow>(a.partials, a.ticket, f_tot)) return;
-    if (tid == 0) {
-        for (int k = 0; k < 29; k++) f_stats[k] = f_tot[k];
-        for (int k = 29; k < kNStats; k++) f_stats[k] = 0.0;
-        f_stats[kNStats] = f_tot[29];                        // sum r_g^2
-        f_stats[kNStats + 1] = f_tot[30];                    // sum r_c^2
+    __device__ void finish(const double *tot, double *stats) const
+    {
+        expand_moments<true>(tot, stats);                    // (the point-to-plane layout: the totals are the statistics)
+        stats[kNStats] = tot[29];                            // sum r_g^2
+        stats[kNStats + 1] = tot[30];                        // sum r_c^2
     }
-    publish_tagged_stats<kColoredPublished>(f_stats, a.host_out, a.seq);
-}
+};
 
-hipError_t launch_colored_reduce(const ColoredArgs &a, hipStream_t stream)
-{
-    const dim3 grid((unsigned)robust_reduce_blocks(a.ns)), block(kColoredThreads);
-    if (a.src64) hipLaunchKernelGGL(colored_reduce_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(colored_reduce_kernel<false>, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
+hipError_t launch_colored_reduce(const ColoredArgs &a, hipStream_t stream) { return launch_pair_reduce<ColoredReduce>(a, a.src64 != nullptr, stream); }
 
 // I = (r + g + b) / 3 per point, in f64 and in that order (:94-95), from rows of `stride` doubles picked through `order`
 // (NULL: identity) -- on the host: the one place a colour is read

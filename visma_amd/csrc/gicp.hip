@@ -3,59 +3,40 @@
 // surface element with the point's normal: C = I - (1 - eps) n n^T.  So the sum is C = 2 I - (1 - eps)(n n^T + m m^T),
 // n the target's normal, m = R n_s the source's normal in the target frame (visma_icp.h states the step).
 //
-//  gicp_reduce_kernel<S64>   per pair: p, q as the plain reduction forms them, d = p - q, C, M by the adjugate and the
-//                            determinant of a symmetric 3 x 3, then with J = [-hat(p) | I] the 21 upper entries of
-//                            J^T M J = [[-P M P, P M], [., M]], the 6 of J^T M d = [p x M d; M d], K, |d|^2 and d^T M d:
-//                            30 accumulators.  Then the pair-pass tail the trimmed and the robust reduction end in
-//                            (device_common.h: block_reduce_store, pair_pass_fold, publish_tagged_stats) with rows of
-//                            kGicpRow doubles: the last workgroup has the column totals and publishes 38 statistics
-//                            and the cost.
+//  GicpReduce   per pair: p, q as the plain reduction forms them, d = p - q, C, M by the adjugate and the determinant of a
+//               symmetric 3 x 3, then with J = [-hat(p) | I] the 21 upper entries of J^T M J = [[-P M P, P M], [., M]], the
+//               6 of J^T M d = [p x M d; M d], K, |d|^2 and d^T M d: 30 accumulators.  In the frame of pair_pass.h; the
+//               last workgroup publishes 38 statistics and the cost.
 // A normal is never an index or an address: a non-finite one reaches the sums only; a zero one leaves its point isotropic.
 // No floating-point atomics: a run is bit-identical to itself.  (Reasoning and numbers: DESIGN.md 4.4c5.)
-#include "device_common.h"
+#include "pair_pass.h"
 
 namespace visma {
 
-namespace {
+struct GicpReduce {
+    using Args = GicpArgs;
+    static constexpr int kAcc = 30;                      // K, sum |d|^2, 21 of J^T M J, 6 of J^T M d, sum d^T M d
+    static constexpr int kPublished = kGicpPublished;
+    static constexpr bool kPublishTotals = false;
+    double k1;
 
-constexpr int kGicpThreads = 256;
-constexpr int kGicpAcc = 30;                             // K, sum |d|^2, 21 of J^T M J, 6 of J^T M d, sum d^T M d
-static_assert(kGicpAcc <= kGicpRow && kGicpRow <= 32, "a partial row holds every accumulator; the fold has 32 columns");
-static_assert(kGicpRow <= kRobustRow && kGicpPublished <= kRobustPublished, "the pair passes share one scratch, sized for the robust pass");
-
-template <bool S64>
-__device__ __forceinline__ void load3(const float4 *a32, const Pt64 *a64, long long i, double v[3])
-{
-    if (S64 && a64) { const Pt64 t = a64[i]; v[0] = t.x; v[1] = t.y; v[2] = t.z; }
-    else { const float4 t = a32[i]; v[0] = (double)t.x; v[1] = (double)t.y; v[2] = (double)t.z; }
-}
-
-}  // namespace
-
-template <bool S64>
-__global__ __launch_bounds__(kGicpThreads) void gicp_reduce_kernel(GicpArgs a)
-{
-    __shared__ double f_tot[32];
-    __shared__ double f_stats[kGicpPublished];
-    const int tid = threadIdx.x;
-    const double *T = a.T64.m;
-    const double k1 = 1.0 - a.epsilon;
-    double acc[kGicpAcc];
-#pragma unroll
-    for (int k = 0; k < kGicpAcc; k++) acc[k] = 0.0;
-    for (long long i = (long long)blockIdx.x * kGicpThreads + tid; i < a.ns; i += (long long)gridDim.x * kGicpThreads) {
-        const int j = a.idx[i];
-        if (j < 0) continue;
+    __device__ explicit GicpReduce(const Args &a) : k1(1.0 - a.epsilon) {}
+    template <bool S64>
+    __device__ __forceinline__ void visit(const Args &a, long long i, int j, double *acc)
+    {
+        if (j < 0) return;
+        const double *T = a.T64.m;
         double s[3], q[3], n[3], ns[3];
-        load3<S64>(a.src, a.src64, i, s);
-        load3<S64>(a.tgt, a.tgt64, j, q);
-        load3<S64>(a.nrm, a.nrm64, j, n);
-        load3<S64>(a.snrm, a.snrm64, i, ns);
-        // p = T64 * s: the expression of accumulate_pair_d, then both points into the frame of `off`
+        pair_load3<S64>(a.src, a.src64, i, s);
+        pair_load3<S64>(a.tgt, a.tgt64, j, q);
+        pair_load3<S64>(a.nrm, a.nrm64, j, n);
+        pair_load3<S64>(a.snrm, a.snrm64, i, ns);
+        // p = T64 * s, then both points into the frame of `off`
         double p[3], d[3], m[3];
+        pair_transform(a.T64, s, p);
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-            p[k] = (T[4 * k] * s[0] + T[4 * k + 1] * s[1] + T[4 * k + 2] * s[2] + T[4 * k + 3]) + a.off.v[k];
+            p[k] += a.off.v[k];
             d[k] = p[k] - (q[k] + a.off.v[k]);
             m[k] = T[4 * k] * ns[0] + T[4 * k + 1] * ns[1] + T[4 * k + 2] * ns[2];
         }
@@ -103,22 +84,13 @@ __global__ __launch_bounds__(kGicpThreads) void gicp_reduce_kernel(GicpArgs a)
         acc[26] += e[0]; acc[27] += e[1]; acc[28] += e[2];
         acc[29] += d[0] * e[0] + d[1] * e[1] + d[2] * e[2];
     }
-    block_reduce_store<kGicpAcc, kGicpThreads / 64, false, kGicpRow>(acc, a.partials, true);
-    if (!pair_pass_fold<kGicpAcc, kGicpRow>(a.partials, a.ticket, f_tot)) return;
-    if (tid == 0) {
-        for (int k = 0; k < 29; k++) f_stats[k] = f_tot[k];
-        for (int k = 29; k < kNStats; k++) f_stats[k] = 0.0;
-        f_stats[kNStats] = f_tot[29];                        // sum d^T M d
+    __device__ void finish(const double *tot, double *stats) const
+    {
+        expand_moments<true>(tot, stats);                    // (the point-to-plane layout: the totals are the statistics)
+        stats[kNStats] = tot[29];                            // sum d^T M d
     }
-    publish_tagged_stats<kGicpPublished>(f_stats, a.host_out, a.seq);
-}
+};
 
-hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream)
-{
-    const dim3 grid((unsigned)robust_reduce_blocks(a.ns)), block(kGicpThreads);
-    if (a.src64) hipLaunchKernelGGL(gicp_reduce_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(gicp_reduce_kernel<false>, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
+hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream) { return launch_pair_reduce<GicpReduce>(a, a.src64 != nullptr, stream); }
 
 }  // namespace visma

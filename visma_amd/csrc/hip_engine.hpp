@@ -341,12 +341,13 @@ public:
     void *d_sint_ = nullptr, *d_tint_ = nullptr;            // one double per point: by source position, by original target index
     void *d_grad_ = nullptr;                                // 3 doubles per target point, original order
 
-    // What a pass over the pairs of the last nn_pass works in.  The trimmed and the robust pass share the one instance:
-    // they never overlap on the stream, and each pass re-arms the words it used.  Sized for the larger user.
+    // What a pass over the pairs of the last nn_pass works in.  The trimmed, robust, generalized and colored passes and the
+    // information matrix share the one instance: they never overlap on the stream, and each pass re-arms the words it
+    // used.  Sized by the constants every one of them is checked against (kernels.h, pair_pass.h).
     struct PairScratch {
         unsigned *work = nullptr;                          // kTrimWorkWords: the select's histograms, 4 tickets, its state
-        double *partials = nullptr;                        // 1024 rows of kRobustRow doubles
-        double *host = nullptr, *host_dev = nullptr;       // mapped: kRobustPublished granules {value, sequence number}
+        double *partials = nullptr;                        // kPairMaxBlocks rows of kPairRow doubles
+        double *host = nullptr, *host_dev = nullptr;       // mapped: kPairMaxPublished granules {value, sequence number}
         unsigned long long seq = 0;
         bool dirty = false;                                // a pass did not run to its end: the work words are cleared
         hipError_t ensure();
@@ -354,12 +355,15 @@ public:
         void disarm() { dirty = false; }                   // ... and this when its granules have arrived
         void release();
     } pair_;
-    // the checks and the plain pass under both: K and the sum of d^2 over all pairs in *out (`what`: "trimmed" / "robust")
+    // the checks and the plain pass under all of them: K and the sum of d^2 over all pairs in *out (`what`: "trimmed", ...)
     int pair_pass_begin(const char *what, const Mat4 &Tc, const double *offset, bool plane, PairPass *out);
-    // the arguments both reductions share, the scratch included (a new sequence number)
+    // the arguments the reductions share, the scratch and its ticket word included (a new sequence number)
     int pair_pass_args(const char *what, const Mat4 &Tc, const double *offset, PairPassArgs *a);
     // spins until the n granules at `host` carry `seq`; their values to out[0 .. n)
     int wait_granules(const double *host, int n, unsigned long long seq, const char *what, double *out);
+    // arm, `launches` (the pass's launches on the stream, the reduction last), wait for its n granules -> pub, disarm
+    template <class Launches>
+    int run_pair_pass(const char *what, const PairPassArgs &a, int n, double *pub, Launches launches);
 
     int run_loop_batch(const LoopParams &lp, const std::vector<BatchProblem> &pb, LoopResult *out) override;
 

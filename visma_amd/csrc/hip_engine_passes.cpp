@@ -573,15 +573,15 @@ int HipEngine::get_correspondences(int32_t *idx, float *d2)
     return VISMA_ICP_OK;
 }
 
-// ---- what the trimmed and the robust pass share ----
+// ---- what the passes over the pairs of the last nn_pass share ----
 hipError_t HipEngine::PairScratch::ensure()
 {
     if (host_dev) return hipSuccess;
     hipError_t e = hipMalloc((void **)&work, sizeof(unsigned) * kTrimWorkWords);
-    if (e == hipSuccess) e = hipMalloc((void **)&partials, sizeof(double) * kRobustRow * 1024);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&host, sizeof(double) * 2 * kRobustPublished, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) e = hipMalloc((void **)&partials, sizeof(double) * kPairRow * kPairMaxBlocks);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&host, sizeof(double) * 2 * kPairMaxPublished, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) {
-        std::memset(host, 0, sizeof(double) * 2 * kRobustPublished);
+        std::memset(host, 0, sizeof(double) * 2 * kPairMaxPublished);
         e = hipHostGetDevicePointer((void **)&host_dev, host, 0);
     }
     if (e != hipSuccess) release();                          // (all or nothing: the next call starts over)
@@ -636,6 +636,7 @@ int HipEngine::pair_pass_args(const char *what, const Mat4 &Tc, const double *of
     for (int i = 0; i < 12; i++) a->T64.m[i] = Tc.m[i];
     for (int k = 0; k < 3; k++) a->off.v[k] = offset[k];
     a->partials = pair_.partials;
+    a->ticket = pair_.work + kPairTicketWord;
     a->host_out = pair_.host_dev;
     a->seq = ++pair_.seq;
     return VISMA_ICP_OK;
@@ -664,6 +665,21 @@ int HipEngine::wait_granules(const double *host, int n, unsigned long long seq, 
         const unsigned long long v = g[2 * i];
         std::memcpy(&out[i], &v, sizeof(double));
     }
+    return VISMA_ICP_OK;
+}
+
+// The one sequence of a pair pass on the stream: clear the work words if a pass was cut short, then the pass's launches
+// (a select or the residuals first where it has them, the reduction last), then the wait for the reduction's n tagged
+// granules.
+template <class Launches>
+int HipEngine::run_pair_pass(const char *what, const PairPassArgs &a, int n, double *pub, Launches launches)
+{
+    HIP_TRY(pair_.arm(stream_));
+    const hipError_t e = launches();
+    if (e != hipSuccess) { err_ = std::string(what) + " pass: " + hipGetErrorString(e); return VISMA_ICP_ERR_HIP; }
+    const int rc = wait_granules(pair_.host, n, a.seq, what, pub);
+    if (rc) return rc;
+    pair_.disarm();
     return VISMA_ICP_OK;
 }
 
@@ -707,13 +723,12 @@ int HipEngine::reduce_trimmed(const Mat4 &Tc, const double *offset, double keep,
     a.order = order ? (const int32_t *)d_trim_order_ : nullptr;
     a.work = pair_.work;
     a.mask = (unsigned char *)d_trim_mask_;
-    HIP_TRY(pair_.arm(stream_));
-    HIP_TRY(launch_trim_select(a.d2, a.idx, a.order, ns_, (unsigned)m, a.work, stream_));
-    HIP_TRY(launch_trim_reduce(a, stream_));
     double pub[kTrimPublished];
-    rc = wait_granules(pair_.host, kTrimPublished, a.seq, "trimmed", pub);
+    rc = run_pair_pass("trimmed", a, kTrimPublished, pub, [&] {
+        const hipError_t e = launch_trim_select(a.d2, a.idx, a.order, ns_, (unsigned)m, a.work, stream_);
+        return e != hipSuccess ? e : launch_trim_reduce(a, stream_);
+    });
     if (rc) return rc;
-    pair_.disarm();
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->d2_cut = pub[kNStats];
     if ((int64_t)std::llround(pub[kNStats + 1]) != m) { err_ = "trimmed reduction kept another number of pairs than the select cut"; return VISMA_ICP_ERR_HIP; }
@@ -764,25 +779,24 @@ int HipEngine::reduce_robust(const Mat4 &Tc, const double *offset, bool plane, c
     a.tune_k = cfg.tune * 1.4826;
     a.min_scale = cfg.min_scale;
     a.select_work = pair_.work;
-    a.ticket = pair_.work + kTrimHistWords + 3;              // (the select's rounds take tickets 0 .. 2)
     a.r2_out = (float *)d_rob_r2_;
     a.w_out = (double *)d_rob_w_;
-    HIP_TRY(pair_.arm(stream_));
-    if (automatic) {
-        // the lower median: the m-th smallest ranking value, m = (K + 1) / 2; only its value is used, never the tie order
-        const unsigned m = (unsigned)((K + 1) / 2);
-        const float *rank = (const float *)d_d2_;
-        if (plane) {
-            HIP_TRY(launch_robust_residual(a, stream_));
-            rank = a.r2_out;
-        }
-        HIP_TRY(launch_trim_select(rank, a.idx, nullptr, ns_, m, pair_.work, stream_));
-    }
-    HIP_TRY(launch_robust_reduce(a, plane ? 1 : 0, stream_));
     double pub[kRobustPublished];
-    rc = wait_granules(pair_.host, kRobustPublished, a.seq, "robust", pub);
+    rc = run_pair_pass("robust", a, kRobustPublished, pub, [&] {
+        hipError_t e = hipSuccess;
+        if (automatic) {
+            // the lower median: the m-th smallest ranking value, m = (K + 1) / 2; only its value is used, never the tie order
+            const unsigned m = (unsigned)((K + 1) / 2);
+            const float *rank = (const float *)d_d2_;
+            if (plane) {
+                e = launch_robust_residual(a, stream_);
+                rank = a.r2_out;
+            }
+            if (e == hipSuccess) e = launch_trim_select(rank, a.idx, nullptr, ns_, m, pair_.work, stream_);
+        }
+        return e != hipSuccess ? e : launch_robust_reduce(a, plane ? 1 : 0, stream_);
+    });
     if (rc) return rc;
-    pair_.disarm();
     rob_w_ns_ = ns_;
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->scale = pub[kNStats];
@@ -835,13 +849,9 @@ int HipEngine::reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon,
     a.nrm = (const float4 *)d_nrm_;
     a.snrm = (const float4 *)d_snrm_;
     a.epsilon = epsilon;
-    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
-    HIP_TRY(pair_.arm(stream_));
-    HIP_TRY(launch_gicp_reduce(a, stream_));
     double pub[kGicpPublished];
-    rc = wait_granules(pair_.host, kGicpPublished, a.seq, "generalized", pub);
+    rc = run_pair_pass("generalized", a, kGicpPublished, pub, [&] { return launch_gicp_reduce(a, stream_); });
     if (rc) return rc;
-    pair_.disarm();
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->cost = pub[kNStats];
     return VISMA_ICP_OK;
@@ -929,13 +939,9 @@ int HipEngine::reduce_colored(const Mat4 &Tc, const double *offset, double lambd
     a.tgt_int = (const double *)d_tint_;
     a.sqrt_lambda = std::sqrt(lambda);
     a.sqrt_one_minus_lambda = std::sqrt(1.0 - lambda);
-    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
-    HIP_TRY(pair_.arm(stream_));
-    HIP_TRY(launch_colored_reduce(a, stream_));
     double pub[kColoredPublished];
-    rc = wait_granules(pair_.host, kColoredPublished, a.seq, "colored", pub);
+    rc = run_pair_pass("colored", a, kColoredPublished, pub, [&] { return launch_colored_reduce(a, stream_); });
     if (rc) return rc;
-    pair_.disarm();
     for (int i = 0; i < kNStats; i++) stats[i] = pub[i];
     out->geometric_cost = pub[kNStats];
     out->photometric_cost = pub[kNStats + 1];
@@ -952,13 +958,7 @@ int HipEngine::reduce_information(const Mat4 &Tc, const double *offset, double *
     InformationArgs a;
     rc = pair_pass_args("information", Tc, offset, &a);
     if (rc) return rc;
-    a.ticket = pair_.work + kTrimHistWords + 3;              // (the robust reduction's: the passes never overlap)
-    HIP_TRY(pair_.arm(stream_));
-    HIP_TRY(launch_information_reduce(a, stream_));
-    rc = wait_granules(pair_.host, kInfoAcc, a.seq, "information", sums);
-    if (rc) return rc;
-    pair_.disarm();
-    return VISMA_ICP_OK;
+    return run_pair_pass("information", a, kInfoAcc, sums, [&] { return launch_information_reduce(a, stream_); });
 }
 
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)

@@ -522,7 +522,25 @@ int coop_persist_capacity(int point_to_plane);
 hipError_t launch_finalize_solve_batch(const double *partials, const ProbDesc *descs, DevIcpState *st,
                                        int nprob, hipStream_t stream, int plane = 0);
 
-// ---- passes over the pairs of the last nn_pass (trim.hip, robust.hip): what every such reduction is given ----
+// ---- passes over the pairs of the last nn_pass (pair_pass.h; trim.hip, robust.hip, gicp.hip, colored.hip, information.hip) ----
+// One grid, one row stride, one ticket word and one scratch (HipEngine::PairScratch) for all of them: they never overlap
+// on the stream.
+constexpr int kPairThreads = 256;
+constexpr int kPairRow = 32;                           // doubles per partial row (a pass stores and folds its first kAcc columns)
+constexpr int kPairMaxBlocks = 1024;                   // rows of the partials buffer: the cap of pair_reduce_blocks
+constexpr int kPairMaxPublished = kNStats + 4;         // granules of the mapped host buffer: the robust pass publishes the most
+inline int pair_reduce_blocks(int64_t ns)
+{
+    const int64_t want = (ns + kPairThreads - 1) / kPairThreads;
+    return (int)(want < 1 ? 1 : (want > kPairMaxBlocks ? kPairMaxBlocks : want));
+}
+// the work words (PairScratch::work): the select's histograms, four tickets, then its state
+constexpr int kTrimHistWords = 3 * 2048;               // three rounds of up to 2048 bins
+constexpr int kSelectRounds = 3;                       // each round takes one ticket, then ...
+constexpr int kPairTicketWord = kTrimHistWords + kSelectRounds;   // ... the reduction's
+constexpr int kSelectStateWord = kPairTicketWord + 1;  // {cut d2 bits, need, ties, cut index}
+constexpr int kTrimWorkWords = kSelectStateWord + 4;
+// what every such reduction is given
 struct PairPassArgs {
     const float4 *src = nullptr, *tgt = nullptr;       // fp32 clouds (caller's target order), or ...
     const Pt64 *src64 = nullptr, *tgt64 = nullptr;     // ... the f64 copies when the pass summed from them
@@ -530,31 +548,29 @@ struct PairPassArgs {
     int64_t ns = 0;
     Xform64 T64{};
     Offset64 off{};
-    double *partials = nullptr;                        // one row per workgroup (trimmed: kReduceAcc doubles, robust: kRobustRow)
+    double *partials = nullptr;                        // one row of kPairRow doubles per workgroup
+    unsigned *ticket = nullptr;                        // the word kPairTicketWord of the work words: zero before the first pass (self re-arming)
     double *host_out = nullptr;                        // mapped host memory: granules {value, seq}
     unsigned long long seq = 0;
 };
 
 // ---- trimmed ICP (trim.hip): the m pairs with the smallest key (d2, source index) of the last pass ----
-constexpr int kTrimHistWords = 3 * 2048;               // the select's histograms: three rounds of up to 2048 bins
-constexpr int kTrimWorkWords = kTrimHistWords + 8;     // ... + 4 tickets + the state {cut d2 bits, need, ties, cut index}
 constexpr int kTrimPublished = kNStats + 2;            // granules to the host: 38 statistics, cut d2, kept pairs
 struct TrimReduceArgs : PairPassArgs {
     const float *d2 = nullptr;                         // the winners' fp32 squared distances: the ranking value
     const int32_t *order = nullptr;                    // source position -> caller's source index (NULL: identity)
-    unsigned *work = nullptr;                          // kTrimWorkWords words, zero before the first pass (self re-arming)
+    unsigned *work = nullptr;                          // the work words the select runs on: its state holds the cut
     unsigned char *mask = nullptr;                     // out: 1 per kept source position
 };
 int trim_select_blocks(int64_t ns);
-int trim_reduce_blocks(int64_t ns);
-// the three rounds of the select; m in [1, K]: the rank of the cut among the pairs
+// the three rounds of the select; m in [1, K]: the rank of the cut among the pairs; work: kTrimWorkWords words, zero
+// before the first pass (self re-arming)
 hipError_t launch_trim_select(const float *d2, const int32_t *idx, const int32_t *order, int64_t ns, unsigned m, unsigned *work,
                               hipStream_t stream);
 hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream);
 
 // ---- robust ICP (robust.hip): every pair of the last pass weighted by a function of its own residual ----
 constexpr int kRobustL2 = 0, kRobustHuber = 1, kRobustTukey = 2, kRobustCauchy = 3;   // = VISMA_ICP_ROBUST_*
-constexpr int kRobustRow = 32;                         // doubles per partial row: Acc<PLANE>::N + pairs with w == 0 + sum w r^2
 constexpr int kRobustPublished = kNStats + 4;          // granules to the host: 38 statistics, c, v, pairs with w == 0, sum w r^2
 struct RobustArgs : PairPassArgs {
     const float4 *nrm = nullptr;                       // target normals by original index (point-to-plane), and ...
@@ -562,35 +578,39 @@ struct RobustArgs : PairPassArgs {
     int kernel = kRobustHuber;                         // kRobustHuber / Tukey / Cauchy
     int auto_scale = 0;                                // 0: c = scale; 1: c = max(tune_k * sqrt(v), min_scale), v from the select
     double scale = 0.0, tune_k = 0.0, min_scale = 0.0; // tune_k = tune * 1.4826
-    const unsigned *select_work = nullptr;             // the select's work words (kTrimWorkWords): its state holds v's bits
-    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
+    const unsigned *select_work = nullptr;             // the select's work words: its state holds v's bits
     float *r2_out = nullptr;                           // residual kernel: (float)(r^2) per source position
     double *w_out = nullptr;                           // out: the weight per source position (0: no pair)
 };
-int robust_reduce_blocks(int64_t ns);
 hipError_t launch_robust_residual(const RobustArgs &a, hipStream_t stream);
 hipError_t launch_robust_reduce(const RobustArgs &a, int plane, hipStream_t stream);
 
 // ---- generalized ICP (gicp.hip): every pair of the last pass weighted by the inverse of the sum of both points' surface covariances ----
-constexpr int kGicpRow = 32;                           // doubles per partial row: 30 accumulators (K, sum |d|^2, 21 + 6, the cost)
 constexpr int kGicpPublished = kNStats + 1;            // granules to the host: 38 statistics, sum d^T M d
 struct GicpArgs : PairPassArgs {
     const float4 *nrm = nullptr, *snrm = nullptr;      // target normals by original index, source normals by source position, and ...
     const Pt64 *nrm64 = nullptr, *snrm64 = nullptr;    // ... in f64 where the f64 passes read them (each on its own: NULL = the fp32 copy)
     double epsilon = 1.0;                              // the covariance along the normal, in (0, 1]
-    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
 };
 hipError_t launch_gicp_reduce(const GicpArgs &a, hipStream_t stream);
 
+// ---- colored ICP (colored.hip): a photometric row next to the point-to-plane row of every pair ----
+constexpr int kColoredPublished = kNStats + 2;         // granules to the host: 38 statistics, sum r_g^2, sum r_c^2
+struct ColoredArgs : PairPassArgs {
+    const float4 *nrm = nullptr;                       // target normals by original index, and ...
+    const Pt64 *nrm64 = nullptr;                       // ... in f64 where the f64 passes read them
+    const double *grad = nullptr;                      // the target's colour gradient, 3 doubles per point by original index
+    const double *src_int = nullptr, *tgt_int = nullptr;   // intensities: by source position, by original target index
+    double sqrt_lambda = 1.0, sqrt_one_minus_lambda = 0.0;
+};
+hipError_t launch_colored_reduce(const ColoredArgs &a, hipStream_t stream);
+
 // ---- information matrix (information.hip): the ten sums over the target points of the last pass's pairs ----
 constexpr int kInfoAcc = 10;                           // K, sum x, y, z, sum xx, yy, zz, xy, xz, yz: what is published, too
-constexpr int kInfoRow = 16;                           // doubles per partial row
-struct InformationArgs : PairPassArgs {
-    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
-};
+struct InformationArgs : PairPassArgs {};
 hipError_t launch_information_reduce(const InformationArgs &a, hipStream_t stream);
 
-// ---- colored ICP (color_gradient.hip, colored.hip): a photometric row next to the point-to-plane row of every pair ----
+// ---- the colour side of colored ICP (color_gradient.hip, colored.hip) ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
 inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }
 void color_intensities(const double *rgb, int64_t n, int stride, const int32_t *order, double *out);
@@ -643,17 +663,6 @@ hipError_t ransac_device_chunk(RansacDevice *D, int64_t t0, int64_t n, int8_t *h
                                std::vector<int64_t> *pass_trial, std::vector<double> *pass_T, double *ms);
 // the whole pair list scored under n transforms (h_T: n x 16): pairs with dis2 < max_dist^2 and the sum of their dis2
 hipError_t ransac_score_device(RansacDevice *D, const double *h_T, int64_t n, double max_dist, int64_t *h_good, double *h_err2);
-constexpr int kColoredRow = 32;                       // doubles per partial row: 31 accumulators (K, sum |d|^2, 21 + 6, the two costs)
-constexpr int kColoredPublished = kNStats + 2;         // granules to the host: 38 statistics, sum r_g^2, sum r_c^2
-struct ColoredArgs : PairPassArgs {
-    const float4 *nrm = nullptr;                       // target normals by original index, and ...
-    const Pt64 *nrm64 = nullptr;                       // ... in f64 where the f64 passes read them
-    const double *grad = nullptr;                      // the target's colour gradient, 3 doubles per point by original index
-    const double *src_int = nullptr, *tgt_int = nullptr;   // intensities: by source position, by original target index
-    double sqrt_lambda = 1.0, sqrt_one_minus_lambda = 0.0;
-    unsigned *ticket = nullptr;                        // one word, zero before the first pass (self re-arming)
-};
-hipError_t launch_colored_reduce(const ColoredArgs &a, hipStream_t stream);
 
 // fill n float4 with +inf (target padding)
 hipError_t launch_fill_inf(float4 *dst, int64_t n, hipStream_t stream);

@@ -11,20 +11,17 @@
 //                             many of them are kept (need).  need < ties -- a tie straddles the cut -- is decided by the
 //                             caller's source index: the same select over the 32 index bits of the tied pairs, run by
 //                             that last workgroup alone (rare; the price is three scans of the queries by 256 threads).
-//  trim_reduce_kernel<S64>    the reduction's arithmetic (accumulate_pair / accumulate_pair_d, device_common.h) over
-//                             the pairs with key (d2 bits << 32 | source index) <= cut key, the kept mask, then the
-//                             pair-pass tail (device_common.h: block_reduce_store, pair_pass_fold,
-//                             publish_tagged_stats): the last workgroup has the column totals, expands the moments and
-//                             publishes statistics, cut distance and kept count.  No floating-point atomics: a run is
-//                             bit-identical to itself.
+//  TrimReduce                 the reduction's arithmetic (accumulate_pq_d, device_common.h) over the pairs with key
+//                             (d2 bits << 32 | source index) <= cut key, and the kept mask, in the frame of pair_pass.h;
+//                             the last workgroup expands the moments and publishes statistics, cut distance and kept count.
 // No sort, no copy of the distances to the host.  Four launches per pass (reasoning and numbers: DESIGN.md).
-#include "device_common.h"
+#include "pair_pass.h"
 
 namespace visma {
 
 namespace {
 
-constexpr int kTrimThreads = 256;
+constexpr int kTrimThreads = kPairThreads;
 
 // All 256 threads: the bin of h[0 .. NB) that holds rank `need` (1-based, need <= sum of h) and the count of the bins
 // before it.  Results in res[0] (bin), res[1] (before); h is left as it was.
@@ -153,56 +150,49 @@ __global__ __launch_bounds__(kTrimThreads) void trim_select_kernel(const float *
     }
 }
 
-template <bool S64>
-__global__ __launch_bounds__(kTrimThreads) void trim_reduce_kernel(TrimReduceArgs a)
-{
-    constexpr int NACC = Acc<false>::N;
-    __shared__ double f_tot[32];
-    __shared__ double f_stats[kTrimPublished];
-    const int tid = threadIdx.x;
-    unsigned *tickets = a.work + kTrimHistWords;
-    const unsigned *state = tickets + 4;
-    const unsigned vbits = ld_agent_u32(state), cut_idx = ld_agent_u32(state + 3);
-    const unsigned long long cut_key = ((unsigned long long)vbits << 32) | cut_idx;
-    double acc[NACC];
-#pragma unroll
-    for (int k = 0; k < NACC; k++) acc[k] = 0.0;
-    for (long long i = (long long)blockIdx.x * kTrimThreads + tid; i < a.ns; i += (long long)gridDim.x * kTrimThreads) {
-        const int j = a.idx[i];
+struct TrimReduce {
+    using Args = TrimReduceArgs;
+    static constexpr int kAcc = Acc<false>::N;
+    static constexpr int kPublished = kTrimPublished;
+    static constexpr bool kPublishTotals = false;
+    unsigned vbits;
+    unsigned long long cut_key;
+
+    __device__ explicit TrimReduce(const Args &a)
+    {
+        const unsigned *state = a.work + kSelectStateWord;
+        vbits = ld_agent_u32(state);
+        const unsigned cut_idx = ld_agent_u32(state + 3);
+        cut_key = ((unsigned long long)vbits << 32) | cut_idx;
+    }
+    template <bool S64>
+    __device__ __forceinline__ void visit(const Args &a, long long i, int j, double *acc)
+    {
         const unsigned o = a.order ? (unsigned)a.order[i] : (unsigned)i;
         const unsigned long long key = ((unsigned long long)__float_as_uint(a.d2[i]) << 32) | o;
         const bool kept = j >= 0 && key <= cut_key;
         a.mask[i] = kept ? 1 : 0;
         if (kept) {
-            if constexpr (S64) {
-                const Pt64 s8 = a.src64[i], q8 = a.tgt64[j];
-                accumulate_pair_d<false>(acc, s8.x, s8.y, s8.z, q8.x, q8.y, q8.z, 0.0, 0.0, 0.0, a.T64, a.off);
-            } else {
-                accumulate_pair<false>(acc, a.src[i], a.tgt[j], make_float4(0.f, 0.f, 0.f, 0.f), a.T64, a.off);
-            }
+            double s[3], q[3], t[3];
+            pair_load3<S64>(a.src, a.src64, i, s);
+            pair_load3<S64>(a.tgt, a.tgt64, j, q);
+            pair_transform(a.T64, s, t);
+            accumulate_pq_d<false>(acc, t[0], t[1], t[2], q[0], q[1], q[2], 0.0, 0.0, 0.0, a.off);
         }
     }
-    block_reduce_store<NACC>(acc, a.partials, true);
-    if (!pair_pass_fold<NACC, kReduceAcc>(a.partials, tickets + 3, f_tot)) return;
-    if (tid == 0) {
-        expand_moments<false>(f_tot, f_stats);
-        f_stats[kNStats] = (double)__uint_as_float(vbits);    // the cut: the largest kept d2
-        f_stats[kNStats + 1] = f_tot[0];                       // kept pairs (= stats[0])
+    __device__ void finish(const double *tot, double *stats) const
+    {
+        expand_moments<false>(tot, stats);
+        stats[kNStats] = (double)__uint_as_float(vbits);       // the cut: the largest kept d2
+        stats[kNStats + 1] = tot[0];                           // kept pairs (= stats[0])
     }
-    publish_tagged_stats<kTrimPublished>(f_stats, a.host_out, a.seq);
-}
+};
 
 int trim_select_blocks(int64_t ns)
 {
     // few workgroups with many queries each: what costs is one atomicAdd per non-empty bin per workgroup
     const int64_t want = (ns + 4095) / 4096;
     return (int)(want < 1 ? 1 : (want > 128 ? 128 : want));
-}
-
-int trim_reduce_blocks(int64_t ns)
-{
-    const int64_t want = (ns + kTrimThreads - 1) / kTrimThreads;
-    return (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
 }
 
 hipError_t launch_trim_select(const float *d2, const int32_t *idx, const int32_t *order, int64_t ns, unsigned m, unsigned *work,
@@ -215,12 +205,6 @@ hipError_t launch_trim_select(const float *d2, const int32_t *idx, const int32_t
     return hipGetLastError();
 }
 
-hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream)
-{
-    const dim3 grid((unsigned)trim_reduce_blocks(a.ns)), block(kTrimThreads);
-    if (a.src64) hipLaunchKernelGGL(trim_reduce_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(trim_reduce_kernel<false>, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
+hipError_t launch_trim_reduce(const TrimReduceArgs &a, hipStream_t stream) { return launch_pair_reduce<TrimReduce>(a, a.src64 != nullptr, stream); }
 
 }  // namespace visma
