@@ -10,6 +10,9 @@
 
 #include "Utility/Eigen.h"
 #include "Geometry/PointCloud.h"
+#include "Geometry/Image.h"
+#include "Geometry/RGBDImage.h"
+#include "Camera/PinholeCameraIntrinsic.h"
 #include "Registration/TransformationEstimation.h"
 #include "Registration/Registration.h"
 #include "Registration/Feature.h"
@@ -17,3 +20,6 @@
 #include "Registration/CorrespondenceChecker.h"
 #include "Registration/PoseGraph.h"
 #include "Registration/GlobalOptimization.h"
+#include "Odometry/OdometryOption.h"
+#include "Odometry/RGBDOdometryJacobian.h"
+#include "Odometry/Odometry.h"

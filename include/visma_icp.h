@@ -1080,6 +1080,100 @@ VISMA_ICP_API int visma_icp_information_matrices(visma_icp_ctx *ctx, const visma
 /* The number of points of the source and of the target the context holds (0 for a cloud that is not set). */
 VISMA_ICP_API int visma_icp_get_cloud_sizes(visma_icp_ctx *ctx, int64_t *ns, int64_t *nt);
 
+/* ---- RGB-D odometry: the pose between two consecutive frames and the information matrix of that edge ------------------
+ * (Steinbruecker, Sturm, Cremers: "Real-Time Visual Odometry from Dense RGB-D Images", ICCV workshops 2011 -- the colour
+ * term; Park, Zhou, Koltun: "Colored Point Cloud Registration Revisited", ICCV 2017 -- the hybrid term; the reference's
+ * ComputeRGBDOdometry, Odometry.cpp, RGBDOdometryJacobian.cpp.)  The odometry edges of the pose graph above.
+ *
+ * A frame is a gray image and a depth image (metres), both w x h single-channel fp32, row-major.  intrinsic = {fx, fy,
+ * cx, cy}.  T maps SOURCE-camera coordinates to TARGET-camera coordinates.  The steps, each as the reference computes it
+ * (odometry_image.hip, odometry.hip):
+ *   both frames   Gaussian3 on the grays; depth outside [min_depth, max_depth] or <= 0 becomes NaN, then Gaussian3;
+ *                 the pairs at `init` on the full-size depths; each gray times 0.5 / (its mean over those pairs);
+ *                 n_levels pyramid levels (gray: Gaussian3 + down-sample, depth: down-sample only; level l has
+ *                 floor(w / 2^l) x floor(h / 2^l) pixels and the camera matrix scaled by 2^-l); Sobel dx and dy of the
+ *                 target's gray and depth; the source's xyz image.  The images are the reference's bit for bit.
+ *   pairs at T    per source pixel (u, v) with depth d: uv = d K R K^-1 (u, v, 1) + K t in f64; u_t = (int)(uv.x / uv.z +
+ *                 0.5), v_t likewise (truncation toward zero); inside the image, the target's depth d_t there not NaN,
+ *                 |uv.z - d_t| <= max_depth_diff.
+ *   one step      over the pairs, one row (COLOR) or two (HYBRID, weighted sqrt(1 - 0.968) and sqrt(0.968)) of a
+ *                 Gauss-Newton system in f64; x = -(J^T J)^-1 J^T r unless |det J^T J| < 1e-6 or is not finite; the
+ *                 update Rz(x2) Ry(x1) Rx(x0), translation x[3..6), applied on the left.
+ *   the loop      iterations[0] steps on the COARSEST level, ..., iterations[n_levels - 1] on level 0.  A step without a
+ *                 solution ends the run without success.
+ *   information   over the pairs of the full-size processed depths at the result, the sum G^T G of the section above
+ *                 with q the TARGET's xyz-image point.
+ *
+ * DEVIATIONS from the reference, on purpose:
+ *   - a source pixel whose transformed depth uv.z is <= 0, or whose projection is not finite or beyond 2^30, has no
+ *     pair: the reference casts such a value to int, which is undefined;
+ *   - an all-zero init is the identity EVERYWHERE (the reference treats it so in the loop only, and places the pairs
+ *     of the normalisation with the zero matrix);
+ *   - the information matrix is the pure sum, as visma_icp_information_matrix returns it (the reference adds
+ *     (1 + OpenMP threads) I here too: [5,5] = K + 2 with one thread, K + 4 with three), and the ZERO matrix when the
+ *     run did not succeed (the reference: I);
+ *   - no success is not an error: the call returns VISMA_ICP_OK with success = 0, T = I and the zero matrix.
+ * No floating-point atomics: a run is bit-identical to itself.
+ *
+ * VISMA_ICP_ERR_INVALID, before anything reaches a device: a NULL pointer, w or h < 1, n_levels outside 1 .. 8, a level
+ * that would have no pixels (min(w, h) >> (n_levels - 1) < 1), a negative iteration count, fx or fy zero or not finite,
+ * an unknown method, a level or `which` out of range, a pairs_capacity above 0 and below the sum of the schedule.  A
+ * step, correspondence, image or information call before a prepare: VISMA_ICP_ERR_STATE.  The order for such a call: a
+ * NULL pointer, an unknown method, a `which` outside 0 .. 8 and a level outside 0 .. VISMA_ICP_ODOMETRY_MAX_LEVELS - 1
+ * are INVALID whether or not frames are resident; then STATE without resident frames; then INVALID for a level at or
+ * above the resident pyramid's n_levels.  Sharded contexts: VISMA_ICP_ERR_INVALID.  The frames are independent of the
+ * clouds the context holds. */
+#define VISMA_ICP_ODOMETRY_COLOR 0     /* RGBDOdometryJacobianFromColorTerm */
+#define VISMA_ICP_ODOMETRY_HYBRID 1    /* RGBDOdometryJacobianFromHybridTerm (the reference's default) */
+#define VISMA_ICP_ODOMETRY_MAX_LEVELS 8
+typedef struct {                       /* OdometryOption; NULL where one is taken: 3 levels {20, 10, 5}, 0.03, 0, 4 */
+    int n_levels;
+    int iterations[VISMA_ICP_ODOMETRY_MAX_LEVELS];   /* coarsest level first, as in the reference */
+    double max_depth_diff, min_depth, max_depth;
+} visma_icp_odometry_option;
+typedef struct {
+    int success;
+    int iterations;                    /* steps run, the failing one included */
+    int64_t information_pairs;         /* K of the information matrix (0 without success) */
+    int64_t *pairs;                    /* in: room for pairs_capacity counts, or NULL; out: the pairs of every step */
+    int pairs_capacity;                /* 0: no counts wanted; otherwise at least the sum of option->iterations[0 .. n_levels),
+                                          so that no count is ever cut off (less: VISMA_ICP_ERR_INVALID) */
+} visma_icp_odometry_result;
+/* the images of a level: visma_icp_odometry_get_image's `which` */
+#define VISMA_ICP_ODOMETRY_SRC_GRAY 0
+#define VISMA_ICP_ODOMETRY_SRC_DEPTH 1
+#define VISMA_ICP_ODOMETRY_TGT_GRAY 2
+#define VISMA_ICP_ODOMETRY_TGT_DEPTH 3
+#define VISMA_ICP_ODOMETRY_TGT_GRAY_DX 4
+#define VISMA_ICP_ODOMETRY_TGT_GRAY_DY 5
+#define VISMA_ICP_ODOMETRY_TGT_DEPTH_DX 6
+#define VISMA_ICP_ODOMETRY_TGT_DEPTH_DY 7
+#define VISMA_ICP_ODOMETRY_SRC_XYZ 8   /* three floats per pixel */
+VISMA_ICP_API int visma_icp_odometry_option_default(visma_icp_odometry_option *opt);
+/* The whole of ComputeRGBDOdometry.  option may be NULL; out_info and out_result may be NULL. */
+VISMA_ICP_API int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth,
+                                          const float *tgt_gray, const float *tgt_depth, const double intrinsic[4],
+                                          const double init[16], int method, const visma_icp_odometry_option *option,
+                                          double out_T[16], double out_info[36], visma_icp_odometry_result *out_result);
+/* The first half on its own: both processed pyramids of option->n_levels levels stay resident in the context until the
+ * next prepare or visma_icp_rgbd_odometry (which prepares).  init only places the pairs of the normalisation. */
+VISMA_ICP_API int visma_icp_odometry_prepare(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth,
+                                             const float *tgt_gray, const float *tgt_depth, const double intrinsic[4],
+                                             const double init[16], const visma_icp_odometry_option *option);
+/* A level of a resident pyramid: floor(w / 2^level) x floor(h / 2^level) floats (SRC_XYZ: times three). */
+VISMA_ICP_API int visma_icp_odometry_get_image(visma_icp_ctx *ctx, int which, int level, float *out);
+/* The pairs of a level at T: out_idx[v_s * w_l + u_s] = v_t * w_l + u_t or -1 (may be NULL), *out_k their number.  The
+ * reference's correspondence list is the entries >= 0 in this (row-major source) order. */
+VISMA_ICP_API int visma_icp_odometry_correspondences(visma_icp_ctx *ctx, int level, const double T[16], int32_t *out_idx,
+                                                     int64_t *out_k);
+/* One step's sums at T over those pairs, in the layout of visma_icp_reduce: {K, sum r^2, the 21 upper entries of J^T J
+ * row by row, the 6 of J^T r, nine zeros}; visma_icp_solve_from_stats with VISMA_ICP_SOLVER_GN_EULER solves it.  out_k
+ * and out_sum_r2 (either may be NULL) repeat the first two (the reference prints sum r^2 / rows as "Residual"). */
+VISMA_ICP_API int visma_icp_odometry_step(visma_icp_ctx *ctx, int level, const double T[16], int method,
+                                          double out_stats[VISMA_ICP_NSTATS], int64_t *out_k, double *out_sum_r2);
+/* The information matrix of the resident frames at T (the last step of visma_icp_rgbd_odometry on its own). */
+VISMA_ICP_API int visma_icp_odometry_information(visma_icp_ctx *ctx, const double T[16], double out[36], int64_t *out_k);
+
 /* The pose graph on plain arrays (pure functions; no ctx, no GPU).  Node i has a 4 x 4 pose (row-major, node to world);
  * an edge says: transformation maps the SOURCE node's cloud onto the TARGET node's (PoseGraph.h:52-86).  Odometry edges
  * are certain (uncertain = 0), loop closures uncertain; confidence is the line-process value in [0, 1]. */

@@ -37,6 +37,9 @@
 //                                      GlobalOptimization.h): the information matrix of an edge on the GPU -- one call
 //                                      for every edge of a PoseGraph --, then the line-process pose-graph optimisation
 //                                      on the host.  WITHOUT the identity terms Open3D 0.3.0 adds to the matrix
+//   open3d::cicp::ComputeRGBDOdometry  the odometry edge between two consecutive RGB-D frames and its information matrix
+//                                      (O3D/Core/Odometry/Odometry.h): image pyramids, per-pixel pairs and the colour or
+//                                      hybrid Gauss-Newton rows on the GPU
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -56,6 +59,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <typeinfo>
 #include <vector>
 
@@ -65,6 +69,9 @@
 #include <Core/Registration/PoseGraph.h>
 #include <Core/Registration/GlobalOptimizationConvergenceCriteria.h>
 #include <Core/Registration/GlobalOptimizationMethod.h>
+#include <Core/Geometry/Image.h>
+#include <Core/Geometry/RGBDImage.h>
+#include <Core/Odometry/Odometry.h>
 
 #include "visma_icp.h"
 #include "visma_io.h"
@@ -1651,6 +1658,64 @@ inline Eigen::Matrix4d TransformationEstimationPointToPlaneYaw::ComputeTransform
     return detail::host_update_axis(source, target, corres, true, up_);
 }
 
+// open3d::ComputeRGBDOdometry (Odometry.cpp:490-527) on the GPU: the odometry edge between two consecutive frames and its
+// information matrix -> (success, the pose source camera -> target camera, the 6 x 6).  Both RGBDImages hold single-channel
+// float images of one size (CreateRGBDImageFromColorAndDepth makes them); anything else gives (false, I, 0), as the
+// reference's CheckRGBDImagePair does.  Without success: (false, I, 0) -- the reference returns I as the matrix there; the
+// matrix is the pure sum (visma_icp.h: the deviations).  jacobian_method selects by its type: a
+// RGBDOdometryJacobianFromColorTerm the colour term, anything else the hybrid term.
+inline bool CheckRGBDImagePair(const RGBDImage &source, const RGBDImage &target)
+{
+    const Image *im[4] = {&source.color_, &source.depth_, &target.color_, &target.depth_};
+    for (const Image *i : im)
+        if (i->width_ != im[0]->width_ || i->height_ != im[0]->height_ || i->num_of_channels_ != 1 || i->bytes_per_channel_ != 4 ||
+            !i->HasData()) return false;
+    return true;
+}
+
+// ... on a context of the caller's
+inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
+        visma_icp_ctx *ctx, const RGBDImage &source, const RGBDImage &target, const PinholeCameraIntrinsic &pinhole_camera_intrinsic,
+        const Eigen::Matrix4d &odo_init = Eigen::Matrix4d::Identity(),
+        const RGBDOdometryJacobian &jacobian_method = RGBDOdometryJacobianFromHybridTerm(), const OdometryOption &option = OdometryOption())
+{
+    typedef std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> Out;
+    const Out failed(false, Eigen::Matrix4d::Identity(), Eigen::Matrix6d::Zero());
+    if (!CheckRGBDImagePair(source, target)) return failed;
+    visma_icp_odometry_option opt;
+    visma_icp_odometry_option_default(&opt);
+    opt.n_levels = (int)option.iteration_number_per_pyramid_level_.size();
+    for (int l = 0; l < opt.n_levels && l < VISMA_ICP_ODOMETRY_MAX_LEVELS; l++) opt.iterations[l] = option.iteration_number_per_pyramid_level_[l];
+    opt.max_depth_diff = option.max_depth_diff_; opt.min_depth = option.min_depth_; opt.max_depth = option.max_depth_;
+    const Eigen::Matrix3d &K = pinhole_camera_intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    const int method = typeid(jacobian_method) == typeid(RGBDOdometryJacobianFromColorTerm) ? VISMA_ICP_ODOMETRY_COLOR : VISMA_ICP_ODOMETRY_HYBRID;
+    double init[16], T[16], info[36];
+    detail::to_rowmajor(odo_init, init);
+    visma_icp_odometry_result res = {};
+    detail::check(ctx, visma_icp_rgbd_odometry(ctx, source.color_.width_, source.color_.height_, (const float *)source.color_.data_.data(),
+                                               (const float *)source.depth_.data_.data(), (const float *)target.color_.data_.data(),
+                                               (const float *)target.depth_.data_.data(), k, init, method, &opt, T, info, &res),
+                  "visma_icp_rgbd_odometry");
+    if (!res.success) return failed;
+    Eigen::Matrix4d Tm;
+    Eigen::Matrix6d Im;
+    for (int i = 0; i < 16; i++) Tm(i / 4, i % 4) = T[i];
+    for (int i = 0; i < 36; i++) Im(i / 6, i % 6) = info[i];
+    return Out(true, Tm, Im);
+}
+
+// ... on this thread's context
+inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
+        const RGBDImage &source, const RGBDImage &target, const PinholeCameraIntrinsic &pinhole_camera_intrinsic,
+        const Eigen::Matrix4d &odo_init = Eigen::Matrix4d::Identity(),
+        const RGBDOdometryJacobian &jacobian_method = RGBDOdometryJacobianFromHybridTerm(), const OdometryOption &option = OdometryOption())
+{
+    if (!CheckRGBDImagePair(source, target))                          // (before a context is made)
+        return std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d>(false, Eigen::Matrix4d::Identity(), Eigen::Matrix6d::Zero());
+    return ComputeRGBDOdometry(detail::ThreadContext::instance().get(), source, target, pinhole_camera_intrinsic, odo_init, jacobian_method, option);
+}
+
 }  // namespace cicp
 
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
@@ -1691,6 +1756,12 @@ inline Eigen::Matrix6d GetInformationMatrixFromPointClouds(const PointCloud &sou
                                                            const Eigen::Matrix4d &transformation)
 {
     return cicp::GetInformationMatrixFromPointClouds(source, target, max_correspondence_distance, transformation);
+}
+inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
+        const RGBDImage &source, const RGBDImage &target, const PinholeCameraIntrinsic &pinhole_camera_intrinsic, const Eigen::Matrix4d &odo_init,
+        const RGBDOdometryJacobian &jacobian_method, const OdometryOption &option)
+{
+    return cicp::ComputeRGBDOdometry(source, target, pinhole_camera_intrinsic, odo_init, jacobian_method, option);
 }
 inline void GlobalOptimizationGaussNewton::OptimizePoseGraph(PoseGraph &pose_graph,
                                                              const GlobalOptimizationConvergenceCriteria &criteria,

@@ -73,6 +73,48 @@ class CGlobalOptimizationOption(C.Structure):
                 ("preference_loop_closure", C.c_double), ("reference_node", C.c_int32)]
 
 
+class COdometryOption(C.Structure):
+    """visma_icp_odometry_option"""
+    _fields_ = [("n_levels", C.c_int), ("iterations", C.c_int * 8), ("max_depth_diff", C.c_double), ("min_depth", C.c_double),
+                ("max_depth", C.c_double)]
+
+
+class COdometryResult(C.Structure):
+    """visma_icp_odometry_result"""
+    _fields_ = [("success", C.c_int), ("iterations", C.c_int), ("information_pairs", C.c_int64), ("pairs", C.POINTER(C.c_int64)),
+                ("pairs_capacity", C.c_int)]
+
+
+ODOMETRY_COLOR, ODOMETRY_HYBRID = 0, 1
+# the images of a pyramid level (Context.odometry_image)
+ODOMETRY_IMAGES = ("src_gray", "src_depth", "tgt_gray", "tgt_depth", "tgt_gray_dx", "tgt_gray_dy", "tgt_depth_dx", "tgt_depth_dy", "src_xyz")
+
+
+def odometry_option(iterations=(20, 10, 5), max_depth_diff=0.03, min_depth=0.0, max_depth=4.0):
+    """Open3D's OdometryOption: `iterations` per pyramid level, COARSEST level first (its length is the number of levels)."""
+    o = COdometryOption()
+    its = [int(i) for i in iterations]
+    if not 1 <= len(its) <= 8:
+        raise ValueError("1 .. 8 pyramid levels")
+    o.n_levels = len(its)
+    for i, n in enumerate(its):
+        o.iterations[i] = n
+    o.max_depth_diff, o.min_depth, o.max_depth = float(max_depth_diff), float(min_depth), float(max_depth)
+    return o
+
+
+class OdometryResult:
+    """success, T (4 x 4, source camera -> target camera; the identity without success), information (6 x 6; zero without
+    success), information_pairs (its K), pairs (the number of pairs of every iteration)"""
+
+    def __init__(self, success, T, information, information_pairs, pairs):
+        self.success, self.T, self.information = bool(success), T, information
+        self.information_pairs, self.pairs = int(information_pairs), pairs
+
+    def __iter__(self):                                  # (success, T, information): the reference's tuple
+        return iter((self.success, self.T, self.information))
+
+
 class CGlobalOptimizationCriteria(C.Structure):
     """visma_icp_global_optimization_criteria"""
     _fields_ = [("max_iteration", C.c_int32), ("min_relative_increment", C.c_double),
@@ -296,6 +338,16 @@ def _bind(L):
         L.visma_icp_pose_graph_optimize.argtypes = [_dp, C.c_int, _ep, C.c_int, C.c_int,
                                                     C.POINTER(CGlobalOptimizationCriteria), C.POINTER(CGlobalOptimizationOption)]
         L.visma_icp_get_cloud_sizes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(L, "visma_icp_rgbd_odometry"):            # (A/B runs load older builds through VISMA_ICP_LIB)
+        _oo, _i64 = C.POINTER(COdometryOption), C.POINTER(C.c_int64)
+        frames = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _dp, _dp]
+        L.visma_icp_odometry_option_default.argtypes = [_oo]
+        L.visma_icp_rgbd_odometry.argtypes = frames + [C.c_int, _oo, _dp, _dp, C.POINTER(COdometryResult)]
+        L.visma_icp_odometry_prepare.argtypes = frames + [_oo]
+        L.visma_icp_odometry_get_image.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp]
+        L.visma_icp_odometry_correspondences.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _i64]
+        L.visma_icp_odometry_step.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _i64, _dp]
+        L.visma_icp_odometry_information.argtypes = [C.c_void_p, _dp, _dp, _i64]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -1020,6 +1072,72 @@ class Context:
         self._chk(self.L.visma_icp_get_cloud_sizes(self._h, C.byref(cs), C.byref(ct)))
         self.ns, self.nt = int(cs.value), int(ct.value)
         return out[:n].reshape(n, 6, 6), k[:n]
+
+    # ---- RGB-D odometry (visma_icp.h) ----
+    def _odometry_frames(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init):
+        imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (src_gray, src_depth, tgt_gray, tgt_depth)]
+        if imgs[0].ndim != 2 or any(a.shape != imgs[0].shape for a in imgs):
+            raise ValueError("four h x w images of one size")
+        h, w = imgs[0].shape
+        k = _f64(intrinsic, (4,)); init = _f64(np.eye(4) if init is None else init, (16,))
+        return imgs, k, init, [self._h, w, h] + [_p(a, _fp) for a in imgs] + [_p(k, _dp), _p(init, _dp)]
+
+    def rgbd_odometry(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init=None, method=ODOMETRY_HYBRID, option=None):
+        """Open3D's ComputeRGBDOdometry between two frames (h x w fp32 gray and depth in metres; intrinsic [fx, fy, cx, cy])
+        -> OdometryResult; unpacks as (success, T, information).  Without success: T = I, information = 0, no exception."""
+        option = odometry_option() if option is None else option
+        keep, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
+        T = np.empty(16); info = np.empty(36)
+        cap = max(1, sum(max(0, option.iterations[i]) for i in range(max(0, min(option.n_levels, 8)))))
+        pairs = np.zeros(cap, np.int64)
+        res = COdometryResult(); res.pairs = _p(pairs, C.POINTER(C.c_int64)); res.pairs_capacity = cap
+        self._chk(self.L.visma_icp_rgbd_odometry(*args, int(method), C.byref(option), _p(T, _dp), _p(info, _dp), C.byref(res)))
+        self._odo_shape = (keep[0].shape, option.n_levels)   # (the call prepared: its pyramids are the resident ones)
+        return OdometryResult(res.success, T.reshape(4, 4), info.reshape(6, 6), res.information_pairs, pairs[:res.iterations].copy())
+
+    def odometry_prepare(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init=None, option=None):
+        """Both processed pyramids of a frame pair, resident until the next prepare (what the calls below read)."""
+        option = odometry_option() if option is None else option
+        keep, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
+        self._chk(self.L.visma_icp_odometry_prepare(*args, C.byref(option)))
+        self._odo_shape = (keep[0].shape, option.n_levels)
+
+    def _odometry_level_shape(self, level):
+        (h, w), n = getattr(self, "_odo_shape", ((0, 0), 0))
+        for _ in range(max(0, min(int(level), 8))):
+            h, w = h // 2, w // 2
+        return h, w
+
+    def odometry_image(self, which, level=0):
+        """A level of a resident pyramid: `which` is an index or a name of ODOMETRY_IMAGES -> h_l x w_l fp32 (src_xyz: x 3)."""
+        which = ODOMETRY_IMAGES.index(which) if isinstance(which, str) else int(which)
+        h, w = self._odometry_level_shape(level)
+        out = np.empty((max(h, 1), max(w, 1), 3) if which == 8 else (max(h, 1), max(w, 1)), np.float32)
+        self._chk(self.L.visma_icp_odometry_get_image(self._h, which, int(level), _p(out, _fp)))
+        return out
+
+    def odometry_correspondences(self, level=0, T=None):
+        """The pairs of a level at T -> (idx, K): idx[v_s * w + u_s] = v_t * w + u_t or -1; np.flatnonzero(idx >= 0) and
+        idx[idx >= 0] are the reference's correspondence list."""
+        T = _f64(np.eye(4) if T is None else T, (16,))
+        h, w = self._odometry_level_shape(level)
+        idx = np.empty(max(h * w, 1), np.int32); k = C.c_int64(0)
+        self._chk(self.L.visma_icp_odometry_correspondences(self._h, int(level), _p(T, _dp), _p(idx, _ip), C.byref(k)))
+        return idx[:h * w], k.value
+
+    def odometry_step(self, level=0, T=None, method=ODOMETRY_HYBRID):
+        """One iteration's sums at T -> (stats[38], K, sum r^2); solve_from_stats(stats, SOLVER_GN_EULER) is the update."""
+        T = _f64(np.eye(4) if T is None else T, (16,))
+        stats = np.empty(38); k = C.c_int64(0); r2 = C.c_double(0)
+        self._chk(self.L.visma_icp_odometry_step(self._h, int(level), _p(T, _dp), int(method), _p(stats, _dp), C.byref(k), C.byref(r2)))
+        return stats, k.value, r2.value
+
+    def odometry_information(self, T=None):
+        """The information matrix of the resident frames at T -> (6 x 6, K)."""
+        T = _f64(np.eye(4) if T is None else T, (16,))
+        out = np.empty(36); k = C.c_int64(0)
+        self._chk(self.L.visma_icp_odometry_information(self._h, _p(T, _dp), _p(out, _dp), C.byref(k)))
+        return out.reshape(6, 6), k.value
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""

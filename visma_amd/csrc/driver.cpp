@@ -1551,6 +1551,171 @@ int visma_icp_information_matrices(visma_icp_ctx *ctx, const visma_icp_problem *
     return VISMA_ICP_OK;
 }
 
+// ---- RGB-D odometry (odometry_image.hip, odometry.hip) -----------------------------------------------------------------
+int visma_icp_odometry_option_default(visma_icp_odometry_option *opt)
+{
+    if (!opt) return VISMA_ICP_ERR_INVALID;
+    std::memset(opt, 0, sizeof(*opt));
+    opt->n_levels = 3;
+    opt->iterations[0] = 20; opt->iterations[1] = 10; opt->iterations[2] = 5;
+    opt->max_depth_diff = 0.03; opt->min_depth = 0.0; opt->max_depth = 4.0;
+    return VISMA_ICP_OK;
+}
+
+// an all-zero pose is the identity (visma_icp.h)
+static Mat4 odometry_pose(const double T[16])
+{
+    bool zero = true;
+    for (int i = 0; i < 16; i++) zero = zero && T[i] == 0.0;
+    return zero ? Mat4::identity() : Mat4::from(T);
+}
+
+// every argument check of a frame pair, before anything reaches a device; *in is what the engine is given
+static int check_odometry_frames(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
+                                 const float *tgt_depth, const double *intrinsic, const double *init,
+                                 const visma_icp_odometry_option *option, visma_icp_odometry_option *opt, Engine::OdometryInput *in)
+{
+    if (!src_gray || !src_depth || !tgt_gray || !tgt_depth || !intrinsic || !init) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (w < 1 || h < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image needs w >= 1 and h >= 1");
+    if ((int64_t)w * h > (int64_t)1 << 30) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image of more than 2^30 pixels");
+    if (option) *opt = *option; else visma_icp_odometry_option_default(opt);
+    if (opt->n_levels < 1 || opt->n_levels > VISMA_ICP_ODOMETRY_MAX_LEVELS) return ctx->fail(VISMA_ICP_ERR_INVALID, "n_levels outside 1 .. 8");
+    if ((std::min(w, h) >> (opt->n_levels - 1)) < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "a pyramid level without pixels");
+    for (int l = 0; l < opt->n_levels; l++)
+        if (opt->iterations[l] < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "a negative iteration count");
+    if (!std::isfinite(intrinsic[0]) || !std::isfinite(intrinsic[1]) || intrinsic[0] == 0.0 || intrinsic[1] == 0.0)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "a focal length that is zero or not finite");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "RGB-D odometry runs on one rank");
+    in->w = w; in->h = h; in->n_levels = opt->n_levels;
+    in->src_gray = src_gray; in->src_depth = src_depth; in->tgt_gray = tgt_gray; in->tgt_depth = tgt_depth;
+    in->fx = intrinsic[0]; in->fy = intrinsic[1]; in->cx = intrinsic[2]; in->cy = intrinsic[3];
+    in->init = odometry_pose(init);
+    in->max_depth_diff = opt->max_depth_diff; in->min_depth = opt->min_depth; in->max_depth = opt->max_depth;
+    return VISMA_ICP_OK;
+}
+
+static int odometry_prepare_checked(visma_icp_ctx *ctx, const Engine::OdometryInput &in)
+{
+    ctx->odo.ready = false;
+    int rc = ctx->eng->odometry_prepare(in);
+    if (rc) return ctx->eng_fail(rc);
+    ctx->odo.ready = true; ctx->odo.w = in.w; ctx->odo.h = in.h; ctx->odo.n_levels = in.n_levels;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_prepare(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
+                               const float *tgt_depth, const double intrinsic[4], const double init[16],
+                               const visma_icp_odometry_option *option)
+{
+    CTX_CHECK();
+    visma_icp_odometry_option opt;
+    Engine::OdometryInput in;
+    if (int rc = check_odometry_frames(ctx, w, h, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init, option, &opt, &in)) return rc;
+    return odometry_prepare_checked(ctx, in);
+}
+
+// a level no pyramid can have is INVALID whatever the state; then the call order; then the resident pyramid's own depth
+static int check_odometry_level(visma_icp_ctx *ctx, int level)
+{
+    if (level < 0 || level >= VISMA_ICP_ODOMETRY_MAX_LEVELS) return ctx->fail(VISMA_ICP_ERR_INVALID, "level out of range");
+    if (!ctx->odo.ready) return ctx->fail(VISMA_ICP_ERR_STATE, "no odometry frames: visma_icp_odometry_prepare first");
+    if (level >= ctx->odo.n_levels) return ctx->fail(VISMA_ICP_ERR_INVALID, "level out of range");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_get_image(visma_icp_ctx *ctx, int which, int level, float *out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (which < 0 || which >= kOdoImages) return ctx->fail(VISMA_ICP_ERR_INVALID, "which out of range");
+    if (int rc = check_odometry_level(ctx, level)) return rc;
+    int rc = ctx->eng->odometry_get_image(which, level, out);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_correspondences(visma_icp_ctx *ctx, int level, const double T[16], int32_t *out_idx, int64_t *out_k)
+{
+    CTX_CHECK();
+    if (!T || !out_k) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (int rc = check_odometry_level(ctx, level)) return rc;
+    int rc = ctx->eng->odometry_correspondences(level, odometry_pose(T), out_idx, out_k);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_step(visma_icp_ctx *ctx, int level, const double T[16], int method, double out_stats[VISMA_ICP_NSTATS],
+                            int64_t *out_k, double *out_sum_r2)
+{
+    CTX_CHECK();
+    if (!T || !out_stats) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (method != VISMA_ICP_ODOMETRY_COLOR && method != VISMA_ICP_ODOMETRY_HYBRID) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown odometry method");
+    if (int rc = check_odometry_level(ctx, level)) return rc;
+    int rc = ctx->eng->odometry_step(level, odometry_pose(T), method, out_stats);
+    if (rc) return ctx->eng_fail(rc);
+    if (out_k) *out_k = (int64_t)std::llround(out_stats[0]);
+    if (out_sum_r2) *out_sum_r2 = out_stats[1];
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_information(visma_icp_ctx *ctx, const double T[16], double out[36], int64_t *out_k)
+{
+    CTX_CHECK();
+    if (!T || !out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (int rc = check_odometry_level(ctx, 0)) return rc;
+    double sums[kInfoAcc];
+    int rc = ctx->eng->odometry_information(odometry_pose(T), sums);
+    if (rc) return ctx->eng_fail(rc);
+    information_from_sums(sums, out);
+    if (out_k) *out_k = (int64_t)std::llround(sums[0]);
+    return VISMA_ICP_OK;
+}
+
+// ComputeRGBDOdometry: prepare, ComputeMultiscale (per iteration the correspondence kernel and the reduction on the
+// stream, the 6 x 6 solve here), CreateInformationMatrix
+int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
+                            const float *tgt_depth, const double intrinsic[4], const double init[16], int method,
+                            const visma_icp_odometry_option *option, double out_T[16], double out_info[36],
+                            visma_icp_odometry_result *out_result)
+{
+    CTX_CHECK();
+    if (!out_T) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (method != VISMA_ICP_ODOMETRY_COLOR && method != VISMA_ICP_ODOMETRY_HYBRID) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown odometry method");
+    if (out_result && (out_result->pairs_capacity < 0 || (out_result->pairs_capacity > 0 && !out_result->pairs)))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "pairs_capacity without room");
+    visma_icp_odometry_option opt;
+    Engine::OdometryInput in;
+    if (int rc = check_odometry_frames(ctx, w, h, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init, option, &opt, &in)) return rc;
+    int64_t schedule = 0;
+    for (int l = 0; l < opt.n_levels; l++) schedule += opt.iterations[l];
+    if (out_result && out_result->pairs_capacity > 0 && out_result->pairs_capacity < schedule)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "pairs_capacity below the sum of the schedule");
+    if (int rc = odometry_prepare_checked(ctx, in)) return rc;
+    Mat4 T = in.init;
+    bool ok = true;
+    int steps = 0;
+    for (int level = opt.n_levels - 1; level >= 0 && ok; level--)
+        for (int it = 0; it < opt.iterations[opt.n_levels - level - 1] && ok; it++) {
+            double stats[kNStats];
+            int rc = ctx->eng->odometry_step(level, T, method, stats);
+            if (rc) return ctx->eng_fail(rc);
+            if (out_result && out_result->pairs_capacity > 0) out_result->pairs[steps] = (int64_t)std::llround(stats[0]);
+            steps++;
+            const Mat4 step = gn_from_stats(stats, false, &ok);
+            T = step * T;
+        }
+    const Mat4 I = Mat4::identity();
+    for (int i = 0; i < 16; i++) out_T[i] = ok ? T.m[i] : I.m[i];
+    if (out_info) for (int i = 0; i < 36; i++) out_info[i] = 0.0;
+    int64_t K = 0;
+    if (ok && (out_info || out_result)) {
+        double info[36];
+        int rc = visma_icp_odometry_information(ctx, T.m, info, &K);
+        if (rc) return rc;
+        if (out_info) std::memcpy(out_info, info, sizeof(info));
+    }
+    if (out_result) { out_result->success = ok ? 1 : 0; out_result->iterations = steps; out_result->information_pairs = K; }
+    return VISMA_ICP_OK;
+}
+
 int visma_icp_set_nn_mode(visma_icp_ctx *ctx, int nn_mode)
 {
     CTX_CHECK();

@@ -32,6 +32,8 @@ struct visma_icp_ctx {
     void *host_allreduce_user = nullptr;
     int rank = 0, nranks = 1;
     int64_t ns_total = 0;
+    // the frame pair of the last visma_icp_odometry_prepare (resident on the engine): what the later calls check against
+    struct { bool ready = false; int w = 0, h = 0, n_levels = 0; } odo;
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

@@ -376,6 +376,33 @@ public:
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;
     }
+    // RGB-D odometry (odometry_image.hip, odometry.hip): the processed pyramids of a frame pair, resident until the next
+    // prepare; what the driver checked (sizes, levels, focal lengths) arrives as it is.  `init` only places the pairs
+    // NormalizeIntensity takes its means over.
+    struct OdometryInput {
+        int w = 0, h = 0, n_levels = 1;
+        const float *src_gray = nullptr, *src_depth = nullptr, *tgt_gray = nullptr, *tgt_depth = nullptr;
+        double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
+        Mat4 init;
+        double max_depth_diff = 0.03, min_depth = 0.0, max_depth = 4.0;
+    };
+    virtual int odometry_prepare(const OdometryInput &) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // a level's image (kOdo*: w_l x h_l floats; kOdoSrcXyz: three per pixel)
+    virtual int odometry_get_image(int /* which */, int /* level */, float *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // the pairs of a level at T: per source pixel the target pixel or -1 (idx may be NULL), and their number
+    virtual int odometry_correspondences(int /* level */, const Mat4 &, int32_t * /* idx */, int64_t * /* K */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // ... and the 38 statistics of one Gauss-Newton step over them: {K, sum r^2, 21 of J^T J, 6 of J^T r, zeros}
+    virtual int odometry_step(int /* level */, const Mat4 &, int /* method */, double * /* stats */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // the ten sums of information.hip over the target's xyz image at the full-size pairs of T
+    virtual int odometry_information(const Mat4 &, double * /* sums[10] */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

@@ -50,6 +50,7 @@ public:
         if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
         free_dev(d_trim_mask_); free_dev(d_trim_order_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
         pair_.release();
+        if (odo_.arena) (void)hipFree(odo_.arena);
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -330,6 +331,15 @@ public:
     // information matrix (information.hip): the plain pass, then the ten sums over the target points of its pairs
     int reduce_information(const Mat4 &Tc, const double *offset, double *sums, PairPass *out) override;
 
+    // RGB-D odometry (odometry_image.hip, odometry.hip): both processed pyramids of the last odometry_prepare in ONE device
+    // allocation (grow-only), the pair list of the last correspondence launch, and the passes over it in the shared
+    // PairScratch.  Independent of the clouds: neither side drops the other.
+    int odometry_prepare(const OdometryInput &in) override;
+    int odometry_get_image(int which, int level, float *out) override;
+    int odometry_correspondences(int level, const Mat4 &T, int32_t *idx, int64_t *K) override;
+    int odometry_step(int level, const Mat4 &T, int method, double *stats) override;
+    int odometry_information(const Mat4 &T, double *sums) override;
+
     // colored ICP (color_gradient.hip, colored.hip): f64 intensities of both clouds, the target's colour gradient, then the
     // plain pass and the reduction over the two rows per pair
     int set_source_intensity(const double *by_position, int64_t ns) override;
@@ -411,6 +421,25 @@ public:
     void launch_config(int *tiles, int *splits) override { *tiles = plan_.src_tiles; *splits = plan_.tgt_splits; }
 
 private:
+    // RGB-D odometry: the resident pyramids and what the entry points above share
+    struct OdoState {
+        bool ready = false;
+        int n_levels = 0;
+        int w[kOdoMaxLevels] = {}, h[kOdoMaxLevels] = {};
+        double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0, max_depth_diff = 0.0;   // level 0; level l: times 2^-l, exactly
+        float *img[kOdoMaxLevels][kOdoSrcXyz] = {};          // the eight single-channel images of a level
+        float4 *src_xyz[kOdoMaxLevels] = {};
+        float4 *tgt_xyz = nullptr;                           // level 0: the information matrix's target cloud
+        int32_t *idx = nullptr;                              // w[0] * h[0]
+        float *tmp[2] = {nullptr, nullptr};                  // w[0] * h[0] each: between the two passes of a filter
+        void *arena = nullptr;
+        size_t arena_bytes = 0;
+    } odo_;
+    // the launch of the correspondence kernel of `level` at T into odo_.idx
+    int odometry_launch_correspondences(int level, const Mat4 &T);
+    // the arguments every pass over odo_.idx shares: no clouds, the scratch and its ticket word (a new sequence number)
+    void odometry_pass_args(int level, PairPassArgs *a);
+
     // Cloud-sized device buffers are recycled: a registration after another of about the same size
     // (every caller's loop) re-uses them instead of paying hipFree + hipMalloc (a device sync and ~0.5 ms
     // per 100 MB).  pool_alloc'ed pointers are returned by the ordinary free_dev.

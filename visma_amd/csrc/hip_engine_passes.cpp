@@ -961,6 +961,209 @@ int HipEngine::reduce_information(const Mat4 &Tc, const double *offset, double *
     return run_pair_pass("information", a, kInfoAcc, sums, [&] { return launch_information_reduce(a, stream_); });
 }
 
+// ---- RGB-D odometry (odometry_image.hip, odometry.hip) ----
+// Both processed pyramids of a frame pair, as InitializeRGBDOdometry and ComputeMultiscale build them, left on the device:
+// Gaussian3 on the grays, preprocess + Gaussian3 on the depths, the pairs at `init` on the full-size depths for
+// NormalizeIntensity's two means (one reduction; the host divides and the scale goes back as a kernel argument), then per
+// level Gaussian3 + down-sample of the grays and down-sample of the depths, the target's four Sobel images and the
+// source's xyz image.  Everything on the stream; one host turn-around for the means, one wait at the end.
+int HipEngine::odometry_prepare(const OdometryInput &in)
+{
+    if (is_sharded()) { err_ = "RGB-D odometry runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(device_));
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    HIP_TRY(pair_.ensure());
+    OdoState &o = odo_;
+    o.ready = false;
+    o.n_levels = in.n_levels;
+    o.fx = in.fx; o.fy = in.fy; o.cx = in.cx; o.cy = in.cy; o.max_depth_diff = in.max_depth_diff;
+    size_t bytes = 0;
+    auto take = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
+    size_t at_img[kOdoMaxLevels][kOdoSrcXyz], at_xyz[kOdoMaxLevels];
+    for (int l = 0; l < in.n_levels; l++) {
+        o.w[l] = l ? o.w[l - 1] / 2 : in.w;
+        o.h[l] = l ? o.h[l - 1] / 2 : in.h;
+        const size_t n = (size_t)o.w[l] * o.h[l];
+        for (int k = 0; k < kOdoSrcXyz; k++) at_img[l][k] = take(sizeof(float) * n);
+        at_xyz[l] = take(sizeof(float4) * n);
+    }
+    const size_t n0 = (size_t)in.w * in.h;
+    const size_t at_txyz = take(sizeof(float4) * n0), at_idx = take(sizeof(int32_t) * n0);
+    const size_t at_tmp0 = take(sizeof(float) * n0), at_tmp1 = take(sizeof(float) * n0);
+    if (bytes > o.arena_bytes) {
+        HIP_TRY(hipStreamSynchronize(stream_));
+        if (o.arena) (void)hipFree(o.arena);
+        o.arena = nullptr; o.arena_bytes = 0;
+        HIP_TRY(hipMalloc(&o.arena, bytes));
+        o.arena_bytes = bytes;
+    }
+    char *base = (char *)o.arena;
+    for (int l = 0; l < in.n_levels; l++) {
+        for (int k = 0; k < kOdoSrcXyz; k++) o.img[l][k] = (float *)(base + at_img[l][k]);
+        o.src_xyz[l] = (float4 *)(base + at_xyz[l]);
+    }
+    o.tgt_xyz = (float4 *)(base + at_txyz);
+    o.idx = (int32_t *)(base + at_idx);
+    o.tmp[0] = (float *)(base + at_tmp0); o.tmp[1] = (float *)(base + at_tmp1);
+
+    // a separable 3-tap filter: rows into tmp[1], columns into `out` (`src` may be tmp[0], never tmp[1] or `out`)
+    auto filter = [&](const float *src, float *out, int w, int h, const float kx[3], const float ky[3]) {
+        hipError_t e = launch_odo_filter3(src, o.tmp[1], w, h, kx[0], kx[1], kx[2], 0, stream_);
+        return e != hipSuccess ? e : launch_odo_filter3(o.tmp[1], out, w, h, ky[0], ky[1], ky[2], 1, stream_);
+    };
+    static const float kGauss[3] = {0.25f, 0.5f, 0.25f}, kSobel1[3] = {-1.0f, 0.0f, 1.0f}, kSobel2[3] = {1.0f, 2.0f, 1.0f};
+    const int W = in.w, H = in.h;
+    const struct { const float *host; int which; bool depth; } frames[4] = {
+        {in.src_gray, kOdoSrcGray, false}, {in.tgt_gray, kOdoTgtGray, false}, {in.src_depth, kOdoSrcDepth, true}, {in.tgt_depth, kOdoTgtDepth, true}};
+    for (const auto &f : frames) {
+        HIP_TRY(hipMemcpyAsync(o.tmp[0], f.host, sizeof(float) * n0, hipMemcpyHostToDevice, stream_));
+        if (f.depth) HIP_TRY(launch_odo_preprocess_depth(o.tmp[0], o.tmp[0], (int64_t)n0, in.min_depth, in.max_depth, stream_));
+        HIP_TRY(filter(o.tmp[0], o.img[0][f.which], W, H, kGauss, kGauss));
+        HIP_TRY(hipStreamSynchronize(stream_));                  // (the caller's image is pageable memory; tmp[0] is reused)
+    }
+    // NormalizeIntensity: the means over the pairs at `init`
+    int rc = odometry_launch_correspondences(0, in.init);
+    if (rc) return rc;
+    OdoMeanArgs ma;
+    odometry_pass_args(0, &ma);
+    ma.gray_s = o.img[0][kOdoSrcGray]; ma.gray_t = o.img[0][kOdoTgtGray];
+    double sums[kOdoMeanAcc];
+    rc = run_pair_pass("odometry mean", ma, kOdoMeanAcc, sums, [&] { return launch_odo_mean_reduce(ma, stream_); });
+    if (rc) return rc;
+    const double K = sums[0];
+    const double mean_s = sums[1] / K, mean_t = sums[2] / K;     // (K == 0: NaN, and so is every gray after it, as in the reference)
+    HIP_TRY(launch_odo_scale(o.img[0][kOdoSrcGray], (int64_t)n0, 0.5 / mean_s, stream_));
+    HIP_TRY(launch_odo_scale(o.img[0][kOdoTgtGray], (int64_t)n0, 0.5 / mean_t, stream_));
+    for (int l = 0; l < in.n_levels; l++) {
+        const int w = o.w[l], h = o.h[l];
+        if (l > 0) {
+            const int pw = o.w[l - 1], ph = o.h[l - 1];
+            for (int k : {kOdoSrcGray, kOdoTgtGray}) {
+                HIP_TRY(filter(o.img[l - 1][k], o.tmp[0], pw, ph, kGauss, kGauss));
+                HIP_TRY(launch_odo_downsample(o.tmp[0], pw, ph, o.img[l][k], stream_));
+            }
+            for (int k : {kOdoSrcDepth, kOdoTgtDepth}) HIP_TRY(launch_odo_downsample(o.img[l - 1][k], pw, ph, o.img[l][k], stream_));
+        }
+        HIP_TRY(filter(o.img[l][kOdoTgtGray], o.img[l][kOdoTgtGrayDx], w, h, kSobel1, kSobel2));
+        HIP_TRY(filter(o.img[l][kOdoTgtGray], o.img[l][kOdoTgtGrayDy], w, h, kSobel2, kSobel1));
+        HIP_TRY(filter(o.img[l][kOdoTgtDepth], o.img[l][kOdoTgtDepthDx], w, h, kSobel1, kSobel2));
+        HIP_TRY(filter(o.img[l][kOdoTgtDepth], o.img[l][kOdoTgtDepthDy], w, h, kSobel2, kSobel1));
+        const double s = std::ldexp(1.0, -l);                    // the camera matrix of level l: 0.5 * the previous one, exactly
+        HIP_TRY(launch_odo_xyz(o.img[l][kOdoSrcDepth], w, h, in.cx * s, in.cy * s, 1.0 / (in.fx * s), 1.0 / (in.fy * s), o.src_xyz[l], stream_));
+    }
+    HIP_TRY(launch_odo_xyz(o.img[0][kOdoTgtDepth], W, H, in.cx, in.cy, 1.0 / in.fx, 1.0 / in.fy, o.tgt_xyz, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    o.ready = true;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::odometry_get_image(int which, int level, float *out)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!odo_.ready) { err_ = "no odometry frames: odometry_prepare first"; return VISMA_ICP_ERR_STATE; }
+    const size_t n = (size_t)odo_.w[level] * odo_.h[level];
+    HIP_TRY(hipStreamSynchronize(stream_));
+    if (which < kOdoSrcXyz) {
+        HIP_TRY(hipMemcpy(out, odo_.img[level][which], sizeof(float) * n, hipMemcpyDeviceToHost));
+        return VISMA_ICP_OK;
+    }
+    std::vector<float4> p(n);
+    HIP_TRY(hipMemcpy(p.data(), odo_.src_xyz[level], sizeof(float4) * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) { out[3 * i] = p[i].x; out[3 * i + 1] = p[i].y; out[3 * i + 2] = p[i].z; }
+    return VISMA_ICP_OK;
+}
+
+// K R K^-1 and K t of ComputeCorrespondence in f64 on the host; K = [fx 0 cx; 0 fy cy; 0 0 1] of the level, its inverse
+// written out
+int HipEngine::odometry_launch_correspondences(int level, const Mat4 &T)
+{
+    const OdoState &o = odo_;
+    const double s = std::ldexp(1.0, -level);
+    const double fx = o.fx * s, fy = o.fy * s, cx = o.cx * s, cy = o.cy * s;
+    const double K[9] = {fx, 0.0, cx, 0.0, fy, cy, 0.0, 0.0, 1.0};
+    const double Ki[9] = {1.0 / fx, 0.0, -cx / fx, 0.0, 1.0 / fy, -cy / fy, 0.0, 0.0, 1.0};
+    double KR[9];
+    OdoProjection P;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) KR[i * 3 + j] = K[i * 3] * T(0, j) + K[i * 3 + 1] * T(1, j) + K[i * 3 + 2] * T(2, j);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) P.m[i * 3 + j] = KR[i * 3] * Ki[j] + KR[i * 3 + 1] * Ki[3 + j] + KR[i * 3 + 2] * Ki[6 + j];
+        P.kt[i] = K[i * 3] * T(0, 3) + K[i * 3 + 1] * T(1, 3) + K[i * 3 + 2] * T(2, 3);
+    }
+    HIP_TRY(launch_odo_correspondences(o.img[level][kOdoSrcDepth], o.img[level][kOdoTgtDepth], o.w[level], o.h[level], P, o.max_depth_diff,
+                                       o.idx, stream_));
+    return VISMA_ICP_OK;
+}
+
+void HipEngine::odometry_pass_args(int level, PairPassArgs *a)
+{
+    a->idx = odo_.idx;
+    a->ns = (int64_t)odo_.w[level] * odo_.h[level];
+    a->partials = pair_.partials;
+    a->ticket = pair_.work + kPairTicketWord;
+    a->host_out = pair_.host_dev;
+    a->seq = ++pair_.seq;
+}
+
+int HipEngine::odometry_correspondences(int level, const Mat4 &T, int32_t *idx, int64_t *K)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!odo_.ready) { err_ = "no odometry frames: odometry_prepare first"; return VISMA_ICP_ERR_STATE; }
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    int rc = odometry_launch_correspondences(level, T);
+    if (rc) return rc;
+    const size_t n = (size_t)odo_.w[level] * odo_.h[level];
+    std::vector<int32_t> own;
+    if (!idx) { own.resize(n); idx = own.data(); }
+    HIP_TRY(hipMemcpyAsync(idx, odo_.idx, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));
+    int64_t k = 0;
+    for (size_t i = 0; i < n; i++) k += idx[i] >= 0;
+    if (K) *K = k;
+    return VISMA_ICP_OK;
+}
+
+// One iteration's device work: the correspondence kernel and the reduction on the stream; the host waits for the
+// reduction's tagged granules like reduce() waits for its own.
+int HipEngine::odometry_step(int level, const Mat4 &T, int method, double *stats)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!odo_.ready) { err_ = "no odometry frames: odometry_prepare first"; return VISMA_ICP_ERR_STATE; }
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    HIP_TRY(pair_.ensure());
+    int rc = odometry_launch_correspondences(level, T);
+    if (rc) return rc;
+    const OdoState &o = odo_;
+    OdometryArgs a;
+    odometry_pass_args(level, &a);
+    for (int i = 0; i < 12; i++) a.T64.m[i] = T.m[i];
+    a.gray_s = o.img[level][kOdoSrcGray]; a.gray_t = o.img[level][kOdoTgtGray]; a.depth_t = o.img[level][kOdoTgtDepth];
+    a.gray_dx = o.img[level][kOdoTgtGrayDx]; a.gray_dy = o.img[level][kOdoTgtGrayDy];
+    a.depth_dx = o.img[level][kOdoTgtDepthDx]; a.depth_dy = o.img[level][kOdoTgtDepthDy];
+    a.xyz_s = o.src_xyz[level];
+    const double s = std::ldexp(1.0, -level);
+    a.fx = o.fx * s; a.fy = o.fy * s;
+    a.method = method;
+    a.w_photo = std::sqrt(1.0 - 0.968); a.w_depth = std::sqrt(0.968);      // LAMBDA_HYBRID_DEPTH of the reference
+    return run_pair_pass("odometry", a, kNStats, stats, [&] { return launch_odometry_reduce(a, stream_); });
+}
+
+// CreateInformationMatrix: the pairs of the processed full-size depths at T, then information.hip's ten sums over the
+// target's xyz image as the target cloud
+int HipEngine::odometry_information(const Mat4 &T, double *sums)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!odo_.ready) { err_ = "no odometry frames: odometry_prepare first"; return VISMA_ICP_ERR_STATE; }
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    HIP_TRY(pair_.ensure());
+    int rc = odometry_launch_correspondences(0, T);
+    if (rc) return rc;
+    InformationArgs a;
+    odometry_pass_args(0, &a);
+    a.tgt = odo_.tgt_xyz;
+    return run_pair_pass("odometry information", a, kInfoAcc, sums, [&] { return launch_information_reduce(a, stream_); });
+}
+
 int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopResult *out)
 {
     HIP_TRY(hipSetDevice(device_));

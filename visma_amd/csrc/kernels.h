@@ -610,6 +610,42 @@ constexpr int kInfoAcc = 10;                           // K, sum x, y, z, sum xx
 struct InformationArgs : PairPassArgs {};
 hipError_t launch_information_reduce(const InformationArgs &a, hipStream_t stream);
 
+// ---- RGB-D odometry (odometry_image.hip, odometry.hip): single-channel fp32 images, row-major ----
+constexpr int kOdoMaxLevels = 8;
+// the images of a pyramid level (visma_icp_odometry_get_image's `which`); kOdoSrcXyz has three floats per pixel
+enum { kOdoSrcGray = 0, kOdoSrcDepth, kOdoTgtGray, kOdoTgtDepth, kOdoTgtGrayDx, kOdoTgtGrayDy, kOdoTgtDepthDx, kOdoTgtDepthDy,
+       kOdoSrcXyz, kOdoImages };
+constexpr int kOdoColor = 0, kOdoHybrid = 1;           // = VISMA_ICP_ODOMETRY_COLOR / HYBRID
+// d < min_depth || d > max_depth || d <= 0 -> NaN (in place is allowed)
+hipError_t launch_odo_preprocess_depth(const float *in, float *out, int64_t n, double min_depth, double max_depth, hipStream_t stream);
+// one 3-tap pass along the rows (vertical == 0) or down the columns, indices clamped at the borders
+hipError_t launch_odo_filter3(const float *in, float *out, int w, int h, float k0, float k1, float k2, int vertical, hipStream_t stream);
+// out = floor(w / 2) x floor(h / 2)
+hipError_t launch_odo_downsample(const float *in, int w, int h, float *out, hipStream_t stream);
+// img = (float)(scale * img + 0.0)
+hipError_t launch_odo_scale(float *img, int64_t n, double scale, hipStream_t stream);
+// out[y * w + x] = {(float)((x - ox) * z * inv_fx), (float)((y - oy) * z * inv_fy), z, 0}
+hipError_t launch_odo_xyz(const float *depth, int w, int h, double ox, double oy, double inv_fx, double inv_fy, float4 *out,
+                          hipStream_t stream);
+struct OdoProjection { double m[9]; double kt[3]; };   // K R K^-1 (row-major) and K t, formed on the host in f64
+// idx[v_s * w + u_s] = v_t * w + u_t or -1
+hipError_t launch_odo_correspondences(const float *depth_s, const float *depth_t, int w, int h, const OdoProjection &P,
+                                      double max_depth_diff, int32_t *idx, hipStream_t stream);
+// the sums NormalizeIntensity divides: publishes {K, sum gray_s over the pairs' source pixels, sum gray_t over their target pixels}
+constexpr int kOdoMeanAcc = 3;
+struct OdoMeanArgs : PairPassArgs { const float *gray_s = nullptr, *gray_t = nullptr; };
+hipError_t launch_odo_mean_reduce(const OdoMeanArgs &a, hipStream_t stream);
+// one Gauss-Newton step's sums over the pairs idx: publishes the 38 statistics {K, sum r^2, 21 of J^T J, 6 of J^T r, zeros}
+struct OdometryArgs : PairPassArgs {
+    const float *gray_s = nullptr, *gray_t = nullptr, *depth_t = nullptr;
+    const float *gray_dx = nullptr, *gray_dy = nullptr, *depth_dx = nullptr, *depth_dy = nullptr;   // the target's Sobel images
+    const float4 *xyz_s = nullptr;
+    double fx = 0.0, fy = 0.0;                         // of the level
+    double w_photo = 1.0, w_depth = 0.0;               // hybrid: sqrt(1 - 0.968), sqrt(0.968), formed on the host; colour: 1 (unused)
+    int method = kOdoHybrid;
+};
+hipError_t launch_odometry_reduce(const OdometryArgs &a, hipStream_t stream);
+
 // ---- the colour side of colored ICP (color_gradient.hip, colored.hip) ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
 inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }
