@@ -23,3 +23,6 @@
 #include "Odometry/OdometryOption.h"
 #include "Odometry/RGBDOdometryJacobian.h"
 #include "Odometry/Odometry.h"
+#include "Integration/TSDFVolume.h"
+#include "Integration/UniformTSDFVolume.h"
+#include "Integration/ScalableTSDFVolume.h"

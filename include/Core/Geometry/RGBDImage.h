@@ -4,7 +4,11 @@
 
 #include <memory>
 
+#include <Eigen/Core>
+
+#include "../Camera/PinholeCameraIntrinsic.h"
 #include "Image.h"
+#include "PointCloud.h"
 
 namespace open3d {
 
@@ -28,5 +32,16 @@ inline std::shared_ptr<RGBDImage> CreateRGBDImageFromColorAndDepth(const Image &
     out->color_ = convert_rgb_to_intensity ? *CreateFloatImageFromImage(color) : color;
     return out;
 }
+
+// The points behind a depth image (1 x float in metres, or 1 x uint16 in depth_scale units per metre cut at depth_trunc),
+// every stride-th row and column, and behind an RGB-D image (float depth; colour 3 x uint8 or 1 x float) with their colours,
+// in world coordinates: extrinsic^-1 ((u - cx) d / fx, (v - cy) d / fy, d), row-major pixel order (shapes of
+// O3D/Core/Geometry/PointCloud.h:192-215).  Any other format: an empty cloud, as in the reference.  On the GPU, in
+// visma_icp_open3d.hpp.
+inline std::shared_ptr<PointCloud> CreatePointCloudFromDepthImage(const Image &depth, const PinholeCameraIntrinsic &intrinsic,
+                                                                  const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity(),
+                                                                  double depth_scale = 1000.0, double depth_trunc = 1000.0, int stride = 1);
+inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic,
+                                                                 const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity());
 
 }  // namespace open3d

@@ -1,0 +1,35 @@
+// Core/Integration/TSDFVolume.h -- the interface of a truncated signed distance volume (shape of
+// O3D/Core/Integration/TSDFVolume.h, without ExtractTriangleMesh: DESIGN.md 4.4c11).  Stand-alone and header-only.
+#pragma once
+
+#include <memory>
+
+#include <Eigen/Core>
+
+#include "../Camera/PinholeCameraIntrinsic.h"
+#include "../Geometry/PointCloud.h"
+#include "../Geometry/RGBDImage.h"
+
+namespace open3d {
+
+enum class TSDFVolumeColorType { None = 0, RGB8 = 1, Gray32 = 2 };
+
+class TSDFVolume {
+public:
+    TSDFVolume(double voxel_length, double sdf_trunc, TSDFVolumeColorType color_type)
+        : voxel_length_(voxel_length), sdf_trunc_(sdf_trunc), color_type_(color_type) {}
+    virtual ~TSDFVolume() {}
+
+    virtual void Reset() = 0;
+    // image: a float depth image (metres) and a colour image by color_type_ (RGB8: 3 x uint8, Gray32: 1 x float), both of
+    // the intrinsic's size; extrinsic: world -> camera.  An image that does not fit throws std::invalid_argument (the
+    // reference prints a warning and returns).
+    virtual void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) = 0;
+    virtual std::shared_ptr<PointCloud> ExtractPointCloud() = 0;
+
+    double voxel_length_;
+    double sdf_trunc_;
+    TSDFVolumeColorType color_type_;
+};
+
+}  // namespace open3d

@@ -1174,6 +1174,106 @@ VISMA_ICP_API int visma_icp_odometry_step(visma_icp_ctx *ctx, int level, const d
 /* The information matrix of the resident frames at T (the last step of visma_icp_rgbd_odometry on its own). */
 VISMA_ICP_API int visma_icp_odometry_information(visma_icp_ctx *ctx, const double T[16], double out[36], int64_t *out_k);
 
+/* ---- TSDF integration: RGB-D frames with known poses fused into a truncated signed distance volume ---------------------
+ * (Curless, Levoy: "A Volumetric Method for Building Complex Models from Range Images", SIGGRAPH 1996; the reference's
+ * UniformTSDFVolume, Core/Integration/UniformTSDFVolume.cpp, and CreatePointCloudFromDepthImage / FromRGBDImage,
+ * Core/Geometry/PointCloudFactory.cpp.)  The step behind odometry and the pose graph: with a pose per frame, the frames
+ * become one de-noised cloud with normals and colours -- what the estimators above take as a target.
+ *
+ * A volume is an object owned by the context: several may live at once, each is resident on the device from its creation
+ * to visma_icp_tsdf_destroy or the context's end.  It is a cube of `resolution`^3 voxels of side length / resolution whose
+ * corner is `origin`; voxel (x, y, z) is at x R^2 + y R + z.  A frame is a depth image (metres, w x h fp32, row-major), a
+ * colour image by the volume's colour type (RGB8: w x h x 3 bytes; GRAY32: w x h fp32; NONE: ignored, may be NULL),
+ * the pinhole intrinsic {fx, fy, cx, cy} with ITS image size, and the extrinsic (world -> camera, 4 x 4 row-major).
+ * Each step as the reference computes it (tsdf.hip):
+ *   integrate   per voxel in fp32: the camera-space point of column (x, y) at z = 0, advanced along z by repeated
+ *               addition of extrinsic(:, 2) * voxel_length; the pixel (int)(x fx / z + cx + 0.5), (int)(y fy / z + cy +
+ *               0.5) inside [0.0001, size - 0.0001); its depth d > 0; sdf = (d - z) * sqrtf(xx^2 + yy^2 + 1) > -sdf_trunc;
+ *               tsdf = (tsdf w + min(1, sdf / sdf_trunc)) / (w + 1), colour likewise, w += 1.  The volume is the
+ *               reference's bit for bit.
+ *   extract     ExtractPointCloud: for every voxel in [1, R - 2]^3 with w != 0 and tsdf in [-0.98, 0.98), and each axis
+ *               whose +1 neighbour (index < R - 1) is such a voxel of the other sign: the point between them weighted by
+ *               |tsdf|, its colour, and the normal from six trilinear samples 0.99 voxels away, in f64.  The order is the
+ *               reference's: x, y, z, axis lexicographic.  ExtractVoxelPointCloud: every such voxel's centre, coloured
+ *               (tsdf + 1) / 2.  Points and colours are the reference's bit for bit, normals within 1e-11.
+ *   from depth  per pixel (u, v) of every stride-th row and column with d > 0: extrinsic^-1 ((u - cx) d / fx, (v - cy) d /
+ *               fy, d, 1) in f64, row-major order; with colours rgb / 255 or (gray, gray, gray).
+ *
+ * DEVIATIONS from the reference, on purpose:
+ *   - a frame that does not fit (its size differs from the intrinsic's, no colour image for a coloured volume) is
+ *     VISMA_ICP_ERR_INVALID; the reference prints "Unsupported image format" and returns without integrating;
+ *   - the extractions of a scalable volume come in a defined order (below); the reference's is a hash map's;
+ *   - ExtractTriangleMesh and 16-bit depth are not provided.
+ * No floating-point atomics: every voxel has one writer, and a run is bit-identical to itself.
+ *
+ * VISMA_ICP_ERR_INVALID, before anything reaches a device: a NULL pointer, resolution < 1, a volume of more than 2^31 - 1
+ * voxels (resolution > 1290: too large for memory), length or sdf_trunc not positive and finite, an origin that is not
+ * finite, an unknown colour type, w or h < 1, an image size that differs from the intrinsic's, fx or fy zero or not
+ * finite, a missing colour image, stride < 1, a volume of another context, a get before its extract (VISMA_ICP_ERR_STATE) or
+ * with another row count than the extract returned.  Sharded contexts: VISMA_ICP_ERR_INVALID.  A failed allocation is
+ * VISMA_ICP_ERR_HIP and leaves no volume behind.  Volumes are independent of the clouds and of the odometry frames. */
+#define VISMA_ICP_TSDF_COLOR_NONE 0    /* TSDFVolumeColorType::None */
+#define VISMA_ICP_TSDF_COLOR_RGB8 1    /* TSDFVolumeColorType::RGB8: colour images of 3 x uint8 */
+#define VISMA_ICP_TSDF_COLOR_GRAY32 2  /* TSDFVolumeColorType::Gray32: colour images of 1 x fp32 */
+typedef struct visma_icp_tsdf visma_icp_tsdf;
+/* UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin); origin may be NULL (zero) */
+VISMA_ICP_API int visma_icp_tsdf_create_uniform(visma_icp_ctx *ctx, double length, int resolution, double sdf_trunc, int color_type,
+                                                const double origin[3], visma_icp_tsdf **out);
+VISMA_ICP_API int visma_icp_tsdf_destroy(visma_icp_ctx *ctx, visma_icp_tsdf *volume);
+/* Reset(): a volume equal to a new one */
+VISMA_ICP_API int visma_icp_tsdf_reset(visma_icp_ctx *ctx, visma_icp_tsdf *volume);
+/* Integrate(): w x h is the images' size, intrinsic_w x intrinsic_h the intrinsic's; they must agree */
+VISMA_ICP_API int visma_icp_tsdf_integrate(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int w, int h, const float *depth,
+                                           const void *color, const double intrinsic[4], int intrinsic_w, int intrinsic_h,
+                                           const double extrinsic[16]);
+/* ExtractPointCloud(): the cloud stays on the device, *out_n is its size; then the rows (n as returned; points, normals
+ * and colors are n x 3 doubles, each may be NULL; colors is left untouched for a volume without colour) */
+VISMA_ICP_API int visma_icp_tsdf_extract_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_n);
+VISMA_ICP_API int visma_icp_tsdf_get_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *points, double *normals,
+                                                 double *colors, int64_t n);
+/* ExtractVoxelPointCloud(), by the same pattern */
+VISMA_ICP_API int visma_icp_tsdf_extract_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_n);
+VISMA_ICP_API int visma_icp_tsdf_get_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *points, double *colors,
+                                                       int64_t n);
+/* tsdf_ and weight_ (R^3 floats) and color_ (R^3 x 3 floats, interleaved; untouched without colour) of a uniform volume
+ * (unit_index NULL) or of the unit of a scalable volume with that index; each output may be NULL.  A unit_index for a
+ * uniform volume, none for a scalable one, or an index no unit has: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_tsdf_get_volume(visma_icp_ctx *ctx, visma_icp_tsdf *volume, const int32_t unit_index[3], float *tsdf,
+                                            float *weight, float *color);
+/* ScalableTSDFVolume(voxel_length, sdf_trunc, color_type, volume_unit_resolution, depth_sampling_stride): cubes of
+ * volume_unit_resolution^3 voxels ("units", each a uniform volume of length voxel_length * resolution whose corner is index *
+ * that length), opened where a frame's surface comes near.  Integrate back-projects every stride-th pixel (rows and
+ * columns) with a depth to extrinsic^-1 ((u - cx) d / fx, (v - cy) d / fy, d) in f64 -- the inverse by cofactors on the
+ * host --, opens every unit between floor((p - sdf_trunc) / unit length) and floor((p + sdf_trunc) / unit length) per
+ * component, and integrates the frame into each of those units as above.  The units live in a pool on the device of
+ * initial_units units at first (0: 256) that doubles when it is full; a unit's place in it never changes.  Every unit a
+ * frame touches is opened before its integration starts, and a pool that cannot grow is VISMA_ICP_ERR_HIP with the
+ * volume as it was.  Reset() forgets the units.
+ * THE ORDER of the extractions of a scalable volume is this library's definition -- the reference's is the iteration
+ * order of an unordered_map, which means nothing: units in lexicographic order of their index (x, then y, then z), and
+ * the reference's order within a unit (x, y, z, axis).  visma_icp_tsdf_get_units returns the indices in that order.  An
+ * extracted point's +1 neighbour and the eight corners of a normal's samples are read across unit borders; a unit that
+ * does not exist reads weight 0 and tsdf 0, as in the reference.
+ * VISMA_ICP_ERR_INVALID: volume_unit_resolution < 1 or > 256, voxel_length or sdf_trunc not positive and finite, an
+ * unknown colour type, depth_sampling_stride < 1, initial_units outside 0 .. 2^20. */
+VISMA_ICP_API int visma_icp_tsdf_create_scalable(visma_icp_ctx *ctx, double voxel_length, double sdf_trunc, int color_type,
+                                                 int volume_unit_resolution, int depth_sampling_stride, int initial_units,
+                                                 visma_icp_tsdf **out);
+/* The unit indices of a scalable volume, 3 ints per unit, in the order above: *out_n units; indices may be NULL for the
+ * count alone, otherwise it has room for `capacity` units (less than *out_n: VISMA_ICP_ERR_INVALID, *out_n set). */
+VISMA_ICP_API int visma_icp_tsdf_get_units(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int32_t *indices, int64_t capacity,
+                                           int64_t *out_n);
+/* CreatePointCloudFromDepthImage (float depth) and CreatePointCloudFromRGBDImage (color_type RGB8 or GRAY32, as above).
+ * extrinsic may be NULL (the identity).  *out_n is the number of points.  points (n x 3 doubles) may be NULL for the count
+ * alone; otherwise points (and colors, which may be NULL) have room for `capacity` rows, at least ceil(w / stride) *
+ * ceil(h / stride) (stride 1 for the RGB-D form): less is VISMA_ICP_ERR_INVALID before anything reaches a device. */
+VISMA_ICP_API int visma_icp_point_cloud_from_depth(visma_icp_ctx *ctx, int w, int h, const float *depth, const double intrinsic[4],
+                                                   const double extrinsic[16], int stride, double *points, int64_t capacity,
+                                                   int64_t *out_n);
+VISMA_ICP_API int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int h, const float *depth, const void *color,
+                                                  int color_type, const double intrinsic[4], const double extrinsic[16],
+                                                  double *points, double *colors, int64_t capacity, int64_t *out_n);
+
 /* The pose graph on plain arrays (pure functions; no ctx, no GPU).  Node i has a 4 x 4 pose (row-major, node to world);
  * an edge says: transformation maps the SOURCE node's cloud onto the TARGET node's (PoseGraph.h:52-86).  Odometry edges
  * are certain (uncertain = 0), loop closures uncertain; confidence is the line-process value in [0, 1]. */

@@ -38,6 +38,8 @@
 //                                      for every edge of a PoseGraph --, then the line-process pose-graph optimisation
 //                                      on the host.  WITHOUT the identity terms Open3D 0.3.0 adds to the matrix
 //   open3d::cicp::ComputeRGBDOdometry  the odometry edge between two consecutive RGB-D frames and its information matrix
+//   open3d::cicp::CreatePointCloudFromDepthImage / FromRGBDImage   the points behind a frame; and, with the stand-alone
+//                                      header set, open3d::UniformTSDFVolume: frames with poses fused into a volume on the GPU
 //                                      (O3D/Core/Odometry/Odometry.h): image pyramids, per-pixel pairs and the colour or
 //                                      hybrid Gauss-Newton rows on the GPU
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
@@ -72,6 +74,10 @@
 #include <Core/Geometry/Image.h>
 #include <Core/Geometry/RGBDImage.h>
 #include <Core/Odometry/Odometry.h>
+#ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
+#include <Core/Integration/UniformTSDFVolume.h>
+#include <Core/Integration/ScalableTSDFVolume.h>
+#endif
 
 #include "visma_icp.h"
 #include "visma_io.h"
@@ -1716,10 +1722,232 @@ inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
     return ComputeRGBDOdometry(detail::ThreadContext::instance().get(), source, target, pinhole_camera_intrinsic, odo_init, jacobian_method, option);
 }
 
+// open3d::CreatePointCloudFromDepthImage / CreatePointCloudFromRGBDImage (PointCloudFactory.cpp) on the GPU.  A 16-bit depth
+// image is converted on the host first (ConvertDepthToFloatImage); any other format gives an empty cloud, as the reference.
+namespace detail {
+inline std::shared_ptr<PointCloud> cloud_from_frame(visma_icp_ctx *ctx, const Image &depth, const Image *color, int color_type,
+                                                    const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic, int stride)
+{
+    auto out = std::make_shared<PointCloud>();
+    const Eigen::Matrix3d &K = intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    double E[16];
+    to_rowmajor(extrinsic, E);
+    const int w = depth.width_, h = depth.height_;
+    if (w < 1 || h < 1 || stride < 1) return out;
+    const int64_t cap = (((int64_t)w - 1) / stride + 1) * (((int64_t)h - 1) / stride + 1);
+    std::vector<double> pts(3 * (size_t)cap), col(color ? 3 * (size_t)cap : 0);
+    int64_t n = 0;
+    if (color)
+        check(ctx, visma_icp_point_cloud_from_rgbd(ctx, w, h, (const float *)depth.data_.data(), color->data_.data(), color_type, k, E,
+                                                   pts.data(), col.data(), cap, &n), "visma_icp_point_cloud_from_rgbd");
+    else
+        check(ctx, visma_icp_point_cloud_from_depth(ctx, w, h, (const float *)depth.data_.data(), k, E, stride, pts.data(), cap, &n),
+              "visma_icp_point_cloud_from_depth");
+    out->points_.resize((size_t)n);
+    for (size_t i = 0; i < (size_t)n; i++) out->points_[i] = Eigen::Vector3d(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+    if (color) {
+        out->colors_.resize((size_t)n);
+        for (size_t i = 0; i < (size_t)n; i++) out->colors_[i] = Eigen::Vector3d(col[3 * i], col[3 * i + 1], col[3 * i + 2]);
+    }
+    return out;
+}
+}  // namespace detail
+
+// what open3d::UniformTSDFVolume and ScalableTSDFVolume share (stand-alone header set): a volume of the context by its handle
+namespace detail {
+inline void tsdf_integrate(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int color_type, const char *who, const RGBDImage &image,
+                           const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic)
+{
+    const Image &d = image.depth_, &c = image.color_;
+    const bool rgb = color_type == VISMA_ICP_TSDF_COLOR_RGB8, gray = color_type == VISMA_ICP_TSDF_COLOR_GRAY32;
+    if (d.num_of_channels_ != 1 || d.bytes_per_channel_ != 4 || !d.HasData() || (rgb && (c.num_of_channels_ != 3 || c.bytes_per_channel_ != 1)) ||
+        (gray && (c.num_of_channels_ != 1 || c.bytes_per_channel_ != 4)) ||
+        ((rgb || gray) && (c.width_ != d.width_ || c.height_ != d.height_ || !c.HasData())))
+        throw std::invalid_argument(std::string(who) + "Unsupported image format.");
+    const Eigen::Matrix3d &K = intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    double E[16];
+    to_rowmajor(extrinsic, E);
+    const int rc = visma_icp_tsdf_integrate(ctx, volume, d.width_, d.height_, (const float *)d.data_.data(),
+                                            (rgb || gray) ? (const void *)c.data_.data() : nullptr, k, intrinsic.width_, intrinsic.height_, E);
+    if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string(who) + visma_icp_last_error(ctx));
+    check(ctx, rc, "visma_icp_tsdf_integrate");
+}
+inline std::shared_ptr<PointCloud> tsdf_extract_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, bool colored)
+{
+    auto out = std::make_shared<PointCloud>();
+    int64_t n = 0;
+    check(ctx, visma_icp_tsdf_extract_point_cloud(ctx, volume, &n), "visma_icp_tsdf_extract_point_cloud");
+    out->points_.resize((size_t)n); out->normals_.resize((size_t)n); out->colors_.resize(colored ? (size_t)n : 0);
+    // (std::vector<Eigen::Vector3d> is contiguous AoS f64 with stride 3)
+    check(ctx, visma_icp_tsdf_get_point_cloud(ctx, volume, n ? out->points_[0].data() : nullptr, n ? out->normals_[0].data() : nullptr,
+                                              colored && n ? out->colors_[0].data() : nullptr, n), "visma_icp_tsdf_get_point_cloud");
+    return out;
+}
+inline std::shared_ptr<PointCloud> tsdf_extract_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume)
+{
+    auto out = std::make_shared<PointCloud>();
+    int64_t n = 0;
+    check(ctx, visma_icp_tsdf_extract_voxel_point_cloud(ctx, volume, &n), "visma_icp_tsdf_extract_voxel_point_cloud");
+    out->points_.resize((size_t)n); out->colors_.resize((size_t)n);
+    check(ctx, visma_icp_tsdf_get_voxel_point_cloud(ctx, volume, n ? out->points_[0].data() : nullptr, n ? out->colors_[0].data() : nullptr, n),
+          "visma_icp_tsdf_get_voxel_point_cloud");
+    return out;
+}
+inline void tsdf_download(visma_icp_ctx *ctx, visma_icp_tsdf *volume, const int32_t *unit, size_t voxels, bool colored, std::vector<float> &tsdf,
+                          std::vector<float> &weight, std::vector<Eigen::Vector3f> &color)
+{
+    tsdf.assign(voxels, 0.0f); weight.assign(voxels, 0.0f);
+    std::vector<float> c(colored ? 3 * voxels : 0);
+    check(ctx, visma_icp_tsdf_get_volume(ctx, volume, unit, tsdf.data(), weight.data(), colored ? c.data() : nullptr), "visma_icp_tsdf_get_volume");
+    color.resize(colored ? voxels : 0);
+    for (size_t i = 0; i < color.size(); i++) color[i] = Eigen::Vector3f(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
+}
+}  // namespace detail
+
+// ... on a context of the caller's
+inline std::shared_ptr<PointCloud> CreatePointCloudFromDepthImage(visma_icp_ctx *ctx, const Image &depth, const PinholeCameraIntrinsic &intrinsic,
+                                                                  const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity(),
+                                                                  double depth_scale = 1000.0, double depth_trunc = 1000.0, int stride = 1)
+{
+    if (depth.num_of_channels_ == 1 && depth.bytes_per_channel_ == 2 && depth.HasData())
+        return detail::cloud_from_frame(ctx, *ConvertDepthToFloatImage(depth, depth_scale, depth_trunc), nullptr, 0, intrinsic, extrinsic, stride);
+    if (depth.num_of_channels_ == 1 && depth.bytes_per_channel_ == 4 && depth.HasData())
+        return detail::cloud_from_frame(ctx, depth, nullptr, 0, intrinsic, extrinsic, stride);
+    return std::make_shared<PointCloud>();
+}
+inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(visma_icp_ctx *ctx, const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic,
+                                                                 const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity())
+{
+    const Image &d = image.depth_, &c = image.color_;
+    if (d.num_of_channels_ == 1 && d.bytes_per_channel_ == 4 && d.HasData() && c.HasData() && c.width_ == d.width_ && c.height_ == d.height_) {
+        if (c.bytes_per_channel_ == 1 && c.num_of_channels_ == 3)
+            return detail::cloud_from_frame(ctx, d, &c, VISMA_ICP_TSDF_COLOR_RGB8, intrinsic, extrinsic, 1);
+        if (c.bytes_per_channel_ == 4 && c.num_of_channels_ == 1)
+            return detail::cloud_from_frame(ctx, d, &c, VISMA_ICP_TSDF_COLOR_GRAY32, intrinsic, extrinsic, 1);
+    }
+    return std::make_shared<PointCloud>();
+}
+// ... on this thread's context
+inline std::shared_ptr<PointCloud> CreatePointCloudFromDepthImage(const Image &depth, const PinholeCameraIntrinsic &intrinsic,
+                                                                  const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity(),
+                                                                  double depth_scale = 1000.0, double depth_trunc = 1000.0, int stride = 1)
+{
+    return CreatePointCloudFromDepthImage(detail::ThreadContext::instance().get(), depth, intrinsic, extrinsic, depth_scale, depth_trunc, stride);
+}
+inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic,
+                                                                 const Eigen::Matrix4d &extrinsic = Eigen::Matrix4d::Identity())
+{
+    return CreatePointCloudFromRGBDImage(detail::ThreadContext::instance().get(), image, intrinsic, extrinsic);
+}
+
 }  // namespace cicp
 
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
 // Stand-alone header set: give the stock names their bodies too.
+inline std::shared_ptr<PointCloud> CreatePointCloudFromDepthImage(const Image &depth, const PinholeCameraIntrinsic &intrinsic,
+                                                                  const Eigen::Matrix4d &extrinsic, double depth_scale, double depth_trunc,
+                                                                  int stride)
+{
+    return cicp::CreatePointCloudFromDepthImage(depth, intrinsic, extrinsic, depth_scale, depth_trunc, stride);
+}
+inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic,
+                                                                 const Eigen::Matrix4d &extrinsic)
+{
+    return cicp::CreatePointCloudFromRGBDImage(image, intrinsic, extrinsic);
+}
+// open3d::UniformTSDFVolume (Core/Integration/UniformTSDFVolume.h): the volume is an object of the context, resident on the GPU
+inline void UniformTSDFVolume::Create(visma_icp_ctx *ctx)
+{
+    ctx_ = ctx;
+    cicp::detail::check(ctx_, visma_icp_tsdf_create_uniform(ctx_, length_, resolution_, sdf_trunc_, (int)color_type_, origin_.data(), &volume_),
+                        "visma_icp_tsdf_create_uniform");
+}
+inline UniformTSDFVolume::UniformTSDFVolume(double length, int resolution, double sdf_trunc, TSDFVolumeColorType color_type,
+                                            const Eigen::Vector3d &origin)
+    : TSDFVolume(length / (double)resolution, sdf_trunc, color_type), origin_(origin), length_(length), resolution_(resolution),
+      voxel_num_(resolution * resolution * resolution)
+{
+    Create(cicp::detail::ThreadContext::instance().get());
+}
+inline UniformTSDFVolume::UniformTSDFVolume(visma_icp_ctx *ctx, double length, int resolution, double sdf_trunc,
+                                            TSDFVolumeColorType color_type, const Eigen::Vector3d &origin)
+    : TSDFVolume(length / (double)resolution, sdf_trunc, color_type), origin_(origin), length_(length), resolution_(resolution),
+      voxel_num_(resolution * resolution * resolution)
+{
+    Create(ctx);
+}
+inline UniformTSDFVolume::~UniformTSDFVolume()
+{
+    if (volume_) (void)visma_icp_tsdf_destroy(ctx_, volume_);
+}
+inline void UniformTSDFVolume::Reset() { cicp::detail::check(ctx_, visma_icp_tsdf_reset(ctx_, volume_), "visma_icp_tsdf_reset"); }
+inline void UniformTSDFVolume::Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic)
+{
+    cicp::detail::tsdf_integrate(ctx_, volume_, (int)color_type_, "[UniformTSDFVolume::Integrate] ", image, intrinsic, extrinsic);
+}
+inline std::shared_ptr<PointCloud> UniformTSDFVolume::ExtractPointCloud()
+{
+    return cicp::detail::tsdf_extract_point_cloud(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
+}
+inline std::shared_ptr<PointCloud> UniformTSDFVolume::ExtractVoxelPointCloud() { return cicp::detail::tsdf_extract_voxel_point_cloud(ctx_, volume_); }
+inline void UniformTSDFVolume::Download(std::vector<float> &tsdf, std::vector<float> &weight, std::vector<Eigen::Vector3f> &color) const
+{
+    cicp::detail::tsdf_download(ctx_, volume_, nullptr, (size_t)voxel_num_, color_type_ != TSDFVolumeColorType::None, tsdf, weight, color);
+}
+// open3d::ScalableTSDFVolume (Core/Integration/ScalableTSDFVolume.h)
+inline ScalableTSDFVolume::ScalableTSDFVolume(visma_icp_ctx *ctx, double voxel_length, double sdf_trunc, TSDFVolumeColorType color_type,
+                                              int volume_unit_resolution, int depth_sampling_stride, int initial_units)
+    : TSDFVolume(voxel_length, sdf_trunc, color_type), volume_unit_resolution_(volume_unit_resolution),
+      volume_unit_length_(voxel_length * volume_unit_resolution), depth_sampling_stride_(depth_sampling_stride), ctx_(ctx)
+{
+    cicp::detail::check(ctx_, visma_icp_tsdf_create_scalable(ctx_, voxel_length_, sdf_trunc_, (int)color_type_, volume_unit_resolution_,
+                                                             depth_sampling_stride_, initial_units, &volume_),
+                        "visma_icp_tsdf_create_scalable");
+}
+inline ScalableTSDFVolume::ScalableTSDFVolume(double voxel_length, double sdf_trunc, TSDFVolumeColorType color_type, int volume_unit_resolution,
+                                              int depth_sampling_stride)
+    : ScalableTSDFVolume(cicp::detail::ThreadContext::instance().get(), voxel_length, sdf_trunc, color_type, volume_unit_resolution,
+                         depth_sampling_stride, 0)
+{
+}
+inline ScalableTSDFVolume::~ScalableTSDFVolume()
+{
+    if (volume_) (void)visma_icp_tsdf_destroy(ctx_, volume_);
+}
+inline void ScalableTSDFVolume::Reset() { cicp::detail::check(ctx_, visma_icp_tsdf_reset(ctx_, volume_), "visma_icp_tsdf_reset"); }
+inline void ScalableTSDFVolume::Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic)
+{
+    cicp::detail::tsdf_integrate(ctx_, volume_, (int)color_type_, "[ScalableTSDFVolume::Integrate] ", image, intrinsic, extrinsic);
+}
+inline std::shared_ptr<PointCloud> ScalableTSDFVolume::ExtractPointCloud()
+{
+    return cicp::detail::tsdf_extract_point_cloud(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
+}
+inline std::shared_ptr<PointCloud> ScalableTSDFVolume::ExtractVoxelPointCloud() { return cicp::detail::tsdf_extract_voxel_point_cloud(ctx_, volume_); }
+inline std::vector<Eigen::Vector3i> ScalableTSDFVolume::Units() const
+{
+    int64_t n = 0;
+    cicp::detail::check(ctx_, visma_icp_tsdf_get_units(ctx_, volume_, nullptr, 0, &n), "visma_icp_tsdf_get_units");
+    std::vector<int32_t> k(3 * (size_t)n + 3);
+    cicp::detail::check(ctx_, visma_icp_tsdf_get_units(ctx_, volume_, k.data(), n, &n), "visma_icp_tsdf_get_units");
+    std::vector<Eigen::Vector3i> out((size_t)n);
+    for (size_t i = 0; i < out.size(); i++) out[i] = Eigen::Vector3i(k[3 * i], k[3 * i + 1], k[3 * i + 2]);
+    return out;
+}
+inline bool ScalableTSDFVolume::DownloadUnit(const Eigen::Vector3i &index, std::vector<float> &tsdf, std::vector<float> &weight,
+                                             std::vector<Eigen::Vector3f> &color) const
+{
+    for (const auto &u : Units())
+        if (u == index) {
+            const int32_t key[3] = {index(0), index(1), index(2)};
+            const size_t n = (size_t)volume_unit_resolution_ * volume_unit_resolution_ * volume_unit_resolution_;
+            cicp::detail::tsdf_download(ctx_, volume_, key, n, color_type_ != TSDFVolumeColorType::None, tsdf, weight, color);
+            return true;
+        }
+    return false;
+}
 inline double TransformationEstimationPointToPoint::ComputeRMSE(
     const PointCloud &s, const PointCloud &t, const CorrespondenceSet &c) const
 {

@@ -1,0 +1,395 @@
+"""The numpy specification of TSDF integration (Open3D 0.3.0: Core/Integration/UniformTSDFVolume.cpp,
+CreateDepthToCameraDistanceMultiplierFloatImage of Core/Geometry/ImageFactory.cpp and CreatePointCloudFromDepthImage /
+CreatePointCloudFromRGBDImage of Core/Geometry/PointCloudFactory.cpp; ScalableTSDFVolume.cpp at the end), operation by operation, as the library computes it
+(visma_amd/csrc/tsdf.hip).  tests/golden/tsdf.npz (tests/golden/gen_tsdf.py) pins it to the compiled reference.
+
+A volume is a dict: resolution R, length, sdf_trunc, color_type, origin, and the arrays tsdf, weight (R^3 fp32, voxel
+x R^2 + y R + z) and color (R^3 x 3 fp32, or None).  Images are h x w arrays in C order.
+
+What is exact and what is bounded:
+
+  integration    bit for bit.  Everything is fp32.  The camera-space point of a column (x, y) is formed once at z = 0 --
+                 each row of extrinsic_f times (X, Y, Z0, 1) summed as ((e0 X + e1 Y) + e2 Z0) + e3, the order of the
+                 compiled reference's 4 x 4 product -- and advanced by repeated fp32 addition of extrinsic_f(:, 2) *
+                 voxel_length_f: the serial chain along z is part of the arithmetic.
+  extraction     points, colours and the voxel cloud bit for bit: f64 with the fp32 weights |f0|, |f1| promoted and their
+                 SUM formed in fp32 first; the voxel cloud's z advances by repeated f64 addition.
+  normals        bit for bit as well, with the squared norm summed as (x^2 + y^2) + z^2 and a true division by its root
+                 (the tests assert that).  The bound that holds for ANY evaluation order is NORMAL_TOL = 1e-11 per
+                 component: a trilinear GetTSDFAt of values in [-1, 1] carries at most about 8 roundings of 2^-53, a
+                 difference of two about 17, and the generator refuses a fixture with an unnormalised gradient below 1e-3.
+  scalable       the unit sets equal (the f64 floors of (p -+ sdf_trunc) / unit length: the generator refuses a fixture with one
+                 within 1e-9 of its boundary), every unit bit for bit, the extractions bit for bit once both sides' rows are
+                 sorted -- the reference's order is a hash map's; the specification's is units in lexicographic order.
+  point clouds   bit for bit with the identity extrinsic; with another, within 1e-12 relative (the inverse's rounding).
+
+Deviation the specification shares with the library (include/visma_icp.h): a frame whose format or size does not fit is an
+error, not a silent return."""
+import hashlib
+
+import numpy as np
+
+F32 = np.float32
+COLOR_NONE, COLOR_RGB8, COLOR_GRAY32 = 0, 1, 2
+NORMAL_TOL = 1e-11
+POINT_TOL = 1e-12
+
+
+def digest(a, dtype):
+    """SHA-256 of the array's bytes as `dtype` (C order) -> 32 uint8"""
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a, dtype).tobytes()).digest(), np.uint8).copy()
+
+
+def new_volume(length, resolution, sdf_trunc, color_type, origin=(0.0, 0.0, 0.0)):
+    n = resolution ** 3
+    return dict(R=int(resolution), length=float(length), voxel_length=float(length) / float(resolution), sdf_trunc=float(sdf_trunc),
+                color_type=int(color_type), origin=np.asarray(origin, np.float64).copy(), tsdf=np.zeros(n, F32),
+                weight=np.zeros(n, F32), color=np.zeros((n, 3), F32) if color_type != COLOR_NONE else None)
+
+
+def multiplier_image(w, h, intrinsic):
+    """CreateDepthToCameraDistanceMultiplierFloatImage: sqrtf(xx^2 + yy^2 + 1) with xx = (j - (float)cx) * (1.0f / (float)fx)"""
+    fx, fy, cx, cy = [F32(v) for v in intrinsic]
+    xx = (np.arange(w).astype(F32) - cx) * (F32(1.0) / fx)
+    yy = (np.arange(h).astype(F32) - cy) * (F32(1.0) / fy)
+    return np.sqrt((xx * xx)[None, :] + (yy * yy)[:, None] + F32(1.0)).astype(F32)
+
+
+def integrate(vol, depth, color, intrinsic, extrinsic, trace=None):
+    """UniformTSDFVolume::Integrate of one frame, in place.  color: h x w x 3 uint8 (RGB8), h x w fp32 (Gray32) or None.
+    trace (a dict, optional) counts the branches taken."""
+    R = vol["R"]
+    h, w = depth.shape
+    depth = np.ascontiguousarray(depth, F32)
+    mult = multiplier_image(w, h, intrinsic)
+    fx, fy, cx, cy = [F32(v) for v in intrinsic]
+    E = np.asarray(extrinsic, np.float64).reshape(4, 4).astype(F32)
+    vl = F32(vol["voxel_length"])
+    half = vl * F32(0.5)
+    trunc = F32(vol["sdf_trunc"])
+    trunc_inv = F32(1.0) / trunc
+    Es = E * vl
+    safe_w, safe_h = F32(w) - F32(0.0001), F32(h) - F32(0.0001)
+    o = vol["origin"].astype(F32)
+    idx = np.arange(R).astype(F32)
+    X = ((half + vl * idx) + o[0])[:, None] * np.ones((1, R), F32)     # (R, R): x down, y across
+    Y = ((half + vl * idx) + o[1])[None, :] * np.ones((R, 1), F32)
+    Z0 = half + o[2]
+    p = [((E[r, 0] * X + E[r, 1] * Y) + E[r, 2] * Z0) + E[r, 3] for r in range(3)]
+    tsdf = vol["tsdf"].reshape(R, R, R); weight = vol["weight"].reshape(R, R, R)
+    col = vol["color"].reshape(R, R, R, 3) if vol["color_type"] != COLOR_NONE else None
+    if vol["color_type"] == COLOR_RGB8:
+        cf = np.ascontiguousarray(color, np.uint8).reshape(h, w, 3).astype(F32)
+    elif vol["color_type"] == COLOR_GRAY32:
+        cf = np.repeat(np.ascontiguousarray(color, F32).reshape(h, w, 1), 3, axis=2)
+    count = dict(behind=0, left=0, right=0, top=0, bottom=0, hole=0, far_behind=0, clamped=0, integrated=0)
+    with np.errstate(all="ignore"):
+        for z in range(R):
+            px, py, pz = p
+            front = pz > 0
+            uf = (px * fx / pz + cx) + F32(0.5)
+            vf = (py * fy / pz + cy) + F32(0.5)
+            inside = front & (uf >= F32(0.0001)) & (uf < safe_w) & (vf >= F32(0.0001)) & (vf < safe_h)
+            u = np.where(inside, uf, 0).astype(np.int64); v = np.where(inside, vf, 0).astype(np.int64)
+            d = depth[v, u]
+            seen = inside & (d > 0)
+            sdf = (d - pz) * mult[v, u]
+            go = seen & (sdf > -trunc)
+            t = np.minimum(F32(1.0), sdf * trunc_inv)
+            wz = weight[:, :, z]
+            w1 = wz + F32(1.0)
+            tsdf[:, :, z] = np.where(go, (tsdf[:, :, z] * wz + t) / w1, tsdf[:, :, z])
+            if col is not None:
+                col[:, :, z, :] = np.where(go[..., None], (col[:, :, z, :] * wz[..., None] + cf[v, u]) / w1[..., None], col[:, :, z, :])
+            weight[:, :, z] = np.where(go, w1, wz)
+            count["behind"] += int(np.count_nonzero(~front))
+            count["left"] += int(np.count_nonzero(front & ~(uf >= F32(0.0001))))
+            count["right"] += int(np.count_nonzero(front & ~(uf < safe_w)))
+            count["top"] += int(np.count_nonzero(front & ~(vf >= F32(0.0001))))
+            count["bottom"] += int(np.count_nonzero(front & ~(vf < safe_h)))
+            count["hole"] += int(np.count_nonzero(inside & ~(d > 0)))
+            count["far_behind"] += int(np.count_nonzero(seen & ~go))
+            count["clamped"] += int(np.count_nonzero(go & (sdf * trunc_inv > F32(1.0))))
+            count["integrated"] += int(np.count_nonzero(go))
+            p = [px + Es[0, 2], py + Es[1, 2], pz + Es[2, 2]]
+    if trace is not None:
+        for k, n in count.items():
+            trace[k] = trace.get(k, 0) + n
+    return vol
+
+
+def _valid(w, f):
+    return (w != 0) & (f < F32(0.98)) & (f >= F32(-0.98))
+
+
+def tsdf_at(vol, p):
+    """UniformTSDFVolume::GetTSDFAt at the rows of p (volume coordinates, without the origin), f64"""
+    R = vol["R"]
+    t = vol["tsdf"].reshape(R, R, R).astype(np.float64)
+    g = p / vol["voxel_length"] - 0.5
+    i = np.floor(g).astype(np.int64)
+    r = g - i
+    x, y, z = i[:, 0], i[:, 1], i[:, 2]
+    r0, r1, r2 = r[:, 0], r[:, 1], r[:, 2]
+    return (1 - r0) * ((1 - r1) * ((1 - r2) * t[x, y, z] + r2 * t[x, y, z + 1]) + r1 * ((1 - r2) * t[x, y + 1, z] + r2 * t[x, y + 1, z + 1])) \
+        + r0 * ((1 - r1) * ((1 - r2) * t[x + 1, y, z] + r2 * t[x + 1, y, z + 1]) + r1 * ((1 - r2) * t[x + 1, y + 1, z] + r2 * t[x + 1, y + 1, z + 1]))
+
+
+def gradient_at(vol, p):
+    """the unnormalised n of GetNormalAt: GetTSDFAt(p + 0.99 voxel e_i) - GetTSDFAt(p - 0.99 voxel e_i)"""
+    gap = 0.99 * vol["voxel_length"]
+    n = np.empty_like(p)
+    for i in range(3):
+        lo, hi = p.copy(), p.copy()
+        lo[:, i] -= gap; hi[:, i] += gap
+        n[:, i] = tsdf_at(vol, hi) - tsdf_at(vol, lo)
+    return n
+
+
+def normalized(n):
+    """Eigen's normalized(): n / sqrt((x^2 + y^2) + z^2) where that is positive, n otherwise"""
+    z = (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]
+    with np.errstate(all="ignore"):
+        return np.where((z > 0)[:, None], n / np.sqrt(z)[:, None], n)
+
+
+def extract_point_cloud(vol, with_gradient=False):
+    """UniformTSDFVolume::ExtractPointCloud -> points, normals, colors (None without colour), in the reference's order: x, y,
+    z, axis lexicographic"""
+    R = vol["R"]
+    vl = vol["voxel_length"]; half = vl * 0.5
+    f = vol["tsdf"].reshape(R, R, R); w = vol["weight"].reshape(R, R, R)
+    ok = _valid(w, f)
+    rows = []
+    for i in range(3):
+        a = [slice(1, R - 1)] * 3; b = [slice(1, R - 1)] * 3
+        a[i] = slice(1, R - 2); b[i] = slice(2, R - 1)                 # idx1(i) < R - 1
+        a, b = tuple(a), tuple(b)
+        with np.errstate(all="ignore"):
+            m = ok[a] & ok[b] & (f[a] * f[b] < 0)
+        at = np.argwhere(m) + 1
+        rows.append(np.concatenate([at, np.full((len(at), 1), i)], 1))
+    rows = np.concatenate(rows, 0) if R > 3 else np.zeros((0, 4), np.int64)
+    rows = rows[np.lexsort((rows[:, 3], rows[:, 2], rows[:, 1], rows[:, 0]))]
+    x0 = rows[:, :3]; ax = rows[:, 3]; n = len(rows)
+    x1 = x0.copy(); x1[np.arange(n), ax] += 1
+    f0 = f[x0[:, 0], x0[:, 1], x0[:, 2]]; f1 = f[x1[:, 0], x1[:, 1], x1[:, 2]]
+    r0, r1 = np.abs(f0), np.abs(f1)
+    rs = (r0 + r1).astype(np.float64)                                  # the fp32 sum, promoted
+    p = half + vl * x0.astype(np.float64)
+    p0 = p[np.arange(n), ax]
+    p1 = p0 + vl
+    p[np.arange(n), ax] = (p0 * r1.astype(np.float64) + p1 * r0.astype(np.float64)) / rs
+    colors = None
+    if vol["color_type"] != COLOR_NONE:
+        c = vol["color"].reshape(R, R, R, 3)
+        c0 = c[x0[:, 0], x0[:, 1], x0[:, 2]]; c1 = c[x1[:, 0], x1[:, 1], x1[:, 2]]
+        cc = (c0 * r1[:, None] + c1 * r0[:, None]) / (r0 + r1)[:, None]
+        if vol["color_type"] == COLOR_RGB8:
+            cc = cc / F32(255.0)
+        colors = cc.astype(np.float64)
+    g = gradient_at(vol, p) if n else np.zeros((0, 3))
+    out = (p + vol["origin"], normalized(g), colors)
+    return out + (g,) if with_gradient else out
+
+
+def extract_voxel_point_cloud(vol):
+    """UniformTSDFVolume::ExtractVoxelPointCloud -> points, colors"""
+    R = vol["R"]
+    vl = vol["voxel_length"]; half = vl * 0.5
+    f = vol["tsdf"].reshape(R, R, R); w = vol["weight"].reshape(R, R, R)
+    zs = np.empty(R)
+    z = half
+    for k in range(R):                                                 # pt(2) += voxel_length_
+        zs[k] = z
+        z += vl
+    at = np.argwhere(_valid(w, f))
+    p = np.stack([half + vl * at[:, 0], half + vl * at[:, 1], zs[at[:, 2]]], 1) + vol["origin"] if len(at) else np.zeros((0, 3))
+    c = (f[at[:, 0], at[:, 1], at[:, 2]].astype(np.float64) + 1.0) * 0.5
+    return p, np.repeat(c[:, None], 3, axis=1)
+
+
+def invert_pose(extrinsic):
+    return np.linalg.inv(np.asarray(extrinsic, np.float64).reshape(4, 4))
+
+
+def point_cloud_from_depth(depth, intrinsic, extrinsic=None, stride=1, color=None):
+    """CreatePointCloudFromDepthImage (float depth; `stride`) and, with `color` (h x w x 3 uint8 or h x w fp32),
+    CreatePointCloudFromRGBDImage (stride 1) -> points, colors (None without colour), row-major pixel order"""
+    depth = np.ascontiguousarray(depth, F32)
+    h, w = depth.shape
+    fx, fy, cx, cy = [float(v) for v in intrinsic]
+    identity = extrinsic is None or np.array_equal(np.asarray(extrinsic, np.float64).reshape(4, 4), np.eye(4))
+    P = np.eye(4) if identity else invert_pose(extrinsic)
+    i, j = np.meshgrid(np.arange(0, h, stride), np.arange(0, w, stride), indexing="ij")
+    d = depth[i, j]
+    m = d > 0
+    i, j, z = i[m], j[m], d[m].astype(np.float64)
+    x = (j - cx) * z / fx
+    y = (i - cy) * z / fy
+    pts = np.stack([((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3)], 1) if len(z) else np.zeros((0, 3))
+    colors = None
+    if color is not None:
+        color = np.asarray(color)
+        if color.dtype == np.uint8:
+            colors = color.reshape(h, w, 3)[i, j].astype(np.float64) / 255.0
+        else:
+            colors = np.repeat(np.ascontiguousarray(color, F32).reshape(h, w)[i, j].astype(np.float64)[:, None], 3, axis=1)
+    return pts, colors
+
+
+# ---------------------------------------------------------------------------
+# ScalableTSDFVolume (Core/Integration/ScalableTSDFVolume.cpp): a hash of uniform volume units of resolution R
+# ---------------------------------------------------------------------------
+def new_scalable(voxel_length, sdf_trunc, color_type, unit_resolution=16, stride=4):
+    """units: {(ix, iy, iz): a uniform volume of length unit_length and origin index * unit_length}.  A unit's OWN voxel
+    length is unit_length / R = (voxel_length * R) / R, as the reference's OpenVolumeUnit makes it."""
+    return dict(voxel_length=float(voxel_length), sdf_trunc=float(sdf_trunc), color_type=int(color_type), R=int(unit_resolution),
+                unit_length=float(voxel_length) * int(unit_resolution), stride=int(stride), units={})
+
+
+def locate_units(points, unit_length):
+    """LocateVolumeUnit: (int)floor(p / unit_length) per component; also how far the nearest quotient is from an integer,
+    relative to its magnitude (the margin of the f64 decision)"""
+    q = points / unit_length
+    with np.errstate(all="ignore"):
+        margin = float(np.min(np.abs(q - np.rint(q)) / np.maximum(np.abs(q), 1.0))) if q.size else np.inf
+    return np.floor(q).astype(np.int64), margin
+
+
+def touched_units(svol, depth, intrinsic, extrinsic, trace=None):
+    """the unit indices ScalableTSDFVolume::Integrate opens for a frame (sorted): every unit between LocateVolumeUnit(p -
+    sdf_trunc) and LocateVolumeUnit(p + sdf_trunc) of every strided back-projected point"""
+    pts, _ = point_cloud_from_depth(depth, intrinsic, extrinsic, svol["stride"])
+    if not len(pts):
+        return []
+    lo, m0 = locate_units(pts - svol["sdf_trunc"], svol["unit_length"])
+    hi, m1 = locate_units(pts + svol["sdf_trunc"], svol["unit_length"])
+    if trace is not None:
+        trace["floor_margin"] = min(trace.get("floor_margin", np.inf), m0, m1)
+        trace["span"] = max(trace.get("span", 0), int((hi - lo).max()) + 1)
+    keys = set()
+    for row in set(map(tuple, np.concatenate([lo, hi], 1).tolist())):
+        for x in range(row[0], row[3] + 1):
+            for y in range(row[1], row[4] + 1):
+                for z in range(row[2], row[5] + 1):
+                    keys.add((x, y, z))
+    return sorted(keys)
+
+
+def scalable_integrate(svol, depth, color, intrinsic, extrinsic, trace=None):
+    for key in touched_units(svol, depth, intrinsic, extrinsic, trace):
+        if key not in svol["units"]:
+            svol["units"][key] = new_volume(svol["unit_length"], svol["R"], svol["sdf_trunc"], svol["color_type"],
+                                            np.array(key, np.float64) * svol["unit_length"])
+        integrate(svol["units"][key], depth, color, intrinsic, extrinsic)
+    return svol
+
+
+def _dense(svol):
+    """every unit laid into one grid of global voxel coordinates (a missing unit: weight 0, tsdf 0, as the reference reads
+    it), one unit of margin on the far side -> tsdf, weight, color, present (per unit), lo (the first unit's index)"""
+    R = svol["R"]
+    keys = np.array(sorted(svol["units"]), np.int64).reshape(-1, 3)
+    lo = keys.min(0) - 1
+    n = keys.max(0) - lo + 2
+    f = np.zeros(tuple(n * R), F32); w = np.zeros(tuple(n * R), F32)
+    c = np.zeros(tuple(n * R) + (3,), F32) if svol["color_type"] != COLOR_NONE else None
+    present = np.zeros(tuple(n), bool)
+    for key in map(tuple, keys):
+        u = svol["units"][key]
+        a = (np.array(key) - lo) * R
+        sl = tuple(slice(a[i], a[i] + R) for i in range(3))
+        f[sl] = u["tsdf"].reshape(R, R, R); w[sl] = u["weight"].reshape(R, R, R)
+        if c is not None:
+            c[sl] = u["color"].reshape(R, R, R, 3)
+        present[tuple(np.array(key) - lo)] = True
+    return f, w, c, present, lo
+
+
+def _scalable_tsdf_at(svol, dense, p):
+    """ScalableTSDFVolume::GetTSDFAt at the rows of p, f64: 0 where the unit of p - voxel_length / 2 is missing; the voxel index
+    clamped into the unit; a corner in a missing unit reads 0"""
+    f, w, c, present, lo = dense
+    R, vl, ul = svol["R"], svol["voxel_length"], svol["unit_length"]
+    t = f.astype(np.float64)
+    pl = p - 0.5 * vl
+    index0 = np.floor(pl / ul).astype(np.int64)
+    g = (pl - index0.astype(np.float64) * ul) / vl
+    idx0 = np.clip(np.floor(g).astype(np.int64), 0, R - 1)
+    r = g - idx0
+    u = index0 - lo
+    inside = np.all((u >= 0) & (u < np.array(present.shape)), axis=1)
+    uc = np.where(inside[:, None], u, 0)
+    have = inside & present[uc[:, 0], uc[:, 1], uc[:, 2]]
+    gi = np.where(have[:, None], uc * R + idx0, 0)
+    x, y, z = gi[:, 0], gi[:, 1], gi[:, 2]
+    r0, r1, r2 = r[:, 0], r[:, 1], r[:, 2]
+    v = (1 - r0) * ((1 - r1) * ((1 - r2) * t[x, y, z] + r2 * t[x, y, z + 1]) + r1 * ((1 - r2) * t[x, y + 1, z] + r2 * t[x, y + 1, z + 1])) \
+        + r0 * ((1 - r1) * ((1 - r2) * t[x + 1, y, z] + r2 * t[x + 1, y, z + 1]) + r1 * ((1 - r2) * t[x + 1, y + 1, z] + r2 * t[x + 1, y + 1, z + 1]))
+    return np.where(have, v, 0.0)
+
+
+def scalable_extract_point_cloud(svol, with_gradient=False):
+    """ScalableTSDFVolume::ExtractPointCloud -> points, normals, colors.  The order is the library's definition (the
+    reference's is the iteration order of an unordered_map): units in lexicographic order of their index, and x, y, z, axis
+    lexicographic within a unit."""
+    empty = (np.zeros((0, 3)), np.zeros((0, 3)), None if svol["color_type"] == COLOR_NONE else np.zeros((0, 3)))
+    if not svol["units"]:
+        return empty + (np.zeros((0, 3)),) if with_gradient else empty
+    R, vl, ul = svol["R"], svol["voxel_length"], svol["unit_length"]
+    half = vl * 0.5
+    dense = _dense(svol)
+    f, w, c, present, lo = dense
+    ok = _valid(w, f)
+    rows = []
+    for i in range(3):
+        a = tuple(slice(0, f.shape[k] - 1) for k in range(3))
+        b = tuple(slice(1, f.shape[k]) if k == i else slice(0, f.shape[k] - 1) for k in range(3))
+        with np.errstate(all="ignore"):
+            m = ok[a] & ok[b] & (f[a] * f[b] < 0)
+        at = np.argwhere(m)
+        rows.append(np.concatenate([at, np.full((len(at), 1), i)], 1))
+    rows = np.concatenate(rows, 0)
+    unit, loc = rows[:, :3] // R, rows[:, :3] % R
+    order = np.lexsort((rows[:, 3], loc[:, 2], loc[:, 1], loc[:, 0], unit[:, 2], unit[:, 1], unit[:, 0]))
+    rows, unit, loc = rows[order], unit[order], loc[order]
+    n = len(rows); ax = rows[:, 3]
+    g0 = rows[:, :3]; g1 = g0.copy(); g1[np.arange(n), ax] += 1
+    f0 = f[g0[:, 0], g0[:, 1], g0[:, 2]]; f1 = f[g1[:, 0], g1[:, 1], g1[:, 2]]
+    r0, r1 = np.abs(f0), np.abs(f1)
+    rs = (r0 + r1).astype(np.float64)
+    p = (half + vl * loc.astype(np.float64)) + (unit + lo).astype(np.float64) * ul
+    p0 = p[np.arange(n), ax]
+    p1 = p0 + vl
+    p[np.arange(n), ax] = (p0 * r1.astype(np.float64) + p1 * r0.astype(np.float64)) / rs
+    colors = None
+    if svol["color_type"] != COLOR_NONE:
+        c0 = c[g0[:, 0], g0[:, 1], g0[:, 2]]; c1 = c[g1[:, 0], g1[:, 1], g1[:, 2]]
+        cc = (c0 * r1[:, None] + c1 * r0[:, None]) / (r0 + r1)[:, None]
+        if svol["color_type"] == COLOR_RGB8:
+            cc = cc / F32(255.0)
+        colors = cc.astype(np.float64)
+    gap = 0.99 * vl
+    g = np.empty_like(p)
+    for i in range(3):
+        lo_p, hi_p = p.copy(), p.copy()
+        lo_p[:, i] -= gap; hi_p[:, i] += gap
+        g[:, i] = _scalable_tsdf_at(svol, dense, hi_p) - _scalable_tsdf_at(svol, dense, lo_p)
+    out = (p, normalized(g), colors)
+    return out + (g,) if with_gradient else out
+
+
+def scalable_extract_voxel_point_cloud(svol):
+    """ScalableTSDFVolume::ExtractVoxelPointCloud: every unit's own voxel cloud, units in lexicographic order"""
+    pts, cols = [np.zeros((0, 3))], [np.zeros((0, 3))]
+    for key in sorted(svol["units"]):
+        p, c = extract_voxel_point_cloud(svol["units"][key])
+        pts.append(p); cols.append(c)
+    return np.concatenate(pts, 0), np.concatenate(cols, 0)
+
+
+def sort_rows(points, *others):
+    """rows in lexicographic order of their points (what the fixture's scalable extractions are recorded in)"""
+    order = np.lexsort((points[:, 2], points[:, 1], points[:, 0]))
+    return (points[order],) + tuple(None if o is None else o[order] for o in others)

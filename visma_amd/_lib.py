@@ -115,6 +115,99 @@ class OdometryResult:
         return iter((self.success, self.T, self.information))
 
 
+TSDF_COLOR_NONE, TSDF_COLOR_RGB8, TSDF_COLOR_GRAY32 = 0, 1, 2
+_TSDF_COLOR_NAMES = {"none": TSDF_COLOR_NONE, "rgb8": TSDF_COLOR_RGB8, "gray32": TSDF_COLOR_GRAY32}
+
+
+def _tsdf_color_type(color_type):
+    return _TSDF_COLOR_NAMES[color_type.lower()] if isinstance(color_type, str) else int(color_type)
+
+
+def _tsdf_color_image(color, color_type, shape):
+    """the colour image of a frame as the C ABI takes it: h x w x 3 uint8 (RGB8), h x w fp32 (GRAY32), None otherwise"""
+    if color_type == TSDF_COLOR_NONE or color is None:
+        return None
+    color = np.ascontiguousarray(color, dtype=np.uint8 if color_type == TSDF_COLOR_RGB8 else np.float32)
+    if color.shape != (shape + (3,) if color_type == TSDF_COLOR_RGB8 else shape):
+        raise ValueError("the colour image does not fit the depth image and the colour type")
+    return color
+
+
+class TsdfVolume:
+    """A TSDF volume resident on the device (visma_icp_tsdf): Open3D's UniformTSDFVolume (Context.tsdf_uniform) or
+    ScalableTSDFVolume (Context.tsdf_scalable; `resolution` is then a unit's and `length` its side).  Lives until close()
+    or the context's end."""
+
+    def __init__(self, ctx, handle, length, resolution, sdf_trunc, color_type, origin, scalable=False, voxel_length=None):
+        self.ctx, self._v = ctx, handle
+        self.length, self.resolution, self.sdf_trunc, self.color_type = float(length), int(resolution), float(sdf_trunc), color_type
+        self.origin, self.scalable = origin, bool(scalable)
+        self.voxel_length = self.length / self.resolution if voxel_length is None else float(voxel_length)
+
+    def close(self):
+        if self._v is not None and self.ctx._h:
+            self.ctx._chk(self.ctx.L.visma_icp_tsdf_destroy(self.ctx._h, self._v))
+        self._v = None
+
+    def reset(self):
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_reset(self.ctx._h, self._v))
+
+    def integrate(self, depth, color, intrinsic, extrinsic, intrinsic_size=None):
+        """Integrate(): depth h x w fp32 (metres), color by the volume's colour type (h x w x 3 uint8 | h x w fp32 | None),
+        intrinsic [fx, fy, cx, cy] of an image of intrinsic_size = (w, h) (default: the depth image's), extrinsic 4 x 4
+        world -> camera."""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.ndim != 2:
+            raise ValueError("an h x w depth image")
+        h, w = depth.shape
+        color = _tsdf_color_image(color, self.color_type, (h, w))
+        k = _f64(intrinsic, (4,)); E = _f64(extrinsic, (16,))
+        iw, ih = (w, h) if intrinsic_size is None else intrinsic_size
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_integrate(self.ctx._h, self._v, w, h, _p(depth, _fp),
+                                                          None if color is None else color.ctypes.data_as(C.c_void_p), _p(k, _dp),
+                                                          int(iw), int(ih), _p(E, _dp)))
+
+    def extract_point_cloud(self):
+        """ExtractPointCloud() -> points, normals, colors (n x 3 f64; colors None for a volume without colour), in the
+        reference's order: x, y, z, axis lexicographic."""
+        n = C.c_int64(0)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_extract_point_cloud(self.ctx._h, self._v, C.byref(n)))
+        n = n.value
+        pts, nrm = np.empty((n, 3)), np.empty((n, 3))
+        col = np.empty((n, 3)) if self.color_type != TSDF_COLOR_NONE else None
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_point_cloud(self.ctx._h, self._v, _p(pts, _dp), _p(nrm, _dp),
+                                                                None if col is None else _p(col, _dp), n))
+        return pts, nrm, col
+
+    def extract_voxel_point_cloud(self):
+        """ExtractVoxelPointCloud() -> points, colors (n x 3 f64)"""
+        n = C.c_int64(0)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_extract_voxel_point_cloud(self.ctx._h, self._v, C.byref(n)))
+        n = n.value
+        pts, col = np.empty((n, 3)), np.empty((n, 3))
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_voxel_point_cloud(self.ctx._h, self._v, _p(pts, _dp), _p(col, _dp), n))
+        return pts, col
+
+    def units(self):
+        """The unit indices of a scalable volume (n x 3 int32) in lexicographic order: the order of its extractions."""
+        n = C.c_int64(0)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_units(self.ctx._h, self._v, None, 0, C.byref(n)))
+        out = np.empty((max(n.value, 1), 3), np.int32)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_units(self.ctx._h, self._v, _p(out, _ip), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def volume(self, unit=None):
+        """-> tsdf, weight (R^3 fp32, voxel x R^2 + y R + z), color (R^3 x 3 fp32, or None) of a uniform volume, or of the
+        unit with index `unit` (three ints) of a scalable one"""
+        unit = None if unit is None else np.ascontiguousarray(unit, dtype=np.int32).reshape(3)
+        n = self.resolution ** 3
+        tsdf, weight = np.empty(n, np.float32), np.empty(n, np.float32)
+        color = np.empty((n, 3), np.float32) if self.color_type != TSDF_COLOR_NONE else None
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_volume(self.ctx._h, self._v, None if unit is None else _p(unit, _ip), _p(tsdf, _fp), _p(weight, _fp),
+                                                           None if color is None else _p(color, _fp)))
+        return tsdf, weight, color
+
+
 class CGlobalOptimizationCriteria(C.Structure):
     """visma_icp_global_optimization_criteria"""
     _fields_ = [("max_iteration", C.c_int32), ("min_relative_increment", C.c_double),
@@ -348,6 +441,21 @@ def _bind(L):
         L.visma_icp_odometry_correspondences.argtypes = [C.c_void_p, C.c_int, _dp, _ip, _i64]
         L.visma_icp_odometry_step.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int, _dp, _i64, _dp]
         L.visma_icp_odometry_information.argtypes = [C.c_void_p, _dp, _dp, _i64]
+    if hasattr(L, "visma_icp_tsdf_create_uniform"):      # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp = C.POINTER(C.c_int64), C.c_void_p
+        L.visma_icp_tsdf_create_uniform.argtypes = [_vp, C.c_double, C.c_int, C.c_double, C.c_int, _dp, C.POINTER(_vp)]
+        L.visma_icp_tsdf_destroy.argtypes = [_vp, _vp]
+        L.visma_icp_tsdf_reset.argtypes = [_vp, _vp]
+        L.visma_icp_tsdf_integrate.argtypes = [_vp, _vp, C.c_int, C.c_int, _fp, _vp, _dp, C.c_int, C.c_int, _dp]
+        L.visma_icp_tsdf_extract_point_cloud.argtypes = [_vp, _vp, _i64]
+        L.visma_icp_tsdf_get_point_cloud.argtypes = [_vp, _vp, _dp, _dp, _dp, C.c_int64]
+        L.visma_icp_tsdf_extract_voxel_point_cloud.argtypes = [_vp, _vp, _i64]
+        L.visma_icp_tsdf_get_voxel_point_cloud.argtypes = [_vp, _vp, _dp, _dp, C.c_int64]
+        L.visma_icp_tsdf_get_volume.argtypes = [_vp, _vp, _ip, _fp, _fp, _fp]
+        L.visma_icp_tsdf_create_scalable.argtypes = [_vp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]
+        L.visma_icp_tsdf_get_units.argtypes = [_vp, _vp, _ip, C.c_int64, _i64]
+        L.visma_icp_point_cloud_from_depth.argtypes = [_vp, C.c_int, C.c_int, _fp, _dp, _dp, C.c_int, _dp, C.c_int64, _i64]
+        L.visma_icp_point_cloud_from_rgbd.argtypes = [_vp, C.c_int, C.c_int, _fp, _vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -1138,6 +1246,58 @@ class Context:
         out = np.empty(36); k = C.c_int64(0)
         self._chk(self.L.visma_icp_odometry_information(self._h, _p(T, _dp), _p(out, _dp), C.byref(k)))
         return out.reshape(6, 6), k.value
+
+    # ---- TSDF integration (visma_icp.h) ----
+    def tsdf_uniform(self, length, resolution, sdf_trunc, color_type=TSDF_COLOR_NONE, origin=(0.0, 0.0, 0.0)):
+        """Open3D's UniformTSDFVolume(length, resolution, sdf_trunc, color_type, origin) on the device -> TsdfVolume.
+        color_type: TSDF_COLOR_NONE | TSDF_COLOR_RGB8 | TSDF_COLOR_GRAY32 or "none" | "rgb8" | "gray32"."""
+        color_type = _tsdf_color_type(color_type)
+        origin = _f64(origin, (3,))
+        v = C.c_void_p()
+        self._chk(self.L.visma_icp_tsdf_create_uniform(self._h, float(length), int(resolution), float(sdf_trunc), color_type,
+                                                       _p(origin, _dp), C.byref(v)))
+        return TsdfVolume(self, v, length, resolution, sdf_trunc, color_type, origin)
+
+    def tsdf_scalable(self, voxel_length, sdf_trunc, color_type=TSDF_COLOR_NONE, volume_unit_resolution=16, depth_sampling_stride=4,
+                      initial_units=0):
+        """Open3D's ScalableTSDFVolume(voxel_length, sdf_trunc, color_type, volume_unit_resolution, depth_sampling_stride) on
+        the device -> TsdfVolume; initial_units: the first capacity of its unit pool (0: 256; it doubles when full)."""
+        color_type = _tsdf_color_type(color_type)
+        v = C.c_void_p()
+        self._chk(self.L.visma_icp_tsdf_create_scalable(self._h, float(voxel_length), float(sdf_trunc), color_type,
+                                                        int(volume_unit_resolution), int(depth_sampling_stride), int(initial_units), C.byref(v)))
+        return TsdfVolume(self, v, float(voxel_length) * int(volume_unit_resolution), volume_unit_resolution, sdf_trunc, color_type, None,
+                          scalable=True, voxel_length=voxel_length)
+
+    def _point_cloud_capacity(self, depth, stride):
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        if depth.ndim != 2:
+            raise ValueError("an h x w depth image")
+        h, w = depth.shape
+        s = max(int(stride), 1)
+        return depth, h, w, max(1, -(-w // s) * -(-h // s))
+
+    def point_cloud_from_depth(self, depth, intrinsic, extrinsic=None, stride=1):
+        """Open3D's CreatePointCloudFromDepthImage of a float depth image (metres) -> points (n x 3 f64), row-major pixel
+        order; extrinsic: world -> camera (default: the identity)."""
+        depth, h, w, cap = self._point_cloud_capacity(depth, stride)
+        k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+        pts = np.empty((cap, 3)); n = C.c_int64(0)
+        self._chk(self.L.visma_icp_point_cloud_from_depth(self._h, w, h, _p(depth, _fp), _p(k, _dp), _p(E, _dp), int(stride),
+                                                          _p(pts, _dp), cap, C.byref(n)))
+        return pts[:n.value].copy()
+
+    def point_cloud_from_rgbd(self, depth, color, intrinsic, extrinsic=None):
+        """Open3D's CreatePointCloudFromRGBDImage: color h x w x 3 uint8 or h x w fp32 -> points, colors (n x 3 f64)."""
+        depth, h, w, cap = self._point_cloud_capacity(depth, 1)
+        color = np.asarray(color)
+        color_type = TSDF_COLOR_RGB8 if color.dtype == np.uint8 else TSDF_COLOR_GRAY32
+        color = _tsdf_color_image(color, color_type, (h, w))
+        k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+        pts, col = np.empty((cap, 3)), np.empty((cap, 3)); n = C.c_int64(0)
+        self._chk(self.L.visma_icp_point_cloud_from_rgbd(self._h, w, h, _p(depth, _fp), color.ctypes.data_as(C.c_void_p), color_type,
+                                                         _p(k, _dp), _p(E, _dp), _p(pts, _dp), _p(col, _dp), cap, C.byref(n)))
+        return pts[:n.value].copy(), col[:n.value].copy()
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""

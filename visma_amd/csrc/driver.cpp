@@ -1716,6 +1716,230 @@ int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_g
     return VISMA_ICP_OK;
 }
 
+// ---- TSDF integration (tsdf.hip) -----------------------------------------------------------------------------------------
+// every argument check of a volume call, before anything reaches a device
+static int check_tsdf_volume(visma_icp_ctx *ctx, visma_icp_tsdf *volume)
+{
+    if (!volume) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL volume");
+    for (const auto &v : ctx->volumes)
+        if (v.get() == volume) return VISMA_ICP_OK;
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "not a volume of this context");
+}
+
+static bool finite_positive(double v) { return std::isfinite(v) && v > 0.0; }
+
+// ... and of a frame: sizes, intrinsic, colour by colour type; *f is what the engine is given
+static int check_tsdf_frame(visma_icp_ctx *ctx, int w, int h, const float *depth, const void *color, int color_type, const double *intrinsic,
+                            int intrinsic_w, int intrinsic_h, const double *extrinsic, TsdfFrame *f)
+{
+    if (!depth || !intrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (w < 1 || h < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image needs w >= 1 and h >= 1");
+    if ((int64_t)w * h > (int64_t)1 << 30) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image of more than 2^30 pixels");
+    if (w != intrinsic_w || h != intrinsic_h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the image size differs from the intrinsic's");
+    if (color_type != kTsdfColorNone && !color) return ctx->fail(VISMA_ICP_ERR_INVALID, "no colour image for a coloured volume");
+    if (!std::isfinite(intrinsic[0]) || !std::isfinite(intrinsic[1]) || intrinsic[0] == 0.0 || intrinsic[1] == 0.0)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "a focal length that is zero or not finite");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "TSDF integration runs on one rank");
+    f->w = w; f->h = h; f->depth = depth; f->color = color_type != kTsdfColorNone ? color : nullptr;
+    f->fx = intrinsic[0]; f->fy = intrinsic[1]; f->cx = intrinsic[2]; f->cy = intrinsic[3];
+    const Mat4 E = extrinsic ? Mat4::from(extrinsic) : Mat4::identity();
+    std::memcpy(f->extrinsic, E.m, sizeof(E.m));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_create_uniform(visma_icp_ctx *ctx, double length, int resolution, double sdf_trunc, int color_type,
+                                  const double origin[3], visma_icp_tsdf **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (resolution < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "resolution < 1");
+    if (!finite_positive(length) || !finite_positive(sdf_trunc))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "length and sdf_trunc must be positive and finite");
+    if (color_type != kTsdfColorNone && color_type != kTsdfColorRgb8 && color_type != kTsdfColorGray32)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown colour type");
+    if (origin && !(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2])))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "an origin that is not finite");
+    // the reference's voxel index is an int: 1290^3 < 2^31 <= 1291^3 (five floats per voxel: 43 GB at most)
+    if (resolution > 1290) return ctx->fail(VISMA_ICP_ERR_INVALID, "a volume too large for memory");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "TSDF integration runs on one rank");
+    std::unique_ptr<visma_icp_tsdf> v(new visma_icp_tsdf);
+    v->cfg.resolution = resolution; v->cfg.length = length; v->cfg.sdf_trunc = sdf_trunc; v->cfg.color_type = color_type;
+    for (int a = 0; a < 3; a++) v->cfg.origin[a] = origin ? origin[a] : 0.0;
+    int rc = ctx->eng->tsdf_create(v->cfg, &v->id);
+    if (rc) return ctx->eng_fail(rc);
+    *out = v.get();
+    ctx->volumes.push_back(std::move(v));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_create_scalable(visma_icp_ctx *ctx, double voxel_length, double sdf_trunc, int color_type, int volume_unit_resolution,
+                                   int depth_sampling_stride, int initial_units, visma_icp_tsdf **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (volume_unit_resolution < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "resolution < 1");
+    if (volume_unit_resolution > 256) return ctx->fail(VISMA_ICP_ERR_INVALID, "a volume unit too large for memory");
+    if (!finite_positive(voxel_length) || !finite_positive(sdf_trunc))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "voxel_length and sdf_trunc must be positive and finite");
+    if (color_type != kTsdfColorNone && color_type != kTsdfColorRgb8 && color_type != kTsdfColorGray32)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown colour type");
+    if (depth_sampling_stride < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "stride < 1");
+    if (initial_units < 0 || initial_units > 1 << 20) return ctx->fail(VISMA_ICP_ERR_INVALID, "initial_units outside 0 .. 2^20");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "TSDF integration runs on one rank");
+    std::unique_ptr<visma_icp_tsdf> v(new visma_icp_tsdf);
+    v->cfg.scalable = 1;
+    v->cfg.resolution = volume_unit_resolution; v->cfg.voxel_length = voxel_length;
+    v->cfg.length = voxel_length * volume_unit_resolution;           // volume_unit_length_
+    v->cfg.sdf_trunc = sdf_trunc; v->cfg.color_type = color_type;
+    v->cfg.stride = depth_sampling_stride;
+    v->cfg.initial_units = initial_units > 0 ? initial_units : 256;
+    int rc = ctx->eng->tsdf_create(v->cfg, &v->id);
+    if (rc) return ctx->eng_fail(rc);
+    *out = v.get();
+    ctx->volumes.push_back(std::move(v));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_get_units(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int32_t *indices, int64_t capacity, int64_t *out_n)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (!out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out_n = 0;
+    if (!volume->cfg.scalable) return ctx->fail(VISMA_ICP_ERR_INVALID, "a uniform volume has no units");
+    std::vector<int32_t> keys;
+    int rc = ctx->eng->tsdf_get_units(volume->id, &keys);
+    if (rc) return ctx->eng_fail(rc);
+    *out_n = (int64_t)(keys.size() / 3);
+    if (!indices) return VISMA_ICP_OK;
+    if (capacity < *out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "capacity below the number of units");
+    std::copy(keys.begin(), keys.end(), indices);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_destroy(visma_icp_ctx *ctx, visma_icp_tsdf *volume)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    int rc = ctx->eng->tsdf_destroy(volume->id);
+    for (size_t i = 0; i < ctx->volumes.size(); i++)
+        if (ctx->volumes[i].get() == volume) { ctx->volumes.erase(ctx->volumes.begin() + (std::ptrdiff_t)i); break; }
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_reset(visma_icp_ctx *ctx, visma_icp_tsdf *volume)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    volume->rows[0] = volume->rows[1] = -1;
+    int rc = ctx->eng->tsdf_reset(volume->id);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_integrate(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int w, int h, const float *depth, const void *color,
+                             const double intrinsic[4], int intrinsic_w, int intrinsic_h, const double extrinsic[16])
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (!extrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    TsdfFrame f;
+    if (int rc = check_tsdf_frame(ctx, w, h, depth, color, volume->cfg.color_type, intrinsic, intrinsic_w, intrinsic_h, extrinsic, &f))
+        return rc;
+    volume->rows[0] = volume->rows[1] = -1;
+    int rc = ctx->eng->tsdf_integrate(volume->id, f);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+static int tsdf_extract(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int voxel_cloud, int64_t *out_n)
+{
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (!out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    volume->rows[voxel_cloud] = -1;
+    int rc = ctx->eng->tsdf_extract(volume->id, voxel_cloud, out_n);
+    if (rc) return ctx->eng_fail(rc);
+    volume->rows[voxel_cloud] = *out_n;
+    return VISMA_ICP_OK;
+}
+
+static int tsdf_get_extract(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int voxel_cloud, double *points, double *normals,
+                            double *colors, int64_t n)
+{
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (volume->rows[voxel_cloud] < 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no extraction: extract first");
+    if (n != volume->rows[voxel_cloud]) return ctx->fail(VISMA_ICP_ERR_INVALID, "n differs from the extraction's row count");
+    int rc = ctx->eng->tsdf_get_extract(volume->id, voxel_cloud, points, normals, colors);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_extract_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_n)
+{
+    CTX_CHECK();
+    return tsdf_extract(ctx, volume, 0, out_n);
+}
+
+int visma_icp_tsdf_get_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *points, double *normals, double *colors,
+                                   int64_t n)
+{
+    CTX_CHECK();
+    return tsdf_get_extract(ctx, volume, 0, points, normals, colors, n);
+}
+
+int visma_icp_tsdf_extract_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_n)
+{
+    CTX_CHECK();
+    return tsdf_extract(ctx, volume, 1, out_n);
+}
+
+int visma_icp_tsdf_get_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *points, double *colors, int64_t n)
+{
+    CTX_CHECK();
+    return tsdf_get_extract(ctx, volume, 1, points, nullptr, colors, n);
+}
+
+int visma_icp_tsdf_get_volume(visma_icp_ctx *ctx, visma_icp_tsdf *volume, const int32_t unit_index[3], float *tsdf, float *weight,
+                              float *color)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (volume->cfg.scalable && !unit_index) return ctx->fail(VISMA_ICP_ERR_INVALID, "a scalable volume is read unit by unit: no unit index");
+    if (!volume->cfg.scalable && unit_index) return ctx->fail(VISMA_ICP_ERR_INVALID, "a uniform volume has no units");
+    int rc = ctx->eng->tsdf_get_volume(volume->id, unit_index, tsdf, weight, color);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+static int point_cloud_from_frame(visma_icp_ctx *ctx, int w, int h, const float *depth, const void *color, int color_type,
+                                  const double *intrinsic, const double *extrinsic, int stride, double *points, double *colors,
+                                  int64_t capacity, int64_t *out_n)
+{
+    if (!out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out_n = 0;
+    if (stride < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "stride < 1");
+    TsdfFrame f;
+    if (int rc = check_tsdf_frame(ctx, w, h, depth, color, color_type, intrinsic, w, h, extrinsic, &f)) return rc;
+    const int64_t most = (((int64_t)w - 1) / stride + 1) * (((int64_t)h - 1) / stride + 1);   // (in 64 bits: stride may be INT_MAX)
+    if (points && capacity < most) return ctx->fail(VISMA_ICP_ERR_INVALID, "capacity below ceil(w / stride) * ceil(h / stride)");
+    int rc = ctx->eng->point_cloud_from_depth(f, color_type, stride, points, points ? colors : nullptr, out_n);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_point_cloud_from_depth(visma_icp_ctx *ctx, int w, int h, const float *depth, const double intrinsic[4],
+                                     const double extrinsic[16], int stride, double *points, int64_t capacity, int64_t *out_n)
+{
+    CTX_CHECK();
+    return point_cloud_from_frame(ctx, w, h, depth, nullptr, kTsdfColorNone, intrinsic, extrinsic, stride, points, nullptr, capacity, out_n);
+}
+
+int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int h, const float *depth, const void *color, int color_type,
+                                    const double intrinsic[4], const double extrinsic[16], double *points, double *colors,
+                                    int64_t capacity, int64_t *out_n)
+{
+    CTX_CHECK();
+    if (color_type != kTsdfColorRgb8 && color_type != kTsdfColorGray32) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown colour type");
+    return point_cloud_from_frame(ctx, w, h, depth, color, color_type, intrinsic, extrinsic, 1, points, colors, capacity, out_n);
+}
+
 int visma_icp_set_nn_mode(visma_icp_ctx *ctx, int nn_mode)
 {
     CTX_CHECK();

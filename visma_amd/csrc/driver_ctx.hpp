@@ -5,6 +5,13 @@
 using namespace visma;
 using namespace visma::drv;
 
+// a TSDF volume of a context: the engine's id, what it was created with, and the rows of its last extractions
+struct visma_icp_tsdf {
+    int id = 0;
+    TsdfConfig cfg;
+    int64_t rows[2] = {-1, -1};       // [0] ExtractPointCloud, [1] ExtractVoxelPointCloud; -1: none since the last change
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -34,6 +41,7 @@ struct visma_icp_ctx {
     int64_t ns_total = 0;
     // the frame pair of the last visma_icp_odometry_prepare (resident on the engine): what the later calls check against
     struct { bool ready = false; int w = 0, h = 0, n_levels = 0; } odo;
+    std::vector<std::unique_ptr<visma_icp_tsdf>> volumes;   // the engine frees their device memory with itself
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

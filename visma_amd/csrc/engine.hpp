@@ -403,6 +403,36 @@ public:
     }
     // the ten sums of information.hip over the target's xyz image at the full-size pairs of T
     virtual int odometry_information(const Mat4 &, double * /* sums[10] */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // TSDF integration (tsdf.hip): volumes resident on the engine, named by the id tsdf_create hands out; they live until
+    // tsdf_destroy or the engine's end.  What the driver checked arrives as it is.  Independent of the clouds and of the
+    // odometry frames.  (TsdfConfig, TsdfFrame: kernels.h.)
+    virtual int tsdf_create(const TsdfConfig &, int * /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int tsdf_destroy(int /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int tsdf_reset(int /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int tsdf_integrate(int /* id */, const TsdfFrame &) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // ExtractPointCloud (voxel_cloud == 0) or ExtractVoxelPointCloud, left on the engine: the number of rows
+    virtual int tsdf_extract(int /* id */, int /* voxel_cloud */, int64_t * /* n */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // ... and its rows (n x 3 doubles each; normals and colors may be NULL)
+    virtual int tsdf_get_extract(int /* id */, int /* voxel_cloud */, double * /* points */, double * /* normals */, double * /* colors */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // the unit indices of a scalable volume, 3 per unit, in lexicographic order
+    virtual int tsdf_get_units(int /* id */, std::vector<int32_t> *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // a uniform volume (unit == NULL) or the unit of that index (VISMA_ICP_ERR_INVALID: no such unit)
+    virtual int tsdf_get_volume(int /* id */, const int32_t * /* unit */, float * /* tsdf */, float * /* weight */, float * /* color */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
+    // CreatePointCloudFromDepthImage / FromRGBDImage of one frame: the rows in row-major pixel order (points NULL: count only)
+    virtual int point_cloud_from_depth(const TsdfFrame &, int /* color_type */, int /* stride */, double * /* points */, double * /* colors */,
+                                       int64_t * /* n */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

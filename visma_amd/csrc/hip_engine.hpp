@@ -51,6 +51,7 @@ public:
         free_dev(d_trim_mask_); free_dev(d_trim_order_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
         pair_.release();
         if (odo_.arena) (void)hipFree(odo_.arena);
+        for (auto &v : tsdf_) tsdf_device_destroy(v.second);
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -340,6 +341,17 @@ public:
     int odometry_step(int level, const Mat4 &T, int method, double *stats) override;
     int odometry_information(const Mat4 &T, double *sums) override;
 
+    // TSDF integration (tsdf.hip): the volumes by id; each owns its device memory (tsdf_device_*), all on the one stream
+    int tsdf_create(const TsdfConfig &cfg, int *id) override;
+    int tsdf_destroy(int id) override;
+    int tsdf_reset(int id) override;
+    int tsdf_integrate(int id, const TsdfFrame &f) override;
+    int tsdf_extract(int id, int voxel_cloud, int64_t *n) override;
+    int tsdf_get_extract(int id, int voxel_cloud, double *points, double *normals, double *colors) override;
+    int tsdf_get_units(int id, std::vector<int32_t> *keys) override;
+    int tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *weight, float *color) override;
+    int point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n) override;
+
     // colored ICP (color_gradient.hip, colored.hip): f64 intensities of both clouds, the target's colour gradient, then the
     // plain pass and the reduction over the two rows per pair
     int set_source_intensity(const double *by_position, int64_t ns) override;
@@ -435,6 +447,11 @@ private:
         void *arena = nullptr;
         size_t arena_bytes = 0;
     } odo_;
+    // TSDF volumes: id -> device object; ids are never reused within an engine
+    std::unordered_map<int, TsdfDevice *> tsdf_;
+    int tsdf_next_id_ = 1;
+    // the device bound, no persistent launch left on the stream, and the volume of `id` (NULL with err_ set: unknown id)
+    int tsdf_enter(int id, TsdfDevice **D);
     // the launch of the correspondence kernel of `level` at T into odo_.idx
     int odometry_launch_correspondences(int level, const Mat4 &T);
     // the arguments every pass over odo_.idx shares: no clouds, the scratch and its ticket word (a new sequence number)

@@ -1073,6 +1073,115 @@ int HipEngine::odometry_get_image(int which, int level, float *out)
     return VISMA_ICP_OK;
 }
 
+// ---- TSDF integration (tsdf.hip) ----
+int HipEngine::tsdf_enter(int id, TsdfDevice **D)
+{
+    if (is_sharded()) { err_ = "TSDF integration runs on one rank"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(hipSetDevice(device_));
+    if (sess_live_) { int rc = end_session(); if (rc) return rc; }
+    if (D) {
+        auto it = tsdf_.find(id);
+        if (it == tsdf_.end()) { err_ = "no such TSDF volume"; return VISMA_ICP_ERR_INVALID; }
+        *D = it->second;
+    }
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_create(const TsdfConfig &cfg, int *id)
+{
+    int rc = tsdf_enter(0, nullptr);
+    if (rc) return rc;
+    TsdfDevice *D = nullptr;
+    HIP_TRY(tsdf_device_create(cfg, stream_, &D));
+    *id = tsdf_next_id_++;
+    tsdf_[*id] = D;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_destroy(int id)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    tsdf_device_destroy(D);
+    tsdf_.erase(id);
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_reset(int id)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(tsdf_device_reset(D));
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_integrate(int id, const TsdfFrame &f)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    // (a scalable volume back-projects the strided pixels: the camera pose is the extrinsic's inverse, as below)
+    const Mat4 pose = inverse4(Mat4::from(f.extrinsic));
+    HIP_TRY(tsdf_device_integrate(D, f, pose.m));
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_extract(int id, int voxel_cloud, int64_t *n)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(tsdf_device_extract(D, voxel_cloud, n));
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_get_extract(int id, int voxel_cloud, double *points, double *normals, double *colors)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(tsdf_device_get_extract(D, voxel_cloud, points, normals, colors));
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_get_units(int id, std::vector<int32_t> *keys)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    tsdf_device_get_units(D, keys);
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *weight, float *color)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(stream_));
+    const hipError_t e = tsdf_device_get_volume(D, unit, tsdf, weight, color);
+    if (e == hipErrorInvalidValue) { (void)hipGetLastError(); err_ = "no unit with that index"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(e);
+    return VISMA_ICP_OK;
+}
+
+// the camera pose is the extrinsic's inverse, by cofactors in f64 on the host (what Eigen's fixed-size inverse() evaluates)
+int HipEngine::point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n)
+{
+    int rc = tsdf_enter(0, nullptr);
+    if (rc) return rc;
+    const Mat4 E = Mat4::from(f.extrinsic);
+    bool identity = true;
+    const Mat4 I = Mat4::identity();
+    for (int i = 0; i < 16; i++) identity = identity && E.m[i] == I.m[i];
+    const Mat4 pose = identity ? I : inverse4(E);
+    HIP_TRY(point_cloud_from_depth_device(f, pose.m, color_type, stride, points, colors, n, stream_));
+    return VISMA_ICP_OK;
+}
+
 // K R K^-1 and K t of ComputeCorrespondence in f64 on the host; K = [fx 0 cx; 0 fy cy; 0 0 1] of the level, its inverse
 // written out
 int HipEngine::odometry_launch_correspondences(int level, const Mat4 &T)

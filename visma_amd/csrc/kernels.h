@@ -646,6 +646,51 @@ struct OdometryArgs : PairPassArgs {
 };
 hipError_t launch_odometry_reduce(const OdometryArgs &a, hipStream_t stream);
 
+// ---- TSDF integration (tsdf.hip): a uniform volume, or the units of a scalable one, resident on the device ----
+constexpr int kTsdfColorNone = 0, kTsdfColorRgb8 = 1, kTsdfColorGray32 = 2;   // = VISMA_ICP_TSDF_COLOR_*
+struct TsdfConfig {
+    int resolution = 0;
+    double length = 0.0, sdf_trunc = 0.0;
+    int color_type = kTsdfColorNone;
+    double origin[3] = {0.0, 0.0, 0.0};
+    // a scalable volume (ScalableTSDFVolume): resolution and length are a UNIT's (length = voxel_length * resolution, so
+    // that a unit's own voxel length is length / resolution as the reference's OpenVolumeUnit makes it); origin is unused
+    int scalable = 0;
+    double voxel_length = 0.0;
+    int stride = 4;                                    // depth_sampling_stride
+    int initial_units = 0;                             // the pool's first capacity (it doubles when it is full)
+};
+// one frame (host arrays): depth w x h fp32; color w x h x 3 uint8 (RGB8), w x h fp32 (Gray32) or NULL; extrinsic row-major
+struct TsdfFrame {
+    int w = 0, h = 0;
+    const float *depth = nullptr;
+    const void *color = nullptr;
+    double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
+    double extrinsic[16] = {};
+};
+struct TsdfDevice;                                     // the volume, the last frame and the last extraction on the device
+// allocates the zero-filled volume; nothing is left allocated where it fails
+hipError_t tsdf_device_create(const TsdfConfig &cfg, hipStream_t stream, TsdfDevice **out);
+void tsdf_device_destroy(TsdfDevice *D);
+hipError_t tsdf_device_reset(TsdfDevice *D);
+// Integrate; pose = extrinsic^-1 (row-major, inverted by the caller in f64; read by a scalable volume only).  Returns with
+// the stream idle (the frame is the caller's pageable memory).  A scalable volume opens every touched unit first; where the
+// pool cannot grow it returns the error with the volume as it was.
+hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double pose[16]);
+// ExtractPointCloud (voxel_cloud == 0) or ExtractVoxelPointCloud into the device's output buffers: *n rows
+hipError_t tsdf_device_extract(TsdfDevice *D, int voxel_cloud, int64_t *n);
+// the rows of the last extraction of that kind (n x 3 doubles each; normals / colors may be NULL)
+hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *points, double *normals, double *colors);
+// the indices of a scalable volume's units, 3 per unit, in lexicographic order (the order of its extractions)
+void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys);
+// tsdf, weight (R^3) and color (R^3 x 3, interleaved as the reference keeps it) of a uniform volume (unit == NULL) or of
+// the unit with that index (hipErrorInvalidValue: no such unit); each output may be NULL
+hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsdf, float *weight, float *color);
+// CreatePointCloudFromDepthImage / FromRGBDImage: pose = extrinsic^-1 (row-major, inverted by the caller in f64);
+// color_type as above.  points / colors: room for ceil(w / stride) * ceil(h / stride) rows, or NULL (count only).
+hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
+                                         double *colors, int64_t *n, hipStream_t stream);
+
 // ---- the colour side of colored ICP (color_gradient.hip, colored.hip) ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
 inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }

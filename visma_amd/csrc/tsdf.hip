@@ -1,0 +1,969 @@
+// tsdf.hip -- TSDF integration (Open3D's UniformTSDFVolume: Integrate, ExtractPointCloud, ExtractVoxelPointCloud;
+// CreateDepthToCameraDistanceMultiplierFloatImage; CreatePointCloudFromDepthImage / FromRGBDImage) on gfx950.
+//
+// The volume keeps the reference's voxel order x R^2 + y R + z: a COLUMN (x, y) is R contiguous floats.  tsdf and weight are
+// one array each; colour is kept in planes (three for RGB8; ONE for Gray32, whose three channels undergo the same
+// operations on the same values and are equal bit for bit) and interleaved by the getter.
+//
+//  multiplier   sqrtf(xx^2 + yy^2 + 1), xx = ((float)j - (float)cx) * (1.0f / (float)fx): built once per intrinsic and kept.
+//  integrate    one lane per column, neighbouring lanes on neighbouring columns (a wave covers 64 R contiguous floats; at
+//               R = 16 that is 4 KiB, and a lane's column is four 16-byte vectors).  The lane forms the camera-space point
+//               of its column at z = 0 and advances it by fp32 additions of extrinsic_f(:, 2) * voxel_length_f: that
+//               serial chain is the reference's arithmetic and is kept.  It walks z in 16-byte vectors -- scalar steps
+//               up to the first 16-byte boundary of its column (R odd: columns are not aligned) and behind the last
+//               whole vector -- and stores a vector only where a voxel of it changed: a frame changes the voxels in its
+//               frustum within the truncation band, the rest of the volume is read once and not written.  Every voxel has
+//               one writer; there are no atomics.  Everything is fp32, contraction off (the build's -ffp-contract=off),
+//               `/` and sqrtf correctly rounded (hipcc's default).
+//  extract      count, scan, write over tiles of 256 consecutive voxels (the same three kernels, instantiated for the
+//               surface points -- up to three per voxel, one per axis -- and for the voxel cloud): a tile's count, an
+//               exclusive scan of the tile counts by one workgroup, then every tile scans its voxels' counts in LDS and
+//               writes its rows at its offset.  The output order is the voxel order, then the axis: x, y, z, axis
+//               lexicographic, the reference's.  Points, normals and colours are computed in the write pass, in f64 with
+//               the fp32 weights promoted as the reference promotes them.
+//  from depth   the same three kernels over the strided pixels in row-major order.
+//  scalable     ScalableTSDFVolume: units of R^3 voxels in a pool of slots (tsdf, weight, colour planes of capacity x R^3).
+//               touched_kernel finds the unit boxes of a frame's strided pixels in f64, the host removes duplicates and
+//               opens every new unit (the pool grows by allocate, copy, free; slots never move) BEFORE the integrate kernel
+//               runs over the list of touched units -- the same kernel, a uniform volume being a list of one.  Extraction
+//               walks the units in lexicographic order of their index and reads a +1 neighbour or a corner of GetTSDFAt in
+//               the unit next door through a sorted key array (UnitList::find); a missing unit reads weight 0, tsdf 0.
+// (Reasoning: DESIGN.md 4.4c11.)
+#include "kernels.h"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <array>
+#include <map>
+#include <set>
+#include <vector>
+
+namespace visma {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 2048;                         // memory-bound passes: the grid is capped and strides
+constexpr int kScanThreads = 1024;
+
+inline unsigned capped_blocks(long long n) { return (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, kMaxBlocks); }
+
+__global__ __launch_bounds__(kThreads) void multiplier_kernel(float *out, int w, int h, float cx, float cy, float inv_fx, float inv_fy)
+{
+    const long long n = (long long)w * h;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        const int y = (int)(i / w), x = (int)(i - (long long)y * w);
+        const float xx = ((float)x - cx) * inv_fx, yy = ((float)y - cy) * inv_fy;
+        out[i] = sqrtf(xx * xx + yy * yy + 1.0f);
+    }
+}
+
+// a uniform volume, or one unit of a scalable one: where its R^3 voxels start in the arrays (slot * R^3) and its origin
+struct TsdfUnit { int slot; float ox, oy, oz; };
+
+struct IntegrateArgs {
+    float *tsdf, *weight, *c0, *c1, *c2;                 // slots x R^3 each; c1, c2 only for RGB8
+    const TsdfUnit *units;                               // the units this frame integrates into
+    int n_units;
+    int R;
+    const float *depth, *mult, *gray;
+    const uint8_t *rgb;
+    int w, h;
+    float fx, fy, cx, cy;
+    float e[12];                                         // extrinsic_f, rows 0 .. 2
+    float es[3];                                         // extrinsic_f(:, 2) * voxel_length_f
+    float vl, half, trunc, trunc_inv, safe_w, safe_h;
+};
+
+// one voxel: the reference's loop body.  Returns whether the voxel was integrated.
+template <int CT>
+__device__ inline bool integrate_voxel(const IntegrateArgs &a, float px, float py, float pz, float &t, float &wt, float &c0, float &c1, float &c2)
+{
+    if (!(pz > 0.0f)) return false;
+    const float u_f = px * a.fx / pz + a.cx + 0.5f;
+    const float v_f = py * a.fy / pz + a.cy + 0.5f;
+    if (!(u_f >= 0.0001f && u_f < a.safe_w && v_f >= 0.0001f && v_f < a.safe_h)) return false;
+    const int u = (int)u_f, v = (int)v_f;
+    const long long at = (long long)v * a.w + u;
+    const float d = a.depth[at];
+    if (!(d > 0.0f)) return false;
+    const float sdf = (d - pz) * a.mult[at];
+    if (!(sdf > -a.trunc)) return false;
+    const float s = sdf * a.trunc_inv;
+    const float ts = s < 1.0f ? s : 1.0f;                // std::min(1.0f, s)
+    const float w1 = wt + 1.0f;
+    t = (t * wt + ts) / w1;
+    if (CT == kTsdfColorRgb8) {
+        const uint8_t *rgb = a.rgb + 3 * at;
+        c0 = (c0 * wt + (float)rgb[0]) / w1;
+        c1 = (c1 * wt + (float)rgb[1]) / w1;
+        c2 = (c2 * wt + (float)rgb[2]) / w1;
+    } else if (CT == kTsdfColorGray32) {
+        c0 = (c0 * wt + a.gray[at]) / w1;
+    }
+    wt = w1;
+    return true;
+}
+
+template <int CT>
+__global__ __launch_bounds__(kThreads) void integrate_kernel(IntegrateArgs a)
+{
+    const int R = a.R;
+    const long long columns = (long long)R * R, items = columns * a.n_units;
+    for (long long item = (long long)blockIdx.x * kThreads + threadIdx.x; item < items; item += (long long)gridDim.x * kThreads) {
+        const TsdfUnit unit = a.units[item / columns];
+        const long long col = item % columns;
+        const int x = (int)(col / R), y = (int)(col - (long long)x * R);
+        const float X = a.half + a.vl * (float)x + unit.ox, Y = a.half + a.vl * (float)y + unit.oy, Z = a.half + unit.oz;
+        float px = a.e[0] * X + a.e[1] * Y + a.e[2] * Z + a.e[3];
+        float py = a.e[4] * X + a.e[5] * Y + a.e[6] * Z + a.e[7];
+        float pz = a.e[8] * X + a.e[9] * Y + a.e[10] * Z + a.e[11];
+        const long long base = ((long long)unit.slot * columns + col) * R;   // the column's first voxel; the arrays are 16-byte aligned
+        int z = 0;
+        const int head = std::min(R, (int)((4 - (base & 3)) & 3));
+        auto scalar_steps = [&](int end) {
+            for (; z < end; z++) {
+                const long long i = base + z;
+                float t = a.tsdf[i], wt = a.weight[i], c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;
+                if (CT != kTsdfColorNone) c0 = a.c0[i];
+                if (CT == kTsdfColorRgb8) { c1 = a.c1[i]; c2 = a.c2[i]; }
+                if (integrate_voxel<CT>(a, px, py, pz, t, wt, c0, c1, c2)) {
+                    a.tsdf[i] = t; a.weight[i] = wt;
+                    if (CT != kTsdfColorNone) a.c0[i] = c0;
+                    if (CT == kTsdfColorRgb8) { a.c1[i] = c1; a.c2[i] = c2; }
+                }
+                px += a.es[0]; py += a.es[1]; pz += a.es[2];
+            }
+        };
+        scalar_steps(head);
+        for (; z + 4 <= R; z += 4) {
+            const long long i = base + z;                // a multiple of 4
+            float4 t = *reinterpret_cast<const float4 *>(a.tsdf + i), wt = *reinterpret_cast<const float4 *>(a.weight + i);
+            float4 c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0}, c2 = {0, 0, 0, 0};
+            if (CT != kTsdfColorNone) c0 = *reinterpret_cast<const float4 *>(a.c0 + i);
+            if (CT == kTsdfColorRgb8) { c1 = *reinterpret_cast<const float4 *>(a.c1 + i); c2 = *reinterpret_cast<const float4 *>(a.c2 + i); }
+            bool any = integrate_voxel<CT>(a, px, py, pz, t.x, wt.x, c0.x, c1.x, c2.x);
+            px += a.es[0]; py += a.es[1]; pz += a.es[2];
+            any |= integrate_voxel<CT>(a, px, py, pz, t.y, wt.y, c0.y, c1.y, c2.y);
+            px += a.es[0]; py += a.es[1]; pz += a.es[2];
+            any |= integrate_voxel<CT>(a, px, py, pz, t.z, wt.z, c0.z, c1.z, c2.z);
+            px += a.es[0]; py += a.es[1]; pz += a.es[2];
+            any |= integrate_voxel<CT>(a, px, py, pz, t.w, wt.w, c0.w, c1.w, c2.w);
+            px += a.es[0]; py += a.es[1]; pz += a.es[2];
+            if (any) {
+                *reinterpret_cast<float4 *>(a.tsdf + i) = t; *reinterpret_cast<float4 *>(a.weight + i) = wt;
+                if (CT != kTsdfColorNone) *reinterpret_cast<float4 *>(a.c0 + i) = c0;
+                if (CT == kTsdfColorRgb8) { *reinterpret_cast<float4 *>(a.c1 + i) = c1; *reinterpret_cast<float4 *>(a.c2 + i) = c2; }
+            }
+        }
+        scalar_steps(R);
+    }
+}
+
+// ---- count, scan, write: an ordered compaction over n items in tiles of kThreads ----
+// A Source has  __device__ int count(long long i) const  (rows item i emits) and
+//               __device__ void emit(long long i, long long row) const  (writes them at row, row + 1, ...).
+template <class Source>
+__global__ __launch_bounds__(kThreads) void count_kernel(Source s, long long n, long long tiles, int *tile_count)
+{
+    __shared__ int wave_sum[kThreads / 64];
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long i = tile * kThreads + threadIdx.x;
+        int c = i < n ? s.count(i) : 0;
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = 0;
+            for (int k = 0; k < kThreads / 64; k++) t += wave_sum[k];
+            tile_count[tile] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// exclusive scan of tile_count[0 .. tiles) into tile_offset, the total into *total: ONE workgroup, chunk by chunk with a carry
+__global__ __launch_bounds__(kScanThreads) void scan_kernel(const int *tile_count, long long tiles, long long *tile_offset, long long *total)
+{
+    __shared__ long long buf[kScanThreads];
+    __shared__ long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (long long at = 0; at < tiles; at += kScanThreads) {
+        const long long i = at + threadIdx.x;
+        const long long v = i < tiles ? (long long)tile_count[i] : 0;
+        buf[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 1; o < kScanThreads; o <<= 1) {                     // Hillis-Steele, inclusive
+            const long long add = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
+            __syncthreads();
+            buf[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < tiles) tile_offset[i] = carry + buf[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == kScanThreads - 1) carry += buf[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+template <class Source>
+__global__ __launch_bounds__(kThreads) void write_kernel(Source s, long long n, long long tiles, const long long *tile_offset)
+{
+    __shared__ int buf[kThreads];
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long i = tile * kThreads + threadIdx.x;
+        const int c = i < n ? s.count(i) : 0;
+        buf[threadIdx.x] = c;
+        __syncthreads();
+        for (int o = 1; o < kThreads; o <<= 1) {
+            const int add = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
+            __syncthreads();
+            buf[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (c > 0) s.emit(i, tile_offset[tile] + (long long)(buf[threadIdx.x] - c));
+        __syncthreads();
+    }
+}
+
+// what the compaction works in: grow-only
+struct Compactor {
+    int *tile_count = nullptr;
+    long long *tile_offset = nullptr, *total = nullptr;
+    long long capacity = 0;
+    hipError_t ensure(long long tiles)
+    {
+        if (!total) { hipError_t e = hipMalloc(&total, sizeof(long long)); if (e != hipSuccess) return e; }
+        if (tiles <= capacity) return hipSuccess;
+        if (tile_count) (void)hipFree(tile_count);
+        if (tile_offset) (void)hipFree(tile_offset);
+        tile_count = nullptr; tile_offset = nullptr; capacity = 0;
+        hipError_t e = hipMalloc(&tile_count, sizeof(int) * (size_t)tiles);
+        if (e != hipSuccess) return e;
+        e = hipMalloc(&tile_offset, sizeof(long long) * (size_t)tiles);
+        if (e != hipSuccess) return e;
+        capacity = tiles;
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (tile_count) (void)hipFree(tile_count);
+        if (tile_offset) (void)hipFree(tile_offset);
+        if (total) (void)hipFree(total);
+        tile_count = nullptr; tile_offset = nullptr; total = nullptr; capacity = 0;
+    }
+    // the count pass and the scan; *rows on the host (one wait)
+    template <class Source>
+    hipError_t count(const Source &s, long long n, hipStream_t stream, long long *rows)
+    {
+        *rows = 0;
+        if (n <= 0) return hipSuccess;                   // nothing is launched over nothing
+        const long long tiles = (n + kThreads - 1) / kThreads;
+        hipError_t e = ensure(tiles);
+        if (e != hipSuccess) return e;
+        count_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_count);
+        scan_kernel<<<1, kScanThreads, 0, stream>>>(tile_count, tiles, tile_offset, total);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(rows, total, sizeof(long long), hipMemcpyDeviceToHost, stream);
+        if (e != hipSuccess) return e;
+        return hipStreamSynchronize(stream);
+    }
+    // ... and the write pass behind it (the Source now holds its output pointers)
+    template <class Source>
+    hipError_t write(const Source &s, long long n, hipStream_t stream)
+    {
+        if (n <= 0) return hipSuccess;
+        const long long tiles = (n + kThreads - 1) / kThreads;
+        write_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_offset);
+        return hipGetLastError();
+    }
+};
+
+__device__ inline bool voxel_valid(float w, float f) { return w != 0.0f && f < 0.98f && f >= -0.98f; }
+
+// The units of an extraction in ITS order (a uniform volume: one; a scalable one: lexicographic by index), on the device:
+// keys 3 ints per unit (the index), slots, origins 3 doubles per unit (index * unit length, formed on the host in f64)
+struct UnitList {
+    const int *keys, *slots;
+    const double *origins;
+    int n;
+    // the position of unit (kx, ky, kz) in the sorted keys, or -1: the index -> slot map of the neighbour lookups
+    __device__ int find(int kx, int ky, int kz) const
+    {
+        int lo = 0, hi = n - 1;
+        while (lo <= hi) {
+            const int mid = (lo + hi) >> 1;
+            const int *k = keys + 3 * mid;
+            const int c = k[0] != kx ? (k[0] < kx ? -1 : 1) : k[1] != ky ? (k[1] < ky ? -1 : 1) : k[2] != kz ? (k[2] < kz ? -1 : 1) : 0;
+            if (c == 0) return mid;
+            if (c < 0) lo = mid + 1; else hi = mid - 1;
+        }
+        return -1;
+    }
+};
+
+// UniformTSDFVolume::ExtractVoxelPointCloud of every unit: item = (unit in list order, voxel)
+struct VoxelCloudSource {
+    const float *tsdf, *weight;
+    const double *zs;                                    // half + k additions of voxel_length, k = 0 .. R - 1 (formed on the host)
+    UnitList units;
+    int R;
+    double vl, half;                                     // the unit's own voxel length
+    double *points, *colors;
+    __device__ long long voxel(long long i) const { const long long R3 = (long long)R * R * R; return units.slots[i / R3] * R3 + i % R3; }
+    __device__ int count(long long i) const { const long long v = voxel(i); return voxel_valid(weight[v], tsdf[v]) ? 1 : 0; }
+    __device__ void emit(long long item, long long row) const
+    {
+        const long long R3 = (long long)R * R * R, i = item % R3;
+        const double *o = units.origins + 3 * (item / R3);
+        const double ox = o[0], oy = o[1], oz = o[2];
+        const long long v = voxel(item);
+        const int z = (int)(i % R), y = (int)((i / R) % R), x = (int)(i / ((long long)R * R));
+        points[3 * row] = half + vl * x + ox;
+        points[3 * row + 1] = half + vl * y + oy;
+        points[3 * row + 2] = zs[z] + oz;
+        const double c = ((double)tsdf[v] + 1.0) * 0.5;
+        colors[3 * row] = c; colors[3 * row + 1] = c; colors[3 * row + 2] = c;
+    }
+};
+
+// UniformTSDFVolume::ExtractPointCloud: item = voxel, up to three rows (one per axis)
+struct SurfaceSource {
+    const float *tsdf, *weight, *c0, *c1, *c2;
+    int R, color_type;
+    double vl, half, ox, oy, oz;
+    double *points, *normals, *colors;
+
+    __device__ long long stride(int axis) const { return axis == 0 ? (long long)R * R : axis == 1 ? R : 1; }
+    // bit `axis` set: the edge from voxel i to its +1 neighbour along `axis` carries a point
+    __device__ int mask(long long i) const
+    {
+        const int z = (int)(i % R), y = (int)((i / R) % R), x = (int)(i / ((long long)R * R));
+        if (x < 1 || y < 1 || z < 1 || x > R - 2 || y > R - 2 || z > R - 2) return 0;
+        const float f0 = tsdf[i];
+        if (!voxel_valid(weight[i], f0)) return 0;
+        const int at[3] = {x, y, z};
+        int m = 0;
+        for (int a = 0; a < 3; a++) {
+            if (at[a] + 1 >= R - 1) continue;
+            const long long j = i + stride(a);
+            const float f1 = tsdf[j];
+            if (voxel_valid(weight[j], f1) && f0 * f1 < 0.0f) m |= 1 << a;
+        }
+        return m;
+    }
+    __device__ int count(long long i) const { return __popc((unsigned)mask(i)); }
+
+    // UniformTSDFVolume::GetTSDFAt (indices clamped into the volume: an extracted point never leaves it)
+    __device__ double tsdf_at(double px, double py, double pz) const
+    {
+        const double gx = px / vl - 0.5, gy = py / vl - 0.5, gz = pz / vl - 0.5;
+        const double fx = floor(gx), fy = floor(gy), fz = floor(gz);
+        const double r0 = gx - fx, r1 = gy - fy, r2 = gz - fz;
+        auto clampi = [this](double f) { const int v = (int)f; return v < 0 ? 0 : v > R - 2 ? R - 2 : v; };
+        const int x = clampi(fx), y = clampi(fy), z = clampi(fz);
+        const float *t = tsdf + ((long long)x * R + y) * R + z;
+        const long long sx = (long long)R * R, sy = R;
+        return (1 - r0) * ((1 - r1) * ((1 - r2) * t[0] + r2 * t[1]) + r1 * ((1 - r2) * t[sy] + r2 * t[sy + 1])) +
+               r0 * ((1 - r1) * ((1 - r2) * t[sx] + r2 * t[sx + 1]) + r1 * ((1 - r2) * t[sx + sy] + r2 * t[sx + sy + 1]));
+    }
+
+    __device__ void emit(long long i, long long row) const
+    {
+        const int z = (int)(i % R), y = (int)((i / R) % R), x = (int)(i / ((long long)R * R));
+        const int m = mask(i);
+        const float f0 = tsdf[i];
+        const double p0[3] = {half + vl * x, half + vl * y, half + vl * z};
+        const double gap = 0.99 * vl;
+        for (int a = 0; a < 3; a++) {
+            if (!(m & (1 << a))) continue;
+            const long long j = i + stride(a);
+            const float f1 = tsdf[j];
+            const float r0 = fabsf(f0), r1 = fabsf(f1);
+            const float rs = r0 + r1;
+            double p[3] = {p0[0], p0[1], p0[2]};
+            const double p1 = p0[a] + vl;
+            p[a] = (p0[a] * r1 + p1 * r0) / rs;
+            points[3 * row] = p[0] + ox; points[3 * row + 1] = p[1] + oy; points[3 * row + 2] = p[2] + oz;
+            if (color_type == kTsdfColorRgb8) {
+                colors[3 * row] = (double)((c0[i] * r1 + c0[j] * r0) / rs / 255.0f);
+                colors[3 * row + 1] = (double)((c1[i] * r1 + c1[j] * r0) / rs / 255.0f);
+                colors[3 * row + 2] = (double)((c2[i] * r1 + c2[j] * r0) / rs / 255.0f);
+            } else if (color_type == kTsdfColorGray32) {
+                const double g = (double)((c0[i] * r1 + c0[j] * r0) / rs);
+                colors[3 * row] = g; colors[3 * row + 1] = g; colors[3 * row + 2] = g;
+            }
+            // GetNormalAt
+            double n[3];
+            for (int k = 0; k < 3; k++) {
+                double lo[3] = {p[0], p[1], p[2]}, hi[3] = {p[0], p[1], p[2]};
+                lo[k] -= gap; hi[k] += gap;
+                n[k] = tsdf_at(hi[0], hi[1], hi[2]) - tsdf_at(lo[0], lo[1], lo[2]);
+            }
+            const double zz = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];       // Eigen's normalized(): (x^2 + y^2) + z^2
+            if (zz > 0.0) { const double s = sqrt(zz); n[0] /= s; n[1] /= s; n[2] /= s; }
+            normals[3 * row] = n[0]; normals[3 * row + 1] = n[1]; normals[3 * row + 2] = n[2];
+            row++;
+        }
+    }
+};
+
+// ScalableTSDFVolume::ExtractPointCloud: item = (unit in lexicographic order, voxel), up to three rows.  A +1 neighbour or
+// a corner of GetTSDFAt beyond the unit is looked up in the unit next door; a missing unit reads weight 0, tsdf 0.
+struct ScalableSurfaceSource {
+    const float *tsdf, *weight, *c0, *c1, *c2;
+    UnitList units;
+    int R, color_type;
+    double vl, half, ul;                                 // the volume's voxel length, half of it, the unit length
+    double *points, *normals, *colors;
+
+    // the memory position of voxel (x, y, z) of the unit at list position u, each coordinate in [0, 2 R): beyond R - 1 it is
+    // the neighbouring unit's; -1 where that unit does not exist
+    __device__ long long at(int u, int x, int y, int z) const
+    {
+        const long long R3 = (long long)R * R * R;
+        int slot = units.slots[u];
+        if (x >= R || y >= R || z >= R) {
+            const int *k = units.keys + 3 * u;
+            const int v = units.find(k[0] + (x >= R), k[1] + (y >= R), k[2] + (z >= R));
+            if (v < 0) return -1;
+            slot = units.slots[v];
+            if (x >= R) x -= R;
+            if (y >= R) y -= R;
+            if (z >= R) z -= R;
+        }
+        return slot * R3 + ((long long)x * R + y) * R + z;
+    }
+    __device__ int mask(long long item) const
+    {
+        const long long R3 = (long long)R * R * R, i = item % R3;
+        const int u = (int)(item / R3);
+        const int z = (int)(i % R), y = (int)((i / R) % R), x = (int)(i / ((long long)R * R));
+        const long long v0 = at(u, x, y, z);
+        const float f0 = tsdf[v0];
+        if (!voxel_valid(weight[v0], f0)) return 0;
+        int m = 0;
+        for (int a = 0; a < 3; a++) {
+            const long long v1 = at(u, x + (a == 0), y + (a == 1), z + (a == 2));
+            if (v1 < 0) continue;
+            const float f1 = tsdf[v1];
+            if (voxel_valid(weight[v1], f1) && f0 * f1 < 0.0f) m |= 1 << a;
+        }
+        return m;
+    }
+    __device__ int count(long long item) const { return __popc((unsigned)mask(item)); }
+
+    // ScalableTSDFVolume::GetTSDFAt
+    __device__ double tsdf_at(double px, double py, double pz) const
+    {
+        const double lx = px - 0.5 * vl, ly = py - 0.5 * vl, lz = pz - 0.5 * vl;
+        const double ux = floor(lx / ul), uy = floor(ly / ul), uz = floor(lz / ul);
+        const int u = units.find((int)ux, (int)uy, (int)uz);
+        if (u < 0) return 0.0;
+        const double gx = (lx - ux * ul) / vl, gy = (ly - uy * ul) / vl, gz = (lz - uz * ul) / vl;
+        auto clampi = [this](double f) { const int v = (int)floor(f); return v < 0 ? 0 : v > R - 1 ? R - 1 : v; };
+        const int x = clampi(gx), y = clampi(gy), z = clampi(gz);
+        const double r0 = gx - x, r1 = gy - y, r2 = gz - z;
+        float f[2][2][2];
+        for (int a = 0; a < 2; a++)
+            for (int b = 0; b < 2; b++)
+                for (int c = 0; c < 2; c++) {
+                    const long long v = at(u, x + a, y + b, z + c);
+                    f[a][b][c] = v < 0 ? 0.0f : tsdf[v];
+                }
+        return (1 - r0) * ((1 - r1) * ((1 - r2) * f[0][0][0] + r2 * f[0][0][1]) + r1 * ((1 - r2) * f[0][1][0] + r2 * f[0][1][1])) +
+               r0 * ((1 - r1) * ((1 - r2) * f[1][0][0] + r2 * f[1][0][1]) + r1 * ((1 - r2) * f[1][1][0] + r2 * f[1][1][1]));
+    }
+
+    __device__ void emit(long long item, long long row) const
+    {
+        const long long R3 = (long long)R * R * R, i = item % R3;
+        const int u = (int)(item / R3);
+        const int z = (int)(i % R), y = (int)((i / R) % R), x = (int)(i / ((long long)R * R));
+        const int *k = units.keys + 3 * u;
+        const int m = mask(item);
+        const long long v0 = at(u, x, y, z);
+        const float f0 = tsdf[v0];
+        const double p0[3] = {half + vl * x + (double)k[0] * ul, half + vl * y + (double)k[1] * ul, half + vl * z + (double)k[2] * ul};
+        const double gap = 0.99 * vl;
+        for (int a = 0; a < 3; a++) {
+            if (!(m & (1 << a))) continue;
+            const long long v1 = at(u, x + (a == 0), y + (a == 1), z + (a == 2));
+            const float f1 = tsdf[v1];
+            const float r0 = fabsf(f0), r1 = fabsf(f1);
+            const float rs = r0 + r1;
+            double p[3] = {p0[0], p0[1], p0[2]};
+            const double p1 = p0[a] + vl;
+            p[a] = (p0[a] * r1 + p1 * r0) / rs;
+            points[3 * row] = p[0]; points[3 * row + 1] = p[1]; points[3 * row + 2] = p[2];
+            if (color_type == kTsdfColorRgb8) {
+                colors[3 * row] = (double)((c0[v0] * r1 + c0[v1] * r0) / rs / 255.0f);
+                colors[3 * row + 1] = (double)((c1[v0] * r1 + c1[v1] * r0) / rs / 255.0f);
+                colors[3 * row + 2] = (double)((c2[v0] * r1 + c2[v1] * r0) / rs / 255.0f);
+            } else if (color_type == kTsdfColorGray32) {
+                const double g = (double)((c0[v0] * r1 + c0[v1] * r0) / rs);
+                colors[3 * row] = g; colors[3 * row + 1] = g; colors[3 * row + 2] = g;
+            }
+            double n[3];
+            for (int q = 0; q < 3; q++) {
+                double lo[3] = {p[0], p[1], p[2]}, hi[3] = {p[0], p[1], p[2]};
+                lo[q] -= gap; hi[q] += gap;
+                n[q] = tsdf_at(hi[0], hi[1], hi[2]) - tsdf_at(lo[0], lo[1], lo[2]);
+            }
+            const double zz = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+            if (zz > 0.0) { const double sq = sqrt(zz); n[0] /= sq; n[1] /= sq; n[2] /= sq; }
+            normals[3 * row] = n[0]; normals[3 * row + 1] = n[1]; normals[3 * row + 2] = n[2];
+            row++;
+        }
+    }
+};
+
+// CreatePointCloudFromFloatDepthImage / CreatePointCloudFromRGBDImageT: item = strided pixel, row-major
+struct DepthSource {
+    const float *depth, *gray;
+    const uint8_t *rgb;
+    int w, sw, stride, color_type;                       // sw: strided pixels per row
+    double fx, fy, cx, cy;
+    double pose[12];
+    double *points, *colors;
+    __device__ long long pixel(long long i) const { return (i / sw) * stride * (long long)w + (i % sw) * stride; }
+    __device__ int count(long long i) const { return depth[pixel(i)] > 0.0f ? 1 : 0; }
+    __device__ void point(long long i, double p[3]) const
+    {
+        const long long at = pixel(i);
+        const int v = (int)(at / w), u = (int)(at % w);
+        const double z = (double)depth[at];
+        const double x = (u - cx) * z / fx, y = (v - cy) * z / fy;
+        for (int r = 0; r < 3; r++) p[r] = pose[4 * r] * x + pose[4 * r + 1] * y + pose[4 * r + 2] * z + pose[4 * r + 3];
+    }
+    __device__ void emit(long long i, long long row) const
+    {
+        const long long at = pixel(i);
+        point(i, points + 3 * row);
+        if (color_type == kTsdfColorRgb8) {
+            for (int c = 0; c < 3; c++) colors[3 * row + c] = (double)rgb[3 * at + c] / 255.0;
+        } else if (color_type == kTsdfColorGray32) {
+            const double g = (double)gray[at];
+            colors[3 * row] = g; colors[3 * row + 1] = g; colors[3 * row + 2] = g;
+        }
+    }
+};
+
+// ScalableTSDFVolume::Integrate's touched units: per strided pixel with a depth, LocateVolumeUnit(point - sdf_trunc) and
+// LocateVolumeUnit(point + sdf_trunc) in f64 -- six ints, the first INT_MIN where the pixel has no depth.  The host
+// expands the boxes into unit keys and removes the duplicates.
+__global__ __launch_bounds__(kThreads) void touched_kernel(DepthSource s, long long n, double trunc, double ul, int *bounds)
+{
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        int *b = bounds + 6 * i;
+        if (!s.count(i)) { b[0] = INT_MIN; continue; }
+        double p[3];
+        s.point(i, p);
+        for (int a = 0; a < 3; a++) {
+            b[a] = (int)floor((p[a] - trunc) / ul);
+            b[3 + a] = (int)floor((p[a] + trunc) / ul);
+        }
+    }
+}
+
+template <class T>
+hipError_t grow(T **p, size_t *have, size_t want)
+{
+    if (want <= *have && *p) return hipSuccess;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr; *have = 0;
+    hipError_t e = hipMalloc(p, sizeof(T) * std::max<size_t>(want, 1));
+    if (e == hipSuccess) *have = std::max<size_t>(want, 1);
+    return e;
+}
+
+#define TSDF_TRY(expr)                                   \
+    do {                                                 \
+        hipError_t e_ = (expr);                          \
+        if (e_ != hipSuccess) return e_;                 \
+    } while (0)
+
+}  // namespace
+
+struct TsdfDevice {
+    TsdfConfig cfg;
+    hipStream_t stream = nullptr;
+    size_t R3 = 0;                                       // voxels of a unit
+    size_t capacity = 0;                                 // units the pool holds (a uniform volume: one)
+    float *tsdf = nullptr, *weight = nullptr, *color[3] = {nullptr, nullptr, nullptr};   // capacity x R3 each
+    double *zs = nullptr;
+    // unit index -> slot, in lexicographic order of the index; slots are handed out in opening order and never move
+    std::map<std::array<int, 3>, int> slot_of;
+    // the last frame: depth, colour, the multiplier image of the last intrinsic, the touched boxes, the unit list
+    float *depth = nullptr, *gray = nullptr, *mult = nullptr;
+    uint8_t *rgb = nullptr;
+    int *bounds = nullptr;
+    TsdfUnit *unit_list = nullptr;
+    size_t depth_cap = 0, gray_cap = 0, rgb_cap = 0, mult_cap = 0, bounds_cap = 0, unit_list_cap = 0;
+    int mult_w = 0, mult_h = 0;
+    double mult_k[4] = {0, 0, 0, 0};
+    Compactor comp;
+    // an extraction's unit list on the device
+    int *x_keys = nullptr, *x_slots = nullptr;
+    double *x_origins = nullptr;
+    size_t x_keys_cap = 0, x_slots_cap = 0, x_origins_cap = 0;
+    // the last extractions: [0] surface points, [1] voxel cloud
+    double *out_points[2] = {nullptr, nullptr}, *out_normals = nullptr, *out_colors[2] = {nullptr, nullptr};
+    size_t out_points_cap[2] = {0, 0}, out_normals_cap = 0, out_colors_cap[2] = {0, 0};
+    long long rows[2] = {-1, -1};
+    int planes() const { return cfg.color_type == kTsdfColorRgb8 ? 3 : cfg.color_type == kTsdfColorGray32 ? 1 : 0; }
+    double unit_length() const { return cfg.length; }
+    double unit_voxel_length() const { return cfg.length / (double)cfg.resolution; }
+};
+
+namespace {
+
+// the pool at `units` units: new arrays, the old contents copied, the rest zero; the old arrays are freed only when every
+// new one exists -- a failed allocation leaves the volume as it was
+hipError_t pool_resize(TsdfDevice *D, size_t units)
+{
+    float *fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float **old[5] = {&D->tsdf, &D->weight, &D->color[0], &D->color[1], &D->color[2]};
+    const int arrays = 2 + D->planes();
+    const size_t bytes = sizeof(float) * D->R3 * units, keep = sizeof(float) * D->R3 * std::min(units, D->capacity);
+    hipError_t e = hipSuccess;
+    for (int a = 0; a < arrays && e == hipSuccess; a++) e = hipMalloc(&fresh[a], bytes);
+    for (int a = 0; a < arrays && e == hipSuccess; a++) {
+        e = hipMemsetAsync(fresh[a], 0, bytes, D->stream);
+        if (e == hipSuccess && keep && *old[a]) e = hipMemcpyAsync(fresh[a], *old[a], keep, hipMemcpyDeviceToDevice, D->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
+    if (e != hipSuccess) {
+        for (float *f : fresh)
+            if (f) (void)hipFree(f);
+        (void)hipGetLastError();
+        return e;
+    }
+    for (int a = 0; a < arrays; a++) {
+        if (*old[a]) (void)hipFree(*old[a]);
+        *old[a] = fresh[a];
+    }
+    D->capacity = units;
+    return hipSuccess;
+}
+
+// the units of an extraction, in the map's (lexicographic) order, on the device
+hipError_t upload_unit_list(TsdfDevice *D, UnitList *out)
+{
+    const size_t n = D->cfg.scalable ? D->slot_of.size() : 1;
+    std::vector<int> keys(3 * n, 0), slots(n, 0);
+    std::vector<double> origins(3 * n);
+    if (D->cfg.scalable) {
+        size_t u = 0;
+        for (const auto &kv : D->slot_of) {
+            for (int a = 0; a < 3; a++) { keys[3 * u + a] = kv.first[a]; origins[3 * u + a] = (double)kv.first[a] * D->unit_length(); }
+            slots[u++] = kv.second;
+        }
+    } else {
+        for (int a = 0; a < 3; a++) origins[a] = D->cfg.origin[a];
+    }
+    TSDF_TRY(grow(&D->x_keys, &D->x_keys_cap, 3 * n));
+    TSDF_TRY(grow(&D->x_slots, &D->x_slots_cap, n));
+    TSDF_TRY(grow(&D->x_origins, &D->x_origins_cap, 3 * n));
+    if (n) {
+        TSDF_TRY(hipMemcpyAsync(D->x_keys, keys.data(), sizeof(int) * 3 * n, hipMemcpyHostToDevice, D->stream));
+        TSDF_TRY(hipMemcpyAsync(D->x_slots, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice, D->stream));
+        TSDF_TRY(hipMemcpyAsync(D->x_origins, origins.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, D->stream));
+        TSDF_TRY(hipStreamSynchronize(D->stream));           // (the vectors are this function's)
+    }
+    out->keys = D->x_keys; out->slots = D->x_slots; out->origins = D->x_origins; out->n = (int)n;
+    return hipSuccess;
+}
+
+}  // namespace
+
+void tsdf_device_destroy(TsdfDevice *D)
+{
+    if (!D) return;
+    void *all[] = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], D->zs, D->depth, D->gray, D->mult, D->rgb, D->bounds,
+                   D->unit_list, D->x_keys, D->x_slots, D->x_origins,
+                   D->out_points[0], D->out_points[1], D->out_normals, D->out_colors[0], D->out_colors[1]};
+    for (void *p : all)
+        if (p) (void)hipFree(p);
+    D->comp.release();
+    delete D;
+}
+
+// Reset(): a uniform volume's voxels to zero; a scalable volume forgets its units (a slot is zeroed when it is handed out)
+hipError_t tsdf_device_reset(TsdfDevice *D)
+{
+    D->rows[0] = D->rows[1] = -1;
+    D->slot_of.clear();
+    const size_t bytes = sizeof(float) * D->R3 * D->capacity;
+    TSDF_TRY(hipMemsetAsync(D->tsdf, 0, bytes, D->stream));
+    TSDF_TRY(hipMemsetAsync(D->weight, 0, bytes, D->stream));
+    for (int c = 0; c < D->planes(); c++) TSDF_TRY(hipMemsetAsync(D->color[c], 0, bytes, D->stream));
+    return hipStreamSynchronize(D->stream);
+}
+
+hipError_t tsdf_device_create(const TsdfConfig &cfg, hipStream_t stream, TsdfDevice **out)
+{
+    *out = nullptr;
+    TsdfDevice *D = new TsdfDevice;
+    D->cfg = cfg; D->stream = stream;
+    const int R = cfg.resolution;
+    D->R3 = (size_t)R * R * R;
+    hipError_t e = pool_resize(D, cfg.scalable ? (size_t)std::max(cfg.initial_units, 1) : 1);
+    if (e == hipSuccess) e = hipMalloc(&D->zs, sizeof(double) * (size_t)R);
+    if (e == hipSuccess) {
+        // ExtractVoxelPointCloud's pt(2): half_voxel_length, then += voxel_length_ per voxel, in f64
+        std::vector<double> zs((size_t)R);
+        const double vl = D->unit_voxel_length();
+        double z = vl * 0.5;
+        for (int k = 0; k < R; k++, z += vl) zs[(size_t)k] = z;
+        e = hipMemcpy(D->zs, zs.data(), sizeof(double) * (size_t)R, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { tsdf_device_destroy(D); (void)hipGetLastError(); return e; }
+    *out = D;
+    return hipSuccess;
+}
+
+hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double pose[16])
+{
+    const TsdfConfig &c = D->cfg;
+    const size_t n = (size_t)f.w * f.h;
+    TSDF_TRY(grow(&D->depth, &D->depth_cap, n));
+    TSDF_TRY(hipMemcpyAsync(D->depth, f.depth, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+    if (c.color_type == kTsdfColorRgb8) {
+        TSDF_TRY(grow(&D->rgb, &D->rgb_cap, 3 * n));
+        TSDF_TRY(hipMemcpyAsync(D->rgb, f.color, 3 * n, hipMemcpyHostToDevice, D->stream));
+    } else if (c.color_type == kTsdfColorGray32) {
+        TSDF_TRY(grow(&D->gray, &D->gray_cap, n));
+        TSDF_TRY(hipMemcpyAsync(D->gray, f.color, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+    }
+    // the units of this frame: the one of a uniform volume, or the touched ones, every one of them open before any kernel
+    // of the integration starts
+    std::vector<TsdfUnit> list;
+    if (!c.scalable) {
+        list.push_back({0, (float)c.origin[0], (float)c.origin[1], (float)c.origin[2]});
+    } else {
+        const long long sw = ((long long)f.w - 1) / c.stride + 1, sh = ((long long)f.h - 1) / c.stride + 1, items = sw * sh;
+        DepthSource s;
+        s.depth = D->depth; s.gray = nullptr; s.rgb = nullptr;
+        s.w = f.w; s.sw = (int)sw; s.stride = c.stride; s.color_type = kTsdfColorNone;
+        s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
+        for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
+        s.points = nullptr; s.colors = nullptr;
+        TSDF_TRY(grow(&D->bounds, &D->bounds_cap, 6 * (size_t)items));
+        touched_kernel<<<capped_blocks(items), kThreads, 0, D->stream>>>(s, items, c.sdf_trunc, D->unit_length(), D->bounds);
+        TSDF_TRY(hipGetLastError());
+        std::vector<int> b(6 * (size_t)items);
+        TSDF_TRY(hipMemcpyAsync(b.data(), D->bounds, sizeof(int) * b.size(), hipMemcpyDeviceToHost, D->stream));
+        TSDF_TRY(hipStreamSynchronize(D->stream));
+        std::set<std::array<int, 3>> touched;
+        std::set<std::array<int, 6>> boxes;
+        for (long long i = 0; i < items; i++)
+            if (b[6 * i] != INT_MIN) boxes.insert({b[6 * i], b[6 * i + 1], b[6 * i + 2], b[6 * i + 3], b[6 * i + 4], b[6 * i + 5]});
+        for (const auto &q : boxes)
+            for (int x = q[0]; x <= q[3]; x++)
+                for (int y = q[1]; y <= q[4]; y++)
+                    for (int z = q[2]; z <= q[5]; z++) touched.insert({x, y, z});
+        if (touched.empty()) return hipSuccess;          // nothing is launched with an empty list
+        size_t next = D->slot_of.size();
+        std::vector<std::array<int, 3>> opened;
+        for (const auto &k : touched)
+            if (!D->slot_of.count(k)) opened.push_back(k);
+        const size_t need = next + opened.size();
+        if (need > D->capacity) {
+            const hipError_t e = pool_resize(D, std::max(need, 2 * D->capacity));
+            if (e != hipSuccess) return e;               // (no unit was opened: the volume is as it was)
+        }
+        if (!opened.empty()) {                           // the slots handed out are zeroed: a Reset() leaves old voxels in them
+            const size_t at = D->R3 * next, bytes = sizeof(float) * D->R3 * opened.size();
+            TSDF_TRY(hipMemsetAsync(D->tsdf + at, 0, bytes, D->stream));
+            TSDF_TRY(hipMemsetAsync(D->weight + at, 0, bytes, D->stream));
+            for (int p = 0; p < D->planes(); p++) TSDF_TRY(hipMemsetAsync(D->color[p] + at, 0, bytes, D->stream));
+        }
+        for (const auto &k : opened) D->slot_of[k] = (int)next++;
+        for (const auto &k : touched)
+            list.push_back({D->slot_of[k], (float)((double)k[0] * D->unit_length()), (float)((double)k[1] * D->unit_length()),
+                            (float)((double)k[2] * D->unit_length())});
+    }
+    TSDF_TRY(grow(&D->unit_list, &D->unit_list_cap, list.size()));
+    TSDF_TRY(hipMemcpyAsync(D->unit_list, list.data(), sizeof(TsdfUnit) * list.size(), hipMemcpyHostToDevice, D->stream));
+    const float fx = (float)f.fx, fy = (float)f.fy, cx = (float)f.cx, cy = (float)f.cy;
+    const double k[4] = {f.fx, f.fy, f.cx, f.cy};
+    if (!D->mult || D->mult_w != f.w || D->mult_h != f.h || std::memcmp(k, D->mult_k, sizeof(k)) != 0) {
+        D->mult_w = 0;
+        TSDF_TRY(grow(&D->mult, &D->mult_cap, n));
+        multiplier_kernel<<<capped_blocks((long long)n), kThreads, 0, D->stream>>>(D->mult, f.w, f.h, cx, cy, 1.0f / fx, 1.0f / fy);
+        TSDF_TRY(hipGetLastError());
+        D->mult_w = f.w; D->mult_h = f.h;
+        std::memcpy(D->mult_k, k, sizeof(k));
+    }
+    IntegrateArgs a;
+    a.tsdf = D->tsdf; a.weight = D->weight; a.c0 = D->color[0]; a.c1 = D->color[1]; a.c2 = D->color[2];
+    a.units = D->unit_list; a.n_units = (int)list.size();
+    a.R = c.resolution;
+    a.depth = D->depth; a.mult = D->mult; a.gray = D->gray; a.rgb = D->rgb;
+    a.w = f.w; a.h = f.h;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.vl = (float)D->unit_voxel_length();
+    a.half = a.vl * 0.5f;
+    a.trunc = (float)c.sdf_trunc;
+    a.trunc_inv = 1.0f / a.trunc;
+    for (int i = 0; i < 12; i++) a.e[i] = (float)f.extrinsic[i];
+    for (int r = 0; r < 3; r++) a.es[r] = a.e[4 * r + 2] * a.vl;
+    a.safe_w = (float)f.w - 0.0001f; a.safe_h = (float)f.h - 0.0001f;
+    const unsigned blocks = capped_blocks((long long)c.resolution * c.resolution * (long long)list.size());
+    if (c.color_type == kTsdfColorRgb8) integrate_kernel<kTsdfColorRgb8><<<blocks, kThreads, 0, D->stream>>>(a);
+    else if (c.color_type == kTsdfColorGray32) integrate_kernel<kTsdfColorGray32><<<blocks, kThreads, 0, D->stream>>>(a);
+    else integrate_kernel<kTsdfColorNone><<<blocks, kThreads, 0, D->stream>>>(a);
+    TSDF_TRY(hipGetLastError());
+    D->rows[0] = D->rows[1] = -1;
+    return hipStreamSynchronize(D->stream);
+}
+
+hipError_t tsdf_device_extract(TsdfDevice *D, int voxel_cloud, int64_t *n)
+{
+    const TsdfConfig &c = D->cfg;
+    const int which = voxel_cloud ? 1 : 0;
+    D->rows[which] = -1;
+    *n = 0;
+    long long rows = 0;
+    UnitList units;
+    TSDF_TRY(upload_unit_list(D, &units));
+    const long long items = (long long)D->R3 * units.n;
+    if (voxel_cloud) {
+        const double vl = D->unit_voxel_length();
+        VoxelCloudSource s = {D->tsdf, D->weight, D->zs, units, c.resolution, vl, vl * 0.5, nullptr, nullptr};
+        TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
+        TSDF_TRY(grow(&D->out_points[1], &D->out_points_cap[1], 3 * (size_t)rows));
+        TSDF_TRY(grow(&D->out_colors[1], &D->out_colors_cap[1], 3 * (size_t)rows));
+        s.points = D->out_points[1]; s.colors = D->out_colors[1];
+        if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+    } else {
+        auto outputs = [&]() -> hipError_t {
+            TSDF_TRY(grow(&D->out_points[0], &D->out_points_cap[0], 3 * (size_t)rows));
+            TSDF_TRY(grow(&D->out_normals, &D->out_normals_cap, 3 * (size_t)rows));
+            return grow(&D->out_colors[0], &D->out_colors_cap[0], 3 * (size_t)rows);
+        };
+        if (c.scalable) {
+            ScalableSurfaceSource s = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], units, c.resolution, c.color_type,
+                                       c.voxel_length, c.voxel_length * 0.5, D->unit_length(), nullptr, nullptr, nullptr};
+            TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
+            TSDF_TRY(outputs());
+            s.points = D->out_points[0]; s.normals = D->out_normals; s.colors = D->out_colors[0];
+            if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+        } else {
+            const double vl = D->unit_voxel_length();
+            SurfaceSource s = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], c.resolution, c.color_type, vl, vl * 0.5,
+                               c.origin[0], c.origin[1], c.origin[2], nullptr, nullptr, nullptr};
+            TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
+            TSDF_TRY(outputs());
+            s.points = D->out_points[0]; s.normals = D->out_normals; s.colors = D->out_colors[0];
+            if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+        }
+    }
+    TSDF_TRY(hipStreamSynchronize(D->stream));
+    D->rows[which] = rows;
+    *n = (int64_t)rows;
+    return hipSuccess;
+}
+
+hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *points, double *normals, double *colors)
+{
+    const int which = voxel_cloud ? 1 : 0;
+    const long long rows = D->rows[which];
+    if (rows <= 0) return hipSuccess;
+    const size_t bytes = sizeof(double) * 3 * (size_t)rows;
+    if (points) TSDF_TRY(hipMemcpy(points, D->out_points[which], bytes, hipMemcpyDeviceToHost));
+    if (normals && !voxel_cloud) TSDF_TRY(hipMemcpy(normals, D->out_normals, bytes, hipMemcpyDeviceToHost));
+    if (colors && (voxel_cloud || D->planes() > 0)) TSDF_TRY(hipMemcpy(colors, D->out_colors[which], bytes, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys)
+{
+    keys->clear();
+    for (const auto &kv : D->slot_of)
+        for (int a = 0; a < 3; a++) keys->push_back(kv.first[a]);
+}
+
+hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsdf, float *weight, float *color)
+{
+    size_t slot = 0;
+    if (D->cfg.scalable) {
+        if (!unit) return hipErrorInvalidValue;
+        const auto it = D->slot_of.find({unit[0], unit[1], unit[2]});
+        if (it == D->slot_of.end()) return hipErrorInvalidValue;
+        slot = (size_t)it->second;
+    }
+    const size_t at = slot * D->R3, bytes = sizeof(float) * D->R3;
+    if (tsdf) TSDF_TRY(hipMemcpy(tsdf, D->tsdf + at, bytes, hipMemcpyDeviceToHost));
+    if (weight) TSDF_TRY(hipMemcpy(weight, D->weight + at, bytes, hipMemcpyDeviceToHost));
+    if (color && D->planes() > 0) {
+        // plane by plane in pieces of 4 M voxels (16 MB on the host whatever the resolution), interleaved as the reference
+        // keeps the colour; Gray32: the one plane, three times
+        const size_t piece = (size_t)1 << 22;
+        std::vector<float> buf(std::min(piece, D->R3));
+        for (size_t v0 = 0; v0 < D->R3; v0 += piece) {
+            const size_t m = std::min(piece, D->R3 - v0);
+            for (int c = 0; c < 3; c++) {
+                if (c < D->planes()) TSDF_TRY(hipMemcpy(buf.data(), D->color[c] + at + v0, sizeof(float) * m, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < m; i++) color[3 * (v0 + i) + (size_t)c] = buf[i];
+            }
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
+                                         double *colors, int64_t *n, hipStream_t stream)
+{
+    *n = 0;
+    const size_t px = (size_t)f.w * f.h;
+    const long long sw = ((long long)f.w - 1) / stride + 1, sh = ((long long)f.h - 1) / stride + 1, items = sw * sh;
+    float *d_depth = nullptr, *d_gray = nullptr;
+    uint8_t *d_rgb = nullptr;
+    double *d_points = nullptr, *d_colors = nullptr;
+    Compactor comp;
+    auto run = [&]() -> hipError_t {
+        TSDF_TRY(hipMalloc(&d_depth, sizeof(float) * px));
+        TSDF_TRY(hipMemcpyAsync(d_depth, f.depth, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+        if (color_type == kTsdfColorRgb8) {
+            TSDF_TRY(hipMalloc(&d_rgb, 3 * px));
+            TSDF_TRY(hipMemcpyAsync(d_rgb, f.color, 3 * px, hipMemcpyHostToDevice, stream));
+        } else if (color_type == kTsdfColorGray32) {
+            TSDF_TRY(hipMalloc(&d_gray, sizeof(float) * px));
+            TSDF_TRY(hipMemcpyAsync(d_gray, f.color, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+        }
+        DepthSource s;
+        s.depth = d_depth; s.gray = d_gray; s.rgb = d_rgb;
+        s.w = f.w; s.sw = (int)sw; s.stride = stride; s.color_type = color_type;
+        s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
+        for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
+        s.points = nullptr; s.colors = nullptr;
+        long long rows = 0;
+        TSDF_TRY(comp.count(s, items, stream, &rows));
+        *n = (int64_t)rows;
+        if (rows == 0 || !points) return hipSuccess;
+        const size_t bytes = sizeof(double) * 3 * (size_t)rows;
+        TSDF_TRY(hipMalloc(&d_points, bytes));
+        if (color_type != kTsdfColorNone) TSDF_TRY(hipMalloc(&d_colors, bytes));
+        s.points = d_points; s.colors = d_colors;
+        TSDF_TRY(comp.write(s, items, stream));
+        TSDF_TRY(hipMemcpyAsync(points, d_points, bytes, hipMemcpyDeviceToHost, stream));
+        if (colors && d_colors) TSDF_TRY(hipMemcpyAsync(colors, d_colors, bytes, hipMemcpyDeviceToHost, stream));
+        return hipStreamSynchronize(stream);
+    };
+    const hipError_t e = run();
+    if (e != hipSuccess) (void)hipStreamSynchronize(stream);
+    void *all[] = {d_depth, d_gray, d_rgb, d_points, d_colors};
+    for (void *p : all)
+        if (p) (void)hipFree(p);
+    comp.release();
+    return e;
+}
+
+}  // namespace visma
