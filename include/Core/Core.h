@@ -26,3 +26,6 @@
 #include "Integration/TSDFVolume.h"
 #include "Integration/UniformTSDFVolume.h"
 #include "Integration/ScalableTSDFVolume.h"
+#include "Geometry/TriangleMesh.h"
+#include "Camera/PinholeCameraTrajectory.h"
+#include "ColorMap/ColorMapOptimization.h"

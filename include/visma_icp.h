@@ -1274,6 +1274,85 @@ VISMA_ICP_API int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int
                                                   int color_type, const double intrinsic[4], const double extrinsic[16],
                                                   double *points, double *colors, int64_t capacity, int64_t *out_n);
 
+/* ---- Color map optimization: camera poses refined against the vertices' intensities, then the vertices re-coloured ------
+ *
+ * Open3D's ColorMapOptimization (Zhou and Koltun, SIGGRAPH 2014; Core/ColorMap/ColorMapOptimization.cpp), the RIGID variant
+ * (non_rigid_camera_coordinate == 0, Open3D's default).  The NON-RIGID variant is not built: a call with that flag set returns
+ * VISMA_ICP_ERR_INVALID and touches nothing; the option struct carries its fields so that the layout is the reference's.
+ *
+ * A color map is an object of its context (several may live at once; the context's end frees them all), resident on the
+ * GPU (colormap.hip).  The staged calls, in order: create, set every image and the vertices, prepare, then
+ * any of the getters, sums, step, run, and the colours.  A call before its stage is VISMA_ICP_ERR_INVALID; setting an image or
+ * the vertices again asks for a new prepare.  Every argument check comes before a device is touched.
+ *   images      gray = Gaussian3 of (0.2990f R + 0.5870f G + 0.1140f B) / 255.0f, dx and dy its Sobel3Dx and Sobel3Dy; the
+ *               mask is 255 where the Sobel gradient of the depth exceeds depth_threshold_for_discontinuity_check, dilated by
+ *               a square of half-size half_dilation_kernel_size_for_discontinuity_map.  Bit for bit the reference's.
+ *   visibility  computed ONCE, by prepare, from the poses of that moment: z >= 0, the rounded pixel inside the image, its
+ *               depth <= maximum_allowable_depth, its mask not 255, |z - depth| < depth_threshold_for_visiblity_check.
+ *   iteration   per camera over its visible vertices inside the 10-pixel margin: the 6 x 6 system of the intensity residual
+ *               against the vertex's proxy (the mean over its cameras), x = -JJ^-1 Jb, pose <- [Rz Ry Rx | t] pose; then the
+ *               proxies anew.  All cameras in one launch, f64, no atomics: a run is bit-identical to itself.
+ * Deviations from the reference:
+ *   - the ORDER of visibility is defined: a camera's vertex list ascends in vertex id, a vertex's camera list ascends in
+ *     camera id (the reference's per-vertex order is a race between its threads);
+ *   - a camera with fewer than 6 accepted vertices, or with a singular JJ, KEEPS its pose for that iteration and reports
+ *     its count (the reference inverts a zero matrix and turns the pose into NaN);
+ *   - a vertex whose projection is not finite is not visible (undefined behaviour in the reference). */
+typedef struct {                       /* ColorMapOptmizationOption, field for field */
+    int32_t non_rigid_camera_coordinate;                       /* must be 0 */
+    int32_t number_of_vertical_anchors;                        /* 16; non-rigid only */
+    double non_rigid_anchor_point_weight;                      /* 0.316; non-rigid only */
+    double maximum_iteration;                                  /* 300 (a double in the reference) */
+    double maximum_allowable_depth;                            /* 2.5 */
+    double depth_threshold_for_visiblity_check;                /* 0.03 */
+    double depth_threshold_for_discontinuity_check;            /* 0.1 */
+    int32_t half_dilation_kernel_size_for_discontinuity_map;   /* 3; 0 .. 64 */
+    int32_t reserved;
+} visma_icp_color_map_option;
+VISMA_ICP_API void visma_icp_color_map_option_default(visma_icp_color_map_option *option);
+typedef struct visma_icp_color_map visma_icp_color_map;
+#define VISMA_ICP_COLOR_MAP_GRAY 0
+#define VISMA_ICP_COLOR_MAP_DX 1
+#define VISMA_ICP_COLOR_MAP_DY 2
+#define VISMA_ICP_COLOR_MAP_MASK 3     /* uint8; the others fp32 */
+#define VISMA_ICP_COLOR_MAP_SUMS 29    /* per camera: the 21 upper entries of JJ row by row, Jb[6], rr, count */
+/* n_images frames of w x h (both above 20: the margin leaves an interior), intrinsic = {fx, fy, cx, cy}; option NULL: the
+ * defaults */
+VISMA_ICP_API int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                             const visma_icp_color_map_option *option, visma_icp_color_map **out);
+VISMA_ICP_API int visma_icp_color_map_destroy(visma_icp_ctx *ctx, visma_icp_color_map *map);
+/* frame i: depth w x h fp32 in metres, color w x h x color_channels uint8 (color_channels must be 3: RGB8), extrinsic 4 x 4
+ * row-major, world -> camera */
+VISMA_ICP_API int visma_icp_color_map_set_image(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, const float *depth,
+                                                const uint8_t *color, int color_channels, const double extrinsic[16]);
+VISMA_ICP_API int visma_icp_color_map_set_vertices(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *vertices, int64_t n);
+/* images, masks and visibility; visible_counts[n_images] (may be NULL) */
+VISMA_ICP_API int visma_icp_color_map_prepare(visma_icp_ctx *ctx, visma_icp_color_map *map, int64_t *visible_counts);
+/* which: VISMA_ICP_COLOR_MAP_*; out: w x h fp32, or uint8 for the mask */
+VISMA_ICP_API int visma_icp_color_map_get_image(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, int which, void *out);
+/* camera i's visible vertices, ascending: *out_n of them; indices may be NULL for the count alone, else room for capacity */
+VISMA_ICP_API int visma_icp_color_map_get_visible(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, int32_t *indices,
+                                                  int64_t capacity, int64_t *out_n);
+/* the proxy intensities of the current poses: n doubles, n the vertex count */
+VISMA_ICP_API int visma_icp_color_map_get_proxy(visma_icp_ctx *ctx, visma_icp_color_map *map, double *proxy, int64_t n);
+/* sums[n_images x 29] at the current poses; no pose moves */
+VISMA_ICP_API int visma_icp_color_map_sums(visma_icp_ctx *ctx, visma_icp_color_map *map, double *sums);
+/* one iteration: rr[n_images] and count[n_images] of the poses BEFORE the step */
+VISMA_ICP_API int visma_icp_color_map_step(visma_icp_ctx *ctx, visma_icp_color_map *map, double *rr, int64_t *count);
+/* k iterations (k < 0: the option's maximum_iteration); residual[k] (may be NULL): the sum of rr over the cameras, per iteration */
+VISMA_ICP_API int visma_icp_color_map_run(visma_icp_ctx *ctx, visma_icp_color_map *map, int k, double *residual);
+/* n_images x 16 doubles, row-major */
+VISMA_ICP_API int visma_icp_color_map_get_extrinsics(visma_icp_ctx *ctx, visma_icp_color_map *map, double *extrinsics);
+VISMA_ICP_API int visma_icp_color_map_set_extrinsics(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *extrinsics);
+/* the colour average of the current poses: n x 3 doubles, n the vertex count */
+VISMA_ICP_API int visma_icp_color_map_get_colors(visma_icp_ctx *ctx, visma_icp_color_map *map, double *colors, int64_t n);
+/* Everything in one call: depth n_images x h x w fp32, color n_images x h x w x 3 uint8, extrinsics n_images x 16 in and out,
+ * vertices n x 3, colors n x 3 out.  option->maximum_iteration iterations. */
+VISMA_ICP_API int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                                   const float *depth, const uint8_t *color, double *extrinsics,
+                                                   const double *vertices, int64_t n, const visma_icp_color_map_option *option,
+                                                   double *colors);
+
 /* The pose graph on plain arrays (pure functions; no ctx, no GPU).  Node i has a 4 x 4 pose (row-major, node to world);
  * an edge says: transformation maps the SOURCE node's cloud onto the TARGET node's (PoseGraph.h:52-86).  Odometry edges
  * are certain (uncertain = 0), loop closures uncertain; confidence is the line-process value in [0, 1]. */

@@ -42,6 +42,9 @@
 //                                      header set, open3d::UniformTSDFVolume: frames with poses fused into a volume on the GPU
 //                                      (O3D/Core/Odometry/Odometry.h): image pyramids, per-pixel pairs and the colour or
 //                                      hybrid Gauss-Newton rows on the GPU
+//   open3d::cicp::ColorMapOptimization camera poses refined against the vertices' intensities and the vertices re-coloured
+//                                      (O3D/Core/ColorMap/ColorMapOptimization.h, rigid variant), on a TriangleMesh or a
+//                                      PointCloud; with the stand-alone header set
 //   open3d::cicp::ICPRefinement        the ICP call of feh::ICPRefinement
 //                                      (src/evaluation.cpp:258-271)
 //   open3d::cicp::ComputePointCloudToPointCloudDistance / ComputePointCloudNearestNeighborDistance
@@ -77,6 +80,7 @@
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
 #include <Core/Integration/UniformTSDFVolume.h>
 #include <Core/Integration/ScalableTSDFVolume.h>
+#include <Core/ColorMap/ColorMapOptimization.h>
 #endif
 
 #include "visma_icp.h"
@@ -1842,10 +1846,88 @@ inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage
     return CreatePointCloudFromRGBDImage(detail::ThreadContext::instance().get(), image, intrinsic, extrinsic);
 }
 
+#ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
+// open3d::ColorMapOptimization (ColorMapOptimization.cpp, rigid) on the GPU: the one-call entry point of visma_icp.h.  The
+// non-rigid option and an image that is not float depth + RGB8 of the intrinsic's size throw std::invalid_argument.
+namespace detail {
+inline void color_map_optimization(visma_icp_ctx *ctx, const std::vector<Eigen::Vector3d> &vertices, std::vector<Eigen::Vector3d> &colors,
+                                   const std::vector<RGBDImage> &images, PinholeCameraTrajectory &camera,
+                                   const ColorMapOptmizationOption &option)
+{
+    const char *who = "[ColorMapOptimization] ";
+    if (option.non_rigid_camera_coordinate_) throw std::invalid_argument(std::string(who) + "the non-rigid optimization is not built.");
+    const size_t n = images.size();
+    if (n == 0 || camera.extrinsic_.size() != n) throw std::invalid_argument(std::string(who) + "one extrinsic per image, at least one.");
+    const int w = images[0].depth_.width_, h = images[0].depth_.height_;
+    std::vector<float> depth(n * (size_t)w * h);
+    std::vector<uint8_t> color(n * (size_t)w * h * 3);
+    std::vector<double> E(n * 16);
+    for (size_t i = 0; i < n; i++) {
+        const Image &d = images[i].depth_, &c = images[i].color_;
+        if (d.width_ != w || d.height_ != h || c.width_ != w || c.height_ != h || d.num_of_channels_ != 1 || d.bytes_per_channel_ != 4 ||
+            c.num_of_channels_ != 3 || c.bytes_per_channel_ != 1 || !d.HasData() || !c.HasData())
+            throw std::invalid_argument(std::string(who) + "Unsupported image format.");
+        std::memcpy(depth.data() + i * (size_t)w * h, d.data_.data(), (size_t)w * h * 4);
+        std::memcpy(color.data() + i * (size_t)w * h * 3, c.data_.data(), (size_t)w * h * 3);
+        to_rowmajor(camera.extrinsic_[i], E.data() + 16 * i);
+    }
+    const Eigen::Matrix3d &K = camera.intrinsic_.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    visma_icp_color_map_option o;
+    visma_icp_color_map_option_default(&o);
+    o.number_of_vertical_anchors = option.number_of_vertical_anchors_;
+    o.non_rigid_anchor_point_weight = option.non_rigid_anchor_point_weight_;
+    o.maximum_iteration = option.maximum_iteration_;
+    o.maximum_allowable_depth = option.maximum_allowable_depth_;
+    o.depth_threshold_for_visiblity_check = option.depth_threshold_for_visiblity_check_;
+    o.depth_threshold_for_discontinuity_check = option.depth_threshold_for_discontinuity_check_;
+    o.half_dilation_kernel_size_for_discontinuity_map = option.half_dilation_kernel_size_for_discontinuity_map_;
+    colors.assign(vertices.size(), Eigen::Vector3d::Zero());
+    // (std::vector<Eigen::Vector3d> is contiguous AoS f64 with stride 3)
+    const int rc = visma_icp_color_map_optimization(ctx, w, h, (int)n, k, depth.data(), color.data(), E.data(),
+                                                    vertices.empty() ? nullptr : vertices[0].data(), (int64_t)vertices.size(), &o,
+                                                    colors.empty() ? nullptr : colors[0].data());
+    if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string(who) + visma_icp_last_error(ctx));
+    check(ctx, rc, "visma_icp_color_map_optimization");
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 16; a++) camera.extrinsic_[i](a / 4, a % 4) = E[16 * i + (size_t)a];
+}
+}  // namespace detail
+
+// ... on a context of the caller's
+inline void ColorMapOptimization(visma_icp_ctx *ctx, TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd,
+                                 PinholeCameraTrajectory &camera, const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    detail::color_map_optimization(ctx, mesh.vertices_, mesh.vertex_colors_, images_rgbd, camera, option);
+}
+// ... on the points of a cloud (what ExtractPointCloud gives): colors_ is written
+inline void ColorMapOptimization(visma_icp_ctx *ctx, PointCloud &cloud, const std::vector<RGBDImage> &images_rgbd,
+                                 PinholeCameraTrajectory &camera, const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    detail::color_map_optimization(ctx, cloud.points_, cloud.colors_, images_rgbd, camera, option);
+}
+// ... on this thread's context
+inline void ColorMapOptimization(TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
+                                 const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    ColorMapOptimization(detail::ThreadContext::instance().get(), mesh, images_rgbd, camera, option);
+}
+inline void ColorMapOptimization(PointCloud &cloud, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
+                                 const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    ColorMapOptimization(detail::ThreadContext::instance().get(), cloud, images_rgbd, camera, option);
+}
+#endif
+
 }  // namespace cicp
 
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
 // Stand-alone header set: give the stock names their bodies too.
+inline void ColorMapOptimization(TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
+                                 const ColorMapOptmizationOption &option)
+{
+    cicp::ColorMapOptimization(mesh, images_rgbd, camera, option);
+}
 inline std::shared_ptr<PointCloud> CreatePointCloudFromDepthImage(const Image &depth, const PinholeCameraIntrinsic &intrinsic,
                                                                   const Eigen::Matrix4d &extrinsic, double depth_scale, double depth_trunc,
                                                                   int stride)

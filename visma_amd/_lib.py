@@ -208,6 +208,117 @@ class TsdfVolume:
         return tsdf, weight, color
 
 
+class CColorMapOption(C.Structure):
+    """visma_icp_color_map_option (Open3D's ColorMapOptmizationOption, field for field)"""
+    _fields_ = [("non_rigid_camera_coordinate", C.c_int32), ("number_of_vertical_anchors", C.c_int32),
+                ("non_rigid_anchor_point_weight", C.c_double), ("maximum_iteration", C.c_double), ("maximum_allowable_depth", C.c_double),
+                ("depth_threshold_for_visiblity_check", C.c_double), ("depth_threshold_for_discontinuity_check", C.c_double),
+                ("half_dilation_kernel_size_for_discontinuity_map", C.c_int32), ("reserved", C.c_int32)]
+
+
+COLOR_MAP_IMAGES = ("gray", "dx", "dy", "mask")
+COLOR_MAP_SUMS = 29
+
+
+def color_map_option(**fields):
+    """The library's defaults (visma_icp_color_map_option_default: Open3D's) with `fields` on top, e.g. maximum_iteration=8."""
+    o = CColorMapOption()
+    load().visma_icp_color_map_option_default(C.byref(o))
+    for k, v in fields.items():
+        if k not in dict(CColorMapOption._fields_) or k == "reserved":
+            raise TypeError("no such option: " + k)
+        setattr(o, k, v)
+    return o
+
+
+class ColorMap:
+    """A color map optimization resident on the device (visma_icp_color_map; Context.color_map): the staged calls of
+    visma_icp.h.  Lives until close() or the context's end."""
+
+    def __init__(self, ctx, handle, w, h, n_images):
+        self.ctx, self._m, self.w, self.h, self.n_images, self.n_vertices = ctx, handle, int(w), int(h), int(n_images), 0
+
+    def _call(self, name, *args):
+        self.ctx._chk(getattr(self.ctx.L, "visma_icp_color_map_" + name)(self.ctx._h, self._m, *args))
+
+    def close(self):
+        if self._m is not None and self.ctx._h:
+            self._call("destroy")
+        self._m = None
+
+    def set_image(self, i, depth, color, extrinsic):
+        """frame i: depth h x w fp32 (metres), color h x w x 3 uint8, extrinsic 4 x 4 world -> camera"""
+        depth = np.ascontiguousarray(depth, dtype=np.float32)
+        color = np.ascontiguousarray(color, dtype=np.uint8)
+        if depth.shape != (self.h, self.w) or color.ndim != 3 or color.shape[:2] != (self.h, self.w):
+            raise ValueError("the images do not fit the color map's size")
+        E = _f64(extrinsic, (16,))
+        self._call("set_image", int(i), _p(depth, _fp), color.ctypes.data_as(C.POINTER(C.c_uint8)), int(color.shape[2]), _p(E, _dp))
+
+    def set_vertices(self, vertices):
+        v = _f64(vertices, (-1, 3))
+        self._call("set_vertices", _p(v, _dp), len(v))
+        self.n_vertices = len(v)
+
+    def prepare(self):
+        """images, masks, visibility -> the visible vertex count of every camera (int64)"""
+        counts = np.zeros(self.n_images, np.int64)
+        self._call("prepare", counts.ctypes.data_as(C.POINTER(C.c_int64)))
+        return counts
+
+    def image(self, i, which):
+        """which: "gray" | "dx" | "dy" (h x w fp32) | "mask" (h x w uint8)"""
+        k = COLOR_MAP_IMAGES.index(which) if isinstance(which, str) else int(which)
+        out = np.empty((self.h, self.w), np.uint8 if k == 3 else np.float32)
+        self._call("get_image", int(i), k, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def visible(self, i):
+        """camera i's visible vertices, ascending (int32)"""
+        n = C.c_int64(0)
+        self._call("get_visible", int(i), None, 0, C.byref(n))
+        out = np.empty(max(n.value, 1), np.int32)
+        self._call("get_visible", int(i), _p(out, _ip), len(out), C.byref(n))
+        return out[:n.value].copy()
+
+    def proxy(self):
+        out = np.empty(self.n_vertices)
+        self._call("get_proxy", _p(out, _dp), self.n_vertices)
+        return out
+
+    def sums(self):
+        """n_images x 29 at the current poses: JJ's 21 upper entries row by row, Jb[6], rr, count; no pose moves"""
+        out = np.empty((self.n_images, COLOR_MAP_SUMS))
+        self._call("sums", _p(out, _dp))
+        return out
+
+    def step(self):
+        """one iteration -> rr (n_images f64), count (n_images int64) of the poses before it"""
+        rr, count = np.empty(self.n_images), np.empty(self.n_images, np.int64)
+        self._call("step", _p(rr, _dp), count.ctypes.data_as(C.POINTER(C.c_int64)))
+        return rr, count
+
+    def run(self, k=-1):
+        """k iterations (default: the option's maximum_iteration) -> the residual of every iteration"""
+        out = np.empty(max(int(k), 0)) if k >= 0 else None
+        self._call("run", int(k), None if out is None else _p(out, _dp))
+        return out
+
+    def extrinsics(self):
+        out = np.empty((self.n_images, 4, 4))
+        self._call("get_extrinsics", _p(out, _dp))
+        return out
+
+    def set_extrinsics(self, extrinsics):
+        E = _f64(extrinsics, (self.n_images * 16,))
+        self._call("set_extrinsics", _p(E, _dp))
+
+    def colors(self):
+        out = np.empty((self.n_vertices, 3))
+        self._call("get_colors", _p(out, _dp), self.n_vertices)
+        return out
+
+
 class CGlobalOptimizationCriteria(C.Structure):
     """visma_icp_global_optimization_criteria"""
     _fields_ = [("max_iteration", C.c_int32), ("min_relative_increment", C.c_double),
@@ -456,6 +567,26 @@ def _bind(L):
         L.visma_icp_tsdf_get_units.argtypes = [_vp, _vp, _ip, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_depth.argtypes = [_vp, C.c_int, C.c_int, _fp, _dp, _dp, C.c_int, _dp, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_rgbd.argtypes = [_vp, C.c_int, C.c_int, _fp, _vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64]
+    if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
+        _opt = C.POINTER(CColorMapOption)
+        L.visma_icp_color_map_option_default.argtypes = [_opt]
+        L.visma_icp_color_map_option_default.restype = None
+        L.visma_icp_color_map_create.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _opt, C.POINTER(_vp)]
+        L.visma_icp_color_map_destroy.argtypes = [_vp, _vp]
+        L.visma_icp_color_map_set_image.argtypes = [_vp, _vp, C.c_int, _fp, _u8, C.c_int, _dp]
+        L.visma_icp_color_map_set_vertices.argtypes = [_vp, _vp, _dp, C.c_int64]
+        L.visma_icp_color_map_prepare.argtypes = [_vp, _vp, _i64]
+        L.visma_icp_color_map_get_image.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
+        L.visma_icp_color_map_get_visible.argtypes = [_vp, _vp, C.c_int, _ip, C.c_int64, _i64]
+        L.visma_icp_color_map_get_proxy.argtypes = [_vp, _vp, _dp, C.c_int64]
+        L.visma_icp_color_map_sums.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_step.argtypes = [_vp, _vp, _dp, _i64]
+        L.visma_icp_color_map_run.argtypes = [_vp, _vp, C.c_int, _dp]
+        L.visma_icp_color_map_get_extrinsics.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_set_extrinsics.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_get_colors.argtypes = [_vp, _vp, _dp, C.c_int64]
+        L.visma_icp_color_map_optimization.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _fp, _u8, _dp, _dp, C.c_int64, _opt, _dp]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -1298,6 +1429,32 @@ class Context:
         self._chk(self.L.visma_icp_point_cloud_from_rgbd(self._h, w, h, _p(depth, _fp), color.ctypes.data_as(C.c_void_p), color_type,
                                                          _p(k, _dp), _p(E, _dp), _p(pts, _dp), _p(col, _dp), cap, C.byref(n)))
         return pts[:n.value].copy(), col[:n.value].copy()
+
+    # ---- color map optimization (visma_icp.h) ----
+    def color_map(self, w, h, n_images, intrinsic, option=None):
+        """Open3D's ColorMapOptimization (rigid) as staged calls -> ColorMap.  intrinsic [fx, fy, cx, cy]; option:
+        color_map_option(...) (default: Open3D's)."""
+        k = _f64(intrinsic, (4,))
+        m = C.c_void_p()
+        self._chk(self.L.visma_icp_color_map_create(self._h, int(w), int(h), int(n_images), _p(k, _dp),
+                                                    None if option is None else C.byref(option), C.byref(m)))
+        return ColorMap(self, m, w, h, n_images)
+
+    def color_map_optimization(self, vertices, depths, colors, intrinsic, extrinsics, option=None):
+        """ColorMapOptimization in one call: depths n x h x w fp32, colors n x h x w x 3 uint8, extrinsics n x 4 x 4
+        -> (refined extrinsics n x 4 x 4, vertex colours m x 3)."""
+        depths = np.ascontiguousarray(depths, dtype=np.float32)
+        colors = np.ascontiguousarray(colors, dtype=np.uint8)
+        if depths.ndim != 3 or colors.shape != depths.shape + (3,):
+            raise ValueError("depths n x h x w and colors n x h x w x 3")
+        n, h, w = depths.shape
+        v = _f64(vertices, (-1, 3)); k = _f64(intrinsic, (4,))
+        E = _f64(extrinsics, (n * 16,)).copy()
+        out = np.empty((len(v), 3))
+        self._chk(self.L.visma_icp_color_map_optimization(self._h, w, h, n, _p(k, _dp), _p(depths, _fp),
+                                                          colors.ctypes.data_as(C.POINTER(C.c_uint8)), _p(E, _dp), _p(v, _dp), len(v),
+                                                          None if option is None else C.byref(option), _p(out, _dp)))
+        return E.reshape(n, 4, 4), out
 
     def iterate(self, T, max_dist, steps, solver=SOLVER_KABSCH, with_scaling=False):
         """Exactly `steps` fixed iterations from T; returns (T_new, Result of last pass)."""

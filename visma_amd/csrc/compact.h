@@ -1,0 +1,143 @@
+// compact.h -- count, scan, write: the ordered compaction tsdf.hip (extraction, frame clouds) and colormap.hip (the visible
+// vertex lists) share.  Kernels and the grow-only Compactor; each including file gets its own copy (unnamed namespace).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+namespace visma {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 2048;                         // memory-bound passes: the grid is capped and strides
+constexpr int kScanThreads = 1024;
+
+inline unsigned capped_blocks(long long n) { return (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, kMaxBlocks); }
+
+// ---- count, scan, write: an ordered compaction over n items in tiles of kThreads ----
+// A Source has  __device__ int count(long long i) const  (rows item i emits) and
+//               __device__ void emit(long long i, long long row) const  (writes them at row, row + 1, ...).
+template <class Source>
+__global__ __launch_bounds__(kThreads) void count_kernel(Source s, long long n, long long tiles, int *tile_count)
+{
+    __shared__ int wave_sum[kThreads / 64];
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long i = tile * kThreads + threadIdx.x;
+        int c = i < n ? s.count(i) : 0;
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = c;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = 0;
+            for (int k = 0; k < kThreads / 64; k++) t += wave_sum[k];
+            tile_count[tile] = t;
+        }
+        __syncthreads();
+    }
+}
+
+// exclusive scan of tile_count[0 .. tiles) into tile_offset, the total into *total: ONE workgroup, chunk by chunk with a carry
+__global__ __launch_bounds__(kScanThreads) void scan_kernel(const int *tile_count, long long tiles, long long *tile_offset, long long *total)
+{
+    __shared__ long long buf[kScanThreads];
+    __shared__ long long carry;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (long long at = 0; at < tiles; at += kScanThreads) {
+        const long long i = at + threadIdx.x;
+        const long long v = i < tiles ? (long long)tile_count[i] : 0;
+        buf[threadIdx.x] = v;
+        __syncthreads();
+        for (int o = 1; o < kScanThreads; o <<= 1) {                     // Hillis-Steele, inclusive
+            const long long add = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
+            __syncthreads();
+            buf[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (i < tiles) tile_offset[i] = carry + buf[threadIdx.x] - v;
+        __syncthreads();
+        if (threadIdx.x == kScanThreads - 1) carry += buf[threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+template <class Source>
+__global__ __launch_bounds__(kThreads) void write_kernel(Source s, long long n, long long tiles, const long long *tile_offset)
+{
+    __shared__ int buf[kThreads];
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long i = tile * kThreads + threadIdx.x;
+        const int c = i < n ? s.count(i) : 0;
+        buf[threadIdx.x] = c;
+        __syncthreads();
+        for (int o = 1; o < kThreads; o <<= 1) {
+            const int add = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
+            __syncthreads();
+            buf[threadIdx.x] += add;
+            __syncthreads();
+        }
+        if (c > 0) s.emit(i, tile_offset[tile] + (long long)(buf[threadIdx.x] - c));
+        __syncthreads();
+    }
+}
+
+// what the compaction works in: grow-only
+struct Compactor {
+    int *tile_count = nullptr;
+    long long *tile_offset = nullptr, *total = nullptr;
+    long long capacity = 0;
+    hipError_t ensure(long long tiles)
+    {
+        if (!total) { hipError_t e = hipMalloc(&total, sizeof(long long)); if (e != hipSuccess) return e; }
+        if (tiles <= capacity) return hipSuccess;
+        if (tile_count) (void)hipFree(tile_count);
+        if (tile_offset) (void)hipFree(tile_offset);
+        tile_count = nullptr; tile_offset = nullptr; capacity = 0;
+        hipError_t e = hipMalloc(&tile_count, sizeof(int) * (size_t)tiles);
+        if (e != hipSuccess) return e;
+        e = hipMalloc(&tile_offset, sizeof(long long) * (size_t)tiles);
+        if (e != hipSuccess) return e;
+        capacity = tiles;
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (tile_count) (void)hipFree(tile_count);
+        if (tile_offset) (void)hipFree(tile_offset);
+        if (total) (void)hipFree(total);
+        tile_count = nullptr; tile_offset = nullptr; total = nullptr; capacity = 0;
+    }
+    // the count pass and the scan; *rows on the host (one wait)
+    template <class Source>
+    hipError_t count(const Source &s, long long n, hipStream_t stream, long long *rows)
+    {
+        *rows = 0;
+        if (n <= 0) return hipSuccess;                   // nothing is launched over nothing
+        const long long tiles = (n + kThreads - 1) / kThreads;
+        hipError_t e = ensure(tiles);
+        if (e != hipSuccess) return e;
+        count_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_count);
+        scan_kernel<<<1, kScanThreads, 0, stream>>>(tile_count, tiles, tile_offset, total);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(rows, total, sizeof(long long), hipMemcpyDeviceToHost, stream);
+        if (e != hipSuccess) return e;
+        return hipStreamSynchronize(stream);
+    }
+    // ... and the write pass behind it (the Source now holds its output pointers)
+    template <class Source>
+    hipError_t write(const Source &s, long long n, hipStream_t stream)
+    {
+        if (n <= 0) return hipSuccess;
+        const long long tiles = (n + kThreads - 1) / kThreads;
+        write_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_offset);
+        return hipGetLastError();
+    }
+};
+
+}  // namespace
+
+}  // namespace visma

@@ -1940,6 +1940,265 @@ int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int h, const floa
     return point_cloud_from_frame(ctx, w, h, depth, color, color_type, intrinsic, extrinsic, 1, points, colors, capacity, out_n);
 }
 
+// ---- color map optimization (colormap.hip) --------------------------------------------------------------------------------
+void visma_icp_color_map_option_default(visma_icp_color_map_option *o)
+{
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->number_of_vertical_anchors = 16;
+    o->non_rigid_anchor_point_weight = 0.316;
+    o->maximum_iteration = 300.0;
+    o->maximum_allowable_depth = 2.5;
+    o->depth_threshold_for_visiblity_check = 0.03;
+    o->depth_threshold_for_discontinuity_check = 0.1;
+    o->half_dilation_kernel_size_for_discontinuity_map = 3;
+}
+
+// every argument check of a color map call, before anything reaches a device; stage 0: created, 1: prepared
+static int check_color_map(visma_icp_ctx *ctx, visma_icp_color_map *map, int stage)
+{
+    if (!map) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL color map");
+    for (const auto &m : ctx->color_maps)
+        if (m.get() == map) {
+            if (stage > 0 && !map->prepared) return ctx->fail(VISMA_ICP_ERR_INVALID, "the color map is not prepared: set the images and the vertices, then prepare");
+            return VISMA_ICP_OK;
+        }
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "not a color map of this context");
+}
+
+static int check_color_map_option(visma_icp_ctx *ctx, const visma_icp_color_map_option &o)
+{
+    if (o.non_rigid_camera_coordinate) return ctx->fail(VISMA_ICP_ERR_INVALID, "the non-rigid color map optimization is not built");
+    if (std::isnan(o.maximum_iteration) || std::isnan(o.maximum_allowable_depth) || std::isnan(o.depth_threshold_for_visiblity_check) ||
+        std::isnan(o.depth_threshold_for_discontinuity_check))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "an option that is not a number");
+    if (o.half_dilation_kernel_size_for_discontinuity_map < 0 || o.half_dilation_kernel_size_for_discontinuity_map > 64)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "half_dilation_kernel_size_for_discontinuity_map outside 0 .. 64");
+    return VISMA_ICP_OK;
+}
+
+#define COLOR_MAP_CALL(map, expr)                                                                           \
+    do {                                                                                                    \
+        int rc__ = ctx->eng->color_map_call((map)->id, [&](ColorMapDevice *D) -> hipError_t { return (expr); }); \
+        if (rc__) return ctx->eng_fail(rc__);                                                               \
+    } while (0)
+
+int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                               const visma_icp_color_map_option *option, visma_icp_color_map **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!intrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (n_images < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "n_images < 1");
+    if (w <= 20 || h <= 20) return ctx->fail(VISMA_ICP_ERR_INVALID, "w and h must be above 20: the 10-pixel margin leaves no interior");
+    if ((int64_t)w * h > (int64_t)1 << 26 || (int64_t)w * h * n_images > (int64_t)1 << 30)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "images of more than 2^30 pixels in all");
+    for (int k = 0; k < 4; k++)
+        if (!std::isfinite(intrinsic[k])) return ctx->fail(VISMA_ICP_ERR_INVALID, "an intrinsic that is not finite");
+    if (intrinsic[0] == 0.0 || intrinsic[1] == 0.0) return ctx->fail(VISMA_ICP_ERR_INVALID, "a focal length that is zero");
+    visma_icp_color_map_option o;
+    visma_icp_color_map_option_default(&o);
+    if (option) o = *option;
+    if (int rc = check_color_map_option(ctx, o)) return rc;
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "color map optimization runs on one rank");
+    std::unique_ptr<visma_icp_color_map> m(new visma_icp_color_map);
+    m->cfg.w = w; m->cfg.h = h; m->cfg.n_images = n_images;
+    m->cfg.fx = intrinsic[0]; m->cfg.fy = intrinsic[1]; m->cfg.cx = intrinsic[2]; m->cfg.cy = intrinsic[3];
+    m->cfg.max_depth = o.maximum_allowable_depth; m->cfg.visibility_threshold = o.depth_threshold_for_visiblity_check;
+    m->cfg.discontinuity_threshold = o.depth_threshold_for_discontinuity_check;
+    m->cfg.half_dilation = o.half_dilation_kernel_size_for_discontinuity_map;
+    m->iterations = o.maximum_iteration > 0.0 ? (o.maximum_iteration < 1e9 ? (int)std::ceil(o.maximum_iteration) : 1000000000) : 0;
+    m->image_set.assign((size_t)n_images, 0);
+    int rc = ctx->eng->color_map_create(m->cfg, &m->id);
+    if (rc) return ctx->eng_fail(rc);
+    *out = m.get();
+    ctx->color_maps.push_back(std::move(m));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_destroy(visma_icp_ctx *ctx, visma_icp_color_map *map)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    int rc = ctx->eng->color_map_destroy(map->id);
+    for (size_t i = 0; i < ctx->color_maps.size(); i++)
+        if (ctx->color_maps[i].get() == map) { ctx->color_maps.erase(ctx->color_maps.begin() + (std::ptrdiff_t)i); break; }
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_set_image(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, const float *depth, const uint8_t *color,
+                                  int color_channels, const double extrinsic[16])
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    if (!depth || !color || !extrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (color_channels != 3) return ctx->fail(VISMA_ICP_ERR_INVALID, "the colour image must be RGB8: 3 channels of uint8");
+    if (i < 0 || i >= map->cfg.n_images) return ctx->fail(VISMA_ICP_ERR_INVALID, "image index out of range");
+    map->prepared = false;
+    map->image_set[(size_t)i] = 0;
+    COLOR_MAP_CALL(map, color_map_device_set_image(D, i, depth, color, extrinsic));
+    map->image_set[(size_t)i] = 1;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_set_vertices(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *vertices, int64_t n)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    if (!vertices) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (n < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "no vertices");
+    // (vertex ids are int32, as the reference's; the compaction walks n_images lists of them)
+    if (n > (int64_t)1 << 30 || (n + 256) * map->cfg.n_images > (int64_t)1 << 36) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many vertices");
+    map->prepared = false;
+    map->n_vertices = -1;
+    COLOR_MAP_CALL(map, color_map_device_set_vertices(D, vertices, n));
+    map->n_vertices = n;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_prepare(visma_icp_ctx *ctx, visma_icp_color_map *map, int64_t *visible_counts)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    for (char s : map->image_set)
+        if (!s) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image is not set");
+    if (map->n_vertices < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "the vertices are not set");
+    map->prepared = false;
+    std::vector<int64_t> counts((size_t)map->cfg.n_images);
+    COLOR_MAP_CALL(map, color_map_device_prepare(D, counts.data()));
+    if (visible_counts) std::copy(counts.begin(), counts.end(), visible_counts);
+    map->prepared = true;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_image(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, int which, void *out)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (i < 0 || i >= map->cfg.n_images) return ctx->fail(VISMA_ICP_ERR_INVALID, "image index out of range");
+    if (which < VISMA_ICP_COLOR_MAP_GRAY || which > VISMA_ICP_COLOR_MAP_MASK) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown image");
+    COLOR_MAP_CALL(map, color_map_device_get_image(D, i, which, out));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_visible(visma_icp_ctx *ctx, visma_icp_color_map *map, int i, int32_t *indices, int64_t capacity,
+                                    int64_t *out_n)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out_n = 0;
+    if (i < 0 || i >= map->cfg.n_images) return ctx->fail(VISMA_ICP_ERR_INVALID, "image index out of range");
+    COLOR_MAP_CALL(map, (*out_n = color_map_device_visible_count(D, i), hipSuccess));
+    if (!indices) return VISMA_ICP_OK;
+    if (capacity < *out_n) return ctx->fail(VISMA_ICP_ERR_INVALID, "capacity below the number of visible vertices");
+    COLOR_MAP_CALL(map, color_map_device_get_visible(D, i, indices));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_proxy(visma_icp_ctx *ctx, visma_icp_color_map *map, double *proxy, int64_t n)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!proxy) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (n != map->n_vertices) return ctx->fail(VISMA_ICP_ERR_INVALID, "n differs from the vertex count");
+    COLOR_MAP_CALL(map, color_map_device_get_proxy(D, proxy));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_sums(visma_icp_ctx *ctx, visma_icp_color_map *map, double *sums)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!sums) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    COLOR_MAP_CALL(map, color_map_device_sums(D, sums));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_step(visma_icp_ctx *ctx, visma_icp_color_map *map, double *rr, int64_t *count)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!rr || !count) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    COLOR_MAP_CALL(map, color_map_device_step(D, rr, count));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_run(visma_icp_ctx *ctx, visma_icp_color_map *map, int k, double *residual)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (k < 0) k = map->iterations;
+    const size_t n = (size_t)map->cfg.n_images;
+    std::vector<double> rr(n);
+    std::vector<int64_t> count(n);
+    for (int it = 0; it < k; it++) {
+        COLOR_MAP_CALL(map, color_map_device_step(D, rr.data(), count.data()));
+        if (residual) {
+            double s = 0.0;
+            for (double v : rr) s += v;
+            residual[it] = s;
+        }
+    }
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_extrinsics(visma_icp_ctx *ctx, visma_icp_color_map *map, double *extrinsics)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    if (!extrinsics) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    for (char s : map->image_set)
+        if (!s) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image is not set");
+    COLOR_MAP_CALL(map, (color_map_device_get_extrinsics(D, extrinsics), hipSuccess));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_set_extrinsics(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *extrinsics)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 0)) return rc;
+    if (!extrinsics) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    COLOR_MAP_CALL(map, color_map_device_set_extrinsics(D, extrinsics));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_colors(visma_icp_ctx *ctx, visma_icp_color_map *map, double *colors, int64_t n)
+{
+    CTX_CHECK();
+    if (int rc = check_color_map(ctx, map, 1)) return rc;
+    if (!colors) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (n != map->n_vertices) return ctx->fail(VISMA_ICP_ERR_INVALID, "n differs from the vertex count");
+    COLOR_MAP_CALL(map, color_map_device_get_colors(D, colors));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4], const float *depth,
+                                     const uint8_t *color, double *extrinsics, const double *vertices, int64_t n,
+                                     const visma_icp_color_map_option *option, double *colors)
+{
+    CTX_CHECK();
+    if (!depth || !color || !extrinsics || !vertices || !colors) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (n < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "no vertices");
+    visma_icp_color_map *map = nullptr;
+    int rc = visma_icp_color_map_create(ctx, w, h, n_images, intrinsic, option, &map);
+    if (rc) return rc;
+    const size_t px = (size_t)w * h;
+    for (int i = 0; i < n_images && !rc; i++)
+        rc = visma_icp_color_map_set_image(ctx, map, i, depth + (size_t)i * px, color + (size_t)i * px * 3, 3, extrinsics + 16 * (size_t)i);
+    if (!rc) rc = visma_icp_color_map_set_vertices(ctx, map, vertices, n);
+    if (!rc) rc = visma_icp_color_map_prepare(ctx, map, nullptr);
+    if (!rc) rc = visma_icp_color_map_run(ctx, map, -1, nullptr);
+    if (!rc) rc = visma_icp_color_map_get_colors(ctx, map, colors, n);
+    if (!rc) rc = visma_icp_color_map_get_extrinsics(ctx, map, extrinsics);
+    const std::string err = ctx->err;
+    (void)visma_icp_color_map_destroy(ctx, map);
+    if (rc) ctx->err = err;
+    return rc;
+}
+
 int visma_icp_set_nn_mode(visma_icp_ctx *ctx, int nn_mode)
 {
     CTX_CHECK();

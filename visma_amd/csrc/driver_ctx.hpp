@@ -12,6 +12,16 @@ struct visma_icp_tsdf {
     int64_t rows[2] = {-1, -1};       // [0] ExtractPointCloud, [1] ExtractVoxelPointCloud; -1: none since the last change
 };
 
+// a color map object of a context: the engine's id, what it was created with and how far its staged calls have come
+struct visma_icp_color_map {
+    int id = 0;
+    ColorMapConfig cfg;
+    int iterations = 0;               // the option's maximum_iteration
+    std::vector<char> image_set;      // per frame: set since create
+    int64_t n_vertices = -1;          // -1: no vertices yet
+    bool prepared = false;
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -41,6 +51,7 @@ struct visma_icp_ctx {
     int64_t ns_total = 0;
     // the frame pair of the last visma_icp_odometry_prepare (resident on the engine): what the later calls check against
     struct { bool ready = false; int w = 0, h = 0, n_levels = 0; } odo;
+    std::vector<std::unique_ptr<visma_icp_color_map>> color_maps;   // likewise
     std::vector<std::unique_ptr<visma_icp_tsdf>> volumes;   // the engine frees their device memory with itself
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;

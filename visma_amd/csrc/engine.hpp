@@ -433,6 +433,16 @@ public:
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;
     }
+    // Color map optimization (colormap.hip): objects resident on the engine, named by the id color_map_create hands out; they
+    // live until color_map_destroy or the engine's end.  color_map_call binds the device, runs `f` on the object and turns
+    // its hipError_t into the engine's error.  (ColorMapConfig and the color_map_device_* functions: kernels.h.)
+    virtual int color_map_create(const ColorMapConfig &, int * /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int color_map_destroy(int /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int color_map_call(int /* id */, const std::function<hipError_t(ColorMapDevice *)> &)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // The host loop of ONE registration announces itself: between loop_begin(n) and loop_end() the caller runs at most
     // n passes (nn_pass + reduce, nothing else) -- an engine may then keep ONE launch alive across them (HipEngine:
     // the persistent certificate kernel).  loop_end() must follow on every path; LoopScope does that.

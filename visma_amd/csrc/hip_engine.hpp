@@ -52,6 +52,7 @@ public:
         pair_.release();
         if (odo_.arena) (void)hipFree(odo_.arena);
         for (auto &v : tsdf_) tsdf_device_destroy(v.second);
+        for (auto &v : color_maps_) color_map_device_destroy(v.second);
         pool_trim(0);
         if (d_raw_src_) (void)hipFree(d_raw_src_);
         if (stream_src_) (void)hipStreamDestroy(stream_src_);
@@ -352,6 +353,11 @@ public:
     int tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *weight, float *color) override;
     int point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n) override;
 
+    // color map optimization (colormap.hip): the objects by id; each owns its device memory, all on the one stream
+    int color_map_create(const ColorMapConfig &cfg, int *id) override;
+    int color_map_destroy(int id) override;
+    int color_map_call(int id, const std::function<hipError_t(ColorMapDevice *)> &f) override;
+
     // colored ICP (color_gradient.hip, colored.hip): f64 intensities of both clouds, the target's colour gradient, then the
     // plain pass and the reduction over the two rows per pair
     int set_source_intensity(const double *by_position, int64_t ns) override;
@@ -452,6 +458,9 @@ private:
     int tsdf_next_id_ = 1;
     // the device bound, no persistent launch left on the stream, and the volume of `id` (NULL with err_ set: unknown id)
     int tsdf_enter(int id, TsdfDevice **D);
+    // color map objects: id -> device object; ids are never reused within an engine
+    std::unordered_map<int, ColorMapDevice *> color_maps_;
+    int color_map_next_id_ = 1;
     // the launch of the correspondence kernel of `level` at T into odo_.idx
     int odometry_launch_correspondences(int level, const Mat4 &T);
     // the arguments every pass over odo_.idx shares: no clouds, the scratch and its ticket word (a new sequence number)

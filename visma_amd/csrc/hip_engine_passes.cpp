@@ -1182,6 +1182,40 @@ int HipEngine::point_cloud_from_depth(const TsdfFrame &f, int color_type, int st
     return VISMA_ICP_OK;
 }
 
+// ---- color map optimization (colormap.hip) ----
+int HipEngine::color_map_create(const ColorMapConfig &cfg, int *id)
+{
+    int rc = tsdf_enter(0, nullptr);                     // (the device bound, no persistent launch left on the stream)
+    if (rc) return rc;
+    ColorMapDevice *D = nullptr;
+    HIP_TRY(color_map_device_create(cfg, stream_, &D));
+    *id = color_map_next_id_++;
+    color_maps_[*id] = D;
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::color_map_destroy(int id)
+{
+    int rc = tsdf_enter(0, nullptr);
+    if (rc) return rc;
+    auto it = color_maps_.find(id);
+    if (it == color_maps_.end()) { err_ = "no such color map"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    color_map_device_destroy(it->second);
+    color_maps_.erase(it);
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::color_map_call(int id, const std::function<hipError_t(ColorMapDevice *)> &f)
+{
+    int rc = tsdf_enter(0, nullptr);
+    if (rc) return rc;
+    auto it = color_maps_.find(id);
+    if (it == color_maps_.end()) { err_ = "no such color map"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(f(it->second));
+    return VISMA_ICP_OK;
+}
+
 // K R K^-1 and K t of ComputeCorrespondence in f64 on the host; K = [fx 0 cx; 0 fy cy; 0 0 1] of the level, its inverse
 // written out
 int HipEngine::odometry_launch_correspondences(int level, const Mat4 &T)

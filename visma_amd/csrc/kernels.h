@@ -691,6 +691,40 @@ hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsd
 hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
                                          double *colors, int64_t *n, hipStream_t stream);
 
+// ---- color map optimization (colormap.hip): frames, vertices, visibility and poses resident on the device ----
+constexpr int kColorMapSums = 29;                      // per camera: 21 upper entries of JJ (row by row), 6 of Jb, rr, count
+constexpr int kColorMapMaxBlocks = 512;                // workgroups per camera of the iteration launch: beyond 512 * 256 visible
+                                                       // vertices a camera's list is walked in strides (measured:
+                                                       // profiles/colormap_blocks_ab.txt)
+struct ColorMapConfig {
+    int w = 0, h = 0, n_images = 0;
+    double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
+    double max_depth = 2.5, visibility_threshold = 0.03, discontinuity_threshold = 0.1;
+    int half_dilation = 3;
+};
+struct ColorMapDevice;
+// allocates the frames' buffers; nothing is left allocated where it fails
+hipError_t color_map_device_create(const ColorMapConfig &cfg, hipStream_t stream, ColorMapDevice **out);
+void color_map_device_destroy(ColorMapDevice *D);
+// frame i: depth w x h fp32 (metres), rgb w x h x 3 uint8, extrinsic row-major (host arrays; copied before the return)
+hipError_t color_map_device_set_image(ColorMapDevice *D, int i, const float *depth, const unsigned char *rgb, const double extrinsic[16]);
+hipError_t color_map_device_set_vertices(ColorMapDevice *D, const double *vertices, int64_t n);
+// gradient images, masks and the visibility of the poses as they are now; counts[n_images]: the cameras' visible vertices
+hipError_t color_map_device_prepare(ColorMapDevice *D, int64_t *counts);
+// which: 0 gray, 1 dx, 2 dy (w x h fp32), 3 mask (w x h uint8)
+hipError_t color_map_device_get_image(ColorMapDevice *D, int i, int which, void *out);
+int64_t color_map_device_visible_count(const ColorMapDevice *D, int i);
+hipError_t color_map_device_get_visible(ColorMapDevice *D, int i, int32_t *out);      // ascending vertex ids
+void color_map_device_get_extrinsics(const ColorMapDevice *D, double *out);           // n_images x 16
+hipError_t color_map_device_set_extrinsics(ColorMapDevice *D, const double *in);
+hipError_t color_map_device_get_proxy(ColorMapDevice *D, double *out);                // n_vertices, of the current poses
+// rows[n_images x kColorMapSums] at the current poses; nothing moves
+hipError_t color_map_device_sums(ColorMapDevice *D, double *rows);
+// one Gauss-Newton iteration of every camera; rr[n_images], count[n_images] (a camera with count < 6 or a singular system
+// keeps its pose)
+hipError_t color_map_device_step(ColorMapDevice *D, double *rr, int64_t *count);
+hipError_t color_map_device_get_colors(ColorMapDevice *D, double *out);               // n_vertices x 3, of the current poses
+
 // ---- the colour side of colored ICP (color_gradient.hip, colored.hip) ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
 inline double color_intensity(const double *rgb) { return (rgb[0] + rgb[1] + rgb[2]) / 3.0; }
