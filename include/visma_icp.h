@@ -1203,6 +1203,13 @@ VISMA_ICP_API int visma_icp_odometry_information(visma_icp_ctx *ctx, const doubl
  *   - a frame that does not fit (its size differs from the intrinsic's, no colour image for a coloured volume) is
  *     VISMA_ICP_ERR_INVALID; the reference prints "Unsupported image format" and returns without integrating;
  *   - the extractions of a scalable volume come in a defined order (below); the reference's is a hash map's;
+ *   - a scalable volume: a strided pixel touches no unit if its back-projected point has a coordinate that is not finite
+ *     (a depth of inf; a huge depth times a pose), or if either of its unit indices floor((p -+ sdf_trunc) / unit length)
+ *     lies outside +-2^30 on any axis; the rest of the frame integrates as usual, and a frame of nothing but such pixels
+ *     opens no unit and is not an error.  (The reference converts such a floor to int, which is undefined behaviour; on
+ *     x86-64 it opens one junk unit at index INT_MIN.)  A uniform volume needs no rule: a depth that is not > 0 (NaN, -inf,
+ *     negative, 0) is skipped and a depth of +inf integrates as tsdf 1, as in the reference; the point clouds from a frame
+ *     hold a row that is not finite for such a pixel, as the reference's do;
  *   - ExtractTriangleMesh and 16-bit depth are not provided.
  * No floating-point atomics: every voxel has one writer, and a run is bit-identical to itself.
  *
@@ -1245,7 +1252,8 @@ VISMA_ICP_API int visma_icp_tsdf_get_volume(visma_icp_ctx *ctx, visma_icp_tsdf *
  * that length), opened where a frame's surface comes near.  Integrate back-projects every stride-th pixel (rows and
  * columns) with a depth to extrinsic^-1 ((u - cx) d / fx, (v - cy) d / fy, d) in f64 -- the inverse by cofactors on the
  * host --, opens every unit between floor((p - sdf_trunc) / unit length) and floor((p + sdf_trunc) / unit length) per
- * component, and integrates the frame into each of those units as above.  The units live in a pool on the device of
+ * component (none for a pixel whose point is not finite or whose index lies beyond +-2^30: DEVIATIONS above), and
+ * integrates the frame into each of those units as above.  The units live in a pool on the device of
  * initial_units units at first (0: 256) that doubles when it is full; a unit's place in it never changes.  Every unit a
  * frame touches is opened before its integration starts, and a pool that cannot grow is VISMA_ICP_ERR_HIP with the
  * volume as it was.  Reset() forgets the units.

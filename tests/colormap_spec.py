@@ -77,7 +77,8 @@ def depth_mask(depth, threshold, k):
 def transform(E, V):
     """rows ((e0 X + e1 Y) + e2 Z) + e3 -> three f64 arrays"""
     X, Y, Z = V[:, 0], V[:, 1], V[:, 2]
-    return tuple(((E[r, 0] * X + E[r, 1] * Y) + E[r, 2] * Z) + E[r, 3] for r in range(3))
+    with np.errstate(invalid="ignore"):                                # (a vertex that is not finite)
+        return tuple(((E[r, 0] * X + E[r, 1] * Y) + E[r, 2] * Z) + E[r, 3] for r in range(3))
 
 
 def project(E, K, V):

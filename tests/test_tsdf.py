@@ -156,7 +156,7 @@ def check_scalable_extraction(golden, name, pc, vx):
     assert np.array_equal(S.digest(pts, np.float64), golden[name + "_pc_points_sha"])
     at = golden[name + "_pc_at"]
     assert same_bits(pts[at], golden[name + "_pc_points"])
-    dn = float(np.max(np.abs(nrm[at] - golden[name + "_pc_normals"])))
+    dn = float(np.max(np.abs(nrm[at] - golden[name + "_pc_normals"]), initial=0.0))               # (initial: a cloud may be empty)
     assert dn <= S.NORMAL_TOL, dn
     assert same_bits(nrm[at], golden[name + "_pc_normals"]), dn        # (the specification reaches bit for bit)
     if t == S.COLOR_NONE:
@@ -178,7 +178,7 @@ def check_extraction(golden, R, t, pc, vx):
     assert np.array_equal(S.digest(pts, np.float64), golden["u%d_pc_points_sha" % R])        # count, points and order
     at = golden["u%d_pc_at" % R]
     assert same_bits(pts[at], golden["u%d_pc_points" % R])
-    dn = float(np.max(np.abs(nrm[at] - golden["u%d_pc_normals" % R])))
+    dn = float(np.max(np.abs(nrm[at] - golden["u%d_pc_normals" % R]), initial=0.0))                 # (initial: a cloud may be empty)
     assert dn <= S.NORMAL_TOL, dn
     assert same_bits(nrm[at], golden["u%d_pc_normals" % R]), dn               # (the specification reaches bit for bit: so must the library)
     if t == S.COLOR_NONE:

@@ -23,8 +23,10 @@ What is exact and what is bounded:
                  sorted -- the reference's order is a hash map's; the specification's is units in lexicographic order.
   point clouds   bit for bit with the identity extrinsic; with another, within 1e-12 relative (the inverse's rounding).
 
-Deviation the specification shares with the library (include/visma_icp.h): a frame whose format or size does not fit is an
-error, not a silent return."""
+Deviations the specification shares with the library (include/visma_icp.h): a frame whose format or size does not fit is an
+error, not a silent return; a strided pixel of a scalable volume's frame touches no unit if its point has a coordinate that
+is not finite or if a unit index lies outside +-2^30 (touched_units).  tests/golden/rgbd_hostile.npz
+(tests/golden/gen_rgbd_hostile.py) pins the specification on hostile frames."""
 import hashlib
 
 import numpy as np
@@ -82,7 +84,8 @@ def integrate(vol, depth, color, intrinsic, extrinsic, trace=None):
         cf = np.ascontiguousarray(color, np.uint8).reshape(h, w, 3).astype(F32)
     elif vol["color_type"] == COLOR_GRAY32:
         cf = np.repeat(np.ascontiguousarray(color, F32).reshape(h, w, 1), 3, axis=2)
-    count = dict(behind=0, left=0, right=0, top=0, bottom=0, hole=0, far_behind=0, clamped=0, integrated=0)
+    count = dict(behind=0, left=0, right=0, top=0, bottom=0, hole=0, far_behind=0, clamped=0, integrated=0,
+                 at_camera_plane=0, depth_nan=0, depth_negative=0, depth_inf=0, depth_huge=0, depth_denormal=0)
     with np.errstate(all="ignore"):
         for z in range(R):
             px, py, pz = p
@@ -111,6 +114,14 @@ def integrate(vol, depth, color, intrinsic, extrinsic, trace=None):
             count["far_behind"] += int(np.count_nonzero(seen & ~go))
             count["clamped"] += int(np.count_nonzero(go & (sdf * trunc_inv > F32(1.0))))
             count["integrated"] += int(np.count_nonzero(go))
+            count["at_camera_plane"] += int(np.count_nonzero(pz == 0))
+            # what a sensor hands over besides a depth, under a voxel that projects into the image: skipped (NaN, negative
+            # or -inf: "hole" too) or integrated as tsdf 1 (+inf, 1e30) or as a depth (a denormal)
+            count["depth_nan"] += int(np.count_nonzero(inside & np.isnan(d)))
+            count["depth_negative"] += int(np.count_nonzero(inside & (d < 0)))
+            count["depth_inf"] += int(np.count_nonzero(go & np.isinf(d)))
+            count["depth_huge"] += int(np.count_nonzero(go & np.isfinite(d) & (d > F32(1e20))))
+            count["depth_denormal"] += int(np.count_nonzero(seen & (d < np.finfo(F32).tiny)))
             p = [px + Es[0, 2], py + Es[1, 2], pz + Es[2, 2]]
     if trace is not None:
         for k, n in count.items():
@@ -225,9 +236,11 @@ def point_cloud_from_depth(depth, intrinsic, extrinsic=None, stride=1, color=Non
     d = depth[i, j]
     m = d > 0
     i, j, z = i[m], j[m], d[m].astype(np.float64)
-    x = (j - cx) * z / fx
-    y = (i - cy) * z / fy
-    pts = np.stack([((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3)], 1) if len(z) else np.zeros((0, 3))
+    with np.errstate(all="ignore"):
+        x = (j - cx) * z / fx
+        y = (i - cy) * z / fy
+    with np.errstate(all="ignore"):                                    # (a depth of inf gives rows that are not finite, as in the reference)
+        pts = np.stack([((P[r, 0] * x + P[r, 1] * y) + P[r, 2] * z) + P[r, 3] for r in range(3)], 1) if len(z) else np.zeros((0, 3))
     colors = None
     if color is not None:
         color = np.asarray(color)
@@ -248,25 +261,42 @@ def new_scalable(voxel_length, sdf_trunc, color_type, unit_resolution=16, stride
                 unit_length=float(voxel_length) * int(unit_resolution), stride=int(stride), units={})
 
 
+UNIT_INDEX_LIMIT = 2 ** 30
+
+
 def locate_units(points, unit_length):
-    """LocateVolumeUnit: (int)floor(p / unit_length) per component; also how far the nearest quotient is from an integer,
-    relative to its magnitude (the margin of the f64 decision)"""
-    q = points / unit_length
+    """LocateVolumeUnit: floor(p / unit_length) per component, as f64 -- NOT converted to an integer: the quotient of a point
+    that is not finite, or beyond what an int holds, has no index (touched_units drops such rows by THE RULE below before it
+    converts); also, per row, how far the nearest quotient is from an integer, relative to its magnitude (the margin of the f64
+    decision)"""
     with np.errstate(all="ignore"):
-        margin = float(np.min(np.abs(q - np.rint(q)) / np.maximum(np.abs(q), 1.0))) if q.size else np.inf
-    return np.floor(q).astype(np.int64), margin
+        q = points / unit_length
+        near = (np.abs(q - np.rint(q)) / np.maximum(np.abs(q), 1.0)).min(1) if q.size else np.zeros(0)
+        return np.floor(q), near
 
 
 def touched_units(svol, depth, intrinsic, extrinsic, trace=None):
     """the unit indices ScalableTSDFVolume::Integrate opens for a frame (sorted): every unit between LocateVolumeUnit(p -
-    sdf_trunc) and LocateVolumeUnit(p + sdf_trunc) of every strided back-projected point"""
+    sdf_trunc) and LocateVolumeUnit(p + sdf_trunc) of every strided back-projected point.
+
+    THE RULE (a deviation the specification shares with the library, include/visma_icp.h): a strided pixel touches no unit
+    if its point has a coordinate that is not finite, or if either of its box indices lies outside +-2^30 on any axis.  (The
+    reference converts such a floor to int, which is undefined; on x86-64 it opens one junk unit at INT_MIN.)  trace
+    counts the pixels dropped as "dropped_pixels"."""
     pts, _ = point_cloud_from_depth(depth, intrinsic, extrinsic, svol["stride"])
     if not len(pts):
         return []
     lo, m0 = locate_units(pts - svol["sdf_trunc"], svol["unit_length"])
     hi, m1 = locate_units(pts + svol["sdf_trunc"], svol["unit_length"])
+    with np.errstate(all="ignore"):
+        keep = np.isfinite(pts).all(1) & (np.abs(lo) <= UNIT_INDEX_LIMIT).all(1) & (np.abs(hi) <= UNIT_INDEX_LIMIT).all(1)
     if trace is not None:
-        trace["floor_margin"] = min(trace.get("floor_margin", np.inf), m0, m1)
+        trace["dropped_pixels"] = trace.get("dropped_pixels", 0) + int(np.count_nonzero(~keep))
+    lo, hi = lo[keep].astype(np.int64), hi[keep].astype(np.int64)
+    if not len(lo):
+        return []
+    if trace is not None:
+        trace["floor_margin"] = min(trace.get("floor_margin", np.inf), float(m0[keep].min()), float(m1[keep].min()))
         trace["span"] = max(trace.get("span", 0), int((hi - lo).max()) + 1)
     keys = set()
     for row in set(map(tuple, np.concatenate([lo, hi], 1).tolist())):

@@ -23,7 +23,8 @@
 //               the fp32 weights promoted as the reference promotes them.
 //  from depth   the same three kernels over the strided pixels in row-major order.
 //  scalable     ScalableTSDFVolume: units of R^3 voxels in a pool of slots (tsdf, weight, colour planes of capacity x R^3).
-//               touched_kernel finds the unit boxes of a frame's strided pixels in f64, the host removes duplicates and
+//               touched_kernel finds the unit boxes of a frame's strided pixels in f64 (none for a pixel whose point is not
+//               finite or whose unit index lies beyond +-2^30), the host (tsdf_units.h) removes duplicates and
 //               opens every new unit (the pool grows by allocate, copy, free; slots never move) BEFORE the integrate kernel
 //               runs over the list of touched units -- the same kernel, a uniform volume being a list of one.  Extraction
 //               walks the units in lexicographic order of their index and reads a +1 neighbour or a corner of GetTSDFAt in
@@ -31,9 +32,9 @@
 // (Reasoning: DESIGN.md 4.4c11.)
 #include "kernels.h"
 #include "compact.h"
+#include "tsdf_units.h"
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
 #include <cstring>
 #include <array>
@@ -429,19 +430,26 @@ struct DepthSource {
 };
 
 // ScalableTSDFVolume::Integrate's touched units: per strided pixel with a depth, LocateVolumeUnit(point - sdf_trunc) and
-// LocateVolumeUnit(point + sdf_trunc) in f64 -- six ints, the first INT_MIN where the pixel has no depth.  The host
-// expands the boxes into unit keys and removes the duplicates.
-__global__ __launch_bounds__(kThreads) void touched_kernel(DepthSource s, long long n, double trunc, double ul, int *bounds)
+// LocateVolumeUnit(point + sdf_trunc) in f64 -- a TouchedBox.  The host expands the boxes into unit keys and removes the
+// duplicates (tsdf_units.h).  A pixel without a depth, with a point that is not finite (a depth of inf, or of 1e38 times a
+// pose) or with an index beyond +-2^30 has valid = 0.  The comparisons are made on the f64 floors and are false for a NaN,
+// so no value is converted to int that an int cannot hold.
+__global__ __launch_bounds__(kThreads) void touched_kernel(DepthSource s, long long n, double trunc, double ul, TouchedBox *boxes)
 {
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
-        int *b = bounds + 6 * i;
-        if (!s.count(i)) { b[0] = INT_MIN; continue; }
-        double p[3];
-        s.point(i, p);
-        for (int a = 0; a < 3; a++) {
-            b[a] = (int)floor((p[a] - trunc) / ul);
-            b[3 + a] = (int)floor((p[a] + trunc) / ul);
+        TouchedBox b = {{0, 0, 0}, {0, 0, 0}, 0};
+        if (s.count(i)) {
+            double p[3];
+            s.point(i, p);
+            bool ok = true;
+            for (int a = 0; a < 3; a++) {
+                const double lo = floor((p[a] - trunc) / ul), hi = floor((p[a] + trunc) / ul);
+                ok = ok && isfinite(p[a]) && fabs(lo) <= (double)kTsdfUnitIndexLimit && fabs(hi) <= (double)kTsdfUnitIndexLimit;
+                if (ok) { b.lo[a] = (int32_t)lo; b.hi[a] = (int32_t)hi; }
+            }
+            b.valid = ok ? 1 : 0;
         }
+        boxes[i] = b;
     }
 }
 
@@ -476,7 +484,7 @@ struct TsdfDevice {
     // the last frame: depth, colour, the multiplier image of the last intrinsic, the touched boxes, the unit list
     float *depth = nullptr, *gray = nullptr, *mult = nullptr;
     uint8_t *rgb = nullptr;
-    int *bounds = nullptr;
+    TouchedBox *bounds = nullptr;
     TsdfUnit *unit_list = nullptr;
     size_t depth_cap = 0, gray_cap = 0, rgb_cap = 0, mult_cap = 0, bounds_cap = 0, unit_list_cap = 0;
     int mult_w = 0, mult_h = 0;
@@ -628,20 +636,13 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
         s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
         for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
         s.points = nullptr; s.colors = nullptr;
-        TSDF_TRY(grow(&D->bounds, &D->bounds_cap, 6 * (size_t)items));
+        TSDF_TRY(grow(&D->bounds, &D->bounds_cap, (size_t)items));
         touched_kernel<<<capped_blocks(items), kThreads, 0, D->stream>>>(s, items, c.sdf_trunc, D->unit_length(), D->bounds);
         TSDF_TRY(hipGetLastError());
-        std::vector<int> b(6 * (size_t)items);
-        TSDF_TRY(hipMemcpyAsync(b.data(), D->bounds, sizeof(int) * b.size(), hipMemcpyDeviceToHost, D->stream));
+        std::vector<TouchedBox> b((size_t)items);
+        TSDF_TRY(hipMemcpyAsync(b.data(), D->bounds, sizeof(TouchedBox) * b.size(), hipMemcpyDeviceToHost, D->stream));
         TSDF_TRY(hipStreamSynchronize(D->stream));
-        std::set<std::array<int, 3>> touched;
-        std::set<std::array<int, 6>> boxes;
-        for (long long i = 0; i < items; i++)
-            if (b[6 * i] != INT_MIN) boxes.insert({b[6 * i], b[6 * i + 1], b[6 * i + 2], b[6 * i + 3], b[6 * i + 4], b[6 * i + 5]});
-        for (const auto &q : boxes)
-            for (int x = q[0]; x <= q[3]; x++)
-                for (int y = q[1]; y <= q[4]; y++)
-                    for (int z = q[2]; z <= q[5]; z++) touched.insert({x, y, z});
+        const std::set<std::array<int, 3>> touched = expand_touched_boxes(b.data(), b.size());
         if (touched.empty()) return hipSuccess;          // nothing is launched with an empty list
         size_t next = D->slot_of.size();
         std::vector<std::array<int, 3>> opened;
