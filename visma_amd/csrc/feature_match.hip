@@ -73,30 +73,7 @@ __global__ __launch_bounds__(kMatchThreads) void match_features_kernel(const dou
     }
 }
 
-struct MatchBufs {
-    std::vector<void *> ptrs;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~MatchBufs()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1));
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return hipSuccess;
-    }
-};
-
 }  // namespace
-
-#define MATCH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 // h_nn: nb indices into fa (-1: none); h_d2 (may be NULL): nb squared distances; kernel_ms (may be NULL): device time
 hipError_t match_features_device(const double *h_fa, int64_t na, const double *h_fb, int64_t nb, int dim, int32_t *h_nn,
@@ -112,30 +89,31 @@ hipError_t match_features_device(const double *h_fa, int64_t na, const double *h
         }
         return hipSuccess;
     }
-    MatchBufs B;
+    DevBufs B;
+    DevEvents<2> ev;
     double *d_fa = nullptr, *d_fb = nullptr, *d_d2 = nullptr;
     int *d_nn = nullptr;
-    MATCH_TRY(B.alloc(&d_fa, (size_t)na * dim));
-    MATCH_TRY(B.alloc(&d_fb, (size_t)nb * dim));
-    MATCH_TRY(B.alloc(&d_nn, (size_t)nb));
-    MATCH_TRY(B.alloc(&d_d2, (size_t)nb));
-    for (hipEvent_t &e : B.ev) MATCH_TRY(hipEventCreate(&e));
-    MATCH_TRY(hipMemcpyAsync(d_fa, h_fa, sizeof(double) * (size_t)na * dim, hipMemcpyHostToDevice, stream));
-    MATCH_TRY(hipMemcpyAsync(d_fb, h_fb, sizeof(double) * (size_t)nb * dim, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(B.alloc(&d_fa, (size_t)na * dim));
+    VISMA_TRY(B.alloc(&d_fb, (size_t)nb * dim));
+    VISMA_TRY(B.alloc(&d_nn, (size_t)nb));
+    VISMA_TRY(B.alloc(&d_d2, (size_t)nb));
+    VISMA_TRY(ev.create());
+    VISMA_TRY(hipMemcpyAsync(d_fa, h_fa, sizeof(double) * (size_t)na * dim, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(hipMemcpyAsync(d_fb, h_fb, sizeof(double) * (size_t)nb * dim, hipMemcpyHostToDevice, stream));
     const dim3 grid((unsigned)((nb + kMatchThreads - 1) / kMatchThreads)), block(kMatchThreads);
-    MATCH_TRY(hipEventRecord(B.ev[0], stream));
+    VISMA_TRY(hipEventRecord(ev[0], stream));
     if (dim <= 4) hipLaunchKernelGGL(match_features_kernel<4>, grid, block, 0, stream, d_fa, (long long)na, d_fb, (long long)nb, dim, d_nn, d_d2);
     else if (dim <= 16) hipLaunchKernelGGL(match_features_kernel<16>, grid, block, 0, stream, d_fa, (long long)na, d_fb, (long long)nb, dim, d_nn, d_d2);
     else if (dim <= 36) hipLaunchKernelGGL(match_features_kernel<36>, grid, block, 0, stream, d_fa, (long long)na, d_fb, (long long)nb, dim, d_nn, d_d2);
     else hipLaunchKernelGGL(match_features_kernel<64>, grid, block, 0, stream, d_fa, (long long)na, d_fb, (long long)nb, dim, d_nn, d_d2);
-    MATCH_TRY(hipGetLastError());
-    MATCH_TRY(hipEventRecord(B.ev[1], stream));
-    MATCH_TRY(hipMemcpyAsync(h_nn, d_nn, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, stream));
-    if (h_d2) MATCH_TRY(hipMemcpyAsync(h_d2, d_d2, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, stream));
-    MATCH_TRY(hipStreamSynchronize(stream));
+    VISMA_TRY(hipGetLastError());
+    VISMA_TRY(hipEventRecord(ev[1], stream));
+    VISMA_TRY(hipMemcpyAsync(h_nn, d_nn, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, stream));
+    if (h_d2) VISMA_TRY(hipMemcpyAsync(h_d2, d_d2, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
     if (kernel_ms) {
         float t = 0.f;
-        MATCH_TRY(hipEventElapsedTime(&t, B.ev[0], B.ev[1]));
+        VISMA_TRY(hipEventElapsedTime(&t, ev[0], ev[1]));
         *kernel_ms = (double)t;
     }
     return hipSuccess;

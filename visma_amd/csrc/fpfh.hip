@@ -2,8 +2,8 @@
 // Point Feature Histograms (FPFH) for 3D Registration", ICRA 2009): the 33-bin descriptor per point that fast global
 // registration matches when there is no initial pose.
 //
-// Two passes over one neighbour list per point -- KNN(knn) or Hybrid(radius, max_nn), the list, its order and the walk over
-// the cells nn_list.h's, shared with normals.hip and color_gradient.hip:
+// Two passes over one neighbour list per point -- KNN(knn) or Hybrid(radius, max_nn); the grid and the tuning of its cells
+// are nn_grid.hip's, the search and the list nn_list.h's, shared with normals.hip and color_gradient.hip:
 //   SPFH (:72-108)   entry 0 of the list is skipped whatever index it holds, every other entry gives the four pair
 //                    features of ComputePairFeatures (:38-70), three of which are binned into 11 bins each with the
 //                    weight 100 / (len - 1); a list of length <= 1 leaves the column zero.
@@ -15,7 +15,7 @@
 // non-finite normal or coordinate reaches sums only, never an index or an address.
 //
 // One thread per point, in cell order; lists of up to kNormalsMaxList entries in LDS, nn_list_threads(cap) threads per
-// workgroup (cap = 100: 64 threads on 75 KiB, two workgroups per CU by LDS).  The second pass needs the lists again: the first pass either
+// workgroup by nn_launch (cap = 100: 64 threads on 75 KiB, two workgroups per CU by LDS).  The second pass needs the lists again: the first pass either
 // KEEPS them in global memory ([cap][n], 12 bytes per entry, read back coalesced) or the second pass REBUILDS them by the
 // same search.  Kept where they fit the budget below (measured: DESIGN.md 4.4c7, profiles/fpfh_fgr_probe.txt).
 #include "nn_list.h"
@@ -32,11 +32,7 @@ namespace {
 constexpr int kFpfhDim = 33;
 
 struct FpfhArgs {
-    const float4 *sorted;        // cell-sorted fp32 copy (cell binning only)
-    const Pt64 *sorted64;        // cell-sorted points, w = original index
-    const unsigned *start;
-    GridParams g;
-    const Pt64 *pts;             // original order
+    NnGridView view;
     const double *nrm;           // n x 3, original order
     double *spfh;                // n x 33, original order
     double *out;                 // n x 33, original order
@@ -46,7 +42,6 @@ struct FpfhArgs {
     double *keep_d2;             // kept lists: [cap][n] by query in cell order, or NULL
     int *keep_id;
     int *keep_cnt;               // n
-    unsigned long long *n27;     // (sampling pass) sum of 27-cell populations, queries counted
 };
 
 // (int)floor(v) clamped to [0, 10] as Feature.cpp:92-94 gives it on x86-64: the conversion of a NaN, an infinity or a value
@@ -122,57 +117,23 @@ __device__ __forceinline__ void fpfh_column(const FpfhArgs &a, int me, int len, 
 }
 
 // TYPE: 0 KNN, 2 Hybrid.  PASS 0: SPFH (and the lists to global memory where a.keep_d2 is set); PASS 1: the list rebuilt,
-// then FPFH; PASS 2: only count the 27-cell population of every 64th point (KNN cell-size tuning, as normals.hip).
+// then FPFH.
 template <int TYPE, int NTH, int PASS>
 __global__ __launch_bounds__(NTH) void fpfh_search_kernel(FpfhArgs a)
 {
     extern __shared__ double lds_raw[];
-    const int tid = threadIdx.x;
-    const long long t = (long long)blockIdx.x * NTH + tid;
+    const long long t = (long long)blockIdx.x * NTH + threadIdx.x;
+    // (the list's addresses before the bounds test: the kernel argument loads then merge as they did before the search moved
+    // to nn_list.h, and the search loop keeps its place in the instruction cache lines -- 4 bytes off cost 1.7 % of a pass,
+    // profiles/nn_search_ab.txt)
+    NnList L = nn_list_lds(lds_raw, threadIdx.x, NTH, a.cap);
     if (t >= a.n) return;
-    const Pt64 q = a.sorted64[t];                                 // queries in cell order
-    const float4 qf = a.sorted[t];
-    const GridParams g = a.g;
-    const int cx = cell_coord(qf.x, g.mn[0], g.inv_h, g.dim[0]);
-    const int cy = cell_coord(qf.y, g.mn[1], g.inv_hs, g.dim[1]);
-    const int cz = cell_coord(qf.z, g.mn[2], g.inv_hs, g.dim[2]);
-    if (PASS == 2) {
-        if ((t & 63) != 0) return;
-        unsigned long long tot = 0;
-        for (int dz = -1; dz <= 1; dz++)
-            for (int dy = -1; dy <= 1; dy++) {
-                const int z = cz + dz, y = cy + dy;
-                if (z < 0 || z >= g.dim[2] || y < 0 || y >= g.dim[1]) continue;
-                const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-                if (x0 > x1) continue;
-                const long long row = ((long long)z * g.dim[1] + y) * g.dim[0];
-                tot += a.start[row + x1 + 1] - a.start[row + x0];
-            }
-        atomicAdd(a.n27, tot);
-        atomicAdd(a.n27 + 1, 1ull);
-        return;
-    }
-    NnList L = nn_list_lds(lds_raw, tid, NTH, a.cap);
-    auto consider = [&](const Pt64 &p) {
-        const double d = nn_dist2(q, p);
-        if (TYPE != 0 && !(d < a.r2d)) return;                    // flann radiusSearch: strict
-        if (TYPE == 0 && d != d) return;                          // a NaN distance has no place in an ordered list
-        nn_list_insert(L, d, (int)p.w);
-    };
-    const int rmax = TYPE == 0 ? max(max(g.dim[0], g.dim[1]), g.dim[2]) : 1;
-    for (int R = 0; R <= rmax; R++) {
-        nn_scan_shell(g, a.start, a.sorted64, cx, cy, cz, R, consider);
-        if (TYPE != 0) continue;                                  // cells of edge 1.001 r: the 27 cover the radius
-        // KNN: every point nearer than R cell edges has been seen (0.1 % slack for the fp32 binning); normals.hip
-        if (L.cnt == a.cap && R >= 1) {
-            const double cover = (double)R * (double)g.h * 0.999;
-            if (L.d2[(size_t)(a.cap - 1) * L.stride] <= cover * cover) break;
-        }
-        if (cx - R <= 0 && cy - R <= 0 && cz - R <= 0 && cx + R >= g.dim[0] - 1 && cy + R >= g.dim[1] - 1 &&
-            cz + R >= g.dim[2] - 1)
-            break;                                                // the whole grid has been scanned
-    }
-    const int me = (int)q.w;
+    const NnQuery query = nn_query(a.view, t);                    // queries in cell order
+    // Hybrid: flann's radiusSearch, strict.  KNN: a NaN distance has no place in an ordered list and is dropped
+    // (normals.hip's KNN lets it in: each file keeps its own rule)
+    nn_search<TYPE == 0>(a.view, query, L, [&](double d) { return TYPE == 0 ? d == d : d < a.r2d; });
+    const Pt64 q = query.p;
+    const int me = query.me;
     if (PASS == 1) {
         fpfh_column(a, me, L.cnt, L.d2, L.id, L.stride);
         return;
@@ -191,7 +152,7 @@ __global__ __launch_bounds__(NTH) void fpfh_search_kernel(FpfhArgs a)
         const double incr = 100.0 / (double)(L.cnt - 1);
         for (int k = 1; k < L.cnt; k++) {
             const int id = L.id[(size_t)k * L.stride];
-            const Pt64 p = a.pts[id];
+            const Pt64 p = a.view.pts[id];
             const double n2[3] = {a.nrm[3ll * id], a.nrm[3ll * id + 1], a.nrm[3ll * id + 2]};
             double f[3];
             pair_features(q, n1, p, n2, f);
@@ -209,68 +170,17 @@ __global__ __launch_bounds__(256) void fpfh_from_lists_kernel(FpfhArgs a)
 {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= a.n) return;
-    const int me = (int)a.sorted64[t].w;
+    const int me = (int)a.view.sorted64[t].w;
     fpfh_column(a, me, a.keep_cnt[t], a.keep_d2 + t, a.keep_id + t, (size_t)a.n);
-}
-
-__global__ void fpfh_pack_kernel(const double *__restrict__ xyz, long long n, double cx, double cy, double cz,
-                                 float4 *__restrict__ f4, Pt64 *__restrict__ p8)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    // the fp32 copy is for BINNING only, relative to a point of the cloud (normals.hip: pack_points_kernel)
-    f4[i] = make_float4((float)(x - cx), (float)(y - cy), (float)(z - cz), __uint_as_float((unsigned)i));
-    p8[i] = Pt64{x, y, z, (unsigned long long)i};
-}
-
-struct FpfhBufs {
-    std::vector<void *> ptrs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~FpfhBufs()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1));
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return hipSuccess;
-    }
-};
-
-template <int TYPE, int NTH, int PASS>
-hipError_t launch_fpfh_nth(const FpfhArgs &a, size_t lds, hipStream_t stream)
-{
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void *)fpfh_search_kernel<TYPE, NTH, PASS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((fpfh_search_kernel<TYPE, NTH, PASS>), dim3((unsigned)((a.n + NTH - 1) / NTH)), dim3(NTH), lds, stream, a);
-    return hipGetLastError();
 }
 
 template <int TYPE, int PASS>
 hipError_t launch_fpfh(const FpfhArgs &a, hipStream_t stream)
 {
-    const int lds_cap = PASS == 2 ? 0 : a.cap;
-    const int nth = nn_list_threads(lds_cap);
-    const size_t lds = nn_list_lds_bytes(lds_cap, nth);
-    if (nth == 256) return launch_fpfh_nth<TYPE, 256, PASS>(a, lds, stream);
-    if (nth == 128) return launch_fpfh_nth<TYPE, 128, PASS>(a, lds, stream);
-    return launch_fpfh_nth<TYPE, 64, PASS>(a, lds, stream);
+    return nn_launch(a.cap, a.n, a, stream, [](auto nth) { return &fpfh_search_kernel<TYPE, decltype(nth)::value, PASS>; });
 }
 
 }  // namespace
-
-#define FPFH_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 // search_type 0 KNN(knn) | 2 Hybrid(radius, max_nn = knn); knn in [2, kNormalsMaxList].  second_pass 0: lists kept where
 // they fit, 1: kept, 2: rebuilt.  ms (may be NULL): device time of the grid build, the first and the second pass.
@@ -289,81 +199,27 @@ hipError_t compute_fpfh_device(const double *h_xyz, int64_t n, const double *h_n
         std::fill(h_out, h_out + (size_t)n * kFpfhDim, 0.0);
         return hipSuccess;
     }
-    FpfhBufs B;
+    NnGrid G;
+    DevBufs B;
+    DevEvents<4> ev;
     double *d_xyz = nullptr, *d_nrm = nullptr, *d_spfh = nullptr, *d_out = nullptr;
-    float4 *d_f4 = nullptr, *d_sorted = nullptr;
-    Pt64 *d_p8 = nullptr, *d_sorted64 = nullptr;
-    unsigned *d_box = nullptr, *d_cell_of = nullptr;
-    unsigned long long *d_n27 = nullptr;
-    FPFH_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
-    FPFH_TRY(B.alloc(&d_nrm, 3 * (size_t)n));
-    FPFH_TRY(B.alloc(&d_spfh, kFpfhDim * (size_t)n));
-    FPFH_TRY(B.alloc(&d_out, kFpfhDim * (size_t)n));
-    FPFH_TRY(B.alloc(&d_f4, (size_t)n));
-    FPFH_TRY(B.alloc(&d_sorted, (size_t)n + kSortedSlack));
-    FPFH_TRY(B.alloc(&d_p8, (size_t)n));
-    FPFH_TRY(B.alloc(&d_sorted64, (size_t)n));
-    FPFH_TRY(B.alloc(&d_box, 8));
-    FPFH_TRY(B.alloc(&d_cell_of, 2 * (size_t)n));
-    FPFH_TRY(B.alloc(&d_n27, 2));
-    for (hipEvent_t &e : B.ev) FPFH_TRY(hipEventCreate(&e));
-    FPFH_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
-    FPFH_TRY(hipMemcpyAsync(d_nrm, h_nrm, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
-    FPFH_TRY(hipEventRecord(B.ev[0], stream));
-    {
-        double c0[3] = {0.0, 0.0, 0.0};                           // a finite point of the cloud as the binning origin
-        for (int64_t i = 0; i < n; i++)
-            if (std::isfinite(h_xyz[3 * i]) && std::isfinite(h_xyz[3 * i + 1]) && std::isfinite(h_xyz[3 * i + 2])) {
-                c0[0] = h_xyz[3 * i]; c0[1] = h_xyz[3 * i + 1]; c0[2] = h_xyz[3 * i + 2];
-                break;
-            }
-        hipLaunchKernelGGL(fpfh_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz, (long long)n,
-                           c0[0], c0[1], c0[2], d_f4, d_p8);
-        FPFH_TRY(hipGetLastError());
-    }
-    FPFH_TRY(launch_grid_bbox(d_f4, n, d_box, stream));
-    unsigned box[6];
-    FPFH_TRY(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, stream));
-    FPFH_TRY(hipStreamSynchronize(stream));
-    float mn[3], mx[3];
-    grid_decode_bbox(box, mn, mx);
-    double diag = 0.0;
-    for (int k = 0; k < 3; k++) diag += ((double)mx[k] - mn[k]) * ((double)mx[k] - mn[k]);
-    diag = std::sqrt(diag);
-    // KNN: a first guess of the distance to the knn-th neighbour on a surface, refined from the measured population of
-    // the 27 cells (normals.hip); any cell size is exact, rings of cells are added until the knn-th distance is covered
-    double cell = use_r ? radius : 0.6 * diag * std::sqrt((double)cap / (double)n);
-    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
+    VISMA_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
+    VISMA_TRY(B.alloc(&d_nrm, 3 * (size_t)n));
+    VISMA_TRY(B.alloc(&d_spfh, kFpfhDim * (size_t)n));
+    VISMA_TRY(B.alloc(&d_out, kFpfhDim * (size_t)n));
+    VISMA_TRY(G.alloc(n));
+    VISMA_TRY(ev.create());
+    VISMA_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(hipMemcpyAsync(d_nrm, h_nrm, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(hipEventRecord(ev[0], stream));                     // ms[0]: from here, the uploads queued ...
+    ColorGradientInput in;
+    in.xyz = d_xyz; in.n = n;
+    nn_binning_origin(h_xyz, n, in.origin);
+    VISMA_TRY(G.build(in, nullptr, radius, use_r ? 0 : cap, stream));
     FpfhArgs a{};
-    unsigned *d_count = nullptr, *d_start = nullptr, *d_bsum = nullptr;
-    int64_t cell_cap = 0;
-    for (int attempt = 0;; attempt++) {
-        const int64_t max_cells = std::min<int64_t>(kGridMaxCells, std::max<int64_t>(4096, 8 * n));
-        const GridParams g = grid_plan(mn, mx, cell, max_cells);
-        if (g.ncell + 1 > cell_cap) {
-            FPFH_TRY(B.alloc(&d_count, (size_t)g.ncell + 1));
-            FPFH_TRY(B.alloc(&d_start, (size_t)g.ncell + 9));
-            FPFH_TRY(B.alloc(&d_bsum, (size_t)grid_scan_blocks(g.ncell) + 1));
-            cell_cap = g.ncell + 1;
-        }
-        FPFH_TRY(launch_grid_build(d_f4, n, g, d_cell_of, d_count, d_bsum, d_start, d_sorted, stream, d_p8, d_sorted64));
-        a.sorted = d_sorted; a.sorted64 = d_sorted64; a.start = d_start; a.g = g; a.pts = d_p8; a.nrm = d_nrm;
-        a.spfh = d_spfh; a.out = d_out; a.n = (int)n; a.cap = cap; a.n27 = d_n27;
-        const float r2f = (float)(radius * radius);
-        a.r2d = (double)r2f;
-        if (use_r || attempt >= 3) break;
-        FPFH_TRY(hipMemsetAsync(d_n27, 0, 2 * sizeof(unsigned long long), stream));
-        FPFH_TRY((launch_fpfh<0, 2>(a, stream)));
-        unsigned long long h27[2];
-        FPFH_TRY(hipMemcpyAsync(h27, d_n27, sizeof(h27), hipMemcpyDeviceToHost, stream));
-        FPFH_TRY(hipStreamSynchronize(stream));
-        const double mean27 = h27[1] ? (double)h27[0] / h27[1] : 0.0, want = 2.5 * cap;
-        if (mean27 >= 0.6 * want && mean27 <= 2.5 * want) break;
-        const double f = mean27 > 0.0 ? std::sqrt(want / mean27) : 2.0;
-        const double next = cell * std::min(std::max(f, 0.25), 4.0);
-        if (g.h > (float)(cell * 1.01) && next < cell) break;              // the cell cap already enlarged the cells
-        cell = next;
-    }
+    a.view = G.view;
+    a.nrm = d_nrm; a.spfh = d_spfh; a.out = d_out; a.n = (int)n; a.cap = cap;
+    a.r2d = nn_radius2(radius);
     // the lists kept for the second pass: n * cap * 12 bytes, within 1 GiB and half of what the device has free
     bool keep = second_pass != 2;
     const size_t entries = (size_t)n * (size_t)cap;
@@ -373,29 +229,29 @@ hipError_t compute_fpfh_device(const double *h_xyz, int64_t n, const double *h_n
         keep = entries * kNnListEntryBytes <= budget;
     }
     if (keep) {
-        FPFH_TRY(B.alloc(&a.keep_d2, entries));
-        FPFH_TRY(B.alloc(&a.keep_id, entries));
-        FPFH_TRY(B.alloc(&a.keep_cnt, (size_t)n));
+        VISMA_TRY(B.alloc(&a.keep_d2, entries));
+        VISMA_TRY(B.alloc(&a.keep_id, entries));
+        VISMA_TRY(B.alloc(&a.keep_cnt, (size_t)n));
     }
-    FPFH_TRY(hipEventRecord(B.ev[1], stream));
-    if (use_r) FPFH_TRY((launch_fpfh<2, 0>(a, stream)));
-    else FPFH_TRY((launch_fpfh<0, 0>(a, stream)));
-    FPFH_TRY(hipEventRecord(B.ev[2], stream));
+    VISMA_TRY(hipEventRecord(ev[1], stream));
+    if (use_r) VISMA_TRY((launch_fpfh<2, 0>(a, stream)));
+    else VISMA_TRY((launch_fpfh<0, 0>(a, stream)));
+    VISMA_TRY(hipEventRecord(ev[2], stream));
     if (keep) {
         hipLaunchKernelGGL(fpfh_from_lists_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-        FPFH_TRY(hipGetLastError());
+        VISMA_TRY(hipGetLastError());
     } else if (use_r) {
-        FPFH_TRY((launch_fpfh<2, 1>(a, stream)));
+        VISMA_TRY((launch_fpfh<2, 1>(a, stream)));
     } else {
-        FPFH_TRY((launch_fpfh<0, 1>(a, stream)));
+        VISMA_TRY((launch_fpfh<0, 1>(a, stream)));
     }
-    FPFH_TRY(hipEventRecord(B.ev[3], stream));
-    FPFH_TRY(hipMemcpyAsync(h_out, d_out, sizeof(double) * kFpfhDim * (size_t)n, hipMemcpyDeviceToHost, stream));
-    FPFH_TRY(hipStreamSynchronize(stream));
+    VISMA_TRY(hipEventRecord(ev[3], stream));
+    VISMA_TRY(hipMemcpyAsync(h_out, d_out, sizeof(double) * kFpfhDim * (size_t)n, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
     if (ms)
         for (int k = 0; k < 3; k++) {
             float t = 0.f;
-            FPFH_TRY(hipEventElapsedTime(&t, B.ev[k], B.ev[k + 1]));
+            VISMA_TRY(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
             ms[k] = (double)t;
         }
     return hipSuccess;

@@ -7,6 +7,45 @@
 
 namespace visma {
 
+// ---- the device memory and events of one host-in, host-out call (the neighbourhood features, feature_match.hip, ransac.hip)
+#define VISMA_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+// every allocation is freed with the object
+struct DevBufs {
+    std::vector<void *> ptrs;
+    DevBufs() = default;
+    DevBufs(const DevBufs &) = delete;
+    DevBufs &operator=(const DevBufs &) = delete;
+    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
+    template <class T>
+    hipError_t alloc(T **out, size_t count)
+    {
+        void *p = nullptr;
+        VISMA_TRY(hipMalloc(&p, sizeof(T) * (count ? count : 1)));
+        ptrs.push_back(p);
+        *out = (T *)p;
+        return hipSuccess;
+    }
+};
+// ... and N events for the calls that report device time
+template <int N>
+struct DevEvents {
+    hipEvent_t ev[N] = {};
+    DevEvents() = default;
+    DevEvents(const DevEvents &) = delete;
+    DevEvents &operator=(const DevEvents &) = delete;
+    ~DevEvents()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create()
+    {
+        for (hipEvent_t &e : ev) VISMA_TRY(hipEventCreate(&e));
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return ev[k]; }
+};
+
 // ---- compile-time tile constants (reported by visma_icp_get_tile_config) ----
 constexpr int kBlock = 256;         // threads per workgroup (4 wave64)
 constexpr int kSptLarge = 8;        // source points per thread, large clouds
@@ -738,6 +777,37 @@ struct ColorGradientInput {
     int64_t n = 0;
     double origin[3] = {0.0, 0.0, 0.0};
 };
+// ---- the grid of ONE cloud that normals.hip, color_gradient.hip and fpfh.hip search (nn_grid.hip; the search: nn_list.h) ----
+// what each of their kernels is given first
+struct NnGridView {
+    const float4 *sorted;        // cell-sorted fp32 copy (cell binning only)
+    const Pt64 *sorted64;        // cell-sorted points, w = original index
+    const unsigned *start;       // cell table
+    GridParams g;
+    const Pt64 *pts;             // original order
+};
+// The first finite point of the cloud, the origin of the fp32 binning copy; `origin` stays as it is where there is none.
+void nn_binning_origin(const double *h_xyz, int64_t n, double origin[3]);
+// The grid and its buffers, freed with the object.  knn_cap == 0: cells of edge 1.001 `radius`, the 27 cells around a point
+// cover the radius.  knn_cap > 0 (a KNN search of that many neighbours, `radius` unused): cells of about the distance to the
+// knn_cap-th neighbour, sized from the measured population of the 27 cells -- any size is exact there.
+struct NnGrid {
+    NnGridView view{};
+    // the buffers that depend on n alone (the cell table's are build's own)
+    hipError_t alloc(int64_t n);
+    // Points from whichever of the three forms `in` holds; d_nrm3 != NULL: its Pt64 or float4 normals repacked there as
+    // n x 3 doubles.  The last grid build is still queued when it returns.
+    hipError_t build(const ColorGradientInput &in, double *d_nrm3, double radius, int knn_cap, hipStream_t stream);
+
+    // (build's own)
+    DevBufs bufs;
+    int64_t n = 0;
+    float4 *f4 = nullptr, *sorted = nullptr;
+    Pt64 *p8 = nullptr, *sorted64 = nullptr;
+    unsigned *box = nullptr, *cell_of = nullptr;
+    unsigned long long *n27 = nullptr;       // (KNN) sum of the sampled 27-cell populations, points sampled
+};
+
 // the gradient per point (n x 3 doubles on the device, the points' order) by the Hybrid search (radius, max_nn);
 // max_nn outside [3, kNormalsMaxList]: hipErrorInvalidValue.  Returns with the stream idle.
 hipError_t color_gradient_on_device(const ColorGradientInput &in, double radius, int max_nn, double *d_grad, hipStream_t stream);

@@ -1,10 +1,17 @@
-// nn_list.h -- the neighbour list of one query point on the radius-cell grid of grid.hip, in the order of the reference's
-// KDTreeFlann result list: ascending (d2, index), flann's sum of squares in f64.  One thread per query; the list lives
-// in LDS as [cap][threads] (element j of thread t at j * threads + t), squared distances first, indices behind them.
-// Shared by normals.hip (KNN / Hybrid / the counting pass; its lists beyond the LDS live in a heap of its own) and
-// color_gradient.hip (Hybrid).
+// nn_list.h -- the neighbour search of one query point on the radius-cell grid of grid.hip, as normals.hip, color_gradient.hip
+// and fpfh.hip run it: one thread per point in cell order over the grid of one cloud (nn_grid.hip builds it: NnGrid), the
+// result in the order of the reference's KDTreeFlann result list: ascending (d2, index), flann's sum of squares in f64.
+//   NnGridView, nn_query   what every such kernel is given first, and the query of thread t
+//   NnList                 the list in LDS as [cap][threads] (element j of thread t at j * threads + t), squared distances
+//                          first, indices behind them; kept sorted
+//   NnHeap                 the same surface over global memory: a max-heap while the search runs, sorted at the end
+//   nn_search              the walk over the rings of cells; which distances enter the list is the caller's `accept`
+//   nn_launch              threads per workgroup by the LDS the lists take, the kernel instantiated for them
+// What a kernel does with its list -- moments, gradient rows, histograms -- is its own file's.
 #pragma once
 #include "device_common.h"
+
+#include <type_traits>
 
 namespace visma {
 
@@ -21,13 +28,99 @@ inline int nn_list_threads(int cap)
 }
 inline size_t nn_list_lds_bytes(int cap, int nth) { return (size_t)cap * kNnListEntryBytes * nth + 64; }
 
+// the bound of flann's radiusSearch: r * r rounded to fp32 (KDTreeFlann.cpp:157-158, 184-185)
+inline double nn_radius2(double radius) { return (double)(float)(radius * radius); }
+
 #ifdef __HIPCC__
-struct NnList {
-    double *d2;                  // element j at d2[j * stride]
+// One workgroup of `queries` / NTH per NTH queries, NTH = nn_list_threads(lds_cap) and the dynamic LDS its lists take
+// (lds_cap = 0: the kernel keeps no list there).  kernel_of(std::integral_constant<int, NTH>) returns the kernel's
+// instantiation for NTH threads.
+template <class Args, class KernelOf>
+hipError_t nn_launch(int lds_cap, long long queries, const Args &a, hipStream_t stream, KernelOf kernel_of)
+{
+    if (queries <= 0) return hipSuccess;
+    const int nth = nn_list_threads(lds_cap);
+    const size_t lds = nn_list_lds_bytes(lds_cap, nth);
+    auto launch = [&](auto nth_c) -> hipError_t {
+        constexpr int NTH = decltype(nth_c)::value;
+        void (*const kernel)(Args) = kernel_of(nth_c);
+        if (lds > 48 * 1024)
+            VISMA_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((queries + NTH - 1) / NTH)), dim3(NTH), lds, stream, a);
+        return hipGetLastError();
+    };
+    if (nth == 256) return launch(std::integral_constant<int, 256>{});
+    if (nth == 128) return launch(std::integral_constant<int, 128>{});
+    return launch(std::integral_constant<int, 64>{});
+}
+
+// the query of thread t (cell order): the point, its cell, its index in the caller's order
+struct NnQuery {
+    Pt64 p;
+    int cx, cy, cz;
+    int me;
+};
+__device__ __forceinline__ NnQuery nn_query(const NnGridView &v, long long t)
+{
+    NnQuery q;
+    q.p = v.sorted64[t];
+    const float4 qf = v.sorted[t];
+    q.cx = cell_coord(qf.x, v.g.mn[0], v.g.inv_h, v.g.dim[0]);
+    q.cy = cell_coord(qf.y, v.g.mn[1], v.g.inv_hs, v.g.dim[1]);
+    q.cz = cell_coord(qf.z, v.g.mn[2], v.g.inv_hs, v.g.dim[2]);
+    q.me = (int)q.p.w;
+    return q;
+}
+
+// flann L2 (dist.h:159-176): result += diff * diff over x, y, z
+__device__ __forceinline__ double nn_dist2(const Pt64 &q, const Pt64 &p)
+{
+    const double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
+    double d = dx * dx;
+    d += dy * dy;
+    d += dz * dz;
+    return d;
+}
+
+// `cnt` of `cap` entries (d2, id), entry j at [j * stride]: what NnList and NnHeap keep, each in its own order
+struct NnEntries {
+    double *d2;
     int *id;
     size_t stride;
     int cap;
     int cnt = 0;
+
+    __device__ __forceinline__ void set(int j, double d, int i) { d2[(size_t)j * stride] = d; id[(size_t)j * stride] = i; }
+    __device__ __forceinline__ void move(int to, int from)
+    {
+        d2[(size_t)to * stride] = d2[(size_t)from * stride];
+        id[(size_t)to * stride] = id[(size_t)from * stride];
+    }
+    // (d, i) before entry j
+    __device__ __forceinline__ bool less(double d, int i, int j) const
+    {
+        const double dj = d2[(size_t)j * stride];
+        return d < dj || (d == dj && i < id[(size_t)j * stride]);
+    }
+};
+
+// the sorted list: ascending (d2, id) at any time
+struct NnList : NnEntries {
+    // keep the cap nearest: insertion into the sorted list, the farthest entry dropped when it is full
+    __device__ __forceinline__ void insert(double d, int i)
+    {
+        int pos;
+        if (cnt < cap) pos = cnt++;
+        else if (less(d, i, cap - 1)) pos = cap - 1;
+        else return;
+        while (pos > 0 && less(d, i, pos - 1)) {
+            move(pos, pos - 1);
+            pos--;
+        }
+        set(pos, d, i);
+    }
+    // of a full list
+    __device__ __forceinline__ double farthest() const { return d2[(size_t)(cap - 1) * stride]; }
 };
 
 // the list of thread `tid` of `nth` in the workgroup's dynamic LDS
@@ -41,37 +134,62 @@ __device__ __forceinline__ NnList nn_list_lds(double *lds_raw, int tid, int nth,
     return l;
 }
 
-// flann L2 (dist.h:159-176): result += diff * diff over x, y, z
-__device__ __forceinline__ double nn_dist2(const Pt64 &q, const Pt64 &p)
-{
-    const double dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;
-    double d = dx * dx;
-    d += dy * dy;
-    d += dz * dz;
-    return d;
-}
-
-// (d, id) before entry j
-__device__ __forceinline__ bool nn_list_less(const NnList &l, double d, int id, int j)
-{
-    const double dj = l.d2[(size_t)j * l.stride];
-    return d < dj || (d == dj && id < l.id[(size_t)j * l.stride]);
-}
-
-// keep the cap nearest: insertion into the sorted list, the farthest entry dropped when it is full
-__device__ __forceinline__ void nn_list_insert(NnList &l, double d, int id)
-{
-    int pos;
-    if (l.cnt < l.cap) pos = l.cnt++;
-    else if (nn_list_less(l, d, id, l.cap - 1)) pos = l.cap - 1;
-    else return;
-    while (pos > 0 && nn_list_less(l, d, id, pos - 1)) {
-        l.d2[(size_t)pos * l.stride] = l.d2[(size_t)(pos - 1) * l.stride];
-        l.id[(size_t)pos * l.stride] = l.id[(size_t)(pos - 1) * l.stride];
-        pos--;
+// the max-heap on (d2, id): the root is the entry a nearer candidate replaces; sort() then leaves the order of NnList
+struct NnHeap : NnEntries {
+    // (d, i) into the hole at `pos` of a heap of `len`: larger children move up
+    __device__ __forceinline__ void sift_down(int pos, int len, double d, int i)
+    {
+        for (;;) {
+            int ch = 2 * pos + 1;
+            if (ch >= len) break;
+            if (ch + 1 < len && less(d2[(size_t)ch * stride], id[(size_t)ch * stride], ch + 1)) ch++;
+            if (!less(d, i, ch)) break;
+            move(pos, ch);
+            pos = ch;
+        }
+        set(pos, d, i);
     }
-    l.d2[(size_t)pos * l.stride] = d;
-    l.id[(size_t)pos * l.stride] = id;
+    __device__ __forceinline__ void insert(double d, int i)
+    {
+        if (cnt < cap) {
+            // sift up: parents smaller than the new entry move down
+            int pos = cnt++;
+            while (pos > 0) {
+                const int par = (pos - 1) >> 1;
+                const double dp = d2[(size_t)par * stride];
+                const int ip = id[(size_t)par * stride];
+                if (!(dp < d || (dp == d && ip < i))) break;
+                set(pos, dp, ip);
+                pos = par;
+            }
+            set(pos, d, i);
+        } else if (less(d, i, 0)) {
+            sift_down(0, cap, d, i);
+        }
+    }
+    // of a full heap
+    __device__ __forceinline__ double farthest() const { return d2[0]; }
+    // heap sort in place: ascending (d2, id) = the order of the reference's result list
+    __device__ __forceinline__ void sort()
+    {
+        for (int end = cnt - 1; end > 0; end--) {
+            const double dl = d2[(size_t)end * stride];
+            const int il = id[(size_t)end * stride];
+            move(end, 0);
+            sift_down(0, end, dl, il);
+        }
+    }
+};
+
+// the heap of query `u` of a slab of `queries`, in global memory as [cap][queries] (coalesced across threads)
+__device__ __forceinline__ NnHeap nn_heap_global(double *d2, int *id, long long u, int queries, int cap)
+{
+    NnHeap l;
+    l.d2 = d2 + u;
+    l.id = id + u;
+    l.stride = (size_t)queries;
+    l.cap = cap;
+    return l;
 }
 
 // cells xa..xb of row (y, z), clipped: consider(point) for every point in them
@@ -100,6 +218,34 @@ __device__ __forceinline__ void nn_scan_shell(const GridParams &g, const unsigne
                 nn_scan_cells(g, start, sorted64, cz + dz, cy + dy, cx + R, cx + R, consider);
             }
         }
+}
+
+// Every point of the cells around q whose squared distance d passes accept(d) goes to list.insert(d, index).
+//   KNN = false  cells of edge 1.001 r: the 27 cells (rings 0 and 1) cover the radius, `accept` holds the radius test
+//   KNN = true   any cell size: rings are added until the list is full and its farthest entry lies within the rings
+//                scanned (0.1 % slack for the fp32 binning), or the whole grid has been scanned
+// `list` needs insert and, for KNN, cnt, cap and farthest: NnList, NnHeap, or a caller's own that only counts.
+template <bool KNN, class List, class Accept>
+__device__ __forceinline__ void nn_search(const NnGridView &v, const NnQuery &q, List &list, Accept accept)
+{
+    const GridParams g = v.g;
+    auto consider = [&](const Pt64 &p) {
+        const double d = nn_dist2(q.p, p);
+        if (accept(d)) list.insert(d, (int)p.w);
+    };
+    const int rmax = KNN ? max(max(g.dim[0], g.dim[1]), g.dim[2]) : 1;
+    for (int R = 0; R <= rmax; R++) {
+        nn_scan_shell(g, v.start, v.sorted64, q.cx, q.cy, q.cz, R, consider);
+        if constexpr (KNN) {
+            if (list.cnt == list.cap && R >= 1) {
+                const double cover = (double)R * (double)g.h * 0.999;
+                if (list.farthest() <= cover * cover) break;
+            }
+            if (q.cx - R <= 0 && q.cy - R <= 0 && q.cz - R <= 0 && q.cx + R >= g.dim[0] - 1 && q.cy + R >= g.dim[1] - 1 &&
+                q.cz + R >= g.dim[2] - 1)
+                break;                                              // the whole grid has been scanned
+        }
+    }
 }
 #endif  // __HIPCC__
 

@@ -21,7 +21,9 @@
 // heap-sorted at the end: any knn / max_nn.  Radius searches (no bound on the list) first COUNT every point's
 // neighbours, then run as a Hybrid search whose max_nn is the largest count: the moments are summed in list order
 // like the reference's (round 2 summed them in scan order: 3e-7 off where two eigenvalues nearly coincide).
-// The LDS-resident list, its order and the walk over the cells are nn_list.h's (shared with color_gradient.hip).
+// The grid of the cloud and the tuning of its cells are nn_grid.hip's, the walk over the cells and both kinds of list
+// nn_list.h's (shared with color_gradient.hip and fpfh.hip); which distances enter a list, the counting pass, the runs
+// and the slabs of heaps are this file's.
 #include "nn_list.h"
 
 #include <math.h>
@@ -34,17 +36,12 @@ namespace visma {
 namespace {
 
 struct NormalArgs {
-    const float4 *sorted;        // cell-sorted fp32 copy (cell binning only)
-    const Pt64 *sorted64;        // cell-sorted points, w = original index
-    const unsigned *start;
-    GridParams g;
-    const Pt64 *pts;             // original order
+    NnGridView view;
     const double *nrm_in;        // n x 3 or NULL
     double *nrm_out;             // n x 3
     int n;
     int cap;                     // list capacity (knn / max_nn); unused for Radius
     double r2d;                  // (double)(float)(r * r); unused for KNN
-    unsigned long long *n27;     // (sampling pass) sum of 27-cell populations, queries counted
     int *count_out;              // (counting pass) neighbours within the radius, per point in cell order
     double *spill_d2;            // (spilled lists) [cap][q_count] squared distances ...
     int *spill_id;               // ... and indices, one max-heap per query of the slab
@@ -99,128 +96,21 @@ __device__ bool fast_eigen_3x3(const double A[3][3], double out[3])
     return true;
 }
 
-// TYPE: 0 KNN, 1 Radius (counting pass only), 2 Hybrid.  MODE 1: only count the 27-cell population of every
-// 64th point (cell-size tuning); MODE 2: only count the neighbours within the radius.  SPILL: the list is a
-// max-heap in global memory instead of a sorted array in LDS.
-template <int TYPE, int NTH, int MODE, bool SPILL>
-__global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
+// the normal of point `me` from its list in the reference's order (EstimateNormals.cpp:86-149)
+__device__ __forceinline__ void normal_from_list(const NormalArgs &a, int me, const NnEntries &L)
 {
-    constexpr bool SAMPLE = MODE == 1, COUNT = MODE == 2;
-    extern __shared__ double lds_raw[];
-    const int tid = threadIdx.x;
-    const long long u = (long long)blockIdx.x * NTH + tid;          // query of the slab
-    if (u >= a.q_count) return;
-    const long long t = a.q_begin + u;
-    // element j of this thread's list: LDS [cap][NTH] or global [cap][q_count] (coalesced across threads)
-    double *ld2 = SPILL ? a.spill_d2 + u : lds_raw + tid;
-    int *lid = SPILL ? a.spill_id + u : reinterpret_cast<int *>(lds_raw + (size_t)a.cap * NTH) + tid;
-    const size_t lstride = SPILL ? (size_t)a.q_count : (size_t)NTH;
-    const Pt64 q = a.sorted64[t];                                 // queries in cell order
-    const float4 qf = a.sorted[t];
-    const GridParams g = a.g;
-    const int cx = cell_coord(qf.x, g.mn[0], g.inv_h, g.dim[0]);
-    const int cy = cell_coord(qf.y, g.mn[1], g.inv_hs, g.dim[1]);
-    const int cz = cell_coord(qf.z, g.mn[2], g.inv_hs, g.dim[2]);
-    if (SAMPLE) {
-        if ((t & 63) != 0) return;
-        unsigned long long tot = 0;
-        for (int dz = -1; dz <= 1; dz++)
-            for (int dy = -1; dy <= 1; dy++) {
-                const int z = cz + dz, y = cy + dy;
-                if (z < 0 || z >= g.dim[2] || y < 0 || y >= g.dim[1]) continue;
-                const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-                const long long row = ((long long)z * g.dim[1] + y) * g.dim[0];
-                tot += a.start[row + x1 + 1] - a.start[row + x0];
-            }
-        atomicAdd(a.n27, tot);
-        atomicAdd(a.n27 + 1, 1ull);
-        return;
-    }
-    NnList L;                                                     // (SPILL: the same fields address the heap)
-    L.d2 = ld2; L.id = lid; L.stride = lstride; L.cap = a.cap;
-    int &cnt = L.cnt;
-    double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    auto moments = [&](const double x, const double y, const double z) {
-        // EstimateNormals.cpp:95-105
-        c[0] += x; c[1] += y; c[2] += z;
-        c[3] += x * x; c[4] += x * y; c[5] += x * z;
-        c[6] += y * y; c[7] += y * z; c[8] += z * z;
-    };
-    auto less = [&](double d, int id, int j) { return nn_list_less(L, d, id, j); };
-    // (SPILL) max-heap on (d2, index): the root is the entry a nearer candidate replaces
-    auto sift_down = [&](int pos, int len, double d, int id) {
-        for (;;) {
-            int ch = 2 * pos + 1;
-            if (ch >= len) break;
-            if (ch + 1 < len && less(ld2[(size_t)ch * lstride], lid[(size_t)ch * lstride], ch + 1)) ch++;
-            if (!less(d, id, ch)) break;
-            ld2[(size_t)pos * lstride] = ld2[(size_t)ch * lstride];
-            lid[(size_t)pos * lstride] = lid[(size_t)ch * lstride];
-            pos = ch;
-        }
-        ld2[(size_t)pos * lstride] = d;
-        lid[(size_t)pos * lstride] = id;
-    };
-    auto consider = [&](const Pt64 &p) {
-        const double d = nn_dist2(q, p);
-        if (TYPE != 0 && !(d < a.r2d)) return;
-        if (COUNT) { cnt++; return; }
-        const int id = (int)p.w;
-        if (SPILL) {
-            if (cnt < a.cap) {
-                // sift up: parents smaller than the new entry move down
-                int pos = cnt++;
-                while (pos > 0) {
-                    const int par = (pos - 1) >> 1;
-                    const double dp = ld2[(size_t)par * lstride];
-                    const int ip = lid[(size_t)par * lstride];
-                    if (!(dp < d || (dp == d && ip < id))) break;
-                    ld2[(size_t)pos * lstride] = dp;
-                    lid[(size_t)pos * lstride] = ip;
-                    pos = par;
-                }
-                ld2[(size_t)pos * lstride] = d;
-                lid[(size_t)pos * lstride] = id;
-            } else if (less(d, id, 0)) {
-                sift_down(0, a.cap, d, id);
-            }
-            return;
-        }
-        nn_list_insert(L, d, id);
-    };
-    const int rmax = TYPE == 0 ? max(max(g.dim[0], g.dim[1]), g.dim[2]) : 1;
-    for (int R = 0; R <= rmax; R++) {
-        nn_scan_shell(g, a.start, a.sorted64, cx, cy, cz, R, consider);
-        if (TYPE != 0) continue;
-        // every point nearer than R cell edges has been seen (0.1 % slack for the fp32 binning)
-        if (cnt == a.cap && R >= 1) {
-            const double cover = (double)R * (double)g.h * 0.999;
-            const double farthest = ld2[(size_t)(SPILL ? 0 : a.cap - 1) * lstride];      // heap root / end of the sorted list
-            if (farthest <= cover * cover) break;
-        }
-        if (cx - R <= 0 && cy - R <= 0 && cz - R <= 0 && cx + R >= g.dim[0] - 1 && cy + R >= g.dim[1] - 1 &&
-            cz + R >= g.dim[2] - 1)
-            break;                                                  // the whole grid has been scanned
-    }
-    if (COUNT) { a.count_out[t] = cnt; return; }
-    const int me = (int)q.w;
     double nrm[3] = {0.0, 0.0, 1.0};                                // fewer than 3 neighbours (:147-149)
-    if (cnt >= 3) {
-        if (SPILL) {
-            // heap sort in place: ascending (d2, index) = the order of the reference's result list
-            for (int end = cnt - 1; end > 0; end--) {
-                const double dl = ld2[(size_t)end * lstride];
-                const int il = lid[(size_t)end * lstride];
-                ld2[(size_t)end * lstride] = ld2[0];
-                lid[(size_t)end * lstride] = lid[0];
-                sift_down(0, end, dl, il);
-            }
+    if (L.cnt >= 3) {
+        double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int j = 0; j < L.cnt; j++) {
+            // EstimateNormals.cpp:95-105
+            const Pt64 p = a.view.pts[L.id[(size_t)j * L.stride]];
+            const double x = p.x, y = p.y, z = p.z;
+            c[0] += x; c[1] += y; c[2] += z;
+            c[3] += x * x; c[4] += x * y; c[5] += x * z;
+            c[6] += y * y; c[7] += y * z; c[8] += z * z;
         }
-        for (int j = 0; j < cnt; j++) {
-            const Pt64 p = a.pts[lid[(size_t)j * lstride]];
-            moments(p.x, p.y, p.z);
-        }
-        const double inv = (double)cnt;
+        const double inv = (double)L.cnt;
         for (int k = 0; k < 9; k++) c[k] /= inv;
         double A[3][3];
         A[0][0] = c[3] - c[0] * c[0];
@@ -244,63 +134,51 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
     a.nrm_out[3ll * me + 2] = nrm[2];
 }
 
-// The fp32 copy is used for BINNING only and is taken relative to a point of the cloud (subtracted in f64): its
-// rounding error then scales with the cloud's extent, not with its distance from the origin -- a scan 100 m from
-// the origin with a 5 mm radius would otherwise put neighbours one cell off (0.1 % slack between cell and radius).
-// Distances and moments use the caller's f64 coordinates, so the results do not depend on the shift.
-__global__ void pack_points_kernel(const double *__restrict__ xyz, long long n, double cx, double cy, double cz,
-                                   float4 *__restrict__ f4, Pt64 *__restrict__ p8)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    f4[i] = make_float4((float)(x - cx), (float)(y - cy), (float)(z - cz), __uint_as_float((unsigned)i));
-    p8[i] = Pt64{x, y, z, (unsigned long long)i};
-}
-
-struct DevBufs {
-    std::vector<void *> ptrs;
-    ~DevBufs() { for (void *p : ptrs) (void)hipFree(p); }
-    template <class T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1));
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return hipSuccess;
-    }
+// the "list" of the Radius counting pass
+struct NnCount {
+    int cnt = 0;
+    __device__ __forceinline__ void insert(double, int) { cnt++; }
 };
 
-template <int TYPE, int MODE, bool SPILL>
+// TYPE: 0 KNN, 1 Radius (counting pass only), 2 Hybrid.  COUNT: only count the neighbours within the radius.  SPILL: the
+// list is a max-heap in global memory instead of a sorted array in LDS.
+template <int TYPE, int NTH, bool COUNT, bool SPILL>
+__global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
+{
+    extern __shared__ double lds_raw[];
+    const long long u = (long long)blockIdx.x * NTH + threadIdx.x;  // query of the slab
+    if (u >= a.q_count) return;
+    const long long t = a.q_begin + u;
+    const NnQuery q = nn_query(a.view, t);                          // queries in cell order
+    // Radius / Hybrid: flann's radiusSearch, strict (false for a NaN).  KNN: EVERY distance enters the list, a NaN too: it
+    // then sits at the list's end and blocks replacement once the list is full.  fpfh.hip drops such a distance; which of
+    // the two the reference does is not pinned yet, so this file keeps what it always did.
+    auto accept = [&](double d) { return TYPE == 0 || d < a.r2d; };
+    if constexpr (COUNT) {
+        NnCount L;
+        nn_search<false>(a.view, q, L, accept);
+        a.count_out[t] = L.cnt;
+    } else if constexpr (SPILL) {
+        NnHeap L = nn_heap_global(a.spill_d2, a.spill_id, u, a.q_count, a.cap);
+        nn_search<TYPE == 0>(a.view, q, L, accept);
+        if (L.cnt >= 3) L.sort();
+        normal_from_list(a, q.me, L);
+    } else {
+        NnList L = nn_list_lds(lds_raw, threadIdx.x, NTH, a.cap);
+        nn_search<TYPE == 0>(a.view, q, L, accept);
+        normal_from_list(a, q.me, L);
+    }
+}
+
+template <int TYPE, bool COUNT, bool SPILL>
 hipError_t launch_normals(const NormalArgs &a, hipStream_t stream)
 {
-    // LDS lists only: the workgroup size and the bytes its lists take (nn_list.h)
-    const int lds_cap = (MODE != 0 || SPILL) ? 0 : a.cap;
-    const int nth = nn_list_threads(lds_cap);
-    const size_t lds = nn_list_lds_bytes(lds_cap, nth);
-    const unsigned blocks = (unsigned)((a.q_count + nth - 1) / nth);
-    if (a.q_count <= 0) return hipSuccess;
-#define VISMA_NRM_LAUNCH(NTH_)                                                                                  \
-    do {                                                                                                        \
-        if (lds > 48 * 1024) {                                                                                  \
-            hipError_t e = hipFuncSetAttribute((const void *)estimate_normals_kernel<TYPE, NTH_, MODE, SPILL>,  \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-            if (e != hipSuccess) return e;                                                                      \
-        }                                                                                                       \
-        hipLaunchKernelGGL((estimate_normals_kernel<TYPE, NTH_, MODE, SPILL>), dim3(blocks), dim3(NTH_), lds, stream, a); \
-    } while (0)
-    if (nth == 256) VISMA_NRM_LAUNCH(256);
-    else if (nth == 128) VISMA_NRM_LAUNCH(128);
-    else VISMA_NRM_LAUNCH(64);
-#undef VISMA_NRM_LAUNCH
-    return hipGetLastError();
+    // only lists in LDS size the workgroup
+    return nn_launch((COUNT || SPILL) ? 0 : a.cap, a.q_count, a, stream,
+                     [](auto nth) { return &estimate_normals_kernel<TYPE, decltype(nth)::value, COUNT, SPILL>; });
 }
 
 }  // namespace
-
-#define NRM_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 // search_type 0 KNN(knn) | 1 Radius(radius) | 2 Hybrid(radius, knn = max_nn); h_nrm_in may be NULL
 hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double *h_nrm_in, int search_type,
@@ -316,94 +194,37 @@ hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double 
         return hipSuccess;
     }
     int cap = search_type == 1 ? 1 : (int)std::min<int64_t>(knn, n);           // (Radius: set from the counting pass)
+    NnGrid G;
     DevBufs B;
     double *d_xyz = nullptr, *d_nin = nullptr, *d_out = nullptr;
-    float4 *d_f4 = nullptr, *d_sorted = nullptr;
-    Pt64 *d_p8 = nullptr, *d_sorted64 = nullptr;
-    unsigned *d_box = nullptr, *d_cell_of = nullptr;
-    unsigned long long *d_n27 = nullptr;
-    NRM_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
-    NRM_TRY(B.alloc(&d_out, 3 * (size_t)n));
-    NRM_TRY(B.alloc(&d_f4, (size_t)n));
-    NRM_TRY(B.alloc(&d_sorted, (size_t)n + kSortedSlack));
-    NRM_TRY(B.alloc(&d_p8, (size_t)n));
-    NRM_TRY(B.alloc(&d_sorted64, (size_t)n));
-    NRM_TRY(B.alloc(&d_box, 8));
-    NRM_TRY(B.alloc(&d_cell_of, 2 * (size_t)n));   // (cell, rank in the cell)
-    NRM_TRY(B.alloc(&d_n27, 2));
+    VISMA_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
+    VISMA_TRY(B.alloc(&d_out, 3 * (size_t)n));
+    VISMA_TRY(G.alloc(n));
     if (h_nrm_in) {
-        NRM_TRY(B.alloc(&d_nin, 3 * (size_t)n));
-        NRM_TRY(hipMemcpyAsync(d_nin, h_nrm_in, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+        VISMA_TRY(B.alloc(&d_nin, 3 * (size_t)n));
+        VISMA_TRY(hipMemcpyAsync(d_nin, h_nrm_in, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
     }
-    NRM_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
-    {
-        // a finite point of the cloud as the binning origin
-        double c0[3] = {0.0, 0.0, 0.0};
-        for (int64_t i = 0; i < n; i++)
-            if (std::isfinite(h_xyz[3 * i]) && std::isfinite(h_xyz[3 * i + 1]) && std::isfinite(h_xyz[3 * i + 2])) {
-                c0[0] = h_xyz[3 * i]; c0[1] = h_xyz[3 * i + 1]; c0[2] = h_xyz[3 * i + 2];
-                break;
-            }
-        hipLaunchKernelGGL(pack_points_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_xyz,
-                           (long long)n, c0[0], c0[1], c0[2], d_f4, d_p8);
-    }
-    NRM_TRY(launch_grid_bbox(d_f4, n, d_box, stream));
-    unsigned box[6];
-    NRM_TRY(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, stream));
-    NRM_TRY(hipStreamSynchronize(stream));
-    float mn[3], mx[3];
-    grid_decode_bbox(box, mn, mx);
-    double diag = 0.0;
-    for (int k = 0; k < 3; k++) diag += ((double)mx[k] - mn[k]) * ((double)mx[k] - mn[k]);
-    diag = std::sqrt(diag);
-    // KNN: a first guess of the distance to the knn-th neighbour on a surface; refined below from
-    // the measured population of the 27 cells
-    double cell = use_r ? radius : 0.6 * diag * std::sqrt((double)cap / (double)n);
-    if (!(cell > 0.0) || !std::isfinite(cell)) cell = 1.0;
+    VISMA_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    ColorGradientInput in;
+    in.xyz = d_xyz; in.n = n;
+    nn_binning_origin(h_xyz, n, in.origin);
+    VISMA_TRY(G.build(in, nullptr, radius, use_r ? 0 : cap, stream));
     NormalArgs a{};
-    unsigned *d_count = nullptr, *d_start = nullptr, *d_bsum = nullptr;
-    int64_t cell_cap = 0;
-    for (int attempt = 0;; attempt++) {
-        const int64_t max_cells = std::min<int64_t>(kGridMaxCells, std::max<int64_t>(4096, 8 * n));
-        const GridParams g = grid_plan(mn, mx, cell, max_cells);
-        if (g.ncell + 1 > cell_cap) {
-            NRM_TRY(B.alloc(&d_count, (size_t)g.ncell + 1));
-            NRM_TRY(B.alloc(&d_start, (size_t)g.ncell + 9));
-            NRM_TRY(B.alloc(&d_bsum, (size_t)grid_scan_blocks(g.ncell) + 1));
-            cell_cap = g.ncell + 1;
-        }
-        NRM_TRY(launch_grid_build(d_f4, n, g, d_cell_of, d_count, d_bsum, d_start, d_sorted, stream, d_p8, d_sorted64));
-        a.sorted = d_sorted; a.sorted64 = d_sorted64; a.start = d_start; a.g = g; a.pts = d_p8;
-        a.nrm_in = d_nin; a.nrm_out = d_out; a.n = (int)n; a.cap = cap;
-        a.q_begin = 0; a.q_count = (int)n;
-        const float r2f = (float)(radius * radius);
-        a.r2d = (double)r2f;
-        a.n27 = d_n27;
-        if (use_r || attempt >= 3) break;
-        // KNN: aim at 2.5 knn points in the 27 cells (one ring is then enough for most points)
-        NRM_TRY(hipMemsetAsync(d_n27, 0, 2 * sizeof(unsigned long long), stream));
-        NRM_TRY((launch_normals<0, 1, false>(a, stream)));
-        unsigned long long h27[2];
-        NRM_TRY(hipMemcpyAsync(h27, d_n27, sizeof(h27), hipMemcpyDeviceToHost, stream));
-        NRM_TRY(hipStreamSynchronize(stream));
-        const double mean27 = h27[1] ? (double)h27[0] / h27[1] : 0.0, want = 2.5 * cap;
-        if (mean27 >= 0.6 * want && mean27 <= 2.5 * want) break;
-        const double f = mean27 > 0.0 ? std::sqrt(want / mean27) : 2.0;      // surface scaling; rings cover the rest
-        const double next = cell * std::min(std::max(f, 0.25), 4.0);
-        if (g.h > (float)(cell * 1.01) && next < cell) break;              // the cell cap already enlarged the cells
-        cell = next;
-    }
+    a.view = G.view;
+    a.nrm_in = d_nin; a.nrm_out = d_out; a.n = (int)n; a.cap = cap;
+    a.q_begin = 0; a.q_count = (int)n;
+    a.r2d = nn_radius2(radius);
     int type = search_type;
     std::vector<int> cnt;                                        // (Radius) neighbours per query, cell order
     if (search_type == 1) {
         // Radius: count every point's neighbours, then run as a Hybrid search that keeps them all
         int *d_cnt = nullptr;
-        NRM_TRY(B.alloc(&d_cnt, (size_t)n));
+        VISMA_TRY(B.alloc(&d_cnt, (size_t)n));
         a.count_out = d_cnt;
-        NRM_TRY((launch_normals<1, 2, false>(a, stream)));
+        VISMA_TRY((launch_normals<1, true, false>(a, stream)));
         cnt.resize((size_t)n);
-        NRM_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
-        NRM_TRY(hipStreamSynchronize(stream));
+        VISMA_TRY(hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, stream));
+        VISMA_TRY(hipStreamSynchronize(stream));
         type = 2;
     }
     // Runs of queries (cell order) and the list capacity each needs.  KNN / Hybrid: one run, the caller's bound.
@@ -444,8 +265,8 @@ hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double 
     double *d_sd = nullptr;
     int *d_si = nullptr;
     if (spill_entries) {
-        NRM_TRY(B.alloc(&d_sd, spill_entries));
-        NRM_TRY(B.alloc(&d_si, spill_entries));
+        VISMA_TRY(B.alloc(&d_sd, spill_entries));
+        VISMA_TRY(B.alloc(&d_si, spill_entries));
         a.spill_d2 = d_sd; a.spill_id = d_si;
     }
     for (const Run &r : runs) {
@@ -453,20 +274,20 @@ hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double 
         if (r.cap <= kNormalsMaxList) {
             a.q_begin = (int)r.q0;
             a.q_count = (int)r.qn;
-            if (type == 0) NRM_TRY((launch_normals<0, 0, false>(a, stream)));
-            else NRM_TRY((launch_normals<2, 0, false>(a, stream)));
+            if (type == 0) VISMA_TRY((launch_normals<0, false, false>(a, stream)));
+            else VISMA_TRY((launch_normals<2, false, false>(a, stream)));
             continue;
         }
         const int64_t slab = std::min<int64_t>(r.qn, std::max<int64_t>(64, (int64_t)(budget / ((size_t)r.cap * 12))));
         for (int64_t q0 = r.q0; q0 < r.q0 + r.qn; q0 += slab) {
             a.q_begin = (int)q0;
             a.q_count = (int)std::min<int64_t>(slab, r.q0 + r.qn - q0);
-            if (type == 0) NRM_TRY((launch_normals<0, 0, true>(a, stream)));
-            else NRM_TRY((launch_normals<2, 0, true>(a, stream)));
+            if (type == 0) VISMA_TRY((launch_normals<0, false, true>(a, stream)));
+            else VISMA_TRY((launch_normals<2, false, true>(a, stream)));
         }
     }
-    NRM_TRY(hipMemcpyAsync(h_out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
-    NRM_TRY(hipStreamSynchronize(stream));
+    VISMA_TRY(hipMemcpyAsync(h_out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
     return hipSuccess;
 }
 

@@ -123,9 +123,8 @@ __global__ __launch_bounds__(kRansacThreads) void ransac_score_kernel(const doub
 
 }  // namespace
 
-struct RansacDevice {
-    std::vector<void *> ptrs;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+struct RansacDevice : DevBufs {
+    DevEvents<2> ev;
     hipStream_t stream = nullptr;
     RansacView v;                       // device pointers
     int n = 0;                          // ransac_n
@@ -134,22 +133,6 @@ struct RansacDevice {
     signed char *verdict = nullptr;
     double *T_slot = nullptr, *T_out = nullptr;
     int *idx = nullptr, *cnt = nullptr;                      // *cnt: trials of the chunk that passed
-    ~RansacDevice()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
-    template <class T>
-    hipError_t alloc(T **out, size_t count)
-    {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, sizeof(T) * std::max<size_t>(count, 1));
-        if (e != hipSuccess) return e;
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return hipSuccess;
-    }
     template <class T>
     hipError_t upload(const T **out, const T *h, size_t count)
     {
@@ -161,7 +144,6 @@ struct RansacDevice {
     }
 };
 
-#define RANSAC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 #define RANSAC_FOR_N(n, CALL)                                     \
     switch (n) {                                                  \
     case 3: CALL(3); break;                                       \
@@ -182,25 +164,25 @@ static hipError_t ransac_device_create_impl(const RansacProblem &p, int64_t chun
     D->cap = chunk_cap;
     D->n_draw_trials = p.draws ? p.n_draw_trials : -1;
     RansacView &v = D->v;
-    RANSAC_TRY(D->upload(&v.src, p.src, (size_t)p.ns * 3));
-    RANSAC_TRY(D->upload(&v.tgt, p.tgt, (size_t)p.nt * 3));
+    VISMA_TRY(D->upload(&v.src, p.src, (size_t)p.ns * 3));
+    VISMA_TRY(D->upload(&v.tgt, p.tgt, (size_t)p.nt * 3));
     if (p.src_n && p.tgt_n) {
-        RANSAC_TRY(D->upload(&v.src_n, p.src_n, (size_t)p.ns * 3));
-        RANSAC_TRY(D->upload(&v.tgt_n, p.tgt_n, (size_t)p.nt * 3));
+        VISMA_TRY(D->upload(&v.src_n, p.src_n, (size_t)p.ns * 3));
+        VISMA_TRY(D->upload(&v.tgt_n, p.tgt_n, (size_t)p.nt * 3));
     }
-    if (p.pair_src) RANSAC_TRY(D->upload(&v.pair_src, p.pair_src, (size_t)p.n_pairs));
-    RANSAC_TRY(D->upload(&v.pair_tgt, p.pair_tgt, (size_t)p.n_pairs));
-    if (p.draws) RANSAC_TRY(D->upload(&v.draws, p.draws, (size_t)p.n_draw_trials * p.ransac_n));
+    if (p.pair_src) VISMA_TRY(D->upload(&v.pair_src, p.pair_src, (size_t)p.n_pairs));
+    VISMA_TRY(D->upload(&v.pair_tgt, p.pair_tgt, (size_t)p.n_pairs));
+    if (p.draws) VISMA_TRY(D->upload(&v.draws, p.draws, (size_t)p.n_draw_trials * p.ransac_n));
     v.n_pairs = p.n_pairs;
     v.seed = p.seed;
     v.edge = p.edge; v.dist = p.dist; v.cos_normal = p.cos_normal;
     v.use_edge = p.use_edge; v.use_dist = p.use_dist; v.use_normal = p.use_normal;
-    RANSAC_TRY(D->alloc(&D->verdict, (size_t)chunk_cap));
-    RANSAC_TRY(D->alloc(&D->T_slot, (size_t)chunk_cap * 12));
-    RANSAC_TRY(D->alloc(&D->T_out, (size_t)chunk_cap * 12));
-    RANSAC_TRY(D->alloc(&D->idx, (size_t)chunk_cap));
-    RANSAC_TRY(D->alloc(&D->cnt, 1));
-    for (hipEvent_t &e : D->ev) RANSAC_TRY(hipEventCreate(&e));
+    VISMA_TRY(D->alloc(&D->verdict, (size_t)chunk_cap));
+    VISMA_TRY(D->alloc(&D->T_slot, (size_t)chunk_cap * 12));
+    VISMA_TRY(D->alloc(&D->T_out, (size_t)chunk_cap * 12));
+    VISMA_TRY(D->alloc(&D->idx, (size_t)chunk_cap));
+    VISMA_TRY(D->alloc(&D->cnt, 1));
+    VISMA_TRY(D->ev.create());
     return hipStreamSynchronize(stream);
 }
 
@@ -223,28 +205,28 @@ hipError_t ransac_device_chunk(RansacDevice *D, int64_t t0, int64_t n64, int8_t 
     const int n = (int)n64;
     hipStream_t st = D->stream;
     const dim3 block(kRansacThreads), grid((unsigned)((n + kRansacThreads - 1) / kRansacThreads));
-    RANSAC_TRY(hipEventRecord(D->ev[0], st));
+    VISMA_TRY(hipEventRecord(D->ev[0], st));
 #define RANSAC_ONE(N) hipLaunchKernelGGL(ransac_trial_kernel<N>, grid, block, 0, st, D->v, (long long)t0, n, D->verdict, D->T_slot)
     RANSAC_FOR_N(D->n, RANSAC_ONE)
 #undef RANSAC_ONE
-    RANSAC_TRY(hipGetLastError());
+    VISMA_TRY(hipGetLastError());
     hipLaunchKernelGGL(ransac_compact_kernel, dim3(1), dim3(kCompactThreads), 0, st, D->verdict, n, kRansacPass, D->idx, D->cnt);
-    RANSAC_TRY(hipGetLastError());
+    VISMA_TRY(hipGetLastError());
     hipLaunchKernelGGL(ransac_gather_kernel, dim3(std::min<unsigned>(grid.x, 256u)), block, 0, st, D->idx, D->cnt, n, D->T_slot, D->T_out);
-    RANSAC_TRY(hipGetLastError());
-    RANSAC_TRY(hipEventRecord(D->ev[1], st));
+    VISMA_TRY(hipGetLastError());
+    VISMA_TRY(hipEventRecord(D->ev[1], st));
     int h_cnt = 0;
-    RANSAC_TRY(hipMemcpyAsync(&h_cnt, D->cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-    RANSAC_TRY(hipMemcpyAsync(h_verdict, D->verdict, (size_t)n, hipMemcpyDeviceToHost, st));
+    VISMA_TRY(hipMemcpyAsync(&h_cnt, D->cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+    VISMA_TRY(hipMemcpyAsync(h_verdict, D->verdict, (size_t)n, hipMemcpyDeviceToHost, st));
     std::vector<double> t12;
     if (h_T_all) {
         t12.resize((size_t)n * 12);
-        RANSAC_TRY(hipMemcpyAsync(t12.data(), D->T_slot, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, st));
+        VISMA_TRY(hipMemcpyAsync(t12.data(), D->T_slot, sizeof(double) * 12 * (size_t)n, hipMemcpyDeviceToHost, st));
     }
-    RANSAC_TRY(hipStreamSynchronize(st));
+    VISMA_TRY(hipStreamSynchronize(st));
     if (ms) {
         float t = 0.f;
-        RANSAC_TRY(hipEventElapsedTime(&t, D->ev[0], D->ev[1]));
+        VISMA_TRY(hipEventElapsedTime(&t, D->ev[0], D->ev[1]));
         *ms += (double)t;
     }
     auto widen = [](const double *t12, double *t16) {
@@ -261,9 +243,9 @@ hipError_t ransac_device_chunk(RansacDevice *D, int64_t t0, int64_t n64, int8_t 
     if (pass_trial && pass_T && h_cnt > 0) {
         std::vector<int> idx((size_t)h_cnt);
         std::vector<double> T((size_t)h_cnt * 12);
-        RANSAC_TRY(hipMemcpyAsync(idx.data(), D->idx, sizeof(int) * (size_t)h_cnt, hipMemcpyDeviceToHost, st));
-        RANSAC_TRY(hipMemcpyAsync(T.data(), D->T_out, sizeof(double) * 12 * (size_t)h_cnt, hipMemcpyDeviceToHost, st));
-        RANSAC_TRY(hipStreamSynchronize(st));
+        VISMA_TRY(hipMemcpyAsync(idx.data(), D->idx, sizeof(int) * (size_t)h_cnt, hipMemcpyDeviceToHost, st));
+        VISMA_TRY(hipMemcpyAsync(T.data(), D->T_out, sizeof(double) * 12 * (size_t)h_cnt, hipMemcpyDeviceToHost, st));
+        VISMA_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < h_cnt; k++) {
             pass_trial->push_back(t0 + idx[(size_t)k]);
             pass_T->resize(pass_T->size() + 16);
@@ -284,17 +266,17 @@ hipError_t ransac_score_device(RansacDevice *D, const double *h_T, int64_t n, do
     for (int64_t i = 0; i < n; i++) std::copy(h_T + 16 * i, h_T + 16 * i + 12, t12.begin() + 12 * i);
     double *d_T = nullptr, *d_e = nullptr;
     long long *d_g = nullptr;
-    RANSAC_TRY(D->alloc(&d_T, (size_t)n * 12));
-    RANSAC_TRY(D->alloc(&d_e, (size_t)n));
-    RANSAC_TRY(D->alloc(&d_g, (size_t)n));
-    RANSAC_TRY(hipMemcpyAsync(d_T, t12.data(), sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, st));
+    VISMA_TRY(D->alloc(&d_T, (size_t)n * 12));
+    VISMA_TRY(D->alloc(&d_e, (size_t)n));
+    VISMA_TRY(D->alloc(&d_g, (size_t)n));
+    VISMA_TRY(hipMemcpyAsync(d_T, t12.data(), sizeof(double) * 12 * (size_t)n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ransac_score_kernel, dim3((unsigned)n), dim3(kRansacThreads), 0, st, D->v.src, D->v.tgt, D->v.pair_src,
                        D->v.pair_tgt, D->v.n_pairs, d_T, max_dist * max_dist, d_g, d_e);
-    RANSAC_TRY(hipGetLastError());
+    VISMA_TRY(hipGetLastError());
     std::vector<long long> g((size_t)n);
-    RANSAC_TRY(hipMemcpyAsync(g.data(), d_g, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, st));
-    RANSAC_TRY(hipMemcpyAsync(h_err2, d_e, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    RANSAC_TRY(hipStreamSynchronize(st));
+    VISMA_TRY(hipMemcpyAsync(g.data(), d_g, sizeof(long long) * (size_t)n, hipMemcpyDeviceToHost, st));
+    VISMA_TRY(hipMemcpyAsync(h_err2, d_e, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    VISMA_TRY(hipStreamSynchronize(st));
     for (int64_t i = 0; i < n; i++) h_good[i] = (int64_t)g[(size_t)i];
     return hipSuccess;
 }
