@@ -856,7 +856,12 @@ VISMA_ICP_API int visma_icp_sample_mesh(visma_icp_ctx *ctx, const double *V, int
  * -- fewer than 3 neighbours: (0,0,1); normals_in (may be NULL) are the cloud's existing normals, whose
  * sign is kept (EstimateNormals.cpp:133-146).  n x 3 f64 in, n x 3 f64 out.  Any knn /
  * max_nn: lists of up to 170 entries live in LDS, longer ones (and dense Radius searches) in a heap per point in
- * global memory; Radius results are summed in the order of the reference's result list too. */
+ * global memory; Radius results are summed in the order of the reference's result list too.
+ * The lists are in flann's order, ascending (d2, index), d2 flann's f64 sum; where distances tie exactly the lower index
+ * comes first.  A neighbour at a NaN distance is never listed, in any search type: a point with a NaN coordinate is
+ * nobody's neighbour and has none itself (its normal is (0,0,1)), every other point's normal is what it is on the cloud
+ * without that point, and the result is a function of the input.  An infinite distance (a point with an infinite
+ * coordinate) is a legitimate KNN entry, behind every finite one. */
 VISMA_ICP_API int visma_icp_estimate_normals(visma_icp_ctx *ctx, const double *xyz, int64_t n,
                                              const double *normals_in, int search_type, int knn,
                                              double radius, double *normals_out);

@@ -124,6 +124,18 @@ VISMA_ICP_API int visma_icp_selftest_so3_jac(const double *w, int n, double *R, 
 VISMA_ICP_API int visma_icp_selftest_se3(const double *g, const double *h, const double *v, int n,
                                          double *gh, double *gv, double *g_inv);
 
+/* The neighbour lists that visma_icp_estimate_normals, the colour gradient and visma_icp_compute_fpfh are computed from
+ * (visma_amd/csrc/nn_list.h), built ON THE GPU over the grid those calls build, and handed out as they are.  xyz n x 3.
+ * search_type 0 KNN(cap) | 2 Hybrid(radius, cap) | 1 Radius(radius) as the normals' counting pass runs it: writes cnt
+ * only, idx / d2 may be NULL.  list_kind 0: the sorted list in LDS, cap in 1..170; 1: the max-heap in global memory, any
+ * cap >= 1, heap-sorted at the end.  In the caller's point order: idx (n x cap) the neighbours ascending in (d2, index),
+ * padded with -1; d2 (n x cap) their squared distances (flann's f64 sum), padded with +inf; cnt (n) the entries of each
+ * list, at most min(cap, n).  A neighbour at a NaN distance is never listed; Radius / Hybrid list d2 <
+ * (double)(float)(radius * radius), strictly.  VISMA_ICP_ERR_INVALID, before any launch: n < 1, cap < 1, list_kind 0 with
+ * cap > 170, another search_type or list_kind, a radius that is not finite and positive (Radius / Hybrid), a NULL array. */
+VISMA_ICP_API int visma_icp_selftest_neighbor_lists(const double *xyz, int64_t n, int search_type, int cap, double radius,
+                                                    int list_kind, int32_t *idx, double *d2, int32_t *cnt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -965,7 +965,9 @@ static int cmp_nbr(const void *a, const void *b)
  * exhaustive scan: search_type 0 = the knn nearest (SearchKNN), 1 = every point with
  * d2 < (double)(float)(r*r) (SearchRadius: flann radiusSearch is strict), 2 = the knn nearest of
  * those (SearchHybrid); results ascending in (d2, index) -- flann orders exactly equal distances by
- * tree traversal instead.  d2 is flann's L2 (dist.h:159-176).  normals_in may be NULL. */
+ * tree traversal instead.  d2 is flann's L2 (dist.h:159-176).  A neighbour at a NaN distance is never
+ * listed in any search type (a NaN has no place in an ordered list: qsort's comparison would not be
+ * an order); an infinite one is.  normals_in may be NULL. */
 void vo_estimate_normals(const double *xyz, int64_t n, const double *normals_in, int search_type,
                          int knn, double radius, double *out)
 {
@@ -982,6 +984,7 @@ void vo_estimate_normals(const double *xyz, int64_t n, const double *normals_in,
                 double d = dx * dx;
                 d += dy * dy;
                 d += dz * dz;
+                if (d != d) continue;                        /* a neighbour at a NaN distance is never listed */
                 if (search_type != 0 && !(d < r2)) continue;
                 nb[m].d = d; nb[m].i = (int32_t)j; m++;
             }

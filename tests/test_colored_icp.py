@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+from nn_spec import spec_lists
 from oracle_engine import OracleEngine
 from visma_amd import _lib, synth  # noqa: F401
 
@@ -221,7 +222,8 @@ def _rand_T(rng, ang=0.2, tr=0.1):
 
 
 # ---------------------------------------------------------------------------
-# the gradient's clouds (jittered: no two distances tie) and their specification, computed once
+# the gradient's clouds (jittered: no two distances tie -- but for `lattice`, `lattice04` and `dups`, which are there for
+# the ties) and their specification, computed once
 # ---------------------------------------------------------------------------
 def plane_cloud(n=48, h=0.05, seed=1, lo=0.0):
     rng = np.random.default_rng(seed)
@@ -249,10 +251,18 @@ def _grad_cloud(name):
         rng = np.random.default_rng(9)
         p = rng.random((200, 3))
         return p, _unit(rng.standard_normal((200, 3))), rng.random((200, 3)), 0.12
+    if name in ("lattice", "lattice04"):                   # NOT jittered: a 32 x 32 lattice, spacing 0.0625 (every d2 exact, so
+        i, j = np.meshgrid(np.arange(32), np.arange(32), indexing="ij")     # ties are exact ties); radius 0.25 / 0.4
+        p = np.stack([i.ravel() * 0.0625, j.ravel() * 0.0625, np.zeros(1024)], 1)
+        return p, np.tile([0.0, 0.0, 1.0], (1024, 1)), rgb_of(texture(p[:, 0], p[:, 1], 0.9, 2.3)), (0.25 if name == "lattice" else 0.4)
+    if name == "dups":                                     # the plane with every 7th point once more at a lower and at a higher index
+        q = plane_cloud()
+        p = np.concatenate([q[::7], q, q[::7]])
+        return p, np.tile([0.0, 0.0, 1.0], (len(p), 1)), rgb_of(texture(p[:, 0], p[:, 1], 0.9, 2.3)), 0.4
     raise KeyError(name)
 
 
-GRAD_CLOUDS = ["plane", "sphere", "sparse", "sphere1", "sphere2", "sphere3", "sphere65", "plane_tiny"]
+GRAD_CLOUDS = ["plane", "sphere", "sparse", "sphere1", "sphere2", "sphere3", "sphere65", "plane_tiny", "lattice", "lattice04", "dups"]
 MAX_NNS = [3, 30, 170]
 _grad_cache = {}
 
@@ -291,6 +301,18 @@ def test_specification_gradient_excludes_no_point_and_covers_the_zero_cases(name
             assert (~below).all() and np.abs(c["g"]).max() > 0.1
     if name == "plane" and max_nn == 3:
         assert below.sum() > 10 and (~below).sum() > 10                  # both sides of the guard
+    if name == "lattice":
+        # the cut at max_nn falls inside a tie (the max_nn-th and the next distance are equal): which of the tied points
+        # enters is the (d2, index) order's to say, and the gradient is of order 1, so it shows
+        _, d2, cnt = spec_lists(c["p"], 2, max_nn + 1, c["r"])
+        tied = (cnt == max_nn + 1) & (d2[:, max_nn - 1] == d2[:, max_nn])
+        assert int(tied.sum()) == {3: 1020, 30: 888, 170: 0}[max_nn]
+        assert np.abs(c["g"]).max() > 1.0
+    if name == "dups":
+        idx, d2, cnt = spec_lists(c["p"], 2, 3, c["r"])
+        twice = idx[:, 0] != np.arange(len(idx))                         # entry 0, the one that is skipped, is a duplicate ...
+        assert twice.sum() == 2 * 330 and (d2[twice, :3] == 0.0).all()   # ... and the point itself is listed: a zero row
+        assert (c["cnts"] == max_nn).sum() > 0.5 * len(c["p"])
 
 
 @pytest.mark.parametrize("max_nn", [3, 30])

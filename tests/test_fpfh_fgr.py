@@ -23,6 +23,7 @@ import sys
 import numpy as np
 import pytest
 
+from nn_spec import cube_cloud, spec_lists  # noqa: F401  (the neighbour lists: shared with tests/test_nn_lists.py)
 from oracle_engine import OracleEngine
 from visma_amd import _lib, synth  # noqa: F401
 
@@ -41,30 +42,6 @@ DIM = 33
 # ---------------------------------------------------------------------------
 # the specification
 # ---------------------------------------------------------------------------
-def spec_lists(xyz, search_type, knn, radius):
-    """Brute-force neighbour lists in flann's order: ascending (d2, index), d2 = ((dx*dx) + dy*dy) + dz*dz in f64;
-    Hybrid: d2 < (double)(float)(r*r), strictly.  A NaN distance is never listed.  -> idx (n, cap), d2 (n, cap), cnt (n,)"""
-    p = np.asarray(xyz, np.float64)
-    n = len(p)
-    cap = min(knn, n)
-    d = p[:, None, :] - p[None, :, :]
-    with np.errstate(invalid="ignore", over="ignore"):
-        d2 = d[..., 0] * d[..., 0]
-        d2 = d2 + d[..., 1] * d[..., 1]
-        d2 = d2 + d[..., 2] * d[..., 2]
-    ok = ~np.isnan(d2)
-    if search_type == 2:
-        if not (np.isfinite(radius) and radius > 0):
-            ok[:] = False
-        else:
-            with np.errstate(invalid="ignore"):
-                ok &= d2 < float(np.float32(radius * radius))
-    key = np.where(ok, d2, np.inf)
-    order = np.argsort(key, axis=1, kind="stable")[:, :cap]         # stable: ties in ascending index
-    cnt = np.minimum(ok.sum(1), cap)
-    return order.astype(np.int64), np.take_along_axis(key, order, 1), cnt
-
-
 def _bin(v):
     """(int)floor(v) clamped to [0, 10]; not finite -> 0 (Feature.cpp:92-94 on x86-64)"""
     with np.errstate(invalid="ignore"):
@@ -563,6 +540,40 @@ def test_fpfh_corner_grid(ctx):
     g, gn = corner_grid()
     spec, det = spec_fpfh(g, gn, 2, 30, 0.12, details=True)
     check_fpfh(ctx.compute_fpfh(g, gn, knn=30, radius=0.12), spec, det, "corner grid Hybrid(0.12, 30)")
+
+
+def cube_case(kind):
+    """nn_spec.cube_cloud(shuffled): a 9 x 9 x 9 lattice in a seeded order, normals from a seed.  Nearly every list is cut
+    inside an exact tie, so the columns say which of the tied points the (d2, index) order lets in."""
+    key = ("cube",) + kind
+    if key not in _CACHE:
+        p = cube_cloud(shuffled=True)
+        nr = np.random.default_rng(19).standard_normal(p.shape)
+        nr /= np.linalg.norm(nr, axis=1)[:, None]
+        _CACHE[key] = (p, nr) + spec_fpfh(p, nr, *kind, details=True)
+    return _CACHE[key]
+
+
+CUBE_KINDS = [(0, 30, 0.0), (2, 30, 0.3)]
+
+
+@pytest.mark.parametrize("kind", CUBE_KINDS)
+def test_specification_fpfh_of_the_lattice_depends_on_the_tie_break(kind):
+    """with the ties broken by DESCENDING index instead (the same cloud, its order reversed) the columns differ: the case
+    sees the rule"""
+    p, nr, spec, det = cube_case(kind)
+    assert (det["slack"] > 0).sum() <= 0.01 * len(p)
+    other = spec_fpfh(p[::-1], nr[::-1], *kind)[::-1]
+    assert (np.abs(other - spec).max(1) > 1e-3).sum() > 0.5 * len(p)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", CUBE_KINDS)
+def test_fpfh_lattice_with_the_cut_inside_ties(ctx, kind):
+    p, nr, spec, det = cube_case(kind)
+    for mode in (1, 2):                                           # both designs of the second pass
+        got = ctx.compute_fpfh(p, nr, knn=kind[1], radius=kind[2] if kind[0] == 2 else None, second_pass=mode)
+        check_fpfh(got, spec, det, "shuffled 9 x 9 x 9 lattice %s, second pass %d" % (kind, mode))
 
 
 @pytest.mark.gpu

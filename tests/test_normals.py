@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from visma_amd import _lib, synth  # noqa: E402
+from nn_spec import nonfinite_cloud  # noqa: E402
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "normals.npz")
 
@@ -165,3 +166,56 @@ def test_gpu_argument_errors(lib):
     out = ctx.estimate_normals(pts, knn=None, radius=0.0)    # no neighbours anywhere
     assert np.array_equal(out, np.tile([0.0, 0.0, 1.0], (100, 1)))
     assert ctx.estimate_normals(np.empty((0, 3)), knn=30).shape == (0, 3)
+
+
+# ---------------------------------------------------------------------------
+# Non-finite points.  The rule (visma_icp.h): a neighbour at a NaN distance is never listed, in any search type.  A point
+# with a NaN coordinate is then nobody's neighbour and has no neighbours itself: the fall-back normal (0, 0, 1).  A point
+# with an infinite coordinate is at distance +inf of every finite point: a legitimate KNN entry, but behind every finite one.
+# The cloud is nn_spec.nonfinite_cloud (tests/test_nn_lists.py pins its lists): 597 finite points, a with one NaN
+# coordinate, b with one +inf coordinate, one row entirely NaN.
+# ---------------------------------------------------------------------------
+NONFINITE_SEARCHES = {"knn12": dict(knn=12), "knn170": dict(knn=170), "knn171": dict(knn=171),
+                      "hybrid": dict(knn=30, radius=0.3), "radius": dict(knn=None, radius=0.2)}
+FALLBACK = [0.0, 0.0, 1.0]
+
+
+def _check_nonfinite(estimate, kw):
+    """what needs no reference: rows a and the NaN row are the fall-back, a second call is the first bit for bit, and on
+    the finite rows the result is bit-identical to the call on the cloud with the non-finite rows deleted (knn is below
+    the number of finite points: the lists are the same points in the same (d2, index) order, and the sums run in list
+    order).  -> the normals"""
+    pts, a, b, nan_row = nonfinite_cloud()
+    got = estimate(pts, **kw)
+    assert np.array_equal(got[[a, nan_row]], [FALLBACK, FALLBACK])
+    if kw.get("radius") is not None:
+        assert np.array_equal(got[b], FALLBACK)                  # nobody within a radius of b; KNN: its list is at +inf
+    assert np.array_equal(got, estimate(pts, **kw), equal_nan=True)
+    finite = np.isfinite(pts).all(1)
+    assert finite.sum() == 597
+    clean = estimate(pts[finite], **kw)
+    assert np.isfinite(clean).all() and (clean != FALLBACK).any(1).sum() > 500
+    assert np.array_equal(got[finite], clean)
+    return got
+
+
+@pytest.mark.parametrize("name", sorted(NONFINITE_SEARCHES))
+def test_oracle_lists_no_neighbour_at_a_nan_distance(oracle, name):
+    _check_nonfinite(oracle.estimate_normals, NONFINITE_SEARCHES[name])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(NONFINITE_SEARCHES))
+def test_gpu_lists_no_neighbour_at_a_nan_distance(lib, oracle, name):
+    """... and the GPU equals the oracle to the file's 1e-9, fall-backs exactly; knn = 170 (the list in LDS) and 171 (the
+    heap in global memory) follow the same rule."""
+    kw = NONFINITE_SEARCHES[name]
+    ctx = _lib.Context(0)
+    got = _check_nonfinite(ctx.estimate_normals, kw)
+    want = oracle.estimate_normals(nonfinite_cloud()[0], **kw)
+    fb = (want == FALLBACK).all(1)
+    assert np.array_equal(got[fb], want[fb]), name
+    err = np.abs(got - want).max(1)
+    print("normals on the non-finite cloud, %s: max |diff| to the oracle %.3e, %d fall-backs" % (name, np.nanmax(err), int(fb.sum())))
+    assert np.allclose(got, want, rtol=0.0, atol=1e-9, equal_nan=True), (name, float(np.nanmax(err)), int(np.nanargmax(err)))
+    assert np.array_equal(np.isnan(got), np.isnan(want))

@@ -601,6 +601,8 @@ def _bind(L):
     L.visma_so3_project.argtypes = [_dp, _dp]
     L.visma_so3_matrix_derivatives.argtypes = [_dp] * 7
     L.visma_icp_selftest_so3_jac.argtypes = [_dp, C.c_int, _dp, _dp, _dp, _dp, _dp]
+    L.visma_icp_selftest_neighbor_lists.argtypes = [_dp, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int,
+                                                    C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32)]
     L.visma_icp_run_yaw_sweep_point_to_plane.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double,
                                                          C.c_double, C.POINTER(CResult), C.POINTER(C.c_int),
                                                          C.POINTER(CResult)]
@@ -1979,6 +1981,24 @@ def error_metric(errors):
     if rc != OK:
         raise IcpError(rc, "error_metric")
     return dict(zip(("mean", "std", "median", "min", "max"), out))
+
+
+def selftest_neighbor_lists(xyz, search_type, cap, radius=0.0, list_kind=0):
+    """(tests) visma_icp_selftest_neighbor_lists: the neighbour lists of nn_list.h as the GPU builds them -> idx (n, cap)
+    int32 padded with -1, d2 (n, cap) padded with +inf, cnt (n,); search_type 1 (Radius, the counting pass): cnt alone."""
+    L = load()
+    p = _f64(xyz, (-1, 3)); n = len(p)
+    cnt = np.full(n, -7, np.int32)
+    if search_type == 1:
+        idx = d2 = None
+    else:
+        idx = np.full((n, max(cap, 0)), -7, np.int32); d2 = np.full((n, max(cap, 0)), np.nan)
+    rc = L.visma_icp_selftest_neighbor_lists(_p(p, _dp), n, search_type, cap, radius, list_kind,
+                                             None if idx is None else _p(idx, _ip), None if d2 is None else _p(d2, _dp),
+                                             _p(cnt, _ip))
+    if rc != OK:
+        raise IcpError(rc, "selftest_neighbor_lists")
+    return cnt if search_type == 1 else (idx, d2, cnt)
 
 
 class CIoCloud(C.Structure):

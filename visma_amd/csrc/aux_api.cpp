@@ -965,6 +965,21 @@ int visma_icp_selftest_so3_jac(const double *w, int n, double *R, double *dR_dw,
     return rc;
 }
 
+int visma_icp_selftest_neighbor_lists(const double *xyz, int64_t n, int search_type, int cap, double radius, int list_kind,
+                                      int32_t *idx, double *d2, int32_t *cnt)
+{
+    const bool lists = search_type != 1;
+    if (!xyz || !cnt || n <= 0 || n > 0x7fffffff || search_type < 0 || search_type > 2 || cap < 1 || list_kind < 0 ||
+        list_kind > 1 || (list_kind == 0 && cap > kNormalsMaxList) || (lists && (!idx || !d2)) ||
+        (search_type != 0 && (!(radius > 0.0) || !std::isfinite(radius))))
+        return VISMA_ICP_ERR_INVALID;
+    const hipError_t e = nn_selftest_lists_device(xyz, n, search_type, cap, radius, list_kind, idx, d2, cnt, nullptr);
+    if (e == hipSuccess) return VISMA_ICP_OK;
+    (void)hipGetLastError();
+    g_create_error = std::string("neighbor lists selftest: ") + hipGetErrorString(e);
+    return VISMA_ICP_ERR_HIP;
+}
+
 // ---- the gravity alignment and pose composition of feh::AnnotationTool (src/annotation.cpp:82-91, 111-153): host
 // code (plane_math.hpp); the clouds it looks at are the ones about to be uploaded
 int visma_geom_find_plane_normal(const double *xyz, int64_t n, double normal_out[3])

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(NTH) void color_gradient_kernel(GradArgs a)
     if (t >= a.n) return;
     NnList L = nn_list_lds(lds_raw, threadIdx.x, NTH, a.cap);
     const NnQuery query = nn_query(a.view, t);
-    nn_search<false>(a.view, query, L, [&](double d) { return d < a.r2d; });     // flann radiusSearch: strict
+    nn_search<false>(a.view, query, L, nn_accept<false>(a.r2d));                 // flann radiusSearch: strict
     const Pt64 q = query.p;
     const int me = query.me;
     double x[3] = {0.0, 0.0, 0.0};

@@ -129,9 +129,8 @@ __global__ __launch_bounds__(NTH) void fpfh_search_kernel(FpfhArgs a)
     NnList L = nn_list_lds(lds_raw, threadIdx.x, NTH, a.cap);
     if (t >= a.n) return;
     const NnQuery query = nn_query(a.view, t);                    // queries in cell order
-    // Hybrid: flann's radiusSearch, strict.  KNN: a NaN distance has no place in an ordered list and is dropped
-    // (normals.hip's KNN lets it in: each file keeps its own rule)
-    nn_search<TYPE == 0>(a.view, query, L, [&](double d) { return TYPE == 0 ? d == d : d < a.r2d; });
+    // nn_list.h's rule (Hybrid: flann's radiusSearch, strict; a neighbour at a NaN distance is never listed)
+    nn_search<TYPE == 0>(a.view, query, L, nn_accept<TYPE == 0>(a.r2d));
     const Pt64 q = query.p;
     const int me = query.me;
     if (PASS == 1) {

@@ -808,6 +808,12 @@ struct NnGrid {
     unsigned long long *n27 = nullptr;       // (KNN) sum of the sampled 27-cell populations, points sampled
 };
 
+// (tests: nn_selftest.hip) the lists themselves, host arrays in and out, in the points' order: idx / d2 n x cap padded with
+// -1 / +inf behind the min(cap, n) entries a list can hold, cnt n.  search_type 0 KNN | 1 Radius as the normals' counting
+// pass (cnt only) | 2 Hybrid; list_kind 0 NnList in LDS (cap <= kNormalsMaxList) | 1 NnHeap in global memory, sorted.
+hipError_t nn_selftest_lists_device(const double *h_xyz, int64_t n, int search_type, int cap, double radius, int list_kind,
+                                    int32_t *h_idx, double *h_d2, int32_t *h_cnt, hipStream_t stream);
+
 // the gradient per point (n x 3 doubles on the device, the points' order) by the Hybrid search (radius, max_nn);
 // max_nn outside [3, kNormalsMaxList]: hipErrorInvalidValue.  Returns with the stream idle.
 hipError_t color_gradient_on_device(const ColorGradientInput &in, double radius, int max_nn, double *d_grad, hipStream_t stream);

@@ -5,7 +5,8 @@
 //   NnList                 the list in LDS as [cap][threads] (element j of thread t at j * threads + t), squared distances
 //                          first, indices behind them; kept sorted
 //   NnHeap                 the same surface over global memory: a max-heap while the search runs, sorted at the end
-//   nn_search              the walk over the rings of cells; which distances enter the list is the caller's `accept`
+//   nn_accept              which distances enter a list: the one rule of every caller
+//   nn_search              the walk over the rings of cells
 //   nn_launch              threads per workgroup by the LDS the lists take, the kernel instantiated for them
 // What a kernel does with its list -- moments, gradient rows, histograms -- is its own file's.
 #pragma once
@@ -65,9 +66,11 @@ __device__ __forceinline__ NnQuery nn_query(const NnGridView &v, long long t)
     NnQuery q;
     q.p = v.sorted64[t];
     const float4 qf = v.sorted[t];
-    q.cx = cell_coord(qf.x, v.g.mn[0], v.g.inv_h, v.g.dim[0]);
-    q.cy = cell_coord(qf.y, v.g.mn[1], v.g.inv_hs, v.g.dim[1]);
-    q.cz = cell_coord(qf.z, v.g.mn[2], v.g.inv_hs, v.g.dim[2]);
+    // the cell the build put the point in (cell_count_kernel clamps the same way): an infinite coordinate collapses its
+    // axis to one cell, and an unclamped query two cells beyond it would scan nothing
+    q.cx = min(max(cell_coord(qf.x, v.g.mn[0], v.g.inv_h, v.g.dim[0]), 0), v.g.dim[0] - 1);
+    q.cy = min(max(cell_coord(qf.y, v.g.mn[1], v.g.inv_hs, v.g.dim[1]), 0), v.g.dim[1] - 1);
+    q.cz = min(max(cell_coord(qf.z, v.g.mn[2], v.g.inv_hs, v.g.dim[2]), 0), v.g.dim[2] - 1);
     q.me = (int)q.p.w;
     return q;
 }
@@ -81,6 +84,18 @@ __device__ __forceinline__ double nn_dist2(const Pt64 &q, const Pt64 &p)
     d += dz * dz;
     return d;
 }
+
+// Which squared distances enter a list, for every caller.  A neighbour at a NaN distance is NEVER listed: a NaN has no place
+// in an ordered list (in NnList it would sit at the end and block every later, nearer candidate; in NnHeap it would not).
+//   KNN = true   every distance that is one (an infinite distance is a legitimate entry)
+//   KNN = false  Radius / Hybrid: flann's radiusSearch, d2 < (double)(float)(r * r), strict -- false for a NaN
+template <bool KNN>
+struct NnAccept {
+    double r2d;
+    __device__ __forceinline__ bool operator()(double d) const { return KNN ? d == d : d < r2d; }
+};
+template <bool KNN>
+__device__ __forceinline__ NnAccept<KNN> nn_accept(double r2d) { return NnAccept<KNN>{r2d}; }
 
 // `cnt` of `cap` entries (d2, id), entry j at [j * stride]: what NnList and NnHeap keep, each in its own order
 struct NnEntries {
@@ -192,6 +207,12 @@ __device__ __forceinline__ NnHeap nn_heap_global(double *d2, int *id, long long 
     return l;
 }
 
+// the "list" of a Radius counting pass
+struct NnCount {
+    int cnt = 0;
+    __device__ __forceinline__ void insert(double, int) { cnt++; }
+};
+
 // cells xa..xb of row (y, z), clipped: consider(point) for every point in them
 template <class F>
 __device__ __forceinline__ void nn_scan_cells(const GridParams &g, const unsigned *start, const Pt64 *sorted64, int z, int y,
@@ -205,13 +226,18 @@ __device__ __forceinline__ void nn_scan_cells(const GridParams &g, const unsigne
     for (unsigned j = b; j < e; j++) consider(sorted64[j]);
 }
 
-// the shell of cells at Chebyshev distance R of cell (cx, cy, cz): full x-runs on its y/z faces, two cells elsewhere
-template <class F>
+// the shell of cells at Chebyshev distance R of cell (cx, cy, cz), a cell of the grid: full x-runs on its y/z faces, two
+// cells elsewhere.  CLIP (KNN, whose rings may reach far beyond the grid): only the rows the grid has -- a lone point R cells
+// from the rest of a grid one cell wide in y and z would otherwise walk (2 R + 1)^2 empty rows a ring, R^3 in all (a cloud
+// with one outlier some 870 cells away: of the order of 1e9 empty rows for that one query, tests/test_nn_lists.py `outlier`).
+template <bool CLIP, class F>
 __device__ __forceinline__ void nn_scan_shell(const GridParams &g, const unsigned *start, const Pt64 *sorted64, int cx, int cy,
                                               int cz, int R, F &consider)
 {
-    for (int dz = -R; dz <= R; dz++)
-        for (int dy = -R; dy <= R; dy++) {
+    const int z0 = CLIP ? max(-R, -cz) : -R, z1 = CLIP ? min(R, g.dim[2] - 1 - cz) : R;
+    const int y0 = CLIP ? max(-R, -cy) : -R, y1 = CLIP ? min(R, g.dim[1] - 1 - cy) : R;
+    for (int dz = z0; dz <= z1; dz++)
+        for (int dy = y0; dy <= y1; dy++) {
             if (max(abs(dy), abs(dz)) == R) nn_scan_cells(g, start, sorted64, cz + dz, cy + dy, cx - R, cx + R, consider);
             else {
                 nn_scan_cells(g, start, sorted64, cz + dz, cy + dy, cx - R, cx - R, consider);
@@ -220,7 +246,7 @@ __device__ __forceinline__ void nn_scan_shell(const GridParams &g, const unsigne
         }
 }
 
-// Every point of the cells around q whose squared distance d passes accept(d) goes to list.insert(d, index).
+// Every point of the cells around q whose squared distance d passes accept(d) (nn_accept) goes to list.insert(d, index).
 //   KNN = false  cells of edge 1.001 r: the 27 cells (rings 0 and 1) cover the radius, `accept` holds the radius test
 //   KNN = true   any cell size: rings are added until the list is full and its farthest entry lies within the rings
 //                scanned (0.1 % slack for the fp32 binning), or the whole grid has been scanned
@@ -235,7 +261,7 @@ __device__ __forceinline__ void nn_search(const NnGridView &v, const NnQuery &q,
     };
     const int rmax = KNN ? max(max(g.dim[0], g.dim[1]), g.dim[2]) : 1;
     for (int R = 0; R <= rmax; R++) {
-        nn_scan_shell(g, v.start, v.sorted64, q.cx, q.cy, q.cz, R, consider);
+        nn_scan_shell<KNN>(g, v.start, v.sorted64, q.cx, q.cy, q.cz, R, consider);
         if constexpr (KNN) {
             if (list.cnt == list.cap && R >= 1) {
                 const double cover = (double)R * (double)g.h * 0.999;

@@ -22,8 +22,8 @@
 // neighbours, then run as a Hybrid search whose max_nn is the largest count: the moments are summed in list order
 // like the reference's (round 2 summed them in scan order: 3e-7 off where two eigenvalues nearly coincide).
 // The grid of the cloud and the tuning of its cells are nn_grid.hip's, the walk over the cells and both kinds of list
-// nn_list.h's (shared with color_gradient.hip and fpfh.hip); which distances enter a list, the counting pass, the runs
-// and the slabs of heaps are this file's.
+// nn_list.h's, as is the rule which distances enter a list (shared with color_gradient.hip and fpfh.hip: a neighbour at a
+// NaN distance is never listed); the counting pass, the runs and the slabs of heaps are this file's.
 #include "nn_list.h"
 
 #include <math.h>
@@ -134,12 +134,6 @@ __device__ __forceinline__ void normal_from_list(const NormalArgs &a, int me, co
     a.nrm_out[3ll * me + 2] = nrm[2];
 }
 
-// the "list" of the Radius counting pass
-struct NnCount {
-    int cnt = 0;
-    __device__ __forceinline__ void insert(double, int) { cnt++; }
-};
-
 // TYPE: 0 KNN, 1 Radius (counting pass only), 2 Hybrid.  COUNT: only count the neighbours within the radius.  SPILL: the
 // list is a max-heap in global memory instead of a sorted array in LDS.
 template <int TYPE, int NTH, bool COUNT, bool SPILL>
@@ -150,10 +144,9 @@ __global__ __launch_bounds__(NTH) void estimate_normals_kernel(NormalArgs a)
     if (u >= a.q_count) return;
     const long long t = a.q_begin + u;
     const NnQuery q = nn_query(a.view, t);                          // queries in cell order
-    // Radius / Hybrid: flann's radiusSearch, strict (false for a NaN).  KNN: EVERY distance enters the list, a NaN too: it
-    // then sits at the list's end and blocks replacement once the list is full.  fpfh.hip drops such a distance; which of
-    // the two the reference does is not pinned yet, so this file keeps what it always did.
-    auto accept = [&](double d) { return TYPE == 0 || d < a.r2d; };
+    // nn_list.h's rule: a neighbour at a NaN distance is never listed.  A point with a NaN coordinate is then nobody's
+    // neighbour and its own list is empty: the fall-back normal
+    const auto accept = nn_accept<TYPE == 0>(a.r2d);
     if constexpr (COUNT) {
         NnCount L;
         nn_search<false>(a.view, q, L, accept);
