@@ -1,7 +1,8 @@
 // Core/ColorMap/ColorMapOptimization.h -- color map optimization (Q.-Y. Zhou and V. Koltun, Color Map Optimization for 3D
 // Reconstruction with Consumer Depth Cameras, SIGGRAPH 2014; shape of O3D/Core/ColorMap/ColorMapOptimization.h).  The
-// rigid variant runs on the GPU (visma_icp_open3d.hpp); the non-rigid one is not built: an option with
-// non_rigid_camera_coordinate_ set throws std::invalid_argument.  Stand-alone and header-only.
+// rigid variant runs on the GPU (visma_icp_open3d.hpp) as ColorMapOptimization; the non-rigid one -- a warping field per
+// image -- as cicp::ColorMapOptimizationNonRigid, a function of its own: ColorMapOptimization with
+// non_rigid_camera_coordinate_ set throws std::invalid_argument and says so.  Stand-alone and header-only.
 #pragma once
 
 #include <vector>
@@ -41,5 +42,8 @@ public:
 // but vertices_.  On the GPU, in visma_icp_open3d.hpp (this thread's context; cicp::ColorMapOptimization takes one).
 inline void ColorMapOptimization(TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
                                  const ColorMapOptmizationOption &option = ColorMapOptmizationOption());
+// (A caller who sets non_rigid_camera_coordinate_ calls cicp::ColorMapOptimizationNonRigid(mesh or cloud, images_rgbd, camera,
+//  option[, ctx first]) of visma_icp_open3d.hpp instead: number_of_vertical_anchors_ and non_rigid_anchor_point_weight_ are read
+//  there whatever the flag says.)
 
 }  // namespace open3d

@@ -1290,8 +1290,9 @@ VISMA_ICP_API int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int
 /* ---- Color map optimization: camera poses refined against the vertices' intensities, then the vertices re-coloured ------
  *
  * Open3D's ColorMapOptimization (Zhou and Koltun, SIGGRAPH 2014; Core/ColorMap/ColorMapOptimization.cpp), the RIGID variant
- * (non_rigid_camera_coordinate == 0, Open3D's default).  The NON-RIGID variant is not built: a call with that flag set returns
- * VISMA_ICP_ERR_INVALID and touches nothing; the option struct carries its fields so that the layout is the reference's.
+ * (non_rigid_camera_coordinate == 0, Open3D's default).  The NON-RIGID variant has entry points of its own, further down
+ * (visma_icp_color_map_create_non_rigid, visma_icp_color_map_optimization_non_rigid): the calls here answer an option with
+ * that flag set with VISMA_ICP_ERR_INVALID and touch nothing.
  *
  * A color map is an object of its context (several may live at once; the context's end frees them all), resident on the
  * GPU (colormap.hip).  The staged calls, in order: create, set every image and the vertices, prepare, then
@@ -1312,7 +1313,7 @@ VISMA_ICP_API int visma_icp_point_cloud_from_rgbd(visma_icp_ctx *ctx, int w, int
  *     its count (the reference inverts a zero matrix and turns the pose into NaN);
  *   - a vertex whose projection is not finite is not visible (undefined behaviour in the reference). */
 typedef struct {                       /* ColorMapOptmizationOption, field for field */
-    int32_t non_rigid_camera_coordinate;                       /* must be 0 */
+    int32_t non_rigid_camera_coordinate;                       /* must be 0 here; the non-rigid entry points do not read it */
     int32_t number_of_vertical_anchors;                        /* 16; non-rigid only */
     double non_rigid_anchor_point_weight;                      /* 0.316; non-rigid only */
     double maximum_iteration;                                  /* 300 (a double in the reference) */
@@ -1365,6 +1366,62 @@ VISMA_ICP_API int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, in
                                                    const float *depth, const uint8_t *color, double *extrinsics,
                                                    const double *vertices, int64_t n, const visma_icp_color_map_option *option,
                                                    double *colors);
+
+/* ---- The NON-RIGID color map optimization: besides its pose, every image carries a bilinear warping field --------------
+ *
+ * Open3D's OptimizeImageCoorNonrigid (the method of Zhou and Koltun's paper): a rigid pose cannot absorb lens distortion,
+ * rolling shutter or depth-dependent misregistration; a field of anchor_w x anchor_h anchors per image can.  GPU:
+ * colormap_warp.hip, DESIGN.md 4.4c13.
+ *   field       anchor_h = number_of_vertical_anchors, anchor_step = double(h) / (anchor_h - 1),
+ *               anchor_w = int(ceil(double(w) / anchor_step) + 1); flow[(i + j anchor_w) 2 + {0, 1}] = {i step, j step} is the
+ *               initial value and what the regulariser pulls toward.
+ *   proxies and colours   the fp32 projection and its margin test as above; then the cell i = (int)(u / step), j likewise,
+ *               p = (u - i step) / step, q likewise; the shift ((1-p)(1-q)) g00 + ((1-p) q) g01 + (p (1-q)) g10 + (p q) g11,
+ *               the margin test on it, the pixel int(round(shift)).
+ *   iteration   per camera over its visible list: u, v in f64, the cell and p, q, the shift (uu, vv), the margin test on
+ *               it, gray / dx / dy there, the chain rule through the field, C[14] (6 of the pose, 2 per corner anchor),
+ *               r = proxy - gray; the sums are kept PER CELL (121 each: the 105 upper entries of C C^T row by row, the 14
+ *               of -r C, rr, count).  weight = non_rigid_anchor_point_weight * count / n_vertex; per flow entry
+ *               JJ(d, d) += weight^2, Jb(d) += weight * weight (flow - flow_init), rr_reg += (weight (flow - flow_init))^2;
+ *               x = -JJ^-1 Jb (on the host: a banded Cholesky with a border of six); the pose update as above, flow += x[6:].
+ * Deviations from the reference:
+ *   1. a visit whose cell (ii, jj) is outside [0, anchor_w - 2] x [0, anchor_h - 2], or whose u / step or v / step is not
+ *      finite or reaches 2^30 in magnitude (compared as doubles, before the conversion to int), is SKIPPED: the reference
+ *      indexes JJ out of bounds there.  (int) truncates toward zero: u in (-step, 0) is cell 0 with p < 0, in range, kept.
+ *   2. a camera KEEPS its pose and its flow for that iteration, and reports its count, with fewer than 6 accepted visits,
+ *      with a pivot of the factorisation that is not positive and finite, or with a step that is not finite (the reference
+ *      continues only at count == 0);
+ *   3. the ORDER is defined: within a camera the visits are summed cell by cell, within a cell in ascending vertex id.
+ * The staged calls above serve both kinds of map (run's residual is the data residual); visma_icp_color_map_sums on a
+ * non-rigid map is VISMA_ICP_ERR_INVALID, the calls below on a rigid one likewise. */
+#define VISMA_ICP_COLOR_MAP_CELL_SUMS 121
+/* the checks of visma_icp_color_map_create (the option's flag field is not read), and: 2 <= number_of_vertical_anchors <= 64,
+ * anchor_w * anchor_h <= 8192, the weight finite and >= 0 */
+VISMA_ICP_API int visma_icp_color_map_create_non_rigid(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                                       const visma_icp_color_map_option *option, visma_icp_color_map **out);
+/* each output may be NULL */
+VISMA_ICP_API int visma_icp_color_map_get_anchor_shape(visma_icp_ctx *ctx, visma_icp_color_map *map, int *anchor_w, int *anchor_h,
+                                                       double *anchor_step);
+/* n_images x anchor_w anchor_h 2 doubles, the reference's layout; set_flow invalidates the proxies, as set_extrinsics does */
+VISMA_ICP_API int visma_icp_color_map_get_flow(visma_icp_ctx *ctx, visma_icp_color_map *map, double *flow);
+VISMA_ICP_API int visma_icp_color_map_set_flow(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *flow);
+/* sums[n_images x (anchor_w - 1)(anchor_h - 1) x 121] at the current poses and fields, cell ii + jj (anchor_w - 1); nothing moves */
+VISMA_ICP_API int visma_icp_color_map_cell_sums(visma_icp_ctx *ctx, visma_icp_color_map *map, double *sums);
+/* one iteration: rr, rr_reg and count [n_images] of the state BEFORE the step */
+VISMA_ICP_API int visma_icp_color_map_step_non_rigid(visma_icp_ctx *ctx, visma_icp_color_map *map, double *rr, double *rr_reg,
+                                                     int64_t *count);
+/* visma_icp_color_map_optimization with a field per image; flow (may be NULL): n_images x anchor_w anchor_h 2 out */
+VISMA_ICP_API int visma_icp_color_map_optimization_non_rigid(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                                             const float *depth, const uint8_t *color, double *extrinsics,
+                                                             const double *vertices, int64_t n,
+                                                             const visma_icp_color_map_option *option, double *colors, double *flow);
+/* Host only, no ctx, no GPU: one camera's system assembled from its (anchor_w - 1)(anchor_h - 1) cell rows, the regulariser
+ * (weight_option: non_rigid_anchor_point_weight; n_vertex: the mesh's vertex count), and the solve.  flow, flow_init:
+ * anchor_w anchor_h 2; x: 6 + anchor_w anchor_h 2 out (zero where the camera keeps: *kept = 1, deviation 2); rr_reg, kept may
+ * be NULL. */
+VISMA_ICP_API int visma_icp_color_map_solve_non_rigid(int anchor_w, int anchor_h, const double *cell_sums, int64_t n_vertex,
+                                                      double weight_option, const double *flow, const double *flow_init, double *x,
+                                                      double *rr_reg, int *kept);
 
 /* The pose graph on plain arrays (pure functions; no ctx, no GPU).  Node i has a 4 x 4 pose (row-major, node to world);
  * an edge says: transformation maps the SOURCE node's cloud onto the TARGET node's (PoseGraph.h:52-86).  Odometry edges

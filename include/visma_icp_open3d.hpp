@@ -1849,13 +1849,16 @@ inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
 // open3d::ColorMapOptimization (ColorMapOptimization.cpp, rigid) on the GPU: the one-call entry point of visma_icp.h.  The
 // non-rigid option and an image that is not float depth + RGB8 of the intrinsic's size throw std::invalid_argument.
+// The NON-RIGID optimization (a warping field per image) is ColorMapOptimizationNonRigid, below: it reads the anchors and
+// the weight from the option, whatever the option's flag says.
 namespace detail {
 inline void color_map_optimization(visma_icp_ctx *ctx, const std::vector<Eigen::Vector3d> &vertices, std::vector<Eigen::Vector3d> &colors,
                                    const std::vector<RGBDImage> &images, PinholeCameraTrajectory &camera,
-                                   const ColorMapOptmizationOption &option)
+                                   const ColorMapOptmizationOption &option, bool non_rigid = false)
 {
-    const char *who = "[ColorMapOptimization] ";
-    if (option.non_rigid_camera_coordinate_) throw std::invalid_argument(std::string(who) + "the non-rigid optimization is not built.");
+    const char *who = non_rigid ? "[ColorMapOptimizationNonRigid] " : "[ColorMapOptimization] ";
+    if (!non_rigid && option.non_rigid_camera_coordinate_)
+        throw std::invalid_argument(std::string(who) + "non_rigid_camera_coordinate_ is set: call ColorMapOptimizationNonRigid.");
     const size_t n = images.size();
     if (n == 0 || camera.extrinsic_.size() != n) throw std::invalid_argument(std::string(who) + "one extrinsic per image, at least one.");
     const int w = images[0].depth_.width_, h = images[0].depth_.height_;
@@ -1884,11 +1887,14 @@ inline void color_map_optimization(visma_icp_ctx *ctx, const std::vector<Eigen::
     o.half_dilation_kernel_size_for_discontinuity_map = option.half_dilation_kernel_size_for_discontinuity_map_;
     colors.assign(vertices.size(), Eigen::Vector3d::Zero());
     // (std::vector<Eigen::Vector3d> is contiguous AoS f64 with stride 3)
-    const int rc = visma_icp_color_map_optimization(ctx, w, h, (int)n, k, depth.data(), color.data(), E.data(),
-                                                    vertices.empty() ? nullptr : vertices[0].data(), (int64_t)vertices.size(), &o,
-                                                    colors.empty() ? nullptr : colors[0].data());
+    const double *vp = vertices.empty() ? nullptr : vertices[0].data();
+    double *cp = colors.empty() ? nullptr : colors[0].data();
+    const int rc = non_rigid ? visma_icp_color_map_optimization_non_rigid(ctx, w, h, (int)n, k, depth.data(), color.data(), E.data(), vp,
+                                                                          (int64_t)vertices.size(), &o, cp, nullptr)
+                             : visma_icp_color_map_optimization(ctx, w, h, (int)n, k, depth.data(), color.data(), E.data(), vp,
+                                                                (int64_t)vertices.size(), &o, cp);
     if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string(who) + visma_icp_last_error(ctx));
-    check(ctx, rc, "visma_icp_color_map_optimization");
+    check(ctx, rc, non_rigid ? "visma_icp_color_map_optimization_non_rigid" : "visma_icp_color_map_optimization");
     for (size_t i = 0; i < n; i++)
         for (int a = 0; a < 16; a++) camera.extrinsic_[i](a / 4, a % 4) = E[16 * i + (size_t)a];
 }
@@ -1916,6 +1922,30 @@ inline void ColorMapOptimization(PointCloud &cloud, const std::vector<RGBDImage>
                                  const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
 {
     ColorMapOptimization(detail::ThreadContext::instance().get(), cloud, images_rgbd, camera, option);
+}
+
+// The non-rigid optimization (OptimizeImageCoorNonrigid; visma_icp.h states its deviations): number_of_vertical_anchors_
+// and non_rigid_anchor_point_weight_ are read from the option whatever non_rigid_camera_coordinate_ says.  The fields
+// themselves stay inside, as in the reference; the staged calls of visma_icp.h hand them out.
+inline void ColorMapOptimizationNonRigid(visma_icp_ctx *ctx, TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd,
+                                         PinholeCameraTrajectory &camera, const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    detail::color_map_optimization(ctx, mesh.vertices_, mesh.vertex_colors_, images_rgbd, camera, option, true);
+}
+inline void ColorMapOptimizationNonRigid(visma_icp_ctx *ctx, PointCloud &cloud, const std::vector<RGBDImage> &images_rgbd,
+                                         PinholeCameraTrajectory &camera, const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    detail::color_map_optimization(ctx, cloud.points_, cloud.colors_, images_rgbd, camera, option, true);
+}
+inline void ColorMapOptimizationNonRigid(TriangleMesh &mesh, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
+                                         const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    ColorMapOptimizationNonRigid(detail::ThreadContext::instance().get(), mesh, images_rgbd, camera, option);
+}
+inline void ColorMapOptimizationNonRigid(PointCloud &cloud, const std::vector<RGBDImage> &images_rgbd, PinholeCameraTrajectory &camera,
+                                         const ColorMapOptmizationOption &option = ColorMapOptmizationOption())
+{
+    ColorMapOptimizationNonRigid(detail::ThreadContext::instance().get(), cloud, images_rgbd, camera, option);
 }
 #endif
 

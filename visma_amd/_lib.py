@@ -218,6 +218,7 @@ class CColorMapOption(C.Structure):
 
 COLOR_MAP_IMAGES = ("gray", "dx", "dy", "mask")
 COLOR_MAP_SUMS = 29
+COLOR_MAP_CELL_SUMS = 121
 
 
 def color_map_option(**fields):
@@ -237,6 +238,7 @@ class ColorMap:
 
     def __init__(self, ctx, handle, w, h, n_images):
         self.ctx, self._m, self.w, self.h, self.n_images, self.n_vertices = ctx, handle, int(w), int(h), int(n_images), 0
+        self._shape = None
 
     def _call(self, name, *args):
         self.ctx._chk(getattr(self.ctx.L, "visma_icp_color_map_" + name)(self.ctx._h, self._m, *args))
@@ -317,6 +319,55 @@ class ColorMap:
         out = np.empty((self.n_vertices, 3))
         self._call("get_colors", _p(out, _dp), self.n_vertices)
         return out
+
+    # ---- a non-rigid map (Context.color_map_non_rigid) alone ----
+    def anchor_shape(self):
+        """-> (anchor_w, anchor_h, anchor_step)"""
+        if self._shape is None:
+            aw, ah, step = C.c_int(0), C.c_int(0), C.c_double(0.0)
+            self._call("get_anchor_shape", C.byref(aw), C.byref(ah), C.byref(step))
+            self._shape = (aw.value, ah.value, step.value)
+        return self._shape
+
+    def flow(self):
+        """n_images x (anchor_w anchor_h 2): entry (i + j anchor_w) 2 + {0, 1} is where anchor (i, j) points"""
+        aw, ah, _ = self.anchor_shape()
+        out = np.empty((self.n_images, aw * ah * 2))
+        self._call("get_flow", _p(out, _dp))
+        return out
+
+    def set_flow(self, flow):
+        aw, ah, _ = self.anchor_shape()
+        f = _f64(flow, (self.n_images * aw * ah * 2,))
+        self._call("set_flow", _p(f, _dp))
+
+    def cell_sums(self):
+        """n_images x cells x 121 at the current poses and fields (cell ii + jj (anchor_w - 1)); nothing moves"""
+        aw, ah, _ = self.anchor_shape()
+        out = np.empty((self.n_images, (aw - 1) * (ah - 1), COLOR_MAP_CELL_SUMS))
+        self._call("cell_sums", _p(out, _dp))
+        return out
+
+    def step_non_rigid(self):
+        """one iteration -> rr, rr_reg (n_images f64), count (n_images int64) of the state before it"""
+        rr, reg, count = np.empty(self.n_images), np.empty(self.n_images), np.empty(self.n_images, np.int64)
+        self._call("step_non_rigid", _p(rr, _dp), _p(reg, _dp), count.ctypes.data_as(C.POINTER(C.c_int64)))
+        return rr, reg, count
+
+
+def color_map_solve_non_rigid(anchor_w, anchor_h, cell_sums, n_vertex, weight, flow, flow_init):
+    """visma_icp_color_map_solve_non_rigid (host only): one camera's cell rows -> (x of 6 + anchor_w anchor_h 2, rr_reg, kept)"""
+    aw, ah = int(anchor_w), int(anchor_h)
+    if aw < 2 or ah < 2 or aw * ah > 8192:
+        raise IcpError(1, "color_map_solve_non_rigid: bad anchor shape")
+    rows = _f64(cell_sums, ((aw - 1) * (ah - 1) * COLOR_MAP_CELL_SUMS,))
+    f, f0 = _f64(flow, (aw * ah * 2,)), _f64(flow_init, (aw * ah * 2,))
+    x, reg, kept = np.empty(6 + aw * ah * 2), C.c_double(0.0), C.c_int(0)
+    rc = load().visma_icp_color_map_solve_non_rigid(aw, ah, _p(rows, _dp), int(n_vertex), float(weight), _p(f, _dp), _p(f0, _dp),
+                                                    _p(x, _dp), C.byref(reg), C.byref(kept))
+    if rc != 0:
+        raise IcpError(rc, "color_map_solve_non_rigid: bad arguments")
+    return x, reg.value, bool(kept.value)
 
 
 class CGlobalOptimizationCriteria(C.Structure):
@@ -587,6 +638,18 @@ def _bind(L):
         L.visma_icp_color_map_set_extrinsics.argtypes = [_vp, _vp, _dp]
         L.visma_icp_color_map_get_colors.argtypes = [_vp, _vp, _dp, C.c_int64]
         L.visma_icp_color_map_optimization.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _fp, _u8, _dp, _dp, C.c_int64, _opt, _dp]
+    if hasattr(L, "visma_icp_color_map_create_non_rigid"):
+        _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
+        _opt = C.POINTER(CColorMapOption)
+        L.visma_icp_color_map_create_non_rigid.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _opt, C.POINTER(_vp)]
+        L.visma_icp_color_map_get_anchor_shape.argtypes = [_vp, _vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.visma_icp_color_map_get_flow.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_set_flow.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_cell_sums.argtypes = [_vp, _vp, _dp]
+        L.visma_icp_color_map_step_non_rigid.argtypes = [_vp, _vp, _dp, _dp, _i64]
+        L.visma_icp_color_map_optimization_non_rigid.argtypes = [_vp, C.c_int, C.c_int, C.c_int, _dp, _fp, _u8, _dp, _dp, C.c_int64, _opt, _dp, _dp]
+        L.visma_icp_color_map_solve_non_rigid.argtypes = [C.c_int, C.c_int, _dp, C.c_int64, C.c_double, _dp, _dp, _dp,
+                                                          C.POINTER(C.c_double), C.POINTER(C.c_int)]
     L.visma_icp_set_persistent_cu_share.argtypes = [C.c_double]
     L.visma_icp_get_persistent_info.argtypes = [C.c_void_p, C.POINTER(CPersistentInfo)]
     L.visma_icp_get_timing_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
@@ -1441,6 +1504,36 @@ class Context:
         self._chk(self.L.visma_icp_color_map_create(self._h, int(w), int(h), int(n_images), _p(k, _dp),
                                                     None if option is None else C.byref(option), C.byref(m)))
         return ColorMap(self, m, w, h, n_images)
+
+    def color_map_non_rigid(self, w, h, n_images, intrinsic, option=None):
+        """The NON-RIGID ColorMapOptimization as staged calls -> ColorMap with a warping field per image (anchor_shape, flow,
+        set_flow, cell_sums, step_non_rigid).  The anchors and the weight come from `option`, whatever its flag says."""
+        k = _f64(intrinsic, (4,))
+        m = C.c_void_p()
+        self._chk(self.L.visma_icp_color_map_create_non_rigid(self._h, int(w), int(h), int(n_images), _p(k, _dp),
+                                                              None if option is None else C.byref(option), C.byref(m)))
+        return ColorMap(self, m, w, h, n_images)
+
+    def color_map_optimization_non_rigid(self, vertices, depths, colors, intrinsic, extrinsics, option=None):
+        """The non-rigid ColorMapOptimization in one call (arguments as color_map_optimization)
+        -> (refined extrinsics n x 4 x 4, vertex colours m x 3, flows n x (anchor_w anchor_h 2))."""
+        depths = np.ascontiguousarray(depths, dtype=np.float32)
+        colors = np.ascontiguousarray(colors, dtype=np.uint8)
+        if depths.ndim != 3 or colors.shape != depths.shape + (3,):
+            raise ValueError("depths n x h x w and colors n x h x w x 3")
+        n, h, w = depths.shape
+        anchors = 16 if option is None else int(option.number_of_vertical_anchors)
+        if anchors < 2 or anchors > 64:
+            raise IcpError(1, "number_of_vertical_anchors outside 2 .. 64")
+        aw = int(np.ceil(float(w) / (float(h) / (anchors - 1))) + 1)
+        v = _f64(vertices, (-1, 3)); k = _f64(intrinsic, (4,))
+        E = _f64(extrinsics, (n * 16,)).copy()
+        out, flow = np.empty((len(v), 3)), np.empty((n, aw * anchors * 2))
+        self._chk(self.L.visma_icp_color_map_optimization_non_rigid(self._h, w, h, n, _p(k, _dp), _p(depths, _fp),
+                                                                    colors.ctypes.data_as(C.POINTER(C.c_uint8)), _p(E, _dp), _p(v, _dp),
+                                                                    len(v), None if option is None else C.byref(option), _p(out, _dp),
+                                                                    _p(flow, _dp)))
+        return E.reshape(n, 4, 4), out, flow
 
     def color_map_optimization(self, vertices, depths, colors, intrinsic, extrinsics, option=None):
         """ColorMapOptimization in one call: depths n x h x w fp32, colors n x h x w x 3 uint8, extrinsics n x 4 x 4

@@ -24,8 +24,11 @@
 //               proxy (8 B), four texels (64 B); it never reads the bit matrix.  The 6 x 6 solve and the pose update run on
 //               the host (host_math.hpp) with one read-back per iteration.
 //  colours      one lane per vertex, as the proxy, from the RGB8 images.
-// (Reasoning: DESIGN.md 4.4c12.)
+// The non-rigid variant (a warping field per image) shares this object: its vertex passes are the WARP instantiations here,
+// its iteration is colormap_warp.hip.
+// (Reasoning: DESIGN.md 4.4c12, 4.4c13.)
 #include "kernels.h"
+#include "colormap_device.h"
 #include "compact.h"
 #include "device_common.h"
 #include "host_math.hpp"
@@ -37,10 +40,6 @@
 namespace visma {
 
 namespace {
-
-constexpr double kCmMargin = 10.0;                       // IMAGE_BOUNDARY_MARGIN
-
-struct CmCamera { double fx, fy, cx, cy; int w, h; };
 
 __global__ __launch_bounds__(kThreads) void cm_gray_kernel(const unsigned char *__restrict__ rgb, float *__restrict__ out, long long n)
 {
@@ -97,12 +96,6 @@ __device__ __forceinline__ void cm_project(const double *__restrict__ E, const C
     *z = (float)t2;
 }
 
-// TestImageBoundary(u, v, 10) on doubles; a NaN fails
-__device__ __forceinline__ bool cm_inside(double u, double v, const CmCamera &K)
-{
-    return u >= kCmMargin && u < (double)K.w - kCmMargin && v >= kCmMargin && v < (double)K.h - kCmMargin;
-}
-
 // the compaction's Source: item i = c * nvp + v
 struct VisibilitySource {
     const double *vertices;          // n_vertices x 3
@@ -138,6 +131,8 @@ struct VisibilitySource {
     }
 };
 
+inline unsigned cm_blocks(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
 struct VertexPassArgs {
     const double *vertices, *extrinsics;
     const unsigned *bits;
@@ -147,10 +142,14 @@ struct VertexPassArgs {
     long long nv;
     int words, n_cameras;
     double *out;                     // proxy: nv; colours: nv x 3
+    const double *flow;              // WARP: n_cameras fields of 2 aw ah
+    int aw, ah;
+    double step;
 };
 
 // COLOR false: the proxy intensity; true: the colour average.  One lane per vertex, its cameras in ascending id.
-template <bool COLOR>
+// WARP (the non-rigid map): the pixel is the field's shift of (u, v), after a margin test of its own.
+template <bool COLOR, bool WARP>
 __global__ __launch_bounds__(kThreads) void cm_vertex_kernel(VertexPassArgs a)
 {
     const long long j = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -169,7 +168,20 @@ __global__ __launch_bounds__(kThreads) void cm_vertex_kernel(VertexPassArgs a)
             cm_project(a.extrinsics + 16 * c, a.K, X, Y, Z, &u, &v, &z);
             if (!cm_inside((double)u, (double)v, a.K)) continue;
             // inside the margin: the rounded pixel is inside the image
-            const long long p = (long long)c * plane + (long long)(int)roundf(v) * a.K.w + (int)roundf(u);
+            long long p;
+            if (WARP) {
+                // 10 <= u < w - 10 puts (int)(u / step) in 0 .. aw - 2 (aw - 1 >= w / step): the clamp never acts
+                const double du = (double)u, dv = (double)v;
+                int ci = (int)(du / a.step), cj = (int)(dv / a.step);
+                ci = ci < a.aw - 2 ? ci : a.aw - 2; cj = cj < a.ah - 2 ? cj : a.ah - 2;
+                const double pp = (du - ci * a.step) / a.step, qq = (dv - cj * a.step) / a.step;
+                double su, sv;
+                cm_warp_shift(cm_warp_cell(a.flow + (long long)c * 2 * a.aw * a.ah, a.aw, ci, cj), pp, qq, &su, &sv);
+                if (!cm_inside(su, sv, a.K)) continue;
+                p = (long long)c * plane + (long long)(int)round(sv) * a.K.w + (int)round(su);
+            } else {
+                p = (long long)c * plane + (long long)(int)roundf(v) * a.K.w + (int)roundf(u);
+            }
             if (COLOR) {
                 const unsigned char *q = a.rgb + 3 * p;
                 s0 += (double)((float)q[0] / 255.0f); s1 += (double)((float)q[1] / 255.0f); s2 += (double)((float)q[2] / 255.0f);
@@ -259,44 +271,11 @@ __global__ __launch_bounds__(kPairThreads) void cm_iteration_kernel(IterationArg
     if (tid < kPairRow) a.sums[(long long)cam * kPairRow + tid] = tid < kCmAcc ? f_tot[tid] : 0.0;
 }
 
-inline unsigned cm_blocks(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-template <class T>
-hipError_t cm_alloc(T **p, size_t n)
-{
-    return hipMalloc((void **)p, sizeof(T) * (n ? n : 1));
-}
-
 }  // namespace
 
-struct ColorMapDevice {
-    ColorMapConfig cfg;
-    hipStream_t stream = nullptr;
-    CmCamera K;
-    long long plane = 0, nv = 0, nvp = 0;
-    int words = 0, blocks = 1;
-    // the frames
-    float *depth = nullptr;
-    unsigned char *rgb = nullptr, *mask = nullptr;
-    float4 *texels = nullptr;
-    double *extrinsics = nullptr;    // the CURRENT poses; host_extr is their copy
-    double *extr0 = nullptr;         // the poses of prepare (what visibility read)
-    std::vector<double> host_extr;
-    // per image scratch: five fp32 planes and two mask planes
-    float *tmp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned char *mtmp[2] = {nullptr, nullptr};
-    // the vertices and what hangs off them
-    double *vertices = nullptr, *proxy = nullptr, *colors = nullptr;
-    unsigned *bits = nullptr;
-    int32_t *list = nullptr;
-    long long *offsets = nullptr;
-    std::vector<long long> host_offsets;
-    Compactor compactor;
-    // the iteration
-    double *partials = nullptr, *sums = nullptr;
-    unsigned *tickets = nullptr;
-    bool proxy_valid = false;
-};
+namespace cm {
+struct CmCompactor { Compactor c; };
+}  // namespace cm
 
 void color_map_device_destroy(ColorMapDevice *D)
 {
@@ -305,13 +284,15 @@ void color_map_device_destroy(ColorMapDevice *D)
                    D->mtmp[0], D->mtmp[1], D->vertices, D->proxy, D->colors, D->bits, D->list, D->offsets, D->partials, D->sums, D->tickets};
     for (void *p : all)
         if (p) (void)hipFree(p);
-    D->compactor.release();
+    color_map_warp_release(D);
+    if (D->compactor) { D->compactor->c.release(); delete D->compactor; }
     delete D;
 }
 
 hipError_t color_map_device_create(const ColorMapConfig &cfg, hipStream_t stream, ColorMapDevice **out)
 {
     ColorMapDevice *D = new ColorMapDevice;
+    D->compactor = new CmCompactor;
     D->cfg = cfg; D->stream = stream;
     D->K = CmCamera{cfg.fx, cfg.fy, cfg.cx, cfg.cy, cfg.w, cfg.h};
     D->plane = (long long)cfg.w * cfg.h;
@@ -329,6 +310,7 @@ hipError_t color_map_device_create(const ColorMapConfig &cfg, hipStream_t stream
     if (e == hipSuccess) e = cm_alloc(&D->sums, n * kPairRow);
     if (e == hipSuccess) e = cm_alloc(&D->tickets, n);
     if (e == hipSuccess) e = hipMemsetAsync(D->tickets, 0, sizeof(unsigned) * n, stream);
+    if (e == hipSuccess && cfg.anchors > 0) e = color_map_warp_create(D);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) { color_map_device_destroy(D); return e; }
     D->host_extr.assign(n * 16, 0.0);
@@ -413,19 +395,19 @@ hipError_t color_map_device_prepare(ColorMapDevice *D, int64_t *counts)
     src.list = nullptr; src.bits = D->bits;
     const long long items = (long long)n * D->nvp;
     long long rows = 0;
-    e = D->compactor.count(src, items, s, &rows);
+    e = D->compactor->c.count(src, items, s, &rows);
     if (e != hipSuccess) return e;
     if (D->list) { (void)hipFree(D->list); D->list = nullptr; }
     e = cm_alloc(&D->list, (size_t)rows);
     if (e != hipSuccess) return e;
     src.list = D->list;
-    e = D->compactor.write(src, items, s);
+    e = D->compactor->c.write(src, items, s);
     if (e != hipSuccess) return e;
     // camera c's list begins where its first tile does
     D->host_offsets.assign((size_t)n + 1, rows);
     const long long tiles_per_camera = D->nvp / kThreads;
     for (int c = 0; c < n && tiles_per_camera > 0 && e == hipSuccess; c++)
-        e = hipMemcpyAsync(&D->host_offsets[(size_t)c], D->compactor.tile_offset + c * tiles_per_camera, sizeof(long long),
+        e = hipMemcpyAsync(&D->host_offsets[(size_t)c], D->compactor->c.tile_offset + c * tiles_per_camera, sizeof(long long),
                            hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -439,6 +421,7 @@ hipError_t color_map_device_prepare(ColorMapDevice *D, int64_t *counts)
     e = cm_alloc(&D->partials, (size_t)n * D->blocks * kPairRow);
     if (e == hipSuccess) e = hipMemcpyAsync(D->offsets, D->host_offsets.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && D->warp) e = color_map_warp_prepare(D);
     D->proxy_valid = false;
     return e;
 }
@@ -485,17 +468,22 @@ static VertexPassArgs cm_vertex_args(ColorMapDevice *D, double *out)
     VertexPassArgs a;
     a.vertices = D->vertices; a.extrinsics = D->extrinsics; a.bits = D->bits; a.texels = D->texels; a.rgb = D->rgb; a.K = D->K;
     a.nv = D->nv; a.words = D->words; a.n_cameras = D->cfg.n_images; a.out = out;
+    a.flow = D->flow; a.aw = D->aw; a.ah = D->ah; a.step = D->step;
     return a;
 }
 
 // the poses on the device and the proxies of them
-static hipError_t cm_refresh_proxy(ColorMapDevice *D)
+hipError_t cm_refresh_proxy(ColorMapDevice *D)
 {
     if (D->proxy_valid) return hipSuccess;
     hipError_t e = cm_upload_extrinsics(D);
+    if (e == hipSuccess && D->warp) e = color_map_warp_upload_flow(D);
     if (e != hipSuccess) return e;
     if (D->nv > 0) {
-        hipLaunchKernelGGL(cm_vertex_kernel<false>, dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->proxy));
+        if (D->warp)
+            hipLaunchKernelGGL((cm_vertex_kernel<false, true>), dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->proxy));
+        else
+            hipLaunchKernelGGL((cm_vertex_kernel<false, false>), dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->proxy));
         e = hipGetLastError();
     }
     // (the upload's source is host_extr: it must not change before the copy has run)
@@ -564,9 +552,13 @@ hipError_t color_map_device_step(ColorMapDevice *D, double *rr, int64_t *count)
 hipError_t color_map_device_get_colors(ColorMapDevice *D, double *out)
 {
     hipError_t e = cm_upload_extrinsics(D);
+    if (e == hipSuccess && D->warp) e = color_map_warp_upload_flow(D);
     if (e != hipSuccess) return e;
     if (D->nv == 0) return hipStreamSynchronize(D->stream);
-    hipLaunchKernelGGL(cm_vertex_kernel<true>, dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->colors));
+    if (D->warp)
+        hipLaunchKernelGGL((cm_vertex_kernel<true, true>), dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->colors));
+    else
+        hipLaunchKernelGGL((cm_vertex_kernel<true, false>), dim3(cm_blocks(D->nv)), dim3(kThreads), 0, D->stream, cm_vertex_args(D, D->colors));
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, D->colors, sizeof(double) * 3 * (size_t)D->nv, hipMemcpyDeviceToHost, D->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(D->stream);

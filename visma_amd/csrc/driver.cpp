@@ -2,6 +2,7 @@
 // batched forms, options, multi-GPU bring-up.  (Engine / HipEngine: engine.hpp, hip_engine.cpp; the steps either
 // side of ICP: aux_api.cpp; the corpus work queue: corpus.cpp.)
 #include "driver_ctx.hpp"
+#include "colormap_solve.hpp"
 #ifdef VISMA_TEST_SEAMS
 #include "../../include/visma_icp_testing.h"
 #endif
@@ -1966,9 +1967,9 @@ static int check_color_map(visma_icp_ctx *ctx, visma_icp_color_map *map, int sta
     return ctx->fail(VISMA_ICP_ERR_INVALID, "not a color map of this context");
 }
 
-static int check_color_map_option(visma_icp_ctx *ctx, const visma_icp_color_map_option &o)
+static int check_color_map_option(visma_icp_ctx *ctx, const visma_icp_color_map_option &o, bool non_rigid)
 {
-    if (o.non_rigid_camera_coordinate) return ctx->fail(VISMA_ICP_ERR_INVALID, "the non-rigid color map optimization is not built");
+    if (!non_rigid && o.non_rigid_camera_coordinate) return ctx->fail(VISMA_ICP_ERR_INVALID, "non_rigid_camera_coordinate is set: the non-rigid optimization has entry points of its own, visma_icp_color_map_create_non_rigid and visma_icp_color_map_optimization_non_rigid");
     if (std::isnan(o.maximum_iteration) || std::isnan(o.maximum_allowable_depth) || std::isnan(o.depth_threshold_for_visiblity_check) ||
         std::isnan(o.depth_threshold_for_discontinuity_check))
         return ctx->fail(VISMA_ICP_ERR_INVALID, "an option that is not a number");
@@ -1983,10 +1984,10 @@ static int check_color_map_option(visma_icp_ctx *ctx, const visma_icp_color_map_
         if (rc__) return ctx->eng_fail(rc__);                                                               \
     } while (0)
 
-int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
-                               const visma_icp_color_map_option *option, visma_icp_color_map **out)
+// create and create_non_rigid
+static int color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                            const visma_icp_color_map_option *option, bool non_rigid, visma_icp_color_map **out)
 {
-    CTX_CHECK();
     if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
     *out = nullptr;
     if (!intrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
@@ -2000,7 +2001,17 @@ int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, c
     visma_icp_color_map_option o;
     visma_icp_color_map_option_default(&o);
     if (option) o = *option;
-    if (int rc = check_color_map_option(ctx, o)) return rc;
+    if (int rc = check_color_map_option(ctx, o, non_rigid)) return rc;
+    int aw = 0, ah = 0;
+    double step = 0.0;
+    if (non_rigid) {                                     // (the flag field is not read: these entry points ARE the flag)
+        if (o.number_of_vertical_anchors < 2 || o.number_of_vertical_anchors > 64)
+            return ctx->fail(VISMA_ICP_ERR_INVALID, "number_of_vertical_anchors outside 2 .. 64");
+        cm_warp_shape(w, h, o.number_of_vertical_anchors, &aw, &ah, &step);
+        if ((int64_t)aw * ah > kCmWarpMaxAnchors) return ctx->fail(VISMA_ICP_ERR_INVALID, "more than 8192 anchors per image");
+        if (!std::isfinite(o.non_rigid_anchor_point_weight) || o.non_rigid_anchor_point_weight < 0.0)
+            return ctx->fail(VISMA_ICP_ERR_INVALID, "non_rigid_anchor_point_weight must be finite and not negative");
+    }
     if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "color map optimization runs on one rank");
     std::unique_ptr<visma_icp_color_map> m(new visma_icp_color_map);
     m->cfg.w = w; m->cfg.h = h; m->cfg.n_images = n_images;
@@ -2010,11 +2021,29 @@ int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, c
     m->cfg.half_dilation = o.half_dilation_kernel_size_for_discontinuity_map;
     m->iterations = o.maximum_iteration > 0.0 ? (o.maximum_iteration < 1e9 ? (int)std::ceil(o.maximum_iteration) : 1000000000) : 0;
     m->image_set.assign((size_t)n_images, 0);
+    if (non_rigid) {
+        m->non_rigid = true; m->anchor_w = aw; m->anchor_h = ah; m->anchor_step = step;
+        m->cfg.anchors = o.number_of_vertical_anchors; m->cfg.anchor_weight = o.non_rigid_anchor_point_weight;
+    }
     int rc = ctx->eng->color_map_create(m->cfg, &m->id);
     if (rc) return ctx->eng_fail(rc);
     *out = m.get();
     ctx->color_maps.push_back(std::move(m));
     return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_create(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                               const visma_icp_color_map_option *option, visma_icp_color_map **out)
+{
+    CTX_CHECK();
+    return color_map_create(ctx, w, h, n_images, intrinsic, option, false, out);
+}
+
+int visma_icp_color_map_create_non_rigid(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                         const visma_icp_color_map_option *option, visma_icp_color_map **out)
+{
+    CTX_CHECK();
+    return color_map_create(ctx, w, h, n_images, intrinsic, option, true, out);
 }
 
 int visma_icp_color_map_destroy(visma_icp_ctx *ctx, visma_icp_color_map *map)
@@ -2113,6 +2142,7 @@ int visma_icp_color_map_sums(visma_icp_ctx *ctx, visma_icp_color_map *map, doubl
     CTX_CHECK();
     if (int rc = check_color_map(ctx, map, 1)) return rc;
     if (!sums) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (map->non_rigid) return ctx->fail(VISMA_ICP_ERR_INVALID, "a non-rigid color map has cell sums: visma_icp_color_map_cell_sums");
     COLOR_MAP_CALL(map, color_map_device_sums(D, sums));
     return VISMA_ICP_OK;
 }
@@ -2122,7 +2152,80 @@ int visma_icp_color_map_step(visma_icp_ctx *ctx, visma_icp_color_map *map, doubl
     CTX_CHECK();
     if (int rc = check_color_map(ctx, map, 1)) return rc;
     if (!rr || !count) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    if (map->non_rigid) {
+        std::vector<double> reg((size_t)map->cfg.n_images);
+        COLOR_MAP_CALL(map, color_map_device_step_non_rigid(D, rr, reg.data(), count));
+        return VISMA_ICP_OK;
+    }
     COLOR_MAP_CALL(map, color_map_device_step(D, rr, count));
+    return VISMA_ICP_OK;
+}
+
+// the calls of a non-rigid map alone
+static int check_non_rigid(visma_icp_ctx *ctx, visma_icp_color_map *map, int stage)
+{
+    if (int rc = check_color_map(ctx, map, stage)) return rc;
+    if (!map->non_rigid) return ctx->fail(VISMA_ICP_ERR_INVALID, "not a non-rigid color map (visma_icp_color_map_create_non_rigid makes one)");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_anchor_shape(visma_icp_ctx *ctx, visma_icp_color_map *map, int *anchor_w, int *anchor_h, double *anchor_step)
+{
+    CTX_CHECK();
+    if (int rc = check_non_rigid(ctx, map, 0)) return rc;
+    if (anchor_w) *anchor_w = map->anchor_w;
+    if (anchor_h) *anchor_h = map->anchor_h;
+    if (anchor_step) *anchor_step = map->anchor_step;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_get_flow(visma_icp_ctx *ctx, visma_icp_color_map *map, double *flow)
+{
+    CTX_CHECK();
+    if (int rc = check_non_rigid(ctx, map, 0)) return rc;
+    if (!flow) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    COLOR_MAP_CALL(map, color_map_device_get_flow(D, flow));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_set_flow(visma_icp_ctx *ctx, visma_icp_color_map *map, const double *flow)
+{
+    CTX_CHECK();
+    if (int rc = check_non_rigid(ctx, map, 0)) return rc;
+    if (!flow) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    COLOR_MAP_CALL(map, color_map_device_set_flow(D, flow));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_cell_sums(visma_icp_ctx *ctx, visma_icp_color_map *map, double *sums)
+{
+    CTX_CHECK();
+    if (int rc = check_non_rigid(ctx, map, 1)) return rc;
+    if (!sums) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    COLOR_MAP_CALL(map, color_map_device_cell_sums(D, sums));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_step_non_rigid(visma_icp_ctx *ctx, visma_icp_color_map *map, double *rr, double *rr_reg, int64_t *count)
+{
+    CTX_CHECK();
+    if (int rc = check_non_rigid(ctx, map, 1)) return rc;
+    if (!rr || !rr_reg || !count) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    COLOR_MAP_CALL(map, color_map_device_step_non_rigid(D, rr, rr_reg, count));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_color_map_solve_non_rigid(int anchor_w, int anchor_h, const double *cell_sums, int64_t n_vertex, double weight_option,
+                                        const double *flow, const double *flow_init, double *x, double *rr_reg, int *kept)
+{
+    if (anchor_w < 2 || anchor_h < 2 || (int64_t)anchor_w * anchor_h > kCmWarpMaxAnchors) return VISMA_ICP_ERR_INVALID;
+    if (!cell_sums || !flow || !flow_init || !x || n_vertex < 1) return VISMA_ICP_ERR_INVALID;
+    if (!std::isfinite(weight_option) || weight_option < 0.0) return VISMA_ICP_ERR_INVALID;
+    double rr = 0.0, reg = 0.0;
+    int64_t count = 0;
+    const bool moved = cm_warp_solve_camera(anchor_w, anchor_h, cell_sums, (double)n_vertex, weight_option, flow, flow_init, x, &rr, &reg, &count);
+    if (rr_reg) *rr_reg = reg;
+    if (kept) *kept = moved ? 0 : 1;
     return VISMA_ICP_OK;
 }
 
@@ -2135,7 +2238,12 @@ int visma_icp_color_map_run(visma_icp_ctx *ctx, visma_icp_color_map *map, int k,
     std::vector<double> rr(n);
     std::vector<int64_t> count(n);
     for (int it = 0; it < k; it++) {
-        COLOR_MAP_CALL(map, color_map_device_step(D, rr.data(), count.data()));
+        if (map->non_rigid) {
+            std::vector<double> reg(n);
+            COLOR_MAP_CALL(map, color_map_device_step_non_rigid(D, rr.data(), reg.data(), count.data()));
+        } else {
+            COLOR_MAP_CALL(map, color_map_device_step(D, rr.data(), count.data()));
+        }
         if (residual) {
             double s = 0.0;
             for (double v : rr) s += v;
@@ -2175,15 +2283,15 @@ int visma_icp_color_map_get_colors(visma_icp_ctx *ctx, visma_icp_color_map *map,
     return VISMA_ICP_OK;
 }
 
-int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4], const float *depth,
-                                     const uint8_t *color, double *extrinsics, const double *vertices, int64_t n,
-                                     const visma_icp_color_map_option *option, double *colors)
+// optimization and optimization_non_rigid
+static int color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4], const float *depth,
+                                  const uint8_t *color, double *extrinsics, const double *vertices, int64_t n,
+                                  const visma_icp_color_map_option *option, double *colors, bool non_rigid, double *flow)
 {
-    CTX_CHECK();
     if (!depth || !color || !extrinsics || !vertices || !colors) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
     if (n < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "no vertices");
     visma_icp_color_map *map = nullptr;
-    int rc = visma_icp_color_map_create(ctx, w, h, n_images, intrinsic, option, &map);
+    int rc = color_map_create(ctx, w, h, n_images, intrinsic, option, non_rigid, &map);
     if (rc) return rc;
     const size_t px = (size_t)w * h;
     for (int i = 0; i < n_images && !rc; i++)
@@ -2193,10 +2301,27 @@ int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_ima
     if (!rc) rc = visma_icp_color_map_run(ctx, map, -1, nullptr);
     if (!rc) rc = visma_icp_color_map_get_colors(ctx, map, colors, n);
     if (!rc) rc = visma_icp_color_map_get_extrinsics(ctx, map, extrinsics);
+    if (!rc && non_rigid && flow) rc = visma_icp_color_map_get_flow(ctx, map, flow);
     const std::string err = ctx->err;
     (void)visma_icp_color_map_destroy(ctx, map);
     if (rc) ctx->err = err;
     return rc;
+}
+
+int visma_icp_color_map_optimization(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4], const float *depth,
+                                     const uint8_t *color, double *extrinsics, const double *vertices, int64_t n,
+                                     const visma_icp_color_map_option *option, double *colors)
+{
+    CTX_CHECK();
+    return color_map_optimization(ctx, w, h, n_images, intrinsic, depth, color, extrinsics, vertices, n, option, colors, false, nullptr);
+}
+
+int visma_icp_color_map_optimization_non_rigid(visma_icp_ctx *ctx, int w, int h, int n_images, const double intrinsic[4],
+                                               const float *depth, const uint8_t *color, double *extrinsics, const double *vertices,
+                                               int64_t n, const visma_icp_color_map_option *option, double *colors, double *flow)
+{
+    CTX_CHECK();
+    return color_map_optimization(ctx, w, h, n_images, intrinsic, depth, color, extrinsics, vertices, n, option, colors, true, flow);
 }
 
 int visma_icp_set_nn_mode(visma_icp_ctx *ctx, int nn_mode)

@@ -20,6 +20,9 @@ struct visma_icp_color_map {
     std::vector<char> image_set;      // per frame: set since create
     int64_t n_vertices = -1;          // -1: no vertices yet
     bool prepared = false;
+    bool non_rigid = false;           // made by visma_icp_color_map_create_non_rigid: a warping field per image
+    int anchor_w = 0, anchor_h = 0;
+    double anchor_step = 0.0;
 };
 
 // ---- the driver -----------------------------------------------------------------

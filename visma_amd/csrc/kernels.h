@@ -740,6 +740,8 @@ struct ColorMapConfig {
     double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
     double max_depth = 2.5, visibility_threshold = 0.03, discontinuity_threshold = 0.1;
     int half_dilation = 3;
+    int anchors = 0;                                   // > 0: a NON-RIGID map (colormap_warp.hip) with that many vertical anchors
+    double anchor_weight = 0.316;                      // ... and its non_rigid_anchor_point_weight
 };
 struct ColorMapDevice;
 // allocates the frames' buffers; nothing is left allocated where it fails
@@ -763,6 +765,13 @@ hipError_t color_map_device_sums(ColorMapDevice *D, double *rows);
 // keeps its pose)
 hipError_t color_map_device_step(ColorMapDevice *D, double *rr, int64_t *count);
 hipError_t color_map_device_get_colors(ColorMapDevice *D, double *out);               // n_vertices x 3, of the current poses
+// -- a non-rigid map (cfg.anchors > 0; colormap_warp.hip); hipErrorInvalidValue on a rigid one --
+hipError_t color_map_device_get_flow(const ColorMapDevice *D, double *out);           // n_images x 2 aw ah
+hipError_t color_map_device_set_flow(ColorMapDevice *D, const double *in);
+// rows[n_images x (aw - 1)(ah - 1) x 121] at the current poses and fields; nothing moves
+hipError_t color_map_device_cell_sums(ColorMapDevice *D, double *rows);
+// one iteration of every camera: pose and field; rr, rr_reg, count [n_images] of the state BEFORE the step
+hipError_t color_map_device_step_non_rigid(ColorMapDevice *D, double *rr, double *rr_reg, int64_t *count);
 
 // ---- the colour side of colored ICP (color_gradient.hip, colored.hip) ----
 // I = (r + g + b) / 3.0 in f64, in that order (ColoredICP.cpp:94-95)
