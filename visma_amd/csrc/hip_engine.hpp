@@ -1,11 +1,23 @@
 // hip_engine.hpp -- class HipEngine: the product engine of the ICP driver (gfx950 kernels on one HIP stream).
 // Members, small inline methods and the declarations of the large ones, which live in
-//   hip_engine_clouds.cpp   uploads and layout, the radius-cell grid, buffers and pools, timing
+//   hip_engine_clouds.cpp   uploads and layout, the radius-cell grid, the growth of the buffers, timing
+//   dev_buf.h               DevPool and DevBuf<T>: who owns the device and pinned memory (host-only)
 //   hip_engine_passes.cpp   the per-pass launches, the fused fold, the device-resident loops (single, sweeps, batches)
 //   hip_engine_comm.cpp     the transports of the source- and target-sharded modes (IPC mailboxes, RCCL, exchanges)
 //   hip_engine.cpp          the factory
 #pragma once
 #include "engine.hpp"
+#include "dev_buf.h"
+
+// a DevBuf's reserve / reset: the allocator's error code takes HIP_TRY's way out (err_, VISMA_ICP_ERR_HIP)
+#define BUF_TRY(expr)                                                                      \
+    do {                                                                                   \
+        const int e__ = (expr);                                                            \
+        if (e__ != 0) {                                                                    \
+            err_ = std::string(#expr) + ": " + hipGetErrorString((hipError_t)e__);         \
+            return VISMA_ICP_ERR_HIP;                                                      \
+        }                                                                                  \
+    } while (0)
 
 namespace visma {
 namespace drv {
@@ -23,40 +35,15 @@ public:
         if (comm_) g_rccl.CommDestroy(comm_);
         for (int r = 0; r < ipc_n_; r++)
             if (r != ipc_rank_ && peers_.box[r]) (void)hipIpcCloseMemHandle(peers_.box[r]);
-        free_dev(d_mbox_); free_dev(d_ipc_flag_); free_dev(d_raw_); free_dev(d_sorted12_); free_dev(bt_sorted12_);
-        free_dev(d_pend_count_); free_dev(d_pend_q32_); free_dev(d_pend_q64_); free_dev(d_pend_best_); free_dev(d_pend_idx_);
         for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
-        free_dev(d_src_); free_dev(d_tgt_); free_dev(d_nrm_); free_dev(d_keys_); free_dev(d_gkeys_);
-        free_dev(d_claim_); free_dev(d_d64_);
-        free_dev(d_src64_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
-        free_dev(d_snrm_); free_dev(d_snrm64_);
-        free_dev(d_sint_); free_dev(d_tint_); free_dev(d_grad_);
-        for (int i = 0; i < 4; i++) if (pin_[i]) (void)hipHostFree(pin_[i]);
-        free_dev(d_idx_); free_dev(d_d2_); free_dev(d_pos_); free_dev(d_ru_); free_dev(d_partials_); free_dev(d_stats_);
-        if (d_vox_out_) (void)hipFree(d_vox_out_);
-        free_dev(d_box_); free_dev(d_sorted_); free_dev(d_cell_of_); free_dev(d_count_); free_dev(d_occ_); free_dev(d_ring_tab_);
-        free_dev(d_start_); free_dev(d_bsum_); free_dev(d_cand_); free_dev(d_state_);
-        free_dev(d_partials2_); free_dev(d_tickets_); free_dev(d_tstats_); free_dev(d_second_);
-        free_dev(bt_src_); free_dev(bt_idx_); free_dev(bt_d2_); free_dev(bt_pos_); free_dev(bt_tgt_); free_dev(bt_sorted_);
-        free_dev(bt_nrm_); free_dev(bt_nrm64_); free_dev(bt_raw_);
-        free_dev(bt_src64_); free_dev(bt_tgt64_); free_dev(bt_sorted64_);
-        free_dev(bt_cell_of_); free_dev(bt_count_); free_dev(bt_start_); free_dev(bt_bsum_); free_dev(bt_descs_);
-        if (h_state_) (void)hipHostFree(h_state_);
+        // (mapped host memory with a device alias of its own: freed by name, see the member block)
         if (h_stats_) (void)hipHostFree(h_stats_);
         if (h_cmd_ && !cmd_direct_) (void)hipHostFree(h_cmd_);
-        if (d_cmd_block_) (void)hipFree(d_cmd_block_);
         if (h_flag_) (void)hipHostFree(h_flag_);
-        free_dev(d_relay_); free_dev(d_timeline_); free_dev(d_peer_table_); free_dev(d_fold_tag_);
-        if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
-        free_dev(d_trim_mask_); free_dev(d_trim_order_); free_dev(d_rob_w_); free_dev(d_rob_r2_);
         pair_.release();
-        if (odo_.arena) (void)hipFree(odo_.arena);
         for (auto &v : tsdf_) tsdf_device_destroy(v.second);
         for (auto &v : color_maps_) color_map_device_destroy(v.second);
-        pool_trim(0);
-        if (d_raw_src_) (void)hipFree(d_raw_src_);
-        if (stream_src_) (void)hipStreamDestroy(stream_src_);
-        if (stream_) (void)hipStreamDestroy(stream_);
+        // (the owned buffers, the pool and then the two streams go with the members, in that order)
     }
 
     int init();
@@ -77,20 +64,17 @@ public:
         if (n > 0) HIP_TRY(hipMemcpy(out, d_vox_out_, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
         return VISMA_ICP_OK;
     }
-    double *d_vox_out_ = nullptr;
     int64_t vox_out_n_ = -1;
     int prepare_search(int64_t ns, bool want64, double max_dist) override;
     int64_t prepared_ns_ = -1;
     bool prepared_want64_ = false;
     int begin_raw_source(int64_t ns, bool want64, std::vector<int32_t> &order);
-    int ensure_raw(size_t points)
+    // room for `points` raw f64 triples (+ `spare` bytes) in d_raw_ or d_raw_src_; `busy`: the stream that may still read the old one
+    int ensure_raw(DevBuf<char> &raw, size_t points, size_t spare = 0, hipStream_t busy = nullptr)
     {
-        if (points * 24 > raw_bytes_) {
-            free_dev(d_raw_);
-            int rc = pool_alloc(&d_raw_, points * 24);
-            if (rc) return rc;
-            raw_bytes_ = points * 24;
-        }
+        if (points * 24 <= raw.count()) return VISMA_ICP_OK;
+        if (busy) HIP_TRY(hipStreamSynchronize(busy));
+        BUF_TRY(raw.reset(points * 24 + spare));
         return VISMA_ICP_OK;
     }
     int finish_raw_source(int64_t ns, const double *c, std::vector<int32_t> &order, const void *raw = nullptr, hipStream_t st = nullptr);
@@ -109,27 +93,24 @@ public:
     int set_source64(const Pt64 *src) override
     {
         HIP_TRY(hipSetDevice(device_));
-        free_dev(d_src64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
+        d_src64_.release(); d_sorted64_.release(); d_nrm64_.release();
         grid_valid_ = false;
         { int irc = invalidate_pos(); if (irc) return irc; }
         if (!src || !d_tgt64_) { err_ = "set_source64 without an f64 target"; return VISMA_ICP_ERR_STATE; }
-        { int prc = pool_alloc(&d_src64_, sizeof(Pt64) * (size_t)std::max<int64_t>(ns_, 1)); if (prc) return prc; }
+        BUF_TRY(d_src64_.reset((size_t)std::max<int64_t>(ns_, 1)));
         if (ns_ > 0) HIP_TRY(hipMemcpyAsync(d_src64_, src, sizeof(Pt64) * ns_, hipMemcpyHostToDevice, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
         return VISMA_ICP_OK;
     }
-    void *d_raw_ = nullptr;
-    size_t raw_bytes_ = 0;
-    void *d_sorted12_ = nullptr;                           // packed (x,y,z) copy of d_sorted_ for the exact search
     int set_clouds64(const Pt64 *src, const Pt64 *tgt) override
     {
         HIP_TRY(hipSetDevice(device_));
-        free_dev(d_src64_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
+        d_src64_.release(); d_tgt64_.release(); d_sorted64_.release(); d_nrm64_.release();
         grid_valid_ = false;                                     // the sorted f64 copy is built with the grid
         { int irc = invalidate_pos(); if (irc) return irc; }
         if (!src || !tgt) return VISMA_ICP_OK;
-        { int prc = pool_alloc(&d_src64_, sizeof(Pt64) * (size_t)std::max<int64_t>(ns_, 1)); if (prc) return prc; }
-        { int prc = pool_alloc(&d_tgt64_, sizeof(Pt64) * (size_t)std::max<int64_t>(nt_, 1)); if (prc) return prc; }
+        BUF_TRY(d_src64_.reset((size_t)std::max<int64_t>(ns_, 1)));
+        BUF_TRY(d_tgt64_.reset((size_t)std::max<int64_t>(nt_, 1)));
         if (ns_ > 0) HIP_TRY(hipMemcpyAsync(d_src64_, src, sizeof(Pt64) * ns_, hipMemcpyHostToDevice, stream_));
         if (nt_ > 0) HIP_TRY(hipMemcpyAsync(d_tgt64_, tgt, sizeof(Pt64) * nt_, hipMemcpyHostToDevice, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
@@ -143,8 +124,6 @@ public:
     // which exchange the fp32 keys of this path)
     bool brute_exact() const { return !use_grid_ && exact_ && d_src64_ && d_tgt64_ && !tshard_; }
     int ensure_second(int64_t ns_pad, int splits);
-    void *d_pend_count_ = nullptr, *d_pend_q32_ = nullptr, *d_pend_q64_ = nullptr, *d_pend_best_ = nullptr,
-         *d_pend_idx_ = nullptr;
     BruteExact bex_store_{};
     const BruteExact *bex_ptr()
     {
@@ -161,7 +140,7 @@ public:
         e.second = (const float *)d_second_;
         e.nt = nt_;
         e.pend = BrutePend{};
-        if (d_pend_count_ && 2 * reduce_max_blocks() <= (int)partial_rows_) {
+        if (d_pend_count_ && 2 * reduce_max_blocks() <= (int)partial_rows()) {
             e.pend.count = (int *)d_pend_count_;
             e.pend.q32 = (float4 *)d_pend_q32_;
             e.pend.q64 = (Pt64 *)d_pend_q64_;
@@ -176,18 +155,11 @@ public:
     float *staging(int slot, size_t nfloats) override
     {
         slot &= 3;
-        if (pin_cap_[slot] < nfloats) {
-            if (pin_[slot]) (void)hipHostFree(pin_[slot]);
-            pin_[slot] = nullptr;
-            pin_cap_[slot] = 0;
-            const size_t want = nfloats + nfloats / 4 + 1024;
-            if (hipSetDevice(device_) != hipSuccess ||
-                hipHostMalloc((void **)&pin_[slot], want * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+        if (pin_[slot].count() < nfloats) {
+            if (hipSetDevice(device_) != hipSuccess || pin_[slot].reset(nfloats + nfloats / 4 + 1024) != 0) {
                 (void)hipGetLastError();
-                pin_[slot] = nullptr;
                 return Engine::staging(slot, nfloats);     // pageable memory still works, only slower
             }
-            pin_cap_[slot] = want;
         }
         return pin_[slot];
     }
@@ -231,8 +203,7 @@ public:
     {
         HIP_TRY(hipSetDevice(device_));
         if (nt != nt_) { err_ = "normals count != target count"; return VISMA_ICP_ERR_INVALID; }
-        free_dev(d_nrm_);
-        HIP_TRY(hipMalloc(&d_nrm_, sizeof(float4) * (nt > 0 ? nt : 1)));
+        BUF_TRY(d_nrm_.reset((size_t)(nt > 0 ? nt : 1)));
         if (nt > 0) HIP_TRY(hipMemcpy(d_nrm_, nxyzw, sizeof(float4) * nt, hipMemcpyHostToDevice));
         has_normals_ = true;
         drop_color_gradient();                                   // (it was computed with the previous normals)
@@ -313,8 +284,7 @@ public:
                        double *stats, TrimPass *out) override;
     int get_kept_mask(uint8_t *mask) override;
     bool is_sharded() const override { return comm_ != nullptr || ipc_n_ > 1 || tshard_ || minreduce_ != nullptr; }
-    void *d_trim_mask_ = nullptr, *d_trim_order_ = nullptr;
-    int64_t trim_mask_cap_ = 0, trim_order_cap_ = 0, trim_mask_ns_ = -1;
+    int64_t trim_mask_ns_ = -1;
     unsigned long long trim_order_gen_ = ~0ull;
     const int32_t *trim_order_src_ = nullptr;
 
@@ -322,13 +292,11 @@ public:
     int reduce_robust(const Mat4 &Tc, const double *offset, bool plane, const RobustConfig &cfg, double *stats,
                       RobustPass *out) override;
     int get_pair_weights(double *w) override;
-    void *d_rob_w_ = nullptr, *d_rob_r2_ = nullptr;
-    int64_t rob_w_cap_ = 0, rob_r2_cap_ = 0, rob_w_ns_ = -1;
+    int64_t rob_w_ns_ = -1;
 
     // generalized ICP (gicp.hip): the plain pass, then the reduction weighted by both points' surface covariances
     int set_source_normals(const float *nxyzw, const Pt64 *n64, int64_t ns) override;
     int reduce_gicp(const Mat4 &Tc, const double *offset, double epsilon, double *stats, GicpPass *out) override;
-    void *d_snrm_ = nullptr, *d_snrm64_ = nullptr;          // source normals by source position: fp32, and f64 next to d_src64_
 
     // information matrix (information.hip): the plain pass, then the ten sums over the target points of its pairs
     int reduce_information(const Mat4 &Tc, const double *offset, double *sums, PairPass *out) override;
@@ -365,16 +333,15 @@ public:
     int prepare_colored(double radius, int max_nn) override;
     int get_color_gradient(double *out) override;
     int reduce_colored(const Mat4 &Tc, const double *offset, double lambda, double *stats, ColoredPass *out) override;
-    void drop_color_gradient() override { free_dev(d_grad_); has_color_gradient_ = false; }
-    void *d_sint_ = nullptr, *d_tint_ = nullptr;            // one double per point: by source position, by original target index
-    void *d_grad_ = nullptr;                                // 3 doubles per target point, original order
+    void drop_color_gradient() override { d_grad_.release(); has_color_gradient_ = false; }
 
     // What a pass over the pairs of the last nn_pass works in.  The trimmed, robust, generalized and colored passes and the
     // information matrix share the one instance: they never overlap on the stream, and each pass re-arms the words it
     // used.  Sized by the constants every one of them is checked against (kernels.h, pair_pass.h).
     struct PairScratch {
-        unsigned *work = nullptr;                          // kTrimWorkWords: the select's histograms, 4 tickets, its state
-        double *partials = nullptr;                        // kPairMaxBlocks rows of kPairRow doubles
+        explicit PairScratch(const RawAlloc &raw) : work(raw), partials(raw) {}
+        DevBuf<unsigned> work;                             // kTrimWorkWords: the select's histograms, 4 tickets, its state
+        DevBuf<double> partials;                           // kPairMaxBlocks rows of kPairRow doubles
         double *host = nullptr, *host_dev = nullptr;       // mapped: kPairMaxPublished granules {value, sequence number}
         unsigned long long seq = 0;
         bool dirty = false;                                // a pass did not run to its end: the work words are cleared
@@ -382,7 +349,7 @@ public:
         hipError_t arm(hipStream_t stream);                // clear if dirty, mark dirty: call before a pass's first launch
         void disarm() { dirty = false; }                   // ... and this when its granules have arrived
         void release();
-    } pair_;
+    };
     // the checks and the plain pass under all of them: K and the sum of d^2 over all pairs in *out (`what`: "trimmed", ...)
     int pair_pass_begin(const char *what, const Mat4 &Tc, const double *offset, bool plane, PairPass *out);
     // the arguments the reductions share, the scratch and its ticket word included (a new sequence number)
@@ -450,9 +417,9 @@ private:
         float4 *tgt_xyz = nullptr;                           // level 0: the information matrix's target cloud
         int32_t *idx = nullptr;                              // w[0] * h[0]
         float *tmp[2] = {nullptr, nullptr};                  // w[0] * h[0] each: between the two passes of a filter
-        void *arena = nullptr;
-        size_t arena_bytes = 0;
-    } odo_;
+        explicit OdoState(const RawAlloc &raw) : arena(raw) {}
+        DevBuf<char> arena;
+    };
     // TSDF volumes: id -> device object; ids are never reused within an engine
     std::unordered_map<int, TsdfDevice *> tsdf_;
     int tsdf_next_id_ = 1;
@@ -466,44 +433,17 @@ private:
     // the arguments every pass over odo_.idx shares: no clouds, the scratch and its ticket word (a new sequence number)
     void odometry_pass_args(int level, PairPassArgs *a);
 
-    // Cloud-sized device buffers are recycled: a registration after another of about the same size
-    // (every caller's loop) re-uses them instead of paying hipFree + hipMalloc (a device sync and ~0.5 ms
-    // per 100 MB).  pool_alloc'ed pointers are returned by the ordinary free_dev.
-    std::unordered_map<void *, size_t> pool_live_;
-    std::vector<std::pair<void *, size_t>> pool_free_;
-    int pool_alloc(void **p, size_t bytes);
-    void pool_trim(size_t keep)
-    {
-        while (pool_free_.size() > keep) {
-            (void)hipFree(pool_free_.front().first);
-            pool_free_.erase(pool_free_.begin());
-        }
-    }
-    void free_dev(void *&p)
-    {
-        if (!p) return;
-        auto it = pool_live_.find(p);
-        if (it == pool_live_.end()) {
-            (void)hipFree(p);
-        } else {
-            pool_free_.push_back({p, it->second});
-            pool_live_.erase(it);
-            pool_trim(10);
-        }
-        p = nullptr;
-    }
     int ensure_source(int64_t ns)
     {
         if (ns < 0) { err_ = "negative point count"; return VISMA_ICP_ERR_INVALID; }
         if (ns > 0x7fffffff - 4096) { err_ = "source too large for 32-bit indices"; return VISMA_ICP_ERR_INVALID; }
-        free_dev(d_src_);
-        { int prc = pool_alloc(&d_src_, sizeof(float4) * (size_t)(ns > 0 ? ns : 1)); if (prc) return prc; }
+        BUF_TRY(d_src_.reset((size_t)(ns > 0 ? ns : 1)));
         ns_ = ns;
         have_pass_ = false;
-        free_dev(d_src64_);                                      // belongs to the previous source
-        free_dev(d_snrm_); free_dev(d_snrm64_);                  // ... and so do its normals
+        d_src64_.release();                                      // belongs to the previous source
+        d_snrm_.release(); d_snrm64_.release();                  // ... and so do its normals
         has_source_normals_ = false;
-        free_dev(d_sint_);                                       // ... and its colours
+        d_sint_.release();                                       // ... and its colours
         has_source_colors_ = false;
         return invalidate_pos();
     }
@@ -534,22 +474,87 @@ private:
     int collect_timing();
 
     int device_;
-    hipStream_t stream_ = nullptr;
+    // Both streams end after everything that ran on them is freed: declared before the pool and the buffers, so they go last.
+    struct Stream {
+        hipStream_t s = nullptr;
+        Stream() = default;
+        Stream(const Stream &) = delete;
+        Stream &operator=(const Stream &) = delete;
+        ~Stream() { if (s) (void)hipStreamDestroy(s); }
+        operator hipStream_t() const { return s; }
+    };
+    Stream stream_;
     // (round 6) the raw SOURCE upload -- copy, Morton order on the device, the permutation back -- runs on a stream of its
     // own, from a buffer of its own: it needs the target's centroid (known when the host has staged the last piece) and
     // nothing else of the target, so it overlaps the tail of the target's copies and the grid build that prepare_search
     // queued behind them (set_target_f64 no longer drains the stream on its way out).  VISMA_ICP_UPLOAD_OVERLAP=0: as before.
-    hipStream_t stream_src_ = nullptr;
-    void *d_raw_src_ = nullptr;
-    size_t raw_src_bytes_ = 0;
+    Stream stream_src_;
     int upload_overlap_ = 1;
-    void *d_src_ = nullptr, *d_tgt_ = nullptr, *d_nrm_ = nullptr, *d_keys_ = nullptr;
-    void *d_idx_ = nullptr, *d_d2_ = nullptr, *d_partials_ = nullptr, *d_stats_ = nullptr;
+
+    // ---- Owned memory (dev_buf.h).  Every DevBuf frees itself, through the allocator it was bound to here: the pool for
+    // the cloud-sized buffers that come and go with every registration, plain device memory for the rest, pinned host
+    // memory for the staging areas and the host copy of the loop states.  Members run down in reverse order -- buffers,
+    // then the pool, then the streams above -- after the destructor's body has bound the device.
+    // NOT owned this way, and freed or closed by name in the destructor:
+    //   peers_.box[r]                      the peers' mailboxes, opened through IPC
+    //   h_stats_, h_cmd_, h_flag_          mapped host memory; h_*_dev_ is the device's alias of the same block
+    //   pair_.host / host_dev              the same for the pair passes' granules
+    // d_mbox_ and d_cmd_block_ come from hipExtMallocWithFlags, d_vox_out_ and d_ring_tab_ from the module that fills
+    // them: plain hipFree memory that the buffer adopts.
+    static int device_alloc(void **p, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; }
+        return (int)e;
+    }
+    static void device_free(void *p) { (void)hipFree(p); }
+    static int pinned_alloc(void **p, size_t bytes)
+    {
+        const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; }
+        return (int)e;
+    }
+    static void pinned_free(void *p) { (void)hipHostFree(p); }
+    static RawAlloc device_memory() { return RawAlloc{&device_alloc, &device_free}; }
+    static RawAlloc pinned_memory() { return RawAlloc{&pinned_alloc, &pinned_free}; }
+    DevPool pool_{device_memory()};
+    // the clouds: fp32 and f64 copies, the target's cell-sorted copies (f64, packed fp32 for the exact search), the raw
+    // upload areas (target and mesh-sampled source on stream_, the uploaded source on stream_src_)
+    DevBuf<float4> d_src_{pool_}, d_tgt_{pool_};
+    DevBuf<Pt64> d_src64_{pool_}, d_tgt64_{pool_}, d_sorted64_{pool_};
+    DevBuf<float> d_sorted12_{pool_};
+    DevBuf<char> d_raw_{pool_}, d_raw_src_{device_memory()};
+    DevBuf<double> d_vox_out_{device_memory()};
+    DevBuf<float> pin_[4] = {DevBuf<float>(pinned_memory()), DevBuf<float>(pinned_memory()), DevBuf<float>(pinned_memory()),
+                             DevBuf<float>(pinned_memory())};   // pinned staging (see staging())
+    DevBuf<float4> d_nrm_{device_memory()}, d_snrm_{device_memory()};   // normals: target by index, source by position ...
+    DevBuf<Pt64> d_nrm64_{device_memory()}, d_snrm64_{device_memory()}; // ... and in f64 next to the f64 clouds
+    DevBuf<double> d_sint_{device_memory()}, d_tint_{device_memory()};  // one double per point: by source position, by original target index
+    DevBuf<double> d_grad_{device_memory()};                 // 3 doubles per target point, original order
+    // what a pass writes and folds
+    DevBuf<unsigned long long> d_keys_{device_memory()};
+    DevBuf<int32_t> d_idx_{device_memory()};
+    DevBuf<float> d_d2_{device_memory()};
+    DevBuf<double> d_partials_{device_memory()}, d_stats_{device_memory()};
+    size_t partial_rows() const { return d_partials_.count() / kReduceAcc; }
+    int ensure_partials(size_t rows) { BUF_TRY(d_partials_.reserve((size_t)kReduceAcc * rows)); return VISMA_ICP_OK; }
+    // the brute-force search's exact flavour: the queries its reduce kernel leaves to the rescan passes
+    DevBuf<int> d_pend_count_{device_memory()};
+    DevBuf<float4> d_pend_q32_{device_memory()};
+    DevBuf<Pt64> d_pend_q64_{device_memory()};
+    DevBuf<unsigned long long> d_pend_best_{device_memory()};
+    DevBuf<unsigned> d_pend_idx_{device_memory()};
+    // trimmed and robust passes
+    DevBuf<unsigned char> d_trim_mask_{device_memory()};
+    DevBuf<int32_t> d_trim_order_{device_memory()};
+    DevBuf<double> d_rob_w_{device_memory()};
+    DevBuf<float> d_rob_r2_{device_memory()};
+    PairScratch pair_{device_memory()};
+    OdoState odo_{device_memory()};
     double *h_stats_ = nullptr, *h_stats_dev_ = nullptr;
     unsigned long long pub_seq_ = 0;
     bool inited_ = false;
-    int64_t nt_pad_ = 0, ns_pad_ = 0, aux_cap_ = 0;
-    size_t keys_bytes_ = 0;
+    int64_t nt_pad_ = 0, ns_pad_ = 0;
     NNLaunch plan_{0, 0, 0};
     Xform32 T32_{};
     float r2f_ = 0.f;
@@ -560,20 +565,23 @@ private:
     int ev_used_ = 0;
     std::vector<std::pair<int, int>> pending_;
     visma_icp_timing timing_{};
-    void *d_src64_ = nullptr, *d_tgt64_ = nullptr, *d_sorted64_ = nullptr;   // double-precision search
-    void *d_nrm64_ = nullptr;
-    float *pin_[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned staging (see staging())
-    size_t pin_cap_[4] = {0, 0, 0, 0};
     NcclComm comm_ = nullptr;
-    void *d_mbox_ = nullptr, *d_ipc_flag_ = nullptr;      // peer-to-peer all-reduce: own mailbox, timeout flag
+    DevBuf<char> d_mbox_{device_memory()};                 // peer-to-peer all-reduce: own mailbox ...
+    DevBuf<int> d_ipc_flag_{device_memory()};              // ... and 16 bytes: {int timeout flag, pad, u64 exchange counter}
     IpcPeers peers_{};
     int ipc_rank_ = 0, ipc_n_ = 0;
     // (the exchange counter lives next to the timeout flag in device memory: d_ipc_flag_ + 8 bytes)
-    unsigned long long *ipc_seq_dev() const { return reinterpret_cast<unsigned long long *>((char *)d_ipc_flag_ + 8); }
+    unsigned long long *ipc_seq_dev() const { return reinterpret_cast<unsigned long long *>(d_ipc_flag_.get() + 2); }
     bool tshard_ = false;                 // target-sharded rank (else: source-sharded / single)
-    int64_t tgt_offset_ = 0, tgt_global_ = 0, gkeys_cap_ = 0;
-    void *d_gkeys_ = nullptr, *d_claim_ = nullptr, *d_d64_ = nullptr;   // shard exchange: keys, index claims, local f64 d2
-    int64_t d64_cap_ = 0;
+    int64_t tgt_offset_ = 0, tgt_global_ = 0;
+    DevBuf<unsigned long long> d_gkeys_{device_memory()}, d_claim_{device_memory()};   // shard exchange: keys, index claims ...
+    DevBuf<double> d_d64_{device_memory()};                                            // ... and the local f64 d2
+    int ensure_shard_keys()
+    {
+        BUF_TRY(d_gkeys_.reserve((size_t)ns_));
+        BUF_TRY(d_claim_.reserve((size_t)ns_));
+        return VISMA_ICP_OK;
+    }
     // target-sharded rank running the exact / f64 grid search: the buffer its f64 distances go to
     // Which exchange the sharded ranks run must not depend on what a rank happens to hold (an empty
     // shard, a degenerate grid): every rank with f64 clouds and without a forced brute-force search
@@ -582,12 +590,8 @@ private:
     double *shard_d64()
     {
         if (!shard_f64_protocol()) return nullptr;
-        if (ns_ > d64_cap_) {
-            free_dev(d_d64_);
-            if (hipMalloc(&d_d64_, sizeof(double) * std::max<int64_t>(ns_, 1)) != hipSuccess) { (void)hipGetLastError(); d_d64_ = nullptr; d64_cap_ = 0; return nullptr; }
-            d64_cap_ = ns_;
-        }
-        return (double *)d_d64_;
+        if (d_d64_.reserve((size_t)ns_) != 0) return nullptr;
+        return d_d64_;
     }
     std::vector<unsigned long long> h_gkeys_;
     visma_icp_minreduce_fn minreduce_ = nullptr;
@@ -597,26 +601,59 @@ private:
     bool use_grid_ = false, grid_valid_ = false, grid_pending_ = false, brute_reduced_ = false;
     double grid_radius_ = 0.0;
     GridParams grid_{};
-    void *d_box_ = nullptr, *d_sorted_ = nullptr, *d_cell_of_ = nullptr, *d_count_ = nullptr;
-    void *d_start_ = nullptr, *d_bsum_ = nullptr, *d_cand_ = nullptr;
-    void *d_state_ = nullptr;
-    DevIcpState *h_state_ = nullptr;
-    int state_cap_ = 0;
-    size_t partial_rows_ = 0;
+    DevBuf<unsigned> d_box_{device_memory()};
+    DevBuf<float4> d_sorted_{device_memory()};             // (+ kSortedSlack: batches read past a run's end)
+    DevBuf<unsigned> d_cell_of_{device_memory()};          // (cell, rank in the cell) per target point
+    DevBuf<unsigned> d_count_{device_memory()}, d_start_{device_memory()}, d_bsum_{device_memory()};
+    DevBuf<unsigned long long> d_cand_{device_memory()};
+    // device-resident loops: the problems' states on the device and their pinned host copy
+    DevBuf<DevIcpState> d_state_{device_memory()}, h_state_{pinned_memory()};
+    int ensure_states(int n)
+    {
+        BUF_TRY(d_state_.reserve((size_t)n));
+        BUF_TRY(h_state_.reserve((size_t)n));
+        return VISMA_ICP_OK;
+    }
+    // a problem's state as its loop starts (Tc0, the cloud centre, the number of source points over all ranks, r^2)
+    void fill_state(DevIcpState &h, const LoopParams &lp, const Mat4 &Tc0, const double centre[3], int64_t ns_total, float r2f)
+    {
+        std::memset(&h, 0, sizeof(h));
+        for (int i = 0; i < 12; i++) h.Tc[i] = Tc0.m[i];
+        for (int a = 0; a < 3; a++) h.centre[a] = centre[a];
+        h.rel_fit = lp.rel_fit; h.rel_rmse = lp.rel_rmse;
+        h.ns_total = ns_total;
+        h.active = 1;
+        h.max_iter = lp.max_iter; h.solver = lp.solver; h.scaling = lp.scaling ? 1 : 0;
+        h.plane = lp.plane ? 1 : 0; h.world_frame = lp.world ? 1 : 0;
+        h.check_stop = lp.check_stop ? 1 : 0;
+        h.r2f = r2f;
+        h.use_axis = lp.use_axis ? 1 : 0;
+        for (int a = 0; a < 3; a++) h.axis[a] = lp.axis[a];
+    }
+    // ... and what the first n states in h_state_ hold when it has ended
+    void read_results(int n, LoopResult *out)
+    {
+        for (int b = 0; b < n; b++) {
+            const DevIcpState &h = h_state_[b];
+            out[b].Tc = Mat4::identity();
+            for (int i = 0; i < 12; i++) out[b].Tc.m[i] = h.Tc[i];
+            out[b].fit = h.fit; out[b].rmse = h.rmse;
+            out[b].k = (int64_t)std::llround(h.K);
+            out[b].iters = h.iter; out[b].passes = h.passes;
+        }
+    }
     // batch of problems with their own clouds (concatenated arrays)
-    void *bt_src_ = nullptr, *bt_idx_ = nullptr, *bt_d2_ = nullptr, *bt_pos_ = nullptr, *bt_tgt_ = nullptr, *bt_sorted_ = nullptr;
-    void *bt_src64_ = nullptr, *bt_tgt64_ = nullptr, *bt_sorted64_ = nullptr;
-    int64_t bt_src64_cap_ = 0, bt_tgt64_cap_ = 0;
-    void *bt_sorted12_ = nullptr;                          // packed copy of bt_sorted_ (exact search)
-    int64_t bt_sorted12_cap_ = 0;
-    void *bt_raw_ = nullptr;                               // targets as uploaded (caller's f64 values)
-    size_t bt_raw_bytes_ = 0;
-    void *bt_nrm_ = nullptr, *bt_nrm64_ = nullptr;         // point-to-plane batches: target normals
-    int64_t bt_nrm_cap_ = 0, bt_nrm64_cap_ = 0;
-    void *bt_cell_of_ = nullptr, *bt_count_ = nullptr, *bt_start_ = nullptr, *bt_bsum_ = nullptr, *bt_descs_ = nullptr;
-    int64_t bt_src_cap_ = 0, bt_tgt_cap_ = 0, bt_cell_cap_ = 0, bt_out_cap_ = 0;
-    int bt_bsum_cap_ = 0;
-    size_t bt_desc_cap_ = 0;
+    DevBuf<float4> bt_src_{device_memory()}, bt_tgt_{device_memory()}, bt_sorted_{device_memory()};
+    DevBuf<int32_t> bt_idx_{device_memory()};
+    DevBuf<float> bt_d2_{device_memory()};
+    DevBuf<Pt64> bt_pos_{device_memory()};
+    DevBuf<Pt64> bt_src64_{device_memory()}, bt_tgt64_{device_memory()}, bt_sorted64_{device_memory()};
+    DevBuf<float> bt_sorted12_{device_memory()};           // packed copy of bt_sorted_ (exact search)
+    DevBuf<double> bt_raw_{device_memory()};               // targets as uploaded (caller's f64 values)
+    DevBuf<float4> bt_nrm_{device_memory()};               // point-to-plane batches: target normals
+    DevBuf<Pt64> bt_nrm64_{device_memory()};
+    DevBuf<unsigned> bt_cell_of_{device_memory()}, bt_count_{device_memory()}, bt_start_{device_memory()}, bt_bsum_{device_memory()};
+    DevBuf<char> bt_descs_{device_memory()};
     std::vector<char> bt_desc_host_;                       // (kept: the copy is asynchronous)
     int64_t view_offset_ = 0, loop_out_stride_ = 0;
     static constexpr int kGridMaxBlocks = 32768;   // (8 M queries at one per lane: the warm kernel keeps 4 waves per SIMD only there)
@@ -675,13 +712,13 @@ private:
     // changes) -- so any pass may read it; pos_fresh_ only says that some pass has filled it since (policy:
     // the first pass of a registration runs the lane-serial kernel, which prunes progressively; the later ones
     // the warm-started kernel).
-    void *d_pos_ = nullptr;
+    DevBuf<Pt64> d_pos_{device_memory()};
     bool pos_fresh_ = false;
     // the runner-up half of that state (round 5b, grid_coop.hip: kCoopRu): per query the runner-up's f64 point, its
     // index | LB3 << 32; all bits set = none; same size, same resets as d_pos_.  The kernels are built WITHOUT that code
     // by default (-DVISMA_COOP_RU=1 builds it: measured slower), so the buffer exists only when asked for:
     // VISMA_ICP_RUNNER_UP=1 (read when the context is created) with such a build
-    void *d_ru_ = nullptr;
+    DevBuf<Pt64> d_ru_{device_memory()};
     int runner_up_ = 0;
     // the certificate of grid_coop.hip: the transform of the pass that left the state (host-driven passes over ONE
     // problem; device loops carry it in their DevIcpState and leave prev_T_valid_ false behind them)
@@ -697,8 +734,8 @@ private:
     {
         pos_fresh_ = false;
         prev_T_valid_ = false;
-        if (d_pos_ && aux_cap_ > 0) HIP_TRY(hipMemsetAsync(d_pos_, 0xFF, sizeof(Pt64) * (size_t)aux_cap_, stream_));
-        if (d_ru_ && aux_cap_ > 0) HIP_TRY(hipMemsetAsync(d_ru_, 0xFF, sizeof(Pt64) * (size_t)aux_cap_, stream_));
+        if (d_pos_) HIP_TRY(hipMemsetAsync(d_pos_, 0xFF, d_pos_.bytes(), stream_));
+        if (d_ru_) HIP_TRY(hipMemsetAsync(d_ru_, 0xFF, d_ru_.bytes(), stream_));
         return VISMA_ICP_OK;
     }
     bool coop_ok() const
@@ -773,7 +810,8 @@ private:
         if (!(grid_occupancy_ >= ring_occ_min_single_ && grid_occupancy_ < ring_occ_min_)) return false;   // both callers agree
         return ring_for_sweep_ != caller_sweep_;
     }
-    void *d_occ_ = nullptr, *d_ring_tab_ = nullptr;
+    DevBuf<unsigned long long> d_occ_{device_memory()};
+    DevBuf<RingRow> d_ring_tab_{device_memory()};
     int ring_tab_rings_ = 0;
     RingTable ring_tab_{nullptr, 0};         // what a ring pass gets beside grid_ (SearchArgs::ring)
     static int nrows_of_rings(int rings) { return (2 * rings + 1) * (2 * rings + 1); }
@@ -796,7 +834,6 @@ private:
         if (nprob > 1) return q <= 32768 ? 804 : 402;          // sweeps: many queries per launch
         return ns_ <= 32768 ? 804 : (ns_ <= 98304 ? 802 : 1201);
     }
-    int64_t sorted_cap_ = 0, cell_cap_ = 0;
 
     // ---- streamed search with exact tie-breaks + fused fold (tile.hip) --------------------
     bool exact_ = true;          // search precision "exact" (default): fp32 ranking, f64 re-rank of near-ties
@@ -805,11 +842,11 @@ private:
     int tile_config_ = -1;       // VISMA_ICP_TILE_CONFIG: LDS tile geometry (see launch_nn_tile_reduce)
     int tile_fallback_ = 0;      // VISMA_ICP_TILE_FALLBACK=1: every workgroup searches from global memory (tests)
     int tile_fused_fold_ = 1;    // VISMA_ICP_TILE_FOLD=0: fold the partial rows in a second launch (experiments)
-    void *d_partials2_ = nullptr, *d_tickets_ = nullptr, *d_tstats_ = nullptr;
-    size_t tickets_cap_ = 0;     // words in d_tickets_ (= rows in d_partials2_)
+    DevBuf<double> d_partials2_{device_memory()};            // kReduceAcc doubles per word of ...
+    DevBuf<unsigned> d_tickets_{device_memory()};
+    DevBuf<unsigned long long> d_tstats_{device_memory()};
     Xform64 T64_last_{};         // transform of the last nn_pass, f64
-    void *d_second_ = nullptr;   // brute force, exact flavour: runner-up distances [splits][ns_pad]
-    size_t second_bytes_ = 0;
+    DevBuf<float> d_second_{device_memory()};   // brute force, exact flavour: runner-up distances [splits][ns_pad]
     int last_mode_ = 0;          // see search_is_f64()
     // (tile.hip is an experiment that lost -- 2.4-3x slower than the gather kernels, DESIGN.md 4.1b -- and is
     //  only compiled into the side build -DVISMA_WITH_TILE that tests/test_tile_kernel.py loads)
@@ -925,8 +962,7 @@ private:
     // stop test inside it.  Closed-form point-to-point loops on one GPU whose workgroups all fit the device at once;
     // VISMA_ICP_SWEEP_PERSIST=0: one search launch + one solve launch per pass, as before.
     int sweep_persist_ = 1;
-    void *d_sweep_relay_ = nullptr;      // 32 words per problem + the "dead" word behind them
-    int sweep_relay_cap_ = 0;
+    DevBuf<unsigned long long> d_sweep_relay_{device_memory()};   // 32 words per problem + the "dead" word behind them (+ 8)
     unsigned sweep_tag_ = 0;
     double sweep_launches_total_ = 0.0, sweep_aborts_total_ = 0.0;
     int sess_pass_ = 0, sess_max_ = 0;
@@ -939,9 +975,9 @@ private:
     int sess_e0_ = -1;               // its event pair (profiling)
     std::vector<std::pair<int, int>> sess_pending_;   // (event pair, passes run) of finished sessions
     unsigned long long *h_cmd_ = nullptr, *h_cmd_dev_ = nullptr;   // kPersistWords command words; word 32: the kernel's flag
-    void *d_relay_ = nullptr;
-    void *d_fold_tag_ = nullptr;     // the polled fold's granule rows (2,048 rows + 256 group rows of 32 granules)
-    void *d_peer_table_ = nullptr;   // peers_ in device memory (the persistent kernel's fold reads the mailboxes from there)
+    DevBuf<unsigned long long> d_relay_{device_memory()};
+    DevBuf<char> d_fold_tag_{device_memory()};      // the polled fold's granule rows (2,048 rows + 256 group rows of 32 granules)
+    DevBuf<void *> d_peer_table_{device_memory()};  // peers_ in device memory (the persistent kernel's fold reads the mailboxes from there)
     bool peers_share_device_ = true; // some peer of the IPC ring sits on THIS device (tests): no persistent launch then --
                                      // the ranks' launches would each hold a part of the compute units and wait for the rest
     // Source-sharded ranks keep their launches alive across passes only when ASKED (VISMA_ICP_PERSIST_RANKS=1, read when
@@ -954,13 +990,13 @@ private:
         return persist_ranks_ && ipc_n_ > 1 && d_peer_table_ && !comm_ && (!peers_share_device_ || shared_ok);
     }
     bool cmd_direct_ = false;        // h_cmd_ is fine-grained DEVICE memory, stored to through the PCIe BAR (large-BAR systems)
-    void *d_cmd_block_ = nullptr;
+    DevBuf<unsigned long long> d_cmd_block_{device_memory()};
     unsigned *h_flag_ = nullptr, *h_flag_dev_ = nullptr;   // the launch's "gave up" word, always in mapped host memory
     std::chrono::steady_clock::time_point t_stats_seen_{}, t_posted_{};   // when the host saw a pass's statistics / posted a command
     static bool trace_persist() { static const bool t = std::getenv("VISMA_ICP_PERSIST_TRACE") != nullptr; return t; }
     double host_gap_us_ = 0.0, wait_us_ = 0.0;
     int host_gaps_ = 0;
-    void *d_timeline_ = nullptr;     // VISMA_ICP_PERSIST_TIMELINE=<file>: per pass and workgroup clocks of every session, appended
+    DevBuf<unsigned long long> d_timeline_{device_memory()};   // VISMA_ICP_PERSIST_TIMELINE=<file>: per pass and workgroup clocks of every session, appended
     int timeline_passes_ = 0, timeline_blocks_ = 0;
     std::string timeline_path_;
     int stall_nth_ = 0;              // (tests) sleep stall_ms_ before the stall_nth_-th command from now

@@ -1,4 +1,4 @@
-// hip_engine_clouds.cpp -- HipEngine: uploads and layout of the clouds, the radius-cell grid, device buffers and their pool, timing read-back.
+// hip_engine_clouds.cpp -- HipEngine: uploads and layout of the clouds, the radius-cell grid, the growth of the device buffers, timing read-back.
 #include "hip_engine.hpp"
 
 namespace visma {
@@ -22,8 +22,8 @@ int HipEngine::init()
         err_ = std::string("device is ") + prop.gcnArchName + ", this build targets gfx950 only";
         return VISMA_ICP_ERR_NO_DEVICE;
     }
-    HIP_TRY(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&stream_src_, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream_.s, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&stream_src_.s, hipStreamNonBlocking));
     if (const char *e = std::getenv("VISMA_ICP_UPLOAD_OVERLAP")) upload_overlap_ = std::atoi(e) != 0;
     if (const char *e = std::getenv("VISMA_ICP_GRID_SUB")) {
         const int v = std::atoi(e);
@@ -33,10 +33,9 @@ int HipEngine::init()
         const int v = std::atoi(e);
         if (v >= 1 && v <= kGridMaxBlocks) grid_blocks_env_ = v;
     }
-    HIP_TRY(hipMalloc(&d_partials_, sizeof(double) * kReduceAcc * kGridMaxBlocks));
-    partial_rows_ = (size_t)kGridMaxBlocks;
-    HIP_TRY(hipMalloc(&d_stats_, sizeof(double) * kNStats));
-    HIP_TRY(hipMalloc(&d_cand_, 3 * 4096 * sizeof(unsigned long long)));
+    { int rc = ensure_partials((size_t)kGridMaxBlocks); if (rc) return rc; }
+    BUF_TRY(d_stats_.reset(kNStats));
+    BUF_TRY(d_cand_.reset(3 * 4096));
     HIP_TRY(hipMemset(d_cand_, 0, 3 * 4096 * sizeof(unsigned long long)));
     if (const char *e = std::getenv("VISMA_ICP_COOP")) coop_enabled_ = std::atoi(e) != 0;
     if (const char *e = std::getenv("VISMA_ICP_CERT")) cert_enabled_ = std::atoi(e) != 0;
@@ -81,15 +80,16 @@ int HipEngine::init()
         if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device_) != hipSuccess) { (void)hipGetLastError(); large_bar = 0; }
         const char *e = std::getenv("VISMA_ICP_PERSIST_CMD");
         const bool want_direct = e ? (e[0] == 'd') : large_bar != 0;
+        void *block = nullptr;
         if (want_direct && large_bar &&
-            hipExtMallocWithFlags(&d_cmd_block_, sizeof(unsigned long long) * 64, hipDeviceMallocFinegrained) == hipSuccess) {
+            hipExtMallocWithFlags(&block, sizeof(unsigned long long) * 64, hipDeviceMallocFinegrained) == hipSuccess) {
+            d_cmd_block_.adopt((unsigned long long *)block, 64);
             HIP_TRY(hipMemset(d_cmd_block_, 0, sizeof(unsigned long long) * 64));
             HIP_TRY(hipDeviceSynchronize());
-            h_cmd_ = h_cmd_dev_ = (unsigned long long *)d_cmd_block_;
+            h_cmd_ = h_cmd_dev_ = d_cmd_block_;
             cmd_direct_ = true;
         } else {
             (void)hipGetLastError();
-            d_cmd_block_ = nullptr;
             HIP_TRY(hipHostMalloc((void **)&h_cmd_, sizeof(unsigned long long) * 64, hipHostMallocMapped | hipHostMallocCoherent));
             std::memset(h_cmd_, 0, sizeof(unsigned long long) * 64);
             HIP_TRY(hipHostGetDevicePointer((void **)&h_cmd_dev_, h_cmd_, 0));
@@ -98,7 +98,7 @@ int HipEngine::init()
         std::memset(h_flag_, 0, 64);
         HIP_TRY(hipHostGetDevicePointer((void **)&h_flag_dev_, h_flag_, 0));
     }
-    HIP_TRY(hipMalloc(&d_relay_, sizeof(unsigned long long) * 64));
+    BUF_TRY(d_relay_.reset(64));
     HIP_TRY(hipMemset(d_relay_, 0, sizeof(unsigned long long) * 64));
     inited_ = true;
     return VISMA_ICP_OK;
@@ -122,14 +122,10 @@ int HipEngine::set_target_f64(const double *xyz, int64_t nt, int stride, double 
     raw_source_points_ = 0;                              // (d_raw_ is about to be reused)
     int rc = ensure_target(nt);
     if (rc) return rc;
-    if (want64) { rc = pool_alloc(&d_tgt64_, sizeof(Pt64) * (size_t)std::max<int64_t>(nt, 1)); if (rc) return rc; }
+    if (want64) BUF_TRY(d_tgt64_.reset((size_t)std::max<int64_t>(nt, 1)));
     if (nt > 0) {
-        if ((size_t)nt * 24 > raw_bytes_) {
-            free_dev(d_raw_);
-            rc = pool_alloc(&d_raw_, (size_t)nt * 24);
-            if (rc) return rc;
-            raw_bytes_ = (size_t)nt * 24;
-        }
+        rc = ensure_raw(d_raw_, (size_t)nt);
+        if (rc) return rc;
         double *pin = reinterpret_cast<double *>(staging(2, (size_t)nt * 6));
         const int64_t nch_all = (nt + kHostChunk - 1) / kHostChunk;
         std::vector<double> part(compute_centre ? (size_t)nch_all * 3 : 0, 0.0);
@@ -200,14 +196,9 @@ int HipEngine::set_target_f64(const double *xyz, int64_t nt, int stride, double 
                 try32 = false;
             }
             stage_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_p0).count();
-            // (an fp32 piece of a LATER upload may still be in flight from this area: the stream is in order,
-            //  and the previous upload ended with a synchronise)
-            if (as32)
-                HIP_TRY(hipMemcpyAsync((char *)d_raw_ + (size_t)lo * 24, pin + 3 * lo, sizeof(float) * 3 * (size_t)(hi - lo),
-                                       hipMemcpyHostToDevice, stream_));
-            else
-                HIP_TRY(hipMemcpyAsync((double *)d_raw_ + 3 * lo, pin + 3 * lo, sizeof(double) * 3 * (size_t)(hi - lo),
-                                       hipMemcpyHostToDevice, stream_));
+            // (nothing of an EARLIER upload is still in flight from this area: this one began with a synchronise)
+            HIP_TRY(hipMemcpyAsync(d_raw_ + (size_t)lo * 24, pin + 3 * lo, (as32 ? sizeof(float) : sizeof(double)) * 3 * (size_t)(hi - lo),
+                                   hipMemcpyHostToDevice, stream_));
             pieces.push_back({lo, hi, as32});
         }
         if (compute_centre) {
@@ -218,10 +209,10 @@ int HipEngine::set_target_f64(const double *xyz, int64_t nt, int stride, double 
         }
         for (const Piece &pc : pieces) {
             if (pc.f32)
-                HIP_TRY(launch_expand_f32(reinterpret_cast<const float *>((const char *)d_raw_ + (size_t)pc.lo * 24), pc.hi - pc.lo,
+                HIP_TRY(launch_expand_f32(reinterpret_cast<const float *>(d_raw_ + (size_t)pc.lo * 24), pc.hi - pc.lo,
                                           pc.lo, c, (float4 *)d_tgt_ + pc.lo, d_tgt64_ ? (Pt64 *)d_tgt64_ + pc.lo : nullptr, stream_));
             else
-                HIP_TRY(launch_expand_f64((const double *)d_raw_ + 3 * pc.lo, pc.hi - pc.lo, c, (float4 *)d_tgt_ + pc.lo,
+                HIP_TRY(launch_expand_f64((const double *)d_raw_.get() + 3 * pc.lo, pc.hi - pc.lo, c, (float4 *)d_tgt_ + pc.lo,
                                           d_tgt64_ ? (Pt64 *)d_tgt64_ + pc.lo : nullptr, stream_, pc.lo));
         }
         last_upload_f32_ = !pieces.empty() && pieces.back().f32;
@@ -261,10 +252,9 @@ int HipEngine::set_target_voxel_f64(const double *xyz, int64_t n, int stride, do
     HIP_TRY(hipSetDevice(device_));
     *nt_out = 0;
     if (n < 0 || n > 0x7fffffff - 4096) { err_ = "scene too large for 32-bit indices"; return VISMA_ICP_ERR_INVALID; }
-    void *d_in = nullptr;
+    DevBuf<double> d_in(pool_);
     if (n > 0) {
-        int rc = pool_alloc(&d_in, (size_t)n * 24);
-        if (rc) return rc;
+        BUF_TRY(d_in.reset(3 * (size_t)n));
         double *pin = reinterpret_cast<double *>(staging(2, (size_t)n * 6));
         const int64_t piece = 1 << 20;
         for (int64_t lo = 0; lo < n; lo += piece) {
@@ -286,23 +276,22 @@ int HipEngine::set_target_voxel_f64(const double *xyz, int64_t n, int stride, do
     int64_t nvox = 0;
     hipError_t e = voxel_down_sample_core((const double *)d_in, nullptr, nullptr, n, voxel, &d_o, nullptr, nullptr, &nvox,
                                           stream_);
-    free_dev(d_in);
+    d_in.release();
     if (e != hipSuccess) { err_ = std::string("voxel_down_sample: ") + hipGetErrorString(e); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
-    if (d_vox_out_) (void)hipFree(d_vox_out_);
-    d_vox_out_ = d_o;
+    d_vox_out_.adopt(d_o, 3 * (size_t)std::max<int64_t>(nvox, 0));
     vox_out_n_ = nvox;
     int rc = ensure_target(nvox);
     if (rc) return rc;
-    if (want64) { rc = pool_alloc(&d_tgt64_, sizeof(Pt64) * (size_t)std::max<int64_t>(nvox, 1)); if (rc) return rc; }
+    if (want64) BUF_TRY(d_tgt64_.reset((size_t)std::max<int64_t>(nvox, 1)));
     if (nvox > 0) {
         if (compute_centre) {
             const int64_t nch = (nvox + kHostChunk - 1) / kHostChunk;
-            double *d_part = nullptr;
-            HIP_TRY(hipMalloc((void **)&d_part, sizeof(double) * (size_t)(3 * nch + 3)));
+            DevBuf<double> d_part(device_memory());
+            BUF_TRY(d_part.reset((size_t)(3 * nch + 3)));
             hipError_t e2 = centroid_device(d_o, nvox, kHostChunk, d_part, d_part + 3 * nch, stream_);
             if (e2 == hipSuccess) e2 = hipMemcpyAsync(c, d_part + 3 * nch, sizeof(double) * 3, hipMemcpyDeviceToHost, stream_);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream_);
-            (void)hipFree(d_part);
+            d_part.release();
             if (e2 != hipSuccess) { err_ = std::string("centroid: ") + hipGetErrorString(e2); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
         }
         HIP_TRY(launch_expand_f64(d_o, nvox, c, (float4 *)d_tgt_, (Pt64 *)d_tgt64_, stream_));
@@ -346,13 +335,12 @@ int HipEngine::begin_raw_source(int64_t ns, bool want64, std::vector<int32_t> &o
     prepared_ns_ = -1;
     int rc = ensure_source(ns);
     if (rc) return rc;
-    free_dev(d_sorted64_); free_dev(d_nrm64_);
+    d_sorted64_.release(); d_nrm64_.release();
     grid_valid_ = false;
     order.resize((size_t)std::max<int64_t>(ns, 0));
     if (want64) {
         if (!d_tgt64_) { err_ = "set_source_f64 without an f64 target"; return VISMA_ICP_ERR_STATE; }
-        rc = pool_alloc(&d_src64_, sizeof(Pt64) * (size_t)std::max<int64_t>(ns, 1));
-        if (rc) return rc;
+        BUF_TRY(d_src64_.reset((size_t)std::max<int64_t>(ns, 1)));
     }
     return VISMA_ICP_OK;
 }
@@ -360,20 +348,18 @@ int HipEngine::begin_raw_source(int64_t ns, bool want64, std::vector<int32_t> &o
 // d_raw_ holds ns points (caller order): Morton order on the device, fp32 + f64 copies, the permutation back
 int HipEngine::finish_raw_source(int64_t ns, const double *c, std::vector<int32_t> &order, const void *raw, hipStream_t st)
 {
-    if (!raw) raw = d_raw_;
+    if (!raw) raw = d_raw_.get();
     if (!st) st = stream_;
-    void *scratch = nullptr, *d_order = nullptr;
+    DevBuf<int32_t> d_order(pool_);                          // (declared first: the scratch goes back to the pool before it)
+    DevBuf<char> scratch(pool_);
     const size_t sb = order_source_scratch_bytes(ns);
-    int rc = pool_alloc(&scratch, sb);
-    if (rc) return rc;
-    rc = pool_alloc(&d_order, sizeof(int32_t) * (size_t)ns);
-    if (rc) { free_dev(scratch); return rc; }
-    hipError_t e = order_source_device((const double *)raw, ns, c, (float4 *)d_src_, (Pt64 *)d_src64_,
-                                       (int32_t *)d_order, scratch, sb, st);
+    BUF_TRY(scratch.reset(sb));
+    BUF_TRY(d_order.reset((size_t)ns));
+    hipError_t e = order_source_device((const double *)raw, ns, c, d_src_, d_src64_, d_order, scratch.get(), sb, st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(order.data(), d_order, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    free_dev(scratch); free_dev(d_order);
+    scratch.release(); d_order.release();
     if (e != hipSuccess) { err_ = std::string("source ordering: ") + hipGetErrorString(e); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
     return VISMA_ICP_OK;
 }
@@ -390,19 +376,14 @@ int HipEngine::set_source_f64(const double *xyz, int64_t ns, int stride, const d
         hipStream_t st = stream_;
         if (upload_overlap_) {
             // its own buffer, its own stream (hip_engine.hpp: stream_src_)
-            if ((size_t)ns * 24 > raw_src_bytes_) {
-                HIP_TRY(hipStreamSynchronize(stream_src_));
-                if (d_raw_src_) (void)hipFree(d_raw_src_);
-                d_raw_src_ = nullptr; raw_src_bytes_ = 0;
-                HIP_TRY(hipMalloc(&d_raw_src_, (size_t)ns * 24 + (size_t)ns * 6));
-                raw_src_bytes_ = (size_t)ns * 24 + (size_t)ns * 6;
-            }
-            raw = d_raw_src_;
+            rc = ensure_raw(d_raw_src_, (size_t)ns, (size_t)ns * 6, stream_src_);
+            if (rc) return rc;
+            raw = d_raw_src_.get();
             st = stream_src_;
         } else {
-            rc = ensure_raw((size_t)ns);
+            rc = ensure_raw(d_raw_, (size_t)ns);
             if (rc) return rc;
-            raw = d_raw_;
+            raw = d_raw_.get();
         }
         double *pin = reinterpret_cast<double *>(staging(3, (size_t)ns * 6));
         parallel_for((ns + kHostChunk - 1) / kHostChunk, 1, [&](int64_t ch) {
@@ -436,7 +417,7 @@ int HipEngine::set_source_meshes_f64(const MeshSource *meshes, int n_meshes, int
         if (meshes[k].nf > 0) room += meshes[k].samples;
     }
     if (room > 0x7fffffff - 4096) { err_ = "source too large for 32-bit indices"; return VISMA_ICP_ERR_INVALID; }
-    int rc = ensure_raw((size_t)std::max<int64_t>(room, 1));
+    int rc = ensure_raw(d_raw_, (size_t)std::max<int64_t>(room, 1));
     if (rc) return rc;
     int64_t ns = 0;
     for (int k = 0; k < n_meshes; k++) {
@@ -444,7 +425,7 @@ int HipEngine::set_source_meshes_f64(const MeshSource *meshes, int n_meshes, int
         hipError_t e = sample_mesh_transformed_device(meshes[k].V, meshes[k].nv, meshes[k].F, meshes[k].nf, meshes[k].samples,
                                                       quirks, seed + (unsigned long long)k,
                                                       meshes[k].has_transform ? meshes[k].T : nullptr,
-                                                      (double *)d_raw_ + 3 * ns, room - ns, &m, stream_);
+                                                      (double *)d_raw_.get() + 3 * ns, room - ns, &m, stream_);
         if (e != hipSuccess) {
             err_ = std::string("mesh source: ") + (e == hipErrorInvalidValue ? "face index out of range" : hipGetErrorString(e));
             (void)hipGetLastError();
@@ -465,28 +446,23 @@ int HipEngine::set_source_meshes_f64(const MeshSource *meshes, int n_meshes, int
 
 int HipEngine::ensure_second(int64_t ns_pad, int splits)
 {
-    if (!d_pend_count_) {              // the list of queries the reduce kernel leaves to the rescan passes
-        HIP_TRY(hipMalloc(&d_pend_count_, sizeof(int)));
-        HIP_TRY(hipMalloc(&d_pend_q32_, sizeof(float4) * kBrutePendCap));
-        HIP_TRY(hipMalloc(&d_pend_q64_, sizeof(Pt64) * kBrutePendCap));
-        HIP_TRY(hipMalloc(&d_pend_best_, sizeof(unsigned long long) * kBrutePendCap));
-        HIP_TRY(hipMalloc(&d_pend_idx_, sizeof(unsigned) * kBrutePendCap));
-    }
-    const size_t need = sizeof(float) * (size_t)ns_pad * (size_t)splits;
-    if (need > second_bytes_) {
-        free_dev(d_second_);
-        HIP_TRY(hipMalloc(&d_second_, need));
-        second_bytes_ = need;
-    }
+    // the list of queries the reduce kernel leaves to the rescan passes (d_pend_count_ is made last: brute_ex() reads it
+    // as "the list is there")
+    BUF_TRY(d_pend_q32_.reserve(kBrutePendCap));
+    BUF_TRY(d_pend_q64_.reserve(kBrutePendCap));
+    BUF_TRY(d_pend_best_.reserve(kBrutePendCap));
+    BUF_TRY(d_pend_idx_.reserve(kBrutePendCap));
+    BUF_TRY(d_pend_count_.reserve(1));
+    BUF_TRY(d_second_.reserve((size_t)ns_pad * (size_t)splits));
     return VISMA_ICP_OK;
 }
 
 int HipEngine::set_target_normals64(const Pt64 *n)
 {
     HIP_TRY(hipSetDevice(device_));
-    free_dev(d_nrm64_);
+    d_nrm64_.release();
     if (!n || !d_tgt64_) return VISMA_ICP_OK;
-    HIP_TRY(hipMalloc(&d_nrm64_, sizeof(Pt64) * std::max<int64_t>(nt_, 1)));
+    BUF_TRY(d_nrm64_.reset((size_t)std::max<int64_t>(nt_, 1)));
     if (nt_ > 0) HIP_TRY(hipMemcpy(d_nrm64_, n, sizeof(Pt64) * nt_, hipMemcpyHostToDevice));
     return VISMA_ICP_OK;
 }
@@ -529,46 +505,20 @@ void HipEngine::get_timing(visma_icp_timing *t, bool reset)
     }
 }
 
-int HipEngine::pool_alloc(void **p, size_t bytes)
-{
-    bytes = std::max<size_t>(bytes, 256);
-    int best = -1;
-    for (int i = 0; i < (int)pool_free_.size(); i++)
-        if (pool_free_[i].second >= bytes && pool_free_[i].second <= 2 * bytes + (1u << 20) &&
-            (best < 0 || pool_free_[i].second < pool_free_[best].second))
-            best = i;
-    if (best >= 0) {
-        *p = pool_free_[best].first;
-        pool_live_[*p] = pool_free_[best].second;
-        pool_free_.erase(pool_free_.begin() + best);
-        return VISMA_ICP_OK;
-    }
-    const size_t want = bytes + bytes / 8;                 // a little head-room: the next cloud is rarely the same size
-    if (hipMalloc(p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        pool_trim(0);                                      // give the recycled buffers back and try the exact size
-        HIP_TRY(hipMalloc(p, bytes));
-        pool_live_[*p] = bytes;
-        return VISMA_ICP_OK;
-    }
-    pool_live_[*p] = want;
-    return VISMA_ICP_OK;
-}
-
 int HipEngine::ensure_target(int64_t nt)
 {
     if (nt < 0) { err_ = "negative point count"; return VISMA_ICP_ERR_INVALID; }
     if (nt > 0x7fffffff - 4096) { err_ = "target too large for 32-bit indices"; return VISMA_ICP_ERR_INVALID; }
-    free_dev(d_tgt_); free_dev(d_nrm_); free_dev(d_tgt64_); free_dev(d_sorted64_); free_dev(d_nrm64_);
+    d_tgt_.release(); d_nrm_.release(); d_tgt64_.release(); d_sorted64_.release(); d_nrm64_.release();
     has_normals_ = false;
-    free_dev(d_tint_);                                       // the previous target's colours and their gradient
+    d_tint_.release();                                       // the previous target's colours and their gradient
     has_target_colors_ = false;
     drop_color_gradient();
     host_box_valid_ = false;
     // pad to a whole number of LDS chunks with +inf points (never accepted)
     nt_pad_ = ((nt + kTChunk - 1) / kTChunk) * kTChunk;
     if (nt_pad_ == 0) nt_pad_ = kTChunk;
-    { int prc = pool_alloc(&d_tgt_, sizeof(float4) * (size_t)nt_pad_); if (prc) return prc; }
+    BUF_TRY(d_tgt_.reset((size_t)nt_pad_));
     HIP_TRY(launch_fill_inf((float4 *)d_tgt_ + nt, nt_pad_ - nt, stream_));
     nt_ = nt;
     grid_valid_ = false;
@@ -579,16 +529,12 @@ int HipEngine::ensure_target(int64_t nt)
 
 int HipEngine::ensure_aux(int64_t ns_pad)
 {
-    if (ns_pad > aux_cap_) {
-        free_dev(d_idx_); free_dev(d_d2_); free_dev(d_pos_); free_dev(d_ru_);
-        HIP_TRY(hipMalloc(&d_idx_, sizeof(int32_t) * (ns_pad > 0 ? ns_pad : 1)));
-        HIP_TRY(hipMalloc(&d_d2_, sizeof(float) * (ns_pad > 0 ? ns_pad : 1)));
-        HIP_TRY(hipMalloc(&d_pos_, sizeof(Pt64) * (ns_pad > 0 ? ns_pad : 1)));
-        if (runner_up_) HIP_TRY(hipMalloc(&d_ru_, sizeof(Pt64) * (ns_pad > 0 ? ns_pad : 1)));
-        aux_cap_ = ns_pad;
-        return invalidate_pos();
-    }
-    return VISMA_ICP_OK;
+    bool grew = false;
+    BUF_TRY(d_idx_.reserve((size_t)ns_pad, &grew));
+    BUF_TRY(d_d2_.reserve((size_t)ns_pad, &grew));
+    BUF_TRY(d_pos_.reserve((size_t)ns_pad, &grew));
+    if (runner_up_) BUF_TRY(d_ru_.reserve((size_t)ns_pad, &grew));
+    return grew ? invalidate_pos() : VISMA_ICP_OK;
 }
 
 // Pick brute force or the grid for this (target, radius); build the grid if needed.
@@ -630,7 +576,7 @@ int HipEngine::build_grid(double max_dist)
     float mn[3], mx[3];
     static const bool check_box = std::getenv("VISMA_ICP_CHECK_BOX") != nullptr;   // (tests: both ways, must agree)
     if (!host_box_valid_ || check_box) {
-        if (!d_box_) HIP_TRY(hipMalloc(&d_box_, sizeof(unsigned) * 8));
+        BUF_TRY(d_box_.reserve(8));
         HIP_TRY(launch_grid_bbox((const float4 *)d_tgt_, nt_, (unsigned *)d_box_, stream_));
         unsigned box[6];
         HIP_TRY(hipMemcpyAsync(box, d_box_, sizeof(box), hipMemcpyDeviceToHost, stream_));
@@ -649,31 +595,26 @@ int HipEngine::build_grid(double max_dist)
     grid_occupancy_ = 0.0;
     // cells, counts, scan, scatter (+ the f64 and the packed copies) for the plan in grid_
     auto build = [&]() -> int {
-        if ((int64_t)nt_ > sorted_cap_) {
-            free_dev(d_sorted_); free_dev(d_cell_of_);
-            HIP_TRY(hipMalloc(&d_sorted_, sizeof(float4) * (nt_ + kSortedSlack)));   // batches read past a run's end
-            HIP_TRY(hipMalloc(&d_cell_of_, 2 * sizeof(unsigned) * nt_));   // (cell, rank in the cell)
-            sorted_cap_ = nt_;
+        BUF_TRY(d_sorted_.reserve((size_t)nt_, nullptr, kSortedSlack));   // batches read past a run's end
+        BUF_TRY(d_cell_of_.reserve(2 * (size_t)nt_));
+        // the cell tables grow together: one of them short (a larger plan, or an allocation that failed) renews all three
+        const size_t nstart = (size_t)grid_.ncell + 1, nscan = (size_t)grid_scan_blocks(grid_.ncell) + 1;
+        if (d_count_.count() < nstart || d_start_.count() < nstart || d_bsum_.count() < nscan) {
+            BUF_TRY(d_count_.reset(nstart));
+            BUF_TRY(d_start_.reset(nstart, 7));                           // (16-byte reads near the end)
+            HIP_TRY(hipMemsetAsync(d_start_, 0, d_start_.bytes(), stream_));
+            BUF_TRY(d_bsum_.reset(nscan));
         }
-        if (grid_.ncell + 1 > cell_cap_) {
-            free_dev(d_count_); free_dev(d_start_); free_dev(d_bsum_);
-            HIP_TRY(hipMalloc(&d_count_, sizeof(unsigned) * (grid_.ncell + 1)));
-            HIP_TRY(hipMalloc(&d_start_, sizeof(unsigned) * (grid_.ncell + 8)));    // (16-byte reads near the end)
-            HIP_TRY(hipMemsetAsync(d_start_, 0, sizeof(unsigned) * (grid_.ncell + 8), stream_));
-            HIP_TRY(hipMalloc(&d_bsum_, sizeof(unsigned) * (grid_scan_blocks(grid_.ncell) + 1)));
-            cell_cap_ = grid_.ncell + 1;
-        }
-        free_dev(d_sorted64_);
-        if (d_tgt64_ && d_src64_) { int prc = pool_alloc(&d_sorted64_, sizeof(Pt64) * (size_t)std::max<int64_t>(nt_, 1)); if (prc) return prc; }
+        d_sorted64_.release();
+        if (d_tgt64_ && d_src64_) BUF_TRY(d_sorted64_.reset((size_t)std::max<int64_t>(nt_, 1)));
         HIP_TRY(launch_grid_build((const float4 *)d_tgt_, nt_, grid_, (unsigned *)d_cell_of_,
                                   (unsigned *)d_count_, (unsigned *)d_bsum_, (unsigned *)d_start_,
                                   (float4 *)d_sorted_, stream_, d_sorted64_ ? (const Pt64 *)d_tgt64_ : nullptr,
                                   (Pt64 *)d_sorted64_));
         // the exact search ranks on a packed copy: 12 bytes per candidate (grid.hip: P12)
-        free_dev(d_sorted12_);
+        d_sorted12_.release();
         if (d_sorted64_) {
-            int prc = pool_alloc(&d_sorted12_, sizeof(float) * 3 * (size_t)(nt_ + kSortedSlack));
-            if (prc) return prc;
+            BUF_TRY(d_sorted12_.reset(3 * (size_t)nt_, 3 * kSortedSlack));
             HIP_TRY(launch_pack12((const float4 *)d_sorted_, (float *)d_sorted12_, nt_, stream_));
         }
         return VISMA_ICP_OK;
@@ -692,7 +633,7 @@ int HipEngine::build_grid(double max_dist)
                              (double)std::max(grid_.dim[0], std::max(grid_.dim[1], grid_.dim[2]));
     ring_for_sweep_ = caller_sweep_;
     if (ring_possible && (ring_mode_ > 0 || occ_guess >= ring_occ_min_)) {
-        if (!d_occ_) HIP_TRY(hipMalloc(&d_occ_, sizeof(unsigned long long)));
+        BUF_TRY(d_occ_.reserve(1));
         HIP_TRY(hipMemsetAsync(d_occ_, 0, sizeof(unsigned long long), stream_));
         HIP_TRY(launch_count_occupied((const unsigned *)d_count_, grid_.ncell, (unsigned long long *)d_occ_, stream_));
         unsigned long long occupied = 0ull;
@@ -706,10 +647,12 @@ int HipEngine::build_grid(double max_dist)
             if (fine.ring > 0) {
                 // the rows' visiting order around a query (the same for every query: a table per ring count)
                 if (!d_ring_tab_ || ring_tab_rings_ != fine.ring) {
-                    free_dev(d_ring_tab_);
+                    d_ring_tab_.release();
                     ring_tab_rings_ = 0;
                     int nrows = 0;
-                    HIP_TRY(build_ring_table(fine.ring, &d_ring_tab_, &nrows));
+                    void *tab = nullptr;
+                    HIP_TRY(build_ring_table(fine.ring, &tab, &nrows));
+                    d_ring_tab_.adopt((RingRow *)tab, (size_t)nrows);
                     ring_tab_rings_ = fine.ring;
                 }
                 grid_ = fine;
@@ -752,22 +695,15 @@ int HipEngine::collect_timing()
 
 int HipEngine::ensure_tile_buffers(size_t rows, size_t ticket_words)
 {
-    if (rows > partial_rows_) {
-        free_dev(d_partials_);
-        HIP_TRY(hipMalloc(&d_partials_, sizeof(double) * kReduceAcc * rows));
-        partial_rows_ = rows;
-    }
-    if (ticket_words > tickets_cap_) {
-        free_dev(d_partials2_); free_dev(d_tickets_);
-        HIP_TRY(hipMalloc(&d_partials2_, sizeof(double) * kReduceAcc * ticket_words));
-        HIP_TRY(hipMalloc(&d_tickets_, sizeof(unsigned) * ticket_words));
-        HIP_TRY(hipMemsetAsync(d_tickets_, 0, sizeof(unsigned) * ticket_words, stream_));
-        tickets_cap_ = ticket_words;
-    }
-    if (!d_tstats_) {
-        HIP_TRY(hipMalloc(&d_tstats_, sizeof(unsigned long long) * 24 * 512));
-        HIP_TRY(hipMemsetAsync(d_tstats_, 0, sizeof(unsigned long long) * 24 * 512, stream_));
-    }
+    int rc = ensure_partials(rows);
+    if (rc) return rc;
+    bool grew = false;
+    BUF_TRY(d_partials2_.reserve((size_t)kReduceAcc * ticket_words));
+    BUF_TRY(d_tickets_.reserve(ticket_words, &grew));
+    if (grew) HIP_TRY(hipMemsetAsync(d_tickets_, 0, d_tickets_.bytes(), stream_));
+    grew = false;
+    BUF_TRY(d_tstats_.reserve(24 * 512, &grew));
+    if (grew) HIP_TRY(hipMemsetAsync(d_tstats_, 0, d_tstats_.bytes(), stream_));
     return VISMA_ICP_OK;
 }
 
@@ -776,13 +712,13 @@ int HipEngine::ensure_f64_views()
 {
     if (!exact_) return VISMA_ICP_OK;
     if (!d_src64_ && d_src_) {
-        HIP_TRY(hipMalloc(&d_src64_, sizeof(Pt64) * std::max<int64_t>(ns_, 1)));
+        BUF_TRY(d_src64_.reset((size_t)std::max<int64_t>(ns_, 1)));
         HIP_TRY(launch_promote_pt64((const float4 *)d_src_, (Pt64 *)d_src64_, ns_, stream_));
     }
     if (!d_tgt64_ && d_tgt_) {
-        HIP_TRY(hipMalloc(&d_tgt64_, sizeof(Pt64) * std::max<int64_t>(nt_, 1)));
+        BUF_TRY(d_tgt64_.reset((size_t)std::max<int64_t>(nt_, 1)));
         HIP_TRY(launch_promote_pt64((const float4 *)d_tgt_, (Pt64 *)d_tgt64_, nt_, stream_));
-        free_dev(d_sorted64_);
+        d_sorted64_.release();
         grid_valid_ = false;
     }
     if (!d_sorted64_) grid_valid_ = false;

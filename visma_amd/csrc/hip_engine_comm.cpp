@@ -20,12 +20,7 @@ int HipEngine::shard_exchange(const Xform64 &T64, bool plane, const double offse
 {
     if (tgt_offset_ + nt_ > tgt_global_) { err_ = "target shard exceeds the global target"; return VISMA_ICP_ERR_INVALID; }
     if (!comm_ && !minreduce_) { err_ = "target-sharded mode needs visma_icp_comm_init or visma_icp_set_minreduce"; return VISMA_ICP_ERR_STATE; }
-    if (ns_ > gkeys_cap_) {
-        free_dev(d_gkeys_); free_dev(d_claim_);
-        HIP_TRY(hipMalloc(&d_gkeys_, sizeof(unsigned long long) * std::max<int64_t>(ns_, 1)));
-        HIP_TRY(hipMalloc(&d_claim_, sizeof(unsigned long long) * std::max<int64_t>(ns_, 1)));
-        gkeys_cap_ = ns_;
-    }
+    { int rc = ensure_shard_keys(); if (rc) return rc; }
     // MIN over the ranks of `keys` (RCCL on the stream, or the host-supplied exchange)
     auto min_reduce = [&](void *keys) -> int {
         if (comm_) {
@@ -84,12 +79,7 @@ int HipEngine::shard_exchange(const Xform64 &T64, bool plane, const double offse
 int HipEngine::shard_exchange_on_stream(const DevIcpState *st, int plane, int *nblocks)
 {
     if (tgt_offset_ + nt_ > tgt_global_) { err_ = "target shard exceeds the global target"; return VISMA_ICP_ERR_INVALID; }
-    if (ns_ > gkeys_cap_) {
-        free_dev(d_gkeys_); free_dev(d_claim_);
-        HIP_TRY(hipMalloc(&d_gkeys_, sizeof(unsigned long long) * std::max<int64_t>(ns_, 1)));
-        HIP_TRY(hipMalloc(&d_claim_, sizeof(unsigned long long) * std::max<int64_t>(ns_, 1)));
-        gkeys_cap_ = ns_;
-    }
+    { int rc = ensure_shard_keys(); if (rc) return rc; }
     auto min_reduce = [&](void *keys) -> int {
         int rc = g_rccl.AllReduce(keys, keys, (size_t)ns_, kNcclUint64, kNcclMin, comm_, stream_);
         if (rc != 0) {
@@ -135,12 +125,14 @@ int HipEngine::ensure_mailbox()
     if (d_mbox_) return VISMA_ICP_OK;
     const size_t bytes = sizeof(double) * 2 * kNStats * kIpcMaxRanks * 2;   // two halves, see ipc_allreduce_kernel
     // uncached device memory: remote stores and local polls both go to memory
-    if (hipExtMallocWithFlags(&d_mbox_, bytes, hipDeviceMallocUncached) != hipSuccess) {
+    void *box = nullptr;
+    if (hipExtMallocWithFlags(&box, bytes, hipDeviceMallocUncached) != hipSuccess) {
         (void)hipGetLastError();
-        HIP_TRY(hipExtMallocWithFlags(&d_mbox_, bytes, hipDeviceMallocFinegrained));
+        HIP_TRY(hipExtMallocWithFlags(&box, bytes, hipDeviceMallocFinegrained));
     }
+    d_mbox_.adopt((char *)box, bytes);
     HIP_TRY(hipMemset(d_mbox_, 0, bytes));
-    HIP_TRY(hipMalloc(&d_ipc_flag_, 16));                    // {int timeout flag, pad, u64 exchange counter}
+    BUF_TRY(d_ipc_flag_.reset(4));                           // {int timeout flag, pad, u64 exchange counter}
     HIP_TRY(hipMemset(d_ipc_flag_, 0, 16));
     return VISMA_ICP_OK;
 }
@@ -196,8 +188,8 @@ int HipEngine::ipc_init(int rank, int nranks, const void *handles)
     // stores arrive in this rank's mailbox and the other way round -- a mapping that opens but does
     // not carry traffic (no peer access between two devices) must fail HERE, not in the first iteration.
     if (nranks > 1) {
-        double *d_hs = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_hs, sizeof(double) * kNStats));
+        DevBuf<double> d_hs(device_memory());
+        BUF_TRY(d_hs.reset(kNStats));
         std::vector<double> hs((size_t)kNStats);
         for (int a = 0; a < kNStats; a++) hs[(size_t)a] = (double)((rank + 1) * (a + 1));
         hipError_t e = hipMemcpyAsync(d_hs, hs.data(), sizeof(double) * kNStats, hipMemcpyHostToDevice, stream_);
@@ -209,7 +201,7 @@ int HipEngine::ipc_init(int rank, int nranks, const void *handles)
         if (e == hipSuccess) e = hipMemcpyAsync(hs.data(), d_hs, sizeof(double) * kNStats, hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_ipc_flag_, sizeof(int), hipMemcpyDeviceToHost, stream_);
         if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-        (void)hipFree(d_hs);
+        d_hs.release();
         bool good = e == hipSuccess && flag == 0;
         const double tri = 0.5 * (double)nranks * (double)(nranks + 1);
         for (int a = 0; good && a < kNStats; a++) good = hs[(size_t)a] == tri * (double)(a + 1);
@@ -239,7 +231,7 @@ int HipEngine::ipc_init(int rank, int nranks, const void *handles)
             // (the exchange runs in the statistics buffer every context owns: no allocation that could fail on one rank
             //  only -- a rank that skipped this collective would leave the mailbox call count, and with it the half in use,
             //  out of step with its peers for every later pass)
-            double *d_id = (double *)d_stats_;
+            double *d_id = d_stats_;
             {
                 hipError_t e2 = hipMemcpyAsync(d_id, hs.data(), sizeof(double) * kNStats, hipMemcpyHostToDevice, stream_);
                 if (e2 == hipSuccess)
@@ -259,15 +251,10 @@ int HipEngine::ipc_init(int rank, int nranks, const void *handles)
             }
         }
         // the mailboxes as a table in device memory (what the persistent kernel's fold indexes)
-        free_dev(d_peer_table_);
-        if (hipMalloc(&d_peer_table_, sizeof(void *) * kIpcMaxRanks) == hipSuccess) {
-            if (hipMemcpy(d_peer_table_, peers_.box, sizeof(void *) * kIpcMaxRanks, hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipGetLastError();
-                free_dev(d_peer_table_);
-            }
-        } else {
+        if (d_peer_table_.reset(kIpcMaxRanks) == 0 &&
+            hipMemcpy(d_peer_table_, peers_.box, sizeof(void *) * kIpcMaxRanks, hipMemcpyHostToDevice) != hipSuccess) {
             (void)hipGetLastError();
-            d_peer_table_ = nullptr;
+            d_peer_table_.release();
         }
     }
     return VISMA_ICP_OK;

@@ -42,12 +42,7 @@ int HipEngine::nn_pass(const Mat4 &Tc, double max_dist)
     }
     plan_ = nn_plan(ns_, nt_pad_);
     const int64_t ns_pad = (int64_t)plan_.src_tiles * kBlock * plan_.spt;
-    const size_t need = sizeof(unsigned long long) * (size_t)ns_pad * plan_.tgt_splits;
-    if (need > keys_bytes_) {
-        free_dev(d_keys_);
-        HIP_TRY(hipMalloc(&d_keys_, need));
-        keys_bytes_ = need;
-    }
+    BUF_TRY(d_keys_.reserve((size_t)ns_pad * plan_.tgt_splits));
     rc = ensure_aux(ns_pad);
     if (rc) return rc;
     ns_pad_ = ns_pad;
@@ -165,7 +160,7 @@ int HipEngine::reduce(const Mat4 &Tc, bool plane, const double offset[3], double
                     HIP_TRY(hipMemsetAsync((unsigned long long *)d_relay_ + kPersistDead, 0, 2 * sizeof(unsigned long long), stream_));   // (dead, started)
                     if (!timeline_path_.empty()) {
                         // (measurement: clocks of up to 64 passes of this launch, read back when it has ended)
-                        if (!d_timeline_) HIP_TRY(hipMalloc(&d_timeline_, sizeof(unsigned long long) * 2 * 64 * 1024));
+                        BUF_TRY(d_timeline_.reserve(2 * 64 * 1024));
                         if (nb <= 1024) {
                             HIP_TRY(hipMemsetAsync(d_timeline_, 0, sizeof(unsigned long long) * 2 * 64 * 1024, stream_));
                             pa.timeline = (unsigned long long *)d_timeline_;
@@ -291,7 +286,7 @@ int HipEngine::reduce(const Mat4 &Tc, bool plane, const double offset[3], double
             // Whatever made it leave (the host thread away for longer than four times its patience, a command that
             // arrived torn over more than that): some workgroups may have begun the pass and others not.  Nothing of a
             // half-run pass is kept: the fold's tickets are re-armed and the winners forgotten -- the pass runs cold.
-            if (d_tickets_ && tickets_cap_ > 0) HIP_TRY(hipMemsetAsync(d_tickets_, 0, sizeof(unsigned) * tickets_cap_, stream_));
+            if (d_tickets_) HIP_TRY(hipMemsetAsync(d_tickets_, 0, d_tickets_.bytes(), stream_));
             { int irc = invalidate_pos(); if (irc) return irc; }
             int nblocks = 1;
             int rc = launch_grid_pass(T64, plane, offset, seq, false, nullptr, &nblocks, &ipc_done);
@@ -351,10 +346,9 @@ int HipEngine::launch_grid_pass(const Xform64 &T64, bool plane, const double off
             // the persistent launch folds by polling: rows and group rows as tagged granules (no tickets)
             constexpr size_t kRows = 2048, kGroups = (kRows + kFoldGroup - 1) / kFoldGroup, kRowBytes = 32 * 16;
             static_assert(kFoldGroup >= 1 && kGroups <= kRows, "group rows of the polled fold");
-            if (!d_fold_tag_) {
-                HIP_TRY(hipMalloc(&d_fold_tag_, (kRows + kGroups) * kRowBytes));
-                HIP_TRY(hipMemsetAsync(d_fold_tag_, 0, (kRows + kGroups) * kRowBytes, stream_));
-            }
+            bool grew = false;
+            BUF_TRY(d_fold_tag_.reserve((kRows + kGroups) * kRowBytes, &grew));
+            if (grew) HIP_TRY(hipMemsetAsync(d_fold_tag_, 0, (kRows + kGroups) * kRowBytes, stream_));
             if ((size_t)nblocks > kRows) { err_ = "persistent launch larger than its fold rows"; return VISMA_ICP_ERR_STATE; }
             // (the rows validate themselves with fold_row_tag(sequence number): when a session's numbers run through the
             //  tag's wrap, the buffer is cleared first -- a row of 2^32 - 1 passes ago must not validate)
@@ -577,8 +571,8 @@ int HipEngine::get_correspondences(int32_t *idx, float *d2)
 hipError_t HipEngine::PairScratch::ensure()
 {
     if (host_dev) return hipSuccess;
-    hipError_t e = hipMalloc((void **)&work, sizeof(unsigned) * kTrimWorkWords);
-    if (e == hipSuccess) e = hipMalloc((void **)&partials, sizeof(double) * kPairRow * kPairMaxBlocks);
+    hipError_t e = (hipError_t)work.reset(kTrimWorkWords);
+    if (e == hipSuccess) e = (hipError_t)partials.reset((size_t)kPairRow * kPairMaxBlocks);
     if (e == hipSuccess) e = hipHostMalloc((void **)&host, sizeof(double) * 2 * kPairMaxPublished, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) {
         std::memset(host, 0, sizeof(double) * 2 * kPairMaxPublished);
@@ -598,10 +592,12 @@ hipError_t HipEngine::PairScratch::arm(hipStream_t stream)
 
 void HipEngine::PairScratch::release()
 {
-    if (work) (void)hipFree(work);
-    if (partials) (void)hipFree(partials);
+    work.release();
+    partials.release();
     if (host) (void)hipHostFree(host);
-    *this = PairScratch();
+    host = host_dev = nullptr;
+    seq = 0;
+    dirty = false;
 }
 
 static const double kNoOffset[3] = {0, 0, 0};
@@ -694,23 +690,15 @@ int HipEngine::reduce_trimmed(const Mat4 &Tc, const double *offset, double keep,
     const int64_t m = trim_count(out->found, ns_, keep);
     out->kept = m;
     out->d2_cut = 0.0;
-    if (ns_ > trim_mask_cap_) {
-        free_dev(d_trim_mask_);
-        HIP_TRY(hipMalloc(&d_trim_mask_, (size_t)std::max<int64_t>(ns_, 1)));
-        trim_mask_cap_ = ns_;
-    }
+    BUF_TRY(d_trim_mask_.reserve((size_t)ns_));
     trim_mask_ns_ = ns_;
     if (m <= 0) {
         for (int i = 0; i < kNStats; i++) stats[i] = 0.0;
         if (ns_ > 0) HIP_TRY(hipMemsetAsync(d_trim_mask_, 0, (size_t)ns_, stream_));
         return VISMA_ICP_OK;
     }
-    if (order && (order_gen != trim_order_gen_ || order != trim_order_src_ || ns_ > trim_order_cap_)) {
-        if (ns_ > trim_order_cap_) {
-            free_dev(d_trim_order_);
-            HIP_TRY(hipMalloc(&d_trim_order_, sizeof(int32_t) * (size_t)ns_));
-            trim_order_cap_ = ns_;
-        }
+    if (order && (order_gen != trim_order_gen_ || order != trim_order_src_ || (size_t)ns_ > d_trim_order_.count())) {
+        BUF_TRY(d_trim_order_.reserve((size_t)ns_));
         HIP_TRY(hipMemcpyAsync(d_trim_order_, order, sizeof(int32_t) * (size_t)ns_, hipMemcpyHostToDevice, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));                 // (the caller's vector may change after this call)
         trim_order_gen_ = order_gen;
@@ -756,18 +744,10 @@ int HipEngine::reduce_robust(const Mat4 &Tc, const double *offset, bool plane, c
     if (rc) return rc;
     *out = found;
     const int64_t K = out->found;
-    if (ns_ > rob_w_cap_) {
-        free_dev(d_rob_w_);
-        HIP_TRY(hipMalloc(&d_rob_w_, sizeof(double) * (size_t)std::max<int64_t>(ns_, 1)));
-        rob_w_cap_ = ns_;
-    }
+    BUF_TRY(d_rob_w_.reserve((size_t)ns_));
     rob_w_ns_ = -1;                                          // (until this pass has written every weight)
     const bool automatic = cfg.scale == 0.0 && K > 0;        // (K == 0: c = min_scale, nothing to rank)
-    if (automatic && plane && ns_ > rob_r2_cap_) {
-        free_dev(d_rob_r2_);
-        HIP_TRY(hipMalloc(&d_rob_r2_, sizeof(float) * (size_t)std::max<int64_t>(ns_, 1)));
-        rob_r2_cap_ = ns_;
-    }
+    if (automatic && plane) BUF_TRY(d_rob_r2_.reserve((size_t)ns_));
     RobustArgs a;
     rc = pair_pass_args("robust", Tc, offset, &a);
     if (rc) return rc;
@@ -820,12 +800,12 @@ int HipEngine::set_source_normals(const float *nxyzw, const Pt64 *n64, int64_t n
 {
     HIP_TRY(hipSetDevice(device_));
     if (ns != ns_) { err_ = "normals count != source count"; return VISMA_ICP_ERR_INVALID; }
-    free_dev(d_snrm_); free_dev(d_snrm64_);
+    d_snrm_.release(); d_snrm64_.release();
     has_source_normals_ = false;
-    HIP_TRY(hipMalloc(&d_snrm_, sizeof(float4) * (size_t)std::max<int64_t>(ns, 1)));
+    BUF_TRY(d_snrm_.reset((size_t)std::max<int64_t>(ns, 1)));
     if (ns > 0) HIP_TRY(hipMemcpy(d_snrm_, nxyzw, sizeof(float4) * (size_t)ns, hipMemcpyHostToDevice));
     if (n64 && d_src64_) {                                   // (read where the pass sums from the f64 clouds)
-        HIP_TRY(hipMalloc(&d_snrm64_, sizeof(Pt64) * (size_t)std::max<int64_t>(ns, 1)));
+        BUF_TRY(d_snrm64_.reset((size_t)std::max<int64_t>(ns, 1)));
         if (ns > 0) HIP_TRY(hipMemcpy(d_snrm64_, n64, sizeof(Pt64) * (size_t)ns, hipMemcpyHostToDevice));
     }
     has_source_normals_ = true;
@@ -861,9 +841,9 @@ int HipEngine::set_source_intensity(const double *by_position, int64_t ns)
 {
     HIP_TRY(hipSetDevice(device_));
     if (ns != ns_) { err_ = "colours count != source count"; return VISMA_ICP_ERR_INVALID; }
-    free_dev(d_sint_);
+    d_sint_.release();
     has_source_colors_ = false;
-    HIP_TRY(hipMalloc(&d_sint_, sizeof(double) * (size_t)std::max<int64_t>(ns, 1)));
+    BUF_TRY(d_sint_.reset((size_t)std::max<int64_t>(ns, 1)));
     if (ns > 0) HIP_TRY(hipMemcpy(d_sint_, by_position, sizeof(double) * (size_t)ns, hipMemcpyHostToDevice));
     has_source_colors_ = true;
     return VISMA_ICP_OK;
@@ -873,10 +853,10 @@ int HipEngine::set_target_intensity(const double *by_index, int64_t nt)
 {
     HIP_TRY(hipSetDevice(device_));
     if (nt != nt_) { err_ = "colours count != target count"; return VISMA_ICP_ERR_INVALID; }
-    free_dev(d_tint_);
+    d_tint_.release();
     has_target_colors_ = false;
     drop_color_gradient();
-    HIP_TRY(hipMalloc(&d_tint_, sizeof(double) * (size_t)std::max<int64_t>(nt, 1)));
+    BUF_TRY(d_tint_.reset((size_t)std::max<int64_t>(nt, 1)));
     if (nt > 0) HIP_TRY(hipMemcpy(d_tint_, by_index, sizeof(double) * (size_t)nt, hipMemcpyHostToDevice));
     has_target_colors_ = true;
     return VISMA_ICP_OK;
@@ -892,7 +872,7 @@ int HipEngine::prepare_colored(double radius, int max_nn)
     if (!d_nrm_ || !d_tint_ || !d_tgt_) { err_ = "colored ICP needs target normals and target colours"; return VISMA_ICP_ERR_STATE; }
     if (sess_live_) { int rc = end_session(); if (rc) return rc; }
     drop_color_gradient();
-    HIP_TRY(hipMalloc(&d_grad_, sizeof(double) * 3 * (size_t)std::max<int64_t>(nt_, 1)));
+    BUF_TRY(d_grad_.reset(3 * (size_t)std::max<int64_t>(nt_, 1)));
     ColorGradientInput in;
     if (d_tgt64_) in.xyz64 = (const Pt64 *)d_tgt64_; else in.xyz32 = (const float4 *)d_tgt_;
     if (d_tgt64_ && d_nrm64_) in.nrm64 = (const Pt64 *)d_nrm64_; else in.nrm32 = (const float4 *)d_nrm_;
@@ -901,7 +881,7 @@ int HipEngine::prepare_colored(double radius, int max_nn)
     HIP_TRY(hipStreamSynchronize(stream_));
     hipError_t e = color_gradient_on_device(in, radius, max_nn, (double *)d_grad_, stream_);
     if (e != hipSuccess) {
-        free_dev(d_grad_);
+        d_grad_.release();
         err_ = std::string("color gradient: ") + hipGetErrorString(e);
         return e == hipErrorInvalidValue ? VISMA_ICP_ERR_INVALID : VISMA_ICP_ERR_HIP;
     }
@@ -990,14 +970,11 @@ int HipEngine::odometry_prepare(const OdometryInput &in)
     const size_t n0 = (size_t)in.w * in.h;
     const size_t at_txyz = take(sizeof(float4) * n0), at_idx = take(sizeof(int32_t) * n0);
     const size_t at_tmp0 = take(sizeof(float) * n0), at_tmp1 = take(sizeof(float) * n0);
-    if (bytes > o.arena_bytes) {
+    if (bytes > o.arena.count()) {
         HIP_TRY(hipStreamSynchronize(stream_));
-        if (o.arena) (void)hipFree(o.arena);
-        o.arena = nullptr; o.arena_bytes = 0;
-        HIP_TRY(hipMalloc(&o.arena, bytes));
-        o.arena_bytes = bytes;
+        BUF_TRY(o.arena.reset(bytes));
     }
-    char *base = (char *)o.arena;
+    char *base = o.arena;
     for (int l = 0; l < in.n_levels; l++) {
         for (int k = 0; k < kOdoSrcXyz; k++) o.img[l][k] = (float *)(base + at_img[l][k]);
         o.src_xyz[l] = (float4 *)(base + at_xyz[l]);
@@ -1341,50 +1318,22 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
     if (use_grid_) {
         rc = ensure_aux(ns_rounded * nprob);
         if (rc) return rc;
-        const size_t rows = (size_t)reduce_max_blocks() * nprob;
-        if (rows > partial_rows_) {
-            free_dev(d_partials_);
-            HIP_TRY(hipMalloc(&d_partials_, sizeof(double) * kReduceAcc * rows));
-            partial_rows_ = rows;
-        }
+        rc = ensure_partials((size_t)reduce_max_blocks() * nprob);
+        if (rc) return rc;
     } else {
         plan_ = nn_plan(ns_, nt_pad_);
         ns_pad_ = (int64_t)plan_.src_tiles * kBlock * plan_.spt;
-        const size_t need = sizeof(unsigned long long) * (size_t)ns_pad_ * plan_.tgt_splits;
-        if (need > keys_bytes_) {
-            free_dev(d_keys_);
-            HIP_TRY(hipMalloc(&d_keys_, need));
-            keys_bytes_ = need;
-        }
+        BUF_TRY(d_keys_.reserve((size_t)ns_pad_ * plan_.tgt_splits));
         rc = ensure_aux(ns_pad_);
         if (rc) return rc;
         if (brute_exact()) { rc = ensure_second(ns_pad_, plan_.tgt_splits); if (rc) return rc; }
     }
-    if (nprob > state_cap_) {
-        free_dev(d_state_);
-        if (h_state_) { (void)hipHostFree(h_state_); h_state_ = nullptr; }
-        HIP_TRY(hipMalloc(&d_state_, sizeof(DevIcpState) * nprob));
-        HIP_TRY(hipHostMalloc((void **)&h_state_, sizeof(DevIcpState) * nprob, hipHostMallocDefault));
-        state_cap_ = nprob;
-    }
-    for (int b = 0; b < nprob; b++) {
-        DevIcpState &h = h_state_[b];
-        std::memset(&h, 0, sizeof(h));
-        const Mat4 &T0 = Tc0s ? Tc0s[b] : lp.Tc0;
-        for (int i = 0; i < 12; i++) h.Tc[i] = T0.m[i];
-        for (int a = 0; a < 3; a++) h.centre[a] = lp.centre[a];
-        h.rel_fit = lp.rel_fit; h.rel_rmse = lp.rel_rmse;
-        h.ns_total = lp.ns_total > 0 ? lp.ns_total : ns_;
-        h.active = 1;
-        h.max_iter = lp.max_iter; h.solver = lp.solver; h.scaling = lp.scaling ? 1 : 0;
-        h.plane = lp.plane ? 1 : 0; h.world_frame = lp.world ? 1 : 0;
-        h.check_stop = lp.check_stop ? 1 : 0;
-        h.r2f = r2f_;
-        h.use_axis = lp.use_axis ? 1 : 0;
-        for (int a = 0; a < 3; a++) h.axis[a] = lp.axis[a];
-    }
+    rc = ensure_states(nprob);
+    if (rc) return rc;
+    for (int b = 0; b < nprob; b++)
+        fill_state(h_state_[b], lp, Tc0s ? Tc0s[b] : lp.Tc0, lp.centre, lp.ns_total > 0 ? lp.ns_total : ns_, r2f_);
     HIP_TRY(hipMemcpyAsync(d_state_, h_state_, sizeof(DevIcpState) * nprob, hipMemcpyHostToDevice, stream_));
-    DevIcpState *st = (DevIcpState *)d_state_;
+    DevIcpState *st = d_state_;
     const Xform64 T64{};   // ignored: the kernels read the transform from the state
     const int plane = lp.plane ? 1 : 0;
     // with a stop test the host looks at the state every `chunk` passes; launches
@@ -1411,20 +1360,16 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
             if ((int64_t)nb * kBlock >= ns_ && (int64_t)nb * nprob <= (int64_t)((double)cap * persist_cu_share()) &&
                 g_persist_slot[device_].compare_exchange_strong(expect, 1)) {
                 struct SlotGuard { int d; ~SlotGuard() { g_persist_slot[d].store(0); } } guard{device_};
-                if (nprob > sweep_relay_cap_) {
-                    if (d_sweep_relay_) (void)hipFree(d_sweep_relay_);
-                    d_sweep_relay_ = nullptr; sweep_relay_cap_ = 0;
-                    HIP_TRY(hipMalloc(&d_sweep_relay_, sizeof(unsigned long long) * (32 * (size_t)nprob + 8)));
-                    sweep_relay_cap_ = nprob;
-                    sweep_tag_ = 0;
-                }
+                bool relay_grew = false;
+                BUF_TRY(d_sweep_relay_.reserve(32 * (size_t)nprob, &relay_grew, 8));
+                if (relay_grew) sweep_tag_ = 0;
                 const int rem = lp.passes - done;
                 if (sweep_tag_ == 0u || sweep_tag_ + (unsigned)rem + 2u < sweep_tag_) {
                     // (tags never 0, never wrap inside a launch: a cleared relay validates nothing)
-                    HIP_TRY(hipMemsetAsync(d_sweep_relay_, 0, sizeof(unsigned long long) * (32 * (size_t)sweep_relay_cap_ + 8), stream_));
+                    HIP_TRY(hipMemsetAsync(d_sweep_relay_, 0, d_sweep_relay_.bytes(), stream_));
                     sweep_tag_ = 1u;
                 }
-                unsigned long long *dead = (unsigned long long *)d_sweep_relay_ + 32 * (size_t)sweep_relay_cap_;
+                unsigned long long *dead = d_sweep_relay_ + d_sweep_relay_.count();
                 HIP_TRY(hipMemsetAsync(dead, 0, sizeof(unsigned long long), stream_));
                 SearchArgs a = search_args();
                 a.max_blocks = reduce_max_blocks();            // (nb workgroups per problem)
@@ -1561,14 +1506,7 @@ int HipEngine::run_loop(const LoopParams &lp, const Mat4 *Tc0s, int nprob, LoopR
         for (int b = 0; b < nprob; b++) any = any || h_state_[b].active;
         if (!any) break;
     }
-    for (int b = 0; b < nprob; b++) {
-        const DevIcpState &h = h_state_[b];
-        out[b].Tc = Mat4::identity();
-        for (int i = 0; i < 12; i++) out[b].Tc.m[i] = h.Tc[i];
-        out[b].fit = h.fit; out[b].rmse = h.rmse;
-        out[b].k = (int64_t)std::llround(h.K);
-        out[b].iters = h.iter; out[b].passes = h.passes;
-    }
+    read_results(nprob, out);
     for (int i = 0; i < 12; i++) T32_.m[i] = (float)h_state_[0].Tc[i];
     have_pass_ = true;
     grid_pending_ = false;
@@ -1650,23 +1588,18 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
         total_blocks += d.nblocks;
     }
     // ---- device buffers
-    if (src_tot > bt_src_cap_) {
-        free_dev(bt_src_);
-        HIP_TRY(hipMalloc(&bt_src_, sizeof(float4) * std::max<int64_t>(src_tot, 1)));
-        bt_src_cap_ = src_tot;
-    }
+    BUF_TRY(bt_src_.reserve((size_t)src_tot));
     bool f64 = B > 0;
     for (int b = 0; b < B; b++) {
         const BatchProblem &q = pb[b];
         const BatchProblem &sq = q.src_share >= 0 ? pb[q.src_share] : q, &tq = q.grid_share >= 0 ? pb[q.grid_share] : q;
         f64 = f64 && (q.ns == 0 || sq.src64) && (q.nt == 0 || tq.tgt64 || (tq.tgt_raw && tq.tgt_f64));
     }
-    if (f64 && (src_tot > bt_src64_cap_ || tgt_tot > bt_tgt64_cap_)) {
-        free_dev(bt_src64_); free_dev(bt_tgt64_); free_dev(bt_sorted64_);
-        HIP_TRY(hipMalloc(&bt_src64_, sizeof(Pt64) * std::max<int64_t>(src_tot, 1)));
-        HIP_TRY(hipMalloc(&bt_tgt64_, sizeof(Pt64) * std::max<int64_t>(tgt_tot, 1)));
-        HIP_TRY(hipMalloc(&bt_sorted64_, sizeof(Pt64) * std::max<int64_t>(tgt_tot, 1)));
-        bt_src64_cap_ = src_tot; bt_tgt64_cap_ = tgt_tot;
+    // (the three f64 arrays are renewed together, at this batch's sizes, as soon as one of them is short)
+    if (f64 && ((size_t)src_tot > bt_src64_.count() || (size_t)tgt_tot > bt_tgt64_.count() || (size_t)tgt_tot > bt_sorted64_.count())) {
+        BUF_TRY(bt_src64_.reset((size_t)std::max<int64_t>(src_tot, 1)));
+        BUF_TRY(bt_tgt64_.reset((size_t)std::max<int64_t>(tgt_tot, 1)));
+        BUF_TRY(bt_sorted64_.reset((size_t)std::max<int64_t>(tgt_tot, 1)));
     }
     if (lp.plane) {
         for (int b = 0; b < B; b++) {
@@ -1677,75 +1610,34 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
             }
         }
         if (f64 && !exact_) { err_ = "point-to-plane batches run the exact or the fp32 search"; return VISMA_ICP_ERR_STATE; }
-        if (f64 && tgt_tot > bt_nrm64_cap_) {
-            free_dev(bt_nrm64_);
-            HIP_TRY(hipMalloc(&bt_nrm64_, sizeof(Pt64) * std::max<int64_t>(tgt_tot, 1)));
-            bt_nrm64_cap_ = tgt_tot;
-        }
-        if (!f64 && tgt_tot > bt_nrm_cap_) {
-            free_dev(bt_nrm_);
-            HIP_TRY(hipMalloc(&bt_nrm_, sizeof(float4) * std::max<int64_t>(tgt_tot, 1)));
-            bt_nrm_cap_ = tgt_tot;
-        }
+        if (f64) BUF_TRY(bt_nrm64_.reserve((size_t)tgt_tot));
+        else BUF_TRY(bt_nrm_.reserve((size_t)tgt_tot));
     }
-    if (out_tot > bt_out_cap_) {
-        free_dev(bt_idx_); free_dev(bt_d2_); free_dev(bt_pos_);
-        HIP_TRY(hipMalloc(&bt_idx_, sizeof(int32_t) * std::max<int64_t>(out_tot, 1)));
-        HIP_TRY(hipMalloc(&bt_d2_, sizeof(float) * std::max<int64_t>(out_tot, 1)));
-        HIP_TRY(hipMalloc(&bt_pos_, sizeof(Pt64) * std::max<int64_t>(out_tot, 1)));
-        bt_out_cap_ = out_tot;
-    }
+    BUF_TRY(bt_idx_.reserve((size_t)out_tot));
+    BUF_TRY(bt_d2_.reserve((size_t)out_tot));
+    BUF_TRY(bt_pos_.reserve((size_t)out_tot));
     tr.mark("layout, buffers");
     // (new problems: no previous winners)
     HIP_TRY(hipMemsetAsync(bt_pos_, 0xFF, sizeof(Pt64) * (size_t)std::max<int64_t>(out_tot, 1), stream_));
     {
         bool any_raw = false;
         for (int b = 0; b < B; b++) any_raw = any_raw || pb[b].tgt_raw != nullptr;
-        if (any_raw && (size_t)tgt_tot * 24 > bt_raw_bytes_) {
-            free_dev(bt_raw_);
-            HIP_TRY(hipMalloc(&bt_raw_, (size_t)std::max<int64_t>(tgt_tot, 1) * 24));
-            bt_raw_bytes_ = (size_t)tgt_tot * 24;
-        }
+        if (any_raw) BUF_TRY(bt_raw_.reserve(3 * (size_t)tgt_tot));
     }
-    if (tgt_tot > bt_tgt_cap_) {
-        free_dev(bt_tgt_); free_dev(bt_sorted_); free_dev(bt_cell_of_);
-        HIP_TRY(hipMalloc(&bt_tgt_, sizeof(float4) * std::max<int64_t>(tgt_tot, 1)));
-        HIP_TRY(hipMalloc(&bt_sorted_, sizeof(float4) * (std::max<int64_t>(tgt_tot, 1) + kSortedSlack)));
-        HIP_TRY(hipMalloc(&bt_cell_of_, 2 * sizeof(unsigned) * std::max<int64_t>(tgt_tot, 1)));   // (cell, rank)
-        bt_tgt_cap_ = tgt_tot;
-    }
-    if (cell_tot > bt_cell_cap_) {
-        free_dev(bt_count_); free_dev(bt_start_);
-        HIP_TRY(hipMalloc(&bt_count_, sizeof(unsigned) * cell_tot));
-        HIP_TRY(hipMalloc(&bt_start_, sizeof(unsigned) * (cell_tot + 8)));      // (16-byte reads near the end)
-        HIP_TRY(hipMemsetAsync(bt_start_, 0, sizeof(unsigned) * (cell_tot + 8), stream_));
-        bt_cell_cap_ = cell_tot;
-    }
-    if (grid_scan_blocks(max_ncell) + 1 > bt_bsum_cap_) {
-        free_dev(bt_bsum_);
-        bt_bsum_cap_ = grid_scan_blocks(max_ncell) + 1;
-        HIP_TRY(hipMalloc(&bt_bsum_, sizeof(unsigned) * bt_bsum_cap_));
-    }
+    BUF_TRY(bt_tgt_.reserve((size_t)tgt_tot));
+    BUF_TRY(bt_sorted_.reserve((size_t)tgt_tot, nullptr, kSortedSlack));
+    BUF_TRY(bt_cell_of_.reserve(2 * (size_t)tgt_tot));          // (cell, rank)
+    BUF_TRY(bt_count_.reserve((size_t)cell_tot));
+    bool start_grew = false;
+    BUF_TRY(bt_start_.reserve((size_t)cell_tot, &start_grew, 8));   // (16-byte reads near the end)
+    if (start_grew) HIP_TRY(hipMemsetAsync(bt_start_, 0, bt_start_.bytes(), stream_));
+    BUF_TRY(bt_bsum_.reserve((size_t)grid_scan_blocks(max_ncell) + 1));
     // descriptors, followed by the workgroup -> problem map (one word per workgroup: the warm kernel reads its
     // problem with one load instead of a binary search over the descriptors -- ~9 dependent scalar loads per wave)
     const size_t desc_bytes = sizeof(ProbDesc) * (size_t)B + sizeof(int) * (size_t)std::max(total_blocks, 1);
-    if (desc_bytes > bt_desc_cap_) {
-        free_dev(bt_descs_);
-        HIP_TRY(hipMalloc(&bt_descs_, desc_bytes));
-        bt_desc_cap_ = desc_bytes;
-    }
-    if ((size_t)total_blocks > partial_rows_) {
-        free_dev(d_partials_);
-        HIP_TRY(hipMalloc(&d_partials_, sizeof(double) * kReduceAcc * (size_t)total_blocks));
-        partial_rows_ = (size_t)total_blocks;
-    }
-    if (B > state_cap_) {
-        free_dev(d_state_);
-        if (h_state_) { (void)hipHostFree(h_state_); h_state_ = nullptr; }
-        HIP_TRY(hipMalloc(&d_state_, sizeof(DevIcpState) * B));
-        HIP_TRY(hipHostMalloc((void **)&h_state_, sizeof(DevIcpState) * B, hipHostMallocDefault));
-        state_cap_ = B;
-    }
+    BUF_TRY(bt_descs_.reserve(desc_bytes));
+    { int brc = ensure_partials((size_t)total_blocks); if (brc) return brc; }
+    { int brc = ensure_states(B); if (brc) return brc; }
     last_mode_ = f64 ? (exact_ ? 1 : 2) : 0;
     // ---- uploads + per-problem grid builds (stream ordered, no host sync)
     int e0 = -1;
@@ -1758,7 +1650,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
             HIP_TRY(hipMemcpyAsync((Pt64 *)bt_src64_ + d.src_off, q.src64, sizeof(Pt64) * q.ns, hipMemcpyHostToDevice, stream_));
         if (q.grid_share >= 0) continue;
         if (q.nt > 0 && q.tgt_raw) {
-            double *raw = (double *)bt_raw_ + 3 * d.sorted_off;
+            double *raw = bt_raw_ + 3 * d.sorted_off;
             HIP_TRY(hipMemcpyAsync(raw, q.tgt_raw, sizeof(double) * 3 * q.nt, hipMemcpyHostToDevice, stream_));
             HIP_TRY(launch_expand_f64(raw, q.nt, q.centre, (float4 *)bt_tgt_ + d.sorted_off,
                                       f64 ? (Pt64 *)bt_tgt64_ + d.sorted_off : nullptr, stream_));
@@ -1780,11 +1672,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
     }
     const bool packed = f64 && exact_;                   // the exact search ranks on packed (x,y,z) triples
     if (packed) {
-        if (tgt_tot > bt_sorted12_cap_) {
-            free_dev(bt_sorted12_);
-            HIP_TRY(hipMalloc(&bt_sorted12_, sizeof(float) * 3 * (size_t)(std::max<int64_t>(tgt_tot, 1) + kSortedSlack)));
-            bt_sorted12_cap_ = tgt_tot;
-        }
+        BUF_TRY(bt_sorted12_.reserve(3 * (size_t)tgt_tot, nullptr, 3 * kSortedSlack));
         HIP_TRY(launch_pack12((const float4 *)bt_sorted_, (float *)bt_sorted12_, tgt_tot, stream_));
     }
     bt_desc_host_.resize(desc_bytes);
@@ -1795,20 +1683,8 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
             for (int k = 0; k < descs[b].nblocks; k++) map[descs[b].first_block + k] = b;
     }
     HIP_TRY(hipMemcpyAsync(bt_descs_, bt_desc_host_.data(), desc_bytes, hipMemcpyHostToDevice, stream_));
-    for (int b = 0; b < B; b++) {
-        DevIcpState &h = h_state_[b];
-        std::memset(&h, 0, sizeof(h));
-        for (int i = 0; i < 12; i++) h.Tc[i] = pb[b].Tc0.m[i];
-        for (int a = 0; a < 3; a++) h.centre[a] = pb[b].centre[a];
-        h.rel_fit = lp.rel_fit; h.rel_rmse = lp.rel_rmse;
-        h.ns_total = pb[b].ns;
-        h.active = 1;
-        h.max_iter = lp.max_iter; h.solver = lp.solver; h.scaling = lp.scaling ? 1 : 0;
-        h.plane = lp.plane ? 1 : 0; h.world_frame = lp.world ? 1 : 0; h.check_stop = lp.check_stop ? 1 : 0;
-        h.r2f = (float)(pb[b].max_dist * pb[b].max_dist);
-        h.use_axis = lp.use_axis ? 1 : 0;
-        for (int a = 0; a < 3; a++) h.axis[a] = lp.axis[a];
-    }
+    for (int b = 0; b < B; b++)
+        fill_state(h_state_[b], lp, pb[b].Tc0, pb[b].centre, pb[b].ns, (float)(pb[b].max_dist * pb[b].max_dist));
     HIP_TRY(hipMemcpyAsync(d_state_, h_state_, sizeof(DevIcpState) * B, hipMemcpyHostToDevice, stream_));
     // the staging memory of the caller must stay valid until the copies are done
     tr.mark("uploads, grids enqueued");
@@ -1816,7 +1692,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
     tr.mark("... and finished");
     if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 2}); }
     // ---- the loop: one NN launch (search + fold) + one solve launch per pass for ALL problems
-    DevIcpState *st = (DevIcpState *)d_state_;
+    DevIcpState *st = d_state_;
     SearchArgs ba;
     FoldArgs &bfa = ba.fold;
     if (fused_fold_) {
@@ -1845,7 +1721,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
     if (f64) { ba.src64 = (const Pt64 *)bt_src64_; ba.sorted64 = (const Pt64 *)bt_sorted64_; }
     ba.start = (const unsigned *)bt_start_;
     if (lp.plane && f64) ba.nrm64 = (const Pt64 *)bt_nrm64_; else if (lp.plane) ba.nrm = (const float4 *)bt_nrm_;
-    ba.descs = (const ProbDesc *)bt_descs_;
+    ba.descs = (const ProbDesc *)bt_descs_.get();
     ba.nprob = B;
     ba.total_blocks = total_blocks;
     ba.one_per_lane = one_per_lane ? 1 : 0;
@@ -1869,7 +1745,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
             if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 0}); }
             if (profiling_) { e0 = next_event_pair(); HIP_TRY(hipEventRecord(ev_[e0], stream_)); }
             if (fused_fold_) { if (!bfa.solve) HIP_TRY(launch_solve_state(st, B, stream_)); }
-            else HIP_TRY(launch_finalize_solve_batch((const double *)d_partials_, (const ProbDesc *)bt_descs_, st, B, stream_, lp.plane ? 1 : 0));
+            else HIP_TRY(launch_finalize_solve_batch((const double *)d_partials_, (const ProbDesc *)bt_descs_.get(), st, B, stream_, lp.plane ? 1 : 0));
             if (profiling_) { HIP_TRY(hipEventRecord(ev_[e0 + 1], stream_)); pending_.push_back({e0, 1}); }
         }
         done += n;
@@ -1882,14 +1758,7 @@ int HipEngine::run_loop_batch(const LoopParams &lp, const std::vector<BatchProbl
         if (!any) break;
     }
     tr.mark("passes");
-    for (int b = 0; b < B; b++) {
-        const DevIcpState &h = h_state_[b];
-        out[b].Tc = Mat4::identity();
-        for (int i = 0; i < 12; i++) out[b].Tc.m[i] = h.Tc[i];
-        out[b].fit = h.fit; out[b].rmse = h.rmse;
-        out[b].k = (int64_t)std::llround(h.K);
-        out[b].iters = h.iter; out[b].passes = h.passes;
-    }
+    read_results(B, out);
     return VISMA_ICP_OK;
 }
 
