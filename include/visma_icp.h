@@ -185,7 +185,26 @@ VISMA_ICP_API int visma_icp_get_mesh_source(visma_icp_ctx *ctx, double *xyz_out,
  * BOTH clouds on one point; these setters (and the _device ones) upload in the caller's frame.
  * The two frames cannot be combined: the first uncentred upload after a centred one INVALIDATES
  * the other cloud -- set it again (the next run fails with VISMA_ICP_ERR_STATE "clouds not set"
- * otherwise). */
+ * otherwise).
+ *
+ * POINTS THAT ARE NOT FINITE (NaN or +-inf in a coordinate; the NaN rows of an organised cloud from a depth camera) are
+ * no error, in any upload, search kernel (brute force, lane-serial, warm cooperative one launch per pass or persistent,
+ * ring, wave; fp32, exact or f64 precision), nn_mode or loop.  The rule is DELETE AND REMAP; it is the arithmetic of
+ * vk_nn_pass_f32 in oracle/icp_oracle.c, where `d < best` is false for a NaN and for an inf:
+ *   1. a source point whose TRANSFORMED position has a coordinate that is not finite has no pair;
+ *   2. a target point with a coordinate that is not finite is nobody's partner;
+ *   3. every other query gets the partner, the d2 bits and the tie-break (lowest original index) it gets on the clouds
+ *      with those rows deleted; indices refer to the caller's order;
+ *   4. K, the kept pairs of a trimmed pass, the weights of a robust one and the 38 statistics are those of the deleted
+ *      clouds (the trimmed share stays floor(keep * ns) with ns the source rows as uploaded, finite or not);
+ *   5. a run / iterate / sweep / batch over such clouds ends and returns the pose of the same call on the deleted clouds;
+ *   6. visma_icp_set_clouds_f64 centres both clouds on the target's centroid: a TARGET coordinate that is not finite
+ *      makes that centre non-finite, so nothing has a pair -- K = 0 and the pose stays the initial one; a SOURCE row
+ *      that is not finite follows 1, 3 and 4 there too.
+ * The grid's bounding box is the box of the target coordinates that ARE finite (a target without any is one empty
+ * cell); a finite row far away (1e30) only makes the cells coarse.  A box of finite coordinates wider than half the
+ * fp32 range (1.7e38) on an axis cannot be binned in fp32: the grid searches refuse it with VISMA_ICP_ERR_INVALID,
+ * VISMA_ICP_NN_BRUTE searches it.  tests/test_core_hostile.py pins all of this against an independent reference. */
 VISMA_ICP_API int visma_icp_set_target(visma_icp_ctx *ctx, const float *xyz, int64_t nt,
                                        int stride_floats);
 VISMA_ICP_API int visma_icp_set_source(visma_icp_ctx *ctx, const float *xyz, int64_t ns,
@@ -206,7 +225,7 @@ VISMA_ICP_API int visma_icp_set_target_normals_f64(visma_icp_ctx *ctx,
  * GetRegistrationResultAndCorrespondences (Registration.cpp:41-96): apply T
  * (caller frame) to the pristine source and find, per source point, the
  * nearest target point with d^2 < (float)(max_dist^2).  Results stay on the
- * device. */
+ * device.  Points that are not finite: the rule at visma_icp_set_target. */
 VISMA_ICP_API int visma_icp_nn_pass(visma_icp_ctx *ctx, const double T[16],
                                     double max_dist);
 /* Per-correspondence Jacobian/residual + wavefront-shuffle reduction to the
@@ -1063,7 +1082,7 @@ VISMA_ICP_API int visma_icp_registration_ransac_correspondence(visma_icp_ctx *ct
  *
  * No floating-point atomics: a run is bit-identical to itself, and an edge's matrix does not depend on what else a call
  * computed.  K = 0: the zero matrix, VISMA_ICP_OK.  A non-finite entry of T: the zero matrix and *k = 0 without a search
- * (as the RANSAC validation treats such a pose).  Non-finite points are what the search makes of them, no error: a
+ * (as the RANSAC validation treats such a pose).  Non-finite points follow the rule at visma_icp_set_target, no error: a
  * non-finite SOURCE point has no pair (the matrix is that of the other pairs); a non-finite TARGET coordinate makes the
  * centroid visma_icp_set_clouds_f64 centres both clouds on non-finite, so nothing has a pair: K = 0, the zero matrix.
  * Clouds not set: VISMA_ICP_ERR_STATE.

@@ -51,6 +51,14 @@ __device__ __forceinline__ int cell_coord(float v, float mn, float inv_h, int di
     return (int)u;
 }
 
+// The squared cell edge the slab bounds of every grid search are formed with: a little short (fp32 rounding of d2), and
+// FINITE.  One far-away finite target row (1e30) stretches the box until the cell edge's square overflows fp32; with
+// +inf here the bound of the query's own row -- 0 cells away -- became 0 * inf = NaN, and the warm search, which lists a
+// cell only where `bound <= limit` holds, listed none (tests/test_core_hostile.py, the `big` rows).  A capped edge
+// makes a bound smaller, never larger: a cell more is visited, none is missed.  For every other grid the value is
+// unchanged to the bit.
+__device__ __forceinline__ float slab_h2(float h) { return fminf(h * h, 3.0e38f) * (1.0f - 1e-5f); }
+
 __device__ __forceinline__ float sqdist_f32(const float4 q, float px, float py, float pz)
 {
     const float dx = q.x - px, dy = q.y - py, dz = q.z - pz;

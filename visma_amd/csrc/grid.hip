@@ -41,12 +41,16 @@ __global__ void bbox_init_kernel(unsigned *box)
 __global__ __launch_bounds__(256) void bbox_kernel(const float4 *__restrict__ pts, int n,
                                                    unsigned *__restrict__ box)
 {
+    // The box of the coordinates that ARE finite: fminf / fmaxf skip a NaN by themselves, an infinite coordinate is
+    // turned into one first.  (An infinite extent used to collapse its axis to one cell, whose queries then looked at
+    // no cell at all; a point that is not finite is nobody's partner and may land in any cell.)
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float4 q = pts[i];
-        mn[0] = fminf(mn[0], q.x); mx[0] = fmaxf(mx[0], q.x);
-        mn[1] = fminf(mn[1], q.y); mx[1] = fmaxf(mx[1], q.y);
-        mn[2] = fminf(mn[2], q.z); mx[2] = fmaxf(mx[2], q.z);
+        const float4 p = pts[i];
+        const float q[3] = {fabsf(p.x) < INFINITY ? p.x : NAN, fabsf(p.y) < INFINITY ? p.y : NAN,
+                            fabsf(p.z) < INFINITY ? p.z : NAN};
+#pragma unroll
+        for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], q[a]); mx[a] = fmaxf(mx[a], q[a]); }
     }
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -238,10 +242,15 @@ GridParams grid_plan(const float mn[3], const float mx[3], double max_dist, int6
         if (f >= 1.0 && f <= 64.0) h = (float)(max_dist * 1.001 * f);
     }
     if (!(h > 0.f) || !isfinite(h)) h = 1.0f;
+    // An axis without a finite box (no finite coordinate on it: launch_grid_bbox leaves +inf .. -inf; a caller's box that
+    // is not finite) is one cell at the origin: every query finds cell 0 or nothing, never a cell coordinate formed
+    // from a non-finite origin.
+    float lo[3];
     double ext[3];
     for (int a = 0; a < 3; a++) {
-        ext[a] = (double)mx[a] - (double)mn[a];
-        if (!(ext[a] >= 0.0) || !isfinite(ext[a])) ext[a] = 0.0;
+        const bool boxed = isfinite(mn[a]) && isfinite(mx[a]) && mn[a] <= mx[a];
+        lo[a] = boxed ? mn[a] : 0.f;
+        ext[a] = boxed ? (double)mx[a] - (double)mn[a] : 0.0;
     }
     for (;;) {
         double n = 1.0;
@@ -268,7 +277,7 @@ GridParams grid_plan(const float mn[3], const float mx[3], double max_dist, int6
             g.dim[2] = (int)dz;
         }
     }
-    for (int a = 0; a < 3; a++) g.mn[a] = mn[a];
+    for (int a = 0; a < 3; a++) g.mn[a] = lo[a];
     g.h = h;
     g.inv_h = 1.0f / h;
     g.hs = g.sub == 2 ? 0.5f * h : h;
@@ -410,7 +419,10 @@ __device__ __forceinline__ float med3_f32(float a, float b, float c)
 // straight-line VALU code: compares first, then the values (v_med3 / v_min), then the positions
 // (v_cndmask).  Written as one asm block per insertion: the compiler turns the equivalent selects
 // into nested exec-mask regions (it knows d < h1 implies d < h2), which costs more scalar
-// instructions than the selects it avoids.  d is never NaN here.
+// instructions than the selects it avoids.  A NaN d (a candidate that is not finite) never gets a position: the
+// compares are false and v_min keeps h0; v_med3 with a NaN operand returns the minimum of the other two, so h1 (h2) may
+// then repeat h0 (h1) -- a runner-up value that is too small only sends a candidate more to the f64 ranking and makes the
+// bound left to the certificates smaller (tests/test_core_hostile.py).
 #ifndef VISMA_GRID_NTOP
 #define VISMA_GRID_NTOP 2
 #endif
@@ -611,7 +623,8 @@ __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
         const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
         // (d2, original index) packed so that ONE 64-bit unsigned compare is the
         // lexicographic test; d2 >= 0, so its IEEE bits are order preserving.  The
-        // start key (r2f, 0) makes the acceptance strict: d2 < r2f.
+        // start key (r2f, 0) makes the acceptance strict: d2 < r2f.  (A NaN d2, of either
+        // sign, has bits above +inf's: never below a key.)
         unsigned long long bkey = (unsigned long long)__float_as_uint(r2f) << 32;
         unsigned bpos = 0xFFFFFFFFu;
         double bd = r2d;                                   // F64: best d2 so far (strictly below r2d once set)
@@ -645,7 +658,7 @@ __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
         const float mgn = HYB ? 1e-3f + 4.0f * hyb_E * g.inv_hs : 1e-3f;    // HYB: plus the rounding band
         const float lo_y = fmaxf(fy - mgn, 0.f), hi_y = fmaxf(1.0f - fy - mgn, 0.f);
         const float lo_z = fmaxf(fz - mgn, 0.f), hi_z = fmaxf(1.0f - fz - mgn, 0.f);
-        const float h2 = g.hs * g.hs * (1.0f - 1e-5f);
+        const float h2 = slab_h2(g.hs);
         // squared lower bound of row offset (dy, dz), compile-time offsets
         auto row_bound_of = [&](int dy, int dz) {
             const float ey = dy == 0 ? 0.f : (dy < 0 ? lo_y + (float)(-dy - 1) : hi_y + (float)(dy - 1));

@@ -99,7 +99,9 @@ constexpr float kCoopRoom = VISMA_COOP_ROOM;  // listing margin beyond the previ
 
 // minimum over the 8 lanes of an aligned lane octet: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror.
 // (v_min_f32_dpp reads its first source through the permutation; a VALU result needs two wait states
-// before a DPP read, which the compiler does not insert inside an asm block.)  d is never NaN.
+// before a DPP read, which the compiler does not insert inside an asm block.)  A NaN d (a candidate that is not finite) is
+// skipped: v_min_f32 returns its other operand; an octet of nothing but NaN gives NaN, which no comparison after it
+// accepts (tests/test_core_hostile.py).
 __device__ __forceinline__ float octet_min(float d)
 {
     float r;
@@ -362,7 +364,7 @@ __device__ __forceinline__ bool coop_body(
         const float lo_x = fmaxf(fx - mgn, 0.f), hi_x = fmaxf(1.0f - fx - mgn, 0.f);
         const float lo_y = fmaxf(fy - mgn, 0.f), hi_y = fmaxf(1.0f - fy - mgn, 0.f);
         const float lo_z = fmaxf(fz - mgn, 0.f), hi_z = fmaxf(1.0f - fz - mgn, 0.f);
-        const float h2 = g.hs * g.hs * (1.0f - 1e-5f);
+        const float h2 = slab_h2(g.hs);
         // LB, geometric part: what everything outside the 27 cells is at least away (squared): one cell plus the
         // nearest face of the own cell; a query far outside the grid's bounding box (clamped cell coordinate): its
         // distance to the box, in cells (same fp32 binning, same margin).  The cells NOT listed: pruned2 below.

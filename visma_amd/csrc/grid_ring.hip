@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kBlock) VISMA_RING_OCCUPANCY void nn_ring_kernel(
     const long long i_end = i_begin + per_group < (long long)ns ? i_begin + per_group : (long long)ns;
 
     const int K = g.ring;
-    const float h2 = g.h * g.h * (1.0f - 1e-5f);
+    const float h2 = slab_h2(g.h);
     const float inv_h2 = 1.0f / h2;
     const float mgn = 1e-3f;                               // fp32 binning of query and candidates (kGridMaxDim)
     const float reach = (float)(K + 1);                    // cells: farther outside the table than this = no partner

@@ -65,7 +65,9 @@ constexpr int kCoopDepth = VISMA_WAVE_DEPTH;  // chunks per lane octet in flight
 
 // minimum over the 8 lanes of an aligned lane octet: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror.
 // (v_min_f32_dpp reads its first source through the permutation; a VALU result needs two wait states
-// before a DPP read, which the compiler does not insert inside an asm block.)  d is never NaN.
+// before a DPP read, which the compiler does not insert inside an asm block.)  A NaN d (a candidate that is not finite) is
+// skipped: v_min_f32 returns its other operand; an octet of nothing but NaN gives NaN, which no comparison after it
+// accepts (tests/test_core_hostile.py).
 __device__ __forceinline__ float octet_min(float d)
 {
     float r;
@@ -254,7 +256,7 @@ __device__ __forceinline__ bool wave_body(
         const float lo_x = fmaxf(fx - mgn, 0.f), hi_x = fmaxf(1.0f - fx - mgn, 0.f);
         const float lo_y = fmaxf(fy - mgn, 0.f), hi_y = fmaxf(1.0f - fy - mgn, 0.f);
         const float lo_z = fmaxf(fz - mgn, 0.f), hi_z = fmaxf(1.0f - fz - mgn, 0.f);
-        const float h2 = g.hs * g.hs * (1.0f - 1e-5f);
+        const float h2 = slab_h2(g.hs);
         float exq[3];
 #pragma unroll
         for (int j = 0; j < 3; j++) {

@@ -1,6 +1,8 @@
 // hip_engine_clouds.cpp -- HipEngine: uploads and layout of the clouds, the radius-cell grid, the growth of the device buffers, timing read-back.
 #include "hip_engine.hpp"
 
+#include <cfloat>
+
 namespace visma {
 namespace drv {
 
@@ -159,6 +161,9 @@ int HipEngine::set_target_f64(const double *xyz, int64_t nt, int stride, double 
                     for (int64_t j = a; j < b; j++) {
                         const double *q = xyz + (size_t)j * stride;
                         for (int k = 0; k < 3; k++) {
+                            // (a NaN is skipped, an infinite coordinate is kept: the box is then not finite and is not
+                            //  used -- host_box_valid_ below --, the device forms the box of the finite coordinates:
+                            //  no second test in the loop every upload pays for)
                             if (q[k] < lo3[k]) lo3[k] = q[k];
                             if (q[k] > hi3[k]) hi3[k] = q[k];
                         }
@@ -591,6 +596,14 @@ int HipEngine::build_grid(double max_dist)
         std::memcpy(mn, host_mn_, sizeof(mn));
         std::memcpy(mx, host_mx_, sizeof(mx));
     }
+    // cell_coord forms v - mn in fp32.  Inside a box no wider than half the fp32 range that difference cannot overflow for
+    // a point of the box, and a query for which it does lies 1.7e38 outside, farther than any radius whose square fp32
+    // holds.  A wider box of finite coordinates is refused, not binned wrongly.
+    for (int a = 0; a < 3; a++)
+        if ((double)mx[a] - (double)mn[a] > 0.5 * (double)FLT_MAX) {
+            err_ = "the target's bounding box is wider than half the fp32 range: the grid search cannot bin it (VISMA_ICP_NN_BRUTE can search it)";
+            return VISMA_ICP_ERR_INVALID;
+        }
     grid_ = grid_plan(mn, mx, max_dist, kGridMaxCells, grid_sub_);
     grid_occupancy_ = 0.0;
     // cells, counts, scan, scatter (+ the f64 and the packed copies) for the plan in grid_

@@ -376,7 +376,8 @@ __global__ __launch_bounds__(kBlock) void reduce_exact_kernel(
 // The pending queries of reduce_exact_kernel against the whole target, all of them in one sweep: every
 // thread takes targets j, j + stride, ... and tests each against every pending query (fp32 filter, then
 // the reference's f64 distance).  PASS 0: the smallest f64 d2 per query (atomic minimum of its bits --
-// order preserving for d2 >= 0; the start value is the radius bound, so the acceptance stays strict).
+// order preserving for d2 >= 0; the start value is the radius bound, so the acceptance stays strict; a point that is not
+// finite fails the fp32 filter before it -- NaN <= L is false -- and never reaches the minimum).
 // PASS 1: the lowest index among the targets AT that distance.
 template <int PASS>
 __global__ __launch_bounds__(256) void brute_rescan_kernel(const float4 *__restrict__ tgt, const Pt64 *__restrict__ tgt64,

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(NTH, 3) void nn_tile_reduce_kernel(const TileArgs a
     const float mgn = 1e-3f + 4.0f * E * g.inv_hs;
     const float lo_y = fmaxf(fy - mgn, 0.f), hi_y = fmaxf(1.0f - fy - mgn, 0.f);
     const float lo_z = fmaxf(fz - mgn, 0.f), hi_z = fmaxf(1.0f - fz - mgn, 0.f);
-    const float h2 = g.hs * g.hs * (1.0f - 1e-5f);
+    const float h2 = slab_h2(g.hs);
 
     // results of the query (valid on every lane of its group after the search)
     float b1 = lim, b2 = lim;
