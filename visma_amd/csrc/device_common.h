@@ -69,20 +69,39 @@ __device__ __forceinline__ float sqdist_f32(const float4 q, float px, float py, 
 // p32 = fl(p64) and q32 = fl(q64) the difference vector is off by at most u (|p| + |q|) per
 // component (u = 2^-24) and the fp32 evaluation of d2 adds 3u relative, so
 // |d64 - sqrt(d2_32)| <= u (2 |p| + 2.5 r); the band half-width E is more than twice that.
+// (an fp32 length rounded UP by more than an ulp: the radius, a distance narrowed from f64)
+__device__ __forceinline__ float band_round_up(float v) { return v * (1.0f + 2.4e-7f); }
+// (the half-width for a query at p and the radius r_up, rounded up: what callers that keep r_up themselves use)
+__device__ __forceinline__ float exact_band_at(float px, float py, float pz, float r_up)
+{
+    return 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + r_up) + 4.8e-7f * r_up;
+}
 __device__ __forceinline__ float exact_band(float px, float py, float pz, float r2f, float *r_up_out = nullptr)
 {
-    const float r_up = sqrtf(r2f) * (1.0f + 2.4e-7f);
+    const float r_up = band_round_up(sqrtf(r2f));
     if (r_up_out) *r_up_out = r_up;
-    return 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + r_up) + 4.8e-7f * r_up;
+    return exact_band_at(px, py, pz, r_up);
+}
+// the band of the fp32 length s, squared: squared fp32 distances at or beyond it lie outside (s + 2E in f64 terms)
+__device__ __forceinline__ float exact_band_square(float s, float E)
+{
+    const float t = s + 2.0f * E;
+    return t * t * (1.0f + 6e-7f);
 }
 // squared fp32 distance at or beyond which a candidate cannot be accepted in f64
 __device__ __forceinline__ float exact_band_limit(float px, float py, float pz, float r2f)
 {
     float r_up;
     const float E = exact_band(px, py, pz, r2f, &r_up);
-    const float t = r_up + 2.0f * E;
-    return t * t * (1.0f + 6e-7f);
+    return exact_band_square(r_up, E);
 }
+// ... and beyond which nothing can win or tie in f64 against a candidate at the squared fp32 distance g (inside the radius)
+__device__ __forceinline__ float exact_band_limit_from(float E, float r_up, float g)
+{
+    return exact_band_square(fminf(sqrtf(g), r_up), E);
+}
+
+struct P12 { float x, y, z; };                // fp32 rounding of a cell-sorted f64 target point (launch_pack12)
 
 // one VALU op: min of three (v_min3_f32); inputs are never NaN-producing here
 __device__ __forceinline__ float min3_f32(float a, float b, float c)

@@ -482,8 +482,6 @@ struct TopN {
 };
 typedef TopN<VISMA_GRID_NTOP> TopK;
 
-struct P12 { float x, y, z; };            // a candidate of the exact search: fp32 rounding of the f64 coordinates
-
 template <bool PLANE, int G, int U, bool ONE, bool F64 = false, bool HYB = false>
 __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
     const float4 *__restrict__ src, int ns, const float4 *__restrict__ sorted,
@@ -635,11 +633,9 @@ __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
         float hyb_E = 0.f, hyb_rup = 0.f;
         TopK top;
         if constexpr (HYB) {
-            const float r_f = sqrtf(r2f);
-            hyb_rup = r_f * (1.0f + 2.4e-7f);
-            hyb_E = 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + hyb_rup) + 4.8e-7f * hyb_rup;
-            const float t = hyb_rup + 2.0f * hyb_E;
-            top.init(t * t * (1.0f + 6e-7f));              // candidates at or beyond it never matter
+            hyb_rup = band_round_up(sqrtf(r2f));
+            hyb_E = exact_band_at(px, py, pz, hyb_rup);
+            top.init(exact_band_square(hyb_rup, hyb_E));   // candidates at or beyond it never matter
         }
         // what a row bound is compared with: the best squared distance so far, as fp32
         auto best_f32 = [&]() {
@@ -893,8 +889,7 @@ __global__ __launch_bounds__(kBlock) void nn_grid_reduce_kernel(
                 } else {
                     // more candidates inside one band than positions kept: every candidate of the 27 cells
                     // that the fp32 filter cannot exclude, in f64
-                    const float sl = fminf(sqrtf(top.h[0]), hyb_rup) + 2.0f * hyb_E;
-                    const float L = sl * sl * (1.0f + 6e-7f);
+                    const float L = exact_band_limit_from(hyb_E, hyb_rup, top.h[0]);
 #pragma unroll 1
                     for (int k = 0; k < 9; k++) {
                         unsigned rb, re;

@@ -40,26 +40,17 @@
 //    few iterations almost every query certifies and the pass streams.  LB <- t; anything else runs the search
 //    below and renews LB.  Near-ties (more than one flagged candidate, a re-scan) leave LB = 0: never certified.
 //
-// Exactness without per-candidate top-2 bookkeeping: the eight lanes of a chunk reduce
-// their fp32 d2 to the chunk minimum m (three DPP steps) and flag every candidate with d2 <= m + W, W an
-// upper bound of band(m) - m for any m inside the radius (band(m) = (sqrt(m) + 2E)^2, E the rounding
-// half-width of exact_band()).  The query keeps its two best CHUNKS (m, first slot, flag byte) and the
-// third chunk minimum.  Any candidate within the rounding band of the global fp32 minimum g lies in a
-// chunk with m <= g + W and is flagged there (d2 <= band(g) <= band(m) <= m + W), so ranking the flagged
-// candidates of the kept chunks with m <= g + W in f64 (reference arithmetic, lowest original index on
-// exact ties, strict d2 < (double)(float)r2) returns the reference's correspondence; a third chunk inside
-// g + W, or more than four flagged candidates, sends the query to the f64 re-scan of its 27 cells (points
-// given several times).
+// The exactness argument of the chunk bookkeeping, and every piece this kernel shares with grid_wave.hip (problem
+// resolver, rounding band, row listing, best chunks, f64 ranking, whole-wave re-scan): warm_search.h.
 #include <cstdlib>
 
-#include "device_common.h"
+#include "warm_search.h"
 #include "grid_coop_probe.h"   // COOP_MARK: no-ops outside the measurement builds
 
 namespace visma {
 
 namespace {
 
-struct P12 { float x, y, z; };                // fp32 rounding of a cell-sorted f64 target point
 #ifndef VISMA_COOP_RU
 #define VISMA_COOP_RU 0
 #endif
@@ -97,24 +88,6 @@ constexpr int kCoopDepth = VISMA_COOP_DEPTH;  // chunks per lane octet in flight
 #endif
 constexpr float kCoopRoom = VISMA_COOP_ROOM;  // listing margin beyond the previous winner's distance, in search radii
 
-// minimum over the 8 lanes of an aligned lane octet: quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror.
-// (v_min_f32_dpp reads its first source through the permutation; a VALU result needs two wait states
-// before a DPP read, which the compiler does not insert inside an asm block.)  A NaN d (a candidate that is not finite) is
-// skipped: v_min_f32 returns its other operand; an octet of nothing but NaN gives NaN, which no comparison after it
-// accepts (tests/test_core_hostile.py).
-__device__ __forceinline__ float octet_min(float d)
-{
-    float r;
-    asm volatile("s_nop 1\n\t"
-                 "v_min_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                 "s_nop 1\n\t"
-                 "v_min_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf"
-                 : "=&v"(r)
-                 : "v"(d));
-    return r;
-}
 
 // the side word of a chunk result (s_sec): both values are lower bounds after the truncation (d2 >= 0: sign bit clear)
 // (without the runner-up code the word is sec itself, unrounded)
@@ -126,18 +99,6 @@ __device__ __forceinline__ unsigned pack_sec(float sec, float third, unsigned la
 __device__ __forceinline__ float sec_of(unsigned w) { return __uint_as_float(kCoopRu ? (w & 0xFFFF0000u) : w); }
 [[maybe_unused]] __device__ __forceinline__ float third_of(unsigned w) { return __uint_as_float(((w >> 3) & 0x1FFFu) << 18); }
 
-// inclusive prefix sum over the 64 lanes: DPP row shifts inside the 16-lane rows (absent lanes read 0), then the
-// last lane of row 0 / 2 broadcast into row 1 / 3 and lane 31 into the upper half -- no LDS round trips
-__device__ __forceinline__ unsigned wave_scan_incl(unsigned v, int)
-{
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
 
 }  // namespace
 
@@ -189,45 +150,23 @@ __device__ __forceinline__ bool coop_body(
 {
     constexpr int NACC = Acc<PLANE>::N;
     const P12 *s12 = reinterpret_cast<const P12 *>(s12f);
-    int prob, lb;
-    long long row0;
-    if (descs) {
-        // batch of problems with their own clouds (largest p with first_block <= blockIdx.x; wave-uniform)
-        if (warm & kWarmMap) {
-            // (the launcher put a workgroup -> problem map behind the descriptors)
-            prob = reinterpret_cast<const int *>(descs + nprob)[blockIdx.x];
-        } else {
-            int lo = 0, hi = nprob - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (descs[mid].first_block <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-            }
-            prob = lo;
-        }
-        const ProbDesc d = descs[prob];
-        lb = (int)blockIdx.x - d.first_block;
-        bpp = d.nblocks;
+    const WarmProblem pb = resolve_problem(descs, nprob, warm, ns, bpp, g, out_stride, [&](const ProbDesc &d) {
         src64 += d.src_off;
-        ns = d.ns;
         s12 += d.sorted_off;
         sorted64 += d.sorted_off;
         if constexpr (PLANE) {
             if (nrm) nrm += d.sorted_off;
             if (nrm64) nrm64 += d.sorted_off;
         }
-        row0 = d.first_block;
         start += d.start_off;
-        g = d.g;
-        out_stride = 0;
         idx_out += d.out_off;
         d2_out += d.out_off;
         wst_io += d.out_off;
         if (ru_io) ru_io += d.out_off;
-    } else {
-        prob = blockIdx.x / bpp;
-        lb = blockIdx.x - prob * bpp;
-        row0 = (long long)prob * bpp;
-    }
+    });
+    const int prob = pb.prob, lb = pb.lb;
+    const long long row0 = pb.row0;
+    ns = pb.ns; bpp = pb.bpp; g = pb.g;
     if (st) st += prob;
     {
         Xform32 T32_unused;
@@ -245,10 +184,10 @@ __device__ __forceinline__ bool coop_body(
     }
     const double r2d = (double)r2f;                         // (double)(float)(r*r): KDTreeFlann.cpp:184-185
     COOP_PROBE_BEGIN();
-    idx_out += (long long)prob * out_stride;
-    d2_out += (long long)prob * out_stride;
-    wst_io += (long long)prob * out_stride;
-    if (ru_io) ru_io += (long long)prob * out_stride;
+    idx_out += (long long)prob * pb.out_stride;
+    d2_out += (long long)prob * pb.out_stride;
+    wst_io += (long long)prob * pb.out_stride;
+    if (ru_io) ru_io += (long long)prob * pb.out_stride;
     double acc[NACC];
 #pragma unroll
     for (int a = 0; a < NACC; a++) acc[a] = 0.0;
@@ -333,102 +272,6 @@ __device__ __forceinline__ bool coop_body(
             else { const float4 n4 = nrm[bidx]; nx = n4.x; ny = n4.y; nz = n4.z; }
         }
         accumulate_pq_d<PLANE>(acc, pxd, pyd, pzd, qx, qy, qz, nx, ny, nz, off);
-    };
-    // ---- The slot ranges of the query at (px, py, pz) that can hold a candidate at or within the squared fp32 distance
-    // bound0: xb[k] .. xe[k] of row k = (dy, dz) of the 3 x 3 x 3 cells around it, and lbgeo2, a lower bound (squared) of
-    // the distance to every target point that lies in NONE of those ranges.  `want`: this lane looks its rows up at all.
-    auto list_rows = [&](const float px, const float py, const float pz, const float E, const float bound0, const bool want,
-                         unsigned (&xb)[9], unsigned (&xe)[9], float &lbgeo2, unsigned &looked) {
-        const int cx = cell_coord(px, g.mn[0], g.inv_h, g.dim[0]);
-        const int cy = cell_coord(py, g.mn[1], g.inv_hs, g.dim[1]);
-        const int cz = cell_coord(pz, g.mn[2], g.inv_hs, g.dim[2]);
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dim[0] - 1);
-        const int span = x1 + 1 - x0;                        // cells of a row that exist: <= 0, 1, 2 or 3
-        // ---- starts of the cells x0 .. x0+3 of a row: one 16-byte load (absent row / lane: zeros = empty)
-        typedef unsigned u4a __attribute__((ext_vector_type(4), aligned(4)));
-        // (cell indices fit 32 bits: kGridMaxCells; which of the three y / z rows exist is tested once per axis)
-        const bool yok[3] = {cy - 1 >= 0 && cy - 1 < g.dim[1], cy >= 0 && cy < g.dim[1], cy + 1 >= 0 && cy + 1 < g.dim[1]};
-        const bool zok[3] = {cz - 1 >= 0 && cz - 1 < g.dim[2], cz >= 0 && cz < g.dim[2], cz + 1 >= 0 && cz + 1 < g.dim[2]};
-        const int row_c = (cz * g.dim[1] + cy) * g.dim[0] + x0, pitch_y = g.dim[0], pitch_z = g.dim[1] * g.dim[0];
-        auto load_row = [&](int k, bool wanted) {
-            const bool ok = wanted && span > 0 && zok[k / 3] && yok[k % 3];
-            u4a v = {0u, 0u, 0u, 0u};
-            if (ok) v = *reinterpret_cast<const u4a *>(reinterpret_cast<const char *>(start) + (unsigned)(row_c + (k / 3 - 1) * pitch_z + (k % 3 - 1) * pitch_y) * 4u);
-            return v;
-        };
-        // slab distances (in cells) of the neighbouring rows / cells, margins as in nn_grid_reduce_kernel
-        const float fx = (px - g.mn[0]) * g.inv_h - (float)cx;
-        const float fy = (py - g.mn[1]) * g.inv_hs - (float)cy;
-        const float fz = (pz - g.mn[2]) * g.inv_hs - (float)cz;
-        const float mgn = 1e-3f + 4.0f * E * g.inv_hs;
-        const float lo_x = fmaxf(fx - mgn, 0.f), hi_x = fmaxf(1.0f - fx - mgn, 0.f);
-        const float lo_y = fmaxf(fy - mgn, 0.f), hi_y = fmaxf(1.0f - fy - mgn, 0.f);
-        const float lo_z = fmaxf(fz - mgn, 0.f), hi_z = fmaxf(1.0f - fz - mgn, 0.f);
-        const float h2 = slab_h2(g.hs);
-        // LB, geometric part: what everything outside the 27 cells is at least away (squared): one cell plus the
-        // nearest face of the own cell; a query far outside the grid's bounding box (clamped cell coordinate): its
-        // distance to the box, in cells (same fp32 binning, same margin).  The cells NOT listed: pruned2 below.
-        float out2;
-        {
-            const float face = fminf(fminf(fminf(lo_x, hi_x), fminf(lo_y, hi_y)), fminf(lo_z, hi_z));
-            const float ux = fx + (float)cx, uy = fy + (float)cy, uz = fz + (float)cz;
-            const float far = fmaxf(fmaxf(fmaxf(-ux, ux - (float)g.dim[0]), fmaxf(-uy, uy - (float)g.dim[1])),
-                                    fmaxf(-uz, uz - (float)g.dim[2])) - 2.0f * mgn;
-            const float outc = fmaxf(1.0f + face, far);
-            out2 = outc * outc * h2;
-        }
-        float exq[3];                                        // (a cell past the span: +inf -- never listed, bounds nothing)
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            const int xi = x0 + j;
-            const float ex = xi == cx ? 0.f : (xi < cx ? lo_x + (float)(cx - xi - 1) : hi_x + (float)(xi - cx - 1));
-            exq[j] = j < span ? ex * ex * h2 : INFINITY;
-        }
-        const float ey2[3] = {lo_y * lo_y, 0.f, hi_y * hi_y}, ez2[3] = {lo_z * lo_z, 0.f, hi_z * hi_z};
-        float rowB[9];                                       // squared slab bound of row k = (dy, dz); a row that does not exist: +inf
-#pragma unroll
-        for (int k = 0; k < 9; k++) rowB[k] = (zok[k / 3] && yok[k % 3]) ? (ey2[k % 3] + ez2[k / 3]) * h2 : INFINITY;
-        // ---- only the rows whose slab can hold a point at or within bound0 are looked up at all (a converged
-        // pass needs 1.9 of the 9 per query), all of them in ONE round of gathers: nothing depends on a load
-        // from here to the candidates
-        u4a cs[9];
-        looked = 0u;
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const bool w = want && !(rowB[k] > bound0);
-            cs[k] = load_row(k, w);
-            looked += (w && span > 0) ? 1u : 0u;             // (profiling)
-        }
-        // ---- the slots of each row that can hold a candidate at or within bound0: cells whose slab bound
-        // (y, z and x slab distances, squared) does not exceed it.  A skipped cell holds nothing that could
-        // win or tie (margins: fp32 binning + rounding band, as in the lane-serial kernel).
-        // (B + exq[j] <= bound0 tested as B <= bound0 - exq[j]: the slab bounds carry a relative margin of ~1e-3, a
-        //  rounding of the subtraction cannot drop a cell that matters; a cell that does not exist: -inf)
-        const float lim0 = bound0 - exq[0];                  // (-inf for a cell past the span)
-        const float lim1 = bound0 - exq[1];
-        const float lim2 = bound0 - exq[2];
-        float pruned2 = INFINITY;                            // smallest slab bound (squared) among the cells NOT listed
-        const float thr0 = bound0 * (1.0f - 1e-6f);
-#pragma unroll
-        for (int k = 0; k < 9; k++) {
-            const float B = rowB[k];
-            const bool n0 = B <= lim0, n1 = B <= lim1, n2 = B <= lim2;
-            // (a cell is NOT listed iff B > fl(bound0 - exq[j]), which implies fl(B + exq[j]) > bound0 (1 - 2e-7): every
-            //  such cell is in this minimum; a listed cell within 1e-6 of bound0 may be too -- its slab bound holds as well.
-            //  Own comparisons, so that the 27 listing masks need not stay live)
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                const float S = B + exq[j];
-                pruned2 = fminf(pruned2, S >= thr0 ? S : INFINITY);
-            }
-            const u4a v = cs[k];                             // (a row not looked up reads as zeros: empty)
-            const unsigned b = n0 ? v.x : (n1 ? v.y : v.z);
-            unsigned e = n2 ? v.w : (n1 ? v.z : (n0 ? v.y : b));
-            if (!(n0 || n1 || n2)) e = b;
-            xb[k] = b;
-            xe[k] = e;
-        }
-        lbgeo2 = fminf(out2, pruned2);
     };
     // ---- One ROUND = one query per lane of the workgroup.
     //  A  every lane, its own ("home") query: source point + state in, the certificate; a certified query writes its
@@ -523,9 +366,7 @@ __device__ __forceinline__ bool coop_body(
         bool cert = false;
         if (warm & kWarmTprev) {
             const float hx = (float)hp[0], hy = (float)hp[1], hz = (float)hp[2];
-            const float rup = sqrtf(r2f) * (1.0f + 2.4e-7f);
-            const float E = 2.4e-7f * (fabsf(hx) + fabsf(hy) + fabsf(hz) + rup) + 4.8e-7f * rup;
-            const float tlim = rup + 2.0f * E;
+            const float tlim = warm_band(hx, hy, hz, r2f).tlim;
             // delta = |T s - T_prev s|: same products, same order as the transform itself, so the two computed
             // points are the ones the bounds speak about; rounded up
             double pp[3];
@@ -668,19 +509,13 @@ __device__ __forceinline__ bool coop_body(
                 const float dprev = sact ? s_dprev[home] : __uint_as_float(~0u);
                 const float px = (float)pxd, py = (float)pyd, pz = (float)pzd;
                 COOP_MARK(0);                                // the query taken over from its home lane
-                // rounding band (exact_band): E bounds |d64 - sqrt(d2_32)|; L = squared fp32 distance at or beyond
-                // which a candidate cannot be accepted in f64; W >= band(m) - m for every m < L
-                const float rup = sqrtf(r2f) * (1.0f + 2.4e-7f);
-                const float E = 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + rup) + 4.8e-7f * rup;
-                const float tlim = rup + 2.0f * E;
-                const float L = tlim * tlim * (1.0f + 6e-7f);
-                const float W = (4.0f * E * tlim + 4.0f * E * E) * (1.0f + 1e-6f) + L * 5e-7f;
-                s_qp[tid] = make_float4(px, py, pz, W);
+                const WarmBand band = warm_band(px, py, pz, r2f);
+                s_qp[tid] = make_float4(px, py, pz, band.W);
                 // what nothing nearer than can be missed by: the previous winner's distance now, or the radius
-                float bound0 = L;
-                if (dprev < L) bound0 = dprev;               // (NaN = no previous winner: the radius)
+                float bound0 = band.L;
+                if (dprev < band.L) bound0 = dprev;          // (NaN = no previous winner: the radius)
                 unsigned looked;
-                list_rows(px, py, pz, E, bound0, sact, xb, xe, lbgeo2, looked);
+                list_rows(start, g, px, py, pz, band.E, bound0, sact, xb, xe, lbgeo2, looked);
                 // (pin the value here: left to itself the compiler sinks the whole slab arithmetic down to the bound's
                 //  only use at the end of the query and spills its 40 inputs across the chunk phase instead)
                 asm volatile("" : "+v"(lbgeo2));
@@ -722,21 +557,10 @@ __device__ __forceinline__ bool coop_body(
                 m_all += c;
             }
             if (work_out) *work_out = nq_all | (m_all << 12);    // (measurement: queued queries, chunks listed)
-            // the two best chunks (minimum, first slot, flag byte) and the third chunk minimum
-            float gh0 = INFINITY, gh1 = INFINITY, gh2 = INFINITY;
+            // the two best chunks (minimum, first slot, flag byte) and the third chunk minimum; the side word of the best
+            // chunk (sec = third = +inf)
+            ChunkBest cb(INFINITY, 0x7F800000u | (0x1FE0u << 3));
             float gsec = INFINITY;                           // best candidate outside the rounding band of its chunk's minimum
-            unsigned gb0 = 0xFFFFFFFFu, gb1 = 0xFFFFFFFFu, gm0 = 0u, gm1 = 0u;
-            unsigned gs0 = 0x7F800000u | (0x1FE0u << 3);     // the side word of the best chunk (sec = third = +inf)
-            auto chunk_insert = [&](float m, unsigned b, unsigned flags, unsigned side) {
-                const bool c1 = m < gh0, c2 = m < gh1;
-                gh2 = __builtin_amdgcn_fmed3f(gh1, gh2, m);
-                gh1 = __builtin_amdgcn_fmed3f(gh0, gh1, m);
-                gh0 = fminf(gh0, m);
-                gb1 = c2 ? b : gb1; gm1 = c2 ? flags : gm1;
-                gb1 = c1 ? gb0 : gb1; gm1 = c1 ? gm0 : gm1;
-                gb0 = c1 ? b : gb0; gm0 = c1 ? flags : gm0;
-                if constexpr (kCoopRu) gs0 = c1 ? side : gs0;
-            };
             // -- B2: the list, one window at a time (one window unless the cloud is very dense).  A query's chunks take
             // CONSECUTIVE entries, row after row: the owner reads its results back as one short run.
             for (unsigned w0 = 0; w0 < m_all; w0 += kCapAll) {
@@ -826,7 +650,9 @@ __device__ __forceinline__ bool coop_body(
                         }
 #pragma unroll
                         for (int u = 0; u < 4; u++) {
-                            chunk_insert(in[u] ? __uint_as_float(r[u].y & 0xFFFFFF00u) : INFINITY, r[u].x, r[u].y & 0xFFu, rs[u]);
+                            const float m = in[u] ? __uint_as_float(r[u].y & 0xFFFFFF00u) : INFINITY;
+                            if constexpr (kCoopRu) chunk_insert(cb, m, r[u].x, r[u].y & 0xFFu, rs[u]);
+                            else chunk_insert(cb, m, r[u].x, r[u].y & 0xFFu);
                             gsec = fminf(gsec, in[u] ? sec_of(rs[u]) : INFINITY);
                         }
                     }
@@ -844,52 +670,25 @@ __device__ __forceinline__ bool coop_body(
             if (searching) {
                 const bool need = sact, active = sact;
                 float lb_new = 0.f;                          // what this pass leaves as LB
-                double bd = r2d;                             // best d2 so far (strictly below r2d once set)
-                unsigned bidx = 0xFFFFFFFFu, bpos = 0xFFFFFFFFu;
-                Pt64 bq = Pt64{0.0, 0.0, 0.0, 0ull};
+                Best best(r2d);
                 auto tail = [&](const double pxd, const double pyd, const double pzd, const float px, const float py, const float pz,
                                 const float W) {
-                const float rup = sqrtf(r2f) * (1.0f + 2.4e-7f);
-                const float E = 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + rup) + 4.8e-7f * rup;
-                const float tlim = rup + 2.0f * E;
-                const float L = tlim * tlim * (1.0f + 6e-7f);
-                auto rank = [&](const Pt64 &c8, unsigned pos) {
-                    // flann L2 (dist.h:159-176): result += diff * diff over x, y, z
-                    const double dx = c8.x - pxd, dy = c8.y - pyd, dz = c8.z - pzd;
-                    double d = dx * dx;
-                    d += dy * dy;
-                    d += dz * dz;
-                    const unsigned id = (unsigned)c8.w;
-                    const bool lt = d < bd || (d == bd && id < bidx && bidx != 0xFFFFFFFFu);
-                    bd = lt ? d : bd;
-                    bidx = lt ? id : bidx;
-                    bpos = lt ? pos : bpos;
-                    bq.x = lt ? c8.x : bq.x; bq.y = lt ? c8.y : bq.y; bq.z = lt ? c8.z : bq.z; bq.w = lt ? c8.w : bq.w;
-                };
+                const WarmBand band = warm_band(px, py, pz, r2f);
                 bool slow = false;                                   // needs every listed candidate ranked in f64
                 // (the kept chunk minima were rounded down by < 2^-15 relative: g_up bounds the fp32 minimum from above, and
                 //  the tests below stay on the safe side -- a chunk or candidate more is ranked in f64, never one less)
-                const float g_up = gh0 * (1.0f + 6.2e-5f);
+                const float g_up = cb.h0 * (1.0f + 6.2e-5f);
                 int n = 0;                                           // candidates ranked in f64
                 // the runner-up the state will keep (kCoopRu): its slot, the squared bound of everything but it and the winner
                 unsigned rupos = 0xFFFFFFFFu;
                 float lb3_2 = 0.f;
                 // (chunk minima at or beyond L cannot be accepted in f64: such chunks only serve the LB)
-                if (need && gh0 < L) {
+                if (need && cb.h0 < band.L) {
                     const float thr = g_up + W;
                     unsigned c[4] = {0u, 0u, 0u, 0u};
-                    slow = gh2 <= thr;                               // a third chunk reaches into the band
-                    auto add = [&](unsigned b, unsigned flags) {
-                        while (flags) {
-                            const unsigned pos = b + (unsigned)__builtin_ctz(flags);
-                            flags &= flags - 1u;
-                            if (n == 0) c[0] = pos; else if (n == 1) c[1] = pos; else if (n == 2) c[2] = pos; else if (n == 3) c[3] = pos;
-                            else slow = true;
-                            n++;
-                        }
-                    };
-                    add(gb0, gm0);
-                    if (gh1 <= thr) add(gb1, gm1);
+                    slow = cb.h2 <= thr;                               // a third chunk reaches into the band
+                    add_flagged(cb.b0, cb.m0, c, n, slow);
+                    if (cb.h1 <= thr) add_flagged(cb.b1, cb.m1, c, n, slow);
                     if constexpr (kCoopRu) {
                         // One flagged candidate in all (the usual case): it is THE candidate of the best chunk.  The
                         // runner-up is the best of (A) that chunk's best candidate outside the band -- then every other
@@ -897,131 +696,39 @@ __device__ __forceinline__ bool coop_body(
                         // chunk's minimum, if that chunk flagged one candidate only -- then the rest of every chunk is at
                         // least gsec away and every other chunk gh2.  (All values rounded down: lower bounds.)
                         if (ru_io && n == 1 && !slow) {
-                            const float secA = sec_of(gs0);
-                            if (secA < INFINITY && secA <= gh1) {
-                                rupos = gb0 + (gs0 & 7u);
-                                lb3_2 = fminf(gh1, third_of(gs0));
-                            } else if (gh1 < INFINITY && __builtin_popcount(gm1) == 1) {
-                                rupos = gb1 + (unsigned)__builtin_ctz(gm1);
-                                lb3_2 = fminf(gh2, gsec);
+                            const float secA = sec_of(cb.s0);
+                            if (secA < INFINITY && secA <= cb.h1) {
+                                rupos = cb.b0 + (cb.s0 & 7u);
+                                lb3_2 = fminf(cb.h1, third_of(cb.s0));
+                            } else if (cb.h1 < INFINITY && __builtin_popcount(cb.m1) == 1) {
+                                rupos = cb.b1 + (unsigned)__builtin_ctz(cb.m1);
+                                lb3_2 = fminf(cb.h2, gsec);
                             }
                             lb3_2 = fminf(lb3_2, lbgeo2);
                         }
                     }
-                    // (a second flagged candidate: one query in a thousand; a third: duplicated points)
-                    Pt64 c8a = Pt64{0.0, 0.0, 0.0, 0ull}, c8b = c8a;
-                    if (n > 0) c8a = sorted64[c[0]];
-                    if (n > 1) c8b = sorted64[c[1]];
-                    if (n > 0) rank(c8a, c[0]);
-                    if (n > 1) rank(c8b, c[1]);
-                    if (n > 2) rank(sorted64[c[2]], c[2]);
-                    if (n > 3) rank(sorted64[c[3]], c[3]);
+                    rank_flagged(best, sorted64, c, n, pxd, pyd, pzd);
                 }
-                // ---- the re-scan, by the WHOLE WAVE for one such query at a time (a few per launch at C4, and the launch
-                // lasts as long as its slowest wave: one lane walking its 27 cells alone -- ~90 dependent loads -- put 6 us
-                // on the tail of every launch).  The query's listed slot ranges (everything that can win or tie lies in
-                // them, see the pruning above) are flattened over the lanes: one fp32 filter load, one f64 load, a
-                // butterfly over (d2, original index), the winner's coordinates handed to the owner lane.
+                // ---- the re-scan (rescan_wave).  The query's slot ranges are listed again (its lane alone looks the rows
+                // up) against Ls: nothing at or within it is left out, and nothing was kept in registers for this rare path
                 for (unsigned long long rem = __builtin_amdgcn_ballot_w64(slow); rem; rem &= rem - 1ull) {
                     const int q = (int)__builtin_ctzll(rem);         // wave-uniform
-                    auto bcast_u = [&](unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)v, q); };
-                    auto bcast_f = [&](float v) { return __uint_as_float(bcast_u(__float_as_uint(v))); };
-                    auto bcast_d = [&](double v) {
-                        const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-                        return __longlong_as_double((long long)(((unsigned long long)bcast_u((unsigned)(u >> 32)) << 32) | bcast_u((unsigned)u)));
-                    };
-                    const float qx = bcast_f(px), qy = bcast_f(py), qz = bcast_f(pz);
-                    const double qxd = bcast_d(pxd), qyd = bcast_d(pyd), qzd = bcast_d(pzd);
-                    const float qrup = rup, qE = bcast_f(E);
-                    const float sl = fminf(sqrtf(bcast_f(g_up)), qrup) + 2.0f * qE;
-                    const float Ls = sl * sl * (1.0f + 6e-7f);       // fp32 distances beyond it cannot win or tie in f64
-                    // the query's slot ranges, listed again (its lane alone looks the rows up) against Ls: nothing at or within
-                    // it is left out, and nothing was kept in registers for this rare path
+                    const WaveQuery wq = broadcast_query(q, px, py, pz, pxd, pyd, pzd, band.rup, band.E, g_up);
                     unsigned qb[9], pre[10];
-                    pre[0] = 0u;
                     {
                         unsigned sb[9], se[9], looked_unused;
                         float geo_unused;
-                        list_rows(px, py, pz, E, Ls, lane == q, sb, se, geo_unused, looked_unused);
-        #pragma unroll
-                        for (int k = 0; k < 9; k++) {
-                            qb[k] = bcast_u(sb[k]);
-                            pre[k + 1] = pre[k] + (bcast_u(se[k]) - qb[k]);
-                        }
+                        list_rows(start, g, px, py, pz, band.E, wq.Ls, lane == q, sb, se, geo_unused, looked_unused);
+                        broadcast_ranges(q, sb, se, qb, pre);
                     }
-                    double ld = r2d;
-                    unsigned lid = 0xFFFFFFFFu, lpos = 0xFFFFFFFFu;
-                    Pt64 lq = Pt64{0.0, 0.0, 0.0, 0ull};
-                    for (unsigned f0 = 0; f0 < pre[9]; f0 += 128u) {  // (one trip unless the rows are very dense)
-                        unsigned j[2];
-                        bool in[2];
-                        P12 t[2];
-        #pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            const unsigned f = f0 + (unsigned)u * 64u + (unsigned)lane;
-                            in[u] = f < pre[9];
-                            unsigned jj = 0u;
-        #pragma unroll
-                            for (int k = 0; k < 9; k++)
-                                if (f >= pre[k] && f < pre[k + 1]) jj = qb[k] + (f - pre[k]);
-                            j[u] = jj;
-                            t[u] = P12{0.f, 0.f, 0.f};
-                            if (in[u]) t[u] = s12[jj];
-                        }
-                        Pt64 c8[2];
-        #pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            in[u] = in[u] && sqdist_f32(make_float4(t[u].x, t[u].y, t[u].z, 0.f), qx, qy, qz) <= Ls;
-                            c8[u] = Pt64{0.0, 0.0, 0.0, 0ull};
-                            if (in[u]) c8[u] = sorted64[j[u]];
-                        }
-        #pragma unroll
-                        for (int u = 0; u < 2; u++)
-                            if (in[u]) {
-                                // flann L2 (dist.h:159-176), as rank() above
-                                const double dx = c8[u].x - qxd, dy = c8[u].y - qyd, dz = c8[u].z - qzd;
-                                double d = dx * dx;
-                                d += dy * dy;
-                                d += dz * dz;
-                                const unsigned id = (unsigned)c8[u].w;
-                                const bool lt = d < ld || (d == ld && id < lid && lid != 0xFFFFFFFFu);
-                                if (lt) { ld = d; lid = id; lpos = j[u]; lq = c8[u]; }
-                            }
-                    }
-                    // minimum over the lanes by (d2, original index); lanes without a candidate hold (r2d, none)
-                    double rd = ld;
-                    unsigned rid = lid;
-        #pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) {
-                        const double od = __shfl_xor(rd, o, 64);
-                        const unsigned oid = (unsigned)__shfl_xor((int)rid, o, 64);
-                        const bool lt = oid != 0xFFFFFFFFu && (od < rd || (od == rd && oid < rid));
-                        rd = lt ? od : rd;
-                        rid = lt ? oid : rid;
-                    }
-                    if (rid != 0xFFFFFFFFu) {                        // (wave-uniform)
-                        const unsigned long long holders = __builtin_amdgcn_ballot_w64(lid == rid && ld == rd);
-                        const int wl = (int)__builtin_ctzll(holders);
-                        auto from_w = [&](unsigned v) { return (unsigned)__builtin_amdgcn_readlane((int)v, wl); };
-                        auto from_w64 = [&](unsigned long long u) { return ((unsigned long long)from_w((unsigned)(u >> 32)) << 32) | from_w((unsigned)u); };
-                        Pt64 w8;
-                        w8.x = __longlong_as_double((long long)from_w64((unsigned long long)__double_as_longlong(lq.x)));
-                        w8.y = __longlong_as_double((long long)from_w64((unsigned long long)__double_as_longlong(lq.y)));
-                        w8.z = __longlong_as_double((long long)from_w64((unsigned long long)__double_as_longlong(lq.z)));
-                        w8.w = from_w64(lq.w);
-                        const unsigned wpos = from_w(lpos);
-                        if (lane == q) {
-                            const bool lt = rd < bd || (rd == bd && rid < bidx && bidx != 0xFFFFFFFFu);
-                            if (lt) { bd = rd; bidx = rid; bpos = wpos; bq = w8; }
-                        }
-                    }
+                    rescan_wave(best, q, lane, qb, pre, wq, r2d, s12, sorted64);
                 }
                 // ---- LB: what every target point but the winner (every target point, without a winner) is at least away
                 if (need) {
-                    float lb2 = fminf(lbgeo2, fminf(gh1, gsec));
-                    if (bpos == 0xFFFFFFFFu) lb2 = fminf(lb2, gh0);  // nothing accepted: the best candidate bounds like the rest
+                    float lb2 = fminf(lbgeo2, fminf(cb.h1, gsec));
+                    if (best.pos == 0xFFFFFFFFu) lb2 = fminf(lb2, cb.h0);  // nothing accepted: the best candidate bounds like the rest
                     // (examined candidates: |d64 - sqrt(d2_32)| <= E inside the radius, <= 2E out to the corners of the 27 cells)
-                    float lb = sqrtf(lb2) * (1.0f - 1e-6f) - 4.0f * E;
+                    float lb = sqrtf(lb2) * (1.0f - 1e-6f) - 4.0f * band.E;
                     // a near-tie (several candidates ranked in f64, a re-scan): the runner-up was not bounded
                     if (slow || n > 1) lb = 0.f;
                     lb_new = fminf(fmaxf(lb, 0.f), 3.0e38f);
@@ -1029,28 +736,28 @@ __device__ __forceinline__ bool coop_body(
                     // (tools/lb_probe.py, measurement build) what limits the bound a search leaves: the runner-up among the
                     // examined candidates, or the cells that were not listed?  counter 0: sum over the candidate-limited
                     // queries of (geometric bound - candidate bound) in micrometres; counter 1: their number
-                    if (cand_count && bpos != 0xFFFFFFFFu && !(slow || n > 1)) {
-                        const float cb = fminf(gh1, gsec);
-                        if (cb < lbgeo2) {
+                    if (cand_count && best.pos != 0xFFFFFFFFu && !(slow || n > 1)) {
+                        const float cand2 = fminf(cb.h1, gsec);
+                        if (cand2 < lbgeo2) {
                             unsigned long long *slot = cand_count + 2 * (blockIdx.x & 4095);
-                            atomicAdd(slot, (unsigned long long)((sqrtf(fminf(lbgeo2, 4.0f * r2f)) - sqrtf(cb)) * 1e6f));
+                            atomicAdd(slot, (unsigned long long)((sqrtf(fminf(lbgeo2, 4.0f * r2f)) - sqrtf(cand2)) * 1e6f));
                             atomicAdd(slot + 1, 1ull);
                         }
                     }
 #endif
                 }
-                const bool found = bpos != 0xFFFFFFFFu;
+                const bool found = best.pos != 0xFFFFFFFFu;
                 COOP_MARK(5);                                // f64 winner arrived and ranked
                 if (active) {
                     const long long i = (long long)(vb * NTH + (int)s_home[tid]) * per_group + it;   // its home thread's query of the round
-                    emit(i, (unsigned)s_home[tid], false, bd, bidx, found, bq.x, bq.y, bq.z, lb_new);
+                    emit(i, (unsigned)s_home[tid], false, best.d, best.idx, found, best.q.x, best.q.y, best.q.z, lb_new);
                     if constexpr (kCoopRu) {
                         // (examined candidates and slab bounds alike: the margins of LB)
                         // The runner-up's f64 point is NOT fetched here, where the kernel has no register to spare (eight more
                         // live across the re-scan loop spilled 21: ~3 us of scratch round trips per pass): slot and bound go
                         // to the home lane through the chunk list's memory, which nobody needs any more this round, and
                         // the home lane fetches the point in phase C, behind its moments.
-                        const float lb3 = sqrtf(lb3_2) * (1.0f - 1e-6f) - 4.0f * E;
+                        const float lb3 = sqrtf(lb3_2) * (1.0f - 1e-6f) - 4.0f * band.E;
                         const bool have = found && rupos != 0xFFFFFFFFu && !(slow || n > 1) && lb3 > 0.f && lb_new > 0.f;
                         if (ru_io) s_item[s_home[tid]] = make_uint2(have ? rupos : 0xFFFFFFFFu, __float_as_uint(fminf(lb3, 3.0e38f)));
                     }
@@ -1059,8 +766,8 @@ __device__ __forceinline__ bool coop_body(
                 if (active) {
                     const unsigned h = s_home[tid];
                     const double none = __longlong_as_double(-1ll);
-                    s_q64[h][0] = found ? bq.x : none; s_q64[h][1] = found ? bq.y : none; s_q64[h][2] = found ? bq.z : none;
-                    s_dprev[h] = __uint_as_float(found ? bidx : 0xFFFFFFFFu);
+                    s_q64[h][0] = found ? best.q.x : none; s_q64[h][1] = found ? best.q.y : none; s_q64[h][2] = found ? best.q.z : none;
+                    s_dprev[h] = __uint_as_float(found ? best.idx : 0xFFFFFFFFu);
                 }
                 };   // tail
                 const float4 me = s_qp[tid];
@@ -1234,20 +941,6 @@ struct CoopPersistParams {
     const Pt64 *sorted64; const Pt64 *nrm64; FoldArgs fold; Pt64 *wst_io; int warm; Xform64 Tprev; PersistArgs pa;
     Pt64 *ru_io;
 };
-
-// a (member of a) kernel argument read through the laundered kernarg pointer, word by word
-template <class T>
-__device__ __forceinline__ T ld_karg(const T __attribute__((address_space(4))) *p)
-{
-    static_assert(sizeof(T) % 4 == 0, "words");
-    constexpr int N = (int)(sizeof(T) / 4);
-    union U { T v; unsigned w[N]; __device__ U() {} } u;
-    typedef const unsigned __attribute__((address_space(4))) *WordPtr;
-    const WordPtr pw = (WordPtr)p;
-#pragma unroll
-    for (int k = 0; k < N; k++) u.w[k] = pw[k];
-    return u.v;
-}
 
 template <bool PLANE>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void nn_coop_kernel_persist(const CoopPersistParams P)

@@ -66,8 +66,6 @@ constexpr int kRingU = VISMA_RING_U;                       // 32-byte candidates
 constexpr unsigned kRingNone = 0xFFFFFFFFu;     // no winner (the largest index: loses every tie)
 constexpr unsigned kRingState = 0xFFFFFFFEu;    // the winner is the point the state holds (no slot known)
 
-struct P12 { float x, y, z; };                  // fp32 rounding of a cell-sorted f64 target point (launch_pack12)
-
 // the two best (d2, slot) a lane has seen and the value of the third: every candidate not recorded is at least h2 away
 struct Top2 {
     float h0, h1, h2;
@@ -184,14 +182,12 @@ __global__ __launch_bounds__(kBlock) VISMA_RING_OCCUPANCY void nn_ring_kernel(
 
         // fp32 ranking (the packed 12-byte copy): rounding band as in nn_grid_reduce_kernel<HYB> -- p32 = fl(p64),
         // q32 = fl(q64), E more than twice the bound of |d64 - sqrt(d2_32)| for candidates within the limit
-        const float r_f = sqrtf(r2f);
-        const float rup = r_f * (1.0f + 2.4e-7f);
-        const float E = 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + rup) + 4.8e-7f * rup;
+        const float rup = band_round_up(sqrtf(r2f));
+        const float E = exact_band_at(px, py, pz, rup);
         Top2 top;
         top.init(INFINITY);
         // candidates at or beyond the limit never matter: the radius, or the previous winner's distance
-        const float sp = fminf(rup, sqrtf((float)bd) * (1.0f + 2.4e-7f)) + 2.0f * E;
-        const float lim = sp * sp * (1.0f + 6e-7f);
+        const float lim = exact_band_square(fminf(rup, band_round_up(sqrtf((float)bd))), E);
 
         const float ux = (px - g.mn[0]) * g.inv_h, uy = (py - g.mn[1]) * g.inv_h, uz = (pz - g.mn[2]) * g.inv_h;
         // (written so that a NaN query is outside)

@@ -287,8 +287,7 @@ __global__ __launch_bounds__(kBlock) void reduce_exact_kernel(
         const float b1 = __uint_as_float((unsigned)(key >> 32));
         float r_up;
         const float E = exact_band(px, py, pz, r2f, &r_up);
-        const float sl = fminf(sqrtf(b1), r_up) + 2.0f * E;
-        const float L = sl * sl * (1.0f + 6e-7f);
+        const float L = exact_band_limit_from(E, r_up, b1);
         double bd = r2d;
         unsigned bidx = 0xFFFFFFFFu;
         auto rank = [&](unsigned j, double qx, double qy, double qz) {

@@ -251,13 +251,9 @@ __global__ __launch_bounds__(NTH, 3) void nn_tile_reduce_kernel(const TileArgs a
     // u (|p|+|q|) per component, u = 2^-24, and the fp32 evaluation of d2 adds 3u relative, so
     // |d64 - sqrt(d2_32)| <= u (2 |p| + 2.5 r).  E is more than twice that.
     const float r_f = sqrtf(r2f);
-    const float r_up = r_f * (1.0f + 2.4e-7f), r_dn = r_f * (1.0f - 2.4e-7f);
-    const float E = 2.4e-7f * (fabsf(px) + fabsf(py) + fabsf(pz) + r_up) + 4.8e-7f * r_up;
-    float lim;                                               // candidates at or beyond it never matter
-    {
-        const float t = r_up + 2.0f * E;
-        lim = t * t * (1.0f + 6e-7f);
-    }
+    const float r_up = band_round_up(r_f), r_dn = r_f * (1.0f - 2.4e-7f);   // (r_dn, rounded DOWN: not the band)
+    const float E = exact_band_at(px, py, pz, r_up);
+    const float lim = exact_band_square(r_up, E);            // candidates at or beyond it never matter
     // A row (dy,dz) is SKIPPED when its slab cannot hold a candidate that matters: every point
     // of it is at least |(dist to the slab in y, in z)| away.  Margins: 1e-3 cell (fp32 binning
     // of query and candidates, kGridMaxDim) plus the rounding band, 1e-5 relative on the square.
@@ -517,8 +513,7 @@ __global__ __launch_bounds__(NTH, 3) void nn_tile_reduce_kernel(const TileArgs a
             if (amb) {
                 // exact: every candidate inside the band, ranked by the reference's f64 sum of squares,
                 // lowest original index on exact ties, accepted iff d2 < (double)(float)(r*r)
-                const float sl = fminf(sqrtf(b1), r_up) + 2.0f * E;
-                const float L = sl * sl * (1.0f + 6e-7f);
+                const float L = exact_band_limit_from(E, r_up, b1);
                 unsigned bidx = kNone;
 #pragma unroll 1
                 for (int kk = 0; kk < 9; kk++) {
