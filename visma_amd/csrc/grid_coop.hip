@@ -43,6 +43,7 @@
 // The exactness argument of the chunk bookkeeping, and every piece this kernel shares with grid_wave.hip (problem
 // resolver, rounding band, row listing, best chunks, f64 ranking, whole-wave re-scan): warm_search.h.
 #include <cstdlib>
+#include <type_traits>
 
 #include "warm_search.h"
 #include "grid_coop_probe.h"   // COOP_MARK: no-ops outside the measurement builds
@@ -98,6 +99,19 @@ __device__ __forceinline__ unsigned pack_sec(float sec, float third, unsigned la
 }
 __device__ __forceinline__ float sec_of(unsigned w) { return __uint_as_float(kCoopRu ? (w & 0xFFFF0000u) : w); }
 [[maybe_unused]] __device__ __forceinline__ float third_of(unsigned w) { return __uint_as_float(((w >> 3) & 0x1FFFu) << 18); }
+
+
+// body(K) for K = live (a wave-uniform count, 1 .. kCoopDepth; 0: nothing), K a compile-time constant to the body
+template <int K, class Body>
+__device__ __forceinline__ void live_slots(unsigned live, Body &body)
+{
+    if constexpr (K >= kCoopDepth) {
+        if (live != 0u) body(std::integral_constant<int, kCoopDepth>{});
+    } else {
+        if (live == (unsigned)K) body(std::integral_constant<int, K>{});
+        else live_slots<K + 1>(live, body);
+    }
+}
 
 
 }  // namespace
@@ -586,51 +600,74 @@ __device__ __forceinline__ bool coop_body(
                 const unsigned mw = min(m_all - w0, kCapAll);
                 for (unsigned tb = 0; tb < mw; tb += (unsigned)(NW * 8 * kCoopDepth)) {            // (uniform trip count)
                     const unsigned t = tb + (unsigned)(wave * 8 + oct);
-                    P12 c4[kCoopDepth];
-                    unsigned meta[kCoopDepth];
+                    // The slots of this trip that hold a chunk for at least one octet of this wave: slot u begins at the
+                    // wave's first position + u * NW * 8, and the positions at or beyond mw hold nothing.  A wave-uniform
+                    // scalar, so the slots beyond it cost a scalar compare instead of a descriptor read, a load, the
+                    // distance, two octet minima, a ballot and a store (a workgroup fresh from the identity lists ~135
+                    // chunks: 3 of the 7 slots of its one trip are empty; twenty passes on it lists 26: 6 of 7).
+                    const unsigned tw = tb + (unsigned)__builtin_amdgcn_readfirstlane(wave * 8);
+                    const unsigned live = tw < mw ? min((mw - tw + (unsigned)(NW * 8 - 1)) / (unsigned)(NW * 8), (unsigned)kCoopDepth) : 0u;
+                    // One straight-line body per count (live_slots picks it): guards around the single slots made the compiler
+                    // wait for each load before it issued the next one.  The loads of a body are issued back to back.
+                    auto slots = [&](auto count) {
+                        constexpr int kLive = decltype(count)::value;
+                        P12 c4[kLive];
+                        unsigned meta[kLive], at[kLive];
 #pragma unroll
-                    for (int u = 0; u < kCoopDepth; u++) {
-                        const unsigned c = t + (unsigned)(u * NW * 8);
-                        uint2 dsc = make_uint2(0u, 0u);      // (past the window's end: a null descriptor, count 0)
-                        if (c < mw) dsc = s_item[c];
-                        meta[u] = dsc.y;
+                        for (int u = 0; u < kLive; u++) {
+                            const unsigned c = t + (unsigned)(u * NW * 8);
+                            uint2 dsc = make_uint2(0u, 0u);  // (an octet past the window's end: a null descriptor, count 0)
+                            if (c < mw) dsc = s_item[c];
+                            meta[u] = dsc.y;
+                            at[u] = dsc.x;
+                        }
                         // scalar base + 32-bit byte offset (the launcher keeps 12 * slots below 2^32; the array carries
-                        // kSortedSlack entries of slack)
-                        c4[u] = *reinterpret_cast<const P12 *>(reinterpret_cast<const char *>(s12) + (((dsc.x * 3u) << 2) + (unsigned)l8 * 12u));
-                    }
+                        // kSortedSlack entries of slack).  The candidate array lies in device memory, and the load says so: the
+                        // persistent kernel reads its pointers from the kernarg segment as generic ones, and a FLAT load
+                        // counts as an LDS operation as well -- the wait for the next slot's descriptor then waited for the
+                        // load before it, and the loads of a trip went out one memory round trip after the other.
+                        typedef const char __attribute__((address_space(1))) *GlobalBytes;
+                        typedef const float __attribute__((address_space(1))) *GlobalFloats;
 #pragma unroll
-                    for (int u = 0; u < kCoopDepth; u++) {
-                        const unsigned c = t + (unsigned)(u * NW * 8);
-                        const unsigned cnt = meta[u] >> 16;
-                        const float4 p = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_qp) + (meta[u] & 0xFFF0u));
-                        float d = sqdist_f32(make_float4(c4[u].x, c4[u].y, c4[u].z, 0.f), p.x, p.y, p.z);
-                        const bool mine = (unsigned)l8 < cnt;            // (lane 0 of the octet: the chunk exists)
-                        d = mine ? d : INFINITY;
-                        const float m = octet_min(d);
-                        // (a lane past the chunk's end holds +inf: never within m + W of a finite minimum; a null
-                        //  descriptor's result is not stored)
-                        const bool fl = d <= m + p.w;
-                        const unsigned long long bal = __builtin_amdgcn_ballot_w64(fl);
-                        const unsigned flags = (unsigned)(bal >> (oct * 8)) & 0xFFu;
-                        // the chunk's best candidate that is NOT flagged (for the LB the query leaves behind), its lane, and
-                        // the best of the rest (the runner-up's chunk: what bounds everything but winner and runner-up)
-                        const float dn = fl ? INFINITY : d;
-                        const float sec = octet_min(dn);
-                        unsigned secl = 0u;
-                        float third = INFINITY;
-                        if constexpr (kCoopRu) {
-                            const unsigned long long bs = __builtin_amdgcn_ballot_w64(dn == sec && sec < INFINITY);
-                            const unsigned b8 = (unsigned)(bs >> (oct * 8)) & 0xFFu;
-                            secl = b8 ? (unsigned)__builtin_ctz(b8) : 0u;
-                            third = octet_min((b8 != 0u && (unsigned)l8 == secl) ? INFINITY : dn);
+                        for (int u = 0; u < kLive; u++) {
+                            const GlobalFloats f = (GlobalFloats)((GlobalBytes)reinterpret_cast<const char *>(s12) + (((at[u] * 3u) << 2) + (unsigned)l8 * 12u));
+                            c4[u] = P12{f[0], f[1], f[2]};
                         }
-                        // the result takes the place of the descriptor's second word: the chunk minimum rounded DOWN to
-                        // 16 mantissa bits | the flag byte (the first word, the chunk's position, stays)
-                        if (l8 == 0 && mine) {
-                            s_item[c].y = (__float_as_uint(m) & 0xFFFFFF00u) | flags;
-                            s_sec[c] = pack_sec(sec, third, secl);
+#pragma unroll
+                        for (int u = 0; u < kLive; u++) {
+                            const unsigned c = t + (unsigned)(u * NW * 8);
+                            const unsigned cnt = meta[u] >> 16;
+                            const float4 p = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(s_qp) + (meta[u] & 0xFFF0u));
+                            float d = sqdist_f32(make_float4(c4[u].x, c4[u].y, c4[u].z, 0.f), p.x, p.y, p.z);
+                            const bool mine = (unsigned)l8 < cnt;            // (lane 0 of the octet: the chunk exists)
+                            d = mine ? d : INFINITY;
+                            const float m = octet_min(d);
+                            // (a lane past the chunk's end holds +inf: never within m + W of a finite minimum; a null
+                            //  descriptor's result is not stored)
+                            const bool fl = d <= m + p.w;
+                            const unsigned long long bal = __builtin_amdgcn_ballot_w64(fl);
+                            const unsigned flags = (unsigned)(bal >> (oct * 8)) & 0xFFu;
+                            // the chunk's best candidate that is NOT flagged (for the LB the query leaves behind), its lane, and
+                            // the best of the rest (the runner-up's chunk: what bounds everything but winner and runner-up)
+                            const float dn = fl ? INFINITY : d;
+                            const float sec = octet_min(dn);
+                            unsigned secl = 0u;
+                            float third = INFINITY;
+                            if constexpr (kCoopRu) {
+                                const unsigned long long bs = __builtin_amdgcn_ballot_w64(dn == sec && sec < INFINITY);
+                                const unsigned b8 = (unsigned)(bs >> (oct * 8)) & 0xFFu;
+                                secl = b8 ? (unsigned)__builtin_ctz(b8) : 0u;
+                                third = octet_min((b8 != 0u && (unsigned)l8 == secl) ? INFINITY : dn);
+                            }
+                            // the result takes the place of the descriptor's second word: the chunk minimum rounded DOWN to
+                            // 16 mantissa bits | the flag byte (the first word, the chunk's position, stays)
+                            if (l8 == 0 && mine) {
+                                s_item[c].y = (__float_as_uint(m) & 0xFFFFFF00u) | flags;
+                                s_sec[c] = pack_sec(sec, third, secl);
+                            }
                         }
-                    }
+                    };
+                    live_slots<1>(live, slots);
                 }
                 if (searching) COOP_MARK(3);                 // chunks worked off (this wave's share)
                 __syncthreads();
