@@ -10,6 +10,7 @@
 
 #include "Utility/Eigen.h"
 #include "Geometry/PointCloud.h"
+#include "Geometry/KDTreeFlann.h"
 #include "Geometry/Image.h"
 #include "Geometry/RGBDImage.h"
 #include "Camera/PinholeCameraIntrinsic.h"

@@ -1530,6 +1530,66 @@ VISMA_ICP_API int visma_icp_point_cloud_distance(visma_icp_ctx *ctx, const doubl
  * visma_icp_point_cloud_distance. */
 VISMA_ICP_API int visma_icp_nearest_neighbor_distance(visma_icp_ctx *ctx, const double *xyz, int64_t n,
                                                       double *dist_out);
+/* ---- KDTreeFlann: neighbour queries for ANY points against a cloud resident on the device --------------------------------
+ * (the reference's Core/Geometry/KDTreeFlann.cpp: SearchKNN :117-140, SearchRadius :142-164, SearchHybrid :166-189.)
+ * The exact search under normal estimation, the colour gradient and FPFH, handed to the caller: what an outlier filter, a
+ * correspondence rule or a descriptor of the caller's own is built on.  A tree is an object owned by the context: the cloud
+ * (n x 3 f64, n >= 1) is uploaded once and stays resident until visma_icp_kdtree_destroy or the context's end.
+ *
+ * Results, for every search: rows in the caller's query order; within a row ascending (d2, index) -- flann's result order
+ * with the index deciding exact ties; d2 = ((dx dx) + dy dy) + dz dz in f64 (flann/algorithms/dist.h:159-176), equal to the
+ * reference's to the bit.  Radius and Hybrid accept a neighbour iff d2 < (double)(float)(radius * radius), strictly
+ * (KDTreeFlann.cpp:157-158, 184-185).  A neighbour at a NaN distance is never listed: a query with a NaN coordinate gets
+ * empty lists and a point of the cloud with one is in no list; a query with an infinite coordinate is at d2 = +inf from every
+ * finite point: KNN lists the lowest indices with d2 = +inf, Radius and Hybrid list nothing.  A second identical call
+ * returns identical bytes.  Queries may lie anywhere: outside the cloud's bounding box, or far away from it.
+ *   search_knn     idx, d2: nq x knn, cnt: nq.  A list holds min(knn, n) entries; behind cnt[i] entries row i is padded
+ *                  with -1 and +inf.
+ *   search_hybrid  the same layout with max_nn for knn: the max_nn nearest of those within the radius.
+ *   search_radius  every neighbour within the radius, however many: the call counts, scans and writes the lists, which
+ *                  STAY ON THE DEVICE; offsets (nq + 1) and *total come back.  visma_icp_kdtree_get_radius_result then
+ *                  copies the *total entries out, in CSR order: query i owns [offsets[i], offsets[i + 1]).  It may be called
+ *                  until the next search_radius on the tree; before any: VISMA_ICP_ERR_STATE.  A result of more than
+ *                  VISMA_ICP_KDTREE_MAX_RADIUS_ENTRIES entries (12 bytes each on the device) is refused with
+ *                  VISMA_ICP_ERR_INVALID, *total set and nothing kept: search fewer queries a call.
+ * The grid: a tree searches a grid of cells built for the radius of the call (Radius and Hybrid share it) or sized for knn
+ * (min(knn, n)).  It is KEPT for the next call that asks for the same parameter; a different radius or knn REBUILDS it (a
+ * counting sort of the cloud, and for knn up to three more to size the cells).  A caller who alternates radii pays for a
+ * rebuild each time: group the calls, or keep one tree per parameter.  The answers do not depend on the grid.
+ * Memory: the cloud and its grid (about 100 bytes a point), the queries of a call, and the rows of at most 2^22 list entries
+ * at a time (KNN and Hybrid go through the device in slabs of queries) plus, for lists longer than 170, as much again.
+ *
+ * VISMA_ICP_ERR_INVALID, before anything reaches a device: a NULL pointer, n < 1, nq < 0, knn < 1, max_nn < 1, a radius
+ * that is not finite and > 0.  nq == 0 is not an error: nothing is written (offsets[0] = 0, *total = 0).  An error leaves
+ * the tree usable.
+ *
+ * DEVIATIONS from the reference, on purpose:
+ *   - three dimensions only: SetFeature and SetMatrixData with rows() != 3 are not provided (the 33-dimensional 1-NN of
+ *     the feature matching is visma_icp_match_features);
+ *   - the C ABI is stricter than the class: knn < 1, max_nn < 1 and a radius <= 0 are VISMA_ICP_ERR_INVALID, and a tree of
+ *     no points cannot be made.  The class returns -1 from every search of an empty tree and for knn or max_nn < 0; it
+ *     SQUARES a negative radius (the answer of its absolute value) and finds nothing below a radius of 0; with knn = 0 flann's
+ *     KNNSimpleResultSet(0) writes dist_index_[-1] (flann/util/result_set.h:124), and with max_nn = 0 flann only counts and
+ *     the class returns that count with vectors it has not filled.  The C++ shim (Core/Geometry/KDTreeFlann.h) returns what
+ *     the class returns wherever that is defined -- -1 for an empty tree and for knn or max_nn < 0, the answer of |radius|,
+ *     nothing for a radius of 0 -- and 0 with empty vectors for knn = 0 or max_nn = 0; a radius that is not finite finds
+ *     nothing there (tests/golden/kdtree.npz records the reference's answers to the degenerate calls that are safe to make);
+ *   - where distances tie exactly, the lower index comes first; flann's order among exact ties is its tree's. */
+#define VISMA_ICP_KDTREE_MAX_RADIUS_ENTRIES 268435456ll   /* 2^28 */
+typedef struct visma_icp_kdtree visma_icp_kdtree;
+VISMA_ICP_API int visma_icp_kdtree_create(visma_icp_ctx *ctx, const double *xyz, int64_t n, visma_icp_kdtree **out);
+VISMA_ICP_API int visma_icp_kdtree_destroy(visma_icp_kdtree *tree);
+/* the number of points; 0 for NULL */
+VISMA_ICP_API int64_t visma_icp_kdtree_size(const visma_icp_kdtree *tree);
+VISMA_ICP_API int visma_icp_kdtree_search_knn(visma_icp_kdtree *tree, const double *queries, int64_t nq, int knn, int32_t *idx,
+                                              double *d2, int32_t *cnt);
+VISMA_ICP_API int visma_icp_kdtree_search_hybrid(visma_icp_kdtree *tree, const double *queries, int64_t nq, double radius,
+                                                 int max_nn, int32_t *idx, double *d2, int32_t *cnt);
+VISMA_ICP_API int visma_icp_kdtree_search_radius(visma_icp_kdtree *tree, const double *queries, int64_t nq, double radius,
+                                                 int64_t *offsets, int64_t *total);
+VISMA_ICP_API int visma_icp_kdtree_get_radius_result(visma_icp_kdtree *tree, int32_t *idx, double *d2);
+/* Errors of a tree's calls are its context's: visma_icp_last_error(ctx). */
+
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

@@ -61,6 +61,7 @@
 #include <Eigen/Core>
 #include <cmath>
 #include <cstdio>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -81,6 +82,7 @@
 #include <Core/Integration/UniformTSDFVolume.h>
 #include <Core/Integration/ScalableTSDFVolume.h>
 #include <Core/ColorMap/ColorMapOptimization.h>
+#include <Core/Geometry/KDTreeFlann.h>
 #endif
 
 #include "visma_icp.h"
@@ -1949,6 +1951,67 @@ inline void ColorMapOptimizationNonRigid(PointCloud &cloud, const std::vector<RG
 }
 #endif
 
+#ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
+// ---- open3d::KDTreeFlann for MANY queries in one call (visma_icp.h, "KDTreeFlann") ----
+// A KDTreeFlann::Search is a launch and a round trip per query; these take every query at once and return flat arrays.
+// KNN / Hybrid: indices and distance2 are queries.size() x knn (max_nn), row i padded with -1 and +inf behind its counts[i]
+// entries.  Returns the number of queries, or -1 as the class does (an empty tree, knn or max_nn < 0); knn or max_nn = 0,
+// and for Hybrid a radius of 0 or one that is not finite: rows of no entries.
+namespace detail {
+inline int kdtree_search_lists(const KDTreeFlann &tree, bool knn, const std::vector<Eigen::Vector3d> &queries, double radius, int cap,
+                               std::vector<int> &indices, std::vector<double> &distance2, std::vector<int> &counts)
+{
+    static_assert(sizeof(int) == sizeof(int32_t), "the index arrays are handed to the C ABI as they are");
+    if (!tree.handle() || cap < 0) return -1;
+    const size_t nq = queries.size();
+    indices.assign(nq * (size_t)cap, -1);
+    distance2.assign(nq * (size_t)cap, std::numeric_limits<double>::infinity());
+    counts.assign(nq, 0);
+    radius = std::fabs(radius);                                     // (the reference squares it)
+    if (nq == 0 || cap == 0 || (!knn && !(radius > 0.0 && std::isfinite(radius)))) return (int)nq;
+    if (knn)
+        check(tree.context(), visma_icp_kdtree_search_knn(tree.handle(), xyz(queries), (int64_t)nq, cap, indices.data(), distance2.data(), counts.data()),
+              "visma_icp_kdtree_search_knn");
+    else
+        check(tree.context(), visma_icp_kdtree_search_hybrid(tree.handle(), xyz(queries), (int64_t)nq, radius, cap, indices.data(), distance2.data(),
+                                                             counts.data()),
+              "visma_icp_kdtree_search_hybrid");
+    return (int)nq;
+}
+}  // namespace detail
+inline int KDTreeSearchKNN(const KDTreeFlann &tree, const std::vector<Eigen::Vector3d> &queries, int knn, std::vector<int> &indices,
+                           std::vector<double> &distance2, std::vector<int> &counts)
+{
+    return detail::kdtree_search_lists(tree, true, queries, 0.0, knn, indices, distance2, counts);
+}
+inline int KDTreeSearchHybrid(const KDTreeFlann &tree, const std::vector<Eigen::Vector3d> &queries, double radius, int max_nn,
+                              std::vector<int> &indices, std::vector<double> &distance2, std::vector<int> &counts)
+{
+    return detail::kdtree_search_lists(tree, false, queries, radius, max_nn, indices, distance2, counts);
+}
+// Radius: CSR -- query i owns [offsets[i], offsets[i + 1]) of indices and distance2, offsets has queries.size() + 1 entries.
+// Returns the number of queries, or -1 for an empty tree; a radius of 0 or one that is not finite: no entries.
+inline int KDTreeSearchRadius(const KDTreeFlann &tree, const std::vector<Eigen::Vector3d> &queries, double radius,
+                              std::vector<int64_t> &offsets, std::vector<int> &indices, std::vector<double> &distance2)
+{
+    if (!tree.handle()) return -1;
+    const size_t nq = queries.size();
+    offsets.assign(nq + 1, 0);
+    indices.clear();
+    distance2.clear();
+    radius = std::fabs(radius);
+    if (nq == 0 || !(radius > 0.0 && std::isfinite(radius))) return (int)nq;
+    int64_t total = 0;
+    detail::check(tree.context(), visma_icp_kdtree_search_radius(tree.handle(), detail::xyz(queries), (int64_t)nq, radius, offsets.data(), &total),
+                  "visma_icp_kdtree_search_radius");
+    indices.resize((size_t)total);
+    distance2.resize((size_t)total);
+    detail::check(tree.context(), visma_icp_kdtree_get_radius_result(tree.handle(), indices.data(), distance2.data()),
+                  "visma_icp_kdtree_get_radius_result");
+    return (int)nq;
+}
+#endif
+
 }  // namespace cicp
 
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
@@ -1968,6 +2031,74 @@ inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage
                                                                  const Eigen::Matrix4d &extrinsic)
 {
     return cicp::CreatePointCloudFromRGBDImage(image, intrinsic, extrinsic);
+}
+// open3d::KDTreeFlann (Core/Geometry/KDTreeFlann.h): the tree is an object of the context, resident on the GPU
+inline KDTreeFlann::~KDTreeFlann()
+{
+    if (tree_) (void)visma_icp_kdtree_destroy(tree_);
+}
+inline bool KDTreeFlann::SetRawData(const double *xyz, size_t n)
+{
+    if (tree_) (void)visma_icp_kdtree_destroy(tree_);
+    tree_ = nullptr;
+    dataset_size_ = 0;
+    if (n == 0) return false;                                       // (KDTreeFlann.cpp:195-198: "Failed due to no data")
+    if (!ctx_) ctx_ = cicp::detail::ThreadContext::instance().get();
+    cicp::detail::check(ctx_, visma_icp_kdtree_create(ctx_, xyz, (int64_t)n, &tree_), "visma_icp_kdtree_create");
+    dataset_size_ = n;
+    return true;
+}
+inline bool KDTreeFlann::SetMatrixData(const Eigen::MatrixXd &data)
+{
+    if (data.rows() != 3) { SetRawData(nullptr, 0); return false; }
+    std::vector<double> xyz((size_t)data.cols() * 3);               // (either storage order)
+    for (Eigen::Index j = 0; j < data.cols(); j++)
+        for (int k = 0; k < 3; k++) xyz[(size_t)j * 3 + k] = data(k, j);
+    return SetRawData(xyz.data(), (size_t)data.cols());
+}
+inline bool KDTreeFlann::SetGeometry(const PointCloud &geometry) { return SetRawData(cicp::detail::xyz(geometry.points_), geometry.points_.size()); }
+inline bool KDTreeFlann::SetGeometry(const TriangleMesh &geometry) { return SetRawData(cicp::detail::xyz(geometry.vertices_), geometry.vertices_.size()); }
+template <typename T>
+inline int KDTreeFlann::Search(const T &query, const KDTreeSearchParam &param, std::vector<int> &indices, std::vector<double> &distance2) const
+{
+    switch (param.GetSearchType()) {
+    case KDTreeSearchParam::SearchType::Knn: return SearchKNN(query, ((const KDTreeSearchParamKNN &)param).knn_, indices, distance2);
+    case KDTreeSearchParam::SearchType::Radius: return SearchRadius(query, ((const KDTreeSearchParamRadius &)param).radius_, indices, distance2);
+    case KDTreeSearchParam::SearchType::Hybrid:
+        return SearchHybrid(query, ((const KDTreeSearchParamHybrid &)param).radius_, ((const KDTreeSearchParamHybrid &)param).max_nn_, indices, distance2);
+    default: return -1;
+    }
+}
+template <typename T>
+inline int KDTreeFlann::SearchKNN(const T &query, int knn, std::vector<int> &indices, std::vector<double> &distance2) const
+{
+    if (!tree_ || query.rows() != 3 || knn < 0) return -1;          // KDTreeFlann.cpp:124-128
+    const std::vector<Eigen::Vector3d> q(1, Eigen::Vector3d(query(0), query(1), query(2)));
+    std::vector<int> count;
+    cicp::KDTreeSearchKNN(*this, q, knn, indices, distance2, count);
+    indices.resize((size_t)count[0]);
+    distance2.resize((size_t)count[0]);
+    return count[0];
+}
+template <typename T>
+inline int KDTreeFlann::SearchRadius(const T &query, double radius, std::vector<int> &indices, std::vector<double> &distance2) const
+{
+    if (!tree_ || query.rows() != 3) return -1;                     // KDTreeFlann.cpp:149-151
+    const std::vector<Eigen::Vector3d> q(1, Eigen::Vector3d(query(0), query(1), query(2)));
+    std::vector<int64_t> offsets;
+    cicp::KDTreeSearchRadius(*this, q, radius, offsets, indices, distance2);
+    return (int)offsets[1];
+}
+template <typename T>
+inline int KDTreeFlann::SearchHybrid(const T &query, double radius, int max_nn, std::vector<int> &indices, std::vector<double> &distance2) const
+{
+    if (!tree_ || query.rows() != 3 || max_nn < 0) return -1;       // KDTreeFlann.cpp:172-175
+    const std::vector<Eigen::Vector3d> q(1, Eigen::Vector3d(query(0), query(1), query(2)));
+    std::vector<int> count;
+    cicp::KDTreeSearchHybrid(*this, q, radius, max_nn, indices, distance2, count);
+    indices.resize((size_t)count[0]);
+    distance2.resize((size_t)count[0]);
+    return count[0];
 }
 // open3d::UniformTSDFVolume (Core/Integration/UniformTSDFVolume.h): the volume is an object of the context, resident on the GPU
 inline void UniformTSDFVolume::Create(visma_icp_ctx *ctx)

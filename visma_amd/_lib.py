@@ -208,6 +208,60 @@ class TsdfVolume:
         return tsdf, weight, color
 
 
+class KDTree:
+    """A cloud resident on the device for neighbour queries (visma_icp_kdtree; Context.kdtree): Open3D's KDTreeFlann for
+    batches of queries.  Every result is in the queries' order, a list ascending in (d2, index).  The grid behind a search is
+    kept for the next call with the same radius or knn; another one rebuilds it.  Lives until close() or the context's end;
+    usable as a context manager."""
+
+    def __init__(self, ctx, handle, n):
+        self.ctx, self._t, self.n = ctx, handle, int(n)
+
+    def __len__(self):
+        return self.n
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self._t is not None and self.ctx._h:
+            self.ctx._chk(self.ctx.L.visma_icp_kdtree_destroy(self._t))
+        self._t = None
+
+    def _lists(self, call, queries, cap, *args):
+        q = _f64(queries, (-1, 3))
+        if int(cap) < 1:                                  # (no row can be shaped: the library's answer without its call)
+            raise IcpError(1, "a list of at least one entry")
+        rows = max(len(q), 1)
+        idx, d2, cnt = np.empty((rows, int(cap)), np.int32), np.empty((rows, int(cap))), np.empty(rows, np.int32)
+        self.ctx._chk(call(self._t, _p(q, _dp), len(q), *args, _p(idx, _ip), _p(d2, _dp), _p(cnt, _ip)))
+        return idx[:len(q)], d2[:len(q)], cnt[:len(q)]
+
+    def search_knn(self, queries, knn):
+        """SearchKNN for every row of queries (nq x 3) -> idx (nq x knn int32, -1 behind a list), d2 (nq x knn, +inf behind
+        it), cnt (nq): the min(knn, n) nearest."""
+        return self._lists(self.ctx.L.visma_icp_kdtree_search_knn, queries, knn, int(knn))
+
+    def search_hybrid(self, queries, radius, max_nn):
+        """SearchHybrid: the max_nn nearest of those with d2 < (double)(float)(radius * radius); the layout of search_knn."""
+        return self._lists(self.ctx.L.visma_icp_kdtree_search_hybrid, queries, max_nn, float(radius), int(max_nn))
+
+    def search_radius(self, queries, radius):
+        """SearchRadius: every neighbour with d2 < (double)(float)(radius * radius) -> offsets (nq + 1 int64), idx (total
+        int32), d2 (total): query i owns [offsets[i], offsets[i + 1])."""
+        q = _f64(queries, (-1, 3))
+        offsets, total = np.zeros(len(q) + 1, np.int64), C.c_int64(0)
+        self.ctx._chk(self.ctx.L.visma_icp_kdtree_search_radius(self._t, _p(q, _dp), len(q), float(radius),
+                                                                _p(offsets, C.POINTER(C.c_int64)), C.byref(total)))
+        idx, d2 = np.empty(max(total.value, 1), np.int32), np.empty(max(total.value, 1))
+        self.ctx._chk(self.ctx.L.visma_icp_kdtree_get_radius_result(self._t, _p(idx, _ip), _p(d2, _dp)))
+        return offsets, idx[:total.value], d2[:total.value]
+
+
 class CColorMapOption(C.Structure):
     """visma_icp_color_map_option (Open3D's ColorMapOptmizationOption, field for field)"""
     _fields_ = [("non_rigid_camera_coordinate", C.c_int32), ("number_of_vertical_anchors", C.c_int32),
@@ -618,6 +672,16 @@ def _bind(L):
         L.visma_icp_tsdf_get_units.argtypes = [_vp, _vp, _ip, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_depth.argtypes = [_vp, C.c_int, C.c_int, _fp, _dp, _dp, C.c_int, _dp, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_rgbd.argtypes = [_vp, C.c_int, C.c_int, _fp, _vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64]
+    if hasattr(L, "visma_icp_kdtree_create"):            # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp = C.POINTER(C.c_int64), C.c_void_p
+        L.visma_icp_kdtree_create.argtypes = [_vp, _dp, C.c_int64, C.POINTER(_vp)]
+        L.visma_icp_kdtree_destroy.argtypes = [_vp]
+        L.visma_icp_kdtree_size.argtypes = [_vp]
+        L.visma_icp_kdtree_size.restype = C.c_int64
+        L.visma_icp_kdtree_search_knn.argtypes = [_vp, _dp, C.c_int64, C.c_int, _ip, _dp, _ip]
+        L.visma_icp_kdtree_search_hybrid.argtypes = [_vp, _dp, C.c_int64, C.c_double, C.c_int, _ip, _dp, _ip]
+        L.visma_icp_kdtree_search_radius.argtypes = [_vp, _dp, C.c_int64, C.c_double, _i64, _i64]
+        L.visma_icp_kdtree_get_radius_result.argtypes = [_vp, _ip, _dp]
     if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
         _opt = C.POINTER(CColorMapOption)
@@ -1442,6 +1506,14 @@ class Context:
         out = np.empty(36); k = C.c_int64(0)
         self._chk(self.L.visma_icp_odometry_information(self._h, _p(T, _dp), _p(out, _dp), C.byref(k)))
         return out.reshape(6, 6), k.value
+
+    # ---- KDTreeFlann (visma_icp.h) ----
+    def kdtree(self, xyz):
+        """Open3D's KDTreeFlann over xyz (n x 3 f64, n >= 1), resident on the device -> KDTree."""
+        p = _f64(xyz, (-1, 3))
+        t = C.c_void_p()
+        self._chk(self.L.visma_icp_kdtree_create(self._h, _p(p, _dp), len(p), C.byref(t)))
+        return KDTree(self, t, len(p))
 
     # ---- TSDF integration (visma_icp.h) ----
     def tsdf_uniform(self, length, resolution, sdf_trunc, color_type=TSDF_COLOR_NONE, origin=(0.0, 0.0, 0.0)):

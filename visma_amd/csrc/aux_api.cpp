@@ -56,6 +56,101 @@ int visma_icp_color_gradient(visma_icp_ctx *ctx, const double *xyz, int64_t n, c
     return VISMA_ICP_OK;
 }
 
+// ---- KDTreeFlann: a cloud resident on the device, searched for any query points (kdtree.hip) ----
+#define TREE_CHECK()                                                                                  \
+    if (!tree || !tree->ctx) { g_create_error = "tree is NULL"; return VISMA_ICP_ERR_INVALID; }      \
+    visma_icp_ctx *const ctx = tree->ctx;
+
+static int kdtree_fail(visma_icp_ctx *ctx, const char *what, hipError_t e)
+{
+    (void)hipGetLastError();
+    return ctx->fail(VISMA_ICP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+static bool kdtree_radius_ok(double radius) { return std::isfinite(radius) && radius > 0.0; }
+
+int visma_icp_kdtree_create(visma_icp_ctx *ctx, const double *xyz, int64_t n, visma_icp_kdtree **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!xyz || n < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "kdtree_create: a cloud of at least one point");
+    if (n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many points for 32-bit indices");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "kdtree needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    std::unique_ptr<visma_icp_kdtree> t(new visma_icp_kdtree);
+    t->ctx = ctx; t->n = n;
+    const hipError_t e = kdtree_device_create(xyz, n, ctx->eng->aux_stream(), &t->dev);
+    if (e != hipSuccess) return kdtree_fail(ctx, "kdtree_create", e);
+    *out = t.get();
+    ctx->trees.push_back(std::move(t));
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_kdtree_destroy(visma_icp_kdtree *tree)
+{
+    TREE_CHECK();
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    for (size_t i = 0; i < ctx->trees.size(); i++)
+        if (ctx->trees[i].get() == tree) { ctx->trees.erase(ctx->trees.begin() + (std::ptrdiff_t)i); return VISMA_ICP_OK; }
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "no such tree");
+}
+
+int64_t visma_icp_kdtree_size(const visma_icp_kdtree *tree) { return tree ? tree->n : 0; }
+
+static int kdtree_search_lists(visma_icp_kdtree *tree, bool knn, const double *queries, int64_t nq, double radius, int cap,
+                               int32_t *idx, double *d2, int32_t *cnt)
+{
+    TREE_CHECK();
+    const char *what = knn ? "kdtree_search_knn" : "kdtree_search_hybrid";
+    if (nq < 0 || cap < 1 || (!knn && !kdtree_radius_ok(radius)))
+        return ctx->fail(VISMA_ICP_ERR_INVALID, std::string(what) + (knn ? ": nq >= 0 and knn >= 1" : ": nq >= 0, max_nn >= 1 and a finite radius > 0"));
+    if (nq > 0 && (!queries || !idx || !d2 || !cnt)) return ctx->fail(VISMA_ICP_ERR_INVALID, std::string(what) + ": NULL argument");
+    if (nq > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many queries for one call");
+    if (nq == 0) return VISMA_ICP_OK;
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    const hipError_t e = kdtree_device_search(tree->dev, knn, queries, nq, knn ? 0.0 : radius, cap, idx, d2, cnt, ctx->eng->aux_stream());
+    return e == hipSuccess ? VISMA_ICP_OK : kdtree_fail(ctx, what, e);
+}
+
+int visma_icp_kdtree_search_knn(visma_icp_kdtree *tree, const double *queries, int64_t nq, int knn, int32_t *idx, double *d2,
+                                int32_t *cnt)
+{
+    return kdtree_search_lists(tree, true, queries, nq, 0.0, knn, idx, d2, cnt);
+}
+
+int visma_icp_kdtree_search_hybrid(visma_icp_kdtree *tree, const double *queries, int64_t nq, double radius, int max_nn,
+                                   int32_t *idx, double *d2, int32_t *cnt)
+{
+    return kdtree_search_lists(tree, false, queries, nq, radius, max_nn, idx, d2, cnt);
+}
+
+int visma_icp_kdtree_search_radius(visma_icp_kdtree *tree, const double *queries, int64_t nq, double radius, int64_t *offsets,
+                                   int64_t *total)
+{
+    TREE_CHECK();
+    if (nq < 0 || !kdtree_radius_ok(radius)) return ctx->fail(VISMA_ICP_ERR_INVALID, "kdtree_search_radius: nq >= 0 and a finite radius > 0");
+    if (!offsets || !total || (nq > 0 && !queries)) return ctx->fail(VISMA_ICP_ERR_INVALID, "kdtree_search_radius: NULL argument");
+    if (nq > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "too many queries for one call");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    const hipError_t e = kdtree_device_search_radius(tree->dev, queries, nq, radius, offsets, total, ctx->eng->aux_stream());
+    if (e == hipErrorOutOfMemory && *total > kKdTreeMaxRadiusEntries) {
+        (void)hipGetLastError();
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "kdtree_search_radius: more than VISMA_ICP_KDTREE_MAX_RADIUS_ENTRIES entries; search fewer queries a call");
+    }
+    return e == hipSuccess ? VISMA_ICP_OK : kdtree_fail(ctx, "kdtree_search_radius", e);
+}
+
+int visma_icp_kdtree_get_radius_result(visma_icp_kdtree *tree, int32_t *idx, double *d2)
+{
+    TREE_CHECK();
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    const hipError_t e = kdtree_device_radius_result(tree->dev, idx, d2, ctx->eng->aux_stream());
+    if (e == hipErrorNotReady) return ctx->fail(VISMA_ICP_ERR_STATE, "kdtree_get_radius_result: no radius search before it");
+    if (e == hipErrorInvalidValue) return ctx->fail(VISMA_ICP_ERR_INVALID, "kdtree_get_radius_result: NULL argument");
+    return e == hipSuccess ? VISMA_ICP_OK : kdtree_fail(ctx, "kdtree_get_radius_result", e);
+}
+
 // ---- FPFH, feature matching, fast global registration ----
 
 int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type,

@@ -25,6 +25,17 @@ struct visma_icp_color_map {
     double anchor_step = 0.0;
 };
 
+// a KDTreeFlann of a context: the cloud resident on the device with the grid of its last search (kdtree.hip)
+struct visma_icp_kdtree {
+    visma_icp_ctx *ctx = nullptr;
+    KdTreeDevice *dev = nullptr;
+    int64_t n = 0;
+    visma_icp_kdtree() = default;
+    visma_icp_kdtree(const visma_icp_kdtree &) = delete;
+    visma_icp_kdtree &operator=(const visma_icp_kdtree &) = delete;
+    ~visma_icp_kdtree() { kdtree_device_destroy(dev); }
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -56,6 +67,7 @@ struct visma_icp_ctx {
     struct { bool ready = false; int w = 0, h = 0, n_levels = 0; } odo;
     std::vector<std::unique_ptr<visma_icp_color_map>> color_maps;   // likewise
     std::vector<std::unique_ptr<visma_icp_tsdf>> volumes;   // the engine frees their device memory with itself
+    std::vector<std::unique_ptr<visma_icp_kdtree>> trees;   // each frees its own, before the engine goes
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

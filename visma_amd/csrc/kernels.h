@@ -823,6 +823,24 @@ struct NnGrid {
 hipError_t nn_selftest_lists_device(const double *h_xyz, int64_t n, int search_type, int cap, double radius, int list_kind,
                                     int32_t *h_idx, double *h_d2, int32_t *h_cnt, hipStream_t stream);
 
+// ---- KDTreeFlann (kdtree.hip): a cloud resident on the device, searched for ANY query points (host arrays in and out) ----
+// The search is nn_list.h's; the grid is NnGrid's, built for the radius or the knn of a call and kept for the next call with
+// the same parameter.  Lists in the queries' order, ascending (d2, index); idx / d2 nq x cap, -1 / +inf behind a list.
+constexpr int64_t kKdTreeSlabEntries = 1ll << 22;        // list entries one KNN / Hybrid launch writes (its queries: a slab)
+constexpr int64_t kKdTreeMaxRadiusEntries = 1ll << 28;   // entries of one uncapped Radius result (12 bytes each on the device)
+struct KdTreeDevice;
+hipError_t kdtree_device_create(const double *h_xyz, int64_t n, hipStream_t stream, KdTreeDevice **out);
+void kdtree_device_destroy(KdTreeDevice *T);
+// cap = knn (radius unused) or max_nn; the arguments are checked by the caller (aux_api.cpp)
+hipError_t kdtree_device_search(KdTreeDevice *T, bool knn, const double *h_q, int64_t nq, double radius, int cap,
+                                int32_t *h_idx, double *h_d2, int32_t *h_cnt, hipStream_t stream);
+// count, scan, write: offsets[nq + 1], *total; the lists stay on the device for kdtree_device_radius_result.  More than
+// kKdTreeMaxRadiusEntries: hipErrorOutOfMemory with *total set and nothing kept.
+hipError_t kdtree_device_search_radius(KdTreeDevice *T, const double *h_q, int64_t nq, double radius, int64_t *h_offsets,
+                                       int64_t *total, hipStream_t stream);
+// hipErrorNotReady without a radius search before it, hipErrorInvalidValue for a NULL array where there are entries
+hipError_t kdtree_device_radius_result(KdTreeDevice *T, int32_t *h_idx, double *h_d2, hipStream_t stream);
+
 // the gradient per point (n x 3 doubles on the device, the points' order) by the Hybrid search (radius, max_nn);
 // max_nn outside [3, kNormalsMaxList]: hipErrorInvalidValue.  Returns with the stream idle.
 hipError_t color_gradient_on_device(const ColorGradientInput &in, double radius, int max_nn, double *d_grad, hipStream_t stream);

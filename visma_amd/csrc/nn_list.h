@@ -55,9 +55,11 @@ hipError_t nn_launch(int lds_cap, long long queries, const Args &a, hipStream_t 
     return launch(std::integral_constant<int, 64>{});
 }
 
-// the query of thread t (cell order): the point, its cell, its index in the caller's order
+// the query of thread t (cell order): the point, its cell, its index in the caller's order; b: where the binning saw it
+// (its coordinates relative to the binning origin) -- what the KNN stopping rule measures from
 struct NnQuery {
     Pt64 p;
+    double b[3];
     int cx, cy, cz;
     int me;
 };
@@ -71,6 +73,7 @@ __device__ __forceinline__ NnQuery nn_query(const NnGridView &v, long long t)
     q.cx = min(max(cell_coord(qf.x, v.g.mn[0], v.g.inv_h, v.g.dim[0]), 0), v.g.dim[0] - 1);
     q.cy = min(max(cell_coord(qf.y, v.g.mn[1], v.g.inv_hs, v.g.dim[1]), 0), v.g.dim[1] - 1);
     q.cz = min(max(cell_coord(qf.z, v.g.mn[2], v.g.inv_hs, v.g.dim[2]), 0), v.g.dim[2] - 1);
+    q.b[0] = (double)qf.x; q.b[1] = (double)qf.y; q.b[2] = (double)qf.z;
     q.me = (int)q.p.w;
     return q;
 }
@@ -246,10 +249,43 @@ __device__ __forceinline__ void nn_scan_shell(const GridParams &g, const unsigne
         }
 }
 
+// After rings 0 .. R around the query's cell: the squared distance from the query to the nearest point that may still be
+// unscanned, +inf with *open = false once the whole grid has been scanned.  True for ANY query, inside its cell or clamped
+// into the grid from outside: an unscanned point lies in a cell beyond one of the six faces of the scanned block, so inside
+// the slab of the grid's box beyond that face (the finite coordinates of the cloud lie inside the box: grid.hip, bbox_kernel),
+// and the distance from the query to a slab is that to an axis-aligned box: beyond the face along its axis, outside the
+// grid's box along the other two.  Only faces with cells of the grid beyond them count.  The fp32 binning may see a point
+// 1e-3 cell from where it is (kGridMaxDim), and the query of a self-search likewise: every length is taken short by
+// 0.1 % of the R + 1 cells it spans.  (A point whose coordinate is not finite sits in a clamped cell outside every slab: its
+// distance is infinite or NaN, and nn_search stops only on a farthest entry below the bound: a finite one.)
+__device__ __forceinline__ double nn_unscanned_d2(const GridParams &g, const NnQuery &q, int R, bool *open)
+{
+    const double edge[3] = {(double)g.h, (double)g.hs, (double)g.hs};
+    const int c[3] = {q.cx, q.cy, q.cz};
+    double lo[3], hi[3], out2[3];                                   // to the two faces (-1: none beyond); outside the box, squared
+    for (int a = 0; a < 3; a++) {
+        const double slack = 1e-3 * (double)(R + 1) * edge[a];
+        const double u = q.b[a] - (double)g.mn[a];                  // from the box's lower corner
+        const double o = fmax(fmax(-u, u - (double)g.dim[a] * edge[a]) - slack, 0.0);
+        out2[a] = o * o;
+        lo[a] = c[a] - R > 0 ? fmax(u - (double)(c[a] - R) * edge[a] - slack, 0.0) : -1.0;
+        hi[a] = c[a] + R < g.dim[a] - 1 ? fmax((double)(c[a] + R + 1) * edge[a] - u - slack, 0.0) : -1.0;
+    }
+    double best = INFINITY;
+    *open = false;
+    for (int a = 0; a < 3; a++) {
+        const double rest = out2[(a + 1) % 3] + out2[(a + 2) % 3];
+        if (lo[a] >= 0.0) { *open = true; best = fmin(best, lo[a] * lo[a] + rest); }
+        if (hi[a] >= 0.0) { *open = true; best = fmin(best, hi[a] * hi[a] + rest); }
+    }
+    return best;
+}
+
 // Every point of the cells around q whose squared distance d passes accept(d) (nn_accept) goes to list.insert(d, index).
-//   KNN = false  cells of edge 1.001 r: the 27 cells (rings 0 and 1) cover the radius, `accept` holds the radius test
-//   KNN = true   any cell size: rings are added until the list is full and its farthest entry lies within the rings
-//                scanned (0.1 % slack for the fp32 binning), or the whole grid has been scanned
+//   KNN = false  cells of edge 1.001 r: the 27 cells (rings 0 and 1) cover the radius, `accept` holds the radius test;
+//                for a query clamped into the grid from outside they still do (the block only moves towards the cloud)
+//   KNN = true   any cell size: rings are added until the list is full and its farthest entry lies nearer than anything
+//                unscanned can (nn_unscanned_d2), or the whole grid has been scanned
 // `list` needs insert and, for KNN, cnt, cap and farthest: NnList, NnHeap, or a caller's own that only counts.
 template <bool KNN, class List, class Accept>
 __device__ __forceinline__ void nn_search(const NnGridView &v, const NnQuery &q, List &list, Accept accept)
@@ -263,13 +299,10 @@ __device__ __forceinline__ void nn_search(const NnGridView &v, const NnQuery &q,
     for (int R = 0; R <= rmax; R++) {
         nn_scan_shell<KNN>(g, v.start, v.sorted64, q.cx, q.cy, q.cz, R, consider);
         if constexpr (KNN) {
-            if (list.cnt == list.cap && R >= 1) {
-                const double cover = (double)R * (double)g.h * 0.999;
-                if (list.farthest() <= cover * cover) break;
-            }
-            if (q.cx - R <= 0 && q.cy - R <= 0 && q.cz - R <= 0 && q.cx + R >= g.dim[0] - 1 && q.cy + R >= g.dim[1] - 1 &&
-                q.cz + R >= g.dim[2] - 1)
-                break;                                              // the whole grid has been scanned
+            bool open;
+            const double beyond = nn_unscanned_d2(g, q, R, &open);
+            if (!open) break;                                       // the whole grid has been scanned
+            if (list.cnt == list.cap && list.farthest() < beyond) break;     // (strictly: a finite entry, and no tie left open)
         }
     }
 }
