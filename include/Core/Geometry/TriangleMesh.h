@@ -1,5 +1,5 @@
 // Core/Geometry/TriangleMesh.h -- the data carrier of a triangle mesh (shape of O3D/Core/Geometry/TriangleMesh.h: AoS f64
-// vertices, normals and colours, int triangles).  Minimal: what color map optimization reads and writes.  Stand-alone and
+// vertices, normals and colours, int triangles).  Minimal: what ExtractTriangleMesh fills and color map optimization reads and writes.  Stand-alone and
 // header-only.
 #pragma once
 #include <Eigen/Core>

@@ -1,5 +1,5 @@
 // Core/Integration/ScalableTSDFVolume.h -- volume units of volume_unit_resolution^3 voxels, opened where the frames' surfaces
-// are, resident on the GPU (shape of O3D/Core/Integration/ScalableTSDFVolume.h, without ExtractTriangleMesh).  The methods
+// are, resident on the GPU (shape of O3D/Core/Integration/ScalableTSDFVolume.h).  The methods
 // are defined in visma_icp_open3d.hpp (visma_icp.h: the steps, the unit pool and THE ORDER of the extractions, which is
 // this library's definition: units in lexicographic order of their index, the reference's order within a unit).  The
 // units live on the device: the reference's volume_units_ map is read through Units() and DownloadUnit().
@@ -29,6 +29,7 @@ public:
     void Reset() override;
     void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) override;
     std::shared_ptr<PointCloud> ExtractPointCloud() override;
+    std::shared_ptr<TriangleMesh> ExtractTriangleMesh() override;
     std::shared_ptr<PointCloud> ExtractVoxelPointCloud();
     // the indices of the open units, in lexicographic order
     std::vector<Eigen::Vector3i> Units() const;

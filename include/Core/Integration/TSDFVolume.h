@@ -1,5 +1,5 @@
 // Core/Integration/TSDFVolume.h -- the interface of a truncated signed distance volume (shape of
-// O3D/Core/Integration/TSDFVolume.h, without ExtractTriangleMesh: DESIGN.md 4.4c11).  Stand-alone and header-only.
+// O3D/Core/Integration/TSDFVolume.h).  Stand-alone and header-only.
 #pragma once
 
 #include <memory>
@@ -9,6 +9,7 @@
 #include "../Camera/PinholeCameraIntrinsic.h"
 #include "../Geometry/PointCloud.h"
 #include "../Geometry/RGBDImage.h"
+#include "../Geometry/TriangleMesh.h"
 
 namespace open3d {
 
@@ -26,6 +27,9 @@ public:
     // reference prints a warning and returns).
     virtual void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) = 0;
     virtual std::shared_ptr<PointCloud> ExtractPointCloud() = 0;
+    // marching cubes: vertices_, vertex_colors_ (empty without colour) and triangles_.  The vertices and their colours are the
+    // reference's; their order and the triangulation of a cube are this library's (visma_icp.h: THE ORDER, THE CASE RULE)
+    virtual std::shared_ptr<TriangleMesh> ExtractTriangleMesh() = 0;
 
     double voxel_length_;
     double sdf_trunc_;

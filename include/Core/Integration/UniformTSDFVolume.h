@@ -28,6 +28,7 @@ public:
     void Reset() override;
     void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) override;
     std::shared_ptr<PointCloud> ExtractPointCloud() override;
+    std::shared_ptr<TriangleMesh> ExtractTriangleMesh() override;
     // every voxel with a weight and a tsdf in [-0.98, 0.98): its centre, coloured (tsdf + 1) / 2
     std::shared_ptr<PointCloud> ExtractVoxelPointCloud();
     // the reference's tsdf_, weight_ (voxel_num_ floats) and color_ (voxel_num_ entries, empty without colour)

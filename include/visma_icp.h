@@ -1234,7 +1234,14 @@ VISMA_ICP_API int visma_icp_odometry_information(visma_icp_ctx *ctx, const doubl
  *     x86-64 it opens one junk unit at index INT_MIN.)  A uniform volume needs no rule: a depth that is not > 0 (NaN, -inf,
  *     negative, 0) is skipped and a depth of +inf integrates as tsdf 1, as in the reference; the point clouds from a frame
  *     hold a row that is not finite for such a pixel, as the reference's do;
- *   - ExtractTriangleMesh and 16-bit depth are not provided.
+ *   - 16-bit depth is not provided;
+ *   - ExtractTriangleMesh (below): the valid cubes, the edges that carry a vertex and every vertex's position and colour are
+ *     the reference's bit for bit; THE ORDER of the vertices and triangles and THE CASE RULE -- how a cube's cut edges are
+ *     joined into triangles -- are this library's.  The reference's case tables are its program text and are not part of
+ *     this library; a rule made independently splits a cube's patch along other diagonals and joins the edges of a cube
+ *     with a face of alternating signs in its own way, so the reference's triangle list is not reproduced index for index.
+ *     Where no valid cube has such a face the two meshes have the same vertices, the same number of triangles, the same
+ *     boundary and the same Euler characteristic, and the same winding.
  * No floating-point atomics: every voxel has one writer, and a run is bit-identical to itself.
  *
  * VISMA_ICP_ERR_INVALID, before anything reaches a device: a NULL pointer, resolution < 1, a volume of more than 2^31 - 1
@@ -1266,6 +1273,42 @@ VISMA_ICP_API int visma_icp_tsdf_get_point_cloud(visma_icp_ctx *ctx, visma_icp_t
 VISMA_ICP_API int visma_icp_tsdf_extract_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_n);
 VISMA_ICP_API int visma_icp_tsdf_get_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *points, double *colors,
                                                        int64_t n);
+/* ExtractTriangleMesh(): marching cubes over the resident volume (tsdf.hip).  The mesh stays on the
+ * device, *out_nv and *out_nt are its vertex and triangle counts; then the rows (nv, nt as returned; vertices and colors are
+ * nv x 3 doubles, triangles nt x 3 int32 vertex indices; each may be NULL; colors is left untouched for a volume without
+ * colour).  A get before its extract is VISMA_ICP_ERR_STATE; other counts than the extract returned, a volume of another
+ * context or a sharded context are VISMA_ICP_ERR_INVALID before anything reaches a device.  resolution < 2, or a volume no
+ * frame went into, gives an empty mesh and launches nothing.
+ *   cubes      uniform: every (x, y, z) in [0, R - 2]^3; scalable: every voxel of every unit, a corner beyond the unit read
+ *              from the unit next door, a missing unit reading weight 0.  A cube is VALID iff its eight weights are != 0
+ *              (there is no tsdf range test here).  A corner is INSIDE iff tsdf < 0 (-0.0 is outside).  Cubes with all
+ *              corners inside or all outside emit nothing.
+ *   vertices   one per voxel edge (lower voxel, axis) whose two ends differ in sign and that lies on at least one valid cube,
+ *              shared by the cubes around it.  In f64, in this order: each component half + voxel_length * index; the axis
+ *              component += f0 * voxel_length / (f0 + f1) with f0 = |(double)tsdf(lower)|, f1 = |(double)tsdf(upper)|; a
+ *              uniform volume then adds its origin, a scalable one uses global voxel indices.  Colour (f1 c0 + f0 c1) /
+ *              (f0 + f1) in f64, c = (double)colour / 255.0 (RGB8) or (double)colour (GRAY32).  Bit for bit the reference's.
+ *   THE ORDER  vertices ascend by (x, y, z, axis) of their edge -- ExtractPointCloud's order; a scalable volume's by the
+ *              unit that owns the lower voxel, units in lexicographic index order, then (x, y, z, axis) in the unit.
+ *              Triangles ascend by cube in the same order, within a cube in the order of the case rule.
+ *   THE CASE RULE  bit i of a cube's case is its corner at offset (i & 1, (i >> 1) & 1, (i >> 2) & 1) being inside.  A cube
+ *              edge is (lower corner, axis) with id 4 axis + j, j = the lower corner's two other coordinates, the earlier
+ *              axis as bit 0 (0 .. 3: the x edges at (y, z) = (0,0) (1,0) (0,1) (1,1); 4 .. 7: the y edges at (x, z); 8 .. 11:
+ *              the z edges at (x, y)).  On each face the cut edges are joined into segments that each cut off one group of
+ *              inside corners connected along the face's edges; a face with four cut edges has two groups of one corner.
+ *              Every cut edge then ends one segment and begins one; the segments close into loops; loops in the order of
+ *              their lowest edge id, each started there and fanned from its start.  At most 5 triangles per cube.  The rule
+ *              reads a face's four signs only: two cubes always agree on their common face, the mesh has no cracks.
+ *   winding    the reference's: a triangle's normal (b - a) x (c - a) points towards increasing tsdf (free space).
+ *   degenerate triangles (a vertex with f0 == 0 coincides with its neighbours') are kept, as in the reference.
+ * Vertex indices are int32: a mesh of more than 2^31 - 1 vertices or triangles is VISMA_ICP_ERR_INVALID.
+ * No atomics, one writer per row: a run is bit-identical to itself. */
+VISMA_ICP_API int visma_icp_tsdf_extract_triangle_mesh(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_nv, int64_t *out_nt);
+VISMA_ICP_API int visma_icp_tsdf_get_triangle_mesh(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *vertices, double *colors,
+                                                   int32_t *triangles, int64_t nv, int64_t nt);
+/* The triangles of one case of THE CASE RULE as edge ids (host only, no context): cube_case in 0 .. 255, edge_ids has room
+ * for 15 ints (5 triangles), *n_triangles is their number.  Anything else: VISMA_ICP_ERR_INVALID. */
+VISMA_ICP_API int visma_icp_marching_cubes_case(int cube_case, int32_t *edge_ids, int *n_triangles);
 /* tsdf_ and weight_ (R^3 floats) and color_ (R^3 x 3 floats, interleaved; untouched without colour) of a uniform volume
  * (unit_index NULL) or of the unit of a scalable volume with that index; each output may be NULL.  A unit_index for a
  * uniform volume, none for a scalable one, or an index no unit has: VISMA_ICP_ERR_INVALID. */

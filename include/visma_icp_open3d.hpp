@@ -77,6 +77,7 @@
 #include <Core/Registration/GlobalOptimizationMethod.h>
 #include <Core/Geometry/Image.h>
 #include <Core/Geometry/RGBDImage.h>
+#include <Core/Geometry/TriangleMesh.h>
 #include <Core/Odometry/Odometry.h>
 #ifdef VISMA_ICP_STANDALONE_OPEN3D_TYPES
 #include <Core/Integration/UniformTSDFVolume.h>
@@ -1801,6 +1802,20 @@ inline std::shared_ptr<PointCloud> tsdf_extract_voxel_point_cloud(visma_icp_ctx 
           "visma_icp_tsdf_get_voxel_point_cloud");
     return out;
 }
+inline std::shared_ptr<TriangleMesh> tsdf_extract_triangle_mesh(visma_icp_ctx *ctx, visma_icp_tsdf *volume, bool colored)
+{
+    auto out = std::make_shared<TriangleMesh>();
+    int64_t nv = 0, nt = 0;
+    check(ctx, visma_icp_tsdf_extract_triangle_mesh(ctx, volume, &nv, &nt), "visma_icp_tsdf_extract_triangle_mesh");
+    out->vertices_.resize((size_t)nv); out->vertex_colors_.resize(colored ? (size_t)nv : 0);
+    std::vector<int32_t> tri(3 * (size_t)nt);
+    check(ctx, visma_icp_tsdf_get_triangle_mesh(ctx, volume, nv ? out->vertices_[0].data() : nullptr,
+                                                colored && nv ? out->vertex_colors_[0].data() : nullptr, nt ? tri.data() : nullptr, nv, nt),
+          "visma_icp_tsdf_get_triangle_mesh");
+    out->triangles_.resize((size_t)nt);
+    for (size_t i = 0; i < (size_t)nt; i++) out->triangles_[i] = Eigen::Vector3i(tri[3 * i], tri[3 * i + 1], tri[3 * i + 2]);
+    return out;
+}
 inline void tsdf_download(visma_icp_ctx *ctx, visma_icp_tsdf *volume, const int32_t *unit, size_t voxels, bool colored, std::vector<float> &tsdf,
                           std::vector<float> &weight, std::vector<Eigen::Vector3f> &color)
 {
@@ -2134,6 +2149,10 @@ inline std::shared_ptr<PointCloud> UniformTSDFVolume::ExtractPointCloud()
 {
     return cicp::detail::tsdf_extract_point_cloud(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
 }
+inline std::shared_ptr<TriangleMesh> UniformTSDFVolume::ExtractTriangleMesh()
+{
+    return cicp::detail::tsdf_extract_triangle_mesh(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
+}
 inline std::shared_ptr<PointCloud> UniformTSDFVolume::ExtractVoxelPointCloud() { return cicp::detail::tsdf_extract_voxel_point_cloud(ctx_, volume_); }
 inline void UniformTSDFVolume::Download(std::vector<float> &tsdf, std::vector<float> &weight, std::vector<Eigen::Vector3f> &color) const
 {
@@ -2167,6 +2186,10 @@ inline void ScalableTSDFVolume::Integrate(const RGBDImage &image, const PinholeC
 inline std::shared_ptr<PointCloud> ScalableTSDFVolume::ExtractPointCloud()
 {
     return cicp::detail::tsdf_extract_point_cloud(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
+}
+inline std::shared_ptr<TriangleMesh> ScalableTSDFVolume::ExtractTriangleMesh()
+{
+    return cicp::detail::tsdf_extract_triangle_mesh(ctx_, volume_, color_type_ != TSDFVolumeColorType::None);
 }
 inline std::shared_ptr<PointCloud> ScalableTSDFVolume::ExtractVoxelPointCloud() { return cicp::detail::tsdf_extract_voxel_point_cloud(ctx_, volume_); }
 inline std::vector<Eigen::Vector3i> ScalableTSDFVolume::Units() const

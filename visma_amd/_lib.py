@@ -188,6 +188,20 @@ class TsdfVolume:
         self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_voxel_point_cloud(self.ctx._h, self._v, _p(pts, _dp), _p(col, _dp), n))
         return pts, col
 
+    def extract_triangle_mesh(self):
+        """ExtractTriangleMesh() -> vertices (n x 3 f64), colors (n x 3 f64, None for a volume without colour), triangles
+        (m x 3 int32 vertex indices).  Vertices in ExtractPointCloud's order (x, y, z, axis of their voxel edge; a scalable
+        volume's unit by unit), triangles cube by cube in that order (include/visma_icp.h: THE ORDER, THE CASE RULE)."""
+        nv, nt = C.c_int64(0), C.c_int64(0)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_extract_triangle_mesh(self.ctx._h, self._v, C.byref(nv), C.byref(nt)))
+        nv, nt = nv.value, nt.value
+        vtx = np.empty((nv, 3))
+        col = np.empty((nv, 3)) if self.color_type != TSDF_COLOR_NONE else None
+        tri = np.empty((nt, 3), np.int32)
+        self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_triangle_mesh(self.ctx._h, self._v, _p(vtx, _dp), None if col is None else _p(col, _dp),
+                                                                  _p(tri, _ip), nv, nt))
+        return vtx, col, tri
+
     def units(self):
         """The unit indices of a scalable volume (n x 3 int32) in lexicographic order: the order of its extractions."""
         n = C.c_int64(0)
@@ -672,6 +686,11 @@ def _bind(L):
         L.visma_icp_tsdf_get_units.argtypes = [_vp, _vp, _ip, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_depth.argtypes = [_vp, C.c_int, C.c_int, _fp, _dp, _dp, C.c_int, _dp, C.c_int64, _i64]
         L.visma_icp_point_cloud_from_rgbd.argtypes = [_vp, C.c_int, C.c_int, _fp, _vp, C.c_int, _dp, _dp, _dp, _dp, C.c_int64, _i64]
+    if hasattr(L, "visma_icp_tsdf_extract_triangle_mesh"):   # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp = C.POINTER(C.c_int64), C.c_void_p
+        L.visma_icp_tsdf_extract_triangle_mesh.argtypes = [_vp, _vp, _i64, _i64]
+        L.visma_icp_tsdf_get_triangle_mesh.argtypes = [_vp, _vp, _dp, _dp, _ip, C.c_int64, C.c_int64]
+        L.visma_icp_marching_cubes_case.argtypes = [C.c_int, _ip, C.POINTER(C.c_int)]
     if hasattr(L, "visma_icp_kdtree_create"):            # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp = C.POINTER(C.c_int64), C.c_void_p
         L.visma_icp_kdtree_create.argtypes = [_vp, _dp, C.c_int64, C.POINTER(_vp)]
@@ -1016,6 +1035,17 @@ def _pose_graph_args(poses, edges):
         arr[i].uncertain = 1 if e.uncertain else 0
         arr[i].confidence = float(e.confidence)
     return P, arr
+
+
+def marching_cubes_case(cube_case):
+    """The triangles of one case of ExtractTriangleMesh's case rule as edge ids (t x 3 int32, t <= 5); host only.
+    Bit i of cube_case: the corner at offset (i & 1, (i >> 1) & 1, (i >> 2) & 1) is inside; edge id 4 axis + j."""
+    ids = np.zeros(15, np.int32)
+    n = C.c_int(0)
+    rc = load().visma_icp_marching_cubes_case(int(cube_case), _p(ids, _ip), C.byref(n))
+    if rc:
+        raise IcpError(rc, "marching_cubes_case: a case outside 0 .. 255")
+    return ids[:3 * n.value].reshape(-1, 3).copy()
 
 
 def pose_graph_validate(n_nodes, edges):

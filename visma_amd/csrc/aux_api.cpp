@@ -4,6 +4,7 @@
 #include "driver_ctx.hpp"
 #include "plane_math.hpp"
 #include "ransac.hpp"
+#include "mc_table.h"
 
 extern "C" {
 
@@ -1128,6 +1129,16 @@ int visma_annot_total_pose(const double T0[16], const double T1[16], const doubl
     for (int i = 0; i < 3; i++) Ai[4 * i + 3] = -(Ai[4 * i] * A[3] + Ai[4 * i + 1] * A[7] + Ai[4 * i + 2] * A[11]);
     mul(Ai, T3, A);
     mul(A, T2, Ttot);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_marching_cubes_case(int cube_case, int32_t *edge_ids, int *n_triangles)
+{
+    if (cube_case < 0 || cube_case > 255 || !edge_ids || !n_triangles) return VISMA_ICP_ERR_INVALID;
+    const visma::McCase &c = visma::mc_table().c[cube_case];
+    if (c.n > visma::kMcMaxTriangles) return VISMA_ICP_ERR_STATE;     // (the rule gave more than the table holds: never)
+    *n_triangles = c.n;
+    for (int i = 0; i < 3 * c.n; i++) edge_ids[i] = c.edge[i];
     return VISMA_ICP_OK;
 }
 

@@ -1835,6 +1835,7 @@ int visma_icp_tsdf_reset(visma_icp_ctx *ctx, visma_icp_tsdf *volume)
     CTX_CHECK();
     if (int rc = check_tsdf_volume(ctx, volume)) return rc;
     volume->rows[0] = volume->rows[1] = -1;
+    volume->mesh_rows[0] = volume->mesh_rows[1] = -1;
     int rc = ctx->eng->tsdf_reset(volume->id);
     return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
 }
@@ -1849,6 +1850,7 @@ int visma_icp_tsdf_integrate(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int w, 
     if (int rc = check_tsdf_frame(ctx, w, h, depth, color, volume->cfg.color_type, intrinsic, intrinsic_w, intrinsic_h, extrinsic, &f))
         return rc;
     volume->rows[0] = volume->rows[1] = -1;
+    volume->mesh_rows[0] = volume->mesh_rows[1] = -1;
     int rc = ctx->eng->tsdf_integrate(volume->id, f);
     return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
 }
@@ -1897,6 +1899,33 @@ int visma_icp_tsdf_get_voxel_point_cloud(visma_icp_ctx *ctx, visma_icp_tsdf *vol
 {
     CTX_CHECK();
     return tsdf_get_extract(ctx, volume, 1, points, nullptr, colors, n);
+}
+
+int visma_icp_tsdf_extract_triangle_mesh(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int64_t *out_nv, int64_t *out_nt)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (!out_nv || !out_nt) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out_nv = *out_nt = 0;
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "TSDF integration runs on one rank");
+    volume->mesh_rows[0] = volume->mesh_rows[1] = -1;
+    int rc = ctx->eng->tsdf_extract_mesh(volume->id, out_nv, out_nt);
+    if (rc) return ctx->eng_fail(rc);
+    volume->mesh_rows[0] = *out_nv; volume->mesh_rows[1] = *out_nt;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_tsdf_get_triangle_mesh(visma_icp_ctx *ctx, visma_icp_tsdf *volume, double *vertices, double *colors, int32_t *triangles,
+                                     int64_t nv, int64_t nt)
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "TSDF integration runs on one rank");
+    if (volume->mesh_rows[0] < 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no mesh: extract first");
+    if (nv != volume->mesh_rows[0] || nt != volume->mesh_rows[1])
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "nv or nt differs from the extraction's counts");
+    int rc = ctx->eng->tsdf_get_mesh(volume->id, vertices, colors, triangles);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
 }
 
 int visma_icp_tsdf_get_volume(visma_icp_ctx *ctx, visma_icp_tsdf *volume, const int32_t unit_index[3], float *tsdf, float *weight,

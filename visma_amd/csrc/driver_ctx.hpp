@@ -10,6 +10,7 @@ struct visma_icp_tsdf {
     int id = 0;
     TsdfConfig cfg;
     int64_t rows[2] = {-1, -1};       // [0] ExtractPointCloud, [1] ExtractVoxelPointCloud; -1: none since the last change
+    int64_t mesh_rows[2] = {-1, -1};  // ExtractTriangleMesh: vertices, triangles; -1: none since the last change
 };
 
 // a color map object of a context: the engine's id, what it was created with and how far its staged calls have come

@@ -411,6 +411,12 @@ public:
     virtual int tsdf_reset(int /* id */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     virtual int tsdf_integrate(int /* id */, const TsdfFrame &) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // ExtractPointCloud (voxel_cloud == 0) or ExtractVoxelPointCloud, left on the engine: the number of rows
+    virtual int tsdf_extract_mesh(int /* id */, int64_t * /* nv */, int64_t * /* nt */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    virtual int tsdf_get_mesh(int /* id */, double * /* vertices */, double * /* colors */, int32_t * /* triangles */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     virtual int tsdf_extract(int /* id */, int /* voxel_cloud */, int64_t * /* n */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // ... and its rows (n x 3 doubles each; normals and colors may be NULL)
     virtual int tsdf_get_extract(int /* id */, int /* voxel_cloud */, double * /* points */, double * /* normals */, double * /* colors */)

@@ -1124,6 +1124,26 @@ int HipEngine::tsdf_get_extract(int id, int voxel_cloud, double *points, double 
     return VISMA_ICP_OK;
 }
 
+int HipEngine::tsdf_extract_mesh(int id, int64_t *nv, int64_t *nt)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    const hipError_t e = tsdf_device_extract_mesh(D, nv, nt);
+    if (e == hipErrorInvalidValue) { (void)hipGetLastError(); err_ = "a mesh of more than 2^31 - 1 vertices or triangles"; return VISMA_ICP_ERR_INVALID; }
+    HIP_TRY(e);
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::tsdf_get_mesh(int id, double *vertices, double *colors, int32_t *triangles)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    HIP_TRY(tsdf_device_get_mesh(D, vertices, colors, triangles));
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::tsdf_get_units(int id, std::vector<int32_t> *keys)
 {
     TsdfDevice *D = nullptr;

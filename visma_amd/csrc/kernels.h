@@ -720,6 +720,12 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
 hipError_t tsdf_device_extract(TsdfDevice *D, int voxel_cloud, int64_t *n);
 // the rows of the last extraction of that kind (n x 3 doubles each; normals / colors may be NULL)
 hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *points, double *normals, double *colors);
+// ExtractTriangleMesh (marching cubes; the case rule: mc_table.h) into the device's mesh buffers: *nv vertices, *nt triangles.
+// hipErrorInvalidValue: more than 2^31 - 1 of either (vertex indices are int32).  Nothing is launched over a volume of
+// R < 2, or over a scalable volume without units.
+hipError_t tsdf_device_extract_mesh(TsdfDevice *D, int64_t *nv, int64_t *nt);
+// the rows of the last mesh (vertices, colors nv x 3 doubles, triangles nt x 3 int32; each may be NULL)
+hipError_t tsdf_device_get_mesh(TsdfDevice *D, double *vertices, double *colors, int32_t *triangles);
 // the indices of a scalable volume's units, 3 per unit, in lexicographic order (the order of its extractions)
 void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys);
 // tsdf, weight (R^3) and color (R^3 x 3, interleaved as the reference keeps it) of a uniform volume (unit == NULL) or of

@@ -29,10 +29,17 @@
 //               runs over the list of touched units -- the same kernel, a uniform volume being a list of one.  Extraction
 //               walks the units in lexicographic order of their index and reads a +1 neighbour or a corner of GetTSDFAt in
 //               the unit next door through a sorted key array (UnitList::find); a missing unit reads weight 0, tsdf 0.
+//  mesh         ExtractTriangleMesh: marching cubes, the 256 cases computed from a rule (mc_table.h).  cube_kernel writes a
+//               16-bit record per voxel (the case of the cube it is the base of), then two ordered compactions: the vertices
+//               (item = voxel, up to three edges; decided from the records of the cubes around an edge; positions and
+//               colours in f64 in the reference's order of operations) and the triangles (item = cube; a vertex index is the
+//               vertex pass's tile offset + a second 16-bit record).  Both volume kinds behind one corner fetch.
 // (Reasoning: DESIGN.md 4.4c11.)
 #include "kernels.h"
 #include "compact.h"
 #include "tsdf_units.h"
+#include "dev_buf.h"
+#include "mc_table.h"
 
 #include <algorithm>
 #include <cmath>
@@ -398,6 +405,207 @@ struct ScalableSurfaceSource {
     }
 };
 
+// ---- ExtractTriangleMesh: marching cubes (the case rule: mc_table.h; the semantics: visma_icp.h) ----
+// An item is a voxel in extraction order (unit in list order, then x R^2 + y R + z): the base of a cube and the lower end of
+// up to three vertex edges.  Three passes share two 16-bit records per item:
+//   cube_rec   cube_kernel: the cube's case (bits 0 .. 7), bit 8: the cube is valid, bit 9: the voxel's own weight is != 0
+//   vert_rec   the vertex pass's write: which of the voxel's +x, +y, +z edges carry a vertex (bits 0 .. 2) and the row of its
+//              first vertex within its tile of 256 items (bits 3 .. 12; at most 255 * 3)
+// so the vertex of an edge is tile_offset[item / 256] + (vert_rec >> 3) + the set mask bits below its axis: no hash.
+// The two grids are the corner fetch: where the neighbour of a voxel is, and its global index.
+struct UniformGrid {
+    int R;
+    static constexpr bool kOrigin = true;
+    __device__ void split(long long item, int &u, int &x, int &y, int &z) const
+    {
+        u = 0; z = (int)(item % R); y = (int)((item / R) % R); x = (int)(item / ((long long)R * R));
+    }
+    // the item at (x, y, z), each in [-1, R], or -1 beyond the volume
+    __device__ long long item_at(int, int x, int y, int z) const
+    {
+        if ((unsigned)x >= (unsigned)R || (unsigned)y >= (unsigned)R || (unsigned)z >= (unsigned)R) return -1;
+        return ((long long)x * R + y) * R + z;
+    }
+    __device__ long long voxel(long long item) const { return item; }
+    __device__ void index(int, int x, int y, int z, double g[3]) const { g[0] = (double)x; g[1] = (double)y; g[2] = (double)z; }
+};
+
+struct ScalableGrid {
+    UnitList units;
+    int R;
+    static constexpr bool kOrigin = false;
+    __device__ void split(long long item, int &u, int &x, int &y, int &z) const
+    {
+        const long long R3 = (long long)R * R * R, i = item % R3;
+        u = (int)(item / R3); z = (int)(i % R); y = (int)((i / R) % R); x = (int)(i / ((long long)R * R));
+    }
+    // ... of the unit at list position u; beyond the unit it is the neighbouring unit's, -1 where that does not exist
+    __device__ long long item_at(int u, int x, int y, int z) const
+    {
+        const int dx = x < 0 ? -1 : x >= R ? 1 : 0, dy = y < 0 ? -1 : y >= R ? 1 : 0, dz = z < 0 ? -1 : z >= R ? 1 : 0;
+        if (dx | dy | dz) {
+            const int *k = units.keys + 3 * u;
+            u = units.find(k[0] + dx, k[1] + dy, k[2] + dz);
+            if (u < 0) return -1;
+            x -= dx * R; y -= dy * R; z -= dz * R;
+        }
+        return (long long)u * R * R * R + ((long long)x * R + y) * R + z;
+    }
+    __device__ long long voxel(long long item) const
+    {
+        const long long R3 = (long long)R * R * R;
+        return units.slots[item / R3] * R3 + item % R3;
+    }
+    // the global voxel index
+    __device__ void index(int u, int x, int y, int z, double g[3]) const
+    {
+        const int *k = units.keys + 3 * u;
+        g[0] = (double)((long long)k[0] * R + x); g[1] = (double)((long long)k[1] * R + y); g[2] = (double)((long long)k[2] * R + z);
+    }
+};
+
+constexpr unsigned kCubeValid = 0x100, kCubeOwnWeight = 0x200;
+
+template <class Grid>
+struct MeshArgs {
+    Grid g;
+    const float *tsdf, *weight, *c0, *c1, *c2;
+    int color_type;
+    double vl, half, ox, oy, oz;
+    uint16_t *cube_rec, *vert_rec;
+    const McCase *table;
+    const long long *vert_tile_offset;                   // the vertex pass's tile offsets
+    double *vertices, *colors;
+    int *triangles;
+};
+
+// the cube of every item: most voxels have weight 0 and are decided by that one load
+template <class Grid>
+__global__ __launch_bounds__(kThreads) void cube_kernel(MeshArgs<Grid> a, long long n)
+{
+    for (long long item = (long long)blockIdx.x * kThreads + threadIdx.x; item < n; item += (long long)gridDim.x * kThreads) {
+        const long long v0 = a.g.voxel(item);
+        unsigned rec = 0;
+        if (a.weight[v0] != 0.0f) {
+            int u, x, y, z;
+            a.g.split(item, u, x, y, z);
+            unsigned cs = a.tsdf[v0] < 0.0f ? 1u : 0u;
+            bool valid = true;
+            for (int i = 1; i < 8 && valid; i++) {
+                const long long j = a.g.item_at(u, x + (i & 1), y + ((i >> 1) & 1), z + (i >> 2));
+                if (j < 0) { valid = false; break; }
+                const long long v = a.g.voxel(j);
+                if (a.weight[v] == 0.0f) { valid = false; break; }
+                if (a.tsdf[v] < 0.0f) cs |= 1u << i;
+            }
+            rec = kCubeOwnWeight | (valid ? (kCubeValid | cs) : 0u);
+        }
+        a.cube_rec[item] = (uint16_t)rec;
+    }
+}
+
+// the vertices: item = voxel, up to three rows (its +x, +y, +z edges)
+template <class Grid>
+struct MeshVertexSource {
+    MeshArgs<Grid> a;
+    // bit `axis`: the two ends differ in sign in a valid cube around the edge (any valid cube holds both ends' signs)
+    __device__ int mask(long long item) const
+    {
+        const unsigned own = a.cube_rec[item];
+        if (!(own & kCubeOwnWeight)) return 0;
+        int u, x, y, z;
+        a.g.split(item, u, x, y, z);
+        // the cubes at (x - i, y - j, z - k), i, j, k in {0, 1}; the one at (-1, -1, -1) holds none of the three edges
+        unsigned rec[2][2][2];
+        for (int i = 0; i < 2; i++)
+            for (int j = 0; j < 2; j++)
+                for (int k = 0; k < 2; k++) {
+                    rec[i][j][k] = 0;
+                    if (i + j + k == 0) { rec[0][0][0] = own; continue; }
+                    if (i + j + k == 3) continue;
+                    const long long c = a.g.item_at(u, x - i, y - j, z - k);
+                    if (c >= 0) rec[i][j][k] = a.cube_rec[c];
+                }
+        int m = 0;
+        for (int axis = 0; axis < 3; axis++) {
+            bool cut = false;
+            for (int i = 0; i < 2; i++)
+                for (int j = 0; j < 2; j++)
+                    for (int k = 0; k < 2; k++) {
+                        const int d[3] = {i, j, k};
+                        if (d[axis]) continue;
+                        const unsigned r = rec[i][j][k];
+                        if (!(r & kCubeValid)) continue;
+                        const int lo = i | (j << 1) | (k << 2);                // this voxel as a corner of that cube
+                        cut = cut || (((r >> lo) ^ (r >> (lo | (1 << axis)))) & 1u);
+                    }
+            if (cut) m |= 1 << axis;
+        }
+        return m;
+    }
+    __device__ int count(long long item) const { return __popc((unsigned)mask(item)); }
+
+    // f64, in the reference's order of operations (contraction is off for the whole build)
+    __device__ void emit(long long item, long long row) const
+    {
+        const int m = mask(item);
+        a.vert_rec[item] = (uint16_t)((unsigned)m | ((unsigned)(row - a.vert_tile_offset[item / kThreads]) << 3));
+        int u, x, y, z;
+        a.g.split(item, u, x, y, z);
+        const long long v0 = a.g.voxel(item);
+        const double f0 = fabs((double)a.tsdf[v0]);
+        double g[3];
+        a.g.index(u, x, y, z, g);
+        const double p0[3] = {a.half + a.vl * g[0], a.half + a.vl * g[1], a.half + a.vl * g[2]};
+        for (int axis = 0; axis < 3; axis++) {
+            if (!(m & (1 << axis))) continue;
+            const long long v1 = a.g.voxel(a.g.item_at(u, x + (axis == 0), y + (axis == 1), z + (axis == 2)));
+            const double f1 = fabs((double)a.tsdf[v1]);
+            double p[3] = {p0[0], p0[1], p0[2]};
+            p[axis] += f0 * a.vl / (f0 + f1);
+            if (Grid::kOrigin) { p[0] = p[0] + a.ox; p[1] = p[1] + a.oy; p[2] = p[2] + a.oz; }
+            a.vertices[3 * row] = p[0]; a.vertices[3 * row + 1] = p[1]; a.vertices[3 * row + 2] = p[2];
+            if (a.color_type == kTsdfColorRgb8) {
+                const float *plane[3] = {a.c0, a.c1, a.c2};
+                for (int c = 0; c < 3; c++) {
+                    const double k0 = (double)plane[c][v0] / 255.0, k1 = (double)plane[c][v1] / 255.0;
+                    a.colors[3 * row + c] = (f1 * k0 + f0 * k1) / (f0 + f1);
+                }
+            } else if (a.color_type == kTsdfColorGray32) {
+                const double k0 = (double)a.c0[v0], k1 = (double)a.c0[v1];
+                const double gray = (f1 * k0 + f0 * k1) / (f0 + f1);
+                a.colors[3 * row] = gray; a.colors[3 * row + 1] = gray; a.colors[3 * row + 2] = gray;
+            }
+            row++;
+        }
+    }
+};
+
+// the triangles: item = cube, the rows of its case
+template <class Grid>
+struct MeshTriangleSource {
+    MeshArgs<Grid> a;
+    __device__ int count(long long item) const
+    {
+        const unsigned r = a.cube_rec[item];
+        return (r & kCubeValid) ? a.table[r & 0xffu].n : 0;
+    }
+    __device__ void emit(long long item, long long row) const
+    {
+        const McCase cs = a.table[a.cube_rec[item] & 0xffu];
+        int u, x, y, z;
+        a.g.split(item, u, x, y, z);
+        long long corner[8];                             // (every corner of a valid cube exists)
+        for (int i = 0; i < 8; i++) corner[i] = i ? a.g.item_at(u, x + (i & 1), y + ((i >> 1) & 1), z + (i >> 2)) : item;
+        for (int t = 0; t < 3 * (int)cs.n; t++) {
+            const int e = cs.edge[t], axis = e >> 2;
+            const long long lower = corner[mc_edge_lower(e)];
+            const unsigned vr = a.vert_rec[lower];
+            a.triangles[3 * row + t] = (int)(a.vert_tile_offset[lower / kThreads] + (long long)(vr >> 3) + __popc(vr & ((1u << axis) - 1u)));
+        }
+    }
+};
+
 // CreatePointCloudFromFloatDepthImage / CreatePointCloudFromRGBDImageT: item = strided pixel, row-major
 struct DepthSource {
     const float *depth, *gray;
@@ -464,6 +672,15 @@ hipError_t grow(T **p, size_t *have, size_t want)
     return e;
 }
 
+int raw_alloc(void **p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
+    return (int)e;
+}
+void raw_free(void *p) { (void)hipFree(p); }
+const drv::RawAlloc kRaw = {raw_alloc, raw_free};
+
 #define TSDF_TRY(expr)                                   \
     do {                                                 \
         hipError_t e_ = (expr);                          \
@@ -498,6 +715,15 @@ struct TsdfDevice {
     double *out_points[2] = {nullptr, nullptr}, *out_normals = nullptr, *out_colors[2] = {nullptr, nullptr};
     size_t out_points_cap[2] = {0, 0}, out_normals_cap = 0, out_colors_cap[2] = {0, 0};
     long long rows[2] = {-1, -1};
+    // ExtractTriangleMesh: the second compaction (comp keeps the vertex pass's tile offsets for the triangle pass), the two
+    // records per item (4 transient bytes per voxel, grow-only), the case table, and the last mesh
+    bool integrated = false;                             // a frame went in since the creation or the last Reset()
+    Compactor comp_tri;
+    drv::DevBuf<uint16_t> cube_rec{kRaw}, vert_rec{kRaw};
+    drv::DevBuf<McCase> mc_cases{kRaw};
+    drv::DevBuf<double> mesh_vertices{kRaw}, mesh_colors{kRaw};
+    drv::DevBuf<int> mesh_triangles{kRaw};
+    long long mesh_nv = -1, mesh_nt = -1;
     int planes() const { return cfg.color_type == kTsdfColorRgb8 ? 3 : cfg.color_type == kTsdfColorGray32 ? 1 : 0; }
     double unit_length() const { return cfg.length; }
     double unit_voxel_length() const { return cfg.length / (double)cfg.resolution; }
@@ -573,6 +799,7 @@ void tsdf_device_destroy(TsdfDevice *D)
     for (void *p : all)
         if (p) (void)hipFree(p);
     D->comp.release();
+    D->comp_tri.release();
     delete D;
 }
 
@@ -580,6 +807,8 @@ void tsdf_device_destroy(TsdfDevice *D)
 hipError_t tsdf_device_reset(TsdfDevice *D)
 {
     D->rows[0] = D->rows[1] = -1;
+    D->mesh_nv = D->mesh_nt = -1;
+    D->integrated = false;
     D->slot_of.clear();
     const size_t bytes = sizeof(float) * D->R3 * D->capacity;
     TSDF_TRY(hipMemsetAsync(D->tsdf, 0, bytes, D->stream));
@@ -696,6 +925,8 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
     else integrate_kernel<kTsdfColorNone><<<blocks, kThreads, 0, D->stream>>>(a);
     TSDF_TRY(hipGetLastError());
     D->rows[0] = D->rows[1] = -1;
+    D->mesh_nv = D->mesh_nt = -1;
+    D->integrated = true;
     return hipStreamSynchronize(D->stream);
 }
 
@@ -755,6 +986,91 @@ hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *point
     if (points) TSDF_TRY(hipMemcpy(points, D->out_points[which], bytes, hipMemcpyDeviceToHost));
     if (normals && !voxel_cloud) TSDF_TRY(hipMemcpy(normals, D->out_normals, bytes, hipMemcpyDeviceToHost));
     if (colors && (voxel_cloud || D->planes() > 0)) TSDF_TRY(hipMemcpy(colors, D->out_colors[which], bytes, hipMemcpyDeviceToHost));
+    return hipSuccess;
+}
+
+namespace {
+
+#define TSDF_RESERVE(buf, count)                                               \
+    do { if (int rc_ = (buf).reserve(count)) return (hipError_t)rc_; } while (0)
+
+template <class Grid>
+hipError_t extract_mesh(TsdfDevice *D, MeshArgs<Grid> a, long long items, long long *nv, long long *nt)
+{
+    cube_kernel<Grid><<<capped_blocks(items), kThreads, 0, D->stream>>>(a, items);
+    TSDF_TRY(hipGetLastError());
+    MeshVertexSource<Grid> vs = {a};
+    TSDF_TRY(D->comp.count(vs, items, D->stream, nv));
+    if (*nv > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (*nv == 0) return hipSuccess;                     // no vertex, no triangle
+    TSDF_RESERVE(D->mesh_vertices, 3 * (size_t)*nv);
+    if (D->planes() > 0) TSDF_RESERVE(D->mesh_colors, 3 * (size_t)*nv);
+    vs.a.vertices = D->mesh_vertices.get(); vs.a.colors = D->mesh_colors.get();
+    vs.a.vert_tile_offset = D->comp.tile_offset;
+    TSDF_TRY(D->comp.write(vs, items, D->stream));
+    MeshTriangleSource<Grid> ts = {vs.a};
+    TSDF_TRY(D->comp_tri.count(ts, items, D->stream, nt));
+    if (*nt > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (*nt == 0) return hipSuccess;
+    TSDF_RESERVE(D->mesh_triangles, 3 * (size_t)*nt);
+    ts.a.triangles = D->mesh_triangles.get();
+    return D->comp_tri.write(ts, items, D->stream);
+}
+
+}  // namespace
+
+hipError_t tsdf_device_extract_mesh(TsdfDevice *D, int64_t *nv, int64_t *nt)
+{
+    const TsdfConfig &c = D->cfg;
+    D->mesh_nv = D->mesh_nt = -1;
+    *nv = *nt = 0;
+    long long n_vertices = 0, n_triangles = 0;
+    // nothing is launched over a volume without a cube or without a frame
+    const bool empty = !D->integrated || (c.scalable ? D->slot_of.empty() : c.resolution < 2);
+    if (!empty) {
+        UnitList units;
+        TSDF_TRY(upload_unit_list(D, &units));
+        const long long items = (long long)D->R3 * units.n;
+        TSDF_RESERVE(D->cube_rec, (size_t)items);
+        TSDF_RESERVE(D->vert_rec, (size_t)items);
+        if (!D->mc_cases) {
+            const McTable &t = mc_table();
+            for (const McCase &cs : t.c)
+                if (cs.n > kMcMaxTriangles) return hipErrorUnknown;          // (the rule gave more than a row holds: never)
+            TSDF_RESERVE(D->mc_cases, 256);
+            const hipError_t e = hipMemcpyAsync(D->mc_cases.get(), t.c, sizeof(t.c), hipMemcpyHostToDevice, D->stream);   // (a static table)
+            if (e != hipSuccess) { D->mc_cases.release(); return e; }
+        }
+        hipError_t e;
+        if (c.scalable) {
+            MeshArgs<ScalableGrid> a = {{units, c.resolution}, D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], c.color_type,
+                                        c.voxel_length, c.voxel_length * 0.5, 0.0, 0.0, 0.0, D->cube_rec.get(), D->vert_rec.get(),
+                                        D->mc_cases.get(), nullptr, nullptr, nullptr, nullptr};
+            e = extract_mesh(D, a, items, &n_vertices, &n_triangles);
+        } else {
+            const double vl = D->unit_voxel_length();
+            MeshArgs<UniformGrid> a = {{c.resolution}, D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], c.color_type,
+                                       vl, vl * 0.5, c.origin[0], c.origin[1], c.origin[2], D->cube_rec.get(), D->vert_rec.get(),
+                                       D->mc_cases.get(), nullptr, nullptr, nullptr, nullptr};
+            e = extract_mesh(D, a, items, &n_vertices, &n_triangles);
+        }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(D->stream); return e; }
+        TSDF_TRY(hipStreamSynchronize(D->stream));
+    }
+    D->mesh_nv = n_vertices; D->mesh_nt = n_triangles;
+    *nv = (int64_t)n_vertices; *nt = (int64_t)n_triangles;
+    return hipSuccess;
+}
+
+hipError_t tsdf_device_get_mesh(TsdfDevice *D, double *vertices, double *colors, int32_t *triangles)
+{
+    if (D->mesh_nv > 0) {
+        const size_t bytes = sizeof(double) * 3 * (size_t)D->mesh_nv;
+        if (vertices) TSDF_TRY(hipMemcpy(vertices, D->mesh_vertices.get(), bytes, hipMemcpyDeviceToHost));
+        if (colors && D->planes() > 0) TSDF_TRY(hipMemcpy(colors, D->mesh_colors.get(), bytes, hipMemcpyDeviceToHost));
+    }
+    if (D->mesh_nt > 0 && triangles)
+        TSDF_TRY(hipMemcpy(triangles, D->mesh_triangles.get(), sizeof(int32_t) * 3 * (size_t)D->mesh_nt, hipMemcpyDeviceToHost));
     return hipSuccess;
 }
 
