@@ -30,6 +30,8 @@ public:
     void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) override;
     std::shared_ptr<PointCloud> ExtractPointCloud() override;
     std::shared_ptr<TriangleMesh> ExtractTriangleMesh() override;
+    visma_icp_ctx *Context() const override { return ctx_; }
+    visma_icp_tsdf *Handle() const override { return volume_; }
     std::shared_ptr<PointCloud> ExtractVoxelPointCloud();
     // the indices of the open units, in lexicographic order
     std::vector<Eigen::Vector3i> Units() const;

@@ -11,6 +11,9 @@
 #include "../Geometry/RGBDImage.h"
 #include "../Geometry/TriangleMesh.h"
 
+struct visma_icp_ctx;
+struct visma_icp_tsdf;
+
 namespace open3d {
 
 enum class TSDFVolumeColorType { None = 0, RGB8 = 1, Gray32 = 2 };
@@ -30,6 +33,10 @@ public:
     // marching cubes: vertices_, vertex_colors_ (empty without colour) and triangles_.  The vertices and their colours are the
     // reference's; their order and the triangulation of a cube are this library's (visma_icp.h: THE ORDER, THE CASE RULE)
     virtual std::shared_ptr<TriangleMesh> ExtractTriangleMesh() = 0;
+    // the resident volume's context and handle: what cicp::ExtractTriangleMesh(volume, purge, vertex_normals) and
+    // cicp::DeviceTriangleMesh::FromVolume take the extracted mesh through WITHOUT a host copy (visma_icp_open3d.hpp)
+    virtual visma_icp_ctx *Context() const = 0;
+    virtual visma_icp_tsdf *Handle() const = 0;
 
     double voxel_length_;
     double sdf_trunc_;

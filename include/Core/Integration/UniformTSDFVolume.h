@@ -29,6 +29,8 @@ public:
     void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) override;
     std::shared_ptr<PointCloud> ExtractPointCloud() override;
     std::shared_ptr<TriangleMesh> ExtractTriangleMesh() override;
+    visma_icp_ctx *Context() const override { return ctx_; }
+    visma_icp_tsdf *Handle() const override { return volume_; }
     // every voxel with a weight and a tsdf in [-0.98, 0.98): its centre, coloured (tsdf + 1) / 2
     std::shared_ptr<PointCloud> ExtractVoxelPointCloud();
     // the reference's tsdf_, weight_ (voxel_num_ floats) and color_ (voxel_num_ entries, empty without colour)

@@ -1633,6 +1633,84 @@ VISMA_ICP_API int visma_icp_kdtree_search_radius(visma_icp_kdtree *tree, const d
 VISMA_ICP_API int visma_icp_kdtree_get_radius_result(visma_icp_kdtree *tree, int32_t *idx, double *d2);
 /* Errors of a tree's calls are its context's: visma_icp_last_error(ctx). */
 
+/* ---- TriangleMesh: normals, Purge, select, crop and Transform over a mesh resident on the device -------------------------
+ * (the reference's Core/Geometry/TriangleMesh.cpp and .h, DownSample.cpp :107-177 and :256-274, Eigen's Dot.h for
+ * normalize().)  What follows ExtractTriangleMesh in the reference pipeline, without a host round trip.  A mesh is an object
+ * owned by its context; it lives until visma_icp_trimesh_destroy or the context's end and holds on the device: vertices
+ * (nv x 3 f64), optional vertex normals and vertex colours (nv x 3 f64), triangles (nt x 3 int32), optional triangle
+ * normals (nt x 3 f64).  "Has X" is the reference's HasX(): an attribute of no rows is not had.  Empty meshes are legal
+ * everywhere and launch nothing.
+ *
+ * EVERY RESULT IS THE REFERENCE'S BIT FOR BIT, and a second identical call returns identical bytes: f64, every product,
+ * difference and sum rounded on its own (no fused multiply-add: the reference is built for plain x86-64), correctly rounded
+ * square root and division, every sum in the reference's serial order; no floating-point atomics, one writer per row.
+ *   triangle normals  (v1 - v0) x (v2 - v0) by Eigen's component formula (y z' - z y', z x' - x z', x y' - y x').
+ *   normalize_normals per vector, vertex and triangle normals alike: n2 = (x x + y y) + z z; if n2 > 0 every component is
+ *                     divided by sqrt(n2), else the vector is left as it is (a zero vector stays zero; one whose n2 overflows
+ *                     is divided by inf); then, if x -- and only x -- is NaN, the vector becomes (0, 0, 1): a vector whose
+ *                     y alone is NaN stays.  compute_*_normals(normalized != 0) end in this call, which, as in the
+ *                     reference, normalises BOTH kinds of normals the mesh has.
+ *   vertex normals    every triangle's normal is added to its three corners in triangle order, then corner order: the sum of
+ *                     a vertex has that fixed order (an incidence list by one stable radix sort; one lane per vertex walks
+ *                     its list -- a vertex shared by very many triangles is summed by ONE lane: the price of the
+ *                     reference's order).  A degenerate triangle (a, a, b) adds twice to a.  Two behaviours of the reference
+ *                     are kept: triangle normals the mesh already HAS are used as they are (normalised or not), else
+ *                     unnormalised ones are computed and kept; vertex normals the mesh already HAS are ADDED ONTO (the
+ *                     reference's resize(n, Zero) does not reset), else the sums start from zero.
+ *   remove_duplicated_vertices   two vertices are the same iff all three coordinates compare == as doubles (-0.0 == 0.0;
+ *                     a vertex with a NaN coordinate equals nothing, itself included).  The lowest index of a group stays,
+ *                     with its normal and colour; survivors keep their order; triangles are remapped.
+ *   remove_duplicated_triangles  the key is the reference's rotation to the smallest index with its <= ties as written:
+ *                     (0,1,2), (1,2,0), (2,0,1) share a key, (0,2,1) does not, and (0,1,0) and (0,0,1) do not although one
+ *                     is a rotation of the other.  The first occurrence stays, with its corner order and its normal.
+ *   remove_non_manifold_triangles  a triangle with two equal indices goes.
+ *   remove_non_manifold_vertices   a vertex no triangle uses goes; triangles are remapped.
+ *   purge             the four in this order; removed[4] in this order.
+ *   select            a NEW mesh: the triangles whose three corners are among indices[] (duplicates change nothing), the
+ *                     vertices those triangles use, order kept, attributes carried; then purged.
+ *   crop              min_bound[k] > max_bound[k] for some k: an empty mesh.  Else select over the vertices with
+ *                     min <= p <= max in every component, bounds included; a NaN, in a vertex or a bound, fails every test.
+ *   transform         T row-major 4 x 4: a row is ((T_i0 x + T_i1 y) + T_i2 z) + T_i3 w, w = 1 for vertices and w = 0 for
+ *                     both kinds of normals (T_i3 * 0 is added: a NaN or infinite translation reaches the normals, as in
+ *                     the reference); the fourth row of T is not read.
+ * from_tsdf copies the LAST EXTRACTED mesh of a volume device to device: the volume's colours become vertex colours, there
+ * are no normals; VISMA_ICP_ERR_STATE before an extract (or after a frame or a reset), VISMA_ICP_ERR_INVALID for a volume
+ * of another context.  get: each output may be NULL; counts other than the mesh's are VISMA_ICP_ERR_INVALID, asking for an
+ * attribute the mesh does not have VISMA_ICP_ERR_STATE.  size: has_flags is a mask of VISMA_ICP_TRIMESH_HAS_*.
+ *
+ * DEVIATION from the reference, on purpose: every triangle index is checked on the device before a mesh exists, and every
+ * selected index before a select; one outside [0, nv) is VISMA_ICP_ERR_INVALID (the reference reads out of bounds).  No
+ * kernel indexes a vertex array with an index that has not passed that check.
+ * Limits: nv, nt and 3 nt must each fit an int (the sorts take an int count), else VISMA_ICP_ERR_INVALID before anything is
+ * allocated.  A sharded context: VISMA_ICP_ERR_INVALID, as for the TSDF volumes.  A mesh of another context:
+ * VISMA_ICP_ERR_INVALID.  Memory: the mesh, and while a call runs about as much again (a compaction writes new arrays). */
+#define VISMA_ICP_TRIMESH_HAS_VERTEX_NORMALS 1
+#define VISMA_ICP_TRIMESH_HAS_VERTEX_COLORS 2
+#define VISMA_ICP_TRIMESH_HAS_TRIANGLE_NORMALS 4
+typedef struct visma_icp_trimesh visma_icp_trimesh;
+VISMA_ICP_API int visma_icp_trimesh_create(visma_icp_ctx *ctx, const double *vertices, int64_t nv, const double *vertex_normals,
+                                           const double *vertex_colors, const int32_t *triangles, int64_t nt,
+                                           const double *triangle_normals, visma_icp_trimesh **out);
+VISMA_ICP_API int visma_icp_trimesh_from_tsdf(visma_icp_ctx *ctx, visma_icp_tsdf *volume, visma_icp_trimesh **out);
+VISMA_ICP_API int visma_icp_trimesh_destroy(visma_icp_ctx *ctx, visma_icp_trimesh *mesh);
+VISMA_ICP_API int visma_icp_trimesh_size(const visma_icp_trimesh *mesh, int64_t *nv, int64_t *nt, int *has_flags);
+VISMA_ICP_API int visma_icp_trimesh_get(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, double *vertices, double *vertex_normals,
+                                        double *vertex_colors, int32_t *triangles, double *triangle_normals, int64_t nv, int64_t nt);
+VISMA_ICP_API int visma_icp_trimesh_compute_triangle_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int normalized);
+VISMA_ICP_API int visma_icp_trimesh_compute_vertex_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int normalized);
+VISMA_ICP_API int visma_icp_trimesh_normalize_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh);
+/* the four steps of Purge; *removed (may be NULL): the rows the step removed */
+VISMA_ICP_API int visma_icp_trimesh_remove_duplicated_vertices(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed);
+VISMA_ICP_API int visma_icp_trimesh_remove_duplicated_triangles(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed);
+VISMA_ICP_API int visma_icp_trimesh_remove_non_manifold_triangles(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed);
+VISMA_ICP_API int visma_icp_trimesh_remove_non_manifold_vertices(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed);
+VISMA_ICP_API int visma_icp_trimesh_purge(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t removed[4]);
+VISMA_ICP_API int visma_icp_trimesh_select(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const int64_t *indices, int64_t n,
+                                           visma_icp_trimesh **out);
+VISMA_ICP_API int visma_icp_trimesh_crop(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const double min_bound[3],
+                                         const double max_bound[3], visma_icp_trimesh **out);
+VISMA_ICP_API int visma_icp_trimesh_transform(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const double T[16]);
+
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

@@ -2025,6 +2025,191 @@ inline int KDTreeSearchRadius(const KDTreeFlann &tree, const std::vector<Eigen::
                   "visma_icp_kdtree_get_radius_result");
     return (int)nq;
 }
+
+// ---- open3d::TriangleMesh on the GPU (visma_icp.h, "TriangleMesh") ----
+// DeviceTriangleMesh: a mesh resident on the device, for a chain of steps with one upload and one download -- or none: the
+// mesh a TSDF volume extracted is taken where it lies (FromVolume).  The members of open3d::TriangleMesh and the free
+// functions below are one such chain each.  An index outside [0, vertices) throws std::runtime_error.
+class DeviceTriangleMesh {
+public:
+    DeviceTriangleMesh(visma_icp_ctx *ctx, const TriangleMesh &mesh) : ctx_(ctx)
+    {
+        const size_t nv = mesh.vertices_.size(), nt = mesh.triangles_.size();
+        static_assert(sizeof(Eigen::Vector3i) == 3 * sizeof(int32_t), "triangles are uploaded as they lie");
+        detail::check(ctx_, visma_icp_trimesh_create(ctx_, detail::xyz(mesh.vertices_), (int64_t)nv,
+                                                     mesh.HasVertexNormals() ? detail::xyz(mesh.vertex_normals_) : nullptr,
+                                                     mesh.HasVertexColors() ? detail::xyz(mesh.vertex_colors_) : nullptr,
+                                                     nt ? mesh.triangles_[0].data() : nullptr, (int64_t)nt,
+                                                     mesh.HasTriangleNormals() ? detail::xyz(mesh.triangle_normals_) : nullptr, &mesh_),
+                      "visma_icp_trimesh_create");
+    }
+    explicit DeviceTriangleMesh(const TriangleMesh &mesh) : DeviceTriangleMesh(detail::ThreadContext::instance().get(), mesh) {}
+    // the volume's last extracted mesh, copied device to device (ExtractTriangleMesh first: cicp::ExtractTriangleMesh does both)
+    static DeviceTriangleMesh FromVolume(const TSDFVolume &volume)
+    {
+        DeviceTriangleMesh m(volume.Context(), nullptr);
+        detail::check(m.ctx_, visma_icp_trimesh_from_tsdf(m.ctx_, volume.Handle(), &m.mesh_), "visma_icp_trimesh_from_tsdf");
+        return m;
+    }
+    ~DeviceTriangleMesh() { if (mesh_) (void)visma_icp_trimesh_destroy(ctx_, mesh_); }
+    DeviceTriangleMesh(DeviceTriangleMesh &&o) noexcept : ctx_(o.ctx_), mesh_(o.mesh_) { o.mesh_ = nullptr; }
+    DeviceTriangleMesh(const DeviceTriangleMesh &) = delete;
+    DeviceTriangleMesh &operator=(const DeviceTriangleMesh &) = delete;
+
+    void NormalizeNormals() { detail::check(ctx_, visma_icp_trimesh_normalize_normals(ctx_, mesh_), "visma_icp_trimesh_normalize_normals"); }
+    void ComputeTriangleNormals(bool normalized = true)
+    {
+        detail::check(ctx_, visma_icp_trimesh_compute_triangle_normals(ctx_, mesh_, normalized), "visma_icp_trimesh_compute_triangle_normals");
+    }
+    void ComputeVertexNormals(bool normalized = true)
+    {
+        detail::check(ctx_, visma_icp_trimesh_compute_vertex_normals(ctx_, mesh_, normalized), "visma_icp_trimesh_compute_vertex_normals");
+    }
+    void Transform(const Eigen::Matrix4d &T)
+    {
+        double t[16];
+        for (int i = 0; i < 16; i++) t[i] = T(i / 4, i % 4);          // (either storage order)
+        detail::check(ctx_, visma_icp_trimesh_transform(ctx_, mesh_, t), "visma_icp_trimesh_transform");
+    }
+    // -> the rows Purge's four steps removed
+    std::vector<int64_t> Purge()
+    {
+        std::vector<int64_t> removed(4, 0);
+        detail::check(ctx_, visma_icp_trimesh_purge(ctx_, mesh_, removed.data()), "visma_icp_trimesh_purge");
+        return removed;
+    }
+    DeviceTriangleMesh Select(const std::vector<size_t> &indices) const
+    {
+        const std::vector<int64_t> idx(indices.begin(), indices.end());
+        DeviceTriangleMesh out(ctx_, nullptr);
+        detail::check(ctx_, visma_icp_trimesh_select(ctx_, mesh_, idx.data(), (int64_t)idx.size(), &out.mesh_), "visma_icp_trimesh_select");
+        return out;
+    }
+    DeviceTriangleMesh Crop(const Eigen::Vector3d &min_bound, const Eigen::Vector3d &max_bound) const
+    {
+        DeviceTriangleMesh out(ctx_, nullptr);
+        detail::check(ctx_, visma_icp_trimesh_crop(ctx_, mesh_, min_bound.data(), max_bound.data(), &out.mesh_), "visma_icp_trimesh_crop");
+        return out;
+    }
+    // the device's rows into `mesh`: every attribute the device mesh has; one it does not have is left as it is where
+    // keep_others (what the reference's in-place members do to arrays that do not fit the mesh), else cleared
+    void Download(TriangleMesh &mesh, bool keep_others = false) const
+    {
+        int64_t nv = 0, nt = 0;
+        int has = 0;
+        detail::check(ctx_, visma_icp_trimesh_size(mesh_, &nv, &nt, &has), "visma_icp_trimesh_size");
+        const bool vn = has & VISMA_ICP_TRIMESH_HAS_VERTEX_NORMALS, vc = has & VISMA_ICP_TRIMESH_HAS_VERTEX_COLORS,
+                   tn = has & VISMA_ICP_TRIMESH_HAS_TRIANGLE_NORMALS;
+        mesh.vertices_.resize((size_t)nv);
+        mesh.triangles_.resize((size_t)nt);
+        if (vn) mesh.vertex_normals_.resize((size_t)nv); else if (!keep_others) mesh.vertex_normals_.clear();
+        if (vc) mesh.vertex_colors_.resize((size_t)nv); else if (!keep_others) mesh.vertex_colors_.clear();
+        if (tn) mesh.triangle_normals_.resize((size_t)nt); else if (!keep_others) mesh.triangle_normals_.clear();
+        detail::check(ctx_, visma_icp_trimesh_get(ctx_, mesh_, nv ? mesh.vertices_[0].data() : nullptr, vn ? mesh.vertex_normals_[0].data() : nullptr,
+                                                  vc ? mesh.vertex_colors_[0].data() : nullptr, nt ? mesh.triangles_[0].data() : nullptr,
+                                                  tn ? mesh.triangle_normals_[0].data() : nullptr, nv, nt),
+                      "visma_icp_trimesh_get");
+    }
+    std::shared_ptr<TriangleMesh> Download() const
+    {
+        auto out = std::make_shared<TriangleMesh>();
+        Download(*out);
+        return out;
+    }
+    visma_icp_ctx *context() const { return ctx_; }
+    visma_icp_trimesh *handle() const { return mesh_; }
+
+private:
+    DeviceTriangleMesh(visma_icp_ctx *ctx, std::nullptr_t) : ctx_(ctx) {}
+    visma_icp_ctx *ctx_ = nullptr;
+    visma_icp_trimesh *mesh_ = nullptr;
+};
+
+namespace detail {
+// rows that are no attribute of a consistent mesh (the reference's NormalizeNormals and Transform walk vertex_normals_ and
+// triangle_normals_ whatever their sizes): as the vertex normals of a mesh of as many vertices and no triangle
+template <class Op>
+inline void trimesh_normal_rows(visma_icp_ctx *ctx, std::vector<Eigen::Vector3d> &rows, Op op)
+{
+    if (rows.empty()) return;
+    TriangleMesh carrier;
+    carrier.vertices_ = rows;
+    carrier.vertex_normals_ = rows;
+    DeviceTriangleMesh d(ctx, carrier);
+    op(d);
+    d.Download(carrier);
+    rows = carrier.vertex_normals_;
+}
+// the whole mesh through one step on the device; normals whose size does not fit the mesh go through `rows_op` on their own
+template <class Op>
+inline void trimesh_in_place(visma_icp_ctx *ctx, TriangleMesh &mesh, bool normals_too, Op op)
+{
+    const bool had_vn = mesh.HasVertexNormals(), had_vc = mesh.HasVertexColors(), had_tn = mesh.HasTriangleNormals();
+    const bool loose_vn = normals_too && !had_vn, loose_tn = normals_too && !had_tn;
+    DeviceTriangleMesh d(ctx, mesh);
+    op(d);
+    d.Download(mesh, true);
+    // (an attribute the mesh had shrinks with it, to no rows too)
+    if (had_vn && !mesh.HasVertexNormals()) mesh.vertex_normals_.resize(mesh.vertices_.size());
+    if (had_vc && !mesh.HasVertexColors()) mesh.vertex_colors_.resize(mesh.vertices_.size());
+    if (had_tn && !mesh.HasTriangleNormals()) mesh.triangle_normals_.resize(mesh.triangles_.size());
+    if (loose_vn) trimesh_normal_rows(ctx, mesh.vertex_normals_, op);
+    if (loose_tn) trimesh_normal_rows(ctx, mesh.triangle_normals_, op);
+}
+}  // namespace detail
+
+// the members of open3d::TriangleMesh on a context of the caller's
+inline void NormalizeNormals(visma_icp_ctx *ctx, TriangleMesh &mesh)
+{
+    detail::trimesh_in_place(ctx, mesh, true, [](DeviceTriangleMesh &d) { d.NormalizeNormals(); });
+}
+inline void Transform(visma_icp_ctx *ctx, TriangleMesh &mesh, const Eigen::Matrix4d &T)
+{
+    detail::trimesh_in_place(ctx, mesh, true, [&T](DeviceTriangleMesh &d) { d.Transform(T); });
+}
+inline void ComputeTriangleNormals(visma_icp_ctx *ctx, TriangleMesh &mesh, bool normalized = true)
+{
+    // (TriangleMesh.cpp:148: the normals are resized, then every row is written; vertex normals that do not fit the mesh are
+    //  normalised all the same)
+    const bool loose_vn = normalized && !mesh.HasVertexNormals();
+    mesh.triangle_normals_.clear();
+    detail::trimesh_in_place(ctx, mesh, false, [normalized](DeviceTriangleMesh &d) { d.ComputeTriangleNormals(normalized); });
+    if (!mesh.HasTriangleNormals()) mesh.triangle_normals_.resize(mesh.triangles_.size());      // (a mesh without vertices)
+    if (loose_vn) detail::trimesh_normal_rows(ctx, mesh.vertex_normals_, [](DeviceTriangleMesh &d) { d.NormalizeNormals(); });
+}
+inline void ComputeVertexNormals(visma_icp_ctx *ctx, TriangleMesh &mesh, bool normalized = true)
+{
+    // (TriangleMesh.cpp:162-165: triangle normals that fit are used as they are; resize(n, Zero) keeps the rows that exist)
+    if (!mesh.HasTriangleNormals()) mesh.triangle_normals_.clear();
+    mesh.vertex_normals_.resize(mesh.vertices_.size(), Eigen::Vector3d::Zero());
+    detail::trimesh_in_place(ctx, mesh, false, [normalized](DeviceTriangleMesh &d) { d.ComputeVertexNormals(normalized); });
+    if (!mesh.HasTriangleNormals()) mesh.triangle_normals_.resize(mesh.triangles_.size());
+}
+inline void Purge(visma_icp_ctx *ctx, TriangleMesh &mesh)
+{
+    detail::trimesh_in_place(ctx, mesh, false, [](DeviceTriangleMesh &d) { d.Purge(); });
+}
+inline std::shared_ptr<TriangleMesh> SelectDownSample(visma_icp_ctx *ctx, const TriangleMesh &input, const std::vector<size_t> &indices)
+{
+    return DeviceTriangleMesh(ctx, input).Select(indices).Download();
+}
+inline std::shared_ptr<TriangleMesh> CropTriangleMesh(visma_icp_ctx *ctx, const TriangleMesh &input, const Eigen::Vector3d &min_bound,
+                                                      const Eigen::Vector3d &max_bound)
+{
+    return DeviceTriangleMesh(ctx, input).Crop(min_bound, max_bound).Download();
+}
+// ExtractTriangleMesh and what follows it in the reference pipeline, on the device, with ONE download: the volume's mesh is
+// copied device to device, purged where asked, and given vertex normals (ComputeVertexNormals(normalized)) where asked
+inline std::shared_ptr<TriangleMesh> ExtractTriangleMesh(TSDFVolume &volume, bool purge, bool vertex_normals, bool normalized = true)
+{
+    int64_t nv = 0, nt = 0;
+    detail::check(volume.Context(), visma_icp_tsdf_extract_triangle_mesh(volume.Context(), volume.Handle(), &nv, &nt),
+                  "visma_icp_tsdf_extract_triangle_mesh");
+    DeviceTriangleMesh d = DeviceTriangleMesh::FromVolume(volume);
+    if (purge) d.Purge();
+    if (vertex_normals) d.ComputeVertexNormals(normalized);
+    return d.Download();
+}
 #endif
 
 }  // namespace cicp
@@ -2046,6 +2231,29 @@ inline std::shared_ptr<PointCloud> CreatePointCloudFromRGBDImage(const RGBDImage
                                                                  const Eigen::Matrix4d &extrinsic)
 {
     return cicp::CreatePointCloudFromRGBDImage(image, intrinsic, extrinsic);
+}
+// open3d::TriangleMesh (Core/Geometry/TriangleMesh.h): the members that compute, on this thread's context
+inline void TriangleMesh::NormalizeNormals() { cicp::NormalizeNormals(cicp::detail::ThreadContext::instance().get(), *this); }
+inline void TriangleMesh::Transform(const Eigen::Matrix4d &transformation)
+{
+    cicp::Transform(cicp::detail::ThreadContext::instance().get(), *this, transformation);
+}
+inline void TriangleMesh::ComputeTriangleNormals(bool normalized)
+{
+    cicp::ComputeTriangleNormals(cicp::detail::ThreadContext::instance().get(), *this, normalized);
+}
+inline void TriangleMesh::ComputeVertexNormals(bool normalized)
+{
+    cicp::ComputeVertexNormals(cicp::detail::ThreadContext::instance().get(), *this, normalized);
+}
+inline void TriangleMesh::Purge() { cicp::Purge(cicp::detail::ThreadContext::instance().get(), *this); }
+inline std::shared_ptr<TriangleMesh> SelectDownSample(const TriangleMesh &input, const std::vector<size_t> &indices)
+{
+    return cicp::SelectDownSample(cicp::detail::ThreadContext::instance().get(), input, indices);
+}
+inline std::shared_ptr<TriangleMesh> CropTriangleMesh(const TriangleMesh &input, const Eigen::Vector3d &min_bound, const Eigen::Vector3d &max_bound)
+{
+    return cicp::CropTriangleMesh(cicp::detail::ThreadContext::instance().get(), input, min_bound, max_bound);
 }
 // open3d::KDTreeFlann (Core/Geometry/KDTreeFlann.h): the tree is an object of the context, resident on the GPU
 inline KDTreeFlann::~KDTreeFlann()

@@ -202,6 +202,13 @@ class TsdfVolume:
                                                                   _p(tri, _ip), nv, nt))
         return vtx, col, tri
 
+    def triangle_mesh(self):
+        """The last extracted mesh as a TriMesh, copied device to device (visma_icp_trimesh_from_tsdf): the volume's colours
+        are its vertex colours, it has no normals.  Before an extract_triangle_mesh(): IcpError (state)."""
+        m = C.c_void_p()
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_from_tsdf(self.ctx._h, self._v, C.byref(m)))
+        return TriMesh(self.ctx, m)
+
     def units(self):
         """The unit indices of a scalable volume (n x 3 int32) in lexicographic order: the order of its extractions."""
         n = C.c_int64(0)
@@ -220,6 +227,102 @@ class TsdfVolume:
         self.ctx._chk(self.ctx.L.visma_icp_tsdf_get_volume(self.ctx._h, self._v, None if unit is None else _p(unit, _ip), _p(tsdf, _fp), _p(weight, _fp),
                                                            None if color is None else _p(color, _fp)))
         return tsdf, weight, color
+
+
+TRIMESH_HAS_VERTEX_NORMALS, TRIMESH_HAS_VERTEX_COLORS, TRIMESH_HAS_TRIANGLE_NORMALS = 1, 2, 4
+
+
+class TriMesh:
+    """Open3D's TriangleMesh resident on the device (visma_icp_trimesh; Context.trimesh, TsdfVolume.triangle_mesh): normals,
+    Purge, select, crop and Transform, every result the reference's bit for bit (include/visma_icp.h has the rules).  Lives
+    until close() or the context's end; usable as a context manager."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._m = ctx, handle
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self._m is not None and self.ctx._h:
+            self.ctx._chk(self.ctx.L.visma_icp_trimesh_destroy(self.ctx._h, self._m))
+        self._m = None
+
+    def size(self):
+        """-> nv, nt, has_flags (a mask of TRIMESH_HAS_*)"""
+        nv, nt, f = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_size(self._m, C.byref(nv), C.byref(nt), C.byref(f)))
+        return nv.value, nt.value, f.value
+
+    def get(self):
+        """-> dict(vertices nv x 3 f64, triangles nt x 3 int32, vertex_normals, vertex_colors, triangle_normals: f64 rows, or
+        None for what the mesh does not have)"""
+        nv, nt, f = self.size()
+        out = dict(vertices=np.empty((nv, 3)), triangles=np.empty((nt, 3), np.int32),
+                   vertex_normals=np.empty((nv, 3)) if f & TRIMESH_HAS_VERTEX_NORMALS else None,
+                   vertex_colors=np.empty((nv, 3)) if f & TRIMESH_HAS_VERTEX_COLORS else None,
+                   triangle_normals=np.empty((nt, 3)) if f & TRIMESH_HAS_TRIANGLE_NORMALS else None)
+        dp = lambda k: None if out[k] is None else _p(out[k], _dp)
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_get(self.ctx._h, self._m, dp("vertices"), dp("vertex_normals"), dp("vertex_colors"),
+                                                       _p(out["triangles"], _ip), dp("triangle_normals"), nv, nt))
+        return out
+
+    def compute_triangle_normals(self, normalized=True):
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_compute_triangle_normals(self.ctx._h, self._m, int(bool(normalized))))
+
+    def compute_vertex_normals(self, normalized=True):
+        """ComputeVertexNormals: triangle normals the mesh has are used as they are, vertex normals it has are added onto"""
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_compute_vertex_normals(self.ctx._h, self._m, int(bool(normalized))))
+
+    def normalize_normals(self):
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_normalize_normals(self.ctx._h, self._m))
+
+    def _remove(self, call):
+        r = C.c_int64(0)
+        self.ctx._chk(call(self.ctx._h, self._m, C.byref(r)))
+        return r.value
+
+    def remove_duplicated_vertices(self):
+        """-> the number of vertices removed"""
+        return self._remove(self.ctx.L.visma_icp_trimesh_remove_duplicated_vertices)
+
+    def remove_duplicated_triangles(self):
+        return self._remove(self.ctx.L.visma_icp_trimesh_remove_duplicated_triangles)
+
+    def remove_non_manifold_triangles(self):
+        return self._remove(self.ctx.L.visma_icp_trimesh_remove_non_manifold_triangles)
+
+    def remove_non_manifold_vertices(self):
+        return self._remove(self.ctx.L.visma_icp_trimesh_remove_non_manifold_vertices)
+
+    def purge(self):
+        """Purge() -> the rows removed by its four steps: duplicated vertices, duplicated triangles, non-manifold triangles,
+        non-manifold vertices"""
+        r = (C.c_int64 * 4)()
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_purge(self.ctx._h, self._m, r))
+        return tuple(int(v) for v in r)
+
+    def select(self, indices):
+        """SelectDownSample -> a new TriMesh, purged"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        m = C.c_void_p()
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_select(self.ctx._h, self._m, _p(idx, C.POINTER(C.c_int64)), len(idx), C.byref(m)))
+        return TriMesh(self.ctx, m)
+
+    def crop(self, min_bound, max_bound):
+        """CropTriangleMesh -> a new TriMesh, purged"""
+        lo, hi = _f64(min_bound, (3,)), _f64(max_bound, (3,))
+        m = C.c_void_p()
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_crop(self.ctx._h, self._m, _p(lo, _dp), _p(hi, _dp), C.byref(m)))
+        return TriMesh(self.ctx, m)
+
+    def transform(self, T):
+        T = _f64(T, (16,))
+        self.ctx._chk(self.ctx.L.visma_icp_trimesh_transform(self.ctx._h, self._m, _p(T, _dp)))
 
 
 class KDTree:
@@ -701,6 +804,22 @@ def _bind(L):
         L.visma_icp_kdtree_search_hybrid.argtypes = [_vp, _dp, C.c_int64, C.c_double, C.c_int, _ip, _dp, _ip]
         L.visma_icp_kdtree_search_radius.argtypes = [_vp, _dp, C.c_int64, C.c_double, _i64, _i64]
         L.visma_icp_kdtree_get_radius_result.argtypes = [_vp, _ip, _dp]
+    if hasattr(L, "visma_icp_trimesh_create"):           # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp = C.POINTER(C.c_int64), C.c_void_p
+        L.visma_icp_trimesh_create.argtypes = [_vp, _dp, C.c_int64, _dp, _dp, _ip, C.c_int64, _dp, C.POINTER(_vp)]
+        L.visma_icp_trimesh_from_tsdf.argtypes = [_vp, _vp, C.POINTER(_vp)]
+        L.visma_icp_trimesh_destroy.argtypes = [_vp, _vp]
+        L.visma_icp_trimesh_size.argtypes = [_vp, _i64, _i64, C.POINTER(C.c_int)]
+        L.visma_icp_trimesh_get.argtypes = [_vp, _vp, _dp, _dp, _dp, _ip, _dp, C.c_int64, C.c_int64]
+        for name in ("compute_triangle_normals", "compute_vertex_normals"):
+            getattr(L, "visma_icp_trimesh_" + name).argtypes = [_vp, _vp, C.c_int]
+        L.visma_icp_trimesh_normalize_normals.argtypes = [_vp, _vp]
+        for name in ("remove_duplicated_vertices", "remove_duplicated_triangles", "remove_non_manifold_triangles",
+                     "remove_non_manifold_vertices", "purge"):
+            getattr(L, "visma_icp_trimesh_" + name).argtypes = [_vp, _vp, _i64]
+        L.visma_icp_trimesh_select.argtypes = [_vp, _vp, _i64, C.c_int64, C.POINTER(_vp)]
+        L.visma_icp_trimesh_crop.argtypes = [_vp, _vp, _dp, _dp, C.POINTER(_vp)]
+        L.visma_icp_trimesh_transform.argtypes = [_vp, _vp, _dp]
     if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
         _opt = C.POINTER(CColorMapOption)
@@ -1544,6 +1663,19 @@ class Context:
         t = C.c_void_p()
         self._chk(self.L.visma_icp_kdtree_create(self._h, _p(p, _dp), len(p), C.byref(t)))
         return KDTree(self, t, len(p))
+
+    # ---- TriangleMesh (visma_icp.h) ----
+    def trimesh(self, vertices, triangles, vertex_normals=None, vertex_colors=None, triangle_normals=None):
+        """Open3D's TriangleMesh on the device -> TriMesh.  vertices nv x 3 f64, triangles nt x 3 int32 (an index outside
+        [0, nv): IcpError), the optional attributes nv x 3 / nt x 3 f64."""
+        v = _f64(vertices, (-1, 3))
+        t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+        opt = lambda a, n: None if a is None else _f64(a, (n, 3))
+        vn, vc, tn = opt(vertex_normals, len(v)), opt(vertex_colors, len(v)), opt(triangle_normals, len(t))
+        dp = lambda a: None if a is None else _p(a, _dp)
+        m = C.c_void_p()
+        self._chk(self.L.visma_icp_trimesh_create(self._h, _p(v, _dp), len(v), dp(vn), dp(vc), _p(t, _ip), len(t), dp(tn), C.byref(m)))
+        return TriMesh(self, m)
 
     # ---- TSDF integration (visma_icp.h) ----
     def tsdf_uniform(self, length, resolution, sdf_trunc, color_type=TSDF_COLOR_NONE, origin=(0.0, 0.0, 0.0)):

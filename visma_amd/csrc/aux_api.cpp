@@ -152,6 +152,197 @@ int visma_icp_kdtree_get_radius_result(visma_icp_kdtree *tree, int32_t *idx, dou
     return e == hipSuccess ? VISMA_ICP_OK : kdtree_fail(ctx, "kdtree_get_radius_result", e);
 }
 
+// ---- TriangleMesh: a mesh resident on the device (trimesh.hip) ----
+static int trimesh_enter(visma_icp_ctx *ctx, visma_icp_trimesh *mesh)
+{
+    if (mesh) {
+        bool mine = false;
+        for (const auto &m : ctx->meshes) mine = mine || m.get() == mesh;
+        if (!mine) return ctx->fail(VISMA_ICP_ERR_INVALID, "not a mesh of this context");
+    }
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "a triangle mesh lives on one rank");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "a triangle mesh needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+static int trimesh_done(visma_icp_ctx *ctx, const char *what, hipError_t e)
+{
+    if (e == hipSuccess) return VISMA_ICP_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorInvalidValue) return ctx->fail(VISMA_ICP_ERR_INVALID, std::string(what) + ": an index outside [0, nv)");
+    return ctx->fail(VISMA_ICP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+static int trimesh_adopt(visma_icp_ctx *ctx, TriMeshDevice *dev, visma_icp_trimesh **out)
+{
+    std::unique_ptr<visma_icp_trimesh> m(new visma_icp_trimesh);
+    m->ctx = ctx; m->dev = dev;
+    *out = m.get();
+    ctx->meshes.push_back(std::move(m));
+    return VISMA_ICP_OK;
+}
+
+#define TRIMESH_CHECK(mesh)                                                                  \
+    CTX_CHECK();                                                                             \
+    if (!(mesh)) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL mesh");                      \
+    if (int rc_ = trimesh_enter(ctx, (mesh))) return rc_;
+
+// hipCUB's sorts take an int count: nv, nt and 3 nt must each fit one
+static bool trimesh_counts_ok(int64_t nv, int64_t nt) { return nv >= 0 && nt >= 0 && nv <= 0x7fffffff && nt <= 0x7fffffff / 3; }
+
+int visma_icp_trimesh_create(visma_icp_ctx *ctx, const double *vertices, int64_t nv, const double *vertex_normals,
+                             const double *vertex_colors, const int32_t *triangles, int64_t nt, const double *triangle_normals,
+                             visma_icp_trimesh **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!trimesh_counts_ok(nv, nt)) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_create: nv, nt and 3 nt must each fit an int");
+    if ((nv > 0 && !vertices) || (nt > 0 && !triangles)) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_create: NULL argument");
+    if (int rc = trimesh_enter(ctx, nullptr)) return rc;
+    TriMeshDevice *dev = nullptr;
+    const hipError_t e = trimesh_device_create(vertices, nv, vertex_normals, vertex_colors, triangles, nt, triangle_normals, false,
+                                               ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return trimesh_done(ctx, "trimesh_create", e);
+    return trimesh_adopt(ctx, dev, out);
+}
+
+int visma_icp_trimesh_from_tsdf(visma_icp_ctx *ctx, visma_icp_tsdf *volume, visma_icp_trimesh **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    bool mine = false;
+    for (const auto &v : ctx->volumes) mine = mine || (volume && v.get() == volume);
+    if (!mine) return ctx->fail(VISMA_ICP_ERR_INVALID, volume ? "not a volume of this context" : "NULL volume");
+    if (int rc = trimesh_enter(ctx, nullptr)) return rc;
+    if (volume->mesh_rows[0] < 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no mesh: extract first");
+    TsdfMeshView view;
+    if (int rc = ctx->eng->tsdf_mesh_view(volume->id, &view)) return ctx->eng_fail(rc);
+    if (!trimesh_counts_ok(view.nv, view.nt)) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_from_tsdf: nv, nt and 3 nt must each fit an int");
+    TriMeshDevice *dev = nullptr;
+    const hipError_t e = trimesh_device_create(view.vertices, view.nv, nullptr, view.colors, view.triangles, view.nt, nullptr, true,
+                                               ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return trimesh_done(ctx, "trimesh_from_tsdf", e);
+    return trimesh_adopt(ctx, dev, out);
+}
+
+int visma_icp_trimesh_destroy(visma_icp_ctx *ctx, visma_icp_trimesh *mesh)
+{
+    CTX_CHECK();
+    if (!mesh) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL mesh");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    for (size_t i = 0; i < ctx->meshes.size(); i++)
+        if (ctx->meshes[i].get() == mesh) { ctx->meshes.erase(ctx->meshes.begin() + (std::ptrdiff_t)i); return VISMA_ICP_OK; }
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "not a mesh of this context");
+}
+
+int visma_icp_trimesh_size(const visma_icp_trimesh *mesh, int64_t *nv, int64_t *nt, int *has_flags)
+{
+    if (!mesh || !mesh->dev) { g_create_error = "mesh is NULL"; return VISMA_ICP_ERR_INVALID; }
+    int64_t v = 0, t = 0;
+    int f = 0;
+    trimesh_device_size(mesh->dev, &v, &t, &f);
+    if (nv) *nv = v;
+    if (nt) *nt = t;
+    if (has_flags) *has_flags = f;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_trimesh_get(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, double *vertices, double *vertex_normals, double *vertex_colors,
+                          int32_t *triangles, double *triangle_normals, int64_t nv, int64_t nt)
+{
+    TRIMESH_CHECK(mesh);
+    int64_t v = 0, t = 0;
+    int f = 0;
+    trimesh_device_size(mesh->dev, &v, &t, &f);
+    if (nv != v || nt != t) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_get: nv or nt differs from the mesh's counts");
+    if ((vertex_normals && !(f & kTriMeshVertexNormals)) || (vertex_colors && !(f & kTriMeshVertexColors)) ||
+        (triangle_normals && !(f & kTriMeshTriangleNormals)))
+        return ctx->fail(VISMA_ICP_ERR_STATE, "trimesh_get: the mesh does not have that attribute");
+    return trimesh_done(ctx, "trimesh_get", trimesh_device_get(mesh->dev, vertices, vertex_normals, vertex_colors, triangles,
+                                                               triangle_normals, ctx->eng->aux_stream()));
+}
+
+int visma_icp_trimesh_compute_triangle_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int normalized)
+{
+    TRIMESH_CHECK(mesh);
+    return trimesh_done(ctx, "trimesh_compute_triangle_normals",
+                        trimesh_device_compute_triangle_normals(mesh->dev, normalized != 0, ctx->eng->aux_stream()));
+}
+
+int visma_icp_trimesh_compute_vertex_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int normalized)
+{
+    TRIMESH_CHECK(mesh);
+    return trimesh_done(ctx, "trimesh_compute_vertex_normals",
+                        trimesh_device_compute_vertex_normals(mesh->dev, normalized != 0, ctx->eng->aux_stream()));
+}
+
+int visma_icp_trimesh_normalize_normals(visma_icp_ctx *ctx, visma_icp_trimesh *mesh)
+{
+    TRIMESH_CHECK(mesh);
+    return trimesh_done(ctx, "trimesh_normalize_normals", trimesh_device_normalize_normals(mesh->dev, ctx->eng->aux_stream()));
+}
+
+static int trimesh_remove(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int step, int64_t *removed)
+{
+    TRIMESH_CHECK(mesh);
+    int64_t r = 0;
+    const hipError_t e = trimesh_device_remove(mesh->dev, step, &r, ctx->eng->aux_stream());
+    if (removed) *removed = r;
+    return trimesh_done(ctx, "trimesh_remove", e);
+}
+
+int visma_icp_trimesh_remove_duplicated_vertices(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed) { return trimesh_remove(ctx, mesh, 0, removed); }
+int visma_icp_trimesh_remove_duplicated_triangles(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed) { return trimesh_remove(ctx, mesh, 1, removed); }
+int visma_icp_trimesh_remove_non_manifold_triangles(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed) { return trimesh_remove(ctx, mesh, 2, removed); }
+int visma_icp_trimesh_remove_non_manifold_vertices(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t *removed) { return trimesh_remove(ctx, mesh, 3, removed); }
+
+int visma_icp_trimesh_purge(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int64_t removed[4])
+{
+    TRIMESH_CHECK(mesh);
+    int64_t r[4] = {0, 0, 0, 0};
+    const hipError_t e = trimesh_device_purge(mesh->dev, r, ctx->eng->aux_stream());
+    if (removed) std::copy(r, r + 4, removed);
+    return trimesh_done(ctx, "trimesh_purge", e);
+}
+
+int visma_icp_trimesh_select(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const int64_t *indices, int64_t n, visma_icp_trimesh **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!mesh) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL mesh");
+    if (n < 0 || (n > 0 && !indices)) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_select: n >= 0 indices");
+    if (int rc = trimesh_enter(ctx, mesh)) return rc;
+    TriMeshDevice *dev = nullptr;
+    const hipError_t e = trimesh_device_select(mesh->dev, indices, n, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return trimesh_done(ctx, "trimesh_select", e);
+    return trimesh_adopt(ctx, dev, out);
+}
+
+int visma_icp_trimesh_crop(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const double min_bound[3], const double max_bound[3],
+                           visma_icp_trimesh **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!mesh || !min_bound || !max_bound) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_crop: NULL argument");
+    if (int rc = trimesh_enter(ctx, mesh)) return rc;
+    TriMeshDevice *dev = nullptr;
+    const hipError_t e = trimesh_device_crop(mesh->dev, min_bound, max_bound, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return trimesh_done(ctx, "trimesh_crop", e);
+    return trimesh_adopt(ctx, dev, out);
+}
+
+int visma_icp_trimesh_transform(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const double T[16])
+{
+    TRIMESH_CHECK(mesh);
+    if (!T) return ctx->fail(VISMA_ICP_ERR_INVALID, "trimesh_transform: NULL argument");
+    return trimesh_done(ctx, "trimesh_transform", trimesh_device_transform(mesh->dev, T, ctx->eng->aux_stream()));
+}
+
 // ---- FPFH, feature matching, fast global registration ----
 
 int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type,

@@ -37,6 +37,16 @@ struct visma_icp_kdtree {
     ~visma_icp_kdtree() { kdtree_device_destroy(dev); }
 };
 
+// a TriangleMesh of a context, resident on the device (trimesh.hip)
+struct visma_icp_trimesh {
+    visma_icp_ctx *ctx = nullptr;
+    TriMeshDevice *dev = nullptr;
+    visma_icp_trimesh() = default;
+    visma_icp_trimesh(const visma_icp_trimesh &) = delete;
+    visma_icp_trimesh &operator=(const visma_icp_trimesh &) = delete;
+    ~visma_icp_trimesh() { trimesh_device_destroy(dev); }
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -69,6 +79,7 @@ struct visma_icp_ctx {
     std::vector<std::unique_ptr<visma_icp_color_map>> color_maps;   // likewise
     std::vector<std::unique_ptr<visma_icp_tsdf>> volumes;   // the engine frees their device memory with itself
     std::vector<std::unique_ptr<visma_icp_kdtree>> trees;   // each frees its own, before the engine goes
+    std::vector<std::unique_ptr<visma_icp_trimesh>> meshes;   // likewise
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

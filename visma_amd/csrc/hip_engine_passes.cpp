@@ -1144,6 +1144,15 @@ int HipEngine::tsdf_get_mesh(int id, double *vertices, double *colors, int32_t *
     return VISMA_ICP_OK;
 }
 
+int HipEngine::tsdf_mesh_view(int id, TsdfMeshView *view)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    if (!tsdf_device_mesh_view(D, view)) { err_ = "no mesh: extract first"; return VISMA_ICP_ERR_STATE; }
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::tsdf_get_units(int id, std::vector<int32_t> *keys)
 {
     TsdfDevice *D = nullptr;

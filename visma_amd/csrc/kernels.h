@@ -726,6 +726,13 @@ hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *point
 hipError_t tsdf_device_extract_mesh(TsdfDevice *D, int64_t *nv, int64_t *nt);
 // the rows of the last mesh (vertices, colors nv x 3 doubles, triangles nt x 3 int32; each may be NULL)
 hipError_t tsdf_device_get_mesh(TsdfDevice *D, double *vertices, double *colors, int32_t *triangles);
+// the last mesh where it lies ON THE DEVICE (colors NULL for a volume without colour); false: no mesh since the last change
+struct TsdfMeshView {
+    const double *vertices = nullptr, *colors = nullptr;
+    const int32_t *triangles = nullptr;
+    int64_t nv = 0, nt = 0;
+};
+bool tsdf_device_mesh_view(const TsdfDevice *D, TsdfMeshView *view);
 // the indices of a scalable volume's units, 3 per unit, in lexicographic order (the order of its extractions)
 void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys);
 // tsdf, weight (R^3) and color (R^3 x 3, interleaved as the reference keeps it) of a uniform volume (unit == NULL) or of
@@ -735,6 +742,30 @@ hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsd
 // color_type as above.  points / colors: room for ceil(w / stride) * ceil(h / stride) rows, or NULL (count only).
 hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
                                          double *colors, int64_t *n, hipStream_t stream);
+
+// ---- TriangleMesh (trimesh.hip): a mesh resident on the device: normals, Purge, select, crop, Transform ----
+// Every result is the reference's bit for bit (TriangleMesh.cpp, DownSample.cpp); the rules: visma_icp.h.  Each call returns
+// with the stream idle.  The arguments are checked by the caller (aux_api.cpp) but for the indices: a triangle index outside
+// [0, nv) (create) or a selected index outside it (select) is hipErrorInvalidValue, and nothing is made.
+constexpr int kTriMeshVertexNormals = 1, kTriMeshVertexColors = 2, kTriMeshTriangleNormals = 4;
+struct TriMeshDevice;
+// vn, vc, tn may be NULL.  on_device: the arrays lie on this device and are copied there (the mesh of a TSDF volume)
+hipError_t trimesh_device_create(const double *v, int64_t nv, const double *vn, const double *vc, const int32_t *tri, int64_t nt,
+                                 const double *tn, bool on_device, hipStream_t stream, TriMeshDevice **out);
+void trimesh_device_destroy(TriMeshDevice *M);
+void trimesh_device_size(const TriMeshDevice *M, int64_t *nv, int64_t *nt, int *flags);
+// each output may be NULL; an attribute the mesh does not have is not written
+hipError_t trimesh_device_get(TriMeshDevice *M, double *v, double *vn, double *vc, int32_t *tri, double *tn, hipStream_t stream);
+hipError_t trimesh_device_normalize_normals(TriMeshDevice *M, hipStream_t stream);
+hipError_t trimesh_device_compute_triangle_normals(TriMeshDevice *M, bool normalized, hipStream_t stream);
+hipError_t trimesh_device_compute_vertex_normals(TriMeshDevice *M, bool normalized, hipStream_t stream);
+// step 0 .. 3: RemoveDuplicatedVertices, RemoveDuplicatedTriangles, RemoveNonManifoldTriangles, RemoveNonManifoldVertices
+hipError_t trimesh_device_remove(TriMeshDevice *M, int step, int64_t *removed, hipStream_t stream);
+hipError_t trimesh_device_purge(TriMeshDevice *M, int64_t removed[4], hipStream_t stream);
+// a new mesh, purged (the source's scratch buffers are used: it is not const)
+hipError_t trimesh_device_select(TriMeshDevice *S, const int64_t *indices, int64_t n, hipStream_t stream, TriMeshDevice **out);
+hipError_t trimesh_device_crop(TriMeshDevice *S, const double lo[3], const double hi[3], hipStream_t stream, TriMeshDevice **out);
+hipError_t trimesh_device_transform(TriMeshDevice *M, const double T[16], hipStream_t stream);
 
 // ---- color map optimization (colormap.hip): frames, vertices, visibility and poses resident on the device ----
 constexpr int kColorMapSums = 29;                      // per camera: 21 upper entries of JJ (row by row), 6 of Jb, rr, count

@@ -1074,6 +1074,16 @@ hipError_t tsdf_device_get_mesh(TsdfDevice *D, double *vertices, double *colors,
     return hipSuccess;
 }
 
+bool tsdf_device_mesh_view(const TsdfDevice *D, TsdfMeshView *view)
+{
+    if (D->mesh_nv < 0) return false;
+    view->vertices = D->mesh_vertices.get();
+    view->colors = D->planes() > 0 ? D->mesh_colors.get() : nullptr;
+    view->triangles = D->mesh_triangles.get();
+    view->nv = D->mesh_nv; view->nt = D->mesh_nt;
+    return true;
+}
+
 void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys)
 {
     keys->clear();
