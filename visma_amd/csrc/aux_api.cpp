@@ -1143,19 +1143,17 @@ int visma_icp_measure_surface_error(visma_icp_ctx *ctx, const double *Vs, int64_
 int visma_icp_selftest_so3(const double *w, double *R, double *w_back, int n)
 {
     if (!w || !R || !w_back || n <= 0) return VISMA_ICP_ERR_INVALID;
+    DevBufs bufs;
     double *dw = nullptr, *dR = nullptr, *dw2 = nullptr;
-    int rc = VISMA_ICP_ERR_HIP;
-    if (hipMalloc(&dw, sizeof(double) * 3 * n) == hipSuccess &&
-        hipMalloc(&dR, sizeof(double) * 9 * n) == hipSuccess &&
-        hipMalloc(&dw2, sizeof(double) * 3 * n) == hipSuccess &&
+    if (bufs.alloc(&dw, 3 * (size_t)n) == hipSuccess && bufs.alloc(&dR, 9 * (size_t)n) == hipSuccess &&
+        bufs.alloc(&dw2, 3 * (size_t)n) == hipSuccess &&
         hipMemcpy(dw, w, sizeof(double) * 3 * n, hipMemcpyHostToDevice) == hipSuccess &&
         launch_so3_selftest(dw, dR, dw2, n, nullptr) == hipSuccess &&
         hipMemcpy(R, dR, sizeof(double) * 9 * n, hipMemcpyDeviceToHost) == hipSuccess &&
         hipMemcpy(w_back, dw2, sizeof(double) * 3 * n, hipMemcpyDeviceToHost) == hipSuccess)
-        rc = VISMA_ICP_OK;
-    if (rc != VISMA_ICP_OK) g_create_error = "so3 selftest: HIP call failed (no GPU?)";
-    (void)hipFree(dw); (void)hipFree(dR); (void)hipFree(dw2);
-    return rc;
+        return VISMA_ICP_OK;
+    g_create_error = "so3 selftest: HIP call failed (no GPU?)";
+    return VISMA_ICP_ERR_HIP;
 }
 
 int visma_se3_compose(const double a[12], const double b[12], double out[12])
@@ -1183,16 +1181,16 @@ int visma_icp_selftest_se3(const double *g, const double *h, const double *v, in
 {
     if (n < 0 || (n > 0 && (!g || !h || !v || !gh || !gv || !gi))) return VISMA_ICP_ERR_INVALID;
     if (n == 0) return VISMA_ICP_OK;
+    DevBufs bufs;
     double *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t sz[6] = {12, 12, 3, 12, 3, 12};
     const double *in[3] = {g, h, v};
     double *outp[3] = {gh, gv, gi};
     bool ok = true;
-    for (int k = 0; k < 6 && ok; k++) ok = hipMalloc((void **)&d[k], sizeof(double) * sz[k] * (size_t)n) == hipSuccess;
+    for (int k = 0; k < 6 && ok; k++) ok = bufs.alloc(&d[k], sz[k] * (size_t)n) == hipSuccess;
     for (int k = 0; k < 3 && ok; k++) ok = hipMemcpy(d[k], in[k], sizeof(double) * sz[k] * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && launch_se3_selftest(d[0], d[1], d[2], n, d[3], d[4], d[5], nullptr) == hipSuccess;
     for (int k = 0; k < 3 && ok; k++) ok = hipMemcpy(outp[k], d[3 + k], sizeof(double) * sz[3 + k] * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
-    for (int k = 0; k < 6; k++) if (d[k]) (void)hipFree(d[k]);
     if (!ok) { (void)hipGetLastError(); g_create_error = "se3 selftest: HIP call failed (no GPU?)"; return VISMA_ICP_ERR_HIP; }
     return VISMA_ICP_OK;
 }
@@ -1237,19 +1235,18 @@ int visma_icp_selftest_so3_jac(const double *w, int n, double *R, double *dR_dw,
                                double *proj)
 {
     if (!w || !R || !dR_dw || !w_back || !dw_dR || !proj || n <= 0) return VISMA_ICP_ERR_INVALID;
+    DevBufs bufs;
     double *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t sz[6] = {3, 9, 27, 3, 27, 9};
-    int rc = VISMA_ICP_ERR_HIP;
     bool ok = true;
-    for (int k = 0; k < 6 && ok; k++) ok = hipMalloc(&d[k], sizeof(double) * sz[k] * n) == hipSuccess;
+    for (int k = 0; k < 6 && ok; k++) ok = bufs.alloc(&d[k], sz[k] * (size_t)n) == hipSuccess;
     ok = ok && hipMemcpy(d[0], w, sizeof(double) * 3 * n, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && launch_so3_selftest_jac(d[0], n, d[1], d[2], d[3], d[4], d[5], nullptr) == hipSuccess;
     double *out[6] = {nullptr, R, dR_dw, w_back, dw_dR, proj};
     for (int k = 1; k < 6 && ok; k++) ok = hipMemcpy(out[k], d[k], sizeof(double) * sz[k] * n, hipMemcpyDeviceToHost) == hipSuccess;
-    if (ok) rc = VISMA_ICP_OK;
-    else g_create_error = "so3 selftest: HIP call failed (no GPU?)";
-    for (int k = 0; k < 6; k++) (void)hipFree(d[k]);
-    return rc;
+    if (ok) return VISMA_ICP_OK;
+    g_create_error = "so3 selftest: HIP call failed (no GPU?)";
+    return VISMA_ICP_ERR_HIP;
 }
 
 int visma_icp_selftest_neighbor_lists(const double *xyz, int64_t n, int search_type, int cap, double radius, int list_kind,

@@ -7,21 +7,13 @@
 #pragma once
 
 #include "device_common.h"
+#include "dev_mem.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <math.h>
 
 namespace visma {
-
-struct DBuf {                                       // device allocation, freed on scope exit
-    void *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-    template <typename T> T *as() const { return (T *)p; }
-};
-
-#define BVH_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
 
 struct MortonParams {
     double lo[3], inv[3];            // code = min(1023, (c - lo) * inv)
@@ -76,12 +68,12 @@ static inline MortonParams morton_params(const double lo[3], const double hi[3])
 // Stable LSD radix sort of n (< 2^31) 30-bit codes with their u32 payload: (key, val) -> (key_out, val_out).  `tmp`
 // receives hipcub's scratch and must outlive the sort's kernels on `stream`.
 static inline hipError_t morton_sort(unsigned *key, unsigned *key_out, unsigned *val, unsigned *val_out, int64_t n,
-                                     DBuf &tmp, hipStream_t stream)
+                                     DevBuf<char> &tmp, hipStream_t stream)
 {
     size_t tmp_bytes = 0;
-    BVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key, key_out, val, val_out, (int)n, 0, 30, stream));
-    BVH_TRY(tmp.alloc(tmp_bytes));
-    return hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, key, key_out, val, val_out, (int)n, 0, 30, stream);
+    VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, key, key_out, val, val_out, (int)n, 0, 30, stream));
+    DEV_RESET(tmp, tmp_bytes);
+    return hipcub::DeviceRadixSort::SortPairs(tmp.get(), tmp_bytes, key, key_out, val, val_out, (int)n, 0, 30, stream);
 }
 
 // node n = union of its children 2n, 2n+1 (boxes as lo[3], hi[3]); one launch per level, leaves first

@@ -157,7 +157,8 @@ __global__ __launch_bounds__(kCloudBlock) void cloud_nn_kernel(
 namespace {
 
 struct DevCloudTree {
-    DBuf pts, key, order, nodes;         // sorted points, their sorted codes and caller indices, 2P boxes
+    DeviceBuf<double> pts, nodes;        // sorted points, 2P boxes
+    DeviceBuf<unsigned> key, order;      // their sorted codes and caller indices
     int64_t n = 0, P = 0;
     MortonParams mp;
 };
@@ -173,29 +174,31 @@ hipError_t build_cloud_tree(const double *h_xyz, int64_t n, DevCloudTree &t, hip
         }
     t.n = n;
     t.mp = morton_params(lo, hi);
-    DBuf raw, key, val, tmp;
-    BVH_TRY(raw.alloc(sizeof(double) * 3 * n));
-    BVH_TRY(key.alloc(sizeof(unsigned) * n));
-    BVH_TRY(val.alloc(sizeof(unsigned) * n));
-    BVH_TRY(t.key.alloc(sizeof(unsigned) * n));
-    BVH_TRY(t.order.alloc(sizeof(unsigned) * n));
-    BVH_TRY(t.pts.alloc(sizeof(double) * 3 * n));
-    BVH_TRY(hipMemcpyAsync(raw.p, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    DeviceBuf<double> raw;
+    DeviceBuf<unsigned> key, val;
+    DeviceBuf<char> tmp;
+    DEV_RESET(raw, 3 * n);
+    DEV_RESET(key, n);
+    DEV_RESET(val, n);
+    DEV_RESET(t.key, n);
+    DEV_RESET(t.order, n);
+    DEV_RESET(t.pts, 3 * n);
+    VISMA_TRY(hipMemcpyAsync(raw, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
     const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(point_code_kernel, dim3(nb), dim3(256), 0, stream, raw.as<double>(), (long long)n, t.mp,
-                       key.as<unsigned>(), val.as<unsigned>());
-    BVH_TRY(morton_sort(key.as<unsigned>(), t.key.as<unsigned>(), val.as<unsigned>(), t.order.as<unsigned>(), n, tmp,
+    hipLaunchKernelGGL(point_code_kernel, dim3(nb), dim3(256), 0, stream, raw, (long long)n, t.mp,
+                       key, val);
+    VISMA_TRY(morton_sort(key, t.key, val, t.order, n, tmp,
                         stream));
-    hipLaunchKernelGGL(cloud_gather_kernel, dim3(nb), dim3(256), 0, stream, raw.as<double>(),
-                       t.order.as<unsigned>(), (long long)n, t.pts.as<double>());
+    hipLaunchKernelGGL(cloud_gather_kernel, dim3(nb), dim3(256), 0, stream, raw,
+                       t.order, (long long)n, t.pts);
     const int64_t nleaf = (n + kPtLeaf - 1) / kPtLeaf;
     int64_t P = 1;
     while (P < nleaf) P <<= 1;
     t.P = P;
-    BVH_TRY(t.nodes.alloc(sizeof(double) * 6 * 2 * P));
+    DEV_RESET(t.nodes, 6 * 2 * P);
     hipLaunchKernelGGL(cloud_leaf_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream,
-                       t.pts.as<double>(), (long long)n, (long long)P, t.nodes.as<double>());
-    BVH_TRY(build_bvh_levels(t.nodes.as<double>(), P, stream));
+                       t.pts, (long long)n, (long long)P, t.nodes);
+    VISMA_TRY(build_bvh_levels(t.nodes, P, stream));
     // the temporaries above are freed when this function returns: wait for the kernels using them
     return hipStreamSynchronize(stream);
 }
@@ -204,18 +207,18 @@ hipError_t build_cloud_tree(const double *h_xyz, int64_t n, DevCloudTree &t, hip
 hipError_t query_cloud_tree(const DevCloudTree &t, const double *d_q, int64_t nq, const unsigned *qorder,
                             const unsigned *qkey, double *h_dist, hipStream_t stream)
 {
-    DBuf d2;
-    BVH_TRY(d2.alloc(sizeof(double) * nq));
+    DeviceBuf<double> d2;
+    DEV_RESET(d2, nq);
     int depth = 2;                                   // levels below the root + slack
     for (int64_t q = t.P; q > 1; q >>= 1) depth++;
     hipLaunchKernelGGL(cloud_nn_kernel, dim3((unsigned)((nq + kCloudBlock - 1) / kCloudBlock)), dim3(kCloudBlock),
-                       (size_t)depth * kCloudBlock * 8, stream, d_q, (long long)nq, qorder, qkey, t.pts.as<double>(),
-                       t.key.as<unsigned>(), (long long)t.n, t.nodes.as<double>(), (long long)t.P, depth,
-                       d2.as<double>());
-    hipLaunchKernelGGL(sqrt_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d2.as<double>(),
+                       (size_t)depth * kCloudBlock * 8, stream, d_q, (long long)nq, qorder, qkey, t.pts,
+                       t.key, (long long)t.n, t.nodes, (long long)t.P, depth,
+                       d2);
+    hipLaunchKernelGGL(sqrt_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, d2,
                        (long long)nq);
-    BVH_TRY(hipGetLastError());
-    BVH_TRY(hipMemcpyAsync(h_dist, d2.p, sizeof(double) * nq, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipGetLastError());
+    VISMA_TRY(hipMemcpyAsync(h_dist, d2, sizeof(double) * nq, hipMemcpyDeviceToHost, stream));
     return hipStreamSynchronize(stream);
 }
 
@@ -231,20 +234,22 @@ hipError_t point_cloud_distance_device(const double *h_src, int64_t ns, const do
         return hipSuccess;
     }
     DevCloudTree tree;
-    BVH_TRY(build_cloud_tree(h_tgt, nt, tree, stream));
-    DBuf q, key, val, qkey, qorder, tmp;
-    BVH_TRY(q.alloc(sizeof(double) * 3 * ns));
-    BVH_TRY(key.alloc(sizeof(unsigned) * ns));
-    BVH_TRY(val.alloc(sizeof(unsigned) * ns));
-    BVH_TRY(qkey.alloc(sizeof(unsigned) * ns));
-    BVH_TRY(qorder.alloc(sizeof(unsigned) * ns));
-    BVH_TRY(hipMemcpyAsync(q.p, h_src, sizeof(double) * 3 * ns, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(build_cloud_tree(h_tgt, nt, tree, stream));
+    DeviceBuf<double> q;
+    DeviceBuf<unsigned> key, val, qkey, qorder;
+    DeviceBuf<char> tmp;
+    DEV_RESET(q, 3 * ns);
+    DEV_RESET(key, ns);
+    DEV_RESET(val, ns);
+    DEV_RESET(qkey, ns);
+    DEV_RESET(qorder, ns);
+    VISMA_TRY(hipMemcpyAsync(q, h_src, sizeof(double) * 3 * ns, hipMemcpyHostToDevice, stream));
     // the queries sorted by their code over the TARGET's box: the rank of that code among the target's is the seed
-    hipLaunchKernelGGL(point_code_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, q.as<double>(),
-                       (long long)ns, tree.mp, key.as<unsigned>(), val.as<unsigned>());
-    BVH_TRY(morton_sort(key.as<unsigned>(), qkey.as<unsigned>(), val.as<unsigned>(), qorder.as<unsigned>(), ns, tmp,
+    hipLaunchKernelGGL(point_code_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, stream, q,
+                       (long long)ns, tree.mp, key, val);
+    VISMA_TRY(morton_sort(key, qkey, val, qorder, ns, tmp,
                         stream));
-    return query_cloud_tree(tree, q.as<double>(), ns, qorder.as<unsigned>(), qkey.as<unsigned>(), h_dist, stream);
+    return query_cloud_tree(tree, q, ns, qorder, qkey, h_dist, stream);
 }
 
 hipError_t nearest_neighbor_distance_device(const double *h_xyz, int64_t n, double *h_dist, hipStream_t stream)
@@ -256,8 +261,8 @@ hipError_t nearest_neighbor_distance_device(const double *h_xyz, int64_t n, doub
         return hipSuccess;
     }
     DevCloudTree tree;
-    BVH_TRY(build_cloud_tree(h_xyz, n, tree, stream));
-    return query_cloud_tree(tree, nullptr, n, tree.order.as<unsigned>(), nullptr, h_dist, stream);
+    VISMA_TRY(build_cloud_tree(h_xyz, n, tree, stream));
+    return query_cloud_tree(tree, nullptr, n, tree.order, nullptr, h_dist, stream);
 }
 
 }  // namespace visma

@@ -273,47 +273,37 @@ __global__ __launch_bounds__(kPairThreads) void cm_iteration_kernel(IterationArg
 
 }  // namespace
 
-namespace cm {
-struct CmCompactor { Compactor c; };
-}  // namespace cm
+void color_map_device_destroy(ColorMapDevice *D) { delete D; }
 
-void color_map_device_destroy(ColorMapDevice *D)
+static hipError_t cm_create_buffers(ColorMapDevice *D)
 {
-    if (!D) return;
-    void *all[] = {D->depth, D->rgb, D->mask, D->texels, D->extrinsics, D->extr0, D->tmp[0], D->tmp[1], D->tmp[2], D->tmp[3], D->tmp[4],
-                   D->mtmp[0], D->mtmp[1], D->vertices, D->proxy, D->colors, D->bits, D->list, D->offsets, D->partials, D->sums, D->tickets};
-    for (void *p : all)
-        if (p) (void)hipFree(p);
-    color_map_warp_release(D);
-    if (D->compactor) { D->compactor->c.release(); delete D->compactor; }
-    delete D;
+    const size_t n = (size_t)D->cfg.n_images, px = (size_t)D->plane;
+    DEV_RESET(D->depth, n * px);
+    DEV_RESET(D->rgb, n * px * 3);
+    DEV_RESET(D->mask, n * px);
+    DEV_RESET(D->texels, n * px);
+    DEV_RESET(D->extrinsics, n * 16);
+    DEV_RESET(D->extr0, n * 16);
+    for (auto &t : D->tmp) DEV_RESET(t, px);
+    for (auto &t : D->mtmp) DEV_RESET(t, px);
+    DEV_RESET(D->offsets, n + 1);
+    DEV_RESET(D->sums, n * kPairRow);
+    DEV_RESET(D->tickets, n);
+    VISMA_TRY(hipMemsetAsync(D->tickets, 0, sizeof(unsigned) * n, D->stream));
+    if (D->cfg.anchors > 0) VISMA_TRY(color_map_warp_create(D));
+    return hipStreamSynchronize(D->stream);
 }
 
 hipError_t color_map_device_create(const ColorMapConfig &cfg, hipStream_t stream, ColorMapDevice **out)
 {
     ColorMapDevice *D = new ColorMapDevice;
-    D->compactor = new CmCompactor;
     D->cfg = cfg; D->stream = stream;
     D->K = CmCamera{cfg.fx, cfg.fy, cfg.cx, cfg.cy, cfg.w, cfg.h};
     D->plane = (long long)cfg.w * cfg.h;
     D->words = (cfg.n_images + 31) / 32;
-    const size_t n = (size_t)cfg.n_images, px = (size_t)D->plane;
-    hipError_t e = cm_alloc(&D->depth, n * px);
-    if (e == hipSuccess) e = cm_alloc(&D->rgb, n * px * 3);
-    if (e == hipSuccess) e = cm_alloc(&D->mask, n * px);
-    if (e == hipSuccess) e = cm_alloc(&D->texels, n * px);
-    if (e == hipSuccess) e = cm_alloc(&D->extrinsics, n * 16);
-    if (e == hipSuccess) e = cm_alloc(&D->extr0, n * 16);
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = cm_alloc(&D->tmp[k], px);
-    for (int k = 0; k < 2 && e == hipSuccess; k++) e = cm_alloc(&D->mtmp[k], px);
-    if (e == hipSuccess) e = cm_alloc(&D->offsets, n + 1);
-    if (e == hipSuccess) e = cm_alloc(&D->sums, n * kPairRow);
-    if (e == hipSuccess) e = cm_alloc(&D->tickets, n);
-    if (e == hipSuccess) e = hipMemsetAsync(D->tickets, 0, sizeof(unsigned) * n, stream);
-    if (e == hipSuccess && cfg.anchors > 0) e = color_map_warp_create(D);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { color_map_device_destroy(D); return e; }
-    D->host_extr.assign(n * 16, 0.0);
+    const hipError_t e = cm_create_buffers(D);
+    if (e != hipSuccess) { delete D; return e; }
+    D->host_extr.assign((size_t)cfg.n_images * 16, 0.0);
     *out = D;
     return hipSuccess;
 }
@@ -332,19 +322,15 @@ hipError_t color_map_device_set_image(ColorMapDevice *D, int i, const float *dep
 
 hipError_t color_map_device_set_vertices(ColorMapDevice *D, const double *vertices, int64_t n)
 {
-    void *old[] = {D->vertices, D->proxy, D->colors, D->bits, D->list};
-    for (void *p : old)
-        if (p) (void)hipFree(p);
-    D->vertices = D->proxy = D->colors = nullptr; D->bits = nullptr; D->list = nullptr;
+    D->vertices.release(); D->proxy.release(); D->colors.release(); D->bits.release(); D->list.release();
     D->nv = n;
     D->nvp = (n + kThreads - 1) / kThreads * kThreads;
     D->proxy_valid = false;
-    hipError_t e = cm_alloc(&D->vertices, (size_t)n * 3);
-    if (e == hipSuccess) e = cm_alloc(&D->proxy, (size_t)n);
-    if (e == hipSuccess) e = cm_alloc(&D->colors, (size_t)n * 3);
-    if (e == hipSuccess) e = cm_alloc(&D->bits, (size_t)n * D->words);
-    if (e == hipSuccess && n > 0) e = hipMemcpyAsync(D->vertices, vertices, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, D->stream);
-    if (e != hipSuccess) return e;
+    DEV_RESET(D->vertices, (size_t)n * 3);
+    DEV_RESET(D->proxy, (size_t)n);
+    DEV_RESET(D->colors, (size_t)n * 3);
+    DEV_RESET(D->bits, (size_t)n * D->words);
+    if (n > 0) VISMA_TRY(hipMemcpyAsync(D->vertices, vertices, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, D->stream));
     return hipStreamSynchronize(D->stream);
 }
 
@@ -395,19 +381,17 @@ hipError_t color_map_device_prepare(ColorMapDevice *D, int64_t *counts)
     src.list = nullptr; src.bits = D->bits;
     const long long items = (long long)n * D->nvp;
     long long rows = 0;
-    e = D->compactor->c.count(src, items, s, &rows);
+    e = compact_count(D->compactor, src, items, s, &rows);
     if (e != hipSuccess) return e;
-    if (D->list) { (void)hipFree(D->list); D->list = nullptr; }
-    e = cm_alloc(&D->list, (size_t)rows);
-    if (e != hipSuccess) return e;
+    DEV_RESET(D->list, (size_t)rows);
     src.list = D->list;
-    e = D->compactor->c.write(src, items, s);
+    e = compact_write(D->compactor, src, items, s);
     if (e != hipSuccess) return e;
     // camera c's list begins where its first tile does
     D->host_offsets.assign((size_t)n + 1, rows);
     const long long tiles_per_camera = D->nvp / kThreads;
     for (int c = 0; c < n && tiles_per_camera > 0 && e == hipSuccess; c++)
-        e = hipMemcpyAsync(&D->host_offsets[(size_t)c], D->compactor->c.tile_offset + c * tiles_per_camera, sizeof(long long),
+        e = hipMemcpyAsync(&D->host_offsets[(size_t)c], D->compactor.tile_offset.get() + c * tiles_per_camera, sizeof(long long),
                            hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return e;
@@ -417,9 +401,8 @@ hipError_t color_map_device_prepare(ColorMapDevice *D, int64_t *counts)
         most = std::max<long long>(most, counts[c]);
     }
     D->blocks = (int)std::min<long long>(std::max<long long>((most + kPairThreads - 1) / kPairThreads, 1), kColorMapMaxBlocks);
-    if (D->partials) { (void)hipFree(D->partials); D->partials = nullptr; }
-    e = cm_alloc(&D->partials, (size_t)n * D->blocks * kPairRow);
-    if (e == hipSuccess) e = hipMemcpyAsync(D->offsets, D->host_offsets.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
+    DEV_RESET(D->partials, (size_t)n * D->blocks * kPairRow);
+    e = hipMemcpyAsync(D->offsets, D->host_offsets.data(), sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess && D->warp) e = color_map_warp_prepare(D);
     D->proxy_valid = false;

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "kernels.h"
+#include "dev_mem.h"
 
 #include <vector>
 
@@ -41,14 +42,6 @@ __device__ __forceinline__ void cm_warp_shift(const CmWarpCell &g, double p, dou
     *sv = ((w00 * g.y00 + w01 * g.y01) + w10 * g.y10) + w11 * g.y11;
 }
 
-template <class T>
-inline hipError_t cm_alloc(T **p, size_t n)
-{
-    return hipMalloc((void **)p, sizeof(T) * (n ? n : 1));
-}
-
-struct CmCompactor;                  // colormap.hip: the grow-only buffers of compact.h's compaction
-
 }  // namespace cm
 
 using namespace cm;
@@ -60,45 +53,44 @@ struct ColorMapDevice {
     long long plane = 0, nv = 0, nvp = 0;
     int words = 0, blocks = 1;
     // the frames
-    float *depth = nullptr;
-    unsigned char *rgb = nullptr, *mask = nullptr;
-    float4 *texels = nullptr;
-    double *extrinsics = nullptr;    // the CURRENT poses; host_extr is their copy
-    double *extr0 = nullptr;         // the poses of prepare (what visibility read)
+    DeviceBuf<float> depth;
+    DeviceBuf<unsigned char> rgb, mask;
+    DeviceBuf<float4> texels;
+    DeviceBuf<double> extrinsics;    // the CURRENT poses; host_extr is their copy
+    DeviceBuf<double> extr0;         // the poses of prepare (what visibility read)
     std::vector<double> host_extr;
     // per image scratch: five fp32 planes and two mask planes
-    float *tmp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    unsigned char *mtmp[2] = {nullptr, nullptr};
+    DeviceBuf<float> tmp[5];
+    DeviceBuf<unsigned char> mtmp[2];
     // the vertices and what hangs off them
-    double *vertices = nullptr, *proxy = nullptr, *colors = nullptr;
-    unsigned *bits = nullptr;
-    int32_t *list = nullptr;
-    long long *offsets = nullptr;
+    DeviceBuf<double> vertices, proxy, colors;
+    DeviceBuf<unsigned> bits;
+    DeviceBuf<int32_t> list;
+    DeviceBuf<long long> offsets;
     std::vector<long long> host_offsets;
-    CmCompactor *compactor = nullptr;
+    Compactor compactor;             // the visibility lists' compaction (compact.h, in colormap.hip)
     // the iteration
-    double *partials = nullptr, *sums = nullptr;
-    unsigned *tickets = nullptr;
+    DeviceBuf<double> partials, sums;
+    DeviceBuf<unsigned> tickets;
     bool proxy_valid = false;
     // the non-rigid map (cfg.anchors > 0; colormap_warp.hip): a warping field per image
     bool warp = false;
     int aw = 0, ah = 0;
     double step = 0.0;
-    double *flow = nullptr;          // n_images x 2 aw ah, the CURRENT fields; host_flow is their copy
+    DeviceBuf<double> flow;          // n_images x 2 aw ah, the CURRENT fields; host_flow is their copy
     std::vector<double> host_flow, host_flow_init;       // (host_flow_init: one field, 2 aw ah)
-    int32_t *keys = nullptr, *sorted = nullptr;          // per visit of the concatenated list: its cell; the vertex ids by cell
-    int *hist = nullptr;             // n_images x bins x tiles: the tiles' histograms
-    int *hist_scan = nullptr;        // their exclusive scan, camera by camera: where (bin, tile) begins in the camera's list
-    double *cell_sums = nullptr;     // n_images x cells x 121
+    DeviceBuf<int32_t> keys, sorted;                     // per visit of the concatenated list: its cell; the vertex ids by cell
+    DeviceBuf<int> hist;             // n_images x bins x tiles: the tiles' histograms
+    DeviceBuf<int> hist_scan;        // their exclusive scan, camera by camera: where (bin, tile) begins in the camera's list
+    DeviceBuf<double> cell_sums;     // n_images x cells x 121
     long long warp_tiles = 0, warp_rows = 0;
 };
 
 // (colormap.hip) the poses -- and the fields of a non-rigid map -- on the device and the proxies of them
 hipError_t cm_refresh_proxy(ColorMapDevice *D);
-// (colormap_warp.hip) the field's buffers at create, the sort's at prepare, all of them at destroy
+// (colormap_warp.hip) the field's buffers at create, the sort's at prepare
 hipError_t color_map_warp_create(ColorMapDevice *D);
 hipError_t color_map_warp_prepare(ColorMapDevice *D);
-void color_map_warp_release(ColorMapDevice *D);
 hipError_t color_map_warp_upload_flow(ColorMapDevice *D);
 
 }  // namespace visma

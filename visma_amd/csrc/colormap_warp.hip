@@ -262,37 +262,26 @@ hipError_t color_map_warp_create(ColorMapDevice *D)
         }
     D->host_flow.resize(n * A * 2);
     for (size_t c = 0; c < n; c++) std::memcpy(D->host_flow.data() + c * A * 2, D->host_flow_init.data(), sizeof(double) * A * 2);
-    hipError_t e = cm_alloc(&D->flow, n * A * 2);
-    if (e == hipSuccess) e = cm_alloc(&D->cell_sums, n * (size_t)(D->aw - 1) * (D->ah - 1) * kCmWarpRow);
-    return e;
-}
-
-void color_map_warp_release(ColorMapDevice *D)
-{
-    void *all[] = {D->flow, D->keys, D->sorted, D->hist, D->hist_scan, D->cell_sums};
-    for (void *p : all)
-        if (p) (void)hipFree(p);
-    D->flow = nullptr; D->keys = nullptr; D->sorted = nullptr; D->hist = nullptr; D->hist_scan = nullptr; D->cell_sums = nullptr;
+    DEV_RESET(D->flow, n * A * 2);
+    DEV_RESET(D->cell_sums, n * (size_t)(D->aw - 1) * (D->ah - 1) * kCmWarpRow);
+    return hipSuccess;
 }
 
 // behind colormap.hip's prepare: the sort's buffers for the lists as they are now
 hipError_t color_map_warp_prepare(ColorMapDevice *D)
 {
-    void *old[] = {D->keys, D->sorted, D->hist, D->hist_scan};
-    for (void *p : old)
-        if (p) (void)hipFree(p);
-    D->keys = nullptr; D->sorted = nullptr; D->hist = nullptr; D->hist_scan = nullptr;
+    D->keys.release(); D->sorted.release(); D->hist.release(); D->hist_scan.release();   // (all four go before the first comes)
     const int n = D->cfg.n_images;
     long long most = 0;
     for (int c = 0; c < n; c++) most = std::max<long long>(most, D->host_offsets[(size_t)c + 1] - D->host_offsets[(size_t)c]);
     D->warp_rows = D->host_offsets[(size_t)n];
     D->warp_tiles = std::max<long long>((most + kWarpTile - 1) / kWarpTile, 1);
     const size_t bins = (size_t)(D->aw - 1) * (D->ah - 1) + 1;
-    hipError_t e = cm_alloc(&D->keys, (size_t)D->warp_rows);
-    if (e == hipSuccess) e = cm_alloc(&D->sorted, (size_t)D->warp_rows);
-    if (e == hipSuccess) e = cm_alloc(&D->hist, (size_t)n * bins * (size_t)D->warp_tiles);
-    if (e == hipSuccess) e = cm_alloc(&D->hist_scan, (size_t)n * bins * (size_t)D->warp_tiles);
-    return e;
+    DEV_RESET(D->keys, (size_t)D->warp_rows);
+    DEV_RESET(D->sorted, (size_t)D->warp_rows);
+    DEV_RESET(D->hist, (size_t)n * bins * (size_t)D->warp_tiles);
+    DEV_RESET(D->hist_scan, (size_t)n * bins * (size_t)D->warp_tiles);
+    return hipSuccess;
 }
 
 hipError_t color_map_warp_upload_flow(ColorMapDevice *D)

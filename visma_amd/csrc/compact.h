@@ -1,6 +1,9 @@
 // compact.h -- count, scan, write: the ordered compaction tsdf.hip (extraction, frame clouds) and colormap.hip (the visible
-// vertex lists) share.  Kernels and the grow-only Compactor; each including file gets its own copy (unnamed namespace).
+// vertex lists) share.  The kernels and the two passes; each including file gets its own copy (unnamed namespace).  The
+// buffers they work in are dev_mem.h's Compactor.
 #pragma once
+
+#include "dev_mem.h"
 
 #include <hip/hip_runtime.h>
 
@@ -84,59 +87,32 @@ __global__ __launch_bounds__(kThreads) void write_kernel(Source s, long long n, 
     }
 }
 
-// what the compaction works in: grow-only
-struct Compactor {
-    int *tile_count = nullptr;
-    long long *tile_offset = nullptr, *total = nullptr;
-    long long capacity = 0;
-    hipError_t ensure(long long tiles)
-    {
-        if (!total) { hipError_t e = hipMalloc(&total, sizeof(long long)); if (e != hipSuccess) return e; }
-        if (tiles <= capacity) return hipSuccess;
-        if (tile_count) (void)hipFree(tile_count);
-        if (tile_offset) (void)hipFree(tile_offset);
-        tile_count = nullptr; tile_offset = nullptr; capacity = 0;
-        hipError_t e = hipMalloc(&tile_count, sizeof(int) * (size_t)tiles);
-        if (e != hipSuccess) return e;
-        e = hipMalloc(&tile_offset, sizeof(long long) * (size_t)tiles);
-        if (e != hipSuccess) return e;
-        capacity = tiles;
-        return hipSuccess;
-    }
-    void release()
-    {
-        if (tile_count) (void)hipFree(tile_count);
-        if (tile_offset) (void)hipFree(tile_offset);
-        if (total) (void)hipFree(total);
-        tile_count = nullptr; tile_offset = nullptr; total = nullptr; capacity = 0;
-    }
-    // the count pass and the scan; *rows on the host (one wait)
-    template <class Source>
-    hipError_t count(const Source &s, long long n, hipStream_t stream, long long *rows)
-    {
-        *rows = 0;
-        if (n <= 0) return hipSuccess;                   // nothing is launched over nothing
-        const long long tiles = (n + kThreads - 1) / kThreads;
-        hipError_t e = ensure(tiles);
-        if (e != hipSuccess) return e;
-        count_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_count);
-        scan_kernel<<<1, kScanThreads, 0, stream>>>(tile_count, tiles, tile_offset, total);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        e = hipMemcpyAsync(rows, total, sizeof(long long), hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(stream);
-    }
-    // ... and the write pass behind it (the Source now holds its output pointers)
-    template <class Source>
-    hipError_t write(const Source &s, long long n, hipStream_t stream)
-    {
-        if (n <= 0) return hipSuccess;
-        const long long tiles = (n + kThreads - 1) / kThreads;
-        write_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, tile_offset);
-        return hipGetLastError();
-    }
-};
+// the count pass and the scan over c's buffers (dev_mem.h: grow-only); *rows on the host (one wait)
+template <class Source>
+hipError_t compact_count(Compactor &c, const Source &s, long long n, hipStream_t stream, long long *rows)
+{
+    *rows = 0;
+    if (n <= 0) return hipSuccess;                       // nothing is launched over nothing
+    const long long tiles = (n + kThreads - 1) / kThreads;
+    hipError_t e = c.ensure(tiles);
+    if (e != hipSuccess) return e;
+    count_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, c.tile_count);
+    scan_kernel<<<1, kScanThreads, 0, stream>>>(c.tile_count, tiles, c.tile_offset, c.total);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = hipMemcpyAsync(rows, c.total, sizeof(long long), hipMemcpyDeviceToHost, stream);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(stream);
+}
+// ... and the write pass behind it (the Source now holds its output pointers)
+template <class Source>
+hipError_t compact_write(const Compactor &c, const Source &s, long long n, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    const long long tiles = (n + kThreads - 1) / kThreads;
+    write_kernel<Source><<<(unsigned)std::min<long long>(tiles, kMaxBlocks), kThreads, 0, stream>>>(s, n, tiles, c.tile_offset);
+    return hipGetLastError();
+}
 
 }  // namespace
 

@@ -528,18 +528,15 @@ std::vector<RingRow> ring_visiting_order(int rings)
     return rows;
 }
 
-hipError_t build_ring_table(int rings, void **d_tab, int *nrows)
+hipError_t build_ring_table(int rings, drv::DevBuf<RingRow> &d_tab)
 {
-    if (rings < 1 || rings > kRingMaxRings || !d_tab || !nrows) return hipErrorInvalidValue;
+    d_tab.release();
+    if (rings < 1 || rings > kRingMaxRings) return hipErrorInvalidValue;
     const std::vector<RingRow> rows = ring_visiting_order(rings);
-    void *d = nullptr;
-    hipError_t e = hipMalloc(&d, sizeof(RingRow) * rows.size());
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(d, rows.data(), sizeof(RingRow) * rows.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return e; }
-    *d_tab = d;
-    *nrows = (int)rows.size();
-    return hipSuccess;
+    if (const int rc = d_tab.reset(rows.size())) return (hipError_t)rc;
+    const hipError_t e = hipMemcpy(d_tab, rows.data(), sizeof(RingRow) * rows.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) d_tab.release();
+    return e;
 }
 
 // *out (device, zeroed by the caller) += the number of entries of count[0 .. n) that are not zero

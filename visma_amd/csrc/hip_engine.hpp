@@ -7,7 +7,7 @@
 //   hip_engine.cpp          the factory
 #pragma once
 #include "engine.hpp"
-#include "dev_buf.h"
+#include "dev_mem.h"
 
 // a DevBuf's reserve / reset: the allocator's error code takes HIP_TRY's way out (err_, VISMA_ICP_ERR_HIP)
 #define BUF_TRY(expr)                                                                      \
@@ -502,15 +502,11 @@ private:
     //   peers_.box[r]                      the peers' mailboxes, opened through IPC
     //   h_stats_, h_cmd_, h_flag_          mapped host memory; h_*_dev_ is the device's alias of the same block
     //   pair_.host / host_dev              the same for the pair passes' granules
-    // d_mbox_ and d_cmd_block_ come from hipExtMallocWithFlags, d_vox_out_ and d_ring_tab_ from the module that fills
-    // them: plain hipFree memory that the buffer adopts.
-    static int device_alloc(void **p, size_t bytes)
-    {
-        const hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; }
-        return (int)e;
-    }
-    static void device_free(void *p) { (void)hipFree(p); }
+    // d_mbox_ and d_cmd_block_ come from hipExtMallocWithFlags: plain hipFree memory that the buffer adopts.  d_vox_out_ and
+    // d_ring_tab_ are filled by the module that computes them (voxel.hip, grid_ring.hip).
+    // device_memory() is dev_mem.h's, the one the rest of the library allocates through.  Its rounding of zero bytes up to
+    // one never shows here: a pooled request is at least 256 bytes, and every unpooled reset() asks for a count that is a
+    // constant, max(n, 1), or larger than the count it replaces.
     static int pinned_alloc(void **p, size_t bytes)
     {
         const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
@@ -518,7 +514,6 @@ private:
         return (int)e;
     }
     static void pinned_free(void *p) { (void)hipHostFree(p); }
-    static RawAlloc device_memory() { return RawAlloc{&device_alloc, &device_free}; }
     static RawAlloc pinned_memory() { return RawAlloc{&pinned_alloc, &pinned_free}; }
     DevPool pool_{device_memory()};
     // the clouds: fp32 and f64 copies, the target's cell-sorted copies (f64, packed fp32 for the exact search), the raw

@@ -277,13 +277,13 @@ int HipEngine::set_target_voxel_f64(const double *xyz, int64_t n, int stride, do
                                    hipMemcpyHostToDevice, stream_));
         }
     }
-    double *d_o = nullptr;
+    DevBuf<double> d_o(device_memory());
     int64_t nvox = 0;
-    hipError_t e = voxel_down_sample_core((const double *)d_in, nullptr, nullptr, n, voxel, &d_o, nullptr, nullptr, &nvox,
+    hipError_t e = voxel_down_sample_core((const double *)d_in, nullptr, nullptr, n, voxel, d_o, nullptr, nullptr, &nvox,
                                           stream_);
     d_in.release();
     if (e != hipSuccess) { err_ = std::string("voxel_down_sample: ") + hipGetErrorString(e); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
-    d_vox_out_.adopt(d_o, 3 * (size_t)std::max<int64_t>(nvox, 0));
+    d_vox_out_ = std::move(d_o);
     vox_out_n_ = nvox;
     int rc = ensure_target(nvox);
     if (rc) return rc;
@@ -293,13 +293,13 @@ int HipEngine::set_target_voxel_f64(const double *xyz, int64_t n, int stride, do
             const int64_t nch = (nvox + kHostChunk - 1) / kHostChunk;
             DevBuf<double> d_part(device_memory());
             BUF_TRY(d_part.reset((size_t)(3 * nch + 3)));
-            hipError_t e2 = centroid_device(d_o, nvox, kHostChunk, d_part, d_part + 3 * nch, stream_);
+            hipError_t e2 = centroid_device(d_vox_out_, nvox, kHostChunk, d_part, d_part + 3 * nch, stream_);
             if (e2 == hipSuccess) e2 = hipMemcpyAsync(c, d_part + 3 * nch, sizeof(double) * 3, hipMemcpyDeviceToHost, stream_);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream_);
             d_part.release();
             if (e2 != hipSuccess) { err_ = std::string("centroid: ") + hipGetErrorString(e2); (void)hipGetLastError(); return VISMA_ICP_ERR_HIP; }
         }
-        HIP_TRY(launch_expand_f64(d_o, nvox, c, (float4 *)d_tgt_, (Pt64 *)d_tgt64_, stream_));
+        HIP_TRY(launch_expand_f64(d_vox_out_, nvox, c, (float4 *)d_tgt_, (Pt64 *)d_tgt64_, stream_));
     } else if (compute_centre) {
         c[0] = c[1] = c[2] = 0.0;
     }
@@ -660,12 +660,8 @@ int HipEngine::build_grid(double max_dist)
             if (fine.ring > 0) {
                 // the rows' visiting order around a query (the same for every query: a table per ring count)
                 if (!d_ring_tab_ || ring_tab_rings_ != fine.ring) {
-                    d_ring_tab_.release();
                     ring_tab_rings_ = 0;
-                    int nrows = 0;
-                    void *tab = nullptr;
-                    HIP_TRY(build_ring_table(fine.ring, &tab, &nrows));
-                    d_ring_tab_.adopt((RingRow *)tab, (size_t)nrows);
+                    HIP_TRY(build_ring_table(fine.ring, d_ring_tab_));
                     ring_tab_rings_ = fine.ring;
                 }
                 grid_ = fine;

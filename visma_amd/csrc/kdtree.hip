@@ -9,7 +9,7 @@
 //   kd_write_kernel     pass in which every query fills its own CSR segment as a heap and sorts it in place
 // One thread per query in the caller's order, one writer per output element, no floating-point atomics.
 #include "compact.h"
-#include "dev_buf.h"
+#include "dev_mem.h"
 #include "nn_list.h"
 
 #include <math.h>
@@ -134,36 +134,25 @@ __global__ __launch_bounds__(NTH) void kd_write_kernel(KdArgs a)
     L.sort();
 }
 
-int raw_alloc(void **p, size_t bytes)
-{
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
-    return (int)e;
-}
-void raw_free(void *p) { (void)hipFree(p); }
-const drv::RawAlloc kRaw = {raw_alloc, raw_free};
-
-#define KD_RESERVE(buf, count)                                                 \
-    do { if (int rc_ = (buf).reserve(count)) return (hipError_t)rc_; } while (0)
 
 }  // namespace
 
 struct KdTreeDevice {
     int64_t n = 0;
     double origin[3] = {0.0, 0.0, 0.0};
-    drv::DevBuf<double> xyz{kRaw};               // the cloud, n x 3
+    DeviceBuf<double> xyz;               // the cloud, n x 3
     // the grid of the last search: built for a radius (Radius / Hybrid) or for a knn (NnGrid::build sizes the cells)
     std::unique_ptr<NnGrid> grid;
     bool grid_knn = false;
     double grid_radius = 0.0;
     int grid_cap = 0;
     // what a call works in: grow-only
-    drv::DevBuf<double> q{kRaw}, out_d2{kRaw}, heap_d2{kRaw};
-    drv::DevBuf<int> out_idx{kRaw}, heap_id{kRaw}, cnt{kRaw};
-    drv::DevBuf<long long> offsets{kRaw};        // nq + 1: the last is the total
+    DeviceBuf<double> q, out_d2, heap_d2;
+    DeviceBuf<int> out_idx, heap_id, cnt;
+    DeviceBuf<long long> offsets;        // nq + 1: the last is the total
     // the lists of the last Radius search
-    drv::DevBuf<int> r_idx{kRaw};
-    drv::DevBuf<double> r_d2{kRaw};
+    DeviceBuf<int> r_idx;
+    DeviceBuf<double> r_d2;
     int64_t r_total = -1;                        // -1: none
 
     hipError_t ensure_grid(bool knn, double radius, int cap, hipStream_t stream)
@@ -197,7 +186,7 @@ hipError_t kdtree_device_create(const double *h_xyz, int64_t n, hipStream_t stre
     std::unique_ptr<KdTreeDevice> T(new KdTreeDevice);
     T->n = n;
     nn_binning_origin(h_xyz, n, T->origin);
-    KD_RESERVE(T->xyz, 3 * (size_t)n);
+    DEV_RESERVE(T->xyz, 3 * (size_t)n);
     VISMA_TRY(hipMemcpyAsync(T->xyz.get(), h_xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, stream));
     VISMA_TRY(hipStreamSynchronize(stream));
     *out = T.release();
@@ -225,13 +214,13 @@ hipError_t kdtree_device_search(KdTreeDevice *T, bool knn, const double *h_q, in
     const bool heap = eff > kNormalsMaxList;
     // slabs: the rows of one launch, and its heaps, hold kKdTreeSlabEntries entries at the most (one query where a row is longer)
     const int64_t slab = std::min<int64_t>(nq, std::max<int64_t>(1, kKdTreeSlabEntries / cap));
-    KD_RESERVE(T->q, 3 * (size_t)slab);
-    KD_RESERVE(T->out_idx, (size_t)slab * (size_t)cap);
-    KD_RESERVE(T->out_d2, (size_t)slab * (size_t)cap);
-    KD_RESERVE(T->cnt, (size_t)slab);
+    DEV_RESERVE(T->q, 3 * (size_t)slab);
+    DEV_RESERVE(T->out_idx, (size_t)slab * (size_t)cap);
+    DEV_RESERVE(T->out_d2, (size_t)slab * (size_t)cap);
+    DEV_RESERVE(T->cnt, (size_t)slab);
     if (heap) {
-        KD_RESERVE(T->heap_d2, (size_t)slab * (size_t)eff);
-        KD_RESERVE(T->heap_id, (size_t)slab * (size_t)eff);
+        DEV_RESERVE(T->heap_d2, (size_t)slab * (size_t)eff);
+        DEV_RESERVE(T->heap_id, (size_t)slab * (size_t)eff);
     }
     for (int64_t at = 0; at < nq; at += slab) {
         const int64_t m = std::min<int64_t>(slab, nq - at);
@@ -261,9 +250,9 @@ hipError_t kdtree_device_search_radius(KdTreeDevice *T, const double *h_q, int64
     h_offsets[0] = 0;
     if (nq <= 0) { T->r_total = 0; return hipSuccess; }
     VISMA_TRY(T->ensure_grid(false, radius, 0, stream));
-    KD_RESERVE(T->q, 3 * (size_t)nq);
-    KD_RESERVE(T->cnt, (size_t)nq);
-    KD_RESERVE(T->offsets, (size_t)nq + 1);
+    DEV_RESERVE(T->q, 3 * (size_t)nq);
+    DEV_RESERVE(T->cnt, (size_t)nq);
+    DEV_RESERVE(T->offsets, (size_t)nq + 1);
     VISMA_TRY(hipMemcpyAsync(T->q.get(), h_q, sizeof(double) * 3 * (size_t)nq, hipMemcpyHostToDevice, stream));
     KdArgs a = T->args(nq);
     a.r2d = nn_radius2(radius);
@@ -276,8 +265,8 @@ hipError_t kdtree_device_search_radius(KdTreeDevice *T, const double *h_q, int64
     VISMA_TRY(hipStreamSynchronize(stream));
     *total = h_offsets[nq];
     if (*total > kKdTreeMaxRadiusEntries) return hipErrorOutOfMemory;
-    KD_RESERVE(T->r_idx, (size_t)*total);
-    KD_RESERVE(T->r_d2, (size_t)*total);
+    DEV_RESERVE(T->r_idx, (size_t)*total);
+    DEV_RESERVE(T->r_d2, (size_t)*total);
     a.idx = T->r_idx.get(); a.d2 = T->r_d2.get(); a.offsets = T->offsets.get();
     VISMA_TRY(nn_launch(0, nq, a, stream, [](auto nth) { return &kd_write_kernel<decltype(nth)::value>; }));
     VISMA_TRY(hipStreamSynchronize(stream));

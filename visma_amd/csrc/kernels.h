@@ -1,6 +1,8 @@
 // kernels.h -- launch interface of the gfx950 ICP kernels (kernels.hip).
 #pragma once
 
+#include "dev_buf.h"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <vector>
@@ -424,11 +426,11 @@ hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double 
 hipError_t voxel_down_sample_device(const double *h_xyz, const double *h_nrm, const double *h_col,
                                     int64_t n, double voxel, double *h_out_xyz, double *h_out_nrm,
                                     double *h_out_col, int64_t *n_out, hipStream_t stream);
-// ... the device part alone (resident input, hipMalloc'ed resident output that the caller frees), and the centroid
-// of resident points with the host's summation order (centroid_f64): what the device-resident caller pipeline uses
+// ... the device part alone (resident input; the resident output in the caller's buffers, d_onrm / d_ocol or NULL), and the
+// centroid of resident points with the host's summation order (centroid_f64): what the device-resident caller pipeline uses
 hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, const double *d_col, int64_t n, double voxel,
-                                  double **d_oxyz_out, double **d_onrm_out, double **d_ocol_out, int64_t *n_out,
-                                  hipStream_t stream);
+                                  drv::DevBuf<double> &d_oxyz, drv::DevBuf<double> *d_onrm, drv::DevBuf<double> *d_ocol,
+                                  int64_t *n_out, hipStream_t stream);
 hipError_t centroid_device(const double *d_xyz, int64_t n, int64_t chunk, double *d_part, double *d_out, hipStream_t stream);
 // counting sort of the target by cell: start[ncell+1], sorted[nt] = (x,y,z, bits(orig index))
 // tgt64 / sorted64 (both or neither): the f64 copy of the target is scattered in the same order
@@ -550,7 +552,7 @@ hipError_t launch_nn_ring(const SearchArgs &a, int nblocks, hipStream_t stream);
 // the persistent sweep: nprob problems of search_blocks(ns, kCoopLanes, max_blocks) workgroups, one query per lane
 hipError_t launch_nn_wave_sweep(const SearchArgs &a, const SweepArgs &sa, hipStream_t stream);
 // the visiting order of a grid with g.ring = rings (a new device buffer the caller owns: hipFree); *nrows = (2 rings + 1)^2
-hipError_t build_ring_table(int rings, void **d_tab, int *nrows);
+hipError_t build_ring_table(int rings, drv::DevBuf<RingRow> &d_tab);
 // ... the same order on the host (empty for rings outside 1 .. kRingMaxRings)
 std::vector<RingRow> ring_visiting_order(int rings);
 // *out (device, zeroed by the caller) += the number of non-zero entries of count[0 .. n)

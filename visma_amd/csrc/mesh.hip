@@ -329,10 +329,9 @@ hipError_t launch_exclusive_scan_u32(const unsigned *in, long long n, unsigned *
 // ---------------------------------------------------------------------------
 namespace {
 
-#define MESH_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) return e__; } while (0)
-
 struct DevMesh {
-    DBuf V, F;
+    DeviceBuf<double> V;
+    DeviceBuf<int> F;
     int64_t nv = 0, nf = 0;
     double lo[3], hi[3];                             // vertex bounding box (host)
 };
@@ -349,15 +348,16 @@ hipError_t upload_mesh(const double *h_V, int64_t nv, const int32_t *h_F, int64_
             if (v > m.hi[a]) m.hi[a] = v;
         }
     m.nv = nv; m.nf = nf;
-    MESH_TRY(m.V.alloc(sizeof(double) * 3 * nv));
-    MESH_TRY(m.F.alloc(sizeof(int) * 3 * nf));
-    if (nv > 0) MESH_TRY(hipMemcpyAsync(m.V.p, h_V, sizeof(double) * 3 * nv, hipMemcpyHostToDevice, stream));
-    if (nf > 0) MESH_TRY(hipMemcpyAsync(m.F.p, h_F, sizeof(int) * 3 * nf, hipMemcpyHostToDevice, stream));
+    DEV_RESET(m.V, 3 * nv);
+    DEV_RESET(m.F, 3 * nf);
+    if (nv > 0) VISMA_TRY(hipMemcpyAsync(m.V, h_V, sizeof(double) * 3 * nv, hipMemcpyHostToDevice, stream));
+    if (nf > 0) VISMA_TRY(hipMemcpyAsync(m.F, h_F, sizeof(int) * 3 * nf, hipMemcpyHostToDevice, stream));
     return hipSuccess;
 }
 
 struct DevBvh {
-    DBuf tri, faceid, nodes;
+    DeviceBuf<double> tri, nodes;
+    DeviceBuf<unsigned> faceid;
     int64_t nf = 0, P = 0;
     bool tree = false;
     MortonParams mp;
@@ -369,12 +369,12 @@ hipError_t build_search(const DevMesh &m, int method, DevBvh &b, hipStream_t str
     const int64_t nf = m.nf;
     b.nf = nf;
     b.tree = method == 2 || (method == 0 && nf >= 64);
-    MESH_TRY(b.tri.alloc(sizeof(double) * 9 * nf));
+    DEV_RESET(b.tri, 9 * nf);
     if (nf == 0) { b.tree = false; return hipSuccess; }
     const unsigned fb = (unsigned)((nf + 255) / 256);
     if (!b.tree) {
-        hipLaunchKernelGGL(tri_gather_kernel, dim3(fb), dim3(256), 0, stream, m.V.as<double>(), m.F.as<int>(),
-                           (const unsigned *)nullptr, (long long)nf, b.tri.as<double>());
+        hipLaunchKernelGGL(tri_gather_kernel, dim3(fb), dim3(256), 0, stream, m.V, m.F,
+                           (const unsigned *)nullptr, (long long)nf, b.tri);
         return hipGetLastError();
     }
     if (nf >= ((int64_t)1 << 25)) return hipErrorInvalidValue;
@@ -382,25 +382,26 @@ hipError_t build_search(const DevMesh &m, int method, DevBvh &b, hipStream_t str
     const MortonParams &mp = b.mp;
     double ext = 0.0;
     for (int a = 0; a < 3; a++) ext = fmax(ext, fmax(fabs(m.lo[a]), fabs(m.hi[a])));
-    DBuf key, key2, val, tmp;
-    MESH_TRY(key.alloc(sizeof(unsigned) * nf));
-    MESH_TRY(key2.alloc(sizeof(unsigned) * nf));
-    MESH_TRY(val.alloc(sizeof(unsigned) * nf));
-    MESH_TRY(b.faceid.alloc(sizeof(unsigned) * nf));
-    hipLaunchKernelGGL(tri_code_kernel, dim3(fb), dim3(256), 0, stream, m.V.as<double>(), m.F.as<int>(), (long long)nf,
-                       mp, key.as<unsigned>(), val.as<unsigned>());
-    MESH_TRY(morton_sort(key.as<unsigned>(), key2.as<unsigned>(), val.as<unsigned>(), b.faceid.as<unsigned>(), nf, tmp,
+    DeviceBuf<unsigned> key, key2, val;
+    DeviceBuf<char> tmp;
+    DEV_RESET(key, nf);
+    DEV_RESET(key2, nf);
+    DEV_RESET(val, nf);
+    DEV_RESET(b.faceid, nf);
+    hipLaunchKernelGGL(tri_code_kernel, dim3(fb), dim3(256), 0, stream, m.V, m.F, (long long)nf,
+                       mp, key, val);
+    VISMA_TRY(morton_sort(key, key2, val, b.faceid, nf, tmp,
                          stream));
-    hipLaunchKernelGGL(tri_gather_kernel, dim3(fb), dim3(256), 0, stream, m.V.as<double>(), m.F.as<int>(),
-                       b.faceid.as<unsigned>(), (long long)nf, b.tri.as<double>());
+    hipLaunchKernelGGL(tri_gather_kernel, dim3(fb), dim3(256), 0, stream, m.V, m.F,
+                       b.faceid, (long long)nf, b.tri);
     const int64_t nleaf = (nf + kLeaf - 1) / kLeaf;
     int64_t P = 1;
     while (P < nleaf) P <<= 1;
     b.P = P;
-    MESH_TRY(b.nodes.alloc(sizeof(double) * 6 * 2 * P));
-    hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, b.tri.as<double>(),
-                       (long long)nf, (long long)P, ldexp(ext, -40), b.nodes.as<double>());
-    MESH_TRY(build_bvh_levels(b.nodes.as<double>(), P, stream));
+    DEV_RESET(b.nodes, 6 * 2 * P);
+    hipLaunchKernelGGL(bvh_leaf_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, stream, b.tri,
+                       (long long)nf, (long long)P, ldexp(ext, -40), b.nodes);
+    VISMA_TRY(build_bvh_levels(b.nodes, P, stream));
     // the temporaries above are freed when this function returns: wait for the kernels using them
     return hipStreamSynchronize(stream);
 }
@@ -411,40 +412,41 @@ hipError_t launch_query(const DevBvh &b, const double *d_P, int64_t np, double *
     if (np <= 0) return hipSuccess;
     if (!b.tree) {
         hipLaunchKernelGGL(point_mesh_kernel, dim3((unsigned)((np + kMeshBlock - 1) / kMeshBlock)), dim3(kMeshBlock), 0,
-                           stream, d_P, (long long)np, b.tri.as<double>(), (long long)b.nf, d_d2, d_face, d_cl);
+                           stream, d_P, (long long)np, b.tri, (long long)b.nf, d_d2, d_face, d_cl);
         return hipGetLastError();
     }
-    DBuf key, key2, val, order, tmp;
+    DeviceBuf<unsigned> key, key2, val, order;
+    DeviceBuf<char> tmp;
     const bool sorted = np >= 4096 && np < ((int64_t)1 << 31);
     if (sorted) {
-        MESH_TRY(key.alloc(sizeof(unsigned) * np));
-        MESH_TRY(key2.alloc(sizeof(unsigned) * np));
-        MESH_TRY(val.alloc(sizeof(unsigned) * np));
-        MESH_TRY(order.alloc(sizeof(unsigned) * np));
+        DEV_RESET(key, np);
+        DEV_RESET(key2, np);
+        DEV_RESET(val, np);
+        DEV_RESET(order, np);
         hipLaunchKernelGGL(point_code_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, stream, d_P,
-                           (long long)np, b.mp, key.as<unsigned>(), val.as<unsigned>());
-        MESH_TRY(morton_sort(key.as<unsigned>(), key2.as<unsigned>(), val.as<unsigned>(), order.as<unsigned>(), np,
+                           (long long)np, b.mp, key, val);
+        VISMA_TRY(morton_sort(key, key2, val, order, np,
                              tmp, stream));
     }
     int depth = 2;                                   // levels below the root + slack
     for (int64_t q = b.P; q > 1; q >>= 1) depth++;
     hipLaunchKernelGGL(point_mesh_bvh_kernel, dim3((unsigned)((np + kBvhBlock - 1) / kBvhBlock)), dim3(kBvhBlock),
-                       (size_t)depth * kBvhBlock * 8, stream, d_P, (long long)np, b.tri.as<double>(),
-                       b.faceid.as<unsigned>(), b.nodes.as<double>(), (long long)b.nf, (long long)b.P, depth,
-                       sorted ? order.as<unsigned>() : (const unsigned *)nullptr, d_d2, d_face, d_cl);
-    MESH_TRY(hipGetLastError());
+                       (size_t)depth * kBvhBlock * 8, stream, d_P, (long long)np, b.tri,
+                       b.faceid, b.nodes, (long long)b.nf, (long long)b.P, depth,
+                       sorted ? order.get() : (const unsigned *)nullptr, d_d2, d_face, d_cl);
+    VISMA_TRY(hipGetLastError());
     return sorted ? hipStreamSynchronize(stream) : hipSuccess;     // the temporaries die here
 }
 
 struct Events {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    hipError_t create() { MESH_TRY(hipEventCreate(&e0)); return hipEventCreate(&e1); }
+    hipError_t create() { VISMA_TRY(hipEventCreate(&e0)); return hipEventCreate(&e1); }
 };
 
 // sample on the device; leaves the compacted points in `out` (n rows allocated), *m rows valid
 hipError_t sample_on_device(const double *h_V, const int32_t *h_F, const DevMesh &mesh, int64_t n, int quirks,
-                            unsigned long long seed, const double *h_uniforms, DBuf &out, int64_t *m,
+                            unsigned long long seed, const double *h_uniforms, DevBuf<double> &out, int64_t *m,
                             hipStream_t stream)
 {
     const int64_t nf = mesh.nf;
@@ -465,37 +467,38 @@ hipError_t sample_on_device(const double *h_V, const int32_t *h_F, const DevMesh
     cdf[0] /= total;
     for (int64_t i = 1; i < nf; i++) cdf[i] = cdf[i - 1] + cdf[i] / total;
 
-    DBuf d_cdf, d_u, d_pts, d_valid, d_pos, d_bsum;
+    DeviceBuf<double> d_cdf, d_u, d_pts;
+    DeviceBuf<unsigned> d_valid, d_pos, d_bsum;
     unsigned last_pos = 0, last_valid = 0;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    MESH_TRY(d_cdf.alloc(sizeof(double) * nf));
-    MESH_TRY(d_pts.alloc(sizeof(double) * 3 * n));
-    MESH_TRY(out.alloc(sizeof(double) * 3 * n));
-    MESH_TRY(d_valid.alloc(sizeof(unsigned) * (n + 1)));
-    MESH_TRY(d_pos.alloc(sizeof(unsigned) * (n + 1)));
-    MESH_TRY(d_bsum.alloc(sizeof(unsigned) * (n / 2048 + 2)));
-    MESH_TRY(hipMemcpyAsync(d_cdf.p, cdf.data(), sizeof(double) * nf, hipMemcpyHostToDevice, stream));
+    DEV_RESET(d_cdf, nf);
+    DEV_RESET(d_pts, 3 * n);
+    DEV_RESET(out, 3 * n);
+    DEV_RESET(d_valid, (n + 1));
+    DEV_RESET(d_pos, (n + 1));
+    DEV_RESET(d_bsum, (n / 2048 + 2));
+    VISMA_TRY(hipMemcpyAsync(d_cdf, cdf.data(), sizeof(double) * nf, hipMemcpyHostToDevice, stream));
     if (h_uniforms) {
-        MESH_TRY(d_u.alloc(sizeof(double) * 3 * n));
-        MESH_TRY(hipMemcpyAsync(d_u.p, h_uniforms, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+        DEV_RESET(d_u, 3 * n);
+        VISMA_TRY(hipMemcpyAsync(d_u, h_uniforms, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
     }
-    hipLaunchKernelGGL(sample_mesh_kernel, dim3(blocks), dim3(256), 0, stream, mesh.V.as<double>(), mesh.F.as<int>(),
-                       d_cdf.as<double>(), (long long)nf, (long long)n, quirks, seed, d_u.as<double>(),
-                       d_pts.as<double>(), d_valid.as<unsigned>());
+    hipLaunchKernelGGL(sample_mesh_kernel, dim3(blocks), dim3(256), 0, stream, mesh.V, mesh.F,
+                       d_cdf, (long long)nf, (long long)n, quirks, seed, d_u,
+                       d_pts, d_valid);
     if (quirks) {
-        MESH_TRY(launch_exclusive_scan_u32(d_valid.as<unsigned>(), (long long)n, d_bsum.as<unsigned>(),
-                                           d_pos.as<unsigned>(), stream));
-        hipLaunchKernelGGL(compact_points_kernel, dim3(blocks), dim3(256), 0, stream, d_pts.as<double>(),
-                           d_valid.as<unsigned>(), d_pos.as<unsigned>(), (long long)n, out.as<double>());
-        MESH_TRY(hipGetLastError());
-        MESH_TRY(hipMemcpyAsync(&last_pos, d_pos.as<unsigned>() + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        MESH_TRY(hipMemcpyAsync(&last_valid, d_valid.as<unsigned>() + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        MESH_TRY(hipStreamSynchronize(stream));
+        VISMA_TRY(launch_exclusive_scan_u32(d_valid, (long long)n, d_bsum,
+                                           d_pos, stream));
+        hipLaunchKernelGGL(compact_points_kernel, dim3(blocks), dim3(256), 0, stream, d_pts,
+                           d_valid, d_pos, (long long)n, out);
+        VISMA_TRY(hipGetLastError());
+        VISMA_TRY(hipMemcpyAsync(&last_pos, d_pos + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        VISMA_TRY(hipMemcpyAsync(&last_valid, d_valid + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        VISMA_TRY(hipStreamSynchronize(stream));
         *m = (int64_t)last_pos + (int64_t)last_valid;
     } else {                                        // every draw yields a point: no compaction
-        MESH_TRY(hipGetLastError());
-        MESH_TRY(hipMemcpyAsync(out.p, d_pts.p, sizeof(double) * 3 * n, hipMemcpyDeviceToDevice, stream));
-        MESH_TRY(hipStreamSynchronize(stream));
+        VISMA_TRY(hipGetLastError());
+        VISMA_TRY(hipMemcpyAsync(out, d_pts, sizeof(double) * 3 * n, hipMemcpyDeviceToDevice, stream));
+        VISMA_TRY(hipStreamSynchronize(stream));
         *m = n;
     }
     return hipSuccess;
@@ -512,30 +515,31 @@ hipError_t point_mesh_distance_device(const double *h_P, int64_t np, const doubl
     DevMesh mesh;
     DevBvh bvh;
     Events ev;
-    DBuf d_P, d_d2, d_face, d_cl;
+    DeviceBuf<double> d_P, d_d2, d_cl;
+    DeviceBuf<int> d_face;
     float ms = 0.f;
-    MESH_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
+    VISMA_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
     if (np <= 0) return hipSuccess;
-    MESH_TRY(ev.create());
-    MESH_TRY(hipEventRecord(ev.e0, stream));
-    MESH_TRY(build_search(mesh, method, bvh, stream));
-    MESH_TRY(hipEventRecord(ev.e1, stream));
-    MESH_TRY(hipEventSynchronize(ev.e1));
-    MESH_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    VISMA_TRY(ev.create());
+    VISMA_TRY(hipEventRecord(ev.e0, stream));
+    VISMA_TRY(build_search(mesh, method, bvh, stream));
+    VISMA_TRY(hipEventRecord(ev.e1, stream));
+    VISMA_TRY(hipEventSynchronize(ev.e1));
+    VISMA_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     if (build_ms) *build_ms = ms;
-    MESH_TRY(d_P.alloc(sizeof(double) * 3 * np));
-    MESH_TRY(d_d2.alloc(sizeof(double) * np));
-    MESH_TRY(d_face.alloc(sizeof(int) * np));
-    MESH_TRY(d_cl.alloc(sizeof(double) * 3 * np));
-    MESH_TRY(hipMemcpyAsync(d_P.p, h_P, sizeof(double) * 3 * np, hipMemcpyHostToDevice, stream));
-    MESH_TRY(hipEventRecord(ev.e0, stream));
-    MESH_TRY(launch_query(bvh, d_P.as<double>(), np, d_d2.as<double>(), d_face.as<int>(), d_cl.as<double>(), stream));
-    MESH_TRY(hipEventRecord(ev.e1, stream));
-    MESH_TRY(hipMemcpyAsync(h_d2, d_d2.p, sizeof(double) * np, hipMemcpyDeviceToHost, stream));
-    if (h_face) MESH_TRY(hipMemcpyAsync(h_face, d_face.p, sizeof(int) * np, hipMemcpyDeviceToHost, stream));
-    if (h_closest) MESH_TRY(hipMemcpyAsync(h_closest, d_cl.p, sizeof(double) * 3 * np, hipMemcpyDeviceToHost, stream));
-    MESH_TRY(hipStreamSynchronize(stream));
-    if (kernel_ms) MESH_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
+    DEV_RESET(d_P, 3 * np);
+    DEV_RESET(d_d2, np);
+    DEV_RESET(d_face, np);
+    DEV_RESET(d_cl, 3 * np);
+    VISMA_TRY(hipMemcpyAsync(d_P, h_P, sizeof(double) * 3 * np, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(hipEventRecord(ev.e0, stream));
+    VISMA_TRY(launch_query(bvh, d_P, np, d_d2, d_face, d_cl, stream));
+    VISMA_TRY(hipEventRecord(ev.e1, stream));
+    VISMA_TRY(hipMemcpyAsync(h_d2, d_d2, sizeof(double) * np, hipMemcpyDeviceToHost, stream));
+    if (h_face) VISMA_TRY(hipMemcpyAsync(h_face, d_face, sizeof(int) * np, hipMemcpyDeviceToHost, stream));
+    if (h_closest) VISMA_TRY(hipMemcpyAsync(h_closest, d_cl, sizeof(double) * 3 * np, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) VISMA_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
     return hipSuccess;
 }
 
@@ -546,11 +550,11 @@ hipError_t sample_mesh_device(const double *h_V, int64_t nv, const int32_t *h_F,
     *n_out = 0;
     if (nf <= 0 || n <= 0) return hipSuccess;
     DevMesh mesh;
-    DBuf pts;
+    DeviceBuf<double> pts;
     int64_t m = 0;
-    MESH_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
-    MESH_TRY(sample_on_device(h_V, h_F, mesh, n, quirks, seed, h_uniforms, pts, &m, stream));
-    if (m > 0) MESH_TRY(hipMemcpy(h_out, pts.p, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
+    VISMA_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
+    VISMA_TRY(sample_on_device(h_V, h_F, mesh, n, quirks, seed, h_uniforms, pts, &m, stream));
+    if (m > 0) VISMA_TRY(hipMemcpy(h_out, pts, sizeof(double) * 3 * m, hipMemcpyDeviceToHost));
     *n_out = m;
     return hipSuccess;
 }
@@ -582,19 +586,19 @@ hipError_t sample_mesh_transformed_device(const double *h_V, int64_t nv, const i
     if (nf <= 0 || n <= 0) return hipSuccess;
     if (n > room) return hipErrorInvalidValue;
     DevMesh mesh;
-    DBuf pts, d_T;
+    DeviceBuf<double> pts, d_T;
     int64_t m = 0;
-    MESH_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
-    MESH_TRY(sample_on_device(h_V, h_F, mesh, n, quirks, seed, nullptr, pts, &m, stream));
+    VISMA_TRY(upload_mesh(h_V, nv, h_F, nf, mesh, stream));
+    VISMA_TRY(sample_on_device(h_V, h_F, mesh, n, quirks, seed, nullptr, pts, &m, stream));
     if (m > 0) {
         if (T16) {
-            MESH_TRY(d_T.alloc(sizeof(double) * 16));
-            MESH_TRY(hipMemcpyAsync(d_T.p, T16, sizeof(double) * 16, hipMemcpyHostToDevice, stream));
+            DEV_RESET(d_T, 16);
+            VISMA_TRY(hipMemcpyAsync(d_T, T16, sizeof(double) * 16, hipMemcpyHostToDevice, stream));
         }
         hipLaunchKernelGGL(transform_points_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream,
-                           pts.as<double>(), (long long)m, T16 ? d_T.as<double>() : (const double *)nullptr, d_out);
-        MESH_TRY(hipGetLastError());
-        MESH_TRY(hipStreamSynchronize(stream));          // (pts and d_T are freed on return)
+                           pts, (long long)m, T16 ? d_T.get() : (const double *)nullptr, d_out);
+        VISMA_TRY(hipGetLastError());
+        VISMA_TRY(hipStreamSynchronize(stream));          // (pts and d_T are freed on return)
     }
     *m_out = m;
     return hipSuccess;
@@ -615,27 +619,27 @@ hipError_t surface_distances_device(const double *h_Vs, int64_t nvs, const int32
     DevMesh src, tgt;
     DevBvh bvh;
     Events ev;
-    DBuf pts, d_d2;
+    DeviceBuf<double> pts, d_d2;
     int64_t m = 0;
     float ms = 0.f;
-    MESH_TRY(upload_mesh(h_Vs, nvs, h_Fs, nfs, src, stream));
-    MESH_TRY(upload_mesh(h_Vt, nvt, h_Ft, nft, tgt, stream));
-    MESH_TRY(ev.create());
-    MESH_TRY(hipEventRecord(ev.e0, stream));
-    MESH_TRY(build_search(tgt, method, bvh, stream));
-    MESH_TRY(hipEventRecord(ev.e1, stream));
-    MESH_TRY(sample_on_device(h_Vs, h_Fs, src, n, quirks, seed, nullptr, pts, &m, stream));
-    MESH_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    VISMA_TRY(upload_mesh(h_Vs, nvs, h_Fs, nfs, src, stream));
+    VISMA_TRY(upload_mesh(h_Vt, nvt, h_Ft, nft, tgt, stream));
+    VISMA_TRY(ev.create());
+    VISMA_TRY(hipEventRecord(ev.e0, stream));
+    VISMA_TRY(build_search(tgt, method, bvh, stream));
+    VISMA_TRY(hipEventRecord(ev.e1, stream));
+    VISMA_TRY(sample_on_device(h_Vs, h_Fs, src, n, quirks, seed, nullptr, pts, &m, stream));
+    VISMA_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     if (build_ms) *build_ms = ms;
     if (m == 0) return hipSuccess;
-    MESH_TRY(d_d2.alloc(sizeof(double) * m));
-    MESH_TRY(hipEventRecord(ev.e0, stream));
-    MESH_TRY(launch_query(bvh, pts.as<double>(), m, d_d2.as<double>(), nullptr, nullptr, stream));
-    MESH_TRY(hipEventRecord(ev.e1, stream));
-    hipLaunchKernelGGL(sqrt_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, d_d2.as<double>(), (long long)m);
-    MESH_TRY(hipMemcpyAsync(h_dist, d_d2.p, sizeof(double) * m, hipMemcpyDeviceToHost, stream));
-    MESH_TRY(hipStreamSynchronize(stream));
-    if (kernel_ms) MESH_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
+    DEV_RESET(d_d2, m);
+    VISMA_TRY(hipEventRecord(ev.e0, stream));
+    VISMA_TRY(launch_query(bvh, pts, m, d_d2, nullptr, nullptr, stream));
+    VISMA_TRY(hipEventRecord(ev.e1, stream));
+    hipLaunchKernelGGL(sqrt_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, d_d2, (long long)m);
+    VISMA_TRY(hipMemcpyAsync(h_dist, d_d2, sizeof(double) * m, hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
+    if (kernel_ms) VISMA_TRY(hipEventElapsedTime(kernel_ms, ev.e0, ev.e1));
     *n_out = m;
     return hipSuccess;
 }

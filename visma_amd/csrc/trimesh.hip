@@ -20,7 +20,7 @@
 //                           mark the same vertex all store the same 1)
 // The passes are streaming: grid-capped stride loops of 256 lanes (compact.h's shape).
 #include "compact.h"
-#include "dev_buf.h"
+#include "dev_mem.h"
 #include "kernels.h"
 
 #include <hipcub/hipcub.hpp>
@@ -268,19 +268,6 @@ struct TriangleCompact {
     }
 };
 
-int raw_alloc(void **p, size_t bytes)
-{
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
-    return (int)e;
-}
-void raw_free(void *p) { (void)hipFree(p); }
-const drv::RawAlloc kRaw = {raw_alloc, raw_free};
-
-#define TM_RESERVE(buf, count) \
-    do { if (int rc_ = (buf).reserve(count)) return (hipError_t)rc_; } while (0)
-#define TM_RESET(buf, count) \
-    do { if (int rc_ = (buf).reset(count)) return (hipError_t)rc_; } while (0)
 
 int bits_for(long long n)            // the bits that hold 0 .. n - 1, at least one
 {
@@ -294,16 +281,15 @@ int bits_for(long long n)            // the bits that hold 0 .. n - 1, at least 
 struct TriMeshDevice {
     int64_t nv = 0, nt = 0;
     bool has_vn = false, has_vc = false, has_tn = false;     // the reference's HasVertexNormals() ...: never set on no rows
-    drv::DevBuf<double> v{kRaw}, vn{kRaw}, vc{kRaw}, tn{kRaw};
-    drv::DevBuf<int> tri{kRaw};
+    DeviceBuf<double> v, vn, vc, tn;
+    DeviceBuf<int> tri;
     // what a call works in: grow-only
     Compactor comp;
-    drv::DevBuf<unsigned long long> k64a{kRaw}, k64b{kRaw};
-    drv::DevBuf<unsigned> k32a{kRaw}, k32b{kRaw};
-    drv::DevBuf<int> ia{kRaw}, ib{kRaw}, start{kRaw}, rep{kRaw}, flag{kRaw}, tflag{kRaw}, map{kRaw};
-    drv::DevBuf<long long> sel{kRaw};
-    drv::DevBuf<char> tmp{kRaw};
-    ~TriMeshDevice() { comp.release(); }
+    DeviceBuf<unsigned long long> k64a, k64b;
+    DeviceBuf<unsigned> k32a, k32b;
+    DeviceBuf<int> ia, ib, start, rep, flag, tflag, map;
+    DeviceBuf<long long> sel;
+    DeviceBuf<char> tmp;
 };
 
 namespace {
@@ -314,7 +300,7 @@ hipError_t sort_pairs(TriMeshDevice *M, K *kin, K *kout, int *vin, int *vout, lo
 {
     size_t bytes = 0;
     VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kin, kout, vin, vout, (int)n, 0, bits, stream));
-    TM_RESERVE(M->tmp, bytes);
+    DEV_RESERVE(M->tmp, bytes);
     return hipcub::DeviceRadixSort::SortPairs((void *)M->tmp.get(), bytes, kin, kout, vin, vout, (int)n, 0, bits, stream);
 }
 
@@ -322,7 +308,7 @@ hipError_t validate(TriMeshDevice *M, hipStream_t stream)
 {
     BadIndexSource s{M->tri.get(), (int)M->nv};
     long long bad = 0;
-    VISMA_TRY(M->comp.count(s, 3 * M->nt, stream, &bad));
+    VISMA_TRY(compact_count(M->comp, s, 3 * M->nt, stream, &bad));
     return bad == 0 ? hipSuccess : hipErrorInvalidValue;
 }
 
@@ -338,15 +324,15 @@ hipError_t compact_vertices(TriMeshDevice *S, TriMeshDevice *O, const int *flag,
 {
     VertexCompact c{flag, S->v.get(), S->has_vn ? S->vn.get() : nullptr, S->has_vc ? S->vc.get() : nullptr, nullptr, nullptr, nullptr, nullptr};
     long long rows = 0;
-    VISMA_TRY(S->comp.count(c, S->nv, stream, &rows));
-    drv::DevBuf<double> ov{kRaw}, ovn{kRaw}, ovc{kRaw};
-    TM_RESET(ov, 3 * (size_t)rows);
-    if (c.vn) TM_RESET(ovn, 3 * (size_t)rows);
-    if (c.vc) TM_RESET(ovc, 3 * (size_t)rows);
-    TM_RESERVE(S->map, (size_t)std::max<int64_t>(S->nv, 1));
+    VISMA_TRY(compact_count(S->comp, c, S->nv, stream, &rows));
+    DeviceBuf<double> ov, ovn, ovc;
+    DEV_RESET(ov, 3 * (size_t)rows);
+    if (c.vn) DEV_RESET(ovn, 3 * (size_t)rows);
+    if (c.vc) DEV_RESET(ovc, 3 * (size_t)rows);
+    DEV_RESERVE(S->map, (size_t)std::max<int64_t>(S->nv, 1));
     VISMA_TRY(hipMemsetAsync(S->map.get(), 0, sizeof(int) * (size_t)std::max<int64_t>(S->nv, 1), stream));
     c.ov = ov.get(); c.ovn = ovn.get(); c.ovc = ovc.get(); c.new_index = S->map.get();
-    VISMA_TRY(S->comp.write(c, S->nv, stream));
+    VISMA_TRY(compact_write(S->comp, c, S->nv, stream));
     VISMA_TRY(hipStreamSynchronize(stream));
     const bool vn = c.vn != nullptr, vc = c.vc != nullptr;
     O->v = std::move(ov); O->vn = std::move(ovn); O->vc = std::move(ovc);
@@ -361,13 +347,13 @@ hipError_t compact_triangles(TriMeshDevice *S, TriMeshDevice *O, const int *flag
 {
     TriangleCompact c{flag, S->tri.get(), S->has_tn ? S->tn.get() : nullptr, remap, nullptr, nullptr};
     long long rows = 0;
-    VISMA_TRY(S->comp.count(c, S->nt, stream, &rows));
-    drv::DevBuf<int> otri{kRaw};
-    drv::DevBuf<double> otn{kRaw};
-    TM_RESET(otri, 3 * (size_t)rows);
-    if (c.tn) TM_RESET(otn, 3 * (size_t)rows);
+    VISMA_TRY(compact_count(S->comp, c, S->nt, stream, &rows));
+    DeviceBuf<int> otri;
+    DeviceBuf<double> otn;
+    DEV_RESET(otri, 3 * (size_t)rows);
+    if (c.tn) DEV_RESET(otn, 3 * (size_t)rows);
     c.otri = otri.get(); c.otn = otn.get();
-    VISMA_TRY(S->comp.write(c, S->nt, stream));
+    VISMA_TRY(compact_write(S->comp, c, S->nt, stream));
     VISMA_TRY(hipStreamSynchronize(stream));
     const bool tn = c.tn != nullptr;
     O->tri = std::move(otri); O->tn = std::move(otn);
@@ -382,9 +368,9 @@ hipError_t remove_duplicated_vertices(TriMeshDevice *M, hipStream_t stream, int6
     *removed = 0;
     if (n == 0) return hipSuccess;
     const unsigned g = capped_blocks(n);
-    TM_RESERVE(M->ia, (size_t)n); TM_RESERVE(M->ib, (size_t)n);
-    TM_RESERVE(M->k64a, (size_t)n); TM_RESERVE(M->k64b, (size_t)n);
-    TM_RESERVE(M->start, (size_t)n); TM_RESERVE(M->rep, (size_t)n); TM_RESERVE(M->flag, (size_t)n);
+    DEV_RESERVE(M->ia, (size_t)n); DEV_RESERVE(M->ib, (size_t)n);
+    DEV_RESERVE(M->k64a, (size_t)n); DEV_RESERVE(M->k64b, (size_t)n);
+    DEV_RESERVE(M->start, (size_t)n); DEV_RESERVE(M->rep, (size_t)n); DEV_RESERVE(M->flag, (size_t)n);
     int *cur = M->ia.get(), *nxt = M->ib.get();
     tm_iota<<<g, kThreads, 0, stream>>>(cur, n);
     for (int axis = 2; axis >= 0; axis--) {                  // least significant first: z, then y, then x
@@ -395,8 +381,8 @@ hipError_t remove_duplicated_vertices(TriMeshDevice *M, hipStream_t stream, int6
     }
     VertexHeadSource h{M->v.get(), cur, M->start.get()};
     long long runs = 0;
-    VISMA_TRY(M->comp.count(h, n, stream, &runs));
-    VISMA_TRY(M->comp.write(h, n, stream));
+    VISMA_TRY(compact_count(M->comp, h, n, stream, &runs));
+    VISMA_TRY(compact_write(M->comp, h, n, stream));
     tm_representative<<<g, kThreads, 0, stream>>>(cur, M->start.get(), runs, M->rep.get(), M->flag.get(), n);
     VISMA_TRY(hipGetLastError());
     VISMA_TRY(compact_vertices(M, M, M->flag.get(), stream));
@@ -415,9 +401,9 @@ hipError_t remove_duplicated_triangles(TriMeshDevice *M, hipStream_t stream, int
     *removed = 0;
     if (n == 0) return hipSuccess;
     const unsigned g = capped_blocks(n);
-    TM_RESERVE(M->ia, (size_t)n); TM_RESERVE(M->ib, (size_t)n);
-    TM_RESERVE(M->k32a, (size_t)n); TM_RESERVE(M->k32b, (size_t)n);
-    TM_RESERVE(M->tflag, (size_t)n);
+    DEV_RESERVE(M->ia, (size_t)n); DEV_RESERVE(M->ib, (size_t)n);
+    DEV_RESERVE(M->k32a, (size_t)n); DEV_RESERVE(M->k32b, (size_t)n);
+    DEV_RESERVE(M->tflag, (size_t)n);
     int *cur = M->ia.get(), *nxt = M->ib.get();
     const int bits = bits_for(M->nv);
     tm_iota<<<g, kThreads, 0, stream>>>(cur, n);
@@ -439,7 +425,7 @@ hipError_t remove_non_manifold_triangles(TriMeshDevice *M, hipStream_t stream, i
     const long long n = M->nt;
     *removed = 0;
     if (n == 0) return hipSuccess;
-    TM_RESERVE(M->tflag, (size_t)n);
+    DEV_RESERVE(M->tflag, (size_t)n);
     tm_manifold_flag<<<capped_blocks(n), kThreads, 0, stream>>>(M->tri.get(), M->tflag.get(), n);
     VISMA_TRY(hipGetLastError());
     VISMA_TRY(compact_triangles(M, M, M->tflag.get(), nullptr, stream));
@@ -452,7 +438,7 @@ hipError_t remove_non_manifold_vertices(TriMeshDevice *M, hipStream_t stream, in
     const long long n = M->nv;
     *removed = 0;
     if (n == 0) return hipSuccess;
-    TM_RESERVE(M->flag, (size_t)n);
+    DEV_RESERVE(M->flag, (size_t)n);
     VISMA_TRY(hipMemsetAsync(M->flag.get(), 0, sizeof(int) * (size_t)n, stream));
     if (M->nt > 0) {
         tm_mark_corners<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->tri.get(), nullptr, M->flag.get(), M->nt);
@@ -472,10 +458,10 @@ hipError_t remove_non_manifold_vertices(TriMeshDevice *M, hipStream_t stream, in
 hipError_t select_marked(TriMeshDevice *S, hipStream_t stream, TriMeshDevice *O)
 {
     if (S->nv == 0) return hipSuccess;
-    TM_RESERVE(S->rep, (size_t)S->nv);                       // (here: the vertices a surviving triangle uses)
+    DEV_RESERVE(S->rep, (size_t)S->nv);                       // (here: the vertices a surviving triangle uses)
     VISMA_TRY(hipMemsetAsync(S->rep.get(), 0, sizeof(int) * (size_t)S->nv, stream));
     if (S->nt > 0) {
-        TM_RESERVE(S->tflag, (size_t)S->nt);
+        DEV_RESERVE(S->tflag, (size_t)S->nt);
         const unsigned g = capped_blocks(S->nt);
         tm_all_selected<<<g, kThreads, 0, stream>>>(S->tri.get(), S->flag.get(), S->tflag.get(), S->nt);
         tm_mark_corners<<<g, kThreads, 0, stream>>>(S->tri.get(), S->tflag.get(), S->rep.get(), S->nt);
@@ -502,15 +488,15 @@ hipError_t trimesh_device_create(const double *h_v, int64_t nv, const double *h_
     const size_t vb = sizeof(double) * 3 * (size_t)nv, tb = sizeof(double) * 3 * (size_t)nt;
     set_flags(M.get(), h_vn != nullptr, h_vc != nullptr, h_tn != nullptr);
     if (nv > 0) {
-        TM_RESET(M->v, 3 * (size_t)nv);
+        DEV_RESET(M->v, 3 * (size_t)nv);
         VISMA_TRY(hipMemcpyAsync(M->v.get(), h_v, vb, kind, stream));
-        if (M->has_vn) { TM_RESET(M->vn, 3 * (size_t)nv); VISMA_TRY(hipMemcpyAsync(M->vn.get(), h_vn, vb, kind, stream)); }
-        if (M->has_vc) { TM_RESET(M->vc, 3 * (size_t)nv); VISMA_TRY(hipMemcpyAsync(M->vc.get(), h_vc, vb, kind, stream)); }
+        if (M->has_vn) { DEV_RESET(M->vn, 3 * (size_t)nv); VISMA_TRY(hipMemcpyAsync(M->vn.get(), h_vn, vb, kind, stream)); }
+        if (M->has_vc) { DEV_RESET(M->vc, 3 * (size_t)nv); VISMA_TRY(hipMemcpyAsync(M->vc.get(), h_vc, vb, kind, stream)); }
     }
     if (nt > 0) {
-        TM_RESET(M->tri, 3 * (size_t)nt);
+        DEV_RESET(M->tri, 3 * (size_t)nt);
         VISMA_TRY(hipMemcpyAsync(M->tri.get(), h_tri, sizeof(int32_t) * 3 * (size_t)nt, kind, stream));
-        if (M->has_tn) { TM_RESET(M->tn, 3 * (size_t)nt); VISMA_TRY(hipMemcpyAsync(M->tn.get(), h_tn, tb, kind, stream)); }
+        if (M->has_tn) { DEV_RESET(M->tn, 3 * (size_t)nt); VISMA_TRY(hipMemcpyAsync(M->tn.get(), h_tn, tb, kind, stream)); }
         VISMA_TRY(validate(M.get(), stream));
     }
     VISMA_TRY(hipStreamSynchronize(stream));
@@ -550,7 +536,7 @@ hipError_t trimesh_device_normalize_normals(TriMeshDevice *M, hipStream_t stream
 hipError_t trimesh_device_compute_triangle_normals(TriMeshDevice *M, bool normalized, hipStream_t stream)
 {
     if (M->nt > 0) {
-        TM_RESERVE(M->tn, 3 * (size_t)M->nt);
+        DEV_RESERVE(M->tn, 3 * (size_t)M->nt);
         tm_triangle_normals<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->v.get(), M->tri.get(), M->tn.get(), M->nt);
         VISMA_TRY(hipGetLastError());
         M->has_tn = true;
@@ -563,22 +549,22 @@ hipError_t trimesh_device_compute_vertex_normals(TriMeshDevice *M, bool normaliz
 {
     if (!M->has_tn) VISMA_TRY(trimesh_device_compute_triangle_normals(M, false, stream));
     if (M->nv > 0 && !M->has_vn) {                            // resize(n, Zero): rows that exist keep their values
-        TM_RESERVE(M->vn, 3 * (size_t)M->nv);
+        DEV_RESERVE(M->vn, 3 * (size_t)M->nv);
         VISMA_TRY(hipMemsetAsync(M->vn.get(), 0, sizeof(double) * 3 * (size_t)M->nv, stream));
         M->has_vn = true;
     }
     const long long n3 = 3 * M->nt;
     if (n3 > 0) {
-        TM_RESERVE(M->k32a, (size_t)n3); TM_RESERVE(M->k32b, (size_t)n3);
-        TM_RESERVE(M->ia, (size_t)n3); TM_RESERVE(M->ib, (size_t)n3);
-        TM_RESERVE(M->start, (size_t)n3);
+        DEV_RESERVE(M->k32a, (size_t)n3); DEV_RESERVE(M->k32b, (size_t)n3);
+        DEV_RESERVE(M->ia, (size_t)n3); DEV_RESERVE(M->ib, (size_t)n3);
+        DEV_RESERVE(M->start, (size_t)n3);
         tm_pairs<<<capped_blocks(n3), kThreads, 0, stream>>>(M->tri.get(), M->k32a.get(), M->ia.get(), n3);
         VISMA_TRY(hipGetLastError());
         VISMA_TRY(sort_pairs(M, M->k32a.get(), M->k32b.get(), M->ia.get(), M->ib.get(), n3, bits_for(M->nv), stream));
         RunHeadSource h{M->k32b.get(), M->start.get()};
         long long runs = 0;
-        VISMA_TRY(M->comp.count(h, n3, stream, &runs));
-        VISMA_TRY(M->comp.write(h, n3, stream));
+        VISMA_TRY(compact_count(M->comp, h, n3, stream, &runs));
+        VISMA_TRY(compact_write(M->comp, h, n3, stream));
         tm_vertex_sum<<<capped_blocks(runs), kThreads, 0, stream>>>(M->k32b.get(), M->ib.get(), M->start.get(), runs, n3, M->tn.get(), M->vn.get());
         VISMA_TRY(hipGetLastError());
     }
@@ -611,10 +597,10 @@ hipError_t trimesh_device_select(TriMeshDevice *S, const int64_t *h_indices, int
         if (h_indices[i] < 0 || h_indices[i] >= S->nv) return hipErrorInvalidValue;   // (the reference reads out of bounds)
     std::unique_ptr<TriMeshDevice> O(new TriMeshDevice);
     if (S->nv > 0) {
-        TM_RESERVE(S->flag, (size_t)S->nv);
+        DEV_RESERVE(S->flag, (size_t)S->nv);
         VISMA_TRY(hipMemsetAsync(S->flag.get(), 0, sizeof(int) * (size_t)S->nv, stream));
         if (n > 0) {
-            TM_RESERVE(S->sel, (size_t)n);
+            DEV_RESERVE(S->sel, (size_t)n);
             VISMA_TRY(hipMemcpyAsync(S->sel.get(), h_indices, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, stream));
             tm_mark_selected<<<capped_blocks(n), kThreads, 0, stream>>>(S->sel.get(), n, S->flag.get());
             VISMA_TRY(hipGetLastError());
@@ -631,7 +617,7 @@ hipError_t trimesh_device_crop(TriMeshDevice *S, const double lo[3], const doubl
     std::unique_ptr<TriMeshDevice> O(new TriMeshDevice);
     const bool illegal = lo[0] > hi[0] || lo[1] > hi[1] || lo[2] > hi[2];   // DownSample.cpp:259-263: an empty mesh
     if (!illegal && S->nv > 0) {
-        TM_RESERVE(S->flag, (size_t)S->nv);
+        DEV_RESERVE(S->flag, (size_t)S->nv);
         Box b;
         for (int k = 0; k < 3; k++) { b.lo[k] = lo[k]; b.hi[k] = hi[k]; }
         tm_mark_inside<<<capped_blocks(S->nv), kThreads, 0, stream>>>(S->v.get(), S->nv, b, S->flag.get());

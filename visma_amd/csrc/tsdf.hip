@@ -38,7 +38,6 @@
 #include "kernels.h"
 #include "compact.h"
 #include "tsdf_units.h"
-#include "dev_buf.h"
 #include "mc_table.h"
 
 #include <algorithm>
@@ -661,32 +660,6 @@ __global__ __launch_bounds__(kThreads) void touched_kernel(DepthSource s, long l
     }
 }
 
-template <class T>
-hipError_t grow(T **p, size_t *have, size_t want)
-{
-    if (want <= *have && *p) return hipSuccess;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr; *have = 0;
-    hipError_t e = hipMalloc(p, sizeof(T) * std::max<size_t>(want, 1));
-    if (e == hipSuccess) *have = std::max<size_t>(want, 1);
-    return e;
-}
-
-int raw_alloc(void **p, size_t bytes)
-{
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
-    if (e != hipSuccess) { *p = nullptr; (void)hipGetLastError(); }
-    return (int)e;
-}
-void raw_free(void *p) { (void)hipFree(p); }
-const drv::RawAlloc kRaw = {raw_alloc, raw_free};
-
-#define TSDF_TRY(expr)                                   \
-    do {                                                 \
-        hipError_t e_ = (expr);                          \
-        if (e_ != hipSuccess) return e_;                 \
-    } while (0)
-
 }  // namespace
 
 struct TsdfDevice {
@@ -694,35 +667,32 @@ struct TsdfDevice {
     hipStream_t stream = nullptr;
     size_t R3 = 0;                                       // voxels of a unit
     size_t capacity = 0;                                 // units the pool holds (a uniform volume: one)
-    float *tsdf = nullptr, *weight = nullptr, *color[3] = {nullptr, nullptr, nullptr};   // capacity x R3 each
-    double *zs = nullptr;
+    DeviceBuf<float> tsdf, weight, color[3];              // capacity x R3 each; the planes beyond planes() stay empty
+    DeviceBuf<double> zs;
     // unit index -> slot, in lexicographic order of the index; slots are handed out in opening order and never move
     std::map<std::array<int, 3>, int> slot_of;
     // the last frame: depth, colour, the multiplier image of the last intrinsic, the touched boxes, the unit list
-    float *depth = nullptr, *gray = nullptr, *mult = nullptr;
-    uint8_t *rgb = nullptr;
-    TouchedBox *bounds = nullptr;
-    TsdfUnit *unit_list = nullptr;
-    size_t depth_cap = 0, gray_cap = 0, rgb_cap = 0, mult_cap = 0, bounds_cap = 0, unit_list_cap = 0;
+    DeviceBuf<float> depth, gray, mult;
+    DeviceBuf<uint8_t> rgb;
+    DeviceBuf<TouchedBox> bounds;
+    DeviceBuf<TsdfUnit> unit_list;
     int mult_w = 0, mult_h = 0;
     double mult_k[4] = {0, 0, 0, 0};
     Compactor comp;
     // an extraction's unit list on the device
-    int *x_keys = nullptr, *x_slots = nullptr;
-    double *x_origins = nullptr;
-    size_t x_keys_cap = 0, x_slots_cap = 0, x_origins_cap = 0;
+    DeviceBuf<int> x_keys, x_slots;
+    DeviceBuf<double> x_origins;
     // the last extractions: [0] surface points, [1] voxel cloud
-    double *out_points[2] = {nullptr, nullptr}, *out_normals = nullptr, *out_colors[2] = {nullptr, nullptr};
-    size_t out_points_cap[2] = {0, 0}, out_normals_cap = 0, out_colors_cap[2] = {0, 0};
+    DeviceBuf<double> out_points[2], out_normals, out_colors[2];
     long long rows[2] = {-1, -1};
     // ExtractTriangleMesh: the second compaction (comp keeps the vertex pass's tile offsets for the triangle pass), the two
     // records per item (4 transient bytes per voxel, grow-only), the case table, and the last mesh
     bool integrated = false;                             // a frame went in since the creation or the last Reset()
     Compactor comp_tri;
-    drv::DevBuf<uint16_t> cube_rec{kRaw}, vert_rec{kRaw};
-    drv::DevBuf<McCase> mc_cases{kRaw};
-    drv::DevBuf<double> mesh_vertices{kRaw}, mesh_colors{kRaw};
-    drv::DevBuf<int> mesh_triangles{kRaw};
+    DeviceBuf<uint16_t> cube_rec, vert_rec;
+    DeviceBuf<McCase> mc_cases;
+    DeviceBuf<double> mesh_vertices, mesh_colors;
+    DeviceBuf<int> mesh_triangles;
     long long mesh_nv = -1, mesh_nt = -1;
     int planes() const { return cfg.color_type == kTsdfColorRgb8 ? 3 : cfg.color_type == kTsdfColorGray32 ? 1 : 0; }
     double unit_length() const { return cfg.length; }
@@ -731,31 +701,22 @@ struct TsdfDevice {
 
 namespace {
 
-// the pool at `units` units: new arrays, the old contents copied, the rest zero; the old arrays are freed only when every
-// new one exists -- a failed allocation leaves the volume as it was
+// the pool at `units` units: new arrays, the old contents copied, the rest zero; they take the old ones' place only when
+// every one of them exists and is filled -- a failed allocation or copy leaves the volume as it was
 hipError_t pool_resize(TsdfDevice *D, size_t units)
 {
-    float *fresh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float **old[5] = {&D->tsdf, &D->weight, &D->color[0], &D->color[1], &D->color[2]};
+    DeviceBuf<float> fresh[5], *old[5] = {&D->tsdf, &D->weight, &D->color[0], &D->color[1], &D->color[2]};
     const int arrays = 2 + D->planes();
     const size_t bytes = sizeof(float) * D->R3 * units, keep = sizeof(float) * D->R3 * std::min(units, D->capacity);
+    for (int a = 0; a < arrays; a++) DEV_RESET(fresh[a], D->R3 * units);
     hipError_t e = hipSuccess;
-    for (int a = 0; a < arrays && e == hipSuccess; a++) e = hipMalloc(&fresh[a], bytes);
     for (int a = 0; a < arrays && e == hipSuccess; a++) {
         e = hipMemsetAsync(fresh[a], 0, bytes, D->stream);
         if (e == hipSuccess && keep && *old[a]) e = hipMemcpyAsync(fresh[a], *old[a], keep, hipMemcpyDeviceToDevice, D->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(D->stream);
-    if (e != hipSuccess) {
-        for (float *f : fresh)
-            if (f) (void)hipFree(f);
-        (void)hipGetLastError();
-        return e;
-    }
-    for (int a = 0; a < arrays; a++) {
-        if (*old[a]) (void)hipFree(*old[a]);
-        *old[a] = fresh[a];
-    }
+    if (e != hipSuccess) { (void)hipGetLastError(); return e; }
+    for (int a = 0; a < arrays; a++) *old[a] = std::move(fresh[a]);
     D->capacity = units;
     return hipSuccess;
 }
@@ -775,14 +736,14 @@ hipError_t upload_unit_list(TsdfDevice *D, UnitList *out)
     } else {
         for (int a = 0; a < 3; a++) origins[a] = D->cfg.origin[a];
     }
-    TSDF_TRY(grow(&D->x_keys, &D->x_keys_cap, 3 * n));
-    TSDF_TRY(grow(&D->x_slots, &D->x_slots_cap, n));
-    TSDF_TRY(grow(&D->x_origins, &D->x_origins_cap, 3 * n));
+    DEV_RESERVE(D->x_keys, 3 * n);
+    DEV_RESERVE(D->x_slots, n);
+    DEV_RESERVE(D->x_origins, 3 * n);
     if (n) {
-        TSDF_TRY(hipMemcpyAsync(D->x_keys, keys.data(), sizeof(int) * 3 * n, hipMemcpyHostToDevice, D->stream));
-        TSDF_TRY(hipMemcpyAsync(D->x_slots, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice, D->stream));
-        TSDF_TRY(hipMemcpyAsync(D->x_origins, origins.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, D->stream));
-        TSDF_TRY(hipStreamSynchronize(D->stream));           // (the vectors are this function's)
+        VISMA_TRY(hipMemcpyAsync(D->x_keys, keys.data(), sizeof(int) * 3 * n, hipMemcpyHostToDevice, D->stream));
+        VISMA_TRY(hipMemcpyAsync(D->x_slots, slots.data(), sizeof(int) * n, hipMemcpyHostToDevice, D->stream));
+        VISMA_TRY(hipMemcpyAsync(D->x_origins, origins.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, D->stream));
+        VISMA_TRY(hipStreamSynchronize(D->stream));           // (the vectors are this function's)
     }
     out->keys = D->x_keys; out->slots = D->x_slots; out->origins = D->x_origins; out->n = (int)n;
     return hipSuccess;
@@ -790,18 +751,7 @@ hipError_t upload_unit_list(TsdfDevice *D, UnitList *out)
 
 }  // namespace
 
-void tsdf_device_destroy(TsdfDevice *D)
-{
-    if (!D) return;
-    void *all[] = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], D->zs, D->depth, D->gray, D->mult, D->rgb, D->bounds,
-                   D->unit_list, D->x_keys, D->x_slots, D->x_origins,
-                   D->out_points[0], D->out_points[1], D->out_normals, D->out_colors[0], D->out_colors[1]};
-    for (void *p : all)
-        if (p) (void)hipFree(p);
-    D->comp.release();
-    D->comp_tri.release();
-    delete D;
-}
+void tsdf_device_destroy(TsdfDevice *D) { delete D; }
 
 // Reset(): a uniform volume's voxels to zero; a scalable volume forgets its units (a slot is zeroed when it is handed out)
 hipError_t tsdf_device_reset(TsdfDevice *D)
@@ -811,9 +761,9 @@ hipError_t tsdf_device_reset(TsdfDevice *D)
     D->integrated = false;
     D->slot_of.clear();
     const size_t bytes = sizeof(float) * D->R3 * D->capacity;
-    TSDF_TRY(hipMemsetAsync(D->tsdf, 0, bytes, D->stream));
-    TSDF_TRY(hipMemsetAsync(D->weight, 0, bytes, D->stream));
-    for (int c = 0; c < D->planes(); c++) TSDF_TRY(hipMemsetAsync(D->color[c], 0, bytes, D->stream));
+    VISMA_TRY(hipMemsetAsync(D->tsdf, 0, bytes, D->stream));
+    VISMA_TRY(hipMemsetAsync(D->weight, 0, bytes, D->stream));
+    for (int c = 0; c < D->planes(); c++) VISMA_TRY(hipMemsetAsync(D->color[c], 0, bytes, D->stream));
     return hipStreamSynchronize(D->stream);
 }
 
@@ -825,7 +775,7 @@ hipError_t tsdf_device_create(const TsdfConfig &cfg, hipStream_t stream, TsdfDev
     const int R = cfg.resolution;
     D->R3 = (size_t)R * R * R;
     hipError_t e = pool_resize(D, cfg.scalable ? (size_t)std::max(cfg.initial_units, 1) : 1);
-    if (e == hipSuccess) e = hipMalloc(&D->zs, sizeof(double) * (size_t)R);
+    if (e == hipSuccess) e = (hipError_t)D->zs.reset((size_t)R);
     if (e == hipSuccess) {
         // ExtractVoxelPointCloud's pt(2): half_voxel_length, then += voxel_length_ per voxel, in f64
         std::vector<double> zs((size_t)R);
@@ -843,14 +793,14 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
 {
     const TsdfConfig &c = D->cfg;
     const size_t n = (size_t)f.w * f.h;
-    TSDF_TRY(grow(&D->depth, &D->depth_cap, n));
-    TSDF_TRY(hipMemcpyAsync(D->depth, f.depth, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+    DEV_RESERVE(D->depth, n);
+    VISMA_TRY(hipMemcpyAsync(D->depth, f.depth, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
     if (c.color_type == kTsdfColorRgb8) {
-        TSDF_TRY(grow(&D->rgb, &D->rgb_cap, 3 * n));
-        TSDF_TRY(hipMemcpyAsync(D->rgb, f.color, 3 * n, hipMemcpyHostToDevice, D->stream));
+        DEV_RESERVE(D->rgb, 3 * n);
+        VISMA_TRY(hipMemcpyAsync(D->rgb, f.color, 3 * n, hipMemcpyHostToDevice, D->stream));
     } else if (c.color_type == kTsdfColorGray32) {
-        TSDF_TRY(grow(&D->gray, &D->gray_cap, n));
-        TSDF_TRY(hipMemcpyAsync(D->gray, f.color, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+        DEV_RESERVE(D->gray, n);
+        VISMA_TRY(hipMemcpyAsync(D->gray, f.color, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
     }
     // the units of this frame: the one of a uniform volume, or the touched ones, every one of them open before any kernel
     // of the integration starts
@@ -865,12 +815,12 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
         s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
         for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
         s.points = nullptr; s.colors = nullptr;
-        TSDF_TRY(grow(&D->bounds, &D->bounds_cap, (size_t)items));
+        DEV_RESERVE(D->bounds, (size_t)items);
         touched_kernel<<<capped_blocks(items), kThreads, 0, D->stream>>>(s, items, c.sdf_trunc, D->unit_length(), D->bounds);
-        TSDF_TRY(hipGetLastError());
+        VISMA_TRY(hipGetLastError());
         std::vector<TouchedBox> b((size_t)items);
-        TSDF_TRY(hipMemcpyAsync(b.data(), D->bounds, sizeof(TouchedBox) * b.size(), hipMemcpyDeviceToHost, D->stream));
-        TSDF_TRY(hipStreamSynchronize(D->stream));
+        VISMA_TRY(hipMemcpyAsync(b.data(), D->bounds, sizeof(TouchedBox) * b.size(), hipMemcpyDeviceToHost, D->stream));
+        VISMA_TRY(hipStreamSynchronize(D->stream));
         const std::set<std::array<int, 3>> touched = expand_touched_boxes(b.data(), b.size());
         if (touched.empty()) return hipSuccess;          // nothing is launched with an empty list
         size_t next = D->slot_of.size();
@@ -884,24 +834,24 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
         }
         if (!opened.empty()) {                           // the slots handed out are zeroed: a Reset() leaves old voxels in them
             const size_t at = D->R3 * next, bytes = sizeof(float) * D->R3 * opened.size();
-            TSDF_TRY(hipMemsetAsync(D->tsdf + at, 0, bytes, D->stream));
-            TSDF_TRY(hipMemsetAsync(D->weight + at, 0, bytes, D->stream));
-            for (int p = 0; p < D->planes(); p++) TSDF_TRY(hipMemsetAsync(D->color[p] + at, 0, bytes, D->stream));
+            VISMA_TRY(hipMemsetAsync(D->tsdf + at, 0, bytes, D->stream));
+            VISMA_TRY(hipMemsetAsync(D->weight + at, 0, bytes, D->stream));
+            for (int p = 0; p < D->planes(); p++) VISMA_TRY(hipMemsetAsync(D->color[p] + at, 0, bytes, D->stream));
         }
         for (const auto &k : opened) D->slot_of[k] = (int)next++;
         for (const auto &k : touched)
             list.push_back({D->slot_of[k], (float)((double)k[0] * D->unit_length()), (float)((double)k[1] * D->unit_length()),
                             (float)((double)k[2] * D->unit_length())});
     }
-    TSDF_TRY(grow(&D->unit_list, &D->unit_list_cap, list.size()));
-    TSDF_TRY(hipMemcpyAsync(D->unit_list, list.data(), sizeof(TsdfUnit) * list.size(), hipMemcpyHostToDevice, D->stream));
+    DEV_RESERVE(D->unit_list, list.size());
+    VISMA_TRY(hipMemcpyAsync(D->unit_list, list.data(), sizeof(TsdfUnit) * list.size(), hipMemcpyHostToDevice, D->stream));
     const float fx = (float)f.fx, fy = (float)f.fy, cx = (float)f.cx, cy = (float)f.cy;
     const double k[4] = {f.fx, f.fy, f.cx, f.cy};
     if (!D->mult || D->mult_w != f.w || D->mult_h != f.h || std::memcmp(k, D->mult_k, sizeof(k)) != 0) {
         D->mult_w = 0;
-        TSDF_TRY(grow(&D->mult, &D->mult_cap, n));
+        DEV_RESERVE(D->mult, n);
         multiplier_kernel<<<capped_blocks((long long)n), kThreads, 0, D->stream>>>(D->mult, f.w, f.h, cx, cy, 1.0f / fx, 1.0f / fy);
-        TSDF_TRY(hipGetLastError());
+        VISMA_TRY(hipGetLastError());
         D->mult_w = f.w; D->mult_h = f.h;
         std::memcpy(D->mult_k, k, sizeof(k));
     }
@@ -923,7 +873,7 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
     if (c.color_type == kTsdfColorRgb8) integrate_kernel<kTsdfColorRgb8><<<blocks, kThreads, 0, D->stream>>>(a);
     else if (c.color_type == kTsdfColorGray32) integrate_kernel<kTsdfColorGray32><<<blocks, kThreads, 0, D->stream>>>(a);
     else integrate_kernel<kTsdfColorNone><<<blocks, kThreads, 0, D->stream>>>(a);
-    TSDF_TRY(hipGetLastError());
+    VISMA_TRY(hipGetLastError());
     D->rows[0] = D->rows[1] = -1;
     D->mesh_nv = D->mesh_nt = -1;
     D->integrated = true;
@@ -938,40 +888,41 @@ hipError_t tsdf_device_extract(TsdfDevice *D, int voxel_cloud, int64_t *n)
     *n = 0;
     long long rows = 0;
     UnitList units;
-    TSDF_TRY(upload_unit_list(D, &units));
+    VISMA_TRY(upload_unit_list(D, &units));
     const long long items = (long long)D->R3 * units.n;
     if (voxel_cloud) {
         const double vl = D->unit_voxel_length();
         VoxelCloudSource s = {D->tsdf, D->weight, D->zs, units, c.resolution, vl, vl * 0.5, nullptr, nullptr};
-        TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
-        TSDF_TRY(grow(&D->out_points[1], &D->out_points_cap[1], 3 * (size_t)rows));
-        TSDF_TRY(grow(&D->out_colors[1], &D->out_colors_cap[1], 3 * (size_t)rows));
+        VISMA_TRY(compact_count(D->comp, s, items, D->stream, &rows));
+        DEV_RESERVE(D->out_points[1], 3 * (size_t)rows);
+        DEV_RESERVE(D->out_colors[1], 3 * (size_t)rows);
         s.points = D->out_points[1]; s.colors = D->out_colors[1];
-        if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+        if (rows > 0) VISMA_TRY(compact_write(D->comp, s, items, D->stream));
     } else {
         auto outputs = [&]() -> hipError_t {
-            TSDF_TRY(grow(&D->out_points[0], &D->out_points_cap[0], 3 * (size_t)rows));
-            TSDF_TRY(grow(&D->out_normals, &D->out_normals_cap, 3 * (size_t)rows));
-            return grow(&D->out_colors[0], &D->out_colors_cap[0], 3 * (size_t)rows);
+            DEV_RESERVE(D->out_points[0], 3 * (size_t)rows);
+            DEV_RESERVE(D->out_normals, 3 * (size_t)rows);
+            DEV_RESERVE(D->out_colors[0], 3 * (size_t)rows);
+            return hipSuccess;
         };
         if (c.scalable) {
             ScalableSurfaceSource s = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], units, c.resolution, c.color_type,
                                        c.voxel_length, c.voxel_length * 0.5, D->unit_length(), nullptr, nullptr, nullptr};
-            TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
-            TSDF_TRY(outputs());
+            VISMA_TRY(compact_count(D->comp, s, items, D->stream, &rows));
+            VISMA_TRY(outputs());
             s.points = D->out_points[0]; s.normals = D->out_normals; s.colors = D->out_colors[0];
-            if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+            if (rows > 0) VISMA_TRY(compact_write(D->comp, s, items, D->stream));
         } else {
             const double vl = D->unit_voxel_length();
             SurfaceSource s = {D->tsdf, D->weight, D->color[0], D->color[1], D->color[2], c.resolution, c.color_type, vl, vl * 0.5,
                                c.origin[0], c.origin[1], c.origin[2], nullptr, nullptr, nullptr};
-            TSDF_TRY(D->comp.count(s, items, D->stream, &rows));
-            TSDF_TRY(outputs());
+            VISMA_TRY(compact_count(D->comp, s, items, D->stream, &rows));
+            VISMA_TRY(outputs());
             s.points = D->out_points[0]; s.normals = D->out_normals; s.colors = D->out_colors[0];
-            if (rows > 0) TSDF_TRY(D->comp.write(s, items, D->stream));
+            if (rows > 0) VISMA_TRY(compact_write(D->comp, s, items, D->stream));
         }
     }
-    TSDF_TRY(hipStreamSynchronize(D->stream));
+    VISMA_TRY(hipStreamSynchronize(D->stream));
     D->rows[which] = rows;
     *n = (int64_t)rows;
     return hipSuccess;
@@ -983,38 +934,35 @@ hipError_t tsdf_device_get_extract(TsdfDevice *D, int voxel_cloud, double *point
     const long long rows = D->rows[which];
     if (rows <= 0) return hipSuccess;
     const size_t bytes = sizeof(double) * 3 * (size_t)rows;
-    if (points) TSDF_TRY(hipMemcpy(points, D->out_points[which], bytes, hipMemcpyDeviceToHost));
-    if (normals && !voxel_cloud) TSDF_TRY(hipMemcpy(normals, D->out_normals, bytes, hipMemcpyDeviceToHost));
-    if (colors && (voxel_cloud || D->planes() > 0)) TSDF_TRY(hipMemcpy(colors, D->out_colors[which], bytes, hipMemcpyDeviceToHost));
+    if (points) VISMA_TRY(hipMemcpy(points, D->out_points[which], bytes, hipMemcpyDeviceToHost));
+    if (normals && !voxel_cloud) VISMA_TRY(hipMemcpy(normals, D->out_normals, bytes, hipMemcpyDeviceToHost));
+    if (colors && (voxel_cloud || D->planes() > 0)) VISMA_TRY(hipMemcpy(colors, D->out_colors[which], bytes, hipMemcpyDeviceToHost));
     return hipSuccess;
 }
 
 namespace {
 
-#define TSDF_RESERVE(buf, count)                                               \
-    do { if (int rc_ = (buf).reserve(count)) return (hipError_t)rc_; } while (0)
-
 template <class Grid>
 hipError_t extract_mesh(TsdfDevice *D, MeshArgs<Grid> a, long long items, long long *nv, long long *nt)
 {
     cube_kernel<Grid><<<capped_blocks(items), kThreads, 0, D->stream>>>(a, items);
-    TSDF_TRY(hipGetLastError());
+    VISMA_TRY(hipGetLastError());
     MeshVertexSource<Grid> vs = {a};
-    TSDF_TRY(D->comp.count(vs, items, D->stream, nv));
+    VISMA_TRY(compact_count(D->comp, vs, items, D->stream, nv));
     if (*nv > 0x7fffffffLL) return hipErrorInvalidValue;
     if (*nv == 0) return hipSuccess;                     // no vertex, no triangle
-    TSDF_RESERVE(D->mesh_vertices, 3 * (size_t)*nv);
-    if (D->planes() > 0) TSDF_RESERVE(D->mesh_colors, 3 * (size_t)*nv);
+    DEV_RESERVE(D->mesh_vertices, 3 * (size_t)*nv);
+    if (D->planes() > 0) DEV_RESERVE(D->mesh_colors, 3 * (size_t)*nv);
     vs.a.vertices = D->mesh_vertices.get(); vs.a.colors = D->mesh_colors.get();
-    vs.a.vert_tile_offset = D->comp.tile_offset;
-    TSDF_TRY(D->comp.write(vs, items, D->stream));
+    vs.a.vert_tile_offset = D->comp.tile_offset.get();
+    VISMA_TRY(compact_write(D->comp, vs, items, D->stream));
     MeshTriangleSource<Grid> ts = {vs.a};
-    TSDF_TRY(D->comp_tri.count(ts, items, D->stream, nt));
+    VISMA_TRY(compact_count(D->comp_tri, ts, items, D->stream, nt));
     if (*nt > 0x7fffffffLL) return hipErrorInvalidValue;
     if (*nt == 0) return hipSuccess;
-    TSDF_RESERVE(D->mesh_triangles, 3 * (size_t)*nt);
+    DEV_RESERVE(D->mesh_triangles, 3 * (size_t)*nt);
     ts.a.triangles = D->mesh_triangles.get();
-    return D->comp_tri.write(ts, items, D->stream);
+    return compact_write(D->comp_tri, ts, items, D->stream);
 }
 
 }  // namespace
@@ -1029,15 +977,15 @@ hipError_t tsdf_device_extract_mesh(TsdfDevice *D, int64_t *nv, int64_t *nt)
     const bool empty = !D->integrated || (c.scalable ? D->slot_of.empty() : c.resolution < 2);
     if (!empty) {
         UnitList units;
-        TSDF_TRY(upload_unit_list(D, &units));
+        VISMA_TRY(upload_unit_list(D, &units));
         const long long items = (long long)D->R3 * units.n;
-        TSDF_RESERVE(D->cube_rec, (size_t)items);
-        TSDF_RESERVE(D->vert_rec, (size_t)items);
+        DEV_RESERVE(D->cube_rec, (size_t)items);
+        DEV_RESERVE(D->vert_rec, (size_t)items);
         if (!D->mc_cases) {
             const McTable &t = mc_table();
             for (const McCase &cs : t.c)
                 if (cs.n > kMcMaxTriangles) return hipErrorUnknown;          // (the rule gave more than a row holds: never)
-            TSDF_RESERVE(D->mc_cases, 256);
+            DEV_RESERVE(D->mc_cases, 256);
             const hipError_t e = hipMemcpyAsync(D->mc_cases.get(), t.c, sizeof(t.c), hipMemcpyHostToDevice, D->stream);   // (a static table)
             if (e != hipSuccess) { D->mc_cases.release(); return e; }
         }
@@ -1055,7 +1003,7 @@ hipError_t tsdf_device_extract_mesh(TsdfDevice *D, int64_t *nv, int64_t *nt)
             e = extract_mesh(D, a, items, &n_vertices, &n_triangles);
         }
         if (e != hipSuccess) { (void)hipStreamSynchronize(D->stream); return e; }
-        TSDF_TRY(hipStreamSynchronize(D->stream));
+        VISMA_TRY(hipStreamSynchronize(D->stream));
     }
     D->mesh_nv = n_vertices; D->mesh_nt = n_triangles;
     *nv = (int64_t)n_vertices; *nt = (int64_t)n_triangles;
@@ -1066,11 +1014,11 @@ hipError_t tsdf_device_get_mesh(TsdfDevice *D, double *vertices, double *colors,
 {
     if (D->mesh_nv > 0) {
         const size_t bytes = sizeof(double) * 3 * (size_t)D->mesh_nv;
-        if (vertices) TSDF_TRY(hipMemcpy(vertices, D->mesh_vertices.get(), bytes, hipMemcpyDeviceToHost));
-        if (colors && D->planes() > 0) TSDF_TRY(hipMemcpy(colors, D->mesh_colors.get(), bytes, hipMemcpyDeviceToHost));
+        if (vertices) VISMA_TRY(hipMemcpy(vertices, D->mesh_vertices.get(), bytes, hipMemcpyDeviceToHost));
+        if (colors && D->planes() > 0) VISMA_TRY(hipMemcpy(colors, D->mesh_colors.get(), bytes, hipMemcpyDeviceToHost));
     }
     if (D->mesh_nt > 0 && triangles)
-        TSDF_TRY(hipMemcpy(triangles, D->mesh_triangles.get(), sizeof(int32_t) * 3 * (size_t)D->mesh_nt, hipMemcpyDeviceToHost));
+        VISMA_TRY(hipMemcpy(triangles, D->mesh_triangles.get(), sizeof(int32_t) * 3 * (size_t)D->mesh_nt, hipMemcpyDeviceToHost));
     return hipSuccess;
 }
 
@@ -1101,8 +1049,8 @@ hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsd
         slot = (size_t)it->second;
     }
     const size_t at = slot * D->R3, bytes = sizeof(float) * D->R3;
-    if (tsdf) TSDF_TRY(hipMemcpy(tsdf, D->tsdf + at, bytes, hipMemcpyDeviceToHost));
-    if (weight) TSDF_TRY(hipMemcpy(weight, D->weight + at, bytes, hipMemcpyDeviceToHost));
+    if (tsdf) VISMA_TRY(hipMemcpy(tsdf, D->tsdf + at, bytes, hipMemcpyDeviceToHost));
+    if (weight) VISMA_TRY(hipMemcpy(weight, D->weight + at, bytes, hipMemcpyDeviceToHost));
     if (color && D->planes() > 0) {
         // plane by plane in pieces of 4 M voxels (16 MB on the host whatever the resolution), interleaved as the reference
         // keeps the colour; Gray32: the one plane, three times
@@ -1111,7 +1059,7 @@ hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsd
         for (size_t v0 = 0; v0 < D->R3; v0 += piece) {
             const size_t m = std::min(piece, D->R3 - v0);
             for (int c = 0; c < 3; c++) {
-                if (c < D->planes()) TSDF_TRY(hipMemcpy(buf.data(), D->color[c] + at + v0, sizeof(float) * m, hipMemcpyDeviceToHost));
+                if (c < D->planes()) VISMA_TRY(hipMemcpy(buf.data(), D->color[c] + at + v0, sizeof(float) * m, hipMemcpyDeviceToHost));
                 for (size_t i = 0; i < m; i++) color[3 * (v0 + i) + (size_t)c] = buf[i];
             }
         }
@@ -1125,46 +1073,38 @@ hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[1
     *n = 0;
     const size_t px = (size_t)f.w * f.h;
     const long long sw = ((long long)f.w - 1) / stride + 1, sh = ((long long)f.h - 1) / stride + 1, items = sw * sh;
-    float *d_depth = nullptr, *d_gray = nullptr;
-    uint8_t *d_rgb = nullptr;
-    double *d_points = nullptr, *d_colors = nullptr;
+    DeviceBuf<float> d_depth, d_gray;
+    DeviceBuf<uint8_t> d_rgb;
+    DeviceBuf<double> d_points, d_colors;
     Compactor comp;
-    auto run = [&]() -> hipError_t {
-        TSDF_TRY(hipMalloc(&d_depth, sizeof(float) * px));
-        TSDF_TRY(hipMemcpyAsync(d_depth, f.depth, sizeof(float) * px, hipMemcpyHostToDevice, stream));
-        if (color_type == kTsdfColorRgb8) {
-            TSDF_TRY(hipMalloc(&d_rgb, 3 * px));
-            TSDF_TRY(hipMemcpyAsync(d_rgb, f.color, 3 * px, hipMemcpyHostToDevice, stream));
-        } else if (color_type == kTsdfColorGray32) {
-            TSDF_TRY(hipMalloc(&d_gray, sizeof(float) * px));
-            TSDF_TRY(hipMemcpyAsync(d_gray, f.color, sizeof(float) * px, hipMemcpyHostToDevice, stream));
-        }
-        DepthSource s;
-        s.depth = d_depth; s.gray = d_gray; s.rgb = d_rgb;
-        s.w = f.w; s.sw = (int)sw; s.stride = stride; s.color_type = color_type;
-        s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
-        for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
-        s.points = nullptr; s.colors = nullptr;
-        long long rows = 0;
-        TSDF_TRY(comp.count(s, items, stream, &rows));
-        *n = (int64_t)rows;
-        if (rows == 0 || !points) return hipSuccess;
-        const size_t bytes = sizeof(double) * 3 * (size_t)rows;
-        TSDF_TRY(hipMalloc(&d_points, bytes));
-        if (color_type != kTsdfColorNone) TSDF_TRY(hipMalloc(&d_colors, bytes));
-        s.points = d_points; s.colors = d_colors;
-        TSDF_TRY(comp.write(s, items, stream));
-        TSDF_TRY(hipMemcpyAsync(points, d_points, bytes, hipMemcpyDeviceToHost, stream));
-        if (colors && d_colors) TSDF_TRY(hipMemcpyAsync(colors, d_colors, bytes, hipMemcpyDeviceToHost, stream));
-        return hipStreamSynchronize(stream);
-    };
-    const hipError_t e = run();
-    if (e != hipSuccess) (void)hipStreamSynchronize(stream);
-    void *all[] = {d_depth, d_gray, d_rgb, d_points, d_colors};
-    for (void *p : all)
-        if (p) (void)hipFree(p);
-    comp.release();
-    return e;
+    // (a return with work in flight is safe: the buffers' hipFree waits for the device before the caller has its arrays back)
+    DEV_RESET(d_depth, px);
+    VISMA_TRY(hipMemcpyAsync(d_depth, f.depth, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+    if (color_type == kTsdfColorRgb8) {
+        DEV_RESET(d_rgb, 3 * px);
+        VISMA_TRY(hipMemcpyAsync(d_rgb, f.color, 3 * px, hipMemcpyHostToDevice, stream));
+    } else if (color_type == kTsdfColorGray32) {
+        DEV_RESET(d_gray, px);
+        VISMA_TRY(hipMemcpyAsync(d_gray, f.color, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+    }
+    DepthSource s;
+    s.depth = d_depth; s.gray = d_gray; s.rgb = d_rgb;
+    s.w = f.w; s.sw = (int)sw; s.stride = stride; s.color_type = color_type;
+    s.fx = f.fx; s.fy = f.fy; s.cx = f.cx; s.cy = f.cy;
+    for (int i = 0; i < 12; i++) s.pose[i] = pose[i];
+    s.points = nullptr; s.colors = nullptr;
+    long long rows = 0;
+    VISMA_TRY(compact_count(comp, s, items, stream, &rows));
+    *n = (int64_t)rows;
+    if (rows == 0 || !points) return hipSuccess;
+    const size_t bytes = sizeof(double) * 3 * (size_t)rows;
+    DEV_RESET(d_points, 3 * (size_t)rows);
+    if (color_type != kTsdfColorNone) DEV_RESET(d_colors, 3 * (size_t)rows);
+    s.points = d_points; s.colors = d_colors;
+    VISMA_TRY(compact_write(comp, s, items, stream));
+    VISMA_TRY(hipMemcpyAsync(points, d_points, bytes, hipMemcpyDeviceToHost, stream));
+    if (colors && d_colors) VISMA_TRY(hipMemcpyAsync(colors, d_colors, bytes, hipMemcpyDeviceToHost, stream));
+    return hipStreamSynchronize(stream);
 }
 
 }  // namespace visma

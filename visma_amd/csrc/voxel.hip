@@ -19,6 +19,7 @@
 // then ix -- and run heads compare the three indices: the same ascending
 // (ix, iy, iz) output order, the same input-order sums.
 #include "device_common.h"
+#include "dev_mem.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -187,112 +188,97 @@ static double ord2d(unsigned long long o)
 hipError_t launch_exclusive_scan_u32(const unsigned *in, long long n, unsigned *bsum, unsigned *out,
                                      hipStream_t stream);
 
-#define VOX_TRY(x) do { hipError_t e__ = (x); if (e__ != hipSuccess) { rc = e__; goto done; } } while (0)
-
-// The device part: d_xyz (+ d_nrm, d_col or NULL), n points resident -> *d_oxyz (+ *d_onrm, *d_ocol) hipMalloc'ed
-// here with *n_out voxels (NULL / 0 when the reference would return an empty cloud); the caller frees them.
+// The device part: d_xyz (+ d_nrm, d_col or NULL), n points resident -> d_oxyz (+ *d_onrm, *d_ocol where the input has them
+// and the caller passes a buffer) with *n_out voxels; the outputs are empty when the reference would return an empty cloud,
+// and hold nothing to read after a failure.
 hipError_t voxel_down_sample_core(const double *d_xyz, const double *d_nrm, const double *d_col, int64_t n, double voxel,
-                                  double **d_oxyz_out, double **d_onrm_out, double **d_ocol_out, int64_t *n_out,
+                                  DevBuf<double> &d_oxyz, DevBuf<double> *d_onrm, DevBuf<double> *d_ocol, int64_t *n_out,
                                   hipStream_t stream)
 {
     *n_out = 0;
-    *d_oxyz_out = nullptr;
-    if (d_onrm_out) *d_onrm_out = nullptr;
-    if (d_ocol_out) *d_ocol_out = nullptr;
+    d_oxyz.release();
+    if (d_onrm) d_onrm->release();
+    if (d_ocol) d_ocol->release();
     if (!(voxel > 0.0) || n <= 0) return hipSuccess;       // DownSample.cpp:183-186
-    hipError_t rc = hipSuccess;
-    double *d_oxyz = nullptr, *d_onrm = nullptr, *d_ocol = nullptr;
-    unsigned long long *d_box = nullptr, *d_key = nullptr, *d_key2 = nullptr;
-    unsigned *d_vi = nullptr, *d_k32 = nullptr, *d_k32b = nullptr;
-    unsigned *d_val = nullptr, *d_val2 = nullptr, *d_head = nullptr, *d_vid = nullptr, *d_bsum = nullptr, *d_vstart = nullptr;
-    void *d_tmp = nullptr;
+    DeviceBuf<unsigned long long> d_box, d_key, d_key2;
+    DeviceBuf<unsigned> d_vi, d_k32, d_k32b, d_val, d_val2, d_head, d_vid, d_bsum, d_vstart;
+    DeviceBuf<char> d_tmp;
     size_t tmp_bytes = 0;
     unsigned long long box[6];
     const int pb = (int)((n + 255) / 256);
     VoxParams vp;
     double mn[3], mx[3], ext = 0.0, dims[3], cells = 1.0;
     unsigned last_vid = 0, last_head = 0;
-    int64_t nvox = 0;
-    int end_bit = 64;
-    bool keep = false, wide = false;
 
-    VOX_TRY(hipMalloc(&d_box, sizeof(unsigned long long) * 8));
+    DEV_RESET(d_box, 8);
     hipLaunchKernelGGL(vox_bbox_init_kernel, dim3(1), dim3(64), 0, stream, d_box);
     hipLaunchKernelGGL(vox_bbox_kernel, dim3(pb > 1024 ? 1024 : pb), dim3(256), 0, stream, d_xyz, (long long)n, d_box);
-    VOX_TRY(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, stream));
-    VOX_TRY(hipStreamSynchronize(stream));
+    VISMA_TRY(hipMemcpyAsync(box, d_box, sizeof(box), hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
     for (int a = 0; a < 3; a++) { mn[a] = ord2d(box[a]); mx[a] = ord2d(box[3 + a]); }
     for (int a = 0; a < 3; a++) {                              // :189-190
         vp.vmin[a] = mn[a] - voxel * 0.5;
         const double e = (mx[a] + voxel * 0.5) - vp.vmin[a];
         if (e > ext) ext = e;
     }
-    if (voxel * 2147483647.0 < ext) goto done;                 // :191-195 -> empty cloud
+    if (voxel * 2147483647.0 < ext) return hipSuccess;         // :191-195 -> empty cloud
     for (int a = 0; a < 3; a++) {
         dims[a] = floor(((mx[a] - vp.vmin[a]) / voxel)) + 2.0;
         cells *= dims[a];
     }
-    wide = !(cells < 4.0e18);                                  // the grid does not fit one 64-bit key
+    const bool wide = !(cells < 4.0e18);                       // the grid does not fit one 64-bit key
     vp.voxel = voxel;
     vp.ny = (long long)dims[1];
     vp.nz = (long long)dims[2];
-    VOX_TRY(hipMalloc(&d_val, sizeof(unsigned) * n));
-    VOX_TRY(hipMalloc(&d_val2, sizeof(unsigned) * n));
-    VOX_TRY(hipMalloc(&d_head, sizeof(unsigned) * (n + 1)));
-    VOX_TRY(hipMalloc(&d_vid, sizeof(unsigned) * (n + 1)));
-    VOX_TRY(hipMalloc(&d_bsum, sizeof(unsigned) * (n / 2048 + 2)));
+    DEV_RESET(d_val, (size_t)n);
+    DEV_RESET(d_val2, (size_t)n);
+    DEV_RESET(d_head, (size_t)n + 1);
+    DEV_RESET(d_vid, (size_t)n + 1);
+    DEV_RESET(d_bsum, (size_t)n / 2048 + 2);
     if (!wide) {
-        end_bit = 1;
+        int end_bit = 1;
         while (end_bit < 64 && ldexp(1.0, end_bit) < cells) end_bit++;
-        VOX_TRY(hipMalloc(&d_key, sizeof(unsigned long long) * n));
-        VOX_TRY(hipMalloc(&d_key2, sizeof(unsigned long long) * n));
+        DEV_RESET(d_key, (size_t)n);
+        DEV_RESET(d_key2, (size_t)n);
         hipLaunchKernelGGL(vox_key_kernel, dim3(pb), dim3(256), 0, stream, d_xyz, (long long)n, vp, d_key, d_val);
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
-        VOX_TRY(hipMalloc(&d_tmp, tmp_bytes > 0 ? tmp_bytes : 16));
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_key, d_key2, d_val, d_val2, (int)n, 0, end_bit, stream));
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key.get(), d_key2.get(), d_val.get(), d_val2.get(), (int)n, 0, end_bit, stream));
+        DEV_RESET(d_tmp, tmp_bytes);
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tmp_bytes, d_key.get(), d_key2.get(), d_val.get(), d_val2.get(), (int)n, 0, end_bit, stream));
         hipLaunchKernelGGL(vox_head_kernel, dim3(pb), dim3(256), 0, stream, d_key2, (long long)n, d_head);
     } else {
         // least significant index first; every pass is stable, so after the third the points stand in
         // ascending (ix, iy, iz) and, within a voxel, in ascending point index.  The order ends in d_val2.
-        VOX_TRY(hipMalloc(&d_vi, sizeof(unsigned) * 3 * n));
-        VOX_TRY(hipMalloc(&d_k32, sizeof(unsigned) * n));
-        VOX_TRY(hipMalloc(&d_k32b, sizeof(unsigned) * n));
+        DEV_RESET(d_vi, 3 * (size_t)n);
+        DEV_RESET(d_k32, (size_t)n);
+        DEV_RESET(d_k32b, (size_t)n);
         hipLaunchKernelGGL(vox_index_kernel, dim3(pb), dim3(256), 0, stream, d_xyz, (long long)n, vp, d_vi, d_k32, d_val);
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
-        VOX_TRY(hipMalloc(&d_tmp, tmp_bytes > 0 ? tmp_bytes : 16));
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_k32.get(), d_k32b.get(), d_val.get(), d_val2.get(), (int)n, 0, 32, stream));
+        DEV_RESET(d_tmp, tmp_bytes);
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tmp_bytes, d_k32.get(), d_k32b.get(), d_val.get(), d_val2.get(), (int)n, 0, 32, stream));
         hipLaunchKernelGGL(vox_axis_key_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val2, (long long)n, 1, d_k32);
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val2, d_val, (int)n, 0, 32, stream));
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tmp_bytes, d_k32.get(), d_k32b.get(), d_val2.get(), d_val.get(), (int)n, 0, 32, stream));
         hipLaunchKernelGGL(vox_axis_key_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val, (long long)n, 0, d_k32);
-        VOX_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp, tmp_bytes, d_k32, d_k32b, d_val, d_val2, (int)n, 0, 32, stream));
+        VISMA_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.get(), tmp_bytes, d_k32.get(), d_k32b.get(), d_val.get(), d_val2.get(), (int)n, 0, 32, stream));
         hipLaunchKernelGGL(vox_head3_kernel, dim3(pb), dim3(256), 0, stream, d_vi, d_val2, (long long)n, d_head);
     }
-    VOX_TRY(launch_exclusive_scan_u32(d_head, (long long)n, d_bsum, d_vid, stream));
-    VOX_TRY(hipMemcpyAsync(&last_vid, d_vid + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    VOX_TRY(hipMemcpyAsync(&last_head, d_head + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    VOX_TRY(hipStreamSynchronize(stream));
-    nvox = (int64_t)last_vid + (int64_t)last_head;
-    VOX_TRY(hipMalloc(&d_vstart, sizeof(unsigned) * (nvox + 1)));
+    VISMA_TRY(launch_exclusive_scan_u32(d_head, (long long)n, d_bsum, d_vid, stream));
+    VISMA_TRY(hipMemcpyAsync(&last_vid, d_vid + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipMemcpyAsync(&last_head, d_head + (n - 1), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    VISMA_TRY(hipStreamSynchronize(stream));
+    const int64_t nvox = (int64_t)last_vid + (int64_t)last_head;
+    DEV_RESET(d_vstart, (size_t)nvox + 1);
     hipLaunchKernelGGL(vox_starts_kernel, dim3(pb), dim3(256), 0, stream, d_head, d_vid, (long long)n, d_vstart);
-    VOX_TRY(hipMalloc(&d_oxyz, sizeof(double) * 3 * nvox));
-    if (d_nrm && d_onrm_out) VOX_TRY(hipMalloc(&d_onrm, sizeof(double) * 3 * nvox));
-    if (d_col && d_ocol_out) VOX_TRY(hipMalloc(&d_ocol, sizeof(double) * 3 * nvox));
+    const bool with_nrm = d_nrm && d_onrm, with_col = d_col && d_ocol;
+    DEV_RESET(d_oxyz, 3 * (size_t)nvox);
+    if (with_nrm) DEV_RESET(*d_onrm, 3 * (size_t)nvox);
+    if (with_col) DEV_RESET(*d_ocol, 3 * (size_t)nvox);
     hipLaunchKernelGGL(vox_reduce_kernel, dim3((unsigned)((nvox + 255) / 256)), dim3(256), 0, stream, d_xyz,
-                       d_onrm ? d_nrm : nullptr, d_ocol ? d_col : nullptr, d_val2, d_vstart, (long long)nvox, (long long)n,
-                       d_oxyz, d_onrm, d_ocol);
-    VOX_TRY(hipGetLastError());
-    VOX_TRY(hipStreamSynchronize(stream));                     // (the scratch below is freed on return)
+                       with_nrm ? d_nrm : nullptr, with_col ? d_col : nullptr, d_val2, d_vstart, (long long)nvox, (long long)n,
+                       d_oxyz, with_nrm ? d_onrm->get() : nullptr, with_col ? d_ocol->get() : nullptr);
+    VISMA_TRY(hipGetLastError());
+    VISMA_TRY(hipStreamSynchronize(stream));                   // (the scratch is freed on return)
     *n_out = nvox;
-    *d_oxyz_out = d_oxyz;
-    if (d_onrm_out) *d_onrm_out = d_onrm;
-    if (d_ocol_out) *d_ocol_out = d_ocol;
-    keep = true;
-done:
-    if (!keep) { (void)hipFree(d_oxyz); (void)hipFree(d_onrm); (void)hipFree(d_ocol); }
-    (void)hipFree(d_box); (void)hipFree(d_key); (void)hipFree(d_key2); (void)hipFree(d_val);
-    (void)hipFree(d_val2); (void)hipFree(d_head); (void)hipFree(d_vid); (void)hipFree(d_bsum); (void)hipFree(d_vstart);
-    (void)hipFree(d_tmp); (void)hipFree(d_vi); (void)hipFree(d_k32); (void)hipFree(d_k32b);
-    return rc;
+    return hipSuccess;
 }
 
 // Host arrays in, host arrays out.  Returns hipSuccess and *n_out (0 when the reference would return an empty
@@ -303,25 +289,22 @@ hipError_t voxel_down_sample_device(const double *h_xyz, const double *h_nrm, co
 {
     *n_out = 0;
     if (!(voxel > 0.0) || n <= 0) return hipSuccess;       // DownSample.cpp:183-186
-    hipError_t rc = hipSuccess;
-    double *d_xyz = nullptr, *d_nrm = nullptr, *d_col = nullptr, *d_oxyz = nullptr, *d_onrm = nullptr, *d_ocol = nullptr;
+    DeviceBuf<double> d_xyz, d_nrm, d_col, d_oxyz, d_onrm, d_ocol;
     int64_t nvox = 0;
-    VOX_TRY(hipMalloc(&d_xyz, sizeof(double) * 3 * n));
-    VOX_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
-    if (h_nrm) { VOX_TRY(hipMalloc(&d_nrm, sizeof(double) * 3 * n)); VOX_TRY(hipMemcpyAsync(d_nrm, h_nrm, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream)); }
-    if (h_col) { VOX_TRY(hipMalloc(&d_col, sizeof(double) * 3 * n)); VOX_TRY(hipMemcpyAsync(d_col, h_col, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream)); }
-    VOX_TRY(voxel_down_sample_core(d_xyz, d_nrm, d_col, n, voxel, &d_oxyz, &d_onrm, &d_ocol, &nvox, stream));
+    const size_t bytes = sizeof(double) * 3 * (size_t)n;
+    DEV_RESET(d_xyz, 3 * (size_t)n);
+    VISMA_TRY(hipMemcpyAsync(d_xyz, h_xyz, bytes, hipMemcpyHostToDevice, stream));
+    if (h_nrm) { DEV_RESET(d_nrm, 3 * (size_t)n); VISMA_TRY(hipMemcpyAsync(d_nrm, h_nrm, bytes, hipMemcpyHostToDevice, stream)); }
+    if (h_col) { DEV_RESET(d_col, 3 * (size_t)n); VISMA_TRY(hipMemcpyAsync(d_col, h_col, bytes, hipMemcpyHostToDevice, stream)); }
+    VISMA_TRY(voxel_down_sample_core(d_xyz, d_nrm, d_col, n, voxel, d_oxyz, &d_onrm, &d_ocol, &nvox, stream));
     if (nvox > 0) {
-        VOX_TRY(hipMemcpyAsync(h_out_xyz, d_oxyz, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
-        if (h_nrm && h_out_nrm) VOX_TRY(hipMemcpyAsync(h_out_nrm, d_onrm, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
-        if (h_col && h_out_col) VOX_TRY(hipMemcpyAsync(h_out_col, d_ocol, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
-        VOX_TRY(hipStreamSynchronize(stream));
+        VISMA_TRY(hipMemcpyAsync(h_out_xyz, d_oxyz, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
+        if (h_nrm && h_out_nrm) VISMA_TRY(hipMemcpyAsync(h_out_nrm, d_onrm, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
+        if (h_col && h_out_col) VISMA_TRY(hipMemcpyAsync(h_out_col, d_ocol, sizeof(double) * 3 * nvox, hipMemcpyDeviceToHost, stream));
+        VISMA_TRY(hipStreamSynchronize(stream));
     }
     *n_out = nvox;
-done:
-    (void)hipFree(d_xyz); (void)hipFree(d_nrm); (void)hipFree(d_col); (void)hipFree(d_oxyz); (void)hipFree(d_onrm);
-    (void)hipFree(d_ocol);
-    return rc;
+    return hipSuccess;
 }
 
 // The centroid of n device-resident points as centroid_f64 (driver.cpp) computes it on the host: sequential f64
