@@ -1711,6 +1711,101 @@ VISMA_ICP_API int visma_icp_trimesh_crop(visma_icp_ctx *ctx, visma_icp_trimesh *
                                          const double max_bound[3], visma_icp_trimesh **out);
 VISMA_ICP_API int visma_icp_trimesh_transform(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, const double T[16]);
 
+/* ---- PointCloud: a cloud resident on the device between the steps of a pipeline -------------------------------------------
+ * (the reference's Core/Geometry/PointCloud.h and .cpp :47-198, DownSample.cpp :90-105 and :222-254, EstimateNormals.cpp
+ * :158-204, Eigen's Dot.h and LU/InverseImpl.h.)  A cloud is an object owned by its context; it lives until
+ * visma_icp_cloud_destroy or the context's end and holds on the device: points (n x 3 f64) and, optionally, normals and
+ * colours (n x 3 f64).  "Has X" is the reference's HasX(): an attribute of no rows is not had.  n = 0 is a legal cloud
+ * everywhere and launches nothing.  from_tsdf copies the LAST ExtractPointCloud (voxel_cloud 0: points, normals, and colours
+ * unless the volume has none) or ExtractVoxelPointCloud (1: points and colours, no normals) of a volume device to device;
+ * VISMA_ICP_ERR_STATE before that extract (or after a frame or a reset).
+ *
+ * EVERY RESULT IS THE REFERENCE'S BIT FOR BIT but for the stated deviations, and a second identical call returns identical
+ * bytes: f64, every product, difference and sum rounded on its own (no fused multiply-add), correctly rounded square root and
+ * division; no floating-point atomics, one writer per row.
+ *   bounds            per axis std::min_element / max_element with a < b.  An empty cloud: zeros.  If the coordinate of
+ *                     point 0 is NaN the result is that NaN; otherwise NaNs are skipped and, among equal values, the lowest
+ *                     index wins: {0.0, -0.0} gives 0.0 and {-0.0, 0.0} gives -0.0.  (A reduction over (value, index)
+ *                     pairs, exact in any order.)
+ *   transform         T row-major 4 x 4: a row is ((T_i0 x + T_i1 y) + T_i2 z) + T_i3 w, w = 1 for points and w = 0 for
+ *                     normals (T_i3 * 0 is added: a NaN or infinite translation reaches the normals); the fourth row of T
+ *                     is not read.  Colours stay.  The kernel is the TriangleMesh's.
+ *   normalize_normals per normal n2 = (x x + y y) + z z; if n2 > 0 every component is divided by sqrt(n2), else the normal
+ *                     is left as it is.  The kernel is the TriangleMesh's WITHOUT its last step: PointCloud.h has no
+ *                     "x is NaN -> (0, 0, 1)" rule, so a NaN normal stays and (inf, 1, 1) becomes (NaN, 0, 0).
+ *   paint_uniform_color  every colour becomes rgb; an empty cloud stays without colours.
+ *   append            operator+=.  other empty: NOTHING changes (the reference does not even clear the normals).  Else the
+ *                     normals survive iff (this is empty or has normals) and other has them; colours by the same rule.
+ *                     other may be the cloud itself: it doubles.
+ *   select            a NEW cloud: the rows in the order of indices[], a repeated index repeats the row; normals and colours
+ *                     are carried.  DEVIATION: an index outside [0, n) is VISMA_ICP_ERR_INVALID (the reference reads out of
+ *                     bounds).
+ *   uniform_down_sample  a NEW cloud: every_k == 0 gives an empty one (and VISMA_ICP_OK), else the rows 0, k, 2k, ...;
+ *                     every_k < 0 is VISMA_ICP_ERR_INVALID (the reference's is a size_t).
+ *   crop              a NEW cloud: min_bound[k] > max_bound[k] for some k gives an empty one.  Else the points with
+ *                     min <= p <= max in every component, bounds included, in their order; a NaN, in a point or a bound,
+ *                     fails every test.
+ *   voxel_down_sample a NEW cloud: byte for byte what visma_icp_voxel_down_sample returns for the same rows.
+ *   estimate_normals  in place; normals the cloud has keep their sign.  Byte for byte what visma_icp_estimate_normals returns
+ *                     for the same rows and normals_in (the search grid's origin, the first point with three finite
+ *                     coordinates, is found on the device).  knn < 3 (KNN, Hybrid) or radius <= 0 (Radius, Hybrid): every
+ *                     normal is (0, 0, 1).
+ *   orient_normals_to_align_with_direction   per normal: norm() == 0.0 -- that is sqrt((x x + y y) + z z) == 0.0, so a squared
+ *                     norm that underflows counts as zero -- : the normal becomes ref; else if (x rx + y ry) + z rz < 0 it is
+ *                     multiplied by -1.0.
+ *   orient_normals_towards_camera_location   ref = camera - point per point; norm() == 0.0: the normal becomes ref,
+ *                     normalised as above -- or (0, 0, 1) where ref's norm() == 0.0 too (the camera at the point); else the
+ *                     sign rule.  DEVIATION, both: a cloud without normals is VISMA_ICP_ERR_STATE (the reference indexes an
+ *                     empty vector).
+ *   mean_and_covariance  an empty cloud: a zero mean and the identity.  Else the nine cumulants x, y, z, xx, xy, xz, yy, yz, zz
+ *                     (products rounded, then added), divided by n; mean = the first three; cov(0,0) = c3 - c0 c0, ... as
+ *                     PointCloud.cpp:164-178; cov row-major.  DEVIATION in the order of the sums, of the kind the centroid of
+ *                     visma_icp_set_clouds_f64 has: they run serially over chunks of 16,384 consecutive points and the chunk
+ *                     sums are added in chunk order.  A cloud of at most 16,384 points is summed in the reference's own order
+ *                     and equals it to the bit; a larger one differs in the last bits but is a function of the input only.
+ *   mahalanobis_distance  out[i] = sqrt((p^T C^-1) p), p = point - mean, with the mean and covariance above.  C^-1 is Eigen
+ *                     3.3.2's 3 x 3 inverse on the host: the cofactors, det as the sum of the first cofactor column times
+ *                     column 0, 1 / det, no invertibility test -- a singular covariance propagates inf and NaN, as in the
+ *                     reference.  Three-term sums are (a0 + a1) + a2, as the compiled reference's.
+ * get: each output may be NULL; n other than the cloud's is VISMA_ICP_ERR_INVALID, asking for an attribute the cloud does
+ * not have VISMA_ICP_ERR_STATE.  size: has_flags is a mask of VISMA_ICP_CLOUD_HAS_*.
+ * Limits: n must fit an int (also the sum of an append, and the number of selected indices), else VISMA_ICP_ERR_INVALID.
+ * A sharded context: VISMA_ICP_ERR_INVALID.  A cloud or a volume of another context: VISMA_ICP_ERR_INVALID.  Every call
+ * returns with the stream idle.  Memory: the cloud, and while a call runs about as much again. */
+#define VISMA_ICP_CLOUD_HAS_NORMALS 1
+#define VISMA_ICP_CLOUD_HAS_COLORS 2
+typedef struct visma_icp_cloud visma_icp_cloud;
+VISMA_ICP_API int visma_icp_cloud_create(visma_icp_ctx *ctx, const double *points, int64_t n, const double *normals,
+                                         const double *colors, visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_from_tsdf(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int voxel_cloud, visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_destroy(visma_icp_ctx *ctx, visma_icp_cloud *cloud);
+VISMA_ICP_API int visma_icp_cloud_size(const visma_icp_cloud *cloud, int64_t *n, int *has_flags);
+VISMA_ICP_API int visma_icp_cloud_get(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double *points, double *normals, double *colors,
+                                      int64_t n);
+VISMA_ICP_API int visma_icp_cloud_transform(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double T[16]);
+VISMA_ICP_API int visma_icp_cloud_normalize_normals(visma_icp_ctx *ctx, visma_icp_cloud *cloud);
+VISMA_ICP_API int visma_icp_cloud_paint_uniform_color(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double rgb[3]);
+VISMA_ICP_API int visma_icp_cloud_append(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const visma_icp_cloud *other);
+VISMA_ICP_API int visma_icp_cloud_bounds(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double min_bound[3], double max_bound[3]);
+VISMA_ICP_API int visma_icp_cloud_select(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const int64_t *indices, int64_t n,
+                                         visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_uniform_down_sample(visma_icp_ctx *ctx, visma_icp_cloud *cloud, int64_t every_k,
+                                                      visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_crop(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double min_bound[3],
+                                       const double max_bound[3], visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_voxel_down_sample(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double voxel_size,
+                                                    visma_icp_cloud **out);
+/* search_type, knn, radius: as visma_icp_estimate_normals */
+VISMA_ICP_API int visma_icp_cloud_estimate_normals(visma_icp_ctx *ctx, visma_icp_cloud *cloud, int search_type, int knn,
+                                                   double radius);
+VISMA_ICP_API int visma_icp_cloud_orient_normals_to_align_with_direction(visma_icp_ctx *ctx, visma_icp_cloud *cloud,
+                                                                         const double ref[3]);
+VISMA_ICP_API int visma_icp_cloud_orient_normals_towards_camera_location(visma_icp_ctx *ctx, visma_icp_cloud *cloud,
+                                                                         const double camera[3]);
+VISMA_ICP_API int visma_icp_cloud_mean_and_covariance(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double mean[3], double cov[9]);
+/* out: n doubles on the host */
+VISMA_ICP_API int visma_icp_cloud_mahalanobis_distance(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double *out);
+
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

@@ -1018,6 +1018,28 @@ inline std::shared_ptr<PointCloud> VoxelDownSample(const PointCloud &input, doub
     return output;
 }
 
+namespace detail {
+// a KDTreeSearchParam as the C ABI takes it: search_type 0 KNN | 1 Radius | 2 Hybrid, knn (max_nn), radius
+inline void search_arguments(const KDTreeSearchParam &search_param, int *type, int *knn, double *radius)
+{
+    *type = 0; *knn = 0; *radius = 0.0;
+    switch (search_param.GetSearchType()) {
+    case KDTreeSearchParam::SearchType::Knn:
+        *knn = static_cast<const KDTreeSearchParamKNN &>(search_param).knn_;
+        break;
+    case KDTreeSearchParam::SearchType::Radius:
+        *type = 1;
+        *radius = static_cast<const KDTreeSearchParamRadius &>(search_param).radius_;
+        break;
+    case KDTreeSearchParam::SearchType::Hybrid:
+        *type = 2;
+        *radius = static_cast<const KDTreeSearchParamHybrid &>(search_param).radius_;
+        *knn = static_cast<const KDTreeSearchParamHybrid &>(search_param).max_nn_;
+        break;
+    }
+}
+}  // namespace detail
+
 // open3d::EstimateNormals (O3D/Core/Geometry/EstimateNormals.cpp:114-153) on the GPU: the three
 // KDTreeFlann searches, FastEigen3x3, (0,0,1) for fewer than 3 neighbours, the sign of existing normals
 // kept.  What a caller runs before the point-to-plane estimator on clouds without normals
@@ -1028,20 +1050,7 @@ inline bool EstimateNormals(PointCloud &cloud, const KDTreeSearchParam &search_p
     const bool has_normal = cloud.HasNormals();
     int type = 0, knn = 0;
     double radius = 0.0;
-    switch (search_param.GetSearchType()) {
-    case KDTreeSearchParam::SearchType::Knn:
-        knn = static_cast<const KDTreeSearchParamKNN &>(search_param).knn_;
-        break;
-    case KDTreeSearchParam::SearchType::Radius:
-        type = 1;
-        radius = static_cast<const KDTreeSearchParamRadius &>(search_param).radius_;
-        break;
-    case KDTreeSearchParam::SearchType::Hybrid:
-        type = 2;
-        radius = static_cast<const KDTreeSearchParamHybrid &>(search_param).radius_;
-        knn = static_cast<const KDTreeSearchParamHybrid &>(search_param).max_nn_;
-        break;
-    }
+    detail::search_arguments(search_param, &type, &knn, &radius);
     std::vector<Eigen::Vector3d> out((size_t)n);
     if (n > 0) {
         visma_icp_ctx *ctx = detail::ThreadContext::instance().get();
@@ -2210,6 +2219,190 @@ inline std::shared_ptr<TriangleMesh> ExtractTriangleMesh(TSDFVolume &volume, boo
     if (vertex_normals) d.ComputeVertexNormals(normalized);
     return d.Download();
 }
+
+// ---- open3d::PointCloud on the GPU (visma_icp.h, "PointCloud") ----
+// DevicePointCloud: a cloud resident on the device, for a chain of steps with one upload and one download -- or none: the
+// cloud a TSDF volume extracted is taken where it lies (FromVolume).  The free functions below are one such chain each.  A
+// selected index outside [0, points) throws std::runtime_error, as do the OrientNormals* of a cloud without normals.
+class DevicePointCloud {
+public:
+    DevicePointCloud(visma_icp_ctx *ctx, const PointCloud &cloud) : ctx_(ctx)
+    {
+        detail::check(ctx_, visma_icp_cloud_create(ctx_, detail::xyz(cloud.points_), (int64_t)cloud.points_.size(),
+                                                   cloud.HasNormals() ? detail::xyz(cloud.normals_) : nullptr,
+                                                   cloud.HasColors() ? detail::xyz(cloud.colors_) : nullptr, &cloud_),
+                      "visma_icp_cloud_create");
+    }
+    explicit DevicePointCloud(const PointCloud &cloud) : DevicePointCloud(detail::ThreadContext::instance().get(), cloud) {}
+    // the volume's last ExtractPointCloud (or, voxel_cloud, ExtractVoxelPointCloud), copied device to device (extract first:
+    // cicp::ExtractPointCloud does both)
+    static DevicePointCloud FromVolume(const TSDFVolume &volume, bool voxel_cloud = false)
+    {
+        DevicePointCloud c(volume.Context(), nullptr);
+        detail::check(c.ctx_, visma_icp_cloud_from_tsdf(c.ctx_, volume.Handle(), voxel_cloud ? 1 : 0, &c.cloud_), "visma_icp_cloud_from_tsdf");
+        return c;
+    }
+    ~DevicePointCloud() { if (cloud_) (void)visma_icp_cloud_destroy(ctx_, cloud_); }
+    DevicePointCloud(DevicePointCloud &&o) noexcept : ctx_(o.ctx_), cloud_(o.cloud_) { o.cloud_ = nullptr; }
+    DevicePointCloud &operator=(DevicePointCloud &&o) noexcept                       // (c = c.Crop(lo, hi): the old cloud is freed)
+    {
+        if (this != &o) {
+            if (cloud_) (void)visma_icp_cloud_destroy(ctx_, cloud_);
+            ctx_ = o.ctx_; cloud_ = o.cloud_;
+            o.cloud_ = nullptr;
+        }
+        return *this;
+    }
+    DevicePointCloud(const DevicePointCloud &) = delete;
+    DevicePointCloud &operator=(const DevicePointCloud &) = delete;
+
+    size_t size() const
+    {
+        int64_t n = 0;
+        detail::check(ctx_, visma_icp_cloud_size(cloud_, &n, nullptr), "visma_icp_cloud_size");
+        return (size_t)n;
+    }
+    void Transform(const Eigen::Matrix4d &T)
+    {
+        double t[16];
+        for (int i = 0; i < 16; i++) t[i] = T(i / 4, i % 4);          // (either storage order)
+        detail::check(ctx_, visma_icp_cloud_transform(ctx_, cloud_, t), "visma_icp_cloud_transform");
+    }
+    void NormalizeNormals() { detail::check(ctx_, visma_icp_cloud_normalize_normals(ctx_, cloud_), "visma_icp_cloud_normalize_normals"); }
+    void PaintUniformColor(const Eigen::Vector3d &color)
+    {
+        detail::check(ctx_, visma_icp_cloud_paint_uniform_color(ctx_, cloud_, color.data()), "visma_icp_cloud_paint_uniform_color");
+    }
+    DevicePointCloud &operator+=(const DevicePointCloud &other)
+    {
+        detail::check(ctx_, visma_icp_cloud_append(ctx_, cloud_, other.cloud_), "visma_icp_cloud_append");
+        return *this;
+    }
+    Eigen::Vector3d GetMinBound() const { return Bounds().first; }
+    Eigen::Vector3d GetMaxBound() const { return Bounds().second; }
+    std::pair<Eigen::Vector3d, Eigen::Vector3d> Bounds() const
+    {
+        Eigen::Vector3d lo, hi;
+        detail::check(ctx_, visma_icp_cloud_bounds(ctx_, cloud_, lo.data(), hi.data()), "visma_icp_cloud_bounds");
+        return std::make_pair(lo, hi);
+    }
+    DevicePointCloud Select(const std::vector<size_t> &indices) const
+    {
+        const std::vector<int64_t> idx(indices.begin(), indices.end());
+        DevicePointCloud out(ctx_, nullptr);
+        detail::check(ctx_, visma_icp_cloud_select(ctx_, cloud_, idx.data(), (int64_t)idx.size(), &out.cloud_), "visma_icp_cloud_select");
+        return out;
+    }
+    DevicePointCloud UniformDownSample(size_t every_k_points) const
+    {
+        DevicePointCloud out(ctx_, nullptr);
+        const int64_t k = every_k_points > (size_t)std::numeric_limits<int64_t>::max() ? std::numeric_limits<int64_t>::max() : (int64_t)every_k_points;
+        detail::check(ctx_, visma_icp_cloud_uniform_down_sample(ctx_, cloud_, k, &out.cloud_), "visma_icp_cloud_uniform_down_sample");
+        return out;
+    }
+    DevicePointCloud Crop(const Eigen::Vector3d &min_bound, const Eigen::Vector3d &max_bound) const
+    {
+        DevicePointCloud out(ctx_, nullptr);
+        detail::check(ctx_, visma_icp_cloud_crop(ctx_, cloud_, min_bound.data(), max_bound.data(), &out.cloud_), "visma_icp_cloud_crop");
+        return out;
+    }
+    DevicePointCloud VoxelDownSample(double voxel_size) const
+    {
+        DevicePointCloud out(ctx_, nullptr);
+        detail::check(ctx_, visma_icp_cloud_voxel_down_sample(ctx_, cloud_, voxel_size, &out.cloud_), "visma_icp_cloud_voxel_down_sample");
+        return out;
+    }
+    void EstimateNormals(const KDTreeSearchParam &search_param = KDTreeSearchParamKNN())
+    {
+        int type = 0, knn = 0;
+        double radius = 0.0;
+        detail::search_arguments(search_param, &type, &knn, &radius);
+        detail::check(ctx_, visma_icp_cloud_estimate_normals(ctx_, cloud_, type, knn, radius), "visma_icp_cloud_estimate_normals");
+    }
+    void OrientNormalsToAlignWithDirection(const Eigen::Vector3d &orientation_reference = Eigen::Vector3d(0.0, 0.0, 1.0))
+    {
+        detail::check(ctx_, visma_icp_cloud_orient_normals_to_align_with_direction(ctx_, cloud_, orientation_reference.data()),
+                      "visma_icp_cloud_orient_normals_to_align_with_direction");
+    }
+    void OrientNormalsTowardsCameraLocation(const Eigen::Vector3d &camera_location = Eigen::Vector3d::Zero())
+    {
+        detail::check(ctx_, visma_icp_cloud_orient_normals_towards_camera_location(ctx_, cloud_, camera_location.data()),
+                      "visma_icp_cloud_orient_normals_towards_camera_location");
+    }
+    std::tuple<Eigen::Vector3d, Eigen::Matrix3d> MeanAndCovariance() const
+    {
+        Eigen::Vector3d mean;
+        double cov[9];
+        detail::check(ctx_, visma_icp_cloud_mean_and_covariance(ctx_, cloud_, mean.data(), cov), "visma_icp_cloud_mean_and_covariance");
+        Eigen::Matrix3d C;
+        for (int i = 0; i < 9; i++) C(i / 3, i % 3) = cov[i];          // (either storage order)
+        return std::make_tuple(mean, C);
+    }
+    std::vector<double> MahalanobisDistance() const
+    {
+        std::vector<double> out(size());
+        detail::check(ctx_, visma_icp_cloud_mahalanobis_distance(ctx_, cloud_, out.data()), "visma_icp_cloud_mahalanobis_distance");
+        return out;
+    }
+    // the device's rows into `cloud`; an attribute the device cloud does not have is cleared
+    void Download(PointCloud &cloud) const
+    {
+        int64_t n = 0;
+        int has = 0;
+        detail::check(ctx_, visma_icp_cloud_size(cloud_, &n, &has), "visma_icp_cloud_size");
+        const bool hn = has & VISMA_ICP_CLOUD_HAS_NORMALS, hc = has & VISMA_ICP_CLOUD_HAS_COLORS;
+        cloud.points_.resize((size_t)n);
+        cloud.normals_.resize(hn ? (size_t)n : 0);
+        cloud.colors_.resize(hc ? (size_t)n : 0);
+        detail::check(ctx_, visma_icp_cloud_get(ctx_, cloud_, n ? cloud.points_[0].data() : nullptr, hn ? cloud.normals_[0].data() : nullptr,
+                                                hc ? cloud.colors_[0].data() : nullptr, n),
+                      "visma_icp_cloud_get");
+    }
+    std::shared_ptr<PointCloud> Download() const
+    {
+        auto out = std::make_shared<PointCloud>();
+        Download(*out);
+        return out;
+    }
+    visma_icp_ctx *context() const { return ctx_; }
+    visma_icp_cloud *handle() const { return cloud_; }
+
+private:
+    DevicePointCloud(visma_icp_ctx *ctx, std::nullptr_t) : ctx_(ctx) {}
+    visma_icp_ctx *ctx_ = nullptr;
+    visma_icp_cloud *cloud_ = nullptr;
+};
+
+// the free functions of Core/Geometry/PointCloud.h on a context of the caller's: one upload, one operation, one download
+inline std::shared_ptr<PointCloud> SelectDownSample(visma_icp_ctx *ctx, const PointCloud &input, const std::vector<size_t> &indices)
+{
+    return DevicePointCloud(ctx, input).Select(indices).Download();
+}
+inline std::shared_ptr<PointCloud> UniformDownSample(visma_icp_ctx *ctx, const PointCloud &input, size_t every_k_points)
+{
+    return DevicePointCloud(ctx, input).UniformDownSample(every_k_points).Download();
+}
+inline std::shared_ptr<PointCloud> CropPointCloud(visma_icp_ctx *ctx, const PointCloud &input, const Eigen::Vector3d &min_bound,
+                                                  const Eigen::Vector3d &max_bound)
+{
+    return DevicePointCloud(ctx, input).Crop(min_bound, max_bound).Download();
+}
+inline std::tuple<Eigen::Vector3d, Eigen::Matrix3d> ComputePointCloudMeanAndCovariance(visma_icp_ctx *ctx, const PointCloud &input)
+{
+    return DevicePointCloud(ctx, input).MeanAndCovariance();
+}
+inline std::vector<double> ComputePointCloudMahalanobisDistance(visma_icp_ctx *ctx, const PointCloud &input)
+{
+    return DevicePointCloud(ctx, input).MahalanobisDistance();
+}
+// ExtractPointCloud with the cloud left on the device: what follows it in the reference pipeline (crop, VoxelDownSample,
+// EstimateNormals) runs there, and Download() is the one copy to the host
+inline DevicePointCloud ExtractPointCloud(TSDFVolume &volume)
+{
+    int64_t n = 0;
+    detail::check(volume.Context(), visma_icp_tsdf_extract_point_cloud(volume.Context(), volume.Handle(), &n), "visma_icp_tsdf_extract_point_cloud");
+    return DevicePointCloud::FromVolume(volume);
+}
 #endif
 
 }  // namespace cicp
@@ -2452,6 +2645,26 @@ inline Eigen::Matrix4d TransformationEstimationPointToPlane::ComputeTransformati
 inline std::shared_ptr<PointCloud> VoxelDownSample(const PointCloud &input, double voxel_size)
 {
     return cicp::VoxelDownSample(input, voxel_size);
+}
+inline std::shared_ptr<PointCloud> SelectDownSample(const PointCloud &input, const std::vector<size_t> &indices)
+{
+    return cicp::SelectDownSample(cicp::detail::ThreadContext::instance().get(), input, indices);
+}
+inline std::shared_ptr<PointCloud> UniformDownSample(const PointCloud &input, size_t every_k_points)
+{
+    return cicp::UniformDownSample(cicp::detail::ThreadContext::instance().get(), input, every_k_points);
+}
+inline std::shared_ptr<PointCloud> CropPointCloud(const PointCloud &input, const Eigen::Vector3d &min_bound, const Eigen::Vector3d &max_bound)
+{
+    return cicp::CropPointCloud(cicp::detail::ThreadContext::instance().get(), input, min_bound, max_bound);
+}
+inline std::tuple<Eigen::Vector3d, Eigen::Matrix3d> ComputePointCloudMeanAndCovariance(const PointCloud &input)
+{
+    return cicp::ComputePointCloudMeanAndCovariance(cicp::detail::ThreadContext::instance().get(), input);
+}
+inline std::vector<double> ComputePointCloudMahalanobisDistance(const PointCloud &input)
+{
+    return cicp::ComputePointCloudMahalanobisDistance(cicp::detail::ThreadContext::instance().get(), input);
 }
 inline Eigen::Matrix6d GetInformationMatrixFromPointClouds(const PointCloud &source, const PointCloud &target,
                                                            double max_correspondence_distance,

@@ -209,6 +209,13 @@ class TsdfVolume:
         self.ctx._chk(self.ctx.L.visma_icp_trimesh_from_tsdf(self.ctx._h, self._v, C.byref(m)))
         return TriMesh(self.ctx, m)
 
+    def point_cloud(self, voxel=False):
+        """The last extract_point_cloud() (voxel=False) or extract_voxel_point_cloud() (True) as a Cloud, copied device to
+        device (visma_icp_cloud_from_tsdf).  Before that extract, or after a frame or a reset: IcpError (state)."""
+        c = C.c_void_p()
+        self.ctx._chk(self.ctx.L.visma_icp_cloud_from_tsdf(self.ctx._h, self._v, int(bool(voxel)), C.byref(c)))
+        return Cloud(self.ctx, c)
+
     def units(self):
         """The unit indices of a scalable volume (n x 3 int32) in lexicographic order: the order of its extractions."""
         n = C.c_int64(0)
@@ -323,6 +330,118 @@ class TriMesh:
     def transform(self, T):
         T = _f64(T, (16,))
         self.ctx._chk(self.ctx.L.visma_icp_trimesh_transform(self.ctx._h, self._m, _p(T, _dp)))
+
+
+CLOUD_HAS_NORMALS, CLOUD_HAS_COLORS = 1, 2
+
+
+class Cloud:
+    """Open3D's PointCloud resident on the device (visma_icp_cloud; Context.cloud, TsdfVolume.point_cloud): points and,
+    optionally, normals and colours stay there between the steps of a pipeline (include/visma_icp.h has the rules and the
+    deviations).  The operations that make a new cloud return a Cloud.  Lives until close() or the context's end; usable as
+    a context manager."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._c = ctx, handle
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _call(self, name, *args):
+        self.ctx._chk(getattr(self.ctx.L, "visma_icp_cloud_" + name)(self.ctx._h, self._c, *args))
+
+    def _new(self, name, *args):
+        c = C.c_void_p()
+        self._call(name, *args, C.byref(c))
+        return Cloud(self.ctx, c)
+
+    def close(self):
+        if self._c is not None and self.ctx._h:
+            self._call("destroy")
+        self._c = None
+
+    def size(self):
+        """-> n, has_flags (a mask of CLOUD_HAS_*)"""
+        n, f = C.c_int64(0), C.c_int(0)
+        self.ctx._chk(self.ctx.L.visma_icp_cloud_size(self._c, C.byref(n), C.byref(f)))
+        return n.value, f.value
+
+    def __len__(self):
+        return self.size()[0]
+
+    def get(self):
+        """-> dict(points n x 3 f64, normals, colors: n x 3 f64, or None for what the cloud does not have)"""
+        n, f = self.size()
+        out = dict(points=np.empty((n, 3)), normals=np.empty((n, 3)) if f & CLOUD_HAS_NORMALS else None,
+                   colors=np.empty((n, 3)) if f & CLOUD_HAS_COLORS else None)
+        dp = lambda k: None if out[k] is None else _p(out[k], _dp)
+        self._call("get", dp("points"), dp("normals"), dp("colors"), n)
+        return out
+
+    def transform(self, T):
+        self._call("transform", _p(_f64(T, (16,)), _dp))
+
+    def normalize_normals(self):
+        self._call("normalize_normals")
+
+    def paint_uniform_color(self, rgb):
+        self._call("paint_uniform_color", _p(_f64(rgb, (3,)), _dp))
+
+    def append(self, other):
+        """operator+=; other may be this cloud"""
+        self._call("append", other._c)
+
+    def bounds(self):
+        """GetMinBound(), GetMaxBound() -> min (3), max (3)"""
+        lo, hi = np.empty(3), np.empty(3)
+        self._call("bounds", _p(lo, _dp), _p(hi, _dp))
+        return lo, hi
+
+    def select(self, indices):
+        """SelectDownSample -> a new Cloud: the rows in the order of indices"""
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        return self._new("select", _p(idx, C.POINTER(C.c_int64)), len(idx))
+
+    def uniform_down_sample(self, every_k):
+        """UniformDownSample -> a new Cloud: the rows 0, k, 2k, ... (every_k == 0: an empty one)"""
+        return self._new("uniform_down_sample", int(every_k))
+
+    def crop(self, min_bound, max_bound):
+        """CropPointCloud -> a new Cloud"""
+        lo, hi = _f64(min_bound, (3,)), _f64(max_bound, (3,))
+        return self._new("crop", _p(lo, _dp), _p(hi, _dp))
+
+    def voxel_down_sample(self, voxel_size):
+        """VoxelDownSample -> a new Cloud: the rows of Context.voxel_down_sample"""
+        return self._new("voxel_down_sample", float(voxel_size))
+
+    def estimate_normals(self, knn=30, radius=None):
+        """EstimateNormals in place: the normals of Context.estimate_normals for the same rows.  radius None: KNN(knn); knn
+        None: Radius(radius); both: Hybrid.  Normals the cloud has keep their sign."""
+        kind = 0 if radius is None else (1 if knn is None else 2)
+        self._call("estimate_normals", kind, int(knn or 0), float(radius or 0.0))
+
+    def orient_normals_to_align_with_direction(self, ref=(0.0, 0.0, 1.0)):
+        self._call("orient_normals_to_align_with_direction", _p(_f64(ref, (3,)), _dp))
+
+    def orient_normals_towards_camera_location(self, camera=(0.0, 0.0, 0.0)):
+        self._call("orient_normals_towards_camera_location", _p(_f64(camera, (3,)), _dp))
+
+    def mean_and_covariance(self):
+        """ComputePointCloudMeanAndCovariance -> mean (3), covariance (3 x 3)"""
+        mean, cov = np.empty(3), np.empty((3, 3))
+        self._call("mean_and_covariance", _p(mean, _dp), _p(cov, _dp))
+        return mean, cov
+
+    def mahalanobis_distance(self):
+        """ComputePointCloudMahalanobisDistance -> n f64"""
+        out = np.empty(max(self.size()[0], 1))
+        self._call("mahalanobis_distance", _p(out, _dp))
+        return out[:self.size()[0]]
 
 
 class KDTree:
@@ -820,6 +939,25 @@ def _bind(L):
         L.visma_icp_trimesh_select.argtypes = [_vp, _vp, _i64, C.c_int64, C.POINTER(_vp)]
         L.visma_icp_trimesh_crop.argtypes = [_vp, _vp, _dp, _dp, C.POINTER(_vp)]
         L.visma_icp_trimesh_transform.argtypes = [_vp, _vp, _dp]
+    if hasattr(L, "visma_icp_cloud_create"):             # (A/B runs load older builds through VISMA_ICP_LIB)
+        _i64, _vp, _out = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_void_p)
+        L.visma_icp_cloud_create.argtypes = [_vp, _dp, C.c_int64, _dp, _dp, _out]
+        L.visma_icp_cloud_from_tsdf.argtypes = [_vp, _vp, C.c_int, _out]
+        L.visma_icp_cloud_destroy.argtypes = [_vp, _vp]
+        L.visma_icp_cloud_size.argtypes = [_vp, _i64, C.POINTER(C.c_int)]
+        L.visma_icp_cloud_get.argtypes = [_vp, _vp, _dp, _dp, _dp, C.c_int64]
+        for name in ("transform", "paint_uniform_color", "orient_normals_to_align_with_direction",
+                     "orient_normals_towards_camera_location", "mahalanobis_distance"):
+            getattr(L, "visma_icp_cloud_" + name).argtypes = [_vp, _vp, _dp]
+        L.visma_icp_cloud_normalize_normals.argtypes = [_vp, _vp]
+        L.visma_icp_cloud_append.argtypes = [_vp, _vp, _vp]
+        L.visma_icp_cloud_bounds.argtypes = [_vp, _vp, _dp, _dp]
+        L.visma_icp_cloud_mean_and_covariance.argtypes = [_vp, _vp, _dp, _dp]
+        L.visma_icp_cloud_select.argtypes = [_vp, _vp, _i64, C.c_int64, _out]
+        L.visma_icp_cloud_uniform_down_sample.argtypes = [_vp, _vp, C.c_int64, _out]
+        L.visma_icp_cloud_crop.argtypes = [_vp, _vp, _dp, _dp, _out]
+        L.visma_icp_cloud_voxel_down_sample.argtypes = [_vp, _vp, C.c_double, _out]
+        L.visma_icp_cloud_estimate_normals.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_double]
     if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
         _opt = C.POINTER(CColorMapOption)
@@ -1676,6 +1814,18 @@ class Context:
         m = C.c_void_p()
         self._chk(self.L.visma_icp_trimesh_create(self._h, _p(v, _dp), len(v), dp(vn), dp(vc), _p(t, _ip), len(t), dp(tn), C.byref(m)))
         return TriMesh(self, m)
+
+    # ---- PointCloud (visma_icp.h) ----
+    def cloud(self, points, normals=None, colors=None):
+        """Open3D's PointCloud on the device -> Cloud.  points n x 3 f64 (n = 0 is a cloud), normals and colors n x 3 f64 or
+        None."""
+        p = _f64(points, (-1, 3))
+        opt = lambda a: None if a is None else _f64(a, (len(p), 3))
+        nrm, col = opt(normals), opt(colors)
+        dp = lambda a: None if a is None else _p(a, _dp)
+        c = C.c_void_p()
+        self._chk(self.L.visma_icp_cloud_create(self._h, _p(p, _dp), len(p), dp(nrm), dp(col), C.byref(c)))
+        return Cloud(self, c)
 
     # ---- TSDF integration (visma_icp.h) ----
     def tsdf_uniform(self, length, resolution, sdf_trunc, color_type=TSDF_COLOR_NONE, origin=(0.0, 0.0, 0.0)):

@@ -343,6 +343,262 @@ int visma_icp_trimesh_transform(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, con
     return trimesh_done(ctx, "trimesh_transform", trimesh_device_transform(mesh->dev, T, ctx->eng->aux_stream()));
 }
 
+// ---- PointCloud: a cloud resident on the device (cloud.hip) ----
+static int cloud_enter(visma_icp_ctx *ctx, const visma_icp_cloud *cloud)
+{
+    if (cloud) {
+        bool mine = false;
+        for (const auto &c : ctx->clouds) mine = mine || c.get() == cloud;
+        if (!mine) return ctx->fail(VISMA_ICP_ERR_INVALID, "not a cloud of this context");
+    }
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "a point cloud lives on one rank");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "a point cloud needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+static int cloud_done(visma_icp_ctx *ctx, const char *what, hipError_t e)
+{
+    if (e == hipSuccess) return VISMA_ICP_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorInvalidValue) return ctx->fail(VISMA_ICP_ERR_INVALID, std::string(what) + ": an index outside [0, n), or more rows than an int holds");
+    return ctx->fail(VISMA_ICP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+static int cloud_adopt(visma_icp_ctx *ctx, CloudDevice *dev, visma_icp_cloud **out)
+{
+    std::unique_ptr<visma_icp_cloud> c(new visma_icp_cloud);
+    c->ctx = ctx; c->dev = dev;
+    *out = c.get();
+    ctx->clouds.push_back(std::move(c));
+    return VISMA_ICP_OK;
+}
+
+#define CLOUD_CHECK(cloud)                                                                   \
+    CTX_CHECK();                                                                             \
+    if (!(cloud)) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL cloud");                    \
+    if (int rc_ = cloud_enter(ctx, (cloud))) return rc_;
+
+// an operation that makes a new cloud: the checks before it
+#define CLOUD_NEW_CHECK(cloud)                                                               \
+    CTX_CHECK();                                                                             \
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");                       \
+    *out = nullptr;                                                                          \
+    if (!(cloud)) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL cloud");                    \
+    if (int rc_ = cloud_enter(ctx, (cloud))) return rc_;
+
+int visma_icp_cloud_create(visma_icp_ctx *ctx, const double *points, int64_t n, const double *normals, const double *colors,
+                           visma_icp_cloud **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (n < 0 || n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_create: n must fit an int");
+    if (n > 0 && !points) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_create: NULL argument");
+    if (int rc = cloud_enter(ctx, nullptr)) return rc;
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_create(points, n, normals, colors, false, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_create", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_from_tsdf(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int voxel_cloud, visma_icp_cloud **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    bool mine = false;
+    for (const auto &v : ctx->volumes) mine = mine || (volume && v.get() == volume);
+    if (!mine) return ctx->fail(VISMA_ICP_ERR_INVALID, volume ? "not a volume of this context" : "NULL volume");
+    if (voxel_cloud != 0 && voxel_cloud != 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_from_tsdf: voxel_cloud is 0 or 1");
+    if (int rc = cloud_enter(ctx, nullptr)) return rc;
+    if (volume->rows[voxel_cloud] < 0) return ctx->fail(VISMA_ICP_ERR_STATE, "no extraction: extract first");
+    TsdfCloudView view;
+    if (int rc = ctx->eng->tsdf_cloud_view(volume->id, voxel_cloud, &view)) return ctx->eng_fail(rc);
+    if (view.n > 0x7fffffff) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_from_tsdf: n must fit an int");
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_create(view.points, view.n, view.normals, view.colors, true, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_from_tsdf", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_destroy(visma_icp_ctx *ctx, visma_icp_cloud *cloud)
+{
+    CTX_CHECK();
+    if (!cloud) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL cloud");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    for (size_t i = 0; i < ctx->clouds.size(); i++)
+        if (ctx->clouds[i].get() == cloud) { ctx->clouds.erase(ctx->clouds.begin() + (std::ptrdiff_t)i); return VISMA_ICP_OK; }
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "not a cloud of this context");
+}
+
+int visma_icp_cloud_size(const visma_icp_cloud *cloud, int64_t *n, int *has_flags)
+{
+    if (!cloud || !cloud->dev) { g_create_error = "cloud is NULL"; return VISMA_ICP_ERR_INVALID; }
+    int64_t rows = 0;
+    int f = 0;
+    cloud_device_size(cloud->dev, &rows, &f);
+    if (n) *n = rows;
+    if (has_flags) *has_flags = f;
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_cloud_get(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double *points, double *normals, double *colors, int64_t n)
+{
+    CLOUD_CHECK(cloud);
+    int64_t rows = 0;
+    int f = 0;
+    cloud_device_size(cloud->dev, &rows, &f);
+    if (n != rows) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_get: n differs from the cloud's count");
+    if ((normals && !(f & kCloudNormals)) || (colors && !(f & kCloudColors)))
+        return ctx->fail(VISMA_ICP_ERR_STATE, "cloud_get: the cloud does not have that attribute");
+    return cloud_done(ctx, "cloud_get", cloud_device_get(cloud->dev, points, normals, colors, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_transform(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double T[16])
+{
+    CLOUD_CHECK(cloud);
+    if (!T) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_transform: NULL argument");
+    return cloud_done(ctx, "cloud_transform", cloud_device_transform(cloud->dev, T, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_normalize_normals(visma_icp_ctx *ctx, visma_icp_cloud *cloud)
+{
+    CLOUD_CHECK(cloud);
+    return cloud_done(ctx, "cloud_normalize_normals", cloud_device_normalize_normals(cloud->dev, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_paint_uniform_color(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double rgb[3])
+{
+    CLOUD_CHECK(cloud);
+    if (!rgb) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_paint_uniform_color: NULL argument");
+    return cloud_done(ctx, "cloud_paint_uniform_color", cloud_device_paint_uniform_color(cloud->dev, rgb, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_append(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const visma_icp_cloud *other)
+{
+    CLOUD_CHECK(cloud);
+    if (!other) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL cloud");
+    if (int rc = cloud_enter(ctx, other)) return rc;
+    return cloud_done(ctx, "cloud_append", cloud_device_append(cloud->dev, other->dev, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_bounds(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double min_bound[3], double max_bound[3])
+{
+    CLOUD_CHECK(cloud);
+    if (!min_bound || !max_bound) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_bounds: NULL argument");
+    return cloud_done(ctx, "cloud_bounds", cloud_device_bounds(cloud->dev, min_bound, max_bound, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_select(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const int64_t *indices, int64_t n, visma_icp_cloud **out)
+{
+    CLOUD_NEW_CHECK(cloud);
+    if (n < 0 || n > 0x7fffffff || (n > 0 && !indices)) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_select: 0 <= n indices, n fits an int");
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_select(cloud->dev, indices, n, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_select", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_uniform_down_sample(visma_icp_ctx *ctx, visma_icp_cloud *cloud, int64_t every_k, visma_icp_cloud **out)
+{
+    CLOUD_NEW_CHECK(cloud);
+    if (every_k < 0) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_uniform_down_sample: every_k >= 0");
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_uniform_down_sample(cloud->dev, every_k, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_uniform_down_sample", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_crop(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double min_bound[3], const double max_bound[3],
+                         visma_icp_cloud **out)
+{
+    CLOUD_NEW_CHECK(cloud);
+    if (!min_bound || !max_bound) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_crop: NULL argument");
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_crop(cloud->dev, min_bound, max_bound, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_crop", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_voxel_down_sample(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double voxel_size, visma_icp_cloud **out)
+{
+    CLOUD_NEW_CHECK(cloud);
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_voxel_down_sample(cloud->dev, voxel_size, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_voxel_down_sample", e);
+    return cloud_adopt(ctx, dev, out);
+}
+
+int visma_icp_cloud_estimate_normals(visma_icp_ctx *ctx, visma_icp_cloud *cloud, int search_type, int knn, double radius)
+{
+    CLOUD_CHECK(cloud);
+    if (search_type < 0 || search_type > 2) return ctx->fail(VISMA_ICP_ERR_INVALID, "bad estimate_normals arguments");
+    return cloud_done(ctx, "cloud_estimate_normals",
+                      cloud_device_estimate_normals(cloud->dev, search_type, knn, radius, ctx->eng->aux_stream()));
+}
+
+static int cloud_orient(visma_icp_ctx *ctx, visma_icp_cloud *cloud, bool camera, const double ref[3])
+{
+    CLOUD_CHECK(cloud);
+    if (!ref) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_orient_normals: NULL argument");
+    int64_t rows = 0;
+    int f = 0;
+    cloud_device_size(cloud->dev, &rows, &f);
+    if (!(f & kCloudNormals)) return ctx->fail(VISMA_ICP_ERR_STATE, "cloud_orient_normals: the cloud has no normals");   // (the reference indexes an empty vector)
+    return cloud_done(ctx, "cloud_orient_normals", cloud_device_orient_normals(cloud->dev, camera, ref, ctx->eng->aux_stream()));
+}
+
+int visma_icp_cloud_orient_normals_to_align_with_direction(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double ref[3])
+{
+    return cloud_orient(ctx, cloud, false, ref);
+}
+
+int visma_icp_cloud_orient_normals_towards_camera_location(visma_icp_ctx *ctx, visma_icp_cloud *cloud, const double camera[3])
+{
+    return cloud_orient(ctx, cloud, true, camera);
+}
+
+int visma_icp_cloud_mean_and_covariance(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double mean[3], double cov[9])
+{
+    CLOUD_CHECK(cloud);
+    if (!mean || !cov) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_mean_and_covariance: NULL argument");
+    return cloud_done(ctx, "cloud_mean_and_covariance",
+                      cloud_device_mean_and_covariance(cloud->dev, kHostChunk, mean, cov, ctx->eng->aux_stream()));
+}
+
+// Eigen 3.3.2's inverse of a 3 x 3 matrix (LU/InverseImpl.h:126-169), row-major m -> r: the cofactors, the determinant as
+// the sum of the first cofactor column times column 0, 1 / det, no invertibility test
+static void inverse3_eigen(const double m[9], double r[9])
+{
+    const double c0 = m[4] * m[8] - m[5] * m[7];
+    const double c1 = m[7] * m[2] - m[8] * m[1];
+    const double c2 = m[1] * m[5] - m[2] * m[4];
+    const double det = (c0 * m[0] + c1 * m[3]) + c2 * m[6];
+    const double invdet = 1.0 / det;
+    r[0] = c0 * invdet; r[1] = c1 * invdet; r[2] = c2 * invdet;
+    r[3] = (m[5] * m[6] - m[3] * m[8]) * invdet;
+    r[4] = (m[8] * m[0] - m[6] * m[2]) * invdet;
+    r[5] = (m[2] * m[3] - m[0] * m[5]) * invdet;
+    r[6] = (m[3] * m[7] - m[4] * m[6]) * invdet;
+    r[7] = (m[6] * m[1] - m[7] * m[0]) * invdet;
+    r[8] = (m[0] * m[4] - m[1] * m[3]) * invdet;
+}
+
+int visma_icp_cloud_mahalanobis_distance(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double *out)
+{
+    CLOUD_CHECK(cloud);
+    int64_t rows = 0;
+    int f = 0;
+    cloud_device_size(cloud->dev, &rows, &f);
+    if (rows > 0 && !out) return ctx->fail(VISMA_ICP_ERR_INVALID, "cloud_mahalanobis_distance: NULL argument");
+    double mean[3], cov[9], inv[9];
+    hipError_t e = cloud_device_mean_and_covariance(cloud->dev, kHostChunk, mean, cov, ctx->eng->aux_stream());
+    if (e != hipSuccess) return cloud_done(ctx, "cloud_mahalanobis_distance", e);
+    inverse3_eigen(cov, inv);
+    return cloud_done(ctx, "cloud_mahalanobis_distance", cloud_device_mahalanobis(cloud->dev, mean, inv, out, ctx->eng->aux_stream()));
+}
+
 // ---- FPFH, feature matching, fast global registration ----
 
 int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type,

@@ -47,6 +47,16 @@ struct visma_icp_trimesh {
     ~visma_icp_trimesh() { trimesh_device_destroy(dev); }
 };
 
+// a PointCloud of a context, resident on the device (cloud.hip)
+struct visma_icp_cloud {
+    visma_icp_ctx *ctx = nullptr;
+    CloudDevice *dev = nullptr;
+    visma_icp_cloud() = default;
+    visma_icp_cloud(const visma_icp_cloud &) = delete;
+    visma_icp_cloud &operator=(const visma_icp_cloud &) = delete;
+    ~visma_icp_cloud() { cloud_device_destroy(dev); }
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -80,6 +90,7 @@ struct visma_icp_ctx {
     std::vector<std::unique_ptr<visma_icp_tsdf>> volumes;   // the engine frees their device memory with itself
     std::vector<std::unique_ptr<visma_icp_kdtree>> trees;   // each frees its own, before the engine goes
     std::vector<std::unique_ptr<visma_icp_trimesh>> meshes;   // likewise
+    std::vector<std::unique_ptr<visma_icp_cloud>> clouds;   // likewise
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

@@ -419,6 +419,8 @@ public:
     }
     // the last mesh where it lies on the device (trimesh.hip copies it from there); VISMA_ICP_ERR_STATE: none to view
     virtual int tsdf_mesh_view(int /* id */, TsdfMeshView *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // ... and the last point cloud of that kind likewise (cloud.hip copies it from there)
+    virtual int tsdf_cloud_view(int /* id */, int /* voxel_cloud */, TsdfCloudView *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     virtual int tsdf_extract(int /* id */, int /* voxel_cloud */, int64_t * /* n */) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // ... and its rows (n x 3 doubles each; normals and colors may be NULL)
     virtual int tsdf_get_extract(int /* id */, int /* voxel_cloud */, double * /* points */, double * /* normals */, double * /* colors */)

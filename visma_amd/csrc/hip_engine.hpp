@@ -319,6 +319,7 @@ public:
     int tsdf_extract_mesh(int id, int64_t *nv, int64_t *nt) override;
     int tsdf_get_mesh(int id, double *vertices, double *colors, int32_t *triangles) override;
     int tsdf_mesh_view(int id, TsdfMeshView *view) override;
+    int tsdf_cloud_view(int id, int voxel_cloud, TsdfCloudView *view) override;
     int tsdf_get_extract(int id, int voxel_cloud, double *points, double *normals, double *colors) override;
     int tsdf_get_units(int id, std::vector<int32_t> *keys) override;
     int tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *weight, float *color) override;

@@ -1153,6 +1153,15 @@ int HipEngine::tsdf_mesh_view(int id, TsdfMeshView *view)
     return VISMA_ICP_OK;
 }
 
+int HipEngine::tsdf_cloud_view(int id, int voxel_cloud, TsdfCloudView *view)
+{
+    TsdfDevice *D = nullptr;
+    int rc = tsdf_enter(id, &D);
+    if (rc) return rc;
+    if (!tsdf_device_cloud_view(D, voxel_cloud, view)) { err_ = "no extraction: extract first"; return VISMA_ICP_ERR_STATE; }
+    return VISMA_ICP_OK;
+}
+
 int HipEngine::tsdf_get_units(int id, std::vector<int32_t> *keys)
 {
     TsdfDevice *D = nullptr;

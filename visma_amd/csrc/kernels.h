@@ -421,6 +421,11 @@ hipError_t nearest_neighbor_distance_device(const double *h_xyz, int64_t n, doub
 constexpr int kNormalsMaxList = 170;     // longer result lists live in global memory (a heap per point) instead of LDS
 hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double *h_nrm_in, int search_type,
                                    int knn, double radius, double *h_out, hipStream_t stream);
+// ... the device part alone (resident input and output; origin: nn_binning_origin's point of the cloud), not for the trivial
+// case (fewer than 3 neighbours for every point: every normal is (0, 0, 1), which the caller fills in)
+bool estimate_normals_trivial(int search_type, int knn, double radius);
+hipError_t estimate_normals_core(const double *d_xyz, int64_t n, const double *d_nrm_in, const double origin[3], int search_type,
+                                 int knn, double radius, double *d_out, hipStream_t stream);
 
 // ---- voxel down-sampling (voxel.hip): host arrays in, host arrays out ---------
 hipError_t voxel_down_sample_device(const double *h_xyz, const double *h_nrm, const double *h_col,
@@ -735,6 +740,13 @@ struct TsdfMeshView {
     int64_t nv = 0, nt = 0;
 };
 bool tsdf_device_mesh_view(const TsdfDevice *D, TsdfMeshView *view);
+// the last ExtractPointCloud (voxel_cloud == 0) or ExtractVoxelPointCloud likewise (normals NULL for the voxel cloud, colors
+// NULL for a surface cloud of a volume without colour); false: no such extraction since the last change
+struct TsdfCloudView {
+    const double *points = nullptr, *normals = nullptr, *colors = nullptr;
+    int64_t n = 0;
+};
+bool tsdf_device_cloud_view(const TsdfDevice *D, int voxel_cloud, TsdfCloudView *view);
 // the indices of a scalable volume's units, 3 per unit, in lexicographic order (the order of its extractions)
 void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys);
 // tsdf, weight (R^3) and color (R^3 x 3, interleaved as the reference keeps it) of a uniform volume (unit == NULL) or of
@@ -768,6 +780,37 @@ hipError_t trimesh_device_purge(TriMeshDevice *M, int64_t removed[4], hipStream_
 hipError_t trimesh_device_select(TriMeshDevice *S, const int64_t *indices, int64_t n, hipStream_t stream, TriMeshDevice **out);
 hipError_t trimesh_device_crop(TriMeshDevice *S, const double lo[3], const double hi[3], hipStream_t stream, TriMeshDevice **out);
 hipError_t trimesh_device_transform(TriMeshDevice *M, const double T[16], hipStream_t stream);
+
+// ---- PointCloud (cloud.hip): a cloud resident on the device: points and, optionally, normals and colours, n x 3 f64 ----
+// Every result is the reference's bit for bit but for the stated deviations (PointCloud.cpp, DownSample.cpp,
+// EstimateNormals.cpp); the rules: visma_icp.h.  Each call returns with the stream idle.  The arguments are checked by the
+// caller (aux_api.cpp) but for the selected indices: one outside [0, n) is hipErrorInvalidValue, and nothing is made.
+constexpr int kCloudNormals = 1, kCloudColors = 2;
+struct CloudDevice;
+// normals, colors may be NULL.  on_device: the arrays lie on this device and are copied there (the cloud of a TSDF volume)
+hipError_t cloud_device_create(const double *points, int64_t n, const double *normals, const double *colors, bool on_device,
+                               hipStream_t stream, CloudDevice **out);
+void cloud_device_destroy(CloudDevice *P);
+void cloud_device_size(const CloudDevice *P, int64_t *n, int *flags);
+// each output may be NULL; an attribute the cloud does not have is not written
+hipError_t cloud_device_get(CloudDevice *P, double *points, double *normals, double *colors, hipStream_t stream);
+hipError_t cloud_device_transform(CloudDevice *P, const double T[16], hipStream_t stream);
+hipError_t cloud_device_normalize_normals(CloudDevice *P, hipStream_t stream);
+hipError_t cloud_device_paint_uniform_color(CloudDevice *P, const double rgb[3], hipStream_t stream);
+hipError_t cloud_device_append(CloudDevice *P, const CloudDevice *other, hipStream_t stream);       // other may be P
+hipError_t cloud_device_bounds(CloudDevice *P, double lo[3], double hi[3], hipStream_t stream);
+// a new cloud (the source's scratch buffers are used: it is not const)
+hipError_t cloud_device_select(CloudDevice *S, const int64_t *indices, int64_t n, hipStream_t stream, CloudDevice **out);
+hipError_t cloud_device_uniform_down_sample(CloudDevice *S, int64_t every_k, hipStream_t stream, CloudDevice **out);
+hipError_t cloud_device_crop(CloudDevice *S, const double lo[3], const double hi[3], hipStream_t stream, CloudDevice **out);
+hipError_t cloud_device_voxel_down_sample(CloudDevice *S, double voxel, hipStream_t stream, CloudDevice **out);
+hipError_t cloud_device_estimate_normals(CloudDevice *P, int search_type, int knn, double radius, hipStream_t stream);
+// camera == false: OrientNormalsToAlignWithDirection(ref); true: OrientNormalsTowardsCameraLocation(ref).  The cloud has normals
+hipError_t cloud_device_orient_normals(CloudDevice *P, bool camera, const double ref[3], hipStream_t stream);
+// chunk: the points a serial sum runs over (the chunk sums are added in chunk order)
+hipError_t cloud_device_mean_and_covariance(CloudDevice *P, int64_t chunk, double mean[3], double cov[9], hipStream_t stream);
+// inv: the inverse covariance, row-major; out: n doubles on the host
+hipError_t cloud_device_mahalanobis(CloudDevice *P, const double mean[3], const double inv[9], double *out, hipStream_t stream);
 
 // ---- color map optimization (colormap.hip): frames, vertices, visibility and poses resident on the device ----
 constexpr int kColorMapSums = 29;                      // per camera: 21 upper entries of JJ (row by row), 6 of Jb, rr, count

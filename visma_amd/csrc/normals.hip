@@ -173,34 +173,26 @@ hipError_t launch_normals(const NormalArgs &a, hipStream_t stream)
 
 }  // namespace
 
-// search_type 0 KNN(knn) | 1 Radius(radius) | 2 Hybrid(radius, knn = max_nn); h_nrm_in may be NULL
-hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double *h_nrm_in, int search_type,
-                                   int knn, double radius, double *h_out, hipStream_t stream)
+bool estimate_normals_trivial(int search_type, int knn, double radius)
 {
-    if (n <= 0) return hipSuccess;
+    // fewer than 3 neighbours for every point (KDTreeFlann.cpp:121-126,171-176 return -1 / k < 3)
+    return (search_type != 1 && knn < 3) || (search_type != 0 && !(radius > 0.0));
+}
+
+// The device part: n > 0 resident points (d_nrm_in or NULL) -> d_out, binned from `origin` (nn_binning_origin's point).
+// Not for the trivial case.  Returns with the stream idle.
+hipError_t estimate_normals_core(const double *d_xyz, int64_t n, const double *d_nin, const double origin[3], int search_type,
+                                 int knn, double radius, double *d_out, hipStream_t stream)
+{
     if (search_type < 0 || search_type > 2 || n > 0x7fffffff) return hipErrorInvalidValue;
     const bool use_r = search_type != 0;
-    // fewer than 3 neighbours for every point (KDTreeFlann.cpp:121-126,171-176 return -1 / k < 3)
-    const bool trivial = (search_type != 1 && knn < 3) || (use_r && !(radius > 0.0));
-    if (trivial) {
-        for (int64_t i = 0; i < n; i++) { h_out[3 * i] = 0.0; h_out[3 * i + 1] = 0.0; h_out[3 * i + 2] = 1.0; }
-        return hipSuccess;
-    }
     int cap = search_type == 1 ? 1 : (int)std::min<int64_t>(knn, n);           // (Radius: set from the counting pass)
     NnGrid G;
     DevBufs B;
-    double *d_xyz = nullptr, *d_nin = nullptr, *d_out = nullptr;
-    VISMA_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
-    VISMA_TRY(B.alloc(&d_out, 3 * (size_t)n));
     VISMA_TRY(G.alloc(n));
-    if (h_nrm_in) {
-        VISMA_TRY(B.alloc(&d_nin, 3 * (size_t)n));
-        VISMA_TRY(hipMemcpyAsync(d_nin, h_nrm_in, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
-    }
-    VISMA_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
     ColorGradientInput in;
     in.xyz = d_xyz; in.n = n;
-    nn_binning_origin(h_xyz, n, in.origin);
+    for (int k = 0; k < 3; k++) in.origin[k] = origin[k];
     VISMA_TRY(G.build(in, nullptr, radius, use_r ? 0 : cap, stream));
     NormalArgs a{};
     a.view = G.view;
@@ -279,9 +271,33 @@ hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double 
             else VISMA_TRY((launch_normals<2, false, true>(a, stream)));
         }
     }
+    return hipStreamSynchronize(stream);
+}
+
+// search_type 0 KNN(knn) | 1 Radius(radius) | 2 Hybrid(radius, knn = max_nn); h_nrm_in may be NULL: upload, the core, download
+hipError_t estimate_normals_device(const double *h_xyz, int64_t n, const double *h_nrm_in, int search_type,
+                                   int knn, double radius, double *h_out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    if (search_type < 0 || search_type > 2 || n > 0x7fffffff) return hipErrorInvalidValue;
+    if (estimate_normals_trivial(search_type, knn, radius)) {
+        for (int64_t i = 0; i < n; i++) { h_out[3 * i] = 0.0; h_out[3 * i + 1] = 0.0; h_out[3 * i + 2] = 1.0; }
+        return hipSuccess;
+    }
+    DevBufs B;
+    double *d_xyz = nullptr, *d_nin = nullptr, *d_out = nullptr;
+    VISMA_TRY(B.alloc(&d_xyz, 3 * (size_t)n));
+    VISMA_TRY(B.alloc(&d_out, 3 * (size_t)n));
+    if (h_nrm_in) {
+        VISMA_TRY(B.alloc(&d_nin, 3 * (size_t)n));
+        VISMA_TRY(hipMemcpyAsync(d_nin, h_nrm_in, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    }
+    VISMA_TRY(hipMemcpyAsync(d_xyz, h_xyz, sizeof(double) * 3 * n, hipMemcpyHostToDevice, stream));
+    double origin[3] = {0.0, 0.0, 0.0};
+    nn_binning_origin(h_xyz, n, origin);
+    VISMA_TRY(estimate_normals_core(d_xyz, n, d_nin, origin, search_type, knn, radius, d_out, stream));
     VISMA_TRY(hipMemcpyAsync(h_out, d_out, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, stream));
-    VISMA_TRY(hipStreamSynchronize(stream));
-    return hipSuccess;
+    return hipStreamSynchronize(stream);
 }
 
 }  // namespace visma

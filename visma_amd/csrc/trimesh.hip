@@ -6,7 +6,7 @@
 //   BadIndexSource          creation: an index outside [0, nv) is counted (compact.h's count pass); no other kernel of this
 //                           file reads a vertex array through an index that has not passed it, and every remap keeps that
 //   tm_triangle_normals     one lane per triangle: (v1 - v0) x (v2 - v0), Eigen's component formula
-//   tm_normalize            n2 = (x x + y y) + z z; n2 > 0: every component / sqrt(n2); then x NaN -> (0, 0, 1)
+//   rows_normalize          (row_kernels.h, shared with cloud.hip) n2 = (x x + y y) + z z; n2 > 0: every component / sqrt(n2); then x NaN -> (0, 0, 1)
 //   tm_pairs, tm_vertex_sum ComputeVertexNormals: the 3 nt pairs (vertex, 3 t + c) in ONE stable radix sort by vertex over
 //                           ceil(log2 nv) bits, segment starts by head flags and compact.h, then one lane per vertex adds its
 //                           segment's triangle normals in ascending 3 t + c: the reference's order.  A vertex shared by very
@@ -22,6 +22,7 @@
 #include "compact.h"
 #include "dev_mem.h"
 #include "kernels.h"
+#include "row_kernels.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -58,21 +59,6 @@ __global__ __launch_bounds__(kThreads) void tm_triangle_normals(const double *v,
     }
 }
 
-// Eigen's normalize() (Dot.h: z = squaredNorm(); if (z > 0) derived() /= sqrt(z)), then the reference's NaN rule on x
-__global__ __launch_bounds__(kThreads) void tm_normalize(double *a, long long n)
-{
-    TM_LOOP(i, n) {
-        double x = a[3 * i], y = a[3 * i + 1], z = a[3 * i + 2];
-        const double n2 = (x * x + y * y) + z * z;
-        if (n2 > 0.0) {
-            const double len = sqrt(n2);
-            x = x / len; y = y / len; z = z / len;
-        }
-        if (isnan(x)) { x = 0.0; y = 0.0; z = 1.0; }
-        a[3 * i] = x; a[3 * i + 1] = y; a[3 * i + 2] = z;
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void tm_pairs(const int *tri, unsigned *key, int *val, long long n3)
 {
     TM_LOOP(i, n3) { key[i] = (unsigned)tri[i]; val[i] = (int)i; }
@@ -99,17 +85,6 @@ __global__ __launch_bounds__(kThreads) void tm_vertex_sum(const unsigned *key, c
             x = x + n[0]; y = y + n[1]; z = z + n[2];
         }
         vn[3 * v] = x; vn[3 * v + 1] = y; vn[3 * v + 2] = z;
-    }
-}
-
-// ---- Transform: a row is ((T_i0 x + T_i1 y) + T_i2 z) + T_i3 w, w = 1 for points and 0 for normals ---------------------
-struct Mat34 { double m[12]; };
-__global__ __launch_bounds__(kThreads) void tm_transform(double *a, long long n, Mat34 T, double w)
-{
-    TM_LOOP(i, n) {
-        const double x = a[3 * i], y = a[3 * i + 1], z = a[3 * i + 2];
-        for (int r = 0; r < 3; r++)
-            a[3 * i + r] = ((T.m[4 * r] * x + T.m[4 * r + 1] * y) + T.m[4 * r + 2] * z) + T.m[4 * r + 3] * w;
     }
 }
 
@@ -527,8 +502,8 @@ hipError_t trimesh_device_get(TriMeshDevice *M, double *v, double *vn, double *v
 
 hipError_t trimesh_device_normalize_normals(TriMeshDevice *M, hipStream_t stream)
 {
-    if (M->has_vn) tm_normalize<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->vn.get(), M->nv);
-    if (M->has_tn) tm_normalize<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->tn.get(), M->nt);
+    if (M->has_vn) rows_normalize<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->vn.get(), M->nv, true);
+    if (M->has_tn) rows_normalize<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->tn.get(), M->nt, true);
     VISMA_TRY(hipGetLastError());
     return hipStreamSynchronize(stream);
 }
@@ -630,11 +605,10 @@ hipError_t trimesh_device_crop(TriMeshDevice *S, const double lo[3], const doubl
 
 hipError_t trimesh_device_transform(TriMeshDevice *M, const double T[16], hipStream_t stream)
 {
-    Mat34 m;
-    for (int i = 0; i < 12; i++) m.m[i] = T[i];
-    if (M->nv > 0) tm_transform<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->v.get(), M->nv, m, 1.0);
-    if (M->has_vn) tm_transform<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->vn.get(), M->nv, m, 0.0);
-    if (M->has_tn) tm_transform<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->tn.get(), M->nt, m, 0.0);
+    const Mat34 m(T);
+    if (M->nv > 0) rows_transform<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->v.get(), M->nv, m, 1.0);
+    if (M->has_vn) rows_transform<<<capped_blocks(M->nv), kThreads, 0, stream>>>(M->vn.get(), M->nv, m, 0.0);
+    if (M->has_tn) rows_transform<<<capped_blocks(M->nt), kThreads, 0, stream>>>(M->tn.get(), M->nt, m, 0.0);
     VISMA_TRY(hipGetLastError());
     return hipStreamSynchronize(stream);
 }

@@ -1032,6 +1032,17 @@ bool tsdf_device_mesh_view(const TsdfDevice *D, TsdfMeshView *view)
     return true;
 }
 
+bool tsdf_device_cloud_view(const TsdfDevice *D, int voxel_cloud, TsdfCloudView *view)
+{
+    const int which = voxel_cloud ? 1 : 0;
+    if (D->rows[which] < 0) return false;
+    view->n = D->rows[which];
+    view->points = D->out_points[which].get();
+    view->normals = voxel_cloud ? nullptr : D->out_normals.get();
+    view->colors = (voxel_cloud || D->planes() > 0) ? D->out_colors[which].get() : nullptr;
+    return true;
+}
+
 void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys)
 {
     keys->clear();
