@@ -1,18 +1,25 @@
 // Core/Geometry/Image.h -- the image type RGB-D odometry takes (shape of O3D/Core/Geometry/Image.h): a width, a height, a
 // number of channels, bytes per channel and the pixel bytes, row-major.  Stand-alone and header-only: PrepareImage, PointerAt
 // and the two conversions an odometry caller needs (any image -> single-channel float, a depth image -> metres); the
-// filters and pyramids of the reference run on the GPU inside cicp::ComputeRGBDOdometry and are not offered as functions.
+// filters, pyramids and the other functions of the reference's Image.h are declared at the end and run on the GPU
+// (visma_icp_open3d.hpp, over the C ABI's resident image, visma_icp.h: visma_icp_image_*): an upload, the operation and a
+// download each, on the calling thread's context; cicp::DeviceImage keeps an image there across a chain of them.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <memory>
+#include <utility>
 #include <vector>
 
 namespace open3d {
 
+class PinholeCameraIntrinsic;
+
 class Image {
 public:
     enum class ColorToIntensityConversionType { Equal, Weighted };
+    enum class FilterType { Gaussian3, Gaussian5, Gaussian7, Sobel3Dx, Sobel3Dy };
 
     void Clear() { width_ = height_ = num_of_channels_ = bytes_per_channel_ = 0; data_.clear(); }
     bool HasData() const { return width_ > 0 && height_ > 0 && data_.size() == size_t(height_ * BytesPerLine()); }
@@ -23,6 +30,24 @@ public:
         data_.resize((size_t)width_ * height_ * num_of_channels_ * bytes_per_channel_);
     }
     int BytesPerLine() const { return width_ * num_of_channels_ * bytes_per_channel_; }
+    // (u, v) inside the image, at least inner_margin from its border
+    bool TestImageBoundary(double u, double v, double inner_margin = 0.0) const
+    {
+        return u >= inner_margin && u < width_ - inner_margin && v >= inner_margin && v < height_ - inner_margin;
+    }
+    // the bilinear value of a 1 x float image at (u, v) in [0, width - 1] x [0, height - 1], in f64; (false, 0) outside, on
+    // another format, on an image narrower or lower than 2 pixels and for a NaN coordinate (visma_icp.h: the deviation)
+    std::pair<bool, double> FloatValueAt(double u, double v) const
+    {
+        if (num_of_channels_ != 1 || bytes_per_channel_ != 4 || width_ < 2 || height_ < 2 || u != u || v != v || u < 0.0 ||
+            u > (double)(width_ - 1) || v < 0.0 || v > (double)(height_ - 1))
+            return std::make_pair(false, 0.0);
+        const int ui = std::max(std::min((int)u, width_ - 2), 0), vi = std::max(std::min((int)v, height_ - 2), 0);
+        const double pu = u - ui, pv = v - vi;
+        const float *p = (const float *)data_.data() + (size_t)vi * width_ + ui;
+        const double a = p[0], b = p[width_], c = p[1], d = p[width_ + 1];
+        return std::make_pair(true, (a * (1 - pv) + b * pv) * (1 - pu) + (c * (1 - pv) + d * pv) * pu);
+    }
 
     int width_ = 0;
     int height_ = 0;
@@ -79,5 +104,23 @@ inline std::shared_ptr<Image> ConvertDepthToFloatImage(const Image &depth, doubl
     }
     return out;
 }
+
+typedef std::vector<std::shared_ptr<Image>> ImagePyramid;
+
+// The rest of the reference's Image.h, on the GPU (visma_icp_open3d.hpp; the rules and the stated deviations: visma_icp.h,
+// "Image").  An input a function does not take gives the empty Image, as in the reference.
+inline std::shared_ptr<Image> CreateDepthToCameraDistanceMultiplierFloatImage(const PinholeCameraIntrinsic &intrinsic);
+template <typename T>
+std::shared_ptr<Image> CreateImageFromFloatImage(const Image &input);             // T: uint8_t or uint16_t; saturating
+inline std::shared_ptr<Image> FlipImage(const Image &input);                     // a transpose
+inline std::shared_ptr<Image> FilterImage(const Image &input, Image::FilterType type);
+inline std::shared_ptr<Image> FilterImage(const Image &input, const std::vector<double> &dx, const std::vector<double> &dy);
+inline std::shared_ptr<Image> FilterHorizontalImage(const Image &input, const std::vector<double> &kernel);
+inline std::shared_ptr<Image> DownsampleImage(const Image &input);
+inline std::shared_ptr<Image> DilateImage(const Image &input, int half_kernel_size = 1);
+inline void LinearTransformImage(Image &input, double scale, double offset = 0.0);
+inline void ClipIntensityImage(Image &input, double min = 0.0, double max = 1.0);
+inline ImagePyramid FilterImagePyramid(const ImagePyramid &input, Image::FilterType type);
+inline ImagePyramid CreateImagePyramid(const Image &image, size_t num_of_levels, bool with_gaussian_filter = true);
 
 }  // namespace open3d

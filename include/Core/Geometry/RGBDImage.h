@@ -3,6 +3,7 @@
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include <Eigen/Core>
 
@@ -32,6 +33,18 @@ inline std::shared_ptr<RGBDImage> CreateRGBDImageFromColorAndDepth(const Image &
     out->color_ = convert_rgb_to_intensity ? *CreateFloatImageFromImage(color) : color;
     return out;
 }
+
+// The dataset factories (Redwood: 1000 units per metre, 4 m; TUM: 5000, 4 m; SUN: each 16-bit depth rotated right by 3 bits,
+// then 1000, 7 m; NYU: bytes swapped, 351.3 / (1092.5 - d) m, then 1000, 7 m) and the RGB-D pyramids, on the GPU
+// (visma_icp_open3d.hpp).  Unlike the reference, SUN and NYU leave the caller's depth image as it is (visma_icp.h).
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromRedwoodFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity = true);
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromTUMFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity = true);
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromSUNFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity = true);
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromNYUFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity = true);
+typedef std::vector<std::shared_ptr<RGBDImage>> RGBDImagePyramid;
+inline RGBDImagePyramid FilterRGBDImagePyramid(const RGBDImagePyramid &rgbd_image_pyramid, Image::FilterType type);
+inline RGBDImagePyramid CreateRGBDImagePyramid(const RGBDImage &rgbd_image, size_t num_of_levels, bool with_gaussian_filter_for_color = true,
+                                               bool with_gaussian_filter_for_depth = false);
 
 // The points behind a depth image (1 x float in metres, or 1 x uint16 in depth_scale units per metre cut at depth_trunc),
 // every stride-th row and column, and behind an RGB-D image (float depth; colour 3 x uint8 or 1 x float) with their colours,

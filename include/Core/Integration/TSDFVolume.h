@@ -18,6 +18,8 @@ namespace open3d {
 
 enum class TSDFVolumeColorType { None = 0, RGB8 = 1, Gray32 = 2 };
 
+namespace cicp { class DeviceImage; }
+
 class TSDFVolume {
 public:
     TSDFVolume(double voxel_length, double sdf_trunc, TSDFVolumeColorType color_type)
@@ -29,6 +31,10 @@ public:
     // the intrinsic's size; extrinsic: world -> camera.  An image that does not fit throws std::invalid_argument (the
     // reference prints a warning and returns).
     virtual void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) = 0;
+    // ... of images resident on the device (cicp::DeviceImage, visma_icp_open3d.hpp): no host copy; the same voxels.  color
+    // may be NULL for a volume without colour
+    void Integrate(const cicp::DeviceImage &depth, const cicp::DeviceImage *color, const PinholeCameraIntrinsic &intrinsic,
+                   const Eigen::Matrix4d &extrinsic);
     virtual std::shared_ptr<PointCloud> ExtractPointCloud() = 0;
     // marching cubes: vertices_, vertex_colors_ (empty without colour) and triangles_.  The vertices and their colours are the
     // reference's; their order and the triangulation of a cube are this library's (visma_icp.h: THE ORDER, THE CASE RULE)

@@ -27,6 +27,7 @@ public:
 
     void Reset() override;
     void Integrate(const RGBDImage &image, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic) override;
+    using TSDFVolume::Integrate;                         // ... and of cicp::DeviceImages
     std::shared_ptr<PointCloud> ExtractPointCloud() override;
     std::shared_ptr<TriangleMesh> ExtractTriangleMesh() override;
     visma_icp_ctx *Context() const override { return ctx_; }

@@ -1806,6 +1806,134 @@ VISMA_ICP_API int visma_icp_cloud_mean_and_covariance(visma_icp_ctx *ctx, visma_
 /* out: n doubles on the host */
 VISMA_ICP_API int visma_icp_cloud_mahalanobis_distance(visma_icp_ctx *ctx, visma_icp_cloud *cloud, double *out);
 
+/* ---- Image: an image resident on the device between the steps of the RGB-D front end ---------------------------------------
+ * (the reference's Core/Geometry/Image.h, Image.cpp, ImageFactory.cpp, RGBDImage.cpp and RGBDImageFactory.cpp.)  An image is
+ * an object owned by its context; it lives until visma_icp_image_destroy or the context's end and holds on the device
+ * width x height pixels of `channels` channels of 1, 2 or 4 bytes each, row-major, channels interleaved.  create takes 1 .. 4
+ * channels (the reference's functions know 1 and 3).  An image of no pixels keeps its format (the reference's
+ * PrepareImage(0, 0, 1, 4)) and launches nothing.  "The empty image" below is the reference's Image(): 0 x 0, 0 channels,
+ * 0 bytes.  A function whose result is an image returns a NEW object; linear_transform and clip_intensity work in place, as
+ * the reference's do.  The arithmetic is the reference's operation for operation: fp32 where it computes in fp32, f64 where
+ * it widens, one rounding per operation, fp32 denormals kept.  Two runs give identical bytes.
+ *
+ *   to_float          CreateFloatImageFromImage: 1 channel: (float)p / 255.0f (1 byte), (float)p (2 bytes), p (float); 3
+ *                     channels: Equal (a + b + c) / 3.0f, Weighted 0.2990f a + 0.5870f b + 0.1140f c, each / 255.0f for
+ *                     1-byte channels only.  Any other channel count: the all-zero image.  An image without pixels: the empty
+ *                     image.  A type that is neither: VISMA_ICP_ERR_INVALID.
+ *   depth_to_float    ConvertDepthToFloatImage: to_float(Weighted), p /= (float)depth_scale in fp32, then 0 where
+ *                     (double)p >= depth_trunc.
+ *   from_float        CreateImageFromFloatImage<uint8_t> (bytes 1: (T)(p * 255.0f)) and <uint16_t> (bytes 2: (T)p); an input
+ *                     that is not 1 x float: the empty image.  DEVIATION: the reference's static_cast is defined only where
+ *                     the truncated value is representable; outside it this library SATURATES: NaN and negatives give 0,
+ *                     values beyond the maximum the maximum.
+ *   filter_horizontal FilterHorizontalImage: per tap the fp32 product pixel * (float)kernel[k], widened and added into an f64
+ *                     sum in tap order, one cast to fp32; indices clamped at both borders; any odd length (a kernel longer
+ *                     than a row is legal).  An even length, or an input that is not 1 x float: the empty image.
+ *   filter_separable  FilterImage(dx, dy): horizontal(dx), transpose, horizontal(dy), transpose.
+ *   filter            FilterImage(type), VISMA_ICP_IMAGE_GAUSSIAN3 .. SOBEL3DY; an unknown type: VISMA_ICP_ERR_INVALID.
+ *   flip              FlipImage, which is a TRANSPOSE: the output is height x width.
+ *   downsample        (p1 + p2 + p3 + p4) / 4.0f in fp32, in that order; floor(w / 2) x floor(h / 2), which may be 0 x 0.
+ *   dilate            255 where a pixel == 255 lies in the (2k + 1)^2 window inside the image, else 0; k < 0: all zeros.  An
+ *                     input that is not 1 x uint8: the empty image.
+ *   linear_transform  p = (float)(scale * (double)p + offset).  clip_intensity: p > max -> (float)max, then p < min ->
+ *                     (float)min, both compares in f64; a NaN stays.  Both leave an image that is not 1 x float as it is and
+ *                     return VISMA_ICP_OK (the reference warns).
+ *   pyramid           CreateImagePyramid: out[0] a copy, out[i] = downsample(filter(GAUSSIAN3)(out[i - 1])) or
+ *                     downsample(out[i - 1]).  An input that is not 1 x float has NO levels: every out[i] is NULL.
+ *   filter_pyramid    FilterImagePyramid: out[i] = filter(in[i], type).
+ *   distance_multiplier  CreateDepthToCameraDistanceMultiplierFloatImage for intrinsic = {fx, fy, cx, cy} and w x h: the
+ *                     image a TSDF volume integrates with (the same kernel).
+ *   float_value_at    Image::FloatValueAt for n coordinates uv (n x 2 f64: u, v): ok[i] (0 / 1) and value[i].  DEVIATION: on
+ *                     an image narrower or lower than 2 pixels the reference reads out of bounds, and with a NaN coordinate
+ *                     it casts a NaN to int: both give (0, 0.0) here.
+ *   rgbd              CreateRGBDImageFromColorAndDepth (COLOR_AND_DEPTH: the two doubles are read), ...FromRedwoodFormat
+ *                     (1000, 4), ...FromTUMFormat (5000, 4), ...FromSUNFormat (each 16-bit depth rotated right by 3 bits,
+ *                     then 1000, 7), ...FromNYUFormat (bytes swapped, 351.3 / (1092.5 - d), * 1000 rounded, then 1000, 7).
+ *                     out_depth = depth_to_float, out_color = to_float(Weighted) or a copy.  Images of different sizes: both
+ *                     outputs NULL and VISMA_ICP_OK (the reference's empty RGBDImage).  DEVIATIONS: the reference rewrites
+ *                     the caller's SUN / NYU depth in place through a const reference; the resident input is left as it is.
+ *                     NYU's (uint16_t)floor(xx * 1000 + 0.5) is undefined for swapped values 1088 .. 1092 (beyond 65535):
+ *                     saturated to 65535 here, which the 7 m truncation turns into 0.  A SUN / NYU depth that is not
+ *                     1 x uint16 (the reference reinterprets its bytes): VISMA_ICP_ERR_INVALID.
+ *
+ * Hand-offs: each takes the pixels device to device into the device core of the host-array entry point beside it, so the
+ * results are that entry point's byte for byte for the same pixel bytes.
+ *   visma_icp_tsdf_integrate_images    depth 1 x float; color of the volume's colour type (RGB8: 3 x uint8, GRAY32: 1 x float;
+ *                     not read by a volume without colour).  Anything else: VISMA_ICP_ERR_INVALID, the volume untouched.
+ *   visma_icp_odometry_prepare_images, visma_icp_rgbd_odometry_images   four 1 x float images of one size.
+ *   visma_icp_cloud_from_depth_image   CreatePointCloudFromDepthImage into a resident visma_icp_cloud: a 1 x float depth as it is, a
+ *                     1 x uint16 depth through depth_to_float(depth_scale, depth_trunc) first (the two doubles are read for it
+ *                     only); the rows of visma_icp_point_cloud_from_depth.  visma_icp_cloud_from_rgbd_images: a 1 x float depth with
+ *                     a 3 x uint8 or 1 x float colour; the rows of visma_icp_point_cloud_from_rgbd.  Any other format: an empty
+ *                     cloud and VISMA_ICP_OK, as in the reference.  extrinsic NULL: the identity.
+ *   visma_icp_image_from_odometry      a level of the resident odometry pyramid (which < VISMA_ICP_ODOMETRY_SRC_XYZ) as a
+ *                     new image: the device-to-device counterpart of visma_icp_odometry_get_image.
+ *
+ * get: n_bytes other than the image's size is VISMA_ICP_ERR_INVALID.  A sharded context: VISMA_ICP_ERR_INVALID.  An image of
+ * another context: VISMA_ICP_ERR_INVALID.  A context without the HIP engine: VISMA_ICP_ERR_STATE.  Every call returns with the
+ * stream idle. */
+#define VISMA_ICP_IMAGE_EQUAL 0
+#define VISMA_ICP_IMAGE_WEIGHTED 1
+#define VISMA_ICP_IMAGE_GAUSSIAN3 0
+#define VISMA_ICP_IMAGE_GAUSSIAN5 1
+#define VISMA_ICP_IMAGE_GAUSSIAN7 2
+#define VISMA_ICP_IMAGE_SOBEL3DX 3
+#define VISMA_ICP_IMAGE_SOBEL3DY 4
+#define VISMA_ICP_RGBD_COLOR_AND_DEPTH 0
+#define VISMA_ICP_RGBD_REDWOOD 1
+#define VISMA_ICP_RGBD_TUM 2
+#define VISMA_ICP_RGBD_SUN 3
+#define VISMA_ICP_RGBD_NYU 4
+typedef struct visma_icp_image visma_icp_image;
+VISMA_ICP_API int visma_icp_image_create(visma_icp_ctx *ctx, int w, int h, int channels, int bytes_per_channel, const void *data,
+                                         visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_destroy(visma_icp_ctx *ctx, visma_icp_image *img);
+VISMA_ICP_API int visma_icp_image_info(const visma_icp_image *img, int *w, int *h, int *channels, int *bytes_per_channel);
+VISMA_ICP_API int visma_icp_image_get(visma_icp_ctx *ctx, visma_icp_image *img, void *bytes, int64_t n_bytes);
+VISMA_ICP_API int visma_icp_image_copy(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_to_float(visma_icp_ctx *ctx, visma_icp_image *img, int type, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_depth_to_float(visma_icp_ctx *ctx, visma_icp_image *img, double depth_scale, double depth_trunc,
+                                                 visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_from_float(visma_icp_ctx *ctx, visma_icp_image *img, int bytes, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_filter(visma_icp_ctx *ctx, visma_icp_image *img, int type, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_filter_separable(visma_icp_ctx *ctx, visma_icp_image *img, const double *dx, int n_dx,
+                                                   const double *dy, int n_dy, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_filter_horizontal(visma_icp_ctx *ctx, visma_icp_image *img, const double *kernel, int n,
+                                                    visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_flip(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_downsample(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_dilate(visma_icp_ctx *ctx, visma_icp_image *img, int half_kernel_size, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_linear_transform(visma_icp_ctx *ctx, visma_icp_image *img, double scale, double offset);
+VISMA_ICP_API int visma_icp_image_clip_intensity(visma_icp_ctx *ctx, visma_icp_image *img, double min, double max);
+/* out: room for `levels` pointers */
+VISMA_ICP_API int visma_icp_image_pyramid(visma_icp_ctx *ctx, visma_icp_image *img, int levels, int with_gaussian_filter,
+                                          visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_filter_pyramid(visma_icp_ctx *ctx, visma_icp_image *const *in, int levels, int type,
+                                                 visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_distance_multiplier(visma_icp_ctx *ctx, const double intrinsic[4], int w, int h,
+                                                      visma_icp_image **out);
+VISMA_ICP_API int visma_icp_image_float_value_at(visma_icp_ctx *ctx, visma_icp_image *img, const double *uv, int64_t n, uint8_t *ok,
+                                                 double *value);
+VISMA_ICP_API int visma_icp_image_rgbd(visma_icp_ctx *ctx, visma_icp_image *color, visma_icp_image *depth, int format,
+                                       double depth_scale, double depth_trunc, int convert_rgb_to_intensity,
+                                       visma_icp_image **out_color, visma_icp_image **out_depth);
+VISMA_ICP_API int visma_icp_tsdf_integrate_images(visma_icp_ctx *ctx, visma_icp_tsdf *volume, visma_icp_image *depth,
+                                                  visma_icp_image *color, const double intrinsic[4], int intrinsic_w,
+                                                  int intrinsic_h, const double extrinsic[16]);
+VISMA_ICP_API int visma_icp_odometry_prepare_images(visma_icp_ctx *ctx, visma_icp_image *src_gray, visma_icp_image *src_depth,
+                                                    visma_icp_image *tgt_gray, visma_icp_image *tgt_depth, const double intrinsic[4],
+                                                    const double init[16], const visma_icp_odometry_option *option);
+VISMA_ICP_API int visma_icp_rgbd_odometry_images(visma_icp_ctx *ctx, visma_icp_image *src_gray, visma_icp_image *src_depth,
+                                                 visma_icp_image *tgt_gray, visma_icp_image *tgt_depth, const double intrinsic[4],
+                                                 const double init[16], int method, const visma_icp_odometry_option *option,
+                                                 double out_T[16], double out_info[36], visma_icp_odometry_result *out_result);
+VISMA_ICP_API int visma_icp_image_from_odometry(visma_icp_ctx *ctx, int which, int level, visma_icp_image **out);
+VISMA_ICP_API int visma_icp_cloud_from_depth_image(visma_icp_ctx *ctx, visma_icp_image *depth, const double intrinsic[4],
+                                                   const double extrinsic[16], double depth_scale, double depth_trunc, int stride,
+                                                   visma_icp_cloud **out);
+VISMA_ICP_API int visma_icp_cloud_from_rgbd_images(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image *color,
+                                                   const double intrinsic[4], const double extrinsic[16], visma_icp_cloud **out);
+
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

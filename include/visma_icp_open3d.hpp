@@ -2778,6 +2778,257 @@ inline RegistrationResult RegistrationICP(const PointCloud &source, const PointC
     return cicp::RegistrationICP(source, target, max_correspondence_distance, init, estimation,
                                  criteria);
 }
+
+// ---- Image: the reference's Image.h, ImageFactory.cpp, RGBDImage.h and RGBDImageFactory.cpp on the GPU ---------------------
+namespace cicp {
+
+// DeviceImage: an image resident on the device, for a chain of steps with one upload and one download -- or none, where the
+// chain ends in a volume or in the odometry.  Every step that makes an image returns a new DeviceImage.  An EMPTY DeviceImage
+// (no handle) stands for the pair of NULLs visma_icp_image_rgbd answers images of different sizes with.
+class DeviceImage {
+public:
+    DeviceImage(visma_icp_ctx *ctx, const Image &image) : ctx_(ctx)
+    {
+        if (image.num_of_channels_ == 0) return;             // the reference's empty Image: every operation on it gives it again
+        detail::check(ctx_, visma_icp_image_create(ctx_, image.width_, image.height_, image.num_of_channels_, image.bytes_per_channel_,
+                                                   image.data_.data(), &img_), "visma_icp_image_create");
+    }
+    explicit DeviceImage(const Image &image) : DeviceImage(detail::ThreadContext::instance().get(), image) {}
+    DeviceImage(visma_icp_ctx *ctx, visma_icp_image *adopted) : ctx_(ctx), img_(adopted) {}
+    ~DeviceImage() { if (img_) (void)visma_icp_image_destroy(ctx_, img_); }
+    DeviceImage(DeviceImage &&o) noexcept : ctx_(o.ctx_), img_(o.img_) { o.img_ = nullptr; }
+    DeviceImage &operator=(DeviceImage &&o) noexcept
+    {
+        if (this != &o) {
+            if (img_) (void)visma_icp_image_destroy(ctx_, img_);
+            ctx_ = o.ctx_; img_ = o.img_; o.img_ = nullptr;
+        }
+        return *this;
+    }
+    DeviceImage(const DeviceImage &) = delete;
+    DeviceImage &operator=(const DeviceImage &) = delete;
+
+    visma_icp_ctx *Context() const { return ctx_; }
+    visma_icp_image *Handle() const { return img_; }
+    // the one copy to the host; the empty Image for an empty DeviceImage
+    std::shared_ptr<Image> Download() const
+    {
+        auto out = std::make_shared<Image>();
+        if (!img_) return out;
+        int w, h, c, b;
+        detail::check(ctx_, visma_icp_image_info(img_, &w, &h, &c, &b), "visma_icp_image_info");
+        out->PrepareImage(w, h, c, b);
+        detail::check(ctx_, visma_icp_image_get(ctx_, img_, out->data_.data(), (int64_t)out->data_.size()), "visma_icp_image_get");
+        return out;
+    }
+    DeviceImage ToFloat(Image::ColorToIntensityConversionType type = Image::ColorToIntensityConversionType::Weighted) const
+    {
+        return make("visma_icp_image_to_float", [&](visma_icp_image **o) {
+            return visma_icp_image_to_float(ctx_, img_, type == Image::ColorToIntensityConversionType::Equal ? VISMA_ICP_IMAGE_EQUAL : VISMA_ICP_IMAGE_WEIGHTED, o); });
+    }
+    DeviceImage DepthToFloat(double depth_scale = 1000.0, double depth_trunc = 3.0) const
+    {
+        return make("visma_icp_image_depth_to_float", [&](visma_icp_image **o) { return visma_icp_image_depth_to_float(ctx_, img_, depth_scale, depth_trunc, o); });
+    }
+    DeviceImage FromFloat(int bytes) const
+    {
+        return make("visma_icp_image_from_float", [&](visma_icp_image **o) { return visma_icp_image_from_float(ctx_, img_, bytes, o); });
+    }
+    DeviceImage Filter(Image::FilterType type) const
+    {
+        return make("visma_icp_image_filter", [&](visma_icp_image **o) { return visma_icp_image_filter(ctx_, img_, (int)type, o); });
+    }
+    DeviceImage Filter(const std::vector<double> &dx, const std::vector<double> &dy) const
+    {
+        return make("visma_icp_image_filter_separable", [&](visma_icp_image **o) {
+            return visma_icp_image_filter_separable(ctx_, img_, dx.data(), (int)dx.size(), dy.data(), (int)dy.size(), o); });
+    }
+    DeviceImage FilterHorizontal(const std::vector<double> &kernel) const
+    {
+        return make("visma_icp_image_filter_horizontal", [&](visma_icp_image **o) {
+            return visma_icp_image_filter_horizontal(ctx_, img_, kernel.data(), (int)kernel.size(), o); });
+    }
+    DeviceImage Flip() const { return make("visma_icp_image_flip", [&](visma_icp_image **o) { return visma_icp_image_flip(ctx_, img_, o); }); }
+    DeviceImage Downsample() const { return make("visma_icp_image_downsample", [&](visma_icp_image **o) { return visma_icp_image_downsample(ctx_, img_, o); }); }
+    DeviceImage Dilate(int half_kernel_size = 1) const
+    {
+        return make("visma_icp_image_dilate", [&](visma_icp_image **o) { return visma_icp_image_dilate(ctx_, img_, half_kernel_size, o); });
+    }
+    DeviceImage Copy() const { return make("visma_icp_image_copy", [&](visma_icp_image **o) { return visma_icp_image_copy(ctx_, img_, o); }); }
+    DeviceImage &LinearTransform(double scale = 1.0, double offset = 0.0)
+    {
+        if (img_) detail::check(ctx_, visma_icp_image_linear_transform(ctx_, img_, scale, offset), "visma_icp_image_linear_transform");
+        return *this;
+    }
+    DeviceImage &ClipIntensity(double min = 0.0, double max = 1.0)
+    {
+        if (img_) detail::check(ctx_, visma_icp_image_clip_intensity(ctx_, img_, min, max), "visma_icp_image_clip_intensity");
+        return *this;
+    }
+    std::vector<DeviceImage> Pyramid(size_t num_of_levels, bool with_gaussian_filter = true) const
+    {
+        std::vector<visma_icp_image *> h(num_of_levels, nullptr);
+        if (img_) detail::check(ctx_, visma_icp_image_pyramid(ctx_, img_, (int)num_of_levels, with_gaussian_filter ? 1 : 0, h.data()), "visma_icp_image_pyramid");
+        std::vector<DeviceImage> out;
+        for (visma_icp_image *i : h)
+            if (i) out.emplace_back(ctx_, i);
+        return out;
+    }
+    // CreateRGBDImageFrom*: -> (color, depth); two empty DeviceImages for images of different sizes
+    static std::pair<DeviceImage, DeviceImage> RGBD(const DeviceImage &color, const DeviceImage &depth, int format, double depth_scale = 1000.0,
+                                                    double depth_trunc = 3.0, bool convert_rgb_to_intensity = true)
+    {
+        visma_icp_image *c = nullptr, *d = nullptr;
+        detail::check(color.ctx_, visma_icp_image_rgbd(color.ctx_, color.img_, depth.img_, format, depth_scale, depth_trunc, convert_rgb_to_intensity ? 1 : 0, &c, &d),
+                      "visma_icp_image_rgbd");
+        return std::pair<DeviceImage, DeviceImage>(DeviceImage(color.ctx_, c), DeviceImage(color.ctx_, d));
+    }
+
+private:
+    template <class F>
+    DeviceImage make(const char *what, F f) const
+    {
+        visma_icp_image *o = nullptr;
+        if (img_) detail::check(ctx_, f(&o), what);
+        return DeviceImage(ctx_, o);
+    }
+    visma_icp_ctx *ctx_;
+    visma_icp_image *img_ = nullptr;
+};
+
+// ComputeRGBDOdometry of four resident 1 x float images (the gray and the depth of the source and of the target)
+inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
+        const DeviceImage &source_color, const DeviceImage &source_depth, const DeviceImage &target_color, const DeviceImage &target_depth,
+        const PinholeCameraIntrinsic &pinhole_camera_intrinsic, const Eigen::Matrix4d &odo_init = Eigen::Matrix4d::Identity(),
+        const RGBDOdometryJacobian &jacobian_method = RGBDOdometryJacobianFromHybridTerm(), const OdometryOption &option = OdometryOption())
+{
+    typedef std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> Out;
+    visma_icp_ctx *ctx = source_color.Context();
+    visma_icp_odometry_option opt;
+    visma_icp_odometry_option_default(&opt);
+    opt.n_levels = (int)option.iteration_number_per_pyramid_level_.size();
+    for (int l = 0; l < opt.n_levels && l < VISMA_ICP_ODOMETRY_MAX_LEVELS; l++) opt.iterations[l] = option.iteration_number_per_pyramid_level_[l];
+    opt.max_depth_diff = option.max_depth_diff_; opt.min_depth = option.min_depth_; opt.max_depth = option.max_depth_;
+    const Eigen::Matrix3d &K = pinhole_camera_intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    const int method = typeid(jacobian_method) == typeid(RGBDOdometryJacobianFromColorTerm) ? VISMA_ICP_ODOMETRY_COLOR : VISMA_ICP_ODOMETRY_HYBRID;
+    double init[16], T[16], info[36];
+    detail::to_rowmajor(odo_init, init);
+    visma_icp_odometry_result res = {};
+    detail::check(ctx, visma_icp_rgbd_odometry_images(ctx, source_color.Handle(), source_depth.Handle(), target_color.Handle(), target_depth.Handle(), k,
+                                                      init, method, &opt, T, info, &res), "visma_icp_rgbd_odometry_images");
+    if (!res.success) return Out(false, Eigen::Matrix4d::Identity(), Eigen::Matrix6d::Zero());
+    Eigen::Matrix4d Tm;
+    Eigen::Matrix6d Im;
+    for (int i = 0; i < 16; i++) Tm(i / 4, i % 4) = T[i];
+    for (int i = 0; i < 36; i++) Im(i / 6, i % 6) = info[i];
+    return Out(true, Tm, Im);
+}
+
+}  // namespace cicp
+
+inline void TSDFVolume::Integrate(const cicp::DeviceImage &depth, const cicp::DeviceImage *color, const PinholeCameraIntrinsic &intrinsic,
+                                  const Eigen::Matrix4d &extrinsic)
+{
+    const Eigen::Matrix3d &K = intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    double E[16];
+    cicp::detail::to_rowmajor(extrinsic, E);
+    const int rc = visma_icp_tsdf_integrate_images(Context(), Handle(), depth.Handle(), color ? color->Handle() : nullptr, k, intrinsic.width_,
+                                                   intrinsic.height_, E);
+    if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string("[TSDFVolume::Integrate] ") + visma_icp_last_error(Context()));
+    cicp::detail::check(Context(), rc, "visma_icp_tsdf_integrate_images");
+}
+
+// the stock names: one upload, the operation, one download, on this thread's context
+inline std::shared_ptr<Image> CreateDepthToCameraDistanceMultiplierFloatImage(const PinholeCameraIntrinsic &intrinsic)
+{
+    visma_icp_ctx *ctx = cicp::detail::ThreadContext::instance().get();
+    const Eigen::Matrix3d &K = intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    visma_icp_image *o = nullptr;
+    cicp::detail::check(ctx, visma_icp_image_distance_multiplier(ctx, k, intrinsic.width_, intrinsic.height_, &o), "visma_icp_image_distance_multiplier");
+    return cicp::DeviceImage(ctx, o).Download();
+}
+template <typename T>
+std::shared_ptr<Image> CreateImageFromFloatImage(const Image &input)
+{
+    static_assert(sizeof(T) == 1 || sizeof(T) == 2, "uint8_t or uint16_t");
+    return cicp::DeviceImage(input).FromFloat((int)sizeof(T)).Download();
+}
+inline std::shared_ptr<Image> FlipImage(const Image &input) { return cicp::DeviceImage(input).Flip().Download(); }
+inline std::shared_ptr<Image> FilterImage(const Image &input, Image::FilterType type) { return cicp::DeviceImage(input).Filter(type).Download(); }
+inline std::shared_ptr<Image> FilterImage(const Image &input, const std::vector<double> &dx, const std::vector<double> &dy)
+{
+    return cicp::DeviceImage(input).Filter(dx, dy).Download();
+}
+inline std::shared_ptr<Image> FilterHorizontalImage(const Image &input, const std::vector<double> &kernel)
+{
+    return cicp::DeviceImage(input).FilterHorizontal(kernel).Download();
+}
+inline std::shared_ptr<Image> DownsampleImage(const Image &input) { return cicp::DeviceImage(input).Downsample().Download(); }
+inline std::shared_ptr<Image> DilateImage(const Image &input, int half_kernel_size) { return cicp::DeviceImage(input).Dilate(half_kernel_size).Download(); }
+inline void LinearTransformImage(Image &input, double scale, double offset) { input = *cicp::DeviceImage(input).LinearTransform(scale, offset).Download(); }
+inline void ClipIntensityImage(Image &input, double min, double max) { input = *cicp::DeviceImage(input).ClipIntensity(min, max).Download(); }
+inline ImagePyramid FilterImagePyramid(const ImagePyramid &input, Image::FilterType type)
+{
+    ImagePyramid out;
+    for (const auto &level : input) out.push_back(FilterImage(*level, type));
+    return out;
+}
+inline ImagePyramid CreateImagePyramid(const Image &image, size_t num_of_levels, bool with_gaussian_filter)
+{
+    ImagePyramid out;
+    for (const cicp::DeviceImage &level : cicp::DeviceImage(image).Pyramid(num_of_levels, with_gaussian_filter)) out.push_back(level.Download());
+    return out;
+}
+namespace cicp {
+namespace detail {
+inline std::shared_ptr<RGBDImage> rgbd_format(const Image &color, const Image &depth, int format, bool convert_rgb_to_intensity)
+{
+    auto out = std::make_shared<RGBDImage>();
+    if (color.height_ != depth.height_ || color.width_ != depth.width_) return out;
+    DeviceImage c(color), d(depth);
+    std::pair<DeviceImage, DeviceImage> p = DeviceImage::RGBD(c, d, format, 0.0, 0.0, convert_rgb_to_intensity);
+    out->color_ = *p.first.Download();
+    out->depth_ = *p.second.Download();
+    return out;
+}
+}  // namespace detail
+}  // namespace cicp
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromRedwoodFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity)
+{
+    return cicp::detail::rgbd_format(color, depth, VISMA_ICP_RGBD_REDWOOD, convert_rgb_to_intensity);
+}
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromTUMFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity)
+{
+    return cicp::detail::rgbd_format(color, depth, VISMA_ICP_RGBD_TUM, convert_rgb_to_intensity);
+}
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromSUNFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity)
+{
+    return cicp::detail::rgbd_format(color, depth, VISMA_ICP_RGBD_SUN, convert_rgb_to_intensity);
+}
+inline std::shared_ptr<RGBDImage> CreateRGBDImageFromNYUFormat(const Image &color, const Image &depth, bool convert_rgb_to_intensity)
+{
+    return cicp::detail::rgbd_format(color, depth, VISMA_ICP_RGBD_NYU, convert_rgb_to_intensity);
+}
+inline RGBDImagePyramid FilterRGBDImagePyramid(const RGBDImagePyramid &rgbd_image_pyramid, Image::FilterType type)
+{
+    RGBDImagePyramid out;
+    for (const auto &level : rgbd_image_pyramid)
+        out.push_back(std::make_shared<RGBDImage>(*FilterImage(level->color_, type), *FilterImage(level->depth_, type)));
+    return out;
+}
+// (like the reference, this needs both images to be 1 x float: an image without levels has none to pair)
+inline RGBDImagePyramid CreateRGBDImagePyramid(const RGBDImage &rgbd_image, size_t num_of_levels, bool with_gaussian_filter_for_color,
+                                               bool with_gaussian_filter_for_depth)
+{
+    const ImagePyramid color = CreateImagePyramid(rgbd_image.color_, num_of_levels, with_gaussian_filter_for_color);
+    const ImagePyramid depth = CreateImagePyramid(rgbd_image.depth_, num_of_levels, with_gaussian_filter_for_depth);
+    RGBDImagePyramid out;
+    for (size_t l = 0; l < num_of_levels && l < color.size() && l < depth.size(); l++) out.push_back(std::make_shared<RGBDImage>(*color[l], *depth[l]));
+    return out;
+}
 #endif
 
 }  // namespace open3d

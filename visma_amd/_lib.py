@@ -155,7 +155,16 @@ class TsdfVolume:
     def integrate(self, depth, color, intrinsic, extrinsic, intrinsic_size=None):
         """Integrate(): depth h x w fp32 (metres), color by the volume's colour type (h x w x 3 uint8 | h x w fp32 | None),
         intrinsic [fx, fy, cx, cy] of an image of intrinsic_size = (w, h) (default: the depth image's), extrinsic 4 x 4
-        world -> camera."""
+        world -> camera.  depth (and color) may be resident Images (Context.image): the pixels are taken device to device
+        (visma_icp_tsdf_integrate_images; intrinsic_size defaults to the depth image's size)."""
+        if isinstance(depth, Image):
+            if color is not None and not isinstance(color, Image):
+                raise ValueError("a resident depth takes a resident colour image")
+            k = _f64(intrinsic, (4,)); E = _f64(extrinsic, (16,))
+            iw, ih = depth.info()[:2] if intrinsic_size is None else intrinsic_size
+            self.ctx._chk(self.ctx.L.visma_icp_tsdf_integrate_images(self.ctx._h, self._v, depth._i, None if color is None else color._i,
+                                                                     _p(k, _dp), int(iw), int(ih), _p(E, _dp)))
+            return
         depth = np.ascontiguousarray(depth, dtype=np.float32)
         if depth.ndim != 2:
             raise ValueError("an h x w depth image")
@@ -442,6 +451,115 @@ class Cloud:
         out = np.empty(max(self.size()[0], 1))
         self._call("mahalanobis_distance", _p(out, _dp))
         return out[:self.size()[0]]
+
+
+IMAGE_EQUAL, IMAGE_WEIGHTED = 0, 1
+IMAGE_FILTERS = ("gaussian3", "gaussian5", "gaussian7", "sobel3dx", "sobel3dy")
+RGBD_FORMATS = ("color_and_depth", "redwood", "tum", "sun", "nyu")
+_IMAGE_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.float32}
+
+
+def _image_enum(value, names):
+    return names.index(value.lower()) if isinstance(value, str) else int(value)
+
+
+class Image:
+    """Open3D's Image resident on the device (visma_icp_image; Context.image, Context.rgbd): h x w pixels of 1 .. 4 channels
+    of uint8, uint16 or float32 stay there between the steps of the RGB-D front end (include/visma_icp.h has the rules and
+    the deviations).  The operations that make a new image return an Image; linear_transform and clip_intensity work in
+    place.  Lives until close() or the context's end; usable as a context manager."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._i = ctx, handle
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def _call(self, name, *args):
+        self.ctx._chk(getattr(self.ctx.L, "visma_icp_image_" + name)(self.ctx._h, self._i, *args))
+
+    def _new(self, name, *args):
+        i = C.c_void_p()
+        self._call(name, *args, C.byref(i))
+        return Image(self.ctx, i)
+
+    def close(self):
+        if self._i is not None and self.ctx._h:
+            self._call("destroy")
+        self._i = None
+
+    def info(self):
+        """-> width, height, channels, bytes per channel ((0, 0, 0, 0): the reference's empty Image)"""
+        v = [C.c_int(0) for _ in range(4)]
+        self.ctx._chk(self.ctx.L.visma_icp_image_info(self._i, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def get(self):
+        """-> h x w (one channel) or h x w x channels, uint8 / uint16 / float32; the empty Image: 0 x 0 uint8"""
+        w, h, ch, bpc = self.info()
+        out = np.empty((h, w) if ch <= 1 else (h, w, ch), _IMAGE_DTYPES.get(bpc, np.uint8))
+        self._call("get", out.ctypes.data_as(C.c_void_p) if out.size else None, out.nbytes)
+        return out
+
+    def copy(self):
+        return self._new("copy")
+
+    def to_float(self, type=IMAGE_WEIGHTED):
+        """CreateFloatImageFromImage; type IMAGE_EQUAL / IMAGE_WEIGHTED or "equal" / "weighted" """
+        return self._new("to_float", _image_enum(type, ("equal", "weighted")))
+
+    def depth_to_float(self, depth_scale=1000.0, depth_trunc=3.0):
+        return self._new("depth_to_float", float(depth_scale), float(depth_trunc))
+
+    def from_float(self, bytes=1):
+        """CreateImageFromFloatImage<uint8_t> (1) / <uint16_t> (2); saturates outside the representable range"""
+        return self._new("from_float", int(bytes))
+
+    def filter(self, type):
+        """FilterImage(type): an index or a name of IMAGE_FILTERS"""
+        return self._new("filter", _image_enum(type, IMAGE_FILTERS))
+
+    def filter_separable(self, dx, dy):
+        dx, dy = _f64(dx, (-1,)), _f64(dy, (-1,))
+        return self._new("filter_separable", _p(dx, _dp), len(dx), _p(dy, _dp), len(dy))
+
+    def filter_horizontal(self, kernel):
+        k = _f64(kernel, (-1,))
+        return self._new("filter_horizontal", _p(k, _dp), len(k))
+
+    def flip(self):
+        """FlipImage: the transpose"""
+        return self._new("flip")
+
+    def downsample(self):
+        return self._new("downsample")
+
+    def dilate(self, half_kernel_size=1):
+        return self._new("dilate", int(half_kernel_size))
+
+    def linear_transform(self, scale, offset=0.0):
+        self._call("linear_transform", float(scale), float(offset))
+
+    def clip_intensity(self, min=0.0, max=1.0):
+        self._call("clip_intensity", float(min), float(max))
+
+    def pyramid(self, levels, with_gaussian_filter=True):
+        """CreateImagePyramid -> a list of Images ([] for an image that is not 1 x float)"""
+        levels = int(levels)
+        out = (C.c_void_p * max(levels, 1))()
+        self._call("pyramid", levels, int(bool(with_gaussian_filter)), out)
+        return [Image(self.ctx, C.c_void_p(out[l])) for l in range(levels) if out[l]]
+
+    def float_value_at(self, uv):
+        """Image::FloatValueAt for n coordinates (n x 2: u, v) -> ok (n bool), value (n f64)"""
+        uv = _f64(uv, (-1, 2))
+        ok, value = np.zeros(max(len(uv), 1), np.uint8), np.zeros(max(len(uv), 1))
+        self._call("float_value_at", _p(uv, _dp), len(uv), _p(ok, C.POINTER(C.c_uint8)), _p(value, _dp))
+        return ok[:len(uv)].astype(bool), value[:len(uv)]
 
 
 class KDTree:
@@ -958,6 +1076,33 @@ def _bind(L):
         L.visma_icp_cloud_crop.argtypes = [_vp, _vp, _dp, _dp, _out]
         L.visma_icp_cloud_voxel_down_sample.argtypes = [_vp, _vp, C.c_double, _out]
         L.visma_icp_cloud_estimate_normals.argtypes = [_vp, _vp, C.c_int, C.c_int, C.c_double]
+    if hasattr(L, "visma_icp_image_create"):             # (A/B runs load older builds through VISMA_ICP_LIB)
+        _vp, _out, _ci, _cd = C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_double
+        L.visma_icp_image_create.argtypes = [_vp, _ci, _ci, _ci, _ci, _vp, _out]
+        L.visma_icp_image_destroy.argtypes = [_vp, _vp]
+        L.visma_icp_image_info.argtypes = [_vp] + [C.POINTER(_ci)] * 4
+        L.visma_icp_image_get.argtypes = [_vp, _vp, _vp, C.c_int64]
+        for name in ("copy", "flip", "downsample"):
+            getattr(L, "visma_icp_image_" + name).argtypes = [_vp, _vp, _out]
+        for name in ("to_float", "from_float", "filter", "dilate"):
+            getattr(L, "visma_icp_image_" + name).argtypes = [_vp, _vp, _ci, _out]
+        L.visma_icp_image_depth_to_float.argtypes = [_vp, _vp, _cd, _cd, _out]
+        L.visma_icp_image_filter_separable.argtypes = [_vp, _vp, _dp, _ci, _dp, _ci, _out]
+        L.visma_icp_image_filter_horizontal.argtypes = [_vp, _vp, _dp, _ci, _out]
+        L.visma_icp_image_linear_transform.argtypes = [_vp, _vp, _cd, _cd]
+        L.visma_icp_image_clip_intensity.argtypes = [_vp, _vp, _cd, _cd]
+        L.visma_icp_image_pyramid.argtypes = [_vp, _vp, _ci, _ci, _out]
+        L.visma_icp_image_filter_pyramid.argtypes = [_vp, _out, _ci, _ci, _out]
+        L.visma_icp_image_distance_multiplier.argtypes = [_vp, _dp, _ci, _ci, _out]
+        L.visma_icp_image_float_value_at.argtypes = [_vp, _vp, _dp, C.c_int64, C.POINTER(C.c_uint8), _dp]
+        L.visma_icp_image_rgbd.argtypes = [_vp, _vp, _vp, _ci, _cd, _cd, _ci, _out, _out]
+        L.visma_icp_tsdf_integrate_images.argtypes = [_vp, _vp, _vp, _vp, _dp, _ci, _ci, _dp]
+        L.visma_icp_odometry_prepare_images.argtypes = [_vp, _vp, _vp, _vp, _vp, _dp, _dp, C.POINTER(COdometryOption)]
+        L.visma_icp_rgbd_odometry_images.argtypes = [_vp, _vp, _vp, _vp, _vp, _dp, _dp, _ci, C.POINTER(COdometryOption), _dp, _dp,
+                                                     C.POINTER(COdometryResult)]
+        L.visma_icp_image_from_odometry.argtypes = [_vp, _ci, _ci, _out]
+        L.visma_icp_cloud_from_depth_image.argtypes = [_vp, _vp, _dp, _dp, _cd, _cd, _ci, _out]
+        L.visma_icp_cloud_from_rgbd_images.argtypes = [_vp, _vp, _vp, _dp, _dp, _out]
     if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
         _opt = C.POINTER(CColorMapOption)
@@ -1730,32 +1875,48 @@ class Context:
 
     # ---- RGB-D odometry (visma_icp.h) ----
     def _odometry_frames(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init):
+        frames = (src_gray, src_depth, tgt_gray, tgt_depth)
+        if any(isinstance(a, Image) for a in frames):        # resident Images: the *_images entry points
+            if not all(isinstance(a, Image) for a in frames):
+                raise ValueError("four Images, or four arrays")
+            w, h = frames[0].info()[:2]
+            k = _f64(intrinsic, (4,)); init = _f64(np.eye(4) if init is None else init, (16,))
+            return None, (h, w), k, init, [self._h] + [a._i for a in frames] + [_p(k, _dp), _p(init, _dp)]
         imgs = [np.ascontiguousarray(a, dtype=np.float32) for a in (src_gray, src_depth, tgt_gray, tgt_depth)]
         if imgs[0].ndim != 2 or any(a.shape != imgs[0].shape for a in imgs):
             raise ValueError("four h x w images of one size")
         h, w = imgs[0].shape
         k = _f64(intrinsic, (4,)); init = _f64(np.eye(4) if init is None else init, (16,))
-        return imgs, k, init, [self._h, w, h] + [_p(a, _fp) for a in imgs] + [_p(k, _dp), _p(init, _dp)]
+        return imgs, (h, w), k, init, [self._h, w, h] + [_p(a, _fp) for a in imgs] + [_p(k, _dp), _p(init, _dp)]
 
     def rgbd_odometry(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init=None, method=ODOMETRY_HYBRID, option=None):
         """Open3D's ComputeRGBDOdometry between two frames (h x w fp32 gray and depth in metres; intrinsic [fx, fy, cx, cy])
         -> OdometryResult; unpacks as (success, T, information).  Without success: T = I, information = 0, no exception."""
         option = odometry_option() if option is None else option
-        keep, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
+        keep, shape, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
+        call = self.L.visma_icp_rgbd_odometry if keep is not None else self.L.visma_icp_rgbd_odometry_images
         T = np.empty(16); info = np.empty(36)
         cap = max(1, sum(max(0, option.iterations[i]) for i in range(max(0, min(option.n_levels, 8)))))
         pairs = np.zeros(cap, np.int64)
         res = COdometryResult(); res.pairs = _p(pairs, C.POINTER(C.c_int64)); res.pairs_capacity = cap
-        self._chk(self.L.visma_icp_rgbd_odometry(*args, int(method), C.byref(option), _p(T, _dp), _p(info, _dp), C.byref(res)))
-        self._odo_shape = (keep[0].shape, option.n_levels)   # (the call prepared: its pyramids are the resident ones)
+        self._chk(call(*args, int(method), C.byref(option), _p(T, _dp), _p(info, _dp), C.byref(res)))
+        self._odo_shape = (shape, option.n_levels)   # (the call prepared: its pyramids are the resident ones)
         return OdometryResult(res.success, T.reshape(4, 4), info.reshape(6, 6), res.information_pairs, pairs[:res.iterations].copy())
 
     def odometry_prepare(self, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init=None, option=None):
         """Both processed pyramids of a frame pair, resident until the next prepare (what the calls below read)."""
         option = odometry_option() if option is None else option
-        keep, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
-        self._chk(self.L.visma_icp_odometry_prepare(*args, C.byref(option)))
-        self._odo_shape = (keep[0].shape, option.n_levels)
+        keep, shape, k, init, args = self._odometry_frames(src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init)
+        call = self.L.visma_icp_odometry_prepare if keep is not None else self.L.visma_icp_odometry_prepare_images
+        self._chk(call(*args, C.byref(option)))
+        self._odo_shape = (shape, option.n_levels)
+
+    def image_from_odometry(self, which, level=0):
+        """A level of a resident pyramid as an Image, copied device to device (not src_xyz)."""
+        which = ODOMETRY_IMAGES.index(which) if isinstance(which, str) else int(which)
+        i = C.c_void_p()
+        self._chk(self.L.visma_icp_image_from_odometry(self._h, which, int(level), C.byref(i)))
+        return Image(self, i)
 
     def _odometry_level_shape(self, level):
         (h, w), n = getattr(self, "_odo_shape", ((0, 0), 0))
@@ -1825,6 +1986,58 @@ class Context:
         dp = lambda a: None if a is None else _p(a, _dp)
         c = C.c_void_p()
         self._chk(self.L.visma_icp_cloud_create(self._h, _p(p, _dp), len(p), dp(nrm), dp(col), C.byref(c)))
+        return Cloud(self, c)
+
+    # ---- Image (visma_icp.h) ----
+    def image(self, array):
+        """Open3D's Image on the device -> Image.  array h x w or h x w x channels of uint8, uint16 or float32."""
+        a = np.ascontiguousarray(array)
+        if a.dtype not in (np.uint8, np.uint16, np.float32) or a.ndim not in (2, 3):
+            raise ValueError("an h x w (x channels) array of uint8, uint16 or float32")
+        h, w = a.shape[:2]
+        i = C.c_void_p()
+        self._chk(self.L.visma_icp_image_create(self._h, w, h, 1 if a.ndim == 2 else a.shape[2], a.dtype.itemsize,
+                                                a.ctypes.data_as(C.c_void_p) if a.size else None, C.byref(i)))
+        return Image(self, i)
+
+    def distance_multiplier(self, intrinsic, w, h):
+        """CreateDepthToCameraDistanceMultiplierFloatImage for [fx, fy, cx, cy] and w x h -> Image"""
+        k = _f64(intrinsic, (4,))
+        i = C.c_void_p()
+        self._chk(self.L.visma_icp_image_distance_multiplier(self._h, _p(k, _dp), int(w), int(h), C.byref(i)))
+        return Image(self, i)
+
+    def filter_pyramid(self, pyramid, type):
+        """FilterImagePyramid -> a list of Images"""
+        n = len(pyramid)
+        src = (C.c_void_p * max(n, 1))(*[p._i.value for p in pyramid])
+        out = (C.c_void_p * max(n, 1))()
+        self._chk(self.L.visma_icp_image_filter_pyramid(self._h, src, n, _image_enum(type, IMAGE_FILTERS), out))
+        return [Image(self, C.c_void_p(out[l])) for l in range(n)]
+
+    def rgbd(self, color, depth, format="color_and_depth", depth_scale=1000.0, depth_trunc=3.0, convert_rgb_to_intensity=True):
+        """CreateRGBDImageFromColorAndDepth / Redwood / TUM / SUN / NYU format (an index or a name of RGBD_FORMATS) of two
+        Images -> (color, depth) Images, or (None, None) for images of different sizes (the reference's empty RGBDImage)."""
+        c, d = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.visma_icp_image_rgbd(self._h, color._i, depth._i, _image_enum(format, RGBD_FORMATS), float(depth_scale),
+                                              float(depth_trunc), int(bool(convert_rgb_to_intensity)), C.byref(c), C.byref(d)))
+        return (Image(self, c), Image(self, d)) if c.value and d.value else (None, None)
+
+    def cloud_from_depth_image(self, depth, intrinsic, extrinsic=None, depth_scale=1000.0, depth_trunc=1000.0, stride=1):
+        """CreatePointCloudFromDepthImage of a resident Image (1 x float32, or 1 x uint16 through depth_scale / depth_trunc) ->
+        a resident Cloud: the rows of point_cloud_from_depth.  Any other format: an empty Cloud."""
+        k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+        c = C.c_void_p()
+        self._chk(self.L.visma_icp_cloud_from_depth_image(self._h, depth._i, _p(k, _dp), _p(E, _dp), float(depth_scale), float(depth_trunc),
+                                                          int(stride), C.byref(c)))
+        return Cloud(self, c)
+
+    def cloud_from_rgbd_images(self, depth, color, intrinsic, extrinsic=None):
+        """CreatePointCloudFromRGBDImage of resident Images (depth 1 x float32; color 3 x uint8 or 1 x float32) -> a resident
+        Cloud with colours: the rows of point_cloud_from_rgbd.  Any other format: an empty Cloud."""
+        k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+        c = C.c_void_p()
+        self._chk(self.L.visma_icp_cloud_from_rgbd_images(self._h, depth._i, color._i, _p(k, _dp), _p(E, _dp), C.byref(c)))
         return Cloud(self, c)
 
     # ---- TSDF integration (visma_icp.h) ----

@@ -599,6 +599,314 @@ int visma_icp_cloud_mahalanobis_distance(visma_icp_ctx *ctx, visma_icp_cloud *cl
     return cloud_done(ctx, "cloud_mahalanobis_distance", cloud_device_mahalanobis(cloud->dev, mean, inv, out, ctx->eng->aux_stream()));
 }
 
+// ---- Image: an image resident on the device (image.hip) ----
+static int image_enter(visma_icp_ctx *ctx, const visma_icp_image *img)
+{
+    if (img && !ctx->owns(img)) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image lives on one rank");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "an image needs the HIP engine");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    return VISMA_ICP_OK;
+}
+
+static int image_done(visma_icp_ctx *ctx, const char *what, hipError_t e)
+{
+    if (e == hipSuccess) return VISMA_ICP_OK;
+    (void)hipGetLastError();
+    return ctx->fail(VISMA_ICP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+static int image_adopt(visma_icp_ctx *ctx, const char *what, hipError_t e, ImageDevice *dev, visma_icp_image **out)
+{
+    if (e != hipSuccess) return image_done(ctx, what, e);
+    *out = ctx->adopt(dev);
+    return VISMA_ICP_OK;
+}
+
+#define IMAGE_CHECK(img)                                                                     \
+    CTX_CHECK();                                                                             \
+    if (!(img)) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");                      \
+    if (int rc_ = image_enter(ctx, (img))) return rc_;
+
+// an operation that makes a new image: the checks before it
+#define IMAGE_NEW_CHECK(img)                                                                 \
+    CTX_CHECK();                                                                             \
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");                       \
+    *out = nullptr;                                                                          \
+    if (!(img)) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");                      \
+    if (int rc_ = image_enter(ctx, (img))) return rc_;
+
+static bool image_is_float(const visma_icp_image *img)
+{
+    int w, h, ch, bpc;
+    image_device_info(img->dev, &w, &h, &ch, &bpc);
+    return ch == 1 && bpc == 4;
+}
+
+int visma_icp_image_create(visma_icp_ctx *ctx, int w, int h, int channels, int bytes_per_channel, const void *data, visma_icp_image **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (w < 0 || h < 0 || (int64_t)w * h > (int64_t)1 << 30) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_create: 0 <= w, h and at most 2^30 pixels");
+    if (channels < 1 || channels > 4) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_create: 1 .. 4 channels");
+    if (bytes_per_channel != 1 && bytes_per_channel != 2 && bytes_per_channel != 4)
+        return ctx->fail(VISMA_ICP_ERR_INVALID, "image_create: 1, 2 or 4 bytes per channel");
+    if ((int64_t)w * h > 0 && !data) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_create: NULL argument");
+    if (int rc = image_enter(ctx, nullptr)) return rc;
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_create(w, h, channels, bytes_per_channel, data, false, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_create", e, dev, out);
+}
+
+int visma_icp_image_destroy(visma_icp_ctx *ctx, visma_icp_image *img)
+{
+    CTX_CHECK();
+    if (!img) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    for (size_t i = 0; i < ctx->images.size(); i++)
+        if (ctx->images[i].get() == img) { ctx->images.erase(ctx->images.begin() + (std::ptrdiff_t)i); return VISMA_ICP_OK; }
+    return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
+}
+
+int visma_icp_image_info(const visma_icp_image *img, int *w, int *h, int *channels, int *bytes_per_channel)
+{
+    if (!img || !img->dev) { g_create_error = "image is NULL"; return VISMA_ICP_ERR_INVALID; }
+    int v[4];
+    image_device_info(img->dev, &v[0], &v[1], &v[2], &v[3]);
+    if (w) *w = v[0];
+    if (h) *h = v[1];
+    if (channels) *channels = v[2];
+    if (bytes_per_channel) *bytes_per_channel = v[3];
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_image_get(visma_icp_ctx *ctx, visma_icp_image *img, void *bytes, int64_t n_bytes)
+{
+    IMAGE_CHECK(img);
+    int w, h, ch, bpc;
+    image_device_info(img->dev, &w, &h, &ch, &bpc);
+    const int64_t have = (int64_t)w * h * ch * bpc;
+    if (n_bytes != have) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_get: n_bytes differs from the image's size");
+    if (have > 0 && !bytes) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_get: NULL argument");
+    return image_done(ctx, "image_get", image_device_get(img->dev, bytes, ctx->eng->aux_stream()));
+}
+
+int visma_icp_image_copy(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_copy", image_device_copy(img->dev, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_image_to_float(visma_icp_ctx *ctx, visma_icp_image *img, int type, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    if (type != VISMA_ICP_IMAGE_EQUAL && type != VISMA_ICP_IMAGE_WEIGHTED) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_to_float: unknown conversion type");
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_to_float(img->dev, type == VISMA_ICP_IMAGE_WEIGHTED, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_to_float", e, dev, out);
+}
+
+int visma_icp_image_depth_to_float(visma_icp_ctx *ctx, visma_icp_image *img, double depth_scale, double depth_trunc, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_depth_to_float(img->dev, depth_scale, depth_trunc, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_depth_to_float", e, dev, out);
+}
+
+int visma_icp_image_from_float(visma_icp_ctx *ctx, visma_icp_image *img, int bytes, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    if (bytes != 1 && bytes != 2) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_from_float: 1 or 2 bytes");
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_from_float", image_device_from_float(img->dev, bytes, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+// Image.cpp:32-37
+static bool image_filter_kernels(int type, const double **dx, const double **dy, int *n)
+{
+    static const double g3[3] = {0.25, 0.5, 0.25}, g5[5] = {0.0625, 0.25, 0.375, 0.25, 0.0625};
+    static const double g7[7] = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125};
+    static const double s31[3] = {-1.0, 0.0, 1.0}, s32[3] = {1.0, 2.0, 1.0};
+    switch (type) {
+    case VISMA_ICP_IMAGE_GAUSSIAN3: *dx = g3; *dy = g3; *n = 3; return true;
+    case VISMA_ICP_IMAGE_GAUSSIAN5: *dx = g5; *dy = g5; *n = 5; return true;
+    case VISMA_ICP_IMAGE_GAUSSIAN7: *dx = g7; *dy = g7; *n = 7; return true;
+    case VISMA_ICP_IMAGE_SOBEL3DX: *dx = s31; *dy = s32; *n = 3; return true;
+    case VISMA_ICP_IMAGE_SOBEL3DY: *dx = s32; *dy = s31; *n = 3; return true;
+    default: return false;
+    }
+}
+
+int visma_icp_image_filter(visma_icp_ctx *ctx, visma_icp_image *img, int type, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    const double *dx = nullptr, *dy = nullptr;
+    int n = 0;
+    if (!image_filter_kernels(type, &dx, &dy, &n)) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_filter: unknown filter type");
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_filter_separable(img->dev, ctx->image_scratch(), dx, n, dy, n, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_filter", e, dev, out);
+}
+
+int visma_icp_image_filter_separable(visma_icp_ctx *ctx, visma_icp_image *img, const double *dx, int n_dx, const double *dy, int n_dy,
+                                     visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    if (n_dx < 0 || n_dy < 0 || (n_dx > 0 && !dx) || (n_dy > 0 && !dy)) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_filter_separable: bad kernel arguments");
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_filter_separable(img->dev, ctx->image_scratch(), dx, n_dx, dy, n_dy, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_filter_separable", e, dev, out);
+}
+
+int visma_icp_image_filter_horizontal(visma_icp_ctx *ctx, visma_icp_image *img, const double *kernel, int n, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    if (n < 0 || (n > 0 && !kernel)) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_filter_horizontal: bad kernel arguments");
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_filter_horizontal(img->dev, ctx->image_scratch(), kernel, n, ctx->eng->aux_stream(), &dev);
+    return image_adopt(ctx, "image_filter_horizontal", e, dev, out);
+}
+
+int visma_icp_image_flip(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_flip", image_device_flip(img->dev, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_image_downsample(visma_icp_ctx *ctx, visma_icp_image *img, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_downsample", image_device_downsample(img->dev, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_image_dilate(visma_icp_ctx *ctx, visma_icp_image *img, int half_kernel_size, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(img);
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_dilate", image_device_dilate(img->dev, ctx->image_scratch(), half_kernel_size, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_image_linear_transform(visma_icp_ctx *ctx, visma_icp_image *img, double scale, double offset)
+{
+    IMAGE_CHECK(img);
+    return image_done(ctx, "image_linear_transform", image_device_linear_transform(img->dev, scale, offset, ctx->eng->aux_stream()));
+}
+
+int visma_icp_image_clip_intensity(visma_icp_ctx *ctx, visma_icp_image *img, double min, double max)
+{
+    IMAGE_CHECK(img);
+    return image_done(ctx, "image_clip_intensity", image_device_clip_intensity(img->dev, min, max, ctx->eng->aux_stream()));
+}
+
+// the levels made so far are destroyed where a later one fails
+static int image_drop_levels(visma_icp_ctx *ctx, visma_icp_image **out, int levels, int rc)
+{
+    for (int l = 0; l < levels; l++)
+        if (out[l]) { visma_icp_image_destroy(ctx, out[l]); out[l] = nullptr; }
+    return rc;
+}
+
+// ImageFactory.cpp:150-182
+int visma_icp_image_pyramid(visma_icp_ctx *ctx, visma_icp_image *img, int levels, int with_gaussian_filter, visma_icp_image **out)
+{
+    CTX_CHECK();
+    if (levels < 0 || (levels > 0 && !out)) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_pyramid: bad arguments");
+    for (int l = 0; l < levels; l++) out[l] = nullptr;
+    if (!img) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");
+    if (int rc = image_enter(ctx, img)) return rc;
+    if (!image_is_float(img)) return VISMA_ICP_OK;           // no levels
+    for (int l = 0; l < levels; l++) {
+        int rc;
+        if (l == 0) {
+            rc = visma_icp_image_copy(ctx, img, &out[0]);
+        } else if (with_gaussian_filter) {
+            visma_icp_image *blurred = nullptr;
+            rc = visma_icp_image_filter(ctx, out[l - 1], VISMA_ICP_IMAGE_GAUSSIAN3, &blurred);
+            if (!rc) {
+                rc = visma_icp_image_downsample(ctx, blurred, &out[l]);
+                const std::string err = ctx->err;
+                visma_icp_image_destroy(ctx, blurred);
+                if (rc) ctx->err = err;
+            }
+        } else {
+            rc = visma_icp_image_downsample(ctx, out[l - 1], &out[l]);
+        }
+        if (rc) return image_drop_levels(ctx, out, levels, rc);
+    }
+    return VISMA_ICP_OK;
+}
+
+// Image.cpp:259-268
+int visma_icp_image_filter_pyramid(visma_icp_ctx *ctx, visma_icp_image *const *in, int levels, int type, visma_icp_image **out)
+{
+    CTX_CHECK();
+    if (levels < 0 || (levels > 0 && (!in || !out))) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_filter_pyramid: bad arguments");
+    for (int l = 0; l < levels; l++) out[l] = nullptr;
+    for (int l = 0; l < levels; l++)
+        if (int rc = visma_icp_image_filter(ctx, in[l], type, &out[l])) return image_drop_levels(ctx, out, levels, rc);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_image_distance_multiplier(visma_icp_ctx *ctx, const double intrinsic[4], int w, int h, visma_icp_image **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!intrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (w < 0 || h < 0 || (int64_t)w * h > (int64_t)1 << 30) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_distance_multiplier: 0 <= w, h and at most 2^30 pixels");
+    if (int rc = image_enter(ctx, nullptr)) return rc;
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "image_distance_multiplier", image_device_distance_multiplier(w, h, intrinsic, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_image_float_value_at(visma_icp_ctx *ctx, visma_icp_image *img, const double *uv, int64_t n, uint8_t *ok, double *value)
+{
+    IMAGE_CHECK(img);
+    if (n < 0 || n > 0x7fffffff || (n > 0 && (!uv || !ok || !value))) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_float_value_at: bad arguments");
+    return image_done(ctx, "image_float_value_at", image_device_float_value_at(img->dev, uv, n, ok, value, ctx->eng->aux_stream()));
+}
+
+// RGBDImageFactory.cpp
+int visma_icp_image_rgbd(visma_icp_ctx *ctx, visma_icp_image *color, visma_icp_image *depth, int format, double depth_scale, double depth_trunc,
+                         int convert_rgb_to_intensity, visma_icp_image **out_color, visma_icp_image **out_depth)
+{
+    CTX_CHECK();
+    if (!out_color || !out_depth) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out_color = *out_depth = nullptr;
+    if (!color || !depth) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");
+    if (format < VISMA_ICP_RGBD_COLOR_AND_DEPTH || format > VISMA_ICP_RGBD_NYU) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_rgbd: unknown format");
+    if (int rc = image_enter(ctx, color)) return rc;
+    if (int rc = image_enter(ctx, depth)) return rc;
+    int cw, chh, cch, cb, dw, dh, dch, db;
+    image_device_info(color->dev, &cw, &chh, &cch, &cb);
+    image_device_info(depth->dev, &dw, &dh, &dch, &db);
+    if (cw != dw || chh != dh) return VISMA_ICP_OK;          // the reference's empty RGBDImage
+    const bool decode = format == VISMA_ICP_RGBD_SUN || format == VISMA_ICP_RGBD_NYU;
+    if (decode && (dch != 1 || db != 2)) return ctx->fail(VISMA_ICP_ERR_INVALID, "image_rgbd: a SUN or NYU depth is a 1 x uint16 image");
+    switch (format) {
+    case VISMA_ICP_RGBD_REDWOOD: depth_scale = 1000.0; depth_trunc = 4.0; break;
+    case VISMA_ICP_RGBD_TUM: depth_scale = 5000.0; depth_trunc = 4.0; break;
+    case VISMA_ICP_RGBD_SUN: case VISMA_ICP_RGBD_NYU: depth_scale = 1000.0; depth_trunc = 7.0; break;
+    default: break;
+    }
+    hipStream_t s = ctx->eng->aux_stream();
+    ImageDevice *decoded = nullptr, *d = nullptr, *c = nullptr;
+    hipError_t e = hipSuccess;
+    if (decode) e = image_device_decode_depth(depth->dev, format == VISMA_ICP_RGBD_NYU, s, &decoded);
+    if (e == hipSuccess) e = image_device_depth_to_float(decoded ? decoded : depth->dev, depth_scale, depth_trunc, s, &d);
+    image_device_destroy(decoded);
+    if (e == hipSuccess) e = convert_rgb_to_intensity ? image_device_to_float(color->dev, 1, s, &c) : image_device_copy(color->dev, s, &c);
+    if (e != hipSuccess) { image_device_destroy(d); image_device_destroy(c); return image_done(ctx, "image_rgbd", e); }
+    *out_depth = ctx->adopt(d);
+    *out_color = ctx->adopt(c);
+    return VISMA_ICP_OK;
+}
+
 // ---- FPFH, feature matching, fast global registration ----
 
 int visma_icp_compute_fpfh_probe(visma_icp_ctx *ctx, const double *xyz, int64_t n, const double *normals, int search_type,

@@ -1672,12 +1672,11 @@ int visma_icp_odometry_information(visma_icp_ctx *ctx, const double T[16], doubl
 
 // ComputeRGBDOdometry: prepare, ComputeMultiscale (per iteration the correspondence kernel and the reduction on the
 // stream, the 6 x 6 solve here), CreateInformationMatrix
-int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
-                            const float *tgt_depth, const double intrinsic[4], const double init[16], int method,
-                            const visma_icp_odometry_option *option, double out_T[16], double out_info[36],
-                            visma_icp_odometry_result *out_result)
+static int rgbd_odometry_frames(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
+                                const float *tgt_depth, bool on_device, const double intrinsic[4], const double init[16], int method,
+                                const visma_icp_odometry_option *option, double out_T[16], double out_info[36],
+                                visma_icp_odometry_result *out_result)
 {
-    CTX_CHECK();
     if (!out_T) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
     if (method != VISMA_ICP_ODOMETRY_COLOR && method != VISMA_ICP_ODOMETRY_HYBRID) return ctx->fail(VISMA_ICP_ERR_INVALID, "unknown odometry method");
     if (out_result && (out_result->pairs_capacity < 0 || (out_result->pairs_capacity > 0 && !out_result->pairs)))
@@ -1685,6 +1684,7 @@ int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_g
     visma_icp_odometry_option opt;
     Engine::OdometryInput in;
     if (int rc = check_odometry_frames(ctx, w, h, src_gray, src_depth, tgt_gray, tgt_depth, intrinsic, init, option, &opt, &in)) return rc;
+    in.on_device = on_device;
     int64_t schedule = 0;
     for (int l = 0; l < opt.n_levels; l++) schedule += opt.iterations[l];
     if (out_result && out_result->pairs_capacity > 0 && out_result->pairs_capacity < schedule)
@@ -1714,6 +1714,80 @@ int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_g
         if (out_info) std::memcpy(out_info, info, sizeof(info));
     }
     if (out_result) { out_result->success = ok ? 1 : 0; out_result->iterations = steps; out_result->information_pairs = K; }
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_rgbd_odometry(visma_icp_ctx *ctx, int w, int h, const float *src_gray, const float *src_depth, const float *tgt_gray,
+                            const float *tgt_depth, const double intrinsic[4], const double init[16], int method,
+                            const visma_icp_odometry_option *option, double out_T[16], double out_info[36],
+                            visma_icp_odometry_result *out_result)
+{
+    CTX_CHECK();
+    return rgbd_odometry_frames(ctx, w, h, src_gray, src_depth, tgt_gray, tgt_depth, false, intrinsic, init, method, option, out_T,
+                                out_info, out_result);
+}
+
+// ---- the hand-offs of resident Images (image.hip): the same device cores, the pixels taken device to device ----------------
+// the four frames of an odometry call: images of this context, 1 x float, of one size; -> their pixels
+static int odometry_images(visma_icp_ctx *ctx, visma_icp_image *const img[4], const float *px[4], int *w, int *h)
+{
+    for (int k = 0; k < 4; k++) {
+        if (!img[k]) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL image");
+        if (!ctx->owns(img[k])) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
+        int iw, ih, ch, bpc;
+        image_device_info(img[k]->dev, &iw, &ih, &ch, &bpc);
+        if (ch != 1 || bpc != 4) return ctx->fail(VISMA_ICP_ERR_INVALID, "an odometry frame is a 1 x float image");
+        if (k == 0) { *w = iw; *h = ih; }
+        else if (iw != *w || ih != *h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the four images differ in size");
+        px[k] = static_cast<const float *>(image_device_pixels(img[k]->dev));
+    }
+    if (*w < 1 || *h < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "an image needs w >= 1 and h >= 1");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_odometry_prepare_images(visma_icp_ctx *ctx, visma_icp_image *src_gray, visma_icp_image *src_depth, visma_icp_image *tgt_gray,
+                                      visma_icp_image *tgt_depth, const double intrinsic[4], const double init[16],
+                                      const visma_icp_odometry_option *option)
+{
+    CTX_CHECK();
+    visma_icp_image *const img[4] = {src_gray, src_depth, tgt_gray, tgt_depth};
+    const float *px[4];
+    int w = 0, h = 0;
+    if (int rc = odometry_images(ctx, img, px, &w, &h)) return rc;
+    visma_icp_odometry_option opt;
+    Engine::OdometryInput in;
+    if (int rc = check_odometry_frames(ctx, w, h, px[0], px[1], px[2], px[3], intrinsic, init, option, &opt, &in)) return rc;
+    in.on_device = true;
+    return odometry_prepare_checked(ctx, in);
+}
+
+int visma_icp_rgbd_odometry_images(visma_icp_ctx *ctx, visma_icp_image *src_gray, visma_icp_image *src_depth, visma_icp_image *tgt_gray,
+                                   visma_icp_image *tgt_depth, const double intrinsic[4], const double init[16], int method,
+                                   const visma_icp_odometry_option *option, double out_T[16], double out_info[36],
+                                   visma_icp_odometry_result *out_result)
+{
+    CTX_CHECK();
+    visma_icp_image *const img[4] = {src_gray, src_depth, tgt_gray, tgt_depth};
+    const float *px[4];
+    int w = 0, h = 0;
+    if (int rc = odometry_images(ctx, img, px, &w, &h)) return rc;
+    return rgbd_odometry_frames(ctx, w, h, px[0], px[1], px[2], px[3], true, intrinsic, init, method, option, out_T, out_info, out_result);
+}
+
+int visma_icp_image_from_odometry(visma_icp_ctx *ctx, int which, int level, visma_icp_image **out)
+{
+    CTX_CHECK();
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (which < 0 || which >= kOdoSrcXyz) return ctx->fail(VISMA_ICP_ERR_INVALID, "which out of range (the xyz image has three floats per pixel: not an Image)");
+    if (int rc = check_odometry_level(ctx, level)) return rc;
+    const float *px = nullptr;
+    int w = 0, h = 0;
+    if (int rc = ctx->eng->odometry_image_view(which, level, &px, &w, &h)) return ctx->eng_fail(rc);
+    ImageDevice *dev = nullptr;
+    const hipError_t e = image_device_create(w, h, 1, 4, px, true, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(VISMA_ICP_ERR_HIP, std::string("image_from_odometry: ") + hipGetErrorString(e)); }
+    *out = ctx->adopt(dev);
     return VISMA_ICP_OK;
 }
 
@@ -1855,6 +1929,40 @@ int visma_icp_tsdf_integrate(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int w, 
     return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
 }
 
+// Integrate of resident images: the depth 1 x float, the colour what the volume's colour type takes (RGB8: 3 x uint8,
+// Gray32: 1 x float; a volume without colour reads none).  Anything else: INVALID before the volume is touched.
+int visma_icp_tsdf_integrate_images(visma_icp_ctx *ctx, visma_icp_tsdf *volume, visma_icp_image *depth, visma_icp_image *color,
+                                    const double intrinsic[4], int intrinsic_w, int intrinsic_h, const double extrinsic[16])
+{
+    CTX_CHECK();
+    if (int rc = check_tsdf_volume(ctx, volume)) return rc;
+    if (!extrinsic || !depth) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (!ctx->owns(depth) || (color && !ctx->owns(color))) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
+    int w, h, ch, bpc;
+    image_device_info(depth->dev, &w, &h, &ch, &bpc);
+    if (ch != 1 || bpc != 4) return ctx->fail(VISMA_ICP_ERR_INVALID, "the depth is a 1 x float image");
+    const int ct = volume->cfg.color_type;
+    const void *color_px = nullptr;
+    if (ct != kTsdfColorNone) {
+        if (!color) return ctx->fail(VISMA_ICP_ERR_INVALID, "no colour image for a coloured volume");
+        int cw, chh, cch, cb;
+        image_device_info(color->dev, &cw, &chh, &cch, &cb);
+        if (cw != w || chh != h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the colour image differs in size from the depth");
+        if (ct == kTsdfColorRgb8 ? (cch != 3 || cb != 1) : (cch != 1 || cb != 4))
+            return ctx->fail(VISMA_ICP_ERR_INVALID, "the colour image is not of the volume's colour type");
+        color_px = image_device_pixels(color->dev);
+    }
+    TsdfFrame f;
+    if (int rc = check_tsdf_frame(ctx, w, h, static_cast<const float *>(image_device_pixels(depth->dev)), color_px, ct, intrinsic,
+                                  intrinsic_w, intrinsic_h, extrinsic, &f))
+        return rc;
+    f.on_device = true;
+    volume->rows[0] = volume->rows[1] = -1;
+    volume->mesh_rows[0] = volume->mesh_rows[1] = -1;
+    int rc = ctx->eng->tsdf_integrate(volume->id, f);
+    return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
 static int tsdf_extract(visma_icp_ctx *ctx, visma_icp_tsdf *volume, int voxel_cloud, int64_t *out_n)
 {
     if (int rc = check_tsdf_volume(ctx, volume)) return rc;
@@ -1950,8 +2058,82 @@ static int point_cloud_from_frame(visma_icp_ctx *ctx, int w, int h, const float 
     if (int rc = check_tsdf_frame(ctx, w, h, depth, color, color_type, intrinsic, w, h, extrinsic, &f)) return rc;
     const int64_t most = (((int64_t)w - 1) / stride + 1) * (((int64_t)h - 1) / stride + 1);   // (in 64 bits: stride may be INT_MAX)
     if (points && capacity < most) return ctx->fail(VISMA_ICP_ERR_INVALID, "capacity below ceil(w / stride) * ceil(h / stride)");
-    int rc = ctx->eng->point_cloud_from_depth(f, color_type, stride, points, points ? colors : nullptr, out_n);
+    int rc = ctx->eng->point_cloud_from_depth(f, color_type, stride, points, points ? colors : nullptr, out_n, nullptr);
     return rc ? ctx->eng_fail(rc) : VISMA_ICP_OK;
+}
+
+// CreatePointCloudFromDepthImage / FromRGBDImage of resident images into a resident cloud.  depth: the float pixels on the
+// device; color (may be NULL) with its colour type
+static int cloud_from_images(visma_icp_ctx *ctx, int w, int h, const float *depth, const void *color, int color_type, const double *intrinsic,
+                             const double *extrinsic, int stride, visma_icp_cloud **out)
+{
+    TsdfFrame f;
+    if (int rc = check_tsdf_frame(ctx, w, h, depth, color, color_type, intrinsic, w, h, extrinsic, &f)) return rc;
+    f.on_device = true;
+    int64_t n = 0;
+    CloudDevice *dev = nullptr;
+    if (int rc = ctx->eng->point_cloud_from_depth(f, color_type, stride, nullptr, nullptr, &n, &dev)) return ctx->eng_fail(rc);
+    *out = ctx->adopt(dev);
+    return VISMA_ICP_OK;
+}
+
+static int empty_cloud(visma_icp_ctx *ctx, visma_icp_cloud **out)
+{
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    CloudDevice *dev = nullptr;
+    const hipError_t e = cloud_device_create(nullptr, 0, nullptr, nullptr, false, ctx->eng->aux_stream(), &dev);
+    if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(VISMA_ICP_ERR_HIP, hipGetErrorString(e)); }
+    *out = ctx->adopt(dev);
+    return VISMA_ICP_OK;
+}
+
+static int cloud_from_images_enter(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image *color, const double *intrinsic, visma_icp_cloud **out)
+{
+    if (!out) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL output");
+    *out = nullptr;
+    if (!depth || !intrinsic) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    if (!ctx->owns(depth) || (color && !ctx->owns(color))) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
+    if (ctx->sharded() || ctx->eng->is_sharded()) return ctx->fail(VISMA_ICP_ERR_INVALID, "a point cloud lives on one rank");
+    if (!ctx->eng->supports_device_loop()) return ctx->fail(VISMA_ICP_ERR_STATE, "a point cloud needs the HIP engine");
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_cloud_from_depth_image(visma_icp_ctx *ctx, visma_icp_image *depth, const double intrinsic[4], const double extrinsic[16],
+                                     double depth_scale, double depth_trunc, int stride, visma_icp_cloud **out)
+{
+    CTX_CHECK();
+    if (int rc = cloud_from_images_enter(ctx, depth, nullptr, intrinsic, out)) return rc;
+    if (stride < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "stride < 1");
+    int w, h, ch, bpc;
+    image_device_info(depth->dev, &w, &h, &ch, &bpc);
+    if (ch != 1 || (bpc != 2 && bpc != 4) || w < 1 || h < 1) return empty_cloud(ctx, out);      // unsupported format: the empty cloud
+    if (bpc == 4)
+        return cloud_from_images(ctx, w, h, static_cast<const float *>(image_device_pixels(depth->dev)), nullptr, kTsdfColorNone, intrinsic,
+                                 extrinsic, stride, out);
+    if (int rc = ctx->eng->bind_device()) return ctx->eng_fail(rc);
+    ImageDevice *metres = nullptr;                           // ConvertDepthToFloatImage first, as the reference does
+    const hipError_t e = image_device_depth_to_float(depth->dev, depth_scale, depth_trunc, ctx->eng->aux_stream(), &metres);
+    if (e != hipSuccess) { (void)hipGetLastError(); return ctx->fail(VISMA_ICP_ERR_HIP, hipGetErrorString(e)); }
+    const int rc = cloud_from_images(ctx, w, h, static_cast<const float *>(image_device_pixels(metres)), nullptr, kTsdfColorNone, intrinsic,
+                                     extrinsic, stride, out);
+    image_device_destroy(metres);
+    return rc;
+}
+
+int visma_icp_cloud_from_rgbd_images(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image *color, const double intrinsic[4],
+                                     const double extrinsic[16], visma_icp_cloud **out)
+{
+    CTX_CHECK();
+    if (int rc = cloud_from_images_enter(ctx, depth, color, intrinsic, out)) return rc;
+    if (!color) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL argument");
+    int w, h, ch, bpc, cw, chh, cch, cb;
+    image_device_info(depth->dev, &w, &h, &ch, &bpc);
+    image_device_info(color->dev, &cw, &chh, &cch, &cb);
+    const int color_type = cch == 3 && cb == 1 ? kTsdfColorRgb8 : cch == 1 && cb == 4 ? kTsdfColorGray32 : kTsdfColorNone;
+    if (ch != 1 || bpc != 4 || color_type == kTsdfColorNone || w < 1 || h < 1) return empty_cloud(ctx, out);
+    if (cw != w || chh != h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the colour image differs in size from the depth");
+    return cloud_from_images(ctx, w, h, static_cast<const float *>(image_device_pixels(depth->dev)), image_device_pixels(color->dev), color_type,
+                             intrinsic, extrinsic, 1, out);
 }
 
 int visma_icp_point_cloud_from_depth(visma_icp_ctx *ctx, int w, int h, const float *depth, const double intrinsic[4],

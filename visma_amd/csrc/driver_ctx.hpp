@@ -57,6 +57,16 @@ struct visma_icp_cloud {
     ~visma_icp_cloud() { cloud_device_destroy(dev); }
 };
 
+// an Image of a context, resident on the device (image.hip)
+struct visma_icp_image {
+    visma_icp_ctx *ctx = nullptr;
+    ImageDevice *dev = nullptr;
+    visma_icp_image() = default;
+    visma_icp_image(const visma_icp_image &) = delete;
+    visma_icp_image &operator=(const visma_icp_image &) = delete;
+    ~visma_icp_image() { image_device_destroy(dev); }
+};
+
 // ---- the driver -----------------------------------------------------------------
 struct visma_icp_ctx {
     std::unique_ptr<Engine> eng;
@@ -91,6 +101,39 @@ struct visma_icp_ctx {
     std::vector<std::unique_ptr<visma_icp_kdtree>> trees;   // each frees its own, before the engine goes
     std::vector<std::unique_ptr<visma_icp_trimesh>> meshes;   // likewise
     std::vector<std::unique_ptr<visma_icp_cloud>> clouds;   // likewise
+    std::vector<std::unique_ptr<visma_icp_image>> images;   // likewise
+    // what the two-pass image operations work in: one for all images of the context, made at the first use
+    struct ImageScratchOwner {
+        ImageScratch *p = nullptr;
+        ImageScratchOwner() = default;
+        ImageScratchOwner(const ImageScratchOwner &) = delete;
+        ImageScratchOwner &operator=(const ImageScratchOwner &) = delete;
+        ~ImageScratchOwner() { image_scratch_destroy(p); }
+    } image_scratch_owner;
+    ImageScratch *image_scratch()
+    {
+        if (!image_scratch_owner.p) image_scratch_owner.p = image_scratch_create();
+        return image_scratch_owner.p;
+    }
+    bool owns(const visma_icp_image *img) const
+    {
+        for (const auto &i : images) if (i.get() == img) return true;
+        return false;
+    }
+    visma_icp_cloud *adopt(CloudDevice *dev)
+    {
+        std::unique_ptr<visma_icp_cloud> c(new visma_icp_cloud);
+        c->ctx = this; c->dev = dev;
+        clouds.push_back(std::move(c));
+        return clouds.back().get();
+    }
+    visma_icp_image *adopt(ImageDevice *dev)
+    {
+        std::unique_ptr<visma_icp_image> i(new visma_icp_image);
+        i->ctx = this; i->dev = dev;
+        images.push_back(std::move(i));
+        return images.back().get();
+    }
     Mat4 last_Tc = Mat4::identity();
     bool last_plane = false;
     std::vector<int32_t> src_order;   // engine position -> caller's source index (Morton order)

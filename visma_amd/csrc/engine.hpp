@@ -385,10 +385,17 @@ public:
         double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
         Mat4 init;
         double max_depth_diff = 0.03, min_depth = 0.0, max_depth = 4.0;
+        bool on_device = false;       // the four images lie on this device (resident Images)
     };
     virtual int odometry_prepare(const OdometryInput &) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
     // a level's image (kOdo*: w_l x h_l floats; kOdoSrcXyz: three per pixel)
     virtual int odometry_get_image(int /* which */, int /* level */, float *) { err_ = "not supported by this engine"; return VISMA_ICP_ERR_STATE; }
+    // where a level's single-channel image (which < kOdoSrcXyz) lies ON THE DEVICE, and its size
+    virtual int odometry_image_view(int /* which */, int /* level */, const float **, int * /* w */, int * /* h */)
+    {
+        err_ = "not supported by this engine";
+        return VISMA_ICP_ERR_STATE;
+    }
     // the pairs of a level at T: per source pixel the target pixel or -1 (idx may be NULL), and their number
     virtual int odometry_correspondences(int /* level */, const Mat4 &, int32_t * /* idx */, int64_t * /* K */)
     {
@@ -436,9 +443,10 @@ public:
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;
     }
-    // CreatePointCloudFromDepthImage / FromRGBDImage of one frame: the rows in row-major pixel order (points NULL: count only)
+    // CreatePointCloudFromDepthImage / FromRGBDImage of one frame: the rows in row-major pixel order (points NULL: count only);
+    // cloud != NULL: the rows as a new resident cloud instead (the caller owns it)
     virtual int point_cloud_from_depth(const TsdfFrame &, int /* color_type */, int /* stride */, double * /* points */, double * /* colors */,
-                                       int64_t * /* n */)
+                                       int64_t * /* n */, CloudDevice ** /* cloud */)
     {
         err_ = "not supported by this engine";
         return VISMA_ICP_ERR_STATE;

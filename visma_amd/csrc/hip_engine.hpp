@@ -306,6 +306,7 @@ public:
     // PairScratch.  Independent of the clouds: neither side drops the other.
     int odometry_prepare(const OdometryInput &in) override;
     int odometry_get_image(int which, int level, float *out) override;
+    int odometry_image_view(int which, int level, const float **img, int *w, int *h) override;
     int odometry_correspondences(int level, const Mat4 &T, int32_t *idx, int64_t *K) override;
     int odometry_step(int level, const Mat4 &T, int method, double *stats) override;
     int odometry_information(const Mat4 &T, double *sums) override;
@@ -323,7 +324,7 @@ public:
     int tsdf_get_extract(int id, int voxel_cloud, double *points, double *normals, double *colors) override;
     int tsdf_get_units(int id, std::vector<int32_t> *keys) override;
     int tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *weight, float *color) override;
-    int point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n) override;
+    int point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n, CloudDevice **cloud) override;
 
     // color map optimization (colormap.hip): the objects by id; each owns its device memory, all on the one stream
     int color_map_create(const ColorMapConfig &cfg, int *id) override;

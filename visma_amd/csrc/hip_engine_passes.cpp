@@ -993,7 +993,7 @@ int HipEngine::odometry_prepare(const OdometryInput &in)
     const struct { const float *host; int which; bool depth; } frames[4] = {
         {in.src_gray, kOdoSrcGray, false}, {in.tgt_gray, kOdoTgtGray, false}, {in.src_depth, kOdoSrcDepth, true}, {in.tgt_depth, kOdoTgtDepth, true}};
     for (const auto &f : frames) {
-        HIP_TRY(hipMemcpyAsync(o.tmp[0], f.host, sizeof(float) * n0, hipMemcpyHostToDevice, stream_));
+        HIP_TRY(hipMemcpyAsync(o.tmp[0], f.host, sizeof(float) * n0, in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
         if (f.depth) HIP_TRY(launch_odo_preprocess_depth(o.tmp[0], o.tmp[0], (int64_t)n0, in.min_depth, in.max_depth, stream_));
         HIP_TRY(filter(o.tmp[0], o.img[0][f.which], W, H, kGauss, kGauss));
         HIP_TRY(hipStreamSynchronize(stream_));                  // (the caller's image is pageable memory; tmp[0] is reused)
@@ -1047,6 +1047,16 @@ int HipEngine::odometry_get_image(int which, int level, float *out)
     std::vector<float4> p(n);
     HIP_TRY(hipMemcpy(p.data(), odo_.src_xyz[level], sizeof(float4) * n, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) { out[3 * i] = p[i].x; out[3 * i + 1] = p[i].y; out[3 * i + 2] = p[i].z; }
+    return VISMA_ICP_OK;
+}
+
+int HipEngine::odometry_image_view(int which, int level, const float **img, int *w, int *h)
+{
+    HIP_TRY(hipSetDevice(device_));
+    if (!odo_.ready) { err_ = "no odometry frames: odometry_prepare first"; return VISMA_ICP_ERR_STATE; }
+    HIP_TRY(hipStreamSynchronize(stream_));
+    *img = odo_.img[level][which];
+    *w = odo_.w[level]; *h = odo_.h[level];
     return VISMA_ICP_OK;
 }
 
@@ -1184,7 +1194,7 @@ int HipEngine::tsdf_get_volume(int id, const int32_t *unit, float *tsdf, float *
 }
 
 // the camera pose is the extrinsic's inverse, by cofactors in f64 on the host (what Eigen's fixed-size inverse() evaluates)
-int HipEngine::point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n)
+int HipEngine::point_cloud_from_depth(const TsdfFrame &f, int color_type, int stride, double *points, double *colors, int64_t *n, CloudDevice **cloud)
 {
     int rc = tsdf_enter(0, nullptr);
     if (rc) return rc;
@@ -1193,7 +1203,7 @@ int HipEngine::point_cloud_from_depth(const TsdfFrame &f, int color_type, int st
     const Mat4 I = Mat4::identity();
     for (int i = 0; i < 16; i++) identity = identity && E.m[i] == I.m[i];
     const Mat4 pose = identity ? I : inverse4(E);
-    HIP_TRY(point_cloud_from_depth_device(f, pose.m, color_type, stride, points, colors, n, stream_));
+    HIP_TRY(point_cloud_from_depth_device(f, pose.m, color_type, stride, points, colors, n, stream_, cloud));
     return VISMA_ICP_OK;
 }
 

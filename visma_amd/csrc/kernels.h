@@ -713,7 +713,10 @@ struct TsdfFrame {
     const void *color = nullptr;
     double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
     double extrinsic[16] = {};
+    bool on_device = false;                            // depth and color lie on this device (a resident Image's pixels)
 };
+// out[y * w + x] = sqrtf(xx^2 + yy^2 + 1), xx = ((float)x - (float)cx) * (1.0f / (float)fx): the multiplier image of a frame
+hipError_t launch_tsdf_multiplier(float *out, int w, int h, double fx, double fy, double cx, double cy, hipStream_t stream);
 struct TsdfDevice;                                     // the volume, the last frame and the last extraction on the device
 // allocates the zero-filled volume; nothing is left allocated where it fails
 hipError_t tsdf_device_create(const TsdfConfig &cfg, hipStream_t stream, TsdfDevice **out);
@@ -754,8 +757,11 @@ void tsdf_device_get_units(const TsdfDevice *D, std::vector<int32_t> *keys);
 hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsdf, float *weight, float *color);
 // CreatePointCloudFromDepthImage / FromRGBDImage: pose = extrinsic^-1 (row-major, inverted by the caller in f64);
 // color_type as above.  points / colors: room for ceil(w / stride) * ceil(h / stride) rows, or NULL (count only).
+// cloud != NULL: the rows stay on the device as a new resident cloud (points, colours), nothing is downloaded.
+// f.on_device: depth and color lie on this device
+struct CloudDevice;
 hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
-                                         double *colors, int64_t *n, hipStream_t stream);
+                                         double *colors, int64_t *n, hipStream_t stream, CloudDevice **cloud = nullptr);
 
 // ---- TriangleMesh (trimesh.hip): a mesh resident on the device: normals, Purge, select, crop, Transform ----
 // Every result is the reference's bit for bit (TriangleMesh.cpp, DownSample.cpp); the rules: visma_icp.h.  Each call returns
@@ -811,6 +817,40 @@ hipError_t cloud_device_orient_normals(CloudDevice *P, bool camera, const double
 hipError_t cloud_device_mean_and_covariance(CloudDevice *P, int64_t chunk, double mean[3], double cov[9], hipStream_t stream);
 // inv: the inverse covariance, row-major; out: n doubles on the host
 hipError_t cloud_device_mahalanobis(CloudDevice *P, const double mean[3], const double inv[9], double *out, hipStream_t stream);
+
+// ---- Image (image.hip): an image resident on the device: w x h pixels of ch channels of bpc bytes, row-major ----
+// Every result is the reference's bit for bit but for the stated deviations (Image.cpp, ImageFactory.cpp,
+// RGBDImageFactory.cpp); the rules: visma_icp.h.  Each call returns with the stream idle.  The arguments are checked by the
+// caller (aux_api.cpp).  "The empty image" is the reference's Image(): 0 x 0, no channels.
+struct ImageDevice;
+// on_device: `data` lies on this device and is copied there
+hipError_t image_device_create(int w, int h, int ch, int bpc, const void *data, bool on_device, hipStream_t stream, ImageDevice **out);
+void image_device_destroy(ImageDevice *I);
+void image_device_info(const ImageDevice *I, int *w, int *h, int *ch, int *bpc);
+const void *image_device_pixels(const ImageDevice *I);  // on the device
+hipError_t image_device_get(const ImageDevice *I, void *bytes, hipStream_t stream);
+// new images.  ImageScratch: what the two-pass operations work in, one per context (grow-only)
+struct ImageScratch;
+ImageScratch *image_scratch_create();
+void image_scratch_destroy(ImageScratch *W);
+hipError_t image_device_copy(const ImageDevice *S, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_to_float(const ImageDevice *S, int weighted, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_depth_to_float(const ImageDevice *S, double depth_scale, double depth_trunc, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_from_float(const ImageDevice *S, int bytes, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_filter_horizontal(const ImageDevice *S, ImageScratch *W, const double *kernel, int n, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_filter_separable(const ImageDevice *S, ImageScratch *W, const double *dx, int n_dx, const double *dy, int n_dy, hipStream_t stream,
+                                         ImageDevice **out);
+hipError_t image_device_flip(const ImageDevice *S, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_downsample(const ImageDevice *S, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_dilate(const ImageDevice *S, ImageScratch *W, int half_kernel_size, hipStream_t stream, ImageDevice **out);
+// the SUN (nyu == false) or NYU decoding of a 1 x uint16 depth image
+hipError_t image_device_decode_depth(const ImageDevice *S, bool nyu, hipStream_t stream, ImageDevice **out);
+hipError_t image_device_distance_multiplier(int w, int h, const double intrinsic[4], hipStream_t stream, ImageDevice **out);
+// in place; an unsupported format is left as it is
+hipError_t image_device_linear_transform(ImageDevice *I, double scale, double offset, hipStream_t stream);
+hipError_t image_device_clip_intensity(ImageDevice *I, double lo, double hi, hipStream_t stream);
+// uv: n x 2 doubles on the host; ok, value: n each on the host
+hipError_t image_device_float_value_at(const ImageDevice *I, const double *uv, int64_t n, uint8_t *ok, double *value, hipStream_t stream);
 
 // ---- color map optimization (colormap.hip): frames, vertices, visibility and poses resident on the device ----
 constexpr int kColorMapSums = 29;                      // per camera: 21 upper entries of JJ (row by row), 6 of Jb, rr, count

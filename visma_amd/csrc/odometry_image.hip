@@ -5,14 +5,10 @@
 // launch, not by the memory system, so none of them stages anything in LDS.
 //
 //  preprocess_depth   d < min_depth || d > max_depth || d <= 0 -> quiet NaN
-//  filter3            one pass of a separable 3-tap filter along the rows or down the columns, indices clamped at the
-//                     borders.  The reference filters the rows, transposes, filters the rows again and transposes back;
-//                     the second pass here walks the columns with the same per-tap arithmetic: the fp32 product
-//                     pixel * (float)weight, widened and added into an f64 sum in tap order -1, 0, +1, one cast to fp32.
-//                     Every weight in use (.25, .5; 0, +-1, 2) makes the product exact, and a NaN propagates as it does
-//                     there, 0 * NaN included: the images are the reference's bit for bit.
-//  downsample         (p1 + p2 + p3 + p4) / 4.0f in fp32, in that order; floor(w / 2) x floor(h / 2)
-//  scale              NormalizeIntensity's p = (float)(scale * p + 0.0), scale in f64
+//  filter3, downsample, scale   image_kernels.h, shared with the resident Image (image.hip): the separable filter's pass at
+//                     three taps (rows, then the same arithmetic down the columns), (p1 + p2 + p3 + p4) / 4.0f, and
+//                     NormalizeIntensity's p = (float)(scale * p + 0.0).  Every 3-tap weight in use (.25, .5; 0, +-1, 2) makes
+//                     the fp32 product exact: the images are the reference's bit for bit.
 //  xyz                (float)((x - ox) * z * inv_fx) evaluated in f64; float4 per pixel so that the information pass reads it
 //                     as its target cloud
 //  correspondences    one thread per SOURCE pixel, f64: uv = d_s * (K R K^-1) (u, v, 1) + K t, u_t = (int)(uv.x / uv.z + 0.5)
@@ -21,6 +17,7 @@
 //                     arbitrate, no atomics.  Deviation (visma_icp.h): uv.z <= 0 or a projection that is not finite or
 //                     beyond the int range has no pair -- the reference's cast is undefined there.
 // (Reasoning: DESIGN.md 4.4c10.)
+#include "image_kernels.h"
 #include "kernels.h"
 
 #include <cmath>
@@ -28,9 +25,6 @@
 namespace visma {
 
 namespace {
-
-constexpr int kImgThreads = 256;
-inline unsigned img_blocks(int64_t n) { return (unsigned)((n + kImgThreads - 1) / kImgThreads); }
 
 __global__ __launch_bounds__(kImgThreads) void preprocess_depth_kernel(const float *in, float *out, long long n,
                                                                        double min_depth, double max_depth)
@@ -40,44 +34,6 @@ __global__ __launch_bounds__(kImgThreads) void preprocess_depth_kernel(const flo
     const float p = in[i];
     const bool bad = (double)p < min_depth || (double)p > max_depth || p <= 0.0f;
     out[i] = bad ? __builtin_nanf("") : p;
-}
-
-template <bool VERTICAL>
-__global__ __launch_bounds__(kImgThreads) void filter3_kernel(const float *__restrict__ in, float *__restrict__ out, int w, int h,
-                                                              float k0, float k1, float k2)
-{
-    const long long i = (long long)blockIdx.x * kImgThreads + threadIdx.x;
-    if (i >= (long long)w * h) return;
-    const int y = (int)(i / w), x = (int)(i - (long long)y * w);
-    long long a, c;                                          // the clamped neighbours' positions
-    if (VERTICAL) {
-        a = (long long)(y > 0 ? y - 1 : 0) * w + x;
-        c = (long long)(y < h - 1 ? y + 1 : h - 1) * w + x;
-    } else {
-        a = (long long)y * w + (x > 0 ? x - 1 : 0);
-        c = (long long)y * w + (x < w - 1 ? x + 1 : w - 1);
-    }
-    double t = 0.0;
-    t += (double)(in[a] * k0);
-    t += (double)(in[i] * k1);
-    t += (double)(in[c] * k2);
-    out[i] = (float)t;
-}
-
-__global__ __launch_bounds__(kImgThreads) void downsample_kernel(const float *__restrict__ in, int w, float *__restrict__ out, int ow, int oh)
-{
-    const long long i = (long long)blockIdx.x * kImgThreads + threadIdx.x;
-    if (i >= (long long)ow * oh) return;
-    const int y = (int)(i / ow), x = (int)(i - (long long)y * ow);
-    const float *r0 = in + (long long)(2 * y) * w + 2 * x, *r1 = r0 + w;   // 2x + 1 < w and 2y + 1 < h by ow = w / 2, oh = h / 2
-    out[i] = (r0[0] + r0[1] + r1[0] + r1[1]) / 4.0f;
-}
-
-__global__ __launch_bounds__(kImgThreads) void scale_kernel(float *img, long long n, double scale)
-{
-    const long long i = (long long)blockIdx.x * kImgThreads + threadIdx.x;
-    if (i >= n) return;
-    img[i] = (float)(scale * (double)img[i] + 0.0);
 }
 
 __global__ __launch_bounds__(kImgThreads) void xyz_kernel(const float *__restrict__ depth, int w, int h, double ox, double oy,
@@ -133,26 +89,18 @@ hipError_t launch_odo_preprocess_depth(const float *in, float *out, int64_t n, d
 
 hipError_t launch_odo_filter3(const float *in, float *out, int w, int h, float k0, float k1, float k2, int vertical, hipStream_t stream)
 {
-    if (w <= 0 || h <= 0) return hipSuccess;
-    const dim3 grid(img_blocks((int64_t)w * h)), block(kImgThreads);
-    if (vertical) hipLaunchKernelGGL(filter3_kernel<true>, grid, block, 0, stream, in, out, w, h, k0, k1, k2);
-    else hipLaunchKernelGGL(filter3_kernel<false>, grid, block, 0, stream, in, out, w, h, k0, k1, k2);
-    return hipGetLastError();
+    const float k[3] = {k0, k1, k2};
+    return vertical ? img_launch_filter<true>(in, out, w, h, k, 3, nullptr, stream) : img_launch_filter<false>(in, out, w, h, k, 3, nullptr, stream);
 }
 
 hipError_t launch_odo_downsample(const float *in, int w, int h, float *out, hipStream_t stream)
 {
-    const int ow = w / 2, oh = h / 2;
-    if (ow <= 0 || oh <= 0) return hipSuccess;
-    hipLaunchKernelGGL(downsample_kernel, dim3(img_blocks((int64_t)ow * oh)), dim3(kImgThreads), 0, stream, in, w, out, ow, oh);
-    return hipGetLastError();
+    return img_launch_downsample(in, w, h, out, stream);
 }
 
 hipError_t launch_odo_scale(float *img, int64_t n, double scale, hipStream_t stream)
 {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(scale_kernel, dim3(img_blocks(n)), dim3(kImgThreads), 0, stream, img, (long long)n, scale);
-    return hipGetLastError();
+    return img_launch_linear(img, n, scale, 0.0, stream);
 }
 
 hipError_t launch_odo_xyz(const float *depth, int w, int h, double ox, double oy, double inv_fx, double inv_fy, float4 *out,

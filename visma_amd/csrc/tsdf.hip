@@ -789,18 +789,28 @@ hipError_t tsdf_device_create(const TsdfConfig &cfg, hipStream_t stream, TsdfDev
     return hipSuccess;
 }
 
+// CreateDepthToCameraDistanceMultiplierFloatImage (ImageFactory.cpp): the one copy, for a volume's frames and for
+// visma_icp_image_distance_multiplier
+hipError_t launch_tsdf_multiplier(float *out, int w, int h, double fx, double fy, double cx, double cy, hipStream_t stream)
+{
+    if (w <= 0 || h <= 0) return hipSuccess;
+    multiplier_kernel<<<capped_blocks((long long)w * h), kThreads, 0, stream>>>(out, w, h, (float)cx, (float)cy, 1.0f / (float)fx, 1.0f / (float)fy);
+    return hipGetLastError();
+}
+
 hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double pose[16])
 {
     const TsdfConfig &c = D->cfg;
     const size_t n = (size_t)f.w * f.h;
+    const hipMemcpyKind kind = f.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     DEV_RESERVE(D->depth, n);
-    VISMA_TRY(hipMemcpyAsync(D->depth, f.depth, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+    VISMA_TRY(hipMemcpyAsync(D->depth, f.depth, sizeof(float) * n, kind, D->stream));
     if (c.color_type == kTsdfColorRgb8) {
         DEV_RESERVE(D->rgb, 3 * n);
-        VISMA_TRY(hipMemcpyAsync(D->rgb, f.color, 3 * n, hipMemcpyHostToDevice, D->stream));
+        VISMA_TRY(hipMemcpyAsync(D->rgb, f.color, 3 * n, kind, D->stream));
     } else if (c.color_type == kTsdfColorGray32) {
         DEV_RESERVE(D->gray, n);
-        VISMA_TRY(hipMemcpyAsync(D->gray, f.color, sizeof(float) * n, hipMemcpyHostToDevice, D->stream));
+        VISMA_TRY(hipMemcpyAsync(D->gray, f.color, sizeof(float) * n, kind, D->stream));
     }
     // the units of this frame: the one of a uniform volume, or the touched ones, every one of them open before any kernel
     // of the integration starts
@@ -850,8 +860,7 @@ hipError_t tsdf_device_integrate(TsdfDevice *D, const TsdfFrame &f, const double
     if (!D->mult || D->mult_w != f.w || D->mult_h != f.h || std::memcmp(k, D->mult_k, sizeof(k)) != 0) {
         D->mult_w = 0;
         DEV_RESERVE(D->mult, n);
-        multiplier_kernel<<<capped_blocks((long long)n), kThreads, 0, D->stream>>>(D->mult, f.w, f.h, cx, cy, 1.0f / fx, 1.0f / fy);
-        VISMA_TRY(hipGetLastError());
+        VISMA_TRY(launch_tsdf_multiplier(D->mult, f.w, f.h, f.fx, f.fy, f.cx, f.cy, D->stream));
         D->mult_w = f.w; D->mult_h = f.h;
         std::memcpy(D->mult_k, k, sizeof(k));
     }
@@ -1079,9 +1088,11 @@ hipError_t tsdf_device_get_volume(TsdfDevice *D, const int32_t *unit, float *tsd
 }
 
 hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[16], int color_type, int stride, double *points,
-                                         double *colors, int64_t *n, hipStream_t stream)
+                                         double *colors, int64_t *n, hipStream_t stream, CloudDevice **cloud)
 {
     *n = 0;
+    if (cloud) *cloud = nullptr;
+    const hipMemcpyKind kind = f.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const size_t px = (size_t)f.w * f.h;
     const long long sw = ((long long)f.w - 1) / stride + 1, sh = ((long long)f.h - 1) / stride + 1, items = sw * sh;
     DeviceBuf<float> d_depth, d_gray;
@@ -1090,13 +1101,13 @@ hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[1
     Compactor comp;
     // (a return with work in flight is safe: the buffers' hipFree waits for the device before the caller has its arrays back)
     DEV_RESET(d_depth, px);
-    VISMA_TRY(hipMemcpyAsync(d_depth, f.depth, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+    VISMA_TRY(hipMemcpyAsync(d_depth, f.depth, sizeof(float) * px, kind, stream));
     if (color_type == kTsdfColorRgb8) {
         DEV_RESET(d_rgb, 3 * px);
-        VISMA_TRY(hipMemcpyAsync(d_rgb, f.color, 3 * px, hipMemcpyHostToDevice, stream));
+        VISMA_TRY(hipMemcpyAsync(d_rgb, f.color, 3 * px, kind, stream));
     } else if (color_type == kTsdfColorGray32) {
         DEV_RESET(d_gray, px);
-        VISMA_TRY(hipMemcpyAsync(d_gray, f.color, sizeof(float) * px, hipMemcpyHostToDevice, stream));
+        VISMA_TRY(hipMemcpyAsync(d_gray, f.color, sizeof(float) * px, kind, stream));
     }
     DepthSource s;
     s.depth = d_depth; s.gray = d_gray; s.rgb = d_rgb;
@@ -1107,12 +1118,14 @@ hipError_t point_cloud_from_depth_device(const TsdfFrame &f, const double pose[1
     long long rows = 0;
     VISMA_TRY(compact_count(comp, s, items, stream, &rows));
     *n = (int64_t)rows;
-    if (rows == 0 || !points) return hipSuccess;
+    if (rows == 0 && cloud) return cloud_device_create(nullptr, 0, nullptr, nullptr, true, stream, cloud);
+    if (rows == 0 || (!points && !cloud)) return hipSuccess;
     const size_t bytes = sizeof(double) * 3 * (size_t)rows;
     DEV_RESET(d_points, 3 * (size_t)rows);
     if (color_type != kTsdfColorNone) DEV_RESET(d_colors, 3 * (size_t)rows);
     s.points = d_points; s.colors = d_colors;
     VISMA_TRY(compact_write(comp, s, items, stream));
+    if (cloud) return cloud_device_create(d_points, (int64_t)rows, nullptr, d_colors ? d_colors.get() : nullptr, true, stream, cloud);   // device to device
     VISMA_TRY(hipMemcpyAsync(points, d_points, bytes, hipMemcpyDeviceToHost, stream));
     if (colors && d_colors) VISMA_TRY(hipMemcpyAsync(colors, d_colors, bytes, hipMemcpyDeviceToHost, stream));
     return hipStreamSynchronize(stream);
