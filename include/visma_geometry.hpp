@@ -6,6 +6,7 @@
 //   feh::gpu::MeasureSurfaceError        geometry.h:117-141
 //   feh::gpu::FindPlaneNormal            geometry.h:18-26;  RotationBetweenVectors  core/utils.h:229-233
 //   feh::gpu::AnnotateObjects            the per-object loop of AnnotationTool, src/annotation.cpp:103-168
+//   feh::gpu::Renderer, LinearizeDepth   render/renderer.h:32-36, 41-160 (compute on the device; no OpenGL, no window)
 //
 // Header-only over the C ABI in visma_icp.h; works with either Eigen storage
 // order (VISMA compiles with -DEIGEN_DEFAULT_TO_ROW_MAJOR, CMakeLists.txt:11-12).
@@ -336,6 +337,122 @@ inline std::vector<AnnotationPose> AnnotateObjects(const std::vector<AnnotationO
         throw std::runtime_error(std::string("visma_io_write_alignment_json: ") + visma_io_last_error());
     return out;
 }
+
+// renderer.h:32-36
+template <typename T>
+T LinearizeDepth(T zb, T z_near, T z_far)
+{
+    return (T)visma_icp_linearize_depth((double)zb, (double)z_near, (double)z_far);
+}
+
+// feh::Renderer (render/renderer.h:41-160) with its members and their meaning, over visma_icp_render: the mesh is a
+// TriangleMesh resident on the device, every Render* one call.  What differs (visma_icp.h has the rule and the list): the
+// camera point is pose * model * X in the computer-vision frame (z forward, y down) and row y of an output is image row y
+// -- the OpenGL axis flips are dropped --; samples sit at integer pixel coordinates; RenderDepth delivers the depth-buffer
+// value without its 24-bit quantisation, 1 where nothing is drawn, so LinearizeDepth inverts it; RenderEdge works on the
+// true metric depth; RenderMask is 255 on covered pixels.  The outputs are rows() x cols(), row-major.
+class Renderer {
+public:
+    typedef Eigen::Matrix<float, 4, 4, Eigen::ColMajor> Mat4f;
+    Renderer(int maxHeight, int maxWidth, int = 3, int = 2) : rows_(maxHeight), cols_(maxWidth), name_("Render" + std::to_string(counter()++))
+    {
+        for (int i = 0; i < 16; i++) pose_[i] = i % 5 == 0 ? 1.0 : 0.0;
+    }
+    void SetCamera(float z_near, float z_far, const float *intrinsics)
+    {
+        fx_ = intrinsics[0]; fy_ = intrinsics[1]; cx_ = intrinsics[2]; cy_ = intrinsics[3];
+        z_near_ = z_near; z_far_ = z_far;
+    }
+    void SetCamera(float z_near, float z_far, float fx, float fy, float cx, float cy)
+    {
+        const float k[4] = {fx, fy, cx, cy};
+        SetCamera(z_near, z_far, k);
+    }
+    // pose: from the initial camera frame to the current one
+    void SetCamera(const Mat4f &pose) { for (int i = 0; i < 16; i++) pose_[i] = (double)pose(i / 4, i % 4); }
+    void SetMesh(const float *vertices, int num_vertices, const int *faces, int num_faces)
+    {
+        std::vector<double> v(vertices, vertices + 3 * (size_t)num_vertices);
+        static_assert(sizeof(int) == sizeof(int32_t), "faces are uploaded as they lie");
+        visma_icp_ctx *ctx = detail::ctx();
+        if (mesh_) open3d::cicp::detail::check(ctx, visma_icp_trimesh_destroy(ctx, mesh_), "visma_icp_trimesh_destroy");
+        mesh_ = nullptr;
+        open3d::cicp::detail::check(ctx, visma_icp_trimesh_create(ctx, v.data(), num_vertices, nullptr, nullptr, (const int32_t *)faces, num_faces,
+                                                                  nullptr, &mesh_), "visma_icp_trimesh_create");
+        num_vertices_ = num_vertices; num_faces_ = num_faces;
+    }
+    void SetMesh(const std::vector<float> &vertices, const std::vector<int> &faces)
+    {
+        SetMesh(vertices.data(), (int)(vertices.size() / 3), faces.data(), (int)(faces.size() / 3));
+    }
+    void SetMesh(const Eigen::Matrix<float, Eigen::Dynamic, 3, Eigen::RowMajor> &vertices,
+                 const Eigen::Matrix<int, Eigen::Dynamic, 3, Eigen::RowMajor> &faces)
+    {
+        SetMesh(vertices.data(), (int)vertices.rows(), faces.data(), (int)faces.rows());
+    }
+    ~Renderer() { if (mesh_) (void)visma_icp_trimesh_destroy(detail::ctx(), mesh_); }
+    Renderer(const Renderer &) = delete;
+    Renderer &operator=(const Renderer &) = delete;
+
+    // out: rows() x cols() floats, the depth-buffer value (1 where nothing is drawn)
+    void RenderDepth(const Mat4f &model, float *out) { render(model, VISMA_ICP_RENDER_DEPTH_BUFFER, out, nullptr, nullptr); }
+    void RenderMask(const Mat4f &model, uint8_t *out) { render(model, VISMA_ICP_RENDER_METRIC, nullptr, out, nullptr); }
+    void RenderEdge(const Mat4f &model, uint8_t *out) { render(model, VISMA_ICP_RENDER_METRIC, nullptr, nullptr, out); }
+    void Use() {}
+
+    float fx() const { return fx_; }
+    float fy() const { return fy_; }
+    float cx() const { return cx_; }
+    float cy() const { return cy_; }
+    float z_near() const { return z_near_; }
+    float z_far() const { return z_far_; }
+    int width() const { return cols_; }
+    int cols() const { return cols_; }
+    int height() const { return rows_; }
+    int rows() const { return rows_; }
+    const std::string &id() const { return name_; }
+    const std::string &name() const { return name_; }
+
+private:
+    static int &counter() { static int c = 0; return c; }
+    void render(const Mat4f &model, int encoding, float *depth, uint8_t *mask, uint8_t *edges)
+    {
+        if (!mesh_) throw std::runtime_error("[Renderer] SetMesh first");
+        visma_icp_ctx *ctx = detail::ctx();
+        double E[16];                                        // pose * model, in f64
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++) {
+                double a = 0.0;
+                for (int l = 0; l < 4; l++) a += pose_[4 * i + l] * (double)model(l, j);
+                E[4 * i + j] = a;
+            }
+        const double k[4] = {fx_, fy_, cx_, cy_};
+        visma_icp_image *d = nullptr, *m = nullptr;
+        const int rc = visma_icp_render(ctx, mesh_, cols_, rows_, k, E, z_near_, z_far_, encoding, (depth || edges) ? &d : nullptr, nullptr,
+                                        mask ? &m : nullptr);
+        if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string("[Renderer] ") + visma_icp_last_error(ctx));
+        open3d::cicp::detail::check(ctx, rc, "visma_icp_render");
+        struct Held {                                        // (DeviceImage is not declared under Open3D's own headers)
+            visma_icp_ctx *ctx;
+            visma_icp_image *img;
+            ~Held() { if (img) (void)visma_icp_image_destroy(ctx, img); }
+        } D{ctx, d}, M{ctx, m}, Ed{ctx, nullptr};
+        const int64_t px = (int64_t)rows_ * cols_;
+        if (depth) open3d::cicp::detail::check(ctx, visma_icp_image_get(ctx, d, depth, 4 * px), "visma_icp_image_get");
+        if (mask) open3d::cicp::detail::check(ctx, visma_icp_image_get(ctx, m, mask, px), "visma_icp_image_get");
+        if (edges) {
+            open3d::cicp::detail::check(ctx, visma_icp_render_edges(ctx, d, &Ed.img), "visma_icp_render_edges");
+            open3d::cicp::detail::check(ctx, visma_icp_image_get(ctx, Ed.img, edges, px), "visma_icp_image_get");
+        }
+    }
+    float fx_ = 0, fy_ = 0, cx_ = 0, cy_ = 0, z_near_ = 0, z_far_ = 0;
+    int rows_, cols_;
+    int num_vertices_ = 0, num_faces_ = 0;
+    double pose_[16];                                       // row-major
+    visma_icp_trimesh *mesh_ = nullptr;
+    std::string name_;
+};
+typedef std::shared_ptr<Renderer> RendererPtr;
 
 }  // namespace gpu
 }  // namespace feh

@@ -1934,6 +1934,63 @@ VISMA_ICP_API int visma_icp_cloud_from_depth_image(visma_icp_ctx *ctx, visma_icp
 VISMA_ICP_API int visma_icp_cloud_from_rgbd_images(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image *color,
                                                    const double intrinsic[4], const double extrinsic[16], visma_icp_cloud **out);
 
+/* ---- The mesh renderer: a resident TriangleMesh seen through a pinhole camera, into resident Images ---------------------------
+ * The counterpart of the reference's off-screen OpenGL renderer (render/renderer.h:41-160, renderer.cpp, edge_detection.frag):
+ * a depth image, the visible triangle per pixel, a binary mask and a depth-edge image.  It is compute, not a graphics
+ * pipeline, and its picture is a written rule, the same on the device, in visma_icp_render_host and in tests/render_spec.py:
+ *
+ *   camera       w x h pixels, intrinsic = [fx, fy, cx, cy] in Open3D's pixel convention (the sample of pixel (x, y) is the
+ *                point (x, y): PinholeCameraIntrinsic, the TSDF volume and the odometry); extrinsic: world -> camera, row-major
+ *                4 x 4, z forward and y down (the convention of visma_icp_tsdf_integrate); 0 < z_near < z_far
+ *   vertex       P = R X + t in f64, ((R_i0 x + R_i1 y) + R_i2 z) + t_i as visma_icp_trimesh_transform computes it
+ *   triangle     (a, b, c) with camera points A, B, C: n0 = B x C, n1 = C x A, n2 = A x B (a component is u_y v_z - u_z v_y:
+ *                two products, one difference), det = (A_x n0_x + A_y n0_y) + A_z n0_z.  A triangle with a non-finite camera
+ *                coordinate is not drawn
+ *   pixel        d = ((x - cx) / fx, (y - cy) / fy, 1), e_i = (n_i.x d.x + n_i.y d.y) + n_i.z, s = (e0 + e1) + e2.  Covered
+ *                where s != 0 and all e_i >= 0 or all e_i <= 0 (both windings draw, the comparisons are inclusive);
+ *                z = det / s; kept where z_near <= z <= z_far.  No clipping, no gap along a shared edge (the two triangles
+ *                see exactly negated edge values there), and a function of the inputs alone
+ *   winner       the smallest 64-bit key (bits of (float)z << 32) | triangle index: the nearest after the rounding to fp32,
+ *                the lowest index among equals
+ *   depth        1 x float: (float)z, 0 where nothing is drawn (VISMA_ICP_RENDER_METRIC); or the value of OpenGL's depth
+ *                buffer, (float)(0.5 ((z_far + z_near) - 2 z_near z_far / z) / (z_far - z_near) + 0.5) from the winner's f64
+ *                z, 1 where nothing is drawn (VISMA_ICP_RENDER_DEPTH_BUFFER): what visma_icp_linearize_depth inverts
+ *   index        1 x int32: the winning triangle, -1 where nothing is drawn.  visma_icp_image_info reports 1 channel of 4
+ *                bytes, visma_icp_image_is_int32 tells it from a float image; the operations on float images treat it as
+ *                any format they do not know
+ *   mask         1 x uint8: 255 where something is drawn, else 0
+ *   edges        visma_icp_render_edges of a 1 x float METRIC depth image -> 1 x uint8.  v = depth where depth > 0, else
+ *                -1.  0 for x < 5, x >= w - 5, y < 5, y >= h - 5 and where the centre has v = -1; else delta =
+ *                0.25 (((|W - E| + |S - N|) + |NW - SE|) + |SW - NE|) in f64, c = 0 below 0.05, 1 from 0.10, (delta - 0.05) /
+ *                0.05 between; the pixel is floor(255 c + 0.5)
+ *
+ * Deviations from the reference: samples sit at integer pixel coordinates (SetCamera's frustum samples at (i + 1/2)(w - 1)/w);
+ * the depth buffer is not quantised to 24 bits; edges are taken on the true metric depth (the shader re-linearises with
+ * the planes 0.05 / 2.0 fixed at construction, renderer.cpp:95-96, whatever the camera's are); the mask is 255 on covered
+ * pixels (the reference reads back a colour channel no fragment shader writes); the OpenGL axis flips are dropped; a
+ * triangle index outside [0, nv) is already an error of visma_icp_trimesh_create.
+ *
+ * VISMA_ICP_ERR_INVALID with a message and nothing written: w or h <= 0 or more than 2^30 pixels, fx or fy 0, z_near <= 0,
+ * z_far <= z_near, a non-finite camera parameter or extrinsic entry, an unknown encoding, a mesh or image of another context,
+ * an image that is not 1 x float for render_edges.  depth, index, mask: each may be NULL. */
+enum { VISMA_ICP_RENDER_METRIC = 0, VISMA_ICP_RENDER_DEPTH_BUFFER = 1 };
+VISMA_ICP_API int visma_icp_render(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int w, int h, const double intrinsic[4],
+                                   const double extrinsic[16], double z_near, double z_far, int encoding, visma_icp_image **depth,
+                                   visma_icp_image **index, visma_icp_image **mask);
+VISMA_ICP_API int visma_icp_render_edges(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image **edges);
+/* the same arithmetic on host arrays: no context, no GPU.  vertices nv x 3, triangles nt x 3 (an index outside [0, nv):
+ * VISMA_ICP_ERR_INVALID); depth, index, mask, edges: w x h each, each may be NULL.  edges is taken on the metric depth,
+ * whatever `encoding` is. */
+VISMA_ICP_API int visma_icp_render_host(const double *vertices, int64_t nv, const int32_t *triangles, int64_t nt, int w, int h,
+                                        const double intrinsic[4], const double extrinsic[16], double z_near, double z_far,
+                                        int encoding, float *depth, int32_t *index, uint8_t *mask, uint8_t *edges);
+/* the edge rule alone on a host image (w x h floats, metric) */
+VISMA_ICP_API int visma_icp_render_edges_host(const float *depth, int w, int h, uint8_t *edges);
+/* LinearizeDepth (renderer.h:32-36): 2 z_near z_far / (z_far + z_near - (2 zb - 1)(z_far - z_near)), in f64 */
+VISMA_ICP_API double visma_icp_linearize_depth(double zb, double z_near, double z_far);
+/* *is_int32: 1 for the renderer's index image, 0 for every other image */
+VISMA_ICP_API int visma_icp_image_is_int32(const visma_icp_image *img, int *is_int32);
+
 /* feh::ComputeErrorMetric (include/geometry.h:85-101): out = mean, std, median
  * (sorted[n >> 1]), min, max.  Host only. */
 VISMA_ICP_API int visma_icp_error_metric(const double *errors, int64_t n, double out[5]);

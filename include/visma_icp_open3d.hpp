@@ -2925,6 +2925,40 @@ inline std::tuple<bool, Eigen::Matrix4d, Eigen::Matrix6d> ComputeRGBDOdometry(
     return Out(true, Tm, Im);
 }
 
+// The mesh seen through a pinhole camera (visma_icp_render has the rule): the metric depth (0 where nothing is drawn), or
+// OpenGL's depth-buffer value (1 where nothing is drawn), as a resident 1 x float image: what cloud_from_depth_image,
+// Integrate and ComputeRGBDOdometry of DeviceImages take, so volume -> mesh -> depth -> cloud / volume / odometry runs
+// without a host round trip.  index, mask: where given, the visible triangle (1 x int32, -1) and the mask (1 x uint8)
+inline DeviceImage RenderDepth(const DeviceTriangleMesh &mesh, const PinholeCameraIntrinsic &intrinsic, const Eigen::Matrix4d &extrinsic,
+                               double z_near = 0.05, double z_far = 10.0, bool depth_buffer = false, DeviceImage *index = nullptr,
+                               DeviceImage *mask = nullptr)
+{
+    const Eigen::Matrix3d &K = intrinsic.intrinsic_matrix_;
+    const double k[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
+    double E[16];
+    detail::to_rowmajor(extrinsic, E);
+    visma_icp_ctx *ctx = mesh.context();
+    visma_icp_image *d = nullptr, *i = nullptr, *m = nullptr;
+    const int rc = visma_icp_render(ctx, mesh.handle(), intrinsic.width_, intrinsic.height_, k, E, z_near, z_far,
+                                    depth_buffer ? VISMA_ICP_RENDER_DEPTH_BUFFER : VISMA_ICP_RENDER_METRIC, &d, index ? &i : nullptr,
+                                    mask ? &m : nullptr);
+    if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string("[RenderDepth] ") + visma_icp_last_error(ctx));
+    detail::check(ctx, rc, "visma_icp_render");
+    if (index) *index = DeviceImage(ctx, i);
+    if (mask) *mask = DeviceImage(ctx, m);
+    return DeviceImage(ctx, d);
+}
+
+// the depth-edge image (edge_detection.frag's rule) of a resident metric depth
+inline DeviceImage RenderEdges(const DeviceImage &depth)
+{
+    visma_icp_image *e = nullptr;
+    const int rc = visma_icp_render_edges(depth.Context(), depth.Handle(), &e);
+    if (rc == VISMA_ICP_ERR_INVALID) throw std::invalid_argument(std::string("[RenderEdges] ") + visma_icp_last_error(depth.Context()));
+    detail::check(depth.Context(), rc, "visma_icp_render_edges");
+    return DeviceImage(depth.Context(), e);
+}
+
 }  // namespace cicp
 
 inline void TSDFVolume::Integrate(const cicp::DeviceImage &depth, const cicp::DeviceImage *color, const PinholeCameraIntrinsic &intrinsic,

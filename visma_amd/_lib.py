@@ -340,6 +340,16 @@ class TriMesh:
         T = _f64(T, (16,))
         self.ctx._chk(self.ctx.L.visma_icp_trimesh_transform(self.ctx._h, self._m, _p(T, _dp)))
 
+    def render(self, w, h, intrinsic, extrinsic=None, z_near=0.05, z_far=10.0, encoding="metric"):
+        """The mesh seen by a pinhole camera (visma_icp_render has the rule) -> (depth, index, mask) Images: 1 x float32 depth
+        (0 where nothing is drawn; encoding "depth_buffer": OpenGL's depth-buffer value, 1 where nothing is drawn), 1 x int32
+        visible triangle (-1), 1 x uint8 mask (255 / 0).  intrinsic [fx, fy, cx, cy]; extrinsic world -> camera, 4 x 4."""
+        k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+        d, i, m = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.ctx._chk(self.ctx.L.visma_icp_render(self.ctx._h, self._m, int(w), int(h), _p(k, _dp), _p(E, _dp), float(z_near), float(z_far),
+                                                  _image_enum(encoding, RENDER_ENCODINGS), C.byref(d), C.byref(i), C.byref(m)))
+        return Image(self.ctx, d), Image(self.ctx, i), Image(self.ctx, m)
+
 
 CLOUD_HAS_NORMALS, CLOUD_HAS_COLORS = 1, 2
 
@@ -457,6 +467,8 @@ IMAGE_EQUAL, IMAGE_WEIGHTED = 0, 1
 IMAGE_FILTERS = ("gaussian3", "gaussian5", "gaussian7", "sobel3dx", "sobel3dy")
 RGBD_FORMATS = ("color_and_depth", "redwood", "tum", "sun", "nyu")
 _IMAGE_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.float32}
+RENDER_METRIC, RENDER_DEPTH_BUFFER = 0, 1
+RENDER_ENCODINGS = ("metric", "depth_buffer")
 
 
 def _image_enum(value, names):
@@ -498,10 +510,17 @@ class Image:
         self.ctx._chk(self.ctx.L.visma_icp_image_info(self._i, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def is_int32(self):
+        """True for the renderer's index image: one channel of four bytes that hold int32, not float"""
+        v = C.c_int(0)
+        self.ctx._chk(self.ctx.L.visma_icp_image_is_int32(self._i, C.byref(v)))
+        return bool(v.value)
+
     def get(self):
-        """-> h x w (one channel) or h x w x channels, uint8 / uint16 / float32; the empty Image: 0 x 0 uint8"""
+        """-> h x w (one channel) or h x w x channels, uint8 / uint16 / float32 (int32: the renderer's index image); the empty
+        Image: 0 x 0 uint8"""
         w, h, ch, bpc = self.info()
-        out = np.empty((h, w) if ch <= 1 else (h, w, ch), _IMAGE_DTYPES.get(bpc, np.uint8))
+        out = np.empty((h, w) if ch <= 1 else (h, w, ch), np.int32 if self.is_int32() else _IMAGE_DTYPES.get(bpc, np.uint8))
         self._call("get", out.ctypes.data_as(C.c_void_p) if out.size else None, out.nbytes)
         return out
 
@@ -1103,6 +1122,15 @@ def _bind(L):
         L.visma_icp_image_from_odometry.argtypes = [_vp, _ci, _ci, _out]
         L.visma_icp_cloud_from_depth_image.argtypes = [_vp, _vp, _dp, _dp, _cd, _cd, _ci, _out]
         L.visma_icp_cloud_from_rgbd_images.argtypes = [_vp, _vp, _vp, _dp, _dp, _out]
+    if hasattr(L, "visma_icp_render"):                   # (A/B runs load older builds through VISMA_ICP_LIB)
+        _vp, _out, _ci, _cd, _u8 = C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_double, C.POINTER(C.c_uint8)
+        L.visma_icp_render.argtypes = [_vp, _vp, _ci, _ci, _dp, _dp, _cd, _cd, _ci, _out, _out, _out]
+        L.visma_icp_render_edges.argtypes = [_vp, _vp, _out]
+        L.visma_icp_render_host.argtypes = [_dp, C.c_int64, _ip, C.c_int64, _ci, _ci, _dp, _dp, _cd, _cd, _ci, _fp, _ip, _u8, _u8]
+        L.visma_icp_render_edges_host.argtypes = [_fp, _ci, _ci, _u8]
+        L.visma_icp_linearize_depth.argtypes = [_cd, _cd, _cd]
+        L.visma_icp_linearize_depth.restype = _cd
+        L.visma_icp_image_is_int32.argtypes = [_vp, C.POINTER(_ci)]
     if hasattr(L, "visma_icp_color_map_create"):         # (A/B runs load older builds through VISMA_ICP_LIB)
         _i64, _vp, _u8 = C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_uint8)
         _opt = C.POINTER(CColorMapOption)
@@ -1390,6 +1418,42 @@ def ransac_hypotheses_host(src, tgt, pair_tgt, option=None, seed=0, draws=None, 
     if rc != OK:
         raise IcpError(rc, "ransac_hypotheses_host: bad arguments")
     return verdict[:int(n_trials)].copy(), T[:int(n_trials)].reshape(-1, 4, 4).copy()
+
+
+def render_host(vertices, triangles, w, h, intrinsic, extrinsic=None, z_near=0.05, z_far=10.0, encoding="metric"):
+    """TriMesh.render and Context.render_edges on the host: the same arithmetic, no context, no GPU -> depth (h x w float32),
+    index (int32), mask (uint8), edges (uint8; of the metric depth whatever the encoding).  Bad arguments: IcpError, nothing
+    computed."""
+    v = _f64(vertices, (-1, 3))
+    t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+    k = _f64(intrinsic, (4,)); E = _f64(np.eye(4) if extrinsic is None else extrinsic, (16,))
+    w, h = int(w), int(h)
+    shape = (max(h, 0), max(w, 0))
+    depth, index = np.zeros(shape, np.float32), np.zeros(shape, np.int32)
+    mask, edges = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8)
+    u8 = C.POINTER(C.c_uint8)
+    rc = load().visma_icp_render_host(_p(v, _dp), len(v), _p(t, _ip), len(t), w, h, _p(k, _dp), _p(E, _dp), float(z_near), float(z_far),
+                                      _image_enum(encoding, RENDER_ENCODINGS), _p(depth, _fp), _p(index, _ip), _p(mask, u8), _p(edges, u8))
+    if rc != OK:
+        raise IcpError(rc, "render_host: bad arguments")
+    return depth, index, mask, edges
+
+
+def render_edges_host(depth):
+    """Context.render_edges on a host array (h x w float32, metric) -> h x w uint8"""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    out = np.zeros(d.shape, np.uint8)
+    if d.ndim != 2:
+        raise ValueError("an h x w array")
+    rc = load().visma_icp_render_edges_host(_p(d, _fp), d.shape[1], d.shape[0], _p(out, C.POINTER(C.c_uint8)))
+    if rc != OK:
+        raise IcpError(rc, "render_edges_host: bad arguments")
+    return out
+
+
+def linearize_depth(zb, z_near, z_far):
+    """LinearizeDepth (renderer.h): the metric depth of a depth-buffer value, in f64"""
+    return load().visma_icp_linearize_depth(float(zb), float(z_near), float(z_far))
 
 
 class PoseGraphEdge:
@@ -1998,6 +2062,13 @@ class Context:
         i = C.c_void_p()
         self._chk(self.L.visma_icp_image_create(self._h, w, h, 1 if a.ndim == 2 else a.shape[2], a.dtype.itemsize,
                                                 a.ctypes.data_as(C.c_void_p) if a.size else None, C.byref(i)))
+        return Image(self, i)
+
+    def render_edges(self, image):
+        """The depth-edge image (edge_detection.frag's rule on the metric depth; visma_icp_render has it) of a 1 x float32
+        depth Image -> a 1 x uint8 Image"""
+        i = C.c_void_p()
+        self._chk(self.L.visma_icp_render_edges(self._h, image._i, C.byref(i)))
         return Image(self, i)
 
     def distance_multiplier(self, intrinsic, w, h):

@@ -7,8 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libvisma_icp.so")
-SOURCES = ["kernels.hip", "grid.hip", "grid_coop.hip", "grid_wave.hip", "grid_ring.hip", "icp_loop.hip", "voxel.hip", "order.hip", "nn_grid.hip", "nn_selftest.hip", "kdtree.hip", "normals.hip", "mesh.hip", "cloud_distance.hip", "trim.hip", "robust.hip", "gicp.hip", "information.hip", "odometry_image.hip", "odometry.hip", "tsdf.hip", "trimesh.hip", "cloud.hip", "image.hip", "colormap.hip", "colormap_warp.hip", "color_gradient.hip", "colored.hip", "fpfh.hip", "feature_match.hip", "ransac.hip", "hip_engine.cpp", "hip_engine_clouds.cpp", "hip_engine_passes.cpp", "hip_engine_comm.cpp", "driver.cpp", "aux_api.cpp", "corpus.cpp", "io.cpp"]
-HEADERS = ["kernels.h", "device_common.h", "pair_pass.h", "compact.h", "row_kernels.h", "image_kernels.h", "colormap_device.h", "colormap_solve.hpp", "tsdf_units.h", "mc_table.h", "icp_state.h", "so3.h", "host_math.hpp", "engine.hpp", "hip_engine.hpp", "dev_buf.h", "dev_mem.h", "driver_ctx.hpp", "grid_coop_probe.h", "plane_math.hpp", "bvh_common.h", "nn_list.h", "ransac.hpp", "warm_search.h",
+SOURCES = ["kernels.hip", "grid.hip", "grid_coop.hip", "grid_wave.hip", "grid_ring.hip", "icp_loop.hip", "voxel.hip", "order.hip", "nn_grid.hip", "nn_selftest.hip", "kdtree.hip", "normals.hip", "mesh.hip", "cloud_distance.hip", "trim.hip", "robust.hip", "gicp.hip", "information.hip", "odometry_image.hip", "odometry.hip", "tsdf.hip", "trimesh.hip", "cloud.hip", "image.hip", "render.hip", "colormap.hip", "colormap_warp.hip", "color_gradient.hip", "colored.hip", "fpfh.hip", "feature_match.hip", "ransac.hip", "hip_engine.cpp", "hip_engine_clouds.cpp", "hip_engine_passes.cpp", "hip_engine_comm.cpp", "driver.cpp", "aux_api.cpp", "corpus.cpp", "io.cpp"]
+HEADERS = ["kernels.h", "device_common.h", "pair_pass.h", "compact.h", "row_kernels.h", "image_kernels.h", "colormap_device.h", "colormap_solve.hpp", "tsdf_units.h", "mc_table.h", "icp_state.h", "so3.h", "host_math.hpp", "engine.hpp", "hip_engine.hpp", "dev_buf.h", "dev_mem.h", "driver_ctx.hpp", "grid_coop_probe.h", "plane_math.hpp", "bvh_common.h", "nn_list.h", "ransac.hpp", "render_math.hpp", "warm_search.h",
            os.path.join("..", "..", "include", "visma_icp.h"), os.path.join("..", "..", "include", "visma_icp_testing.h")]
 
 

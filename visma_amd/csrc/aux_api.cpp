@@ -4,6 +4,7 @@
 #include "driver_ctx.hpp"
 #include "plane_math.hpp"
 #include "ransac.hpp"
+#include "render_math.hpp"
 #include "mc_table.h"
 
 extern "C" {
@@ -640,7 +641,7 @@ static bool image_is_float(const visma_icp_image *img)
 {
     int w, h, ch, bpc;
     image_device_info(img->dev, &w, &h, &ch, &bpc);
-    return ch == 1 && bpc == 4;
+    return ch == 1 && bpc == 4 && !image_device_is_integer(img->dev);
 }
 
 int visma_icp_image_create(visma_icp_ctx *ctx, int w, int h, int channels, int bytes_per_channel, const void *data, visma_icp_image **out)
@@ -1891,6 +1892,124 @@ int visma_icp_marching_cubes_case(int cube_case, int32_t *edge_ids, int *n_trian
     if (c.n > visma::kMcMaxTriangles) return VISMA_ICP_ERR_STATE;     // (the rule gave more than the table holds: never)
     *n_triangles = c.n;
     for (int i = 0; i < 3 * c.n; i++) edge_ids[i] = c.edge[i];
+    return VISMA_ICP_OK;
+}
+
+// ---- the mesh renderer (render.hip, render_math.hpp) ----
+static const char *render_check_camera(int w, int h, const double *intrinsic, const double *extrinsic, double z_near, double z_far, int encoding)
+{
+    if (!intrinsic || !extrinsic) return "render: NULL argument";
+    if (w <= 0 || h <= 0 || (int64_t)w * h > (int64_t)1 << 30) return "render: 0 < w, h and at most 2^30 pixels";
+    for (int k = 0; k < 4; k++) if (!std::isfinite(intrinsic[k])) return "render: a non-finite camera parameter";
+    for (int k = 0; k < 16; k++) if (!std::isfinite(extrinsic[k])) return "render: a non-finite extrinsic entry";
+    if (!std::isfinite(z_near) || !std::isfinite(z_far)) return "render: a non-finite camera parameter";
+    if (intrinsic[0] == 0.0 || intrinsic[1] == 0.0) return "render: fx or fy is 0";
+    if (!(z_near > 0.0)) return "render: z_near <= 0";
+    if (!(z_far > z_near)) return "render: z_far <= z_near";
+    if (encoding != VISMA_ICP_RENDER_METRIC && encoding != VISMA_ICP_RENDER_DEPTH_BUFFER) return "render: unknown encoding";
+    return nullptr;
+}
+
+static RenderCamera render_camera(int w, int h, const double *k, double z_near, double z_far)
+{
+    RenderCamera c;
+    c.w = w; c.h = h; c.fx = k[0]; c.fy = k[1]; c.cx = k[2]; c.cy = k[3]; c.z_near = z_near; c.z_far = z_far;
+    return c;
+}
+
+int visma_icp_render(visma_icp_ctx *ctx, visma_icp_trimesh *mesh, int w, int h, const double intrinsic[4], const double extrinsic[16],
+                     double z_near, double z_far, int encoding, visma_icp_image **depth, visma_icp_image **index, visma_icp_image **mask)
+{
+    CTX_CHECK();
+    if (depth) *depth = nullptr;
+    if (index) *index = nullptr;
+    if (mask) *mask = nullptr;
+    if (!mesh) return ctx->fail(VISMA_ICP_ERR_INVALID, "NULL mesh");
+    if (const char *m = render_check_camera(w, h, intrinsic, extrinsic, z_near, z_far, encoding)) return ctx->fail(VISMA_ICP_ERR_INVALID, m);
+    if (int rc = trimesh_enter(ctx, mesh)) return rc;
+    ImageDevice *d = nullptr, *i = nullptr, *k = nullptr;
+    const hipError_t e = render_device_render(ctx->render_scratch(), mesh->dev, render_camera(w, h, intrinsic, z_near, z_far), extrinsic,
+                                              encoding, ctx->eng->aux_stream(), depth ? &d : nullptr, index ? &i : nullptr,
+                                              mask ? &k : nullptr);
+    if (e != hipSuccess) return image_done(ctx, "render", e);
+    if (depth) *depth = ctx->adopt(d);
+    if (index) *index = ctx->adopt(i);
+    if (mask) *mask = ctx->adopt(k);
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_render_edges(visma_icp_ctx *ctx, visma_icp_image *depth, visma_icp_image **out)
+{
+    IMAGE_NEW_CHECK(depth);
+    if (!image_is_float(depth)) return ctx->fail(VISMA_ICP_ERR_INVALID, "render_edges: the depth is a 1 x float image");
+    ImageDevice *dev = nullptr;
+    return image_adopt(ctx, "render_edges", render_device_edges(depth->dev, ctx->eng->aux_stream(), &dev), dev, out);
+}
+
+int visma_icp_render_edges_host(const float *depth, int w, int h, uint8_t *edges)
+{
+    if (!depth || !edges || w <= 0 || h <= 0) { g_create_error = "render_edges_host: bad arguments"; return VISMA_ICP_ERR_INVALID; }
+    parallel_for(h, 16, [&](int64_t y) {
+        for (int x = 0; x < w; x++) edges[y * w + x] = render_edge(depth, w, h, x, (int)y);
+    });
+    return VISMA_ICP_OK;
+}
+
+int visma_icp_render_host(const double *vertices, int64_t nv, const int32_t *triangles, int64_t nt, int w, int h, const double intrinsic[4],
+                          const double extrinsic[16], double z_near, double z_far, int encoding, float *depth, int32_t *index,
+                          uint8_t *mask, uint8_t *edges)
+{
+    if (const char *m = render_check_camera(w, h, intrinsic, extrinsic, z_near, z_far, encoding)) { g_create_error = m; return VISMA_ICP_ERR_INVALID; }
+    if (nv < 0 || nt < 0 || nt > 0x7fffffff || (nv > 0 && !vertices) || (nt > 0 && !triangles)) {
+        g_create_error = "render_host: bad mesh arguments";
+        return VISMA_ICP_ERR_INVALID;
+    }
+    for (int64_t k = 0; k < 3 * nt; k++)
+        if (triangles[k] < 0 || triangles[k] >= nv) { g_create_error = "render_host: an index outside [0, nv)"; return VISMA_ICP_ERR_INVALID; }
+    const RenderCamera c = render_camera(w, h, intrinsic, z_near, z_far);
+    std::vector<double> cam(3 * (size_t)nv);
+    for (int64_t i = 0; i < nv; i++) render_camera_point(extrinsic, vertices + 3 * i, cam.data() + 3 * i);
+    std::vector<RenderTri> tris((size_t)nt);
+    std::vector<unsigned long long> keys((size_t)w * (size_t)h, kRenderNoKey);
+    for (int64_t i = 0; i < nt; i++) {
+        RenderTri &t = tris[(size_t)i];
+        render_setup(cam.data() + 3 * (size_t)triangles[3 * i], cam.data() + 3 * (size_t)triangles[3 * i + 1],
+                     cam.data() + 3 * (size_t)triangles[3 * i + 2], c, t);
+        for (int y = t.y0; y <= t.y1; y++)
+            for (int x = t.x0; x <= t.x1; x++) {
+                const unsigned long long key = render_key(t, c, x, y, (unsigned)i);
+                unsigned long long &at = keys[(size_t)y * (size_t)w + (size_t)x];
+                if (key < at) at = key;
+            }
+    }
+    std::vector<float> metric(edges ? keys.size() : 0);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++) {
+            const size_t p = (size_t)y * (size_t)w + (size_t)x;
+            float d;
+            int32_t idx;
+            uint8_t m;
+            render_resolve(keys[p], tris.data(), c, x, y, encoding, &d, &idx, &m);
+            if (depth) depth[p] = d;
+            if (index) index[p] = idx;
+            if (mask) mask[p] = m;
+            if (edges) {
+                if (encoding != VISMA_ICP_RENDER_METRIC) render_resolve(keys[p], tris.data(), c, x, y, VISMA_ICP_RENDER_METRIC, &d, &idx, &m);
+                metric[p] = d;
+            }
+        }
+    if (edges)
+        for (int y = 0; y < h; y++)
+            for (int x = 0; x < w; x++) edges[(size_t)y * (size_t)w + (size_t)x] = render_edge(metric.data(), w, h, x, y);
+    return VISMA_ICP_OK;
+}
+
+double visma_icp_linearize_depth(double zb, double z_near, double z_far) { return render_linearize_depth(zb, z_near, z_far); }
+
+int visma_icp_image_is_int32(const visma_icp_image *img, int *is_int32)
+{
+    if (!img || !img->dev || !is_int32) { g_create_error = "image is NULL"; return VISMA_ICP_ERR_INVALID; }
+    *is_int32 = image_device_is_integer(img->dev) ? 1 : 0;
     return VISMA_ICP_OK;
 }
 

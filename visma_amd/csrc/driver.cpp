@@ -1736,7 +1736,7 @@ static int odometry_images(visma_icp_ctx *ctx, visma_icp_image *const img[4], co
         if (!ctx->owns(img[k])) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
         int iw, ih, ch, bpc;
         image_device_info(img[k]->dev, &iw, &ih, &ch, &bpc);
-        if (ch != 1 || bpc != 4) return ctx->fail(VISMA_ICP_ERR_INVALID, "an odometry frame is a 1 x float image");
+        if (ch != 1 || bpc != 4 || image_device_is_integer(img[k]->dev)) return ctx->fail(VISMA_ICP_ERR_INVALID, "an odometry frame is a 1 x float image");
         if (k == 0) { *w = iw; *h = ih; }
         else if (iw != *w || ih != *h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the four images differ in size");
         px[k] = static_cast<const float *>(image_device_pixels(img[k]->dev));
@@ -1940,7 +1940,7 @@ int visma_icp_tsdf_integrate_images(visma_icp_ctx *ctx, visma_icp_tsdf *volume, 
     if (!ctx->owns(depth) || (color && !ctx->owns(color))) return ctx->fail(VISMA_ICP_ERR_INVALID, "not an image of this context");
     int w, h, ch, bpc;
     image_device_info(depth->dev, &w, &h, &ch, &bpc);
-    if (ch != 1 || bpc != 4) return ctx->fail(VISMA_ICP_ERR_INVALID, "the depth is a 1 x float image");
+    if (ch != 1 || bpc != 4 || image_device_is_integer(depth->dev)) return ctx->fail(VISMA_ICP_ERR_INVALID, "the depth is a 1 x float image");
     const int ct = volume->cfg.color_type;
     const void *color_px = nullptr;
     if (ct != kTsdfColorNone) {
@@ -2106,7 +2106,7 @@ int visma_icp_cloud_from_depth_image(visma_icp_ctx *ctx, visma_icp_image *depth,
     if (stride < 1) return ctx->fail(VISMA_ICP_ERR_INVALID, "stride < 1");
     int w, h, ch, bpc;
     image_device_info(depth->dev, &w, &h, &ch, &bpc);
-    if (ch != 1 || (bpc != 2 && bpc != 4) || w < 1 || h < 1) return empty_cloud(ctx, out);      // unsupported format: the empty cloud
+    if (ch != 1 || (bpc != 2 && bpc != 4) || image_device_is_integer(depth->dev) || w < 1 || h < 1) return empty_cloud(ctx, out);      // unsupported format: the empty cloud
     if (bpc == 4)
         return cloud_from_images(ctx, w, h, static_cast<const float *>(image_device_pixels(depth->dev)), nullptr, kTsdfColorNone, intrinsic,
                                  extrinsic, stride, out);
@@ -2130,7 +2130,7 @@ int visma_icp_cloud_from_rgbd_images(visma_icp_ctx *ctx, visma_icp_image *depth,
     image_device_info(depth->dev, &w, &h, &ch, &bpc);
     image_device_info(color->dev, &cw, &chh, &cch, &cb);
     const int color_type = cch == 3 && cb == 1 ? kTsdfColorRgb8 : cch == 1 && cb == 4 ? kTsdfColorGray32 : kTsdfColorNone;
-    if (ch != 1 || bpc != 4 || color_type == kTsdfColorNone || w < 1 || h < 1) return empty_cloud(ctx, out);
+    if (ch != 1 || bpc != 4 || image_device_is_integer(depth->dev) || color_type == kTsdfColorNone || w < 1 || h < 1) return empty_cloud(ctx, out);
     if (cw != w || chh != h) return ctx->fail(VISMA_ICP_ERR_INVALID, "the colour image differs in size from the depth");
     return cloud_from_images(ctx, w, h, static_cast<const float *>(image_device_pixels(depth->dev)), image_device_pixels(color->dev), color_type,
                              intrinsic, extrinsic, 1, out);

@@ -115,6 +115,19 @@ struct visma_icp_ctx {
         if (!image_scratch_owner.p) image_scratch_owner.p = image_scratch_create();
         return image_scratch_owner.p;
     }
+    // what a render works in: one for all renders of the context, made at the first use
+    struct RenderScratchOwner {
+        RenderScratch *p = nullptr;
+        RenderScratchOwner() = default;
+        RenderScratchOwner(const RenderScratchOwner &) = delete;
+        RenderScratchOwner &operator=(const RenderScratchOwner &) = delete;
+        ~RenderScratchOwner() { render_scratch_destroy(p); }
+    } render_scratch_owner;
+    RenderScratch *render_scratch()
+    {
+        if (!render_scratch_owner.p) render_scratch_owner.p = render_scratch_create();
+        return render_scratch_owner.p;
+    }
     bool owns(const visma_icp_image *img) const
     {
         for (const auto &i : images) if (i.get() == img) return true;

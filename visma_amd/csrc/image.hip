@@ -173,10 +173,11 @@ __global__ __launch_bounds__(kImgThreads) void im_nyu(const uint16_t *__restrict
 
 struct ImageDevice {
     int w = 0, h = 0, ch = 0, bpc = 0;                      // an image without pixels keeps its format (PrepareImage(0, 0, 1, 4))
+    bool integer = false;                                    // 1 x 4 bytes holding int32 (the renderer's index image), not float
     DeviceBuf<uint8_t> px;
     size_t pixels() const { return (size_t)w * (size_t)h; }
     size_t bytes() const { return pixels() * (size_t)ch * (size_t)bpc; }
-    bool is_float() const { return ch == 1 && bpc == 4; }
+    bool is_float() const { return ch == 1 && bpc == 4 && !integer; }
     float *f() const { return reinterpret_cast<float *>(px.get()); }
 };
 
@@ -238,6 +239,18 @@ void image_device_destroy(ImageDevice *I) { delete I; }
 void image_device_info(const ImageDevice *I, int *w, int *h, int *ch, int *bpc) { *w = I->w; *h = I->h; *ch = I->ch; *bpc = I->bpc; }
 
 const void *image_device_pixels(const ImageDevice *I) { return I->px.get(); }
+void *image_device_pixels_rw(ImageDevice *I) { return I->px.get(); }
+bool image_device_is_integer(const ImageDevice *I) { return I->integer; }
+
+hipError_t image_device_alloc(int w, int h, int ch, int bpc, bool integer, ImageDevice **out)
+{
+    *out = nullptr;
+    std::unique_ptr<ImageDevice> O;
+    VISMA_TRY(make_image(w, h, ch, bpc, O));
+    O->integer = integer;
+    *out = O.release();
+    return hipSuccess;
+}
 
 hipError_t image_device_create(int w, int h, int ch, int bpc, const void *data, bool on_device, hipStream_t stream, ImageDevice **out)
 {
@@ -257,7 +270,9 @@ hipError_t image_device_get(const ImageDevice *I, void *bytes, hipStream_t strea
 
 hipError_t image_device_copy(const ImageDevice *S, hipStream_t stream, ImageDevice **out)
 {
-    return image_device_create(S->w, S->h, S->ch, S->bpc, S->px.get(), true, stream, out);
+    VISMA_TRY(image_device_create(S->w, S->h, S->ch, S->bpc, S->px.get(), true, stream, out));
+    (*out)->integer = S->integer;
+    return hipSuccess;
 }
 
 // ImageFactory.cpp:64-120

@@ -786,6 +786,8 @@ hipError_t trimesh_device_purge(TriMeshDevice *M, int64_t removed[4], hipStream_
 hipError_t trimesh_device_select(TriMeshDevice *S, const int64_t *indices, int64_t n, hipStream_t stream, TriMeshDevice **out);
 hipError_t trimesh_device_crop(TriMeshDevice *S, const double lo[3], const double hi[3], hipStream_t stream, TriMeshDevice **out);
 hipError_t trimesh_device_transform(TriMeshDevice *M, const double T[16], hipStream_t stream);
+// the vertices and triangles on the device, for a reader on the same stream (render.hip)
+void trimesh_device_arrays(const TriMeshDevice *M, int64_t *nv, int64_t *nt, const double **v, const int **tri);
 
 // ---- PointCloud (cloud.hip): a cloud resident on the device: points and, optionally, normals and colours, n x 3 f64 ----
 // Every result is the reference's bit for bit but for the stated deviations (PointCloud.cpp, DownSample.cpp,
@@ -829,6 +831,11 @@ void image_device_destroy(ImageDevice *I);
 void image_device_info(const ImageDevice *I, int *w, int *h, int *ch, int *bpc);
 const void *image_device_pixels(const ImageDevice *I);  // on the device
 hipError_t image_device_get(const ImageDevice *I, void *bytes, hipStream_t stream);
+// a new image with uninitialised pixels for a kernel of another file to fill (render.hip).  integer: 1 x 4 bytes that hold
+// int32, which no operation on float images accepts
+hipError_t image_device_alloc(int w, int h, int ch, int bpc, bool integer, ImageDevice **out);
+void *image_device_pixels_rw(ImageDevice *I);
+bool image_device_is_integer(const ImageDevice *I);
 // new images.  ImageScratch: what the two-pass operations work in, one per context (grow-only)
 struct ImageScratch;
 ImageScratch *image_scratch_create();
@@ -851,6 +858,18 @@ hipError_t image_device_linear_transform(ImageDevice *I, double scale, double of
 hipError_t image_device_clip_intensity(ImageDevice *I, double lo, double hi, hipStream_t stream);
 // uv: n x 2 doubles on the host; ok, value: n each on the host
 hipError_t image_device_float_value_at(const ImageDevice *I, const double *uv, int64_t n, uint8_t *ok, double *value, hipStream_t stream);
+
+// ---- the mesh renderer (render.hip): a resident TriangleMesh into resident depth, index, mask and edge Images ----
+// The rule is render_math.hpp's (visma_icp.h states it); visma_icp_render_host runs the same functions on the host.
+struct RenderCamera;
+struct RenderScratch;                                  // what a render works in, one per context (grow-only)
+RenderScratch *render_scratch_create();
+void render_scratch_destroy(RenderScratch *W);
+// E: world -> camera, row-major 4 x 4 (the fourth row is not read).  depth, index, mask: each may be NULL
+hipError_t render_device_render(RenderScratch *W, const TriMeshDevice *M, const RenderCamera &c, const double E[16], int encoding,
+                                hipStream_t stream, ImageDevice **depth, ImageDevice **index, ImageDevice **mask);
+// depth: 1 x float
+hipError_t render_device_edges(const ImageDevice *depth, hipStream_t stream, ImageDevice **out);
 
 // ---- color map optimization (colormap.hip): frames, vertices, visibility and poses resident on the device ----
 constexpr int kColorMapSums = 29;                      // per camera: 21 upper entries of JJ (row by row), 6 of Jb, rr, count

@@ -485,6 +485,11 @@ void trimesh_device_size(const TriMeshDevice *M, int64_t *nv, int64_t *nt, int *
     *flags = (M->has_vn ? kTriMeshVertexNormals : 0) | (M->has_vc ? kTriMeshVertexColors : 0) | (M->has_tn ? kTriMeshTriangleNormals : 0);
 }
 
+void trimesh_device_arrays(const TriMeshDevice *M, int64_t *nv, int64_t *nt, const double **v, const int **tri)
+{
+    *nv = M->nv; *nt = M->nt; *v = M->v.get(); *tri = M->tri.get();
+}
+
 hipError_t trimesh_device_get(TriMeshDevice *M, double *v, double *vn, double *vc, int32_t *tri, double *tn, hipStream_t stream)
 {
     const size_t vb = sizeof(double) * 3 * (size_t)M->nv, tb = sizeof(double) * 3 * (size_t)M->nt;
