@@ -1946,8 +1946,18 @@ VISMA_ICP_API int visma_icp_cloud_from_rgbd_images(visma_icp_ctx *ctx, visma_icp
  *   triangle     (a, b, c) with camera points A, B, C: n0 = B x C, n1 = C x A, n2 = A x B (a component is u_y v_z - u_z v_y:
  *                two products, one difference), det = (A_x n0_x + A_y n0_y) + A_z n0_z.  A triangle with a non-finite camera
  *                coordinate is not drawn
- *   pixel        d = ((x - cx) / fx, (y - cy) / fy, 1), e_i = (n_i.x d.x + n_i.y d.y) + n_i.z, s = (e0 + e1) + e2.  Covered
- *                where s != 0 and all e_i >= 0 or all e_i <= 0 (both windings draw, the comparisons are inclusive);
+ *   box          the pixels a triangle is tested at, part of the rule and not an optimisation.  With k the number of its
+ *                vertices at z >= z_near: nothing for k = 0; the whole image for k = 1 or 2; for k = 3 the projections
+ *                u = fx (X / Z) + cx, v = fy (Y / Z) + cy of the three vertices, columns floor(min u) - 1 .. ceil(max u) + 1
+ *                and rows likewise, clamped to the image (a non-finite min or max: the whole span; wholly off the image:
+ *                nothing).  In exact arithmetic the box contains every pixel the triangle covers.  In f64 the edge values
+ *                of a degenerate triangle are rounding noise and z = det / s is noise over noise, which can fall inside
+ *                [z_near, z_far] anywhere: without the box, a triangle with its vertices on a line through the camera
+ *                centre drew 114 pixels of a 32 x 24 image (exact arithmetic: 0), 215 of 1000 random ones of that family
+ *                drew outside their box, and 1078 of 3000 scenes with every vertex a few ulps under z_near drew pixels
+ *                (exact arithmetic: none)
+ *   pixel        (of the box) d = ((x - cx) / fx, (y - cy) / fy, 1), e_i = (n_i.x d.x + n_i.y d.y) + n_i.z, s = (e0 + e1) + e2.
+ *                Covered where s != 0 and all e_i >= 0 or all e_i <= 0 (both windings draw, the comparisons are inclusive);
  *                z = det / s; kept where z_near <= z <= z_far.  No clipping, no gap along a shared edge (the two triangles
  *                see exactly negated edge values there), and a function of the inputs alone
  *   winner       the smallest 64-bit key (bits of (float)z << 32) | triangle index: the nearest after the rounding to fp32,

@@ -1,5 +1,7 @@
 """The mesh renderer on the GPU (visma_icp_render, visma_icp_render_edges; render.hip) against visma_icp_render_host, which
-tests/test_render_host.py pins to the written rule: every case of tests/render_cases.py bit for bit; a mesh extracted device
+tests/test_render_host.py pins to the written rule: every case of tests/render_cases.py bit for bit, the cull scenes and the
+scenes of the large path (several items per triangle, three compaction tiles) among them; half a million triangles for the
+grid strides, the scan's carry and the tile loops; the edge kernel on uploaded hostile images; a mesh extracted device
 to device from a TSDF volume rendered at its frame's pose, the depth Image handed on to cloud_from_depth_image and to
 TsdfVolume.integrate; two runs and a pose folded into the mesh byte for byte; wrong arguments and wrong-context objects
 refused."""
@@ -7,6 +9,7 @@ import numpy as np
 import pytest
 
 import render_cases as cases
+import render_spec as S
 import tsdf_scene
 
 INVALID = 1
@@ -52,6 +55,48 @@ def same(got, want):
 def test_render_equals_render_host(lib, ctx, name):
     c = cases.CASES[name]
     same(device(ctx, c), cases.host(lib, c))
+
+
+@pytest.mark.gpu
+def test_the_strides_the_scan_carry_and_the_tile_loops(lib, ctx):
+    """2048 x 256 + 300 triangles at 97 x 67 (render_cases.stride), against render_host; the numpy rule would take minutes.
+    Every pass over triangles launches at most 2048 blocks of 256 and strides: rn_setup and rn_cover_small take a second
+    trip, count_kernel and write_kernel a second tile per block (2050 tiles), and the scan carries across its chunks of 1024
+    tiles twice.  Nearly all triangles lie behind the camera; of the 200 others, large (two items each) and small ones sit
+    beyond triangle 2048 x 256, and large ones in tiles beyond 1024, where their item rows depend on the carry
+    (tests/test_render_host.py asserts that the host sees them).  NOT reached, here or anywhere: rn_cover_large's own cap of
+    2^20 blocks.  A second trip of its item loop needs more than 2^20 items, which is four billion box pixels; no test of a
+    few seconds can walk them."""
+    c, large, small = cases.stride()
+    want = cases.stride_host(lib)
+    seen = np.unique(want[1][want[1] >= 0])
+    assert seen.max() > cases.STRIDE and (np.isin(seen, large) & (seen // cases.TILE > 1024)).any()
+    same(device(ctx, c), want)
+
+
+@pytest.mark.gpu
+def test_render_edges_of_uploaded_images(lib, ctx):
+    """rn_edges on images no render produces, against the written rule: NaN, infinities, negatives, -0.0 and a denormal as
+    centres and as neighbours; no interior (w or h <= 10), one interior pixel, rows across blocks of 256 pixels."""
+    def on_device(d):
+        with ctx.image(d) as img, ctx.render_edges(img) as e:
+            assert e.info() == (d.shape[1], d.shape[0], 1, 1)
+            return e.get()
+
+    d = cases.hostile_depth()
+    want = S.edges(d)
+    assert want.any() and (want[5:7, 5:11] == 0).any()
+    got = on_device(d)
+    assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
+    for w, h in cases.EDGE_SHAPES:
+        d = cases.stepped_depth(w, h, 5)
+        want = S.edges(d)
+        assert d.shape == (h, w)
+        assert want.any() == (w > 10 and h > 10), (w, h)
+        if (w, h) == (11, 11):
+            assert want[5, 5] == 255 and want.sum() == 255
+        got = on_device(d)
+        assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), (w, h)
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 // The arithmetic is render_math.hpp's, shared with visma_icp_render_host: f64, unfused, one written order.
 //
 //   rn_vertices     P = R X + t per vertex into a camera-space scratch
-//   rn_setup        per triangle: the three edge normals, det and the screen box that bounds the search
+//   rn_setup        per triangle: the three edge normals, det and the screen box it is drawn in
 //   rn_cover_small  one lane per triangle whose box has at most kSmallArea pixels (a fused TSDF mesh: hundreds of
 //                   thousands of triangles of about a pixel each), the box walked by that lane
 //   rn_cover_large  the other triangles, cut into chunks of kChunk box pixels through ONE ordered compaction (compact.h:

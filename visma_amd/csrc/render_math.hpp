@@ -4,8 +4,8 @@
 //
 // The rule is rasterisation in its ray form (homogeneous edge functions): a pixel's ray d = ((x - cx)/fx, (y - cy)/fy, 1)
 // meets the plane of the camera-space triangle (A, B, C) at depth z = det / s, inside the triangle where the three edge
-// values e_i = n_i . d have one sign.  Nothing is projected and nothing is clipped: a vertex behind the camera is like any
-// other.  The cross products are written so that B x A is exactly -(A x B): two triangles that share an edge see exactly
+// values e_i = n_i . d have one sign.  Nothing is clipped: a vertex behind the camera is like any other.  Vertices are
+// projected only for the triangle's screen box (render_setup), which is part of the rule.  The cross products are written so that B x A is exactly -(A x B): two triangles that share an edge see exactly
 // negated edge values there, so with the inclusive comparison no pixel between them is lost (and one on the edge is in both:
 // the key decides).
 //
@@ -30,7 +30,7 @@ struct RenderCamera {
 constexpr unsigned long long kRenderNoKey = ~0ull;       // background: above every key (z is never a NaN in a key)
 constexpr int kRenderMetric = 0, kRenderDepthBuffer = 1;  // visma_icp.h's VISMA_ICP_RENDER_*
 
-// a triangle after set-up: the three edge normals, det, and the screen box that bounds the search (x1 < x0: nothing to do)
+// a triangle after set-up: the three edge normals, det, and the screen box it is drawn in (x1 < x0: nothing to do)
 struct RenderTri {
     double n0[3], n1[3], n2[3], det;
     int x0, y0, x1, y1;
@@ -62,9 +62,17 @@ VISMA_HD bool render_span(double lo, double hi, int last, int *a, int *b)
     return true;
 }
 
-// Set-up of one triangle.  The box is a search bound only, never what decides a pixel: the projected vertices where all
-// three lie at z >= z_near, the whole image where the triangle straddles that plane, nothing where it lies wholly behind it
-// (the depth of a covered pixel lies between the vertices' depths) or has a non-finite camera coordinate.
+// Set-up of one triangle.  The box is PART OF THE RULE: a triangle is drawn only at the pixels of its box, and tests/render_spec.py
+// computes the same box.  Nothing where a camera coordinate is not finite or no vertex lies at z >= z_near (the depth of a
+// covered pixel lies between the vertices' depths); the whole image where one or two vertices lie at z >= z_near (the
+// triangle straddles that plane); where all three do, the projected vertices u = fx (X / Z) + cx, v = fy (Y / Z) + cy, from
+// floor(min) - 1 to ceil(max) + 1, clamped to the image (a non-finite projection: the whole span; a box wholly off the image:
+// nothing).  In exact arithmetic the box changes no pixel, it contains every pixel the triangle covers.  In f64 it does: the
+// edge values of a degenerate triangle are rounding noise, and z = det / s is noise over noise that can land inside
+// [z_near, z_far] anywhere on the image.  Measured against exact rationals (tests/test_render_spec.py): a triangle whose
+// vertices lie on a line through the camera centre drew 114 pixels of a 32 x 24 image without the box and 0 in exact
+// arithmetic; of 1000 random triangles of that family 215 drew pixels outside their box; of 3000 scenes with every vertex a
+// few ulps under z_near, 1078 drew pixels without the cull (det / s rounds up to z_near) and none in exact arithmetic.
 VISMA_HD void render_setup(const double *A, const double *B, const double *C, const RenderCamera &c, RenderTri &t)
 {
     t.x0 = t.y0 = 0; t.x1 = t.y1 = -1;
